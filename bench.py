@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: PUSCH receive hot path on synthetic 100 MHz n78 slots (273 PRB, 30 kHz SCS).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...). Everything else the
+benchmark measures or checks runs only with --full: the parity check against the oracle, per-kernel times and rooflines, the
+single-slot latency and its HIP-graph replay, the extra legs, the PCIe-inclusive rates and the CPU baselines of the reference.
+--dump-outputs DIR writes what the last timed step computed (transport blocks, result records, codeblock CRC flags, HARQ soft
+buffers; float32 / float64 .npy, seeded samples of the large arrays) so that two builds can be compared output for output.
 
 N > 1 without a launcher: this script starts `python -m torch.distributed.run --nproc-per-node N` on itself as a CHILD process
 before anything touches the GPU, one rank per GPU over RCCL (when the machine has fewer than N GPUs every rank shares cuda:0 over
@@ -14,7 +20,7 @@ codeblocks (BG1, Z=384) per slot, TBS = 319 784 information bits per slot. The s
 region, by the transmit side of the same library on the device (SCH encoder, modulator, DM-RS mapper, OFDM modulator) plus AWGN,
 and are resident in HBM before timing starts.
 
-`value` = LDPC information bits / s over the whole step (all ranks). Extra keys: per-kernel HIP-event times and
+`value` = LDPC information bits / s over the whole step (all ranks). Extra keys of --full: per-kernel HIP-event times and
 algorithmic GB/s, `roofline` of the dominant kernel, `roofline_valu` (the decoder is a VALU kernel), `cpu_baseline` (the
 reference's own receive chain on all host cores; `cpu_baseline_t1`, `cpu_baseline_decoder_only`), `pcie_inclusive`, the other
 codeblock configurations (`legs`: 16QAM R=658, BG1 Z=384 R=1/3, polar AL 1-16) and, with --ingest scatter, `ingest_scatter` (one ingest
@@ -61,11 +67,15 @@ def parse_args():
     ap.add_argument("--no-latency", action="store_true", help="skip the single-slot latency leg (keeps profiles to the timed step only)")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra legs (other MCS / rates, polar, PCIe-inclusive)")
     ap.add_argument("--ingest", choices=["local", "scatter"], default="local",
-                    help="scatter: add the separately timed single-ingest leg (rank 0 scatters the LLR slabs over RCCL, results all-gathered); "
+                    help="scatter (with --full): add the separately timed single-ingest leg (rank 0 scatters the LLR slabs over RCCL, results all-gathered); "
                          "local (default): every rank owns its slots, no collective in the data path")
     ap.add_argument("--ingest-slots", type=int, default=128, help="slots per rank in the scatter leg")
     ap.add_argument("--ldpc-force", type=int, default=0, help="A-B knob of tools/ab_bench.py: miphy_debug_force_ldpc_kernel mode (0 = automatic)")
     ap.add_argument("--extra-multi", action="store_true", help="run the extra GPU legs on rank 0 of a multi-GPU job as well (default: single GPU only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: oracle parity, per-kernel times and rooflines, single-slot latency, extra legs, "
+                         "PCIe-inclusive rates, CPU baselines (--no-cpu / --no-latency / --no-extra leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -414,6 +424,32 @@ def load_stamped(name):
     return j, stamp
 
 
+DUMP_TB_SLOTS = 128            # transport blocks dumped whole (seeded choice of slots): 128 x 39 973 B as float32 = 20 MB
+DUMP_SOFT_SAMPLES = 1 << 21    # seeded positions of the HARQ soft buffers: 8 MB as float32
+
+
+def dump_outputs(d, torch, miphy, tb_d, res_d, crc_d, soft_d, S, C, tb_bytes):
+    """What a caller of the timed path receives after the last step, as .npy files (under 64 MB in all at the default size):
+    transport blocks of a seeded sample of slots, per-slot checksums over every byte of every transport block, the result records,
+    the codeblock CRC flags and a seeded sample of the HARQ soft buffers the decoder leaves for retransmissions."""
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(20231)
+    dev = tb_d.device
+    slots = np.sort(rng.choice(S, min(S, DUMP_TB_SLOTS), replace=False))
+    tb = tb_d.reshape(S, tb_bytes)
+    np.save(os.path.join(d, "transport_block_slots.npy"), slots.astype(np.float64))
+    np.save(os.path.join(d, "transport_blocks.npy"), tb[torch.from_numpy(slots).to(dev)].to(torch.float32).cpu().numpy())
+    tb64 = tb.to(torch.float64)
+    weights = torch.arange(1, tb_bytes + 1, dtype=torch.float64, device=dev)
+    np.save(os.path.join(d, "transport_block_checksums.npy"),  # exact in float64: < 2^53
+            torch.stack([tb64.sum(dim=1), (tb64 * weights).sum(dim=1)], dim=1).cpu().numpy())
+    res = res_d.cpu().numpy().view(miphy.PuschResult)
+    np.save(os.path.join(d, "pusch_results.npy"), np.stack([res[f].astype(np.float64) for f in miphy.PuschResult.names], axis=1))
+    np.save(os.path.join(d, "codeblock_crc_ok.npy"), crc_d[:S * C].reshape(S, C).to(torch.float32).cpu().numpy())
+    pos = np.sort(rng.choice(soft_d.numel(), min(soft_d.numel(), DUMP_SOFT_SAMPLES), replace=False))
+    np.save(os.path.join(d, "harq_soft_buffer_sample.npy"), soft_d[torch.from_numpy(pos).to(dev)].to(torch.float32).cpu().numpy())
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -441,8 +477,6 @@ def main():
     dev = torch.device("cuda", local_rank)
 
     import miphy
-    import oracle_lib as O
-    from miphy import shard
     ctx = miphy.Context(local_rank)
     if args.ldpc_force:
         miphy.lib().miphy_debug_force_ldpc_kernel(args.ldpc_force)
@@ -500,7 +534,8 @@ def main():
                 td[i] = (w["bg"], w["rv"], w["mod"], w["nof_layers"], 1, early_stop, args.max_iter, w["Nref"], w["nsym"], tb_bytes, s * C, s * G,
                          s * tb_bytes)
             p = ctx.pusch_decode_plan(td)
-            p.enable_timing(max(64, args.steps + 8))
+            if args.full:  # the library's own events around the back-end stages (per-kernel times)
+                p.enable_timing(max(64, args.steps + 8))
             plans.append(p)
         return plans
 
@@ -567,14 +602,15 @@ def main():
     for _ in range(args.warmup):
         step(False)
     torch.cuda.synchronize()
-    for p in plans:
-        p.read_timing()  # drop the warm-up samples
+    if args.full:
+        for p in plans:
+            p.read_timing()  # drop the warm-up samples
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(True)
+        step(args.full)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -589,6 +625,68 @@ def main():
         dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
         dt = float(t.item())
         per_rank_ms = {"min": float(tmin.item()) / args.steps * 1e3, "max": dt / args.steps * 1e3, "this_rank": dt_rank / args.steps * 1e3}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, miphy, tb_d, res_d, crc_d, soft_d, S, C, tb_bytes)
+    total_slots = S * args.steps * world
+    value = total_slots * w["tbs"] / dt
+    out = {
+        "metric": "LDPC info-bits/sec + OFDM slots/sec, 100 MHz n78 273-PRB grid",
+        "value": value,
+        "unit": "info_bits/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int8",
+        "data": "synthetic",
+        "config": {"workload": "273-PRB 30kHz PUSCH, 256QAM R=948/1024, 1 layer, 38 CB/slot BG1 Z=384, TBS 319784; per slot, time-domain "
+                               "samples to transport block: OFDM demod (4096-pt, 1 port) + DM-RS channel estimate + equalise/soft-demap/descramble + "
+                               "rate-dematch + LDPC decode (%d it, early_stop=%d) + TB assembly/CRC24A; slots synthesised by the transmit chain + AWGN"
+                               % (args.max_iter, args.early_stop),
+                   "slots_per_gpu_per_step": S, "codeblocks_per_step": S * C * world, "snr_db": args.snr_db,
+                   "parallelism": "slots sharded across GPUs, no data-path collective"},
+        "slots_per_s": total_slots / dt,
+        "kernel_source_sha": kernel_source_sha(),
+    }
+    if per_rank_ms:
+        out["per_rank_ms"] = per_rank_ms
+    if world > 1:
+        out["collective_backend"] = {"name": "gloo (rehearsal)" if rehearsal else "rccl (torch.distributed nccl backend)", "world_size_seen": dist.get_world_size(),
+                                     "use": "barrier + MAX/MIN of the elapsed time" + (" + MIN of the parity verdict" if args.full else "") + "; no collective in the data path"}
+    if rehearsal:
+        out["rehearsal_shared_gpu"] = True
+        out["config"]["parallelism"] += " (REHEARSAL: all ranks share one GPU over gloo; not a scaling measurement)"
+    parity_all_ranks, legs_ok = True, True
+    ok_slots = checked = all_ok = None
+    if args.full:
+        parity_all_ranks, ok_slots, checked, all_ok, legs_ok = full_report(
+            args, out, ctx, miphy, torch, dist, dev, rank, world, rehearsal, w, S, C, N, K, G, tb_bytes, dec_in_len, grids_tx, tbs_u, slot_src,
+            stream, ocfg, slot_samples, ofdm_args, ojobs_d, cjobs_d, djobs_d, samples_d, grid_d, ce_d, sc_d, llr_d, soft_d, msgs_d, crc_d, tb_d,
+            res_d, nsc, rb_words, front, back, stages, ev, G_ch, bounds, plans, make_plans, step, dt)
+    if world > 1:
+        dist.barrier()  # the other ranks wait here while rank 0 runs the CPU baseline legs (after the timed region)
+    if rank == 0:
+        print(json.dumps(out))
+    if not parity_all_ranks or not legs_ok:
+        print("PARITY FAILURE in bench (rank %d: %d of %d slots identical to the oracle, all transport blocks ok: %s, legs ok: %s)" % (rank, ok_slots, checked, all_ok, legs_ok),
+              file=sys.stderr)
+        sys.exit(3)
+    for p in plans:
+        p.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_report(args, out, ctx, miphy, torch, dist, dev, rank, world, rehearsal, w, S, C, N, K, G, tb_bytes, dec_in_len, grids_tx, tbs_u, slot_src,
+                stream, ocfg, slot_samples, ofdm_args, ojobs_d, cjobs_d, djobs_d, samples_d, grid_d, ce_d, sc_d, llr_d, soft_d, msgs_d, crc_d, tb_d,
+                res_d, nsc, rb_words, front, back, stages, ev, G_ch, bounds, plans, make_plans, step, dt):
+    """--full: everything after the timed steps that is not the headline. Adds its keys to `out`; returns (parity of all ranks,
+    slots identical to the oracle, slots checked, all transport blocks ok, extra legs ok)."""
+    import oracle_lib as O
+    from miphy import shard
     back_ms = {k: 0.0 for k in back}
     for p in plans:
         tm = p.read_timing()
@@ -667,8 +765,6 @@ def main():
     # ---- per-launch durations (HIP events on the launching stream); a step has G_ch launches of each kernel
     kernel_ms = {k: float(np.mean([a.elapsed_time(b) for a, b in ev[k]])) * G_ch for k in front}
     kernel_ms.update(back_ms)
-    total_slots = S * args.steps * world
-    value = total_slots * w["tbs"] / dt
     # Algorithmic bytes per launch: decode = LLRs in + K/8 out + 4 B iterations per codeblock; dematch = E in + N
     # out per codeblock; OFDM demod = 61440*8 in + 14*3276*8 out per slot-port; estimator = DM-RS REs in (n_dmrs * 13104 B) +
     # 14*3276*8 out per (slot, port, layer); demodulator = 16 B in + mod B out per data RE and port; TB assembly = K/8 per codeblock in
@@ -710,26 +806,7 @@ def main():
         if mix:
             valu["measured_issue_cost_cycles"] = mix
             valu["frac_of_measured_issue_rate"] = ach / (NOF_SIMDS * CLOCK_GHZ / mix)
-    out = {
-        "metric": "LDPC info-bits/sec + OFDM slots/sec, 100 MHz n78 273-PRB grid",
-        "value": value,
-        "unit": "info_bits/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int8",
-        "data": "synthetic",
-        "config": {"workload": "273-PRB 30kHz PUSCH, 256QAM R=948/1024, 1 layer, 38 CB/slot BG1 Z=384, TBS 319784; per slot, time-domain "
-                               "samples to transport block: OFDM demod (4096-pt, 1 port) + DM-RS channel estimate + equalise/soft-demap/descramble + "
-                               "rate-dematch + LDPC decode (%d it, early_stop=%d) + TB assembly/CRC24A; slots synthesised by the transmit chain + AWGN"
-                               % (args.max_iter, args.early_stop),
-                   "slots_per_gpu_per_step": S, "codeblocks_per_step": S * C * world, "snr_db": args.snr_db,
-                   "parallelism": "slots sharded across GPUs, no data-path collective"},
-        "slots_per_s": total_slots / dt,
+    out.update({
         "kernel_ms": kernel_ms,
         "kernel_algorithmic_GBps": gbs,
         "ofdm_slots_per_s": S * world / (kernel_ms["ofdm_demod"] * 1e-3),
@@ -741,8 +818,7 @@ def main():
         "parity_check": "%d/%d slots: LLRs, codeblocks and CRC verdict identical to the oracle; all %d transport blocks of the last step CRC-ok and equal to the "
                         "transmitted ones: %s" % (ok_slots, checked, S, all_ok),
         "transport_blocks_recovered": nof_tb_good,
-        "kernel_source_sha": kernel_source_sha(),
-    }
+    })
     # Roofline of the dominant kernel. The decoder is bound by VALU issue, not by HBM (SQ counters, roofline_valu): with current counters the
     # line says so and carries the issue-rate figure; the HBM figure of the contract (algorithmic bytes / launch time against 8 TB/s) stays
     # beside it as hbm_frac. Without counters of this build only the HBM figure is known.
@@ -758,15 +834,7 @@ def main():
             roof["note"] = ("no SQ counters of this kernel build under profiles/ (tools/profile_round.sh collects them): achieved / peak / frac are the HBM "
                             "figures, although the kernel is bound by VALU issue")
     out["roofline"] = roof
-    if per_rank_ms:
-        out["per_rank_ms"] = per_rank_ms
-    if world > 1:
-        out["collective_backend"] = {"name": "gloo (rehearsal)" if rehearsal else "rccl (torch.distributed nccl backend)", "world_size_seen": dist.get_world_size(),
-                                     "use": "barrier + MAX/MIN of the elapsed time + MIN of the parity verdict; no collective in the data path"}
     out["parity_all_ranks"] = parity_all_ranks
-    if rehearsal:
-        out["rehearsal_shared_gpu"] = True
-        out["config"]["parallelism"] += " (REHEARSAL: all ranks share one GPU over gloo; not a scaling measurement)"
 
     # ---- single-ingest leg ("RCCL only for the batch scatter/gather"): rank 0 holds the codeword LLRs of world x S_in
     # slots, scatters them (grouped point-to-point sends, one per xGMI peer), every rank runs rate-dematch + LDPC decode + TB assembly
@@ -977,18 +1045,7 @@ def main():
 
     if rank == 0 and world == 1 and not args.no_latency:
         out["single_slot_latency_hip_graph_us"] = graph_latency()
-    if world > 1:
-        dist.barrier()  # the other ranks wait here while rank 0 runs the CPU baseline legs (after the timed region)
-    if rank == 0:
-        print(json.dumps(out))
-    if not parity_all_ranks or not legs_ok:
-        print("PARITY FAILURE in bench (rank %d: %d of %d slots identical to the oracle, all transport blocks ok: %s, legs ok: %s)" % (rank, ok_slots, checked, all_ok, legs_ok),
-              file=sys.stderr)
-        sys.exit(3)
-    for p in plans:
-        p.close()
-    if world > 1:
-        dist.destroy_process_group()
+    return parity_all_ranks, ok_slots, checked, all_ok, legs_ok
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """A/B of kernel variants on the bench workload. Each variant is the in-tree library with ONE translation unit recompiled with extra
 -D flags (debug switches that exist only under those macros), linked into tools/_ab/<name>/libmiphy.so; `run` then executes
-`bench.py --no-cpu --no-extra --no-latency` once per variant (child processes, MIPHY_LIBRARY) and prints the per-kernel times.
+`bench.py --full --no-cpu --no-extra --no-latency` once per variant (child processes, MIPHY_LIBRARY) and prints the per-kernel times.
   python tools/ab_bench.py build name=file.hip:-DA=1,-DB ...      (here or on the GPU box; hipcc cross-compiles)
   python tools/ab_bench.py run [name ...] [-- extra bench flags]
 tools/_ab/ is git-ignored but travels to the GPU box."""
@@ -32,7 +32,7 @@ def run(names, extra):
         env = dict(os.environ)
         if name != "(in-tree)":
             env["MIPHY_LIBRARY"] = os.path.join(AB, name, "libmiphy.so")
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--no-extra", "--no-latency"] + extra, env=env, capture_output=True, text=True)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu", "--no-extra", "--no-latency"] + extra, env=env, capture_output=True, text=True)
         try:
             j = json.loads(r.stdout.strip().splitlines()[-1])
             print("%-18s %7.2f Gbit/s  %6.3f ms/step  %s  parity: %s" % (name, j["value"] / 1e9, j["ms_per_step"], {k: round(v, 4) for k, v in j["kernel_ms"].items()},

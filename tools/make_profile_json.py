@@ -35,7 +35,7 @@ def main():
         if k in STAGE and c == "FETCH_SIZE" and (k, "WRITE_SIZE") in w:
             wr = w[(k, "WRITE_SIZE")][1]
             kern[STAGE[k]] = {"kernel": k, "fetch_kib": v, "write_kib": wr, "hbm_bytes_per_launch": (2 * v + wr) * 1024.0}
-    json.dump({"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE in two separate passes over `python3 bench.py --steps 3 --warmup 1 "
+    json.dump({"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE in two separate passes over `python3 bench.py --full --steps 3 --warmup 1 "
                          "--no-cpu --no-latency --no-extra` (tools/profile_round.sh); bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024",
                "git_commit": commit, "kernel_source_sha": sha, "slots_per_gpu_per_step": slots, "kernels": kern},
               open(os.path.join(d, "%s_traffic.json" % rnd), "w"), indent=1)

@@ -11,7 +11,7 @@ mix=${3:-}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 o=gpurun_out/prof_$tag
 mkdir -p $o
-B="python3 bench.py --no-cpu --no-latency --no-extra"
+B="python3 bench.py --full --no-cpu --no-latency --no-extra"
 rocprofv3 --kernel-trace --stats -d $o/kt -o kt --output-format csv -- $B --steps 20 --warmup 3 > $o/bench.json 2> $o/bench.err
 cp $o/kt/kt_kernel_stats.csv $o/kernel_stats.csv
 echo "kernel-trace done" 
