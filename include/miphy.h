@@ -659,7 +659,7 @@ typedef struct {
 } miphy_pusch_uci;
 
 /* _ex: PDUs with multiplexed UCI and the EVM. `uci`: NULL or n entries (host). The soft bits of the UCI fields go to `uci_llr_out`
- * (device; decoding them stays with the caller: uci_decoder is not on this path), `evm_out` (device, n floats, may be NULL) receives
+ * (device; miphy_pusch_uci_field_jobs + miphy_uci_decode_batch enqueued behind this call on the same stream decode them there), `evm_out` (device, n floats, may be NULL) receives
  * the error vector magnitude of every PDU (pusch_demodulator::demodulation_status::evm). PDUs without codeword are demodulated and
  * demultiplexed only; their result record is zero. */
 int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus /* host */, const miphy_pusch_uci* uci /* host or NULL */, uint32_t n,
@@ -707,6 +707,37 @@ int miphy_ulsch_demux_sizes(const miphy_ulsch_demux_job* job, uint32_t* nof_in_l
 int miphy_ulsch_placeholders(const miphy_ulsch_demux_job* job, uint16_t* re_indices, uint32_t cap, uint32_t* n);
 int miphy_ulsch_demultiplex_batch(miphy_ctx* ctx, const miphy_ulsch_demux_job* jobs /* host */, uint32_t n, const int8_t* llr_in /* device */,
                                   int8_t* sch_out, int8_t* harq_ack_out, int8_t* csi_part1_out, int8_t* csi_part2_out /* device */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * UCI decoder (short-block detector)  --  replaces srsran::uci_decoder::decode / srsran::short_block_detector::detect
+ *   include/srsran/phy/upper/channel_processors/uci_decoder.h:38-56, lib/phy/upper/channel_processors/uci_decoder_impl.cpp:41-50,
+ *   lib/phy/upper/channel_coding/short/short_block_detector_impl.cpp:58-199 (TS 38.212 5.3.3 / 5.4.3)
+ * One job = one UCI field of 1 to 11 bits (the reference decodes no longer field): rate dematch of its nof_llr soft bits with the
+ * saturating LLR sum, ML detection over the codewords of the short block code and the GLRT verdict, bit-exact with the reference.
+ * `payload` receives nof_bits bytes per job (one bit per byte, like span<uint8_t> in the reference), `status[i]` the
+ * srsran::uci_status of job i (include/srsran/phy/upper/channel_processors/uci_status.h:28-41): MIPHY_UCI_STATUS_VALID or _INVALID.
+ * Host jobs are checked first (MIPHY_EINVAL, nothing enqueued: nof_bits outside 1..11, mod not 1/2/4/6/8, and the reference's
+ * preconditions nof_llr > nof_bits for 3..11 bits, nof_llr >= mod for 1 bit, nof_llr >= 3 mod for 2 bits); a device job that fails
+ * them is skipped (its payload and status are not written). n == 0 enqueues nothing. */
+enum { MIPHY_UCI_STATUS_UNKNOWN = 0, MIPHY_UCI_STATUS_VALID = 1, MIPHY_UCI_STATUS_INVALID = 2 };
+typedef struct {
+  uint8_t  nof_bits;       /* K: 1..11 */
+  uint8_t  mod;            /* bits per symbol of the modulation the field was sent with (uci_decoder::configuration::modulation) */
+  uint16_t reserved;
+  uint32_t nof_llr;        /* E: soft bits of the field */
+  uint64_t llr_offset;     /* int8 offset of the field's soft bits inside `llr` (any alignment) */
+  uint64_t payload_offset; /* byte offset of the field's nof_bits payload bytes inside `payload` */
+} miphy_uci_field_job;
+
+int miphy_uci_decode_batch(miphy_ctx* ctx, const miphy_uci_field_job* jobs, int jobs_on_device, uint32_t n, const int8_t* llr /* device */,
+                           uint8_t* payload /* device */, uint8_t* status /* device, n */, void* stream);
+/* Host: the field jobs of n PUSCH PDUs over the `uci_llr_out` layout miphy_pusch_process_batch_ex writes: one job per present field
+ * (nof_*_bits != 0), PDU after PDU in the order HARQ-ACK, CSI part 1, CSI part 2, payloads packed from byte 0 in job order. `jobs`
+ * holds up to 3 n entries; job_field (NULL or as many entries) receives 3 * pdu + field (0 HARQ-ACK, 1 CSI part 1, 2 CSI part 2) per
+ * job, *nof_jobs the count. MIPHY_EINVAL for a field above 11 bits or one the detector refuses. With these jobs, _ex and
+ * miphy_uci_decode_batch go on one stream without a host synchronisation in between. */
+int miphy_pusch_uci_field_jobs(const miphy_pusch_pdu* pdus, const miphy_pusch_uci* uci, uint32_t n, miphy_uci_field_job* jobs, uint32_t* job_field,
+                               uint32_t* nof_jobs);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * PDSCH encoder (whole transport blocks)  --  replaces srsran::pdsch_encoder::encode

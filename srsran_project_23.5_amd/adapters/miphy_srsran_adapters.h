@@ -962,6 +962,49 @@ private:
   std::vector<srsran::cf_t> host, ce_host;
 };
 
+// ---------------------------------------------------------------------------------------------------------------- UCI decoder
+/// srsran::short_block_detector over miphy_uci_decode_batch (short_block_detector.h:38-50), a batch of one: the soft bits go to the
+/// device, the payload bits and the verdict come back. Invalid spans are fatal, as the reference's asserts are.
+class short_block_detector_hip : public srsran::short_block_detector
+{
+public:
+  explicit short_block_detector_hip(std::shared_ptr<context> c) : c(std::move(c)) {}
+  bool detect(srsran::span<uint8_t> output, srsran::span<const srsran::log_likelihood_ratio> input, srsran::modulation_scheme mod) override
+  {
+    miphy_uci_field_job j = {};
+    j.nof_bits = static_cast<uint8_t>(std::min<size_t>(output.size(), 255)), j.mod = static_cast<uint8_t>(srsran::get_bits_per_symbol(mod));
+    j.nof_llr = static_cast<uint32_t>(input.size()), j.llr_offset = 0, j.payload_offset = 0;
+    auto* d = static_cast<uint8_t*>(c->buf(5, 64 + input.size())); // [0,16) payload, [16] status, [64,..) soft bits
+    c->h2d(d + 64, input.data(), input.size());
+    context::check(miphy_uci_decode_batch(c->ctx, &j, 0, 1, reinterpret_cast<const int8_t*>(d + 64), d, d + 16, c->stream), "uci_decode");
+    uint8_t h[17];
+    c->d2h(h, d, sizeof(h));
+    c->sync();
+    std::copy(h, h + output.size(), output.begin());
+    return h[16] == MIPHY_UCI_STATUS_VALID;
+  }
+
+private:
+  std::shared_ptr<context> c;
+};
+
+/// srsran::uci_decoder on the device (uci_decoder_impl.cpp:41-50: every field the reference accepts, 1 to 11 bits, is a short block).
+/// pusch_processor_hip recognises it and decodes the UCI fields of a PDU where the demultiplexer left them, in the same submission.
+class uci_decoder_hip : public srsran::uci_decoder
+{
+public:
+  explicit uci_decoder_hip(std::shared_ptr<context> c) : detector(std::move(c)) {}
+  srsran::uci_status
+  decode(srsran::span<uint8_t> message, srsran::span<const srsran::log_likelihood_ratio> llr, const configuration& config) override
+  {
+    require(message.size() <= 11, "UCI message lengths above 11 bits are not currently supported.");
+    return detector.detect(message, llr, config.modulation) ? srsran::uci_status::valid : srsran::uci_status::invalid;
+  }
+
+private:
+  short_block_detector_hip detector;
+};
+
 // ---------------------------------------------------------------------------------------------------------------- PUSCH processor
 /// srsran::pusch_processor over miphy_pusch_process_batch (pusch_processor.h:158-162): estimation, demodulation and decoding in one
 /// device pass for PDUs that carry a codeword and no UCI; the resource grid goes to the device once, the transport block, the
@@ -969,8 +1012,8 @@ private:
 class pusch_processor_hip : public srsran::pusch_processor
 {
 public:
-  /// \c uci_dec: the reference's UCI decoder (short block / polar decoding of the demultiplexed soft bits stays a CPU block);
-  /// without it PDUs with multiplexed UCI are refused. \c enable_evm as in create_pusch_demodulator_factory_sw.
+  /// \c uci_dec: uci_decoder_hip (the fields are decoded on the device behind the demultiplexer) or the reference's CPU UCI decoder
+  /// (the soft bits come back and are decoded on the host); without it PDUs with multiplexed UCI are refused. \c enable_evm as in create_pusch_demodulator_factory_sw.
   pusch_processor_hip(std::shared_ptr<context> c, unsigned nof_iterations, bool early_stop, std::unique_ptr<srsran::uci_decoder> uci_dec_ = nullptr,
                       bool enable_evm_ = false) :
     c(std::move(c)), dec_nof_iterations(nof_iterations), dec_enable_early_stop(early_stop), uci_dec(std::move(uci_dec_)), enable_evm(enable_evm_)
@@ -1073,10 +1116,24 @@ public:
     c->h2d(d_tb, data.data(), data.size());
     context::check(miphy_pusch_process_batch_ex(c->ctx, &p, &u, 1, d_g, d_soft, d_msg, d_crc, d_tb, d_res, d_sc, d_uci, enable_evm ? d_evm : nullptr, c->stream),
                    "pusch_process");
+    // With the device UCI decoder the fields are decoded behind _ex on the same stream: only payload bits and verdicts come back.
+    const bool           uci_on_device = has_uci && dynamic_cast<uci_decoder_hip*>(uci_dec.get()) != nullptr;
+    miphy_uci_field_job  uci_jobs[3];
+    uint32_t             uci_field[3] = {}, nof_uci_jobs = 0;
+    std::array<uint8_t, 3 * 16 + 3> uci_out = {}; // [16 f, 16 f + 11) payload of field f, [48 + j] status of job j
+    if (uci_on_device) {
+      context::check(miphy_pusch_uci_field_jobs(&p, &u, 1, uci_jobs, uci_field, &nof_uci_jobs), "pusch_uci_field_jobs");
+      for (uint32_t j = 0; j != nof_uci_jobs; ++j) {
+        uci_jobs[j].payload_offset = 16 * uci_field[j];
+      }
+      auto* d_uci_out = static_cast<uint8_t*>(c->buf(5, 64));
+      context::check(miphy_uci_decode_batch(c->ctx, uci_jobs, 0, nof_uci_jobs, d_uci, d_uci_out, d_uci_out + 48, c->stream), "uci_decode");
+      c->d2h(uci_out.data(), d_uci_out, uci_out.size());
+    }
     miphy_pusch_result r;
     float              sc[20], evm = 0.F;
-    uci_llr.resize(nof_uci_llr);
-    if (nof_uci_llr) {
+    uci_llr.resize(uci_on_device ? 0 : nof_uci_llr);
+    if (nof_uci_llr && !uci_on_device) {
       c->d2h(uci_llr.data(), d_uci, nof_uci_llr);
     }
     if (enable_evm) {
@@ -1123,7 +1180,7 @@ public:
       if (enable_evm) {
         ru.evm.emplace(evm);
       }
-      auto field = [&](size_t off, unsigned G, unsigned nof_bits) {
+      auto field = [&](unsigned k, size_t off, unsigned G, unsigned nof_bits) {
         srsran::pusch_uci_field f;
         if (nof_bits == 0) {
           f.payload.clear();
@@ -1131,12 +1188,18 @@ public:
           return f;
         }
         f.payload.resize(nof_bits);
+        if (uci_on_device) {
+          const uint32_t j = static_cast<uint32_t>(std::find(uci_field, uci_field + nof_uci_jobs, k) - uci_field);
+          std::copy(uci_out.begin() + 16 * k, uci_out.begin() + 16 * k + nof_bits, f.payload.begin());
+          f.status = uci_out[48 + j] == MIPHY_UCI_STATUS_VALID ? srsran::uci_status::valid : srsran::uci_status::invalid;
+          return f;
+        }
         f.status = uci_dec->decode(f.payload, srsran::span<const srsran::log_likelihood_ratio>(uci_llr.data() + off, G), ucfg);
         return f;
       };
-      ru.harq_ack  = field(u.harq_ack_offset, u.nof_enc_harq_ack_bits, pdu.uci.nof_harq_ack);
-      ru.csi_part1 = field(u.csi_part1_offset, u.nof_enc_csi_part1_bits, pdu.uci.nof_csi_part1);
-      ru.csi_part2 = field(u.csi_part2_offset, u.nof_enc_csi_part2_bits, pdu.uci.nof_csi_part2);
+      ru.harq_ack  = field(0, u.harq_ack_offset, u.nof_enc_harq_ack_bits, pdu.uci.nof_harq_ack);
+      ru.csi_part1 = field(1, u.csi_part1_offset, u.nof_enc_csi_part1_bits, pdu.uci.nof_csi_part1);
+      ru.csi_part2 = field(2, u.csi_part2_offset, u.nof_enc_csi_part2_bits, pdu.uci.nof_csi_part2);
       notifier.on_uci(ru);
     }
     if (!pdu.codeword.has_value()) {
@@ -2352,6 +2415,8 @@ MIPHY_SIMPLE_FACTORY(pdcch_encoder_factory_hip, pdcch_encoder_factory, pdcch_enc
 MIPHY_SIMPLE_FACTORY(pusch_demodulator_factory_hip, pusch_demodulator_factory, pusch_demodulator, pusch_demodulator_hip)
 MIPHY_SIMPLE_FACTORY(pdsch_modulator_factory_hip, pdsch_modulator_factory, pdsch_modulator, pdsch_modulator_hip)
 MIPHY_SIMPLE_FACTORY(dmrs_pdsch_processor_factory_hip, dmrs_pdsch_processor_factory, dmrs_pdsch_processor, dmrs_pdsch_processor_hip)
+MIPHY_SIMPLE_FACTORY(short_block_detector_factory_hip, short_block_detector_factory, short_block_detector, short_block_detector_hip)
+MIPHY_SIMPLE_FACTORY(uci_decoder_factory_hip, uci_decoder_factory, uci_decoder, uci_decoder_hip)
 #undef MIPHY_SIMPLE_FACTORY
 
 /// The string-selected factory functions of the reference (channel_coding_factories.cpp:86-180) gain a "hip" case that
@@ -2402,6 +2467,16 @@ inline std::shared_ptr<srsran::dmrs_pdsch_processor_factory> create_dmrs_pdsch_p
 inline std::shared_ptr<srsran::pusch_demodulator_factory> create_pusch_demodulator_factory_hip(std::shared_ptr<context> c)
 {
   return std::make_shared<pusch_demodulator_factory_hip>(std::move(c));
+}
+/// Replace create_short_block_detector_factory_sw() and create_uci_decoder_factory_sw(config) (channel_coding_factories.h:123-130,
+/// channel_processor_factories.h:303-314); pass the UCI decoder factory to pusch_processor_factory_hip / uplink_processor_hip.
+inline std::shared_ptr<srsran::short_block_detector_factory> create_short_block_detector_factory_hip(std::shared_ptr<context> c)
+{
+  return std::make_shared<short_block_detector_factory_hip>(std::move(c));
+}
+inline std::shared_ptr<srsran::uci_decoder_factory> create_uci_decoder_factory_hip(std::shared_ptr<context> c)
+{
+  return std::make_shared<uci_decoder_factory_hip>(std::move(c));
 }
 
 /// OFDM factories take a configuration per product (modulation_factories.h:34-76).

@@ -116,6 +116,8 @@ def lib():
             getattr(l, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         l.miphy_ofdm_symbol_size.argtypes = [C.c_void_p, C.c_uint32]
         l.miphy_ofdm_symbol_size.restype = C.c_uint32
+        l.miphy_uci_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
+        l.miphy_pusch_uci_field_jobs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
         _lib = l
     return _lib
 
@@ -260,6 +262,26 @@ PuschUci = np.dtype([("nof_harq_ack_bits", np.uint32), ("nof_csi_part1_bits", np
                      ("nof_harq_ack_rvd", np.uint32), ("has_codeword", np.uint32), ("harq_ack_offset", np.uint64), ("csi_part1_offset", np.uint64),
                      ("csi_part2_offset", np.uint64)], align=True)
 assert PuschUci.itemsize == 56
+
+# Mirrors miphy_uci_field_job; MIPHY_UCI_STATUS_* (srsran::uci_status).
+UciFieldJob = np.dtype([("nof_bits", np.uint8), ("mod", np.uint8), ("reserved", np.uint16), ("nof_llr", np.uint32), ("llr_offset", np.uint64),
+                        ("payload_offset", np.uint64)], align=True)
+assert UciFieldJob.itemsize == 24
+UCI_STATUS_UNKNOWN, UCI_STATUS_VALID, UCI_STATUS_INVALID = 0, 1, 2
+
+
+def pusch_uci_field_jobs(pdus, uci):
+    """UciFieldJob records of the present UCI fields of PuschPdu / PuschUci arrays over the uci_llr_out layout of pusch_process_batch_ex
+    (host function). Returns (jobs, job_field) with job_field = 3 * pdu + field (0 HARQ-ACK, 1 CSI part 1, 2 CSI part 2)."""
+    assert isinstance(pdus, np.ndarray) and pdus.dtype == PuschPdu and isinstance(uci, np.ndarray) and uci.dtype == PuschUci
+    assert pdus.size == uci.size
+    pdus, uci = np.ascontiguousarray(pdus), np.ascontiguousarray(uci)
+    jobs = np.zeros(max(1, 3 * pdus.size), UciFieldJob)
+    field = np.zeros(jobs.size, np.uint32)
+    cnt = C.c_uint32()
+    check(lib().miphy_pusch_uci_field_jobs(C.c_void_p(pdus.ctypes.data), C.c_void_p(uci.ctypes.data), pdus.size, C.c_void_p(jobs.ctypes.data),
+                                           C.c_void_p(field.ctypes.data), C.byref(cnt)))
+    return jobs[:cnt.value].copy(), field[:cnt.value].copy()
 
 
 class PolarCode(C.Structure):
@@ -586,6 +608,14 @@ class Context:
                                                  _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars),
                                                  _dptr(uci_llr) if uci_llr is not None else None, _dptr(evm) if evm is not None else None,
                                                  _stream_ptr(stream)))
+
+    def uci_decode_batch(self, jobs, llr, payload, status, stream=None):
+        """Short-block detection of UCI fields (jobs: numpy UciFieldJob array, or a uint8 device tensor holding the same bytes): llr int8,
+        payload uint8 (one bit per byte) and status uint8 (one per job) device tensors."""
+        import torch
+        jobs, n, ptr, on_dev = self._descs(jobs, UciFieldJob)
+        assert llr.dtype == torch.int8 and payload.dtype == torch.uint8 and status.dtype == torch.uint8
+        check(lib().miphy_uci_decode_batch(self.h, ptr, on_dev, n, _dptr(llr), _dptr(payload), _dptr(status), _stream_ptr(stream)))
 
     def pdsch_encode_batch(self, tbs, tb_in, codeword_out, stream=None):
         assert isinstance(tbs, np.ndarray) and tbs.dtype == PdschTbDesc
