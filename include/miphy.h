@@ -740,6 +740,65 @@ int miphy_pusch_uci_field_jobs(const miphy_pusch_pdu* pdus, const miphy_pusch_uc
                                uint32_t* nof_jobs);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * PUCCH processor, formats 1 and 2  --  replaces srsran::pucch_processor::process(grid, format1_configuration / format2_configuration)
+ *   lib/phy/upper/channel_processors/pucch_processor_impl.cpp:28-189 (estimate, detect or demodulate + decode, CSI),
+ *   lib/phy/upper/signal_processors/pucch/dmrs_pucch_processor_format{1,2}_impl.cpp + port_channel_estimator_average_impl.cpp:97-347
+ *   (pilots, LS, averaging per hop, noise, RSRP / EPRE / SNR, time alignment, interpolation),
+ *   lib/phy/upper/channel_processors/pucch_detector_impl.cpp:155-415 (format 1: ZF 1x1, w* and conj(r_uv), detect_bits, threshold 2.33),
+ *   lib/phy/upper/channel_processors/pucch_demodulator_impl.cpp:28-90 (format 2: ZF 1xN, QPSK soft demapping, descrambling with
+ *   c_init = rnti 2^15 + n_id) followed by the short-block detector of miphy_uci_decode_batch.
+ * All PDUs read one device grid through their own window: grid + grid_offset (cf_t units) laid out [port][14][grid_nprb * 12], the
+ * layout of the rest of the uplink, receive ports 0 .. nof_ports - 1 of the window. A contiguous range of ports is reached through
+ * grid_offset; an arbitrary list of the reference's `ports` (e.g. {0, 2}) cannot be expressed and has to be gathered into a grid of
+ * its own first (pucch_processor_hip does). Normal cyclic prefix, no group or sequence hopping.
+ * Results: `payload` receives one bit per byte from payload_offset in pucch_uci_message order (HARQ-ACK, SR, CSI part 1); format 1
+ * writes nof_harq_ack bytes (none for SR alone: the verdict is the status, VALID for a positive SR, UNKNOWN when the detected bit is 1,
+ * as in the reference). `results[i]` gets the status, the detection metric (format 1, divided by the threshold as in the reference;
+ * 0 for format 2) and the channel state information: EPRE, RSRP and SINR averaged linearly over the ports before the conversion to
+ * dB, time alignment averaged over the ports (channel_estimation.h:211-233). `llr_out` (device, may be NULL) receives the 16 nof_prb
+ * nof_symbols format-2 soft bits from llr_offset. Host jobs are checked first (MIPHY_EINVAL, nothing enqueued) against the
+ * reference's assertions (pucch_processor_impl.cpp:191-285, pucch_detector_impl.cpp:155-186, and the detector's w* table which
+ * asserts an OCC index below each hop's data-symbol count); a device job that fails them is skipped (nothing of it is written).
+ * n == 0 enqueues nothing. The call only enqueues, so it can be captured in a HIP graph. */
+typedef struct {
+  uint8_t  format;               /* 1 or 2 */
+  uint8_t  numerology;           /* slot_point numerology, 0..4 */
+  uint16_t slot;                 /* slot index within the frame */
+  uint8_t  nof_ports;            /* receive ports 1..4 (ports 0 .. nof_ports - 1 of the grid window) */
+  uint8_t  start_symbol;         /* start_symbol_index */
+  uint8_t  nof_symbols;          /* format 1: 4..14, format 2: 1..2 */
+  uint8_t  intra_slot_hopping;   /* format 1: second_hop_prb.has_value(); format 2: must be 0 */
+  uint16_t bwp_start_rb, bwp_size_rb;
+  uint16_t starting_prb;         /* within the BWP */
+  uint16_t second_hop_prb;       /* within the BWP, format 1 with hopping */
+  uint8_t  nof_prb;              /* format 2: 1..16 */
+  uint8_t  initial_cyclic_shift; /* format 1: 0..11 */
+  uint8_t  time_domain_occ;      /* format 1: 0..6 */
+  uint8_t  nof_harq_ack;         /* format 1: 0..2 */
+  uint8_t  nof_sr, nof_csi_part1, nof_csi_part2; /* format 2: 3..11 bits in all, CSI part 2 must be 0 */
+  uint8_t  reserved0;
+  uint16_t n_id;                 /* format 1: 0..1023 (group u = n_id mod 30, v = 0, cyclic-shift hopping c_init); format 2: scrambling */
+  uint16_t n_id_0;               /* format 2: DM-RS scrambling identity */
+  uint16_t rnti;                 /* format 2 */
+  uint16_t reserved1;
+  uint32_t grid_nprb;            /* width of the grid window in PRBs (>= bwp_start_rb + bwp_size_rb) */
+  uint64_t grid_offset;          /* cf_t offset of the window in `grid` */
+  uint64_t payload_offset;       /* byte offset in `payload` */
+  uint64_t llr_offset;           /* int8 offset in `llr_out` (format 2) */
+} miphy_pucch_job;
+
+typedef struct {
+  uint8_t status; /* MIPHY_UCI_STATUS_* */
+  uint8_t reserved[3];
+  float   detection_metric; /* format 1, normalised like the reference (metric / 2.33) */
+  float   epre_db, rsrp_db, sinr_db, time_alignment_s; /* channel_state_information */
+} miphy_pucch_result;
+
+int miphy_pucch_process_batch(miphy_ctx* ctx, const miphy_pucch_job* jobs, int jobs_on_device, uint32_t n, const float* grid /* device cf_t */,
+                              uint8_t* payload /* device */, miphy_pucch_result* results /* device, n */, int8_t* llr_out /* device or NULL */,
+                              void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * PDSCH encoder (whole transport blocks)  --  replaces srsran::pdsch_encoder::encode
  *   include/srsran/phy/upper/channel_processors/pdsch_encoder.h, lib/phy/upper/channel_processors/pdsch_encoder_impl.cpp:28-65
  *   (segment_tx: TB CRC16/24A, CB CRC24B, zero padding, fillers -> LDPC encode -> rate match into the codeword),

@@ -29,6 +29,7 @@
 #include "srsran/phy/upper/upper_phy_rg_gateway.h"
 #include "srsran/ran/csi_rs/csi_rs_pattern.h"
 #include "srsran/ran/pdcch/cce_to_prb_mapping.h"
+#include "srsran/ran/pucch/pucch_info.h"
 #include "srsran/ran/pusch/ulsch_info.h"
 #include "srsran/ran/ssb_mapping.h"
 #include "srsran/ran/precoding/precoding_codebooks.h"
@@ -1004,6 +1005,311 @@ public:
 private:
   short_block_detector_hip detector;
 };
+
+// ---------------------------------------------------------------------------------------------------------------- PUCCH processor
+/// srsran::pucch_processor over miphy_pucch_process_batch (pucch_processor.h:160-193, pucch_processor_impl.cpp:28-189): formats 1 and 2
+/// on the device, one PDU per call or a whole slot through process_batch(). A single PDU copies only its PRB window of the grid (all 14
+/// symbols of its ports) into the device staging buffer; the batch copies the grid once. Formats 0, 3 and 4 go to the CPU processor
+/// given at construction; without one they behave as the reference (format 0 asserts, formats 3 and 4 return an empty result).
+/// Receive ports: the staging grid holds config.ports in order, so the device reads the listed ports. The reference's estimator reads
+/// the listed ports too, but its format-1 detector and format-2 demodulator index the grid and the estimates by position
+/// (pucch_detector_impl.cpp:264-303, pucch_demodulator_impl.cpp:93-125); the two agree only when ports[i] == i, so another list goes to
+/// the CPU processor when there is one.
+class pucch_processor_hip : public srsran::pucch_processor
+{
+public:
+  using format0_configuration = srsran::pucch_processor::format0_configuration;
+  using format1_configuration = srsran::pucch_processor::format1_configuration;
+  using format2_configuration = srsran::pucch_processor::format2_configuration;
+  using format3_configuration = srsran::pucch_processor::format3_configuration;
+  using format4_configuration = srsran::pucch_processor::format4_configuration;
+
+  explicit pucch_processor_hip(std::shared_ptr<context> c, std::unique_ptr<srsran::pucch_processor> cpu_ = nullptr) :
+    c(std::move(c)), cpu(std::move(cpu_))
+  {
+  }
+
+  srsran::pucch_processor_result process(const srsran::resource_grid_reader& grid, const format0_configuration& config) override
+  {
+    if (cpu) {
+      return cpu->process(grid, config);
+    }
+    srsran::report_fatal_error("PUCCH Format 0 not implemented.");
+  }
+  srsran::pucch_processor_result process(const srsran::resource_grid_reader& grid, const format1_configuration& config) override
+  {
+    if (cpu && !identity_ports(config.ports)) {
+      return cpu->process(grid, config);
+    }
+    srsran::pucch_processor_result r;
+    run_one(grid, to_job(config), config.ports, r);
+    return r;
+  }
+  srsran::pucch_processor_result process(const srsran::resource_grid_reader& grid, const format2_configuration& config) override
+  {
+    if (cpu && !identity_ports(config.ports)) {
+      return cpu->process(grid, config);
+    }
+    srsran::pucch_processor_result r;
+    run_one(grid, to_job(config), config.ports, r);
+    return r;
+  }
+  srsran::pucch_processor_result process(const srsran::resource_grid_reader& grid, const format3_configuration& config) override
+  {
+    return cpu ? cpu->process(grid, config) : srsran::pucch_processor_result();
+  }
+  srsran::pucch_processor_result process(const srsran::resource_grid_reader& grid, const format4_configuration& config) override
+  {
+    return cpu ? cpu->process(grid, config) : srsran::pucch_processor_result();
+  }
+
+  /// A slot's PUCCH in one launch: the grid goes to the device once (the ports of the widest PDU, the PRBs up to the end of the
+  /// widest BWP), every PDU is one job, results and payloads come back in one download. out1 / out2: one result per configuration.
+  void process_batch(const srsran::resource_grid_reader&        grid,
+                     srsran::span<const format1_configuration>  f1,
+                     srsran::span<const format2_configuration>  f2,
+                     srsran::span<srsran::pucch_processor_result> out1,
+                     srsran::span<srsran::pucch_processor_result> out2)
+  {
+    require(out1.size() == f1.size() && out2.size() == f2.size(), "pucch_processor_hip::process_batch: one result per configuration.");
+    const size_t n = f1.size() + f2.size();
+    if (n == 0) {
+      return;
+    }
+    std::vector<miphy_pucch_job> jobs;
+    jobs.reserve(n);
+    unsigned nports = 0, nprb = 0;
+    auto add = [&](miphy_pucch_job j, const srsran::static_vector<uint8_t, srsran::MAX_PORTS>& ports) {
+      require(identity_ports(ports), "pucch_processor_hip::process_batch: receive ports must be 0, 1, ... in order.");
+      nports = std::max<unsigned>(nports, j.nof_ports), nprb = std::max<unsigned>(nprb, j.grid_nprb);
+      j.payload_offset = 11 * jobs.size();
+      jobs.push_back(j);
+    };
+    for (const auto& cfg : f1) {
+      add(to_job(cfg), cfg.ports);
+    }
+    for (const auto& cfg : f2) {
+      add(to_job(cfg), cfg.ports);
+    }
+    const unsigned nsc = 12 * nprb;
+    for (auto& j : jobs) { // every PDU reads the first nof_ports ports of the one staged grid, whose rows are nprb PRBs wide
+      j.grid_nprb = nprb;
+    }
+    host.resize(static_cast<size_t>(nports) * 14 * nsc);
+    for (unsigned p = 0; p != nports; ++p) {
+      for (unsigned l = 0; l != 14; ++l) {
+        grid.get(srsran::span<srsran::cf_t>(host.data() + (static_cast<size_t>(p) * 14 + l) * nsc, nsc), p, l, 0);
+      }
+    }
+    auto* d_g = static_cast<float*>(c->buf(6, host.size() * sizeof(srsran::cf_t)));
+    c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
+    download(run(jobs, d_g), jobs, f1, f2, out1, out2);
+  }
+
+private:
+  static bool identity_ports(const srsran::static_vector<uint8_t, srsran::MAX_PORTS>& ports)
+  {
+    for (unsigned i = 0; i != ports.size(); ++i) {
+      if (ports[i] != i) {
+        return false;
+      }
+    }
+    return true;
+  }
+
+  static miphy_pucch_job common(const srsran::slot_point& slot, srsran::cyclic_prefix cp, size_t nof_ports, unsigned start, unsigned nsym,
+                                unsigned bwp_start, unsigned bwp_size)
+  {
+    require(cp == srsran::cyclic_prefix::NORMAL, "pucch_processor_hip: only the normal cyclic prefix is supported.");
+    require(nof_ports >= 1 && nof_ports <= 4, "The number of receive ports must be 1 to 4.");
+    miphy_pucch_job j = {};
+    j.numerology = slot.numerology(), j.slot = slot.slot_index(), j.nof_ports = static_cast<uint8_t>(nof_ports);
+    j.start_symbol = static_cast<uint8_t>(start), j.nof_symbols = static_cast<uint8_t>(nsym);
+    j.bwp_start_rb = static_cast<uint16_t>(bwp_start), j.bwp_size_rb = static_cast<uint16_t>(bwp_size), j.grid_nprb = bwp_start + bwp_size;
+    return j;
+  }
+  static miphy_pucch_job to_job(const format1_configuration& cfg)
+  {
+    miphy_pucch_job j = common(cfg.slot, cfg.cp, cfg.ports.size(), cfg.start_symbol_index, cfg.nof_symbols, cfg.bwp_start_rb, cfg.bwp_size_rb);
+    j.format = 1, j.starting_prb = static_cast<uint16_t>(cfg.starting_prb);
+    j.intra_slot_hopping = cfg.second_hop_prb.has_value() ? 1 : 0;
+    j.second_hop_prb     = static_cast<uint16_t>(cfg.second_hop_prb.has_value() ? cfg.second_hop_prb.value() : 0);
+    j.initial_cyclic_shift = static_cast<uint8_t>(cfg.initial_cyclic_shift), j.time_domain_occ = static_cast<uint8_t>(cfg.time_domain_occ);
+    j.nof_harq_ack = static_cast<uint8_t>(cfg.nof_harq_ack), j.n_id = static_cast<uint16_t>(cfg.n_id);
+    return j;
+  }
+  static miphy_pucch_job to_job(const format2_configuration& cfg)
+  {
+    miphy_pucch_job j = common(cfg.slot, cfg.cp, cfg.ports.size(), cfg.start_symbol_index, cfg.nof_symbols, cfg.bwp_start_rb, cfg.bwp_size_rb);
+    j.format = 2, j.starting_prb = static_cast<uint16_t>(cfg.starting_prb), j.nof_prb = static_cast<uint8_t>(cfg.nof_prb);
+    j.intra_slot_hopping = cfg.second_hop_prb.has_value() ? 1 : 0;
+    j.nof_harq_ack = static_cast<uint8_t>(cfg.nof_harq_ack), j.nof_sr = static_cast<uint8_t>(cfg.nof_sr);
+    j.nof_csi_part1 = static_cast<uint8_t>(cfg.nof_csi_part1), j.nof_csi_part2 = static_cast<uint8_t>(cfg.nof_csi_part2);
+    j.n_id = static_cast<uint16_t>(cfg.n_id), j.n_id_0 = static_cast<uint16_t>(cfg.n_id_0), j.rnti = cfg.rnti;
+    return j;
+  }
+
+  /// One PDU: only its PRB window [lo, hi) of every listed port is read from the grid and uploaded; the staged rows keep the PDU's
+  /// absolute PRB numbering (the format-2 pilots depend on it), the columns outside the window are never read.
+  void run_one(const srsran::resource_grid_reader& grid, miphy_pucch_job j, const srsran::static_vector<uint8_t, srsran::MAX_PORTS>& ports,
+               srsran::pucch_processor_result& r)
+  {
+    unsigned lo = j.bwp_start_rb + j.starting_prb, hi = lo + (j.format == 2 ? j.nof_prb : 1);
+    if (j.format == 1 && j.intra_slot_hopping) {
+      const unsigned p2 = j.bwp_start_rb + j.second_hop_prb;
+      lo = std::min(lo, p2), hi = std::max(hi, p2 + 1);
+    }
+    require(hi <= j.grid_nprb, "PRB allocation goes beyond the BWP.");
+    const unsigned w = 12 * (hi - lo), nsc = 12 * j.grid_nprb, nports = ports.size();
+    host.resize(static_cast<size_t>(nports) * 14 * w);
+    for (unsigned p = 0; p != nports; ++p) {
+      for (unsigned l = 0; l != 14; ++l) {
+        grid.get(srsran::span<srsran::cf_t>(host.data() + (static_cast<size_t>(p) * 14 + l) * w, w), ports[p], l, 12 * lo);
+      }
+    }
+    auto* d_g = static_cast<srsran::cf_t*>(c->buf(6, static_cast<size_t>(nports) * 14 * nsc * sizeof(srsran::cf_t)));
+    context::hip(hipMemcpy2DAsync(d_g + 12 * lo, nsc * sizeof(srsran::cf_t), host.data(), w * sizeof(srsran::cf_t), w * sizeof(srsran::cf_t),
+                                  static_cast<size_t>(nports) * 14, hipMemcpyHostToDevice, c->stream),
+                 "h2d window");
+    std::vector<miphy_pucch_job> jobs{j};
+    const uint8_t* h = run(jobs, reinterpret_cast<float*>(d_g));
+    unpack(h, 0, j, r);
+  }
+
+  /// Launches the jobs on the staged grid and downloads results and payloads: returns the host copy, results first, then 11 payload
+  /// bytes per job.
+  const uint8_t* run(const std::vector<miphy_pucch_job>& jobs, const float* d_g)
+  {
+    const size_t n = jobs.size(), res_bytes = n * sizeof(miphy_pucch_result), bytes = res_bytes + 11 * n;
+    auto*        d  = static_cast<uint8_t*>(c->buf(7, bytes));
+    context::check(miphy_pucch_process_batch(c->ctx, jobs.data(), 0, static_cast<uint32_t>(n), d_g, d + res_bytes,
+                                             reinterpret_cast<miphy_pucch_result*>(d), nullptr, c->stream),
+                   "pucch_process");
+    down.resize(bytes);
+    c->d2h(down.data(), d, bytes);
+    c->sync();
+    return down.data();
+  }
+
+  void download(const uint8_t* h, const std::vector<miphy_pucch_job>& jobs, srsran::span<const format1_configuration> f1,
+                srsran::span<const format2_configuration> f2, srsran::span<srsran::pucch_processor_result> out1,
+                srsran::span<srsran::pucch_processor_result> out2)
+  {
+    for (size_t i = 0; i != jobs.size(); ++i) {
+      unpack(h, i, jobs[i], i < f1.size() ? out1[i] : out2[i - f1.size()]);
+    }
+  }
+
+  /// pucch_processor_result of job i (pucch_processor_impl.cpp:95-100 and 167-186).
+  void unpack(const uint8_t* h, size_t i, const miphy_pucch_job& j, srsran::pucch_processor_result& r) const
+  {
+    const size_t       n = down.size() / (sizeof(miphy_pucch_result) + 11);
+    miphy_pucch_result res;
+    std::memcpy(&res, h + i * sizeof(miphy_pucch_result), sizeof(res));
+    srsran::pucch_uci_message::configuration mc = {};
+    mc.nof_harq_ack = j.nof_harq_ack;
+    if (j.format == 2) {
+      mc.nof_sr = j.nof_sr, mc.nof_csi_part1 = j.nof_csi_part1, mc.nof_csi_part2 = j.nof_csi_part2;
+    }
+    r.message                   = srsran::pucch_uci_message(mc);
+    srsran::span<uint8_t> bits  = r.message.get_full_payload();
+    const uint8_t*        pay   = h + n * sizeof(miphy_pucch_result) + 11 * i;
+    std::copy(pay, pay + bits.size(), bits.begin());
+    r.message.set_status(res.status == MIPHY_UCI_STATUS_VALID     ? srsran::uci_status::valid
+                         : res.status == MIPHY_UCI_STATUS_INVALID ? srsran::uci_status::invalid
+                                                                   : srsran::uci_status::unknown);
+    r.csi.epre_dB        = res.epre_db;
+    r.csi.rsrp_dB        = res.rsrp_db;
+    r.csi.sinr_dB        = res.sinr_db;
+    r.csi.time_alignment = srsran::phy_time_unit::from_seconds(res.time_alignment_s);
+    if (j.format == 1) {
+      r.detection_metric = res.detection_metric;
+    } else {
+      r.detection_metric.reset();
+    }
+  }
+
+  std::shared_ptr<context>                 c;
+  std::unique_ptr<srsran::pucch_processor> cpu;
+  std::vector<srsran::cf_t>                host;
+  std::vector<uint8_t>                     down;
+};
+
+/// srsran::pucch_pdu_validator with the reference's rules (pucch_processor_impl.cpp:287-380) for the maximum channel-estimate
+/// dimensions the processor is built for. Formats 0, 3 and 4 are accepted, as the reference does.
+class pucch_pdu_validator_hip : public srsran::pucch_pdu_validator
+{
+public:
+  explicit pucch_pdu_validator_hip(const srsran::channel_estimate::channel_estimate_dimensions& dims_) : dims(dims_) {}
+  bool is_valid(const srsran::pucch_processor::format0_configuration&) const override { return true; }
+  bool is_valid(const srsran::pucch_processor::format1_configuration& config) const override
+  {
+    if (config.bwp_start_rb + config.bwp_size_rb > dims.nof_prb || config.starting_prb >= config.bwp_size_rb) {
+      return false;
+    }
+    if (config.second_hop_prb.has_value() && config.second_hop_prb.value() >= config.bwp_size_rb) {
+      return false;
+    }
+    return symbols_ok(config.cp, config.start_symbol_index, config.nof_symbols) && ports_ok(config.ports.size());
+  }
+  bool is_valid(const srsran::pucch_processor::format2_configuration& config) const override
+  {
+    const unsigned nof_uci_bits = config.nof_harq_ack + config.nof_sr + config.nof_csi_part1 + config.nof_csi_part2;
+    if (config.bwp_start_rb + config.bwp_size_rb > dims.nof_prb || config.starting_prb + config.nof_prb > config.bwp_size_rb) {
+      return false;
+    }
+    if (!symbols_ok(config.cp, config.start_symbol_index, config.nof_symbols) || !ports_ok(config.ports.size())) {
+      return false;
+    }
+    if (config.nof_csi_part2 != 0 || config.second_hop_prb.has_value()) {
+      return false;
+    }
+    if (srsran::pucch_format2_code_rate(config.nof_prb, config.nof_symbols, nof_uci_bits) > srsran::pucch_constants::MAX_CODE_RATE) {
+      return false;
+    }
+    return nof_uci_bits >= srsran::pucch_constants::FORMAT2_MIN_UCI_NBITS && nof_uci_bits <= 11;
+  }
+  bool is_valid(const srsran::pucch_processor::format3_configuration&) const override { return true; }
+  bool is_valid(const srsran::pucch_processor::format4_configuration&) const override { return true; }
+
+private:
+  bool symbols_ok(srsran::cyclic_prefix cp, unsigned start, unsigned nsym) const
+  {
+    return start + nsym <= srsran::get_nsymb_per_slot(cp) && start + nsym <= dims.nof_symbols;
+  }
+  bool ports_ok(size_t nports) const { return nports != 0 && nports <= dims.nof_rx_ports; }
+
+  srsran::channel_estimate::channel_estimate_dimensions dims;
+};
+
+/// srsran::pucch_processor_factory handing out pucch_processor_hip on one context; \c cpu_factory (may be null) provides the CPU
+/// processor for formats 0, 3 and 4.
+class pucch_processor_factory_hip : public srsran::pucch_processor_factory
+{
+public:
+  pucch_processor_factory_hip(std::shared_ptr<context> c_, const srsran::channel_estimate::channel_estimate_dimensions& dims_,
+                              std::shared_ptr<srsran::pucch_processor_factory> cpu_factory_ = nullptr) :
+    c(std::move(c_)), dims(dims_), cpu_factory(std::move(cpu_factory_))
+  {
+  }
+  std::unique_ptr<srsran::pucch_processor> create() override
+  {
+    return std::make_unique<pucch_processor_hip>(c, cpu_factory ? cpu_factory->create() : nullptr);
+  }
+  std::unique_ptr<srsran::pucch_pdu_validator> create_validator() override { return std::make_unique<pucch_pdu_validator_hip>(dims); }
+
+private:
+  std::shared_ptr<context>                         c;
+  srsran::channel_estimate::channel_estimate_dimensions dims;
+  std::shared_ptr<srsran::pucch_processor_factory> cpu_factory;
+};
+
+inline std::shared_ptr<srsran::pucch_processor_factory>
+create_pucch_processor_factory_hip(std::shared_ptr<context> c, const srsran::channel_estimate::channel_estimate_dimensions& dims,
+                                   std::shared_ptr<srsran::pucch_processor_factory> cpu_factory = nullptr)
+{
+  return std::make_shared<pucch_processor_factory_hip>(std::move(c), dims, std::move(cpu_factory));
+}
 
 // ---------------------------------------------------------------------------------------------------------------- PUSCH processor
 /// srsran::pusch_processor over miphy_pusch_process_batch (pusch_processor.h:158-162): estimation, demodulation and decoding in one

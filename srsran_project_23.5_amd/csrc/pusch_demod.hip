@@ -13,29 +13,13 @@
 // so the LLRs are reproducible bit for bit by a scalar CPU restatement; against the reference AVX2 build they are within one step.
 #define NR_DEMOD_TABLE_ATTR __device__
 #include "gold_device.h"
+#include "demod_device.h"
 #include "mod_device.h"
 #include "miphy_ext.h"
 #include "tables/nr_demod_tables.h"
 #include <cmath>
 
 namespace {
-
-// Quantisation of avx2_helpers.h:103-157: scale, clip to +-120, round to nearest even, NaN -> 0.
-__device__ __forceinline__ int demod_quantize(float v, float scale)
-{
-#pragma clang fp contract(off)
-  float s = v * scale;
-  s       = (s > 120.0f) ? 120.0f : s;
-  s       = (s < -120.0f) ? -120.0f : s;
-  const float r = rintf(s);
-  return (r <= 120.0f && r >= -120.0f) ? (int)r : 0; // NaN -> 0
-}
-// Same for a value that is known not to be NaN (the caller checks the inputs once per resource element).
-__device__ __forceinline__ int demod_quantize_fast(float v, float scale)
-{
-#pragma clang fp contract(off)
-  return (int)rintf(__builtin_amdgcn_fmed3f(v * scale, -120.0f, 120.0f));
-}
 
 // LDS copy of the interval tables of one modulation: level k (bits 2k, 2k+1) at tab[16 k ...], {slope, intercept} pairs. In two steps:
 // the lanes request their table entry from memory (demod_table_entry) as soon as the modulation is known, and put it into LDS

@@ -118,6 +118,7 @@ def lib():
         l.miphy_ofdm_symbol_size.restype = C.c_uint32
         l.miphy_uci_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_pusch_uci_field_jobs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
+        l.miphy_pucch_process_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
         _lib = l
     return _lib
 
@@ -268,6 +269,19 @@ UciFieldJob = np.dtype([("nof_bits", np.uint8), ("mod", np.uint8), ("reserved", 
                         ("payload_offset", np.uint64)], align=True)
 assert UciFieldJob.itemsize == 24
 UCI_STATUS_UNKNOWN, UCI_STATUS_VALID, UCI_STATUS_INVALID = 0, 1, 2
+
+# miphy_pucch_job / miphy_pucch_result (include/miphy.h)
+PucchJob = np.dtype([("format", np.uint8), ("numerology", np.uint8), ("slot", np.uint16), ("nof_ports", np.uint8), ("start_symbol", np.uint8),
+                     ("nof_symbols", np.uint8), ("intra_slot_hopping", np.uint8), ("bwp_start_rb", np.uint16), ("bwp_size_rb", np.uint16),
+                     ("starting_prb", np.uint16), ("second_hop_prb", np.uint16), ("nof_prb", np.uint8), ("initial_cyclic_shift", np.uint8),
+                     ("time_domain_occ", np.uint8), ("nof_harq_ack", np.uint8), ("nof_sr", np.uint8), ("nof_csi_part1", np.uint8),
+                     ("nof_csi_part2", np.uint8), ("reserved0", np.uint8), ("n_id", np.uint16), ("n_id_0", np.uint16), ("rnti", np.uint16),
+                     ("reserved1", np.uint16), ("grid_nprb", np.uint32), ("grid_offset", np.uint64), ("payload_offset", np.uint64),
+                     ("llr_offset", np.uint64)], align=True)
+assert PucchJob.itemsize == 64
+PucchResult = np.dtype([("status", np.uint8), ("reserved", np.uint8, 3), ("detection_metric", np.float32), ("epre_db", np.float32),
+                        ("rsrp_db", np.float32), ("sinr_db", np.float32), ("time_alignment_s", np.float32)], align=True)
+assert PucchResult.itemsize == 24
 
 
 def pusch_uci_field_jobs(pdus, uci):
@@ -616,6 +630,18 @@ class Context:
         jobs, n, ptr, on_dev = self._descs(jobs, UciFieldJob)
         assert llr.dtype == torch.int8 and payload.dtype == torch.uint8 and status.dtype == torch.uint8
         check(lib().miphy_uci_decode_batch(self.h, ptr, on_dev, n, _dptr(llr), _dptr(payload), _dptr(status), _stream_ptr(stream)))
+
+    def pucch_process_batch(self, jobs, grid, payload, results, llr=None, stream=None):
+        """PUCCH formats 1 and 2 (jobs: numpy PucchJob array, or a uint8 device tensor holding the same bytes): grid complex64 device
+        tensor, payload uint8 (one bit per byte), results a uint8 device tensor of n * PucchResult.itemsize bytes (view it with
+        .cpu().numpy().view(PucchResult)), llr None or an int8 device tensor for the format-2 soft bits."""
+        import torch
+        jobs, n, ptr, on_dev = self._descs(jobs, PucchJob)
+        assert grid.dtype == torch.complex64 and payload.dtype == torch.uint8 and results.dtype == torch.uint8
+        assert results.numel() >= n * PucchResult.itemsize
+        assert llr is None or llr.dtype == torch.int8
+        check(lib().miphy_pucch_process_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(payload), _dptr(results),
+                                              None if llr is None else _dptr(llr), _stream_ptr(stream)))
 
     def pdsch_encode_batch(self, tbs, tb_in, codeword_out, stream=None):
         assert isinstance(tbs, np.ndarray) and tbs.dtype == PdschTbDesc
