@@ -48,9 +48,14 @@ typedef struct miphy_ctx miphy_ctx;
  * stream. Descriptor arrays in host memory are copied when the call is made (pinned staging ring of the context: the array can be
  * reused at once; the device is synchronised only when the 8 MB ring wraps) -- or pass descriptors that already live on the device
  * (`*_on_device` = 1). Scratch workspaces belong to the context and are reused by its next call in stream order: use one stream
- * at a time per context. With device-resident descriptors and plans a sequence of calls can be captured in a HIP graph as it is
- * (bench.py replays the single-slot pipeline that way); host descriptors must not be captured: a replay would read a staging
- * slot that has been reused since. */
+ * at a time per context. A workspace that has to grow gets a new block; the old one stays allocated until miphy_destroy.
+ * HIP graph capture (bench.py replays the single-slot pipeline that way):
+ *  - a prepared plan (*_plan_create / *_plan_run) owns its descriptors, scratch and side streams: it can be captured from its
+ *    first run, and a replay stays valid whatever the context runs later;
+ *  - a per-call entry point with device-resident descriptors can be captured once it has run at that size on the context (its
+ *    first runs may grow a workspace or build a cache, e.g. OFDM plans, polar codes, Gold tables); it then stays valid after
+ *    later, larger calls;
+ *  - host descriptors must not be captured: a replay would read a staging slot that has been reused since. */
 int         miphy_create(int device, miphy_ctx** ctx);
 void        miphy_destroy(miphy_ctx* ctx);
 const char* miphy_last_error(void);
@@ -100,7 +105,8 @@ int miphy_ldpc_decode_batch(miphy_ctx*                 ctx,
                             const miphy_ldpc_dec_limits* limits, /* may be NULL */
                             void*                      stream);
 /* Prepared form of miphy_ldpc_decode_batch for batches whose geometry repeats (same descriptors slot after slot): the descriptors
- * are validated, sorted into launch classes and uploaded once; a run only launches (no host synchronisation, no staging). */
+ * are validated, sorted into launch classes and uploaded once, and the launch geometry and message scratch of every class are fixed;
+ * a run only launches (no host synchronisation, no staging, no allocation). */
 typedef struct miphy_ldpc_decode_plan miphy_ldpc_decode_plan;
 int      miphy_ldpc_decode_plan_create(miphy_ctx* ctx, const miphy_ldpc_dec_desc* descs /* host */, uint32_t n, miphy_ldpc_decode_plan** out);
 int      miphy_ldpc_decode_plan_run(miphy_ldpc_decode_plan* plan, const int8_t* llr, uint8_t* out_bits, int32_t* iters, void* stream);
@@ -112,7 +118,8 @@ void     miphy_ldpc_decode_plan_destroy(miphy_ldpc_decode_plan* plan);
  * 3 = class-sorted launches, 4 = class-sorted launches with the geometry of a batch that fills the chip whatever its size (no latency form, messages in global
  * memory wherever that buys residency), 5 = class-sorted launches with the latency form of the packed kernel (two parts) on every class (A-B measurement only),
  * 6 = automatic choice with the latency form in two parts instead of four. Adding 0x100 keeps ALL messages of a GMSG launch in global memory (A-B of the
- * split between LDS and global memory). All kernels produce identical results. */
+ * split between LDS and global memory). All kernels produce identical results. Prepared plans keep the choice in force when they were
+ * created: the knob applies to plans created after it is set (and to every per-call decode). */
 void miphy_debug_force_ldpc_kernel(int mode);
 /* Which decoder kernels have been launched since the last reset (tests assert that a forced choice really ran): */
 #define MIPHY_LDPC_KERNEL_SCALAR 1u /* one check row per lane */
@@ -123,7 +130,8 @@ void miphy_debug_force_ldpc_kernel(int mode);
 #define MIPHY_LDPC_KERNEL_SPLIT 32u /* packed kernel in its latency form: four (or two) times the wavefronts per codeblock (launches of at most one codeblock per CU) */
 #define MIPHY_LDPC_KERNEL_GMSG_PART 64u /* ... a GMSG launch that kept the first layers' messages in LDS (only the layers behind a boundary in global memory) */
 unsigned miphy_debug_ldpc_kernels_used(int reset);
-/* A-B knob: streams the launch classes of one call are spread over (1 = one after another on the caller's stream). */
+/* A-B knob: streams the launch classes of one call are spread over (1 = one after another on the caller's stream). Like
+ * miphy_debug_force_ldpc_kernel, it applies to plans created after it is set. */
 void miphy_debug_set_ldpc_class_streams(int n);
 /* Test hook: codeblocks of the PDSCH encoder launches since the last reset that the bit-packed kernel took (out[0]) and in total (out[1]). */
 void miphy_debug_pdsch_cb_counts(unsigned out[2], int reset);
@@ -582,7 +590,8 @@ int miphy_pusch_decode_batch(miphy_ctx*                 ctx,
                              void*                      stream);
 
 /* Prepared form of miphy_pusch_decode_batch for allocations that repeat (semi-static scheduling, benchmarks): _create runs the
- * segmentation (ldpc_segmenter_impl.cpp:253-334) and uploads the codeblock descriptors once; every _run is kernel launches only
+ * segmentation (ldpc_segmenter_impl.cpp:253-334), uploads the codeblock descriptors and fixes the decoder's launch tables and message
+ * scratch once; every _run is kernel launches only
  * (CRC-flag reset, rate dematching, LDPC decoding, transport-block assembly + TB CRC + result records) with no host
  * synchronisation, on the arrays passed to that run. A plan belongs to the context it was created on and must not run
  * concurrently with itself. */
@@ -862,7 +871,8 @@ uint32_t miphy_pdsch_pdu_nof_re(const miphy_pdsch_pdu* pdu);
 int miphy_pdsch_process_batch(miphy_ctx* ctx, const miphy_pdsch_pdu* pdus /* host */, uint32_t n, const uint8_t* tb_in /* device */,
                               float* grid /* device cf_t; only the mapped REs are written */, void* stream);
 /* Prepared form for allocations that repeat slot after slot: PDU validation, segmentation and descriptor uploads once, a run only
- * launches (TB CRC, codeblock preparation, LDPC encoder, rate matcher, modulator, DM-RS), no staging, no host synchronisation. */
+ * launches (TB CRC, codeblock preparation, LDPC encoder, rate matcher, modulator, DM-RS) on buffers the plan owns, no staging, no
+ * allocation, no host synchronisation. */
 typedef struct miphy_pdsch_process_plan miphy_pdsch_process_plan;
 int  miphy_pdsch_process_plan_create(miphy_ctx* ctx, const miphy_pdsch_pdu* pdus /* host */, uint32_t n, miphy_pdsch_process_plan** out);
 int  miphy_pdsch_process_plan_run(miphy_pdsch_process_plan* plan, const uint8_t* tb_in /* device */, float* grid /* device cf_t */, void* stream);

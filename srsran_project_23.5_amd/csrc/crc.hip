@@ -51,9 +51,9 @@ extern "C" int miphy_crc_batch(miphy_ctx*            ctx,
     for (uint32_t i = 0; i < n; ++i)
       MIPHY_REQUIRE(descs[i].poly <= MIPHY_CRC11, "crc: desc %u: invalid polynomial %u", i, descs[i].poly);
   hipStream_t s       = (hipStream_t)stream;
-  const void* d_descs = nullptr;
-  int         rc      = miphy_stage_descs(ctx, descs, descs_on_device, sizeof(miphy_crc_desc) * (size_t)n, s, &d_descs);
-  if (rc)
+  const void* d_descs = descs;
+  int         rc;
+  if (!descs_on_device && (rc = miphy_stage_descs(ctx, descs, 0, sizeof(miphy_crc_desc) * (size_t)n, s, &d_descs)))
     return rc;
   // Few, long messages (transport blocks): 1024 threads each; many short ones: 256 are plenty.
   hipLaunchKernelGGL(crc_kernel, dim3(n), dim3(n <= CRC_WIDE_BELOW ? 1024 : CRC_NARROW_THREADS), 0, s, (const miphy_crc_desc*)d_descs, ctx->d_tables, data, checksums);

@@ -16,6 +16,7 @@
 //     multiplies it by x^(32k) mod P and the partial remainders are XOR-reduced with wavefront shuffles.
 #include "miphy_internal.h"
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -377,19 +378,15 @@ ldpc_decode_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
 #ifndef LDPC_HYBRID_LDS_MARGIN
 #define LDPC_HYBRID_LDS_MARGIN 2048
 #endif
-static bool     g_hybrid_msgs  = true; // A-B: miphy_debug_force_ldpc_kernel(mode | 0x100) = all messages of a GMSG launch in global memory
-static int      g_force_kernel = 0; // 0 auto, 1 one-row-per-lane kernel, 2 packed kernel as ONE launch, 3 class-sorted launches (miphy_debug_force_ldpc_kernel)
-static unsigned g_kernels_used = 0; // MIPHY_LDPC_KERNEL_* of every decoder launch since the last reset (miphy_debug_ldpc_kernels_used)
+// Debug knobs, read by miphy_ldpc_plan_launches (and the one-launch path of miphy_ldpc_decode_batch) when a launch table is made.
+static bool g_hybrid_msgs  = true; // A-B: miphy_debug_force_ldpc_kernel(mode | 0x100) = all messages of a GMSG launch in global memory
+static int  g_force_kernel = 0; // 0 auto, 1 one-row-per-lane kernel, 2 packed kernel as ONE launch, 3 class-sorted launches (miphy_debug_force_ldpc_kernel)
+static std::atomic<unsigned> g_kernels_used{0}; // MIPHY_LDPC_KERNEL_* of every decoder launch since the last reset (miphy_debug_ldpc_kernels_used)
 
 extern "C" void miphy_debug_force_ldpc_kernel(int mode)
 {
   g_force_kernel = mode & 0xff;
   g_hybrid_msgs  = !(mode & 0x100);
-}
-
-bool miphy_ldpc_scalar_forced()
-{
-  return g_force_kernel == 1;
 }
 
 static int g_class_streams = 1 + MIPHY_NOF_SIDE_STREAMS; // streams the launch classes of a call are spread over (miphy_debug_set_ldpc_class_streams)
@@ -401,10 +398,7 @@ extern "C" void miphy_debug_set_ldpc_class_streams(int n)
 
 extern "C" unsigned miphy_debug_ldpc_kernels_used(int reset)
 {
-  const unsigned m = g_kernels_used;
-  if (reset)
-    g_kernels_used = 0;
-  return m;
+  return reset ? g_kernels_used.exchange(0) : g_kernels_used.load();
 }
 
 // pusch_decoder_impl.cpp:146-149: the codeblock CRC flags of a new transmission start cleared.
@@ -510,46 +504,41 @@ void miphy_ldpc_build_classes(const miphy_ldpc_dec_desc* descs, uint32_t n, cons
   }
 }
 
-int miphy_ldpc_decode_classes_launch(miphy_ctx* ctx, const miphy_ldpc_dec_desc* d_descs, const miphy_ldpc_classes& C, const uint32_t* d_order,
-                                     const uint32_t* d_bundles, const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot,
-                                     uint8_t* harq_crc_ok, hipStream_t s, const miphy_ldpc_rdm_desc* d_rdm, const int8_t* rm_in, bool allow_fuse)
+void miphy_ldpc_plan_launches(const miphy_ctx* ctx, const miphy_ldpc_classes& C, bool fuse, miphy_ldpc_launches& T)
 {
   const size_t nc = C.classes.size();
-  if (nc == 0)
-    return MIPHY_OK;
+  T               = miphy_ldpc_launches{};
+  T.scalar        = g_force_kernel == 1;
+  T.l.resize(nc);
   // Geometry of every class first: the launches of one call run side by side, so each needs message scratch of its own.
-  struct geom {
-    bool   fuse, gm;
-    int    split; // parts of the latency form (0: throughput form)
-    int    threads, pairs, lds_pairs;
-    size_t lds, gmsg_bytes, gmsg_off;
-    int    stream; // 0 = the caller's, 1 .. = side streams
-  };
-  std::vector<geom> g(nc);
-  size_t            gmsg_total = 0;
   for (size_t i = 0; i < nc; ++i) {
-    const miphy_ldpc_class& c = C.classes[i];
-    geom&                   q = g[i];
-    q = geom{};
-    const int bgK = c.bgi ? 10 : 22;
-    if (g_force_kernel == 1)
-      continue;
-    if (c.kind == 0) {
-      q.gmsg_bytes = miphy_ldpc_pkw_gmsg_bytes(ctx, c.bundle_count, c.bgi, c.lay, c.soft_total, g_force_kernel == 4);
+    miphy_ldpc_launch& q = T.l[i];
+    q.c                  = C.classes[i];
+    const miphy_ldpc_class& c = q.c;
+    const int               bgK = c.bgi ? 10 : 22;
+    q.nodes                     = bgK + c.lay;
+    q.parts                     = 1;
+    q.ordered                   = !(C.identity && nc == 1);
+    if (g_force_kernel == 1) { // A-B knob: the one-row-per-lane kernel on every class (the caller has dematched: nothing is fused then)
+      q.used    = MIPHY_LDPC_KERNEL_SCALAR;
+      q.threads = ((c.max_Z + 63) / 64) * 64;
+      q.lds     = ((((size_t)bgK + c.lay) * q.threads + 15) & ~(size_t)15) + (size_t)(c.lay + 4) * q.threads * 4 + 64;
+      q.grid    = c.count;
+    } else if (c.kind == 0) {
+      miphy_ldpc_pkw_geometry(ctx, g_force_kernel == 4, q);
     } else {
-      q.threads = 64 * c.kind;
-      q.pairs   = ctx->h_tables->pair_start[c.bgi][c.lay];
-      q.fuse    = c.fused && allow_fuse && d_rdm;
-      const size_t lds_l = miphy_ldpc_pk_lds_bytes(bgK, c.lay, c.max_Z, q.pairs), lds_g = miphy_ldpc_pk_lds_bytes(bgK, c.lay, c.max_Z, 0);
+      const bool fused = c.fused && fuse;
+      const int  pairs = ctx->h_tables->pair_start[c.bgi][c.lay];
+      const size_t lds_l = miphy_ldpc_pk_lds_bytes(bgK, c.lay, c.max_Z, pairs), lds_g = miphy_ldpc_pk_lds_bytes(bgK, c.lay, c.max_Z, 0);
       // messages in LDS while that keeps as many codeblocks resident per CU as the registers allow; otherwise in global memory
-      auto per_cu = [&](size_t lds) { return std::max(1, std::min((int)((size_t)160 * 1024 / lds), miphy_ldpc_pk_waves_per_cu(q.fuse) / (int)c.kind)); };
+      auto per_cu = [&](size_t lds) { return std::max(1, std::min((int)((size_t)160 * 1024 / lds), miphy_ldpc_pk_waves_per_cu(fused) / (int)c.kind)); };
       // (and only where the class has more codeblocks than stay resident with the messages in LDS: otherwise the global round trip per
       // layer visit buys nothing)
-      q.gm         = per_cu(lds_g) > per_cu(lds_l) && (g_force_kernel == 4 || c.count > (uint32_t)(ctx->num_cus * per_cu(lds_l)));
-      q.lds        = q.gm ? lds_g : lds_l;
+      bool gm   = per_cu(lds_g) > per_cu(lds_l) && (g_force_kernel == 4 || c.count > (uint32_t)(ctx->num_cus * per_cu(lds_l)));
+      q.lds     = gm ? lds_g : lds_l;
       // Only as many layers' messages leave LDS as that residency needs: the first layers keep theirs (a lane's messages are private to it,
       // so the split is free), the global round trip and its L2 traffic are paid for the rest.
-      if (q.gm && g_force_kernel != 4 && g_hybrid_msgs) {
+      if (gm && g_force_kernel != 4 && g_hybrid_msgs) {
         for (int k = c.lay - 1; k > 0; --k) {
           const int    pk_ = ctx->h_tables->pair_start[c.bgi][k];
           const size_t l_  = miphy_ldpc_pk_lds_bytes(bgK, c.lay, c.max_Z, pk_);
@@ -563,120 +552,163 @@ int miphy_ldpc_decode_classes_launch(miphy_ctx* ctx, const miphy_ldpc_dec_desc* 
       // messages in LDS (residency is no concern then).
       // (four parts while the codeblocks of the class still find a CU each and the workgroup stays within 1024 threads; forced mode 6: two)
       const int    parts = (g_force_kernel == 5 || g_force_kernel == 6) ? 2 : 4;
-      const size_t lds_s = miphy_ldpc_pk_lds_bytes(bgK, c.lay, c.max_Z, q.pairs, parts);
-      q.split            = (g_force_kernel != 4 && (c.count <= (uint32_t)ctx->num_cus || g_force_kernel == 5) && lds_s <= (size_t)160 * 1024) ? parts : 0;
-      if (q.split)
-        q.gm = false, q.lds = lds_s;
-      q.gmsg_bytes = miphy_ldpc_pk_gmsg_bytes(ctx, c.count, q.threads, q.lds, q.fuse, q.gm ? q.pairs - q.lds_pairs : 0);
+      const size_t lds_s = miphy_ldpc_pk_lds_bytes(bgK, c.lay, c.max_Z, pairs, parts);
+      if (g_force_kernel != 4 && (c.count <= (uint32_t)ctx->num_cus || g_force_kernel == 5) && lds_s <= (size_t)160 * 1024)
+        q.parts = parts, gm = false, q.lds = lds_s, q.lds_pairs = 0;
+      q.threads    = 64 * c.kind * q.parts;
+      q.gmsg_pairs = gm ? pairs - q.lds_pairs : 0;
+      q.grid       = miphy_ldpc_pk_grid(ctx, c.count, q.threads, q.lds, fused, q.parts);
+      q.gmsg_bytes = gm ? (size_t)q.grid * (q.threads / 64) * (size_t)q.gmsg_pairs * 256 : 0;
+      q.used       = MIPHY_LDPC_KERNEL_PACKED | (fused ? MIPHY_LDPC_KERNEL_FUSED : 0u) | (gm ? MIPHY_LDPC_KERNEL_GMSG : 0u) |
+               (q.parts > 1 ? MIPHY_LDPC_KERNEL_SPLIT : 0u) | ((gm && q.lds_pairs > 0) ? MIPHY_LDPC_KERNEL_GMSG_PART : 0u);
     }
-    q.gmsg_off = gmsg_total;
-    gmsg_total += (q.gmsg_bytes + 255) & ~(size_t)255;
-  }
-  uint8_t* gmsg_base = nullptr;
-  int      rc;
-  if (gmsg_total) {
-    void* w = nullptr;
-    if ((rc = miphy_get_workspace(ctx, gmsg_total, s, &w, 3)))
-      return rc;
-    gmsg_base = (uint8_t*)w;
+    q.gmsg_off = T.gmsg_bytes;
+    T.gmsg_bytes += (q.gmsg_bytes + 255) & ~(size_t)255;
   }
   // Classes to streams. A class whose whole grid is a fraction of the chip (at most four wavefronts per CU: a few hundred small
   // codeblocks) is a latency chain -- one after another such classes each cost their full latency with the chip idle, next to a
   // large class they cost nothing: they go to the side streams, round robin. The large classes stay on the caller's stream one
   // after another: two chip-filling persistent grids side by side was measured slower and erratic (4.6 ms in sequence, 4.1 to 6.7
   // side by side on the mixed slot of bench.py), each holds the registers and LDS the other was tuned to have.
-  int nstreams = 1;
   if (nc > 1 && g_class_streams > 1) {
     int small = 0;
-    for (size_t i = 0; i < nc; ++i) {
-      const miphy_ldpc_class& c = C.classes[i];
-      const uint64_t waves = c.kind == 0 ? c.bundle_count : (uint64_t)c.count * c.kind * (g[i].split ? g[i].split : 1);
+    for (miphy_ldpc_launch& q : T.l) {
+      const uint64_t waves = q.c.kind == 0 ? q.c.bundle_count : (uint64_t)q.c.count * q.c.kind * q.parts;
       if (waves <= (uint64_t)ctx->num_cus * 4)
-        g[i].stream = 1 + (small++ % (g_class_streams - 1));
+        q.stream = 1 + (small++ % (g_class_streams - 1));
     }
     if (small == (int)nc) // nothing large: the first small class takes the caller's stream
-      g[0].stream = 0;
-    if (small > 0)
-      nstreams = g_class_streams;
+      T.l[0].stream = 0;
+    T.side_streams = small > 0;
   }
-  if (nstreams > 1) {
-    if ((rc = miphy_side_streams(ctx)))
-      return rc;
-    MIPHY_HIP_CHECK(hipEventRecord((hipEvent_t)ctx->ev_fork, s));
-    for (int k = 0; k < MIPHY_NOF_SIDE_STREAMS; ++k)
-      MIPHY_HIP_CHECK(hipStreamWaitEvent((hipStream_t)ctx->side_stream[k], (hipEvent_t)ctx->ev_fork, 0));
-  }
-  for (size_t k2 = 0; k2 < 2 * nc; ++k2) { // the side-stream classes first: they start while the large ones are being enqueued
-    const size_t i = k2 % nc;
-    if ((g[i].stream != 0) != (k2 < nc))
+}
+
+namespace {
+// The launches of a table, the side-stream classes first: they start while the large ones are being enqueued.
+int enqueue_launches(miphy_ctx* ctx, const miphy_ldpc_launches& T, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order,
+                     const uint32_t* d_bundles, const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot,
+                     uint8_t* harq_crc_ok, const miphy_ldpc_rdm_desc* d_rdm, const int8_t* rm_in, void* gmsg, hipStream_t s)
+{
+  const size_t nc = T.l.size();
+  for (size_t k2 = 0; k2 < 2 * nc; ++k2) {
+    const miphy_ldpc_launch& L = T.l[k2 % nc];
+    if ((L.stream != 0) != (k2 < nc))
       continue;
-    const miphy_ldpc_class& c  = C.classes[i];
-    const geom&             q  = g[i];
-    hipStream_t             st = q.stream == 0 ? s : (hipStream_t)ctx->side_stream[q.stream - 1];
-    void*                   gb = q.gmsg_bytes ? gmsg_base + q.gmsg_off : nullptr;
-    if (g_force_kernel == 1) { // A-B knob: the one-row-per-lane kernel on every class (the caller has dematched: allow_fuse is false then)
-      const int    bgK = c.bgi ? 10 : 22, threads = ((c.max_Z + 63) / 64) * 64;
-      const size_t lds = ((((size_t)bgK + c.lay) * threads + 15) & ~(size_t)15) + (size_t)(c.lay + 4) * threads * 4 + 64;
-      if (lds > 48 * 1024)
-        MIPHY_HIP_CHECK(hipFuncSetAttribute((const void*)ldpc_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(ldpc_decode_kernel, dim3(c.count), dim3(threads), lds, st, d_descs, ctx->d_tables, llr, out_bits, iters, bgK + c.lay, harq_slot,
-                         harq_crc_ok, d_order + c.first);
+    hipStream_t st = L.stream == 0 ? s : (hipStream_t)ctx->side_stream[L.stream - 1];
+    void*       gb = L.gmsg_bytes ? (uint8_t*)gmsg + L.gmsg_off : nullptr;
+    int         rc = MIPHY_OK;
+    if (L.used & MIPHY_LDPC_KERNEL_SCALAR) {
+      if (L.lds > 48 * 1024)
+        MIPHY_HIP_CHECK(hipFuncSetAttribute((const void*)ldpc_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+      hipLaunchKernelGGL(ldpc_decode_kernel, dim3(L.grid), dim3(L.threads), L.lds, st, d_descs, ctx->d_tables, llr, out_bits, iters, L.nodes, harq_slot,
+                         harq_crc_ok, d_order + L.c.first);
       MIPHY_HIP_CHECK(hipGetLastError());
-      g_kernels_used |= MIPHY_LDPC_KERNEL_SCALAR;
-      continue;
+    } else if (L.used & MIPHY_LDPC_KERNEL_WAVE) {
+      rc = miphy_ldpc_pkw_launch(ctx, L, d_descs, d_order, d_bundles + 2 * (size_t)L.c.bundle_first, llr, out_bits, iters, harq_slot, harq_crc_ok, gb, st);
+    } else {
+      const bool fused = (L.used & MIPHY_LDPC_KERNEL_FUSED) != 0;
+      rc = miphy_ldpc_pk_launch(ctx, L, d_descs, L.ordered ? d_order + L.c.first : nullptr, llr, out_bits, iters, harq_slot, harq_crc_ok,
+                                fused ? d_rdm : nullptr, fused ? rm_in : nullptr, gb, st);
     }
-    if (c.kind == 0) {
-      int gm = 0;
-      if ((rc = miphy_ldpc_pkw_launch(ctx, d_descs, d_order, d_bundles + 2 * (size_t)c.bundle_first, c.bundle_count, c.bgi, c.lay, c.soft_total, llr, out_bits,
-                                      iters, harq_slot, harq_crc_ok, st, &gm, gb, g_force_kernel == 4)))
-        return rc;
-      g_kernels_used |= MIPHY_LDPC_KERNEL_WAVE | (gm ? MIPHY_LDPC_KERNEL_GMSG : 0u);
-      continue;
-    }
-    const int bgK = c.bgi ? 10 : 22;
-    if ((rc = miphy_ldpc_pk_launch(ctx, d_descs, c.count, q.threads, q.lds, llr, out_bits, iters, bgK + c.lay, harq_slot, harq_crc_ok, st,
-                                   q.fuse ? d_rdm : nullptr, q.fuse ? rm_in : nullptr, q.gm ? q.pairs - q.lds_pairs : 0,
-                                   (C.identity && nc == 1) ? nullptr : d_order + c.first, gb, q.split, q.gm ? q.lds_pairs : 0)))
+    if (rc)
       return rc;
-    g_kernels_used |= MIPHY_LDPC_KERNEL_PACKED | (q.fuse ? MIPHY_LDPC_KERNEL_FUSED : 0u) | (q.gm ? MIPHY_LDPC_KERNEL_GMSG : 0u) |
-                      (q.split ? MIPHY_LDPC_KERNEL_SPLIT : 0u) | ((q.gm && q.lds_pairs > 0) ? MIPHY_LDPC_KERNEL_GMSG_PART : 0u);
-  }
-  if (nstreams > 1) {
-    for (int k = 0; k < MIPHY_NOF_SIDE_STREAMS; ++k) {
-      MIPHY_HIP_CHECK(hipEventRecord((hipEvent_t)ctx->ev_join[k], (hipStream_t)ctx->side_stream[k]));
-      MIPHY_HIP_CHECK(hipStreamWaitEvent(s, (hipEvent_t)ctx->ev_join[k], 0));
-    }
+    g_kernels_used.fetch_or(L.used);
   }
   return MIPHY_OK;
 }
 
-// ---- one launch for the whole batch (device-resident descriptors, which the host cannot sort; forced kernels of the A-B knob) -------
-int miphy_ldpc_decode_launch(miphy_ctx*                   ctx,
-                             const miphy_ldpc_dec_desc*   descs,
-                             int                          descs_on_device,
-                             uint32_t                     n,
-                             const int8_t*                llr,
-                             uint8_t*                     out_bits,
-                             int32_t*                     iters,
-                             const miphy_ldpc_dec_limits* limits,
-                             const uint32_t*              harq_slot,
-                             uint8_t*                     harq_crc_ok,
-                             void*                        stream,
-                             const miphy_ldpc_rdm_desc*   fuse_rdm,
-                             const int8_t*                fuse_in,
-                             const miphy_ldpc_rdm_limits* fuse_rlim,
-                             int                          bg_mask,
-                             const uint32_t*              reset_slots,
-                             uint32_t                     nof_reset_slots)
+int hip_status(hipError_t e, const char* what)
+{
+  if (e == hipSuccess)
+    return MIPHY_OK;
+  miphy_set_error("ldpc_decode: %s -> %s", what, hipGetErrorString(e));
+  return MIPHY_EHIP;
+}
+} // namespace
+
+int miphy_ldpc_run_launches(miphy_ctx* ctx, const miphy_ldpc_launches& T, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order,
+                            const uint32_t* d_bundles, const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot,
+                            uint8_t* harq_crc_ok, const miphy_ldpc_rdm_desc* d_rdm, const int8_t* rm_in, void* gmsg, hipStream_t s)
+{
+  if (!T.side_streams)
+    return enqueue_launches(ctx, T, d_descs, d_order, d_bundles, llr, out_bits, iters, harq_slot, harq_crc_ok, d_rdm, rm_in, gmsg, s);
+  MIPHY_REQUIRE(ctx->ev_fork, "ldpc_decode: the side streams of the context have not been created");
+  int rc = hip_status(hipEventRecord((hipEvent_t)ctx->ev_fork, s), "fork");
+  for (int k = 0; k < MIPHY_NOF_SIDE_STREAMS && !rc; ++k)
+    rc = hip_status(hipStreamWaitEvent((hipStream_t)ctx->side_stream[k], (hipEvent_t)ctx->ev_fork, 0), "fork");
+  if (!rc)
+    rc = enqueue_launches(ctx, T, d_descs, d_order, d_bundles, llr, out_bits, iters, harq_slot, harq_crc_ok, d_rdm, rm_in, gmsg, s);
+  // the join on every path after the fork: the caller's stream (and a capture on it) takes back whatever reached the side streams
+  for (int k = 0; k < MIPHY_NOF_SIDE_STREAMS; ++k) {
+    int jc = hip_status(hipEventRecord((hipEvent_t)ctx->ev_join[k], (hipStream_t)ctx->side_stream[k]), "join");
+    if (!jc)
+      jc = hip_status(hipStreamWaitEvent(s, (hipEvent_t)ctx->ev_join[k], 0), "join");
+    rc = rc ? rc : jc;
+  }
+  return rc;
+}
+
+namespace {
+// The reference asserts the same conditions (ldpc_decoder_impl.cpp:66-84).
+int validate_descs(const miphy_ctx* ctx, const miphy_ldpc_dec_desc* descs, uint32_t n)
+{
+  for (uint32_t i = 0; i < n; ++i) {
+    const miphy_ldpc_dec_desc& d = descs[i];
+    MIPHY_REQUIRE(d.bg == 1 || d.bg == 2, "ldpc_decode: desc %u: invalid base graph %u", i, d.bg);
+    MIPHY_REQUIRE(d.Z <= MIPHY_MAX_Z && ctx->h_tables->z_pos[d.Z] != 0xffff, "ldpc_decode: desc %u: invalid lifting size %u", i, d.Z);
+    const unsigned bgK = (d.bg == 1) ? 22 : 10, nshort = (d.bg == 1) ? 66 : 50;
+    MIPHY_REQUIRE(d.in_len >= (bgK + 2) * d.Z && d.in_len <= nshort * d.Z, "ldpc_decode: desc %u: input length %u out of range", i, d.in_len);
+    MIPHY_REQUIRE(d.max_iter > 0, "ldpc_decode: desc %u: max_iter must be > 0", i);
+    MIPHY_REQUIRE(d.crc_poly == MIPHY_CRC_NONE || d.crc_poly <= MIPHY_CRC11, "ldpc_decode: desc %u: invalid CRC", i);
+    MIPHY_REQUIRE(d.nof_filler_bits < bgK * d.Z, "ldpc_decode: desc %u: invalid number of filler bits", i);
+  }
+  return MIPHY_OK;
+}
+
+// A class-sorted batch on the device: [descriptors | order | bundles], staged from one host image.
+struct class_arrays {
+  const miphy_ldpc_dec_desc* descs;
+  const uint32_t*            order;
+  const uint32_t*            bundles;
+};
+std::vector<uint8_t> class_image(const miphy_ldpc_dec_desc* descs, uint32_t n, const miphy_ldpc_classes& C)
+{
+  const size_t         b0 = sizeof(miphy_ldpc_dec_desc) * (size_t)n, b1 = 4 * (size_t)n, b2 = 4 * C.bundles.size();
+  std::vector<uint8_t> h(b0 + b1 + b2);
+  memcpy(h.data(), descs, b0);
+  memcpy(h.data() + b0, C.order.data(), b1);
+  if (b2)
+    memcpy(h.data() + b0 + b1, C.bundles.data(), b2);
+  return h;
+}
+class_arrays class_arrays_at(const void* d, uint32_t n)
+{
+  const uint8_t* b  = static_cast<const uint8_t*>(d);
+  const size_t   b0 = sizeof(miphy_ldpc_dec_desc) * (size_t)n;
+  return {reinterpret_cast<const miphy_ldpc_dec_desc*>(b), reinterpret_cast<const uint32_t*>(b + b0), reinterpret_cast<const uint32_t*>(b + b0 + 4 * (size_t)n)};
+}
+} // namespace
+
+// ---- per call: host descriptors are sorted into launch classes (the table of miphy_ldpc_plan_launches, scratch from the context); device-resident
+// descriptors, which the host cannot sort, and the forced kernels of the A-B knob are ONE launch for the whole batch -------------------------
+extern "C" int miphy_ldpc_decode_batch(miphy_ctx*                   ctx,
+                                       const miphy_ldpc_dec_desc*   descs,
+                                       int                          descs_on_device,
+                                       uint32_t                     n,
+                                       const int8_t*                llr,
+                                       uint8_t*                     out_bits,
+                                       int32_t*                     iters,
+                                       const miphy_ldpc_dec_limits* limits,
+                                       void*                        stream)
 {
   MIPHY_REQUIRE(ctx && descs && llr && out_bits && iters, "ldpc_decode: null argument");
   if (n == 0)
     return MIPHY_OK;
   hipStream_t s = (hipStream_t)stream;
+  int         rc;
   // Launch geometry: threads from the largest Z, LDS from the largest number of layers any codeblock can reach
-  // (nof_layers <= ceil((in_len + 2Z)/Z) - bg_K, ldpc_decoder_impl.cpp:101-114). Host descriptors are validated here
-  // (the reference asserts the same conditions, ldpc_decoder_impl.cpp:66-84); for device descriptors the caller
-  // vouches for validity and may pass `limits` (worst case assumed otherwise).
+  // (nof_layers <= ceil((in_len + 2Z)/Z) - bg_K, ldpc_decoder_impl.cpp:101-114). Host descriptors are validated here;
+  // for device descriptors the caller vouches for validity and may pass `limits` (worst case assumed otherwise).
   int    max_threads = 64;
   int    max_nodes[2] = {0, 0}; // per base graph: largest ceil((in_len + 2Z) / Z)
   auto   account      = [&](unsigned bg, unsigned Z, unsigned in_len) {
@@ -686,42 +718,32 @@ int miphy_ldpc_decode_launch(miphy_ctx*                   ctx,
     max_nodes[bg - 1] = nodes > max_nodes[bg - 1] ? nodes : max_nodes[bg - 1];
   };
   if (!descs_on_device) {
-    for (uint32_t i = 0; i < n; ++i) {
-      const miphy_ldpc_dec_desc& d = descs[i];
-      MIPHY_REQUIRE(d.bg == 1 || d.bg == 2, "ldpc_decode: desc %u: invalid base graph %u", i, d.bg);
-      MIPHY_REQUIRE(d.Z <= MIPHY_MAX_Z && ctx->h_tables->z_pos[d.Z] != 0xffff, "ldpc_decode: desc %u: invalid lifting size %u", i, d.Z);
-      const unsigned bgK = (d.bg == 1) ? 22 : 10, nshort = (d.bg == 1) ? 66 : 50;
-      MIPHY_REQUIRE(d.in_len >= (bgK + 2) * d.Z && d.in_len <= nshort * d.Z, "ldpc_decode: desc %u: input length %u out of range", i, d.in_len);
-      MIPHY_REQUIRE(d.max_iter > 0, "ldpc_decode: desc %u: max_iter must be > 0", i);
-      MIPHY_REQUIRE(d.crc_poly == MIPHY_CRC_NONE || d.crc_poly <= MIPHY_CRC11, "ldpc_decode: desc %u: invalid CRC", i);
-      MIPHY_REQUIRE(d.nof_filler_bits < bgK * d.Z, "ldpc_decode: desc %u: invalid number of filler bits", i);
-      account(d.bg, d.Z, d.in_len);
-    }
-    if (g_force_kernel == 0 || g_force_kernel >= 3) {
-      // host descriptors: sorted into launch classes (nothing is dematched by the decoder on this path: fuse_rdm comes with device
-      // descriptors only)
+    if ((rc = validate_descs(ctx, descs, n)))
+      return rc;
+    for (uint32_t i = 0; i < n; ++i)
+      account(descs[i].bg, descs[i].Z, descs[i].in_len);
+    if (g_force_kernel == 0 || g_force_kernel >= 3) { // host descriptors: sorted into launch classes
       miphy_ldpc_classes C;
       miphy_ldpc_build_classes(descs, n, nullptr, C);
-      const void *d_descs = nullptr, *d_order = nullptr, *d_bundles = nullptr;
-      int         rc;
-      if ((rc = miphy_stage_descs(ctx, descs, 0, sizeof(miphy_ldpc_dec_desc) * (size_t)n, s, &d_descs)))
+      const std::vector<uint8_t> img = class_image(descs, n, C);
+      const void*                d   = nullptr;
+      if ((rc = miphy_stage_descs(ctx, img.data(), 0, img.size(), s, &d)))
         return rc;
-      if ((rc = miphy_stage_descs(ctx, C.order.data(), 0, sizeof(uint32_t) * (size_t)n, s, &d_order)))
+      miphy_ldpc_launches T;
+      miphy_ldpc_plan_launches(ctx, C, false, T);
+      void* gmsg = nullptr;
+      if (T.gmsg_bytes && (rc = miphy_get_workspace(ctx, MIPHY_WS_LDPC_MSGS, T.gmsg_bytes, &gmsg)))
         return rc;
-      if (!C.bundles.empty() && (rc = miphy_stage_descs(ctx, C.bundles.data(), 0, sizeof(uint32_t) * C.bundles.size(), s, &d_bundles)))
+      if (T.side_streams && (rc = miphy_side_streams(ctx)))
         return rc;
-      if ((rc = miphy_ldpc_flags_reset(reset_slots, nof_reset_slots, harq_crc_ok, s)))
-        return rc;
-      return miphy_ldpc_decode_classes_launch(ctx, (const miphy_ldpc_dec_desc*)d_descs, C, (const uint32_t*)d_order, (const uint32_t*)d_bundles, llr, out_bits,
-                                              iters, harq_slot, harq_crc_ok, s, nullptr, nullptr, false);
+      const class_arrays a = class_arrays_at(d, n);
+      return miphy_ldpc_run_launches(ctx, T, a.descs, a.order, a.bundles, llr, out_bits, iters, nullptr, nullptr, nullptr, nullptr, gmsg, s);
     }
   } else if (limits) {
     MIPHY_REQUIRE(limits->max_Z >= 2 && limits->max_Z <= MIPHY_MAX_Z, "ldpc_decode: limits: invalid max_Z");
-    // the base graph of device descriptors is not visible here: size for those the caller names (bg_mask, default both)
-    if (bg_mask & 1)
-      account(1, limits->max_Z, limits->max_in_len);
-    if (bg_mask & 2)
-      account(2, limits->max_Z, limits->max_in_len);
+    // the base graph of device descriptors is not visible here: size for both
+    account(1, limits->max_Z, limits->max_in_len);
+    account(2, limits->max_Z, limits->max_in_len);
   } else {
     account(1, MIPHY_MAX_Z, 66 * MIPHY_MAX_Z);
     account(2, MIPHY_MAX_Z, 50 * MIPHY_MAX_Z);
@@ -740,8 +762,7 @@ int miphy_ldpc_decode_launch(miphy_ctx*                   ctx,
     max_lds          = lds > max_lds ? lds : max_lds;
   }
   const void* d_descs = nullptr;
-  int         rc      = miphy_stage_descs(ctx, descs, descs_on_device, sizeof(miphy_ldpc_dec_desc) * (size_t)n, s, &d_descs);
-  if (rc)
+  if ((rc = miphy_stage_descs(ctx, descs, descs_on_device, sizeof(miphy_ldpc_dec_desc) * (size_t)n, s, &d_descs)))
     return rc;
   // Kernel choice. The packed kernel (two check rows per lane, explicit messages in LDS) executes ~1.6x fewer instructions per
   // row but needs more LDS per codeblock; at low code rates / mid lifting sizes that leaves one small workgroup per CU, and the
@@ -772,8 +793,7 @@ int miphy_ldpc_decode_launch(miphy_ctx*                   ctx,
   // (more than ~6 layers at Z = 384) in global memory, where they cost an L2 round trip per layer visit but leave room for four
   // codeblocks per CU: measured 2.0x at rate 1/3, tools/ldpc_rate_sweep.py.
   const int  pk_waves   = pk_threads / 64;
-  const bool will_fuse  = fuse_rdm && ((uintptr_t)llr & 15) == 0;
-  auto       pk_per_cu  = [&](size_t lds) { return std::max(1, std::min((int)((size_t)160 * 1024 / (lds ? lds : 1)), miphy_ldpc_pk_waves_per_cu(will_fuse) / pk_waves)); };
+  auto       pk_per_cu  = [&](size_t lds) { return std::max(1, std::min((int)((size_t)160 * 1024 / (lds ? lds : 1)), miphy_ldpc_pk_waves_per_cu(false) / pk_waves)); };
   const bool pk_gmsg    = pk_ok && pk_per_cu(pk_lds_g) > pk_per_cu(pk_lds) && (g_force_kernel >= 2 || n > (uint32_t)(ctx->num_cus * pk_per_cu(pk_lds)));
   if (pk_gmsg)
     pk_lds = pk_lds_g;
@@ -790,80 +810,60 @@ int miphy_ldpc_decode_launch(miphy_ctx*                   ctx,
     use_pk = false;
   if (g_force_kernel >= 2)
     use_pk = pk_ok;
-  // The fused form needs 16-byte aligned soft buffers (its write-back is vectorised) and lifting sizes that are multiples of 16 (the
-  // caller vouches for that when it passes fuse_rdm); otherwise the dematcher runs on its own.
-  const bool fuse = fuse_rdm && use_pk && ((uintptr_t)llr & 15) == 0;
-  if (!fuse && (rc = miphy_ldpc_flags_reset(reset_slots, nof_reset_slots, harq_crc_ok, s)))
-    return rc;
-  if (fuse_rdm && !fuse) {
-    if ((rc = miphy_ldpc_rate_dematch_batch(ctx, fuse_rdm, 1, n, fuse_in, const_cast<int8_t*>(llr), fuse_rlim, s)))
-      return rc;
-  }
   if (use_pk) {
-    g_kernels_used |= MIPHY_LDPC_KERNEL_PACKED | (fuse ? MIPHY_LDPC_KERNEL_FUSED : 0u) | (pk_gmsg ? MIPHY_LDPC_KERNEL_GMSG : 0u);
-    return miphy_ldpc_pk_launch(ctx, (const miphy_ldpc_dec_desc*)d_descs, n, pk_threads, pk_lds, llr, out_bits, iters, nodes_all, harq_slot,
-                                harq_crc_ok, s, fuse ? fuse_rdm : nullptr, fuse ? fuse_in : nullptr, pk_gmsg ? pk_pairs : 0);
+    miphy_ldpc_launch L = {};
+    L.c.count           = n;
+    L.used              = MIPHY_LDPC_KERNEL_PACKED | (pk_gmsg ? MIPHY_LDPC_KERNEL_GMSG : 0u);
+    L.threads = pk_threads, L.nodes = nodes_all, L.parts = 1, L.gmsg_pairs = pk_gmsg ? pk_pairs : 0, L.lds = pk_lds;
+    L.grid              = miphy_ldpc_pk_grid(ctx, n, pk_threads, pk_lds, false);
+    void* gmsg          = nullptr;
+    if (pk_gmsg && (rc = miphy_get_workspace(ctx, MIPHY_WS_LDPC_MSGS, (size_t)L.grid * pk_waves * (size_t)pk_pairs * 256, &gmsg)))
+      return rc;
+    g_kernels_used.fetch_or(L.used);
+    return miphy_ldpc_pk_launch(ctx, L, (const miphy_ldpc_dec_desc*)d_descs, nullptr, llr, out_bits, iters, nullptr, nullptr, nullptr, nullptr, gmsg, s);
   }
   // Above the default 64 KB of dynamic LDS the limit has to be raised; it is a per-device attribute of the kernel, so it is set on
   // every such launch (a cache per thread would be wrong for a thread that drives several devices).
   if (max_lds > 48 * 1024) {
     MIPHY_HIP_CHECK(hipFuncSetAttribute((const void*)ldpc_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds));
   }
-  g_kernels_used |= MIPHY_LDPC_KERNEL_SCALAR;
-  hipLaunchKernelGGL(ldpc_decode_kernel, dim3(n), dim3(max_threads), max_lds, s, (const miphy_ldpc_dec_desc*)d_descs, ctx->d_tables, llr, out_bits, iters, nodes_all, harq_slot, harq_crc_ok, (const uint32_t*)nullptr);
+  g_kernels_used.fetch_or(MIPHY_LDPC_KERNEL_SCALAR);
+  hipLaunchKernelGGL(ldpc_decode_kernel, dim3(n), dim3(max_threads), max_lds, s, (const miphy_ldpc_dec_desc*)d_descs, ctx->d_tables, llr, out_bits, iters, nodes_all,
+                     (const uint32_t*)nullptr, (uint8_t*)nullptr, (const uint32_t*)nullptr);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }
 
-extern "C" int miphy_ldpc_decode_batch(miphy_ctx*                   ctx,
-                                       const miphy_ldpc_dec_desc*   descs,
-                                       int                          descs_on_device,
-                                       uint32_t                     n,
-                                       const int8_t*                llr,
-                                       uint8_t*                     out_bits,
-                                       int32_t*                     iters,
-                                       const miphy_ldpc_dec_limits* limits,
-                                       void*                        stream)
-{
-  return miphy_ldpc_decode_launch(ctx, descs, descs_on_device, n, llr, out_bits, iters, limits, nullptr, nullptr, stream);
-}
-
-// ---- prepared form: descriptors validated, sorted into launch classes and uploaded once; every run is launches only -------------------
+// ---- prepared form: descriptors validated, sorted into launch classes and uploaded once, the launch table and its message scratch
+// made once; every run is launches only -------------------------------------------------------------------------------------------
 struct miphy_ldpc_decode_plan {
-  miphy_ctx*         ctx;
-  uint32_t           n;
-  miphy_ldpc_classes cls; // classes only (order / bundles live in d_buf)
-  void*              d_buf;
-  const miphy_ldpc_dec_desc* d_descs;
-  const uint32_t*    d_order;
-  const uint32_t*    d_bundles;
+  miphy_ctx*          ctx;
+  miphy_ldpc_launches T;
+  void*               d_buf; // [descriptors | order | bundles | message scratch]
+  class_arrays        a;
+  void*               d_gmsg;
 };
 
 extern "C" int miphy_ldpc_decode_plan_create(miphy_ctx* ctx, const miphy_ldpc_dec_desc* descs, uint32_t n, miphy_ldpc_decode_plan** out)
 {
   MIPHY_REQUIRE(ctx && descs && out && n > 0, "miphy_ldpc_decode_plan_create: null argument or empty batch");
-  for (uint32_t i = 0; i < n; ++i) {
-    const miphy_ldpc_dec_desc& d = descs[i];
-    MIPHY_REQUIRE(d.bg == 1 || d.bg == 2, "ldpc_decode: desc %u: invalid base graph %u", i, d.bg);
-    MIPHY_REQUIRE(d.Z <= MIPHY_MAX_Z && ctx->h_tables->z_pos[d.Z] != 0xffff, "ldpc_decode: desc %u: invalid lifting size %u", i, d.Z);
-    const unsigned bgK = (d.bg == 1) ? 22 : 10, nshort = (d.bg == 1) ? 66 : 50;
-    MIPHY_REQUIRE(d.in_len >= (bgK + 2) * d.Z && d.in_len <= nshort * d.Z, "ldpc_decode: desc %u: input length %u out of range", i, d.in_len);
-    MIPHY_REQUIRE(d.max_iter > 0, "ldpc_decode: desc %u: max_iter must be > 0", i);
-    MIPHY_REQUIRE(d.crc_poly == MIPHY_CRC_NONE || d.crc_poly <= MIPHY_CRC11, "ldpc_decode: desc %u: invalid CRC", i);
-    MIPHY_REQUIRE(d.nof_filler_bits < bgK * d.Z, "ldpc_decode: desc %u: invalid number of filler bits", i);
-  }
+  int rc = validate_descs(ctx, descs, n);
+  if (rc)
+    return rc;
+  miphy_ldpc_classes C;
+  miphy_ldpc_build_classes(descs, n, nullptr, C);
   auto* p = new miphy_ldpc_decode_plan();
-  p->ctx = ctx, p->n = n, p->d_buf = nullptr;
-  miphy_ldpc_build_classes(descs, n, nullptr, p->cls);
-  const size_t b0 = sizeof(miphy_ldpc_dec_desc) * (size_t)n, b1 = 4 * (size_t)n, b2 = 4 * p->cls.bundles.size();
-  std::vector<uint8_t> host(b0 + b1 + b2);
-  memcpy(host.data(), descs, b0);
-  memcpy(host.data() + b0, p->cls.order.data(), b1);
-  if (b2)
-    memcpy(host.data() + b0 + b1, p->cls.bundles.data(), b2);
-  hipError_t e = hipMalloc(&p->d_buf, host.size());
+  p->ctx = ctx, p->d_buf = nullptr, p->d_gmsg = nullptr;
+  miphy_ldpc_plan_launches(ctx, C, false, p->T);
+  if (p->T.side_streams && (rc = miphy_side_streams(ctx))) {
+    delete p;
+    return rc;
+  }
+  const std::vector<uint8_t> img  = class_image(descs, n, C);
+  const size_t               off  = (img.size() + 255) & ~(size_t)255;
+  hipError_t                 e    = hipMalloc(&p->d_buf, off + p->T.gmsg_bytes);
   if (e == hipSuccess)
-    e = hipMemcpy(p->d_buf, host.data(), host.size(), hipMemcpyHostToDevice);
+    e = hipMemcpy(p->d_buf, img.data(), img.size(), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     miphy_set_error("miphy_ldpc_decode_plan_create: %s", hipGetErrorString(e));
     if (p->d_buf)
@@ -871,25 +871,22 @@ extern "C" int miphy_ldpc_decode_plan_create(miphy_ctx* ctx, const miphy_ldpc_de
     delete p;
     return MIPHY_EHIP;
   }
-  p->d_descs   = reinterpret_cast<const miphy_ldpc_dec_desc*>(p->d_buf);
-  p->d_order   = reinterpret_cast<const uint32_t*>((uint8_t*)p->d_buf + b0);
-  p->d_bundles = reinterpret_cast<const uint32_t*>((uint8_t*)p->d_buf + b0 + b1);
-  std::vector<uint32_t>().swap(p->cls.order);
-  std::vector<uint32_t>().swap(p->cls.bundles);
-  *out = p;
+  p->a      = class_arrays_at(p->d_buf, n);
+  p->d_gmsg = p->T.gmsg_bytes ? (uint8_t*)p->d_buf + off : nullptr;
+  *out      = p;
   return MIPHY_OK;
 }
 
 extern "C" int miphy_ldpc_decode_plan_run(miphy_ldpc_decode_plan* p, const int8_t* llr, uint8_t* out_bits, int32_t* iters, void* stream)
 {
   MIPHY_REQUIRE(p && llr && out_bits && iters, "miphy_ldpc_decode_plan_run: null argument");
-  return miphy_ldpc_decode_classes_launch(p->ctx, p->d_descs, p->cls, p->d_order, p->d_bundles, llr, out_bits, iters, nullptr, nullptr, (hipStream_t)stream,
-                                          nullptr, nullptr, false);
+  return miphy_ldpc_run_launches(p->ctx, p->T, p->a.descs, p->a.order, p->a.bundles, llr, out_bits, iters, nullptr, nullptr, nullptr, nullptr, p->d_gmsg,
+                                 (hipStream_t)stream);
 }
 
 extern "C" uint32_t miphy_ldpc_decode_plan_nof_launches(const miphy_ldpc_decode_plan* p)
 {
-  return p ? (uint32_t)p->cls.classes.size() : 0u;
+  return p ? (uint32_t)p->T.l.size() : 0u;
 }
 
 extern "C" void miphy_ldpc_decode_plan_destroy(miphy_ldpc_decode_plan* p)

@@ -634,49 +634,36 @@ uint32_t miphy_ldpc_pk_grid(const miphy_ctx* ctx, uint32_t n, int threads, size_
   return std::min<uint32_t>(n, (uint32_t)(ctx->num_cus * per_cu));
 }
 
-size_t miphy_ldpc_pk_gmsg_bytes(const miphy_ctx* ctx, uint32_t n, int threads, size_t lds, bool fused, int gmsg_pairs)
+int miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order, const int8_t* llr,
+                         uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot, uint8_t* harq_crc_ok, const miphy_ldpc_rdm_desc* d_rdm,
+                         const int8_t* rm_in, void* gmsg, hipStream_t s)
 {
-  return gmsg_pairs > 0 ? (size_t)miphy_ldpc_pk_grid(ctx, n, threads, lds, fused) * (threads / 64) * (size_t)gmsg_pairs * 256 : 0;
-}
-
-int miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_dec_desc* d_descs, uint32_t n, int threads, size_t lds, const int8_t* llr,
-                         uint8_t* out_bits, int32_t* iters, int nodes_all, const uint32_t* harq_slot, uint8_t* harq_crc_ok, hipStream_t s,
-                         const miphy_ldpc_rdm_desc* d_rdm, const int8_t* rm_in, int gmsg_pairs, const uint32_t* d_order, void* gmsg_buf, int parts, int lds_pairs)
-{
-  const bool fused = d_rdm != nullptr, gm = gmsg_pairs > 0;
-  const bool split = parts > 1;
-  MIPHY_REQUIRE(parts <= 1 || parts == 2 || parts == 4, "ldpc_decode: the latency form has two or four parts");
-  MIPHY_REQUIRE(!(split && gm), "ldpc_decode: the latency form keeps its messages in LDS");
-  if (split)
-    threads *= parts; // `threads` = the row-owning threads of a codeblock; `lds` already holds the exchange slots
-  MIPHY_REQUIRE(threads <= 1024, "ldpc_decode: workgroup of %d threads", threads);
-  const void* kern = parts == 4 ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 4> : (const void*)ldpc_decode_pk_kernel<false, false, 4>)
-                     : split    ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 2> : (const void*)ldpc_decode_pk_kernel<false, false, 2>)
+  // (the geometry is the launch table's: L.threads counts every part of the latency form, whose L.lds holds the exchange slots)
+  const bool fused = (L.used & MIPHY_LDPC_KERNEL_FUSED) != 0, gm = L.gmsg_pairs > 0;
+  MIPHY_REQUIRE(L.threads <= 1024, "ldpc_decode: workgroup of %d threads", L.threads);
+  const void* kern = L.parts == 4 ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 4> : (const void*)ldpc_decode_pk_kernel<false, false, 4>)
+                     : L.parts == 2 ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 2> : (const void*)ldpc_decode_pk_kernel<false, false, 2>)
                            : fused ? (gm ? (const void*)ldpc_decode_pk_kernel<true, true> : (const void*)ldpc_decode_pk_kernel<true, false>)
                                    : (gm ? (const void*)ldpc_decode_pk_kernel<false, true> : (const void*)ldpc_decode_pk_kernel<false, false>);
   // Above the default 64 KB of dynamic LDS the limit has to be raised; it is a per-device attribute of the kernel, so it is set on
   // every such launch (a cache per thread would be wrong for a thread that drives several devices).
-  if (lds > 48 * 1024) {
-    MIPHY_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (L.lds > 48 * 1024) {
+    MIPHY_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
   }
-  const uint32_t grid  = miphy_ldpc_pk_grid(ctx, n, threads, lds, fused, parts);
-  uint32_t*      queue = nullptr;
-  int            rc    = miphy_next_queue_counter(ctx, &queue);
+  uint32_t* queue = nullptr;
+  int       rc    = miphy_next_queue_counter(ctx, &queue);
   if (rc)
     return rc;
-  void* gmsg = gmsg_buf;
-  if (gm && !gmsg && (rc = miphy_get_workspace(ctx, miphy_ldpc_pk_gmsg_bytes(ctx, n, threads, lds, fused, gmsg_pairs), s, &gmsg, 3)))
-    return rc;
-#define PK_LAUNCH(F, G, ...)                                                                                                                         \
-  hipLaunchKernelGGL((ldpc_decode_pk_kernel<F, G, ##__VA_ARGS__>), dim3(grid), dim3(threads), lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, nodes_all, \
-                     harq_slot, harq_crc_ok, n, queue, d_rdm, rm_in, (uint32_t*)gmsg, gmsg_pairs, lds_pairs, d_order)
-  if (parts == 4 && fused)
+#define PK_LAUNCH(F, G, ...)                                                                                                                              \
+  hipLaunchKernelGGL((ldpc_decode_pk_kernel<F, G, ##__VA_ARGS__>), dim3(L.grid), dim3(L.threads), L.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, \
+                     L.nodes, harq_slot, harq_crc_ok, L.c.count, queue, d_rdm, rm_in, (uint32_t*)gmsg, L.gmsg_pairs, gm ? L.lds_pairs : 0, d_order)
+  if (L.parts == 4 && fused)
     PK_LAUNCH(true, false, 4);
-  else if (parts == 4)
+  else if (L.parts == 4)
     PK_LAUNCH(false, false, 4);
-  else if (split && fused)
+  else if (L.parts == 2 && fused)
     PK_LAUNCH(true, false, 2);
-  else if (split)
+  else if (L.parts == 2)
     PK_LAUNCH(false, false, 2);
   else if (fused && gm)
     PK_LAUNCH(true, true);

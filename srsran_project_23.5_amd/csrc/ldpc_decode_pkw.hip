@@ -318,64 +318,45 @@ size_t miphy_ldpc_pkw_lds_bytes(size_t soft_total, int pairs_all)
   return soft_total + (size_t)pairs_all * 256 + 512;
 }
 
-namespace {
-struct pkw_geometry {
-  bool     gm;
-  size_t   lds;
-  uint32_t grid;
-  int      pairs;
-};
-pkw_geometry pkw_geom(const miphy_ctx* ctx, uint32_t nof_bundles, int bgi, int lay, size_t soft_total, bool throughput_form)
+void miphy_ldpc_pkw_geometry(const miphy_ctx* ctx, bool throughput_form, miphy_ldpc_launch& L)
 {
-  pkw_geometry g;
-  g.pairs            = ctx->h_tables->pair_start[bgi][lay];
-  const size_t lds_l = miphy_ldpc_pkw_lds_bytes(soft_total, g.pairs), lds_g = miphy_ldpc_pkw_lds_bytes(soft_total, 0);
+  const miphy_ldpc_class& c     = L.c;
+  const int               pairs = ctx->h_tables->pair_start[c.bgi][c.lay];
+  const size_t            lds_l = miphy_ldpc_pkw_lds_bytes(c.soft_total, pairs), lds_g = miphy_ldpc_pkw_lds_bytes(c.soft_total, 0);
   // Wavefronts per CU: LDS and the 16 the register budget of the kernel allows. The messages move to global memory (one coalesced
   // dword per lane, edge pair and layer visit, re-read out of L2 an iteration later) where LDS would leave fewer than two wavefronts
   // per SIMD and the move buys residency.
   auto per_cu = [](size_t lds) { return std::max(1, std::min((int)((size_t)160 * 1024 / lds), 16)); };
   // ... and only where the launch has more bundles than stay resident with the messages in LDS: a launch that fits the chip anyway is a
   // latency chain, and a global round trip per layer visit would sit on it.
-  g.gm        = per_cu(lds_l) < 8 && per_cu(lds_g) > per_cu(lds_l) && (throughput_form || nof_bundles > (uint32_t)(ctx->num_cus * per_cu(lds_l)));
-  g.lds       = g.gm ? lds_g : lds_l;
-  g.grid      = std::min<uint32_t>(nof_bundles, (uint32_t)(ctx->num_cus * per_cu(g.lds)));
-  return g;
-}
-} // namespace
-
-size_t miphy_ldpc_pkw_gmsg_bytes(const miphy_ctx* ctx, uint32_t nof_bundles, int bgi, int lay, size_t soft_total, bool throughput_form)
-{
-  if (nof_bundles == 0)
-    return 0;
-  const pkw_geometry g = pkw_geom(ctx, nof_bundles, bgi, lay, soft_total, throughput_form);
-  return g.gm ? (size_t)g.grid * (size_t)g.pairs * 256 : 0;
+  const bool gm = per_cu(lds_l) < 8 && per_cu(lds_g) > per_cu(lds_l) && (throughput_form || c.bundle_count > (uint32_t)(ctx->num_cus * per_cu(lds_l)));
+  L.used        = MIPHY_LDPC_KERNEL_WAVE | (gm ? MIPHY_LDPC_KERNEL_GMSG : 0u);
+  L.threads     = 64;
+  L.lds         = gm ? lds_g : lds_l;
+  L.grid        = std::min<uint32_t>(c.bundle_count, (uint32_t)(ctx->num_cus * per_cu(L.lds)));
+  L.gmsg_pairs  = gm ? pairs : 0;
+  L.gmsg_bytes  = gm ? (size_t)L.grid * (size_t)pairs * 256 : 0;
 }
 
-int miphy_ldpc_pkw_launch(miphy_ctx* ctx, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order, const uint32_t* d_bundles, uint32_t nof_bundles,
-                          int bgi, int lay, size_t soft_total, const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot,
-                          uint8_t* harq_crc_ok, hipStream_t s, int* used_gmsg, void* gmsg_buf, bool throughput_form)
+int miphy_ldpc_pkw_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order, const uint32_t* d_bundles,
+                          const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot, uint8_t* harq_crc_ok, void* gmsg, hipStream_t s)
 {
-  if (nof_bundles == 0)
+  if (L.c.bundle_count == 0)
     return MIPHY_OK;
-  const pkw_geometry g = pkw_geom(ctx, nof_bundles, bgi, lay, soft_total, throughput_form);
-  if (used_gmsg)
-    *used_gmsg = g.gm ? 1 : 0;
-  const void* kern = g.gm ? (const void*)ldpc_decode_pkw_kernel<true> : (const void*)ldpc_decode_pkw_kernel<false>;
-  if (g.lds > 48 * 1024)
-    MIPHY_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
+  const bool  gm   = L.gmsg_pairs > 0;
+  const void* kern = gm ? (const void*)ldpc_decode_pkw_kernel<true> : (const void*)ldpc_decode_pkw_kernel<false>;
+  if (L.lds > 48 * 1024)
+    MIPHY_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
   uint32_t* queue = nullptr;
   int       rc    = miphy_next_queue_counter(ctx, &queue);
   if (rc)
     return rc;
-  void* gmsg = gmsg_buf;
-  if (g.gm && !gmsg && (rc = miphy_get_workspace(ctx, (size_t)g.grid * (size_t)g.pairs * 256, s, &gmsg, 3)))
-    return rc;
-  if (g.gm)
-    hipLaunchKernelGGL((ldpc_decode_pkw_kernel<true>), dim3(g.grid), dim3(64), g.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, lay, (int)soft_total,
-                       harq_slot, harq_crc_ok, d_order, d_bundles, nof_bundles, queue, (uint32_t*)gmsg, g.pairs);
+  if (gm)
+    hipLaunchKernelGGL((ldpc_decode_pkw_kernel<true>), dim3(L.grid), dim3(64), L.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, (int)L.c.lay,
+                       (int)L.c.soft_total, harq_slot, harq_crc_ok, d_order, d_bundles, L.c.bundle_count, queue, (uint32_t*)gmsg, L.gmsg_pairs);
   else
-    hipLaunchKernelGGL((ldpc_decode_pkw_kernel<false>), dim3(g.grid), dim3(64), g.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, lay, (int)soft_total,
-                       harq_slot, harq_crc_ok, d_order, d_bundles, nof_bundles, queue, (uint32_t*)nullptr, 0);
+    hipLaunchKernelGGL((ldpc_decode_pkw_kernel<false>), dim3(L.grid), dim3(64), L.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, (int)L.c.lay,
+                       (int)L.c.soft_total, harq_slot, harq_crc_ok, d_order, d_bundles, L.c.bundle_count, queue, (uint32_t*)nullptr, 0);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }

@@ -568,9 +568,9 @@ extern "C" int miphy_ldpc_rate_dematch_batch(miphy_ctx*                 ctx,
       return rc;
   }
   hipStream_t s       = (hipStream_t)stream;
-  const void* d_descs = nullptr;
-  int         rc      = miphy_stage_descs(ctx, descs, descs_on_device, sizeof(miphy_ldpc_rdm_desc) * (size_t)n, s, &d_descs);
-  if (rc)
+  const void* d_descs = descs;
+  int         rc;
+  if (!descs_on_device && (rc = miphy_stage_descs(ctx, descs, 0, sizeof(miphy_ldpc_rdm_desc) * (size_t)n, s, &d_descs)))
     return rc;
   // LDS staging buffer: the largest rate-matched length in the batch (known from host descriptors or `limits`), capped.
   uint32_t max_E = RDM_LDS_BYTES;

@@ -2,6 +2,7 @@
 #include "miphy_internal.h"
 #include "miphy_ext.h"
 #include "tables/nr_ldpc_tables.h"
+#include <algorithm>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstring>
@@ -298,19 +299,20 @@ int miphy_upload(miphy_ctx* ctx, void* dst, const void* src, size_t bytes, hipSt
   return MIPHY_OK;
 }
 
-int miphy_get_workspace(miphy_ctx* ctx, size_t bytes, hipStream_t s, void** out, int which)
+int miphy_get_workspace(miphy_ctx* ctx, miphy_workspace slot, size_t bytes, void** out)
 {
-  if (bytes > ctx->work_bytes[which]) {
-    MIPHY_HIP_CHECK(hipStreamSynchronize(s));
-    if (ctx->d_work[which])
-      MIPHY_HIP_CHECK(hipFree(ctx->d_work[which]));
-    ctx->d_work[which]     = nullptr;
-    ctx->work_bytes[which] = 0;
-    size_t want            = bytes + bytes / 4 + (1u << 20);
-    MIPHY_HIP_CHECK(hipMalloc(&ctx->d_work[which], want));
-    ctx->work_bytes[which] = want;
+  if (bytes > ctx->work_bytes[slot]) {
+    // the old block stays valid for what was enqueued or captured with it: freed in miphy_destroy. Doubling keeps the blocks held back
+    // smaller than the live one together.
+    const size_t want = std::max(bytes + bytes / 4 + (1u << 20), 2 * ctx->work_bytes[slot]);
+    void*        w    = nullptr;
+    MIPHY_HIP_CHECK(hipMalloc(&w, want));
+    if (ctx->d_work[slot])
+      ctx->ext->to_free.push_back(ctx->d_work[slot]);
+    ctx->d_work[slot]     = w;
+    ctx->work_bytes[slot] = want;
   }
-  *out = ctx->d_work[which];
+  *out = ctx->d_work[slot];
   return MIPHY_OK;
 }
 

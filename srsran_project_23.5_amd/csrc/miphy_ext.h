@@ -47,6 +47,14 @@ int  miphy_pdsch_encode_prepare(miphy_ctx* ctx, const miphy_pdsch_tb_desc* tbs, 
 int  miphy_pdsch_encode_prepared_run(miphy_pdsch_encode_prepared* p, const uint8_t* tb_in, uint8_t* codeword_out, hipStream_t s);
 void miphy_pdsch_encode_prepared_destroy(miphy_pdsch_encode_prepared* p);
 
+// Launch halves of miphy_pdsch_modulate_batch and miphy_dmrs_pdsch_map_batch (pdsch_mod.hip), for callers that hold device jobs, the
+// Gold tables (miphy_get_gold_tables) and the modulator's scratch of miphy_pdsch_modulate_scratch_bytes(n) bytes already.
+struct gold_tables;
+size_t miphy_pdsch_modulate_scratch_bytes(uint32_t n);
+int    miphy_pdsch_modulate_launch(const miphy_pdsch_mod_job* d_jobs, uint32_t n, const gold_tables* gt, const uint8_t* codewords, float* grid, void* seq,
+                                   hipStream_t s);
+int    miphy_dmrs_pdsch_map_launch(const miphy_dmrs_pdsch_job* d_jobs, uint32_t n, const gold_tables* gt, float* grid, hipStream_t s);
+
 // One codeblock of the transport-block level PDSCH encoder (pdsch_cb_encode.hip): assembly from the transport block, LDPC encoding and rate
 // matching in one kernel.
 struct miphy_pdsch_cb_desc {

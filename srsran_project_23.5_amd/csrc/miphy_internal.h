@@ -46,6 +46,17 @@ static inline __host__ __device__ int miphy_crc_zmask_index(int crc_id)
   return crc_id == 0 ? 0 : (crc_id == 1 ? 1 : (crc_id == 3 ? 2 : -1));
 }
 
+// Scratch workspaces of a context, one per user group: calls that run one inside another take different slots.
+enum miphy_workspace {
+  MIPHY_WS_GENERAL = 0,  // staged descriptors of the transport-block level entry points (PUSCH decode, PDSCH encode), the UL-SCH
+                         // demultiplexer's plans, the four-step DFT, the PBCH encoder
+  MIPHY_WS_PUSCH_PROC,   // intermediate buffers of miphy_pusch_process_batch (estimates, LLRs, EVM sums)
+  MIPHY_WS_OUTPUT,       // codewords of miphy_pdsch_process_batch, encoded PDCCH / PBCH bits, compacted results of miphy_pusch_process_batch
+  MIPHY_WS_LDPC_MSGS,    // check-to-variable messages of the LDPC decoder when they do not stay in LDS (per-call entry points)
+  MIPHY_WS_SEQUENCES,    // scrambling sequences of the PUSCH demodulator and of the PDSCH modulator (per-call entry point)
+  MIPHY_NOF_WORKSPACES
+};
+
 struct miphy_ctx_ext; // C++ side caches (twiddle tables, OFDM plans), see miphy_ext.h
 
 struct miphy_ctx {
@@ -59,10 +70,8 @@ struct miphy_ctx {
   size_t               staging_head;
   void*                ring_streams[4]; // streams that regions of the ring were staged for since its last wrap (the wrap waits for them)
   int                  nof_ring_streams; // 5 = more than four
-  void*                d_work[5];      // scratch workspaces, grown on demand: [0] the transport-block level entry points, DFT, polar;
-  size_t               work_bytes[5];  // [1] intermediate buffers of miphy_pusch_process_batch, [2] codewords of miphy_pdsch_process_batch,
-                                       // [3] check-to-variable messages of the LDPC decoder when they do not stay in LDS,
-                                       // [4] scrambling sequences of the PUSCH demodulator
+  void*                d_work[MIPHY_NOF_WORKSPACES];     // scratch workspaces, grown on demand (miphy_get_workspace)
+  size_t               work_bytes[MIPHY_NOF_WORKSPACES];
   int                  num_cus; // compute units of the device (persistent-kernel grid sizing)
   uint32_t*            d_queue; // work-queue counters of the persistent kernels: a ring of MIPHY_NOF_QUEUE_COUNTERS words, one per launch
   uint32_t             queue_next;
@@ -121,20 +130,6 @@ int miphy_stage_descs(miphy_ctx* ctx, const void* descs, int on_device, size_t b
 // the ring are copied directly and the stream is synchronised, as every upload was before.)
 int miphy_upload(miphy_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s);
 
-// Decoder launch, ONE kernel launch for the whole batch: device-resident descriptors (which the host cannot sort) and the forced kernels
-// of miphy_debug_force_ldpc_kernel. Host descriptors are sorted into launch classes instead (below) unless a kernel is forced.
-// fuse_rdm / fuse_in / fuse_rlim (device descriptors with the same index as descs): every codeblock is a first transmission that
-// can be rate-dematched while the decoder loads it (conditions in ldpc_decode_pk.hip; sch.hip checks them); `llr` is then the HARQ
-// soft-buffer array the dematched codeblocks are written to. When the packed kernel is not the one selected, the rate dematcher runs
-// as its own launch first -- the result is the same either way.
-int miphy_ldpc_decode_launch(miphy_ctx* ctx, const miphy_ldpc_dec_desc* descs, int descs_on_device, uint32_t n, const int8_t* llr,
-                             uint8_t* out_bits, int32_t* iters, const miphy_ldpc_dec_limits* limits, const uint32_t* harq_slot,
-                             uint8_t* harq_crc_ok, void* stream, const miphy_ldpc_rdm_desc* fuse_rdm = nullptr,
-                             const int8_t* fuse_in = nullptr, const miphy_ldpc_rdm_limits* fuse_rlim = nullptr,
-                             int bg_mask = 3 /* device descriptors: bit 0 / 1 = base graph 1 / 2 occurs */,
-                             const uint32_t* reset_slots = nullptr, uint32_t nof_reset_slots = 0 /* CRC flags to clear before decoding (device
-                             array): new transmissions. Skipped when the decoder dematches itself -- it then writes every flag either way */);
-
 #ifdef __cplusplus
 #include <vector>
 // Launch classes of a batch whose descriptors the host can see (ldpc_decode.hip): codeblocks sorted so that each class shares a
@@ -158,38 +153,60 @@ struct miphy_ldpc_classes {
 };
 // fusable: optional flag per codeblock ("the decoder may dematch it"); descriptors must be valid (validated by the caller).
 void miphy_ldpc_build_classes(const miphy_ldpc_dec_desc* descs, uint32_t n, const uint8_t* fusable, miphy_ldpc_classes& C);
-// One launch per class. d_order / d_bundles = device copies of C.order / C.bundles. d_rdm / rm_in: rate-dematcher descriptors (same
-// index as d_descs) and rate-matched input for the fused classes; allow_fuse = false runs them unfused (the caller has dematched).
-int miphy_ldpc_decode_classes_launch(miphy_ctx* ctx, const miphy_ldpc_dec_desc* d_descs, const miphy_ldpc_classes& C, const uint32_t* d_order,
-                                     const uint32_t* d_bundles, const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot,
-                                     uint8_t* harq_crc_ok, hipStream_t s, const miphy_ldpc_rdm_desc* d_rdm, const int8_t* rm_in, bool allow_fuse);
-bool miphy_ldpc_scalar_forced(); // miphy_debug_force_ldpc_kernel(1): nothing is dematched inside the decoder then
+// One decoder launch per class, its geometry decided on the host once (miphy_ldpc_plan_launches) and enqueued by miphy_ldpc_run_launches.
+struct miphy_ldpc_launch {
+  miphy_ldpc_class c;
+  unsigned         used;       // MIPHY_LDPC_KERNEL_*: SCALAR, WAVE or PACKED names the kernel, the other bits its form
+  int              stream;     // 0 = the caller's, 1 .. = the context's side streams
+  int              threads;    // workgroup size (the latency form: every part)
+  int              nodes;      // variable nodes a codeblock can reach: the kernels size their arrays by it
+  int              parts;      // packed kernel: 1, or 2 / 4 in the latency form
+  int              gmsg_pairs; // message dwords per lane in global memory (0: all in LDS)
+  int              lds_pairs;  // ... and those that stay in LDS in front of them (a layer boundary of the base graph)
+  size_t           lds;
+  uint32_t         grid;
+  bool             ordered;    // decodes order[c.first ...] (false: the codeblocks in array order)
+  size_t           gmsg_off, gmsg_bytes; // the launch's part of the message scratch
+};
+struct miphy_ldpc_launches {
+  std::vector<miphy_ldpc_launch> l;
+  size_t                         gmsg_bytes   = 0;     // message scratch of all launches together (they run side by side)
+  bool                           side_streams = false; // launches fork to the context's side streams (miphy_side_streams first)
+  bool                           scalar       = false; // the one-row-per-lane kernel is forced: nothing is dematched in the decoder
+};
+// Host only: the launch table of the classes C (their order / bundles are device arrays by then). fuse: the fused classes dematch while
+// they load (the caller then passes rate-dematcher descriptors to the run). The debug knobs of miphy_debug_force_ldpc_kernel and
+// miphy_debug_set_ldpc_class_streams are read here, and nowhere else.
+void miphy_ldpc_plan_launches(const miphy_ctx* ctx, const miphy_ldpc_classes& C, bool fuse, miphy_ldpc_launches& T);
+// Enqueues the table on `s`: the fork to the side streams (created by then), one launch per class, the join -- on every path after the
+// fork. d_order / d_bundles = device copies of C.order / C.bundles; gmsg = T.gmsg_bytes of message scratch; d_rdm / rm_in: rate-dematcher
+// descriptors (same index as d_descs) and rate-matched input of the fused classes.
+int miphy_ldpc_run_launches(miphy_ctx* ctx, const miphy_ldpc_launches& T, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order,
+                            const uint32_t* d_bundles, const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot,
+                            uint8_t* harq_crc_ok, const miphy_ldpc_rdm_desc* d_rdm, const int8_t* rm_in, void* gmsg, hipStream_t s);
 int miphy_ldpc_flags_reset(const uint32_t* d_slots, uint32_t n, uint8_t* harq_crc_ok, hipStream_t s);
-// Wave kernel (ldpc_decode_pkw.hip).
-int miphy_ldpc_pkw_launch(miphy_ctx* ctx, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order, const uint32_t* d_bundles, uint32_t nof_bundles,
-                          int bgi, int lay, size_t soft_total, const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot,
-                          uint8_t* harq_crc_ok, hipStream_t s, int* used_gmsg, void* gmsg_buf = nullptr,
-                          bool throughput_form = false /* A-B knob: geometry of a launch that fills the chip, whatever its size */);
-size_t miphy_ldpc_pkw_gmsg_bytes(const miphy_ctx* ctx, uint32_t nof_bundles, int bgi, int lay, size_t soft_total, bool throughput_form = false);
+// Wave kernel (ldpc_decode_pkw.hip): geometry of L.c (lds, grid, messages in global memory or not), and its launch. throughput_form (A-B
+// knob): the geometry of a launch that fills the chip, whatever its size.
+void miphy_ldpc_pkw_geometry(const miphy_ctx* ctx, bool throughput_form, miphy_ldpc_launch& L);
+int  miphy_ldpc_pkw_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order,
+                           const uint32_t* d_bundles, const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot,
+                           uint8_t* harq_crc_ok, void* gmsg, hipStream_t s);
+// Packed (two rows per lane) kernel (ldpc_decode_pk.hip): LDS bytes of a geometry (pairs_all = 0: messages in global memory; parts = 2 / 4:
+// + exchange slots of the latency form), wavefronts per CU its register budget allows, resident workgroups of a launch, and the launch of
+// L.c.count codeblocks (d_order: codeblocks d_order[0 .. count) of the arrays, null: the first count). d_rdm / rm_in with FUSED only.
+size_t   miphy_ldpc_pk_lds_bytes(int bgK, int lay, size_t Zt, int pairs_all, int parts = 1);
+int      miphy_ldpc_pk_waves_per_cu(bool fused, int parts = 1);
+uint32_t miphy_ldpc_pk_grid(const miphy_ctx* ctx, uint32_t n, int threads, size_t lds, bool fused, int parts = 1);
+int      miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order,
+                              const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot, uint8_t* harq_crc_ok,
+                              const miphy_ldpc_rdm_desc* d_rdm, const int8_t* rm_in, void* gmsg, hipStream_t s);
 #endif
 
-// Returns a device scratch buffer of at least `bytes` (reallocated, after a stream sync, when it has to grow).
-int miphy_get_workspace(miphy_ctx* ctx, size_t bytes, hipStream_t s, void** out, int which = 0);
+// A device scratch buffer of at least `bytes` in the context's workspace `slot`. A slot that has to grow gets a new block of at least
+// twice the size; the old one is kept until miphy_destroy (work enqueued or captured earlier may still use it), so nothing waits.
+int miphy_get_workspace(miphy_ctx* ctx, miphy_workspace slot, size_t bytes, void** out);
 
-// Packed (two rows per lane) LDPC decoder kernel, ldpc_decode_pk.hip.
-size_t miphy_ldpc_pk_lds_bytes(int bgK, int lay, size_t Zt, int pairs_all, int parts = 1); // pairs_all = 0: messages in global memory; parts = 2 / 4: + exchange slots of the latency form
-int    miphy_ldpc_pk_waves_per_cu(bool fused, int parts = 1);
-int    miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_dec_desc* d_descs, uint32_t n, int threads, size_t lds, const int8_t* llr,
-                            uint8_t* out_bits, int32_t* iters, int nodes_all, const uint32_t* harq_slot, uint8_t* harq_crc_ok, hipStream_t s,
-                            const miphy_ldpc_rdm_desc* d_rdm = nullptr, const int8_t* rm_in = nullptr, int gmsg_pairs = 0,
-                            const uint32_t* d_order = nullptr /* the launch decodes codeblocks d_order[0 .. n) of the arrays */,
-                            void* gmsg_buf = nullptr /* message scratch of miphy_ldpc_pk_gmsg_bytes() bytes; null: the context's workspace */,
-                            int parts = 1 /* latency form: 2 or 4 times the wavefronts per codeblock (lds from miphy_ldpc_pk_lds_bytes(..., parts)) */,
-                            int lds_pairs = 0 /* with gmsg_pairs > 0: message dwords per lane that stay in LDS in front of the global ones (a layer boundary of the base graph) */);
-// Resident workgroups of such a launch and the bytes of global message scratch it needs (0 with the messages in LDS).
-uint32_t miphy_ldpc_pk_grid(const miphy_ctx* ctx, uint32_t n, int threads, size_t lds, bool fused, int parts = 1);
-size_t   miphy_ldpc_pk_gmsg_bytes(const miphy_ctx* ctx, uint32_t n, int threads, size_t lds, bool fused, int gmsg_pairs);
-// The context's side streams and fork / join events, created on first use.
+// The context's side streams and fork / join events, created on first use (before a run of a table that uses them).
 int miphy_side_streams(miphy_ctx* ctx);
 // The next work-queue counter of the context (zero: every launch leaves its counter cleared).
 int miphy_next_queue_counter(miphy_ctx* ctx, uint32_t** out);

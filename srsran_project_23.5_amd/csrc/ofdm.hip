@@ -497,7 +497,7 @@ extern "C" int miphy_dft_batch(miphy_ctx* ctx, uint32_t size, int inverse, uint3
     if ((rc = miphy_get_twiddles(ctx, N1, &tw1)) || (rc = miphy_get_twiddles(ctx, N2, &tw2)) || (rc = miphy_get_twiddles(ctx, size, &twN)))
       return rc;
     void* tmp = nullptr;
-    if ((rc = miphy_get_workspace(ctx, (size_t)n * size * 8, s, &tmp)))
+    if ((rc = miphy_get_workspace(ctx, MIPHY_WS_GENERAL, (size_t)n * size * 8, &tmp)))
       return rc;
     const size_t lds1 = FS_TILE * fft_lds_bytes(N1), lds2 = FS_TILE * fft_lds_bytes(N2);
     if (inverse) {

@@ -604,14 +604,24 @@ extern "C" int miphy_pdsch_modulate_batch(miphy_ctx* ctx, const miphy_pdsch_mod_
   rc                 = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pdsch_mod_job) * (size_t)n, s, &d_jobs);
   if (rc)
     return rc;
-  void* seq = nullptr; // scrambling sequences of the transmissions (the workspace the PUSCH demodulator keeps its sequences in), then their 14 symbol prefixes
-  const size_t seq_bytes = (size_t)n * PDSCH_SEQ_STRIDE * sizeof(uint32_t);
-  if ((rc = miphy_get_workspace(ctx, seq_bytes + (size_t)n * 14 * sizeof(int), s, &seq, 4)))
+  void* seq = nullptr; // (the workspace the PUSCH demodulator keeps its sequences in)
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, miphy_pdsch_modulate_scratch_bytes(n), &seq)))
     return rc;
-  int* prefix = reinterpret_cast<int*>(static_cast<uint8_t*>(seq) + seq_bytes);
-  hipLaunchKernelGGL(pdsch_seq_kernel, dim3(n), dim3(512), 0, s, (const miphy_pdsch_mod_job*)d_jobs, gt, (uint32_t*)seq, prefix);
-  hipLaunchKernelGGL(pdsch_mod_kernel, dim3(n, 14), dim3(256), 0, s, (const miphy_pdsch_mod_job*)d_jobs, gt, codewords, (float2*)grid, (const uint32_t*)seq,
-                     (const int*)prefix);
+  return miphy_pdsch_modulate_launch((const miphy_pdsch_mod_job*)d_jobs, n, gt, codewords, grid, seq, s);
+}
+
+size_t miphy_pdsch_modulate_scratch_bytes(uint32_t n)
+{
+  return (size_t)n * PDSCH_SEQ_STRIDE * sizeof(uint32_t) + (size_t)n * 14 * sizeof(int);
+}
+
+int miphy_pdsch_modulate_launch(const miphy_pdsch_mod_job* d_jobs, uint32_t n, const gold_tables* gt, const uint8_t* codewords, float* grid, void* seq,
+                                hipStream_t s)
+{
+  // seq: scrambling sequences of the transmissions, then their 14 symbol prefixes
+  int* prefix = reinterpret_cast<int*>(static_cast<uint8_t*>(seq) + (size_t)n * PDSCH_SEQ_STRIDE * sizeof(uint32_t));
+  hipLaunchKernelGGL(pdsch_seq_kernel, dim3(n), dim3(512), 0, s, d_jobs, gt, (uint32_t*)seq, prefix);
+  hipLaunchKernelGGL(pdsch_mod_kernel, dim3(n, 14), dim3(256), 0, s, d_jobs, gt, codewords, (float2*)grid, (const uint32_t*)seq, (const int*)prefix);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }
@@ -640,7 +650,12 @@ extern "C" int miphy_dmrs_pdsch_map_batch(miphy_ctx* ctx, const miphy_dmrs_pdsch
   rc                 = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_dmrs_pdsch_job) * (size_t)n, s, &d_jobs);
   if (rc)
     return rc;
-  hipLaunchKernelGGL(dmrs_pdsch_kernel, dim3(n, 14), dim3(256), 0, s, (const miphy_dmrs_pdsch_job*)d_jobs, gt, (float2*)grid);
+  return miphy_dmrs_pdsch_map_launch((const miphy_dmrs_pdsch_job*)d_jobs, n, gt, grid, s);
+}
+
+int miphy_dmrs_pdsch_map_launch(const miphy_dmrs_pdsch_job* d_jobs, uint32_t n, const gold_tables* gt, float* grid, hipStream_t s)
+{
+  hipLaunchKernelGGL(dmrs_pdsch_kernel, dim3(n, 14), dim3(256), 0, s, d_jobs, gt, (float2*)grid);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }
@@ -672,7 +687,7 @@ extern "C" int miphy_pdcch_process_batch(miphy_ctx* ctx, const miphy_pdcch_pdu* 
     enc_bytes += (108u * al + 15u) & ~15u;
   }
   void* work = nullptr;
-  int   rc   = miphy_get_workspace(ctx, enc_bytes + 64, s, &work, 2);
+  int   rc   = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, enc_bytes + 64, &work);
   if (rc)
     return rc;
   const void* d_pdus = nullptr;
@@ -713,7 +728,7 @@ extern "C" int miphy_ssb_process_batch(miphy_ctx* ctx, const miphy_ssb_pdu* pdus
     msgs[i] = q.msg;
   }
   void* work = nullptr; // encoded PBCH bits, 864 per block
-  int   rc   = miphy_get_workspace(ctx, (size_t)n * 864 + 64, s, &work, 2);
+  int   rc   = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, (size_t)n * 864 + 64, &work);
   if (rc)
     return rc;
   if ((rc = miphy_pbch_encode_batch(ctx, msgs.data(), n, static_cast<uint8_t*>(work), s)))

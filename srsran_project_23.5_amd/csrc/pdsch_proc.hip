@@ -2,6 +2,7 @@
 // Behaviour contract: lib/phy/upper/channel_processors/pdsch_processor_impl.cpp:110-305 (process = encode + modulate + put_dmrs,
 // with the restrictions of assert_pdu :143-196). Host-side composition of miphy_pdsch_encode_batch, miphy_pdsch_modulate_batch and
 // miphy_dmrs_pdsch_map_batch with the parameters the reference derives from the PDU.
+#include "gold_device.h"
 #include "miphy_ext.h"
 #include <cmath>
 #include <vector>
@@ -89,7 +90,7 @@ extern "C" int miphy_pdsch_process_batch(miphy_ctx* ctx, const miphy_pdsch_pdu* 
   if (rc)
     return rc;
   void* work = nullptr; // codewords (one bit per byte) in a workspace of the context
-  if ((rc = miphy_get_workspace(ctx, cw_bytes + 64, s, &work, 2)))
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, cw_bytes + 64, &work)))
     return rc;
   uint8_t* d_cw = static_cast<uint8_t*>(work);
   if ((rc = miphy_pdsch_encode_batch(ctx, tb.data(), n, tb_in, d_cw, s)))
@@ -99,17 +100,19 @@ extern "C" int miphy_pdsch_process_batch(miphy_ctx* ctx, const miphy_pdsch_pdu* 
   return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s);
 }
 
-// ---- prepared form: PDU validation, segmentation and every descriptor upload happen once; a run is the seven launches of the chain, nothing
-// staged, no host synchronisation -- for allocations that repeat slot after slot (and for batches whose descriptors exceed the staging ring,
+// ---- prepared form: PDU validation, segmentation, every descriptor upload and the scratch happen once; a run is the seven launches of the
+// chain, nothing staged or allocated, no host synchronisation -- for allocations that repeat slot after slot (and for batches whose descriptors exceed the staging ring,
 // where the per-call form has to wait for its upload).
 struct miphy_pdsch_process_plan {
   miphy_ctx*                   ctx;
   uint32_t                     n;
   miphy_pdsch_encode_prepared* enc;
-  void*                        d_buf; // [modulator jobs | DM-RS jobs | codewords]
+  const gold_tables*           gt;
+  void*                        d_buf; // [modulator jobs | DM-RS jobs | codewords | the modulator's sequences and prefixes]
   const miphy_pdsch_mod_job*   d_mj;
   const miphy_dmrs_pdsch_job*  d_dj;
   uint8_t*                     d_cw;
+  void*                        d_seq;
 };
 
 extern "C" int miphy_pdsch_process_plan_create(miphy_ctx* ctx, const miphy_pdsch_pdu* pdus, uint32_t n, miphy_pdsch_process_plan** out)
@@ -133,12 +136,13 @@ extern "C" int miphy_pdsch_process_plan_create(miphy_ctx* ctx, const miphy_pdsch
   }
   auto* p = new miphy_pdsch_process_plan();
   p->ctx = ctx, p->n = n, p->enc = nullptr, p->d_buf = nullptr;
-  if ((rc = miphy_pdsch_encode_prepare(ctx, tb.data(), n, &p->enc))) {
+  if ((rc = miphy_get_gold_tables(ctx, &p->gt)) || (rc = miphy_pdsch_encode_prepare(ctx, tb.data(), n, &p->enc))) {
     delete p;
     return rc;
   }
   const size_t b0 = ((size_t)n * sizeof(miphy_pdsch_mod_job) + 15) & ~(size_t)15, b1 = ((size_t)n * sizeof(miphy_dmrs_pdsch_job) + 15) & ~(size_t)15;
-  hipError_t   e  = hipMalloc(&p->d_buf, b0 + b1 + cw_bytes + 64);
+  const size_t b2 = (cw_bytes + 64 + 255) & ~(size_t)255;
+  hipError_t   e  = hipMalloc(&p->d_buf, b0 + b1 + b2 + miphy_pdsch_modulate_scratch_bytes(n));
   if (e == hipSuccess)
     e = hipMemcpy(p->d_buf, mj.data(), (size_t)n * sizeof(miphy_pdsch_mod_job), hipMemcpyHostToDevice);
   if (e == hipSuccess)
@@ -153,8 +157,9 @@ extern "C" int miphy_pdsch_process_plan_create(miphy_ctx* ctx, const miphy_pdsch
   }
   p->d_mj = reinterpret_cast<const miphy_pdsch_mod_job*>(p->d_buf);
   p->d_dj = reinterpret_cast<const miphy_dmrs_pdsch_job*>((uint8_t*)p->d_buf + b0);
-  p->d_cw = (uint8_t*)p->d_buf + b0 + b1;
-  *out    = p;
+  p->d_cw  = (uint8_t*)p->d_buf + b0 + b1;
+  p->d_seq = (uint8_t*)p->d_buf + b0 + b1 + b2;
+  *out     = p;
   return MIPHY_OK;
 }
 
@@ -165,9 +170,9 @@ extern "C" int miphy_pdsch_process_plan_run(miphy_pdsch_process_plan* p, const u
   int         rc;
   if ((rc = miphy_pdsch_encode_prepared_run(p->enc, tb_in, p->d_cw, s)))
     return rc;
-  if ((rc = miphy_pdsch_modulate_batch(p->ctx, p->d_mj, 1, p->n, p->d_cw, grid, s)))
+  if ((rc = miphy_pdsch_modulate_launch(p->d_mj, p->n, p->gt, p->d_cw, grid, p->d_seq, s)))
     return rc;
-  return miphy_dmrs_pdsch_map_batch(p->ctx, p->d_dj, 1, p->n, grid, s);
+  return miphy_dmrs_pdsch_map_launch(p->d_dj, p->n, p->gt, grid, s);
 }
 
 extern "C" void miphy_pdsch_process_plan_destroy(miphy_pdsch_process_plan* p)

@@ -1074,7 +1074,7 @@ extern "C" int miphy_pbch_encode_batch(miphy_ctx* ctx, const miphy_pbch_msg* msg
     return rc;
   hipStream_t s  = (hipStream_t)stream;
   void*       ws = nullptr;
-  if ((rc = miphy_get_workspace(ctx, ap.size(), s, &ws)))
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_GENERAL, ap.size(), &ws)))
     return rc;
   if ((rc = miphy_upload(ctx, ws, ap.data(), ap.size(), s))) // `ap` is a local buffer
     return rc;

@@ -799,7 +799,7 @@ extern "C" int miphy_pusch_demodulate_batch_ex(miphy_ctx* ctx, const miphy_pusch
   void*        work      = nullptr;
   const size_t seq_bytes = (size_t)n * SEQ_STRIDE * sizeof(uint32_t);
   const size_t evm_bytes = evm_sums ? (size_t)n * 14 * DEMOD_MAX_CHUNKS * sizeof(float) : 0;
-  if ((rc = miphy_get_workspace(ctx, seq_bytes + evm_bytes, s, &work, 4)))
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, seq_bytes + evm_bytes, &work)))
     return rc;
   uint32_t* seq      = static_cast<uint32_t*>(work);
   float*    evm_part = evm_sums ? reinterpret_cast<float*>(static_cast<uint8_t*>(work) + seq_bytes) : nullptr;

@@ -148,7 +148,7 @@ extern "C" int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pd
   // context; the estimator scalars go straight to the caller's array.
   const size_t evm_bytes = evm_out ? (size_t)n * 14 * 4 : 0, ph_bytes = (ph.size() * 2 + 15) & ~(size_t)15, nre_bytes = evm_out ? (size_t)n * 4 : 0;
   void*        work      = nullptr;
-  int          rc        = miphy_get_workspace(ctx, ce_elems * 8 + llr_bytes + sch_bytes + evm_bytes + ph_bytes + nre_bytes + 256, s, &work, 1);
+  int          rc        = miphy_get_workspace(ctx, MIPHY_WS_PUSCH_PROC, ce_elems * 8 + llr_bytes + sch_bytes + evm_bytes + ph_bytes + nre_bytes + 256, &work);
   if (rc)
     return rc;
   float*    d_ce  = static_cast<float*>(work);
@@ -178,7 +178,7 @@ extern "C" int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pd
   if (tb.empty())
     return MIPHY_OK;
   void* rws = nullptr;
-  if ((rc = miphy_get_workspace(ctx, tb.size() * sizeof(miphy_pusch_result), s, &rws, 2)))
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, tb.size() * sizeof(miphy_pusch_result), &rws)))
     return rc;
   if ((rc = miphy_pusch_decode_batch(ctx, tb.data(), (uint32_t)tb.size(), d_llr, harq_softbits, harq_msgs, harq_crc_ok, tb_out, (miphy_pusch_result*)rws, s)))
     return rc;

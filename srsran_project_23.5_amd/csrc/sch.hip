@@ -306,14 +306,20 @@ struct pusch_decode_build {
   // Launches: chunks of at most 65535 codeblocks (whole transport blocks), each sorted into the decoder's launch classes
   // (miphy_ldpc_build_classes: by lifting size, base graph, reachable layers, dematch-while-loading or not).
   struct chunk {
-    uint32_t           t0, t1, c0, c1;
-    miphy_ldpc_classes cls;
-    uint32_t           order_off, bundle_off, rdm_nf_off; // positions in the concatenated `order` / `bundles` / `rdm_nf` arrays
+    uint32_t            t0, t1, c0, c1;
+    miphy_ldpc_classes  cls; // (classes only: order and bundles are in the arrays below)
+    uint32_t            order_off, bundle_off, rdm_nf_off; // positions in the concatenated `order` / `bundles` / `rdm_nf` arrays
+    miphy_ldpc_launches launches[2]; // decoder launch tables (pusch_decode_launches): [0] after the dematcher's own launch, [1] dematching the fused classes
   };
   std::vector<chunk>               chunks;
   std::vector<uint32_t>            order, bundles;    // all chunks, indices relative to the chunk's first codeblock
   std::vector<miphy_ldpc_rdm_desc> rdm_nf;            // dematcher descriptors of the codeblocks of classes that are not fused, chunk after chunk
   bool                             all_fused = true;  // every class of every chunk dematches in the decoder
+  bool                             any_fused = false; // some class does (launches[1] exists)
+  bool                             scalar    = false; // the one-row-per-lane kernel is forced: nothing is dematched in the decoder
+  bool                             side_streams = false; // some launch table forks to the context's side streams
+  size_t                           gmsg_bytes   = 0;     // decoder message scratch: the largest any table needs (chunks run one after another)
+  uint32_t                         nof_reset    = 0;     // new transmissions: reset_slots.size() (a plan releases the vector)
 };
 
 // Device-side view of a staged build (pointers into one buffer).
@@ -457,12 +463,28 @@ int build_pusch_decode(const miphy_pusch_tb_desc* tbs, uint32_t n, pusch_decode_
     for (uint32_t k = 0; k < ch.cls.nof_unfused; ++k)
       b.rdm_nf.push_back(b.rdm[ch.c0 + ch.cls.order[k]]);
     b.all_fused &= ch.cls.nof_unfused == 0;
+    b.any_fused |= ch.cls.nof_unfused < ch.c1 - ch.c0;
     std::vector<uint32_t>().swap(ch.cls.order); // kept in b.order
     std::vector<uint32_t>().swap(ch.cls.bundles);
     t0 = ch.t1;
     b.chunks.push_back(std::move(ch));
   }
+  b.nof_reset = (uint32_t)b.reset_slots.size();
   return MIPHY_OK;
+}
+
+// The decoder's launch tables of every chunk: without dematching in the decoder and, where a class can, with it (a run chooses by the
+// alignment of the soft buffers it is given).
+void pusch_decode_launches(const miphy_ctx* ctx, pusch_decode_build& b)
+{
+  for (pusch_decode_build::chunk& ch : b.chunks)
+    for (int f = 0; f < (b.any_fused ? 2 : 1); ++f) {
+      miphy_ldpc_launches& T = ch.launches[f];
+      miphy_ldpc_plan_launches(ctx, ch.cls, f == 1, T);
+      b.scalar       = T.scalar;
+      b.side_streams = b.side_streams || T.side_streams;
+      b.gmsg_bytes   = std::max(b.gmsg_bytes, T.gmsg_bytes);
+    }
 }
 
 size_t pusch_decode_bytes(const pusch_decode_build& b)
@@ -500,17 +522,17 @@ pusch_decode_dev layout_pusch_decode(const pusch_decode_build& b, uint8_t* h, ui
 // soft buffers, LDPC decoding (codeblocks already decoded are skipped), transport-block assembly + TB CRC + result records.
 // Launches of at most 65535 codeblocks each; transport blocks are never split across launches.
 int launch_pusch_decode(miphy_ctx* ctx, const pusch_decode_build& b, const pusch_decode_dev& v, uint32_t n, const int8_t* llrs, int8_t* harq_softbits,
-                        uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results, hipStream_t s,
+                        uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results, void* gmsg, hipStream_t s,
                         hipEvent_t* ev = nullptr /* optional: 4 events around the dematch launches / the decoder launches / the assembly */)
 {
   int rc;
   miphy_ldpc_rdm_limits rlim = {b.max_E};
   // Dematching inside the decoder needs 16-byte aligned soft buffers (its write-back is vectorised; HARQ_CB_STRIDE keeps the slots so)
-  const bool allow_fuse = ((uintptr_t)harq_softbits & 15) == 0 && !miphy_ldpc_scalar_forced();
+  const bool allow_fuse = ((uintptr_t)harq_softbits & 15) == 0 && !b.scalar;
   if (ev)
     MIPHY_HIP_CHECK(hipEventRecord(ev[0], s));
   // the CRC flags of the new transmissions of the call (a decoder that dematches itself writes the flags of its codeblocks either way)
-  if (!(b.all_fused && allow_fuse) && (rc = miphy_ldpc_flags_reset(v.reset, (uint32_t)b.reset_slots.size(), harq_crc_ok, s)))
+  if (!(b.all_fused && allow_fuse) && (rc = miphy_ldpc_flags_reset(v.reset, b.nof_reset, harq_crc_ok, s)))
     return rc;
   for (const pusch_decode_build::chunk& ch : b.chunks) { // rate dematching as launches of its own where the decoder does not do it
     if (!allow_fuse)
@@ -523,8 +545,8 @@ int launch_pusch_decode(miphy_ctx* ctx, const pusch_decode_build& b, const pusch
   if (ev)
     MIPHY_HIP_CHECK(hipEventRecord(ev[1], s));
   for (const pusch_decode_build::chunk& ch : b.chunks) {
-    if ((rc = miphy_ldpc_decode_classes_launch(ctx, v.dec + ch.c0, ch.cls, v.order + ch.order_off, v.bundles + ch.bundle_off, harq_softbits, harq_msgs,
-                                               v.iters + ch.c0, v.slots + ch.c0, harq_crc_ok, s, v.rdm + ch.c0, llrs, allow_fuse)))
+    if ((rc = miphy_ldpc_run_launches(ctx, ch.launches[allow_fuse && b.any_fused], v.dec + ch.c0, v.order + ch.order_off, v.bundles + ch.bundle_off,
+                                      harq_softbits, harq_msgs, v.iters + ch.c0, v.slots + ch.c0, harq_crc_ok, v.rdm + ch.c0, llrs, gmsg, s)))
       return rc;
   }
   if (ev)
@@ -566,12 +588,18 @@ extern "C" int miphy_pusch_decode_batch(miphy_ctx*                 ctx,
   const size_t         bytes = pusch_decode_bytes(b);
   std::vector<uint8_t> host(bytes);
   void*                wsv = nullptr;
-  if ((rc = miphy_get_workspace(ctx, bytes, s, &wsv)))
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_GENERAL, bytes, &wsv)))
     return rc;
   const pusch_decode_dev v = layout_pusch_decode(b, host.data(), (uint8_t*)wsv);
   if ((rc = miphy_upload(ctx, wsv, host.data(), v.staged, s))) // through the pinned ring: the stream is not waited for
     return rc;
-  return launch_pusch_decode(ctx, b, v, n, llrs, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, s);
+  pusch_decode_launches(ctx, b);
+  void* gmsg = nullptr;
+  if (b.gmsg_bytes && (rc = miphy_get_workspace(ctx, MIPHY_WS_LDPC_MSGS, b.gmsg_bytes, &gmsg)))
+    return rc;
+  if (b.side_streams && (rc = miphy_side_streams(ctx)))
+    return rc;
+  return launch_pusch_decode(ctx, b, v, n, llrs, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, gmsg, s);
 }
 
 // ---- prepared form: the segmentation and the descriptor upload happen once, every run is launches only (no host
@@ -579,9 +607,10 @@ extern "C" int miphy_pusch_decode_batch(miphy_ctx*                 ctx,
 struct miphy_pusch_decode_plan {
   miphy_ctx*         ctx;
   uint32_t           n;
-  pusch_decode_build b; // host side kept for the launch limits (the descriptor vectors are released after staging)
+  pusch_decode_build b; // chunks, launch tables and sizes (the descriptor vectors are released after staging)
   pusch_decode_dev   v;
-  void*              d_buf;
+  void*              d_buf; // [staged descriptors | iterations, checksum parts | decoder message scratch]
+  void*              d_gmsg;
   uint32_t           ncb;
   std::vector<hipEvent_t> events; // timing: 4 per run, ring of events.size() / 4 runs
   uint32_t           timed_runs;
@@ -591,18 +620,23 @@ extern "C" int miphy_pusch_decode_plan_create(miphy_ctx* ctx, const miphy_pusch_
 {
   MIPHY_REQUIRE(ctx && tbs && out && n > 0, "miphy_pusch_decode_plan_create: null argument or empty batch");
   auto* p = new miphy_pusch_decode_plan();
-  p->ctx = ctx, p->n = n, p->d_buf = nullptr, p->timed_runs = 0;
+  p->ctx = ctx, p->n = n, p->d_buf = nullptr, p->d_gmsg = nullptr, p->timed_runs = 0;
   int rc = build_pusch_decode(tbs, n, p->b);
   p->ncb = (uint32_t)p->b.dec.size();
   if (rc) {
     delete p;
     return rc;
   }
-  const size_t         bytes = pusch_decode_bytes(p->b);
+  pusch_decode_launches(ctx, p->b);
+  if (p->b.side_streams && (rc = miphy_side_streams(ctx))) {
+    delete p;
+    return rc;
+  }
+  const size_t         bytes = pusch_decode_bytes(p->b), gmsg_off = (bytes + 255) & ~(size_t)255;
   std::vector<uint8_t> host(bytes);
-  hipError_t           e = hipMalloc(&p->d_buf, bytes);
+  hipError_t           e = hipMalloc(&p->d_buf, gmsg_off + p->b.gmsg_bytes);
   if (e != hipSuccess) {
-    miphy_set_error("miphy_pusch_decode_plan_create: hipMalloc(%zu) -> %s", bytes, hipGetErrorString(e));
+    miphy_set_error("miphy_pusch_decode_plan_create: hipMalloc(%zu) -> %s", gmsg_off + p->b.gmsg_bytes, hipGetErrorString(e));
     delete p;
     return MIPHY_EHIP;
   }
@@ -614,15 +648,20 @@ extern "C" int miphy_pusch_decode_plan_create(miphy_ctx* ctx, const miphy_pusch_
     delete p;
     return MIPHY_EHIP;
   }
-  // only sizes and limits are needed from here on
-  std::vector<miphy_ldpc_rdm_desc>().swap(p->b.rdm);
-  std::vector<miphy_ldpc_rdm_desc>().swap(p->b.rdm_nf);
-  std::vector<miphy_ldpc_dec_desc>().swap(p->b.dec);
-  std::vector<uint32_t>().swap(p->b.slots);
-  std::vector<uint32_t>().swap(p->b.cb_tb);
-  std::vector<uint32_t>().swap(p->b.order);
-  std::vector<uint32_t>().swap(p->b.bundles);
-  std::vector<uint8_t>().swap(p->b.fusable);
+  p->d_gmsg = p->b.gmsg_bytes ? (uint8_t*)p->d_buf + gmsg_off : nullptr;
+  // the runs need the chunks, their tables and the sizes only
+  pusch_decode_build& b = p->b;
+  std::vector<miphy_ldpc_rdm_desc>().swap(b.rdm);
+  std::vector<miphy_ldpc_rdm_desc>().swap(b.rdm_nf);
+  std::vector<miphy_ldpc_dec_desc>().swap(b.dec);
+  std::vector<uint32_t>().swap(b.slots);
+  std::vector<uint32_t>().swap(b.reset_slots);
+  std::vector<tb_asm_desc>().swap(b.asmd);
+  std::vector<uint32_t>().swap(b.cb_tb);
+  std::vector<uint32_t>().swap(b.cbw);
+  std::vector<uint32_t>().swap(b.order);
+  std::vector<uint32_t>().swap(b.bundles);
+  std::vector<uint8_t>().swap(b.fusable);
   *out = p;
   return MIPHY_OK;
 }
@@ -643,7 +682,7 @@ extern "C" int miphy_pusch_decode_plan_run(miphy_pusch_decode_plan* p,
     ev                 = &p->events[(size_t)(p->timed_runs % cap) * 4];
     ++p->timed_runs;
   }
-  return launch_pusch_decode(p->ctx, p->b, p->v, p->n, llrs, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, (hipStream_t)stream, ev);
+  return launch_pusch_decode(p->ctx, p->b, p->v, p->n, llrs, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, p->d_gmsg, (hipStream_t)stream, ev);
 }
 
 extern "C" int miphy_pusch_decode_plan_enable_timing(miphy_pusch_decode_plan* p, uint32_t max_runs)
@@ -694,7 +733,7 @@ extern "C" uint32_t miphy_pusch_decode_plan_nof_launches(const miphy_pusch_decod
   uint32_t n = 0;
   if (p)
     for (const auto& ch : p->b.chunks)
-      n += (uint32_t)ch.cls.classes.size();
+      n += (uint32_t)ch.launches[0].l.size();
   return n;
 }
 
@@ -837,7 +876,7 @@ extern "C" int miphy_pdsch_encode_batch(miphy_ctx* ctx, const miphy_pdsch_tb_des
     return rc;
   const size_t bytes = pdsch_encode_bytes(b);
   void*        wsv   = nullptr;
-  if ((rc = miphy_get_workspace(ctx, bytes, s, &wsv)))
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_GENERAL, bytes, &wsv)))
     return rc;
   std::vector<uint8_t>   host(bytes);
   const pdsch_encode_dev v = layout_pdsch_encode(b, host.data(), (uint8_t*)wsv);

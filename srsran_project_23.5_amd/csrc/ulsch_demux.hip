@@ -193,7 +193,7 @@ extern "C" int miphy_ulsch_demultiplex_batch(miphy_ctx* ctx, const miphy_ulsch_d
   hipStream_t  s     = (hipStream_t)stream;
   const size_t bytes = n * (sizeof(ulsch_plan) + sizeof(demux_dev_job)) + 64;
   void*        ws    = nullptr;
-  int          rc    = miphy_get_workspace(ctx, bytes, s, &ws, 0);
+  int          rc    = miphy_get_workspace(ctx, MIPHY_WS_GENERAL, bytes, &ws);
   if (rc)
     return rc;
   auto* d_plans = static_cast<ulsch_plan*>(ws);

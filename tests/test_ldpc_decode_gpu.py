@@ -470,9 +470,11 @@ def test_many_launches_queued_back_to_back(ctx, ldpc_kernel):
         base += int(sizes[l])
 
 
-def test_prepared_plan_matches_the_batch_call(ctx, ldpc_kernel):
-    """miphy_ldpc_decode_plan_*: the class-sorted launches of a heterogeneous batch prepared once and run twice (the second time on
-    other inputs) give the oracle's results; the plan reports one launch per class."""
+def test_prepared_plan_matches_the_batch_call(ldpc_kernel):
+    """miphy_ldpc_decode_plan_*: the class-sorted launches of a heterogeneous batch prepared once, captured in a HIP graph on the plan's
+    first run and replayed after a larger per-call decode has grown the context's workspaces, then run again on other inputs, give the
+    oracle's results; the plan reports one launch per class, and in the throughput form keeps messages in its own global scratch. A
+    context of its own: the session's may hold large workspaces already."""
     import torch
     import miphy
     rng = np.random.default_rng(29)
@@ -485,28 +487,52 @@ def test_prepared_plan_matches_the_batch_call(ctx, ldpc_kernel):
         descs[i] = (c["bg"], c["crc"] if c["crc"] >= 0 else miphy.CRC_NONE, c["Z"], c["max_iter"], c["nf"], c["llr"].size, c.get("flags", 0), llr_off, out_off)
         llr_off += c["llr"].size
         out_off += (BG_K[c["bg"]] * c["Z"] + 7) // 8
-    plan = miphy.LdpcDecodePlan(ctx, descs)
-    assert 2 <= plan.nof_launches() <= 60
-    for rep in range(2):
-        if rep == 1:  # same geometry, other soft bits: sign flips keep the zero / infinity structure of every case
-            for c in cases:
-                flip = rng.random(c["llr"].size) < 0.03
-                c["llr"] = np.where(flip, -c["llr"], c["llr"]).astype(np.int8)
-        llr_d = torch.from_numpy(np.concatenate([c["llr"] for c in cases])).cuda()
-        out_d = torch.full((out_off,), 0x5A, dtype=torch.uint8, device="cuda")
-        it_d = torch.full((n,), -7, dtype=torch.int32, device="cuda")
-        kernels_used()
-        plan.run(llr_d, out_d, it_d)
+    ctx = miphy.Context(0)
+    try:
+        plan = miphy.LdpcDecodePlan(ctx, descs)
+        assert 2 <= plan.nof_launches() <= 60
+        for rep in range(2):
+            if rep == 1:  # same geometry, other soft bits: sign flips keep the zero / infinity structure of every case
+                for c in cases:
+                    flip = rng.random(c["llr"].size) < 0.03
+                    c["llr"] = np.where(flip, -c["llr"], c["llr"]).astype(np.int8)
+            llr_d = torch.from_numpy(np.concatenate([c["llr"] for c in cases])).cuda()
+            out_d = torch.full((out_off,), 0x5A, dtype=torch.uint8, device="cuda")
+            it_d = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            kernels_used()
+            if rep == 0:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    plan.run(llr_d, out_d, it_d, torch.cuda.current_stream())
+                used = kernels_used()
+                # a larger per-call decode of the same codeblocks, four times over, into buffers of its own
+                big = np.concatenate([descs] * 4)
+                for k in range(4):
+                    big[k * n:(k + 1) * n]["out_offset"] += k * out_off
+                out_big = torch.zeros(4 * out_off, dtype=torch.uint8, device="cuda")
+                ctx.ldpc_decode_batch(big, llr_d, out_big, torch.zeros(4 * n, dtype=torch.int32, device="cuda"))
+                torch.cuda.synchronize()
+                g.replay()
+            else:
+                plan.run(llr_d, out_d, it_d)
+                used = kernels_used()
+            torch.cuda.synchronize()
+            assert (used == SCALAR) if ldpc_kernel == "scalar" else (used & PACKED and used & WAVE and not used & SCALAR), used
+            assert bool(used & SPLIT) == (ldpc_kernel in ("auto", "packed", "latency2"))  # (the plan is class-sorted whatever single-launch kernel is forced)
+            if ldpc_kernel == "throughput":
+                assert used & GMSG, used
+            out, its = out_d.cpu().numpy(), it_d.cpu().numpy()
+            for i, c in enumerate(cases):
+                if c.get("flags", 0) & 1:
+                    continue  # covered by run_batch
+                nb = (BG_K[c["bg"]] * c["Z"] + 7) // 8
+                ito, oo = o_ldpc_decode(c["bg"], c["Z"], c["llr"], c["nf"], c["crc"], c["max_iter"], out_init=np.full(nb, 0x5A, np.uint8))
+                o0 = int(descs[i]["out_offset"])
+                assert ito == its[i] and np.array_equal(oo, out[o0:o0 + nb]), (rep, i, c["bg"], c["Z"], ito, int(its[i]))
+            if rep == 0:
+                del g
+        plan.close()
+    finally:
         torch.cuda.synchronize()
-        used = kernels_used()
-        assert (used == SCALAR) if ldpc_kernel == "scalar" else (used & PACKED and used & WAVE and not used & SCALAR), used
-        assert bool(used & SPLIT) == (ldpc_kernel in ("auto", "packed", "latency2"))  # (the plan is class-sorted whatever single-launch kernel is forced)
-        out, its = out_d.cpu().numpy(), it_d.cpu().numpy()
-        for i, c in enumerate(cases):
-            if c.get("flags", 0) & 1:
-                continue  # covered by run_batch
-            nb = (BG_K[c["bg"]] * c["Z"] + 7) // 8
-            ito, oo = o_ldpc_decode(c["bg"], c["Z"], c["llr"], c["nf"], c["crc"], c["max_iter"], out_init=np.full(nb, 0x5A, np.uint8))
-            o0 = int(descs[i]["out_offset"])
-            assert ito == its[i] and np.array_equal(oo, out[o0:o0 + nb]), (rep, i, c["bg"], c["Z"], ito, int(its[i]))
-    plan.close()
+        ctx.close()

@@ -76,14 +76,38 @@ def test_batch_matches_oracle_chain(ctx):
     for i, (p, g) in enumerate(zip(pdus, want)):
         o = int(p["grid_offset"])
         assert np.array_equal(got[o:o + g.size].view(np.uint32), g.reshape(-1).view(np.uint32)), i
-    # the prepared plan (descriptors uploaded once) gives the same grid, run after run
-    plan = miphy.PdschProcessPlan(ctx, pdus)
-    for _ in range(2):
+    # the prepared plan (descriptors uploaded once) gives the same grid, run after run: on a context of its own, its first run captured in a
+    # HIP graph, replayed after a per-call batch of the PDUs repeated has grown that context's workspaces, then run directly
+    pctx = miphy.Context(0)
+    try:
+        plan = miphy.PdschProcessPlan(pctx, pdus)
+        tb_d = torch.from_numpy(tb_all).cuda()
         gp = torch.zeros(grid_off, dtype=torch.complex64, device="cuda")
-        plan.run(torch.from_numpy(tb_all).cuda(), gp)
         torch.cuda.synchronize()
-        assert np.array_equal(gp.cpu().numpy().view(np.uint32), got.view(np.uint32))
-    plan.close()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            plan.run(tb_d, gp, torch.cuda.current_stream())
+        reps = 3
+        big = np.concatenate([pdus] * reps)
+        for k in range(reps):
+            big[k * len(pdus):(k + 1) * len(pdus)]["grid_offset"] += k * grid_off
+        gbig = torch.zeros(reps * grid_off, dtype=torch.complex64, device="cuda")
+        pctx.pdsch_process_batch(big, tb_d, gbig)
+        torch.cuda.synchronize()
+        assert np.array_equal(gbig.cpu().numpy().view(np.uint32), np.tile(got, reps).view(np.uint32))
+        for run in range(3):
+            gp.zero_()
+            if run < 2:
+                graph.replay()
+            else:
+                plan.run(tb_d, gp)
+            torch.cuda.synchronize()
+            assert np.array_equal(gp.cpu().numpy().view(np.uint32), got.view(np.uint32)), run
+        del graph
+        plan.close()
+    finally:
+        torch.cuda.synchronize()
+        pctx.close()
     # a second call reuses the work buffer; one PDU alone gives the same REs
     gd2 = torch.zeros(want[2].size, dtype=torch.complex64, device="cuda")
     one = pdus[2:3].copy()

@@ -152,6 +152,34 @@ def test_compact_estimate_matches_oracle(ctx, mod, ports, cdm, type2, nprb, star
     got = out.cpu().numpy()
     assert np.array_equal(got[pad:pad + exp.size], exp)
     assert np.all(got[:pad] == 99) and np.all(got[pad + exp.size:] == 99)
+    if device_jobs and nprb == 273:
+        # captured once it has run at its size on a context of its own, the call stays valid after a larger call has grown that context's
+        # sequence workspace
+        gctx = miphy.Context(0)
+        try:
+            jobs_d, sc_d = torch.from_numpy(jobs.view(np.uint8)).cuda(), torch.from_numpy(sc).cuda()
+            gctx.pusch_demodulate_batch(jobs_d, g, h, sc_d, out)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                gctx.pusch_demodulate_batch(jobs_d, g, h, sc_d, out, torch.cuda.current_stream())
+            stride = (exp.size + 15) // 16 * 16
+            many = np.repeat(jobs, 64)
+            many["llr_offset"] = np.arange(64) * stride
+            out_many = torch.zeros(64 * stride, dtype=torch.int8, device="cuda")
+            gctx.pusch_demodulate_batch(many, g, h, sc_d, out_many)
+            torch.cuda.synchronize()
+            assert np.array_equal(out_many.cpu().numpy().reshape(64, stride)[:, :exp.size], np.tile(exp, (64, 1)))
+            out.fill_(99)
+            graph.replay()
+            torch.cuda.synchronize()
+            got = out.cpu().numpy()
+            assert np.array_equal(got[pad:pad + exp.size], exp)
+            assert np.all(got[:pad] == 99) and np.all(got[pad + exp.size:] == 99)
+            del graph
+        finally:
+            torch.cuda.synchronize()
+            gctx.close()
 
 
 def test_rejections(ctx):
