@@ -808,6 +808,81 @@ int miphy_pucch_process_batch(miphy_ctx* ctx, const miphy_pucch_job* jobs, int j
                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * PRACH detector and generator  --  replace srsran::prach_detector::detect and srsran::prach_generator::generate
+ *   lib/phy/upper/channel_processors/prach_detector_simple_impl.cpp:35-169 (RSSI, per preamble: correlation in the frequency domain,
+ *   unnormalised IDFT, peak of |c|^2, metric peak / (rssi preamble_power L L) against 0.07, delay sign and window),
+ *   lib/phy/upper/channel_processors/prach_generator_impl.cpp:105-301 (closed-form y_u,v, logical root index modulo the table size),
+ *   lib/ran/prach/prach_cyclic_shifts.cpp (N_CS), lib/ran/prach/prach_preamble_information.cpp (L, RA subcarrier spacing, N_CP).
+ * One job is one PRACH occasion: the detector reads one symbol of L = 839 (formats 0..3) or 139 (the others) cf_t at symbol_offset in
+ * `symbols` -- prach_buffer::get_symbol(0, 0, 0, 0), one port, no combining -- and tests the preamble indices start_preamble_index ..
+ * start_preamble_index + nof_preamble_indices - 1. Unrestricted sets only. Formats and RA subcarrier spacings are numbered like the
+ * reference's enums (MIPHY_PRACH_FORMAT_*, ra_scs 0..3 = 15..120 kHz, read for short formats only).
+ * `results[i]` gets what the detector derives per occasion: the linear RSSI, delay_n_maximum (the smaller of the cyclic prefix in
+ * samples at ra_scs * idft_size and, for N_CS != 0, N_CS idft_size / L), N_CS and whether the N_CS bound was the limiting one (then
+ * time_advance_max = from_seconds(delay_n_maximum / sampling rate), else the cyclic prefix). `preambles` gets one record per
+ * requested preamble index from preamble_offset, detected or not: the index of the peak, delay_n (the peak index, or peak index -
+ * idft_size above idft_size / 2), the peak power (power_dB = 10 log10 of it), the metric, and `detected` = 1 only when the metric is not
+ * below 0.07 and |delay_n| < delay_n_maximum; the reference's result lists those in preamble-index order, with time_advance =
+ * from_seconds(delay_n / sampling rate) and snr_dB = 0. An RSSI that is not a normal float (an all-zero symbol) gives records with
+ * detected = 0 and zero index, power and metric.
+ * idft_size: 1536 or 3072 (the reference asserts a multiple of 1536; these are the ones one LDS pass transforms).
+ * Host jobs are checked first (MIPHY_EINVAL, nothing enqueued) against the reference's assertions: a format it serves (and ra_scs
+ * 0..3 for a short one), an unrestricted set, a zone whose N_CS is not reserved (0..15), start + number <= 64, idft_size; a device job
+ * that fails them is skipped (nothing of it is written). n == 0 enqueues nothing. The call only enqueues and uses no scratch, so it
+ * can be captured in a HIP graph (once the context holds the twiddles of the IDFT size: any earlier call with it). */
+enum {
+  MIPHY_PRACH_FORMAT_0 = 0, MIPHY_PRACH_FORMAT_1, MIPHY_PRACH_FORMAT_2, MIPHY_PRACH_FORMAT_3, MIPHY_PRACH_FORMAT_A1, MIPHY_PRACH_FORMAT_A2,
+  MIPHY_PRACH_FORMAT_A3, MIPHY_PRACH_FORMAT_B1, MIPHY_PRACH_FORMAT_B4, MIPHY_PRACH_FORMAT_C0, MIPHY_PRACH_FORMAT_C2, MIPHY_PRACH_FORMAT_A1_B1,
+  MIPHY_PRACH_FORMAT_A2_B2, MIPHY_PRACH_FORMAT_A3_B3, MIPHY_PRACH_NOF_FORMATS
+};
+#define MIPHY_PRACH_MAX_PREAMBLES 64
+
+typedef struct {
+  uint32_t format;                /* MIPHY_PRACH_FORMAT_* */
+  uint32_t ra_scs;                /* short formats: 0..3 = 15, 30, 60, 120 kHz */
+  uint32_t root_sequence_index;   /* logical; root_sequence_index + preamble offset wraps modulo 838 / 138 */
+  uint32_t zero_correlation_zone; /* 0..15 */
+  uint32_t restricted_set;        /* 0 = unrestricted (the only one served) */
+  uint32_t start_preamble_index;
+  uint32_t nof_preamble_indices;  /* 0..64, start + number <= 64 */
+  uint32_t idft_size;             /* 1536 or 3072 */
+  uint32_t symbol_offset;         /* cf_t offset of the symbol in `symbols` */
+  uint32_t preamble_offset;       /* record offset of the first preamble result in `preambles` */
+} miphy_prach_job;
+
+typedef struct {
+  float    rssi;            /* linear; rssi_dB = 10 log10 */
+  uint32_t delay_n_maximum; /* samples of the IDFT grid */
+  uint32_t n_cs;
+  uint32_t n_cs_limited;    /* 1: delay_n_maximum comes from N_CS, 0: from the cyclic prefix */
+} miphy_prach_result;
+
+typedef struct {
+  uint32_t peak_index;
+  int32_t  delay_n;    /* signed */
+  float    peak_power; /* max |c|^2 */
+  float    metric;     /* peak_power / (rssi preamble_power L L) */
+  uint32_t detected;
+} miphy_prach_preamble_result;
+
+int miphy_prach_detect_batch(miphy_ctx* ctx, const miphy_prach_job* jobs, int jobs_on_device, uint32_t n, const float* symbols /* device cf_t */,
+                             miphy_prach_result* results /* device, n */, miphy_prach_preamble_result* preambles /* device */, void* stream);
+
+/* Frequency-domain preambles y_u,v of n (format, root_sequence_index, zero_correlation_zone, preamble_index): L cf_t each at out_offset
+ * (cf_t units) in `out`. Same checks and conventions as above (restricted_set must be 0; ra_scs plays no part). */
+typedef struct {
+  uint32_t format;
+  uint32_t root_sequence_index;
+  uint32_t zero_correlation_zone;
+  uint32_t restricted_set;
+  uint32_t preamble_index; /* 0..63 */
+  uint32_t out_offset;     /* cf_t offset in `out` */
+} miphy_prach_gen_job;
+
+int miphy_prach_generate_batch(miphy_ctx* ctx, const miphy_prach_gen_job* jobs, int jobs_on_device, uint32_t n, float* out /* device cf_t */,
+                               void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * PDSCH encoder (whole transport blocks)  --  replaces srsran::pdsch_encoder::encode
  *   include/srsran/phy/upper/channel_processors/pdsch_encoder.h, lib/phy/upper/channel_processors/pdsch_encoder_impl.cpp:28-65
  *   (segment_tx: TB CRC16/24A, CB CRC24B, zero padding, fillers -> LDPC encode -> rate match into the codeword),

@@ -32,6 +32,7 @@
 #include "srsran/ran/pucch/pucch_info.h"
 #include "srsran/ran/pusch/ulsch_info.h"
 #include "srsran/ran/ssb_mapping.h"
+#include "srsran/ran/prach/prach_preamble_information.h"
 #include "srsran/ran/precoding/precoding_codebooks.h"
 #include "srsran/phy/upper/rx_softbuffer.h"
 #include "srsran/phy/upper/rx_softbuffer_pool.h"
@@ -42,6 +43,7 @@
 #include "srsran/phy/upper/signal_processors/port_channel_estimator.h"
 #include "srsran/phy/upper/signal_processors/signal_processor_factories.h"
 #include "srsran/support/error_handling.h"
+#include "srsran/support/math_utils.h"
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -1309,6 +1311,198 @@ create_pucch_processor_factory_hip(std::shared_ptr<context> c, const srsran::cha
                                    std::shared_ptr<srsran::pucch_processor_factory> cpu_factory = nullptr)
 {
   return std::make_shared<pucch_processor_factory_hip>(std::move(c), dims, std::move(cpu_factory));
+}
+
+// ---------------------------------------------------------------------------------------------------------------- PRACH
+static_assert(static_cast<unsigned>(srsran::prach_format_type::three) == MIPHY_PRACH_FORMAT_3 &&
+                  static_cast<unsigned>(srsran::prach_format_type::A1) == MIPHY_PRACH_FORMAT_A1 &&
+                  static_cast<unsigned>(srsran::prach_format_type::B4) == MIPHY_PRACH_FORMAT_B4 &&
+                  static_cast<unsigned>(srsran::prach_format_type::A3_B3) == MIPHY_PRACH_FORMAT_A3_B3 &&
+                  static_cast<unsigned>(srsran::prach_format_type::invalid) == MIPHY_PRACH_NOF_FORMATS,
+              "MIPHY_PRACH_FORMAT_* follows srsran::prach_format_type");
+static_assert(static_cast<unsigned>(srsran::prach_subcarrier_spacing::kHz120) == 3 && static_cast<unsigned>(srsran::restricted_set_config::UNRESTRICTED) == 0,
+              "ra_scs and restricted_set of miphy_prach_job follow the reference's enums");
+
+/// srsran::prach_generator over miphy_prach_generate_batch (prach_generator.h:36-58), a batch of one: the frequency-domain sequence
+/// y_u,v comes back into a buffer the generator owns, valid until the next call. What the reference asserts is fatal.
+class prach_generator_hip : public srsran::prach_generator
+{
+public:
+  explicit prach_generator_hip(std::shared_ptr<context> c) : c(std::move(c)) {}
+  srsran::span<const srsran::cf_t> generate(const configuration& config) override
+  {
+    miphy_prach_gen_job j = {};
+    j.format = static_cast<uint32_t>(config.format), j.root_sequence_index = config.root_sequence_index;
+    j.zero_correlation_zone = config.zero_correlation_zone, j.restricted_set = static_cast<uint32_t>(config.restricted_set);
+    j.preamble_index = config.preamble_index, j.out_offset = 0;
+    const size_t L = srsran::is_long_preamble(config.format) ? srsran::prach_constants::LONG_SEQUENCE_LENGTH : srsran::prach_constants::SHORT_SEQUENCE_LENGTH;
+    void*        d = c->buf(8, sequence.size() * sizeof(srsran::cf_t));
+    context::check(miphy_prach_generate_batch(c->ctx, &j, 0, 1, static_cast<float*>(d), c->stream), "prach_generate");
+    c->d2h(sequence.data(), d, L * sizeof(srsran::cf_t));
+    c->sync();
+    return srsran::span<const srsran::cf_t>(sequence.data(), L);
+  }
+
+private:
+  std::shared_ptr<context>                                                  c;
+  std::array<srsran::cf_t, srsran::prach_constants::LONG_SEQUENCE_LENGTH> sequence;
+};
+
+/// srsran::prach_detector over miphy_prach_detect_batch (prach_detector.h:37-72, prach_detector_simple_impl.cpp:35-169): one occasion
+/// per call, or several buffers at once through detect_batch(). Only get_symbol(0, 0, 0, 0) of a buffer is uploaded -- the 23.5
+/// detector reads nothing else. The records of every requested preamble come back and the result is assembled with the reference's
+/// own phy_time_unit::from_seconds and convert_power_to_dB, detections in preamble-index order.
+class prach_detector_hip : public srsran::prach_detector
+{
+public:
+  /// \c idft_size plays the role of the reference factory's dft_size_detector (1536 in upper_phy_factories.cpp): 1536 or 3072.
+  explicit prach_detector_hip(std::shared_ptr<context> c, unsigned idft_size_ = 1536) : c(std::move(c)), idft_size(idft_size_)
+  {
+    require(idft_size == 1536 || idft_size == 3072, "prach_detector_hip: IDFT size {} is not 1536 or 3072.", idft_size);
+  }
+
+  srsran::prach_detection_result detect(const srsran::prach_buffer& input, const configuration& config) override
+  {
+    const srsran::prach_buffer*    in = &input;
+    srsran::prach_detection_result r;
+    detect_batch(srsran::span<const srsran::prach_buffer* const>(&in, 1), srsran::span<const configuration>(&config, 1),
+                 srsran::span<srsran::prach_detection_result>(&r, 1));
+    return r;
+  }
+
+  /// Several occasions in one launch: one upload of their symbols, one job each, one download of the records.
+  void detect_batch(srsran::span<const srsran::prach_buffer* const> inputs,
+                    srsran::span<const configuration>               configs,
+                    srsran::span<srsran::prach_detection_result>    out)
+  {
+    require(inputs.size() == configs.size() && out.size() == configs.size(), "prach_detector_hip::detect_batch: one buffer and one result per configuration.");
+    const size_t n = configs.size();
+    if (n == 0) {
+      return;
+    }
+    jobs.resize(n), infos.resize(n);
+    host_symbols.clear();
+    uint32_t nof_records = 0;
+    for (size_t i = 0; i != n; ++i) {
+      const configuration& cfg = configs[i];
+      require(cfg.start_preamble_index + cfg.nof_preamble_indices <= srsran::prach_constants::MAX_NUM_PREAMBLES,
+              "The start preamble index {} and the number of preambles to detect {}, exceed the maximum of 64.", cfg.start_preamble_index,
+              cfg.nof_preamble_indices);
+      infos[i] = srsran::is_long_preamble(cfg.format) ? srsran::get_prach_preamble_long_info(cfg.format)
+                                                       : srsran::get_prach_preamble_short_info(cfg.format, cfg.ra_scs, false);
+      require(inputs[i]->get_sequence_length() == infos[i].sequence_length,
+              "The input buffer sequence length {} is not equal to the expected preamble sequence length {}.", inputs[i]->get_sequence_length(),
+              infos[i].sequence_length);
+      srsran::span<const srsran::cf_t> symbol = inputs[i]->get_symbol(0, 0, 0, 0);
+      miphy_prach_job&                 j      = jobs[i];
+      j                                       = {};
+      j.format = static_cast<uint32_t>(cfg.format), j.ra_scs = srsran::is_long_preamble(cfg.format) ? 0 : static_cast<uint32_t>(cfg.ra_scs);
+      j.root_sequence_index = cfg.root_sequence_index, j.zero_correlation_zone = cfg.zero_correlation_zone;
+      j.restricted_set = static_cast<uint32_t>(cfg.restricted_set), j.start_preamble_index = cfg.start_preamble_index;
+      j.nof_preamble_indices = cfg.nof_preamble_indices, j.idft_size = idft_size;
+      j.symbol_offset = static_cast<uint32_t>(host_symbols.size()), j.preamble_offset = nof_records;
+      host_symbols.insert(host_symbols.end(), symbol.begin(), symbol.begin() + infos[i].sequence_length);
+      nof_records += cfg.nof_preamble_indices;
+    }
+    // One device buffer: [symbols][results][preamble records], each part 16-byte aligned.
+    const size_t sym_bytes = (host_symbols.size() * sizeof(srsran::cf_t) + 15) & ~size_t(15);
+    const size_t res_bytes = n * sizeof(miphy_prach_result); // 16 bytes each
+    const size_t rec_bytes = nof_records * sizeof(miphy_prach_preamble_result);
+    auto*        d         = static_cast<uint8_t*>(c->buf(8, sym_bytes + res_bytes + rec_bytes + 16));
+    c->h2d(d, host_symbols.data(), host_symbols.size() * sizeof(srsran::cf_t));
+    context::check(miphy_prach_detect_batch(c->ctx, jobs.data(), 0, static_cast<uint32_t>(n), reinterpret_cast<const float*>(d),
+                                            reinterpret_cast<miphy_prach_result*>(d + sym_bytes),
+                                            reinterpret_cast<miphy_prach_preamble_result*>(d + sym_bytes + res_bytes), c->stream),
+                   "prach_detect");
+    host_out.resize(res_bytes + rec_bytes);
+    c->d2h(host_out.data(), d + sym_bytes, host_out.size());
+    c->sync();
+    for (size_t i = 0; i != n; ++i) {
+      miphy_prach_result res;
+      std::memcpy(&res, host_out.data() + i * sizeof(res), sizeof(res));
+      const double                    sampling_rate_Hz = static_cast<double>(srsran::ra_scs_to_Hz(infos[i].scs) * idft_size);
+      srsran::prach_detection_result& r                = out[i];
+      r.rssi_dB                                        = srsran::convert_power_to_dB(res.rssi);
+      r.time_resolution                                = srsran::phy_time_unit::from_seconds(1.0 / sampling_rate_Hz);
+      r.time_advance_max = res.n_cs_limited ? srsran::phy_time_unit::from_seconds(static_cast<double>(res.delay_n_maximum) / sampling_rate_Hz)
+                                            : infos[i].cp_length;
+      r.preambles.clear();
+      for (unsigned k = 0; k != jobs[i].nof_preamble_indices; ++k) {
+        miphy_prach_preamble_result rec;
+        std::memcpy(&rec, host_out.data() + res_bytes + (jobs[i].preamble_offset + k) * sizeof(rec), sizeof(rec));
+        if (!rec.detected) {
+          continue;
+        }
+        srsran::prach_detection_result::preamble_indication& info = r.preambles.emplace_back();
+        info.preamble_index                                       = jobs[i].start_preamble_index + k;
+        info.time_advance = srsran::phy_time_unit::from_seconds(static_cast<double>(rec.delay_n) / sampling_rate_Hz);
+        info.power_dB     = srsran::convert_power_to_dB(rec.peak_power);
+        info.snr_dB       = 0.0F;
+      }
+    }
+  }
+
+private:
+  std::shared_ptr<context>                        c;
+  unsigned                                        idft_size;
+  std::vector<miphy_prach_job>                    jobs;
+  std::vector<srsran::prach_preamble_information> infos;
+  std::vector<srsran::cf_t>                       host_symbols;
+  std::vector<uint8_t>                            host_out;
+};
+
+/// srsran::prach_detector_validator for prach_detector_hip: what the reference's detector and generator assert (an unrestricted set, a
+/// zone whose N_CS is not reserved, at most 64 preamble indices) and what get_prach_preamble_long_info / _short_info serve (a valid
+/// format; a short format with a short RA subcarrier spacing).
+class prach_detector_validator_hip : public srsran::prach_detector_validator
+{
+public:
+  bool is_valid(const srsran::prach_detector::configuration& config) override
+  {
+    if (config.restricted_set != srsran::restricted_set_config::UNRESTRICTED || config.zero_correlation_zone > 15) {
+      return false;
+    }
+    if (config.start_preamble_index + config.nof_preamble_indices > srsran::prach_constants::MAX_NUM_PREAMBLES) {
+      return false;
+    }
+    if (srsran::is_long_preamble(config.format)) {
+      return true;
+    }
+    return srsran::is_short_preamble(config.format) && srsran::is_short_preamble(config.ra_scs);
+  }
+};
+
+/// srsran::prach_detector_factory / prach_generator_factory handing out the device blocks on one context.
+class prach_detector_factory_hip : public srsran::prach_detector_factory
+{
+public:
+  explicit prach_detector_factory_hip(std::shared_ptr<context> c_, unsigned idft_size_ = 1536) : c(std::move(c_)), idft_size(idft_size_) {}
+  std::unique_ptr<srsran::prach_detector>           create() override { return std::make_unique<prach_detector_hip>(c, idft_size); }
+  std::unique_ptr<srsran::prach_detector_validator> create_validator() override { return std::make_unique<prach_detector_validator_hip>(); }
+
+private:
+  std::shared_ptr<context> c;
+  unsigned                 idft_size;
+};
+
+class prach_generator_factory_hip : public srsran::prach_generator_factory
+{
+public:
+  explicit prach_generator_factory_hip(std::shared_ptr<context> c_) : c(std::move(c_)) {}
+  std::unique_ptr<srsran::prach_generator> create() override { return std::make_unique<prach_generator_hip>(c); }
+
+private:
+  std::shared_ptr<context> c;
+};
+
+inline std::shared_ptr<srsran::prach_detector_factory> create_prach_detector_factory_hip(std::shared_ptr<context> c, unsigned idft_size = 1536)
+{
+  return std::make_shared<prach_detector_factory_hip>(std::move(c), idft_size);
+}
+
+inline std::shared_ptr<srsran::prach_generator_factory> create_prach_generator_factory_hip(std::shared_ptr<context> c)
+{
+  return std::make_shared<prach_generator_factory_hip>(std::move(c));
 }
 
 // ---------------------------------------------------------------------------------------------------------------- PUSCH processor

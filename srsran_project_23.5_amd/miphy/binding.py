@@ -119,6 +119,8 @@ def lib():
         l.miphy_uci_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_pusch_uci_field_jobs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
         l.miphy_pucch_process_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
+        l.miphy_prach_detect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
+        l.miphy_prach_generate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 2
         _lib = l
     return _lib
 
@@ -282,6 +284,21 @@ assert PucchJob.itemsize == 64
 PucchResult = np.dtype([("status", np.uint8), ("reserved", np.uint8, 3), ("detection_metric", np.float32), ("epre_db", np.float32),
                         ("rsrp_db", np.float32), ("sinr_db", np.float32), ("time_alignment_s", np.float32)], align=True)
 assert PucchResult.itemsize == 24
+# MIPHY_PRACH_FORMAT_*: PRACH_FORMATS.index("B4") is the format number of a PrachJob
+PRACH_FORMATS = ("0", "1", "2", "3", "A1", "A2", "A3", "B1", "B4", "C0", "C2", "A1/B1", "A2/B2", "A3/B3")
+# miphy_prach_job / miphy_prach_result / miphy_prach_preamble_result / miphy_prach_gen_job (include/miphy.h)
+PrachJob = np.dtype([("format", np.uint32), ("ra_scs", np.uint32), ("root_sequence_index", np.uint32), ("zero_correlation_zone", np.uint32),
+                     ("restricted_set", np.uint32), ("start_preamble_index", np.uint32), ("nof_preamble_indices", np.uint32),
+                     ("idft_size", np.uint32), ("symbol_offset", np.uint32), ("preamble_offset", np.uint32)], align=True)
+assert PrachJob.itemsize == 40
+PrachResult = np.dtype([("rssi", np.float32), ("delay_n_maximum", np.uint32), ("n_cs", np.uint32), ("n_cs_limited", np.uint32)], align=True)
+assert PrachResult.itemsize == 16
+PrachPreambleResult = np.dtype([("peak_index", np.uint32), ("delay_n", np.int32), ("peak_power", np.float32), ("metric", np.float32),
+                                ("detected", np.uint32)], align=True)
+assert PrachPreambleResult.itemsize == 20
+PrachGenJob = np.dtype([("format", np.uint32), ("root_sequence_index", np.uint32), ("zero_correlation_zone", np.uint32),
+                        ("restricted_set", np.uint32), ("preamble_index", np.uint32), ("out_offset", np.uint32)], align=True)
+assert PrachGenJob.itemsize == 24
 
 
 def pusch_uci_field_jobs(pdus, uci):
@@ -642,6 +659,25 @@ class Context:
         assert llr is None or llr.dtype == torch.int8
         check(lib().miphy_pucch_process_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(payload), _dptr(results),
                                               None if llr is None else _dptr(llr), _stream_ptr(stream)))
+
+    def prach_detect_batch(self, jobs, symbols, results, preambles, stream=None):
+        """PRACH detector (jobs: numpy PrachJob array, or a uint8 device tensor holding the same bytes), one job per occasion: symbols
+        complex64 device tensor, results a uint8 device tensor of n * PrachResult.itemsize bytes, preambles a uint8 device tensor of
+        PrachPreambleResult records, one per requested preamble index from each job's preamble_offset (view them with
+        .cpu().numpy().view(PrachResult / PrachPreambleResult))."""
+        import torch
+        jobs, n, ptr, on_dev = self._descs(jobs, PrachJob)
+        assert symbols.dtype == torch.complex64 and results.dtype == torch.uint8 and preambles.dtype == torch.uint8
+        assert results.numel() >= n * PrachResult.itemsize
+        check(lib().miphy_prach_detect_batch(self.h, ptr, on_dev, n, _dptr(symbols), _dptr(results), _dptr(preambles), _stream_ptr(stream)))
+
+    def prach_generate_batch(self, jobs, out, stream=None):
+        """PRACH frequency-domain preambles y_u,v (jobs: numpy PrachGenJob array or a uint8 device tensor): out complex64 device tensor,
+        839 or 139 values per job from its out_offset."""
+        import torch
+        jobs, n, ptr, on_dev = self._descs(jobs, PrachGenJob)
+        assert out.dtype == torch.complex64
+        check(lib().miphy_prach_generate_batch(self.h, ptr, on_dev, n, _dptr(out), _stream_ptr(stream)))
 
     def pdsch_encode_batch(self, tbs, tb_in, codeword_out, stream=None):
         assert isinstance(tbs, np.ndarray) and tbs.dtype == PdschTbDesc
