@@ -1,6 +1,6 @@
 // LDPC decoder, packed variant: every lane owns TWO lifted check rows (l and l + Z/2) and processes them with the packed
 // 16-bit VALU instructions of CDNA (v_pk_add/sub/min/max/mad), halving both the instruction count per codeblock and the
-// number of wavefronts a codeblock occupies. Same arithmetic contract as ldpc_decode.hip (reference:
+// number of wavefronts a codeblock occupies. Same arithmetic contract as ldpc_decode_row.hip (reference:
 // ldpc_decoder_impl.cpp:60-146 + ldpc_decoder_avx2.cpp:66-243, avx2_support.h:65-106); results are bit-identical.
 //
 // Check-to-variable messages are kept EXPLICITLY in LDS, one int8 per (edge, row), no VALU work to rebuild a message from
@@ -17,92 +17,18 @@
 
 namespace {
 
-// Is the checksum of the first L hard bits zero? Mask / popcount form (crc_zmask in miphy_internal.h): no bit-serial division, no
-// position weights. zi = table index of the polynomial, order = its degree.
+// Is the checksum of the first L hard bits zero? (every thread of the block must call) Mask / popcount form where the polynomial has a
+// table (zi >= 0), by division otherwise; words strided over the block's threads.
 __device__ __forceinline__ bool block_crc_is_zero(const int8_t* soft, const miphy_graph_tables* __restrict__ tab, int zi, int order, int L,
                                                   uint32_t* red, int tid, int nt)
 {
-  const int nw = (L + 31) >> 5;
-  uint32_t  acc[24];
-#pragma unroll
-  for (int k = 0; k < 24; ++k)
-    acc[k] = 0;
-  for (int t = tid; t < nw; t += nt) {
-    uint32_t  w   = hard_flags(soft, t);
-    const int rem = L - 32 * t;
-    if (rem < 32) { // last word: positions 4 q + b >= rem are not message bits
-      uint32_t valid = 0;
-      for (int q = 0; q < 8; ++q) {
-        const int      nb = min(4, max(0, rem - 4 * q));                      // message bits among the four of dword q
-        const uint32_t lo = (nb >= 4) ? 0xffffffffu : ((1u << (8 * nb)) - 1u); // their byte lanes
-        valid |= (0x01010101u & lo) << q;
-      }
-      w &= valid;
-    }
-    const uint4* m = reinterpret_cast<const uint4*>(tab->crc_zmask[zi][nw - 1 - t]);
-#pragma unroll
-    for (int g = 0; g < 6; ++g) {
-      const uint4 mk = m[g];
-      acc[4 * g + 0] += __builtin_popcount(w & mk.x);
-      acc[4 * g + 1] += __builtin_popcount(w & mk.y);
-      acc[4 * g + 2] += __builtin_popcount(w & mk.z);
-      acc[4 * g + 3] += __builtin_popcount(w & mk.w);
-    }
-  }
-  uint32_t par = 0;
-#pragma unroll
-  for (int k = 0; k < 24; ++k)
-    par |= (acc[k] & 1u) << k;
-  par &= (1u << order) - 1u;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1)
-    par ^= __shfl_xor(par, off);
-  if ((tid & 63) == 0)
-    red[2 + (tid >> 6)] = par;
-  __syncthreads();
-  uint32_t crc = 0;
-  for (int w = 0; w < (nt >> 6); ++w)
-    crc ^= red[2 + w];
-  __syncthreads();
-  return crc == 0;
+  return block_xor(crc_zmask_partial(soft, tab, zi, order, L, tid, nt), red, tid, nt) == 0;
 }
 
-// CRC over the first L hard bits, words strided over the block's threads.
 __device__ __forceinline__ uint32_t block_crc(const int8_t* soft, const miphy_graph_tables* __restrict__ tab, int crc_id, uint32_t poly,
                                               uint32_t order, int K, int L, uint32_t* red, int tid, int nt)
 {
-  const int      nfull = L >> 5, rbits = L & 31, nwords = (L + 31) >> 5;
-  const uint32_t top   = 1u << order;
-  uint32_t       part  = 0;
-  for (int t = tid; t < nwords; t += nt) {
-    const uint32_t w   = hard_word(soft, t, K);
-    const int      len = min(32, L - 32 * t);
-    uint32_t       reg = 0;
-    for (int b = 0; b < len; ++b) {
-      reg = (reg << 1) ^ (((w >> (31 - b)) & 1u) << order);
-      reg ^= (reg & top) ? poly : 0u;
-    }
-    reg &= top - 1u;
-    if (t < nfull) {
-      reg = gf2_mulmod(reg, tab->crc_pow32[crc_id][nfull - 1 - t], poly, order);
-      for (int b = 0; b < rbits; ++b) {
-        reg <<= 1;
-        reg ^= (reg & top) ? poly : 0u;
-      }
-    }
-    part ^= reg;
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1)
-    part ^= __shfl_xor(part, off);
-  if ((tid & 63) == 0)
-    red[2 + (tid >> 6)] = part;
-  __syncthreads();
-  uint32_t crc = 0;
-  for (int w = 0; w < (nt >> 6); ++w)
-    crc ^= red[2 + w];
-  __syncthreads();
-  return crc;
+  return block_xor(crc_div_partial(soft, tab, crc_id, poly, order, K, L, tid, nt), red, tid, nt);
 }
 
 // Phase timing for tools/ldpc_phase_probe.py (debug build with -DLDPC_PK_PROFILE only; never compiled into libmiphy.so).
@@ -421,7 +347,6 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   last = (int)red[0];
 
   const bool use_crc = dsc.crc_poly != MIPHY_CRC_NONE;
-  const int  kwords  = (K + 31) >> 5;
   if (last == 0) {
     if (!use_crc) {
       for (int b = tid; b < (K + 7) / 8; b += nt) {
@@ -543,17 +468,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   PROF_T(p_crc);
   PROF_ADD(3, p_dec, p_crc);
 
-  const bool out_aligned = ((uintptr_t)out & 3u) == 0;
-  for (int t = tid; t < kwords; t += nt) {
-    const uint32_t w      = hard_word(soft, t, K);
-    const int      nbytes = min(4, (K - 32 * t + 7) / 8);
-    if (nbytes == 4 && out_aligned) {
-      reinterpret_cast<uint32_t*>(out)[t] = __builtin_bswap32(w); // MSB-first bytes
-    } else {
-      for (int q = 0; q < nbytes; ++q)
-        out[4 * t + q] = (uint8_t)(w >> (24 - 8 * q));
-    }
-  }
+  store_hard_words(soft, out, K, tid, nt);
   if (tid == 0) {
     iters_out[cb] = result_iters;
     // A codeblock that is dematched here is a first transmission: its flag is written either way, which is the reset the caller
@@ -606,8 +521,6 @@ extern "C" int miphy_debug_ldpc_profile2(unsigned long long out[8], int reset)
 }
 #endif
 
-// LDS bytes the packed kernel needs for a given geometry (Zt >= Z of every codeblock, lay = layer bound, pairs_all = message
-// dwords per lane of those layers).
 int miphy_ldpc_pk_waves_per_cu(bool fused, int parts)
 {
 #ifdef LDPC_PK_REPORT_WAVES_FUSED // A-B: the register allocation of one occupancy run at another
@@ -617,21 +530,24 @@ int miphy_ldpc_pk_waves_per_cu(bool fused, int parts)
   return 4 * (parts > 1 ? LDPC_PK_MIN_WAVES_SPLIT : (fused ? LDPC_PK_MIN_WAVES_FUSED : LDPC_PK_MIN_WAVES_PLAIN)); // what __launch_bounds__ of the kernel guarantees per CU
 }
 
+// LDS bytes the packed kernel needs for a given geometry (Zt >= Z of every codeblock, lay = layer bound, pairs_all = message
+// dwords per lane of those layers).
 size_t miphy_ldpc_pk_lds_bytes(int bgK, int lay, size_t Zt, int pairs_all, int parts)
 {
   const size_t waves = ((Zt + 1) / 2 + 63) / 64;
   return ((((size_t)bgK + lay) * Zt + 15) & ~(size_t)15) + waves * (size_t)pairs_all * 256 + 64 + (parts > 1 ? (size_t)parts * 3 * 64 * waves * 4 : 0);
 }
 
+// Resident workgroups per CU: LDS, the wavefronts per CU the register budget of the kernel allows (__launch_bounds__; at most the 32 slots).
+int miphy_ldpc_pk_per_cu(size_t lds, int waves, bool fused, int parts)
+{
+  return std::max(1, std::min((int)((size_t)160 * 1024 / lds), miphy_ldpc_pk_waves_per_cu(fused, parts) / waves));
+}
+
 uint32_t miphy_ldpc_pk_grid(const miphy_ctx* ctx, uint32_t n, int threads, size_t lds, bool fused, int parts)
 {
-  // (threads = those of the launch: the latency form passes twice the row-owning threads)
-  // Resident workgroups per CU: LDS, the wavefronts per CU the register budget of the kernel allows (__launch_bounds__), 32 slots.
-  const int waves  = threads / 64;
-  int       per_cu = (int)((size_t)160 * 1024 / lds);
-  per_cu           = std::min(per_cu, miphy_ldpc_pk_waves_per_cu(fused, parts) / waves);
-  per_cu           = std::max(per_cu, 1);
-  return std::min<uint32_t>(n, (uint32_t)(ctx->num_cus * per_cu));
+  // (threads = those of the launch: the latency form counts every part)
+  return std::min<uint32_t>(n, (uint32_t)(ctx->num_cus * miphy_ldpc_pk_per_cu(lds, threads / 64, fused, parts)));
 }
 
 int miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order, const int8_t* llr,

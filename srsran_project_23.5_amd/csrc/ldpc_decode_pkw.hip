@@ -19,47 +19,11 @@
 
 namespace {
 
-// Is the checksum of the first L hard bits of this lane's codeblock zero? Mask / popcount form (crc_zmask), words strided over the
-// H lanes of the group, partial parities combined through the group's word of LDS. Every lane of the wave must call.
-__device__ __forceinline__ bool group_crc_is_zero(const int8_t* softg, const miphy_graph_tables* __restrict__ tab, int zi, int order, int L,
-                                                  uint32_t* redg, int l, int H, bool member)
+// Is the checksum of the first L hard bits of this lane's codeblock zero? Words strided over the H lanes of the group, partial
+// checksums (crc_zmask_partial, or crc_div_partial for a polynomial without a mask table) combined through the group's word of LDS.
+// Every lane of the wave must call.
+__device__ __forceinline__ bool group_word_is_zero(uint32_t* redg, int l, bool member)
 {
-  if (member) {
-    const int nw = (L + 31) >> 5;
-    uint32_t  acc[24];
-#pragma unroll
-    for (int k = 0; k < 24; ++k)
-      acc[k] = 0;
-    for (int t = l; t < nw; t += H) {
-      uint32_t  w   = hard_flags(softg, t);
-      const int rem = L - 32 * t;
-      if (rem < 32) { // last word: positions 4 q + b >= rem are not message bits
-        uint32_t valid = 0;
-        for (int q = 0; q < 8; ++q) {
-          const int      nb = min(4, max(0, rem - 4 * q));
-          const uint32_t lo = (nb >= 4) ? 0xffffffffu : ((1u << (8 * nb)) - 1u);
-          valid |= (0x01010101u & lo) << q;
-        }
-        w &= valid;
-      }
-      const uint4* m = reinterpret_cast<const uint4*>(tab->crc_zmask[zi][nw - 1 - t]);
-#pragma unroll
-      for (int g4 = 0; g4 < 6; ++g4) {
-        const uint4 mk = m[g4];
-        acc[4 * g4 + 0] += __builtin_popcount(w & mk.x);
-        acc[4 * g4 + 1] += __builtin_popcount(w & mk.y);
-        acc[4 * g4 + 2] += __builtin_popcount(w & mk.z);
-        acc[4 * g4 + 3] += __builtin_popcount(w & mk.w);
-      }
-    }
-    uint32_t par = 0;
-#pragma unroll
-    for (int k = 0; k < 24; ++k)
-      par |= (acc[k] & 1u) << k;
-    par &= (1u << order) - 1u;
-    if (par)
-      atomicXor(redg, par);
-  }
   __syncthreads();
   const uint32_t crc = member ? *redg : 1u;
   __syncthreads();
@@ -69,43 +33,26 @@ __device__ __forceinline__ bool group_crc_is_zero(const int8_t* softg, const mip
   return crc == 0;
 }
 
-// The same by division, for polynomials without a mask table (CRC24C, CRC11): partial remainder of each 32-bit word times its
-// position weight.
+__device__ __forceinline__ bool group_crc_is_zero(const int8_t* softg, const miphy_graph_tables* __restrict__ tab, int zi, int order, int L,
+                                                  uint32_t* redg, int l, int H, bool member)
+{
+  if (member) {
+    const uint32_t par = crc_zmask_partial(softg, tab, zi, order, L, l, H);
+    if (par)
+      atomicXor(redg, par);
+  }
+  return group_word_is_zero(redg, l, member);
+}
+
 __device__ __forceinline__ bool group_crc_is_zero_div(const int8_t* softg, const miphy_graph_tables* __restrict__ tab, int crc_id, uint32_t poly,
                                                       uint32_t order, int K, int L, uint32_t* redg, int l, int H, bool member)
 {
   if (member) {
-    const int      nfull = L >> 5, rbits = L & 31, nwords = (L + 31) >> 5;
-    const uint32_t top   = 1u << order;
-    uint32_t       part  = 0;
-    for (int t = l; t < nwords; t += H) {
-      const uint32_t w   = hard_word(softg, t, K);
-      const int      len = min(32, L - 32 * t);
-      uint32_t       reg = 0;
-      for (int b = 0; b < len; ++b) {
-        reg = (reg << 1) ^ (((w >> (31 - b)) & 1u) << order);
-        reg ^= (reg & top) ? poly : 0u;
-      }
-      reg &= top - 1u;
-      if (t < nfull) {
-        reg = gf2_mulmod(reg, tab->crc_pow32[crc_id][nfull - 1 - t], poly, order);
-        for (int b = 0; b < rbits; ++b) {
-          reg <<= 1;
-          reg ^= (reg & top) ? poly : 0u;
-        }
-      }
-      part ^= reg;
-    }
+    const uint32_t part = crc_div_partial(softg, tab, crc_id, poly, order, K, L, l, H);
     if (part)
       atomicXor(redg, part);
   }
-  __syncthreads();
-  const uint32_t crc = member ? *redg : 1u;
-  __syncthreads();
-  if (member && l == 0)
-    *redg = 0;
-  __syncthreads();
-  return crc == 0;
+  return group_word_is_zero(redg, l, member);
 }
 
 // One wavefront per workgroup (so __syncthreads() is a wait for the wave's own LDS operations, no s_barrier is emitted), persistent:
@@ -210,7 +157,6 @@ ldpc_decode_pkw_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
     const bool use_crc    = d0.crc_poly != MIPHY_CRC_NONE;
     const bool final_only = use_crc && (d0.flags & 1u);
     const int  max_iter   = d0.max_iter;
-    const int  kwords     = (K + 31) >> 5;
     if (decode && last == 0) { // ldpc_decoder_impl.cpp:88-94
       if (!use_crc) {
         for (int bb = l; bb < (K + 7) / 8; bb += H) {
@@ -288,17 +234,7 @@ ldpc_decode_pkw_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
       result_iters  = ok ? max_iter : 0;
     }
     if (decode) {
-      const bool out_aligned = ((uintptr_t)out & 3u) == 0;
-      for (int t = l; t < kwords; t += H) {
-        const uint32_t w      = hard_word(soft + base, t, K);
-        const int      nbytes = min(4, (K - 32 * t + 7) / 8);
-        if (nbytes == 4 && out_aligned) {
-          reinterpret_cast<uint32_t*>(out)[t] = __builtin_bswap32(w);
-        } else {
-          for (int qq = 0; qq < nbytes; ++qq)
-            out[4 * t + qq] = (uint8_t)(w >> (24 - 8 * qq));
-        }
-      }
+      store_hard_words(soft, out, K, l, H, base);
       if (l == 0) {
         iters_out[cbi] = result_iters;
         if (harq_crc_ok && result_iters > 0)

@@ -1,6 +1,7 @@
-// Device code shared by the packed LDPC decoder kernels (ldpc_decode_pk.hip: one codeblock per workgroup; ldpc_decode_pkw.hip:
-// several small codeblocks per wavefront). Arithmetic contract: ldpc_decoder_impl.cpp:60-146 + ldpc_decoder_avx2.cpp:66-243,
-// avx2_support.h:65-106 of the reference; every kernel built from these functions is bit-identical to it.
+// Device code shared by the LDPC decoder kernels: the packed row update of ldpc_decode_pk.hip (one codeblock per workgroup) and
+// ldpc_decode_pkw.hip (several small codeblocks per wavefront), and the hard decision, checksum and write-back that these two and the
+// one-row-per-lane kernel of ldpc_decode_row.hip have in common. Arithmetic contract: ldpc_decoder_impl.cpp:60-146 +
+// ldpc_decoder_avx2.cpp:66-243, avx2_support.h:65-106 of the reference; every kernel built from these functions is bit-identical to it.
 #pragma once
 #include "miphy_internal.h"
 
@@ -358,6 +359,8 @@ __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b, uint32_t 
   return r;
 }
 
+// Hard decision of 32 consecutive soft bits starting at soft[32*t]; returns the big-endian numeric value (first bit in
+// bit 31). Positions >= K are masked to 0. bit = (llr <= 0), log_likelihood_ratio.h:86.
 __device__ __forceinline__ uint32_t hard_word(const int8_t* soft, int t, int K)
 {
   const uint32_t* p = reinterpret_cast<const uint32_t*>(soft) + 8 * t;
@@ -393,6 +396,109 @@ __device__ __forceinline__ uint32_t hard_flags(const int8_t* soft, int t)
     w                  = (w << 1) | (le0 >> 7);
   }
   return w;
+}
+
+// Checksum of the first L hard bits in the mask / popcount form (crc_zmask in miphy_internal.h: no bit-serial division, no position
+// weights): this lane's parity word over the message words first, first + stride, ... The XOR of the lanes' words is zero exactly when
+// the checksum is. zi = table index of the polynomial, order = its degree.
+__device__ __forceinline__ uint32_t crc_zmask_partial(const int8_t* soft, const miphy_graph_tables* __restrict__ tab, int zi, int order, int L, int first,
+                                                      int stride)
+{
+  const int nw = (L + 31) >> 5;
+  uint32_t  acc[24];
+#pragma unroll
+  for (int k = 0; k < 24; ++k)
+    acc[k] = 0;
+  for (int t = first; t < nw; t += stride) {
+    uint32_t  w   = hard_flags(soft, t);
+    const int rem = L - 32 * t;
+    if (rem < 32) { // last word: positions 4 q + b >= rem are not message bits
+      uint32_t valid = 0;
+      for (int q = 0; q < 8; ++q) {
+        const int      nb = min(4, max(0, rem - 4 * q));                      // message bits among the four of dword q
+        const uint32_t lo = (nb >= 4) ? 0xffffffffu : ((1u << (8 * nb)) - 1u); // their byte lanes
+        valid |= (0x01010101u & lo) << q;
+      }
+      w &= valid;
+    }
+    const uint4* m = reinterpret_cast<const uint4*>(tab->crc_zmask[zi][nw - 1 - t]);
+#pragma unroll
+    for (int g = 0; g < 6; ++g) {
+      const uint4 mk = m[g];
+      acc[4 * g + 0] += __builtin_popcount(w & mk.x);
+      acc[4 * g + 1] += __builtin_popcount(w & mk.y);
+      acc[4 * g + 2] += __builtin_popcount(w & mk.z);
+      acc[4 * g + 3] += __builtin_popcount(w & mk.w);
+    }
+  }
+  uint32_t par = 0;
+#pragma unroll
+  for (int k = 0; k < 24; ++k)
+    par |= (acc[k] & 1u) << k;
+  return par & ((1u << order) - 1u);
+}
+
+// The same by division, for polynomials without a mask table (CRC24C, CRC11): the partial remainder of each 32-bit word times its
+// position weight x^(32 (nfull - 1 - t) + rbits) mod P. The XOR of the lanes' words is the checksum.
+__device__ __forceinline__ uint32_t crc_div_partial(const int8_t* soft, const miphy_graph_tables* __restrict__ tab, int crc_id, uint32_t poly, uint32_t order,
+                                                    int K, int L, int first, int stride)
+{
+  const int      nfull = L >> 5, rbits = L & 31, nwords = (L + 31) >> 5;
+  const uint32_t top   = 1u << order;
+  uint32_t       part  = 0;
+  for (int t = first; t < nwords; t += stride) {
+    const uint32_t w   = hard_word(soft, t, K);
+    const int      len = min(32, L - 32 * t);
+    uint32_t       reg = 0;
+    for (int b = 0; b < len; ++b) {
+      reg = (reg << 1) ^ (((w >> (31 - b)) & 1u) << order);
+      reg ^= (reg & top) ? poly : 0u;
+    }
+    reg &= top - 1u;
+    if (t < nfull) {
+      reg = gf2_mulmod(reg, tab->crc_pow32[crc_id][nfull - 1 - t], poly, order);
+      for (int b = 0; b < rbits; ++b) {
+        reg <<= 1;
+        reg ^= (reg & top) ? poly : 0u;
+      }
+    }
+    part ^= reg;
+  }
+  return part;
+}
+
+// XOR of a partial checksum over the workgroup (every thread must call): wavefront shuffles, then red[2 ...] of the reduction words.
+__device__ __forceinline__ uint32_t block_xor(uint32_t part, uint32_t* red, int tid, int nt)
+{
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1)
+    part ^= __shfl_xor(part, off);
+  if ((tid & 63) == 0)
+    red[2 + (tid >> 6)] = part;
+  __syncthreads();
+  uint32_t crc = 0;
+  for (int w = 0; w < (nt >> 6); ++w)
+    crc ^= red[2 + w];
+  __syncthreads();
+  return crc;
+}
+
+// The final hard bits of a codeblock, MSB first, words first, first + stride, ... of the K message bits. `base` as in update_rows_pk
+// (the wave kernel's group offset: added per word, which is the code the kernel had with the loop written out).
+__device__ __forceinline__ void store_hard_words(const int8_t* soft, uint8_t* out, int K, int first, int stride, uint32_t base = 0)
+{
+  const bool out_aligned = ((uintptr_t)out & 3u) == 0;
+  const int  kwords      = (K + 31) >> 5;
+  for (int t = first; t < kwords; t += stride) {
+    const uint32_t w      = hard_word(soft + base, t, K);
+    const int      nbytes = min(4, (K - 32 * t + 7) / 8);
+    if (nbytes == 4 && out_aligned) {
+      reinterpret_cast<uint32_t*>(out)[t] = __builtin_bswap32(w); // MSB-first bytes
+    } else {
+      for (int q = 0; q < nbytes; ++q)
+        out[4 * t + q] = (uint8_t)(w >> (24 - 8 * q));
+    }
+  }
 }
 
 } // namespace

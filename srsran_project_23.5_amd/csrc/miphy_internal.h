@@ -132,7 +132,7 @@ int miphy_upload(miphy_ctx* ctx, void* dst, const void* src, size_t bytes, hipSt
 
 #ifdef __cplusplus
 #include <vector>
-// Launch classes of a batch whose descriptors the host can see (ldpc_decode.hip): codeblocks sorted so that each class shares a
+// Launch classes of a batch whose descriptors the host can see (ldpc_decode.hip, the host side of the decoder): codeblocks sorted so that each class shares a
 // workgroup size and an LDS size.
 struct miphy_ldpc_class {
   uint8_t  kind;  // 0 = wave kernel (Z <= 64, several codeblocks per wavefront); 1..3 = packed kernel with that many wavefronts per codeblock
@@ -174,9 +174,21 @@ struct miphy_ldpc_launches {
   bool                           side_streams = false; // launches fork to the context's side streams (miphy_side_streams first)
   bool                           scalar       = false; // the one-row-per-lane kernel is forced: nothing is dematched in the decoder
 };
+// Modes of miphy_debug_force_ldpc_kernel (include/miphy.h): a mode in the low byte, plus flag bits.
+enum miphy_ldpc_force_mode {
+  MIPHY_LDPC_FORCE_AUTO        = 0,
+  MIPHY_LDPC_FORCE_ROW         = 1, // the one-row-per-lane kernel: one launch per call, every class of a table
+  MIPHY_LDPC_FORCE_PACKED_ONE  = 2, // the packed kernel as ONE launch per call (tables: as AUTO)
+  MIPHY_LDPC_FORCE_CLASSES     = 3, // class-sorted launches (what AUTO does with host descriptors)
+  MIPHY_LDPC_FORCE_THROUGHPUT  = 4, // class-sorted, the geometry of a batch that fills the chip: no latency form, messages global wherever that buys residency
+  MIPHY_LDPC_FORCE_LATENCY_ALL = 5, // class-sorted, the latency form in two parts on every packed class
+  MIPHY_LDPC_FORCE_LATENCY2    = 6, // AUTO with the latency form in two parts instead of four
+  MIPHY_LDPC_FORCE_MODE_MASK   = 0xff,
+  MIPHY_LDPC_FORCE_ALL_GMSG    = 0x100 // flag: a GMSG launch keeps ALL its messages in global memory
+};
 // Host only: the launch table of the classes C (their order / bundles are device arrays by then). fuse: the fused classes dematch while
 // they load (the caller then passes rate-dematcher descriptors to the run). The debug knobs of miphy_debug_force_ldpc_kernel and
-// miphy_debug_set_ldpc_class_streams are read here, and nowhere else.
+// miphy_debug_set_ldpc_class_streams are read when a table is made -- one snapshot per table -- and nowhere else.
 void miphy_ldpc_plan_launches(const miphy_ctx* ctx, const miphy_ldpc_classes& C, bool fuse, miphy_ldpc_launches& T);
 // Enqueues the table on `s`: the fork to the side streams (created by then), one launch per class, the join -- on every path after the
 // fork. d_order / d_bundles = device copies of C.order / C.bundles; gmsg = T.gmsg_bytes of message scratch; d_rdm / rm_in: rate-dematcher
@@ -184,7 +196,12 @@ void miphy_ldpc_plan_launches(const miphy_ctx* ctx, const miphy_ldpc_classes& C,
 int miphy_ldpc_run_launches(miphy_ctx* ctx, const miphy_ldpc_launches& T, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order,
                             const uint32_t* d_bundles, const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot,
                             uint8_t* harq_crc_ok, const miphy_ldpc_rdm_desc* d_rdm, const int8_t* rm_in, void* gmsg, hipStream_t s);
-int miphy_ldpc_flags_reset(const uint32_t* d_slots, uint32_t n, uint8_t* harq_crc_ok, hipStream_t s);
+// One-row-per-lane kernel (ldpc_decode_row.hip): LDS bytes of a workgroup of `threads` lanes whose codeblocks reach `lay` layers, geometry
+// of L.c, and the launch of L.grid codeblocks (d_order: codeblocks d_order[0 .. grid) of the arrays, null: the first grid).
+size_t miphy_ldpc_row_lds_bytes(int bgK, int lay, size_t threads);
+void   miphy_ldpc_row_geometry(miphy_ldpc_launch& L);
+int    miphy_ldpc_row_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order, const int8_t* llr,
+                             uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot, uint8_t* harq_crc_ok, hipStream_t s);
 // Wave kernel (ldpc_decode_pkw.hip): geometry of L.c (lds, grid, messages in global memory or not), and its launch. throughput_form (A-B
 // knob): the geometry of a launch that fills the chip, whatever its size.
 void miphy_ldpc_pkw_geometry(const miphy_ctx* ctx, bool throughput_form, miphy_ldpc_launch& L);
@@ -192,10 +209,12 @@ int  miphy_ldpc_pkw_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const mip
                            const uint32_t* d_bundles, const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot,
                            uint8_t* harq_crc_ok, void* gmsg, hipStream_t s);
 // Packed (two rows per lane) kernel (ldpc_decode_pk.hip): LDS bytes of a geometry (pairs_all = 0: messages in global memory; parts = 2 / 4:
-// + exchange slots of the latency form), wavefronts per CU its register budget allows, resident workgroups of a launch, and the launch of
+// + exchange slots of the latency form), wavefronts per CU its register budget allows, resident workgroups per CU (of `waves` wavefronts
+// and `lds` bytes each) and of a launch, and the launch of
 // L.c.count codeblocks (d_order: codeblocks d_order[0 .. count) of the arrays, null: the first count). d_rdm / rm_in with FUSED only.
 size_t   miphy_ldpc_pk_lds_bytes(int bgK, int lay, size_t Zt, int pairs_all, int parts = 1);
 int      miphy_ldpc_pk_waves_per_cu(bool fused, int parts = 1);
+int      miphy_ldpc_pk_per_cu(size_t lds, int waves, bool fused, int parts = 1);
 uint32_t miphy_ldpc_pk_grid(const miphy_ctx* ctx, uint32_t n, int threads, size_t lds, bool fused, int parts = 1);
 int      miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order,
                               const int8_t* llr, uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot, uint8_t* harq_crc_ok,

@@ -518,6 +518,23 @@ pusch_decode_dev layout_pusch_decode(const pusch_decode_build& b, uint8_t* h, ui
   return v;
 }
 
+// pusch_decoder_impl.cpp:146-149: the codeblock CRC flags of a new transmission start cleared.
+__global__ void harq_flags_reset_kernel(const uint32_t* __restrict__ slots, uint32_t n, uint8_t* __restrict__ harq_crc_ok)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n)
+    harq_crc_ok[slots[i]] = 0;
+}
+
+int harq_flags_reset(const uint32_t* d_slots, uint32_t n, uint8_t* harq_crc_ok, hipStream_t s)
+{
+  if (!n || !d_slots || !harq_crc_ok)
+    return MIPHY_OK;
+  hipLaunchKernelGGL(harq_flags_reset_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_slots, n, harq_crc_ok);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
+}
+
 // The launches of one PUSCH decode on staged descriptors: CRC-flag reset of new transmissions, rate dematching into the HARQ
 // soft buffers, LDPC decoding (codeblocks already decoded are skipped), transport-block assembly + TB CRC + result records.
 // Launches of at most 65535 codeblocks each; transport blocks are never split across launches.
@@ -532,7 +549,7 @@ int launch_pusch_decode(miphy_ctx* ctx, const pusch_decode_build& b, const pusch
   if (ev)
     MIPHY_HIP_CHECK(hipEventRecord(ev[0], s));
   // the CRC flags of the new transmissions of the call (a decoder that dematches itself writes the flags of its codeblocks either way)
-  if (!(b.all_fused && allow_fuse) && (rc = miphy_ldpc_flags_reset(v.reset, b.nof_reset, harq_crc_ok, s)))
+  if (!(b.all_fused && allow_fuse) && (rc = harq_flags_reset(v.reset, b.nof_reset, harq_crc_ok, s)))
     return rc;
   for (const pusch_decode_build::chunk& ch : b.chunks) { // rate dematching as launches of its own where the decoder does not do it
     if (!allow_fuse)

@@ -2,7 +2,7 @@
 import numpy as np
 import pytest
 
-from oracle_lib import (ALL_Z, BG_K, BG_NS, CRC16, CRC24A, CRC24B, o_crc_bits, o_ldpc_decode, o_ldpc_encode)
+from oracle_lib import (ALL_Z, BG_K, BG_NS, CRC11, CRC16, CRC24A, CRC24B, CRC24C, CRC_ORDER, o_crc_bits, o_ldpc_decode, o_ldpc_encode)
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +53,7 @@ def noisy_llr(cw, sigma, rng):
 
 def make_codeword(bg, Z, rng, nof_filler=0, poly=CRC24B):
     K = BG_K[bg] * Z
-    nb = 16 if poly == CRC16 else 24
+    nb = CRC_ORDER[poly]
     msg = rng.integers(0, 2, K, dtype=np.uint8)
     c = o_crc_bits(poly, msg[:K - nof_filler - nb])
     msg[K - nof_filler - nb:K - nof_filler] = [(c >> (nb - 1 - i)) & 1 for i in range(nb)]
@@ -318,6 +318,34 @@ def test_wave_kernel_full_bundles(ctx, ldpc_kernel):
     for c in cases[::3]:
         c["flags"] = 1
     bad = run_batch(ctx, cases[:200], ldpc_kernel)
+    assert not bad, bad[:10]
+
+
+def test_crc_by_division(ctx, ldpc_kernel):
+    """CRC24C and CRC11 have no mask table: every kernel checks them by division (partial remainder per 32-bit word times its position
+    weight). One wave-kernel bundle of the smallest Z, the largest wave Z, the smallest packed Z, a two-wavefront and the three-wavefront
+    Z; clean (one iteration) and noisy (early stops at several iteration counts) inputs, early stop and CRC after the last iteration;
+    one codeblock per base graph with fillers (message length no multiple of 32: the tail of the division), and one CRC24B codeblock
+    so that the mask form and the division meet in one batch."""
+    rng = np.random.default_rng(31)
+    cases = []
+
+    def add(bg, Z, poly, nf, sigmas, modes):
+        K = BG_K[bg] * Z
+        msg, cw = make_codeword(bg, Z, rng, nf, poly)
+        for sigma in sigmas:
+            llr = noisy_llr(cw, sigma, rng)
+            if nf:
+                llr[K - 2 * Z - nf:K - 2 * Z] = 127
+            cases.extend(dict(bg=bg, Z=Z, llr=llr, crc=poly, max_iter=6, nf=nf, flags=f) for f in modes)
+
+    for bg, Z, poly, nf in ((2, 2, CRC11, 0), (2, 3, CRC24C, 0), (1, 36, CRC24C, 0), (2, 64, CRC11, 0), (1, 72, CRC24C, 20), (2, 208, CRC11, 37),
+                            (1, 384, CRC24C, 0), (2, 384, CRC11, 0)):
+        add(bg, Z, poly, nf, (0.3, 0.9), (0, 1))
+    add(1, 72, CRC24B, 0, (0.3,), (0,))
+    assert len(cases) == 33
+    assert all((BG_K[c["bg"]] * c["Z"] - c["nf"]) % 32 for c in cases if c["nf"])
+    bad = run_batch(ctx, cases, ldpc_kernel)
     assert not bad, bad[:10]
 
 

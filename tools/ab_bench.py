@@ -18,7 +18,7 @@ def build(specs):
         d = os.path.join(AB, name)
         os.makedirs(d, exist_ok=True)
         obj = os.path.join(d, src.replace(".hip", ".o"))
-        per_file = ["-mllvm", "-enable-post-misched=false"] if src == "ldpc_decode_pk.hip" else []  # as the Makefile builds that file
+        per_file = ["-mllvm", "-enable-post-misched=false"] if src in ("ldpc_decode_pk.hip", "ldpc_decode_pkw.hip") else []  # as the Makefile builds these files
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include")]
                               + per_file + [f for f in flags.split(",") if f] + ["-c", os.path.join(PKG, "csrc", src), "-o", obj])
         others = [o for o in sorted(glob.glob(os.path.join(PKG, "build", "*.o"))) if os.path.basename(o) != os.path.basename(obj)]
