@@ -11,7 +11,7 @@ from oracle_lib import o_dmrs_pusch_estimate, o_gold
 pytestmark = pytest.mark.gpu
 
 
-def make_case(rng, nprb_grid, alloc, nports, nl, dm_syms, numerology=1, slot=3, scr=77, nscid=0, scaling=1.0, delay=0.0, snr_db=25.0):
+def make_case(rng, nprb_grid, alloc, nports, nl, dm_syms, numerology=1, slot=3, scr=77, nscid=0, scaling=1.0, delay=0.0, snr_db=25.0, first=0, nof=14):
     """Builds a grid that really contains the DM-RS of a flat/2-tap channel with a delay (valid pilots), plus noise."""
     rb = np.zeros(nprb_grid, np.uint8)
     rb[alloc] = 1
@@ -40,20 +40,46 @@ def make_case(rng, nprb_grid, alloc, nports, nl, dm_syms, numerology=1, slot=3, 
                         kk = r * 12 + 2 * q + delta
                         g[p, l, kk] += np.complex64(scaling * h[kk] * pil[r * 6 + q] * wf)
                         idx += 1
-    return (numerology, slot, False, scr, nscid, scaling, sm, rb, 0, 14, nl, g)
+    return (numerology, slot, False, scr, nscid, scaling, sm, rb, first, nof, nl, g)
 
 
-def run(ctx, cases):
+def select_ports(case, sel):
+    """A case built on four grid ports, received on the ports `sel` only: the other ports of the grid become NaN, so that a read of a port the
+    job does not name cannot go unnoticed. Returns (case, sel) for run(..., sels=...)."""
+    g = case[-1].copy()
+    assert g.shape[0] == 4 and len(set(sel)) == len(sel) and all(0 <= p < 4 for p in sel)
+    g[[p for p in range(4) if p not in sel]] = np.nan
+    return case[:-1] + (g,), list(sel)
+
+
+CE_GUARD, SC_GUARD, SC_SENTINEL = 5, 3, -77.0  # elements between the records of two jobs; the estimate's sentinel is 1.0
+
+
+def run(ctx, cases, sels=None, compact=False, device=None, room_4x4=False, check=True):
+    """Runs the cases as one batch and compares every job with the oracle. sels: per case None (the grid's ports 0..n-1 in order) or the list
+    of grid ports the job receives on (the grid then has four ports; the unused tail of rx_ports names a port outside the selection).
+    compact: ce_compact = 1 (one row per (layer, port)). device: None (host descriptors), "nohint" or "hint" (descriptors in device memory,
+    without / with the largest port and layer counts of the batch). room_4x4: every job's estimate and scalar records are followed by room
+    for the (layer, port) pairs up to 4 x 4 that it does not have, which must stay untouched. Records are separated by guard elements.
+    Returns per job (estimate [nl][ports][rows][nsc], scalars [ports][nl][5]) as the device wrote them."""
     import torch
     import miphy
+    sels = sels or [None] * len(cases)
     jobs = np.zeros(len(cases), dtype=miphy.PuschChestJob)
-    grids, g_off, ce_off, sc_off = [], 0, 0, 0
-    for i, (mu, slot, t2, scr, nscid, scaling, sm, rb, first, nof, nl, g) in enumerate(cases):
-        nports, _, nsc = g.shape
+    grids, g_off, ce_off, sc_off = [], 0, CE_GUARD, SC_GUARD
+    shapes = []
+    for i, ((mu, slot, t2, scr, nscid, scaling, sm, rb, first, nof, nl, g), sel) in enumerate(zip(cases, sels)):
+        _, _, nsc = g.shape
+        nports = g.shape[0] if sel is None else len(sel)
         j = jobs[i]
         j["numerology"], j["slot_in_frame"], j["scrambling_id"], j["scaling"] = mu, slot, scr, scaling
         j["n_scid"], j["nof_tx_layers"], j["nof_rx_ports"], j["first_symbol"], j["nof_symbols"] = nscid, nl, nports, first, nof
-        j["rx_ports"] = [0, 1, 2, 3]
+        if sel is None:
+            j["rx_ports"] = [0, 1, 2, 3]
+        else:
+            spare = [p for p in range(4) if p not in sel]
+            j["rx_ports"] = list(sel) + spare[:1] * (4 - len(sel))
+        j["ce_compact"] = int(compact)
         j["symbols_mask"] = sum(int(b) << l for l, b in enumerate(sm))
         j["grid_nof_prb"] = rb.size
         m = [0] * 5
@@ -64,24 +90,46 @@ def run(ctx, cases):
         j["grid_offset"], j["ce_offset"], j["scalars_offset"] = g_off, ce_off, sc_off
         grids.append(g.reshape(-1))
         g_off += g.size
-        ce_off += nl * nports * (first + nof) * nsc
-        sc_off += nports * nl * 5
+        rows = 1 if compact else first + nof
+        shapes.append((nl, nports, rows, nsc))
+        ce_off += (16 if room_4x4 else nl * nports) * rows * nsc + CE_GUARD
+        sc_off += (16 if room_4x4 else nports * nl) * 5 + SC_GUARD
     g_d = torch.from_numpy(np.concatenate(grids)).cuda()
     ce_d = torch.ones(ce_off, dtype=torch.complex64, device="cuda")
-    sc_d = torch.zeros(sc_off, dtype=torch.float32, device="cuda")
-    ctx.dmrs_pusch_estimate_batch(jobs, g_d, ce_d, sc_d)
+    sc_d = torch.full((sc_off,), SC_SENTINEL, dtype=torch.float32, device="cuda")
+    if device is None:
+        ctx.dmrs_pusch_estimate_batch(jobs, g_d, ce_d, sc_d)
+    else:
+        hint = dict(max_ports=int(jobs["nof_rx_ports"].max()), max_layers=int(jobs["nof_tx_layers"].max())) if device == "hint" else {}
+        ctx.dmrs_pusch_estimate_batch(torch.from_numpy(jobs.view(np.uint8)).cuda(), g_d, ce_d, sc_d, **hint)
     torch.cuda.synchronize()
     ce, sc = ce_d.cpu().numpy(), sc_d.cpu().numpy()
+    # nothing but the records themselves is written: guards, and the room behind the records
+    used_ce, used_sc = np.zeros(ce.size, bool), np.zeros(sc.size, bool)
+    out = []
+    for i, shp in enumerate(shapes):
+        c0, s0 = int(jobs[i]["ce_offset"]), int(jobs[i]["scalars_offset"])
+        n_ce, n_sc = int(np.prod(shp)), shp[0] * shp[1] * 5
+        used_ce[c0:c0 + n_ce] = True
+        used_sc[s0:s0 + n_sc] = True
+        out.append((ce[c0:c0 + n_ce].reshape(shp), sc[s0:s0 + n_sc].reshape(shp[1], shp[0], 5)))
+    assert np.all(ce[~used_ce] == 1.0) and np.all(sc[~used_sc] == np.float32(SC_SENTINEL)), "written outside the jobs' records"
+    if not check:
+        return out
     oracle_cache = {}
-    for i, a in enumerate(cases):
+    for i, (a, sel) in enumerate(zip(cases, sels)):
         mu, slot, t2, scr, nscid, scaling, sm, rb, first, nof, nl, g = a
-        nports, _, nsc = g.shape
         if id(a) not in oracle_cache:  # (the large-batch test repeats the same case objects within one call)
-            oracle_cache[id(a)] = o_dmrs_pusch_estimate(*a)
+            oracle_cache[id(a)] = o_dmrs_pusch_estimate(*(a if sel is None else a[:-1] + (np.ascontiguousarray(g[sel]),)))
         exp_ce, exp_sc = oracle_cache[id(a)]
-        got_ce = ce[int(jobs[i]["ce_offset"]):][:exp_ce.size].reshape(exp_ce.shape)
-        got_sc = sc[int(jobs[i]["scalars_offset"]):][:exp_sc.size].reshape(exp_sc.shape)
+        got_ce, got_sc = out[i]
+        assert got_sc.shape == exp_sc.shape
         mask = np.repeat(rb.astype(bool), 12)
+        if compact:  # one row, valid for every symbol of the allocation: the oracle's rows are all the same
+            exp_ce = exp_ce[:, :, first:first + 1]
+        else:
+            assert np.all(got_ce[:, :, :first] == 1.0), "rows in front of the allocation are left untouched"
+            got_ce, exp_ce = got_ce[:, :, first:], exp_ce[:, :, first:]
         err = np.abs(got_ce[..., mask] - exp_ce[..., mask]).max() / np.abs(exp_ce[..., mask]).max()
         assert err < 1e-4, (i, err)
         # unallocated PRBs are left untouched (they keep the caller's initial value)
@@ -91,6 +139,7 @@ def run(ctx, cases):
             assert rel.max() < 1e-4, (i, k, got_sc[..., k], exp_sc[..., k])
         tap = 1.0 / (4096 * 15000.0 * (1 << mu))
         assert np.abs(got_sc[..., 4] - exp_sc[..., 4]).max() <= 1.01 * tap, (i, got_sc[..., 4], exp_sc[..., 4])
+    return out
 
 
 def test_chest_configs(ctx):
@@ -130,6 +179,92 @@ def test_chest_random_grid_like_benchmark(ctx):
         sm[syms] = 1
         g = ((rng.standard_normal((nports, 14, 273 * 12)) + 1j * rng.standard_normal((nports, 14, 273 * 12))) * np.sqrt(0.5)).astype(np.complex64)
         cases.append((1, 0, False, 0, 0, 1.0, sm, rb, 0, 14, nl, g))
+    run(ctx, cases)
+
+
+SCATTERED = [63, 64, 65, 127, 128, 191, 192, 255, 256, 274]  # on a 275-PRB grid: an allocation in every 64-bit word of rb_mask
+
+
+def test_chest_port_selection(ctx):
+    """rx_ports: the job receives on the grid ports it names, in the order it names them (the adapter passes the PDU's own list). Four-port
+    grids with a different channel on every port, the ports outside the selection NaN; expected: the oracle on grid[sel], scalars by logical
+    port. One and two layers, one batch."""
+    rng = np.random.default_rng(41)
+    cases, sels = [], []
+    for nl, dsyms, alloc in ((1, [2, 7, 11], slice(4, 40)), (2, [3, 10], [0, 1, 2, 10, 11, 30, 31, 32, 33, 51])):
+        for k, sel in enumerate(([2], [3, 1], [1, 3, 0], [3, 2, 1, 0])):
+            c, sl = select_ports(make_case(rng, 52, alloc, 4, nl, dsyms, slot=5 + k, scr=300 + k, delay=4.0 * k - 6.0), sel)
+            cases.append(c)
+            sels.append(sl)
+    run(ctx, cases, sels)
+
+
+def test_chest_device_resident_jobs(ctx):
+    """Descriptors in device memory cannot be inspected by the host: without a hint the launch is sized for 4 ports x 4 layers and the
+    workgroups of the (port, layer) pairs a job does not have leave at once; with the hint it is sized as for host descriptors. Both must
+    write exactly what the host-descriptor run writes (compared with the oracle there) and nothing else: the room for the pairs a job does
+    not have keeps its sentinel (run() checks everything outside the records)."""
+    import torch
+    rng = np.random.default_rng(42)
+    cases = [make_case(rng, 52, slice(3, 3 + 10 * nports), nports, nl, dsyms, slot=2 + nports, delay=3.0 * nl)
+             for nports, nl, dsyms in ((1, 1, [2]), (2, 2, [2, 11]), (4, 1, [2, 7, 11]), (3, 2, [3, 10]))]
+    # precondition: small enough for the three launches (sized 4 x 2, 4 x 4 and 4 x 2 workgroups per job) to be cut the same way
+    assert len(cases) * 16 * 2 <= torch.cuda.get_device_properties(0).multi_processor_count
+    host = run(ctx, cases, room_4x4=True)
+    for device in ("nohint", "hint"):
+        dev = run(ctx, cases, device=device, room_4x4=True, check=False)
+        for i, ((hce, hsc), (dce, dsc)) in enumerate(zip(host, dev)):
+            assert hce.tobytes() == dce.tobytes() and hsc.tobytes() == dsc.tobytes(), (device, i)
+
+
+def test_chest_compact_estimate(ctx):
+    """ce_compact = 1 (what the fused processor asks for): one row per (layer, port), bit for bit row first_symbol of the full estimate of the
+    same job, written on the allocated PRBs only (run() checks the rest); the scalars are the same."""
+    rng = np.random.default_rng(43)
+    cases = [make_case(rng, 52, [0, 1, 2, 10, 11, 30, 31, 32, 33, 51], 2, 2, [2, 11], delay=5.0),
+             make_case(rng, 25, slice(3, 20), 3, 1, [3, 10], first=2, nof=10, delay=-8.0),
+             make_case(rng, 106, slice(0, 106), 1, 1, [2, 7, 11], delay=2.0)]
+    full = run(ctx, cases)
+    comp = run(ctx, cases, compact=True)
+    for i, (case, (fce, fsc), (cce, csc)) in enumerate(zip(cases, full, comp)):
+        first = case[8]
+        assert cce.shape[2] == 1 and cce[:, :, 0].tobytes() == np.ascontiguousarray(fce[:, :, first]).tobytes(), i
+        assert csc.tobytes() == fsc.tobytes(), i
+
+
+def test_chest_partial_slots_and_dmrs_counts(ctx):
+    """Allocations that do not start at symbol 0 (nothing is written in front of them); 1, 2, 3 and 4 DM-RS symbols on otherwise equal jobs
+    (below three the noise variance is EPRE / 1000, from three on it is measured); a DM-RS mask bit behind the allocation is ignored."""
+    cases = [make_case(np.random.default_rng(44), 52, slice(5, 35), 2, 1, [3, 10], first=2, nof=10, delay=6.0)]
+    for dsyms in ([2], [2, 11], [2, 7, 11], [2, 5, 8, 11]):
+        cases.append(make_case(np.random.default_rng(45), 24, slice(2, 22), 2, 2, dsyms, delay=-5.0))
+    # bit 12 is set (and the grid holds pilots there) but the allocation ends at symbol 11: two DM-RS symbols, not three
+    cases.append(make_case(np.random.default_rng(46), 24, slice(2, 22), 1, 1, [2, 7, 12], first=0, nof=12, delay=3.0))
+    cases.append(make_case(np.random.default_rng(46), 24, slice(2, 22), 1, 1, [2, 7, 12], first=1, nof=13, delay=3.0))  # here it counts
+    out = run(ctx, cases)
+    nv = [float(sc[0, 0, 2] / sc[0, 0, 1]) for _, sc in out]  # noise variance / EPRE
+    assert abs(nv[1] - 1e-3) < 1e-7 and abs(nv[2] - 1e-3) < 1e-7 and abs(nv[3] - 1e-3) > 1e-4 and abs(nv[4] - 1e-3) > 1e-4, nv
+    assert abs(nv[5] - 1e-3) < 1e-7 and abs(nv[6] - 1e-3) > 1e-4, nv
+
+
+def test_chest_numerologies_and_identifiers(ctx):
+    """Numerology 0..3 (the time alignment is counted in IDFT taps of 1 / (4096 * subcarrier spacing): run() scales its tolerance of one tap),
+    each in the last slot of its frame, with n_scid = 1 and the largest scrambling identifier."""
+    rng = np.random.default_rng(47)
+    cases = [make_case(rng, 52, slice(5, 35), 2, 1 + (mu & 1), [2, 11], numerology=mu, slot=10 * (1 << mu) - 1, scr=65535, nscid=1, delay=7.0 - 4.0 * mu)
+             for mu in range(4)]
+    out = run(ctx, cases)
+    for mu, (_, sc) in enumerate(out):  # the delay comes back in seconds of the job's own numerology
+        tap = 1.0 / (4096 * 15000.0 * (1 << mu))
+        assert np.abs(sc[..., 4] - (7.0 - 4.0 * mu) * tap).max() <= 1.01 * tap, (mu, sc[..., 4])
+
+
+def test_chest_allocations_across_mask_words(ctx):
+    """The widest grid: an allocation scattered over all five 64-bit words of rb_mask, and a single PRB in the last bit in use."""
+    rng = np.random.default_rng(48)
+    cases = [make_case(rng, 275, SCATTERED, 2, 2, [2, 11], numerology=3, slot=79, delay=0.0),
+             make_case(rng, 275, SCATTERED, 1, 1, [2, 7, 11], delay=4.0),
+             make_case(rng, 275, [274], 2, 1, [2], delay=-3.0)]
     run(ctx, cases)
 
 

@@ -236,3 +236,154 @@ def test_placeholders_and_evm_match_oracle(ctx, mod, ports, cdm):
     assert np.all(e[:3] == -1.0) and np.all(e[17:] == -1.0) and e[3] == 0.0 and e[3 + 13] == 0.0  # symbols outside the allocation contribute 0
     evm = float(np.sqrt(e[3:17].astype(np.float64).sum() / n_re))
     assert abs(evm - oe) <= 2e-6 * oe + 1e-7, (evm, oe)
+
+
+# ------------------------------------------------------------------------------------------------ port lists, short estimates, the symbol split
+def _item(rng, mod, sel, compact, cdm, type2, rb, start, nof, dsyms, ce_rows=14):
+    """One transmission received on the grid ports `sel` of a four-port grid (the other ports are NaN: a read of a port the job does not name
+    shows up in the LLRs), with its oracle LLRs. The estimate has len(sel) ports in the job's order: one row (compact) or ce_rows rows.
+    As elsewhere in this file: one zero channel coefficient and one NaN sample inside the allocation."""
+    nprb = rb.size
+    nsc = nprb * 12
+    dm = np.zeros(14, np.uint8)
+    dm[list(dsyms)] = 1
+    grid = np.full((4, 14, nsc), np.nan + 1j * np.nan, np.complex64)
+    grid[sel] = (rng.standard_normal((len(sel), 14, nsc)) + 1j * rng.standard_normal((len(sel), 14, nsc))).astype(np.complex64)
+    rows = 1 if compact else ce_rows
+    est = (rng.standard_normal((len(sel), rows, nsc)) + 1j * rng.standard_normal((len(sel), rows, nsc))).astype(np.complex64)
+    mid = int(np.nonzero(rb)[0][rb.sum() // 2])
+    est[0, 0 if compact else start, 12 * mid + 5] = 0
+    grid[sel[-1], start + 1, 12 * mid + 3] = np.nan
+    rnti, n_id, nv = int(rng.integers(1, 65536)), int(rng.integers(0, 1024)), float(rng.uniform(0.01, 0.5))
+    exp = O.o_pusch_demodulate(rnti, n_id, mod, start, nof, dm, type2, cdm, rb, grid[sel], np.repeat(est, 14, axis=1) if compact else est, nv)[0]
+    return dict(mod=mod, sel=list(sel), compact=compact, cdm=cdm, type2=type2, rb=rb, start=start, nof=nof, dm=dm, rows=rows, grid=grid, est=est,
+                rnti=rnti, n_id=n_id, nv=nv, exp=exp)
+
+
+LLR_SENTINEL = 99
+
+
+def _run_items(ctx, items, order, llr_offsets, device_jobs, rng):
+    """Launches items[order[k]] with its codeword at llr_offsets[k] as one batch (copies of an item share its grid, estimate and scalars) and
+    requires every codeword to equal the item's oracle LLRs and every other byte of the output to keep its sentinel. The scalars array
+    is random but for the noise variances, each job's block starts at an offset of its own that is no multiple of five, and the unused tail
+    of rx_ports names a port outside the selection."""
+    import torch
+    import miphy
+    g_off, e_off, s_off = [], [], []
+    go = eo = 0
+    so = 3
+    for it in items:
+        g_off.append(go)
+        e_off.append(eo)
+        s_off.append(so)
+        go += it["grid"].size
+        eo += it["est"].size
+        so += 5 * len(it["sel"]) + 1
+    sc = rng.uniform(0.6, 50.0, so + 8).astype(np.float32)  # a noise variance taken from elsewhere is finite, and wrong
+    for it, s in zip(items, s_off):
+        sc[s + 2] = it["nv"]
+    jobs = []
+    for k, lo in zip(order, llr_offsets):
+        it = items[k]
+        j = _job(miphy, it["rnti"], it["n_id"], it["mod"], it["start"], it["nof"], it["dm"], it["type2"], it["cdm"], it["rb"], len(it["sel"]),
+                 it["rows"] if not it["compact"] else 14, g_off[k], e_off[k], s_off[k], lo)
+        spare = [p for p in range(4) if p not in it["sel"]]
+        j["rx_ports"] = it["sel"] + spare[:1] * (4 - len(it["sel"]))
+        j["ce_compact"] = int(it["compact"])
+        assert j["nof_llr"] == it["exp"].size
+        jobs.append(j)
+    jobs = np.array(jobs, dtype=miphy.PuschDemodJob)
+    total = max(lo + items[k]["exp"].size for k, lo in zip(order, llr_offsets)) + 64
+    out = torch.full((total,), LLR_SENTINEL, dtype=torch.int8, device="cuda")
+    g = torch.from_numpy(np.concatenate([it["grid"].reshape(-1) for it in items])).cuda()
+    # (behind the last estimate: NaN for as much as a stride of 14 rows on four ports could reach, so that a wrong stride reads a wrong value)
+    tail = np.full(4 * 14 * max(it["rb"].size for it in items) * 12, np.nan + 1j * np.nan, np.complex64)
+    h = torch.from_numpy(np.concatenate([it["est"].reshape(-1) for it in items] + [tail])).cuda()
+    ctx.pusch_demodulate_batch(torch.from_numpy(jobs.view(np.uint8)).cuda() if device_jobs else jobs, g, h, torch.from_numpy(sc).cuda(), out)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    used = np.zeros(total, bool)
+    for n, (k, lo) in enumerate(zip(order, llr_offsets)):
+        exp = items[k]["exp"]
+        assert not used[lo:lo + exp.size].any()
+        used[lo:lo + exp.size] = True
+        bad = np.nonzero(got[lo:lo + exp.size] != exp)[0]
+        assert bad.size == 0, (n, k, bad.size, bad[:8], got[lo:lo + exp.size][bad[:8]], exp[bad[:8]])
+    assert np.all(got[~used] == LLR_SENTINEL), "bytes between the codewords were written"
+
+
+def _offsets(sizes, pads=(3, 2, 1, 0, 6, 5, 4, 7)):
+    """Codeword starts with guard bytes in between, at every residue modulo 8 in turn (odd, 2 mod 4, aligned)."""
+    offs, cur = [], 0
+    for n, sz in enumerate(sizes):
+        cur = (cur + 7) // 8 * 8 + pads[n % len(pads)]
+        offs.append(cur)
+        cur += sz + 1
+    return offs
+
+
+@pytest.mark.parametrize("device_jobs", [False, True])
+def test_port_selection_matches_oracle(ctx, device_jobs):
+    """rx_ports on all three walks over the OFDM symbols: one port with the compact estimate (every request in flight at once), several
+    ports with the compact estimate and the full estimate (the general walk), pi/2-BPSK. One batch; the noise variance of every job sits
+    at scalars_offset + 2 of a scalars_offset of its own."""
+    rng = np.random.default_rng(5100)
+    rb = (rng.uniform(size=30) < 0.85).astype(np.uint8)
+    rb[[0, 29]] = 1
+    items = [_item(rng, 6, [2], True, 2, 0, rb, 0, 14, (2,)),
+             _item(rng, 4, [3, 0], True, 1, 0, rb, 2, 12, (3, 10)),
+             _item(rng, 8, [2, 0, 3, 1], True, 2, 0, rb, 0, 14, (2, 11)),
+             _item(rng, 6, [1, 3, 0], False, 2, 1, rb, 0, 13, (2, 7, 11)),
+             _item(rng, 1, [1], True, 2, 0, rb, 1, 9, (4,)),
+             _item(rng, 2, [3], True, 1, 0, rb, 0, 14, (2,))]
+    offs = _offsets([it["exp"].size for it in items])
+    _run_items(ctx, items, range(len(items)), offs, device_jobs, rng)
+
+
+@pytest.mark.parametrize("device_jobs", [False, True])
+def test_estimates_shorter_than_a_slot(ctx, device_jobs):
+    """The estimator writes first_symbol + nof_symbols rows per port: ce_nof_symbols is the stride between the ports of a full estimate."""
+    rng = np.random.default_rng(5200)
+    rb = np.ones(13, np.uint8)
+    rb[4] = 0
+    items = [_item(rng, 4, [3, 1], False, 2, 0, rb, 1, 9, (4,), ce_rows=10),
+             _item(rng, 6, [1, 0, 3, 2], False, 1, 0, rb, 1, 9, (2, 7), ce_rows=10),
+             _item(rng, 8, [0, 2], False, 2, 0, rb, 0, 12, (2, 11), ce_rows=12),
+             _item(rng, 2, [2, 3, 1, 0], False, 2, 1, rb, 0, 12, (3,), ce_rows=12)]
+    offs = _offsets([it["exp"].size for it in items])
+    _run_items(ctx, items, range(len(items)), offs, device_jobs, rng)
+
+
+@pytest.fixture(scope="module")
+def split_items():
+    """Eight transmissions of 22 PRB on a 24-PRB grid: two chunks of subcarriers, the second with 8 live lanes."""
+    rng = np.random.default_rng(5300)
+    rb = np.ones(24, np.uint8)
+    rb[[5, 17]] = 0
+    return [_item(rng, 8, [1], True, 2, 0, rb, 0, 14, (2,)),
+            _item(rng, 6, [3], True, 1, 1, rb, 1, 9, (4, 8)),
+            _item(rng, 4, [2, 0], True, 1, 0, rb, 2, 12, (3, 10)),
+            _item(rng, 2, [0, 3], False, 3, 1, rb, 0, 13, (2,), ce_rows=14),
+            _item(rng, 1, [2], True, 2, 0, rb, 1, 9, (4,)),
+            _item(rng, 6, [1, 2], False, 2, 0, rb, 0, 13, (2, 7, 11), ce_rows=13),
+            _item(rng, 8, [3, 1], True, 2, 1, rb, 2, 12, (2, 11)),
+            _item(rng, 2, [0], True, 1, 0, rb, 0, 14, (2, 11))]
+
+
+@pytest.mark.parametrize("device_jobs", [False, True])
+@pytest.mark.parametrize("q", [1, 2, 3, 4])
+def test_every_symbol_split(ctx, split_items, q, device_jobs):
+    """A batch that leaves compute units idle cuts the OFDM symbols of every transmission into up to four parts, one workgroup each; a part
+    starts at the data elements in front of its first symbol and may own no symbol at all (9 symbols in 4 parts). The batch sizes make
+    compute units // (transmissions x 2 chunks) equal q = 1, 2, 3 and 4 with host descriptors (asserted for the chip at hand); with
+    descriptors in device memory the launch is sized for the widest grid instead. Every copy of every transmission must equal the
+    oracle, codewords at every alignment, the bytes between them untouched."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = cus // (2 * q)
+    assert n >= len(split_items) and cus // (n * 2) == q, (cus, n, q)
+    order = [k % len(split_items) for k in range(n)]
+    offs = _offsets([split_items[k]["exp"].size for k in order])
+    assert any(o % 2 for o in offs) and any(o % 4 == 2 for o in offs)
+    _run_items(ctx, split_items, order, offs, device_jobs, np.random.default_rng(q))
