@@ -164,6 +164,9 @@ __device__ __forceinline__ int pk_fused_image_out(const int8_t* __restrict__ sof
   u32x4*       dst  = reinterpret_cast<u32x4*>(llr_img);
   const uint4* src  = reinterpret_cast<const uint4*>(soft + 2 * Z);
   const int    nimg = in_len >> 4, nall = (((bgi ? 50 : 66) * Z) >> 4);
+  // (the lane index is made opaque, as in pk_fused_load: the compiler otherwise hoists this lane's share of the store address out of the
+  // codeblock loop and carries it across the decoder in scratch)
+  asm volatile("" : "+v"(tid));
   for (int q = tid; q < nimg; q += nt) {
     const uint4 v = src[q];
     const u32x4 o = {v.x, v.y, v.z, v.w};
@@ -407,10 +410,12 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
 #endif
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO1);
   part_edges<PARTS> pe; // latency form: this part's edges of the layer about to run, fetched while the layer before it runs
+  // Iteration 0 starts at layer 1: layer 0 reads both punctured columns, which are zero then, so all its messages are zero and no
+  // soft bit changes (update_rows_pk_zero, ldpc_pk_device.h). Its messages are first written in iteration 1, by the FIRST instance.
   if (SPLIT)
-    load_part_edges<PARTS>(pe, edges_g, (uint32_t)__builtin_amdgcn_readlane((int)lay_info, 0), part);
+    load_part_edges<PARTS>(pe, edges_g, (uint32_t)__builtin_amdgcn_readlane((int)lay_info, 1), part); // the first layer visited
   for (int it = 0; it < max_iter; ++it) {
-    for (int m = 0; m < nof_layers; ++m) {
+    for (int m = (it == 0) ? 1 : 0; m < nof_layers; ++m) {
       const uint32_t  li    = (uint32_t)__builtin_amdgcn_readlane((int)lay_info, m);
       const int       e0    = (int)(li & 0x3ffu);
       const int       d     = (int)((li >> 10) & 0x3fu);
@@ -421,24 +426,16 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
         const uint32_t    lin  = (uint32_t)__builtin_amdgcn_readlane((int)lay_info, (m + 1 < nof_layers) ? m + 1 : 0);
         auto              next = [&]() { load_part_edges<PARTS>(pn, edges_g, lin, part); };
         uint32_t* cl = c2v_lane + 64 * (li >> 16);
-        if (it == 0)
+        if (it == 0 || (it == 1 && m == 0)) // (the latency form keeps the general first-visit instance for layers 1 and 2)
           update_rows_pk_split<true, PARTS>(pe, part, soft, cl, lr, Hv, Zv, lr < H, xch, nth, next);
         else
           update_rows_pk_split<false, PARTS>(pe, part, soft, cl, lr, Hv, Zv, lr < H, xch, nth, next);
         pe = pn;
       } else if (tid < H) {
         if (GMSG && (int)(li >> 16) >= pairs_lds) { // this layer's messages live in global memory (separate code: the address space is part of the instruction)
-          uint32_t* cl = c2v_glob + 64 * (li >> 16);
-          if (it == 0)
-            update_rows_pk_any<true>(d, soft, cl, edges, tid, Hv, Zv);
-          else
-            update_rows_pk_any<false>(d, soft, cl, edges, tid, Hv, Zv);
+          update_rows_pk_visit(it, m, d, soft, c2v_glob + 64 * (li >> 16), edges, tid, Hv, Zv);
         } else {
-          uint32_t* cl = c2v_lane + 64 * (li >> 16);
-          if (it == 0)
-            update_rows_pk_any<true>(d, soft, cl, edges, tid, Hv, Zv);
-          else
-            update_rows_pk_any<false>(d, soft, cl, edges, tid, Hv, Zv);
+          update_rows_pk_visit(it, m, d, soft, c2v_lane + 64 * (li >> 16), edges, tid, Hv, Zv);
         }
       }
       PROF_T(p_l1);

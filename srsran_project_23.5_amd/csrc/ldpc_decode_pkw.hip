@@ -205,18 +205,14 @@ ldpc_decode_pkw_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
     for (int it = 0; it < max_iter; ++it) {
       if (!__any(run))
         break;
-      for (int m = 0; m < nlay_max; ++m) {
+      // Iteration 0 starts at layer 1, for every group alike (update_rows_pk_zero, ldpc_pk_device.h: layer 0 changes nothing there).
+      for (int m = (it == 0) ? 1 : 0; m < nlay_max; ++m) {
         const uint32_t  li    = (uint32_t)__builtin_amdgcn_readlane((int)lay_info, m);
         const int       e0    = (int)(li & 0x3ffu);
         const int       d     = (int)((li >> 10) & 0x3fu);
         const uint32_t* edges = edges_g + 2 * e0;
-        if (run && m < nlay) {
-          uint32_t* cl = msg0 + 64 * (li >> 16);
-          if (it == 0)
-            update_rows_pk_any<true>(d, soft, cl, edges, l, Hv, Zv, base);
-          else
-            update_rows_pk_any<false>(d, soft, cl, edges, l, Hv, Zv, base);
-        }
+        if (run && m < nlay)
+          update_rows_pk_visit(it, m, d, soft, msg0 + 64 * (li >> 16), edges, l, Hv, Zv, base);
         __syncthreads();
       }
       if (use_crc && !final_only) { // ldpc_decoder_impl.cpp:126-133

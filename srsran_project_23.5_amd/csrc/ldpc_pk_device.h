@@ -92,6 +92,30 @@ constexpr int LLR_MAX = 120;
 constexpr int LLR_INF = 127;
 constexpr int INF_MUL = 255; // an infinite soft bit (|s| > 120) becomes a message of magnitude >= 255 + 24
 
+// Stage A of a row update, shared by its forms: both rows' soft-bit addresses of every edge of the layer with packed 16-bit arithmetic:
+// {l, l + H} + shift, wrap at Z by the unsigned minimum of p and p - Z, + column offset -- four packed instructions for the two rows, then
+// one mask and one shift to split the pair (LDS addresses stay below 2^16).
+template <int D>
+__device__ __forceinline__ void pk_edge_addresses(uint32_t (&adrA)[D], uint32_t (&adrB)[D], const uint32_t* __restrict__ edges, int l, int H, int Z, uint32_t base)
+{
+  typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+  const u16x2 X  = {(unsigned short)l, (unsigned short)(l + H)};
+  const u16x2 Zs = {(unsigned short)Z, (unsigned short)Z};
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+#ifdef LDPC_PK_EMU_NOSLOAD // timing-only (WRONG results): no scalar loads of the edge table
+    const unsigned short sh = (unsigned short)(7 * j + (l & 1)), co = (unsigned short)(j * Z);
+#else
+    const unsigned short sh = (unsigned short)edges[2 * j], co = (unsigned short)edges[2 * j + 1];
+#endif
+    const u16x2 T = X + u16x2{sh, sh};
+    const u16x2 R = __builtin_elementwise_min(T, (u16x2)(T - Zs));
+    const uint32_t P = __builtin_bit_cast(uint32_t, (u16x2)(R + u16x2{co, co}));
+    adrA[j] = (P & 0xffffu) + base;
+    adrB[j] = (P >> 16) + base;
+  }
+}
+
 // `base` = LDS byte offset of the codeblock's soft bits (0 where a workgroup holds one codeblock: the term then folds away).
 // PARTS > 1 (latency form of the packed kernel: PARTS times the wavefronts per codeblock, each part of the workgroup owns a share of
 // the edges of a layer): D is the number of edges of THIS part; between the two phases the parts exchange their partial {min1, min2,
@@ -127,26 +151,7 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO); // the address arithmetic and the LDS requests of a layer
   // Stage A: every address of the layer, then every LDS read of the layer in one go (2 soft bits per edge + the old
   // messages): the latency of the LDS pipe is paid once per layer instead of once per group of edges.
-  // Both rows' addresses with packed 16-bit arithmetic: {l, l + H} + shift, wrap at Z by the unsigned minimum of p and p - Z, + column
-  // offset -- four packed instructions for the two rows, then one mask and one shift to split the pair (LDS addresses stay below 2^16).
-  {
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    const u16x2 X  = {(unsigned short)l, (unsigned short)(l + H)};
-    const u16x2 Zs = {(unsigned short)Z, (unsigned short)Z};
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-#ifdef LDPC_PK_EMU_NOSLOAD // timing-only (WRONG results): no scalar loads of the edge table
-      const unsigned short sh = (unsigned short)(7 * j + (l & 1)), co = (unsigned short)(j * Z);
-#else
-      const unsigned short sh = (unsigned short)edges[2 * j], co = (unsigned short)edges[2 * j + 1];
-#endif
-      const u16x2 T = X + u16x2{sh, sh};
-      const u16x2 R = __builtin_elementwise_min(T, (u16x2)(T - Zs));
-      const uint32_t P = __builtin_bit_cast(uint32_t, (u16x2)(R + u16x2{co, co}));
-      adrA[j] = (P & 0xffffu) + base;
-      adrB[j] = (P >> 16) + base;
-    }
-  }
+  pk_edge_addresses<D>(adrA, adrB, edges, l, H, Z, base);
   P2_T(q1);
 #pragma unroll
   for (int j = 0; j < D; ++j) {
@@ -251,6 +256,66 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
   P2_ADD(6, q0, q6);
 }
 
+// The row update of layers 1 and 2 in the FIRST iteration of the throughput form and the wave kernel, where one edge of the row is known
+// to read a soft bit of zero (ZE = its position in the row: 0 in layer 1, 1 in layer 2) and no message of the layer exists yet.
+// What makes it exact ("first iteration"):
+//  - Every decode starts with the two punctured columns, soft bits [0, 2Z), at zero: ldpc_decode_pk.hip pk_fused_load ("the two punctured
+//    nodes") and the plain load ("soft[k] = 0" for k < 2 Z), ldpc_decode_pkw.hip ("clear the group's soft bits").
+//  - Layer 0 of both base graphs holds columns 0 AND 1: two zero inputs, min1 = min2 = 0, every message 0, no soft bit changes -- the
+//    kernels do not visit it in iteration 0 at all, and visit it in iteration 1 with the FIRST instance (no message read = zeros read).
+//  - Layer 1 has column 0 as its edge 0 and lacks column 1; layer 2 has columns 0, 1 as edges 0, 1, and layer 1 has left column 1 at
+//    zero (miphy_ctx.hip asserts these facts of the tables at compile time). With a zero at edge ZE, min1 = 0: the general update gives
+//    every OTHER edge the message 0 and leaves its soft bit as it is; edge ZE gets the product of the other signs times
+//    floor(0.8 min(120, min |s| of the others)) as its message, and, being zero before, as its soft bit too. A further zero among the
+//    other edges (column 0 in layer 2, a zero input) gives min = 0 here and min1 = min2 = 0 there: the same zeros.
+//  - "As it is" has one exception: the general update rewrites a raw input of +-121 ... +-126 to +-127. No output sees it: every
+//    |s| > 120 is treated alike (d != 0 above: same sign, minima clipped at 120, x = 1, stored as +-127 at its next general visit), and
+//    soft bits are not an output -- hard bits, CRC verdict and iteration count are.
+// So: the soft bits of the other D - 1 edges are read, one packed minimum of |s| and the sign parity are accumulated, the value goes to
+// edge ZE's soft bits and byte slots of the layer's message dwords (layout of update_rows_pk, zeros elsewhere); no other soft bit is stored.
+template <int D, int ZE>
+__device__ __forceinline__ void update_rows_pk_zero(int8_t* __restrict__ soft, uint32_t* __restrict__ c2v, const uint32_t* __restrict__ edges, int l, int H, int Z,
+                                                    uint32_t base = 0)
+{
+  static_assert((ZE == 0 || ZE == 1) && D > 2, "the known-zero edge is edge 0 or 1 of its row, and other edges exist");
+  uint32_t adrA[D], adrB[D];
+  int      rawA[D], rawB[D];
+  __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO);
+  pk_edge_addresses<D>(adrA, adrB, edges, l, H, Z, base);
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    if (j != ZE) {
+      rawA[j] = soft[adrA[j]];
+      rawB[j] = soft[adrB[j]];
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO1);
+  __builtin_amdgcn_sched_barrier(0);
+  s16x2    mag = splat(LLR_MAX);
+  uint32_t spx = 0;
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    if (j != ZE) {
+      const s16x2 s = pk_pair(rawA[j], rawB[j]);
+      spx ^= as_u(s);
+      mag = pk_min(mag, pk_max(s, -s));
+    }
+  }
+  __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO2);
+  const uint32_t sA = ((uint32_t)(uint16_t)mag.x * 52428u) >> 16, sB = ((uint32_t)(uint16_t)mag.y * 52428u) >> 16;
+  const s16x2    pm = pk_ashr15(as_s2(spx));
+  const s16x2    c  = as_s2((sA | (sB << 16)) ^ as_u(pm)) - pm; // |c| <= 96: no clamp
+  const uint32_t r  = as_u(c);
+  c2v[0] = ZE ? c2v_pack(splat(0), c) : c2v_pack(c, splat(0));
+#pragma unroll
+  for (int jj = 1; jj < (D + 1) / 2; ++jj)
+    c2v[64 * jj] = 0u; // (an odd degree's last dword holds its last edge twice: zero either way)
+  soft[adrA[ZE]] = (int8_t)r;
+  soft[adrB[ZE]] = (int8_t)(r >> 16);
+  __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO1);
+}
+
 // A part without edges in this layer (a low-degree layer split four ways): it contributes the neutral partial result and takes part in
 // the exchange barrier.
 template <int PARTS, typename MID>
@@ -345,6 +410,34 @@ __device__ __forceinline__ void update_rows_pk_any(int d, int8_t* soft, uint32_t
       update_rows_pk<3, FIRST>(soft, c2v, edges, l, H, Z, base);
       break;
   }
+}
+
+// Layers m = 1 and 2 of the first iteration: the degrees these two layers have in the two base graphs (miphy_ctx.hip asserts them).
+__device__ __forceinline__ void update_rows_pk_zero_any(int m, int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
+{
+  if (m == 1) {
+    if (d == 19)
+      update_rows_pk_zero<19, 0>(soft, c2v, edges, l, H, Z, base);
+    else
+      update_rows_pk_zero<10, 0>(soft, c2v, edges, l, H, Z, base);
+  } else {
+    if (d == 19)
+      update_rows_pk_zero<19, 1>(soft, c2v, edges, l, H, Z, base);
+    else
+      update_rows_pk_zero<8, 1>(soft, c2v, edges, l, H, Z, base);
+  }
+}
+
+// One layer visit of the throughput form and the wave kernel. Iteration 0 starts at layer 1 (see update_rows_pk_zero: layer 0 changes
+// nothing there), so layer 0's messages are first written in iteration 1, by the instance that reads none.
+__device__ __forceinline__ void update_rows_pk_visit(int it, int m, int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
+{
+  if (it == 0 && (m == 1 || m == 2))
+    update_rows_pk_zero_any(m, d, soft, c2v, edges, l, H, Z, base);
+  else if (it == 0 || (it == 1 && m == 0))
+    update_rows_pk_any<true>(d, soft, c2v, edges, l, H, Z, base);
+  else
+    update_rows_pk_any<false>(d, soft, c2v, edges, l, H, Z, base);
 }
 
 __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b, uint32_t poly, uint32_t order)

@@ -55,6 +55,24 @@ static uint32_t gf2_mulmod(uint32_t a, uint32_t b, uint32_t poly, unsigned order
   return r;
 }
 
+// What the decoders' first iteration takes for granted about the first three layers of a base graph (update_rows_pk_zero,
+// ldpc_pk_device.h): layer 0 holds the punctured columns 0 and 1; layer 1 has column 0 as its edge 0, no column 1 and degree d1;
+// layer 2 has columns 0 and 1 as its edges 0 and 1, nowhere else, and degree d2. Checked when a context is made (the generated tables
+// are plain const arrays, which a static_assert cannot read): with a table that stops saying so, miphy_create fails.
+static bool first_layers_as_decoded(const uint16_t* row_start, const uint8_t* col, int d1, int d2)
+{
+  bool has0 = false, has1 = false;
+  for (int e = row_start[0]; e < row_start[1]; ++e)
+    has0 |= col[e] == 0, has1 |= col[e] == 1;
+  bool ok = has0 && has1 && row_start[2] - row_start[1] == d1 && row_start[3] - row_start[2] == d2;
+  ok &= col[row_start[1]] == 0 && col[row_start[2]] == 0 && col[row_start[2] + 1] == 1;
+  for (int e = row_start[1] + 1; e < row_start[2]; ++e)
+    ok &= col[e] > 1;
+  for (int e = row_start[2] + 2; e < row_start[3]; ++e)
+    ok &= col[e] > 1;
+  return ok;
+}
+
 static void build_tables(miphy_graph_tables* t)
 {
   memset(t, 0, sizeof(*t));
@@ -150,6 +168,8 @@ extern "C" int miphy_create(int device, miphy_ctx** out)
     return MIPHY_EINVAL;
   }
   *out = nullptr;
+  MIPHY_REQUIRE(first_layers_as_decoded(NR_LDPC_BG1_ROW_START, NR_LDPC_BG1_COL, 19, 19) && first_layers_as_decoded(NR_LDPC_BG2_ROW_START, NR_LDPC_BG2_COL, 10, 8),
+                "miphy_create: layers 0-2 of the LDPC base graph tables are not what the decoders' first iteration relies on");
   MIPHY_HIP_CHECK(hipSetDevice(device));
   miphy_ctx* c = new (std::nothrow) miphy_ctx();
   if (!c)
