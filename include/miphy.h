@@ -883,6 +883,65 @@ int miphy_prach_generate_batch(miphy_ctx* ctx, const miphy_prach_gen_job* jobs, 
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * OFDM PRACH demodulator  --  replaces srsran::ofdm_prach_demodulator::demodulate
+ *   lib/phy/lower/modulation/ofdm_prach_demodulator_impl.cpp:31-199 (per time-domain occasion: start, cyclic prefix with the 16 kappa
+ *   extensions at 0 and 0.5 ms, one DFT of sampling_rate / RA spacing points per symbol, per frequency-domain occasion the L bins from
+ *   k_start, the lower half of the PRACH grid being the top of the spectrum), lib/ran/prach/prach_preamble_information.cpp (symbol and
+ *   cyclic-prefix lengths, the B value of an A/B pair on the last occasion, get_prach_window_duration),
+ *   lib/ran/prach/prach_frequency_mapping.cpp (nof_rb_ra, k_bar).
+ * One job is one window of baseband samples of one port: nof_samples cf_t at samples_offset in `samples`, the first one being the start
+ * of the slot the configuration counts its start_symbol from. The job's nof_td_occasions x nof_fd_occasions x symbols rows of L cf_t go
+ * to `buffer` laid out like prach_buffer_impl, [td][fd][symbol][L] with the strides max_nof_fd_occasions and max_nof_symbols from
+ * buffer_offset = get_symbol(port, 0, 0, 0): row (td, fd, symbol) starts at buffer_offset + ((td max_nof_fd_occasions + fd)
+ * max_nof_symbols + symbol) L, which is where miphy_prach_job.symbol_offset of a detector job on the same stream can point (symbol 0).
+ * Nothing else of `buffer` is written. DFT sizes: the ones miphy_dft_batch serves; up to 4096 a symbol is one workgroup's transform in
+ * LDS, above (4608 ... 49152) the four-step transform whose second step produces only the bins of the occasions.
+ * JOBS ARE HOST MEMORY in this entry point: launch geometry, DFT sizes, twiddle tables and scratch follow from them. `samples` and
+ * `buffer` are device memory. Every job is checked with miphy_prach_demod_info before anything is enqueued; the table of symbol tasks
+ * travels through the context's staging ring and the call only enqueues. n == 0 does nothing.
+ * miphy_prach_demod_info (host only, no device needed) returns what the reference derives from a job at a sampling rate, or
+ * MIPHY_EINVAL where the reference asserts: a format that is not a PRACH format or a PUSCH spacing above 120 kHz; a long format with
+ * nof_td_occasions != 1; zero occasions; occasions beyond MIPHY_PRACH_MAX_TD_OCCASIONS / MIPHY_PRACH_MAX_FD_OCCASIONS or the buffer's
+ * strides (fd occasions, symbols); a reserved (RA spacing, PUSCH spacing) pair; dft_size <= nof_prb_ul_grid K 12; k_start + L >= that
+ * grid size; a start, cyclic prefix or (short formats) window that is not a whole number of samples at the sampling rate; a sampling
+ * rate the RA spacing does not divide; a window shorter than what an occasion reads or (short formats) than the window duration.
+ * A stride above MIPHY_PRACH_MAX_STRIDE is MIPHY_EINVAL too (this interface's own bound; products of job fields are formed in 64 bits).
+ * MIPHY_EUNSUPP: everything above holds and the DFT size is not one the device transforms (e.g. format 0 at 122.88 MHz).
+ * Size of a call: any n. The task table (64 bytes per window, time-domain occasion and symbol) is staged in pieces of at most 1 MiB, one
+ * launch (pair) per piece, so it never outgrows the ring. Scratch: none up to 4096 points; above, dft_size * 8 bytes per symbol in
+ * flight from the context's general workspace, at most 64 MiB (a piece holds as many symbols as fit: 341 of 24576 points, 170 of 49152),
+ * which the context keeps until it is destroyed. */
+#define MIPHY_PRACH_MAX_TD_OCCASIONS 7
+#define MIPHY_PRACH_MAX_FD_OCCASIONS 8
+#define MIPHY_PRACH_MAX_STRIDE 65535u /* max_nof_fd_occasions, max_nof_symbols */
+typedef struct {
+  uint32_t format;               /* MIPHY_PRACH_FORMAT_* */
+  uint32_t pusch_scs;            /* 0..3 = 15..120 kHz, as srsran::subcarrier_spacing; short formats use it as RA spacing too */
+  uint32_t nof_td_occasions, nof_fd_occasions, start_symbol, rb_offset, nof_prb_ul_grid;
+  uint32_t nof_samples;          /* length of the window at samples_offset */
+  uint64_t samples_offset;       /* cf_t offset of the window (slot start) in `samples` */
+  uint64_t buffer_offset;        /* cf_t offset of get_symbol(port, 0, 0, 0) in `buffer` */
+  uint32_t max_nof_fd_occasions, max_nof_symbols; /* buffer strides: [td][fd][symbol][L], as prach_buffer_impl */
+} miphy_prach_demod_job;          /* one job = one window of one port */
+
+typedef struct {
+  uint32_t L;              /* 839 or 139 */
+  uint32_t ra_scs_hz;      /* 1250, 5000, 15000 << pusch_scs */
+  uint32_t dft_size;       /* sampling rate / ra_scs_hz */
+  uint32_t nof_symbols;    /* per occasion */
+  uint32_t K;              /* PUSCH spacing / RA spacing */
+  uint32_t k_bar, nof_rb_ra;
+  uint32_t window_samples; /* get_prach_window_duration in samples */
+  uint32_t td_sample_offset[MIPHY_PRACH_MAX_TD_OCCASIONS]; /* start of the occasion (its cyclic prefix) in the window */
+  uint32_t td_cp_samples[MIPHY_PRACH_MAX_TD_OCCASIONS];    /* cyclic prefix with the 16 kappa extensions */
+  uint32_t k_start[MIPHY_PRACH_MAX_FD_OCCASIONS];          /* first subcarrier of the occasion in the PRACH grid */
+} miphy_prach_demod_info_t;
+
+int miphy_prach_demod_info(uint32_t sampling_rate_hz, const miphy_prach_demod_job* job, miphy_prach_demod_info_t* out); /* host only */
+int miphy_prach_demodulate_batch(miphy_ctx* ctx, uint32_t sampling_rate_hz, const miphy_prach_demod_job* jobs /* host */, uint32_t n,
+                                 const float* samples /* device cf_t */, float* buffer /* device cf_t */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * PDSCH encoder (whole transport blocks)  --  replaces srsran::pdsch_encoder::encode
  *   include/srsran/phy/upper/channel_processors/pdsch_encoder.h, lib/phy/upper/channel_processors/pdsch_encoder_impl.cpp:28-65
  *   (segment_tx: TB CRC16/24A, CB CRC24B, zero padding, fillers -> LDPC encode -> rate match into the codeword),

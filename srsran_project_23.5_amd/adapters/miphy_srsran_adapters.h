@@ -1505,6 +1505,86 @@ inline std::shared_ptr<srsran::prach_generator_factory> create_prach_generator_f
   return std::make_shared<prach_generator_factory_hip>(std::move(c));
 }
 
+// ---------------------------------------------------------------------------------------------------------------- PRACH demodulator
+static_assert(static_cast<unsigned>(srsran::subcarrier_spacing::kHz15) == 0 && static_cast<unsigned>(srsran::subcarrier_spacing::kHz120) == 3,
+              "pusch_scs of miphy_prach_demod_job follows srsran::subcarrier_spacing");
+
+/// srsran::ofdm_prach_demodulator over miphy_prach_demodulate_batch (ofdm_prach_demodulator.h:36-79,
+/// ofdm_prach_demodulator_impl.cpp:31-199), a batch of one window: only the spans the transforms read (the symbols of every
+/// time-domain occasion, not their cyclic prefixes nor what lies between occasions) are uploaded, one call demodulates, and the rows
+/// come back into buffer.get_symbol(0, td, fd, symbol). What the reference asserts is fatal.
+class ofdm_prach_demodulator_hip : public srsran::ofdm_prach_demodulator
+{
+public:
+  ofdm_prach_demodulator_hip(std::shared_ptr<context> c, srsran::sampling_rate srate_) : c(std::move(c)), srate(srate_) {}
+
+  void demodulate(srsran::prach_buffer& buffer, srsran::span<const srsran::cf_t> input, const configuration& config) override
+  {
+    miphy_prach_demod_job j = {};
+    j.format = static_cast<uint32_t>(config.format), j.pusch_scs = static_cast<uint32_t>(config.pusch_scs);
+    j.nof_td_occasions = config.nof_td_occasions, j.nof_fd_occasions = config.nof_fd_occasions, j.start_symbol = config.start_symbol;
+    j.rb_offset = config.rb_offset, j.nof_prb_ul_grid = config.nof_prb_ul_grid, j.nof_samples = static_cast<uint32_t>(input.size());
+    require(config.nof_td_occasions <= buffer.get_max_nof_td_occasions() && config.nof_fd_occasions <= buffer.get_max_nof_fd_occasions(),
+            "The number of occasions ({} x {}) exceeds the buffer maximum ({} x {}).", config.nof_td_occasions, config.nof_fd_occasions,
+            buffer.get_max_nof_td_occasions(), buffer.get_max_nof_fd_occasions());
+    // The device copy is compact: [td][fd][symbol][L] with exactly the occasions and symbols of the configuration.
+    j.max_nof_fd_occasions = config.nof_fd_occasions, j.max_nof_symbols = buffer.get_max_nof_symbols();
+    miphy_prach_demod_info_t g;
+    context::check(miphy_prach_demod_info(srate.to_Hz(), &j, &g), "prach_demod_info");
+    require(buffer.get_sequence_length() == g.L, "The buffer sequence length {} is not the preamble's {}.", buffer.get_sequence_length(), g.L);
+    j.max_nof_symbols = g.nof_symbols;
+    const size_t read = static_cast<size_t>(g.nof_symbols) * g.dft_size; // samples an occasion's transforms read, behind its cyclic prefix
+    size_t       last = 0;
+    for (unsigned td = 0; td != config.nof_td_occasions; ++td) {
+      last = std::max(last, static_cast<size_t>(g.td_sample_offset[td]) + g.td_cp_samples[td] + read);
+    }
+    const size_t in_bytes = (last * sizeof(srsran::cf_t) + 15) & ~size_t(15);
+    const size_t rows     = static_cast<size_t>(config.nof_td_occasions) * config.nof_fd_occasions * g.nof_symbols;
+    auto*        d        = static_cast<uint8_t*>(c->buf(9, in_bytes + rows * g.L * sizeof(srsran::cf_t)));
+    for (unsigned td = 0; td != config.nof_td_occasions; ++td) {
+      const size_t first = static_cast<size_t>(g.td_sample_offset[td]) + g.td_cp_samples[td];
+      c->h2d(d + first * sizeof(srsran::cf_t), input.data() + first, read * sizeof(srsran::cf_t));
+    }
+    context::check(miphy_prach_demodulate_batch(c->ctx, srate.to_Hz(), &j, 1, reinterpret_cast<const float*>(d), reinterpret_cast<float*>(d + in_bytes),
+                                                c->stream),
+                   "prach_demodulate");
+    host_out.resize(rows * g.L);
+    c->d2h(host_out.data(), d + in_bytes, host_out.size() * sizeof(srsran::cf_t));
+    c->sync();
+    size_t row = 0;
+    for (unsigned td = 0; td != config.nof_td_occasions; ++td) {
+      for (unsigned fd = 0; fd != config.nof_fd_occasions; ++fd) {
+        for (unsigned symbol = 0; symbol != g.nof_symbols; ++symbol, ++row) {
+          srsran::span<srsran::cf_t> dst = buffer.get_symbol(0, td, fd, symbol);
+          std::copy_n(host_out.data() + row * g.L, g.L, dst.begin());
+        }
+      }
+    }
+  }
+
+private:
+  std::shared_ptr<context>  c;
+  srsran::sampling_rate     srate;
+  std::vector<srsran::cf_t> host_out;
+};
+
+class ofdm_prach_demodulator_factory_hip : public srsran::ofdm_prach_demodulator_factory
+{
+public:
+  ofdm_prach_demodulator_factory_hip(std::shared_ptr<context> c_, srsran::sampling_rate srate_) : c(std::move(c_)), srate(srate_) {}
+  std::unique_ptr<srsran::ofdm_prach_demodulator> create() override { return std::make_unique<ofdm_prach_demodulator_hip>(c, srate); }
+
+private:
+  std::shared_ptr<context> c;
+  srsran::sampling_rate    srate;
+};
+
+inline std::shared_ptr<srsran::ofdm_prach_demodulator_factory> create_ofdm_prach_demodulator_factory_hip(std::shared_ptr<context> c,
+                                                                                                        srsran::sampling_rate    srate)
+{
+  return std::make_shared<ofdm_prach_demodulator_factory_hip>(std::move(c), srate);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- PUSCH processor
 /// srsran::pusch_processor over miphy_pusch_process_batch (pusch_processor.h:158-162): estimation, demodulation and decoding in one
 /// device pass for PDUs that carry a codeword and no UCI; the resource grid goes to the device once, the transport block, the

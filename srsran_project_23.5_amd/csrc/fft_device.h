@@ -278,3 +278,46 @@ __device__ __forceinline__ void fft4096_regs(cplx* x, const cplx* __restrict__ t
   fft4096_pass<INV, 64, SKEW>(x, tw, t, a);
   fft4096_pass<INV, 512, SKEW, false, true>(x, tw, t, a);
 }
+
+// ---- sizes above 4096 (up to 49152 = 192 x 256): four-step FFT through HBM. N = N1 * N2, n = N2*n1 + n2, k = k1 + N1*k2:
+//   X[k1 + N1 k2] = sum_n2 W_N^(n2 k1) W_N2^(n2 k2) [ sum_n1 x[N2 n1 + n2] W_N1^(n1 k1) ]
+// Step 1: N1-point transforms down the columns (16 adjacent columns per workgroup so that every row segment is a 128-byte
+// access), times the twiddle W_N^(n2 k1), stored as A[k1][n2]. Step 2 (ofdm.hip: all of X; prach_demod.hip: the bins of the PRACH
+// occasions) works along the rows of A. The factors come from miphy_four_step_factors, the tables from miphy_get_twiddles.
+// Transform blockIdx.y reads N samples from `in + blockIdx.y * N`, or, with a table of offsets, from
+// `in + src_off[blockIdx.y * src_off_stride]` (float2 units; the PRACH demodulator's symbols lie wherever their windows put them).
+constexpr int FS_TILE = 16;
+
+template <bool INV>
+static __global__ void __launch_bounds__(256) dft_fs_step1_kernel(const float2* __restrict__ in,
+                                                                  float2* __restrict__ tmp,
+                                                                  const cplx* __restrict__ tw1,
+                                                                  const cplx* __restrict__ twN,
+                                                                  int N1,
+                                                                  int N2,
+                                                                  const uint64_t* __restrict__ src_off,
+                                                                  uint32_t src_off_stride)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  cplx*         x      = reinterpret_cast<cplx*>(smem);
+  const int     stride = (int)(fft_lds_bytes(N1) / 8);
+  const size_t  N      = (size_t)N1 * N2;
+  const float2* src    = in + (src_off ? (size_t)src_off[(size_t)blockIdx.y * src_off_stride] : (size_t)blockIdx.y * N);
+  float2*       dst    = tmp + (size_t)blockIdx.y * N;
+  const int     c0     = blockIdx.x * FS_TILE;
+  for (int i = threadIdx.x; i < FS_TILE * N1; i += blockDim.x) {
+    const int n1 = i / FS_TILE, c = i % FS_TILE;
+    const float2 v = src[(size_t)N2 * n1 + c0 + c];
+    x[c * stride + fpad(n1)] = {v.x, v.y};
+  }
+  __syncthreads();
+  for (int c = 0; c < FS_TILE; ++c)
+    fft_lds<INV>(x + c * stride, N1, tw1, threadIdx.x, blockDim.x);
+  for (int i = threadIdx.x; i < FS_TILE * N1; i += blockDim.x) {
+    const int k1 = i / FS_TILE, c = i % FS_TILE;
+    const int n2 = c0 + c;
+    const cplx w = cconj_if<INV>(twN[(size_t)n2 * k1 % N]);
+    const cplx v = cmul(x[c * stride + fpad(k1)], w);
+    dst[(size_t)k1 * N2 + n2] = make_float2(v.x, v.y);
+  }
+}

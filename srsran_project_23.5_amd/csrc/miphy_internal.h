@@ -225,6 +225,9 @@ int      miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const 
 // twice the size; the old one is kept until miphy_destroy (work enqueued or captured earlier may still use it), so nothing waits.
 int miphy_get_workspace(miphy_ctx* ctx, miphy_workspace slot, size_t bytes, void** out);
 
+// Factors of the four-step DFT sizes 4608 ... 49152 (ofdm.hip; both multiples of the 16-wide tile of fft_device.h's step 1); false for any other size.
+bool miphy_four_step_factors(uint32_t N, uint32_t& N1, uint32_t& N2);
+
 // The context's side streams and fork / join events, created on first use (before a run of a table that uses them).
 int miphy_side_streams(miphy_ctx* ctx);
 // The next work-queue counter of the context (zero: every launch leaves its counter cleared).

@@ -13,10 +13,11 @@
 //  - peak of |c|^2 as a (power, index) pair, the lowest index winning a tie; metric = peak / (rssi preamble_power L L) with the preamble
 //    power summed like the RSSI; threshold 0.07; delay sign and window. One lane writes the record.
 // What the detector derives before it looks at the signal (L, N_CS, cyclic prefix in samples, delay_n_maximum) is derived here from
-// TS 38.211 Tables 6.3.3.1-1, -2, -5, -6 and -7 by one function that the host uses to validate and the kernel to run, so that jobs may
-// live on the device. No per-call scratch; the launch only needs the twiddle tables the context keeps.
+// TS 38.211 Tables 6.3.3.1-1, -2, -5, -6 and -7 by one function (prach_info.h) that the host uses to validate and the kernel to run, so
+// that jobs may live on the device. No per-call scratch; the launch only needs the twiddle tables the context keeps.
 #include "fft_device.h"
 #include "miphy_ext.h"
+#include "prach_info.h"
 #define NR_PRACH_TABLE_ATTR __device__
 #include "tables/nr_prach_tables.h"
 #include <algorithm>
@@ -32,36 +33,6 @@ constexpr float    PRACH_PI        = 3.14159265358979323846f;
 struct prach_derived {
   uint32_t L, n_cs, delay_n_maximum, n_cs_limited;
 };
-
-// L, RA subcarrier spacing in Hz, N_CP in units of kappa and N_CS of a (format, ra_scs, zone, set); false where the reference asserts
-// (get_prach_preamble_short_info on a long RA spacing, "Unrestricted sets are not implemented", "Reserved cyclic shift").
-__host__ __device__ inline bool prach_preamble_info(uint32_t format, uint32_t ra_scs, uint32_t zone, uint32_t restricted_set, uint32_t& L,
-                                                    uint32_t& scs_hz, uint32_t& cp_kappa, uint32_t& n_cs)
-{
-  // TS 38.211 Tables 6.3.3.1-5, -6, -7 (unrestricted set) and 6.3.3.1-1, -2 (N_CP^RA / kappa; the A/B pairs take the A value, every
-  // occasion but the last one of a slot).
-  static constexpr uint16_t NCS_1_25[16]  = {0, 13, 15, 18, 22, 26, 32, 38, 46, 59, 76, 93, 119, 167, 279, 419};
-  static constexpr uint16_t NCS_5[16]     = {0, 13, 26, 33, 38, 41, 49, 55, 64, 76, 93, 119, 139, 209, 279, 419};
-  static constexpr uint16_t NCS_SHORT[16] = {0, 2, 4, 6, 8, 10, 12, 13, 15, 17, 19, 23, 27, 34, 46, 69};
-  static constexpr uint16_t CP_LONG[4]    = {3168, 21024, 4688, 3168};
-  static constexpr uint16_t CP_SHORT[10]  = {288, 576, 864, 216, 936, 1240, 2048, 288, 576, 864};
-  if (format >= MIPHY_PRACH_NOF_FORMATS || restricted_set != 0 || zone > 15)
-    return false;
-  if (format <= MIPHY_PRACH_FORMAT_3) {
-    L        = 839;
-    scs_hz   = (format == MIPHY_PRACH_FORMAT_3) ? 5000 : 1250;
-    cp_kappa = CP_LONG[format];
-    n_cs     = (format == MIPHY_PRACH_FORMAT_3) ? NCS_5[zone] : NCS_1_25[zone];
-    return true;
-  }
-  if (ra_scs > 3)
-    return false;
-  L        = 139;
-  scs_hz   = 15000u << ra_scs;
-  cp_kappa = (uint32_t)CP_SHORT[format - MIPHY_PRACH_FORMAT_A1] >> ra_scs;
-  n_cs     = NCS_SHORT[zone];
-  return true;
-}
 
 __host__ __device__ inline bool prach_job_derive(const miphy_prach_job& j, prach_derived& d)
 {

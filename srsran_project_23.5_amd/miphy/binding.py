@@ -121,6 +121,8 @@ def lib():
         l.miphy_pucch_process_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
         l.miphy_prach_detect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_prach_generate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 2
+        l.miphy_prach_demod_info.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
+        l.miphy_prach_demodulate_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
         _lib = l
     return _lib
 
@@ -299,6 +301,28 @@ assert PrachPreambleResult.itemsize == 20
 PrachGenJob = np.dtype([("format", np.uint32), ("root_sequence_index", np.uint32), ("zero_correlation_zone", np.uint32),
                         ("restricted_set", np.uint32), ("preamble_index", np.uint32), ("out_offset", np.uint32)], align=True)
 assert PrachGenJob.itemsize == 24
+# miphy_prach_demod_job / miphy_prach_demod_info_t (include/miphy.h)
+PRACH_MAX_TD_OCCASIONS, PRACH_MAX_FD_OCCASIONS = 7, 8
+PrachDemodJob = np.dtype([("format", np.uint32), ("pusch_scs", np.uint32), ("nof_td_occasions", np.uint32), ("nof_fd_occasions", np.uint32),
+                          ("start_symbol", np.uint32), ("rb_offset", np.uint32), ("nof_prb_ul_grid", np.uint32), ("nof_samples", np.uint32),
+                          ("samples_offset", np.uint64), ("buffer_offset", np.uint64), ("max_nof_fd_occasions", np.uint32),
+                          ("max_nof_symbols", np.uint32)], align=True)
+assert PrachDemodJob.itemsize == 56
+PrachDemodInfo = np.dtype([("L", np.uint32), ("ra_scs_hz", np.uint32), ("dft_size", np.uint32), ("nof_symbols", np.uint32), ("K", np.uint32),
+                           ("k_bar", np.uint32), ("nof_rb_ra", np.uint32), ("window_samples", np.uint32),
+                           ("td_sample_offset", np.uint32, PRACH_MAX_TD_OCCASIONS), ("td_cp_samples", np.uint32, PRACH_MAX_TD_OCCASIONS),
+                           ("k_start", np.uint32, PRACH_MAX_FD_OCCASIONS)], align=True)
+assert PrachDemodInfo.itemsize == 120
+
+
+def prach_demod_info(sampling_rate_hz, job):
+    """What the PRACH demodulator derives from one PrachDemodJob record at a sampling rate (host function, no device): a PrachDemodInfo
+    record. Raises with the library's error code (-1 = MIPHY_EINVAL where the reference asserts, -4 = MIPHY_EUNSUPP for a DFT size
+    the device does not transform) in the message."""
+    j = np.ascontiguousarray(np.asarray(job, PrachDemodJob).reshape(1))
+    out = np.zeros(1, PrachDemodInfo)
+    check(lib().miphy_prach_demod_info(int(sampling_rate_hz), C.c_void_p(j.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out[0]
 
 
 def pusch_uci_field_jobs(pdus, uci):
@@ -670,6 +694,23 @@ class Context:
         assert symbols.dtype == torch.complex64 and results.dtype == torch.uint8 and preambles.dtype == torch.uint8
         assert results.numel() >= n * PrachResult.itemsize
         check(lib().miphy_prach_detect_batch(self.h, ptr, on_dev, n, _dptr(symbols), _dptr(results), _dptr(preambles), _stream_ptr(stream)))
+
+    def prach_demodulate_batch(self, sampling_rate_hz, jobs, samples, buffer, stream=None):
+        """OFDM PRACH demodulator (jobs: numpy PrachDemodJob array, HOST memory only: one window of one port each): samples and buffer
+        complex64 device tensors; a job's rows of L bins go to buffer laid out [td][fd][symbol][L] from its buffer_offset with the
+        strides max_nof_fd_occasions and max_nof_symbols, where a PrachJob's symbol_offset can point. Only enqueues."""
+        import torch
+        assert isinstance(jobs, np.ndarray) and jobs.dtype == PrachDemodJob, "prach_demodulate_batch takes host jobs"
+        jobs = np.ascontiguousarray(jobs)
+        assert samples.dtype == torch.complex64 and buffer.dtype == torch.complex64
+        if jobs.size:  # the extents the kernels may touch lie inside the tensors (the library sees raw pointers)
+            i64 = {k: jobs[k].astype(np.int64) for k in ("samples_offset", "nof_samples", "buffer_offset", "nof_td_occasions",
+                                                         "max_nof_fd_occasions", "max_nof_symbols")}
+            assert (i64["samples_offset"] + i64["nof_samples"]).max() <= samples.numel(), "window outside `samples`"
+            rows = i64["nof_td_occasions"] * i64["max_nof_fd_occasions"] * i64["max_nof_symbols"]
+            assert (i64["buffer_offset"] + rows * np.where(jobs["format"] < 4, 839, 139)).max() <= buffer.numel(), "PRACH buffer outside `buffer`"
+        check(lib().miphy_prach_demodulate_batch(self.h, int(sampling_rate_hz), C.c_void_p(jobs.ctypes.data), jobs.size, _dptr(samples),
+                                                 _dptr(buffer), _stream_ptr(stream)))
 
     def prach_generate_batch(self, jobs, out, stream=None):
         """PRACH frequency-domain preambles y_u,v (jobs: numpy PrachGenJob array or a uint8 device tensor): out complex64 device tensor,
