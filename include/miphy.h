@@ -749,6 +749,56 @@ int miphy_pusch_uci_field_jobs(const miphy_pusch_pdu* pdus, const miphy_pusch_uc
                                uint32_t* nof_jobs);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * UCI decoder, polar-coded fields of 12 to 1706 bits  --  beyond the 23.5 reference, whose uci_decoder_impl.cpp:44 stops at 11 bits
+ * while lib/ran/pusch/ulsch_info.cpp:29-42 already sizes these fields. Framing of TS 38.212 6.3.1.2-6.3.1.5 / 6.3.2 (5.2.1, 5.3.1):
+ *   C = 2 if (A >= 360 and E >= 1088) or A >= 1013, else 1; L = 6 (CRC6) for A <= 19, else 11 (CRC11); A' = ceil(A / C) C; with
+ *   C = 2 and odd A one zero bit is prepended; segment r = a'[r A'/C, (r + 1) A'/C) followed by the L CRC bits of the segment alone;
+ *   K_r = A'/C + L, E_r = floor(E / C); segment r owns soft bits [r E_r, (r + 1) E_r) of the field (with C = 2 and odd E the last
+ *   soft bit is never read); polar code (K_r, E_r, nMax = 10, ibil = 1), nPC = 3 for K_r <= 25, CRC bits not interleaved.
+ * A field is accepted when K_r + nPC < E_r and E_r <= 8192. Each segment goes through the reference's rate dematcher, its
+ * list-size-1 SSC decoder and its deallocator (bit-exact with miphy_polar_decode_batch), then its CRC is checked. `payload` always
+ * receives the A decoded bits (one per byte, segments concatenated, pad bit dropped); `status[i]` is MIPHY_UCI_STATUS_VALID when the
+ * CRC of every segment matches, else MIPHY_UCI_STATUS_INVALID. DECISION: the decoded value of the pad bit is not checked.
+ * Jobs are HOST memory only (the polar codes of a call are constructed on the host); device-resident jobs and stream capture of this
+ * entry point are out of scope. The call only enqueues on `stream`. Every job is checked before anything is staged: a bad job gives
+ * MIPHY_EINVAL with the rule in miphy_last_error() and nothing is enqueued; so do null arguments and n > 2^24. n == 0 enqueues
+ * nothing. (A HIP or staging failure between two pieces of a large call, MIPHY_EHIP, leaves the earlier pieces enqueued.) The tables
+ * of a call travel with it through the context's staging ring in pieces of at most 1 MiB (tasks and code tables of the piece
+ * together; a piece is one or two launches); no device allocation is made for a code. */
+#define MIPHY_UCI_POLAR_MIN_BITS 12
+#define MIPHY_UCI_POLAR_MAX_BITS 1706
+typedef struct {
+  uint16_t nof_bits;       /* A: 12..1706 */
+  uint16_t reserved;
+  uint32_t nof_llr;        /* E */
+  uint64_t llr_offset;     /* int8 offset inside `llr`, any alignment */
+  uint64_t payload_offset; /* byte offset of the A payload bytes inside `payload` */
+} miphy_uci_polar_job;
+typedef struct {
+  uint32_t C;   /* segments: 1 or 2 */
+  uint32_t L;   /* CRC bits per segment: 6 or 11 */
+  uint32_t K_r; /* polar message length of a segment, CRC included */
+  uint32_t E_r; /* rate-matched length of a segment */
+  uint32_t n;   /* log2 of the mother code size */
+  uint32_t nPC; /* parity-check bits: 3 or 0 */
+} miphy_uci_polar_info_t;
+/* Host: the framing of a field of nof_bits bits received as nof_llr soft bits; 0, or MIPHY_EINVAL with the rule's message. */
+int miphy_uci_polar_info(uint32_t nof_bits, uint32_t nof_llr, miphy_uci_polar_info_t* out);
+int miphy_uci_polar_decode_batch(miphy_ctx* ctx, const miphy_uci_polar_job* jobs /* host */, uint32_t n, const int8_t* llr /* device */,
+                                 uint8_t* payload /* device */, uint8_t* status /* device, n */, void* stream);
+/* Host: like miphy_pusch_uci_field_jobs, but a PDU's fields of 1..11 bits go to `short_jobs` and those of 12..1706 bits to
+ * `polar_jobs` (up to 3 n entries each), payloads packed from byte 0 of ONE payload buffer in (PDU, field) order whichever list a
+ * field lands in; short_field / polar_field (NULL or as many entries) receive 3 * pdu + field per job as job_field does. With these
+ * jobs, _ex, miphy_uci_decode_batch and miphy_uci_polar_decode_batch go on one stream without a host synchronisation in between
+ * (each decoder with its own status array). */
+int miphy_pusch_uci_jobs(const miphy_pusch_pdu* pdus, const miphy_pusch_uci* uci, uint32_t n, miphy_uci_field_job* short_jobs, uint32_t* short_field,
+                         uint32_t* nof_short, miphy_uci_polar_job* polar_jobs, uint32_t* polar_field, uint32_t* nof_polar);
+/* Test hooks, process-wide: bytes a piece of miphy_uci_polar_decode_batch may take (0 = the default, 1 MiB; a piece always holds at
+ * least one field), and the number of pieces of the call that finished last, on whichever context. */
+void     miphy_debug_set_uci_polar_piece_bytes(size_t bytes);
+unsigned miphy_debug_uci_polar_pieces(void);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * PUCCH processor, formats 1 and 2  --  replaces srsran::pucch_processor::process(grid, format1_configuration / format2_configuration)
  *   lib/phy/upper/channel_processors/pucch_processor_impl.cpp:28-189 (estimate, detect or demodulate + decode, CSI),
  *   lib/phy/upper/signal_processors/pucch/dmrs_pucch_processor_format{1,2}_impl.cpp + port_channel_estimator_average_impl.cpp:97-347

@@ -991,20 +991,35 @@ private:
   std::shared_ptr<context> c;
 };
 
-/// srsran::uci_decoder on the device (uci_decoder_impl.cpp:41-50: every field the reference accepts, 1 to 11 bits, is a short block).
-/// pusch_processor_hip recognises it and decodes the UCI fields of a PDU where the demultiplexer left them, in the same submission.
+/// srsran::uci_decoder on the device: fields of 1 to 11 bits are short blocks (uci_decoder_impl.cpp:41-50, all the reference decodes),
+/// fields of 12 to 1706 bits are polar coded and go to miphy_uci_polar_decode_batch as one job per call (beyond the reference; the
+/// verdict is the CRC of every segment). pusch_processor_hip recognises it and decodes the UCI fields of a PDU where the demultiplexer
+/// left them, in the same submission.
 class uci_decoder_hip : public srsran::uci_decoder
 {
 public:
-  explicit uci_decoder_hip(std::shared_ptr<context> c) : detector(std::move(c)) {}
+  explicit uci_decoder_hip(std::shared_ptr<context> c_) : c(c_), detector(std::move(c_)) {}
   srsran::uci_status
   decode(srsran::span<uint8_t> message, srsran::span<const srsran::log_likelihood_ratio> llr, const configuration& config) override
   {
-    require(message.size() <= 11, "UCI message lengths above 11 bits are not currently supported.");
-    return detector.detect(message, llr, config.modulation) ? srsran::uci_status::valid : srsran::uci_status::invalid;
+    require(message.size() <= MIPHY_UCI_POLAR_MAX_BITS, "UCI message lengths above 1706 bits are not supported.");
+    if (message.size() <= 11) {
+      return detector.detect(message, llr, config.modulation) ? srsran::uci_status::valid : srsran::uci_status::invalid;
+    }
+    miphy_uci_polar_job j = {};
+    j.nof_bits = static_cast<uint16_t>(message.size()), j.nof_llr = static_cast<uint32_t>(llr.size()), j.llr_offset = 0, j.payload_offset = 0;
+    auto* d = static_cast<uint8_t*>(c->buf(5, 2048 + llr.size())); // [0,1706) payload, [1728] status, [2048,..) soft bits
+    c->h2d(d + 2048, llr.data(), llr.size());
+    context::check(miphy_uci_polar_decode_batch(c->ctx, &j, 1, reinterpret_cast<const int8_t*>(d + 2048), d, d + 1728, c->stream), "uci_polar_decode");
+    uint8_t status = MIPHY_UCI_STATUS_UNKNOWN;
+    c->d2h(message.data(), d, message.size());
+    c->d2h(&status, d + 1728, 1);
+    c->sync();
+    return status == MIPHY_UCI_STATUS_VALID ? srsran::uci_status::valid : srsran::uci_status::invalid;
   }
 
 private:
+  std::shared_ptr<context> c;
   short_block_detector_hip detector;
 };
 
@@ -1698,17 +1713,30 @@ public:
                    "pusch_process");
     // With the device UCI decoder the fields are decoded behind _ex on the same stream: only payload bits and verdicts come back.
     const bool           uci_on_device = has_uci && dynamic_cast<uci_decoder_hip*>(uci_dec.get()) != nullptr;
-    miphy_uci_field_job  uci_jobs[3];
-    uint32_t             uci_field[3] = {}, nof_uci_jobs = 0;
-    std::array<uint8_t, 3 * 16 + 3> uci_out = {}; // [16 f, 16 f + 11) payload of field f, [48 + j] status of job j
+    // Fields of 1 to 11 bits go to the short-block detector, longer ones to the polar decoder; both write one payload area.
+    miphy_uci_field_job  uci_short[3];
+    miphy_uci_polar_job  uci_polar[3];
+    uint32_t             short_field[3] = {}, polar_field[3] = {}, nof_short = 0, nof_polar = 0;
+    constexpr size_t     UCI_PAYLOAD = 8; // [0, 3) short-block verdicts, [3, 6) polar verdicts, [8, ..) the payloads packed in field order
+    size_t               nof_uci_out = 0;
     if (uci_on_device) {
-      context::check(miphy_pusch_uci_field_jobs(&p, &u, 1, uci_jobs, uci_field, &nof_uci_jobs), "pusch_uci_field_jobs");
-      for (uint32_t j = 0; j != nof_uci_jobs; ++j) {
-        uci_jobs[j].payload_offset = 16 * uci_field[j];
+      context::check(miphy_pusch_uci_jobs(&p, &u, 1, uci_short, short_field, &nof_short, uci_polar, polar_field, &nof_polar), "pusch_uci_jobs");
+      for (uint32_t j = 0; j != nof_short; ++j) {
+        uci_short[j].payload_offset += UCI_PAYLOAD;
       }
-      auto* d_uci_out = static_cast<uint8_t*>(c->buf(5, 64));
-      context::check(miphy_uci_decode_batch(c->ctx, uci_jobs, 0, nof_uci_jobs, d_uci, d_uci_out, d_uci_out + 48, c->stream), "uci_decode");
-      c->d2h(uci_out.data(), d_uci_out, uci_out.size());
+      for (uint32_t j = 0; j != nof_polar; ++j) {
+        uci_polar[j].payload_offset += UCI_PAYLOAD;
+      }
+      nof_uci_out = UCI_PAYLOAD + pdu.uci.nof_harq_ack + pdu.uci.nof_csi_part1 + pdu.uci.nof_csi_part2;
+      uci_out.resize(nof_uci_out);
+      auto* d_uci_out = static_cast<uint8_t*>(c->buf(5, nof_uci_out));
+      if (nof_short != 0) {
+        context::check(miphy_uci_decode_batch(c->ctx, uci_short, 0, nof_short, d_uci, d_uci_out, d_uci_out, c->stream), "uci_decode");
+      }
+      if (nof_polar != 0) {
+        context::check(miphy_uci_polar_decode_batch(c->ctx, uci_polar, nof_polar, d_uci, d_uci_out, d_uci_out + 3, c->stream), "uci_polar_decode");
+      }
+      c->d2h(uci_out.data(), d_uci_out, nof_uci_out); // (verdict slots without a job are not read)
     }
     miphy_pusch_result r;
     float              sc[20], evm = 0.F;
@@ -1769,9 +1797,12 @@ public:
         }
         f.payload.resize(nof_bits);
         if (uci_on_device) {
-          const uint32_t j = static_cast<uint32_t>(std::find(uci_field, uci_field + nof_uci_jobs, k) - uci_field);
-          std::copy(uci_out.begin() + 16 * k, uci_out.begin() + 16 * k + nof_bits, f.payload.begin());
-          f.status = uci_out[48 + j] == MIPHY_UCI_STATUS_VALID ? srsran::uci_status::valid : srsran::uci_status::invalid;
+          const uint32_t js = static_cast<uint32_t>(std::find(short_field, short_field + nof_short, k) - short_field);
+          const uint32_t jp = static_cast<uint32_t>(std::find(polar_field, polar_field + nof_polar, k) - polar_field);
+          const size_t   at = js != nof_short ? uci_short[js].payload_offset : uci_polar[jp].payload_offset;
+          const uint8_t  st = js != nof_short ? uci_out[js] : uci_out[3 + jp];
+          std::copy(uci_out.begin() + at, uci_out.begin() + at + nof_bits, f.payload.begin());
+          f.status = st == MIPHY_UCI_STATUS_VALID ? srsran::uci_status::valid : srsran::uci_status::invalid;
           return f;
         }
         f.status = uci_dec->decode(f.payload, srsran::span<const srsran::log_likelihood_ratio>(uci_llr.data() + off, G), ucfg);
@@ -1812,6 +1843,7 @@ private:
   bool                                      enable_evm;
   std::vector<srsran::cf_t>                 host;
   std::vector<srsran::log_likelihood_ratio> uci_llr;
+  std::vector<uint8_t>                      uci_out;
 };
 
 /// Replaces create_pusch_processor_factory_sw(config) (channel_processor_factories.h): only the decoder settings of the
@@ -3494,7 +3526,24 @@ public:
   pusch_pdu_validator_hip(std::unique_ptr<srsran::pusch_pdu_validator> ref, bool uci_supported) : ref(std::move(ref)), uci_supported(uci_supported) {}
   bool is_valid(const srsran::pusch_processor::pdu_t& pdu) const override
   {
-    if (!ref->is_valid(pdu)) {
+    // The reference's validator (pusch_processor_impl.cpp:54-58) refuses HARQ-ACK and CSI part 1 above 11 bits because its UCI decoder
+    // does. With the device UCI decoder behind the processor those fields may have up to 1706 bits (polar coded): the reference's
+    // remaining rules are applied to a copy of the PDU whose long fields are shortened to 11 bits, which none of them looks at
+    // otherwise. CSI part 2 stays refused, as the reference refuses it (:60-63). The rate bounds of miphy_uci_polar_info (K_r + nPC < E_r,
+    // E_r <= 8192) depend on the rate-matched lengths, which follow from the transport block size the validator is not given: the
+    // processor checks them (miphy_pusch_uci_jobs) when the PDU arrives.
+    const bool long_ack = pdu.uci.nof_harq_ack >= MIPHY_UCI_POLAR_MIN_BITS, long_csi1 = pdu.uci.nof_csi_part1 >= MIPHY_UCI_POLAR_MIN_BITS;
+    if (long_ack || long_csi1) {
+      if (!uci_supported || pdu.uci.nof_harq_ack > MIPHY_UCI_POLAR_MAX_BITS || pdu.uci.nof_csi_part1 > MIPHY_UCI_POLAR_MAX_BITS) {
+        return false;
+      }
+      srsran::pusch_processor::pdu_t shortened = pdu;
+      shortened.uci.nof_harq_ack               = long_ack ? 11 : pdu.uci.nof_harq_ack;
+      shortened.uci.nof_csi_part1              = long_csi1 ? 11 : pdu.uci.nof_csi_part1;
+      if (!ref->is_valid(shortened)) {
+        return false;
+      }
+    } else if (!ref->is_valid(pdu)) {
       return false;
     }
     const bool has_uci = pdu.uci.nof_harq_ack != 0 || pdu.uci.nof_csi_part1 != 0 || pdu.uci.nof_csi_part2 != 0;

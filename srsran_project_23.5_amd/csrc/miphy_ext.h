@@ -2,6 +2,7 @@
 #pragma once
 #include "miphy_internal.h"
 #include <map>
+#include <memory>
 #include <tuple>
 #include <vector>
 
@@ -27,7 +28,18 @@ struct polar_plan {
   uint32_t  sched_len;
 };
 
+// One constructed code of the polar-coded UCI decoder (uci_polar.hip) on the HOST: header and tables as one relocatable block that is
+// copied into every call that uses the code. A bounded cache, least recently used entry evicted; nothing of it lives on the device.
+struct uci_polar_host_code {
+  uint32_t                                     key  = 0; // K_r << 16 | E_r
+  uint64_t                                     used = 0;
+  std::shared_ptr<const std::vector<uint8_t>>  blob;
+};
+enum { UCI_POLAR_HOST_CACHE_ENTRIES = 128 };
+
 struct miphy_ctx_ext {
+  std::vector<uci_polar_host_code> uci_polar_codes;
+  uint64_t                         uci_polar_clock = 0;
   std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, polar_plan> polar_plans;
   std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, uint8_t*>   polar_kset; // per-position K-set flags (SCL)
   std::map<uint32_t, float*>                                    twiddles; // N -> device exp(-2 pi i j / N), j < N

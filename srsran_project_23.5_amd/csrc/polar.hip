@@ -11,117 +11,9 @@
 // host-composed index tables (sub-block interleaver o bit selection o channel interleaver).
 #include "crc_device.h"
 #include "miphy_ext.h"
-#include "tables/nr_polar_tables.h"
-#include <algorithm>
-#include <vector>
+#include "polar_device.h"
 
 namespace {
-
-enum { OP_F = 1, OP_G = 2, OP_R1 = 3, OP_COMB = 4 };
-
-struct host_code {
-  uint32_t              K, E, n, N, nPC, nWmPC;
-  std::vector<uint8_t>  k_set;
-  std::vector<uint16_t> pc_set;
-  std::vector<uint16_t> blk;
-};
-
-// polar_code_impl.cpp:325-490
-int build_code(const miphy_polar_code* c, host_code& h)
-{
-  const uint32_t K = c->K, E = c->E, nMax = c->nMax;
-  MIPHY_REQUIRE(E <= 8192, "polar: E = %u exceeds EMAX", E);
-  if (nMax == 9) {
-    MIPHY_REQUIRE(!(K < 36 || K > 164), "polar: codeblock length (K=%u) not supported for downlink transmission, choose 165 > K > 35", K);
-  } else if (nMax == 10) {
-    MIPHY_REQUIRE(!(K < 18 || (K > 25 && K < 31) || K > 1023), "polar: codeblock length (K=%u) not supported for uplink transmission", K);
-  } else {
-    MIPHY_REQUIRE(false, "polar: nMax not supported, choose 9 for downlink and 10 for uplink transmissions");
-  }
-  uint32_t nPC = 0, nWmPC = 0;
-  if (K <= 25) {
-    nPC = 3;
-    if (E > K + 189)
-      nWmPC = 1;
-  }
-  MIPHY_REQUIRE(K + nPC < E, "polar: rate-matched codeword length (E=%u) not supported, choose E > K + nPC", E);
-  uint32_t e = 1;
-  while (e <= 13 && (1u << e) < E)
-    ++e;
-  const uint32_t n1 = ((8 * E <= 9 * (1u << (e - 1))) && (16 * K < 9 * E)) ? e - 1 : e;
-  uint32_t       k  = 0;
-  while (k <= 10 && (1u << k) < K)
-    ++k;
-  uint32_t n = std::min(std::min(n1, k + 3), nMax);
-  n          = std::max(n, 5u);
-  const uint32_t N = 1u << n;
-  MIPHY_REQUIRE(K < N, "polar: codeblock length (K=%u) not supported, choose K < N", K);
-  h.K = K, h.E = E, h.n = n, h.N = N, h.nPC = nPC, h.nWmPC = nWmPC;
-  std::vector<uint16_t> mother;
-  for (uint32_t i = 0; i < 1024; ++i)
-    if (NR_POLAR_Q1024[i] < N)
-      mother.push_back(NR_POLAR_Q1024[i]);
-  h.blk.resize(N);
-  for (uint32_t j = 0; j < N; ++j)
-    h.blk[j] = (uint16_t)(NR_POLAR_SUBBLOCK_P[32 * j / N] * (N / 32) + j % (N / 32));
-  std::vector<uint16_t> cand(mother);
-  if (N > E) {
-    std::vector<uint8_t> drop(N, 0);
-    uint32_t             T = 0;
-    if (16 * K <= 7 * E) { // puncturing
-      const uint32_t N_th = 3 * N / 4;
-      T                   = (E >= N_th) ? N_th - (E >> 1) - 1 : 9 * N / 16 - (E >> 2);
-      for (uint32_t i = 0; i < N - E; ++i)
-        drop[h.blk[i]] = 1;
-    } else { // shortening
-      for (uint32_t i = E; i < N; ++i)
-        drop[h.blk[i]] = 1;
-    }
-    cand.clear();
-    for (uint16_t q : mother)
-      if (!(q <= T) && !drop[q]) // setdiff_stable: also drops every index <= T (T = 0 when shortening)
-        cand.push_back(q);
-  }
-  MIPHY_REQUIRE(cand.size() >= K + nPC, "polar: not enough reliable positions");
-  const uint16_t* Kset = cand.data() + (cand.size() - K - nPC);
-  h.pc_set.clear();
-  for (uint32_t i = 0; i < ((nPC > nWmPC) ? nPC - nWmPC : 0); ++i)
-    h.pc_set.push_back(Kset[i]);
-  if (nWmPC == 1)
-    h.pc_set.push_back((K <= 21) ? 252 : 248);
-  std::sort(h.pc_set.begin(), h.pc_set.end());
-  h.k_set.assign(N, 0);
-  for (uint32_t i = 0; i < K + nPC; ++i)
-    h.k_set[Kset[i]] = 1;
-  return MIPHY_OK;
-}
-
-void emit(std::vector<uint32_t>& s, uint32_t op, uint32_t stage, uint32_t pos)
-{
-  s.push_back(op | (stage << 4) | (pos << 8));
-}
-
-// Flattens polar_decoder_impl.cpp:209-333 (rate_0_node / rate_1_node / rate_r_node) into a list of vector operations.
-void build_schedule(const std::vector<uint8_t>& k_set, uint32_t s, uint32_t pos, std::vector<uint32_t>& out)
-{
-  const uint32_t size = 1u << s;
-  bool           any = false, all = true;
-  for (uint32_t i = 0; i < size; ++i) {
-    any |= k_set[pos + i] != 0;
-    all &= k_set[pos + i] != 0;
-  }
-  if (!any)
-    return;
-  if (all) {
-    emit(out, OP_R1, s, pos);
-    return;
-  }
-  emit(out, OP_F, s, pos);
-  build_schedule(k_set, s - 1, pos, out);
-  emit(out, OP_G, s, pos);
-  build_schedule(k_set, s - 1, pos + size / 2, out);
-  emit(out, OP_COMB, s, pos);
-}
 
 template <typename T>
 int upload(miphy_ctx* ctx, const std::vector<T>& v, T** d)
@@ -142,73 +34,18 @@ int get_plan(miphy_ctx* ctx, const miphy_polar_code* c, const polar_plan** out)
     *out = &it->second;
     return MIPHY_OK;
   }
-  host_code h;
-  int       rc = build_code(c, h);
+  polar_host_code h;
+  int       rc = polar_build_code(c, h);
   if (rc)
     return rc;
-  const uint32_t N = h.N, E = h.E, K = h.K;
-  polar_plan     p = {};
-  p.K = K, p.E = E, p.n = h.n, p.N = N, p.nPC = h.nPC;
-  std::vector<uint16_t> info_pos;
-  std::vector<uint8_t>  is_pc;
-  for (uint32_t q = 0; q < N; ++q)
-    if (h.k_set[q]) {
-      info_pos.push_back((uint16_t)q);
-      is_pc.push_back(std::find(h.pc_set.begin(), h.pc_set.end(), (uint16_t)q) != h.pc_set.end());
-    }
-  // Channel interleaver (polar_rate_matcher_impl.cpp:62-88): f[io] = e[ii].
-  std::vector<uint16_t> perm(E);
-  if (c->ibil) {
-    uint32_t S = 1, T = 1;
-    while (S < E) {
-      ++T;
-      S += T;
-    }
-    uint32_t io = 0;
-    for (uint32_t r = 0; r < T; ++r) {
-      uint32_t ii = r;
-      for (uint32_t cc = 0; cc < T - r; ++cc) {
-        if (ii < E) {
-          perm[io++] = (uint16_t)ii;
-          ii += T - cc;
-        } else
-          break;
-      }
-    }
-  } else {
-    for (uint32_t i = 0; i < E; ++i)
-      perm[i] = (uint16_t)i;
-  }
-  // Bit selection (polar_rate_matcher_impl.cpp:43-60): e[k] = y[sel(k)], y[j] = d[blk[j]].
-  const bool punct = (E < N) && (16 * K <= 7 * E);
-  auto       sel   = [&](uint32_t k) { return (E >= N) ? k % N : (punct ? k + (N - E) : k); };
-  std::vector<uint16_t> tx_src(E), rx_fidx(E);
-  for (uint32_t o = 0; o < E; ++o) {
-    tx_src[o]        = h.blk[sel(perm[o])];
-    rx_fidx[perm[o]] = (uint16_t)o;
-  }
-  // Inverse (polar_rate_dematcher_impl.cpp:43-68): for codeword position q = blk[j], y[j] comes from e[j'] (+ repetitions).
-  std::vector<int32_t> rx_first(N);
-  for (uint32_t j = 0; j < N; ++j) {
-    int32_t first;
-    if (E >= N)
-      first = (int32_t)j;
-    else if (punct)
-      first = (j < N - E) ? -1 : (int32_t)(j - (N - E));
-    else
-      first = (j < E) ? (int32_t)j : -2;
-    rx_first[h.blk[j]] = first;
-  }
-  std::vector<uint32_t> sched;
-  build_schedule(h.k_set, h.n, 0, sched);
-  std::vector<uint8_t> pi_il;
-  for (uint32_t m = 0; m < NR_POLAR_K_MAX_IL; ++m)
-    if (K <= NR_POLAR_K_MAX_IL && NR_POLAR_PI_IL_MAX[m] >= NR_POLAR_K_MAX_IL - K)
-      pi_il.push_back((uint8_t)(NR_POLAR_PI_IL_MAX[m] - (NR_POLAR_K_MAX_IL - K)));
-  p.sched_len = (uint32_t)sched.size();
-  if ((rc = upload(ctx, info_pos, &p.d_info_pos)) || (rc = upload(ctx, is_pc, &p.d_is_pc)) || (rc = upload(ctx, tx_src, &p.d_tx_src)) ||
-      (rc = upload(ctx, rx_first, &p.d_rx_first)) || (rc = upload(ctx, rx_fidx, &p.d_rx_fidx)) || (rc = upload(ctx, sched, &p.d_sched)) ||
-      (rc = upload(ctx, pi_il, &p.d_pi_il)))
+  polar_host_tables t;
+  polar_build_tables(h, c->ibil != 0, t);
+  polar_plan p = {};
+  p.K = h.K, p.E = h.E, p.n = h.n, p.N = h.N, p.nPC = h.nPC;
+  p.sched_len = (uint32_t)t.sched.size();
+  if ((rc = upload(ctx, t.info_pos, &p.d_info_pos)) || (rc = upload(ctx, t.is_pc, &p.d_is_pc)) || (rc = upload(ctx, t.tx_src, &p.d_tx_src)) ||
+      (rc = upload(ctx, t.rx_first, &p.d_rx_first)) || (rc = upload(ctx, t.rx_fidx, &p.d_rx_fidx)) || (rc = upload(ctx, t.sched, &p.d_sched)) ||
+      (rc = upload(ctx, t.pi_il, &p.d_pi_il)))
     return rc;
   auto ins = ctx->ext->polar_plans.emplace(key, p);
   *out     = &ins.first->second;
@@ -316,36 +153,9 @@ __global__ void __launch_bounds__(64) pdcch_encode_kernel(polar_plan p, uint32_t
   polar_tx_chain(p, u, cp, out + cw * p.E, nullptr, nullptr, lane);
 }
 
-// LLR algebra of log_likelihood_ratio.cpp:38-85 / .h:208-216.
 #ifndef POLAR_SSC_CW
 #define POLAR_SSC_CW 4
 #endif
-__device__ __forceinline__ int llr_add(int a, int b)
-{ // a + b (special cases inspect the right operand first, like `rhs += *this`)
-  if (b == -a)
-    return 0;
-  if (b > 120 || b < -120)
-    return b;
-  if (a > 120 || a < -120)
-    return a;
-  return min(max(a + b, -120), 120);
-}
-__device__ __forceinline__ int llr_promotion_sum(int a, int b)
-{
-  if (a == -b)
-    return 0;
-  if (a > 120 || a < -120)
-    return a;
-  if (b > 120 || b < -120)
-    return b;
-  const int t = a + b;
-  return (t > 120) ? 127 : ((t < -120) ? -127 : t);
-}
-__device__ __forceinline__ int llr_soft_xor(int x, int y)
-{
-  const int m = min(abs(x), abs(y));
-  return (x * y < 0) ? -m : m;
-}
 
 // C codewords per wavefront, W = 64 / C lanes each. Every codeword of a batch has the same code, hence the same pruned schedule: the codewords of a
 // wavefront run it in lockstep, each on its own LDS slice. One codeword per wavefront kept 23 % of the lanes busy (SQ_THREAD_CYCLES_VALU, profiles/r03):
@@ -369,17 +179,7 @@ __global__ void __launch_bounds__(64) polar_decode_kernel(polar_plan p, uint32_t
   const int8_t*      f = llr_in + (live ? cw : 0) * p.E;
   // Rate dematching (polar_rate_dematcher_impl.cpp:29-118) as a gather: repetitions are accumulated in order.
   for (int q = lane; q < N; q += W) {
-    const int first = p.d_rx_first[q];
-    int       v;
-    if (first == -1) {
-      v = 0;
-    } else if (first == -2) {
-      v = 127;
-    } else {
-      v = f[p.d_rx_fidx[first]];
-      for (int k = first + N; k < E; k += N)
-        v = llr_promotion_sum(v, f[p.d_rx_fidx[k]]);
-    }
+    const int v = polar_dematch_value(p.d_rx_first[q], N, E, f, p.d_rx_fidx);
     L[N + q] = (int8_t)v;
     est[q]   = 0;
     u[q]     = 0;
@@ -387,40 +187,7 @@ __global__ void __launch_bounds__(64) polar_decode_kernel(polar_plan p, uint32_t
       dem_tap[cw * N + q] = (int8_t)v;
   }
   __syncthreads();
-  for (uint32_t k = 0; k < p.sched_len; ++k) {
-    const uint32_t op    = p.d_sched[k];
-    const int      type  = op & 15, s = (op >> 4) & 15, pos = (int)(op >> 8);
-    const int      size  = 1 << s, half = size >> 1;
-    int8_t*        ls    = L + size;
-    int8_t*        lc    = L + half;
-    if (type == OP_F) {
-      for (int i = lane; i < half; i += W)
-        lc[i] = (int8_t)llr_soft_xor(ls[i], ls[i + half]);
-    } else if (type == OP_G) {
-      for (int i = lane; i < half; i += W) {
-        const int x = ls[i], y = ls[i + half];
-        lc[i]       = (int8_t)(est[pos + i] ? llr_add(y, -x) : llr_add(y, x));
-      }
-    } else if (type == OP_R1) {
-      for (int i = lane; i < size; i += W) {
-        const uint8_t b = ls[i] <= 0;
-        est[pos + i]    = b;
-        u[pos + i]      = b;
-      }
-      __syncthreads();
-      for (int h = 1; h < size; h <<= 1) { // re-encode the subtree (polar_decoder_impl.cpp:243-248)
-        for (int t = lane; t < half; t += W) {
-          const int b = ((t / h) * 2 * h) + (t % h);
-          u[pos + b] ^= u[pos + b + h];
-        }
-        __syncthreads();
-      }
-    } else { // OP_COMB
-      for (int i = lane; i < half; i += W)
-        est[pos + i] ^= est[pos + half + i];
-    }
-    __syncthreads();
-  }
+  polar_ssc_run<W>(L, est, u, p.d_sched, p.sched_len, lane);
   if (!live)
     return;
   if (u_tap)
@@ -503,17 +270,7 @@ __global__ void __launch_bounds__(64) polar_block_kernel(polar_plan p, int op, i
     case MIPHY_POLAR_OP_RATE_DEMATCH: { // polar_rate_dematcher_impl.cpp:29-118
       const int8_t* f = reinterpret_cast<const int8_t*>(in) + cw * E;
       for (int q = lane; q < N; q += 64) {
-        const int first = p.d_rx_first[q];
-        int       v;
-        if (first == -1) {
-          v = 0;
-        } else if (first == -2) {
-          v = 127;
-        } else {
-          v = f[p.d_rx_fidx[first]];
-          for (int k = first + N; k < E; k += N)
-            v = llr_promotion_sum(v, f[p.d_rx_fidx[k]]);
-        }
+        const int v = polar_dematch_value(p.d_rx_first[q], N, E, f, p.d_rx_fidx);
         reinterpret_cast<int8_t*>(out)[cw * N + q] = (int8_t)v;
       }
       break;
@@ -525,40 +282,7 @@ __global__ void __launch_bounds__(64) polar_block_kernel(polar_plan p, int op, i
         u[q]     = 0;
       }
       __syncthreads();
-      for (uint32_t k = 0; k < p.sched_len; ++k) {
-        const uint32_t op2  = p.d_sched[k];
-        const int      type = op2 & 15, s = (op2 >> 4) & 15, pos = (int)(op2 >> 8);
-        const int      size = 1 << s, half = size >> 1;
-        int8_t*        ls   = L + size;
-        int8_t*        lc   = L + half;
-        if (type == OP_F) {
-          for (int i = lane; i < half; i += 64)
-            lc[i] = (int8_t)llr_soft_xor(ls[i], ls[i + half]);
-        } else if (type == OP_G) {
-          for (int i = lane; i < half; i += 64) {
-            const int x = ls[i], y = ls[i + half];
-            lc[i]       = (int8_t)(est[pos + i] ? llr_add(y, -x) : llr_add(y, x));
-          }
-        } else if (type == OP_R1) {
-          for (int i = lane; i < size; i += 64) {
-            const uint8_t b = ls[i] <= 0;
-            est[pos + i]    = b;
-            u[pos + i]      = b;
-          }
-          __syncthreads();
-          for (int h = 1; h < size; h <<= 1) {
-            for (int t = lane; t < half; t += 64) {
-              const int b = ((t / h) * 2 * h) + (t % h);
-              u[pos + b] ^= u[pos + b + h];
-            }
-            __syncthreads();
-          }
-        } else {
-          for (int i = lane; i < half; i += 64)
-            est[pos + i] ^= est[pos + half + i];
-        }
-        __syncthreads();
-      }
+      polar_ssc_run<64>(L, est, u, p.d_sched, p.sched_len, lane);
       for (int i = lane; i < N; i += 64)
         out[cw * N + i] = u[i];
       break;
@@ -601,8 +325,8 @@ extern "C" int miphy_polar_code_info(const miphy_polar_code* code, uint32_t* n, 
     miphy_set_error("miphy_polar_code_info: null argument");
     return MIPHY_EINVAL;
   }
-  host_code h;
-  int       rc = build_code(code, h);
+  polar_host_code h;
+  int       rc = polar_build_code(code, h);
   if (rc)
     return rc;
   if (n)
@@ -744,17 +468,7 @@ __global__ void __launch_bounds__(64) polar_scl_kernel(polar_plan p, int L, int 
     kset[q] = k_set[q]; // [0, N): information-set flags, [N, 2N): rate-0 block exponents
   // Rate dematching (same gather as polar_decode_kernel).
   for (int q = lane; q < N; q += 64) {
-    const int first = p.d_rx_first[q];
-    int       v;
-    if (first == -1) {
-      v = 0;
-    } else if (first == -2) {
-      v = 127;
-    } else {
-      v = f_in[p.d_rx_fidx[first]];
-      for (int k = first + N; k < E; k += N)
-        v = llr_promotion_sum(v, f_in[p.d_rx_fidx[k]]);
-    }
+    const int v = polar_dematch_value(p.d_rx_first[q], N, E, f_in, p.d_rx_fidx);
     ch[q] = (int8_t)v;
   }
   if (lane < 8)
@@ -957,8 +671,8 @@ extern "C" int miphy_polar_decode_list_batch(miphy_ctx*              ctx,
   auto key = std::make_tuple(code->K, code->E, code->nMax, code->ibil ? 1u : 0u);
   auto it  = ctx->ext->polar_kset.find(key);
   if (it == ctx->ext->polar_kset.end()) {
-    host_code h;
-    if ((rc = build_code(code, h)))
+    polar_host_code h;
+    if ((rc = polar_build_code(code, h)))
       return rc;
     // followed by, per position, the exponent r of the largest aligned all-frozen block [i, i + 2^r) that starts there
     std::vector<uint8_t> tab(h.k_set.begin(), h.k_set.end());

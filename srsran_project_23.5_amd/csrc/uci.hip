@@ -16,6 +16,7 @@
 // metric is the one correctly rounded quotient of the reference; 0 / 0 (all-zero input) is NaN, which fails the strict > threshold
 // comparison, as in the reference.
 #include "uci_device.h"
+#include "uci_polar_info.h"
 
 namespace {
 
@@ -86,5 +87,49 @@ extern "C" int miphy_pusch_uci_field_jobs(const miphy_pusch_pdu* pdus, const mip
     }
   }
   *nof_jobs = cnt;
+  return MIPHY_OK;
+}
+
+// The field jobs of PUSCH PDUs whose fields may be polar coded: 1..11 bits as above, 12..1706 bits framed by uci_polar_info.h for
+// miphy_uci_polar_decode_batch (uci_polar.hip); one payload area in (PDU, field) order.
+extern "C" int miphy_pusch_uci_jobs(const miphy_pusch_pdu* pdus, const miphy_pusch_uci* uci, uint32_t n, miphy_uci_field_job* short_jobs, uint32_t* short_field,
+                                    uint32_t* nof_short, miphy_uci_polar_job* polar_jobs, uint32_t* polar_field, uint32_t* nof_polar)
+{
+  MIPHY_REQUIRE(pdus && uci && short_jobs && nof_short && polar_jobs && nof_polar, "miphy_pusch_uci_jobs: null argument");
+  uint32_t ns = 0, np = 0;
+  uint64_t pos = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const miphy_pusch_uci& u = uci[i];
+    const uint32_t         O[3] = {u.nof_harq_ack_bits, u.nof_csi_part1_bits, u.nof_csi_part2_bits};
+    const uint32_t         G[3] = {u.nof_enc_harq_ack_bits, u.nof_enc_csi_part1_bits, u.nof_enc_csi_part2_bits};
+    const uint64_t         off[3] = {u.harq_ack_offset, u.csi_part1_offset, u.csi_part2_offset};
+    for (uint32_t k = 0; k < 3; ++k) {
+      if (O[k] == 0)
+        continue;
+      if (O[k] <= 11) {
+        MIPHY_REQUIRE(miphy_uci_job_ok(O[k], pdus[i].mod, G[k]), "pusch_uci_jobs: PDU %u field %u: invalid field (%u bits, %u bits per symbol, %u soft bits)", i,
+                      k, O[k], pdus[i].mod, G[k]);
+        miphy_uci_field_job& j = short_jobs[ns];
+        j                      = {};
+        j.nof_bits = static_cast<uint8_t>(O[k]), j.mod = pdus[i].mod, j.nof_llr = G[k], j.llr_offset = off[k], j.payload_offset = pos;
+        if (short_field)
+          short_field[ns] = 3 * i + k;
+        ++ns;
+      } else {
+        uci_polar_framing f;
+        int               rc = uci_polar_frame_or_error("pusch_uci_jobs", 3 * i + k, O[k], G[k], f);
+        if (rc)
+          return rc;
+        miphy_uci_polar_job& j = polar_jobs[np];
+        j                      = {};
+        j.nof_bits = static_cast<uint16_t>(O[k]), j.nof_llr = G[k], j.llr_offset = off[k], j.payload_offset = pos;
+        if (polar_field)
+          polar_field[np] = 3 * i + k;
+        ++np;
+      }
+      pos += O[k];
+    }
+  }
+  *nof_short = ns, *nof_polar = np;
   return MIPHY_OK;
 }

@@ -118,6 +118,12 @@ def lib():
         l.miphy_ofdm_symbol_size.restype = C.c_uint32
         l.miphy_uci_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_pusch_uci_field_jobs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
+        l.miphy_uci_polar_info.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p]
+        l.miphy_uci_polar_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4
+        l.miphy_pusch_uci_jobs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
+        l.miphy_debug_set_uci_polar_piece_bytes.argtypes = [C.c_size_t]
+        l.miphy_debug_set_uci_polar_piece_bytes.restype = None
+        l.miphy_debug_uci_polar_pieces.restype = C.c_uint
         l.miphy_pucch_process_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
         l.miphy_prach_detect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_prach_generate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 2
@@ -273,6 +279,12 @@ UciFieldJob = np.dtype([("nof_bits", np.uint8), ("mod", np.uint8), ("reserved", 
                         ("payload_offset", np.uint64)], align=True)
 assert UciFieldJob.itemsize == 24
 UCI_STATUS_UNKNOWN, UCI_STATUS_VALID, UCI_STATUS_INVALID = 0, 1, 2
+# Mirrors miphy_uci_polar_job / miphy_uci_polar_info_t (polar-coded UCI fields of 12 to 1706 bits).
+UciPolarJob = np.dtype([("nof_bits", np.uint16), ("reserved", np.uint16), ("nof_llr", np.uint32), ("llr_offset", np.uint64),
+                        ("payload_offset", np.uint64)], align=True)
+assert UciPolarJob.itemsize == 24
+UciPolarInfo = np.dtype([("C", np.uint32), ("L", np.uint32), ("K_r", np.uint32), ("E_r", np.uint32), ("n", np.uint32), ("nPC", np.uint32)], align=True)
+assert UciPolarInfo.itemsize == 24
 
 # miphy_pucch_job / miphy_pucch_result (include/miphy.h)
 PucchJob = np.dtype([("format", np.uint8), ("numerology", np.uint8), ("slot", np.uint16), ("nof_ports", np.uint8), ("start_symbol", np.uint8),
@@ -337,6 +349,29 @@ def pusch_uci_field_jobs(pdus, uci):
     check(lib().miphy_pusch_uci_field_jobs(C.c_void_p(pdus.ctypes.data), C.c_void_p(uci.ctypes.data), pdus.size, C.c_void_p(jobs.ctypes.data),
                                            C.c_void_p(field.ctypes.data), C.byref(cnt)))
     return jobs[:cnt.value].copy(), field[:cnt.value].copy()
+
+
+def uci_polar_info(nof_bits, nof_llr):
+    """The framing of a polar-coded UCI field of nof_bits bits received as nof_llr soft bits (host function, no device): a UciPolarInfo
+    record. Raises with the library's error code (-1 = MIPHY_EINVAL) and the rule that refuses the field in the message."""
+    out = np.zeros(1, UciPolarInfo)
+    check(lib().miphy_uci_polar_info(int(nof_bits), int(nof_llr), C.c_void_p(out.ctypes.data)))
+    return out[0]
+
+
+def pusch_uci_jobs(pdus, uci):
+    """pusch_uci_field_jobs for PDUs whose fields may be longer than 11 bits (host function): fields of 1..11 bits become UciFieldJob
+    records, those of 12..1706 bits UciPolarJob records, all payloads packed into one buffer in (PDU, field) order. Returns
+    (short_jobs, short_field, polar_jobs, polar_field) with *_field = 3 * pdu + field."""
+    assert isinstance(pdus, np.ndarray) and pdus.dtype == PuschPdu and isinstance(uci, np.ndarray) and uci.dtype == PuschUci
+    assert pdus.size == uci.size
+    pdus, uci = np.ascontiguousarray(pdus), np.ascontiguousarray(uci)
+    sj, pj = np.zeros(max(1, 3 * pdus.size), UciFieldJob), np.zeros(max(1, 3 * pdus.size), UciPolarJob)
+    sf, pf = np.zeros(sj.size, np.uint32), np.zeros(pj.size, np.uint32)
+    ns, npol = C.c_uint32(), C.c_uint32()
+    check(lib().miphy_pusch_uci_jobs(C.c_void_p(pdus.ctypes.data), C.c_void_p(uci.ctypes.data), pdus.size, C.c_void_p(sj.ctypes.data),
+                                     C.c_void_p(sf.ctypes.data), C.byref(ns), C.c_void_p(pj.ctypes.data), C.c_void_p(pf.ctypes.data), C.byref(npol)))
+    return sj[:ns.value].copy(), sf[:ns.value].copy(), pj[:npol.value].copy(), pf[:npol.value].copy()
 
 
 class PolarCode(C.Structure):
@@ -671,6 +706,20 @@ class Context:
         jobs, n, ptr, on_dev = self._descs(jobs, UciFieldJob)
         assert llr.dtype == torch.int8 and payload.dtype == torch.uint8 and status.dtype == torch.uint8
         check(lib().miphy_uci_decode_batch(self.h, ptr, on_dev, n, _dptr(llr), _dptr(payload), _dptr(status), _stream_ptr(stream)))
+
+    def uci_polar_decode_batch(self, jobs, llr, payload, status, stream=None):
+        """Polar-coded UCI fields of 12 to 1706 bits (jobs: numpy UciPolarJob array, HOST memory only): llr int8, payload uint8 (one bit
+        per byte, nof_bits bytes per job) and status uint8 (one per job) device tensors. Only enqueues."""
+        import torch
+        assert isinstance(jobs, np.ndarray) and jobs.dtype == UciPolarJob, "uci_polar_decode_batch takes host jobs"
+        jobs = np.ascontiguousarray(jobs)
+        assert llr.dtype == torch.int8 and payload.dtype == torch.uint8 and status.dtype == torch.uint8
+        if jobs.size:  # the extents the kernel may touch lie inside the tensors (the library sees raw pointers)
+            assert (jobs["llr_offset"].astype(np.int64) + jobs["nof_llr"].astype(np.int64)).max() <= llr.numel(), "soft bits outside `llr`"
+            assert (jobs["payload_offset"].astype(np.int64) + jobs["nof_bits"].astype(np.int64)).max() <= payload.numel(), "payload outside `payload`"
+            assert status.numel() >= jobs.size
+        check(lib().miphy_uci_polar_decode_batch(self.h, C.c_void_p(jobs.ctypes.data), jobs.size, _dptr(llr), _dptr(payload), _dptr(status),
+                                                 _stream_ptr(stream)))
 
     def pucch_process_batch(self, jobs, grid, payload, results, llr=None, stream=None):
         """PUCCH formats 1 and 2 (jobs: numpy PucchJob array, or a uint8 device tensor holding the same bytes): grid complex64 device
