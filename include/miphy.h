@@ -797,6 +797,25 @@ int miphy_pusch_uci_jobs(const miphy_pusch_pdu* pdus, const miphy_pusch_uci* uci
  * least one field), and the number of pieces of the call that finished last, on whichever context. */
 void     miphy_debug_set_uci_polar_piece_bytes(size_t bytes);
 unsigned miphy_debug_uci_polar_pieces(void);
+/* CRC-aided list decoding of the same fields: jobs, framing, checks, staging in pieces, outputs and error behaviour are those of
+ * miphy_uci_polar_decode_batch. list_size must be 1, 2, 4 or 8; anything else is MIPHY_EINVAL with nothing enqueued. DECISIONS:
+ *   - list_size == 1 is miphy_uci_polar_decode_batch byte for byte, that is the SSC kernel, not the list recursion at L = 1, which
+ *     breaks the tie of a zero LLR at an information bit differently.
+ *   - Fields of 12..19 bits (CRC6, three parity-check bits) go through the SSC kernel at every list size: a list that forks on
+ *     parity-check positions without enforcing them is not what TS 38.212 intends, and six CRC bits leave no margin for eight
+ *     candidates. One call still takes every field.
+ *   - Fields of 20..1706 bits (CRC11, nPC = 0) at list sizes 2 / 4 / 8, per segment: rate dematching as above, then the list recursion
+ *     of the oracle's orc_polar_scl_decode (LLR path metric, ties to the lower candidate index); the K_r bits of every survivor are
+ *     taken in K-set order (no interleaver, no leading ones, no mask) and CRC11 of the first K_r - 11 is tested against the last 11.
+ *     The segment's result is the survivor with the smallest (metric, slot) among those that pass, or the smallest (metric, slot)
+ *     overall where none passes. The field is VALID when every segment has a passing survivor; `payload` always receives the chosen
+ *     survivors' bits. The call sets the status bytes of these fields on `stream` before the segments, decoded independently of one
+ *     another, overwrite them.
+ * Beyond the 23.5 reference, which has no list decoder; pinned to the oracle through tests/polar_scl_ref.py. */
+int miphy_uci_polar_decode_list_batch(miphy_ctx* ctx, const miphy_uci_polar_job* jobs /* host */, uint32_t n, uint32_t list_size,
+                                      const int8_t* llr /* device */, uint8_t* payload /* device */, uint8_t* status /* device, n */, void* stream);
+/* Test hook, process-wide: the segments the call that finished last sent to the SSC kernel and to the list kernel. */
+void miphy_debug_uci_polar_list_segments(unsigned* ssc, unsigned* list);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * PUCCH processor, formats 1 and 2  --  replaces srsran::pucch_processor::process(grid, format1_configuration / format2_configuration)

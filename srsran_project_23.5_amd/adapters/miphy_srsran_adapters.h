@@ -992,13 +992,18 @@ private:
 };
 
 /// srsran::uci_decoder on the device: fields of 1 to 11 bits are short blocks (uci_decoder_impl.cpp:41-50, all the reference decodes),
-/// fields of 12 to 1706 bits are polar coded and go to miphy_uci_polar_decode_batch as one job per call (beyond the reference; the
-/// verdict is the CRC of every segment). pusch_processor_hip recognises it and decodes the UCI fields of a PDU where the demultiplexer
-/// left them, in the same submission.
+/// fields of 12 to 1706 bits are polar coded and go to miphy_uci_polar_decode_list_batch as one job per call (beyond the reference;
+/// the verdict is the CRC of every segment). \c list_size 1 (the default) is the reference's SSC decoder, 2 / 4 / 8 decode the fields
+/// of 20 bits and more with a CRC-aided list of that size. pusch_processor_hip recognises the decoder and decodes the UCI fields of a
+/// PDU where the demultiplexer left them, in the same submission and at the decoder's list size.
 class uci_decoder_hip : public srsran::uci_decoder
 {
 public:
-  explicit uci_decoder_hip(std::shared_ptr<context> c_) : c(c_), detector(std::move(c_)) {}
+  explicit uci_decoder_hip(std::shared_ptr<context> c_, unsigned list_size_ = 1) : c(c_), detector(std::move(c_)), list_size(list_size_)
+  {
+    require(list_size == 1 || list_size == 2 || list_size == 4 || list_size == 8, "The UCI list size must be 1, 2, 4 or 8.");
+  }
+  unsigned get_list_size() const { return list_size; }
   srsran::uci_status
   decode(srsran::span<uint8_t> message, srsran::span<const srsran::log_likelihood_ratio> llr, const configuration& config) override
   {
@@ -1010,7 +1015,8 @@ public:
     j.nof_bits = static_cast<uint16_t>(message.size()), j.nof_llr = static_cast<uint32_t>(llr.size()), j.llr_offset = 0, j.payload_offset = 0;
     auto* d = static_cast<uint8_t*>(c->buf(5, 2048 + llr.size())); // [0,1706) payload, [1728] status, [2048,..) soft bits
     c->h2d(d + 2048, llr.data(), llr.size());
-    context::check(miphy_uci_polar_decode_batch(c->ctx, &j, 1, reinterpret_cast<const int8_t*>(d + 2048), d, d + 1728, c->stream), "uci_polar_decode");
+    context::check(miphy_uci_polar_decode_list_batch(c->ctx, &j, 1, list_size, reinterpret_cast<const int8_t*>(d + 2048), d, d + 1728, c->stream),
+                   "uci_polar_decode");
     uint8_t status = MIPHY_UCI_STATUS_UNKNOWN;
     c->d2h(message.data(), d, message.size());
     c->d2h(&status, d + 1728, 1);
@@ -1021,6 +1027,7 @@ public:
 private:
   std::shared_ptr<context> c;
   short_block_detector_hip detector;
+  unsigned                 list_size;
 };
 
 // ---------------------------------------------------------------------------------------------------------------- PUCCH processor
@@ -1712,7 +1719,8 @@ public:
     context::check(miphy_pusch_process_batch_ex(c->ctx, &p, &u, 1, d_g, d_soft, d_msg, d_crc, d_tb, d_res, d_sc, d_uci, enable_evm ? d_evm : nullptr, c->stream),
                    "pusch_process");
     // With the device UCI decoder the fields are decoded behind _ex on the same stream: only payload bits and verdicts come back.
-    const bool           uci_on_device = has_uci && dynamic_cast<uci_decoder_hip*>(uci_dec.get()) != nullptr;
+    const auto*          uci_dec_hip   = dynamic_cast<const uci_decoder_hip*>(uci_dec.get());
+    const bool           uci_on_device = has_uci && uci_dec_hip != nullptr;
     // Fields of 1 to 11 bits go to the short-block detector, longer ones to the polar decoder; both write one payload area.
     miphy_uci_field_job  uci_short[3];
     miphy_uci_polar_job  uci_polar[3];
@@ -1734,7 +1742,9 @@ public:
         context::check(miphy_uci_decode_batch(c->ctx, uci_short, 0, nof_short, d_uci, d_uci_out, d_uci_out, c->stream), "uci_decode");
       }
       if (nof_polar != 0) {
-        context::check(miphy_uci_polar_decode_batch(c->ctx, uci_polar, nof_polar, d_uci, d_uci_out, d_uci_out + 3, c->stream), "uci_polar_decode");
+        context::check(miphy_uci_polar_decode_list_batch(
+                           c->ctx, uci_polar, nof_polar, uci_dec_hip->get_list_size(), d_uci, d_uci_out, d_uci_out + 3, c->stream),
+                       "uci_polar_decode");
       }
       c->d2h(uci_out.data(), d_uci_out, nof_uci_out); // (verdict slots without a job are not read)
     }
@@ -3028,8 +3038,19 @@ MIPHY_SIMPLE_FACTORY(pusch_demodulator_factory_hip, pusch_demodulator_factory, p
 MIPHY_SIMPLE_FACTORY(pdsch_modulator_factory_hip, pdsch_modulator_factory, pdsch_modulator, pdsch_modulator_hip)
 MIPHY_SIMPLE_FACTORY(dmrs_pdsch_processor_factory_hip, dmrs_pdsch_processor_factory, dmrs_pdsch_processor, dmrs_pdsch_processor_hip)
 MIPHY_SIMPLE_FACTORY(short_block_detector_factory_hip, short_block_detector_factory, short_block_detector, short_block_detector_hip)
-MIPHY_SIMPLE_FACTORY(uci_decoder_factory_hip, uci_decoder_factory, uci_decoder, uci_decoder_hip)
 #undef MIPHY_SIMPLE_FACTORY
+
+/// The UCI decoders of one factory share the list size of their polar decoder (see uci_decoder_hip).
+class uci_decoder_factory_hip : public srsran::uci_decoder_factory
+{
+public:
+  explicit uci_decoder_factory_hip(std::shared_ptr<context> c, unsigned list_size = 1) : c(std::move(c)), list_size(list_size) {}
+  std::unique_ptr<srsran::uci_decoder> create() override { return std::make_unique<uci_decoder_hip>(c, list_size); }
+
+private:
+  std::shared_ptr<context> c;
+  unsigned                 list_size;
+};
 
 /// The string-selected factory functions of the reference (channel_coding_factories.cpp:86-180) gain a "hip" case that
 /// returns these.
@@ -3086,9 +3107,9 @@ inline std::shared_ptr<srsran::short_block_detector_factory> create_short_block_
 {
   return std::make_shared<short_block_detector_factory_hip>(std::move(c));
 }
-inline std::shared_ptr<srsran::uci_decoder_factory> create_uci_decoder_factory_hip(std::shared_ptr<context> c)
+inline std::shared_ptr<srsran::uci_decoder_factory> create_uci_decoder_factory_hip(std::shared_ptr<context> c, unsigned list_size = 1)
 {
-  return std::make_shared<uci_decoder_factory_hip>(std::move(c));
+  return std::make_shared<uci_decoder_factory_hip>(std::move(c), list_size);
 }
 
 /// OFDM factories take a configuration per product (modulation_factories.h:34-76).

@@ -442,10 +442,8 @@ extern "C" int miphy_pdcch_encode_batch(miphy_ctx*      ctx,
 // ---------------------------------------------------------------------------------------------------- SCL list decoder
 namespace {
 
-// One wavefront per codeword. LDS: channel LLRs [N] + two banks (current / scratch) of L paths x {llr[N], bl[N], u[N]}.
-//   llr: stage s node LLRs at offset 2^s (s < n), bl: left-child partial sums of stage s at offset 2^s, u: decisions.
-// All L paths advance together: a stage of size 2^s over `active` paths is one flat loop over active * 2^s lanes' worth of
-// elements; forking ranks the 2 * active candidates with wavefront shuffles and copies the survivors bank to bank.
+// One wavefront per codeword: rate dematching, the list recursion of polar_device.h (polar_scl_run, shared with uci_polar.hip; the LDS
+// layout is stated there) and the selection among the survivors.
 __global__ void __launch_bounds__(64) polar_scl_kernel(polar_plan p, int L, int crc_mode, const int8_t* __restrict__ llr_in,
                                                        const uint16_t* __restrict__ rnti, const uint8_t* __restrict__ k_set,
                                                        uint8_t* __restrict__ msg_out, uint8_t* __restrict__ crc_ok_out,
@@ -476,116 +474,7 @@ __global__ void __launch_bounds__(64) polar_scl_kernel(polar_plan p, int L, int 
   __syncthreads();
   uint8_t* P = bankA;
   uint8_t* Q = bankB;
-  int      active = 1;
-  for (int i = 0; i < N;) {
-    // An aligned all-frozen block [i, i + 2^r) (rate-0 node) is processed at stage r in one step: its penalty is the sum of the
-    // negative stage-r LLRs, its bits and partial sums are zero.
-    const int r = kset[N + i], B = 1 << r;
-    // ---- stage-r LLRs
-    int t = n;
-    if (i != 0) {
-      t = __ffs(i) - 1;
-      const int sz = 1 << t;
-      for (int idx = lane; idx < active * sz; idx += 64) {
-        const int     q = idx >> t, j = idx & (sz - 1);
-        uint8_t*      a  = P + q * PSZ;
-        const int8_t* up = (t + 1 == n) ? ch : reinterpret_cast<int8_t*>(a) + 2 * sz;
-        const int     x = up[j], y = up[j + sz];
-        reinterpret_cast<int8_t*>(a)[sz + j] = (int8_t)(a[N + sz + j] ? llr_add(y, -x) : llr_add(y, x));
-      }
-      __syncthreads();
-    }
-    for (int s = t - 1; s >= r; --s) {
-      const int sz = 1 << s;
-      for (int idx = lane; idx < active * sz; idx += 64) {
-        const int     q = idx >> s, j = idx & (sz - 1);
-        int8_t*       a  = reinterpret_cast<int8_t*>(P + q * PSZ);
-        const int8_t* up = (s + 1 == n) ? ch : a + 2 * sz;
-        a[sz + j]        = (int8_t)llr_soft_xor(up[j], up[j + sz]);
-      }
-      __syncthreads();
-    }
-    // ---- decision
-    if (!kset[i]) {
-      for (int idx = lane; idx < active * B; idx += 64) {
-        const int q = idx >> r, j = idx & (B - 1);
-        const int v = (r == n) ? ch[j] : reinterpret_cast<int8_t*>(P + q * PSZ)[B + j];
-        P[q * PSZ + 2 * N + i + j] = 0;
-        if (v < 0)
-          atomicAdd(&pm[q], -v);
-      }
-      __syncthreads();
-    } else {
-      const int nc = 2 * active, keep = min(nc, L);
-      int       met = 0x7fffffff, bit = 0;
-      if (lane < nc) {
-        const int q = lane >> 1, l0 = reinterpret_cast<int8_t*>(P + q * PSZ)[1];
-        const int hard = l0 <= 0, al = abs(l0);
-        met = pm[q] + ((lane & 1) ? al : 0);
-        bit = (lane & 1) ? !hard : hard;
-      }
-      int rank = 0;
-      for (int o = 0; o < nc; ++o) {
-        const int mo = __shfl(met, o);
-        rank += (mo < met) || (mo == met && o < lane);
-      }
-      __syncthreads(); // pm[] has been read by everyone
-      if (lane < nc && rank < keep) {
-        sel[rank]      = lane >> 1;
-        sel[8 + rank]  = bit;
-        pm[rank]       = met;
-      }
-      __syncthreads();
-      // survivors: bank P (parent) -> bank Q (slot), 16 bytes per lane per step
-      const int vec_per_path = PSZ >> 4;
-      for (int idx = lane; idx < keep * vec_per_path; idx += 64) {
-        const int r = idx / vec_per_path, v = idx - r * vec_per_path;
-        reinterpret_cast<uint4*>(Q + r * PSZ)[v] = reinterpret_cast<const uint4*>(P + sel[r] * PSZ)[v];
-      }
-      __syncthreads();
-      if (lane < keep)
-        Q[lane * PSZ + 2 * N + i] = (uint8_t)sel[8 + lane];
-      uint8_t* tmp = P;
-      P            = Q;
-      Q            = tmp;
-      active       = keep;
-      __syncthreads();
-    }
-    // ---- partial sums of the finished block at stage r (bank Q's u area serves as the per-path working vector)
-    if (!((i >> r) & 1)) {
-      for (int idx = lane; idx < active * B; idx += 64) {
-        const int q = idx >> r, j = idx & (B - 1);
-        P[q * PSZ + N + B + j] = P[q * PSZ + 2 * N + i + j];
-      }
-    } else {
-      for (int idx = lane; idx < active * B; idx += 64) {
-        const int q = idx >> r, j = idx & (B - 1);
-        Q[q * PSZ + 2 * N + j] = P[q * PSZ + 2 * N + i + j];
-      }
-      __syncthreads();
-      int sz = B, s = r;
-      while (s < n && ((i >> s) & 1)) {
-        for (int idx = lane; idx < active * sz; idx += 64) {
-          const int q = idx >> s, j = idx & (sz - 1);
-          uint8_t*  cur = Q + q * PSZ + 2 * N;
-          const uint8_t c0 = cur[j];
-          cur[sz + j]      = c0;
-          cur[j]           = c0 ^ P[q * PSZ + N + sz + j];
-        }
-        __syncthreads();
-        sz <<= 1;
-        ++s;
-      }
-      if (s < n) {
-        for (int idx = lane; idx < active * sz; idx += 64) {
-          const int q = idx >> s, j = idx & (sz - 1);
-          P[q * PSZ + N + sz + j] = Q[q * PSZ + 2 * N + j];
-        }
-      }
-    }
-    __syncthreads();
-    i += B;
-  }
+  const int active = polar_scl_run(ch, P, Q, pm, sel, kset, N, n, L, lane);
   // ---- selection: extract the K bits of every path (into bank Q), optional de-interleave + CRC, best metric wins
   int      my_pm = 0x7fffffff, my_ok = 0;
   uint8_t* cand  = Q + (lane < 8 ? lane : 0) * PSZ;     // K bits at cand[0..K), K-set order at cand[N..N+K)
@@ -674,33 +563,14 @@ extern "C" int miphy_polar_decode_list_batch(miphy_ctx*              ctx,
     polar_host_code h;
     if ((rc = polar_build_code(code, h)))
       return rc;
-    // followed by, per position, the exponent r of the largest aligned all-frozen block [i, i + 2^r) that starts there
-    std::vector<uint8_t> tab(h.k_set.begin(), h.k_set.end());
-    const uint32_t       Np = (uint32_t)h.k_set.size();
-    uint32_t             np = 0;
-    while ((1u << np) < Np)
-      ++np;
-    tab.resize(2 * Np, 0);
-    for (uint32_t i = 0; i < Np; ++i) {
-      uint32_t r = 0;
-      if (!h.k_set[i]) {
-        while (r < np && (i & ((2u << r) - 1u)) == 0) {
-          bool frozen = true;
-          for (uint32_t j = 0; j < (2u << r) && frozen; ++j)
-            frozen = !h.k_set[i + j];
-          if (!frozen)
-            break;
-          ++r;
-        }
-      }
-      tab[Np + i] = (uint8_t)r;
-    }
+    std::vector<uint8_t> tab;
+    polar_build_list_flags(h, tab);
     uint8_t* d = nullptr;
     if ((rc = upload(ctx, tab, &d)))
       return rc;
     it = ctx->ext->polar_kset.emplace(key, d).first;
   }
-  const size_t lds = (size_t)p->N + 2 * (size_t)list_size * 3 * p->N + 8 * 4 + 24 * 4 + 2 * p->N + 64;
+  const size_t lds = polar_scl_lds_bytes(p->N, list_size);
   // Above the default 64 KB of dynamic LDS the limit has to be raised; it is a per-device attribute of the kernel, so it is set on
   // every such launch (a cache per thread would be wrong for a thread that drives several devices).
   if (lds > 48 * 1024) {

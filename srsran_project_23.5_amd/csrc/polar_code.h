@@ -90,6 +90,32 @@ inline int polar_build_code(const miphy_polar_code* c, polar_host_code& h)
   return MIPHY_OK;
 }
 
+// What the list decoders read per position (polar_scl_run): the N information-set flags, followed by, per position, the exponent r of
+// the largest aligned all-frozen block [i, i + 2^r) that starts there (orc_polar_scl_decode's rate-0 rule; 0 at an information bit).
+inline void polar_build_list_flags(const polar_host_code& h, std::vector<uint8_t>& tab)
+{
+  tab.assign(h.k_set.begin(), h.k_set.end());
+  const uint32_t Np = (uint32_t)h.k_set.size();
+  uint32_t       np = 0;
+  while ((1u << np) < Np)
+    ++np;
+  tab.resize(2 * Np, 0);
+  for (uint32_t i = 0; i < Np; ++i) {
+    uint32_t r = 0;
+    if (!h.k_set[i]) {
+      while (r < np && (i & ((2u << r) - 1u)) == 0) {
+        bool frozen = true;
+        for (uint32_t j = 0; j < (2u << r) && frozen; ++j)
+          frozen = !h.k_set[i + j];
+        if (!frozen)
+          break;
+        ++r;
+      }
+    }
+    tab[Np + i] = (uint8_t)r;
+  }
+}
+
 inline void polar_emit(std::vector<uint32_t>& s, uint32_t op, uint32_t stage, uint32_t pos)
 {
   s.push_back(op | (stage << 4) | (pos << 8));

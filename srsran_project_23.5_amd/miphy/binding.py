@@ -124,6 +124,9 @@ def lib():
         l.miphy_debug_set_uci_polar_piece_bytes.argtypes = [C.c_size_t]
         l.miphy_debug_set_uci_polar_piece_bytes.restype = None
         l.miphy_debug_uci_polar_pieces.restype = C.c_uint
+        l.miphy_uci_polar_decode_list_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+        l.miphy_debug_uci_polar_list_segments.argtypes = [C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+        l.miphy_debug_uci_polar_list_segments.restype = None
         l.miphy_pucch_process_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
         l.miphy_prach_detect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_prach_generate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 2
@@ -720,6 +723,20 @@ class Context:
             assert status.numel() >= jobs.size
         check(lib().miphy_uci_polar_decode_batch(self.h, C.c_void_p(jobs.ctypes.data), jobs.size, _dptr(llr), _dptr(payload), _dptr(status),
                                                  _stream_ptr(stream)))
+
+    def uci_polar_decode_list_batch(self, jobs, list_size, llr, payload, status, stream=None):
+        """uci_polar_decode_batch with CRC-aided list decoding (list_size 1, 2, 4 or 8) of the fields of 20 bits and more; list size 1
+        and the fields of 12..19 bits go through the SSC kernel. Same arguments otherwise. Only enqueues."""
+        import torch
+        assert isinstance(jobs, np.ndarray) and jobs.dtype == UciPolarJob, "uci_polar_decode_list_batch takes host jobs"
+        jobs = np.ascontiguousarray(jobs)
+        assert llr.dtype == torch.int8 and payload.dtype == torch.uint8 and status.dtype == torch.uint8
+        if jobs.size:  # the extents the kernels may touch lie inside the tensors (the library sees raw pointers)
+            assert (jobs["llr_offset"].astype(np.int64) + jobs["nof_llr"].astype(np.int64)).max() <= llr.numel(), "soft bits outside `llr`"
+            assert (jobs["payload_offset"].astype(np.int64) + jobs["nof_bits"].astype(np.int64)).max() <= payload.numel(), "payload outside `payload`"
+            assert status.numel() >= jobs.size
+        check(lib().miphy_uci_polar_decode_list_batch(self.h, C.c_void_p(jobs.ctypes.data), jobs.size, int(list_size), _dptr(llr), _dptr(payload),
+                                                      _dptr(status), _stream_ptr(stream)))
 
     def pucch_process_batch(self, jobs, grid, payload, results, llr=None, stream=None):
         """PUCCH formats 1 and 2 (jobs: numpy PucchJob array, or a uint8 device tensor holding the same bytes): grid complex64 device

@@ -12,7 +12,9 @@ Kernel time proper comes from a kernel trace, in a run of its own per configurat
   rocprofv3 --kernel-trace --stats -d OUT -- python tools/uci_polar_throughput.py --trace A E FIELDS [--reps 6]
 makes --reps calls of each entry point and nothing else; the sum of the durations of uci_polar_decode_kernel (and of
 polar_decode_kernel) in OUT's kernel statistics, divided by --reps, is the kernel time of one call.
-Run on the MI355X:  python tools/uci_polar_throughput.py [--reps 15]
+--list L (2, 4 or 8) measures miphy_uci_polar_decode_list_batch at that list size instead (uci_polar_scl_kernel for the fields of 20
+bits and more); the same command without it gives the list-size-1 figures to put next to them. --shape A E keeps one shape.
+Run on the MI355X:  python tools/uci_polar_throughput.py [--reps 15] [--list L] [--shape A E]
 """
 import argparse
 import json
@@ -48,6 +50,8 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--sizes", type=int, nargs="*", default=[16, 1024, 65536])
     ap.add_argument("--mixed-max", type=int, default=65536, help="largest batch that also runs the mixed draw")
+    ap.add_argument("--list", type=int, default=1, choices=(1, 2, 4, 8), help="list size; above 1 the list entry point is measured")
+    ap.add_argument("--shape", type=int, nargs=2, metavar=("A", "E"), help="this shape only, no mixed draw")
     ap.add_argument("--trace", type=int, nargs=3, metavar=("A", "E", "FIELDS"), help="one configuration, --reps calls of each entry point, "
                     "no timing: the run to put under a kernel trace")
     args = ap.parse_args()
@@ -92,7 +96,7 @@ def main():
         return float(np.median(host)), float(np.median(dev))
 
     for n in ([args.trace[2]] if args.trace else args.sizes):
-        for shape in ([tuple(args.trace[:2])] if args.trace else SHAPES + (["mixed"] if n <= args.mixed_max else [])):
+        for shape in ([tuple(args.trace[:2])] if args.trace else [tuple(args.shape)] if args.shape else SHAPES + (["mixed"] if n <= args.mixed_max else [])):
             reps = min(args.reps, 3) if shape == "mixed" and n > 1024 else args.reps
             if shape == "mixed":
                 A, E = draw_mixed(rng, n, miphy)
@@ -105,8 +109,11 @@ def main():
             llr = torch.from_numpy(rng.integers(-60, 61, int(E.sum())).astype(np.int8)).cuda()
             pay = torch.zeros(int(A.sum()), dtype=torch.uint8, device="cuda")
             st = torch.zeros(n, dtype=torch.uint8, device="cuda")
-            host_us, dev_us = measure(lambda: ctx.uci_polar_decode_batch(jobs, llr, pay, st), reps)
-            row = {"fields": n, "reps": reps, "A": int(A[0]) if shape != "mixed" else "mixed", "E": int(E[0]) if shape != "mixed" else "mixed",
+            if args.list > 1:
+                host_us, dev_us = measure(lambda: ctx.uci_polar_decode_list_batch(jobs, args.list, llr, pay, st), reps)
+            else:
+                host_us, dev_us = measure(lambda: ctx.uci_polar_decode_batch(jobs, llr, pay, st), reps)
+            row = {"list": args.list, "fields": n, "reps": reps, "A": int(A[0]) if shape != "mixed" else "mixed", "E": int(E[0]) if shape != "mixed" else "mixed",
                    "host_us": round(host_us, 1), "device_us": round(dev_us, 1), "pieces": int(miphy.lib().miphy_debug_uci_polar_pieces()),
                    "fields_per_s_device": round(n / dev_us * 1e6)}
             if shape != "mixed":  # the yardstick: the same code, one codeword per segment, tables cached on the device
