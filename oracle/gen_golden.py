@@ -323,6 +323,28 @@ for i, (row, nports, k, cdm, dens, start_rb, nof_rb, l0, slot, scr, amp) in enum
 d["n"] = np.array(len(cases))
 save("csi_rs", **d)
 
+# ---------------------------------------------------------------------- NZP-CSI-RS patterns only (parameters + get_csi_rs_pattern, no grids): 64 cases
+# chosen from a larger draw so that every mapping row, every (start_rb, nof_rb) parity of both half densities (rows 2 and 3) and of densities
+# one and three, and the two jobs of tests/dl_grid.compose_slot are present (dl_grid.csi_rs_coverage_missing lists what a set of cases lacks)
+import dl_grid as D  # noqa: E402
+pool = []
+for (row, nports, k, cdm, dens, start_rb, nof_rb, l0, slot, scr, amp) in O.csi_rs_cases(np.random.default_rng(32), 600):
+    l0 = min(l0, 12)
+    _, bes, rm, sm = O.r_csi_rs_map(1, slot, start_rb, nof_rb, row, k, l0, 0, cdm, dens, scr, amp, nports, 80)
+    pool.append(dict(slot=slot, scr=scr, amp=amp, start_rb=start_rb, nof_rb=nof_rb, bes=bes, row=row, cdm=cdm, dens=dens, nports=nports, l0=l0, k_ref=list(k),
+                     rm=rm[:nports].copy(), sm=sm[:nports].copy()))
+chosen = []
+for fill in (False, True):  # first the cases that close a gap, then the draw's order up to 64
+    for c in pool:
+        if len(chosen) < 64 and not any(c is x for x in chosen) and (fill or len(D.csi_rs_coverage_missing(chosen + [c])) < len(D.csi_rs_coverage_missing(chosen))):
+            chosen.append(c)
+assert len(chosen) == 64 and not D.csi_rs_coverage_missing(chosen), D.csi_rs_coverage_missing(chosen)
+meta, ks, rms, sms = np.zeros((64, 13)), np.full((64, 4), -1, np.int8), np.zeros((64, 16), np.uint16), np.zeros((64, 16), np.uint16)
+for i, c in enumerate(chosen):
+    meta[i] = [c["slot"], c["scr"], c["amp"], c["start_rb"], c["nof_rb"], c["bes"][0], c["bes"][1], c["bes"][2], c["row"], c["cdm"], c["dens"], c["nports"], c["l0"]]
+    ks[i, :len(c["k_ref"])], rms[i, :c["nports"]], sms[i, :c["nports"]] = c["k_ref"], c["rm"], c["sm"]
+save("csi_rs_patterns", meta=meta, k_ref=ks, re_mask=rms, symbol_mask=sms)
+
 # ---------------------------------------------------------------------- zero-forcing equalizer on its own (reference outputs, AVX2 1 x N / scalar 2 x 2)
 d = {}
 erng = np.random.default_rng(5150)

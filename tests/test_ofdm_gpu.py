@@ -161,3 +161,43 @@ def test_ofdm_symbol_entry_points_equal_the_slot_ones(ctx, mu, rb, N, wo, fc):
     ctx.ofdm_modulate_symbols(mcfg, yj, g_d, y_sym)
     torch.cuda.synchronize()
     assert torch.equal(y_slot, y_sym)
+
+
+@pytest.mark.parametrize("mu,rb,N", [(0, 6, 128), (1, 51, 1536)])
+def test_ofdm_demodulate_more_symbols_than_one_wave_of_workgroups(ctx, mu, rb, N):
+    """ofdm_demodulate starts min(symbols, CUs * per_cu) workgroups, each looping over its share of the symbols with a barrier between two of
+    them (the LDS buffer is rewritten). per_cu = min(8, 160 KiB / (fft_lds_bytes(N) + 512)) -- 8 for both sizes here -- so the loop makes a
+    second trip only beyond CUs * 8 symbols: 147 slots on a 256-CU chip, far more than any other test demodulates. Five distinct slots, repeated:
+    every output slot is bit-identical to the same slot demodulated in a batch of five (one trip), which is within TOL of the oracle.
+    This pins the second trip's indexing and results. It does not catch a missing barrier at the end of the loop body: a build without it passed
+    (a wavefront reaches its next LDS write only after a round trip to HBM, long after the others have read their outputs)."""
+    import torch
+    import miphy
+    wo = 3
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    fft_lds_bytes = (N + (N >> 3) + 16) * 8                         # fft_device.h
+    per_cu = max(1, min(8, (160 * 1024) // (fft_lds_bytes + 512)))  # ofdm_demodulate
+    assert per_cu == 8
+    n_slots = (cus * per_cu) // 14 + 40
+    assert 14 * n_slots > cus * per_cu
+    rng = np.random.default_rng(N + 7)
+    cfg, ocfg = miphy.OfdmConfig(mu, rb, N, wo, 0.5, 0.0, 3.5e9), OfdmCfg(mu, rb, N, wo, 0.5, 3.5e9)
+    slot_of = [k % (1 << mu) for k in range(5)]
+    xs = [((rng.standard_normal(cfg.slot_size(s)) + 1j * rng.standard_normal(cfg.slot_size(s))) * 0.7).astype(np.complex64) for s in slot_of]
+    starts = np.concatenate([[0], np.cumsum([x.size for x in xs])[:-1]])
+    x_d = torch.from_numpy(np.concatenate(xs)).cuda()
+    gsz = 14 * rb * 12
+    jobs = np.zeros(n_slots, dtype=miphy.OfdmJob)
+    for i in range(n_slots):
+        jobs[i] = (int(starts[i % 5]), i * gsz, slot_of[i % 5], 0)
+    few_d = torch.zeros(5 * gsz, dtype=torch.complex64, device="cuda")
+    many_d = torch.zeros(n_slots * gsz, dtype=torch.complex64, device="cuda")
+    ctx.ofdm_demodulate_slots(cfg, jobs[:5].copy(), x_d, few_d)
+    ctx.ofdm_demodulate_slots(cfg, jobs, x_d, many_d)
+    torch.cuda.synchronize()
+    few, many = few_d.cpu().numpy().reshape(5, 14, rb * 12), many_d.cpu().numpy().reshape(n_slots, 14, rb * 12)
+    for k in range(5):
+        exp = o_ofdm_demod_slot(ocfg, slot_of[k], xs[k])
+        assert rel_err(few[k], exp) < TOL, (k, rel_err(few[k], exp))
+    bad = [i for i in range(n_slots) if not np.array_equal(many[i].view(np.uint32), few[i % 5].view(np.uint32))]
+    assert not bad, (len(bad), bad[:8])

@@ -278,3 +278,19 @@ def test_nzp_csi_rs_generator():
         assert np.array_equal(out.view(np.uint32), g["grid_%d" % i].view(np.uint32)), i
         rows.add(int(row))
     assert rows == {1, 2, 3, 4, 5, 6, 7, 8}
+
+
+def test_csi_rs_pattern_fixture_coverage():
+    """tests/golden/csi_rs_patterns.npz (parameters and reference patterns, no grids): 64 cases with every mapping row, all four (start_rb, nof_rb)
+    parities for both half densities of rows 2 and 3 and for densities one and three, and the two jobs of the composed slot (dl_grid.compose_slot).
+    The oracle accepts every pattern: the k-th element of the sequence lands on the k-th RE of the pattern, and the counts agree."""
+    import dl_grid as D
+    cases = D.csi_rs_pattern_cases()
+    assert len(cases) == 64 and D.csi_rs_coverage_missing(cases) == []
+    assert D.csi_rs_coverage_missing([c for c in cases if not (c["row"] == 3 and c["dens"] == 0 and c["start_rb"] % 2 == 1 and c["nof_rb"] % 2 == 1)]) != []
+    for i, c in enumerate(cases):
+        assert c["nports"] == dict((r[0], r[1]) for r in O.CSI_RS_ROWS)[c["row"]] and c["start_rb"] + c["nof_rb"] <= 80, i
+        out = np.zeros((c["nports"], 14, 80 * 12), np.complex64)
+        assert O.o_csi_rs_map(c["slot"], c["scr"], c["amp"], c["start_rb"], c["nof_rb"], c["bes"], c["row"], c["cdm"], c["dens"], list(range(c["nports"])), c["rm"],
+                              c["sm"], 80, out) == 0, i
+        assert (out != 0).any(axis=(1, 2)).all(), i

@@ -1,22 +1,13 @@
 """GPU: the fused PDSCH processor (miphy_pdsch_process_batch, pdsch_processor::process): transport blocks to grid REs for a
 batch of PDUs, bit-exact against the oracle chain pdsch_encoder -> pdsch_modulator -> dmrs_pdsch_processor with the parameters
 the reference processor derives (pdsch_processor_impl.cpp:198-305)."""
-import ctypes
-
 import numpy as np
 import pytest
 
-import oracle_lib as O
+import dl_grid as D
 from test_pdsch_mod_gpu import _words
 
 pytestmark = pytest.mark.gpu
-_libm = ctypes.CDLL("libm.so.6")
-_libm.powf.restype = ctypes.c_float
-_libm.powf.argtypes = [ctypes.c_float, ctypes.c_float]
-
-
-def db_to_amplitude(x):  # convert_dB_to_amplitude (math_utils.h:101-104), single precision
-    return float(_libm.powf(10.0, np.float32(x) / np.float32(20.0)))
 
 
 # bg, mod, tbs bits, rv, grid PRBs, bwp (start, size), allocation (first, count), start symbol, nof symbols, DM-RS symbols, CDM groups,
@@ -54,14 +45,12 @@ def test_batch_matches_oracle_chain(ctx):
         for r, (pm, rm, sm) in enumerate(reserved):
             p["reserved"][r]["prb_mask"], p["reserved"][r]["re_mask"], p["reserved"][r]["symbols"] = _words(pm), rm, sm
         p["tb_offset"], p["grid_offset"] = tb_off, grid_off
-        # the oracle chain with the parameters pdsch_processor_impl derives
-        pl = np.nonzero(rb)[0]
-        nre = O.pdsch_nof_re(pl, start, nof, dm, 0, cdm, bs, bz, reserved)
-        assert miphy.pdsch_pdu_nof_re(p) == nre, i
-        cw = O.o_pdsch_encode(bg, rv, mod, lbrm * 8, 1, nre, tb)
+        # the oracle chain with the parameters pdsch_processor_impl derives (dl_grid.o_pdsch_process: one copy for this test and the background-grid ones;
+        # it asserts that the modulator mapped as many elements as O.pdsch_nof_re counts)
         g = np.zeros((ngp, 14, nprb * 12), dtype=np.complex64)
-        assert O.o_pdsch_modulate(rnti, n_id, db_to_amplitude(-xdb), 1, [mod], [cw], start, nof, dm, 0, cdm, bs, bz, pl, reserved, [port], nprb, g) == nre
-        O.o_dmrs_pdsch_map(slot, bs if prb0 else 0, 0, scr, nscid, db_to_amplitude(-ddb), dm, rb, [port], g)
+        nre = D.o_pdsch_process(dict(bg=bg, rv=rv, mod=mod, lbrm_bytes=lbrm, tb=tb, rnti=rnti, n_id=n_id, slot=slot, scr=scr, n_scid=nscid, start=start, nof=nof,
+                                     dmrs_symbols=dsyms, cdm=cdm, bwp=(bs, bz), rb=rb, reserved=reserved, port=port, ref_point_prb0=prb0, dmrs_dB=ddb, data_dB=xdb), g)
+        assert miphy.pdsch_pdu_nof_re(p) == nre, i
         want.append(g)
         tbs.append(tb)
         tb_off += (tb.size + 15) // 16 * 16

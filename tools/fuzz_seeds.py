@@ -12,11 +12,14 @@ ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)),
 DEFAULT = ["tests/test_ldpc_decode_gpu.py", "tests/test_ldpc_chain_gpu.py", "tests/test_sch_gpu.py", "tests/test_pusch_demod_gpu.py", "tests/test_pdsch_mod_gpu.py",
            "tests/test_pdsch_proc_gpu.py", "tests/test_polar_gpu.py", "tests/test_ofh_iq_gpu.py", "tests/test_harq_pool_gpu.py", "tests/test_chest_gpu.py",
            "tests/test_ofdm_gpu.py", "tests/test_pusch_proc_gpu.py", "tests/test_pdcch_proc_gpu.py", "tests/test_ssb_proc_gpu.py", "tests/test_csi_rs_gpu.py",
-           "tests/test_equalizer_gpu.py", "tests/test_ulsch_demux_gpu.py", "tests/test_pusch_uci_gpu.py"]
+           "tests/test_equalizer_gpu.py", "tests/test_ulsch_demux_gpu.py", "tests/test_pusch_uci_gpu.py", "tests/test_dl_grid_gpu.py", "tests/test_prach_gpu.py",
+           "tests/test_prach_demod_gpu.py", "tests/test_pucch_proc_gpu.py", "tests/test_uci_decode_gpu.py", "tests/test_uci_polar_gpu.py",
+           "tests/test_uci_polar_list_gpu.py"]
 
 
 # Scenario tests: besides their parity assertions they assert a particular outcome of a borderline transmission (first attempt fails,
-# a retransmission recovers), which holds for their own seed only; the parity they check is covered by the tests above.
+# a retransmission recovers), which holds for their own seed only; the parity they check is covered by the tests above. (The PRACH, PUCCH and
+# UCI files hold none: all their tests pass under seed shifts 1000 and 2000.)
 SCENARIO = ["tests/test_harq_pool_gpu.py::test_pool_backed_harq", "tests/test_pusch_proc_gpu.py::test_retransmission_through_the_processor"]
 
 
