@@ -54,15 +54,64 @@ def test_dft_large_sizes_four_step(ctx, N):
     assert rel_err(np.fft.fft(y.astype(np.complex128)).astype(np.complex64), o_dft(y, False)) < 1e-6
 
 
-def test_dft_unsupported_size(ctx):
+# Every size the in-LDS transform serves, from the rule in include/miphy.h (2^a * 3^b, 8 <= N <= 4096), not from the kernel.
+SINGLE_PASS = sorted(2 ** a * 3 ** b for a in range(13) for b in range(8) if 8 <= 2 ** a * 3 ** b <= 4096)
+PAD = 16
+SENTINEL = np.complex64(12345.0 - 54321.0j)
+
+
+def test_single_pass_size_list():
+    assert len(SINGLE_PASS) == 51 and len(set(SINGLE_PASS)) == 51
+    assert SINGLE_PASS[0] == 8 and SINGLE_PASS[-1] == 4096
+    assert {9, 27, 81, 243, 729, 2187, 1152, 2304, 3456, 3888} <= set(SINGLE_PASS)
+
+
+@pytest.mark.parametrize("N", SINGLE_PASS)
+def test_dft_every_single_pass_size(ctx, N):
+    """All 51 sizes of the single-pass kernel, both directions, three distinct transforms per call (the per-transform offset), against the
+    double-precision DFT by definition. The ten sizes of test_dft_sizes have at most one factor 3, so there the radix-3 pass runs last and
+    without twiddles; here it runs up to seven times (2187), with non-power-of-two strides and workgroups, and on sizes with fewer
+    butterflies than lanes. 16 sentinel elements behind the n * N results must stay: a scatter past the end would change them.
+    A single-precision restatement of the pass structure (running twiddle product, float tables) measured on the CPU stays within
+    8.5e-7 * rms of the exact transform at every one of the sizes, so TOL has a fourfold margin."""
     import torch
-    x = torch.zeros(5000, dtype=torch.complex64, device="cuda")
-    with pytest.raises(RuntimeError):
-        ctx.dft_batch(5000, False, 1, x, x.clone())
+    rng = np.random.default_rng(N)
+    n = 3
+    x = (rng.uniform(-1, 1, (n, N)) + 1j * rng.uniform(-1, 1, (n, N))).astype(np.complex64)
+    x_d = torch.from_numpy(x.reshape(-1)).cuda()
+    worst = 0.0
+    for inv in (False, True):
+        out_d = torch.full((n * N + PAD,), complex(SENTINEL), dtype=torch.complex64, device="cuda")
+        ctx.dft_batch(N, inv, n, x_d, out_d)
+        torch.cuda.synchronize()
+        out = out_d.cpu().numpy()
+        assert (out[n * N:].view(np.uint64) == np.array([SENTINEL]).view(np.uint64)[0]).all(), (N, inv, "written past the end")
+        errs = [rel_err(out[i * N:(i + 1) * N], o_dft(x[i], inv)) for i in range(n)]
+        worst = max(worst, max(errs))
+        for i in range(n):
+            assert errs[i] < TOL, (N, inv, i, errs[i])
+    print("N = %d: largest distance %.2e" % (N, worst))
+
+
+def test_dft_unsupported_size(ctx):
+    """Below 8 (4, 6), a foreign prime factor (640 = 128 * 5; 4104 = 2^3 * 3^3 * 19, also above 4096), 5000: rejected, nothing written."""
+    import torch
+    for N in (4, 6, 640, 4104, 5000):
+        assert N not in SINGLE_PASS
+        x = torch.zeros(N, dtype=torch.complex64, device="cuda")
+        out = torch.full((N,), complex(SENTINEL), dtype=torch.complex64, device="cuda")
+        with pytest.raises(RuntimeError, match="not supported"):
+            ctx.dft_batch(N, False, 1, x, out)
+        torch.cuda.synchronize()
+        assert (out.cpu().numpy().view(np.uint64) == np.array([SENTINEL]).view(np.uint64)[0]).all(), N
 
 
 CASES = [(1, 273, 4096, 144, 3.5e9), (1, 273, 4096, 0, 3.5e9), (1, 106, 2048, 72, 3.5e9), (0, 52, 1024, 10, 2.6e9),
-         (1, 51, 1536, 0, 3.45e9), (2, 66, 1024, 36, 28e9)]
+         (1, 51, 1536, 0, 3.45e9), (2, 66, 1024, 36, 28e9),
+         # sizes with 3^2 and 3^3 (radix-3 passes with twiddles, workgroups of 192, 320 and 448 threads):
+         (2, 90, 1152, 20, 28e9),    # four slots, long CP on symbols 0 and 28; the CP of 81 samples is odd: 16- and 8-byte loads alternate
+         (0, 190, 2304, 7, 2.6e9),   # odd window offset: every symbol on the unaligned path, phase ramp active
+         (1, 273, 3456, 0, 3.5e9)]   # the widest grid
 
 
 @pytest.mark.parametrize("mu,rb,N,wo,fc", CASES)
@@ -121,7 +170,7 @@ def test_ofdm_demodulate_and_modulate(ctx, mu, rb, N, wo, fc):
     assert rel_err(g2, g) < 2e-5
 
 
-@pytest.mark.parametrize("mu,rb,N,wo,fc", [CASES[0], CASES[2], CASES[5]])
+@pytest.mark.parametrize("mu,rb,N,wo,fc", [CASES[0], CASES[2], CASES[5], CASES[7]])
 def test_ofdm_symbol_entry_points_equal_the_slot_ones(ctx, mu, rb, N, wo, fc):
     """miphy_ofdm_{de}modulate_symbols (ofdm_symbol_demodulator / _modulator, ofdm_demodulator.h:55-74): one job per OFDM symbol, in any
     order, must give the rows / samples the slot entry points give for the same subframe -- bit-identical, it is the same transform."""
@@ -161,6 +210,45 @@ def test_ofdm_symbol_entry_points_equal_the_slot_ones(ctx, mu, rb, N, wo, fc):
     ctx.ofdm_modulate_symbols(mcfg, yj, g_d, y_sym)
     torch.cuda.synchronize()
     assert torch.equal(y_slot, y_sym)
+
+
+@pytest.mark.parametrize("mu,rb,N,wo,fc", [CASES[6], CASES[2]])
+def test_ofdm_device_resident_jobs(ctx, mu, rb, N, wo, fc):
+    """The four entry points with their jobs in device memory (a uint8 tensor of the same bytes; the library then skips its host check of
+    slot_index and reads the table in place): bit-identical to the same call with host jobs."""
+    import torch
+    import miphy
+    rng = np.random.default_rng(N * 5 + rb)
+    nslots = 1 << mu
+    nsc = rb * 12
+    cfg = miphy.OfdmConfig(mu, rb, N, wo, 0.5, 0.0, fc)
+    mcfg = miphy.OfdmConfig(mu, rb, N, 0, 0.01, 0.0, fc)
+    sizes = [cfg.slot_size(s) for s in range(nslots)]
+    sym = [miphy.ofdm_symbol_size(cfg, i) for i in range(14 * nslots)]
+    sj = np.zeros(nslots, dtype=miphy.OfdmJob)
+    for k, s in enumerate(rng.permutation(nslots)):  # slots in any order in the table, each where the subframe puts it
+        sj[k] = (int(np.sum(sizes[:s])), int(s) * 14 * nsc, int(s), 0)
+    starts = np.concatenate([[0], np.cumsum(sym)[:-1]])
+    yj = np.zeros(14 * nslots, dtype=miphy.OfdmJob)
+    for k, i in enumerate(rng.permutation(14 * nslots)):
+        yj[k] = (int(starts[i]), int(i) * nsc, int(i), 0)
+    sj["grid_empty"][-1] = 1
+    yj["grid_empty"][3] = 1
+    x_d = torch.from_numpy(((rng.standard_normal(sum(sizes)) + 1j * rng.standard_normal(sum(sizes))) * 0.7).astype(np.complex64)).cuda()
+    g_d = torch.from_numpy((rng.standard_normal(nslots * 14 * nsc) + 1j * rng.standard_normal(nslots * 14 * nsc)).astype(np.complex64)).cuda()
+    for jobs, demod, mod in ((sj, ctx.ofdm_demodulate_slots, ctx.ofdm_modulate_slots), (yj, ctx.ofdm_demodulate_symbols, ctx.ofdm_modulate_symbols)):
+        jobs_d = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
+        assert jobs_d.is_cuda and jobs_d.numel() == jobs.size * miphy.OfdmJob.itemsize
+        grid_h, grid_dv = torch.zeros_like(g_d), torch.zeros_like(g_d)
+        demod(cfg, jobs, x_d, grid_h)
+        demod(cfg, jobs_d, x_d, grid_dv)
+        y_h, y_dv = torch.full_like(x_d, 7.0), torch.full_like(x_d, 7.0)
+        mod(mcfg, jobs, g_d, y_h)
+        mod(mcfg, jobs_d, g_d, y_dv)
+        torch.cuda.synchronize()
+        bits = lambda t: torch.view_as_real(t).view(torch.int32)
+        assert (grid_h != 0).all() and torch.equal(bits(grid_h), bits(grid_dv))
+        assert (y_h != 7.0).all() and torch.equal(bits(y_h), bits(y_dv))
 
 
 @pytest.mark.parametrize("mu,rb,N", [(0, 6, 128), (1, 51, 1536)])

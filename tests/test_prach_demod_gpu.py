@@ -126,6 +126,29 @@ def test_smallest_single_pass_shapes(ctx, fmt, srate, mu, N, nsym):
     assert e < TOL, e
 
 
+@pytest.mark.parametrize("srate,fmt,mu,nfd,N", [
+    (5760000, 3, 0, 1, 1152),    # single-pass kernel, two radix-3 passes (the second pass's twiddles), 192 threads
+    (11520000, 3, 1, 1, 2304),   # single-pass kernel, 320 threads
+    (17280000, 3, 0, 1, 3456),   # single-pass kernel, three radix-3 passes, 448 threads
+    (17280000, 4, 0, 1, 1152),   # short format, two symbols
+    (46080000, 4, 0, 2, 3072),   # a short format at 46.08 MHz
+    (92160000, 3, 0, 2, 18432),  # four-step at 92.16 MHz
+])
+def test_sizes_and_rates_beyond_the_fixture(ctx, srate, fmt, mu, nfd, N):
+    """Sampling rates the recorded fixture does not hold, among them the three whose format 3 transform has a factor 9 or 27 (no other
+    test of the single-pass kernel here has one). One window of noise each, the first occasion straddling bin 0."""
+    c = straddling(srate, fmt, mu, nfd)
+    g = D.geometry(c)
+    assert g["dft_size"] == N
+    b = D.bins(g, 0)
+    assert b[0] > b[-1]  # wraps from bin N - 1 to bin 0
+    x = noise(srate // 1000 + fmt, int(c[D.C_NSAMPLES]))
+    got, _, _, _ = run(ctx, [c], [x])
+    e = D.rel_err(got[0], D.demodulate(x, c, g))
+    print("%d Hz, format %d, N = %d: distance %.2e" % (srate, fmt, N, e))
+    assert e < TOL, e
+
+
 def test_buffer_strides_and_bounds(ctx):
     """Strides above what is used, slack around every job's buffer, two ports of one configuration through two jobs, a single-pass and a
     four-step configuration in one call: every row lands where the strides put it and nothing else changes."""

@@ -80,11 +80,12 @@ def error_code(cfg, **kw):
 def test_info_equals_the_restated_geometry_on_a_sweep():
     """Every (format, PUSCH spacing, sampling rate, start symbol 0..13): where the restatement accepts, the same numbers; where it
     rejects, MIPHY_EINVAL. Short formats with as many time-domain occasions as the slot holds. 2.25 and 5.76 MHz are there for the
-    times that are not whole numbers of samples (16 kappa is 1.17 and 3 samples)."""
+    times that are not whole numbers of samples (16 kappa is 1.17 and 3 samples); 11.52, 17.28 and 92.16 MHz are rates of the GPU tests
+    (tests/test_prach_demod_gpu.py) outside prach_demod_ref.SRATES."""
     accepted = 0
     for fmt in range(14):
         for mu in range(4):
-            for srate in D.SRATES + (122880000, 2250000, 5760000):
+            for srate in D.SRATES + (122880000, 2250000, 5760000, 11520000, 17280000, 92160000):
                 for start in range(14):
                     duration = 0 if fmt < 4 else D.SHORT[fmt - 4][3]
                     ntd = 1 if fmt < 4 else min(D.MAX_TD, max(1, (14 - start) // duration))
