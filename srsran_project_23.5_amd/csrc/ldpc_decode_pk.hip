@@ -431,11 +431,11 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
         else
           update_rows_pk_split<false, PARTS>(pe, part, soft, cl, lr, Hv, Zv, lr < H, xch, nth, next);
         pe = pn;
-      } else if (tid < H) {
+      } else if (tid < H) { // (<FUSED>: the address form of pk_edge_addresses that adds the column offset in the split pays in the 168-register instances only)
         if (GMSG && (int)(li >> 16) >= pairs_lds) { // this layer's messages live in global memory (separate code: the address space is part of the instruction)
-          update_rows_pk_visit(it, m, d, soft, c2v_glob + 64 * (li >> 16), edges, tid, Hv, Zv);
+          update_rows_pk_visit<FUSED>(it, m, d, soft, c2v_glob + 64 * (li >> 16), edges, tid, Hv, Zv);
         } else {
-          update_rows_pk_visit(it, m, d, soft, c2v_lane + 64 * (li >> 16), edges, tid, Hv, Zv);
+          update_rows_pk_visit<FUSED>(it, m, d, soft, c2v_lane + 64 * (li >> 16), edges, tid, Hv, Zv);
         }
       }
       PROF_T(p_l1);

@@ -212,7 +212,7 @@ ldpc_decode_pkw_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
         const int       d     = (int)((li >> 10) & 0x3fu);
         const uint32_t* edges = edges_g + 2 * e0;
         if (run && m < nlay)
-          update_rows_pk_visit(it, m, d, soft, msg0 + 64 * (li >> 16), edges, l, Hv, Zv, base);
+          update_rows_pk_visit<false>(it, m, d, soft, msg0 + 64 * (li >> 16), edges, l, Hv, Zv, base);
         __syncthreads();
       }
       if (use_crc && !final_only) { // ldpc_decoder_impl.cpp:126-133

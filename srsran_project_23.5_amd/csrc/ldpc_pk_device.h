@@ -93,9 +93,22 @@ constexpr int LLR_INF = 127;
 constexpr int INF_MUL = 255; // an infinite soft bit (|s| > 120) becomes a message of magnitude >= 255 + 24
 
 // Stage A of a row update, shared by its forms: both rows' soft-bit addresses of every edge of the layer with packed 16-bit arithmetic:
-// {l, l + H} + shift, wrap at Z by the unsigned minimum of p and p - Z, + column offset -- four packed instructions for the two rows, then
-// one mask and one shift to split the pair (LDS addresses stay below 2^16).
-template <int D>
+// {l, l + H} + shift, wrap at Z by the unsigned minimum of p and p - Z -- three packed instructions for the two rows. The pair has to be
+// split into two 32-bit addresses, one instruction per row that selects a half (v_add_u32_sdwa); the column offset is the other operand
+// of that very addition, so that it costs no instruction of its own (a packed "+ {co, co}" before the split left the split adding zero).
+// LDS addresses stay below 2^16.
+// FOLD = false adds the column offset to the pair first and `base` in the split, four packed instructions and the two of the split.
+// It is the form of the instances that the other one does not shorten (VALU instructions of a 19-edge visit, FOLD = false / true):
+//  - the wave kernel, request phase 114 / 152: its `base` is a per-lane group offset, and co + base a vector addition per edge on top
+//    of the split;
+//  - the latency form, 6 / 7 per edge: its {shift, column} words are scalar registers fetched a layer ahead, and the compiler leaves
+//    the split as an addition of zero and adds the offset in an instruction of its own;
+//  - the throughput form that does not dematch, compiled for 128 registers: 630 / 628 in its 19-edge visit that reads messages (the
+//    request phase saves its instructions, the allocator spends them again in the second phase), and the kernel spills one vector
+//    register and six scalar ones more (its other visits would gain; the spill is not accepted).
+// The throughput form that dematches while it loads (168 registers, both message homes) takes FOLD = true: request phase 116 -> 95, a
+// 19-edge visit 602 -> 581 (tools/visit_valu_count.py).
+template <int D, bool FOLD>
 __device__ __forceinline__ void pk_edge_addresses(uint32_t (&adrA)[D], uint32_t (&adrB)[D], const uint32_t* __restrict__ edges, int l, int H, int Z, uint32_t base)
 {
   typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -110,9 +123,15 @@ __device__ __forceinline__ void pk_edge_addresses(uint32_t (&adrA)[D], uint32_t 
 #endif
     const u16x2 T = X + u16x2{sh, sh};
     const u16x2 R = __builtin_elementwise_min(T, (u16x2)(T - Zs));
-    const uint32_t P = __builtin_bit_cast(uint32_t, (u16x2)(R + u16x2{co, co}));
-    adrA[j] = (P & 0xffffu) + base;
-    adrB[j] = (P >> 16) + base;
+    if (FOLD) {
+      const uint32_t P = __builtin_bit_cast(uint32_t, R), cb = (uint32_t)co + base;
+      adrA[j] = (P & 0xffffu) + cb;
+      adrB[j] = (P >> 16) + cb;
+    } else {
+      const uint32_t P = __builtin_bit_cast(uint32_t, (u16x2)(R + u16x2{co, co}));
+      adrA[j] = (P & 0xffffu) + base;
+      adrB[j] = (P >> 16) + base;
+    }
   }
 }
 
@@ -128,7 +147,7 @@ struct pk_no_hook {
 };
 // `mid` is called once between the two phases (the latency form issues the scalar loads of the next layer's edges there: behind the last LDS
 // read of the layer, so that they do not turn the partial lgkmcnt waits on the in-order LDS returns into waits for everything).
-template <int D, bool FIRST, int PARTS = 1, typename MID = pk_no_hook>
+template <int D, bool FIRST, int PARTS = 1, typename MID, bool FOLD>
 __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
                                                uint32_t* __restrict__ c2v, // this lane's message dword of edges 0,1 of the layer
                                                const uint32_t* __restrict__ edges, // {shift, column*Z} per edge
@@ -151,7 +170,7 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO); // the address arithmetic and the LDS requests of a layer
   // Stage A: every address of the layer, then every LDS read of the layer in one go (2 soft bits per edge + the old
   // messages): the latency of the LDS pipe is paid once per layer instead of once per group of edges.
-  pk_edge_addresses<D>(adrA, adrB, edges, l, H, Z, base);
+  pk_edge_addresses<D, FOLD>(adrA, adrB, edges, l, H, Z, base);
   P2_T(q1);
 #pragma unroll
   for (int j = 0; j < D; ++j) {
@@ -273,7 +292,7 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
 //    soft bits are not an output -- hard bits, CRC verdict and iteration count are.
 // So: the soft bits of the other D - 1 edges are read, one packed minimum of |s| and the sign parity are accumulated, the value goes to
 // edge ZE's soft bits and byte slots of the layer's message dwords (layout of update_rows_pk, zeros elsewhere); no other soft bit is stored.
-template <int D, int ZE>
+template <int D, int ZE, bool FOLD>
 __device__ __forceinline__ void update_rows_pk_zero(int8_t* __restrict__ soft, uint32_t* __restrict__ c2v, const uint32_t* __restrict__ edges, int l, int H, int Z,
                                                     uint32_t base = 0)
 {
@@ -281,7 +300,7 @@ __device__ __forceinline__ void update_rows_pk_zero(int8_t* __restrict__ soft, u
   uint32_t adrA[D], adrB[D];
   int      rawA[D], rawB[D];
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO);
-  pk_edge_addresses<D>(adrA, adrB, edges, l, H, Z, base);
+  pk_edge_addresses<D, FOLD>(adrA, adrB, edges, l, H, Z, base);
 #pragma unroll
   for (int j = 0; j < D; ++j) {
     if (j != ZE) {
@@ -361,7 +380,7 @@ __device__ __forceinline__ void update_rows_pk_split(const part_edges<PARTS>& pe
 #define PK_SPLIT_CASE(N)                                                                            \
   case N:                                                                                           \
     if (N <= part_edges<PARTS>::EMAX)                                                               \
-      update_rows_pk<(N <= part_edges<PARTS>::EMAX ? N : 1), FIRST, PARTS, MID>(soft, c2v, pe.w, l, H, Z, 0, active, xch, part, xs, mid); \
+      update_rows_pk<(N <= part_edges<PARTS>::EMAX ? N : 1), FIRST, PARTS, MID, false>(soft, c2v, pe.w, l, H, Z, 0, active, xch, part, xs, mid); \
     break;
     PK_SPLIT_CASE(10)
     PK_SPLIT_CASE(9)
@@ -378,66 +397,68 @@ __device__ __forceinline__ void update_rows_pk_split(const part_edges<PARTS>& pe
   }
 }
 
-template <bool FIRST>
+template <bool FIRST, bool FOLD>
 __device__ __forceinline__ void update_rows_pk_any(int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
 {
   switch (d) {
     case 19:
-      update_rows_pk<19, FIRST>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk<19, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
       break;
     case 10:
-      update_rows_pk<10, FIRST>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk<10, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
       break;
     case 9:
-      update_rows_pk<9, FIRST>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk<9, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
       break;
     case 8:
-      update_rows_pk<8, FIRST>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk<8, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
       break;
     case 7:
-      update_rows_pk<7, FIRST>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk<7, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
       break;
     case 6:
-      update_rows_pk<6, FIRST>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk<6, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
       break;
     case 5:
-      update_rows_pk<5, FIRST>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk<5, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
       break;
     case 4:
-      update_rows_pk<4, FIRST>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk<4, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
       break;
     default:
-      update_rows_pk<3, FIRST>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk<3, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
       break;
   }
 }
 
 // Layers m = 1 and 2 of the first iteration: the degrees these two layers have in the two base graphs (miphy_ctx.hip asserts them).
+template <bool FOLD>
 __device__ __forceinline__ void update_rows_pk_zero_any(int m, int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
 {
   if (m == 1) {
     if (d == 19)
-      update_rows_pk_zero<19, 0>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk_zero<19, 0, FOLD>(soft, c2v, edges, l, H, Z, base);
     else
-      update_rows_pk_zero<10, 0>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk_zero<10, 0, FOLD>(soft, c2v, edges, l, H, Z, base);
   } else {
     if (d == 19)
-      update_rows_pk_zero<19, 1>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk_zero<19, 1, FOLD>(soft, c2v, edges, l, H, Z, base);
     else
-      update_rows_pk_zero<8, 1>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk_zero<8, 1, FOLD>(soft, c2v, edges, l, H, Z, base);
   }
 }
 
 // One layer visit of the throughput form and the wave kernel. Iteration 0 starts at layer 1 (see update_rows_pk_zero: layer 0 changes
-// nothing there), so layer 0's messages are first written in iteration 1, by the instance that reads none.
+// nothing there), so layer 0's messages are first written in iteration 1, by the instance that reads none. FOLD: pk_edge_addresses.
+template <bool FOLD>
 __device__ __forceinline__ void update_rows_pk_visit(int it, int m, int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
 {
   if (it == 0 && (m == 1 || m == 2))
-    update_rows_pk_zero_any(m, d, soft, c2v, edges, l, H, Z, base);
+    update_rows_pk_zero_any<FOLD>(m, d, soft, c2v, edges, l, H, Z, base);
   else if (it == 0 || (it == 1 && m == 0))
-    update_rows_pk_any<true>(d, soft, c2v, edges, l, H, Z, base);
+    update_rows_pk_any<true, FOLD>(d, soft, c2v, edges, l, H, Z, base);
   else
-    update_rows_pk_any<false>(d, soft, c2v, edges, l, H, Z, base);
+    update_rows_pk_any<false, FOLD>(d, soft, c2v, edges, l, H, Z, base);
 }
 
 __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b, uint32_t poly, uint32_t order)
