@@ -105,6 +105,45 @@ def test_sch_chain_harq():
                 assert np.array_equal(tbo, tb_r[t]) and np.array_equal(tbo, tb)
 
 
+def test_sch_chain_sizes_and_tb_crc_failure():
+    """The outcomes tests/test_sch_sizes_gpu.py takes from the oracle, pinned to the reference's pusch_decoder: sizes the standard
+    cannot produce (a zero pad behind the TB CRC, 52 codeblocks), the smallest transport block, both sides of the CRC16 / CRC24A
+    switch, and a transport block whose CRC fails although every codeblock CRC passes (tests/sch_tx.py), first at rv 0 and again as a
+    retransmission at rv 2: the iteration minimum and maximum of the second step are those of C fresh decodes, which is the
+    reference's evidence that the first step reset every codeblock flag (pusch_decoder_impl.cpp:218-220)."""
+    from sch_tx import cb_payload_range, sch_codeword
+    rng = np.random.default_rng(40)
+
+    def run(bg, mod, nl, nsym, tb, cws, rvs, expect_ok, payload):
+        llrs = np.stack([((1 - 2 * c.astype(np.int8)) * 40).astype(np.int8) for c in cws])
+        ok_r, tb_r, mm_r = O.RefPuschDecoder("avx2").decode_sequence(bg, mod, 0, nl, nsym, tb.size, rvs, llrs, 6, True)
+        od = O.OraclePuschDecoder(bg, mod, 0, nl, nsym, tb.size)
+        for t, rv in enumerate(rvs):
+            ok, tbo, mm = od.decode(llrs[t], rv, t == 0, 6, True)
+            assert ok == ok_r[t] == expect_ok and mm == mm_r[t], (bg, tb.size, t, ok, ok_r[t], mm, mm_r[t])
+            if ok or od.seg.nof_cbs > 1:  # the transport block is handed out whenever every codeblock passed
+                assert np.array_equal(tbo, tb_r[t]) and np.array_equal(tbo, payload), (bg, tb.size, t)
+        return mm_r
+
+    for bg, nbytes, mod, nl in ((1, 8429, 4, 1), (1, 54753, 8, 2), (1, 1, 2, 1), (1, 478, 2, 1), (1, 479, 6, 3), (2, 3821, 2, 1)):
+        seg = O.o_segmentation(nbytes * 8, bg, 1, 1, 1000)
+        per_layer = 2 * (nbytes * 8 + 24) // (mod * nl) + 1
+        per_layer += 1 if seg.nof_cbs > 1 and per_layer % seg.nof_cbs == 0 else 0
+        nsym = per_layer * nl
+        tb = rng.integers(0, 256, nbytes, dtype=np.uint8)
+        cws = [O.o_pdsch_encode(bg, rv, mod, 0, nl, nsym, tb) for rv in (0, 2)]
+        for rv, cw in zip((0, 2), cws):
+            assert np.array_equal(cw, O.r_pdsch_encode(bg, rv, mod, 0, nl, nsym, tb, "avx2"))
+        run(bg, mod, nl, nsym, tb, cws, (0, 2), True, tb)
+        if seg.nof_cbs == 1:
+            continue
+        lo, hi = cb_payload_range(seg, seg.nof_cbs // 2)
+        for kw in (dict(tb_crc_flip=0x800001), dict(flip_bits=[(lo + hi) // 2])):
+            bad = [sch_codeword(bg, rv, mod, 0, nl, nsym, tb, **kw) for rv in (0, 2)]
+            mm = run(bg, mod, nl, nsym, tb, [b[0] for b in bad], (0, 2), False, bad[0][1])
+            assert mm[0] == mm[1] == (1, 1)  # both steps decoded codeblocks (all of them: the oracle's statistics agree)
+
+
 def test_dft_ofdm_tolerance():
     rng = np.random.default_rng(5)
     for N in (128, 384, 1024, 3072, 4096):
