@@ -118,7 +118,8 @@ void     miphy_ldpc_decode_plan_destroy(miphy_ldpc_decode_plan* plan);
  * 3 = class-sorted launches, 4 = class-sorted launches with the geometry of a batch that fills the chip whatever its size (no latency form, messages in global
  * memory wherever that buys residency), 5 = class-sorted launches with the latency form of the packed kernel (two parts) on every class (A-B measurement only),
  * 6 = automatic choice with the latency form in two parts instead of four. Adding 0x100 keeps ALL messages of a GMSG launch in global memory (A-B of the
- * split between LDS and global memory). All kernels produce identical results. Prepared plans keep the choice in force when they were
+ * split between LDS and global memory). Adding 0x200 keeps every launch computing its soft-bit addresses (no launch reads them from
+ * the table of miphy_ldpc_address_table; A-B of that instance). All kernels produce identical results. Prepared plans keep the choice in force when they were
  * created: the knob applies to plans created after it is set (and to every per-call decode). */
 void miphy_debug_force_ldpc_kernel(int mode);
 /* Which decoder kernels have been launched since the last reset (tests assert that a forced choice really ran): */
@@ -130,6 +131,17 @@ void miphy_debug_force_ldpc_kernel(int mode);
 #define MIPHY_LDPC_KERNEL_SPLIT 32u /* packed kernel in its latency form: four (or two) times the wavefronts per codeblock (launches of at most one codeblock per CU) */
 #define MIPHY_LDPC_KERNEL_GMSG_PART 64u /* ... a GMSG launch that kept the first layers' messages in LDS (only the layers behind a boundary in global memory) */
 unsigned miphy_debug_ldpc_kernels_used(int reset);
+/* Decoder launches since the last reset that read their soft-bit addresses from a table (the instance of the packed kernel for
+ * high-rate codeblocks that are dematched while they load). */
+unsigned miphy_debug_ldpc_address_table_launches(int reset);
+/* Host only (no device needed): the soft-bit address table of base graph `bg` (1 / 2), lifting size Z and the first `layers` layers,
+ * as the decoder reads it. Lane l < ceil(Z / 2) of a codeblock's workgroup owns check rows l and l + ceil(Z / 2) of every layer (an odd
+ * Z: its last lane owns row l twice); the table has 64 ceil(Z / 128) lanes. Layer after layer, ceil(degree / 4) quads of four words each
+ * per layer: word ((first quad of the layer + q) * lanes + l) * 4 + k belongs to edge 4 q + k of the layer (beyond the degree: the last
+ * edge again) and holds the LDS byte address of the soft bit of row l in its low half, of row l + ceil(Z / 2) in its high half:
+ * ((row + shift) mod Z) + column * Z. Lanes without rows hold zeros. Returns the number of 32-bit words (out may be NULL to ask for
+ * it), or a negative error code. */
+int miphy_ldpc_address_table(int bg, int Z, int layers, uint32_t* out);
 /* A-B knob: streams the launch classes of one call are spread over (1 = one after another on the caller's stream). Like
  * miphy_debug_force_ldpc_kernel, it applies to plans created after it is set. */
 void miphy_debug_set_ldpc_class_streams(int n);

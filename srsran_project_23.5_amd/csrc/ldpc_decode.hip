@@ -24,20 +24,24 @@ struct ldpc_knob_values {
   int  force;         // miphy_ldpc_force_mode (miphy_debug_force_ldpc_kernel, low byte)
   bool hybrid_msgs;   // false (mode | MIPHY_LDPC_FORCE_ALL_GMSG): all messages of a GMSG launch in global memory
   int  class_streams; // streams the launch classes of a call are spread over (miphy_debug_set_ldpc_class_streams)
+  bool adr_tables;    // false (mode | MIPHY_LDPC_FORCE_NO_ADR_TABLE): every launch computes its soft-bit addresses
 };
 struct {
   std::atomic<int>  force{MIPHY_LDPC_FORCE_AUTO};
   std::atomic<bool> hybrid_msgs{true};
   std::atomic<int>  class_streams{1 + MIPHY_NOF_SIDE_STREAMS};
-  ldpc_knob_values  snapshot() const { return {force.load(), hybrid_msgs.load(), class_streams.load()}; }
+  std::atomic<bool> adr_tables{true};
+  ldpc_knob_values  snapshot() const { return {force.load(), hybrid_msgs.load(), class_streams.load(), adr_tables.load()}; }
 } g_knobs;
 std::atomic<unsigned> g_kernels_used{0}; // MIPHY_LDPC_KERNEL_* of every decoder launch since the last reset (miphy_debug_ldpc_kernels_used)
+std::atomic<unsigned> g_adr_table_launches{0}; // launches of the address-table instance since the last reset
 } // namespace
 
 extern "C" void miphy_debug_force_ldpc_kernel(int mode)
 {
   g_knobs.force       = mode & MIPHY_LDPC_FORCE_MODE_MASK;
   g_knobs.hybrid_msgs = !(mode & MIPHY_LDPC_FORCE_ALL_GMSG);
+  g_knobs.adr_tables  = !(mode & MIPHY_LDPC_FORCE_NO_ADR_TABLE);
 }
 
 extern "C" void miphy_debug_set_ldpc_class_streams(int n)
@@ -48,6 +52,11 @@ extern "C" void miphy_debug_set_ldpc_class_streams(int n)
 extern "C" unsigned miphy_debug_ldpc_kernels_used(int reset)
 {
   return reset ? g_kernels_used.exchange(0) : g_kernels_used.load();
+}
+
+extern "C" unsigned miphy_debug_ldpc_address_table_launches(int reset)
+{
+  return reset ? g_adr_table_launches.exchange(0) : g_adr_table_launches.load();
 }
 
 // ---- class-sorted launches ------------------------------------------------------------------------------------------------------
@@ -105,12 +114,14 @@ void miphy_ldpc_build_classes(const miphy_ldpc_dec_desc* descs, uint32_t n, cons
     c.kind             = (uint8_t)((it[p].key >> 61) & 3);
     c.bgi              = (uint8_t)((it[p].key >> 60) & 1);
     c.first = p, c.count = q - p;
+    c.min_Z        = 0xffff;
     c.bundle_first = (uint32_t)C.bundles.size() / 2;
     const int bgK  = c.bgi ? 10 : 22;
     for (uint32_t k = p; k < q; ++k) {
       const miphy_ldpc_dec_desc& d = descs[it[k].idx];
       c.lay                        = std::max<uint8_t>(c.lay, (uint8_t)(it[k].key & 63));
       c.max_Z                      = std::max<uint16_t>(c.max_Z, d.Z);
+      c.min_Z                      = std::min<uint16_t>(c.min_Z, d.Z);
       C.order[k]                   = it[k].idx;
       C.identity &= it[k].idx == k;
     }
@@ -176,6 +187,13 @@ void pk_class_geometry(const miphy_ctx* ctx, const ldpc_knob_values& k, bool fus
   q.gmsg_bytes = gm ? (size_t)q.grid * (q.threads / 64) * (size_t)q.gmsg_pairs * 256 : 0;
   q.used       = MIPHY_LDPC_KERNEL_PACKED | (fused ? MIPHY_LDPC_KERNEL_FUSED : 0u) | (gm ? MIPHY_LDPC_KERNEL_GMSG : 0u) |
            (q.parts > 1 ? MIPHY_LDPC_KERNEL_SPLIT : 0u) | ((gm && q.lds_pairs > 0) ? MIPHY_LDPC_KERNEL_GMSG_PART : 0u);
+  // Soft-bit addresses from a table (ldpc_pk_device.h, pk_table_addresses): the throughput form that dematches, messages in LDS, where every
+  // layer the class can reach has the degree the instance is built for (BG1 up to four layers: high-rate codeblocks) and every lifting size a
+  // table index of its own (multiples of 16: all sizes from 128 on). Every other class computes its addresses.
+  bool one_degree = true;
+  for (int m = 0; m < c.lay; ++m)
+    one_degree &= ctx->h_tables->row_start[c.bgi][m + 1] - ctx->h_tables->row_start[c.bgi][m] == MIPHY_LDPC_ADR_TABLE_DEGREE;
+  q.atab = k.adr_tables && fused && !gm && q.parts == 1 && one_degree && c.min_Z >= 128;
 }
 
 void plan_classes(const miphy_ctx* ctx, const miphy_ldpc_classes& C, bool fuse, const ldpc_knob_values& k, miphy_ldpc_launches& T)
@@ -299,9 +317,15 @@ void plan_one_launch(const miphy_ctx* ctx, const ldpc_knob_values& k, const batc
 }
 } // namespace
 
-void miphy_ldpc_plan_launches(const miphy_ctx* ctx, const miphy_ldpc_classes& C, bool fuse, miphy_ldpc_launches& T)
+int miphy_ldpc_plan_launches(miphy_ctx* ctx, const miphy_ldpc_classes& C, bool fuse, miphy_ldpc_launches& T)
 {
   plan_classes(ctx, C, fuse, g_knobs.snapshot(), T);
+  for (miphy_ldpc_launch& q : T.l) {
+    int rc;
+    if (q.atab && (rc = miphy_ldpc_address_tables(ctx, q.c.bgi, q.c.lay, q.c.min_Z, q.c.max_Z, &q.adr_by_z)))
+      return rc;
+  }
+  return MIPHY_OK;
 }
 
 namespace {
@@ -330,6 +354,7 @@ int enqueue_launches(miphy_ctx* ctx, const miphy_ldpc_launches& T, const miphy_l
     if (rc)
       return rc;
     g_kernels_used.fetch_or(L.used);
+    g_adr_table_launches.fetch_add(L.adr_by_z ? 1u : 0u);
   }
   return MIPHY_OK;
 }
@@ -484,8 +509,7 @@ extern "C" int miphy_ldpc_decode_plan_create(miphy_ctx* ctx, const miphy_ldpc_de
   miphy_ldpc_build_classes(descs, n, nullptr, C);
   auto* p = new miphy_ldpc_decode_plan();
   p->ctx = ctx, p->d_buf = nullptr, p->d_gmsg = nullptr;
-  miphy_ldpc_plan_launches(ctx, C, false, p->T);
-  if (p->T.side_streams && (rc = miphy_side_streams(ctx))) {
+  if ((rc = miphy_ldpc_plan_launches(ctx, C, false, p->T)) || (p->T.side_streams && (rc = miphy_side_streams(ctx)))) {
     delete p;
     return rc;
   }

@@ -187,7 +187,12 @@ __device__ __forceinline__ int pk_fused_image_out(const int8_t* __restrict__ sof
 // PARTS > 1 = the latency form for launches that leave most of the chip idle (a single slot is 38 codeblocks on 256 CUs): PARTS times the
 // wavefronts per codeblock, the PARTS parts of the workgroup share the edges of every layer (update_rows_pk, PARTS) -- about 1 / PARTS of the
 // instructions per wavefront and layer for one more barrier, same results, same LDS image (messages always in LDS).
-template <bool FUSED, bool GMSG, int PARTS = 1>
+// ATAB = the soft-bit addresses of a visit are read from a table instead of computed (pk_table_addresses, ldpc_pk_device.h): throughput
+// form of launches whose reachable layers all have PK_ATAB_DEGREE edges. `adr_by_z[Z / 16]` is the table of lifting size Z,
+// [layer][quad][lane of the workgroup]. The quads of the first layer visited are requested in front of the load phase, every other
+// visit's by the visit before it (across the iteration's CRC and the layer barrier: 19 registers, the raw soft bits are dead there).
+constexpr int PK_ATAB_DEGREE = MIPHY_LDPC_ADR_TABLE_DEGREE, PK_ATAB_QUADS = (PK_ATAB_DEGREE + 3) / 4;
+template <bool FUSED, bool GMSG, int PARTS = 1, bool ATAB = false>
 __global__ void __launch_bounds__(192 * PARTS, PARTS > 1 ? LDPC_PK_MIN_WAVES_SPLIT : (FUSED ? LDPC_PK_MIN_WAVES_FUSED : LDPC_PK_MIN_WAVES_PLAIN))
 ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
                       const miphy_graph_tables* __restrict__ tab,
@@ -204,7 +209,8 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
                       uint32_t* __restrict__ gmsg,
                       int gmsg_pairs,
                       int lds_pairs, // GMSG: the first lds_pairs message dwords of a lane stay in LDS (a layer boundary), the other gmsg_pairs are global
-                      const uint32_t* __restrict__ cb_order) // optional: the launch decodes codeblocks order[0 .. n) of the arrays (one class of a sorted batch)
+                      const uint32_t* __restrict__ cb_order, // optional: the launch decodes codeblocks order[0 .. n) of the arrays (one class of a sorted batch)
+                      const pk_adr_quad* const* __restrict__ adr_by_z) // ATAB: the address table of every lifting size of the launch, at [Z / 16]
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -212,6 +218,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   constexpr bool SPLIT = PARTS > 1;
   static_assert(PARTS == 1 || PARTS == 2 || PARTS == 4, "parts of the latency form");
   static_assert(!(SPLIT && GMSG), "the latency form keeps its messages in LDS");
+  static_assert(!ATAB || (FUSED && !GMSG && !SPLIT), "address tables: the throughput form that dematches, messages in LDS");
   const int nth  = nt / PARTS;                   // threads that own rows: the whole workgroup, or each part of it
   // (wave-uniform by construction -- nth is a multiple of 64 --, and said so: the part selects the edges of a layer, which must stay scalar loads)
   const int part = SPLIT ? __builtin_amdgcn_readfirstlane((tid >= nth) + (PARTS > 2 ? (tid >= 2 * nth) + (tid >= 3 * nth) : 0)) : 0;
@@ -308,6 +315,16 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
       }
     }
   };
+  pk_adr_quad    anx[ATAB ? PK_ATAB_QUADS : 1]; // ATAB: the soft-bit addresses of the next layer visit
+  pk_adr_row     atab    = pk_adr_row();        // ... the table of this lifting size
+  const uint32_t astride = 16u * (uint32_t)nt, alayer = PK_ATAB_QUADS * astride; // ... bytes of a quad and of a layer
+  if (ATAB) {
+    // (wave-uniform, and said so: the codeblock index comes out of LDS, and a descriptor the compiler takes for divergent is a loop per load)
+    const int zq = __builtin_amdgcn_readfirstlane(Z >> 4), bytes = __builtin_amdgcn_readfirstlane(min(bgM, max(4, max_nodes - bgK)) * (int)alayer);
+    atab.rsrc    = __builtin_amdgcn_make_buffer_rsrc(const_cast<pk_adr_quad*>(adr_by_z[zq]), 0, bytes, 0x00020000);
+    atab.soff = alayer; // layer 1: the first one visited
+    pk_table_request<PK_ATAB_DEGREE>(anx, atab, 16u * (uint32_t)tid, astride);
+  }
   if (FUSED) {
     const miphy_ldpc_rdm_desc rd = load_words(rdm + cb);
     pk_fused_load(soft, (global_ci8)(rm_in_base + rd.in_offset), (int)rd.E, (int)dsc.nof_filler_bits, (int)rd.mod, Z, bgK, soft_bytes, pre[0], pre[1], pre[2], tid, nt);
@@ -431,6 +448,11 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
         else
           update_rows_pk_split<false, PARTS>(pe, part, soft, cl, lr, Hv, Zv, lr < H, xch, nth, next);
         pe = pn;
+      } else if (ATAB) {
+        if (tid < H)
+          update_rows_pk_visit_tab<PK_ATAB_DEGREE>(it, m, soft, c2v_lane + 64 * (li >> 16), anx,
+                                                   pk_adr_row{atab.rsrc, (uint32_t)__builtin_amdgcn_readfirstlane((m + 1 < nof_layers) ? m + 1 : 0) * alayer},
+                                                   16u * (uint32_t)tid, astride);
       } else if (tid < H) { // (<FUSED>: the address form of pk_edge_addresses that adds the column offset in the split pays in the 168-register instances only)
         if (GMSG && (int)(li >> 16) >= pairs_lds) { // this layer's messages live in global memory (separate code: the address space is part of the instruction)
           update_rows_pk_visit<FUSED>(it, m, d, soft, c2v_glob + 64 * (li >> 16), edges, tid, Hv, Zv);
@@ -554,7 +576,9 @@ int miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy
   // (the geometry is the launch table's: L.threads counts every part of the latency form, whose L.lds holds the exchange slots)
   const bool fused = (L.used & MIPHY_LDPC_KERNEL_FUSED) != 0, gm = L.gmsg_pairs > 0;
   MIPHY_REQUIRE(L.threads <= 1024, "ldpc_decode: workgroup of %d threads", L.threads);
-  const void* kern = L.parts == 4 ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 4> : (const void*)ldpc_decode_pk_kernel<false, false, 4>)
+  const bool  atab = L.adr_by_z != nullptr;
+  MIPHY_REQUIRE(!atab || (fused && !gm && L.parts == 1), "ldpc_decode: address tables with a launch form that has no such instance");
+  const void* kern = atab ? (const void*)ldpc_decode_pk_kernel<true, false, 1, true> : L.parts == 4 ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 4> : (const void*)ldpc_decode_pk_kernel<false, false, 4>)
                      : L.parts == 2 ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 2> : (const void*)ldpc_decode_pk_kernel<false, false, 2>)
                            : fused ? (gm ? (const void*)ldpc_decode_pk_kernel<true, true> : (const void*)ldpc_decode_pk_kernel<true, false>)
                                    : (gm ? (const void*)ldpc_decode_pk_kernel<false, true> : (const void*)ldpc_decode_pk_kernel<false, false>);
@@ -569,8 +593,10 @@ int miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy
     return rc;
 #define PK_LAUNCH(F, G, ...)                                                                                                                              \
   hipLaunchKernelGGL((ldpc_decode_pk_kernel<F, G, ##__VA_ARGS__>), dim3(L.grid), dim3(L.threads), L.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, \
-                     L.nodes, harq_slot, harq_crc_ok, L.c.count, queue, d_rdm, rm_in, (uint32_t*)gmsg, L.gmsg_pairs, gm ? L.lds_pairs : 0, d_order)
-  if (L.parts == 4 && fused)
+                     L.nodes, harq_slot, harq_crc_ok, L.c.count, queue, d_rdm, rm_in, (uint32_t*)gmsg, L.gmsg_pairs, gm ? L.lds_pairs : 0, d_order, (const pk_adr_quad* const*)L.adr_by_z)
+  if (atab)
+    PK_LAUNCH(true, false, 1, true);
+  else if (L.parts == 4 && fused)
     PK_LAUNCH(true, false, 4);
   else if (L.parts == 4)
     PK_LAUNCH(false, false, 4);

@@ -135,6 +135,60 @@ __device__ __forceinline__ void pk_edge_addresses(uint32_t (&adrA)[D], uint32_t 
   }
 }
 
+// The same addresses read from a table (ATAB instances of the throughput form): they depend on lane, base graph, lifting size, layer and
+// edge only, so the host computes them once per (base graph, Z, layers) -- miphy_ldpc_address_table, the arithmetic above with base = 0 --
+// as adr[layer][edge quad][lane] of four dwords, component k = edge 4 q + k as adrA | adrB << 16 (a layer is padded to a multiple of four
+// edges). A visit holds its ceil(D / 4) quads in registers, splits each component with a mask and a shift -- two VALU instructions per
+// edge instead of five -- and requests the quads of the NEXT visit at the start of its second phase, where the raw soft bits of this
+// one are dead: the loads (coalesced, 1 KB per wavefront each, served by L2) return under the second phase and the layer barrier.
+typedef uint32_t pk_adr_quad __attribute__((ext_vector_type(4)));
+// A table is read through a buffer descriptor: the layer and quad offsets are scalar operands of the load and the lane offset its one
+// vector operand, so that a request issues no address arithmetic (a global_load took a 64-bit vector addition per quad), and the
+// descriptor bounds every access by the size of the table.
+struct pk_adr_row {
+  __amdgpu_buffer_rsrc_t rsrc;
+  uint32_t               soff; // byte offset of the layer's first quad (wave-uniform)
+};
+template <int D>
+__device__ __forceinline__ void pk_table_addresses(uint32_t (&adrA)[D], uint32_t (&adrB)[D], const pk_adr_quad* q)
+{
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    uint32_t w = q[j >> 2][j & 3];
+    asm volatile("" : "+v"(w)); // (keeps the split in the visit, behind its s_setprio: the compiler otherwise hoists it out of the instances of a visit, in front of the priority)
+    adrA[j] = w & 0xffffu;
+    adrB[j]          = w >> 16;
+  }
+}
+// A soft bit of an ATAB visit: the table holds LDS addresses, and the soft bits are the first array of the workgroup's LDS (ldpc_decode_pk.hip:
+// the kernel has no static LDS), so an entry IS the address. Through `soft` the compiler adds the array's base to every half it selects
+// (the value is zero, the instruction stays: one slow-class v_add_u32_sdwa per half); as an absolute LDS address the halves are an AND
+// with a literal (fast class, tools/valu_probe) and a shift.
+template <bool ATAB>
+__device__ __forceinline__ int8_t& pk_soft_bit(int8_t* soft, uint32_t adr)
+{
+  if constexpr (ATAB)
+    return *(int8_t*)(__attribute__((address_space(3))) int8_t*)(uintptr_t)adr;
+  else
+    return soft[adr];
+}
+// `voff` = this lane's byte offset in a quad, `stride` = bytes of a quad. Of a last quad with three edges only three words are loaded:
+// nothing reads the fourth, and a register the allocator knows to be free is reused while the load is in flight -- behind a wait for it.
+template <int D>
+__device__ __forceinline__ void pk_table_request(pk_adr_quad* q, pk_adr_row row, uint32_t voff, uint32_t stride)
+{
+  typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+#pragma unroll
+  for (int k = 0; k < (D + 3) / 4; ++k) {
+    if (4 * k + 3 == D) {
+      const u32x3 t = __builtin_amdgcn_raw_buffer_load_b96(row.rsrc, (int)voff, (int)(row.soff + k * stride), 0);
+      q[k]          = pk_adr_quad{t.x, t.y, t.z, 0u};
+    } else {
+      q[k] = __builtin_amdgcn_raw_buffer_load_b128(row.rsrc, (int)voff, (int)(row.soff + k * stride), 0);
+    }
+  }
+}
+
 // `base` = LDS byte offset of the codeblock's soft bits (0 where a workgroup holds one codeblock: the term then folds away).
 // PARTS > 1 (latency form of the packed kernel: PARTS times the wavefronts per codeblock, each part of the workgroup owns a share of
 // the edges of a layer): D is the number of edges of THIS part; between the two phases the parts exchange their partial {min1, min2,
@@ -147,7 +201,8 @@ struct pk_no_hook {
 };
 // `mid` is called once between the two phases (the latency form issues the scalar loads of the next layer's edges there: behind the last LDS
 // read of the layer, so that they do not turn the partial lgkmcnt waits on the in-order LDS returns into waits for everything).
-template <int D, bool FIRST, int PARTS = 1, typename MID, bool FOLD>
+// ATAB: the addresses of this visit arrive in `aq` (pk_table_addresses), which leaves with those of the layer at `anext`.
+template <int D, bool FIRST, int PARTS = 1, typename MID, bool FOLD, bool ATAB = false>
 __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
                                                uint32_t* __restrict__ c2v, // this lane's message dword of edges 0,1 of the layer
                                                const uint32_t* __restrict__ edges, // {shift, column*Z} per edge
@@ -159,7 +214,11 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
                                                uint32_t* xch = nullptr,
                                                int part = 0,
                                                int xs = 0,
-                                               MID mid = MID())
+                                               MID mid = MID(),
+                                               pk_adr_quad* aq = nullptr,
+                                               pk_adr_row anext = pk_adr_row(),
+                                               uint32_t avoff = 0,
+                                               uint32_t astride = 0)
 {
   constexpr bool SPLIT = PARTS > 1;
   s16x2    v2c[D], mabs[D];
@@ -170,12 +229,15 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO); // the address arithmetic and the LDS requests of a layer
   // Stage A: every address of the layer, then every LDS read of the layer in one go (2 soft bits per edge + the old
   // messages): the latency of the LDS pipe is paid once per layer instead of once per group of edges.
-  pk_edge_addresses<D, FOLD>(adrA, adrB, edges, l, H, Z, base);
+  if constexpr (ATAB)
+    pk_table_addresses<D>(adrA, adrB, aq);
+  else
+    pk_edge_addresses<D, FOLD>(adrA, adrB, edges, l, H, Z, base);
   P2_T(q1);
 #pragma unroll
   for (int j = 0; j < D; ++j) {
-    rawA[j] = soft[adrA[j]];
-    rawB[j] = soft[adrB[j]];
+    rawA[j] = pk_soft_bit<ATAB>(soft, adrA[j]);
+    rawB[j] = pk_soft_bit<ATAB>(soft, adrB[j]);
   }
   if (!FIRST) {
 #pragma unroll
@@ -235,6 +297,8 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
   P2_T(q5);
   mid();
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO2); // the second phase: messages, soft-bit stores, then the layer barrier
+  if constexpr (ATAB)
+    pk_table_request<D>(aq, anext, avoff, astride);
   // Scaling by 0.8 = floor(x * 52428 / 65536), per row (avx2_support.h:65-106).
   const uint32_t s1A = ((uint32_t)(uint16_t)mag1.x * 52428u) >> 16, s1B = ((uint32_t)(uint16_t)mag1.y * 52428u) >> 16;
   const uint32_t s2A = ((uint32_t)(uint16_t)mag2.x * 52428u) >> 16, s2B = ((uint32_t)(uint16_t)mag2.y * 52428u) >> 16;
@@ -259,8 +323,8 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
         c2v[64 * (j >> 1)] = c2v_pack(cprev, c);
       else if (j == D - 1)
         c2v[64 * (j >> 1)] = c2v_pack(c, c);
-      soft[adrA[j]] = (int8_t)r;
-      soft[adrB[j]] = (int8_t)(r >> 16);
+      pk_soft_bit<ATAB>(soft, adrA[j]) = (int8_t)r;
+      pk_soft_bit<ATAB>(soft, adrB[j]) = (int8_t)(r >> 16);
     }
     cprev = c;
   }
@@ -292,20 +356,23 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
 //    soft bits are not an output -- hard bits, CRC verdict and iteration count are.
 // So: the soft bits of the other D - 1 edges are read, one packed minimum of |s| and the sign parity are accumulated, the value goes to
 // edge ZE's soft bits and byte slots of the layer's message dwords (layout of update_rows_pk, zeros elsewhere); no other soft bit is stored.
-template <int D, int ZE, bool FOLD>
+template <int D, int ZE, bool FOLD, bool ATAB = false>
 __device__ __forceinline__ void update_rows_pk_zero(int8_t* __restrict__ soft, uint32_t* __restrict__ c2v, const uint32_t* __restrict__ edges, int l, int H, int Z,
-                                                    uint32_t base = 0)
+                                                    uint32_t base = 0, pk_adr_quad* aq = nullptr, pk_adr_row anext = pk_adr_row(), uint32_t avoff = 0, uint32_t astride = 0)
 {
   static_assert((ZE == 0 || ZE == 1) && D > 2, "the known-zero edge is edge 0 or 1 of its row, and other edges exist");
   uint32_t adrA[D], adrB[D];
   int      rawA[D], rawB[D];
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO);
-  pk_edge_addresses<D, FOLD>(adrA, adrB, edges, l, H, Z, base);
+  if constexpr (ATAB)
+    pk_table_addresses<D>(adrA, adrB, aq);
+  else
+    pk_edge_addresses<D, FOLD>(adrA, adrB, edges, l, H, Z, base);
 #pragma unroll
   for (int j = 0; j < D; ++j) {
     if (j != ZE) {
-      rawA[j] = soft[adrA[j]];
-      rawB[j] = soft[adrB[j]];
+      rawA[j] = pk_soft_bit<ATAB>(soft, adrA[j]);
+      rawB[j] = pk_soft_bit<ATAB>(soft, adrB[j]);
     }
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -322,6 +389,8 @@ __device__ __forceinline__ void update_rows_pk_zero(int8_t* __restrict__ soft, u
     }
   }
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO2);
+  if constexpr (ATAB)
+    pk_table_request<D>(aq, anext, avoff, astride);
   const uint32_t sA = ((uint32_t)(uint16_t)mag.x * 52428u) >> 16, sB = ((uint32_t)(uint16_t)mag.y * 52428u) >> 16;
   const s16x2    pm = pk_ashr15(as_s2(spx));
   const s16x2    c  = as_s2((sA | (sB << 16)) ^ as_u(pm)) - pm; // |c| <= 96: no clamp
@@ -330,8 +399,8 @@ __device__ __forceinline__ void update_rows_pk_zero(int8_t* __restrict__ soft, u
 #pragma unroll
   for (int jj = 1; jj < (D + 1) / 2; ++jj)
     c2v[64 * jj] = 0u; // (an odd degree's last dword holds its last edge twice: zero either way)
-  soft[adrA[ZE]] = (int8_t)r;
-  soft[adrB[ZE]] = (int8_t)(r >> 16);
+  pk_soft_bit<ATAB>(soft, adrA[ZE]) = (int8_t)r;
+  pk_soft_bit<ATAB>(soft, adrB[ZE]) = (int8_t)(r >> 16);
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO1);
 }
 
@@ -459,6 +528,20 @@ __device__ __forceinline__ void update_rows_pk_visit(int it, int m, int d, int8_
     update_rows_pk_any<true, FOLD>(d, soft, c2v, edges, l, H, Z, base);
   else
     update_rows_pk_any<false, FOLD>(d, soft, c2v, edges, l, H, Z, base);
+}
+
+// The same visit of an ATAB instance: every layer the launch can reach has degree D (the launch planner sees to that).
+template <int D>
+__device__ __forceinline__ void update_rows_pk_visit_tab(int it, int m, int8_t* soft, uint32_t* c2v, pk_adr_quad* aq, pk_adr_row anext, uint32_t avoff, uint32_t astride)
+{
+  if (it == 0 && m == 1)
+    update_rows_pk_zero<D, 0, true, true>(soft, c2v, nullptr, 0, 0, 0, 0, aq, anext, avoff, astride);
+  else if (it == 0 && m == 2)
+    update_rows_pk_zero<D, 1, true, true>(soft, c2v, nullptr, 0, 0, 0, 0, aq, anext, avoff, astride);
+  else if (it == 0 || (it == 1 && m == 0))
+    update_rows_pk<D, true, 1, pk_no_hook, true, true>(soft, c2v, nullptr, 0, 0, 0, 0, true, nullptr, 0, 0, pk_no_hook(), aq, anext, avoff, astride);
+  else
+    update_rows_pk<D, false, 1, pk_no_hook, true, true>(soft, c2v, nullptr, 0, 0, 0, 0, true, nullptr, 0, 0, pk_no_hook(), aq, anext, avoff, astride);
 }
 
 __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b, uint32_t poly, uint32_t order)

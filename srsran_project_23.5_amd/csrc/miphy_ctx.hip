@@ -161,6 +161,68 @@ static void build_tables(miphy_graph_tables* t)
   }
 }
 
+// The arithmetic of pk_edge_addresses<D, true> (ldpc_pk_device.h) with base = 0, for every lane, layer and edge.
+extern "C" int miphy_ldpc_address_table(int bg, int Z, int layers, uint32_t* out)
+{
+  MIPHY_REQUIRE(bg == 1 || bg == 2, "miphy_ldpc_address_table: invalid base graph %d", bg);
+  MIPHY_REQUIRE(Z >= 2 && Z <= MIPHY_MAX_Z && lifting_set(Z) >= 0, "miphy_ldpc_address_table: invalid lifting size %d", Z);
+  MIPHY_REQUIRE(layers >= 1 && layers <= (bg == 1 ? NR_LDPC_BG1_M : NR_LDPC_BG2_M), "miphy_ldpc_address_table: invalid number of layers %d", layers);
+  const uint16_t* row_start = bg == 1 ? NR_LDPC_BG1_ROW_START : NR_LDPC_BG2_ROW_START;
+  const uint8_t*  col       = bg == 1 ? NR_LDPC_BG1_COL : NR_LDPC_BG2_COL;
+  const int       ils = lifting_set(Z), H = (Z + 1) / 2, lanes = 64 * ((H + 63) / 64);
+  size_t          quad = 0;
+  for (int m = 0; m < layers; ++m) {
+    const int e0 = row_start[m], d = row_start[m + 1] - e0, nq = (d + 3) / 4;
+    if (out) {
+      for (int j = 0; j < 4 * nq; ++j) {
+        const int      e  = e0 + std::min(j, d - 1); // a pad entry repeats the last edge
+        const uint32_t sh = (uint32_t)((bg == 1 ? NR_LDPC_BG1_SHIFT[ils][e] : NR_LDPC_BG2_SHIFT[ils][e]) % Z), co = (uint32_t)col[e] * Z;
+        for (int l = 0; l < lanes; ++l) {
+          uint32_t w = 0;
+          if (l < H) {
+            const uint16_t Hv = (l + H < Z) ? (uint16_t)H : 0; // odd Z: the last lane's second row is its first
+            const uint16_t tA = (uint16_t)(l + sh), tB = (uint16_t)(l + Hv + sh);
+            const uint16_t rA = std::min<uint16_t>(tA, (uint16_t)(tA - Z)), rB = std::min<uint16_t>(tB, (uint16_t)(tB - Z));
+            w                 = ((uint32_t)rA + co) | (((uint32_t)rB + co) << 16);
+          }
+          out[((quad + j / 4) * lanes + l) * 4 + j % 4] = w;
+        }
+      }
+    }
+    quad += nq;
+  }
+  return (int)(quad * lanes * 4);
+}
+
+int miphy_ldpc_address_tables(miphy_ctx* ctx, int bgi, int lay, int min_Z, int max_Z, const void** out)
+{
+  constexpr int    NZ = MIPHY_MAX_Z / 16 + 1;
+  ldpc_adr_tables& T  = ctx->ext->ldpc_adr[{bgi, lay}];
+  if (!T.d_ptr) {
+    MIPHY_HIP_CHECK(hipMalloc((void**)&T.d_ptr, NZ * sizeof(void*)));
+    ctx->ext->to_free.push_back(T.d_ptr);
+    MIPHY_HIP_CHECK(hipMemset(T.d_ptr, 0, NZ * sizeof(void*)));
+  }
+  for (int Z = min_Z; Z <= max_Z; ++Z) {
+    if (ctx->h_tables->z_pos[Z] == 0xffff || T.h_ptr[Z / 16])
+      continue;
+    MIPHY_REQUIRE(Z % 16 == 0, "ldpc address tables: lifting size %d has no table index of its own", Z); // (every size from 128 on has)
+    const int words = miphy_ldpc_address_table(bgi + 1, Z, lay, nullptr);
+    if (words < 0)
+      return words;
+    std::vector<uint32_t> h((size_t)words);
+    (void)miphy_ldpc_address_table(bgi + 1, Z, lay, h.data());
+    void* d = nullptr;
+    MIPHY_HIP_CHECK(hipMalloc(&d, h.size() * 4));
+    ctx->ext->to_free.push_back(d);
+    MIPHY_HIP_CHECK(hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    MIPHY_HIP_CHECK(hipMemcpy(T.d_ptr + Z / 16, &d, sizeof(void*), hipMemcpyHostToDevice)); // (an entry no launch in flight reads: its key was not held)
+    T.h_ptr[Z / 16] = d;
+  }
+  *out = T.d_ptr;
+  return MIPHY_OK;
+}
+
 extern "C" int miphy_create(int device, miphy_ctx** out)
 {
   if (!out) {

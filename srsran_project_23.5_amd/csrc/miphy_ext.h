@@ -37,7 +37,14 @@ struct uci_polar_host_code {
 };
 enum { UCI_POLAR_HOST_CACHE_ENTRIES = 128 };
 
+// Soft-bit address tables of the LDPC decoder (miphy_ldpc_address_tables) of one (base graph, layers): device pointers by Z / 16.
+struct ldpc_adr_tables {
+  const void* h_ptr[MIPHY_MAX_Z / 16 + 1] = {}; // host copy of the device array d_ptr
+  void**      d_ptr                       = nullptr;
+};
+
 struct miphy_ctx_ext {
+  std::map<std::pair<int, int>, ldpc_adr_tables> ldpc_adr; // (base graph - 1, layers) -> tables; freed with to_free
   std::vector<uci_polar_host_code> uci_polar_codes;
   uint64_t                         uci_polar_clock = 0;
   std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, polar_plan> polar_plans;

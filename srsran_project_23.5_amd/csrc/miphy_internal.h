@@ -139,7 +139,7 @@ struct miphy_ldpc_class {
   uint8_t  bgi;   // base graph - 1
   uint8_t  fused; // every codeblock can be rate-dematched by the decoder while it loads
   uint8_t  lay;   // layers a codeblock of the class can reach at most
-  uint16_t max_Z;
+  uint16_t max_Z, min_Z;
   uint32_t first, count;               // the class's range of `order`
   uint32_t bundle_first, bundle_count; // kind 0: its range of `bundles` (pairs of words)
   uint32_t soft_total;                 // kind 0: LDS bytes for the soft bits of a bundle
@@ -166,6 +166,8 @@ struct miphy_ldpc_launch {
   size_t           lds;
   uint32_t         grid;
   bool             ordered;    // decodes order[c.first ...] (false: the codeblocks in array order)
+  bool             atab;       // packed kernel: the instance that reads its soft-bit addresses from a table (ldpc_pk_device.h, pk_table_addresses)
+  const void*      adr_by_z;   // ... device array of the tables of the class, at [Z / 16] (miphy_ldpc_address_tables; owned by the context)
   size_t           gmsg_off, gmsg_bytes; // the launch's part of the message scratch
 };
 struct miphy_ldpc_launches {
@@ -174,6 +176,7 @@ struct miphy_ldpc_launches {
   bool                           side_streams = false; // launches fork to the context's side streams (miphy_side_streams first)
   bool                           scalar       = false; // the one-row-per-lane kernel is forced: nothing is dematched in the decoder
 };
+#define MIPHY_LDPC_ADR_TABLE_DEGREE 19 // edges per layer of the classes that read their soft-bit addresses from a table (PK_ATAB_DEGREE of ldpc_decode_pk.hip)
 // Modes of miphy_debug_force_ldpc_kernel (include/miphy.h): a mode in the low byte, plus flag bits.
 enum miphy_ldpc_force_mode {
   MIPHY_LDPC_FORCE_AUTO        = 0,
@@ -184,12 +187,18 @@ enum miphy_ldpc_force_mode {
   MIPHY_LDPC_FORCE_LATENCY_ALL = 5, // class-sorted, the latency form in two parts on every packed class
   MIPHY_LDPC_FORCE_LATENCY2    = 6, // AUTO with the latency form in two parts instead of four
   MIPHY_LDPC_FORCE_MODE_MASK   = 0xff,
-  MIPHY_LDPC_FORCE_ALL_GMSG    = 0x100 // flag: a GMSG launch keeps ALL its messages in global memory
+  MIPHY_LDPC_FORCE_ALL_GMSG    = 0x100, // flag: a GMSG launch keeps ALL its messages in global memory
+  MIPHY_LDPC_FORCE_NO_ADR_TABLE = 0x200 // flag: no launch reads its soft-bit addresses from a table (every class computes them)
 };
 // Host only: the launch table of the classes C (their order / bundles are device arrays by then). fuse: the fused classes dematch while
 // they load (the caller then passes rate-dematcher descriptors to the run). The debug knobs of miphy_debug_force_ldpc_kernel and
 // miphy_debug_set_ldpc_class_streams are read when a table is made -- one snapshot per table -- and nowhere else.
-void miphy_ldpc_plan_launches(const miphy_ctx* ctx, const miphy_ldpc_classes& C, bool fuse, miphy_ldpc_launches& T);
+// A launch that takes the address-table instance gets the tables of its class from the context's cache (built on first use).
+int miphy_ldpc_plan_launches(miphy_ctx* ctx, const miphy_ldpc_classes& C, bool fuse, miphy_ldpc_launches& T);
+// The soft-bit address tables of the lifting sizes min_Z ... max_Z (multiples of 16) of base graph bgi + 1 with `lay` layers, on the
+// device: *out = device array of table pointers indexed by Z / 16. Built once per (base graph, Z, layers) and kept until miphy_destroy,
+// so that launch tables and prepared plans may hold the pointer; a key the cache holds is never rebuilt.
+int miphy_ldpc_address_tables(miphy_ctx* ctx, int bgi, int lay, int min_Z, int max_Z, const void** out);
 // Enqueues the table on `s`: the fork to the side streams (created by then), one launch per class, the join -- on every path after the
 // fork. d_order / d_bundles = device copies of C.order / C.bundles; gmsg = T.gmsg_bytes of message scratch; d_rdm / rm_in: rate-dematcher
 // descriptors (same index as d_descs) and rate-matched input of the fused classes.

@@ -475,16 +475,19 @@ int build_pusch_decode(const miphy_pusch_tb_desc* tbs, uint32_t n, pusch_decode_
 
 // The decoder's launch tables of every chunk: without dematching in the decoder and, where a class can, with it (a run chooses by the
 // alignment of the soft buffers it is given).
-void pusch_decode_launches(const miphy_ctx* ctx, pusch_decode_build& b)
+int pusch_decode_launches(miphy_ctx* ctx, pusch_decode_build& b)
 {
   for (pusch_decode_build::chunk& ch : b.chunks)
     for (int f = 0; f < (b.any_fused ? 2 : 1); ++f) {
-      miphy_ldpc_launches& T = ch.launches[f];
-      miphy_ldpc_plan_launches(ctx, ch.cls, f == 1, T);
+      miphy_ldpc_launches& T  = ch.launches[f];
+      const int            rc = miphy_ldpc_plan_launches(ctx, ch.cls, f == 1, T);
+      if (rc)
+        return rc;
       b.scalar       = T.scalar;
       b.side_streams = b.side_streams || T.side_streams;
       b.gmsg_bytes   = std::max(b.gmsg_bytes, T.gmsg_bytes);
     }
+  return MIPHY_OK;
 }
 
 size_t pusch_decode_bytes(const pusch_decode_build& b)
@@ -610,7 +613,8 @@ extern "C" int miphy_pusch_decode_batch(miphy_ctx*                 ctx,
   const pusch_decode_dev v = layout_pusch_decode(b, host.data(), (uint8_t*)wsv);
   if ((rc = miphy_upload(ctx, wsv, host.data(), v.staged, s))) // through the pinned ring: the stream is not waited for
     return rc;
-  pusch_decode_launches(ctx, b);
+  if ((rc = pusch_decode_launches(ctx, b)))
+    return rc;
   void* gmsg = nullptr;
   if (b.gmsg_bytes && (rc = miphy_get_workspace(ctx, MIPHY_WS_LDPC_MSGS, b.gmsg_bytes, &gmsg)))
     return rc;
@@ -644,8 +648,7 @@ extern "C" int miphy_pusch_decode_plan_create(miphy_ctx* ctx, const miphy_pusch_
     delete p;
     return rc;
   }
-  pusch_decode_launches(ctx, p->b);
-  if (p->b.side_streams && (rc = miphy_side_streams(ctx))) {
+  if ((rc = pusch_decode_launches(ctx, p->b)) || (p->b.side_streams && (rc = miphy_side_streams(ctx)))) {
     delete p;
     return rc;
   }

@@ -74,6 +74,10 @@ def lib():
         l.miphy_ldpc_decode_plan_destroy.restype = None
         l.miphy_debug_ldpc_kernels_used.argtypes = [C.c_int]
         l.miphy_debug_ldpc_kernels_used.restype = C.c_uint32
+        if hasattr(l, "miphy_ldpc_address_table"):  # (an older build named by MIPHY_LIBRARY for an A-B has neither)
+            l.miphy_ldpc_address_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+            l.miphy_debug_ldpc_address_table_launches.argtypes = [C.c_int]
+            l.miphy_debug_ldpc_address_table_launches.restype = C.c_uint32
         l.miphy_polar_decode_list_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.miphy_pbch_encode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]

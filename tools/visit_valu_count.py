@@ -6,7 +6,8 @@ A visit (update_rows_pk, update_rows_pk_zero) is the code from its `s_setprio <r
 tails of the instances of a switch; every instance of a kernel is inlined once, so the static
 count of a region is the count a wavefront issues per visit (the stores of the latency form's idle lanes sit under a branch and are
 counted as issued). Per kernel: registers, scratch bytes, scratch accesses inside visits; per visit: soft-bit reads (= 2 x edges of the
-instance), message reads (0 = a first-visit instance), VALU per phase (lane reads and writes, which carry spilled scalar registers, are VALU
+instance), message reads (0 = a first-visit instance), address-table loads (the instance that reads its soft-bit addresses: the quads of the
+next visit, requested in the second phase; their split is counted where the compiler puts it, the request phase), VALU per phase (lane reads and writes, which carry spilled scalar registers, are VALU
 instructions and are also shown on their own)."""
 import re, sys
 
@@ -24,7 +25,7 @@ def visits(lines):
         if m:
             p = int(m.group(1))
             if p == REQ:
-                cur, phase = {"valu": [0, 0, 0], "soft_rd": 0, "msg_rd": 0, "scratch": 0, "lane_rd": 0, "sdwa_add": 0, "pk_add": 0, "pk_mul": 0, "mul24": 0}, 0
+                cur, phase = {"valu": [0, 0, 0], "soft_rd": 0, "msg_rd": 0, "scratch": 0, "lane_rd": 0, "tab_rd": 0, "sdwa_add": 0, "pk_add": 0, "pk_mul": 0, "mul24": 0}, 0
             elif cur is not None and p == PH1 and phase == 0:
                 phase = 1
             elif cur is not None and p == PH2:
@@ -42,6 +43,7 @@ def visits(lines):
         cur["soft_rd"] += op in ("ds_read_i8", "ds_read_u8")
         cur["msg_rd"] += op in ("ds_read_b32", "ds_read2_b32", "ds_read2st64_b32", "global_load_dword")
         cur["scratch"] += op.startswith("scratch_")
+        cur["tab_rd"] += op.startswith("buffer_load_dwordx")
         cur["sdwa_add"] += op == "v_add_u32_sdwa"
         cur["pk_add"] += op == "v_pk_add_u16"
         cur["pk_mul"] += op == "v_pk_mul_lo_u16"
@@ -59,8 +61,8 @@ def main(path):
         vs = visits(body)
         print("%s  vgpr %s scratch %s B  visits %d  scratch accesses in visits %d" % (name[len("_ZN12_GLOBAL__N_121"):][:40], vg, scr, len(vs), sum(v["scratch"] for v in vs)))
         for v in vs:
-            print("   edges %2d msg_rd %2d | VALU %3d = %3d + %3d + %3d | sdwa_add %2d pk_add_u16 %2d pk_mul %d mul24 %d scratch %d lane_rd %d" % (
-                v["soft_rd"] // 2, v["msg_rd"], sum(v["valu"]), *v["valu"], v["sdwa_add"], v["pk_add"], v["pk_mul"], v["mul24"], v["scratch"], v["lane_rd"]))
+            print("   edges %2d msg_rd %2d | VALU %3d = %3d + %3d + %3d | sdwa_add %2d pk_add_u16 %2d pk_mul %d mul24 %d scratch %d lane_rd %d tab_rd %d" % (
+                v["soft_rd"] // 2, v["msg_rd"], sum(v["valu"]), *v["valu"], v["sdwa_add"], v["pk_add"], v["pk_mul"], v["mul24"], v["scratch"], v["lane_rd"], v["tab_rd"]))
 
 
 if __name__ == "__main__":
