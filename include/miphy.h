@@ -865,7 +865,7 @@ typedef struct {
   uint8_t  initial_cyclic_shift; /* format 1: 0..11 */
   uint8_t  time_domain_occ;      /* format 1: 0..6 */
   uint8_t  nof_harq_ack;         /* format 1: 0..2 */
-  uint8_t  nof_sr, nof_csi_part1, nof_csi_part2; /* format 2: 3..11 bits in all, CSI part 2 must be 0 */
+  uint8_t  nof_sr, nof_csi_part1, nof_csi_part2; /* format 2: 3..11 bits in all (_ex: 3 and more), CSI part 2 must be 0 */
   uint8_t  reserved0;
   uint16_t n_id;                 /* format 1: 0..1023 (group u = n_id mod 30, v = 0, cyclic-shift hopping c_init); format 2: scrambling */
   uint16_t n_id_0;               /* format 2: DM-RS scrambling identity */
@@ -887,6 +887,27 @@ typedef struct {
 int miphy_pucch_process_batch(miphy_ctx* ctx, const miphy_pucch_job* jobs, int jobs_on_device, uint32_t n, const float* grid /* device cf_t */,
                               uint8_t* payload /* device */, miphy_pucch_result* results /* device, n */, int8_t* llr_out /* device or NULL */,
                               void* stream);
+/* Format 2 above 11 bits  --  beyond the 23.5 reference, whose processor asserts on such a PDU (pucch_processor_impl.cpp:282-287) and
+ * whose uci_decoder stops at 11 bits. A batch may mix format-1 PDUs, format-2 PDUs of 3..11 bits and format-2 PDUs of K = nof_harq_ack
+ * + nof_sr + nof_csi_part1 >= 12 bits ("long"); jobs and results keep their layout. For format-1 and short format-2 PDUs payload, record
+ * and soft bits are those of miphy_pucch_process_batch byte for byte, whatever list_size is. For a long PDU estimation, channel state
+ * information, equalisation, demapping and descrambling are the same kernel's (the soft bits do not depend on K); its E = 16 nof_prb
+ * nof_symbols soft bits are then decoded as ONE polar-coded UCI field of A = K bits exactly as miphy_uci_polar_decode_list_batch
+ * decodes it (E <= 512, so always one segment): `payload` gets the K decoded bits, one per byte, in the order HARQ-ACK, SR, CSI part 1,
+ * whatever the verdict; results[i].status is MIPHY_UCI_STATUS_VALID or _INVALID from the CRC; detection_metric is 0. list_size 1 is
+ * the SSC kernel; 2 / 4 / 8 the list kernel from 20 bits, while 12..19 bits stay with the SSC kernel at every list size.
+ * The call enqueues the PUCCH kernel once for all n PDUs and the polar decoder behind it on the same stream, which stores its verdict
+ * over the status byte the kernel wrote; nothing waits for the device. Without `llr_out` the soft bits of the long PDUs pass through
+ * a workspace of the context (512 bytes per long PDU); payload and status are the same either way.
+ * Jobs are HOST memory only (the polar codes are constructed on the host; no stream capture). Every job is checked before anything is
+ * enqueued; MIPHY_EINVAL with the rule in miphy_last_error() and nothing written for: list_size not 1, 2, 4 or 8; a null argument; a
+ * job miphy_pucch_process_batch refuses for another reason than its bit count above 11; nof_csi_part2 != 0; a long PDU whose (K, E)
+ * miphy_uci_polar_info refuses (12 bits on 16 soft bits, 21 on 32, 501 on 512). n == 0 enqueues nothing. (A HIP or staging failure
+ * behind the PUCCH kernel, MIPHY_EHIP, leaves that kernel enqueued, as between two pieces of miphy_uci_polar_decode_batch.) The code
+ * rate limit of the reference's validator (0.8) is not a rule here: pucch_pdu_validator_hip applies it. */
+int miphy_pucch_process_batch_ex(miphy_ctx* ctx, const miphy_pucch_job* jobs /* HOST */, uint32_t n, uint32_t list_size,
+                                 const float* grid /* device cf_t */, uint8_t* payload /* device */, miphy_pucch_result* results /* device, n */,
+                                 int8_t* llr_out /* device or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * PRACH detector and generator  --  replace srsran::prach_detector::detect and srsran::prach_generator::generate

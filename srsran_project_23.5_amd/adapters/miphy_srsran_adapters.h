@@ -1031,8 +1031,10 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------- PUCCH processor
-/// srsran::pucch_processor over miphy_pucch_process_batch (pucch_processor.h:160-193, pucch_processor_impl.cpp:28-189): formats 1 and 2
-/// on the device, one PDU per call or a whole slot through process_batch(). A single PDU copies only its PRB window of the grid (all 14
+/// srsran::pucch_processor over miphy_pucch_process_batch_ex (pucch_processor.h:160-193, pucch_processor_impl.cpp:28-189): formats 1 and 2
+/// on the device, one PDU per call or a whole slot through process_batch(). A format-2 configuration above 11 bits, on which the
+/// reference asserts, is decoded on the device as one polar-coded UCI field (\c list_size 1, the default, is the SSC decoder, 2 / 4 / 8
+/// decode payloads of 20 bits and more with the CRC-aided list decoder) and fills the pucch_uci_message like a short payload does. A single PDU copies only its PRB window of the grid (all 14
 /// symbols of its ports) into the device staging buffer; the batch copies the grid once. Formats 0, 3 and 4 go to the CPU processor
 /// given at construction; without one they behave as the reference (format 0 asserts, formats 3 and 4 return an empty result).
 /// Receive ports: the staging grid holds config.ports in order, so the device reads the listed ports. The reference's estimator reads
@@ -1048,10 +1050,12 @@ public:
   using format3_configuration = srsran::pucch_processor::format3_configuration;
   using format4_configuration = srsran::pucch_processor::format4_configuration;
 
-  explicit pucch_processor_hip(std::shared_ptr<context> c, std::unique_ptr<srsran::pucch_processor> cpu_ = nullptr) :
-    c(std::move(c)), cpu(std::move(cpu_))
+  explicit pucch_processor_hip(std::shared_ptr<context> c, std::unique_ptr<srsran::pucch_processor> cpu_ = nullptr, unsigned list_size_ = 1) :
+    c(std::move(c)), cpu(std::move(cpu_)), list_size(list_size_)
   {
+    require(list_size == 1 || list_size == 2 || list_size == 4 || list_size == 8, "The UCI list size must be 1, 2, 4 or 8.");
   }
+  unsigned get_list_size() const { return list_size; }
 
   srsran::pucch_processor_result process(const srsran::resource_grid_reader& grid, const format0_configuration& config) override
   {
@@ -1106,7 +1110,6 @@ public:
     auto add = [&](miphy_pucch_job j, const srsran::static_vector<uint8_t, srsran::MAX_PORTS>& ports) {
       require(identity_ports(ports), "pucch_processor_hip::process_batch: receive ports must be 0, 1, ... in order.");
       nports = std::max<unsigned>(nports, j.nof_ports), nprb = std::max<unsigned>(nprb, j.grid_nprb);
-      j.payload_offset = 11 * jobs.size();
       jobs.push_back(j);
     };
     for (const auto& cfg : f1) {
@@ -1197,18 +1200,25 @@ private:
                  "h2d window");
     std::vector<miphy_pucch_job> jobs{j};
     const uint8_t* h = run(jobs, reinterpret_cast<float*>(d_g));
-    unpack(h, 0, j, r);
+    unpack(h, 0, jobs[0], r);
   }
 
-  /// Launches the jobs on the staged grid and downloads results and payloads: returns the host copy, results first, then 11 payload
-  /// bytes per job.
-  const uint8_t* run(const std::vector<miphy_pucch_job>& jobs, const float* d_g)
+  /// Launches the jobs on the staged grid and downloads results and payloads: returns the host copy, results first, then the payload
+  /// bytes of the jobs one after the other from the payload_offset this function gives each job.
+  const uint8_t* run(std::vector<miphy_pucch_job>& jobs, const float* d_g)
   {
-    const size_t n = jobs.size(), res_bytes = n * sizeof(miphy_pucch_result), bytes = res_bytes + 11 * n;
-    auto*        d  = static_cast<uint8_t*>(c->buf(7, bytes));
-    context::check(miphy_pucch_process_batch(c->ctx, jobs.data(), 0, static_cast<uint32_t>(n), d_g, d + res_bytes,
-                                             reinterpret_cast<miphy_pucch_result*>(d), nullptr, c->stream),
+    const size_t n = jobs.size(), res_bytes = n * sizeof(miphy_pucch_result);
+    size_t       pay_bytes = 0;
+    for (auto& j : jobs) {
+      j.payload_offset = pay_bytes;
+      pay_bytes += j.format == 2 ? static_cast<size_t>(j.nof_harq_ack) + j.nof_sr + j.nof_csi_part1 : j.nof_harq_ack;
+    }
+    const size_t bytes = res_bytes + pay_bytes;
+    auto*        d     = static_cast<uint8_t*>(c->buf(7, bytes));
+    context::check(miphy_pucch_process_batch_ex(c->ctx, jobs.data(), static_cast<uint32_t>(n), list_size, d_g, d + res_bytes,
+                                                reinterpret_cast<miphy_pucch_result*>(d), nullptr, c->stream),
                    "pucch_process");
+    nof_run = n;
     down.resize(bytes);
     c->d2h(down.data(), d, bytes);
     c->sync();
@@ -1227,7 +1237,6 @@ private:
   /// pucch_processor_result of job i (pucch_processor_impl.cpp:95-100 and 167-186).
   void unpack(const uint8_t* h, size_t i, const miphy_pucch_job& j, srsran::pucch_processor_result& r) const
   {
-    const size_t       n = down.size() / (sizeof(miphy_pucch_result) + 11);
     miphy_pucch_result res;
     std::memcpy(&res, h + i * sizeof(miphy_pucch_result), sizeof(res));
     srsran::pucch_uci_message::configuration mc = {};
@@ -1237,7 +1246,7 @@ private:
     }
     r.message                   = srsran::pucch_uci_message(mc);
     srsran::span<uint8_t> bits  = r.message.get_full_payload();
-    const uint8_t*        pay   = h + n * sizeof(miphy_pucch_result) + 11 * i;
+    const uint8_t*        pay   = h + nof_run * sizeof(miphy_pucch_result) + j.payload_offset;
     std::copy(pay, pay + bits.size(), bits.begin());
     r.message.set_status(res.status == MIPHY_UCI_STATUS_VALID     ? srsran::uci_status::valid
                          : res.status == MIPHY_UCI_STATUS_INVALID ? srsran::uci_status::invalid
@@ -1255,16 +1264,23 @@ private:
 
   std::shared_ptr<context>                 c;
   std::unique_ptr<srsran::pucch_processor> cpu;
+  unsigned                                 list_size;
+  size_t                                   nof_run = 0; // jobs of the last run(): the payloads follow that many result records
   std::vector<srsran::cf_t>                host;
   std::vector<uint8_t>                     down;
 };
 
 /// srsran::pucch_pdu_validator with the reference's rules (pucch_processor_impl.cpp:287-380) for the maximum channel-estimate
-/// dimensions the processor is built for. Formats 0, 3 and 4 are accepted, as the reference does.
+/// dimensions the processor is built for. Formats 0, 3 and 4 are accepted, as the reference does. \c long_payloads (off by default, the
+/// reference's behaviour) lets format 2 above 11 bits through where pucch_processor_hip decodes it: no CSI part 2, the reference's
+/// code-rate rule on the payload bits, and a payload the polar framing takes in the allocation's 16 nof_prb nof_symbols soft bits.
 class pucch_pdu_validator_hip : public srsran::pucch_pdu_validator
 {
 public:
-  explicit pucch_pdu_validator_hip(const srsran::channel_estimate::channel_estimate_dimensions& dims_) : dims(dims_) {}
+  explicit pucch_pdu_validator_hip(const srsran::channel_estimate::channel_estimate_dimensions& dims_, bool long_payloads_ = false) :
+    dims(dims_), long_payloads(long_payloads_)
+  {
+  }
   bool is_valid(const srsran::pucch_processor::format0_configuration&) const override { return true; }
   bool is_valid(const srsran::pucch_processor::format1_configuration& config) const override
   {
@@ -1291,7 +1307,14 @@ public:
     if (srsran::pucch_format2_code_rate(config.nof_prb, config.nof_symbols, nof_uci_bits) > srsran::pucch_constants::MAX_CODE_RATE) {
       return false;
     }
-    return nof_uci_bits >= srsran::pucch_constants::FORMAT2_MIN_UCI_NBITS && nof_uci_bits <= 11;
+    if (nof_uci_bits < srsran::pucch_constants::FORMAT2_MIN_UCI_NBITS) {
+      return false;
+    }
+    if (nof_uci_bits <= 11) {
+      return true;
+    }
+    miphy_uci_polar_info_t info;
+    return long_payloads && miphy_uci_polar_info(nof_uci_bits, 16 * config.nof_prb * config.nof_symbols, &info) == MIPHY_OK;
   }
   bool is_valid(const srsran::pucch_processor::format3_configuration&) const override { return true; }
   bool is_valid(const srsran::pucch_processor::format4_configuration&) const override { return true; }
@@ -1304,35 +1327,44 @@ private:
   bool ports_ok(size_t nports) const { return nports != 0 && nports <= dims.nof_rx_ports; }
 
   srsran::channel_estimate::channel_estimate_dimensions dims;
+  bool                                                  long_payloads;
 };
 
 /// srsran::pucch_processor_factory handing out pucch_processor_hip on one context; \c cpu_factory (may be null) provides the CPU
-/// processor for formats 0, 3 and 4.
+/// processor for formats 0, 3 and 4. \c list_size goes to the processors, \c long_payloads to the validators.
 class pucch_processor_factory_hip : public srsran::pucch_processor_factory
 {
 public:
   pucch_processor_factory_hip(std::shared_ptr<context> c_, const srsran::channel_estimate::channel_estimate_dimensions& dims_,
-                              std::shared_ptr<srsran::pucch_processor_factory> cpu_factory_ = nullptr) :
-    c(std::move(c_)), dims(dims_), cpu_factory(std::move(cpu_factory_))
+                              std::shared_ptr<srsran::pucch_processor_factory> cpu_factory_ = nullptr, unsigned list_size_ = 1,
+                              bool long_payloads_ = false) :
+    c(std::move(c_)), dims(dims_), cpu_factory(std::move(cpu_factory_)), list_size(list_size_), long_payloads(long_payloads_)
   {
+    require(list_size == 1 || list_size == 2 || list_size == 4 || list_size == 8, "The UCI list size must be 1, 2, 4 or 8.");
   }
   std::unique_ptr<srsran::pucch_processor> create() override
   {
-    return std::make_unique<pucch_processor_hip>(c, cpu_factory ? cpu_factory->create() : nullptr);
+    return std::make_unique<pucch_processor_hip>(c, cpu_factory ? cpu_factory->create() : nullptr, list_size);
   }
-  std::unique_ptr<srsran::pucch_pdu_validator> create_validator() override { return std::make_unique<pucch_pdu_validator_hip>(dims); }
+  std::unique_ptr<srsran::pucch_pdu_validator> create_validator() override
+  {
+    return std::make_unique<pucch_pdu_validator_hip>(dims, long_payloads);
+  }
 
 private:
   std::shared_ptr<context>                         c;
   srsran::channel_estimate::channel_estimate_dimensions dims;
   std::shared_ptr<srsran::pucch_processor_factory> cpu_factory;
+  unsigned                                         list_size;
+  bool                                             long_payloads;
 };
 
 inline std::shared_ptr<srsran::pucch_processor_factory>
 create_pucch_processor_factory_hip(std::shared_ptr<context> c, const srsran::channel_estimate::channel_estimate_dimensions& dims,
-                                   std::shared_ptr<srsran::pucch_processor_factory> cpu_factory = nullptr)
+                                   std::shared_ptr<srsran::pucch_processor_factory> cpu_factory = nullptr, unsigned list_size = 1,
+                                   bool long_payloads = false)
 {
-  return std::make_shared<pucch_processor_factory_hip>(std::move(c), dims, std::move(cpu_factory));
+  return std::make_shared<pucch_processor_factory_hip>(std::move(c), dims, std::move(cpu_factory), list_size, long_payloads);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- PRACH

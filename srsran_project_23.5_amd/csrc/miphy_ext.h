@@ -60,6 +60,11 @@ struct miphy_ctx_ext {
 // Returns the device twiddle table for size N (creates and caches it).
 int miphy_get_twiddles(miphy_ctx* ctx, uint32_t N, const float** out);
 
+// miphy_uci_polar_decode_list_batch (uci_polar.hip) for a caller inside the library whose status bytes sit in records of its own: the
+// verdict of field i goes to status[status_index[i]] (status_index null: status[i]). `who` names the caller in the error messages.
+int miphy_uci_polar_decode_fields(const char* who, miphy_ctx* ctx, const miphy_uci_polar_job* jobs, uint32_t n, uint32_t list_size, const int8_t* llr,
+                                  uint8_t* payload, uint8_t* status, const uint32_t* status_index, hipStream_t s);
+
 // Prepared PDSCH encode (sch.hip): segmentation and descriptor upload once; used by the PDSCH processor plan (pdsch_proc.hip).
 struct miphy_pdsch_encode_prepared;
 int  miphy_pdsch_encode_prepare(miphy_ctx* ctx, const miphy_pdsch_tb_desc* tbs, uint32_t n, miphy_pdsch_encode_prepared** out);

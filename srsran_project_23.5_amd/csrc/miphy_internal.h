@@ -54,6 +54,7 @@ enum miphy_workspace {
   MIPHY_WS_OUTPUT,       // codewords of miphy_pdsch_process_batch, encoded PDCCH / PBCH bits, compacted results of miphy_pusch_process_batch
   MIPHY_WS_LDPC_MSGS,    // check-to-variable messages of the LDPC decoder when they do not stay in LDS (per-call entry points)
   MIPHY_WS_SEQUENCES,    // scrambling sequences of the PUSCH demodulator and of the PDSCH modulator (per-call entry point)
+  MIPHY_WS_PUCCH_LLR,    // soft bits of the long format-2 PDUs of miphy_pucch_process_batch_ex when the caller passes no llr_out
   MIPHY_NOF_WORKSPACES
 };
 

@@ -11,7 +11,10 @@
 //    data-symbol cyclic shifts, average, detect_bits, threshold 2.33, the SR-only rule);
 //  - format 2: pucch_demodulator_impl::demodulate (ZF 1xN with the noise variance of the first port, QPSK soft demapping with the
 //    quantisation of the PUSCH demodulator, descrambling with c_init = rnti 2^15 + n_id) into LDS, then the short-block detector of
-//    uci_device.h by the same wavefront.
+//    uci_device.h by the same wavefront;
+//  - format 2 above 11 bits (miphy_pucch_process_batch_ex only): the same chain up to the soft bits, which leave the kernel; the
+//    polar decoder of uci_polar.hip takes them as one UCI field per PDU behind the kernel on the same stream and stores its CRC
+//    verdict over the status byte of the PDU's record. The kernel holds no second copy of the polar recursion.
 // Time alignment: the reference takes the peak of |IDFT_4096| of the LS estimates inside +-HALF_CP taps. With at most 12 (format 1) or
 // 64 (format 2) pilots per hop, the 288 taps of the window are evaluated directly (a few per lane) instead of the whole transform;
 // the magnitude does not depend on where the pilots sit in the grid, so the pilots are placed from subcarrier 0 of the hop.
@@ -25,12 +28,16 @@
 #include "tables/nr_demod_tables.h"
 #include "tables/nr_low_papr_tables.h"
 #include "uci_device.h"
+#include "uci_polar_info.h"
 #include <cmath>
+#include <cstddef>
+#include <vector>
 
 // The reference's assertions for one PDU (pucch_processor_impl.cpp:191-285, pucch_detector_impl.cpp:155-186; the detector's w*
 // table asserts i < N for the data-symbol count N of every hop). Format 2's code rate (at most 11 bits over 16 nof_prb nof_symbols
-// >= 16 soft bits) never exceeds 0.8.
-__host__ __device__ static inline bool miphy_pucch_job_ok(const miphy_pucch_job& j)
+// >= 16 soft bits) never exceeds 0.8. long_ok: format 2 above 11 bits passes too (whether the polar framing takes its bits in its
+// soft bits is the host's check, uci_polar_frame).
+__host__ __device__ static inline bool miphy_pucch_job_ok(const miphy_pucch_job& j, bool long_ok = false)
 {
   if (j.nof_ports < 1 || j.nof_ports > 4 || j.numerology > 4 || j.slot >= (10u << j.numerology) || j.start_symbol + j.nof_symbols > 14)
     return false;
@@ -49,7 +56,7 @@ __host__ __device__ static inline bool miphy_pucch_job_ok(const miphy_pucch_job&
   if (j.format == 2) {
     const unsigned K = j.nof_harq_ack + j.nof_sr + j.nof_csi_part1;
     return j.nof_symbols >= 1 && j.nof_symbols <= 2 && j.nof_prb >= 1 && j.nof_prb <= 16 && j.starting_prb + j.nof_prb <= j.bwp_size_rb &&
-           !j.intra_slot_hopping && j.nof_csi_part2 == 0 && K >= 3 && K <= 11;
+           !j.intra_slot_hopping && j.nof_csi_part2 == 0 && K >= 3 && (K <= 11 || long_ok);
   }
   return false;
 }
@@ -184,7 +191,8 @@ struct f2_lds {
 
 __global__ void __launch_bounds__(64) pucch_kernel(const miphy_pucch_job* __restrict__ jobs, uint32_t n, const gold_tables* __restrict__ gt,
                                                    const float2* __restrict__ grid, uint8_t* __restrict__ payload,
-                                                   miphy_pucch_result* __restrict__ results, int8_t* __restrict__ llr_out)
+                                                   miphy_pucch_result* __restrict__ results, int8_t* __restrict__ llr_out,
+                                                   int8_t* __restrict__ llr_long)
 {
 #pragma clang fp contract(off)
   __shared__ union {
@@ -196,7 +204,9 @@ __global__ void __launch_bounds__(64) pucch_kernel(const miphy_pucch_job* __rest
   if (pdu >= n)
     return;
   const miphy_pucch_job j = jobs[pdu];
-  if (!miphy_pucch_job_ok(j)) // device jobs the host could not check: nothing is written
+  // Device jobs the host could not check: nothing is written. Format 2 above 11 bits passes only where the caller gave its soft bits
+  // a place (llr_long, miphy_pucch_process_batch_ex).
+  if (!miphy_pucch_job_ok(j, llr_long != nullptr))
     return;
   const int     nsc = 12 * (int)j.grid_nprb;
   const float2* g   = grid + j.grid_offset;
@@ -429,12 +439,15 @@ __global__ void __launch_bounds__(64) pucch_kernel(const miphy_pucch_job* __rest
       L.llr[2 * re + 1] = (int8_t)(((cw >> ((2 * re + 1) & 31)) & 1u) ? -l1 : l1);
     }
     __syncthreads();
-    if (llr_out)
+    const uint32_t K   = j.nof_harq_ack + j.nof_sr + j.nof_csi_part1;
+    int8_t*        dst = K > 11 ? llr_long : llr_out;
+    if (dst)
       for (int i = lane; i < 2 * nre; i += 64)
-        llr_out[j.llr_offset + i] = L.llr[i];
-    const uint32_t K = j.nof_harq_ack + j.nof_sr + j.nof_csi_part1;
-    uci_short_block_field(K, 2, 2 * nre, L.llr, payload + j.payload_offset, &L.status, lane); // the verdict by lane 0, read by lane 0
-    status = L.status;
+        dst[j.llr_offset + i] = L.llr[i];
+    if (K <= 11) {
+      uci_short_block_field(K, 2, 2 * nre, L.llr, payload + j.payload_offset, &L.status, lane); // the verdict by lane 0, read by lane 0
+      status = L.status;
+    } // above 11 bits: status 0 until the polar decoder behind this kernel stores the CRC verdict over it
   }
 
   if (lane == 0) {
@@ -471,7 +484,71 @@ extern "C" int miphy_pucch_process_batch(miphy_ctx* ctx, const miphy_pucch_job* 
   rc                 = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pucch_job) * (size_t)n, s, &d_jobs);
   if (rc)
     return rc;
-  hipLaunchKernelGGL(pucch_kernel, dim3(n), dim3(64), 0, s, (const miphy_pucch_job*)d_jobs, n, gt, (const float2*)grid, payload, results, llr_out);
+  hipLaunchKernelGGL(pucch_kernel, dim3(n), dim3(64), 0, s, (const miphy_pucch_job*)d_jobs, n, gt, (const float2*)grid, payload, results, llr_out,
+                     (int8_t*)nullptr);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
+}
+
+extern "C" int miphy_pucch_process_batch_ex(miphy_ctx* ctx, const miphy_pucch_job* jobs, uint32_t n, uint32_t list_size, const float* grid, uint8_t* payload,
+                                            miphy_pucch_result* results, int8_t* llr_out, void* stream)
+{
+  static const char* const who = "miphy_pucch_process_batch_ex";
+  MIPHY_REQUIRE(ctx && jobs && grid && payload && results, "%s: null argument", who);
+  MIPHY_REQUIRE(list_size == 1 || list_size == 2 || list_size == 4 || list_size == 8, "%s: list size %u not in {1,2,4,8}", who, list_size);
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= (1u << 24), "%s: at most 2^24 PDUs per call", who);
+  // Every job is checked before anything is enqueued; the long PDUs become the polar decoder's fields, in job order.
+  std::vector<miphy_uci_polar_job> fields;
+  std::vector<uint32_t>            status_at; // byte offset of the field's status inside `results`
+  for (uint32_t i = 0; i < n; ++i) {
+    const miphy_pucch_job& j = jobs[i];
+    MIPHY_REQUIRE(j.format != 2 || j.nof_csi_part2 == 0, "%s: job %u: CSI part 2 (%u bits) is not decoded on PUCCH", who, i, j.nof_csi_part2);
+    MIPHY_REQUIRE(miphy_pucch_job_ok(j, true), "%s: job %u: invalid PDU (format %u, %u symbols from %u, %u ports)", who, i, j.format, j.nof_symbols,
+                  j.start_symbol, j.nof_ports);
+    const uint32_t K = j.nof_harq_ack + j.nof_sr + j.nof_csi_part1;
+    if (j.format != 2 || K <= 11)
+      continue;
+    const uint32_t    E = 16u * j.nof_prb * j.nof_symbols;
+    uci_polar_framing f;
+    const int         rc = uci_polar_frame_or_error(who, i, K, E, f);
+    if (rc)
+      return rc;
+    miphy_uci_polar_job pj = {};
+    pj.nof_bits = (uint16_t)K, pj.nof_llr = E, pj.llr_offset = j.llr_offset, pj.payload_offset = j.payload_offset;
+    fields.push_back(pj);
+    status_at.push_back(i * (uint32_t)sizeof(miphy_pucch_result) + (uint32_t)offsetof(miphy_pucch_result, status));
+  }
+  const gold_tables* gt = nullptr;
+  int                rc = miphy_get_gold_tables(ctx, &gt);
+  if (rc)
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // Without llr_out the soft bits of the long PDUs go through the context's workspace, 512 bytes each (E <= 512), and the staged copy
+  // of their jobs points there.
+  int8_t*                      llr_long = llr_out;
+  std::vector<miphy_pucch_job> own;
+  if (!fields.empty() && !llr_out) {
+    void* w = nullptr;
+    if ((rc = miphy_get_workspace(ctx, MIPHY_WS_PUCCH_LLR, 512 * fields.size(), &w)))
+      return rc;
+    llr_long = (int8_t*)w;
+    own.assign(jobs, jobs + n);
+    for (size_t k = 0; k < fields.size(); ++k) {
+      fields[k].llr_offset = 512 * k;
+      own[status_at[k] / sizeof(miphy_pucch_result)].llr_offset = 512 * k;
+    }
+    jobs = own.data();
+  }
+  const void* d_jobs = nullptr;
+  if ((rc = miphy_stage_descs(ctx, jobs, 0, sizeof(miphy_pucch_job) * (size_t)n, s, &d_jobs)))
+    return rc;
+  hipLaunchKernelGGL(pucch_kernel, dim3(n), dim3(64), 0, s, (const miphy_pucch_job*)d_jobs, n, gt, (const float2*)grid, payload, results, llr_out,
+                     fields.empty() ? (int8_t*)nullptr : llr_long);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  if (fields.empty())
+    return MIPHY_OK;
+  // Behind the kernel on the same stream: the decoder's verdict lands on the status byte after the kernel wrote the record.
+  return miphy_uci_polar_decode_fields(who, ctx, fields.data(), (uint32_t)fields.size(), list_size, llr_long, payload, (uint8_t*)results, status_at.data(), s);
 }

@@ -45,7 +45,7 @@ struct uci_polar_code_hdr {
 };
 struct uci_polar_task {
   uint32_t code_off; // byte offset of the field's code block in the piece
-  uint32_t job;      // index of the field in the call: status[job]
+  uint32_t job;      // the field's status byte: status[job] (the index of the field in the call, or the caller's status_index of it)
   uint32_t seg, pad; // seg: the segment a task of the list kernel decodes (the SSC kernel's workgroup takes every segment of its field)
   uint64_t llr_offset, payload_offset;
 };
@@ -358,10 +358,11 @@ extern "C" int miphy_uci_polar_info(uint32_t nof_bits, uint32_t nof_llr, miphy_u
 
 namespace {
 
-// Both entry points. List size 1 is the SSC kernel for every field; above it the CRC6 fields (12..19 bits, parity-check bits) stay with
-// the SSC kernel and every segment of a CRC11 field becomes a task of the list kernel.
+// Every entry point. List size 1 is the SSC kernel for every field; above it the CRC6 fields (12..19 bits, parity-check bits) stay with
+// the SSC kernel and every segment of a CRC11 field becomes a task of the list kernel. The verdict of field i goes to status[i], or to
+// status[status_index[i]] where the caller keeps its status bytes inside records of its own (the PUCCH processor).
 int decode_fields(const char* who, miphy_ctx* ctx, const miphy_uci_polar_job* jobs, uint32_t n, uint32_t list_size, const int8_t* llr, uint8_t* payload,
-                  uint8_t* status, void* stream)
+                  uint8_t* status, const uint32_t* status_index, void* stream)
 {
   MIPHY_REQUIRE(ctx && jobs && llr && payload && status, "%s: null argument", who);
   MIPHY_REQUIRE(list_size == 1 || list_size == 2 || list_size == 4 || list_size == 8, "%s: list size %u not in {1,2,4,8}", who, list_size);
@@ -404,7 +405,7 @@ int decode_fields(const char* who, miphy_ctx* ctx, const miphy_uci_polar_job* jo
       p.codes.insert(p.codes.end(), blob.begin(), blob.end());
     }
     uci_polar_task t = {};
-    t.code_off = it->second, t.job = i, t.pad = fr[i].pad;
+    t.code_off = it->second, t.job = status_index ? status_index[i] : i, t.pad = fr[i].pad;
     t.llr_offset = jobs[i].llr_offset, t.payload_offset = jobs[i].payload_offset;
     if (list) {
       auto& group = p.list[reinterpret_cast<const uci_polar_code_hdr*>(blob.data())->N];
@@ -435,11 +436,17 @@ extern "C" void miphy_debug_uci_polar_list_segments(unsigned* ssc, unsigned* lis
 extern "C" int miphy_uci_polar_decode_batch(miphy_ctx* ctx, const miphy_uci_polar_job* jobs, uint32_t n, const int8_t* llr, uint8_t* payload, uint8_t* status,
                                             void* stream)
 {
-  return decode_fields("miphy_uci_polar_decode_batch", ctx, jobs, n, 1, llr, payload, status, stream);
+  return decode_fields("miphy_uci_polar_decode_batch", ctx, jobs, n, 1, llr, payload, status, nullptr, stream);
 }
 
 extern "C" int miphy_uci_polar_decode_list_batch(miphy_ctx* ctx, const miphy_uci_polar_job* jobs, uint32_t n, uint32_t list_size, const int8_t* llr,
                                                  uint8_t* payload, uint8_t* status, void* stream)
 {
-  return decode_fields("miphy_uci_polar_decode_list_batch", ctx, jobs, n, list_size, llr, payload, status, stream);
+  return decode_fields("miphy_uci_polar_decode_list_batch", ctx, jobs, n, list_size, llr, payload, status, nullptr, stream);
+}
+
+int miphy_uci_polar_decode_fields(const char* who, miphy_ctx* ctx, const miphy_uci_polar_job* jobs, uint32_t n, uint32_t list_size, const int8_t* llr,
+                                  uint8_t* payload, uint8_t* status, const uint32_t* status_index, hipStream_t s)
+{
+  return decode_fields(who, ctx, jobs, n, list_size, llr, payload, status, status_index, s);
 }

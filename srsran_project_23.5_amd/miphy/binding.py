@@ -132,6 +132,7 @@ def lib():
         l.miphy_debug_uci_polar_list_segments.argtypes = [C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
         l.miphy_debug_uci_polar_list_segments.restype = None
         l.miphy_pucch_process_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
+        l.miphy_pucch_process_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
         l.miphy_prach_detect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_prach_generate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 2
         l.miphy_prach_demod_info.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
@@ -753,6 +754,19 @@ class Context:
         assert llr is None or llr.dtype == torch.int8
         check(lib().miphy_pucch_process_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(payload), _dptr(results),
                                               None if llr is None else _dptr(llr), _stream_ptr(stream)))
+
+    def pucch_process_batch_ex(self, jobs, list_size, grid, payload, results, llr=None, stream=None):
+        """pucch_process_batch that also takes format-2 PDUs above 11 bits (jobs: numpy PucchJob array, HOST memory only): their soft
+        bits are decoded as one polar-coded UCI field each at list size 1, 2, 4 or 8, the payload gets their K bits and the status byte
+        of their record the CRC verdict. Other PDUs come out as from pucch_process_batch. Only enqueues."""
+        import torch
+        assert isinstance(jobs, np.ndarray) and jobs.dtype == PucchJob, "pucch_process_batch_ex takes host jobs"
+        jobs = np.ascontiguousarray(jobs)
+        assert grid.dtype == torch.complex64 and payload.dtype == torch.uint8 and results.dtype == torch.uint8
+        assert results.numel() >= jobs.size * PucchResult.itemsize
+        assert llr is None or llr.dtype == torch.int8
+        check(lib().miphy_pucch_process_batch_ex(self.h, C.c_void_p(jobs.ctypes.data), jobs.size, int(list_size), _dptr(grid), _dptr(payload),
+                                                 _dptr(results), None if llr is None else _dptr(llr), _stream_ptr(stream)))
 
     def prach_detect_batch(self, jobs, symbols, results, preambles, stream=None):
         """PRACH detector (jobs: numpy PrachJob array, or a uint8 device tensor holding the same bytes), one job per occasion: symbols
