@@ -493,6 +493,24 @@ typedef struct {
 int miphy_dmrs_pdsch_map_batch(miphy_ctx* ctx, const miphy_dmrs_pdsch_job* jobs, int jobs_on_device, uint32_t n, float* grid /* device cf_t */,
                                void* stream);
 
+/* PDSCH modulator, one codeword on 1..4 layers (beyond the 23.5 reference; the contract is the oracle's orc_pdsch_modulate). Layer
+ * mapping of TS 38.211 7.3.1.3, x^(ly)(i) = d(L i + ly): the resource element of rank i carries codeword symbol L i + ly on grid port
+ * ports[ly]. No precoding. Everything else as miphy_pdsch_modulate_batch: same scrambling, constellations, scaling and RE selection, only
+ * the mapped REs of the named ports are written. The pi/2-BPSK rotation follows the parity of the codeword symbol L i + ly. A batch of
+ * one-layer jobs writes the bytes miphy_pdsch_modulate_batch writes. Host jobs are checked before anything is enqueued (1..4 layers,
+ * distinct ports below 16, nof_bits = REs x L x mod and the rules of the one-layer entry point); a device-resident job that breaks a
+ * rule is skipped by the kernels. Not supported: two codewords (5..8 layers), precoding matrices, interleaved VRB-to-PRB mapping. */
+typedef struct {
+  miphy_pdsch_mod_job base; /* base.port is ignored; base.nof_bits = miphy_pdsch_mod_layers_nof_re() x nof_layers x mod */
+  uint8_t nof_layers;       /* 1..4 */
+  uint8_t ports[4];         /* grid port of each layer, distinct, < 16 */
+  uint8_t pad[3];
+} miphy_pdsch_mod_layers_job;
+
+uint32_t miphy_pdsch_mod_layers_nof_re(const miphy_pdsch_mod_layers_job* job); /* host: data REs per layer; 0 on an invalid job */
+int miphy_pdsch_modulate_layers_batch(miphy_ctx* ctx, const miphy_pdsch_mod_layers_job* jobs, int jobs_on_device, uint32_t n,
+                                      const uint8_t* codewords /* device */, float* grid /* device cf_t */, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Polar code chains  --  replace the chain of srsran::polar_code::set + polar_allocator::allocate + polar_encoder::encode
  * + polar_rate_matcher::rate_match (transmit) and polar_rate_dematcher::rate_dematch + polar_decoder::decode +
@@ -1113,6 +1131,27 @@ typedef struct miphy_pdsch_process_plan miphy_pdsch_process_plan;
 int  miphy_pdsch_process_plan_create(miphy_ctx* ctx, const miphy_pdsch_pdu* pdus /* host */, uint32_t n, miphy_pdsch_process_plan** out);
 int  miphy_pdsch_process_plan_run(miphy_pdsch_process_plan* plan, const uint8_t* tb_in /* device */, float* grid /* device cf_t */, void* stream);
 void miphy_pdsch_process_plan_destroy(miphy_pdsch_process_plan* plan);
+
+/* PDSCH processor, one codeword on 1..4 layers (beyond the 23.5 reference; the contract is the oracle chain orc_pdsch_encode with
+ * nof_layers = L and nof_ch_symbols = REs x L -> orc_pdsch_modulate -> orc_dmrs_pdsch_map on the same port list). As
+ * miphy_pdsch_process_batch with the data-RE count per layer, miphy_pdsch_modulate_layers_batch and the DM-RS of type 1 on DM-RS ports
+ * 1000 .. 1000 + L - 1, DM-RS port p on grid port ports[p]; the two scalings are those of the one-layer processor. base.port is ignored.
+ * One stream, no host synchronisation, the codewords stay on the device. Every PDU is checked before anything is enqueued: the rules of
+ * miphy_pdsch_process_batch and of miphy_pdsch_modulate_layers_batch, and the encoder's limit on the transport block -- at most 52
+ * codeblocks (ldpc::MAX_NOF_SEGMENTS), that is tb_bytes <= 54753 on base graph 1 and <= 24801 on base graph 2, and at least one RE per
+ * layer for each codeblock. A batch of one-layer PDUs writes the bytes miphy_pdsch_process_batch writes. There is no prepared plan for
+ * this entry point (miphy_pdsch_process_plan_* stays one-layer). */
+typedef struct {
+  miphy_pdsch_pdu base;
+  uint8_t nof_layers; /* 1..4 */
+  uint8_t ports[4];   /* grid port of each layer (and of DM-RS port 1000 + layer), distinct, < 16 */
+  uint8_t pad[3];
+} miphy_pdsch_layers_pdu;
+
+/* Data REs of the allocation per layer; 0 on an invalid PDU. Host function. */
+uint32_t miphy_pdsch_layers_pdu_nof_re(const miphy_pdsch_layers_pdu* pdu);
+int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsch_layers_pdu* pdus /* host */, uint32_t n, const uint8_t* tb_in /* device */,
+                                     float* grid /* device cf_t; only the mapped REs are written */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * PDCCH processor (whole PDUs)  --  replaces srsran::pdcch_processor::process after the CCE-to-PRB mapping

@@ -2358,14 +2358,16 @@ inline void put_written_res(srsran::resource_grid_writer& grid, unsigned port, u
 }
 
 /// srsran::pdsch_modulator over miphy_pdsch_modulate_batch (pdsch_modulator.h:98). One codeword on one layer, contiguous
-/// allocation -- the configurations the 23.5 software modulator handles correctly.
+/// allocation -- the configurations the 23.5 software modulator handles correctly -- and, beyond it, one codeword on two to four
+/// layers (config.ports.size() layers, layer ly on port config.ports[ly]) over miphy_pdsch_modulate_layers_batch.
 class pdsch_modulator_hip : public srsran::pdsch_modulator
 {
 public:
   explicit pdsch_modulator_hip(std::shared_ptr<context> c) : c(std::move(c)) {}
   void modulate(srsran::resource_grid_writer& grid, srsran::span<const srsran::bit_buffer> codewords, const config_t& config) override
   {
-    srsran_assert(config.ports.size() == 1 && codewords.size() == 1, "Only one layer / one codeword is supported.");
+    const unsigned nlayers = config.ports.size();
+    srsran_assert(nlayers >= 1 && nlayers <= 4 && codewords.size() == 1, "Only one codeword on one to four layers is supported.");
     srsran_assert(config.freq_allocation.is_contiguous(), "Only contiguous allocations are supported.");
     const srsran::bounded_bitset<srsran::MAX_RB> prb = config.freq_allocation.get_prb_mask(config.bwp_start_rb, config.bwp_size_rb);
     const unsigned                               nprb = prb.size(), nsc = nprb * 12;
@@ -2390,15 +2392,26 @@ public:
     for (unsigned i = 0; i != cw.size(); ++i) {
       bits[i] = cw.extract<uint8_t>(i, 1);
     }
-    host.assign(static_cast<size_t>(14) * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernel"
+    host.assign(static_cast<size_t>(nlayers) * 14 * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernel"
     auto* d_cw = static_cast<uint8_t*>(c->buf(0, bits.size() + 16));
     auto* d_g  = static_cast<float*>(c->buf(1, host.size() * sizeof(srsran::cf_t)));
     c->h2d(d_cw, bits.data(), bits.size());
     c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
-    context::check(miphy_pdsch_modulate_batch(c->ctx, &j, 0, 1, d_cw, d_g, c->stream), "pdsch_modulate");
+    if (nlayers == 1) {
+      context::check(miphy_pdsch_modulate_batch(c->ctx, &j, 0, 1, d_cw, d_g, c->stream), "pdsch_modulate");
+    } else {
+      miphy_pdsch_mod_layers_job lj = {};
+      lj.base = j, lj.nof_layers = nlayers;
+      for (unsigned ly = 0; ly != nlayers; ++ly) {
+        lj.ports[ly] = ly; // the staging grid has one port per layer
+      }
+      context::check(miphy_pdsch_modulate_layers_batch(c->ctx, &lj, 0, 1, d_cw, d_g, c->stream), "pdsch_modulate_layers");
+    }
     c->d2h(host.data(), d_g, host.size() * sizeof(srsran::cf_t));
     c->sync();
-    put_written_res(grid, config.ports[0], nsc, host.data());
+    for (unsigned ly = 0; ly != nlayers; ++ly) {
+      put_written_res(grid, config.ports[ly], nsc, host.data() + static_cast<size_t>(ly) * 14 * nsc);
+    }
   }
 
 private:
@@ -2460,7 +2473,8 @@ private:
 
 // ---------------------------------------------------------------------------------------------------------------- PDSCH processor
 /// srsran::pdsch_processor over miphy_pdsch_process_batch (pdsch_processor.h:164-166): encoding, modulation and DM-RS generation
-/// in one device pass; the transport block goes up, the written resource elements come back.
+/// in one device pass; the transport block goes up, the written resource elements come back. A PDU of one codeword on two to four
+/// layers (pdu.ports.size() layers, layer ly and DM-RS port 1000 + ly on port pdu.ports[ly]) goes to miphy_pdsch_process_layers_batch.
 class pdsch_processor_hip : public srsran::pdsch_processor
 {
 public:
@@ -2469,7 +2483,8 @@ public:
                srsran::static_vector<srsran::span<const uint8_t>, srsran::pdsch_processor::MAX_NOF_TRANSPORT_BLOCKS> data,
                const pdu_t&                                                                         pdu) override
   {
-    srsran_assert(pdu.ports.size() == 1 && pdu.codewords.size() == 1 && data.size() == 1, "Only one layer / one codeword is supported.");
+    const unsigned nlayers = pdu.ports.size();
+    srsran_assert(nlayers >= 1 && nlayers <= 4 && pdu.codewords.size() == 1 && data.size() == 1, "Only one codeword on one to four layers is supported.");
     srsran_assert(pdu.dmrs == srsran::dmrs_type::TYPE1, "Only DM-RS Type 1 is currently supported.");
     srsran_assert(pdu.freq_alloc.is_contiguous(), "Only contiguous allocation is currently supported.");
     const srsran::bounded_bitset<srsran::MAX_RB> prb  = pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb);
@@ -2490,15 +2505,26 @@ public:
     }
     prb.for_each(0, nprb, [&p](unsigned r) { p.rb_mask[r >> 6] |= 1ULL << (r & 63); });
     p.nof_reserved = reserved_rectangles(pdu.reserved, nprb, p.reserved);
-    host.assign(static_cast<size_t>(14) * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernels"
+    host.assign(static_cast<size_t>(nlayers) * 14 * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernels"
     auto* d_tb = static_cast<uint8_t*>(c->buf(0, data[0].size() + 16));
     auto* d_g  = static_cast<float*>(c->buf(1, host.size() * sizeof(srsran::cf_t)));
     c->h2d(d_tb, data[0].data(), data[0].size());
     c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
-    context::check(miphy_pdsch_process_batch(c->ctx, &p, 1, d_tb, d_g, c->stream), "pdsch_process");
+    if (nlayers == 1) {
+      context::check(miphy_pdsch_process_batch(c->ctx, &p, 1, d_tb, d_g, c->stream), "pdsch_process");
+    } else {
+      miphy_pdsch_layers_pdu lp = {};
+      lp.base = p, lp.nof_layers = nlayers;
+      for (unsigned ly = 0; ly != nlayers; ++ly) {
+        lp.ports[ly] = ly; // the staging grid has one port per layer
+      }
+      context::check(miphy_pdsch_process_layers_batch(c->ctx, &lp, 1, d_tb, d_g, c->stream), "pdsch_process_layers");
+    }
     c->d2h(host.data(), d_g, host.size() * sizeof(srsran::cf_t));
     c->sync();
-    put_written_res(grid, pdu.ports[0], nsc, host.data());
+    for (unsigned ly = 0; ly != nlayers; ++ly) {
+      put_written_res(grid, pdu.ports[ly], nsc, host.data() + static_cast<size_t>(ly) * 14 * nsc);
+    }
   }
 
 private:
@@ -2725,7 +2751,8 @@ private:
 // ---------------------------------------------------------------------------------------------------------------- downlink processor
 /// srsran::downlink_processor (downlink_processor.h:45-111, lib/phy/upper/downlink_processor_single_executor_impl.cpp:54-199) that
 /// batches the PDSCH PDUs of a slot: process_pdsch() queues, finish_processing_pdus() -- the reference's own end-of-slot call --
-/// runs miphy_pdsch_process_batch over all of them (transport blocks up once, written REs down once), puts the REs into the grid
+/// runs miphy_pdsch_process_batch over the one-layer PDUs and miphy_pdsch_process_layers_batch over those of two to four layers, on
+/// the same device grid (transport blocks up once, written REs down once), puts the REs into the grid
 /// and sends it through the gateway. PDCCH, SSB and CSI-RS go to the CPU processors given at construction, at once. Same
 /// observable behaviour as the reference processor with its executor: nothing happens without a configured grid, the grid is zeroed
 /// on configuration and sent exactly once, after finish_processing_pdus(). Like the reference (downlink_processor_single_executor_impl
@@ -2781,10 +2808,13 @@ public:
     }
     // The PDU validator of the factory rejects these up front (pdsch_pdu_validator_hip); a caller that skips it fails loudly here
     // also in release builds.
-    require(pdu.ports.size() == 1 && pdu.codewords.size() == 1 && data.size() == 1, "Only one layer / one codeword is supported.");
+    require(pdu.ports.size() >= 1 && pdu.ports.size() <= 4 && pdu.codewords.size() == 1 && data.size() == 1,
+            "Only one codeword on one to four layers is supported.");
     require(pdu.dmrs == srsran::dmrs_type::TYPE1, "Only DM-RS Type 1 is currently supported.");
     require(pdu.freq_alloc.is_contiguous(), "Only contiguous allocation is currently supported.");
-    require(pdu.ports[0] < nports, "Transmit port outside the resource grid.");
+    for (uint8_t port : pdu.ports) {
+      require(port < nports, "Transmit port outside the resource grid.");
+    }
     queue.push_back(entry{data[0], pdu});
   }
   void configure_resource_grid(const srsran::resource_grid_context& context, srsran::resource_grid& grid_) override
@@ -2857,15 +2887,26 @@ private:
     if (queue.empty()) {
       return;
     }
-    const unsigned               n = queue.size(), nsc = nprb * 12;
-    std::vector<miphy_pdsch_pdu> pdus(n);
-    size_t                       tb_bytes = 0;
+    const unsigned                      n = queue.size(), nsc = nprb * 12;
+    std::vector<miphy_pdsch_pdu>        pdus;  // one layer
+    std::vector<miphy_pdsch_layers_pdu> lpdus; // two to four layers
+    std::vector<size_t>                 tb_offset(n);
+    size_t                              tb_bytes = 0;
+    pdus.reserve(n), lpdus.reserve(n);
     for (unsigned i = 0; i != n; ++i) {
       const srsran::pdsch_processor::pdu_t&        pdu = queue[i].pdu;
       const srsran::bounded_bitset<srsran::MAX_RB> prb = pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb);
       srsran_assert(prb.size() <= nprb, "The allocation exceeds the resource grid.");
-      miphy_pdsch_pdu& p = pdus[i];
-      p                  = {};
+      const unsigned nlayers = pdu.ports.size();
+      if (nlayers == 1) {
+        pdus.push_back(miphy_pdsch_pdu{});
+      } else {
+        miphy_pdsch_layers_pdu lp = {};
+        lp.nof_layers             = nlayers;
+        std::copy(pdu.ports.begin(), pdu.ports.end(), lp.ports);
+        lpdus.push_back(lp);
+      }
+      miphy_pdsch_pdu& p = nlayers == 1 ? pdus.back() : lpdus.back().base;
       p.slot_in_frame = pdu.slot.slot_index(), p.rnti = pdu.rnti, p.n_id = pdu.n_id, p.dmrs_scrambling_id = pdu.scrambling_id;
       p.tbs_lbrm_bytes = pdu.tbs_lbrm_bytes, p.tb_bytes = queue[i].data.size();
       p.ratio_pdsch_dmrs_to_sss_dB = pdu.ratio_pdsch_dmrs_to_sss_dB, p.ratio_pdsch_data_to_sss_dB = pdu.ratio_pdsch_data_to_sss_dB;
@@ -2882,18 +2923,24 @@ private:
       prb.for_each(0, prb.size(), [&p](unsigned r) { p.rb_mask[r >> 6] |= 1ULL << (r & 63); });
       p.nof_reserved = reserved_rectangles(pdu.reserved, prb.size(), p.reserved);
       p.tb_offset = tb_bytes, p.grid_offset = 0;
+      tb_offset[i] = tb_bytes;
       tb_bytes += (queue[i].data.size() + 15) & ~static_cast<size_t>(15);
     }
     tbs.assign(tb_bytes + 16, 0);
     for (unsigned i = 0; i != n; ++i) {
-      std::memcpy(&tbs[pdus[i].tb_offset], queue[i].data.data(), queue[i].data.size());
+      std::memcpy(&tbs[tb_offset[i]], queue[i].data.data(), queue[i].data.size());
     }
     host.assign(static_cast<size_t>(nports) * 14 * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernels"
     auto* d_tb = static_cast<uint8_t*>(wc->buf(0, tbs.size()));
     auto* d_g  = static_cast<float*>(wc->buf(1, host.size() * sizeof(srsran::cf_t)));
     wc->h2d(d_tb, tbs.data(), tbs.size());
     wc->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
-    context::check(miphy_pdsch_process_batch(wc->ctx, pdus.data(), n, d_tb, d_g, wc->stream), "pdsch_process");
+    if (!pdus.empty()) {
+      context::check(miphy_pdsch_process_batch(wc->ctx, pdus.data(), pdus.size(), d_tb, d_g, wc->stream), "pdsch_process");
+    }
+    if (!lpdus.empty()) {
+      context::check(miphy_pdsch_process_layers_batch(wc->ctx, lpdus.data(), lpdus.size(), d_tb, d_g, wc->stream), "pdsch_process_layers");
+    }
     wc->d2h(host.data(), d_g, host.size() * sizeof(srsran::cf_t));
     wc->sync();
     for (unsigned p = 0; p != nports; ++p) {
@@ -3617,11 +3664,26 @@ public:
   explicit pdsch_pdu_validator_hip(std::unique_ptr<srsran::pdsch_pdu_validator> ref) : ref(std::move(ref)) {}
   bool is_valid(const srsran::pdsch_processor::pdu_t& pdu) const override
   {
-    if (!ref->is_valid(pdu)) {
+    // device path: one codeword on one to four layers (the number of ports is the number of layers) on distinct ports, DM-RS type 1,
+    // contiguous (non-interleaved) allocation, at most four reserved patterns. The reference validator stops at one layer: it judges
+    // everything else on a copy of the PDU that keeps the first port.
+    const unsigned nlayers = pdu.ports.size();
+    if (nlayers < 1 || nlayers > 4) {
       return false;
     }
-    // device path: one codeword on one layer, DM-RS type 1, contiguous (non-interleaved) allocation, at most four reserved patterns
-    return pdu.codewords.size() == 1 && pdu.ports.size() == 1 && pdu.dmrs == srsran::dmrs_type::TYPE1 && pdu.freq_alloc.is_contiguous() &&
+    for (unsigned a = 0; a != nlayers; ++a) {
+      for (unsigned b = 0; b != a; ++b) {
+        if (pdu.ports[a] == pdu.ports[b]) {
+          return false;
+        }
+      }
+    }
+    srsran::pdsch_processor::pdu_t one = pdu;
+    one.ports.resize(1);
+    if (!ref->is_valid(one)) {
+      return false;
+    }
+    return pdu.codewords.size() == 1 && pdu.dmrs == srsran::dmrs_type::TYPE1 && pdu.freq_alloc.is_contiguous() &&
            pdu.cp == srsran::cyclic_prefix::NORMAL && pdu.reserved.get_nof_entries() <= 4;
   }
 

@@ -9,6 +9,9 @@
 // indexes out of bounds for more than one layer (pdsch_modulator_impl.cpp:80-103) and its non-contiguous mapping path writes a
 // single PRB (map_to_prb_other). One workgroup per (transmission, OFDM symbol); every resource element is written once, with the
 // exact single-precision value of the reference (level * scale [* scaling]).
+// Beyond the reference: one codeword on 1..4 layers (pdsch_mod_layers_kernel, miphy_pdsch_modulate_layers_batch), the layer mapping of
+// TS 38.211 7.3.1.3 as the oracle's orc_pdsch_modulate states it, layer ly on grid port ports[ly], no precoding. The one-layer kernel and
+// entry point are unchanged.
 #include "gold_device.h"
 #include "mod_device.h"
 #include "miphy_ext.h"
@@ -543,6 +546,317 @@ __global__ void __launch_bounds__(256) csi_rs_kernel(const miphy_csi_rs_job* __r
   }
 }
 
+// ---------------------------------------------------------------------------------------------------- one codeword on 1..4 layers
+// TS 38.211 7.3.1.3: x^(ly)(i) = d(L i + ly); layer ly goes to grid port ports[ly], no precoding. Beyond the 23.5 reference (whose layer
+// mapper is broken), so the contract is the oracle's orc_pdsch_modulate. The resource element of rank i_re in the transmission owns the
+// codeword symbols L i_re .. L i_re + L - 1: L mod consecutive bytes of the codeword and L mod <= 32 consecutive bits of the scrambling
+// sequence, so one thread maps all layers of its element from one run of bytes and one 64-bit window of two sequence words.
+constexpr int PDSCH_SEQ_CHUNK = PDSCH_SEQ_STRIDE / 2; // sequence words one workgroup of pdsch_seq_layers_kernel generates (x1 and x2 in LDS)
+constexpr int PDSCH_LAYERS_INFO = 16;                 // ints per transmission: 14 symbol prefixes, the elements per layer, 1 = valid job
+
+// What the kernels check of a job themselves (device-resident jobs reach them unseen by the host): a job that fails is skipped.
+__device__ __forceinline__ bool layers_job_ok(const miphy_pdsch_mod_layers_job& j)
+{
+  const miphy_pdsch_mod_job& b = j.base;
+  const unsigned             L = j.nof_layers;
+  if (L < 1 || L > 4)
+    return false;
+  unsigned seen = 0;
+  for (unsigned ly = 0; ly < L; ++ly) {
+    const unsigned p = j.ports[ly];
+    if (p >= 16 || ((seen >> p) & 1u))
+      return false;
+    seen |= 1u << p;
+  }
+  return (b.mod == 1 || b.mod == 2 || b.mod == 4 || b.mod == 6 || b.mod == 8) && b.nof_symbols >= 1 && b.start_symbol + b.nof_symbols <= 14 &&
+         (b.dmrs_type == 1 || b.dmrs_type == 2) && b.nof_cdm_groups_without_data >= 1 && b.nof_cdm_groups_without_data <= (b.dmrs_type == 1 ? 2 : 3) &&
+         b.grid_nof_prb >= 1 && b.grid_nof_prb <= 275 && b.bwp_start_rb + b.bwp_size_rb <= 275 && b.nof_reserved <= 4 && b.n_id < 1024 && b.rnti < 65536;
+}
+
+// Both LFSR sequences of c(n), held as words in LDS, from `have` (>= 31) to nwords words: the word recurrences w[i] = w[i-28] ^ w[i-31] (x1) and
+// w[i] = w[i-28] ^ w[i-29] ^ w[i-30] ^ w[i-31] (x2) in their squares, as gold_x2_sequence does for x2 alone.
+__device__ __forceinline__ void gold_words_extend(uint32_t* w1, uint32_t* w2, int have, int nwords, int tid, int nt)
+{
+  int k = 0;
+  while ((62 << k) <= have)
+    ++k;
+  while (have < nwords) {
+    const int d = 1 << k, end = min(have + 28 * d, nwords);
+    for (int i = have + tid; i < end; i += nt) {
+      w1[i] = w1[i - 28 * d] ^ w1[i - 31 * d];
+      w2[i] = w2[i - 28 * d] ^ w2[i - 29 * d] ^ w2[i - 30 * d] ^ w2[i - 31 * d];
+    }
+    __syncthreads();
+    have += 28 * d;
+    while ((62 << k) <= have)
+      ++k;
+  }
+}
+
+// Sibling of pdsch_seq_kernel for transmissions on L layers, whose sequence is L times longer than the x1 table and than one workgroup's LDS:
+// workgroup (transmission, chunk) generates PDSCH_SEQ_CHUNK words of it -- both LFSRs jump to the chunk's first bit (gold_state), one lane
+// each runs the 31-word head, the word recurrences do the rest. `stride` = sequence words reserved per transmission. Chunk 0 also validates
+// the job and counts its elements: info[0..13] = elements per layer before every OFDM symbol, info[14] = elements per layer, info[15] = 1 when
+// the job is valid and its bit count is elements x L x mod.
+__global__ void __launch_bounds__(512) pdsch_seq_layers_kernel(const miphy_pdsch_mod_layers_job* __restrict__ jobs, const gold_tables* __restrict__ gt,
+                                                               uint32_t* __restrict__ seq, int* __restrict__ info_out, uint32_t stride)
+{
+  __shared__ uint32_t w1[PDSCH_SEQ_CHUNK], w2[PDSCH_SEQ_CHUNK];
+  __shared__ uint64_t rbm[5], resm[4][5];
+  __shared__ int      cnt[14];
+  const miphy_pdsch_mod_layers_job* __restrict__ lj = jobs + blockIdx.x;
+  const miphy_pdsch_mod_job* __restrict__ jp        = &lj->base;
+  const int      tid = threadIdx.x, nt = blockDim.x, chunk = blockIdx.y;
+  const bool     ok       = layers_job_ok(*lj);
+  const uint32_t nof_bits = jp->nof_bits;
+  const bool     fits     = nof_bits <= 32u * (stride - 2u); // + the 64-bit window of the last resource element
+  if (chunk == 0) {
+    int* info = info_out + (size_t)blockIdx.x * PDSCH_LAYERS_INFO;
+    if (!ok || !fits) {
+      if (tid == 0)
+        info[15] = 0;
+      return;
+    }
+    const unsigned dmask     = dmrs_prb_mask(jp->dmrs_type, jp->nof_cdm_groups_without_data);
+    const unsigned dmrs_syms = jp->dmrs_symbols_mask;
+    const int      nprb_grid = jp->grid_nof_prb, nres = jp->nof_reserved;
+    const int      bwp0 = jp->bwp_start_rb, bwp1 = bwp0 + jp->bwp_size_rb;
+    const int      s0 = jp->start_symbol, s1 = s0 + jp->nof_symbols;
+    if (tid < 5)
+      rbm[tid] = jp->rb_mask[tid];
+    if (tid >= 32 && tid < 32 + 5 * nres)
+      resm[(tid - 32) / 5][(tid - 32) % 5] = jp->reserved[(tid - 32) / 5].prb_mask[(tid - 32) % 5];
+    if (tid >= 64 && tid < 78)
+      cnt[tid - 64] = 0;
+    __syncthreads();
+    for (int q = tid; q < 14 * nprb_grid; q += nt) {
+      const int s = q / nprb_grid, rb = q - s * nprb_grid;
+      if (s < s0 || s >= s1 || !((rbm[rb >> 6] >> (rb & 63)) & 1ull))
+        continue;
+      unsigned ex = (((dmrs_syms >> s) & 1u) && rb >= bwp0 && rb < bwp1) ? dmask : 0u;
+      for (int r = 0; r < nres; ++r)
+        if (((jp->reserved[r].symbols >> s) & 1u) && ((resm[r][rb >> 6] >> (rb & 63)) & 1ull))
+          ex |= jp->reserved[r].re_mask;
+      atomicAdd(&cnt[s], __popc(~ex & 0xfffu));
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int run = 0;
+      for (int s = 0; s < 14; ++s) {
+        info[s] = run;
+        run += cnt[s];
+      }
+      info[14] = run;
+      info[15] = ((uint64_t)run * lj->nof_layers * jp->mod == nof_bits) ? 1 : 0;
+    }
+  }
+  if (!ok || !fits)
+    return;
+  const int nwords = (int)((nof_bits + 31u) >> 5) + 2;
+  const int first  = chunk * PDSCH_SEQ_CHUNK;
+  if (first >= nwords)
+    return;
+  const int n = min(PDSCH_SEQ_CHUNK, nwords - first), head = min(n, 31);
+  if (tid == 0 || tid == 64) { // one lane of two wavefronts: x1 and x2 side by side
+    const bool is_x2 = tid == 64;
+    lfsr_head(gold_state(*gt, is_x2, (jp->rnti << 15) + jp->n_id, 32u * (uint32_t)first), is_x2, head, is_x2 ? w2 : w1);
+  }
+  __syncthreads();
+  gold_words_extend(w1, w2, head, n, tid, nt);
+  uint32_t* o = seq + (size_t)blockIdx.x * stride + first;
+  for (int i = tid; i < n; i += nt)
+    o[i] = w1[i] ^ w2[i];
+}
+
+// The common shapes of pdsch_mod_layers_kernel (16QAM / 256QAM, the element's run of bytes aligned to words) as in pdsch_mod_kernel: the loads of a
+// group of the thread's elements -- the LL x MOD bytes of each as one wide load and the two words of its scrambling window -- are issued before
+// the first of them is mapped, unconditionally (an element that carries no data reads element 0 of the symbol and is not stored). The group
+// shrinks as the element grows, so that the loaded words stay in registers.
+template <int LL, int MOD>
+__device__ __forceinline__ void pdsch_layers_fast(int tid, int nprb, int prefix, const uint16_t* prb_of, const uint16_t* keep_of, const uint16_t* off_of,
+                                                  const uint32_t* __restrict__ seq, const uint8_t* __restrict__ cw, float2* const (&g)[4], bool scale,
+                                                  float scaling)
+{
+  constexpr int NW = LL * MOD / 4; // codeword words of one element
+  constexpr int IT = (275 * 12 + 255) / 256, G = NW >= 6 ? 4 : (NW >= 3 ? 7 : IT);
+  struct alignas(4) words {
+    uint32_t v[NW];
+  };
+  for (int it0 = 0; it0 < IT && it0 * 256 < nprb * 12; it0 += G) {
+    words    cv[G];
+    uint32_t q0[G], q1[G], sh[G];
+    int      dst[G]; // grid column of the element, -1: none
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const int      idx  = tid + (it0 + u) * 256;
+      const bool     in   = idx < nprb * 12;
+      const int      i    = in ? idx / 12 : 0, k = in ? idx - i * 12 : 0;
+      const unsigned keep = keep_of[i];
+      const bool     has  = in && ((keep >> k) & 1u);
+      const int      j    = has ? off_of[i] + __popc(keep & ((1u << k) - 1u)) : 0;
+      const uint32_t d0   = ((uint32_t)prefix + (uint32_t)j) * (uint32_t)LL; // first codeword symbol of the element
+      const uint32_t bi   = d0 * (uint32_t)MOD;
+      q0[u] = seq[bi >> 5], q1[u] = seq[(bi >> 5) + 1];
+      sh[u]  = bi & 31u;
+      cv[u]  = *reinterpret_cast<const words*>(cw + (size_t)d0 * MOD);
+      dst[u] = has ? (int)prb_of[i] * 12 + k : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const uint32_t cb  = (uint32_t)((((uint64_t)q1[u] << 32) | q0[u]) >> sh[u]);
+      uint32_t       raw = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w)
+        raw |= (((cv[u].v[w] & 0x01010101u) * 0x01020408u) >> 24) << (4 * w);
+      const uint32_t bits = raw ^ cb; // scrambled bits of the element, layer after layer
+#pragma unroll
+      for (int ly = 0; ly < LL; ++ly) {
+        float2 x = map_symbol(MOD, (bits >> (ly * MOD)) & ((1u << MOD) - 1u), 0u);
+        if (scale) {
+          x.x = x.x * scaling;
+          x.y = x.y * scaling;
+        }
+        if (dst[u] >= 0)
+          g[ly][dst[u]] = x;
+      }
+    }
+  }
+}
+
+// Same geometry as pdsch_mod_kernel: one workgroup per (transmission, OFDM symbol), the PRB list, the keep masks and the exclusive scan in LDS.
+__global__ void __launch_bounds__(256) pdsch_mod_layers_kernel(const miphy_pdsch_mod_layers_job* __restrict__ jobs, const uint8_t* __restrict__ cw_base,
+                                                               float2* __restrict__ grid, const uint32_t* __restrict__ seq_base,
+                                                               const int* __restrict__ info_base, uint32_t stride)
+{
+  __shared__ uint16_t prb_of[276];
+  __shared__ uint16_t keep_of[276]; // per allocated PRB: 12-bit mask of the REs that carry data in this symbol
+  __shared__ uint16_t off_of[276];  // per allocated PRB: index of its first data RE within the symbol
+  __shared__ uint64_t rbm[5], resm[4][5];
+  __shared__ int      nprb_s, n_re_s;
+  const miphy_pdsch_mod_layers_job* __restrict__ lj = jobs + blockIdx.x;
+  const miphy_pdsch_mod_job* __restrict__ jp        = &lj->base;
+  const int* info = info_base + (size_t)blockIdx.x * PDSCH_LAYERS_INFO;
+  const int  sy = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+  if (!info[15]) // invalid job (pdsch_seq_layers_kernel): skipped
+    return;
+  const int start_symbol = jp->start_symbol, nof_symbols = jp->nof_symbols;
+  if (sy < start_symbol || sy >= start_symbol + nof_symbols)
+    return;
+  const unsigned dmask     = dmrs_prb_mask(jp->dmrs_type, jp->nof_cdm_groups_without_data);
+  const unsigned dmrs_syms = jp->dmrs_symbols_mask;
+  const int      nprb_grid = jp->grid_nof_prb, nres = jp->nof_reserved;
+  const int      bwp0 = jp->bwp_start_rb, bwp1 = bwp0 + jp->bwp_size_rb;
+  if (tid < 5)
+    rbm[tid] = jp->rb_mask[tid];
+  if (tid >= 32 && tid < 32 + 5 * nres)
+    resm[(tid - 32) / 5][(tid - 32) % 5] = jp->reserved[(tid - 32) / 5].prb_mask[(tid - 32) % 5];
+  __syncthreads();
+  build_prb_list(rbm, nprb_grid, 0, prb_of, &nprb_s, tid, nt);
+  __syncthreads();
+  const int nprb = nprb_s;
+  unsigned  res_re[4] = {0, 0, 0, 0}, res_sy[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (r < nres) {
+      res_re[r] = jp->reserved[r].re_mask;
+      res_sy[r] = jp->reserved[r].symbols;
+    }
+  const int prefix = info[sy]; // elements per layer of the transmission in earlier symbols
+  for (int i = tid; i < nprb; i += nt) {
+    const int rb = prb_of[i];
+    unsigned  ex = (((dmrs_syms >> sy) & 1u) && rb >= bwp0 && rb < bwp1) ? dmask : 0u;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (r < nres && ((res_sy[r] >> sy) & 1u) && ((resm[r][rb >> 6] >> (rb & 63)) & 1ull))
+        ex |= res_re[r];
+    keep_of[i] = (uint16_t)(~ex & 0xfffu);
+  }
+  __syncthreads();
+  // exclusive scan of the per-PRB counts of this symbol (<= 275 entries: one wavefront, 5 entries per lane)
+  if (tid < 64) {
+    int c[5], sum = 0;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const int i = tid * 5 + q;
+      c[q]        = (i < nprb) ? __popc((unsigned)keep_of[i]) : 0;
+      sum += c[q];
+    }
+    int inc = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(inc, o);
+      inc += (tid >= o) ? v : 0;
+    }
+    int run = inc - sum;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const int i = tid * 5 + q;
+      if (i < nprb)
+        off_of[i] = (uint16_t)run;
+      run += c[q];
+    }
+    if (tid == 63)
+      n_re_s = inc;
+  }
+  __syncthreads();
+  if (n_re_s == 0)
+    return;
+  const int       mod = jp->mod, L = lj->nof_layers;
+  const uint32_t* seq = seq_base + (size_t)blockIdx.x * stride;
+  const float     scaling = jp->scaling;
+  const bool      scale   = isnormal(scaling);
+  const uint8_t*  cw      = cw_base + jp->cw_offset;
+  const int       nsc     = nprb_grid * 12;
+  float2*         g[4];
+#pragma unroll
+  for (int ly = 0; ly < 4; ++ly)
+    g[ly] = grid + jp->grid_offset + ((size_t)lj->ports[ly < L ? ly : 0] * 14 + sy) * nsc;
+  // Bit offsets stay in 32 bits: the longest codeword is 4 layers x 275 PRB x 12 x 14 symbols x 8 bits = 1 478 400 bits.
+  if ((mod == 4 || mod == 8) && (((uintptr_t)(cw + (size_t)prefix * L * mod)) & 3u) == 0) {
+#define MIPHY_LAYERS_FAST(LL, MOD) pdsch_layers_fast<LL, MOD>(tid, nprb, prefix, prb_of, keep_of, off_of, seq, cw, g, scale, scaling)
+    switch (L * 16 + mod) {
+      case 1 * 16 + 4: MIPHY_LAYERS_FAST(1, 4); break;
+      case 2 * 16 + 4: MIPHY_LAYERS_FAST(2, 4); break;
+      case 3 * 16 + 4: MIPHY_LAYERS_FAST(3, 4); break;
+      case 4 * 16 + 4: MIPHY_LAYERS_FAST(4, 4); break;
+      case 1 * 16 + 8: MIPHY_LAYERS_FAST(1, 8); break;
+      case 2 * 16 + 8: MIPHY_LAYERS_FAST(2, 8); break;
+      case 3 * 16 + 8: MIPHY_LAYERS_FAST(3, 8); break;
+      default: MIPHY_LAYERS_FAST(4, 8); break;
+    }
+#undef MIPHY_LAYERS_FAST
+    return;
+  }
+  const uint32_t mask = (1u << mod) - 1u;
+  for (int idx = tid; idx < nprb * 12; idx += nt) {
+    const int      i = idx / 12, k = idx - i * 12;
+    const unsigned keep = keep_of[i];
+    if (!((keep >> k) & 1u))
+      continue;
+    const int      j  = off_of[i] + __popc(keep & ((1u << k) - 1u)); // RE index within the symbol
+    const uint32_t d0 = ((uint32_t)prefix + (uint32_t)j) * (uint32_t)L; // first codeword symbol of the element
+    const uint32_t bi = d0 * (uint32_t)mod;                             // its first bit: position in the transmission's scrambling sequence
+    const uint64_t two = (uint64_t)seq[bi >> 5] | ((uint64_t)seq[(bi >> 5) + 1] << 32);
+    const uint32_t cb  = (uint32_t)(two >> (bi & 31)); // scrambling bits of the element's L symbols, bit t = t-th bit
+    const uint8_t* cp  = cw + (size_t)bi;
+    const int      col = prb_of[i] * 12 + k;
+#pragma unroll
+    for (int ly = 0; ly < 4; ++ly) {
+      if (ly >= L)
+        break;
+      uint32_t raw = 0;
+      for (int t = 0; t < mod; ++t)
+        raw |= (uint32_t)(cp[ly * mod + t] & 1u) << t;
+      float2 x = map_symbol(mod, (raw ^ (cb >> (ly * mod))) & mask, d0 + (uint32_t)ly); // pi/2-BPSK turns with the parity of the codeword symbol
+      if (scale) {
+        x.x = x.x * scaling;
+        x.y = x.y * scaling;
+      }
+      g[ly][col] = x;
+    }
+  }
+}
+
 uint32_t host_nof_re(const miphy_pdsch_mod_job& j)
 {
   unsigned dm = 0;
@@ -622,6 +936,83 @@ int miphy_pdsch_modulate_launch(const miphy_pdsch_mod_job* d_jobs, uint32_t n, c
   int* prefix = reinterpret_cast<int*>(static_cast<uint8_t*>(seq) + (size_t)n * PDSCH_SEQ_STRIDE * sizeof(uint32_t));
   hipLaunchKernelGGL(pdsch_seq_kernel, dim3(n), dim3(512), 0, s, d_jobs, gt, (uint32_t*)seq, prefix);
   hipLaunchKernelGGL(pdsch_mod_kernel, dim3(n, 14), dim3(256), 0, s, d_jobs, gt, codewords, (float2*)grid, (const uint32_t*)seq, (const int*)prefix);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- PDSCH modulator, 1..4 layers
+extern "C" uint32_t miphy_pdsch_mod_layers_nof_re(const miphy_pdsch_mod_layers_job* j)
+{
+  if (!j || j->nof_layers < 1 || j->nof_layers > 4)
+    return 0;
+  return miphy_pdsch_mod_nof_re(&j->base);
+}
+
+int miphy_pdsch_mod_layers_check(const char* who, const char* what, uint32_t i, const miphy_pdsch_mod_layers_job& lj, uint32_t nof_re)
+{
+  const miphy_pdsch_mod_job& j = lj.base;
+  const unsigned             L = lj.nof_layers;
+  MIPHY_REQUIRE(L >= 1 && L <= 4, "%s: %s %u: invalid number of layers %u (one codeword: 1..4)", who, what, i, L);
+  for (unsigned a = 0; a < L; ++a) {
+    MIPHY_REQUIRE(lj.ports[a] < 16, "%s: %s %u: invalid port %u of layer %u", who, what, i, (unsigned)lj.ports[a], a);
+    for (unsigned b = 0; b < a; ++b)
+      MIPHY_REQUIRE(lj.ports[a] != lj.ports[b], "%s: %s %u: layers %u and %u share port %u", who, what, i, b, a, (unsigned)lj.ports[a]);
+  }
+  MIPHY_REQUIRE(j.mod == 1 || j.mod == 2 || j.mod == 4 || j.mod == 6 || j.mod == 8, "%s: %s %u: invalid modulation order %u", who, what, i, j.mod);
+  MIPHY_REQUIRE(j.nof_symbols >= 1 && j.start_symbol + j.nof_symbols <= 14, "%s: %s %u: invalid time allocation", who, what, i);
+  MIPHY_REQUIRE(j.dmrs_type == 1 || j.dmrs_type == 2, "%s: %s %u: invalid DM-RS type", who, what, i);
+  MIPHY_REQUIRE(j.nof_cdm_groups_without_data >= 1 && j.nof_cdm_groups_without_data <= (j.dmrs_type == 1 ? 2 : 3),
+                "%s: %s %u: invalid number of CDM groups without data", who, what, i);
+  MIPHY_REQUIRE(j.grid_nof_prb >= 1 && j.grid_nof_prb <= 275 && j.bwp_start_rb + j.bwp_size_rb <= 275, "%s: %s %u: invalid grid / BWP", who, what, i);
+  MIPHY_REQUIRE(j.nof_reserved <= 4, "%s: %s %u: at most 4 reserved RE patterns (re_pattern_list::MAX_RE_PATTERN)", who, what, i);
+  MIPHY_REQUIRE(j.n_id < 1024 && j.rnti < 65536, "%s: %s %u: invalid scrambling identifiers", who, what, i);
+  // every element of every layer must be mapped
+  if (nof_re == 0)
+    nof_re = host_nof_re(j);
+  MIPHY_REQUIRE(j.nof_bits == nof_re * L * j.mod, "%s: %s %u: codeword of %u bits, the allocation holds %u on %u layers", who, what, i, j.nof_bits,
+                nof_re * L * j.mod, L);
+  return MIPHY_OK;
+}
+
+extern "C" int miphy_pdsch_modulate_layers_batch(miphy_ctx* ctx, const miphy_pdsch_mod_layers_job* jobs, int jobs_on_device, uint32_t n, const uint8_t* codewords,
+                                                 float* grid, void* stream)
+{
+  MIPHY_REQUIRE(ctx && jobs && codewords && grid, "miphy_pdsch_modulate_layers_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "pdsch_modulate_layers: batch too large (max 65535 transmissions per call)");
+  uint32_t max_layers = 4; // device-resident jobs: the kernels validate them, the scratch is sized for the most they may ask
+  if (!jobs_on_device) {
+    max_layers = 1;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (int rc = miphy_pdsch_mod_layers_check("pdsch_modulate_layers", "job", i, jobs[i], 0))
+        return rc;
+      max_layers = jobs[i].nof_layers > max_layers ? jobs[i].nof_layers : max_layers;
+    }
+  }
+  return miphy_pdsch_modulate_layers_enqueue(ctx, jobs, jobs_on_device, n, max_layers, codewords, grid, (hipStream_t)stream);
+}
+
+int miphy_pdsch_modulate_layers_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_layers_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
+                                        const uint8_t* codewords, float* grid, hipStream_t s)
+{
+  const gold_tables* gt = nullptr;
+  int                rc = miphy_get_gold_tables(ctx, &gt);
+  if (rc)
+    return rc;
+  const void* d_jobs = nullptr;
+  if ((rc = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pdsch_mod_layers_job) * (size_t)n, s, &d_jobs)))
+    return rc;
+  // scratch: the scrambling sequences (a transmission on L layers has L times the bits of one layer: the stride grows with the batch's
+  // largest L), then PDSCH_LAYERS_INFO ints per transmission
+  const uint32_t stride = max_layers * (uint32_t)PDSCH_SEQ_STRIDE;
+  void*          seq    = nullptr;
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, (size_t)n * stride * sizeof(uint32_t) + (size_t)n * PDSCH_LAYERS_INFO * sizeof(int), &seq)))
+    return rc;
+  int* info = reinterpret_cast<int*>(static_cast<uint8_t*>(seq) + (size_t)n * stride * sizeof(uint32_t));
+  hipLaunchKernelGGL(pdsch_seq_layers_kernel, dim3(n, 2 * max_layers), dim3(512), 0, s, (const miphy_pdsch_mod_layers_job*)d_jobs, gt, (uint32_t*)seq, info, stride);
+  hipLaunchKernelGGL(pdsch_mod_layers_kernel, dim3(n, 14), dim3(256), 0, s, (const miphy_pdsch_mod_layers_job*)d_jobs, codewords, (float2*)grid,
+                     (const uint32_t*)seq, (const int*)info, stride);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }

@@ -100,6 +100,76 @@ extern "C" int miphy_pdsch_process_batch(miphy_ctx* ctx, const miphy_pdsch_pdu* 
   return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s);
 }
 
+// ---- one codeword on 1..4 layers: the same composition with the encoder's nof_layers = L and nof_ch_symbols = REs x L, the layered modulator
+// and the DM-RS on L ports. Every PDU is checked before the encoder is enqueued.
+extern "C" uint32_t miphy_pdsch_layers_pdu_nof_re(const miphy_pdsch_layers_pdu* pdu)
+{
+  if (!pdu || pdu->nof_layers < 1 || pdu->nof_layers > 4)
+    return 0;
+  return miphy_pdsch_pdu_nof_re(&pdu->base);
+}
+
+extern "C" int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsch_layers_pdu* pdus, uint32_t n, const uint8_t* tb_in, float* grid, void* stream)
+{
+  MIPHY_REQUIRE(ctx && pdus && tb_in && grid, "miphy_pdsch_process_layers_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "pdsch_process_layers: at most 65535 PDUs per call");
+  hipStream_t                             s = (hipStream_t)stream;
+  std::vector<miphy_pdsch_pdu>            base(n);
+  std::vector<miphy_pdsch_tb_desc>        tb;
+  std::vector<miphy_pdsch_mod_job>        mj;
+  std::vector<miphy_dmrs_pdsch_job>       dj;
+  std::vector<miphy_pdsch_mod_layers_job> lj(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    MIPHY_REQUIRE(pdus[i].nof_layers >= 1 && pdus[i].nof_layers <= 4, "pdsch_process_layers: PDU %u: invalid number of layers %u (one codeword: 1..4)", i,
+                  (unsigned)pdus[i].nof_layers);
+    base[i] = pdus[i].base;
+  }
+  size_t cw_bytes = 0; // (recounted below: a codeword on L layers is L times as long)
+  int    rc       = derive_pdsch_jobs(base.data(), n, tb, mj, dj, cw_bytes);
+  if (rc)
+    return rc;
+  cw_bytes            = 0;
+  uint32_t max_layers = 1;
+  for (uint32_t i = 0; i < n; ++i) {
+    const miphy_pdsch_layers_pdu& p   = pdus[i];
+    const uint32_t                L   = p.nof_layers, nre = tb[i].nof_ch_symbols; // REs per layer
+    MIPHY_REQUIRE(!p.base.ref_point_prb0 || p.base.bwp_start_rb < p.base.grid_nof_prb, "pdsch_process_layers: PDU %u: reference point outside the grid", i);
+    lj[i]               = {};
+    lj[i].base          = mj[i];
+    lj[i].base.nof_bits = nre * L * p.base.mod;
+    lj[i].base.cw_offset = cw_bytes;
+    lj[i].nof_layers    = (uint8_t)L;
+    for (uint32_t ly = 0; ly < 4; ++ly)
+      lj[i].ports[ly] = p.ports[ly];
+    if ((rc = miphy_pdsch_mod_layers_check("pdsch_process_layers", "PDU", i, lj[i], nre)))
+      return rc;
+    max_layers = L > max_layers ? L : max_layers;
+    // what the encoder accepts (sch.hip, ldpc_segmenter_impl.cpp:104-141): at most 52 codeblocks, none of them empty
+    const uint64_t tbs = (uint64_t)p.base.tb_bytes * 8, B = tbs + (tbs <= 3824 ? 16 : 24), Kcb = p.base.bg == 1 ? 8448 : 3840;
+    const uint64_t ncb = B <= Kcb ? 1 : (B + Kcb - 24 - 1) / (Kcb - 24);
+    MIPHY_REQUIRE(p.base.tb_bytes > 0 && ncb <= 52, "pdsch_process_layers: PDU %u: transport block of %u bytes outside what the encoder accepts (1 .. %u bytes on base graph %u)",
+                  i, p.base.tb_bytes, p.base.bg == 1 ? 54753u : 24801u, (unsigned)p.base.bg);
+    MIPHY_REQUIRE(p.base.rv <= 3, "pdsch_process_layers: PDU %u: invalid redundancy version", i);
+    MIPHY_REQUIRE(nre >= ncb, "pdsch_process_layers: PDU %u: %u REs per layer cannot carry %u codeblocks", i, nre, (unsigned)ncb);
+    tb[i].nof_layers = (uint8_t)L, tb[i].nof_ch_symbols = nre * L, tb[i].codeword_offset = cw_bytes;
+    dj[i].nof_ports = (uint8_t)L;
+    for (uint32_t ly = 0; ly < L; ++ly)
+      dj[i].ports[ly] = p.ports[ly];
+    cw_bytes += ((size_t)lj[i].base.nof_bits + 15u) & ~(size_t)15u;
+  }
+  void* work = nullptr; // codewords (one bit per byte) in a workspace of the context
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, cw_bytes + 64, &work)))
+    return rc;
+  uint8_t* d_cw = static_cast<uint8_t*>(work);
+  if ((rc = miphy_pdsch_encode_batch(ctx, tb.data(), n, tb_in, d_cw, s)))
+    return rc;
+  if ((rc = miphy_pdsch_modulate_layers_enqueue(ctx, lj.data(), 0, n, max_layers, d_cw, grid, s))) // (checked above)
+    return rc;
+  return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s);
+}
+
 // ---- prepared form: PDU validation, segmentation, every descriptor upload and the scratch happen once; a run is the seven launches of the
 // chain, nothing staged or allocated, no host synchronisation -- for allocations that repeat slot after slot (and for batches whose descriptors exceed the staging ring,
 // where the per-call form has to wait for its upload).

@@ -93,6 +93,12 @@ def lib():
         l.miphy_pdsch_pdu_nof_re.argtypes = [C.c_void_p]
         l.miphy_pdsch_pdu_nof_re.restype = C.c_uint32
         l.miphy_pdsch_process_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.miphy_pdsch_modulate_layers_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.miphy_pdsch_mod_layers_nof_re.argtypes = [C.c_void_p]
+        l.miphy_pdsch_mod_layers_nof_re.restype = C.c_uint32
+        l.miphy_pdsch_layers_pdu_nof_re.argtypes = [C.c_void_p]
+        l.miphy_pdsch_layers_pdu_nof_re.restype = C.c_uint32
+        l.miphy_pdsch_process_layers_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         l.miphy_ofh_iq_decompress_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         l.miphy_ofh_iq_compress_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         l.miphy_pdcch_process_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -227,6 +233,17 @@ def pdsch_mod_nof_re(job):
     return int(lib().miphy_pdsch_mod_nof_re(a.ctypes.data_as(C.c_void_p)))
 
 
+# Mirrors miphy_pdsch_mod_layers_job: one codeword on 1..4 layers, layer ly on grid port ports[ly].
+PdschModLayersJob = np.dtype([("base", PdschModJob), ("nof_layers", np.uint8), ("ports", np.uint8, 4), ("pad", np.uint8, 3)], align=True)
+assert PdschModLayersJob.itemsize == 288 and PdschModLayersJob.fields["nof_layers"][1] == 280 and PdschModLayersJob.fields["ports"][1] == 281
+
+
+def pdsch_mod_layers_nof_re(job):
+    """Data REs per layer of one PdschModLayersJob record (host computation in the library); 0 on an invalid job."""
+    a = np.ascontiguousarray(np.asarray(job, dtype=PdschModLayersJob).reshape(1))
+    return int(lib().miphy_pdsch_mod_layers_nof_re(a.ctypes.data_as(C.c_void_p)))
+
+
 # Mirrors miphy_ofh_iq_job.
 OfhIqJob = np.dtype([("payload_offset", np.uint64), ("grid_offset", np.uint64), ("nof_prb", np.uint32), ("data_width", np.uint16),
                      ("compression", np.uint16)], align=True)
@@ -248,6 +265,17 @@ def pdsch_pdu_nof_re(pdu):
     """Data REs of one PdschPdu record (pdsch_processor_impl::compute_nof_data_re; host computation in the library)."""
     a = np.ascontiguousarray(np.asarray(pdu, dtype=PdschPdu).reshape(1))
     return int(lib().miphy_pdsch_pdu_nof_re(a.ctypes.data_as(C.c_void_p)))
+
+
+# Mirrors miphy_pdsch_layers_pdu.
+PdschLayersPdu = np.dtype([("base", PdschPdu), ("nof_layers", np.uint8), ("ports", np.uint8, 4), ("pad", np.uint8, 3)], align=True)
+assert PdschLayersPdu.itemsize == 312 and PdschLayersPdu.fields["nof_layers"][1] == 304 and PdschLayersPdu.fields["ports"][1] == 305
+
+
+def pdsch_layers_pdu_nof_re(pdu):
+    """Data REs per layer of one PdschLayersPdu record (host computation in the library); 0 on an invalid PDU."""
+    a = np.ascontiguousarray(np.asarray(pdu, dtype=PdschLayersPdu).reshape(1))
+    return int(lib().miphy_pdsch_layers_pdu_nof_re(a.ctypes.data_as(C.c_void_p)))
 
 
 # Mirrors miphy_csi_rs_job.
@@ -586,6 +614,17 @@ class Context:
         assert isinstance(pdus, np.ndarray) and pdus.dtype == PdschPdu
         pdus = np.ascontiguousarray(pdus)
         check(lib().miphy_pdsch_process_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, _dptr(tb_in), _dptr(grid), _stream_ptr(stream)))
+
+    def pdsch_modulate_layers_batch(self, jobs, codewords, grid, stream=None):
+        """One codeword on 1..4 layers (TS 38.211 7.3.1.3), layer ly on grid port ports[ly]; jobs on the host or on the device."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PdschModLayersJob)
+        check(lib().miphy_pdsch_modulate_layers_batch(self.h, ptr, on_dev, n, _dptr(codewords), _dptr(grid), _stream_ptr(stream)))
+
+    def pdsch_process_layers_batch(self, pdus, tb_in, grid, stream=None):
+        """pdsch_process_batch for PDUs of one codeword on 1..4 layers (host descriptors): transport blocks -> REs of the named grid ports."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PdschLayersPdu
+        pdus = np.ascontiguousarray(pdus)
+        check(lib().miphy_pdsch_process_layers_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, _dptr(tb_in), _dptr(grid), _stream_ptr(stream)))
 
     def csi_rs_map_batch(self, jobs, grid, stream=None):
         jobs, n, ptr, on_dev = self._descs(jobs, CsiRsJob)
