@@ -119,9 +119,13 @@ void     miphy_ldpc_decode_plan_destroy(miphy_ldpc_decode_plan* plan);
  * memory wherever that buys residency), 5 = class-sorted launches with the latency form of the packed kernel (two parts) on every class (A-B measurement only),
  * 6 = automatic choice with the latency form in two parts instead of four. Adding 0x100 keeps ALL messages of a GMSG launch in global memory (A-B of the
  * split between LDS and global memory). Adding 0x200 keeps every launch computing its soft-bit addresses (no launch reads them from
- * the table of miphy_ldpc_address_table; A-B of that instance). All kernels produce identical results. Prepared plans keep the choice in force when they were
+ * the table of miphy_ldpc_address_table; A-B of that instance). Adding 0x400 keeps every launch on the instances of the packed kernel
+ * that run every layer visit (none takes the instance that leaves out the visits of layers whose rows are saturated; A-B of that skip). All kernels produce identical results. Prepared plans keep the choice in force when they were
  * created: the knob applies to plans created after it is set (and to every per-call decode). */
 void miphy_debug_force_ldpc_kernel(int mode);
+/* Launches since the last reset of the packed kernel's instance whose wavefronts leave out the layer visits of saturated rows (taken for
+ * launches whose codeblocks run all their iterations, throughput form, messages in LDS): */
+unsigned miphy_debug_ldpc_row_skip_launches(int reset);
 /* Which decoder kernels have been launched since the last reset (tests assert that a forced choice really ran): */
 #define MIPHY_LDPC_KERNEL_SCALAR 1u /* one check row per lane */
 #define MIPHY_LDPC_KERNEL_PACKED 2u /* two check rows per lane, one codeblock per workgroup */

@@ -25,16 +25,19 @@ struct ldpc_knob_values {
   bool hybrid_msgs;   // false (mode | MIPHY_LDPC_FORCE_ALL_GMSG): all messages of a GMSG launch in global memory
   int  class_streams; // streams the launch classes of a call are spread over (miphy_debug_set_ldpc_class_streams)
   bool adr_tables;    // false (mode | MIPHY_LDPC_FORCE_NO_ADR_TABLE): every launch computes its soft-bit addresses
+  bool row_skip;      // false (mode | MIPHY_LDPC_FORCE_NO_ROW_SKIP): every wavefront of the packed kernel runs every layer visit
 };
 struct {
   std::atomic<int>  force{MIPHY_LDPC_FORCE_AUTO};
   std::atomic<bool> hybrid_msgs{true};
   std::atomic<int>  class_streams{1 + MIPHY_NOF_SIDE_STREAMS};
   std::atomic<bool> adr_tables{true};
-  ldpc_knob_values  snapshot() const { return {force.load(), hybrid_msgs.load(), class_streams.load(), adr_tables.load()}; }
+  std::atomic<bool> row_skip{true};
+  ldpc_knob_values  snapshot() const { return {force.load(), hybrid_msgs.load(), class_streams.load(), adr_tables.load(), row_skip.load()}; }
 } g_knobs;
 std::atomic<unsigned> g_kernels_used{0}; // MIPHY_LDPC_KERNEL_* of every decoder launch since the last reset (miphy_debug_ldpc_kernels_used)
 std::atomic<unsigned> g_adr_table_launches{0}; // launches of the address-table instance since the last reset
+std::atomic<unsigned> g_row_skip_launches{0};  // launches of an instance that leaves out the visits of saturated rows
 } // namespace
 
 extern "C" void miphy_debug_force_ldpc_kernel(int mode)
@@ -42,6 +45,7 @@ extern "C" void miphy_debug_force_ldpc_kernel(int mode)
   g_knobs.force       = mode & MIPHY_LDPC_FORCE_MODE_MASK;
   g_knobs.hybrid_msgs = !(mode & MIPHY_LDPC_FORCE_ALL_GMSG);
   g_knobs.adr_tables  = !(mode & MIPHY_LDPC_FORCE_NO_ADR_TABLE);
+  g_knobs.row_skip    = !(mode & MIPHY_LDPC_FORCE_NO_ROW_SKIP);
 }
 
 extern "C" void miphy_debug_set_ldpc_class_streams(int n)
@@ -52,6 +56,11 @@ extern "C" void miphy_debug_set_ldpc_class_streams(int n)
 extern "C" unsigned miphy_debug_ldpc_kernels_used(int reset)
 {
   return reset ? g_kernels_used.exchange(0) : g_kernels_used.load();
+}
+
+extern "C" unsigned miphy_debug_ldpc_row_skip_launches(int reset)
+{
+  return reset ? g_row_skip_launches.exchange(0) : g_row_skip_launches.load();
 }
 
 extern "C" unsigned miphy_debug_ldpc_address_table_launches(int reset)
@@ -122,6 +131,7 @@ void miphy_ldpc_build_classes(const miphy_ldpc_dec_desc* descs, uint32_t n, cons
       c.lay                        = std::max<uint8_t>(c.lay, (uint8_t)(it[k].key & 63));
       c.max_Z                      = std::max<uint16_t>(c.max_Z, d.Z);
       c.min_Z                      = std::min<uint16_t>(c.min_Z, d.Z);
+      c.runs_all_iterations |= (d.crc_poly == MIPHY_CRC_NONE || (d.flags & 1u)) ? 1 : 0;
       C.order[k]                   = it[k].idx;
       C.identity &= it[k].idx == k;
     }
@@ -194,6 +204,12 @@ void pk_class_geometry(const miphy_ctx* ctx, const ldpc_knob_values& k, bool fus
   for (int m = 0; m < c.lay; ++m)
     one_degree &= ctx->h_tables->row_start[c.bgi][m + 1] - ctx->h_tables->row_start[c.bgi][m] == MIPHY_LDPC_ADR_TABLE_DEGREE;
   q.atab = k.adr_tables && fused && !gm && q.parts == 1 && one_degree && c.min_Z >= 128;
+  // The instance that leaves out the visits of saturated rows (ldpc_decode_pk.hip, RSKIP) where the launch can profit: the throughput form
+  // (the parts of the latency form share a layer's rows), codeblocks that run all their iterations (one that stops at its first good
+  // checksum leaves before its rows saturate), messages in LDS (the classes with messages in global memory are the low rates: most of their
+  // layers hold a parity column with a single check, whose soft bit stays finite unless the channel value itself is clipped). The layer
+  // loop of that instance compiles to slower visits, so every other launch keeps the instance without it.
+  q.row_skip = k.row_skip && q.parts == 1 && !gm && c.runs_all_iterations;
 }
 
 void plan_classes(const miphy_ctx* ctx, const miphy_ldpc_classes& C, bool fuse, const ldpc_knob_values& k, miphy_ldpc_launches& T)
@@ -305,7 +321,7 @@ void plan_one_launch(const miphy_ctx* ctx, const ldpc_knob_values& k, const batc
   L.c.count            = n;
   L.nodes = nodes_all, L.parts = 1;
   if (use_pk) {
-    L.used    = MIPHY_LDPC_KERNEL_PACKED | (pk_gmsg ? MIPHY_LDPC_KERNEL_GMSG : 0u);
+    L.used    = MIPHY_LDPC_KERNEL_PACKED | (pk_gmsg ? MIPHY_LDPC_KERNEL_GMSG : 0u); // (row_skip stays false: whether these codeblocks stop early is not visible here)
     L.threads = pk_threads, L.lds = pk_lds, L.gmsg_pairs = pk_gmsg ? pk_pairs : 0;
     L.grid       = miphy_ldpc_pk_grid(ctx, n, pk_threads, pk_lds, false);
     L.gmsg_bytes = pk_gmsg ? (size_t)L.grid * pk_waves * (size_t)pk_pairs * 256 : 0;
@@ -355,6 +371,7 @@ int enqueue_launches(miphy_ctx* ctx, const miphy_ldpc_launches& T, const miphy_l
       return rc;
     g_kernels_used.fetch_or(L.used);
     g_adr_table_launches.fetch_add(L.adr_by_z ? 1u : 0u);
+    g_row_skip_launches.fetch_add((L.row_skip && (L.used & MIPHY_LDPC_KERNEL_PACKED)) ? 1u : 0u);
   }
   return MIPHY_OK;
 }

@@ -191,8 +191,22 @@ __device__ __forceinline__ int pk_fused_image_out(const int8_t* __restrict__ sof
 // form of launches whose reachable layers all have PK_ATAB_DEGREE edges. `adr_by_z[Z / 16]` is the table of lifting size Z,
 // [layer][quad][lane of the workgroup]. The quads of the first layer visited are requested in front of the load phase, every other
 // visit's by the visit before it (across the iteration's CRC and the layer barrier: 19 registers, the raw soft bits are dead there).
+//
+// Saturated rows (RSKIP instances of the throughput forms; every other instance runs every visit with the row update as it was -- the launch
+// planner takes RSKIP where a launch can profit, ldpc_decode.hip; the argument is DESIGN.md section 4): a general row update reports per lane that every soft
+// bit it read was infinite (update_rows_pk). Such rows are frozen: every later update of them rewrites each soft bit to +-127 with the sign
+// it has and needs no message of theirs, so no hard bit, checksum or iteration count can come out of it differently. A wavefront whose
+// row-owning lanes ALL report it at a visit of layer m sets bit m of a mask of its own (scalar registers, cleared per codeblock) and from
+// then on leaves out the body of its visits of layer m: no request, no arithmetic, no message or soft-bit traffic -- straight to the
+// layer's barrier. Nothing is shared between wavefronts and no wavefront leaves a loop early: each executes exactly the barriers it would
+// without the mask.
+// ATAB and the mask: a visit's addresses are requested by the visit that runs before it, so a visit that runs requests those of the NEXT
+// VISIT THAT RUNS: the next layer in turn whose bit is clear (layer m + 1, or layer 0 behind the last one, while no bit is set). A visit
+// that is left out touches neither the quads nor the table. A layer's bit changes only at its own visits, and the layers between two
+// visits that run have their bits set for good, so the layer named at the request is the one whose visit consumes the quads: no visit
+// ever splits the addresses of another layer. (Once every bit is set the last request names layer 0 and nothing consumes it.)
 constexpr int PK_ATAB_DEGREE = MIPHY_LDPC_ADR_TABLE_DEGREE, PK_ATAB_QUADS = (PK_ATAB_DEGREE + 3) / 4;
-template <bool FUSED, bool GMSG, int PARTS = 1, bool ATAB = false>
+template <bool FUSED, bool GMSG, int PARTS = 1, bool ATAB = false, bool RSKIP = false>
 __global__ void __launch_bounds__(192 * PARTS, PARTS > 1 ? LDPC_PK_MIN_WAVES_SPLIT : (FUSED ? LDPC_PK_MIN_WAVES_FUSED : LDPC_PK_MIN_WAVES_PLAIN))
 ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
                       const miphy_graph_tables* __restrict__ tab,
@@ -219,6 +233,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   static_assert(PARTS == 1 || PARTS == 2 || PARTS == 4, "parts of the latency form");
   static_assert(!(SPLIT && GMSG), "the latency form keeps its messages in LDS");
   static_assert(!ATAB || (FUSED && !GMSG && !SPLIT), "address tables: the throughput form that dematches, messages in LDS");
+  static_assert(!(RSKIP && (SPLIT || GMSG)), "visits are left out by the throughput forms with their messages in LDS");
   const int nth  = nt / PARTS;                   // threads that own rows: the whole workgroup, or each part of it
   // (wave-uniform by construction -- nth is a multiple of 64 --, and said so: the part selects the edges of a layer, which must stay scalar loads)
   const int part = SPLIT ? __builtin_amdgcn_readfirstlane((tid >= nth) + (PARTS > 2 ? (tid >= 2 * nth) + (tid >= 3 * nth) : 0)) : 0;
@@ -431,6 +446,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   // soft bit changes (update_rows_pk_zero, ldpc_pk_device.h). Its messages are first written in iteration 1, by the FIRST instance.
   if (SPLIT)
     load_part_edges<PARTS>(pe, edges_g, (uint32_t)__builtin_amdgcn_readlane((int)lay_info, 1), part); // the first layer visited
+  [[maybe_unused]] uint64_t sat_layers = 0; // bit m: this wavefront's rows of layer m are saturated (wave-uniform; bgM <= 46 layers)
   for (int it = 0; it < max_iter; ++it) {
     for (int m = (it == 0) ? 1 : 0; m < nof_layers; ++m) {
       const uint32_t  li    = (uint32_t)__builtin_amdgcn_readlane((int)lay_info, m);
@@ -448,17 +464,38 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
         else
           update_rows_pk_split<false, PARTS>(pe, part, soft, cl, lr, Hv, Zv, lr < H, xch, nth, next);
         pe = pn;
-      } else if (ATAB) {
-        if (tid < H)
-          update_rows_pk_visit_tab<PK_ATAB_DEGREE>(it, m, soft, c2v_lane + 64 * (li >> 16), anx,
-                                                   pk_adr_row{atab.rsrc, (uint32_t)__builtin_amdgcn_readfirstlane((m + 1 < nof_layers) ? m + 1 : 0) * alayer},
-                                                   16u * (uint32_t)tid, astride);
-      } else if (tid < H) { // (<FUSED>: the address form of pk_edge_addresses that adds the column offset in the split pays in the 168-register instances only)
-        if (GMSG && (int)(li >> 16) >= pairs_lds) { // this layer's messages live in global memory (separate code: the address space is part of the instruction)
-          update_rows_pk_visit<FUSED>(it, m, d, soft, c2v_glob + 64 * (li >> 16), edges, tid, Hv, Zv);
-        } else {
-          update_rows_pk_visit<FUSED>(it, m, d, soft, c2v_lane + 64 * (li >> 16), edges, tid, Hv, Zv);
+      } else if constexpr (!RSKIP) {
+        if (ATAB) {
+          if (tid < H)
+            update_rows_pk_visit_tab<PK_ATAB_DEGREE>(it, m, soft, c2v_lane + 64 * (li >> 16), anx,
+                                                     pk_adr_row{atab.rsrc, (uint32_t)__builtin_amdgcn_readfirstlane((m + 1 < nof_layers) ? m + 1 : 0) * alayer},
+                                                     16u * (uint32_t)tid, astride);
+        } else if (tid < H) { // (<FUSED>: the address form of pk_edge_addresses that adds the column offset in the split pays in the 168-register instances only)
+          if (GMSG && (int)(li >> 16) >= pairs_lds) { // this layer's messages live in global memory (separate code: the address space is part of the instruction)
+            update_rows_pk_visit<FUSED>(it, m, d, soft, c2v_glob + 64 * (li >> 16), edges, tid, Hv, Zv);
+          } else {
+            update_rows_pk_visit<FUSED>(it, m, d, soft, c2v_lane + 64 * (li >> 16), edges, tid, Hv, Zv);
+          }
         }
+      } else if (!((sat_layers >> m) & 1u)) { // RSKIP (a set bit: saturated rows, the visit changes nothing anybody reads)
+        bool all_inf = false; // this lane's rows read infinite soft bits only
+        if (ATAB) {
+          // the addresses of the next visit that RUNS: the next layer in turn whose bit is clear (the next one, and layer 0 behind the last, while no bit is set)
+          const uint64_t live = ~sat_layers & (((uint64_t)1 << nof_layers) - 1u), above = live & ~(((uint64_t)2 << m) - 1u);
+          const int      mn   = __builtin_amdgcn_readfirstlane(above ? __builtin_ctzll(above) : __builtin_ctzll(live));
+          if (tid < H)
+            all_inf = update_rows_pk_visit_tab<PK_ATAB_DEGREE, true>(it, m, soft, c2v_lane + 64 * (li >> 16), anx, pk_adr_row{atab.rsrc, (uint32_t)mn * alayer},
+                                                                     16u * (uint32_t)tid, astride);
+        } else if (tid < H) {
+          if (GMSG && (int)(li >> 16) >= pairs_lds) {
+            all_inf = update_rows_pk_visit<FUSED, true>(it, m, d, soft, c2v_glob + 64 * (li >> 16), edges, tid, Hv, Zv);
+          } else {
+            all_inf = update_rows_pk_visit<FUSED, true>(it, m, d, soft, c2v_lane + 64 * (li >> 16), edges, tid, Hv, Zv);
+          }
+        }
+        // one ballot over the lanes that own rows (a lane of a partial last wavefront that owns none does not count against it)
+        if (__builtin_amdgcn_ballot_w64(tid < H && !all_inf) == 0)
+          sat_layers |= (uint64_t)1 << m;
       }
       PROF_T(p_l1);
       __syncthreads();
@@ -578,7 +615,11 @@ int miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy
   MIPHY_REQUIRE(L.threads <= 1024, "ldpc_decode: workgroup of %d threads", L.threads);
   const bool  atab = L.adr_by_z != nullptr;
   MIPHY_REQUIRE(!atab || (fused && !gm && L.parts == 1), "ldpc_decode: address tables with a launch form that has no such instance");
-  const void* kern = atab ? (const void*)ldpc_decode_pk_kernel<true, false, 1, true> : L.parts == 4 ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 4> : (const void*)ldpc_decode_pk_kernel<false, false, 4>)
+  const bool  rs   = L.row_skip;
+  MIPHY_REQUIRE(!rs || (L.parts == 1 && !gm), "ldpc_decode: saturated rows are left out by the throughput forms with their messages in LDS only");
+  const void* kern = rs ? (atab ? (const void*)ldpc_decode_pk_kernel<true, false, 1, true, true>
+                                : fused ? (const void*)ldpc_decode_pk_kernel<true, false, 1, false, true> : (const void*)ldpc_decode_pk_kernel<false, false, 1, false, true>)
+                     : atab ? (const void*)ldpc_decode_pk_kernel<true, false, 1, true> : L.parts == 4 ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 4> : (const void*)ldpc_decode_pk_kernel<false, false, 4>)
                      : L.parts == 2 ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 2> : (const void*)ldpc_decode_pk_kernel<false, false, 2>)
                            : fused ? (gm ? (const void*)ldpc_decode_pk_kernel<true, true> : (const void*)ldpc_decode_pk_kernel<true, false>)
                                    : (gm ? (const void*)ldpc_decode_pk_kernel<false, true> : (const void*)ldpc_decode_pk_kernel<false, false>);
@@ -594,7 +635,13 @@ int miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy
 #define PK_LAUNCH(F, G, ...)                                                                                                                              \
   hipLaunchKernelGGL((ldpc_decode_pk_kernel<F, G, ##__VA_ARGS__>), dim3(L.grid), dim3(L.threads), L.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, \
                      L.nodes, harq_slot, harq_crc_ok, L.c.count, queue, d_rdm, rm_in, (uint32_t*)gmsg, L.gmsg_pairs, gm ? L.lds_pairs : 0, d_order, (const pk_adr_quad* const*)L.adr_by_z)
-  if (atab)
+  if (rs && atab)
+    PK_LAUNCH(true, false, 1, true, true);
+  else if (rs && fused)
+    PK_LAUNCH(true, false, 1, false, true);
+  else if (rs)
+    PK_LAUNCH(false, false, 1, false, true);
+  else if (atab)
     PK_LAUNCH(true, false, 1, true);
   else if (L.parts == 4 && fused)
     PK_LAUNCH(true, false, 4);

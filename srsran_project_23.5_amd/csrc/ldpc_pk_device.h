@@ -91,6 +91,9 @@ __device__ unsigned long long g_ldpc_prof2[8];
 constexpr int LLR_MAX = 120;
 constexpr int LLR_INF = 127;
 constexpr int INF_MUL = 255; // an infinite soft bit (|s| > 120) becomes a message of magnitude >= 255 + 24
+// The smallest |v| an infinite soft bit can give: 255 |d| + t with |d| >= 1 and |t| <= 120 against it. A finite one gives |v| <= 120, so
+// "min |v| >= 135" says that every soft bit a row read was infinite ("saturated rows").
+constexpr int V_INF_MIN = INF_MUL - LLR_MAX;
 
 // Stage A of a row update, shared by its forms: both rows' soft-bit addresses of every edge of the layer with packed 16-bit arithmetic:
 // {l, l + H} + shift, wrap at Z by the unsigned minimum of p and p - Z -- three packed instructions for the two rows. The pair has to be
@@ -149,13 +152,17 @@ struct pk_adr_row {
   __amdgpu_buffer_rsrc_t rsrc;
   uint32_t               soff; // byte offset of the layer's first quad (wave-uniform)
 };
-template <int D>
+// TIE: an empty asm keeps the split in the visit, behind its s_setprio (the compiler otherwise hoists it out of the instances of a visit, in
+// front of the priority). Not in the instances that can leave a visit out (saturated rows, ldpc_decode_pk.hip): with a path through the
+// layer loop that does not pass through the asm, the tie costs a register copy per word, 19 more VALU instructions per visit.
+template <int D, bool TIE = true>
 __device__ __forceinline__ void pk_table_addresses(uint32_t (&adrA)[D], uint32_t (&adrB)[D], const pk_adr_quad* q)
 {
 #pragma unroll
   for (int j = 0; j < D; ++j) {
     uint32_t w = q[j >> 2][j & 3];
-    asm volatile("" : "+v"(w)); // (keeps the split in the visit, behind its s_setprio: the compiler otherwise hoists it out of the instances of a visit, in front of the priority)
+    if constexpr (TIE)
+      asm volatile("" : "+v"(w));
     adrA[j] = w & 0xffffu;
     adrB[j]          = w >> 16;
   }
@@ -202,8 +209,14 @@ struct pk_no_hook {
 // `mid` is called once between the two phases (the latency form issues the scalar loads of the next layer's edges there: behind the last LDS
 // read of the layer, so that they do not turn the partial lgkmcnt waits on the in-order LDS returns into waits for everything).
 // ATAB: the addresses of this visit arrive in `aq` (pk_table_addresses), which leaves with those of the layer at `anext`.
-template <int D, bool FIRST, int PARTS = 1, typename MID, bool FOLD, bool ATAB = false>
-__device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
+// DETECT (PARTS == 1; the instances of the packed throughput kernel that leave out visits -- every other caller gets the update as it was,
+// instruction for instruction) returns: every one of the 2 D soft bits this lane read was infinite. Such rows are frozen -- this update
+// and every later one of the layer rewrites each of them to +-127 with the sign it has, whatever the messages are -- so a wavefront whose
+// lanes all say so may leave out its later visits of the layer (ldpc_decode_pk.hip, "saturated rows"). The test is four instructions per
+// visit -- three packed minima and a compare: the running minima start from 0x7fff instead of 120 and are clipped behind the edge loop
+// (120 twice in a running minimum IS the clip: the same min1 / min2), and the unclipped min1 of both rows is compared with V_INF_MIN.
+template <int D, bool FIRST, int PARTS = 1, typename MID, bool FOLD, bool ATAB = false, bool DETECT = false>
+__device__ __forceinline__ bool update_rows_pk(int8_t* __restrict__ soft,
                                                uint32_t* __restrict__ c2v, // this lane's message dword of edges 0,1 of the layer
                                                const uint32_t* __restrict__ edges, // {shift, column*Z} per edge
                                                int l,
@@ -229,8 +242,9 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO); // the address arithmetic and the LDS requests of a layer
   // Stage A: every address of the layer, then every LDS read of the layer in one go (2 soft bits per edge + the old
   // messages): the latency of the LDS pipe is paid once per layer instead of once per group of edges.
+  static_assert(!(DETECT && SPLIT), "the latency form runs every visit");
   if constexpr (ATAB)
-    pk_table_addresses<D>(adrA, adrB, aq);
+    pk_table_addresses<D, !DETECT>(adrA, adrB, aq);
   else
     pk_edge_addresses<D, FOLD>(adrA, adrB, edges, l, H, Z, base);
   P2_T(q1);
@@ -248,7 +262,7 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO1);
   __builtin_amdgcn_sched_barrier(0);
   P2_T(q2);
-  s16x2    mag1 = splat(LLR_MAX), mag2 = splat(LLR_MAX);
+  s16x2    mag1 = splat(DETECT ? 0x7fff : LLR_MAX), mag2 = mag1;
   uint32_t spx  = 0;
 #pragma unroll
   for (int j = 0; j < D; ++j) {
@@ -270,6 +284,12 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
     const s16x2 help = pk_max(mag1, av);
     mag1             = pk_min(mag1, av);
     mag2             = pk_min(mag2, help);
+  }
+  bool all_inf = false;
+  if constexpr (DETECT) {
+    all_inf = as_u(pk_min(mag1, splat(V_INF_MIN))) == as_u(splat(V_INF_MIN));
+    mag1    = pk_min(mag1, splat(LLR_MAX));
+    mag2    = pk_min(mag2, splat(LLR_MAX));
   }
   P2_T(q3);
 #ifdef LDPC_PK_PROFILE2
@@ -337,6 +357,7 @@ __device__ __forceinline__ void update_rows_pk(int8_t* __restrict__ soft,
   P2_ADD(4, q4, q5); // exchange: loads + merge
   P2_ADD(5, q5, q6); // scaling + phase 2 + stores
   P2_ADD(6, q0, q6);
+  return all_inf;
 }
 
 // The row update of layers 1 and 2 in the FIRST iteration of the throughput form and the wave kernel, where one edge of the row is known
@@ -466,38 +487,40 @@ __device__ __forceinline__ void update_rows_pk_split(const part_edges<PARTS>& pe
   }
 }
 
-template <bool FIRST, bool FOLD>
-__device__ __forceinline__ void update_rows_pk_any(int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
+template <bool FIRST, bool FOLD, bool DETECT = false>
+__device__ __forceinline__ bool update_rows_pk_any(int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
 {
+  bool r = false;
   switch (d) {
     case 19:
-      update_rows_pk<19, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
+      r = update_rows_pk<19, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
       break;
     case 10:
-      update_rows_pk<10, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
+      r = update_rows_pk<10, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
       break;
     case 9:
-      update_rows_pk<9, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
+      r = update_rows_pk<9, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
       break;
     case 8:
-      update_rows_pk<8, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
+      r = update_rows_pk<8, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
       break;
     case 7:
-      update_rows_pk<7, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
+      r = update_rows_pk<7, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
       break;
     case 6:
-      update_rows_pk<6, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
+      r = update_rows_pk<6, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
       break;
     case 5:
-      update_rows_pk<5, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
+      r = update_rows_pk<5, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
       break;
     case 4:
-      update_rows_pk<4, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
+      r = update_rows_pk<4, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
       break;
     default:
-      update_rows_pk<3, FIRST, 1, pk_no_hook, FOLD>(soft, c2v, edges, l, H, Z, base);
+      r = update_rows_pk<3, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
       break;
   }
+  return r;
 }
 
 // Layers m = 1 and 2 of the first iteration: the degrees these two layers have in the two base graphs (miphy_ctx.hip asserts them).
@@ -519,29 +542,35 @@ __device__ __forceinline__ void update_rows_pk_zero_any(int m, int d, int8_t* so
 
 // One layer visit of the throughput form and the wave kernel. Iteration 0 starts at layer 1 (see update_rows_pk_zero: layer 0 changes
 // nothing there), so layer 0's messages are first written in iteration 1, by the instance that reads none. FOLD: pk_edge_addresses.
-template <bool FOLD>
-__device__ __forceinline__ void update_rows_pk_visit(int it, int m, int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
+// Returns what update_rows_pk does; the known-zero visits read a zero and never say that their rows are saturated.
+template <bool FOLD, bool DETECT = false>
+__device__ __forceinline__ bool update_rows_pk_visit(int it, int m, int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
 {
+  bool r = false;
   if (it == 0 && (m == 1 || m == 2))
     update_rows_pk_zero_any<FOLD>(m, d, soft, c2v, edges, l, H, Z, base);
   else if (it == 0 || (it == 1 && m == 0))
-    update_rows_pk_any<true, FOLD>(d, soft, c2v, edges, l, H, Z, base);
+    r = update_rows_pk_any<true, FOLD, DETECT>(d, soft, c2v, edges, l, H, Z, base);
   else
-    update_rows_pk_any<false, FOLD>(d, soft, c2v, edges, l, H, Z, base);
+    r = update_rows_pk_any<false, FOLD, DETECT>(d, soft, c2v, edges, l, H, Z, base);
+  return r;
 }
 
 // The same visit of an ATAB instance: every layer the launch can reach has degree D (the launch planner sees to that).
-template <int D>
-__device__ __forceinline__ void update_rows_pk_visit_tab(int it, int m, int8_t* soft, uint32_t* c2v, pk_adr_quad* aq, pk_adr_row anext, uint32_t avoff, uint32_t astride)
+template <int D, bool DETECT = false>
+__device__ __forceinline__ bool update_rows_pk_visit_tab(int it, int m, int8_t* soft, uint32_t* c2v, pk_adr_quad* aq, pk_adr_row anext, uint32_t avoff, uint32_t astride)
 {
-  if (it == 0 && m == 1)
+  if (it == 0 && m == 1) {
     update_rows_pk_zero<D, 0, true, true>(soft, c2v, nullptr, 0, 0, 0, 0, aq, anext, avoff, astride);
-  else if (it == 0 && m == 2)
+    return false;
+  }
+  if (it == 0 && m == 2) {
     update_rows_pk_zero<D, 1, true, true>(soft, c2v, nullptr, 0, 0, 0, 0, aq, anext, avoff, astride);
-  else if (it == 0 || (it == 1 && m == 0))
-    update_rows_pk<D, true, 1, pk_no_hook, true, true>(soft, c2v, nullptr, 0, 0, 0, 0, true, nullptr, 0, 0, pk_no_hook(), aq, anext, avoff, astride);
-  else
-    update_rows_pk<D, false, 1, pk_no_hook, true, true>(soft, c2v, nullptr, 0, 0, 0, 0, true, nullptr, 0, 0, pk_no_hook(), aq, anext, avoff, astride);
+    return false;
+  }
+  if (it == 0 || (it == 1 && m == 0))
+    return update_rows_pk<D, true, 1, pk_no_hook, true, true, DETECT>(soft, c2v, nullptr, 0, 0, 0, 0, true, nullptr, 0, 0, pk_no_hook(), aq, anext, avoff, astride);
+  return update_rows_pk<D, false, 1, pk_no_hook, true, true, DETECT>(soft, c2v, nullptr, 0, 0, 0, 0, true, nullptr, 0, 0, pk_no_hook(), aq, anext, avoff, astride);
 }
 
 __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b, uint32_t poly, uint32_t order)

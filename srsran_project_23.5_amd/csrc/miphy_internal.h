@@ -140,6 +140,7 @@ struct miphy_ldpc_class {
   uint8_t  bgi;   // base graph - 1
   uint8_t  fused; // every codeblock can be rate-dematched by the decoder while it loads
   uint8_t  lay;   // layers a codeblock of the class can reach at most
+  uint8_t  runs_all_iterations; // some codeblock of the class cannot stop early (no CRC, or a CRC checked behind the last iteration only)
   uint16_t max_Z, min_Z;
   uint32_t first, count;               // the class's range of `order`
   uint32_t bundle_first, bundle_count; // kind 0: its range of `bundles` (pairs of words)
@@ -169,6 +170,7 @@ struct miphy_ldpc_launch {
   bool             ordered;    // decodes order[c.first ...] (false: the codeblocks in array order)
   bool             atab;       // packed kernel: the instance that reads its soft-bit addresses from a table (ldpc_pk_device.h, pk_table_addresses)
   const void*      adr_by_z;   // ... device array of the tables of the class, at [Z / 16] (miphy_ldpc_address_tables; owned by the context)
+  bool             row_skip;   // packed kernel: the instance whose wavefronts leave out the visits of layers with saturated rows (ldpc_decode_pk.hip, RSKIP)
   size_t           gmsg_off, gmsg_bytes; // the launch's part of the message scratch
 };
 struct miphy_ldpc_launches {
@@ -189,7 +191,8 @@ enum miphy_ldpc_force_mode {
   MIPHY_LDPC_FORCE_LATENCY2    = 6, // AUTO with the latency form in two parts instead of four
   MIPHY_LDPC_FORCE_MODE_MASK   = 0xff,
   MIPHY_LDPC_FORCE_ALL_GMSG    = 0x100, // flag: a GMSG launch keeps ALL its messages in global memory
-  MIPHY_LDPC_FORCE_NO_ADR_TABLE = 0x200 // flag: no launch reads its soft-bit addresses from a table (every class computes them)
+  MIPHY_LDPC_FORCE_NO_ADR_TABLE = 0x200, // flag: no launch reads its soft-bit addresses from a table (every class computes them)
+  MIPHY_LDPC_FORCE_NO_ROW_SKIP  = 0x400  // flag: no launch takes an instance that leaves out the layer visits of saturated rows
 };
 // Host only: the launch table of the classes C (their order / bundles are device arrays by then). fuse: the fused classes dematch while
 // they load (the caller then passes rate-dematcher descriptors to the run). The debug knobs of miphy_debug_force_ldpc_kernel and
