@@ -78,11 +78,14 @@ size_t miphy_pdsch_modulate_scratch_bytes(uint32_t n);
 int    miphy_pdsch_modulate_launch(const miphy_pdsch_mod_job* d_jobs, uint32_t n, const gold_tables* gt, const uint8_t* codewords, float* grid, void* seq,
                                    hipStream_t s);
 int    miphy_dmrs_pdsch_map_launch(const miphy_dmrs_pdsch_job* d_jobs, uint32_t n, const gold_tables* gt, float* grid, hipStream_t s);
-// Every rule miphy_pdsch_modulate_layers_batch has for a host job (pdsch_mod.hip), for the layered PDSCH processor, which refuses a batch before it
-// enqueues the encoder: MIPHY_EINVAL and the message "<who>: <what> <i>: ..." on the first rule the job breaks. nof_re: the data REs per layer
-// where the caller has counted them already, 0: counted here. Then the staging and the two launches of that entry point for jobs that passed (or
-// that sit on the device, which the kernels validate); max_layers = the largest nof_layers of the batch, 4 for device-resident jobs.
-int    miphy_pdsch_mod_layers_check(const char* who, const char* what, uint32_t i, const miphy_pdsch_mod_layers_job& job, uint32_t nof_re);
+// The one list of rules for a modulator job on the host (pdsch_mod.hip), for the two modulator entry points and for the PDSCH processors, which
+// refuse a batch before they enqueue anything: MIPHY_EINVAL and the message "<who>: <what> <i>: ..." on the first rule the job breaks. ports: the grid
+// port of each of the nof_layers layers, null for the one-layer entry points (the port is job.port, and the messages name no layer). nof_re: the
+// data REs per layer where the caller has counted them already, 0: counted here.
+int    miphy_pdsch_mod_job_check(const char* who, const char* what, uint32_t i, const miphy_pdsch_mod_job& job, unsigned nof_layers, const uint8_t* ports,
+                                 uint32_t nof_re);
+// The staging and the two launches of miphy_pdsch_modulate_layers_batch for jobs that passed that check (or that sit on the device, which the
+// kernels validate); max_layers = the largest nof_layers of the batch, 4 for device-resident jobs.
 int    miphy_pdsch_modulate_layers_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_layers_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
                                            const uint8_t* codewords, float* grid, hipStream_t s);
 

@@ -7,26 +7,77 @@
 //   sqrtf(1 / average power)), lib/phy/upper/signal_processors/dmrs_pdsch_processor_impl.cpp:30-169 + dmrs_helper.h:44-96.
 // One transmit layer / one codeword and contiguous (ascending) PRB mapping: the 23.5 reference cannot do more -- its layer mapper
 // indexes out of bounds for more than one layer (pdsch_modulator_impl.cpp:80-103) and its non-contiguous mapping path writes a
-// single PRB (map_to_prb_other). One workgroup per (transmission, OFDM symbol); every resource element is written once, with the
-// exact single-precision value of the reference (level * scale [* scaling]).
-// Beyond the reference: one codeword on 1..4 layers (pdsch_mod_layers_kernel, miphy_pdsch_modulate_layers_batch), the layer mapping of
-// TS 38.211 7.3.1.3 as the oracle's orc_pdsch_modulate states it, layer ly on grid port ports[ly], no precoding. The one-layer kernel and
-// entry point are unchanged.
+// single PRB (map_to_prb_other). Every resource element is written once, with the exact single-precision value of the reference
+// (level * scale [* scaling]).
+// Beyond the reference: one codeword on 1..4 layers (miphy_pdsch_modulate_layers_batch), the layer mapping of TS 38.211 7.3.1.3 as the oracle's
+// orc_pdsch_modulate states it, layer ly on grid port ports[ly], no precoding.
+//
+// Two entry points, two kernels each, one set of helpers. A sequence kernel per entry point (pdsch_seq_kernel: one workgroup per transmission,
+// x1 from the table; pdsch_seq_layers_kernel: chunks with both registers jumped, for sequences L times as long) writes the scrambling sequence
+// and, through pdsch_count_symbols, the data elements of the transmission before every OFDM symbol. A mapping kernel per entry point
+// (pdsch_mod_kernel, pdsch_mod_layers_kernel), one workgroup per (transmission, OFDM symbol), fills a pdsch_symbol_lds through
+// pdsch_symbol_setup and maps its elements through pdsch_layers_fast (16QAM / 256QAM on aligned codewords) or pdsch_map_elements (everything
+// else). Which REs carry data is stated once, in pdsch_keep_rule_of and pdsch_keep_mask, for the four kernels and the host's count; what a job
+// must satisfy is stated once, in PDSCH_MOD_FIELD_RULES, for the kernels' predicate and the host's messages.
 #include "gold_device.h"
 #include "mod_device.h"
 #include "miphy_ext.h"
 #include <cmath>
-#include <type_traits>
 
 namespace {
 
-
-__device__ __forceinline__ unsigned dmrs_prb_mask(int type, unsigned cdm)
+__host__ __device__ __forceinline__ unsigned dmrs_prb_mask(int type, unsigned cdm)
 {
   unsigned m = 0;
   for (unsigned k = 0; k < 12; ++k)
     m |= ((type == 1) ? ((k % 2) < cdm) : ((k % 6) < 2 * cdm)) ? (1u << k) : 0u;
   return m;
+}
+
+// What decides which REs of a PRB carry data, read from the job once: on the device into uniform registers, before the first barrier, so that no
+// load of a job field waits behind one.
+struct pdsch_keep_rule {
+  unsigned dmask;                      // the DM-RS pattern within a PRB (dmrs_prb_mask) ...
+  unsigned dmrs_syms, bwp0, bwp1;      // ... which applies in these OFDM symbols to the PRBs [bwp0, bwp1)
+  unsigned nres, res_re[4], res_sy[4]; // the reserved patterns (at most four): RE mask and OFDM symbols of each
+};
+
+__host__ __device__ __forceinline__ pdsch_keep_rule pdsch_keep_rule_of(const miphy_pdsch_mod_job& j)
+{
+  pdsch_keep_rule k = {};
+  k.dmask     = dmrs_prb_mask(j.dmrs_type, j.nof_cdm_groups_without_data);
+  k.dmrs_syms = j.dmrs_symbols_mask, k.bwp0 = j.bwp_start_rb, k.bwp1 = k.bwp0 + j.bwp_size_rb;
+  k.nres      = j.nof_reserved < 4 ? j.nof_reserved : 4;
+#pragma unroll
+  for (unsigned r = 0; r < 4; ++r)
+    if (r < k.nres) {
+      k.res_re[r] = j.reserved[r].re_mask;
+      k.res_sy[r] = j.reserved[r].symbols;
+    }
+  return k;
+}
+
+// The REs of PRB rb in OFDM symbol s that carry data, as a 12-bit mask: all but the DM-RS pattern where the symbol carries DM-RS and the PRB lies
+// in the bandwidth part, and but the RE masks of the reserved patterns that name the symbol and the PRB. Word w of the PRB mask of pattern r is
+// res_prb[r * res_stride + w]: a copy in LDS on the device, the job itself on the host.
+__host__ __device__ __forceinline__ unsigned pdsch_keep_mask(const pdsch_keep_rule& k, unsigned s, unsigned rb, const uint64_t* res_prb, unsigned res_stride)
+{
+  unsigned ex = (((k.dmrs_syms >> s) & 1u) && rb >= k.bwp0 && rb < k.bwp1) ? k.dmask : 0u;
+#pragma unroll
+  for (unsigned r = 0; r < 4; ++r)
+    if (r < k.nres && ((k.res_sy[r] >> s) & 1u) && ((res_prb[r * res_stride + (rb >> 6)] >> (rb & 63)) & 1ull))
+      ex |= k.res_re[r];
+  return ~ex & 0xfffu;
+}
+
+// The PRB masks of a job -- the allocation and the (at most four) reserved patterns -- into LDS; the caller synchronises.
+__device__ __forceinline__ void pdsch_load_masks(const miphy_pdsch_mod_job& j, uint64_t* rbm, uint64_t (*resm)[5], int tid)
+{
+  const int nres = min((int)j.nof_reserved, 4);
+  if (tid < 5)
+    rbm[tid] = j.rb_mask[tid];
+  if (tid >= 32 && tid < 32 + 5 * nres)
+    resm[(tid - 32) / 5][(tid - 32) % 5] = j.reserved[(tid - 32) / 5].prb_mask[(tid - 32) % 5];
 }
 
 // Allocated-PRB list (compact, ascending) from a 275-bit mask held in LDS; returns the number of allocated PRBs through *count.
@@ -50,10 +101,201 @@ __device__ __forceinline__ void build_prb_list(const uint64_t* rbm, int nprb_gri
   }
 }
 
+// Prologue of the two sequence kernels: the data REs (per layer) of the job in every OFDM symbol of the slot, left in cnt[0..13] behind a barrier.
+// The caller turns them into the prefixes the mapping kernel reads: each (transmission, symbol) workgroup of the modulator used to recount all
+// earlier symbols itself.
+__device__ __forceinline__ void pdsch_count_symbols(const miphy_pdsch_mod_job& j, uint64_t* rbm, uint64_t (*resm)[5], int* cnt, int tid, int nt)
+{
+  const pdsch_keep_rule keep      = pdsch_keep_rule_of(j);
+  const int             nprb_grid = j.grid_nof_prb, s0 = j.start_symbol, s1 = s0 + j.nof_symbols;
+  pdsch_load_masks(j, rbm, resm, tid);
+  if (tid >= 64 && tid < 78)
+    cnt[tid - 64] = 0;
+  __syncthreads();
+  for (int q = tid; q < 14 * nprb_grid; q += nt) {
+    const int s = q / nprb_grid, rb = q - s * nprb_grid;
+    if (s < s0 || s >= s1 || !((rbm[rb >> 6] >> (rb & 63)) & 1ull))
+      continue;
+    atomicAdd(&cnt[s], __popc(pdsch_keep_mask(keep, s, rb, &resm[0][0], 5)));
+  }
+  __syncthreads();
+}
+
+// What a mapping workgroup knows of its OFDM symbol (pdsch_symbol_setup).
+struct pdsch_symbol_lds {
+  uint16_t prb_of[276];  // the allocated PRBs, ascending
+  uint16_t keep_of[276]; // per allocated PRB: 12-bit mask of the REs that carry data in this symbol
+  uint16_t off_of[276];  // per allocated PRB: index of its first data RE within the symbol
+  uint64_t rbm[5], resm[4][5];
+  int      nprb, n_re;   // allocated PRBs, data REs of the symbol
+};
+
+// Fills S for OFDM symbol sy of the job, every thread of the workgroup (at least one wavefront) calling; returns the data REs of the symbol.
+__device__ __forceinline__ int pdsch_symbol_setup(const miphy_pdsch_mod_job& j, int sy, pdsch_symbol_lds& S, int tid, int nt)
+{
+  const pdsch_keep_rule keep      = pdsch_keep_rule_of(j);
+  const int             nprb_grid = j.grid_nof_prb;
+  pdsch_load_masks(j, S.rbm, S.resm, tid);
+  __syncthreads();
+  build_prb_list(S.rbm, nprb_grid, 0, S.prb_of, &S.nprb, tid, nt);
+  __syncthreads();
+  const int nprb = S.nprb;
+  for (int i = tid; i < nprb; i += nt)
+    S.keep_of[i] = (uint16_t)pdsch_keep_mask(keep, sy, S.prb_of[i], &S.resm[0][0], 5);
+  __syncthreads();
+  // exclusive scan of the per-PRB counts of this symbol (<= 275 entries: one wavefront, 5 entries per lane)
+  if (tid < 64) {
+    int c[5], sum = 0;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const int i = tid * 5 + q;
+      c[q]        = (i < nprb) ? __popc((unsigned)S.keep_of[i]) : 0;
+      sum += c[q];
+    }
+    int inc = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(inc, o);
+      inc += (tid >= o) ? v : 0;
+    }
+    int run = inc - sum;
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      const int i = tid * 5 + q;
+      if (i < nprb)
+        S.off_of[i] = (uint16_t)run;
+      run += c[q];
+    }
+    if (tid == 63)
+      S.n_re = inc;
+  }
+  __syncthreads();
+  return S.n_re;
+}
+
+// Bit 0 of each of the mod bytes at cp (one bit per byte, b0 first) gathered into bit t = t-th bit: one wide load where the run of bytes is
+// aligned, then bit 0 of every byte through a multiplication ((x & 0x01010101) * 0x01020408 puts bytes 0..3 into bits 24..27).
+__device__ __forceinline__ uint32_t gather_bits(const uint8_t* cp, int mod)
+{
+  uint32_t raw = 0;
+  if (mod == 8 && (((uintptr_t)cp) & 7u) == 0) {
+    const uint2 v = *reinterpret_cast<const uint2*>(cp);
+    raw           = (((v.x & 0x01010101u) * 0x01020408u) >> 24) | ((((v.y & 0x01010101u) * 0x01020408u) >> 24) << 4);
+  } else if (mod == 4 && (((uintptr_t)cp) & 3u) == 0) {
+    raw = ((*reinterpret_cast<const uint32_t*>(cp) & 0x01010101u) * 0x01020408u) >> 24;
+  } else if (mod == 2 && (((uintptr_t)cp) & 1u) == 0) {
+    const uint32_t v = *reinterpret_cast<const uint16_t*>(cp);
+    raw              = (v & 1u) | ((v >> 7) & 2u);
+  } else if (mod == 6 && (((uintptr_t)cp) & 1u) == 0) {
+    const uint16_t* c2 = reinterpret_cast<const uint16_t*>(cp);
+    const uint32_t  v0 = c2[0], v1 = c2[1], v2 = c2[2];
+    raw = (v0 & 1u) | ((v0 >> 7) & 2u) | ((v1 & 1u) << 2) | ((v1 >> 5) & 8u) | ((v2 & 1u) << 4) | ((v2 >> 3) & 32u);
+  } else {
+    for (int t = 0; t < mod; ++t)
+      raw |= (uint32_t)(cp[t] & 1u) << t;
+  }
+  return raw;
+}
+
+// The elements of one OFDM symbol, one at a time, on L layers (a literal 1 from the one-layer kernel, so that the layer loop folds). TS 38.211
+// 7.3.1.3: x^(ly)(i) = d(L i + ly), so the resource element of rank i_re in the transmission (prefix = its rank at the start of the symbol) owns
+// the codeword symbols L i_re .. L i_re + L - 1: L mod consecutive bytes of the codeword and L mod <= 32 consecutive bits of the scrambling
+// sequence, one 64-bit window of two sequence words. Bit offsets stay in 32 bits: the longest codeword is 4 layers x 275 PRB x 12 x 14
+// symbols x 8 bits = 1 478 400 bits. Layer ly goes to g[ly], the symbol's row of its grid port. This function and pdsch_layers_fast take their
+// arguments by reference, as a lambda captures them: taken by value, both mapping kernels come out two to four registers above the 80 that six
+// waves per SIMD allow (tools/kernel_resources.sh).
+__device__ __forceinline__ void pdsch_map_elements(const pdsch_symbol_lds& S, const int& L, const int& mod, const int& prefix, const uint32_t* const& seq,
+                                                   const uint8_t* const& cw, float2* const (&g)[4], const bool& scale, const float& scaling, const int& tid, const int& nt)
+{
+  const int      nprb = S.nprb;
+  const uint32_t mask = (1u << mod) - 1u;
+  for (int idx = tid; idx < nprb * 12; idx += nt) {
+    const int      i = idx / 12, k = idx - i * 12;
+    const unsigned keep = S.keep_of[i];
+    if (!((keep >> k) & 1u))
+      continue;
+    const int      j  = S.off_of[i] + __popc(keep & ((1u << k) - 1u));   // RE index within the symbol
+    const uint32_t d0 = ((uint32_t)prefix + (uint32_t)j) * (uint32_t)L;  // first codeword symbol of the element
+    const uint32_t bi = d0 * (uint32_t)mod;                              // its first bit: position in the transmission's scrambling sequence
+    const uint64_t two = (uint64_t)seq[bi >> 5] | ((uint64_t)seq[(bi >> 5) + 1] << 32);
+    const uint32_t cb  = (uint32_t)(two >> (bi & 31)); // scrambling bits of the element's L symbols, bit t = t-th bit
+    const uint8_t* cp  = cw + (size_t)bi;
+    const int      col = S.prb_of[i] * 12 + k;
+#pragma unroll
+    for (int ly = 0; ly < 4; ++ly) {
+      if (ly >= L)
+        break;
+      const uint32_t nat = (gather_bits(cp + ly * mod, mod) ^ (cb >> (ly * mod))) & mask; // scrambled bits, bit t = t-th bit of the symbol (b0 first)
+      float2         x   = map_symbol(mod, nat, d0 + (uint32_t)ly); // pi/2-BPSK turns with the parity of the codeword symbol
+      if (scale) {
+        x.x = x.x * scaling;
+        x.y = x.y * scaling;
+      }
+      g[ly][col] = x;
+    }
+  }
+}
+
+// The common shapes (16QAM / 256QAM, the element's run of bytes aligned to words) in two sweeps: the loads of a group of the thread's elements -- the
+// LL x MOD bytes of each as one wide load and the two words of its scrambling window -- are issued before the first of them is mapped, unconditionally
+// (an element that carries no data reads element 0 of the symbol and is not stored). The one-element-at-a-time loop above pays one memory round trip
+// per element: thirteen per thread on 273 PRBs. The group shrinks as the element grows, so that the loaded words stay in registers.
+template <int LL, int MOD>
+__device__ __forceinline__ void pdsch_layers_fast(const pdsch_symbol_lds& S, const int& prefix, const uint32_t* const& seq, const uint8_t* const& cw,
+                                                  float2* const (&g)[4], const bool& scale, const float& scaling, const int& tid)
+{
+  constexpr int NW = LL * MOD / 4; // codeword words of one element
+  constexpr int IT = (275 * 12 + 255) / 256, G = NW >= 6 ? 4 : (NW >= 3 ? 7 : IT);
+  struct alignas(4) words {
+    uint32_t v[NW];
+  };
+  const int nprb = S.nprb;
+  for (int it0 = 0; it0 < IT && it0 * 256 < nprb * 12; it0 += G) {
+    words    cv[G];
+    uint32_t q0[G], q1[G], sh[G];
+    int      dst[G]; // grid column of the element, -1: none
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const int      idx  = tid + (it0 + u) * 256;
+      const bool     in   = idx < nprb * 12;
+      const int      i    = in ? idx / 12 : 0, k = in ? idx - i * 12 : 0;
+      const unsigned keep = S.keep_of[i];
+      const bool     has  = in && ((keep >> k) & 1u);
+      const int      j    = has ? S.off_of[i] + __popc(keep & ((1u << k) - 1u)) : 0;
+      const uint32_t d0   = ((uint32_t)prefix + (uint32_t)j) * (uint32_t)LL; // first codeword symbol of the element
+      const uint32_t bi   = d0 * (uint32_t)MOD;
+      q0[u] = seq[bi >> 5], q1[u] = seq[(bi >> 5) + 1];
+      sh[u]  = bi & 31u;
+      cv[u]  = *reinterpret_cast<const words*>(cw + (size_t)d0 * MOD);
+      dst[u] = has ? (int)S.prb_of[i] * 12 + k : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const uint32_t cb  = (uint32_t)((((uint64_t)q1[u] << 32) | q0[u]) >> sh[u]);
+      uint32_t       raw = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w)
+        raw |= (((cv[u].v[w] & 0x01010101u) * 0x01020408u) >> 24) << (4 * w);
+      const uint32_t bits = raw ^ cb; // scrambled bits of the element, layer after layer
+#pragma unroll
+      for (int ly = 0; ly < LL; ++ly) {
+        float2 x = map_symbol(MOD, (bits >> (ly * MOD)) & ((1u << MOD) - 1u), 0u);
+        if (scale) {
+          x.x = x.x * scaling;
+          x.y = x.y * scaling;
+        }
+        if (dst[u] >= 0)
+          g[ly][dst[u]] = x;
+      }
+    }
+  }
+}
+
 // Scrambling sequence c(0 .. nof_bits - 1) of every transmission, one workgroup each (c_init = rnti * 2^15 + n_id, TS 38.211 7.3.1.1): x1 from
 // the table, x2 from its linear basis and the doubling word recurrence (gold_device.h) -- as the PUSCH demodulator does. The OFDM symbols
 // of a transmission use consecutive pieces of it; before, every (transmission, symbol) workgroup jumped both LFSRs to its first bit and ran
 // the recurrences on one wavefront while three waited (0.40 ms per 1024 slots of 273 PRB: the longest kernel of the transmit chain).
+// prefix_out[job][14]: the data elements of the transmission before every OFDM symbol.
 constexpr int PDSCH_SEQ_STRIDE = GOLD_X1_WORDS;
 __global__ void __launch_bounds__(512) pdsch_seq_kernel(const miphy_pdsch_mod_job* __restrict__ jobs, const gold_tables* __restrict__ gt, uint32_t* __restrict__ seq,
                                                         int* __restrict__ prefix_out)
@@ -63,38 +305,12 @@ __global__ void __launch_bounds__(512) pdsch_seq_kernel(const miphy_pdsch_mod_jo
   __shared__ int      cnt[14];
   const miphy_pdsch_mod_job* __restrict__ jp = jobs + blockIdx.x;
   const int tid = threadIdx.x, nt = blockDim.x;
-  // ---- data elements of the transmission before every OFDM symbol (prefix[job][14]): each (transmission, symbol) workgroup of the
-  // modulator used to recount all earlier symbols itself
-  {
-    const unsigned dmask     = dmrs_prb_mask(jp->dmrs_type, jp->nof_cdm_groups_without_data);
-    const unsigned dmrs_syms = jp->dmrs_symbols_mask;
-    const int      nprb_grid = jp->grid_nof_prb, nres = jp->nof_reserved;
-    const int      bwp0 = jp->bwp_start_rb, bwp1 = bwp0 + jp->bwp_size_rb;
-    const int      s0 = jp->start_symbol, s1 = s0 + jp->nof_symbols;
-    if (tid < 5)
-      rbm[tid] = jp->rb_mask[tid];
-    if (tid >= 32 && tid < 32 + 5 * nres)
-      resm[(tid - 32) / 5][(tid - 32) % 5] = jp->reserved[(tid - 32) / 5].prb_mask[(tid - 32) % 5];
-    if (tid >= 64 && tid < 78)
-      cnt[tid - 64] = 0;
-    __syncthreads();
-    for (int q = tid; q < 14 * nprb_grid; q += nt) {
-      const int s = q / nprb_grid, rb = q - s * nprb_grid;
-      if (s < s0 || s >= s1 || !((rbm[rb >> 6] >> (rb & 63)) & 1ull))
-        continue;
-      unsigned ex = (((dmrs_syms >> s) & 1u) && rb >= bwp0 && rb < bwp1) ? dmask : 0u;
-      for (int r = 0; r < nres; ++r)
-        if (((jp->reserved[r].symbols >> s) & 1u) && ((resm[r][rb >> 6] >> (rb & 63)) & 1ull))
-          ex |= jp->reserved[r].re_mask;
-      atomicAdd(&cnt[s], __popc(~ex & 0xfffu));
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int run = 0;
-      for (int s = 0; s < 14; ++s) {
-        prefix_out[blockIdx.x * 14 + s] = run;
-        run += cnt[s];
-      }
+  pdsch_count_symbols(*jp, rbm, resm, cnt, tid, nt);
+  if (tid == 0) {
+    int run = 0;
+    for (int s = 0; s < 14; ++s) {
+      prefix_out[blockIdx.x * 14 + s] = run;
+      run += cnt[s];
     }
   }
   int       nwords = (int)((jp->nof_bits + 31u) >> 5) + 2; // + the 64-bit window of the last resource element
@@ -109,178 +325,31 @@ __global__ void __launch_bounds__(256) pdsch_mod_kernel(const miphy_pdsch_mod_jo
                                                         const uint8_t* __restrict__ cw_base, float2* __restrict__ grid, const uint32_t* __restrict__ seq_base,
                                                         const int* __restrict__ prefix_base)
 {
-  __shared__ uint16_t prb_of[276];
-  __shared__ uint16_t keep_of[276];  // per allocated PRB: 12-bit mask of the REs that carry data in this symbol
-  __shared__ uint16_t off_of[276];   // per allocated PRB: index of its first data RE within the symbol
-  __shared__ uint64_t rbm[5], resm[4][5];
-  __shared__ int      nprb_s, red[8];
+  __shared__ pdsch_symbol_lds S;
   const miphy_pdsch_mod_job* __restrict__ jp = jobs + blockIdx.x;
   const int sy  = blockIdx.y;
   const int tid = threadIdx.x, nt = blockDim.x;
   const int start_symbol = jp->start_symbol, nof_symbols = jp->nof_symbols;
   if (sy < start_symbol || sy >= start_symbol + nof_symbols)
     return;
-  const unsigned dmask     = dmrs_prb_mask(jp->dmrs_type, jp->nof_cdm_groups_without_data);
-  const unsigned dmrs_syms = jp->dmrs_symbols_mask;
-  const int      nprb_grid = jp->grid_nof_prb, nres = jp->nof_reserved;
-  const int      bwp0 = jp->bwp_start_rb, bwp1 = bwp0 + jp->bwp_size_rb;
-  if (tid < 5)
-    rbm[tid] = jp->rb_mask[tid];
-  if (tid >= 32 && tid < 32 + 5 * nres)
-    resm[(tid - 32) / 5][(tid - 32) % 5] = jp->reserved[(tid - 32) / 5].prb_mask[(tid - 32) % 5];
-  __syncthreads();
-  build_prb_list(rbm, nprb_grid, 0, prb_of, &nprb_s, tid, nt);
-  __syncthreads();
-  const int nprb = nprb_s;
-  // reserved patterns: re_mask / symbols per pattern (uniform registers)
-  unsigned res_re[4] = {0, 0, 0, 0}, res_sy[4] = {0, 0, 0, 0};
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    if (r < nres) {
-      res_re[r] = jp->reserved[r].re_mask;
-      res_sy[r] = jp->reserved[r].symbols;
-    }
-  // data REs per PRB of this symbol; the elements of the transmission in earlier symbols were counted by pdsch_seq_kernel
-  const int prefix = prefix_base[blockIdx.x * 14 + sy];
-  {
-    const int s = sy;
-    for (int i = tid; i < nprb; i += nt) {
-      const int rb = prb_of[i];
-      unsigned  ex = (((dmrs_syms >> s) & 1u) && rb >= bwp0 && rb < bwp1) ? dmask : 0u;
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (r < nres && ((res_sy[r] >> s) & 1u) && ((resm[r][rb >> 6] >> (rb & 63)) & 1ull))
-          ex |= res_re[r];
-      keep_of[i] = (uint16_t)(~ex & 0xfffu);
-    }
-  }
-  __syncthreads();
-  // exclusive scan of the per-PRB counts of this symbol (<= 275 entries: one wavefront, 5 entries per lane)
-  if (tid < 64) {
-    int c[5], sum = 0;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const int i = tid * 5 + q;
-      c[q]        = (i < nprb) ? __popc((unsigned)keep_of[i]) : 0;
-      sum += c[q];
-    }
-    int inc = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(inc, o);
-      inc += (tid >= o) ? v : 0;
-    }
-    int run = inc - sum;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const int i = tid * 5 + q;
-      if (i < nprb)
-        off_of[i] = (uint16_t)run;
-      run += c[q];
-    }
-    if (tid == 63)
-      red[4] = inc;
-  }
-  __syncthreads();
-  const int n_re = red[4];
-  if (n_re == 0)
+  const int prefix = prefix_base[blockIdx.x * 14 + sy]; // elements of the transmission in earlier symbols (pdsch_seq_kernel)
+  if (pdsch_symbol_setup(*jp, sy, S, tid, nt) == 0)
     return;
   const int       mod = jp->mod;
   const uint32_t* seq = seq_base + (size_t)blockIdx.x * PDSCH_SEQ_STRIDE;
-  const float    scaling = jp->scaling;
-  const bool     scale   = isnormal(scaling);
-  const uint8_t* cw      = cw_base + jp->cw_offset;
-  float2*        g       = grid + jp->grid_offset + ((size_t)jp->port * 14 + sy) * (nprb_grid * 12);
-  // The common shapes (16QAM / 256QAM, codeword aligned to its element size) in two sweeps: every request of the thread's resource elements --
-  // the element's bytes as one wide load and the two words of its scrambling window -- is issued before the first element is mapped, with
-  // unconditional loads (an element that carries no data reads element 0 of the symbol and is not stored). The one-element-at-a-time loop
-  // below paid one memory round trip per element: thirteen per thread on 273 PRBs.
-  auto fast = [&](auto MODC) {
-    constexpr int MOD = decltype(MODC)::value;
-    constexpr int IT = (275 * 12 + 255) / 256;
-    uint32_t      lo[IT], hi[IT], q0[IT], q1[IT];
-    int           dst[IT]; // grid column of the element, -1: none
-    uint32_t      sh[IT], dd[IT];
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int      idx  = tid + it * 256;
-      const bool     in   = idx < nprb * 12;
-      const int      i    = in ? idx / 12 : 0, k = in ? idx - i * 12 : 0;
-      const unsigned keep = keep_of[i];
-      const bool     has  = in && ((keep >> k) & 1u);
-      const int      j    = has ? off_of[i] + __popc(keep & ((1u << k) - 1u)) : 0;
-      const uint32_t d    = (uint32_t)prefix + (uint32_t)j;
-      const uint32_t bi   = d * (uint32_t)MOD;
-      q0[it] = seq[bi >> 5], q1[it] = seq[(bi >> 5) + 1];
-      sh[it] = bi & 31u, dd[it] = d;
-      if (MOD == 8) {
-        const uint2 v = *reinterpret_cast<const uint2*>(cw + (size_t)d * 8);
-        lo[it] = v.x, hi[it] = v.y;
-      } else {
-        lo[it] = *reinterpret_cast<const uint32_t*>(cw + (size_t)d * 4), hi[it] = 0;
-      }
-      dst[it] = has ? (int)prb_of[i] * 12 + k : -1;
-    }
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const uint32_t cb  = (uint32_t)((((uint64_t)q1[it] << 32) | q0[it]) >> sh[it]);
-      const uint32_t raw = (((lo[it] & 0x01010101u) * 0x01020408u) >> 24) | ((((hi[it] & 0x01010101u) * 0x01020408u) >> 24) << 4);
-      const uint32_t nat = (raw ^ cb) & ((1u << MOD) - 1u);
-      float2         x   = map_symbol(MOD, nat, dd[it]);
-      if (scale) {
-        x.x = x.x * scaling;
-        x.y = x.y * scaling;
-      }
-      if (dst[it] >= 0)
-        g[dst[it]] = x;
-    }
-  };
-  if (mod == 8 && (((uintptr_t)(cw + (size_t)prefix * 8)) & 7u) == 0) {
-    fast(std::integral_constant<int, 8>{});
+  const float     scaling = jp->scaling;
+  const bool      scale   = isnormal(scaling);
+  const uint8_t*  cw      = cw_base + jp->cw_offset;
+  float2* const   g[4]    = {grid + jp->grid_offset + ((size_t)jp->port * 14 + sy) * (jp->grid_nof_prb * 12), nullptr, nullptr, nullptr};
+  if (mod == 8 && (((uintptr_t)(cw + (size_t)prefix * 8)) & 3u) == 0) {
+    pdsch_layers_fast<1, 8>(S, prefix, seq, cw, g, scale, scaling, tid);
     return;
   }
   if (mod == 4 && (((uintptr_t)(cw + (size_t)prefix * 4)) & 3u) == 0) {
-    fast(std::integral_constant<int, 4>{});
+    pdsch_layers_fast<1, 4>(S, prefix, seq, cw, g, scale, scaling, tid);
     return;
   }
-  for (int idx = tid; idx < nprb * 12; idx += nt) {
-    const int      i = idx / 12, k = idx - i * 12;
-    const unsigned keep = keep_of[i];
-    if (!((keep >> k) & 1u))
-      continue;
-    const int      j  = off_of[i] + __popc(keep & ((1u << k) - 1u)); // RE index within the symbol
-    const size_t   d  = (size_t)prefix + j;                           // symbol index within the codeword
-    const uint32_t bi = (uint32_t)d * (uint32_t)mod;                  // its first bit: position in the transmission's scrambling sequence
-    const uint64_t two = (uint64_t)seq[bi >> 5] | ((uint64_t)seq[(bi >> 5) + 1] << 32);
-    const uint32_t cb  = (uint32_t)(two >> (bi & 31)); // scrambling bits of this RE, bit t = t-th bit
-    // the symbol's bits (one per byte), b0 first, gathered into bit t = t-th bit: one wide load where the run of bytes is aligned, then
-    // bit 0 of every byte through a multiplication ((x & 0x01010101) * 0x01020408 puts bytes 0..3 into bits 24..27)
-    const uint8_t* cp  = cw + d * mod;
-    uint32_t       raw = 0;
-    if (mod == 8 && (((uintptr_t)cp) & 7u) == 0) {
-      const uint2 v = *reinterpret_cast<const uint2*>(cp);
-      raw           = (((v.x & 0x01010101u) * 0x01020408u) >> 24) | ((((v.y & 0x01010101u) * 0x01020408u) >> 24) << 4);
-    } else if (mod == 4 && (((uintptr_t)cp) & 3u) == 0) {
-      raw = ((*reinterpret_cast<const uint32_t*>(cp) & 0x01010101u) * 0x01020408u) >> 24;
-    } else if (mod == 2 && (((uintptr_t)cp) & 1u) == 0) {
-      const uint32_t v = *reinterpret_cast<const uint16_t*>(cp);
-      raw              = (v & 1u) | ((v >> 7) & 2u);
-    } else if (mod == 6 && (((uintptr_t)cp) & 1u) == 0) {
-      const uint16_t* c2 = reinterpret_cast<const uint16_t*>(cp);
-      const uint32_t  v0 = c2[0], v1 = c2[1], v2 = c2[2];
-      raw = (v0 & 1u) | ((v0 >> 7) & 2u) | ((v1 & 1u) << 2) | ((v1 >> 5) & 8u) | ((v2 & 1u) << 4) | ((v2 >> 3) & 32u);
-    } else {
-      for (int t = 0; t < mod; ++t)
-        raw |= (uint32_t)(cp[t] & 1u) << t;
-    }
-    const uint32_t nat = (raw ^ cb) & ((1u << mod) - 1u); // scrambled bits, bit t = t-th bit of the symbol (b0 first)
-    float2 x = map_symbol(mod, nat, (unsigned)d);
-    if (scale) {
-      x.x = x.x * scaling;
-      x.y = x.y * scaling;
-    }
-    g[prb_of[i] * 12 + k] = x;
-  }
+  pdsch_map_elements(S, 1, mod, prefix, seq, cw, g, scale, scaling, tid, nt);
 }
 
 __global__ void __launch_bounds__(256) dmrs_pdsch_kernel(const miphy_dmrs_pdsch_job* __restrict__ jobs, const gold_tables* __restrict__ gt,
@@ -546,19 +615,34 @@ __global__ void __launch_bounds__(256) csi_rs_kernel(const miphy_csi_rs_job* __r
   }
 }
 
+
 // ---------------------------------------------------------------------------------------------------- one codeword on 1..4 layers
-// TS 38.211 7.3.1.3: x^(ly)(i) = d(L i + ly); layer ly goes to grid port ports[ly], no precoding. Beyond the 23.5 reference (whose layer
-// mapper is broken), so the contract is the oracle's orc_pdsch_modulate. The resource element of rank i_re in the transmission owns the
-// codeword symbols L i_re .. L i_re + L - 1: L mod consecutive bytes of the codeword and L mod <= 32 consecutive bits of the scrambling
-// sequence, so one thread maps all layers of its element from one run of bytes and one 64-bit window of two sequence words.
+// Beyond the 23.5 reference (whose layer mapper is broken), so the contract is the oracle's orc_pdsch_modulate.
 constexpr int PDSCH_SEQ_CHUNK = PDSCH_SEQ_STRIDE / 2; // sequence words one workgroup of pdsch_seq_layers_kernel generates (x1 and x2 in LDS)
 constexpr int PDSCH_LAYERS_INFO = 16;                 // ints per transmission: 14 symbol prefixes, the elements per layer, 1 = valid job
+
+// What the fields of a modulator job j must satisfy, once: R(condition, message of the host, its arguments). The kernels skip a device-resident
+// job that breaks a rule (pdsch_mod_fields_ok), the host refuses one with the rule's message (miphy_pdsch_mod_job_check).
+#define PDSCH_MOD_FIELD_RULES(R)                                                                                                                       \
+  R(j.mod == 1 || j.mod == 2 || j.mod == 4 || j.mod == 6 || j.mod == 8, "invalid modulation order %u", j.mod)                                         \
+  R(j.nof_symbols >= 1 && j.start_symbol + j.nof_symbols <= 14, "invalid time allocation")                                                            \
+  R(j.dmrs_type == 1 || j.dmrs_type == 2, "invalid DM-RS type")                                                                                       \
+  R(j.nof_cdm_groups_without_data >= 1 && j.nof_cdm_groups_without_data <= (j.dmrs_type == 1 ? 2 : 3), "invalid number of CDM groups without data")   \
+  R(j.grid_nof_prb >= 1 && j.grid_nof_prb <= 275 && j.bwp_start_rb + j.bwp_size_rb <= 275, "invalid grid / BWP")                                      \
+  R(j.nof_reserved <= 4, "at most 4 reserved RE patterns (re_pattern_list::MAX_RE_PATTERN)")                                                          \
+  R(j.n_id < 1024 && j.rnti < 65536, "invalid scrambling identifiers")
+
+__host__ __device__ __forceinline__ bool pdsch_mod_fields_ok(const miphy_pdsch_mod_job& j)
+{
+#define PDSCH_RULE_HOLDS(cond, ...) &&(cond)
+  return true PDSCH_MOD_FIELD_RULES(PDSCH_RULE_HOLDS);
+#undef PDSCH_RULE_HOLDS
+}
 
 // What the kernels check of a job themselves (device-resident jobs reach them unseen by the host): a job that fails is skipped.
 __device__ __forceinline__ bool layers_job_ok(const miphy_pdsch_mod_layers_job& j)
 {
-  const miphy_pdsch_mod_job& b = j.base;
-  const unsigned             L = j.nof_layers;
+  const unsigned L = j.nof_layers;
   if (L < 1 || L > 4)
     return false;
   unsigned seen = 0;
@@ -568,9 +652,7 @@ __device__ __forceinline__ bool layers_job_ok(const miphy_pdsch_mod_layers_job& 
       return false;
     seen |= 1u << p;
   }
-  return (b.mod == 1 || b.mod == 2 || b.mod == 4 || b.mod == 6 || b.mod == 8) && b.nof_symbols >= 1 && b.start_symbol + b.nof_symbols <= 14 &&
-         (b.dmrs_type == 1 || b.dmrs_type == 2) && b.nof_cdm_groups_without_data >= 1 && b.nof_cdm_groups_without_data <= (b.dmrs_type == 1 ? 2 : 3) &&
-         b.grid_nof_prb >= 1 && b.grid_nof_prb <= 275 && b.bwp_start_rb + b.bwp_size_rb <= 275 && b.nof_reserved <= 4 && b.n_id < 1024 && b.rnti < 65536;
+  return pdsch_mod_fields_ok(j.base);
 }
 
 // Both LFSR sequences of c(n), held as words in LDS, from `have` (>= 31) to nwords words: the word recurrences w[i] = w[i-28] ^ w[i-31] (x1) and
@@ -617,29 +699,7 @@ __global__ void __launch_bounds__(512) pdsch_seq_layers_kernel(const miphy_pdsch
         info[15] = 0;
       return;
     }
-    const unsigned dmask     = dmrs_prb_mask(jp->dmrs_type, jp->nof_cdm_groups_without_data);
-    const unsigned dmrs_syms = jp->dmrs_symbols_mask;
-    const int      nprb_grid = jp->grid_nof_prb, nres = jp->nof_reserved;
-    const int      bwp0 = jp->bwp_start_rb, bwp1 = bwp0 + jp->bwp_size_rb;
-    const int      s0 = jp->start_symbol, s1 = s0 + jp->nof_symbols;
-    if (tid < 5)
-      rbm[tid] = jp->rb_mask[tid];
-    if (tid >= 32 && tid < 32 + 5 * nres)
-      resm[(tid - 32) / 5][(tid - 32) % 5] = jp->reserved[(tid - 32) / 5].prb_mask[(tid - 32) % 5];
-    if (tid >= 64 && tid < 78)
-      cnt[tid - 64] = 0;
-    __syncthreads();
-    for (int q = tid; q < 14 * nprb_grid; q += nt) {
-      const int s = q / nprb_grid, rb = q - s * nprb_grid;
-      if (s < s0 || s >= s1 || !((rbm[rb >> 6] >> (rb & 63)) & 1ull))
-        continue;
-      unsigned ex = (((dmrs_syms >> s) & 1u) && rb >= bwp0 && rb < bwp1) ? dmask : 0u;
-      for (int r = 0; r < nres; ++r)
-        if (((jp->reserved[r].symbols >> s) & 1u) && ((resm[r][rb >> 6] >> (rb & 63)) & 1ull))
-          ex |= jp->reserved[r].re_mask;
-      atomicAdd(&cnt[s], __popc(~ex & 0xfffu));
-    }
-    __syncthreads();
+    pdsch_count_symbols(*jp, rbm, resm, cnt, tid, nt);
     if (tid == 0) {
       int run = 0;
       for (int s = 0; s < 14; ++s) {
@@ -668,71 +728,11 @@ __global__ void __launch_bounds__(512) pdsch_seq_layers_kernel(const miphy_pdsch
     o[i] = w1[i] ^ w2[i];
 }
 
-// The common shapes of pdsch_mod_layers_kernel (16QAM / 256QAM, the element's run of bytes aligned to words) as in pdsch_mod_kernel: the loads of a
-// group of the thread's elements -- the LL x MOD bytes of each as one wide load and the two words of its scrambling window -- are issued before
-// the first of them is mapped, unconditionally (an element that carries no data reads element 0 of the symbol and is not stored). The group
-// shrinks as the element grows, so that the loaded words stay in registers.
-template <int LL, int MOD>
-__device__ __forceinline__ void pdsch_layers_fast(int tid, int nprb, int prefix, const uint16_t* prb_of, const uint16_t* keep_of, const uint16_t* off_of,
-                                                  const uint32_t* __restrict__ seq, const uint8_t* __restrict__ cw, float2* const (&g)[4], bool scale,
-                                                  float scaling)
-{
-  constexpr int NW = LL * MOD / 4; // codeword words of one element
-  constexpr int IT = (275 * 12 + 255) / 256, G = NW >= 6 ? 4 : (NW >= 3 ? 7 : IT);
-  struct alignas(4) words {
-    uint32_t v[NW];
-  };
-  for (int it0 = 0; it0 < IT && it0 * 256 < nprb * 12; it0 += G) {
-    words    cv[G];
-    uint32_t q0[G], q1[G], sh[G];
-    int      dst[G]; // grid column of the element, -1: none
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-      const int      idx  = tid + (it0 + u) * 256;
-      const bool     in   = idx < nprb * 12;
-      const int      i    = in ? idx / 12 : 0, k = in ? idx - i * 12 : 0;
-      const unsigned keep = keep_of[i];
-      const bool     has  = in && ((keep >> k) & 1u);
-      const int      j    = has ? off_of[i] + __popc(keep & ((1u << k) - 1u)) : 0;
-      const uint32_t d0   = ((uint32_t)prefix + (uint32_t)j) * (uint32_t)LL; // first codeword symbol of the element
-      const uint32_t bi   = d0 * (uint32_t)MOD;
-      q0[u] = seq[bi >> 5], q1[u] = seq[(bi >> 5) + 1];
-      sh[u]  = bi & 31u;
-      cv[u]  = *reinterpret_cast<const words*>(cw + (size_t)d0 * MOD);
-      dst[u] = has ? (int)prb_of[i] * 12 + k : -1;
-    }
-#pragma unroll
-    for (int u = 0; u < G; ++u) {
-      const uint32_t cb  = (uint32_t)((((uint64_t)q1[u] << 32) | q0[u]) >> sh[u]);
-      uint32_t       raw = 0;
-#pragma unroll
-      for (int w = 0; w < NW; ++w)
-        raw |= (((cv[u].v[w] & 0x01010101u) * 0x01020408u) >> 24) << (4 * w);
-      const uint32_t bits = raw ^ cb; // scrambled bits of the element, layer after layer
-#pragma unroll
-      for (int ly = 0; ly < LL; ++ly) {
-        float2 x = map_symbol(MOD, (bits >> (ly * MOD)) & ((1u << MOD) - 1u), 0u);
-        if (scale) {
-          x.x = x.x * scaling;
-          x.y = x.y * scaling;
-        }
-        if (dst[u] >= 0)
-          g[ly][dst[u]] = x;
-      }
-    }
-  }
-}
-
-// Same geometry as pdsch_mod_kernel: one workgroup per (transmission, OFDM symbol), the PRB list, the keep masks and the exclusive scan in LDS.
 __global__ void __launch_bounds__(256) pdsch_mod_layers_kernel(const miphy_pdsch_mod_layers_job* __restrict__ jobs, const uint8_t* __restrict__ cw_base,
                                                                float2* __restrict__ grid, const uint32_t* __restrict__ seq_base,
                                                                const int* __restrict__ info_base, uint32_t stride)
 {
-  __shared__ uint16_t prb_of[276];
-  __shared__ uint16_t keep_of[276]; // per allocated PRB: 12-bit mask of the REs that carry data in this symbol
-  __shared__ uint16_t off_of[276];  // per allocated PRB: index of its first data RE within the symbol
-  __shared__ uint64_t rbm[5], resm[4][5];
-  __shared__ int      nprb_s, n_re_s;
+  __shared__ pdsch_symbol_lds S;
   const miphy_pdsch_mod_layers_job* __restrict__ lj = jobs + blockIdx.x;
   const miphy_pdsch_mod_job* __restrict__ jp        = &lj->base;
   const int* info = info_base + (size_t)blockIdx.x * PDSCH_LAYERS_INFO;
@@ -742,78 +742,21 @@ __global__ void __launch_bounds__(256) pdsch_mod_layers_kernel(const miphy_pdsch
   const int start_symbol = jp->start_symbol, nof_symbols = jp->nof_symbols;
   if (sy < start_symbol || sy >= start_symbol + nof_symbols)
     return;
-  const unsigned dmask     = dmrs_prb_mask(jp->dmrs_type, jp->nof_cdm_groups_without_data);
-  const unsigned dmrs_syms = jp->dmrs_symbols_mask;
-  const int      nprb_grid = jp->grid_nof_prb, nres = jp->nof_reserved;
-  const int      bwp0 = jp->bwp_start_rb, bwp1 = bwp0 + jp->bwp_size_rb;
-  if (tid < 5)
-    rbm[tid] = jp->rb_mask[tid];
-  if (tid >= 32 && tid < 32 + 5 * nres)
-    resm[(tid - 32) / 5][(tid - 32) % 5] = jp->reserved[(tid - 32) / 5].prb_mask[(tid - 32) % 5];
-  __syncthreads();
-  build_prb_list(rbm, nprb_grid, 0, prb_of, &nprb_s, tid, nt);
-  __syncthreads();
-  const int nprb = nprb_s;
-  unsigned  res_re[4] = {0, 0, 0, 0}, res_sy[4] = {0, 0, 0, 0};
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    if (r < nres) {
-      res_re[r] = jp->reserved[r].re_mask;
-      res_sy[r] = jp->reserved[r].symbols;
-    }
   const int prefix = info[sy]; // elements per layer of the transmission in earlier symbols
-  for (int i = tid; i < nprb; i += nt) {
-    const int rb = prb_of[i];
-    unsigned  ex = (((dmrs_syms >> sy) & 1u) && rb >= bwp0 && rb < bwp1) ? dmask : 0u;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (r < nres && ((res_sy[r] >> sy) & 1u) && ((resm[r][rb >> 6] >> (rb & 63)) & 1ull))
-        ex |= res_re[r];
-    keep_of[i] = (uint16_t)(~ex & 0xfffu);
-  }
-  __syncthreads();
-  // exclusive scan of the per-PRB counts of this symbol (<= 275 entries: one wavefront, 5 entries per lane)
-  if (tid < 64) {
-    int c[5], sum = 0;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const int i = tid * 5 + q;
-      c[q]        = (i < nprb) ? __popc((unsigned)keep_of[i]) : 0;
-      sum += c[q];
-    }
-    int inc = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(inc, o);
-      inc += (tid >= o) ? v : 0;
-    }
-    int run = inc - sum;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      const int i = tid * 5 + q;
-      if (i < nprb)
-        off_of[i] = (uint16_t)run;
-      run += c[q];
-    }
-    if (tid == 63)
-      n_re_s = inc;
-  }
-  __syncthreads();
-  if (n_re_s == 0)
+  if (pdsch_symbol_setup(*jp, sy, S, tid, nt) == 0)
     return;
   const int       mod = jp->mod, L = lj->nof_layers;
   const uint32_t* seq = seq_base + (size_t)blockIdx.x * stride;
   const float     scaling = jp->scaling;
   const bool      scale   = isnormal(scaling);
   const uint8_t*  cw      = cw_base + jp->cw_offset;
-  const int       nsc     = nprb_grid * 12;
+  const int       nsc     = jp->grid_nof_prb * 12;
   float2*         g[4];
 #pragma unroll
   for (int ly = 0; ly < 4; ++ly)
     g[ly] = grid + jp->grid_offset + ((size_t)lj->ports[ly < L ? ly : 0] * 14 + sy) * nsc;
-  // Bit offsets stay in 32 bits: the longest codeword is 4 layers x 275 PRB x 12 x 14 symbols x 8 bits = 1 478 400 bits.
   if ((mod == 4 || mod == 8) && (((uintptr_t)(cw + (size_t)prefix * L * mod)) & 3u) == 0) {
-#define MIPHY_LAYERS_FAST(LL, MOD) pdsch_layers_fast<LL, MOD>(tid, nprb, prefix, prb_of, keep_of, off_of, seq, cw, g, scale, scaling)
+#define MIPHY_LAYERS_FAST(LL, MOD) pdsch_layers_fast<LL, MOD>(S, prefix, seq, cw, g, scale, scaling, tid)
     switch (L * 16 + mod) {
       case 1 * 16 + 4: MIPHY_LAYERS_FAST(1, 4); break;
       case 2 * 16 + 4: MIPHY_LAYERS_FAST(2, 4); break;
@@ -827,52 +770,17 @@ __global__ void __launch_bounds__(256) pdsch_mod_layers_kernel(const miphy_pdsch
 #undef MIPHY_LAYERS_FAST
     return;
   }
-  const uint32_t mask = (1u << mod) - 1u;
-  for (int idx = tid; idx < nprb * 12; idx += nt) {
-    const int      i = idx / 12, k = idx - i * 12;
-    const unsigned keep = keep_of[i];
-    if (!((keep >> k) & 1u))
-      continue;
-    const int      j  = off_of[i] + __popc(keep & ((1u << k) - 1u)); // RE index within the symbol
-    const uint32_t d0 = ((uint32_t)prefix + (uint32_t)j) * (uint32_t)L; // first codeword symbol of the element
-    const uint32_t bi = d0 * (uint32_t)mod;                             // its first bit: position in the transmission's scrambling sequence
-    const uint64_t two = (uint64_t)seq[bi >> 5] | ((uint64_t)seq[(bi >> 5) + 1] << 32);
-    const uint32_t cb  = (uint32_t)(two >> (bi & 31)); // scrambling bits of the element's L symbols, bit t = t-th bit
-    const uint8_t* cp  = cw + (size_t)bi;
-    const int      col = prb_of[i] * 12 + k;
-#pragma unroll
-    for (int ly = 0; ly < 4; ++ly) {
-      if (ly >= L)
-        break;
-      uint32_t raw = 0;
-      for (int t = 0; t < mod; ++t)
-        raw |= (uint32_t)(cp[ly * mod + t] & 1u) << t;
-      float2 x = map_symbol(mod, (raw ^ (cb >> (ly * mod))) & mask, d0 + (uint32_t)ly); // pi/2-BPSK turns with the parity of the codeword symbol
-      if (scale) {
-        x.x = x.x * scaling;
-        x.y = x.y * scaling;
-      }
-      g[ly][col] = x;
-    }
-  }
+  pdsch_map_elements(S, L, mod, prefix, seq, cw, g, scale, scaling, tid, nt);
 }
 
 uint32_t host_nof_re(const miphy_pdsch_mod_job& j)
 {
-  unsigned dm = 0;
-  for (unsigned k = 0; k < 12; ++k)
-    dm |= ((j.dmrs_type == 1) ? ((k % 2) < j.nof_cdm_groups_without_data) : ((k % 6) < 2u * j.nof_cdm_groups_without_data)) ? (1u << k) : 0u;
-  uint32_t n = 0;
+  const pdsch_keep_rule keep = pdsch_keep_rule_of(j);
+  uint32_t              n    = 0;
   for (unsigned s = j.start_symbol; s < (unsigned)j.start_symbol + j.nof_symbols && s < 14; ++s)
-    for (unsigned rb = 0; rb < j.grid_nof_prb; ++rb) {
-      if (!((j.rb_mask[rb >> 6] >> (rb & 63)) & 1ull))
-        continue;
-      unsigned ex = (((j.dmrs_symbols_mask >> s) & 1u) && rb >= j.bwp_start_rb && rb < (unsigned)j.bwp_start_rb + j.bwp_size_rb) ? dm : 0u;
-      for (unsigned r = 0; r < j.nof_reserved && r < 4; ++r)
-        if (((j.reserved[r].symbols >> s) & 1u) && ((j.reserved[r].prb_mask[rb >> 6] >> (rb & 63)) & 1ull))
-          ex |= j.reserved[r].re_mask;
-      n += (uint32_t)__builtin_popcount(~ex & 0xfffu);
-    }
+    for (unsigned rb = 0; rb < j.grid_nof_prb; ++rb)
+      if ((j.rb_mask[rb >> 6] >> (rb & 63)) & 1ull)
+        n += (uint32_t)__builtin_popcount(pdsch_keep_mask(keep, s, rb, j.reserved[0].prb_mask, sizeof(miphy_re_pattern) / sizeof(uint64_t)));
   return n;
 }
 
@@ -885,6 +793,30 @@ extern "C" uint32_t miphy_pdsch_mod_nof_re(const miphy_pdsch_mod_job* j)
   return host_nof_re(*j);
 }
 
+int miphy_pdsch_mod_job_check(const char* who, const char* what, uint32_t i, const miphy_pdsch_mod_job& j, unsigned L, const uint8_t* ports, uint32_t nof_re)
+{
+  MIPHY_REQUIRE(L >= 1 && L <= 4, "%s: %s %u: invalid number of layers %u (one codeword: 1..4)", who, what, i, L);
+  for (unsigned a = 0; ports && a < L; ++a) {
+    MIPHY_REQUIRE(ports[a] < 16, "%s: %s %u: invalid port %u of layer %u", who, what, i, (unsigned)ports[a], a);
+    for (unsigned b = 0; b < a; ++b)
+      MIPHY_REQUIRE(ports[a] != ports[b], "%s: %s %u: layers %u and %u share port %u", who, what, i, b, a, (unsigned)ports[a]);
+  }
+#define PDSCH_RULE_REQUIRE(cond, fmt, ...) MIPHY_REQUIRE(cond, "%s: %s %u: " fmt, who, what, i, ##__VA_ARGS__);
+  PDSCH_MOD_FIELD_RULES(PDSCH_RULE_REQUIRE)
+#undef PDSCH_RULE_REQUIRE
+  if (!ports)
+    MIPHY_REQUIRE(j.port < 16, "%s: %s %u: invalid port", who, what, i);
+  // pdsch_modulator_impl.cpp:158-160: every element of every layer must be mapped
+  if (nof_re == 0)
+    nof_re = host_nof_re(j);
+  const uint32_t holds = nof_re * L * j.mod;
+  if (!ports)
+    MIPHY_REQUIRE(j.nof_bits == holds, "%s: %s %u: codeword of %u bits, the allocation holds %u", who, what, i, j.nof_bits, holds);
+  else
+    MIPHY_REQUIRE(j.nof_bits == holds, "%s: %s %u: codeword of %u bits, the allocation holds %u on %u layers", who, what, i, j.nof_bits, holds, L);
+  return MIPHY_OK;
+}
+
 extern "C" int miphy_pdsch_modulate_batch(miphy_ctx* ctx, const miphy_pdsch_mod_job* jobs, int jobs_on_device, uint32_t n, const uint8_t* codewords,
                                           float* grid, void* stream)
 {
@@ -892,23 +824,9 @@ extern "C" int miphy_pdsch_modulate_batch(miphy_ctx* ctx, const miphy_pdsch_mod_
   if (n == 0)
     return MIPHY_OK;
   MIPHY_REQUIRE(n <= 65535, "pdsch_modulate: batch too large (max 65535 transmissions per call)");
-  if (!jobs_on_device) {
-    for (uint32_t i = 0; i < n; ++i) {
-      const miphy_pdsch_mod_job& j = jobs[i];
-      MIPHY_REQUIRE(j.mod == 1 || j.mod == 2 || j.mod == 4 || j.mod == 6 || j.mod == 8, "pdsch_modulate: job %u: invalid modulation order %u", i, j.mod);
-      MIPHY_REQUIRE(j.nof_symbols >= 1 && j.start_symbol + j.nof_symbols <= 14, "pdsch_modulate: job %u: invalid time allocation", i);
-      MIPHY_REQUIRE(j.dmrs_type == 1 || j.dmrs_type == 2, "pdsch_modulate: job %u: invalid DM-RS type", i);
-      MIPHY_REQUIRE(j.nof_cdm_groups_without_data >= 1 && j.nof_cdm_groups_without_data <= (j.dmrs_type == 1 ? 2 : 3),
-                    "pdsch_modulate: job %u: invalid number of CDM groups without data", i);
-      MIPHY_REQUIRE(j.grid_nof_prb >= 1 && j.grid_nof_prb <= 275 && j.bwp_start_rb + j.bwp_size_rb <= 275, "pdsch_modulate: job %u: invalid grid / BWP", i);
-      MIPHY_REQUIRE(j.nof_reserved <= 4, "pdsch_modulate: job %u: at most 4 reserved RE patterns (re_pattern_list::MAX_RE_PATTERN)", i);
-      MIPHY_REQUIRE(j.n_id < 1024 && j.rnti < 65536, "pdsch_modulate: job %u: invalid scrambling identifiers", i);
-      MIPHY_REQUIRE(j.port < 16, "pdsch_modulate: job %u: invalid port", i);
-      // pdsch_modulator_impl.cpp:158-160: every element of the layer must be mapped
-      MIPHY_REQUIRE(j.nof_bits == host_nof_re(j) * j.mod, "pdsch_modulate: job %u: codeword of %u bits, the allocation holds %u", i, j.nof_bits,
-                    host_nof_re(j) * j.mod);
-    }
-  }
+  for (uint32_t i = 0; !jobs_on_device && i < n; ++i)
+    if (int rc = miphy_pdsch_mod_job_check("pdsch_modulate", "job", i, jobs[i], 1, nullptr, 0))
+      return rc;
   hipStream_t        s  = (hipStream_t)stream;
   const gold_tables* gt = nullptr;
   int                rc = miphy_get_gold_tables(ctx, &gt);
@@ -948,32 +866,6 @@ extern "C" uint32_t miphy_pdsch_mod_layers_nof_re(const miphy_pdsch_mod_layers_j
   return miphy_pdsch_mod_nof_re(&j->base);
 }
 
-int miphy_pdsch_mod_layers_check(const char* who, const char* what, uint32_t i, const miphy_pdsch_mod_layers_job& lj, uint32_t nof_re)
-{
-  const miphy_pdsch_mod_job& j = lj.base;
-  const unsigned             L = lj.nof_layers;
-  MIPHY_REQUIRE(L >= 1 && L <= 4, "%s: %s %u: invalid number of layers %u (one codeword: 1..4)", who, what, i, L);
-  for (unsigned a = 0; a < L; ++a) {
-    MIPHY_REQUIRE(lj.ports[a] < 16, "%s: %s %u: invalid port %u of layer %u", who, what, i, (unsigned)lj.ports[a], a);
-    for (unsigned b = 0; b < a; ++b)
-      MIPHY_REQUIRE(lj.ports[a] != lj.ports[b], "%s: %s %u: layers %u and %u share port %u", who, what, i, b, a, (unsigned)lj.ports[a]);
-  }
-  MIPHY_REQUIRE(j.mod == 1 || j.mod == 2 || j.mod == 4 || j.mod == 6 || j.mod == 8, "%s: %s %u: invalid modulation order %u", who, what, i, j.mod);
-  MIPHY_REQUIRE(j.nof_symbols >= 1 && j.start_symbol + j.nof_symbols <= 14, "%s: %s %u: invalid time allocation", who, what, i);
-  MIPHY_REQUIRE(j.dmrs_type == 1 || j.dmrs_type == 2, "%s: %s %u: invalid DM-RS type", who, what, i);
-  MIPHY_REQUIRE(j.nof_cdm_groups_without_data >= 1 && j.nof_cdm_groups_without_data <= (j.dmrs_type == 1 ? 2 : 3),
-                "%s: %s %u: invalid number of CDM groups without data", who, what, i);
-  MIPHY_REQUIRE(j.grid_nof_prb >= 1 && j.grid_nof_prb <= 275 && j.bwp_start_rb + j.bwp_size_rb <= 275, "%s: %s %u: invalid grid / BWP", who, what, i);
-  MIPHY_REQUIRE(j.nof_reserved <= 4, "%s: %s %u: at most 4 reserved RE patterns (re_pattern_list::MAX_RE_PATTERN)", who, what, i);
-  MIPHY_REQUIRE(j.n_id < 1024 && j.rnti < 65536, "%s: %s %u: invalid scrambling identifiers", who, what, i);
-  // every element of every layer must be mapped
-  if (nof_re == 0)
-    nof_re = host_nof_re(j);
-  MIPHY_REQUIRE(j.nof_bits == nof_re * L * j.mod, "%s: %s %u: codeword of %u bits, the allocation holds %u on %u layers", who, what, i, j.nof_bits,
-                nof_re * L * j.mod, L);
-  return MIPHY_OK;
-}
-
 extern "C" int miphy_pdsch_modulate_layers_batch(miphy_ctx* ctx, const miphy_pdsch_mod_layers_job* jobs, int jobs_on_device, uint32_t n, const uint8_t* codewords,
                                                  float* grid, void* stream)
 {
@@ -985,7 +877,7 @@ extern "C" int miphy_pdsch_modulate_layers_batch(miphy_ctx* ctx, const miphy_pds
   if (!jobs_on_device) {
     max_layers = 1;
     for (uint32_t i = 0; i < n; ++i) {
-      if (int rc = miphy_pdsch_mod_layers_check("pdsch_modulate_layers", "job", i, jobs[i], 0))
+      if (int rc = miphy_pdsch_mod_job_check("pdsch_modulate_layers", "job", i, jobs[i].base, jobs[i].nof_layers, jobs[i].ports, 0))
         return rc;
       max_layers = jobs[i].nof_layers > max_layers ? jobs[i].nof_layers : max_layers;
     }

@@ -34,44 +34,55 @@ extern "C" uint32_t miphy_pdsch_pdu_nof_re(const miphy_pdsch_pdu* pdu)
 }
 
 namespace {
-// What pdsch_processor_impl::process derives from a batch of PDUs: the encoder's transport-block records, the modulator jobs and the DM-RS jobs
-// (assert_pdu :143-196, modulate :256-276, put_dmrs :278-305); cw_bytes = bytes of the codeword area (one bit per byte).
-int derive_pdsch_jobs(const miphy_pdsch_pdu* pdus, uint32_t n, std::vector<miphy_pdsch_tb_desc>& tb, std::vector<miphy_pdsch_mod_job>& mj,
-                      std::vector<miphy_dmrs_pdsch_job>& dj, size_t& cw_bytes)
+// What pdsch_processor_impl::process derives from PDU i of a batch (assert_pdu :143-196, modulate :256-276, put_dmrs :278-305) for one codeword on L
+// layers: the encoder's transport-block record, the modulator job and the DM-RS job; cw_bytes = bytes of the codeword area so far (one bit per
+// byte), advanced by the PDU's codeword. ports: the grid port of each layer, null for the one-layer forms (L = 1 on p.port). Every rule of the
+// three steps that the PDU can break is checked here, so that a processor refuses a batch before it enqueues or allocates anything.
+int derive_pdsch_jobs(const char* who, uint32_t i, const miphy_pdsch_pdu& p, unsigned L, const uint8_t* ports, miphy_pdsch_tb_desc& t, miphy_pdsch_mod_job& m,
+                      miphy_dmrs_pdsch_job& d, size_t& cw_bytes)
+{
+  MIPHY_REQUIRE(p.dmrs_symbols_mask != 0 && p.dmrs_symbols_mask < (1u << 14), "pdsch_process: PDU %u: invalid DM-RS symbol mask", i);
+  MIPHY_REQUIRE(p.nof_symbols >= 1 && p.start_symbol + p.nof_symbols <= 14, "pdsch_process: PDU %u: the time allocation exceeds the slot", i);
+  const unsigned first_dmrs = __builtin_ctz(p.dmrs_symbols_mask), last_dmrs = 31 - __builtin_clz((unsigned)p.dmrs_symbols_mask);
+  MIPHY_REQUIRE(first_dmrs >= p.start_symbol && last_dmrs < (unsigned)p.start_symbol + p.nof_symbols,
+                "pdsch_process: PDU %u: DM-RS symbols outside the time allocation", i);
+  MIPHY_REQUIRE(p.nof_cdm_groups_without_data >= 1 && p.nof_cdm_groups_without_data <= 2, "pdsch_process: PDU %u: invalid number of CDM groups without data", i);
+  MIPHY_REQUIRE(p.tbs_lbrm_bytes > 0 && p.tbs_lbrm_bytes <= 66 * 384 / 8, "pdsch_process: PDU %u: invalid LBRM size (%u bytes)", i, p.tbs_lbrm_bytes);
+  MIPHY_REQUIRE(p.nof_reserved <= 4, "pdsch_process: PDU %u: at most 4 reserved RE patterns", i);
+  MIPHY_REQUIRE(p.bg == 1 || p.bg == 2, "pdsch_process: PDU %u: invalid base graph", i);
+  mod_job_of(p, m);
+  const uint32_t nre = miphy_pdsch_mod_nof_re(&m); // per layer
+  MIPHY_REQUIRE(nre > 0, "pdsch_process: PDU %u: invalid or empty allocation", i);
+  m.nof_bits  = nre * L * p.mod;
+  m.cw_offset = cw_bytes;
+  if (int rc = miphy_pdsch_mod_job_check(who, "PDU", i, m, L, ports, nre))
+    return rc;
+  MIPHY_REQUIRE(!p.ref_point_prb0 || p.bwp_start_rb < p.grid_nof_prb, "%s: PDU %u: reference point outside the grid", who, i);
+  t    = {};
+  t.bg = p.bg, t.rv = p.rv, t.mod = p.mod, t.nof_layers = (uint8_t)L, t.Nref = p.tbs_lbrm_bytes * 8, t.nof_ch_symbols = nre * L, t.tb_bytes = p.tb_bytes;
+  t.tb_offset = p.tb_offset, t.codeword_offset = cw_bytes;
+  d = {};
+  d.slot_in_frame = p.slot_in_frame, d.reference_point_k_rb = p.ref_point_prb0 ? p.bwp_start_rb : 0, d.scrambling_id = p.dmrs_scrambling_id;
+  d.amplitude = powf(10.0f, -p.ratio_pdsch_dmrs_to_sss_dB / 20.0f);
+  d.dmrs_type = 1, d.n_scid = p.n_scid, d.nof_ports = (uint8_t)L, d.symbols_mask = p.dmrs_symbols_mask, d.grid_nof_prb = p.grid_nof_prb;
+  for (unsigned ly = 0; ly < L; ++ly)
+    d.ports[ly] = ports ? ports[ly] : p.port;
+  for (int k = 0; k < 5; ++k)
+    d.rb_mask[k] = p.rb_mask[k];
+  d.grid_offset = p.grid_offset;
+  cw_bytes += ((size_t)m.nof_bits + 15u) & ~(size_t)15u;
+  return MIPHY_OK;
+}
+
+// The one-layer forms: every PDU of the batch on one layer, on its own port.
+int derive_one_layer_jobs(const miphy_pdsch_pdu* pdus, uint32_t n, std::vector<miphy_pdsch_tb_desc>& tb, std::vector<miphy_pdsch_mod_job>& mj,
+                          std::vector<miphy_dmrs_pdsch_job>& dj, size_t& cw_bytes)
 {
   tb.resize(n), mj.resize(n), dj.resize(n);
   cw_bytes = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    const miphy_pdsch_pdu& p = pdus[i];
-    MIPHY_REQUIRE(p.dmrs_symbols_mask != 0 && p.dmrs_symbols_mask < (1u << 14), "pdsch_process: PDU %u: invalid DM-RS symbol mask", i);
-    MIPHY_REQUIRE(p.nof_symbols >= 1 && p.start_symbol + p.nof_symbols <= 14, "pdsch_process: PDU %u: the time allocation exceeds the slot", i);
-    const unsigned first_dmrs = __builtin_ctz(p.dmrs_symbols_mask), last_dmrs = 31 - __builtin_clz((unsigned)p.dmrs_symbols_mask);
-    MIPHY_REQUIRE(first_dmrs >= p.start_symbol && last_dmrs < (unsigned)p.start_symbol + p.nof_symbols,
-                  "pdsch_process: PDU %u: DM-RS symbols outside the time allocation", i);
-    MIPHY_REQUIRE(p.nof_cdm_groups_without_data >= 1 && p.nof_cdm_groups_without_data <= 2, "pdsch_process: PDU %u: invalid number of CDM groups without data", i);
-    MIPHY_REQUIRE(p.tbs_lbrm_bytes > 0 && p.tbs_lbrm_bytes <= 66 * 384 / 8, "pdsch_process: PDU %u: invalid LBRM size (%u bytes)", i, p.tbs_lbrm_bytes);
-    MIPHY_REQUIRE(p.nof_reserved <= 4, "pdsch_process: PDU %u: at most 4 reserved RE patterns", i);
-    MIPHY_REQUIRE(p.bg == 1 || p.bg == 2, "pdsch_process: PDU %u: invalid base graph", i);
-    miphy_pdsch_mod_job& m = mj[i];
-    mod_job_of(p, m);
-    const uint32_t nre = miphy_pdsch_mod_nof_re(&m);
-    MIPHY_REQUIRE(nre > 0, "pdsch_process: PDU %u: invalid or empty allocation", i);
-    m.nof_bits  = nre * p.mod;
-    m.cw_offset = cw_bytes;
-    miphy_pdsch_tb_desc& t = tb[i];
-    t                      = {};
-    t.bg = p.bg, t.rv = p.rv, t.mod = p.mod, t.nof_layers = 1, t.Nref = p.tbs_lbrm_bytes * 8, t.nof_ch_symbols = nre, t.tb_bytes = p.tb_bytes;
-    t.tb_offset = p.tb_offset, t.codeword_offset = cw_bytes;
-    miphy_dmrs_pdsch_job& d = dj[i];
-    d                       = {};
-    d.slot_in_frame = p.slot_in_frame, d.reference_point_k_rb = p.ref_point_prb0 ? p.bwp_start_rb : 0, d.scrambling_id = p.dmrs_scrambling_id;
-    d.amplitude = powf(10.0f, -p.ratio_pdsch_dmrs_to_sss_dB / 20.0f);
-    d.dmrs_type = 1, d.n_scid = p.n_scid, d.nof_ports = 1, d.ports[0] = p.port, d.symbols_mask = p.dmrs_symbols_mask, d.grid_nof_prb = p.grid_nof_prb;
-    for (int k = 0; k < 5; ++k)
-      d.rb_mask[k] = p.rb_mask[k];
-    d.grid_offset = p.grid_offset;
-    cw_bytes += ((size_t)m.nof_bits + 15u) & ~(size_t)15u;
-  }
+  for (uint32_t i = 0; i < n; ++i)
+    if (int rc = derive_pdsch_jobs("pdsch_process", i, pdus[i], 1, nullptr, tb[i], mj[i], dj[i], cw_bytes))
+      return rc;
   return MIPHY_OK;
 }
 } // namespace
@@ -86,7 +97,7 @@ extern "C" int miphy_pdsch_process_batch(miphy_ctx* ctx, const miphy_pdsch_pdu* 
   std::vector<miphy_pdsch_mod_job>  mj;
   std::vector<miphy_dmrs_pdsch_job> dj;
   size_t                            cw_bytes = 0;
-  int                               rc = derive_pdsch_jobs(pdus, n, tb, mj, dj, cw_bytes);
+  int                               rc = derive_one_layer_jobs(pdus, n, tb, mj, dj, cw_bytes);
   if (rc)
     return rc;
   void* work = nullptr; // codewords (one bit per byte) in a workspace of the context
@@ -101,7 +112,7 @@ extern "C" int miphy_pdsch_process_batch(miphy_ctx* ctx, const miphy_pdsch_pdu* 
 }
 
 // ---- one codeword on 1..4 layers: the same composition with the encoder's nof_layers = L and nof_ch_symbols = REs x L, the layered modulator
-// and the DM-RS on L ports. Every PDU is checked before the encoder is enqueued.
+// and the DM-RS on L ports.
 extern "C" uint32_t miphy_pdsch_layers_pdu_nof_re(const miphy_pdsch_layers_pdu* pdu)
 {
   if (!pdu || pdu->nof_layers < 1 || pdu->nof_layers > 4)
@@ -116,48 +127,30 @@ extern "C" int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsc
     return MIPHY_OK;
   MIPHY_REQUIRE(n <= 65535, "pdsch_process_layers: at most 65535 PDUs per call");
   hipStream_t                             s = (hipStream_t)stream;
-  std::vector<miphy_pdsch_pdu>            base(n);
-  std::vector<miphy_pdsch_tb_desc>        tb;
-  std::vector<miphy_pdsch_mod_job>        mj;
-  std::vector<miphy_dmrs_pdsch_job>       dj;
+  std::vector<miphy_pdsch_tb_desc>        tb(n);
+  std::vector<miphy_dmrs_pdsch_job>       dj(n);
   std::vector<miphy_pdsch_mod_layers_job> lj(n);
+  size_t                                  cw_bytes   = 0;
+  uint32_t                                max_layers = 1;
+  int                                     rc;
   for (uint32_t i = 0; i < n; ++i) {
-    MIPHY_REQUIRE(pdus[i].nof_layers >= 1 && pdus[i].nof_layers <= 4, "pdsch_process_layers: PDU %u: invalid number of layers %u (one codeword: 1..4)", i,
-                  (unsigned)pdus[i].nof_layers);
-    base[i] = pdus[i].base;
-  }
-  size_t cw_bytes = 0; // (recounted below: a codeword on L layers is L times as long)
-  int    rc       = derive_pdsch_jobs(base.data(), n, tb, mj, dj, cw_bytes);
-  if (rc)
-    return rc;
-  cw_bytes            = 0;
-  uint32_t max_layers = 1;
-  for (uint32_t i = 0; i < n; ++i) {
-    const miphy_pdsch_layers_pdu& p   = pdus[i];
-    const uint32_t                L   = p.nof_layers, nre = tb[i].nof_ch_symbols; // REs per layer
-    MIPHY_REQUIRE(!p.base.ref_point_prb0 || p.base.bwp_start_rb < p.base.grid_nof_prb, "pdsch_process_layers: PDU %u: reference point outside the grid", i);
-    lj[i]               = {};
-    lj[i].base          = mj[i];
-    lj[i].base.nof_bits = nre * L * p.base.mod;
-    lj[i].base.cw_offset = cw_bytes;
-    lj[i].nof_layers    = (uint8_t)L;
+    const miphy_pdsch_layers_pdu& p = pdus[i];
+    const uint32_t                L = p.nof_layers;
+    lj[i] = {};
+    if ((rc = derive_pdsch_jobs("pdsch_process_layers", i, p.base, L, p.ports, tb[i], lj[i].base, dj[i], cw_bytes)))
+      return rc;
+    lj[i].nof_layers = (uint8_t)L;
     for (uint32_t ly = 0; ly < 4; ++ly)
       lj[i].ports[ly] = p.ports[ly];
-    if ((rc = miphy_pdsch_mod_layers_check("pdsch_process_layers", "PDU", i, lj[i], nre)))
-      return rc;
     max_layers = L > max_layers ? L : max_layers;
     // what the encoder accepts (sch.hip, ldpc_segmenter_impl.cpp:104-141): at most 52 codeblocks, none of them empty
+    const uint32_t nre = tb[i].nof_ch_symbols / L; // REs per layer
     const uint64_t tbs = (uint64_t)p.base.tb_bytes * 8, B = tbs + (tbs <= 3824 ? 16 : 24), Kcb = p.base.bg == 1 ? 8448 : 3840;
     const uint64_t ncb = B <= Kcb ? 1 : (B + Kcb - 24 - 1) / (Kcb - 24);
     MIPHY_REQUIRE(p.base.tb_bytes > 0 && ncb <= 52, "pdsch_process_layers: PDU %u: transport block of %u bytes outside what the encoder accepts (1 .. %u bytes on base graph %u)",
                   i, p.base.tb_bytes, p.base.bg == 1 ? 54753u : 24801u, (unsigned)p.base.bg);
     MIPHY_REQUIRE(p.base.rv <= 3, "pdsch_process_layers: PDU %u: invalid redundancy version", i);
     MIPHY_REQUIRE(nre >= ncb, "pdsch_process_layers: PDU %u: %u REs per layer cannot carry %u codeblocks", i, nre, (unsigned)ncb);
-    tb[i].nof_layers = (uint8_t)L, tb[i].nof_ch_symbols = nre * L, tb[i].codeword_offset = cw_bytes;
-    dj[i].nof_ports = (uint8_t)L;
-    for (uint32_t ly = 0; ly < L; ++ly)
-      dj[i].ports[ly] = p.ports[ly];
-    cw_bytes += ((size_t)lj[i].base.nof_bits + 15u) & ~(size_t)15u;
   }
   void* work = nullptr; // codewords (one bit per byte) in a workspace of the context
   if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, cw_bytes + 64, &work)))
@@ -165,7 +158,7 @@ extern "C" int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsc
   uint8_t* d_cw = static_cast<uint8_t*>(work);
   if ((rc = miphy_pdsch_encode_batch(ctx, tb.data(), n, tb_in, d_cw, s)))
     return rc;
-  if ((rc = miphy_pdsch_modulate_layers_enqueue(ctx, lj.data(), 0, n, max_layers, d_cw, grid, s))) // (checked above)
+  if ((rc = miphy_pdsch_modulate_layers_enqueue(ctx, lj.data(), 0, n, max_layers, d_cw, grid, s))) // (the jobs passed miphy_pdsch_mod_job_check in derive_pdsch_jobs)
     return rc;
   return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s);
 }
@@ -193,17 +186,9 @@ extern "C" int miphy_pdsch_process_plan_create(miphy_ctx* ctx, const miphy_pdsch
   std::vector<miphy_pdsch_mod_job>  mj;
   std::vector<miphy_dmrs_pdsch_job> dj;
   size_t                            cw_bytes = 0;
-  int                               rc = derive_pdsch_jobs(pdus, n, tb, mj, dj, cw_bytes);
+  int                               rc = derive_one_layer_jobs(pdus, n, tb, mj, dj, cw_bytes);
   if (rc)
     return rc;
-  for (uint32_t i = 0; i < n; ++i) { // what the modulator and DM-RS entry points check on host jobs (device jobs are the caller's promise)
-    const miphy_pdsch_pdu& q = pdus[i];
-    MIPHY_REQUIRE(q.mod == 1 || q.mod == 2 || q.mod == 4 || q.mod == 6 || q.mod == 8, "pdsch_process: PDU %u: invalid modulation order %u", i, q.mod);
-    MIPHY_REQUIRE(q.grid_nof_prb >= 1 && q.grid_nof_prb <= 275 && q.bwp_start_rb + q.bwp_size_rb <= 275, "pdsch_process: PDU %u: invalid grid / BWP", i);
-    MIPHY_REQUIRE(q.n_id < 1024 && q.rnti < 65536, "pdsch_process: PDU %u: invalid scrambling identifiers", i);
-    MIPHY_REQUIRE(q.port < 16, "pdsch_process: PDU %u: invalid port", i);
-    MIPHY_REQUIRE(!q.ref_point_prb0 || q.bwp_start_rb < q.grid_nof_prb, "pdsch_process: PDU %u: reference point outside the grid", i);
-  }
   auto* p = new miphy_pdsch_process_plan();
   p->ctx = ctx, p->n = n, p->enc = nullptr, p->d_buf = nullptr;
   if ((rc = miphy_get_gold_tables(ctx, &p->gt)) || (rc = miphy_pdsch_encode_prepare(ctx, tb.data(), n, &p->enc))) {

@@ -59,6 +59,14 @@ def cases():
     # two on the general path; every later piece starts from a jump of both shift registers
     out.append(_case("j_273prb_14sym_L3_mod8", 3, 8, 273, range(273), nof=14, dmrs=(2,), cdm=2))
     out.append(_case("j_275prb_6sym_L2_mod6", 2, 6, 275, range(275), start=4, nof=6))
+    # (k) the paths the one-layer and the layered entry point share, on the grid of (d). The 16QAM / 256QAM path at L = 1 with an odd codeword
+    # offset, an aligned one, and at 256QAM one that is a multiple of 4 bytes but not of 8
+    for mod, pad in ((4, 1), (4, 0), (8, 3), (8, 0), (8, 4)):
+        out.append(_case("k_L1_mod%d_pad%d" % (mod, pad), 1, mod, 12, range(0, 11), nof=2, dmrs=(1,), cdm=2, cw_pad=pad))
+    # ... the wide gathers of QPSK and 64QAM in the general loop at one and two layers, and QPSK on three, where the layers of one element start
+    # at different alignments
+    for L, mod, pad in ((1, 2, 1), (1, 2, 0), (2, 2, 1), (2, 2, 0), (1, 6, 3), (1, 6, 0), (2, 6, 1), (2, 6, 0), (3, 2, 1)):
+        out.append(_case("k_L%d_mod%d_pad%d" % (L, mod, pad), L, mod, 12, range(0, 11), nof=2, dmrs=(1,), cdm=2, cw_pad=pad))
     assert len({c["name"] for c in out}) == len(out)
     return out
 

@@ -359,3 +359,34 @@ def test_processor_rejects(ctx, k):
     assert "miphy error -1" in str(e.value)
     torch.cuda.synchronize()
     assert np.array_equal(D.bits(gd.cpu().numpy()), D.bits(bg))
+
+
+ALIKE_REJECTIONS = [  # (what to break in the base record, its port, the message all three processor forms give)
+    (lambda b, port: b.__setitem__("mod", 3), "invalid modulation"), (lambda b, port: port(16), "invalid port"),
+    (lambda b, port: b.__setitem__("grid_nof_prb", 276), "invalid or empty allocation"), (lambda b, port: b.__setitem__("n_id", 1024), "invalid scrambling identifiers"),
+    (lambda b, port: b.__setitem__("rnti", 65536), "invalid scrambling identifiers"),
+    (lambda b, port: (b.__setitem__("ref_point_prb0", 1), b.__setitem__("bwp_start_rb", 60), b.__setitem__("bwp_size_rb", 10)), "reference point outside the grid"),
+]
+
+
+@pytest.mark.parametrize("k", range(len(ALIKE_REJECTIONS)))
+def test_processor_forms_refuse_alike(ctx, k):
+    """Two valid one-layer PDUs of which the second breaks one rule: miphy_pdsch_process_batch, the prepared plan and
+    miphy_pdsch_process_layers_batch give the same message with MIPHY_EINVAL and leave the grid at its background."""
+    import torch
+    import miphy
+    edit, msg = ALIKE_REJECTIONS[k]
+    pdus = [dict(p, L=1, ports=p["ports"][:1], tb=p["tb"][:max(8, p["tb"].size // p["L"])]) for p in _pdus()[:2]]
+    rec, tb = _records(miphy, pdus)
+    rec1, tb1 = _records(miphy, pdus, layers=False)
+    edit(rec[1]["base"], lambda v: rec[1]["ports"].__setitem__(0, v))
+    edit(rec1[1], lambda v: rec1[1].__setitem__("port", v))
+    bg = _grid_background()
+    tb_d = torch.from_numpy(tb).cuda()
+    for call in (lambda g: ctx.pdsch_process_batch(rec1, tb_d, g), lambda g: miphy.PdschProcessPlan(ctx, rec1), lambda g: ctx.pdsch_process_layers_batch(rec, tb_d, g)):
+        gd = torch.from_numpy(bg).cuda()
+        with pytest.raises(RuntimeError) as e:
+            call(gd)
+        assert "miphy error -1" in str(e.value) and msg in str(e.value), str(e.value)
+        torch.cuda.synchronize()
+        assert np.array_equal(D.bits(gd.cpu().numpy()), D.bits(bg))

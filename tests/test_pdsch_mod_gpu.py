@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import dl_grid as D
 import oracle_lib as O
 
 pytestmark = pytest.mark.gpu
@@ -156,3 +157,31 @@ def test_rejections(ctx):
             j[k] = v
         with pytest.raises(RuntimeError):
             ctx.pdsch_modulate_batch(np.array([j], dtype=miphy.PdschModJob), cw, g)
+
+
+ONE_LAYER_REJECTIONS = [  # one per rule of miphy_pdsch_modulate_batch for a host job: (field, value or function of the valid job, the message)
+    ("mod", 3, "invalid modulation order 3"), ("nof_symbols", 15, "invalid time allocation"), ("dmrs_type", 0, "invalid DM-RS type"),
+    ("nof_cdm_groups_without_data", 3, "invalid number of CDM groups without data"), ("grid_nof_prb", 276, "invalid grid / BWP"),
+    ("bwp_size_rb", 276, "invalid grid / BWP"), ("nof_reserved", 5, "at most 4 reserved RE patterns"), ("n_id", 1024, "invalid scrambling identifiers"),
+    ("rnti", 65536, "invalid scrambling identifiers"), ("port", 16, "invalid port"),
+    ("nof_bits", lambda j: int(j["nof_bits"]) // 2, "codeword of 3120 bits, the allocation holds 6240"),
+]
+
+
+@pytest.mark.parametrize("field,value,msg", ONE_LAYER_REJECTIONS, ids=["%s_%d" % (r[0], k) for k, r in enumerate(ONE_LAYER_REJECTIONS)])
+def test_rejects_host_jobs_rule_by_rule(ctx, field, value, msg):
+    """MIPHY_EINVAL with the rule's message, and nothing enqueued: the grid still holds its background."""
+    import torch
+    import miphy
+    dm = np.zeros(14, np.uint8)
+    dm[2] = 1
+    j = _mod_job(miphy, 1, 2, 1.0, 4, 0, 0, 14, dm, 0, 2, 0, 10, np.arange(10), [], 10)
+    assert j["nof_bits"] == 6240  # 10 PRBs x (14 x 12 - 12) REs x 4 bits
+    j[field] = value(j) if callable(value) else value
+    bg = D.background(14 * 120, np.random.default_rng(146))
+    g = torch.from_numpy(bg).cuda()
+    with pytest.raises(RuntimeError) as e:
+        ctx.pdsch_modulate_batch(np.array([j], dtype=miphy.PdschModJob), torch.zeros(6240, dtype=torch.uint8, device="cuda"), g)
+    assert "miphy error -1" in str(e.value) and "pdsch_modulate: job 0: " + msg in str(e.value), str(e.value)
+    torch.cuda.synchronize()
+    assert np.array_equal(D.bits(g.cpu().numpy()), D.bits(bg))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the PDSCH modulator and the PDSCH processor on one codeword and L = 1, 2, 4 layers against the one-layer entry points, on the same
-allocation in the same session: 273 PRB, 256QAM, 14 symbols (DM-RS on symbol 2, two CDM groups without data: 42 588 data REs per layer), a batch
+allocation in the same session: 273 PRB, 256QAM (--mod 8, the default; --mod 6 takes the general element loop), 14 symbols (DM-RS on symbol 2, two CDM groups without data: 42 588 data REs per layer), a batch
 of --batch transmissions per call, one stream, calls back to back between two device events.
 - "modulate": miphy_pdsch_modulate_batch (one layer per job) and miphy_pdsch_modulate_layers_batch at L = 1, 2, 4 on random codewords, with host
   jobs (validated and staged by every call: at this size the host's work per job outlasts the device's, so the figure is the enqueue rate)
@@ -11,7 +11,7 @@ of --batch transmissions per call, one stream, calls back to back between two de
   3/4 of the codeword, capped at the encoder's 52 codeblocks of base graph 1 (54 753 bytes): the code rate falls with L and is printed.
 Every figure is the median of --reps repetitions of --iters calls, the variants alternating; the spread (min .. max) is printed with it. One
 JSON line per variant. There is no CPU path: without a device this fails.
-Run:  python tools/pdsch_layers_throughput.py [--batch N] [--iters N] [--reps R]"""
+Run:  python tools/pdsch_layers_throughput.py [--batch N] [--iters N] [--reps R] [--mod 1|2|4|6|8]"""
 import argparse
 import json
 import os
@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "srsran_project_23.5_amd"))
 import miphy  # noqa: E402
 
-NPRB, MOD, NSC = 273, 8, 273 * 12
+NPRB, NSC = 273, 273 * 12
 HBM_PEAK, HBM_ACHIEVABLE = 8.0e12, 6.3e12  # bytes per second
 TB_MAX_BYTES = 54753                       # 52 codeblocks of base graph 1
 
@@ -36,30 +36,30 @@ def rb_words():
     return w
 
 
-def mod_jobs(n, L, layered):
+def mod_jobs(n, L, layered, mod):
     """n transmissions on L layers each; the one-layer form (layered = False, L = 1) for miphy_pdsch_modulate_batch."""
     jobs = np.zeros(n, dtype=miphy.PdschModLayersJob if layered else miphy.PdschModJob)
     b = jobs["base"] if layered else jobs
-    b["rnti"], b["n_id"], b["scaling"], b["mod"], b["nof_symbols"] = 0x4601 + np.arange(n), 935, 0.7943282, MOD, 14
+    b["rnti"], b["n_id"], b["scaling"], b["mod"], b["nof_symbols"] = 0x4601 + np.arange(n), 935, 0.7943282, mod, 14
     b["dmrs_type"], b["nof_cdm_groups_without_data"], b["dmrs_symbols_mask"] = 1, 2, 1 << 2
     b["grid_nof_prb"], b["bwp_size_rb"], b["rb_mask"] = NPRB, NPRB, rb_words()
     nre = miphy.pdsch_mod_nof_re(b[0])
-    b["nof_bits"] = nre * L * MOD
-    b["cw_offset"] = np.arange(n, dtype=np.uint64) * np.uint64(nre * L * MOD)
+    b["nof_bits"] = nre * L * mod
+    b["cw_offset"] = np.arange(n, dtype=np.uint64) * np.uint64(nre * L * mod)
     b["grid_offset"] = np.arange(n, dtype=np.uint64) * np.uint64(L * 14 * NSC)
     if layered:
         jobs["nof_layers"], jobs["ports"] = L, np.arange(4) % L
     return jobs, nre
 
 
-def proc_pdus(n, L, layered):
+def proc_pdus(n, L, layered, mod):
     pdus = np.zeros(n, dtype=miphy.PdschLayersPdu if layered else miphy.PdschPdu)
     b = pdus["base"] if layered else pdus
     b["slot_in_frame"], b["rnti"], b["n_id"], b["dmrs_scrambling_id"], b["tbs_lbrm_bytes"] = 7, 0x4601 + np.arange(n), 935, 42, 3168
-    b["bg"], b["mod"], b["nof_symbols"], b["nof_cdm_groups_without_data"], b["dmrs_symbols_mask"] = 1, MOD, 14, 2, 1 << 2
+    b["bg"], b["mod"], b["nof_symbols"], b["nof_cdm_groups_without_data"], b["dmrs_symbols_mask"] = 1, mod, 14, 2, 1 << 2
     b["grid_nof_prb"], b["bwp_size_rb"], b["rb_mask"] = NPRB, NPRB, rb_words()
     nre = miphy.pdsch_pdu_nof_re(b[0])
-    tb_bytes = min(TB_MAX_BYTES, nre * L * MOD * 3 // 4 // 8)
+    tb_bytes = min(TB_MAX_BYTES, nre * L * mod * 3 // 4 // 8)
     b["tb_bytes"] = tb_bytes
     b["tb_offset"] = np.arange(n, dtype=np.uint64) * np.uint64((tb_bytes + 15) // 16 * 16)
     b["grid_offset"] = np.arange(n, dtype=np.uint64) * np.uint64(L * 14 * NSC)
@@ -96,8 +96,9 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--mod", type=int, default=8, choices=(1, 2, 4, 6, 8), help="bits per symbol")
     a = ap.parse_args()
-    n = a.batch
+    n, mod = a.batch, a.mod
     ctx = miphy.Context(0)
     gen = torch.Generator(device="cuda").manual_seed(1)
     grid = torch.zeros(n * 4 * 14 * NSC, dtype=torch.complex64, device="cuda")
@@ -106,15 +107,15 @@ def main():
     # ---- modulator alone
     fns, meta = [], []
     for name, L, layered in variants:
-        jobs, nre = mod_jobs(n, L, layered)
-        cw = torch.randint(0, 2, (n * nre * L * MOD,), dtype=torch.uint8, device="cuda", generator=gen)
+        jobs, nre = mod_jobs(n, L, layered, mod)
+        cw = torch.randint(0, 2, (n * nre * L * mod,), dtype=torch.uint8, device="cuda", generator=gen)
         call = ctx.pdsch_modulate_layers_batch if layered else ctx.pdsch_modulate_batch
         for where, j in (("host", jobs), ("device", torch.from_numpy(jobs.view(np.uint8).copy()).cuda())):
             fns.append(lambda call=call, j=j, cw=cw: call(j, cw, grid))
             meta.append((name, where, L, nre))
     for (name, where, L, nre), (us, lo, hi) in zip(meta, measure(fns, a.iters, a.reps)):
         mapped = n * nre * L
-        print(json.dumps({"what": "modulate", "entry": name, "jobs": where, "layers": L, "batch": n, "re_per_layer": nre, "us_per_call": round(us, 2),
+        print(json.dumps({"what": "modulate", "entry": name, "jobs": where, "layers": L, "mod": mod, "batch": n, "re_per_layer": nre, "us_per_call": round(us, 2),
                           "us_per_call_spread": [round(lo, 2), round(hi, 2)], "ps_per_re_layer": round(us * 1e6 / mapped, 2),
                           "store_GBps": round(mapped * 8 / us * 1e-3, 1), "share_of_hbm_achievable": round(mapped * 8 / (us * 1e-6) / HBM_ACHIEVABLE, 4),
                           "share_of_hbm_peak": round(mapped * 8 / (us * 1e-6) / HBM_PEAK, 4)}), flush=True)
@@ -122,15 +123,15 @@ def main():
     # ---- processor
     fns, meta = [], []
     for name, L, layered in variants:
-        pdus, nre, tb_bytes = proc_pdus(n, L, layered)
+        pdus, nre, tb_bytes = proc_pdus(n, L, layered, mod)
         tb = torch.randint(0, 256, (n * ((tb_bytes + 15) // 16 * 16) + 16,), dtype=torch.uint8, device="cuda", generator=gen)
         call = ctx.pdsch_process_layers_batch if layered else ctx.pdsch_process_batch
         fns.append(lambda call=call, pdus=pdus, tb=tb: call(pdus, tb, grid))
         meta.append((name, L, nre, tb_bytes))
     for (name, L, nre, tb_bytes), (us, lo, hi) in zip(meta, measure(fns, a.iters, a.reps)):
         mapped = n * nre * L
-        print(json.dumps({"what": "process", "entry": name, "layers": L, "batch": n, "re_per_layer": nre, "tb_bytes": tb_bytes,
-                          "code_rate": round(tb_bytes * 8 / (nre * L * MOD), 3), "us_per_call": round(us, 2), "us_per_call_spread": [round(lo, 2), round(hi, 2)],
+        print(json.dumps({"what": "process", "entry": name, "layers": L, "mod": mod, "batch": n, "re_per_layer": nre, "tb_bytes": tb_bytes,
+                          "code_rate": round(tb_bytes * 8 / (nre * L * mod), 3), "us_per_call": round(us, 2), "us_per_call_spread": [round(lo, 2), round(hi, 2)],
                           "ps_per_re_layer": round(us * 1e6 / mapped, 2), "tb_Gbps": round(n * tb_bytes * 8 / us * 1e-3, 1)}), flush=True)
 
 
