@@ -94,9 +94,8 @@ void miphy_ldpc_build_classes(const miphy_ldpc_dec_desc* descs, uint32_t n, cons
   std::vector<item> it(n);
   for (uint32_t i = 0; i < n; ++i) {
     const miphy_ldpc_dec_desc& d   = descs[i];
-    const int                  bgi = d.bg == 1 ? 0 : 1, bgK = bgi ? 10 : 22, bgM = bgi ? 42 : 46;
-    const int                  nodes = (int)((d.in_len + 2u * d.Z + d.Z - 1u) / d.Z);
-    const int                  lay   = std::min(bgM, std::max(4, nodes - bgK));
+    const int                  bgi   = d.bg == 1 ? 0 : 1;
+    const int                  lay   = miphy_ldpc_layers(bgi, miphy_ldpc_nodes(d.in_len, d.Z));
     const int                  H     = (d.Z + 1) / 2;
     const int                  kind  = d.Z <= 64 ? 0 : (H + 63) / 64;
     const bool                 fus   = fusable && fusable[i] && kind != 0;
@@ -125,7 +124,6 @@ void miphy_ldpc_build_classes(const miphy_ldpc_dec_desc* descs, uint32_t n, cons
     c.first = p, c.count = q - p;
     c.min_Z        = 0xffff;
     c.bundle_first = (uint32_t)C.bundles.size() / 2;
-    const int bgK  = c.bgi ? 10 : 22;
     for (uint32_t k = p; k < q; ++k) {
       const miphy_ldpc_dec_desc& d = descs[it[k].idx];
       c.lay                        = std::max<uint8_t>(c.lay, (uint8_t)(it[k].key & 63));
@@ -146,7 +144,7 @@ void miphy_ldpc_build_classes(const miphy_ldpc_dec_desc* descs, uint32_t n, cons
           ++e;
         C.bundles.push_back(k);
         C.bundles.push_back(e - k);
-        const uint32_t sstride = (((uint32_t)(bgK + c.lay) * d.Z) + 15u) & ~15u;
+        const uint32_t sstride = (uint32_t)miphy_ldpc_soft_bytes(c.bgi, c.lay, d.Z);
         c.soft_total           = std::max(c.soft_total, G * sstride);
         k                      = e;
       }
@@ -162,10 +160,9 @@ namespace {
 void pk_class_geometry(const miphy_ctx* ctx, const ldpc_knob_values& k, bool fuse, miphy_ldpc_launch& q)
 {
   const miphy_ldpc_class& c     = q.c;
-  const int               bgK   = c.bgi ? 10 : 22;
   const bool              fused = c.fused && fuse;
   const int               pairs = ctx->h_tables->pair_start[c.bgi][c.lay];
-  const size_t lds_l = miphy_ldpc_pk_lds_bytes(bgK, c.lay, c.max_Z, pairs), lds_g = miphy_ldpc_pk_lds_bytes(bgK, c.lay, c.max_Z, 0);
+  const size_t lds_l = miphy_ldpc_pk_lds_bytes(c.bgi, c.lay, c.max_Z, pairs), lds_g = miphy_ldpc_pk_lds_bytes(c.bgi, c.lay, c.max_Z, 0);
   // messages in LDS while that keeps as many codeblocks resident per CU as the registers allow; otherwise in global memory
   auto per_cu = [&](size_t lds) { return miphy_ldpc_pk_per_cu(lds, c.kind, fused); };
   // (and only where the class has more codeblocks than stay resident with the messages in LDS: otherwise the global round trip per
@@ -177,7 +174,7 @@ void pk_class_geometry(const miphy_ctx* ctx, const ldpc_knob_values& k, bool fus
   if (gm && k.force != MIPHY_LDPC_FORCE_THROUGHPUT && k.hybrid_msgs) {
     for (int m = c.lay - 1; m > 0; --m) {
       const int    pk_ = ctx->h_tables->pair_start[c.bgi][m];
-      const size_t l_  = miphy_ldpc_pk_lds_bytes(bgK, c.lay, c.max_Z, pk_);
+      const size_t l_  = miphy_ldpc_pk_lds_bytes(c.bgi, c.lay, c.max_Z, pk_);
       if (per_cu(l_ + LDPC_HYBRID_LDS_MARGIN) == per_cu(lds_g)) { // (margin: a CU filled to the last byte of the sum held one workgroup fewer -- allocation granularity)
         q.lds_pairs = pk_, q.lds = l_;
         break;
@@ -188,7 +185,7 @@ void pk_class_geometry(const miphy_ctx* ctx, const ldpc_knob_values& k, bool fus
   // messages in LDS (residency is no concern then).
   // (four parts while the codeblocks of the class still find a CU each and the workgroup stays within 1024 threads; forced latency modes: two)
   const int    parts = (k.force == MIPHY_LDPC_FORCE_LATENCY_ALL || k.force == MIPHY_LDPC_FORCE_LATENCY2) ? 2 : 4;
-  const size_t lds_s = miphy_ldpc_pk_lds_bytes(bgK, c.lay, c.max_Z, pairs, parts);
+  const size_t lds_s = miphy_ldpc_pk_lds_bytes(c.bgi, c.lay, c.max_Z, pairs, parts);
   if (k.force != MIPHY_LDPC_FORCE_THROUGHPUT && (c.count <= (uint32_t)ctx->num_cus || k.force == MIPHY_LDPC_FORCE_LATENCY_ALL) && lds_s <= (size_t)160 * 1024)
     q.parts = parts, gm = false, q.lds = lds_s, q.lds_pairs = 0;
   q.threads    = 64 * c.kind * q.parts;
@@ -222,7 +219,7 @@ void plan_classes(const miphy_ctx* ctx, const miphy_ldpc_classes& C, bool fuse, 
   for (size_t i = 0; i < nc; ++i) {
     miphy_ldpc_launch& q = T.l[i];
     q.c                  = C.classes[i];
-    q.nodes              = (q.c.bgi ? 10 : 22) + q.c.lay;
+    q.nodes              = miphy_bg_K(q.c.bgi) + q.c.lay;
     q.parts              = 1;
     q.ordered            = !(C.identity && nc == 1);
     if (T.scalar) // A-B knob: the one-row-per-lane kernel on every class (the caller has dematched: nothing is fused then)
@@ -262,7 +259,7 @@ struct batch_bounds {
   void account(unsigned bg, unsigned Z, unsigned in_len)
   {
     threads           = std::max(threads, (int)((Z + 63) / 64) * 64);
-    max_nodes[bg - 1] = std::max(max_nodes[bg - 1], (int)((in_len + 2 * Z + Z - 1) / Z));
+    max_nodes[bg - 1] = std::max(max_nodes[bg - 1], miphy_ldpc_nodes(in_len, Z));
   }
 };
 
@@ -292,13 +289,12 @@ void plan_one_launch(const miphy_ctx* ctx, const ldpc_knob_values& k, const batc
   for (int bgi = 0; bgi < 2; ++bgi) { // the base graph of device descriptors is not visible here: the larger need of the two
     if (!b.max_nodes[bgi])
       continue;
-    const int bgK = bgi ? 10 : 22, bgM = bgi ? 42 : 46;
-    const int lay = std::min(bgM, std::max(4, nodes_all - bgK)); // the kernels size their arrays from the batch-wide node bound
-    row_lds       = std::max(row_lds, miphy_ldpc_row_lds_bytes(bgK, lay, (size_t)b.threads));
+    const int lay = miphy_ldpc_layers(bgi, nodes_all); // the kernels size their arrays from the batch-wide node bound
+    row_lds       = std::max(row_lds, miphy_ldpc_row_lds_bytes(bgi, lay, (size_t)b.threads));
     if (b.pk_ok) {
       const int pairs = ctx->h_tables->pair_start[bgi][lay];
-      pk_lds          = std::max(pk_lds, miphy_ldpc_pk_lds_bytes(bgK, lay, (size_t)b.threads, pairs));
-      pk_lds_g        = std::max(pk_lds_g, miphy_ldpc_pk_lds_bytes(bgK, lay, (size_t)b.threads, 0));
+      pk_lds          = std::max(pk_lds, miphy_ldpc_pk_lds_bytes(bgi, lay, (size_t)b.threads, pairs));
+      pk_lds_g        = std::max(pk_lds_g, miphy_ldpc_pk_lds_bytes(bgi, lay, (size_t)b.threads, 0));
       pk_pairs        = std::max(pk_pairs, pairs);
     }
   }
@@ -415,7 +411,7 @@ int validate_descs(const miphy_ctx* ctx, const miphy_ldpc_dec_desc* descs, uint3
     const miphy_ldpc_dec_desc& d = descs[i];
     MIPHY_REQUIRE(d.bg == 1 || d.bg == 2, "ldpc_decode: desc %u: invalid base graph %u", i, d.bg);
     MIPHY_REQUIRE(d.Z <= MIPHY_MAX_Z && ctx->h_tables->z_pos[d.Z] != 0xffff, "ldpc_decode: desc %u: invalid lifting size %u", i, d.Z);
-    const unsigned bgK = (d.bg == 1) ? 22 : 10, nshort = (d.bg == 1) ? 66 : 50;
+    const unsigned bgK = miphy_bg_K(d.bg != 1), nshort = miphy_bg_N_short(d.bg != 1);
     MIPHY_REQUIRE(d.in_len >= (bgK + 2) * d.Z && d.in_len <= nshort * d.Z, "ldpc_decode: desc %u: input length %u out of range", i, d.in_len);
     MIPHY_REQUIRE(d.max_iter > 0, "ldpc_decode: desc %u: max_iter must be > 0", i);
     MIPHY_REQUIRE(d.crc_poly == MIPHY_CRC_NONE || d.crc_poly <= MIPHY_CRC11, "ldpc_decode: desc %u: invalid CRC", i);

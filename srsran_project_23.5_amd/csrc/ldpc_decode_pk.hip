@@ -11,7 +11,7 @@
 // gfx950: a DS write costs ~5 cycles of the CU's LDS pipe whatever its width, a read ~2.8 -- tools/lds_probe.hip).
 #include "miphy_internal.h"
 #include "rdm_device.h"
-#include "ldpc_pk_device.h"
+#include "ldpc_frame_device.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -88,6 +88,33 @@ __device__ __forceinline__ uint4 shift_in16(const raw_in16& r, int mb)
 }
 constexpr int PK_PRE = 3; // rate-matched input vectors per lane fetched one codeblock ahead (3 x 192 lanes x 16 B = 9216 B)
 
+// Whole 16-byte vectors of an input of E bytes whose address is mb bytes past a dword boundary (load_in16 reads a dword beyond a vector
+// that is not aligned).
+__device__ __forceinline__ int pk_in16_vectors(int mb, int E)
+{
+  return (mb == 0) ? (E >> 4) : ((E >= 4) ? ((E - 4) >> 4) : 0);
+}
+// (Re)fills pre[] with the first input vectors of codeblock c of the launch, zeros where there is no such codeblock or vector: every
+// element is always assigned -- an old value must not stay live across the decode of a codeblock.
+__device__ __forceinline__ void pk_prefetch(raw_in16 (&pre)[PK_PRE], uint32_t c, uint32_t n, const miphy_ldpc_rdm_desc* __restrict__ rdm,
+                                            const int8_t* __restrict__ rm_in_base, const uint32_t* __restrict__ cb_order, int tid, int nt)
+{
+#pragma unroll
+  for (int k = 0; k < PK_PRE; ++k)
+    pre[k] = raw_in16{0, 0, 0, 0, 0};
+  if (c < n) {
+    const miphy_ldpc_rdm_desc r  = load_words(rdm + (cb_order ? cb_order[c] : c));
+    const int8_t*             in = rm_in_base + r.in_offset;
+    const int                 mb = (int)(((uintptr_t)in) & 3), nq = pk_in16_vectors(mb, (int)r.E);
+#pragma unroll
+    for (int k = 0; k < PK_PRE; ++k) {
+      pre[k] = raw_in16{0, 0, 0, 0, 0};
+      if (tid + k * nt < nq)
+        pre[k] = load_in16_raw(in, mb, tid + k * nt);
+    }
+  }
+}
+
 // FUSED = the codeblock's first transmission is rate-dematched while it is loaded (ldpc_rate_dematcher_impl.cpp:43-254 for
 // new data, redundancy version 0, full circular buffer, E + fillers <= N): `llr_base` is then the HARQ soft-buffer array, which
 // receives the dematched codeblock exactly as the reference's dematcher leaves it (data, fillers at +127, zeros behind), and the
@@ -114,7 +141,7 @@ __device__ __attribute__((noinline)) void pk_fused_load(int8_t* __restrict__ sof
     int stid = tid;
     asm volatile("" : "+v"(stid));
     const int                 mb  = (int)(((uintptr_t)in) & 3);
-    const int                 nq  = (mb == 0) ? (E >> 4) : ((E >= 4) ? ((E - 4) >> 4) : 0);
+    const int                 nq  = pk_in16_vectors(mb, E);
     int8_t*                   img = soft + 2 * Z;
     rm_geom                   g;
     g.r0 = 0, g.f1 = (bgK - 2) * Z, g.f0 = g.f1 - F, g.F = F, g.E = E, g.mod = mod, g.Kq = E / mod;
@@ -163,7 +190,7 @@ __device__ __forceinline__ int pk_fused_image_out(const int8_t* __restrict__ sof
   int          last = 0;
   u32x4*       dst  = reinterpret_cast<u32x4*>(llr_img);
   const uint4* src  = reinterpret_cast<const uint4*>(soft + 2 * Z);
-  const int    nimg = in_len >> 4, nall = (((bgi ? 50 : 66) * Z) >> 4);
+  const int    nimg = in_len >> 4, nall = ((miphy_bg_N_short(bgi) * Z) >> 4);
   // (the lane index is made opaque, as in pk_fused_load: the compiler otherwise hoists this lane's share of the store address out of the
   // codeblock loop and carries it across the decoder in scratch)
   asm volatile("" : "+v"(tid));
@@ -171,12 +198,7 @@ __device__ __forceinline__ int pk_fused_image_out(const int8_t* __restrict__ sof
     const uint4 v = src[q];
     const u32x4 o = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(o, dst + q);
-    int hi = -1;
-    hi     = v.x ? 3 - (__clz((int)v.x) >> 3) : hi;
-    hi     = v.y ? 7 - (__clz((int)v.y) >> 3) : hi;
-    hi     = v.z ? 11 - (__clz((int)v.z) >> 3) : hi;
-    hi     = v.w ? 15 - (__clz((int)v.w) >> 3) : hi;
-    last   = (hi >= 0) ? 16 * q + hi + 1 : last;
+    last = last_nonzero_behind(v, q, last);
   }
   const u32x4 zero = {0, 0, 0, 0};
   for (int q = nimg + tid; q < nall; q += nt)
@@ -239,20 +261,8 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   const int part = SPLIT ? __builtin_amdgcn_readfirstlane((tid >= nth) + (PARTS > 2 ? (tid >= 2 * nth) + (tid >= 3 * nth) : 0)) : 0;
   const int lr   = tid - part * nth;             // row pair (lr, lr + H) of this lane
   raw_in16  pre[PK_PRE];
-  if (FUSED) {
-    if (blockIdx.x < n) {
-      const miphy_ldpc_rdm_desc r0 = load_words(rdm + (cb_order ? cb_order[blockIdx.x] : blockIdx.x));
-      const int8_t*             in = rm_in_base + r0.in_offset;
-      const int                 mb = (int)(((uintptr_t)in) & 3), E = (int)r0.E;
-      const int                 nq = (mb == 0) ? (E >> 4) : ((E >= 4) ? ((E - 4) >> 4) : 0);
-#pragma unroll
-      for (int k = 0; k < PK_PRE; ++k) {
-        pre[k] = raw_in16{0, 0, 0, 0, 0}; // always assigned: an old value must not stay live across the decode of a codeblock
-        if (tid + k * nt < nq)
-          pre[k] = load_in16_raw(in, mb, tid + k * nt);
-      }
-    }
-  }
+  if (FUSED)
+    pk_prefetch(pre, blockIdx.x, n, rdm, rm_in_base, cb_order, tid, nt);
   // Persistent workgroups: the grid is what the chip holds at once; a workgroup decodes codeblock blockIdx.x first and then takes
   // codeblocks gridDim.x, gridDim.x + 1, ... from the launch's queue counter until the batch is exhausted (every wave reaches the
   // exit: the counter only grows). No workgroup launch / LDS allocation between codeblocks, and heterogeneous batches balance.
@@ -267,8 +277,8 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   const int                 Z   = dsc.Z;
   const int                 H   = (Z + 1) >> 1;
   const int                 bgi = (dsc.bg == 1) ? 0 : 1;
-  const int                 bgK = bgi ? 10 : 22;
-  const int                 bgM = bgi ? 42 : 46;
+  const int                 bgK = miphy_bg_K(bgi);
+  const int                 bgM = miphy_bg_M(bgi);
   const int                 K   = bgK * Z;
   const int                 zp  = tab->z_pos[Z];
 
@@ -277,8 +287,8 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   // [wave][edge pair][64 lanes] dwords, then a few reduction words. Everything is sized by the layers the batch can reach, so
   // a high-rate batch (4 layers, 76 edges) packs 4 codeblocks = 12 waves per CU.
   int8_t*   soft       = reinterpret_cast<int8_t*>(smem);
-  const int lay_alloc  = min(bgM, max(4, max_nodes - bgK));
-  const int soft_bytes = ((bgK + lay_alloc) * Z + 15) & ~15;
+  const int lay_alloc  = miphy_ldpc_layers(bgi, max_nodes);
+  const int soft_bytes = miphy_ldpc_soft_bytes(bgi, lay_alloc, Z);
   const int pairs_all  = tab->pair_start[bgi][lay_alloc];
   const int pairs_lds  = GMSG ? lds_pairs : pairs_all;
   uint32_t* c2v_lane   = reinterpret_cast<uint32_t*>(smem + soft_bytes) + (lr >> 6) * (pairs_lds * 64) + (lr & 63);
@@ -312,30 +322,15 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   if (tid < 15)
     red[tid] = 0;
   int last = 0;
-  // (re)fills pre[] with the first input vectors of codeblock c
-  auto prefetch = [&](uint32_t c) {
-#pragma unroll
-    for (int k = 0; k < PK_PRE; ++k)
-      pre[k] = raw_in16{0, 0, 0, 0, 0};
-    if (c < n) {
-      const miphy_ldpc_rdm_desc rn  = load_words(rdm + (cb_order ? cb_order[c] : c));
-      const int8_t*             inn = rm_in_base + rn.in_offset;
-      const int                 mbn = (int)(((uintptr_t)inn) & 3), En = (int)rn.E;
-      const int                 nqn = (mbn == 0) ? (En >> 4) : ((En >= 4) ? ((En - 4) >> 4) : 0);
-#pragma unroll
-      for (int k = 0; k < PK_PRE; ++k) {
-        pre[k] = raw_in16{0, 0, 0, 0, 0};
-        if (tid + k * nt < nqn)
-          pre[k] = load_in16_raw(inn, mbn, tid + k * nt);
-      }
-    }
-  };
+  // (bound once, by reference, for the two sites below: the closure is what the register allocation of the instances that do not dematch was
+  // tuned with -- without it <false, true> spills two more vector registers)
+  auto prefetch = [&](uint32_t c) { pk_prefetch(pre, c, n, rdm, rm_in_base, cb_order, tid, nt); };
   pk_adr_quad    anx[ATAB ? PK_ATAB_QUADS : 1]; // ATAB: the soft-bit addresses of the next layer visit
   pk_adr_row     atab    = pk_adr_row();        // ... the table of this lifting size
   const uint32_t astride = 16u * (uint32_t)nt, alayer = PK_ATAB_QUADS * astride; // ... bytes of a quad and of a layer
   if (ATAB) {
     // (wave-uniform, and said so: the codeblock index comes out of LDS, and a descriptor the compiler takes for divergent is a loop per load)
-    const int zq = __builtin_amdgcn_readfirstlane(Z >> 4), bytes = __builtin_amdgcn_readfirstlane(min(bgM, max(4, max_nodes - bgK)) * (int)alayer);
+    const int zq = __builtin_amdgcn_readfirstlane(Z >> 4), bytes = __builtin_amdgcn_readfirstlane(lay_alloc * (int)alayer);
     atab.rsrc    = __builtin_amdgcn_make_buffer_rsrc(const_cast<pk_adr_quad*>(adr_by_z[zq]), 0, bytes, 0x00020000);
     atab.soff = alayer; // layer 1: the first one visited
     pk_table_request<PK_ATAB_DEGREE>(anx, atab, 16u * (uint32_t)tid, astride);
@@ -345,37 +340,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
     pk_fused_load(soft, (global_ci8)(rm_in_base + rd.in_offset), (int)rd.E, (int)dsc.nof_filler_bits, (int)rd.mod, Z, bgK, soft_bytes, pre[0], pre[1], pre[2], tid, nt);
     last = pk_fused_image_out(soft, const_cast<int8_t*>(llr), Z, bgi, in_len, tid, nt);
   } else {
-  for (int k = tid; k < 2 * Z; k += nt)
-    soft[k] = 0;
-  for (int k = 2 * Z + in_len + tid; k < soft_bytes; k += nt)
-    soft[k] = 0;
-  __syncthreads();
-  if ((((uintptr_t)llr | (uintptr_t)(2 * Z)) & 15) == 0) {
-    const uint4* src = reinterpret_cast<const uint4*>(llr);
-    uint4*       dst = reinterpret_cast<uint4*>(soft + 2 * Z);
-    const int    nq  = in_len >> 4;
-    for (int q = tid; q < nq; q += nt) {
-      const uint4 v = src[q];
-      dst[q]        = v;
-      int hi = -1;
-      hi     = v.x ? 3 - (__clz((int)v.x) >> 3) : hi;
-      hi     = v.y ? 7 - (__clz((int)v.y) >> 3) : hi;
-      hi     = v.z ? 11 - (__clz((int)v.z) >> 3) : hi;
-      hi     = v.w ? 15 - (__clz((int)v.w) >> 3) : hi;
-      last   = (hi >= 0) ? 16 * q + hi + 1 : last;
-    }
-    for (int k = (nq << 4) + tid; k < in_len; k += nt) {
-      const int8_t v  = llr[k];
-      soft[2 * Z + k] = v;
-      last            = (v != 0) ? k + 1 : last;
-    }
-  } else {
-    for (int k = tid; k < in_len; k += nt) {
-      const int8_t v  = llr[k];
-      soft[2 * Z + k] = v;
-      last            = (v != 0) ? k + 1 : last;
-    }
-  }
+    last = cb_plain_load(soft, llr, in_len, Z, soft_bytes, tid, nt);
   }
   atomicMax(reinterpret_cast<int*>(&red[0]), last);
   __syncthreads();
@@ -384,10 +349,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   const bool use_crc = dsc.crc_poly != MIPHY_CRC_NONE;
   if (last == 0) {
     if (!use_crc) {
-      for (int b = tid; b < (K + 7) / 8; b += nt) {
-        const int rem = K - 8 * b;
-        out[b]        = (rem >= 8) ? 0xff : (uint8_t)(0xff << (8 - rem));
-      }
+      store_all_ones(out, K, tid, nt);
     }
     if (tid == 0) {
       iters_out[cb] = 0;
@@ -399,9 +361,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
     q = red[15];
     continue;
   }
-  int cb_len = max(last + 2 * Z, K + 4 * Z);
-  cb_len     = ((cb_len + Z - 1) / Z) * Z;
-  const int nof_layers = cb_len / Z - bgK;
+  const int nof_layers = cb_nof_layers(last, Z, bgi);
 
   const uint32_t* edges_g   = tab->edge_sb[bgi][zp];
   // Per-layer constants of the base graph, one layer per lane (loaded once per codeblock): first edge (bits 0-9), degree (10-15),
@@ -454,27 +414,28 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
       const int       d     = (int)((li >> 10) & 0x3fu);
       const uint32_t* edges = edges_g + 2 * e0;
       PROF_T(p_l0);
-      if (SPLIT) { // every thread: the function holds the barrier of the exchange
+      if constexpr (SPLIT) { // every thread: the function holds the barrier of the exchange
         part_edges<PARTS> pn;
         const uint32_t    lin  = (uint32_t)__builtin_amdgcn_readlane((int)lay_info, (m + 1 < nof_layers) ? m + 1 : 0);
         auto              next = [&]() { load_part_edges<PARTS>(pn, edges_g, lin, part); };
+        const pk_exchange<decltype(next)> x = {xch, part, nth, lr < H, next};
         uint32_t* cl = c2v_lane + 64 * (li >> 16);
         if (it == 0 || (it == 1 && m == 0)) // (the latency form keeps the general first-visit instance for layers 1 and 2)
-          update_rows_pk_split<true, PARTS>(pe, part, soft, cl, lr, Hv, Zv, lr < H, xch, nth, next);
+          update_rows_pk_split<true, PARTS>(pe, soft, cl, lr, Hv, Zv, x);
         else
-          update_rows_pk_split<false, PARTS>(pe, part, soft, cl, lr, Hv, Zv, lr < H, xch, nth, next);
+          update_rows_pk_split<false, PARTS>(pe, soft, cl, lr, Hv, Zv, x);
         pe = pn;
       } else if constexpr (!RSKIP) {
         if (ATAB) {
           if (tid < H)
-            update_rows_pk_visit_tab<PK_ATAB_DEGREE>(it, m, soft, c2v_lane + 64 * (li >> 16), anx,
-                                                     pk_adr_row{atab.rsrc, (uint32_t)__builtin_amdgcn_readfirstlane((m + 1 < nof_layers) ? m + 1 : 0) * alayer},
-                                                     16u * (uint32_t)tid, astride);
+            update_rows_pk_visit_tab<PK_ATAB_DEGREE>(it, m, soft, c2v_lane + 64 * (li >> 16),
+                                                     pk_adr_table{anx, {atab.rsrc, (uint32_t)__builtin_amdgcn_readfirstlane((m + 1 < nof_layers) ? m + 1 : 0) * alayer},
+                                                                  16u * (uint32_t)tid, astride});
         } else if (tid < H) { // (<FUSED>: the address form of pk_edge_addresses that adds the column offset in the split pays in the 168-register instances only)
           if (GMSG && (int)(li >> 16) >= pairs_lds) { // this layer's messages live in global memory (separate code: the address space is part of the instruction)
-            update_rows_pk_visit<FUSED>(it, m, d, soft, c2v_glob + 64 * (li >> 16), edges, tid, Hv, Zv);
+            update_rows_pk_visit<FUSED>(it, m, d, soft, c2v_glob + 64 * (li >> 16), pk_adr_computed{edges, tid, Hv, Zv, 0});
           } else {
-            update_rows_pk_visit<FUSED>(it, m, d, soft, c2v_lane + 64 * (li >> 16), edges, tid, Hv, Zv);
+            update_rows_pk_visit<FUSED>(it, m, d, soft, c2v_lane + 64 * (li >> 16), pk_adr_computed{edges, tid, Hv, Zv, 0});
           }
         }
       } else if (!((sat_layers >> m) & 1u)) { // RSKIP (a set bit: saturated rows, the visit changes nothing anybody reads)
@@ -484,13 +445,13 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
           const uint64_t live = ~sat_layers & (((uint64_t)1 << nof_layers) - 1u), above = live & ~(((uint64_t)2 << m) - 1u);
           const int      mn   = __builtin_amdgcn_readfirstlane(above ? __builtin_ctzll(above) : __builtin_ctzll(live));
           if (tid < H)
-            all_inf = update_rows_pk_visit_tab<PK_ATAB_DEGREE, true>(it, m, soft, c2v_lane + 64 * (li >> 16), anx, pk_adr_row{atab.rsrc, (uint32_t)mn * alayer},
-                                                                     16u * (uint32_t)tid, astride);
+            all_inf = update_rows_pk_visit_tab<PK_ATAB_DEGREE, true>(it, m, soft, c2v_lane + 64 * (li >> 16),
+                                                                     pk_adr_table{anx, {atab.rsrc, (uint32_t)mn * alayer}, 16u * (uint32_t)tid, astride});
         } else if (tid < H) {
           if (GMSG && (int)(li >> 16) >= pairs_lds) {
-            all_inf = update_rows_pk_visit<FUSED, true>(it, m, d, soft, c2v_glob + 64 * (li >> 16), edges, tid, Hv, Zv);
+            all_inf = update_rows_pk_visit<FUSED, true>(it, m, d, soft, c2v_glob + 64 * (li >> 16), pk_adr_computed{edges, tid, Hv, Zv, 0});
           } else {
-            all_inf = update_rows_pk_visit<FUSED, true>(it, m, d, soft, c2v_lane + 64 * (li >> 16), edges, tid, Hv, Zv);
+            all_inf = update_rows_pk_visit<FUSED, true>(it, m, d, soft, c2v_lane + 64 * (li >> 16), pk_adr_computed{edges, tid, Hv, Zv, 0});
           }
         }
         // one ballot over the lanes that own rows (a lane of a partial last wavefront that owns none does not count against it)
@@ -540,6 +501,31 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   } // codeblock loop
 }
 
+// The instances of the kernel that exist, by what selects them. A row comes from ONE set of template arguments, so a key cannot name another
+// instance's kernel; miphy_ldpc_pk_launch takes the row that matches its launch exactly.
+struct pk_instance_key {
+  bool fused, gmsg;
+  int  parts;
+  bool atab, row_skip;
+  constexpr bool operator==(const pk_instance_key& o) const { return fused == o.fused && gmsg == o.gmsg && parts == o.parts && atab == o.atab && row_skip == o.row_skip; }
+};
+typedef decltype(&ldpc_decode_pk_kernel<false, false>) pk_kernel_fn;
+struct pk_instance {
+  pk_instance_key key;
+  pk_kernel_fn    kernel;
+};
+template <bool FUSED, bool GMSG, int PARTS = 1, bool ATAB = false, bool RSKIP = false>
+constexpr pk_instance pk_instance_of()
+{
+  return {{FUSED, GMSG, PARTS, ATAB, RSKIP}, ldpc_decode_pk_kernel<FUSED, GMSG, PARTS, ATAB, RSKIP>};
+}
+constexpr pk_instance pk_instances[] = {
+    pk_instance_of<false, false>(),        pk_instance_of<false, true>(),         pk_instance_of<true, false>(),         pk_instance_of<true, true>(),
+    pk_instance_of<false, false, 2>(),     pk_instance_of<true, false, 2>(),      pk_instance_of<false, false, 4>(),     pk_instance_of<true, false, 4>(),
+    pk_instance_of<true, false, 1, true>(), pk_instance_of<false, false, 1, false, true>(), pk_instance_of<true, false, 1, false, true>(),
+    pk_instance_of<true, false, 1, true, true>(),
+};
+
 } // namespace
 
 #ifdef LDPC_PK_PROFILE
@@ -588,10 +574,10 @@ int miphy_ldpc_pk_waves_per_cu(bool fused, int parts)
 
 // LDS bytes the packed kernel needs for a given geometry (Zt >= Z of every codeblock, lay = layer bound, pairs_all = message
 // dwords per lane of those layers).
-size_t miphy_ldpc_pk_lds_bytes(int bgK, int lay, size_t Zt, int pairs_all, int parts)
+size_t miphy_ldpc_pk_lds_bytes(int bgi, int lay, size_t Zt, int pairs_all, int parts)
 {
   const size_t waves = ((Zt + 1) / 2 + 63) / 64;
-  return ((((size_t)bgK + lay) * Zt + 15) & ~(size_t)15) + waves * (size_t)pairs_all * 256 + 64 + (parts > 1 ? (size_t)parts * 3 * 64 * waves * 4 : 0);
+  return (size_t)miphy_ldpc_soft_bytes(bgi, lay, (int)Zt) + waves * (size_t)pairs_all * 256 + 64 + (parts > 1 ? (size_t)parts * 3 * 64 * waves * 4 : 0);
 }
 
 // Resident workgroups per CU: LDS, the wavefronts per CU the register budget of the kernel allows (__launch_bounds__; at most the 32 slots).
@@ -613,53 +599,24 @@ int miphy_ldpc_pk_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy
   // (the geometry is the launch table's: L.threads counts every part of the latency form, whose L.lds holds the exchange slots)
   const bool fused = (L.used & MIPHY_LDPC_KERNEL_FUSED) != 0, gm = L.gmsg_pairs > 0;
   MIPHY_REQUIRE(L.threads <= 1024, "ldpc_decode: workgroup of %d threads", L.threads);
-  const bool  atab = L.adr_by_z != nullptr;
-  MIPHY_REQUIRE(!atab || (fused && !gm && L.parts == 1), "ldpc_decode: address tables with a launch form that has no such instance");
-  const bool  rs   = L.row_skip;
-  MIPHY_REQUIRE(!rs || (L.parts == 1 && !gm), "ldpc_decode: saturated rows are left out by the throughput forms with their messages in LDS only");
-  const void* kern = rs ? (atab ? (const void*)ldpc_decode_pk_kernel<true, false, 1, true, true>
-                                : fused ? (const void*)ldpc_decode_pk_kernel<true, false, 1, false, true> : (const void*)ldpc_decode_pk_kernel<false, false, 1, false, true>)
-                     : atab ? (const void*)ldpc_decode_pk_kernel<true, false, 1, true> : L.parts == 4 ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 4> : (const void*)ldpc_decode_pk_kernel<false, false, 4>)
-                     : L.parts == 2 ? (fused ? (const void*)ldpc_decode_pk_kernel<true, false, 2> : (const void*)ldpc_decode_pk_kernel<false, false, 2>)
-                           : fused ? (gm ? (const void*)ldpc_decode_pk_kernel<true, true> : (const void*)ldpc_decode_pk_kernel<true, false>)
-                                   : (gm ? (const void*)ldpc_decode_pk_kernel<false, true> : (const void*)ldpc_decode_pk_kernel<false, false>);
+  const pk_instance_key want = {fused, gm, L.parts, L.adr_by_z != nullptr, L.row_skip};
+  pk_kernel_fn          kern = nullptr;
+  for (const pk_instance& i : pk_instances)
+    if (i.key == want)
+      kern = i.kernel;
+  MIPHY_REQUIRE(kern, "ldpc_decode: no packed kernel instance {fused %d, global messages %d, parts %d, address table %d, row skip %d}", want.fused, want.gmsg, want.parts,
+                want.atab, want.row_skip);
   // Above the default 64 KB of dynamic LDS the limit has to be raised; it is a per-device attribute of the kernel, so it is set on
   // every such launch (a cache per thread would be wrong for a thread that drives several devices).
   if (L.lds > 48 * 1024) {
-    MIPHY_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    MIPHY_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
   }
   uint32_t* queue = nullptr;
   int       rc    = miphy_next_queue_counter(ctx, &queue);
   if (rc)
     return rc;
-#define PK_LAUNCH(F, G, ...)                                                                                                                              \
-  hipLaunchKernelGGL((ldpc_decode_pk_kernel<F, G, ##__VA_ARGS__>), dim3(L.grid), dim3(L.threads), L.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, \
-                     L.nodes, harq_slot, harq_crc_ok, L.c.count, queue, d_rdm, rm_in, (uint32_t*)gmsg, L.gmsg_pairs, gm ? L.lds_pairs : 0, d_order, (const pk_adr_quad* const*)L.adr_by_z)
-  if (rs && atab)
-    PK_LAUNCH(true, false, 1, true, true);
-  else if (rs && fused)
-    PK_LAUNCH(true, false, 1, false, true);
-  else if (rs)
-    PK_LAUNCH(false, false, 1, false, true);
-  else if (atab)
-    PK_LAUNCH(true, false, 1, true);
-  else if (L.parts == 4 && fused)
-    PK_LAUNCH(true, false, 4);
-  else if (L.parts == 4)
-    PK_LAUNCH(false, false, 4);
-  else if (L.parts == 2 && fused)
-    PK_LAUNCH(true, false, 2);
-  else if (L.parts == 2)
-    PK_LAUNCH(false, false, 2);
-  else if (fused && gm)
-    PK_LAUNCH(true, true);
-  else if (fused)
-    PK_LAUNCH(true, false);
-  else if (gm)
-    PK_LAUNCH(false, true);
-  else
-    PK_LAUNCH(false, false);
-#undef PK_LAUNCH
+  hipLaunchKernelGGL(kern, dim3(L.grid), dim3(L.threads), L.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, L.nodes, harq_slot, harq_crc_ok, L.c.count, queue, d_rdm,
+                     rm_in, (uint32_t*)gmsg, L.gmsg_pairs, gm ? L.lds_pairs : 0, d_order, (const pk_adr_quad* const*)L.adr_by_z);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }

@@ -14,7 +14,7 @@
 // bundles are formed on the host from codeblocks that agree in base graph, lifting size, CRC polynomial, CRC mode and iteration
 // limit (miphy_ldpc_build_classes, ldpc_decode.hip), everything else (input length, fillers, buffers, HARQ state) is per group.
 #include "miphy_internal.h"
-#include "ldpc_pk_device.h"
+#include "ldpc_frame_device.h"
 #include <algorithm>
 
 namespace {
@@ -22,8 +22,14 @@ namespace {
 // Is the checksum of the first L hard bits of this lane's codeblock zero? Words strided over the H lanes of the group, partial
 // checksums (crc_zmask_partial, or crc_div_partial for a polynomial without a mask table) combined through the group's word of LDS.
 // Every lane of the wave must call.
-__device__ __forceinline__ bool group_word_is_zero(uint32_t* redg, int l, bool member)
+__device__ __forceinline__ bool group_crc_is_zero(const int8_t* softg, const miphy_graph_tables* __restrict__ tab, int zi, int crc_id, uint32_t poly, uint32_t order, int K,
+                                                  int L, uint32_t* redg, int l, int H, bool member)
 {
+  if (member) {
+    const uint32_t part = zi >= 0 ? crc_zmask_partial(softg, tab, zi, (int)order, L, l, H) : crc_div_partial(softg, tab, crc_id, poly, order, K, L, l, H);
+    if (part)
+      atomicXor(redg, part);
+  }
   __syncthreads();
   const uint32_t crc = member ? *redg : 1u;
   __syncthreads();
@@ -31,28 +37,6 @@ __device__ __forceinline__ bool group_word_is_zero(uint32_t* redg, int l, bool m
     *redg = 0;
   __syncthreads();
   return crc == 0;
-}
-
-__device__ __forceinline__ bool group_crc_is_zero(const int8_t* softg, const miphy_graph_tables* __restrict__ tab, int zi, int order, int L,
-                                                  uint32_t* redg, int l, int H, bool member)
-{
-  if (member) {
-    const uint32_t par = crc_zmask_partial(softg, tab, zi, order, L, l, H);
-    if (par)
-      atomicXor(redg, par);
-  }
-  return group_word_is_zero(redg, l, member);
-}
-
-__device__ __forceinline__ bool group_crc_is_zero_div(const int8_t* softg, const miphy_graph_tables* __restrict__ tab, int crc_id, uint32_t poly,
-                                                      uint32_t order, int K, int L, uint32_t* redg, int l, int H, bool member)
-{
-  if (member) {
-    const uint32_t part = crc_div_partial(softg, tab, crc_id, poly, order, K, L, l, H);
-    if (part)
-      atomicXor(redg, part);
-  }
-  return group_word_is_zero(redg, l, member);
 }
 
 // One wavefront per workgroup (so __syncthreads() is a wait for the wave's own LDS operations, no s_barrier is emitted), persistent:
@@ -94,14 +78,14 @@ ldpc_decode_pkw_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
     const int                 Z     = d0.Z;
     const int                 H     = (Z + 1) >> 1;
     const int                 bgi   = (d0.bg == 1) ? 0 : 1;
-    const int                 bgK   = bgi ? 10 : 22;
-    const int                 bgM   = bgi ? 42 : 46;
+    const int                 bgK   = miphy_bg_K(bgi);
+    const int                 bgM   = miphy_bg_M(bgi);
     const int                 K     = bgK * Z;
     const int                 zp    = tab->z_pos[Z];
     const int                 g     = lane / H; // group = codeblock of the bundle
     const int                 l     = lane - g * H;
     const bool                member = g < (int)cnt;
-    const int                 sstride = (((bgK + lay_alloc) * Z) + 15) & ~15;
+    const int                 sstride = miphy_ldpc_soft_bytes(bgi, lay_alloc, Z);
     const uint32_t            base    = member ? (uint32_t)(g * sstride) : 0u;
     const int                 pairs_all = tab->pair_start[bgi][lay_alloc];
     uint32_t* msg0 = GMSG ? gmsg + (size_t)blockIdx.x * ((size_t)gmsg_pairs * 64) + lane : reinterpret_cast<uint32_t*>(smem + soft_total) + lane;
@@ -159,22 +143,14 @@ ldpc_decode_pkw_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
     const int  max_iter   = d0.max_iter;
     if (decode && last == 0) { // ldpc_decoder_impl.cpp:88-94
       if (!use_crc) {
-        for (int bb = l; bb < (K + 7) / 8; bb += H) {
-          const int rem = K - 8 * bb;
-          out[bb]       = (rem >= 8) ? 0xff : (uint8_t)(0xff << (8 - rem));
-        }
+        store_all_ones(out, K, l, H);
       }
       if (l == 0)
         iters_out[cbi] = 0;
       decode = false;
     }
     // ldpc_decoder_impl.cpp:101-114
-    int nlay = 0;
-    if (decode) {
-      int cb_len = max(last + 2 * Z, K + 4 * Z);
-      cb_len     = ((cb_len + Z - 1) / Z) * Z;
-      nlay       = cb_len / Z - bgK;
-    }
+    const int nlay = decode ? cb_nof_layers(last, Z, bgi) : 0;
     int nlay_max = nlay;
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1)
@@ -212,12 +188,11 @@ ldpc_decode_pkw_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
         const int       d     = (int)((li >> 10) & 0x3fu);
         const uint32_t* edges = edges_g + 2 * e0;
         if (run && m < nlay)
-          update_rows_pk_visit<false>(it, m, d, soft, msg0 + 64 * (li >> 16), edges, l, Hv, Zv, base);
+          update_rows_pk_visit<false>(it, m, d, soft, msg0 + 64 * (li >> 16), pk_adr_computed{edges, l, Hv, Zv, base});
         __syncthreads();
       }
       if (use_crc && !final_only) { // ldpc_decoder_impl.cpp:126-133
-        const bool ok = zi >= 0 ? group_crc_is_zero(soft + base, tab, zi, (int)order_c, L, &red[64 + g], l, H, run)
-                                : group_crc_is_zero_div(soft + base, tab, d0.crc_poly, poly, order_c, K, L, &red[64 + g], l, H, run);
+        const bool ok = group_crc_is_zero(soft + base, tab, zi, d0.crc_poly, poly, order_c, K, L, &red[64 + g], l, H, run);
         if (run && ok) {
           result_iters = it + 1;
           run          = false;
@@ -225,8 +200,7 @@ ldpc_decode_pkw_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
       }
     }
     if (final_only) { // pusch_decoder_impl.cpp:105-118
-      const bool ok = zi >= 0 ? group_crc_is_zero(soft + base, tab, zi, (int)order_c, L, &red[64 + g], l, H, decode)
-                              : group_crc_is_zero_div(soft + base, tab, d0.crc_poly, poly, order_c, K, L, &red[64 + g], l, H, decode);
+      const bool ok = group_crc_is_zero(soft + base, tab, zi, d0.crc_poly, poly, order_c, K, L, &red[64 + g], l, H, decode);
       result_iters  = ok ? max_iter : 0;
     }
     if (decode) {
@@ -240,6 +214,19 @@ ldpc_decode_pkw_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
     b = next;
   }
 }
+
+// The instances of the kernel by what selects them, each row from ONE template argument (as pk_instances of ldpc_decode_pk.hip).
+typedef decltype(&ldpc_decode_pkw_kernel<false>) pkw_kernel_fn;
+struct pkw_instance {
+  bool          gmsg;
+  pkw_kernel_fn kernel;
+};
+template <bool GMSG>
+constexpr pkw_instance pkw_instance_of()
+{
+  return {GMSG, ldpc_decode_pkw_kernel<GMSG>};
+}
+constexpr pkw_instance pkw_instances[] = {pkw_instance_of<false>(), pkw_instance_of<true>()};
 
 } // namespace
 
@@ -275,20 +262,20 @@ int miphy_ldpc_pkw_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miph
 {
   if (L.c.bundle_count == 0)
     return MIPHY_OK;
-  const bool  gm   = L.gmsg_pairs > 0;
-  const void* kern = gm ? (const void*)ldpc_decode_pkw_kernel<true> : (const void*)ldpc_decode_pkw_kernel<false>;
+  const bool gm = L.gmsg_pairs > 0;
+  pkw_kernel_fn kern = nullptr;
+  for (const pkw_instance& i : pkw_instances)
+    if (i.gmsg == gm)
+      kern = i.kernel;
+  MIPHY_REQUIRE(kern, "ldpc_decode: no wave kernel instance {global messages %d}", gm);
   if (L.lds > 48 * 1024)
-    MIPHY_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+    MIPHY_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
   uint32_t* queue = nullptr;
   int       rc    = miphy_next_queue_counter(ctx, &queue);
   if (rc)
     return rc;
-  if (gm)
-    hipLaunchKernelGGL((ldpc_decode_pkw_kernel<true>), dim3(L.grid), dim3(64), L.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, (int)L.c.lay,
-                       (int)L.c.soft_total, harq_slot, harq_crc_ok, d_order, d_bundles, L.c.bundle_count, queue, (uint32_t*)gmsg, L.gmsg_pairs);
-  else
-    hipLaunchKernelGGL((ldpc_decode_pkw_kernel<false>), dim3(L.grid), dim3(64), L.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, (int)L.c.lay,
-                       (int)L.c.soft_total, harq_slot, harq_crc_ok, d_order, d_bundles, L.c.bundle_count, queue, (uint32_t*)nullptr, 0);
+  hipLaunchKernelGGL(kern, dim3(L.grid), dim3(64), L.lds, s, d_descs, ctx->d_tables, llr, out_bits, iters, (int)L.c.lay, (int)L.c.soft_total, harq_slot, harq_crc_ok,
+                     d_order, d_bundles, L.c.bundle_count, queue, gm ? (uint32_t*)gmsg : nullptr, L.gmsg_pairs);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }

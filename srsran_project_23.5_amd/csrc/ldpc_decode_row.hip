@@ -16,7 +16,7 @@
 //   * hard decision + CRC run in-kernel: each lane reduces one 32-bit word of the message to a partial remainder,
 //     multiplies it by x^(32k) mod P and the partial remainders are XOR-reduced with wavefront shuffles.
 #include "miphy_internal.h"
-#include "ldpc_pk_device.h"
+#include "ldpc_frame_device.h"
 
 namespace {
 
@@ -151,14 +151,12 @@ ldpc_decode_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   const int                 nt  = blockDim.x;
   const int                 Z   = dsc.Z;
   const int                 bgi = (dsc.bg == 1) ? 0 : 1;
-  const int                 bgK = bgi ? 10 : 22;
-  const int                 bgM = bgi ? 42 : 46;
-  const int                 K   = bgK * Z;
+  const int                 K   = miphy_bg_K(bgi) * Z;
   const int                 zp  = tab->z_pos[Z];
 
   int8_t*   soft = reinterpret_cast<int8_t*>(smem);
-  const int lay_alloc  = min(bgM, max(4, max_nodes - bgK));
-  const int soft_bytes = ((bgK + lay_alloc) * Z + 15) & ~15;
+  const int lay_alloc  = miphy_ldpc_layers(bgi, max_nodes);
+  const int soft_bytes = miphy_ldpc_soft_bytes(bgi, lay_alloc, Z);
   // Check-row state is only allocated for the layers this launch can reach (host-side bound from in_len).
   uint32_t* st0  = reinterpret_cast<uint32_t*>(smem + soft_bytes);
   uint32_t* st1  = st0 + lay_alloc * Z;
@@ -176,39 +174,7 @@ ldpc_decode_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   if (tid < 16)
     red[tid] = 0;
   // Stage LLRs into LDS (variable nodes 0,1 are punctured -> 0) and find the last non-zero input.
-  for (int k = tid; k < 2 * Z; k += nt)
-    soft[k] = 0;
-  for (int k = 2 * Z + in_len + tid; k < soft_bytes; k += nt)
-    soft[k] = 0;
-  __syncthreads();
-  int last = 0;
-  if ((((uintptr_t)llr | (uintptr_t)(2 * Z)) & 15) == 0) {
-    // 16-byte coalesced path (the common case: Z multiple of 8, 16-byte aligned codeblock buffers).
-    const uint4* src = reinterpret_cast<const uint4*>(llr);
-    uint4*       dst = reinterpret_cast<uint4*>(soft + 2 * Z);
-    const int    nq  = in_len >> 4;
-    for (int q = tid; q < nq; q += nt) {
-      const uint4 v = src[q];
-      dst[q]        = v;
-      int hi = -1;
-      hi     = v.x ? 3 - (__clz((int)v.x) >> 3) : hi;
-      hi     = v.y ? 7 - (__clz((int)v.y) >> 3) : hi;
-      hi     = v.z ? 11 - (__clz((int)v.z) >> 3) : hi;
-      hi     = v.w ? 15 - (__clz((int)v.w) >> 3) : hi;
-      last   = (hi >= 0) ? 16 * q + hi + 1 : last;
-    }
-    for (int k = (nq << 4) + tid; k < in_len; k += nt) {
-      const int8_t v  = llr[k];
-      soft[2 * Z + k] = v;
-      last            = (v != 0) ? k + 1 : last;
-    }
-  } else {
-    for (int k = tid; k < in_len; k += nt) {
-      const int8_t v  = llr[k];
-      soft[2 * Z + k] = v;
-      last            = (v != 0) ? k + 1 : last;
-    }
-  }
+  int last = cb_plain_load(soft, llr, in_len, Z, soft_bytes, tid, nt);
   atomicMax(reinterpret_cast<int*>(&red[0]), last);
   __syncthreads();
   last = (int)red[0];
@@ -216,21 +182,14 @@ ldpc_decode_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   const bool use_crc = dsc.crc_poly != MIPHY_CRC_NONE;
 
   if (last == 0) { // ldpc_decoder_impl.cpp:88-94
-    if (!use_crc) {
-      for (int b = tid; b < (K + 7) / 8; b += nt) {
-        const int rem = K - 8 * b;
-        out[b]        = (rem >= 8) ? 0xff : (uint8_t)(0xff << (8 - rem));
-      }
-    }
+    if (!use_crc)
+      store_all_ones(out, K, tid, nt);
     if (tid == 0)
       iters_out[cbx] = 0;
     return;
   }
 
-  // ldpc_decoder_impl.cpp:101-114
-  int cb_len = max(last + 2 * Z, K + 4 * Z);
-  cb_len     = ((cb_len + Z - 1) / Z) * Z;
-  const int nof_layers = cb_len / Z - bgK;
+  const int nof_layers = cb_nof_layers(last, Z, bgi);
 
   const uint32_t* edges_g   = tab->edge[bgi][zp];
   const uint16_t* row_start = tab->row_start[bgi];
@@ -291,19 +250,18 @@ ldpc_decode_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
 
 // LDS bytes of a workgroup of `threads` (>= Z of every codeblock) lanes whose codeblocks reach `lay` layers: soft bits, one state word per
 // (layer, row) + the second word of the four degree-19 rows, 16 reduction words. The kernel carves the same block up from its node bound.
-size_t miphy_ldpc_row_lds_bytes(int bgK, int lay, size_t threads)
+size_t miphy_ldpc_row_lds_bytes(int bgi, int lay, size_t threads)
 {
-  return ((((size_t)bgK + lay) * threads + 15) & ~(size_t)15) + (size_t)(lay + 4) * threads * 4 + 64;
+  return (size_t)miphy_ldpc_soft_bytes(bgi, lay, (int)threads) + (size_t)(lay + 4) * threads * 4 + 64;
 }
 
 void miphy_ldpc_row_geometry(miphy_ldpc_launch& L)
 {
   const miphy_ldpc_class& c   = L.c;
-  const int               bgK = c.bgi ? 10 : 22;
   L.used    = MIPHY_LDPC_KERNEL_SCALAR;
   L.threads = ((c.max_Z + 63) / 64) * 64;
-  L.nodes   = bgK + c.lay;
-  L.lds     = miphy_ldpc_row_lds_bytes(bgK, c.lay, (size_t)L.threads);
+  L.nodes   = miphy_bg_K(c.bgi) + c.lay;
+  L.lds     = miphy_ldpc_row_lds_bytes(c.bgi, c.lay, (size_t)L.threads);
   L.grid    = c.count;
 }
 

@@ -4,6 +4,7 @@
 // ldpc_decoder_avx2.cpp:66-243, avx2_support.h:65-106 of the reference; every kernel built from these functions is bit-identical to it.
 #pragma once
 #include "miphy_internal.h"
+#include <type_traits>
 
 namespace {
 
@@ -196,44 +197,52 @@ __device__ __forceinline__ void pk_table_request(pk_adr_quad* q, pk_adr_row row,
   }
 }
 
-// `base` = LDS byte offset of the codeblock's soft bits (0 where a workgroup holds one codeblock: the term then folds away).
+// Where the soft-bit addresses of a visit come from. Computed: the layer's {shift, column * Z} words (pk_edge_addresses), this lane's row
+// pair (l, l + H) and `base` = LDS byte offset of the codeblock's soft bits (0 where a workgroup holds one codeblock: the term then folds away).
+struct pk_adr_computed {
+  static constexpr bool TABLE = false;
+  const uint32_t*       edges;
+  int                   l, H, Z;
+  uint32_t              base;
+};
+// From a table (ATAB instances): the addresses of this visit arrive in `q` (pk_table_addresses), which leaves with those of the layer at
+// `next`, requested with this lane's `voff` and the quad `stride` (pk_table_request).
+struct pk_adr_table {
+  static constexpr bool TABLE = true;
+  pk_adr_quad*          q;
+  pk_adr_row            next;
+  uint32_t              voff, stride;
+};
 // PARTS > 1 (latency form of the packed kernel: PARTS times the wavefronts per codeblock, each part of the workgroup owns a share of
 // the edges of a layer): D is the number of edges of THIS part; between the two phases the parts exchange their partial {min1, min2,
 // sign parity} through LDS (`xch` = this lane's column of the exchange area [part][3][xs], `part` = this part) and merge them -- the
 // two smallest magnitudes of a union are min(a1, b1) and min(max(a1, b1), min(a2, b2)), an associative rule. The function then
 // contains a workgroup barrier: EVERY thread calls it, `active` = the lane owns rows (an idle lane computes on soft bits it may read
 // but stores nothing).
-struct pk_no_hook {
-  __device__ __forceinline__ void operator()() const {}
-};
 // `mid` is called once between the two phases (the latency form issues the scalar loads of the next layer's edges there: behind the last LDS
 // read of the layer, so that they do not turn the partial lgkmcnt waits on the in-order LDS returns into waits for everything).
-// ATAB: the addresses of this visit arrive in `aq` (pk_table_addresses), which leaves with those of the layer at `anext`.
+template <typename MID>
+struct pk_exchange {
+  uint32_t* xch;
+  int       part, xs;
+  bool      active;
+  MID       mid;
+};
+struct pk_no_exchange {}; // PARTS == 1: every other caller
 // DETECT (PARTS == 1; the instances of the packed throughput kernel that leave out visits -- every other caller gets the update as it was,
 // instruction for instruction) returns: every one of the 2 D soft bits this lane read was infinite. Such rows are frozen -- this update
 // and every later one of the layer rewrites each of them to +-127 with the sign it has, whatever the messages are -- so a wavefront whose
 // lanes all say so may leave out its later visits of the layer (ldpc_decode_pk.hip, "saturated rows"). The test is four instructions per
 // visit -- three packed minima and a compare: the running minima start from 0x7fff instead of 120 and are clipped behind the edge loop
 // (120 twice in a running minimum IS the clip: the same min1 / min2), and the unclipped min1 of both rows is compared with V_INF_MIN.
-template <int D, bool FIRST, int PARTS = 1, typename MID, bool FOLD, bool ATAB = false, bool DETECT = false>
+template <int D, bool FIRST, int PARTS = 1, bool FOLD, bool DETECT = false, typename ADR, typename XCH = pk_no_exchange>
 __device__ __forceinline__ bool update_rows_pk(int8_t* __restrict__ soft,
                                                uint32_t* __restrict__ c2v, // this lane's message dword of edges 0,1 of the layer
-                                               const uint32_t* __restrict__ edges, // {shift, column*Z} per edge
-                                               int l,
-                                               int H,
-                                               int Z,
-                                               uint32_t base = 0,
-                                               bool active = true,
-                                               uint32_t* xch = nullptr,
-                                               int part = 0,
-                                               int xs = 0,
-                                               MID mid = MID(),
-                                               pk_adr_quad* aq = nullptr,
-                                               pk_adr_row anext = pk_adr_row(),
-                                               uint32_t avoff = 0,
-                                               uint32_t astride = 0)
+                                               ADR adr,
+                                               XCH x = XCH())
 {
-  constexpr bool SPLIT = PARTS > 1;
+  constexpr bool SPLIT = PARTS > 1, ATAB = ADR::TABLE;
+  static_assert(SPLIT != std::is_same<XCH, pk_no_exchange>::value, "the latency form, and nobody else, exchanges partial results");
   s16x2    v2c[D], mabs[D];
   uint32_t adrA[D], adrB[D];
   int      rawA[D], rawB[D];
@@ -244,9 +253,9 @@ __device__ __forceinline__ bool update_rows_pk(int8_t* __restrict__ soft,
   // messages): the latency of the LDS pipe is paid once per layer instead of once per group of edges.
   static_assert(!(DETECT && SPLIT), "the latency form runs every visit");
   if constexpr (ATAB)
-    pk_table_addresses<D, !DETECT>(adrA, adrB, aq);
+    pk_table_addresses<D, !DETECT>(adrA, adrB, adr.q);
   else
-    pk_edge_addresses<D, FOLD>(adrA, adrB, edges, l, H, Z, base);
+    pk_edge_addresses<D, FOLD>(adrA, adrB, adr.edges, adr.l, adr.H, adr.Z, adr.base);
   P2_T(q1);
 #pragma unroll
   for (int j = 0; j < D; ++j) {
@@ -295,8 +304,10 @@ __device__ __forceinline__ bool update_rows_pk(int8_t* __restrict__ soft,
 #ifdef LDPC_PK_PROFILE2
   unsigned long long q4 = q3;
 #endif
-  if (SPLIT) {
-    uint32_t* xw = xch + 3 * part * xs;
+  if constexpr (SPLIT) {
+    uint32_t* const xch = x.xch;
+    const int       part = x.part, xs = x.xs;
+    uint32_t*       xw = xch + 3 * part * xs;
     xw[0] = as_u(mag1), xw[xs] = as_u(mag2), xw[2 * xs] = spx;
 #ifndef LDPC_PK_EMU_NOXBAR // timing-only (WRONG results): no barrier in the exchange
     __syncthreads();
@@ -315,10 +326,14 @@ __device__ __forceinline__ bool update_rows_pk(int8_t* __restrict__ soft,
     }
   }
   P2_T(q5);
-  mid();
+  bool active = true;
+  if constexpr (SPLIT) {
+    x.mid();
+    active = x.active;
+  }
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO2); // the second phase: messages, soft-bit stores, then the layer barrier
   if constexpr (ATAB)
-    pk_table_request<D>(aq, anext, avoff, astride);
+    pk_table_request<D>(adr.q, adr.next, adr.voff, adr.stride);
   // Scaling by 0.8 = floor(x * 52428 / 65536), per row (avx2_support.h:65-106).
   const uint32_t s1A = ((uint32_t)(uint16_t)mag1.x * 52428u) >> 16, s1B = ((uint32_t)(uint16_t)mag1.y * 52428u) >> 16;
   const uint32_t s2A = ((uint32_t)(uint16_t)mag2.x * 52428u) >> 16, s2B = ((uint32_t)(uint16_t)mag2.y * 52428u) >> 16;
@@ -364,7 +379,7 @@ __device__ __forceinline__ bool update_rows_pk(int8_t* __restrict__ soft,
 // to read a soft bit of zero (ZE = its position in the row: 0 in layer 1, 1 in layer 2) and no message of the layer exists yet.
 // What makes it exact ("first iteration"):
 //  - Every decode starts with the two punctured columns, soft bits [0, 2Z), at zero: ldpc_decode_pk.hip pk_fused_load ("the two punctured
-//    nodes") and the plain load ("soft[k] = 0" for k < 2 Z), ldpc_decode_pkw.hip ("clear the group's soft bits").
+//    nodes"), ldpc_frame_device.h cb_plain_load ("soft[k] = 0" for k < 2 Z), ldpc_decode_pkw.hip ("clear the group's soft bits").
 //  - Layer 0 of both base graphs holds columns 0 AND 1: two zero inputs, min1 = min2 = 0, every message 0, no soft bit changes -- the
 //    kernels do not visit it in iteration 0 at all, and visit it in iteration 1 with the FIRST instance (no message read = zeros read).
 //  - Layer 1 has column 0 as its edge 0 and lacks column 1; layer 2 has columns 0, 1 as edges 0, 1, and layer 1 has left column 1 at
@@ -377,18 +392,18 @@ __device__ __forceinline__ bool update_rows_pk(int8_t* __restrict__ soft,
 //    soft bits are not an output -- hard bits, CRC verdict and iteration count are.
 // So: the soft bits of the other D - 1 edges are read, one packed minimum of |s| and the sign parity are accumulated, the value goes to
 // edge ZE's soft bits and byte slots of the layer's message dwords (layout of update_rows_pk, zeros elsewhere); no other soft bit is stored.
-template <int D, int ZE, bool FOLD, bool ATAB = false>
-__device__ __forceinline__ void update_rows_pk_zero(int8_t* __restrict__ soft, uint32_t* __restrict__ c2v, const uint32_t* __restrict__ edges, int l, int H, int Z,
-                                                    uint32_t base = 0, pk_adr_quad* aq = nullptr, pk_adr_row anext = pk_adr_row(), uint32_t avoff = 0, uint32_t astride = 0)
+template <int D, int ZE, bool FOLD, typename ADR>
+__device__ __forceinline__ void update_rows_pk_zero(int8_t* __restrict__ soft, uint32_t* __restrict__ c2v, ADR adr)
 {
+  constexpr bool ATAB = ADR::TABLE;
   static_assert((ZE == 0 || ZE == 1) && D > 2, "the known-zero edge is edge 0 or 1 of its row, and other edges exist");
   uint32_t adrA[D], adrB[D];
   int      rawA[D], rawB[D];
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO);
   if constexpr (ATAB)
-    pk_table_addresses<D>(adrA, adrB, aq);
+    pk_table_addresses<D>(adrA, adrB, adr.q);
   else
-    pk_edge_addresses<D, FOLD>(adrA, adrB, edges, l, H, Z, base);
+    pk_edge_addresses<D, FOLD>(adrA, adrB, adr.edges, adr.l, adr.H, adr.Z, adr.base);
 #pragma unroll
   for (int j = 0; j < D; ++j) {
     if (j != ZE) {
@@ -411,7 +426,7 @@ __device__ __forceinline__ void update_rows_pk_zero(int8_t* __restrict__ soft, u
   }
   __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO2);
   if constexpr (ATAB)
-    pk_table_request<D>(aq, anext, avoff, astride);
+    pk_table_request<D>(adr.q, adr.next, adr.voff, adr.stride);
   const uint32_t sA = ((uint32_t)(uint16_t)mag.x * 52428u) >> 16, sB = ((uint32_t)(uint16_t)mag.y * 52428u) >> 16;
   const s16x2    pm = pk_ashr15(as_s2(spx));
   const s16x2    c  = as_s2((sA | (sB << 16)) ^ as_u(pm)) - pm; // |c| <= 96: no clamp
@@ -427,13 +442,13 @@ __device__ __forceinline__ void update_rows_pk_zero(int8_t* __restrict__ soft, u
 
 // A part without edges in this layer (a low-degree layer split four ways): it contributes the neutral partial result and takes part in
 // the exchange barrier.
-template <int PARTS, typename MID>
-__device__ __forceinline__ void update_rows_pk_none(uint32_t* xch, int part, int xs, MID mid)
+template <typename MID>
+__device__ __forceinline__ void update_rows_pk_none(pk_exchange<MID> x)
 {
-  uint32_t* xw = xch + 3 * part * xs;
-  xw[0] = as_u(splat(LLR_MAX)), xw[xs] = as_u(splat(LLR_MAX)), xw[2 * xs] = 0u;
+  uint32_t* xw = x.xch + 3 * x.part * x.xs;
+  xw[0] = as_u(splat(LLR_MAX)), xw[x.xs] = as_u(splat(LLR_MAX)), xw[2 * x.xs] = 0u;
   __syncthreads();
-  mid();
+  x.mid();
 }
 
 // The latency form: this part's edges of a layer of degree d. The ceil(d / 2) message pairs of the layer are dealt to the parts in
@@ -462,15 +477,15 @@ __device__ __forceinline__ void load_part_edges(part_edges<PARTS>& pe, const uin
 }
 
 template <bool FIRST, int PARTS, typename MID>
-__device__ __forceinline__ void update_rows_pk_split(const part_edges<PARTS>& pe, int part, int8_t* soft, uint32_t* c2v, int l, int H, int Z, bool active,
-                                                     uint32_t* xch, int xs, MID mid)
+__device__ __forceinline__ void update_rows_pk_split(const part_edges<PARTS>& pe, int8_t* soft, uint32_t* c2v, int l, int H, int Z, pk_exchange<MID> x)
 {
+  const pk_adr_computed adr = {pe.w, l, H, Z, 0};
   c2v += 64 * pe.p0;
   switch (pe.da) {
 #define PK_SPLIT_CASE(N)                                                                            \
   case N:                                                                                           \
     if (N <= part_edges<PARTS>::EMAX)                                                               \
-      update_rows_pk<(N <= part_edges<PARTS>::EMAX ? N : 1), FIRST, PARTS, MID, false>(soft, c2v, pe.w, l, H, Z, 0, active, xch, part, xs, mid); \
+      update_rows_pk<(N <= part_edges<PARTS>::EMAX ? N : 1), FIRST, PARTS, false>(soft, c2v, adr, x); \
     break;
     PK_SPLIT_CASE(10)
     PK_SPLIT_CASE(9)
@@ -481,62 +496,47 @@ __device__ __forceinline__ void update_rows_pk_split(const part_edges<PARTS>& pe
     PK_SPLIT_CASE(2)
     PK_SPLIT_CASE(1)
     default:
-      update_rows_pk_none<PARTS, MID>(xch, part, xs, mid);
+      update_rows_pk_none(x);
       break;
 #undef PK_SPLIT_CASE
   }
 }
 
 template <bool FIRST, bool FOLD, bool DETECT = false>
-__device__ __forceinline__ bool update_rows_pk_any(int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
+__device__ __forceinline__ bool update_rows_pk_any(int d, int8_t* soft, uint32_t* c2v, pk_adr_computed adr)
 {
-  bool r = false;
   switch (d) {
-    case 19:
-      r = update_rows_pk<19, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
-      break;
-    case 10:
-      r = update_rows_pk<10, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
-      break;
-    case 9:
-      r = update_rows_pk<9, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
-      break;
-    case 8:
-      r = update_rows_pk<8, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
-      break;
-    case 7:
-      r = update_rows_pk<7, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
-      break;
-    case 6:
-      r = update_rows_pk<6, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
-      break;
-    case 5:
-      r = update_rows_pk<5, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
-      break;
-    case 4:
-      r = update_rows_pk<4, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
-      break;
+#define PK_ANY_CASE(N) \
+  case N:              \
+    return update_rows_pk<N, FIRST, 1, FOLD, DETECT>(soft, c2v, adr);
+    PK_ANY_CASE(19)
+    PK_ANY_CASE(10)
+    PK_ANY_CASE(9)
+    PK_ANY_CASE(8)
+    PK_ANY_CASE(7)
+    PK_ANY_CASE(6)
+    PK_ANY_CASE(5)
+    PK_ANY_CASE(4)
+#undef PK_ANY_CASE
     default:
-      r = update_rows_pk<3, FIRST, 1, pk_no_hook, FOLD, false, DETECT>(soft, c2v, edges, l, H, Z, base);
-      break;
+      return update_rows_pk<3, FIRST, 1, FOLD, DETECT>(soft, c2v, adr);
   }
-  return r;
 }
 
 // Layers m = 1 and 2 of the first iteration: the degrees these two layers have in the two base graphs (miphy_ctx.hip asserts them).
 template <bool FOLD>
-__device__ __forceinline__ void update_rows_pk_zero_any(int m, int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
+__device__ __forceinline__ void update_rows_pk_zero_any(int m, int d, int8_t* soft, uint32_t* c2v, pk_adr_computed adr)
 {
   if (m == 1) {
     if (d == 19)
-      update_rows_pk_zero<19, 0, FOLD>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk_zero<19, 0, FOLD>(soft, c2v, adr);
     else
-      update_rows_pk_zero<10, 0, FOLD>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk_zero<10, 0, FOLD>(soft, c2v, adr);
   } else {
     if (d == 19)
-      update_rows_pk_zero<19, 1, FOLD>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk_zero<19, 1, FOLD>(soft, c2v, adr);
     else
-      update_rows_pk_zero<8, 1, FOLD>(soft, c2v, edges, l, H, Z, base);
+      update_rows_pk_zero<8, 1, FOLD>(soft, c2v, adr);
   }
 }
 
@@ -544,33 +544,33 @@ __device__ __forceinline__ void update_rows_pk_zero_any(int m, int d, int8_t* so
 // nothing there), so layer 0's messages are first written in iteration 1, by the instance that reads none. FOLD: pk_edge_addresses.
 // Returns what update_rows_pk does; the known-zero visits read a zero and never say that their rows are saturated.
 template <bool FOLD, bool DETECT = false>
-__device__ __forceinline__ bool update_rows_pk_visit(int it, int m, int d, int8_t* soft, uint32_t* c2v, const uint32_t* edges, int l, int H, int Z, uint32_t base = 0)
+__device__ __forceinline__ bool update_rows_pk_visit(int it, int m, int d, int8_t* soft, uint32_t* c2v, pk_adr_computed adr)
 {
   bool r = false;
   if (it == 0 && (m == 1 || m == 2))
-    update_rows_pk_zero_any<FOLD>(m, d, soft, c2v, edges, l, H, Z, base);
+    update_rows_pk_zero_any<FOLD>(m, d, soft, c2v, adr);
   else if (it == 0 || (it == 1 && m == 0))
-    r = update_rows_pk_any<true, FOLD, DETECT>(d, soft, c2v, edges, l, H, Z, base);
+    r = update_rows_pk_any<true, FOLD, DETECT>(d, soft, c2v, adr);
   else
-    r = update_rows_pk_any<false, FOLD, DETECT>(d, soft, c2v, edges, l, H, Z, base);
+    r = update_rows_pk_any<false, FOLD, DETECT>(d, soft, c2v, adr);
   return r;
 }
 
 // The same visit of an ATAB instance: every layer the launch can reach has degree D (the launch planner sees to that).
 template <int D, bool DETECT = false>
-__device__ __forceinline__ bool update_rows_pk_visit_tab(int it, int m, int8_t* soft, uint32_t* c2v, pk_adr_quad* aq, pk_adr_row anext, uint32_t avoff, uint32_t astride)
+__device__ __forceinline__ bool update_rows_pk_visit_tab(int it, int m, int8_t* soft, uint32_t* c2v, pk_adr_table adr)
 {
   if (it == 0 && m == 1) {
-    update_rows_pk_zero<D, 0, true, true>(soft, c2v, nullptr, 0, 0, 0, 0, aq, anext, avoff, astride);
+    update_rows_pk_zero<D, 0, true>(soft, c2v, adr);
     return false;
   }
   if (it == 0 && m == 2) {
-    update_rows_pk_zero<D, 1, true, true>(soft, c2v, nullptr, 0, 0, 0, 0, aq, anext, avoff, astride);
+    update_rows_pk_zero<D, 1, true>(soft, c2v, adr);
     return false;
   }
   if (it == 0 || (it == 1 && m == 0))
-    return update_rows_pk<D, true, 1, pk_no_hook, true, true, DETECT>(soft, c2v, nullptr, 0, 0, 0, 0, true, nullptr, 0, 0, pk_no_hook(), aq, anext, avoff, astride);
-  return update_rows_pk<D, false, 1, pk_no_hook, true, true, DETECT>(soft, c2v, nullptr, 0, 0, 0, 0, true, nullptr, 0, 0, pk_no_hook(), aq, anext, avoff, astride);
+    return update_rows_pk<D, true, 1, true, DETECT>(soft, c2v, adr);
+  return update_rows_pk<D, false, 1, true, DETECT>(soft, c2v, adr);
 }
 
 __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b, uint32_t poly, uint32_t order)

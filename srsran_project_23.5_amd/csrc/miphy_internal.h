@@ -46,6 +46,37 @@ static inline __host__ __device__ int miphy_crc_zmask_index(int crc_id)
   return crc_id == 0 ? 0 : (crc_id == 1 ? 1 : (crc_id == 3 ? 2 : -1));
 }
 
+// Geometry of an LDPC codeblock, for host and device alike: the kernels carve their LDS up with the very functions the launch planner
+// sizes it with. bgi = base graph - 1.
+static constexpr __host__ __device__ int miphy_bg_K(int bgi) // systematic columns
+{
+  return bgi ? 10 : 22;
+}
+static constexpr __host__ __device__ int miphy_bg_M(int bgi) // layers (rows of the base graph)
+{
+  return bgi ? 42 : 46;
+}
+static constexpr __host__ __device__ int miphy_bg_N_short(int bgi) // columns without the two punctured ones: the longest input, in units of Z
+{
+  return bgi ? 50 : 66;
+}
+// Variable nodes an input of in_len soft bits reaches: ceil((in_len + 2 Z) / Z), the punctured nodes in front (ldpc_decoder_impl.cpp:101-114).
+static constexpr __host__ __device__ int miphy_ldpc_nodes(unsigned in_len, unsigned Z)
+{
+  return (int)((in_len + 2u * Z + Z - 1u) / Z);
+}
+// Layers a launch can reach from its bound on the variable nodes (no decode runs fewer than four).
+static constexpr __host__ __device__ int miphy_ldpc_layers(int bgi, int nodes)
+{
+  const int M = miphy_bg_M(bgi), lay = nodes - miphy_bg_K(bgi), lo = 4 > lay ? 4 : lay;
+  return M < lo ? M : lo;
+}
+// Bytes of the soft bits of a codeblock that reaches `lay` layers, as a 16-byte multiple (Zt >= Z: the launch's bound or the lifting size).
+static constexpr __host__ __device__ int miphy_ldpc_soft_bytes(int bgi, int lay, int Zt)
+{
+  return ((miphy_bg_K(bgi) + lay) * Zt + 15) & ~15;
+}
+
 // Scratch workspaces of a context, one per user group: calls that run one inside another take different slots.
 enum miphy_workspace {
   MIPHY_WS_GENERAL = 0,  // staged descriptors of the transport-block level entry points (PUSCH decode, PDSCH encode), the UL-SCH
@@ -211,7 +242,7 @@ int miphy_ldpc_run_launches(miphy_ctx* ctx, const miphy_ldpc_launches& T, const 
                             uint8_t* harq_crc_ok, const miphy_ldpc_rdm_desc* d_rdm, const int8_t* rm_in, void* gmsg, hipStream_t s);
 // One-row-per-lane kernel (ldpc_decode_row.hip): LDS bytes of a workgroup of `threads` lanes whose codeblocks reach `lay` layers, geometry
 // of L.c, and the launch of L.grid codeblocks (d_order: codeblocks d_order[0 .. grid) of the arrays, null: the first grid).
-size_t miphy_ldpc_row_lds_bytes(int bgK, int lay, size_t threads);
+size_t miphy_ldpc_row_lds_bytes(int bgi, int lay, size_t threads);
 void   miphy_ldpc_row_geometry(miphy_ldpc_launch& L);
 int    miphy_ldpc_row_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const miphy_ldpc_dec_desc* d_descs, const uint32_t* d_order, const int8_t* llr,
                              uint8_t* out_bits, int32_t* iters, const uint32_t* harq_slot, uint8_t* harq_crc_ok, hipStream_t s);
@@ -225,7 +256,7 @@ int  miphy_ldpc_pkw_launch(miphy_ctx* ctx, const miphy_ldpc_launch& L, const mip
 // + exchange slots of the latency form), wavefronts per CU its register budget allows, resident workgroups per CU (of `waves` wavefronts
 // and `lds` bytes each) and of a launch, and the launch of
 // L.c.count codeblocks (d_order: codeblocks d_order[0 .. count) of the arrays, null: the first count). d_rdm / rm_in with FUSED only.
-size_t   miphy_ldpc_pk_lds_bytes(int bgK, int lay, size_t Zt, int pairs_all, int parts = 1);
+size_t   miphy_ldpc_pk_lds_bytes(int bgi, int lay, size_t Zt, int pairs_all, int parts = 1);
 int      miphy_ldpc_pk_waves_per_cu(bool fused, int parts = 1);
 int      miphy_ldpc_pk_per_cu(size_t lds, int waves, bool fused, int parts = 1);
 uint32_t miphy_ldpc_pk_grid(const miphy_ctx* ctx, uint32_t n, int threads, size_t lds, bool fused, int parts = 1);
