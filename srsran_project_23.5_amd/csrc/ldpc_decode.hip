@@ -203,7 +203,7 @@ void pk_class_geometry(const miphy_ctx* ctx, const ldpc_knob_values& k, bool fus
   q.atab = k.adr_tables && fused && !gm && q.parts == 1 && one_degree && c.min_Z >= 128;
   // The instance that leaves out the visits of saturated rows (ldpc_decode_pk.hip, RSKIP) where the launch can profit: the throughput form
   // (the parts of the latency form share a layer's rows), codeblocks that run all their iterations (one that stops at its first good
-  // checksum leaves before its rows saturate), messages in LDS (the classes with messages in global memory are the low rates: most of their
+  // checksum leaves before its rows saturate -- a row counts as saturated from the visit that WRITES infinite soft bits only), messages in LDS (the classes with messages in global memory are the low rates: most of their
   // layers hold a parity column with a single check, whose soft bit stays finite unless the channel value itself is clipped). The layer
   // loop of that instance compiles to slower visits, so every other launch keeps the instance without it.
   q.row_skip = k.row_skip && q.parts == 1 && !gm && c.runs_all_iterations;

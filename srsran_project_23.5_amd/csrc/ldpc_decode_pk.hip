@@ -216,8 +216,11 @@ __device__ __forceinline__ int pk_fused_image_out(const int8_t* __restrict__ sof
 //
 // Saturated rows (RSKIP instances of the throughput forms; every other instance runs every visit with the row update as it was -- the launch
 // planner takes RSKIP where a launch can profit, ldpc_decode.hip; the argument is DESIGN.md section 4): a general row update reports per lane that every soft
-// bit it read was infinite (update_rows_pk). Such rows are frozen: every later update of them rewrites each soft bit to +-127 with the sign
-// it has and needs no message of theirs, so no hard bit, checksum or iteration count can come out of it differently. A wavefront whose
+// bit it WROTE is infinite (update_rows_pk: a closed form of the two minima and the sign parity, no per-edge work). An infinite soft bit stays
+// infinite with its sign, so these rows read infinite soft bits only from their next visit on, and such rows are frozen: every later update of
+// them rewrites each soft bit to +-127 with the sign it has and needs no message of theirs, so no hard bit, checksum or iteration count can
+// come out of it differently. (Reporting at the visit that READ infinite soft bits only, the first form of the test, paid for one visit per
+// wavefront and layer that was already frozen.) A wavefront whose
 // row-owning lanes ALL report it at a visit of layer m sets bit m of a mask of its own (scalar registers, cleared per codeblock) and from
 // then on leaves out the body of its visits of layer m: no request, no arithmetic, no message or soft-bit traffic -- straight to the
 // layer's barrier. Nothing is shared between wavefronts and no wavefront leaves a loop early: each executes exactly the barriers it would
@@ -439,7 +442,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
           }
         }
       } else if (!((sat_layers >> m) & 1u)) { // RSKIP (a set bit: saturated rows, the visit changes nothing anybody reads)
-        bool all_inf = false; // this lane's rows read infinite soft bits only
+        bool all_inf = false; // this lane's rows wrote infinite soft bits only
         if (ATAB) {
           // the addresses of the next visit that RUNS: the next layer in turn whose bit is clear (the next one, and layer 0 behind the last, while no bit is set)
           const uint64_t live = ~sat_layers & (((uint64_t)1 << nof_layers) - 1u), above = live & ~(((uint64_t)2 << m) - 1u);

@@ -95,6 +95,14 @@ constexpr int INF_MUL = 255; // an infinite soft bit (|s| > 120) becomes a messa
 // The smallest |v| an infinite soft bit can give: 255 |d| + t with |d| >= 1 and |t| <= 120 against it. A finite one gives |v| <= 120, so
 // "min |v| >= 135" says that every soft bit a row read was infinite ("saturated rows").
 constexpr int V_INF_MIN = INF_MUL - LLR_MAX;
+// The smallest magnitude of an infinite soft bit: "every |v + c| >= 121" says that every soft bit a row WRITES is infinite.
+constexpr int S_INF_MIN = LLR_MAX + 1;
+// Scaled 120: the message every edge of a row gets whose inputs are all infinite (both minima clipped at 120).
+constexpr int C_SAT = (LLR_MAX * 52428) >> 16;
+// What the detection of saturated rows takes off the unclipped first minimum of a row of odd parity, so that min1u + C_SAT - it reaches
+// S_INF_MIN exactly when min1u reaches V_INF_MIN, and a finite min1u (<= 120, with any scaled second minimum <= C_SAT) stays below.
+constexpr int ODD_PARITY_DROP = V_INF_MIN + C_SAT - S_INF_MIN;
+static_assert(C_SAT == 95 && ODD_PARITY_DROP == 109 && LLR_MAX + C_SAT - ODD_PARITY_DROP < S_INF_MIN, "saturated rows: the odd-parity term");
 
 // Stage A of a row update, shared by its forms: both rows' soft-bit addresses of every edge of the layer with packed 16-bit arithmetic:
 // {l, l + H} + shift, wrap at Z by the unsigned minimum of p and p - Z -- three packed instructions for the two rows. The pair has to be
@@ -230,11 +238,18 @@ struct pk_exchange {
 };
 struct pk_no_exchange {}; // PARTS == 1: every other caller
 // DETECT (PARTS == 1; the instances of the packed throughput kernel that leave out visits -- every other caller gets the update as it was,
-// instruction for instruction) returns: every one of the 2 D soft bits this lane read was infinite. Such rows are frozen -- this update
-// and every later one of the layer rewrites each of them to +-127 with the sign it has, whatever the messages are -- so a wavefront whose
-// lanes all say so may leave out its later visits of the layer (ldpc_decode_pk.hip, "saturated rows"). The test is four instructions per
-// visit -- three packed minima and a compare: the running minima start from 0x7fff instead of 120 and are clipped behind the edge loop
-// (120 twice in a running minimum IS the clip: the same min1 / min2), and the unclipped min1 of both rows is compared with V_INF_MIN.
+// instruction for instruction) returns: every one of the 2 D soft bits this lane WRITES is infinite. An infinite soft bit stays infinite
+// with its sign, so the next visit of these rows reads infinite soft bits only and is frozen -- it and every later one of the layer
+// rewrites each of them to +-127 with the sign it has, whatever the messages are -- so a wavefront whose lanes all say so may leave out
+// its later visits of the layer (ldpc_decode_pk.hip, "saturated rows"). No per-edge work: with min1 <= min2 the two smallest |v| clipped
+// at 120, s1 / s2 their scaled values and min1u the unclipped min1,
+//   every output infinite  <=>  min1u >= V_INF_MIN (every INPUT infinite), or the sign parity is even and min(min1 + s2, min2 + s1) >= 121:
+// with even parity a message has the sign of its own v, |r| = min(127, |v| + |c|); the edge that holds the minimum gets s2, every other
+// one has |v| >= min2 and gets s1 (a tie at the minimum: min2 = min1); with odd parity a finite edge is pulled towards zero and stays finite.
+// Merged into one comparison: min1u may stand for min1 in the first term (min1u > 120 means min1 = 120, s2 = 95: the term is >= 121 either
+// way), and odd parity takes ODD_PARITY_DROP off that term -- it then reaches 121 exactly when every input is infinite. Eight instructions
+// per visit: the running minima start from 0x7fff instead of 120 and are clipped behind the edge loop (three packed minima; 120 twice in a
+// running minimum IS the clip: the same min1 / min2), then a packed multiply-add, two additions, two minima and a compare.
 template <int D, bool FIRST, int PARTS = 1, bool FOLD, bool DETECT = false, typename ADR, typename XCH = pk_no_exchange>
 __device__ __forceinline__ bool update_rows_pk(int8_t* __restrict__ soft,
                                                uint32_t* __restrict__ c2v, // this lane's message dword of edges 0,1 of the layer
@@ -294,9 +309,10 @@ __device__ __forceinline__ bool update_rows_pk(int8_t* __restrict__ soft,
     mag1             = pk_min(mag1, av);
     mag2             = pk_min(mag2, help);
   }
-  bool all_inf = false;
+  bool                   all_inf = false;
+  [[maybe_unused]] s16x2 mag1u;
   if constexpr (DETECT) {
-    all_inf = as_u(pk_min(mag1, splat(V_INF_MIN))) == as_u(splat(V_INF_MIN));
+    mag1u   = mag1;
     mag1    = pk_min(mag1, splat(LLR_MAX));
     mag2    = pk_min(mag2, splat(LLR_MAX));
   }
@@ -331,9 +347,16 @@ __device__ __forceinline__ bool update_rows_pk(int8_t* __restrict__ soft,
     x.mid();
     active = x.active;
   }
-  __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO2); // the second phase: messages, soft-bit stores, then the layer barrier
-  if constexpr (ATAB)
-    pk_table_request<D>(adr.q, adr.next, adr.voff, adr.stride);
+  // FENCE (the table instance that detects): the scaling and the test come in front of the second phase's address request, fenced off
+  // from it, so that the unclipped minimum is dead before the next visit's quads arrive -- with both alive the allocator, at its limit
+  // of 168 registers there, rebuilds 32 constants of the checksum in front of every visit. Not in the instances that compute their
+  // addresses: the plain one spills more with the fence than without it.
+  constexpr bool FENCE = DETECT && ATAB;
+  if constexpr (!FENCE) {
+    __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO2); // the second phase: messages, soft-bit stores, then the layer barrier
+    if constexpr (ATAB)
+      pk_table_request<D>(adr.q, adr.next, adr.voff, adr.stride);
+  }
   // Scaling by 0.8 = floor(x * 52428 / 65536), per row (avx2_support.h:65-106).
   const uint32_t s1A = ((uint32_t)(uint16_t)mag1.x * 52428u) >> 16, s1B = ((uint32_t)(uint16_t)mag1.y * 52428u) >> 16;
   const uint32_t s2A = ((uint32_t)(uint16_t)mag2.x * 52428u) >> 16, s2B = ((uint32_t)(uint16_t)mag2.y * 52428u) >> 16;
@@ -343,6 +366,15 @@ __device__ __forceinline__ bool update_rows_pk(int8_t* __restrict__ soft,
   const s16x2 s1u = as_s2(s1A | (s1B << 16));
   const s16x2 s2p = as_s2(as_u(s2u) ^ as_u(pm)) - pm;
   const s16x2 dsp = (as_s2(as_u(s1u) ^ as_u(pm)) - pm) - s2p; // +-(min1 - min2), scaled
+  if constexpr (DETECT) { // every soft bit these two rows write is infinite (see above; pm = -1 where the parity is odd)
+    const s16x2 low = pk_min(pm * splat(ODD_PARITY_DROP) + mag1u + s2u, mag2 + s1u);
+    all_inf         = as_u(pk_min(low, splat(S_INF_MIN))) == as_u(splat(S_INF_MIN));
+  }
+  if constexpr (FENCE) {
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_setprio(LDPC_PK_SETPRIO2);
+    pk_table_request<D>(adr.q, adr.next, adr.voff, adr.stride);
+  }
   s16x2 cprev = splat(0);
 #pragma unroll
   for (int j = 0; j < D; ++j) {
