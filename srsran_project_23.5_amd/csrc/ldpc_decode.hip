@@ -420,27 +420,14 @@ int validate_descs(const miphy_ctx* ctx, const miphy_ldpc_dec_desc* descs, uint3
   return MIPHY_OK;
 }
 
-// A class-sorted batch on the device: [descriptors | order | bundles], staged from one host image.
+// A class-sorted batch on the device: [descriptors | order | bundles], the staged part of one image.
 struct class_arrays {
-  const miphy_ldpc_dec_desc* descs;
-  const uint32_t*            order;
-  const uint32_t*            bundles;
+  image_slot<miphy_ldpc_dec_desc> descs;
+  image_slot<uint32_t>            order, bundles;
 };
-std::vector<uint8_t> class_image(const miphy_ldpc_dec_desc* descs, uint32_t n, const miphy_ldpc_classes& C)
+class_arrays class_image(const miphy_ldpc_dec_desc* descs, uint32_t n, const miphy_ldpc_classes& C, device_image& img)
 {
-  const size_t         b0 = sizeof(miphy_ldpc_dec_desc) * (size_t)n, b1 = 4 * (size_t)n, b2 = 4 * C.bundles.size();
-  std::vector<uint8_t> h(b0 + b1 + b2);
-  memcpy(h.data(), descs, b0);
-  memcpy(h.data() + b0, C.order.data(), b1);
-  if (b2)
-    memcpy(h.data() + b0 + b1, C.bundles.data(), b2);
-  return h;
-}
-class_arrays class_arrays_at(const void* d, uint32_t n)
-{
-  const uint8_t* b  = static_cast<const uint8_t*>(d);
-  const size_t   b0 = sizeof(miphy_ldpc_dec_desc) * (size_t)n;
-  return {reinterpret_cast<const miphy_ldpc_dec_desc*>(b), reinterpret_cast<const uint32_t*>(b + b0), reinterpret_cast<const uint32_t*>(b + b0 + 4 * (size_t)n)};
+  return {img.put(descs, n), img.put(C.order), img.put(C.bundles)};
 }
 } // namespace
 
@@ -465,9 +452,11 @@ extern "C" int miphy_ldpc_decode_batch(miphy_ctx*                   ctx,
   // Host descriptors are validated here; for device descriptors the caller vouches for validity and may pass `limits`.
   if (!descs_on_device && (rc = validate_descs(ctx, descs, n)))
     return rc;
-  miphy_ldpc_launches  T;
-  std::vector<uint8_t> img; // class-sorted: [descriptors | order | bundles], staged as one region
-  const bool           one_launch = descs_on_device || k.force == MIPHY_LDPC_FORCE_ROW || k.force == MIPHY_LDPC_FORCE_PACKED_ONE;
+  miphy_ldpc_launches T;
+  miphy_ldpc_classes  C;
+  device_image        img; // class-sorted: [descriptors | order | bundles], staged as one region
+  class_arrays        a;   // (one launch: the descriptors alone, in array order)
+  const bool          one_launch = descs_on_device || k.force == MIPHY_LDPC_FORCE_ROW || k.force == MIPHY_LDPC_FORCE_PACKED_ONE;
   if (one_launch) {
     batch_bounds b;
     b.pk_ok = !descs_on_device || limits;
@@ -484,32 +473,30 @@ extern "C" int miphy_ldpc_decode_batch(miphy_ctx*                   ctx,
     }
     plan_one_launch(ctx, k, b, n, T);
   } else {
-    miphy_ldpc_classes C;
     miphy_ldpc_build_classes(descs, n, nullptr, C);
     plan_classes(ctx, C, false, k, T);
-    img = class_image(descs, n, C);
+    a = class_image(descs, n, C, img);
   }
   const void* d = nullptr;
-  if ((rc = one_launch ? miphy_stage_descs(ctx, descs, descs_on_device, sizeof(miphy_ldpc_dec_desc) * (size_t)n, s, &d)
-                       : miphy_stage_descs(ctx, img.data(), 0, img.size(), s, &d)))
+  if ((rc = one_launch ? miphy_stage_descs(ctx, descs, descs_on_device, sizeof(miphy_ldpc_dec_desc) * (size_t)n, s, &d) : miphy_image_to_ring(ctx, img, s, &d)))
     return rc;
-  const class_arrays a    = one_launch ? class_arrays{static_cast<const miphy_ldpc_dec_desc*>(d), nullptr, nullptr} : class_arrays_at(d, n);
-  void*              gmsg = nullptr;
+  void* gmsg = nullptr;
   if (T.gmsg_bytes && (rc = miphy_get_workspace(ctx, MIPHY_WS_LDPC_MSGS, T.gmsg_bytes, &gmsg)))
     return rc;
   if (T.side_streams && (rc = miphy_side_streams(ctx)))
     return rc;
-  return miphy_ldpc_run_launches(ctx, T, a.descs, a.order, a.bundles, llr, out_bits, iters, nullptr, nullptr, nullptr, nullptr, gmsg, s);
+  return miphy_ldpc_run_launches(ctx, T, a.descs.at(d), one_launch ? nullptr : a.order.at(d), one_launch ? nullptr : a.bundles.at(d), llr, out_bits, iters, nullptr,
+                                 nullptr, nullptr, nullptr, gmsg, s);
 }
 
 // ---- prepared form: descriptors validated, sorted into launch classes and uploaded once, the launch table and its message scratch
 // made once; every run is launches only -------------------------------------------------------------------------------------------
 struct miphy_ldpc_decode_plan {
-  miphy_ctx*          ctx;
+  miphy_ctx*          ctx = nullptr;
   miphy_ldpc_launches T;
-  void*               d_buf; // [descriptors | order | bundles | message scratch]
+  miphy_device_block  buf; // [descriptors | order | bundles | message scratch]
   class_arrays        a;
-  void*               d_gmsg;
+  void*               d_gmsg = nullptr;
 };
 
 extern "C" int miphy_ldpc_decode_plan_create(miphy_ctx* ctx, const miphy_ldpc_dec_desc* descs, uint32_t n, miphy_ldpc_decode_plan** out)
@@ -520,34 +507,25 @@ extern "C" int miphy_ldpc_decode_plan_create(miphy_ctx* ctx, const miphy_ldpc_de
     return rc;
   miphy_ldpc_classes C;
   miphy_ldpc_build_classes(descs, n, nullptr, C);
-  auto* p = new miphy_ldpc_decode_plan();
-  p->ctx = ctx, p->d_buf = nullptr, p->d_gmsg = nullptr;
-  if ((rc = miphy_ldpc_plan_launches(ctx, C, false, p->T)) || (p->T.side_streams && (rc = miphy_side_streams(ctx)))) {
-    delete p;
+  std::unique_ptr<miphy_ldpc_decode_plan> p(new miphy_ldpc_decode_plan());
+  p->ctx = ctx;
+  if ((rc = miphy_ldpc_plan_launches(ctx, C, false, p->T)) || (p->T.side_streams && (rc = miphy_side_streams(ctx))))
     return rc;
-  }
-  const std::vector<uint8_t> img  = class_image(descs, n, C);
-  const size_t               off  = (img.size() + 255) & ~(size_t)255;
-  hipError_t                 e    = hipMalloc(&p->d_buf, off + p->T.gmsg_bytes);
-  if (e == hipSuccess)
-    e = hipMemcpy(p->d_buf, img.data(), img.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    miphy_set_error("miphy_ldpc_decode_plan_create: %s", hipGetErrorString(e));
-    if (p->d_buf)
-      (void)hipFree(p->d_buf);
-    delete p;
-    return MIPHY_EHIP;
-  }
-  p->a      = class_arrays_at(p->d_buf, n);
-  p->d_gmsg = p->T.gmsg_bytes ? (uint8_t*)p->d_buf + off : nullptr;
-  *out      = p;
+  device_image img;
+  p->a                           = class_image(descs, n, C, img);
+  const image_slot<uint8_t> gmsg = img.reserve<uint8_t>(p->T.gmsg_bytes, 256);
+  if ((rc = miphy_image_to_block("miphy_ldpc_decode_plan_create", img, p->buf)))
+    return rc;
+  p->d_gmsg = p->T.gmsg_bytes ? gmsg.at(p->buf.get()) : nullptr;
+  *out      = p.release();
   return MIPHY_OK;
 }
 
 extern "C" int miphy_ldpc_decode_plan_run(miphy_ldpc_decode_plan* p, const int8_t* llr, uint8_t* out_bits, int32_t* iters, void* stream)
 {
   MIPHY_REQUIRE(p && llr && out_bits && iters, "miphy_ldpc_decode_plan_run: null argument");
-  return miphy_ldpc_run_launches(p->ctx, p->T, p->a.descs, p->a.order, p->a.bundles, llr, out_bits, iters, nullptr, nullptr, nullptr, nullptr, p->d_gmsg,
+  void* d = p->buf.get();
+  return miphy_ldpc_run_launches(p->ctx, p->T, p->a.descs.at(d), p->a.order.at(d), p->a.bundles.at(d), llr, out_bits, iters, nullptr, nullptr, nullptr, nullptr, p->d_gmsg,
                                  (hipStream_t)stream);
 }
 
@@ -558,9 +536,5 @@ extern "C" uint32_t miphy_ldpc_decode_plan_nof_launches(const miphy_ldpc_decode_
 
 extern "C" void miphy_ldpc_decode_plan_destroy(miphy_ldpc_decode_plan* p)
 {
-  if (!p)
-    return;
-  if (p->d_buf)
-    (void)hipFree(p->d_buf);
   delete p;
 }

@@ -199,9 +199,9 @@ int miphy_ldpc_address_tables(miphy_ctx* ctx, int bgi, int lay, int min_Z, int m
   constexpr int    NZ = MIPHY_MAX_Z / 16 + 1;
   ldpc_adr_tables& T  = ctx->ext->ldpc_adr[{bgi, lay}];
   if (!T.d_ptr) {
-    MIPHY_HIP_CHECK(hipMalloc((void**)&T.d_ptr, NZ * sizeof(void*)));
-    ctx->ext->to_free.push_back(T.d_ptr);
-    MIPHY_HIP_CHECK(hipMemset(T.d_ptr, 0, NZ * sizeof(void*)));
+    const void* none[NZ] = {};
+    if (int rc = miphy_keep_device_copy(ctx, none, sizeof(none), (void**)&T.d_ptr))
+      return rc;
   }
   for (int Z = min_Z; Z <= max_Z; ++Z) {
     if (ctx->h_tables->z_pos[Z] == 0xffff || T.h_ptr[Z / 16])
@@ -213,9 +213,8 @@ int miphy_ldpc_address_tables(miphy_ctx* ctx, int bgi, int lay, int min_Z, int m
     std::vector<uint32_t> h((size_t)words);
     (void)miphy_ldpc_address_table(bgi + 1, Z, lay, h.data());
     void* d = nullptr;
-    MIPHY_HIP_CHECK(hipMalloc(&d, h.size() * 4));
-    ctx->ext->to_free.push_back(d);
-    MIPHY_HIP_CHECK(hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    if (int rc = miphy_keep_device_copy(ctx, h.data(), h.size() * 4, &d))
+      return rc;
     MIPHY_HIP_CHECK(hipMemcpy(T.d_ptr + Z / 16, &d, sizeof(void*), hipMemcpyHostToDevice)); // (an entry no launch in flight reads: its key was not held)
     T.h_ptr[Z / 16] = d;
   }
@@ -398,23 +397,61 @@ int miphy_get_workspace(miphy_ctx* ctx, miphy_workspace slot, size_t bytes, void
   return MIPHY_OK;
 }
 
+int miphy_image_to_block(const char* who, const device_image& img, miphy_device_block& out)
+{
+  MIPHY_REQUIRE(img.ok(), "%s: an array was appended to the device image behind its reserved regions", who);
+  const std::vector<uint8_t> host = img.staged();
+  void*                      d = nullptr;
+  hipError_t                 e = hipMalloc(&d, img.total_bytes());
+  miphy_device_block         blk(e == hipSuccess ? d : nullptr);
+  if (e == hipSuccess)
+    e = hipMemcpy(d, host.data(), host.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    miphy_set_error("%s: device buffer of %zu bytes (%zu uploaded) -> %s", who, img.total_bytes(), host.size(), hipGetErrorString(e));
+    return MIPHY_EHIP;
+  }
+  out = std::move(blk);
+  return MIPHY_OK;
+}
+
+int miphy_image_to_workspace(miphy_ctx* ctx, miphy_workspace slot, const device_image& img, hipStream_t s, void** base)
+{
+  MIPHY_REQUIRE(img.ok(), "workspace %d: an array was appended to the device image behind its reserved regions", (int)slot);
+  if (int rc = miphy_get_workspace(ctx, slot, img.total_bytes(), base))
+    return rc;
+  const std::vector<uint8_t> host = img.staged();
+  return miphy_upload(ctx, *base, host.data(), host.size(), s); // through the pinned ring: the stream is not waited for
+}
+
+int miphy_image_to_ring(miphy_ctx* ctx, const device_image& img, hipStream_t s, const void** base)
+{
+  MIPHY_REQUIRE(img.ok() && img.total_bytes() == img.staged_bytes(), "staging ring: the device image holds more than staged arrays");
+  const std::vector<uint8_t> host = img.staged();
+  return miphy_stage_descs(ctx, host.data(), 0, host.size(), s, base);
+}
+
+int miphy_keep_device_copy(miphy_ctx* ctx, const void* src, size_t bytes, void** out)
+{
+  void* d = nullptr;
+  MIPHY_HIP_CHECK(hipMalloc(&d, bytes ? bytes : 1));
+  const hipError_t e = bytes ? hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    MIPHY_HIP_CHECK(e);
+  }
+  ctx->ext->to_free.push_back(d);
+  *out = d;
+  return MIPHY_OK;
+}
+
 #include "gold_device.h"
-#include "miphy_ext.h"
 int miphy_get_gold_tables(miphy_ctx* ctx, const gold_tables** out)
 {
   if (!ctx->ext->d_gold) {
-    gold_tables* t = new gold_tables;
+    std::unique_ptr<gold_tables> t(new gold_tables);
     gold_tables_init(*t);
-    hipError_t e = hipMalloc(&ctx->ext->d_gold, sizeof(gold_tables));
-    if (e == hipSuccess)
-      e = hipMemcpy(ctx->ext->d_gold, t, sizeof(gold_tables), hipMemcpyHostToDevice);
-    delete t;
-    if (e != hipSuccess) {
-      miphy_set_error("gold tables: %s", hipGetErrorString(e));
-      ctx->ext->d_gold = nullptr;
-      return MIPHY_EHIP;
-    }
-    ctx->ext->to_free.push_back(ctx->ext->d_gold);
+    if (int rc = miphy_keep_device_copy(ctx, t.get(), sizeof(gold_tables), &ctx->ext->d_gold))
+      return rc;
   }
   if (out)
     *out = (const gold_tables*)ctx->ext->d_gold;

@@ -57,6 +57,19 @@ struct miphy_ctx_ext {
   void*                                                         d_pi_il_max = nullptr; // polar interleaver pattern (polar.hip)
 };
 
+// A device copy of `bytes` of host memory that lives as long as the context (freed by miphy_destroy): what the context's caches hold.
+// When the allocation or the copy fails nothing is kept and *out is left as it was.
+int miphy_keep_device_copy(miphy_ctx* ctx, const void* src, size_t bytes, void** out);
+template <class T>
+int miphy_keep_device_copy(miphy_ctx* ctx, const T* src, size_t count, T** out)
+{
+  void*     d  = nullptr;
+  const int rc = miphy_keep_device_copy(ctx, static_cast<const void*>(src), count * sizeof(T), &d);
+  if (!rc)
+    *out = static_cast<T*>(d);
+  return rc;
+}
+
 // Returns the device twiddle table for size N (creates and caches it).
 int miphy_get_twiddles(miphy_ctx* ctx, uint32_t N, const float** out);
 

@@ -276,3 +276,19 @@ bool miphy_four_step_factors(uint32_t N, uint32_t& N1, uint32_t& N2);
 int miphy_side_streams(miphy_ctx* ctx);
 // The next work-queue counter of the context (zero: every launch leaves its counter cleared).
 int miphy_next_queue_counter(miphy_ctx* ctx, uint32_t** out);
+
+// ---- device buffers laid out with device_image.h ----
+#include "device_image.h"
+#include <memory>
+// Owner of one hipMalloc block (move only): the block is freed with its owner.
+struct miphy_hip_free {
+  void operator()(void* p) const { (void)hipFree(p); }
+};
+using miphy_device_block = std::unique_ptr<void, miphy_hip_free>;
+// A block of img.total_bytes() with the staged part copied into it (the call waits for the copy): what a prepared plan keeps.
+// MIPHY_EHIP and a message that begins with `who` when the allocation or the copy fails; nothing is left allocated then.
+int miphy_image_to_block(const char* who, const device_image& img, miphy_device_block& out);
+// Per call: the image in the context's workspace `slot`, its staged part uploaded on `s` (miphy_upload).
+int miphy_image_to_workspace(miphy_ctx* ctx, miphy_workspace slot, const device_image& img, hipStream_t s, void** base);
+// Per call, an image of staged arrays only: in the staging ring (miphy_stage_descs).
+int miphy_image_to_ring(miphy_ctx* ctx, const device_image& img, hipStream_t s, const void** base);

@@ -337,10 +337,9 @@ int get_plan(miphy_ctx* ctx, const miphy_ofdm_config* c, int is_tx, ofdm_plan_de
     }
   }
   ofdm_plan_dev* d = nullptr;
-  MIPHY_HIP_CHECK(hipMalloc((void**)&d, sizeof(h)));
-  MIPHY_HIP_CHECK(hipMemcpy(d, &h, sizeof(h), hipMemcpyHostToDevice));
+  if (int rc = miphy_keep_device_copy(ctx, &h, 1, &d))
+    return rc;
   ctx->ext->plans[key] = d;
-  ctx->ext->to_free.push_back(d);
   *out = d;
   return MIPHY_OK;
 }
@@ -359,10 +358,9 @@ int get_ramp(miphy_ctx* ctx, uint32_t N, uint32_t offset, const float** out)
   for (uint32_t i = 0; i < N; ++i)
     r[i] = std::exp(omega * static_cast<float>(i));
   float* d = nullptr;
-  MIPHY_HIP_CHECK(hipMalloc((void**)&d, sizeof(float) * 2 * N));
-  MIPHY_HIP_CHECK(hipMemcpy(d, r.data(), sizeof(float) * 2 * N, hipMemcpyHostToDevice));
+  if (int rc = miphy_keep_device_copy(ctx, reinterpret_cast<const float*>(r.data()), 2 * (size_t)N, &d))
+    return rc;
   ctx->ext->ramps[key] = d;
-  ctx->ext->to_free.push_back(d);
   *out = d;
   return MIPHY_OK;
 }
@@ -434,10 +432,9 @@ int miphy_get_twiddles(miphy_ctx* ctx, uint32_t N, const float** out)
     w[2 * j + 1]   = (float)std::sin(a);
   }
   float* d = nullptr;
-  MIPHY_HIP_CHECK(hipMalloc((void**)&d, sizeof(float) * 2 * N));
-  MIPHY_HIP_CHECK(hipMemcpy(d, w.data(), sizeof(float) * 2 * N, hipMemcpyHostToDevice));
+  if (int rc = miphy_keep_device_copy(ctx, w.data(), w.size(), &d))
+    return rc;
   ctx->ext->twiddles[N] = d;
-  ctx->ext->to_free.push_back(d);
   *out = d;
   return MIPHY_OK;
 }

@@ -167,15 +167,15 @@ extern "C" int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsc
 // chain, nothing staged or allocated, no host synchronisation -- for allocations that repeat slot after slot (and for batches whose descriptors exceed the staging ring,
 // where the per-call form has to wait for its upload).
 struct miphy_pdsch_process_plan {
-  miphy_ctx*                   ctx;
-  uint32_t                     n;
-  miphy_pdsch_encode_prepared* enc;
-  const gold_tables*           gt;
-  void*                        d_buf; // [modulator jobs | DM-RS jobs | codewords | the modulator's sequences and prefixes]
-  const miphy_pdsch_mod_job*   d_mj;
-  const miphy_dmrs_pdsch_job*  d_dj;
-  uint8_t*                     d_cw;
-  void*                        d_seq;
+  miphy_ctx*                      ctx = nullptr;
+  uint32_t                        n   = 0;
+  miphy_pdsch_encode_prepared*    enc = nullptr;
+  const gold_tables*              gt  = nullptr;
+  miphy_device_block              buf; // [modulator jobs | DM-RS jobs | codewords | the modulator's sequences and prefixes]
+  image_slot<miphy_pdsch_mod_job>  mj;
+  image_slot<miphy_dmrs_pdsch_job> dj;
+  image_slot<uint8_t>              cw, seq;
+  ~miphy_pdsch_process_plan() { miphy_pdsch_encode_prepared_destroy(enc); }
 };
 
 extern "C" int miphy_pdsch_process_plan_create(miphy_ctx* ctx, const miphy_pdsch_pdu* pdus, uint32_t n, miphy_pdsch_process_plan** out)
@@ -189,32 +189,18 @@ extern "C" int miphy_pdsch_process_plan_create(miphy_ctx* ctx, const miphy_pdsch
   int                               rc = derive_one_layer_jobs(pdus, n, tb, mj, dj, cw_bytes);
   if (rc)
     return rc;
-  auto* p = new miphy_pdsch_process_plan();
-  p->ctx = ctx, p->n = n, p->enc = nullptr, p->d_buf = nullptr;
-  if ((rc = miphy_get_gold_tables(ctx, &p->gt)) || (rc = miphy_pdsch_encode_prepare(ctx, tb.data(), n, &p->enc))) {
-    delete p;
+  std::unique_ptr<miphy_pdsch_process_plan> p(new miphy_pdsch_process_plan());
+  p->ctx = ctx, p->n = n;
+  if ((rc = miphy_get_gold_tables(ctx, &p->gt)) || (rc = miphy_pdsch_encode_prepare(ctx, tb.data(), n, &p->enc)))
     return rc;
-  }
-  const size_t b0 = ((size_t)n * sizeof(miphy_pdsch_mod_job) + 15) & ~(size_t)15, b1 = ((size_t)n * sizeof(miphy_dmrs_pdsch_job) + 15) & ~(size_t)15;
-  const size_t b2 = (cw_bytes + 64 + 255) & ~(size_t)255;
-  hipError_t   e  = hipMalloc(&p->d_buf, b0 + b1 + b2 + miphy_pdsch_modulate_scratch_bytes(n));
-  if (e == hipSuccess)
-    e = hipMemcpy(p->d_buf, mj.data(), (size_t)n * sizeof(miphy_pdsch_mod_job), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy((uint8_t*)p->d_buf + b0, dj.data(), (size_t)n * sizeof(miphy_dmrs_pdsch_job), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    miphy_set_error("miphy_pdsch_process_plan_create: %s", hipGetErrorString(e));
-    if (p->d_buf)
-      (void)hipFree(p->d_buf);
-    miphy_pdsch_encode_prepared_destroy(p->enc);
-    delete p;
-    return MIPHY_EHIP;
-  }
-  p->d_mj = reinterpret_cast<const miphy_pdsch_mod_job*>(p->d_buf);
-  p->d_dj = reinterpret_cast<const miphy_dmrs_pdsch_job*>((uint8_t*)p->d_buf + b0);
-  p->d_cw  = (uint8_t*)p->d_buf + b0 + b1;
-  p->d_seq = (uint8_t*)p->d_buf + b0 + b1 + b2;
-  *out     = p;
+  device_image img;
+  p->mj  = img.put(mj);
+  p->dj  = img.put(dj);
+  p->cw  = img.reserve<uint8_t>(cw_bytes + 64);
+  p->seq = img.reserve<uint8_t>(miphy_pdsch_modulate_scratch_bytes(n), 256);
+  if ((rc = miphy_image_to_block("miphy_pdsch_process_plan_create", img, p->buf)))
+    return rc;
+  *out = p.release();
   return MIPHY_OK;
 }
 
@@ -223,19 +209,16 @@ extern "C" int miphy_pdsch_process_plan_run(miphy_pdsch_process_plan* p, const u
   MIPHY_REQUIRE(p && tb_in && grid, "miphy_pdsch_process_plan_run: null argument");
   hipStream_t s = (hipStream_t)stream;
   int         rc;
-  if ((rc = miphy_pdsch_encode_prepared_run(p->enc, tb_in, p->d_cw, s)))
+  void*       buf = p->buf.get();
+  uint8_t*    cw  = p->cw.at(buf);
+  if ((rc = miphy_pdsch_encode_prepared_run(p->enc, tb_in, cw, s)))
     return rc;
-  if ((rc = miphy_pdsch_modulate_launch(p->d_mj, p->n, p->gt, p->d_cw, grid, p->d_seq, s)))
+  if ((rc = miphy_pdsch_modulate_launch(p->mj.at(buf), p->n, p->gt, cw, grid, p->seq.at(buf), s)))
     return rc;
-  return miphy_dmrs_pdsch_map_launch(p->d_dj, p->n, p->gt, grid, s);
+  return miphy_dmrs_pdsch_map_launch(p->dj.at(buf), p->n, p->gt, grid, s);
 }
 
 extern "C" void miphy_pdsch_process_plan_destroy(miphy_pdsch_process_plan* p)
 {
-  if (!p)
-    return;
-  if (p->d_buf)
-    (void)hipFree(p->d_buf);
-  miphy_pdsch_encode_prepared_destroy(p->enc);
   delete p;
 }

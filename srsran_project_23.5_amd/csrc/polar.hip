@@ -18,12 +18,7 @@ namespace {
 template <typename T>
 int upload(miphy_ctx* ctx, const std::vector<T>& v, T** d)
 {
-  const size_t bytes = std::max<size_t>(sizeof(T), v.size() * sizeof(T));
-  MIPHY_HIP_CHECK(hipMalloc((void**)d, bytes));
-  if (!v.empty())
-    MIPHY_HIP_CHECK(hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  ctx->ext->to_free.push_back(*d);
-  return MIPHY_OK;
+  return miphy_keep_device_copy(ctx, v.data(), v.size(), d);
 }
 
 int get_plan(miphy_ctx* ctx, const miphy_polar_code* c, const polar_plan** out)
@@ -407,11 +402,9 @@ extern "C" int miphy_polar_block_batch(miphy_ctx* ctx, const miphy_polar_code* c
   // the interleaver pattern (TS 38.212 Table 5.3.1.1-1) lives with the device tables of the context
   static_assert(sizeof(NR_POLAR_PI_IL_MAX[0]) == 1, "pattern entries are bytes");
   auto& ext = *ctx->ext;
-  if (!ext.d_pi_il_max) {
-    MIPHY_HIP_CHECK(hipMalloc(&ext.d_pi_il_max, NR_POLAR_K_MAX_IL));
-    MIPHY_HIP_CHECK(hipMemcpy(ext.d_pi_il_max, NR_POLAR_PI_IL_MAX, NR_POLAR_K_MAX_IL, hipMemcpyHostToDevice));
-    ext.to_free.push_back(ext.d_pi_il_max);
-  }
+  if (!ext.d_pi_il_max)
+    if (int rc = miphy_keep_device_copy(ctx, NR_POLAR_PI_IL_MAX, NR_POLAR_K_MAX_IL, &ext.d_pi_il_max))
+      return rc;
   hipLaunchKernelGGL(polar_block_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, *p, (int)op, (int)param, (const uint8_t*)in, (uint8_t*)out,
                      (const uint8_t*)ext.d_pi_il_max);
   MIPHY_HIP_CHECK(hipGetLastError());

@@ -144,22 +144,23 @@ extern "C" int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pd
       t.llr_offset = (t.llr_offset & ~((uint64_t)1 << 63)) + llr_bytes;
   for (auto& x : xj)
     x.sch_offset += llr_bytes;
-  // [channel estimates cf_t | codeword LLRs | UL-SCH LLRs of the PDUs with UCI | EVM sums | placeholders | data REs] in a workspace of the
-  // context; the estimator scalars go straight to the caller's array.
-  const size_t evm_bytes = evm_out ? (size_t)n * 14 * 4 : 0, ph_bytes = (ph.size() * 2 + 15) & ~(size_t)15, nre_bytes = evm_out ? (size_t)n * 4 : 0;
-  void*        work      = nullptr;
-  int          rc        = miphy_get_workspace(ctx, MIPHY_WS_PUSCH_PROC, ce_elems * 8 + llr_bytes + sch_bytes + evm_bytes + ph_bytes + nre_bytes + 256, &work);
+  // [placeholders | data REs || channel estimates cf_t | codeword LLRs, UL-SCH LLRs of the PDUs with UCI | EVM sums] in a workspace of the
+  // context, the two arrays in front uploaded as one; the estimator scalars go straight to the caller's array.
+  device_image img;
+  const auto   s_ph  = img.put(ph);
+  const auto   s_nre = img.put(nof_re.data(), evm_out ? n : 0); // (read by the EVM kernel only)
+  const auto   s_ce  = img.reserve<float>(ce_elems * 2, 256);
+  const auto   s_llr = img.reserve<int8_t>(llr_bytes + sch_bytes, 256);
+  const auto   s_evm = img.reserve<float>(evm_out ? (size_t)n * 14 : 0);
+  void*        work  = nullptr;
+  int          rc    = miphy_image_to_workspace(ctx, MIPHY_WS_PUSCH_PROC, img, s, &work);
   if (rc)
     return rc;
-  float*    d_ce  = static_cast<float*>(work);
-  int8_t*   d_llr = reinterpret_cast<int8_t*>(work) + ce_elems * 8;
-  float*    d_evm = reinterpret_cast<float*>(d_llr + llr_bytes + sch_bytes);
-  uint16_t* d_ph  = reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(d_evm) + evm_bytes);
-  uint32_t* d_nre = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(d_ph) + ph_bytes);
-  if (!ph.empty() && (rc = miphy_upload(ctx, d_ph, ph.data(), ph.size() * 2, s)))
-    return rc;
-  if (evm_out && (rc = miphy_upload(ctx, d_nre, nof_re.data(), (size_t)n * 4, s)))
-    return rc;
+  float*    d_ce  = s_ce.at(work);
+  int8_t*   d_llr = s_llr.at(work);
+  float*    d_evm = s_evm.at(work);
+  uint16_t* d_ph  = s_ph.at(work);
+  uint32_t* d_nre = s_nre.at(work);
   if ((rc = miphy_dmrs_pusch_estimate_batch(ctx, cj.data(), 0, n, grid, d_ce, scalars_out, s)))
     return rc;
   if ((rc = miphy_pusch_demodulate_batch_ex(ctx, dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, ph.empty() ? nullptr : d_ph, evm_out ? d_evm : nullptr, s)))

@@ -8,6 +8,7 @@
 #include "crc_device.h"
 #include "miphy_ext.h"
 #include "tables/nr_ldpc_tables.h"
+#include <atomic>
 #include <cstring>
 #include <vector>
 
@@ -261,17 +262,6 @@ __global__ void __launch_bounds__(1024) pusch_tb_assemble_kernel(const tb_asm_de
       harq_crc_ok[d.harq_cb_index + c] = 0;
 }
 
-template <typename T>
-T* stage_vec(uint8_t*& h, uint8_t*& d, const std::vector<T>& v, size_t& off)
-{
-  off              = (off + 15) & ~(size_t)15;
-  T* dev           = reinterpret_cast<T*>(d + off);
-  if (!v.empty())
-    std::memcpy(h + off, v.data(), v.size() * sizeof(T));
-  off += v.size() * sizeof(T);
-  return dev;
-}
-
 } // namespace
 
 extern "C" int miphy_sch_segmentation_info(uint32_t tb_bytes, uint32_t bg, miphy_sch_segmentation* out)
@@ -292,52 +282,48 @@ extern "C" int miphy_sch_segmentation_info(uint32_t tb_bytes, uint32_t bg, miphy
 
 namespace {
 
-// Host-side product of the segmentation of a batch of transport blocks: everything the three launches of a PUSCH decode need.
+// Host-side product of the segmentation of a batch of transport blocks, in two parts. What every run of its launches needs:
 struct pusch_decode_build {
+  uint32_t ncb = 0, max_nodes = 0, max_E = 0;
+  // Launches: chunks of at most 65535 codeblocks (whole transport blocks), each sorted into the decoder's launch classes
+  // (miphy_ldpc_build_classes: by lifting size, base graph, reachable layers, dematch-while-loading or not).
+  struct chunk {
+    uint32_t            t0, t1, c0, c1;
+    miphy_ldpc_classes  cls; // (classes only: order and bundles are in the descriptor arrays)
+    uint32_t            order_off, bundle_off, rdm_nf_off; // positions in the concatenated `order` / `bundles` / `rdm_nf` arrays
+    miphy_ldpc_launches launches[2]; // decoder launch tables (pusch_decode_launches): [0] after the dematcher's own launch, [1] dematching the fused classes
+  };
+  std::vector<chunk> chunks;
+  bool               all_fused = true;  // every class of every chunk dematches in the decoder
+  bool               any_fused = false; // some class does (launches[1] exists)
+  bool               scalar    = false; // the one-row-per-lane kernel is forced: nothing is dematched in the decoder
+  bool               side_streams = false; // some launch table forks to the context's side streams
+  size_t             gmsg_bytes   = 0;     // decoder message scratch: the largest any table needs (chunks run one after another)
+  uint32_t           nof_reset    = 0;     // new transmissions: the length of reset_slots
+};
+// ... and the descriptor arrays: they go to the device (pusch_decode_image) and die with the call that built them.
+struct pusch_decode_descs {
   std::vector<miphy_ldpc_rdm_desc> rdm;
+  std::vector<miphy_ldpc_rdm_desc> rdm_nf; // dematcher descriptors of the codeblocks of classes that are not fused, chunk after chunk
+  std::vector<uint32_t>            order, bundles; // all chunks, indices relative to the chunk's first codeblock
   std::vector<miphy_ldpc_dec_desc> dec;
   std::vector<uint32_t>            slots, reset_slots;
   std::vector<tb_asm_desc>         asmd;
   std::vector<uint32_t>            cb_tb; // transport block of each codeblock
   std::vector<uint32_t>            cbw;   // per codeblock: x^sh mod CRC24A, the weight of its checksum part in the transport block's (tb assembly)
-  uint32_t                         max_Z = 2, max_nodes = 0, max_E = 0;
-  int                              bg_mask   = 0;     // bit 0 / 1: base graph 1 / 2 occurs (the decoder sizes its LDS per base graph)
-  std::vector<uint8_t>             fusable;           // per codeblock: it can be rate-dematched by the decoder while it loads
-  // Launches: chunks of at most 65535 codeblocks (whole transport blocks), each sorted into the decoder's launch classes
-  // (miphy_ldpc_build_classes: by lifting size, base graph, reachable layers, dematch-while-loading or not).
-  struct chunk {
-    uint32_t            t0, t1, c0, c1;
-    miphy_ldpc_classes  cls; // (classes only: order and bundles are in the arrays below)
-    uint32_t            order_off, bundle_off, rdm_nf_off; // positions in the concatenated `order` / `bundles` / `rdm_nf` arrays
-    miphy_ldpc_launches launches[2]; // decoder launch tables (pusch_decode_launches): [0] after the dematcher's own launch, [1] dematching the fused classes
-  };
-  std::vector<chunk>               chunks;
-  std::vector<uint32_t>            order, bundles;    // all chunks, indices relative to the chunk's first codeblock
-  std::vector<miphy_ldpc_rdm_desc> rdm_nf;            // dematcher descriptors of the codeblocks of classes that are not fused, chunk after chunk
-  bool                             all_fused = true;  // every class of every chunk dematches in the decoder
-  bool                             any_fused = false; // some class does (launches[1] exists)
-  bool                             scalar    = false; // the one-row-per-lane kernel is forced: nothing is dematched in the decoder
-  bool                             side_streams = false; // some launch table forks to the context's side streams
-  size_t                           gmsg_bytes   = 0;     // decoder message scratch: the largest any table needs (chunks run one after another)
-  uint32_t                         nof_reset    = 0;     // new transmissions: reset_slots.size() (a plan releases the vector)
+  std::vector<uint8_t>             fusable; // host only, per codeblock: it can be rate-dematched by the decoder while it loads
 };
 
-// Device-side view of a staged build (pointers into one buffer).
+// Where the arrays of a build sit in its device buffer.
 struct pusch_decode_dev {
-  const miphy_ldpc_rdm_desc* rdm;
-  const miphy_ldpc_rdm_desc* rdm_nf;
-  const uint32_t*            order;
-  const uint32_t*            bundles;
-  const miphy_ldpc_dec_desc* dec;
-  const uint32_t*            slots;
-  const uint32_t*            reset;
-  const tb_asm_desc*         asmd;
-  const uint32_t*            cb_tb;
-  const uint32_t*            cbw;
-  int32_t*                   iters;
-  uint32_t*                  part; // per codeblock: its part of the TB checksum
-  size_t                     staged; // bytes to copy host -> device
-  size_t                     total;  // bytes of the whole buffer
+  image_slot<miphy_ldpc_rdm_desc> rdm, rdm_nf;
+  image_slot<uint32_t>            order, bundles;
+  image_slot<miphy_ldpc_dec_desc> dec;
+  image_slot<uint32_t>            slots, reset;
+  image_slot<tb_asm_desc>         asmd;
+  image_slot<uint32_t>            cb_tb, cbw;
+  image_slot<int32_t>             iters;
+  image_slot<uint32_t>            part; // per codeblock: its part of the TB checksum
 };
 
 // x^e mod the CRC24A polynomial (host, square and multiply).
@@ -362,9 +348,9 @@ static uint32_t crc24a_x_pow(uint64_t e)
   return r;
 }
 
-int build_pusch_decode(const miphy_pusch_tb_desc* tbs, uint32_t n, pusch_decode_build& b)
+int build_pusch_decode(const miphy_pusch_tb_desc* tbs, uint32_t n, pusch_decode_build& b, pusch_decode_descs& v)
 {
-  b.asmd.resize(n);
+  v.asmd.resize(n);
   for (uint32_t t = 0; t < n; ++t) {
     const miphy_pusch_tb_desc& d = tbs[t];
     seg_t                      sg;
@@ -379,8 +365,8 @@ int build_pusch_decode(const miphy_pusch_tb_desc* tbs, uint32_t n, pusch_decode_
     MIPHY_REQUIRE((sg.cb_info_bits % 8) == 0 || sg.nof_cbs == 1,
                   "pusch_decode: TB %u: TBS %u is not a TS 38.214 transport block size (codeblock payloads are not byte aligned)", t, sg.tbs);
     const uint32_t bgK = (d.bg == 1) ? 22 : 10;
-    tb_asm_desc&   a   = b.asmd[t];
-    a.first_desc       = (uint32_t)b.dec.size();
+    tb_asm_desc&   a   = v.asmd[t];
+    a.first_desc       = (uint32_t)v.dec.size();
     a.nof_cbs          = sg.nof_cbs;
     a.harq_cb_index    = d.harq_cb_index;
     a.nof_data_bits    = sg.K - ((sg.nof_cbs == 1) ? sg.nof_tb_crc_bits : 24) - sg.nof_filler_bits; // get_cblk_bit_breakdown
@@ -396,7 +382,7 @@ int build_pusch_decode(const miphy_pusch_tb_desc* tbs, uint32_t n, pusch_decode_
         const uint32_t nbits = std::min(a.nof_data_bits, a.tb_and_crc_bits - std::min(bit0, a.tb_and_crc_bits));
         const uint32_t after = a.tb_and_crc_bits - (bit0 + nbits);
         const uint32_t r     = mask_crc ? 32 * ((nbits + 31) >> 5) - nbits : 0; // zero bits the mask table assumes behind the message
-        b.cbw.push_back(crc24a_x_pow((uint64_t)after + 24 - r));
+        v.cbw.push_back(crc24a_x_pow((uint64_t)after + 24 - r));
       }
       const uint32_t      E    = rm_length(sg, c, d.mod, d.nof_layers, d.nof_ch_symbols);
       const uint32_t      slot = d.harq_cb_index + c;
@@ -406,7 +392,7 @@ int build_pusch_decode(const miphy_pusch_tb_desc* tbs, uint32_t n, pusch_decode_
       r.in_offset = d.llr_offset + cw_off, r.out_offset = (uint64_t)slot * HARQ_CB_STRIDE;
       MIPHY_REQUIRE(E > 0, "pusch_decode: TB %u: empty codeblock", t);
       b.max_E = E > b.max_E ? E : b.max_E;
-      b.rdm.push_back(r);
+      v.rdm.push_back(r);
       miphy_ldpc_dec_desc q = {};
       q.bg = d.bg, q.crc_poly = (uint8_t)sg.crc_poly, q.Z = (uint16_t)sg.Z, q.max_iter = d.nof_ldpc_iterations;
       q.nof_filler_bits = (uint16_t)sg.nof_filler_bits;
@@ -430,46 +416,45 @@ int build_pusch_decode(const miphy_pusch_tb_desc* tbs, uint32_t n, pusch_decode_
       }
       // Dematching while the decoder loads: first transmission at redundancy version 0 into the full circular buffer, the E bits
       // neither wrap around it nor stop inside the systematic part, soft-buffer slots 16-byte aligned (HARQ_CB_STRIDE is).
-      b.fusable.push_back(d.new_data && d.rv == 0 && !(d.Nref > 0 && d.Nref < sg.N) && E + sg.nof_filler_bits <= sg.N &&
+      v.fusable.push_back(d.new_data && d.rv == 0 && !(d.Nref > 0 && d.Nref < sg.N) && E + sg.nof_filler_bits <= sg.N &&
                           E >= (bgK - 2) * sg.Z - sg.nof_filler_bits && (sg.Z % 16) == 0);
-      b.bg_mask |= 1 << (d.bg - 1);
       q.flags           = d.use_early_stop ? 0u : 1u;
       q.llr_offset = (uint64_t)slot * HARQ_CB_STRIDE, q.out_offset = (uint64_t)slot * HARQ_MSG_STRIDE;
-      b.dec.push_back(q);
-      b.cb_tb.push_back(t);
-      b.slots.push_back(slot);
+      v.dec.push_back(q);
+      v.cb_tb.push_back(t);
+      v.slots.push_back(slot);
       if (d.new_data)
-        b.reset_slots.push_back(slot);
+        v.reset_slots.push_back(slot);
       cw_off += E;
     }
     MIPHY_REQUIRE(cw_off == d.nof_ch_symbols * d.mod, "pusch_decode: TB %u: codeblock lengths (%u) do not add up to the codeword (%u)", t, cw_off,
                   d.nof_ch_symbols * d.mod);
-    b.max_Z     = sg.Z > b.max_Z ? sg.Z : b.max_Z;
     b.max_nodes = tb_nodes > b.max_nodes ? tb_nodes : b.max_nodes;
   }
   // chunks of whole transport blocks, each with its launch classes
   for (uint32_t t0 = 0; t0 < n;) {
     pusch_decode_build::chunk ch;
-    ch.t0 = t0, ch.t1 = t0, ch.c0 = b.asmd[t0].first_desc, ch.c1 = ch.c0;
-    while (ch.t1 < n && ch.c1 + b.asmd[ch.t1].nof_cbs - ch.c0 <= 65535) {
-      ch.c1 += b.asmd[ch.t1].nof_cbs;
+    ch.t0 = t0, ch.t1 = t0, ch.c0 = v.asmd[t0].first_desc, ch.c1 = ch.c0;
+    while (ch.t1 < n && ch.c1 + v.asmd[ch.t1].nof_cbs - ch.c0 <= 65535) {
+      ch.c1 += v.asmd[ch.t1].nof_cbs;
       ++ch.t1;
     }
     MIPHY_REQUIRE(ch.t1 > ch.t0, "pusch_decode: TB %u has more than 65535 codeblocks", t0);
-    miphy_ldpc_build_classes(b.dec.data() + ch.c0, ch.c1 - ch.c0, b.fusable.data() + ch.c0, ch.cls);
-    ch.order_off = (uint32_t)b.order.size(), ch.bundle_off = (uint32_t)b.bundles.size(), ch.rdm_nf_off = (uint32_t)b.rdm_nf.size();
-    b.order.insert(b.order.end(), ch.cls.order.begin(), ch.cls.order.end());
-    b.bundles.insert(b.bundles.end(), ch.cls.bundles.begin(), ch.cls.bundles.end());
+    miphy_ldpc_build_classes(v.dec.data() + ch.c0, ch.c1 - ch.c0, v.fusable.data() + ch.c0, ch.cls);
+    ch.order_off = (uint32_t)v.order.size(), ch.bundle_off = (uint32_t)v.bundles.size(), ch.rdm_nf_off = (uint32_t)v.rdm_nf.size();
+    v.order.insert(v.order.end(), ch.cls.order.begin(), ch.cls.order.end());
+    v.bundles.insert(v.bundles.end(), ch.cls.bundles.begin(), ch.cls.bundles.end());
     for (uint32_t k = 0; k < ch.cls.nof_unfused; ++k)
-      b.rdm_nf.push_back(b.rdm[ch.c0 + ch.cls.order[k]]);
+      v.rdm_nf.push_back(v.rdm[ch.c0 + ch.cls.order[k]]);
     b.all_fused &= ch.cls.nof_unfused == 0;
     b.any_fused |= ch.cls.nof_unfused < ch.c1 - ch.c0;
-    std::vector<uint32_t>().swap(ch.cls.order); // kept in b.order
+    std::vector<uint32_t>().swap(ch.cls.order); // kept in v.order
     std::vector<uint32_t>().swap(ch.cls.bundles);
     t0 = ch.t1;
     b.chunks.push_back(std::move(ch));
   }
-  b.nof_reset = (uint32_t)b.reset_slots.size();
+  b.ncb       = (uint32_t)v.dec.size();
+  b.nof_reset = (uint32_t)v.reset_slots.size();
   return MIPHY_OK;
 }
 
@@ -490,34 +475,23 @@ int pusch_decode_launches(miphy_ctx* ctx, pusch_decode_build& b)
   return MIPHY_OK;
 }
 
-size_t pusch_decode_bytes(const pusch_decode_build& b)
-{
-  return 64 + (b.rdm.size() + b.rdm_nf.size()) * sizeof(b.rdm[0]) + b.dec.size() * sizeof(b.dec[0]) + (b.slots.size() + b.reset_slots.size()) * 4 +
-         b.asmd.size() * sizeof(b.asmd[0]) + (b.cb_tb.size() + b.cbw.size() + b.order.size() + b.bundles.size()) * 4 + b.dec.size() * 8 + 16 * 12;
-}
-
-// Lays the build out in a host image `h` of the device buffer `dv` (same offsets) and returns the device pointers.
-pusch_decode_dev layout_pusch_decode(const pusch_decode_build& b, uint8_t* h, uint8_t* dv)
+// Appends the arrays of a build to the image of its device buffer: the descriptors as the staged part, then the iteration counts and
+// checksum parts the launches write. (A plan appends its decoder message scratch behind them.)
+pusch_decode_dev pusch_decode_image(const pusch_decode_descs& d, device_image& img)
 {
   pusch_decode_dev v;
-  size_t           off = 0;
-  v.rdm     = stage_vec(h, dv, b.rdm, off);
-  v.rdm_nf  = stage_vec(h, dv, b.rdm_nf, off);
-  v.order   = stage_vec(h, dv, b.order, off);
-  v.bundles = stage_vec(h, dv, b.bundles, off);
-  v.dec     = stage_vec(h, dv, b.dec, off);
-  v.slots   = stage_vec(h, dv, b.slots, off);
-  v.reset   = stage_vec(h, dv, b.reset_slots, off);
-  v.asmd    = stage_vec(h, dv, b.asmd, off);
-  v.cb_tb   = stage_vec(h, dv, b.cb_tb, off);
-  v.cbw     = stage_vec(h, dv, b.cbw, off);
-  v.staged  = off;
-  off       = (off + 15) & ~(size_t)15;
-  v.iters   = reinterpret_cast<int32_t*>(dv + off);
-  off += b.dec.size() * 4;
-  off   = (off + 15) & ~(size_t)15;
-  v.part  = reinterpret_cast<uint32_t*>(dv + off);
-  v.total = off + b.dec.size() * 4;
+  v.rdm     = img.put(d.rdm);
+  v.rdm_nf  = img.put(d.rdm_nf);
+  v.order   = img.put(d.order);
+  v.bundles = img.put(d.bundles);
+  v.dec     = img.put(d.dec);
+  v.slots   = img.put(d.slots);
+  v.reset   = img.put(d.reset_slots);
+  v.asmd    = img.put(d.asmd);
+  v.cb_tb   = img.put(d.cb_tb);
+  v.cbw     = img.put(d.cbw);
+  v.iters   = img.reserve<int32_t>(d.dec.size());
+  v.part    = img.reserve<uint32_t>(d.dec.size());
   return v;
 }
 
@@ -541,32 +515,35 @@ int harq_flags_reset(const uint32_t* d_slots, uint32_t n, uint8_t* harq_crc_ok, 
 // The launches of one PUSCH decode on staged descriptors: CRC-flag reset of new transmissions, rate dematching into the HARQ
 // soft buffers, LDPC decoding (codeblocks already decoded are skipped), transport-block assembly + TB CRC + result records.
 // Launches of at most 65535 codeblocks each; transport blocks are never split across launches.
-int launch_pusch_decode(miphy_ctx* ctx, const pusch_decode_build& b, const pusch_decode_dev& v, uint32_t n, const int8_t* llrs, int8_t* harq_softbits,
+int launch_pusch_decode(miphy_ctx* ctx, const pusch_decode_build& b, const pusch_decode_dev& v, void* buf, uint32_t n, const int8_t* llrs, int8_t* harq_softbits,
                         uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results, void* gmsg, hipStream_t s,
                         hipEvent_t* ev = nullptr /* optional: 4 events around the dematch launches / the decoder launches / the assembly */)
 {
   int rc;
+  const miphy_ldpc_rdm_desc *rdm = v.rdm.at(buf), *rdm_nf = v.rdm_nf.at(buf);
+  const miphy_ldpc_dec_desc* dec   = v.dec.at(buf);
+  int32_t*                   iters = v.iters.at(buf);
   miphy_ldpc_rdm_limits rlim = {b.max_E};
   // Dematching inside the decoder needs 16-byte aligned soft buffers (its write-back is vectorised; HARQ_CB_STRIDE keeps the slots so)
   const bool allow_fuse = ((uintptr_t)harq_softbits & 15) == 0 && !b.scalar;
   if (ev)
     MIPHY_HIP_CHECK(hipEventRecord(ev[0], s));
   // the CRC flags of the new transmissions of the call (a decoder that dematches itself writes the flags of its codeblocks either way)
-  if (!(b.all_fused && allow_fuse) && (rc = harq_flags_reset(v.reset, b.nof_reset, harq_crc_ok, s)))
+  if (!(b.all_fused && allow_fuse) && (rc = harq_flags_reset(v.reset.at(buf), b.nof_reset, harq_crc_ok, s)))
     return rc;
   for (const pusch_decode_build::chunk& ch : b.chunks) { // rate dematching as launches of its own where the decoder does not do it
     if (!allow_fuse)
-      rc = miphy_ldpc_rate_dematch_batch(ctx, v.rdm + ch.c0, 1, ch.c1 - ch.c0, llrs, harq_softbits, &rlim, s);
+      rc = miphy_ldpc_rate_dematch_batch(ctx, rdm + ch.c0, 1, ch.c1 - ch.c0, llrs, harq_softbits, &rlim, s);
     else
-      rc = ch.cls.nof_unfused ? miphy_ldpc_rate_dematch_batch(ctx, v.rdm_nf + ch.rdm_nf_off, 1, ch.cls.nof_unfused, llrs, harq_softbits, &rlim, s) : MIPHY_OK;
+      rc = ch.cls.nof_unfused ? miphy_ldpc_rate_dematch_batch(ctx, rdm_nf + ch.rdm_nf_off, 1, ch.cls.nof_unfused, llrs, harq_softbits, &rlim, s) : MIPHY_OK;
     if (rc)
       return rc;
   }
   if (ev)
     MIPHY_HIP_CHECK(hipEventRecord(ev[1], s));
   for (const pusch_decode_build::chunk& ch : b.chunks) {
-    if ((rc = miphy_ldpc_run_launches(ctx, ch.launches[allow_fuse && b.any_fused], v.dec + ch.c0, v.order + ch.order_off, v.bundles + ch.bundle_off,
-                                      harq_softbits, harq_msgs, v.iters + ch.c0, v.slots + ch.c0, harq_crc_ok, v.rdm + ch.c0, llrs, gmsg, s)))
+    if ((rc = miphy_ldpc_run_launches(ctx, ch.launches[allow_fuse && b.any_fused], dec + ch.c0, v.order.at(buf) + ch.order_off, v.bundles.at(buf) + ch.bundle_off,
+                                      harq_softbits, harq_msgs, iters + ch.c0, v.slots.at(buf) + ch.c0, harq_crc_ok, rdm + ch.c0, llrs, gmsg, s)))
       return rc;
   }
   if (ev)
@@ -577,7 +554,7 @@ int launch_pusch_decode(miphy_ctx* ctx, const pusch_decode_build& b, const pusch
   // One workgroup per transport block, one wavefront per codeblock in turns: eight wavefronts when the batch fills the chip (measured
   // best at 1024 transport blocks), sixteen when it does not (a single slot: three turns of its 38 codeblocks instead of five).
   const unsigned tba_threads = n * 4u <= (unsigned)ctx->num_cus ? 1024u : (unsigned)TBA_THREADS;
-  hipLaunchKernelGGL(pusch_tb_assemble_kernel, dim3(n), dim3(tba_threads), 0, s, v.asmd, ctx->d_tables, v.iters, harq_msgs, harq_crc_ok, tb_out, results, v.cbw);
+  hipLaunchKernelGGL(pusch_tb_assemble_kernel, dim3(n), dim3(tba_threads), 0, s, v.asmd.at(buf), ctx->d_tables, iters, harq_msgs, harq_crc_ok, tb_out, results, v.cbw.at(buf));
   if (ev)
     MIPHY_HIP_CHECK(hipEventRecord(ev[3], s));
   MIPHY_HIP_CHECK(hipGetLastError());
@@ -602,16 +579,14 @@ extern "C" int miphy_pusch_decode_batch(miphy_ctx*                 ctx,
     return MIPHY_OK;
   hipStream_t        s = (hipStream_t)stream;
   pusch_decode_build b;
-  int                rc = build_pusch_decode(tbs, n, b);
+  pusch_decode_descs d;
+  int                rc = build_pusch_decode(tbs, n, b, d);
   if (rc)
     return rc;
-  const size_t         bytes = pusch_decode_bytes(b);
-  std::vector<uint8_t> host(bytes);
-  void*                wsv = nullptr;
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_GENERAL, bytes, &wsv)))
-    return rc;
-  const pusch_decode_dev v = layout_pusch_decode(b, host.data(), (uint8_t*)wsv);
-  if ((rc = miphy_upload(ctx, wsv, host.data(), v.staged, s))) // through the pinned ring: the stream is not waited for
+  device_image           img;
+  const pusch_decode_dev v   = pusch_decode_image(d, img);
+  void*                  buf = nullptr;
+  if ((rc = miphy_image_to_workspace(ctx, MIPHY_WS_GENERAL, img, s, &buf)))
     return rc;
   if ((rc = pusch_decode_launches(ctx, b)))
     return rc;
@@ -620,69 +595,43 @@ extern "C" int miphy_pusch_decode_batch(miphy_ctx*                 ctx,
     return rc;
   if (b.side_streams && (rc = miphy_side_streams(ctx)))
     return rc;
-  return launch_pusch_decode(ctx, b, v, n, llrs, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, gmsg, s);
+  return launch_pusch_decode(ctx, b, v, buf, n, llrs, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, gmsg, s);
 }
 
 // ---- prepared form: the segmentation and the descriptor upload happen once, every run is launches only (no host
 // synchronisation), for allocations that repeat slot after slot.
 struct miphy_pusch_decode_plan {
-  miphy_ctx*         ctx;
-  uint32_t           n;
-  pusch_decode_build b; // chunks, launch tables and sizes (the descriptor vectors are released after staging)
-  pusch_decode_dev   v;
-  void*              d_buf; // [staged descriptors | iterations, checksum parts | decoder message scratch]
-  void*              d_gmsg;
-  uint32_t           ncb;
+  miphy_ctx*              ctx = nullptr;
+  uint32_t                n   = 0;
+  pusch_decode_build      b; // chunks, launch tables and sizes
+  pusch_decode_dev        v;
+  miphy_device_block      buf; // [staged descriptors | iterations, checksum parts | decoder message scratch]
+  void*                   d_gmsg = nullptr;
   std::vector<hipEvent_t> events; // timing: 4 per run, ring of events.size() / 4 runs
-  uint32_t           timed_runs;
+  uint32_t                timed_runs = 0;
+  ~miphy_pusch_decode_plan()
+  {
+    for (hipEvent_t e : events)
+      (void)hipEventDestroy(e);
+  }
 };
 
 extern "C" int miphy_pusch_decode_plan_create(miphy_ctx* ctx, const miphy_pusch_tb_desc* tbs, uint32_t n, miphy_pusch_decode_plan** out)
 {
   MIPHY_REQUIRE(ctx && tbs && out && n > 0, "miphy_pusch_decode_plan_create: null argument or empty batch");
-  auto* p = new miphy_pusch_decode_plan();
-  p->ctx = ctx, p->n = n, p->d_buf = nullptr, p->d_gmsg = nullptr, p->timed_runs = 0;
-  int rc = build_pusch_decode(tbs, n, p->b);
-  p->ncb = (uint32_t)p->b.dec.size();
-  if (rc) {
-    delete p;
+  std::unique_ptr<miphy_pusch_decode_plan> p(new miphy_pusch_decode_plan());
+  p->ctx = ctx, p->n = n;
+  pusch_decode_descs d; // the runs need the chunks, their tables and the sizes only
+  int                rc;
+  if ((rc = build_pusch_decode(tbs, n, p->b, d)) || (rc = pusch_decode_launches(ctx, p->b)) || (p->b.side_streams && (rc = miphy_side_streams(ctx))))
     return rc;
-  }
-  if ((rc = pusch_decode_launches(ctx, p->b)) || (p->b.side_streams && (rc = miphy_side_streams(ctx)))) {
-    delete p;
+  device_image img;
+  p->v                           = pusch_decode_image(d, img);
+  const image_slot<uint8_t> gmsg = img.reserve<uint8_t>(p->b.gmsg_bytes, 256);
+  if ((rc = miphy_image_to_block("miphy_pusch_decode_plan_create", img, p->buf)))
     return rc;
-  }
-  const size_t         bytes = pusch_decode_bytes(p->b), gmsg_off = (bytes + 255) & ~(size_t)255;
-  std::vector<uint8_t> host(bytes);
-  hipError_t           e = hipMalloc(&p->d_buf, gmsg_off + p->b.gmsg_bytes);
-  if (e != hipSuccess) {
-    miphy_set_error("miphy_pusch_decode_plan_create: hipMalloc(%zu) -> %s", gmsg_off + p->b.gmsg_bytes, hipGetErrorString(e));
-    delete p;
-    return MIPHY_EHIP;
-  }
-  p->v = layout_pusch_decode(p->b, host.data(), (uint8_t*)p->d_buf);
-  e    = hipMemcpy(p->d_buf, host.data(), p->v.staged, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    miphy_set_error("miphy_pusch_decode_plan_create: hipMemcpy -> %s", hipGetErrorString(e));
-    (void)hipFree(p->d_buf);
-    delete p;
-    return MIPHY_EHIP;
-  }
-  p->d_gmsg = p->b.gmsg_bytes ? (uint8_t*)p->d_buf + gmsg_off : nullptr;
-  // the runs need the chunks, their tables and the sizes only
-  pusch_decode_build& b = p->b;
-  std::vector<miphy_ldpc_rdm_desc>().swap(b.rdm);
-  std::vector<miphy_ldpc_rdm_desc>().swap(b.rdm_nf);
-  std::vector<miphy_ldpc_dec_desc>().swap(b.dec);
-  std::vector<uint32_t>().swap(b.slots);
-  std::vector<uint32_t>().swap(b.reset_slots);
-  std::vector<tb_asm_desc>().swap(b.asmd);
-  std::vector<uint32_t>().swap(b.cb_tb);
-  std::vector<uint32_t>().swap(b.cbw);
-  std::vector<uint32_t>().swap(b.order);
-  std::vector<uint32_t>().swap(b.bundles);
-  std::vector<uint8_t>().swap(b.fusable);
-  *out = p;
+  p->d_gmsg = p->b.gmsg_bytes ? gmsg.at(p->buf.get()) : nullptr;
+  *out      = p.release();
   return MIPHY_OK;
 }
 
@@ -702,7 +651,7 @@ extern "C" int miphy_pusch_decode_plan_run(miphy_pusch_decode_plan* p,
     ev                 = &p->events[(size_t)(p->timed_runs % cap) * 4];
     ++p->timed_runs;
   }
-  return launch_pusch_decode(p->ctx, p->b, p->v, p->n, llrs, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, p->d_gmsg, (hipStream_t)stream, ev);
+  return launch_pusch_decode(p->ctx, p->b, p->v, p->buf.get(), p->n, llrs, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, p->d_gmsg, (hipStream_t)stream, ev);
 }
 
 extern "C" int miphy_pusch_decode_plan_enable_timing(miphy_pusch_decode_plan* p, uint32_t max_runs)
@@ -742,7 +691,7 @@ extern "C" int miphy_pusch_decode_plan_read_timing(miphy_pusch_decode_plan* p, f
 extern "C" int miphy_pusch_decode_plan_info(const miphy_pusch_decode_plan* p, uint32_t info[3])
 {
   MIPHY_REQUIRE(p && info, "miphy_pusch_decode_plan_info: null argument");
-  info[0] = p->ncb;
+  info[0] = p->b.ncb;
   info[1] = p->b.all_fused ? 1u : 0u;
   info[2] = p->b.max_nodes;
   return MIPHY_OK;
@@ -759,35 +708,29 @@ extern "C" uint32_t miphy_pusch_decode_plan_nof_launches(const miphy_pusch_decod
 
 extern "C" void miphy_pusch_decode_plan_destroy(miphy_pusch_decode_plan* p)
 {
-  if (!p)
-    return;
-  if (p->d_buf)
-    (void)hipFree(p->d_buf);
-  for (hipEvent_t e : p->events)
-    (void)hipEventDestroy(e);
   delete p;
 }
 
 namespace {
-// Host-side product of the segmentation of a batch of downlink transport blocks: what the four launches of a PDSCH encode need.
+// Host-side product of the segmentation of a batch of downlink transport blocks: what the launches of a PDSCH encode need (the sizes and
+// the places of the arrays in the device buffer) and the descriptor arrays, which go to the device (pdsch_encode_image).
 struct pdsch_encode_build {
+  size_t   max_lds = 0, max_lds_pk = 0; // of the one-lane-per-bit kernel's codeblocks / of the packed kernel's
+  uint32_t npacked = 0;
+  uint32_t n = 0, ncb = 0;
+  image_slot<miphy_crc_desc>      crcd;
+  image_slot<miphy_pdsch_cb_desc> cbs;
+  image_slot<uint32_t>            tbcrc;
+};
+struct pdsch_encode_descs {
   std::vector<miphy_crc_desc>      crcd;
   std::vector<miphy_pdsch_cb_desc> cbs; // one record per codeblock for the fused kernel (pdsch_cb_encode.hip)
-  size_t                           max_lds = 0, max_lds_pk = 0; // of the one-lane-per-bit kernel's codeblocks / of the packed kernel's
-  uint32_t                         npacked = 0;
-  uint32_t                         n = 0, ncb = 0;
-};
-struct pdsch_encode_dev {
-  const miphy_crc_desc*      crcd;
-  const miphy_pdsch_cb_desc* cbs;
-  uint32_t*                  tbcrc;
-  size_t                     staged, total;
 };
 
-int build_pdsch_encode(const miphy_pdsch_tb_desc* tbs, uint32_t n, pdsch_encode_build& b)
+int build_pdsch_encode(const miphy_pdsch_tb_desc* tbs, uint32_t n, pdsch_encode_build& b, pdsch_encode_descs& v)
 {
   b.n = n;
-  b.crcd.resize(n);
+  v.crcd.resize(n);
   for (uint32_t t = 0; t < n; ++t) {
     const miphy_pdsch_tb_desc& d = tbs[t];
     seg_t                      sg;
@@ -798,9 +741,9 @@ int build_pdsch_encode(const miphy_pdsch_tb_desc* tbs, uint32_t n, pdsch_encode_
     MIPHY_REQUIRE(d.nof_layers >= 1 && d.nof_layers <= 4, "pdsch_encode: TB %u: invalid number of layers", t);
     MIPHY_REQUIRE(d.mod == 1 || d.mod == 2 || d.mod == 4 || d.mod == 6 || d.mod == 8, "pdsch_encode: TB %u: invalid modulation", t);
     MIPHY_REQUIRE(d.nof_ch_symbols % d.nof_layers == 0, "pdsch_encode: TB %u: channel symbols not a multiple of the layers", t);
-    b.crcd[t].bit_offset = d.tb_offset * 8;
-    b.crcd[t].nbits      = sg.tbs;
-    b.crcd[t].poly       = (sg.nof_tb_crc_bits == 16) ? MIPHY_CRC16 : MIPHY_CRC24A;
+    v.crcd[t].bit_offset = d.tb_offset * 8;
+    v.crcd[t].nbits      = sg.tbs;
+    v.crcd[t].poly       = (sg.nof_tb_crc_bits == 16) ? MIPHY_CRC16 : MIPHY_CRC24A;
     uint32_t tb_bit = 0, cw_off = 0;
     for (uint32_t c = 0; c < sg.nof_cbs; ++c) {
       const bool          last = (c == sg.nof_cbs - 1);
@@ -831,57 +774,45 @@ int build_pdsch_encode(const miphy_pdsch_tb_desc* tbs, uint32_t n, pdsch_encode_
         b.max_lds_pk = std::max(b.max_lds_pk, lp), ++b.npacked;
       else
         b.max_lds = std::max(b.max_lds, miphy_pdsch_cb_encode_lds(sg.K, sg.Z, p.out_len));
-      b.cbs.push_back(p);
+      v.cbs.push_back(p);
       cw_off += E;
     }
     MIPHY_REQUIRE(cw_off == d.nof_ch_symbols * d.mod, "pdsch_encode: TB %u: codeblock lengths (%u) do not add up to the codeword (%u)", t, cw_off,
                   d.nof_ch_symbols * d.mod);
   }
-  b.ncb = (uint32_t)b.cbs.size();
+  b.ncb = (uint32_t)v.cbs.size();
   MIPHY_REQUIRE(b.ncb <= 65535, "pdsch_encode: %u codeblocks in one call (max 65535)", b.ncb);
   return MIPHY_OK;
 }
 
-size_t pdsch_encode_bytes(const pdsch_encode_build& b)
+// The descriptors as the staged part of the image of the device buffer; the TB checksums follow.
+void pdsch_encode_image(pdsch_encode_build& b, const pdsch_encode_descs& d, device_image& img)
 {
-  return 128 + b.crcd.size() * sizeof(b.crcd[0]) + b.cbs.size() * sizeof(b.cbs[0]) + (size_t)b.n * 4 + 16 * 8;
-}
-
-// Lays the descriptors out in a host image `h` of the device buffer `dv` (same offsets); the TB checksums follow the staged part.
-pdsch_encode_dev layout_pdsch_encode(const pdsch_encode_build& b, uint8_t* h, uint8_t* dv)
-{
-  pdsch_encode_dev v;
-  size_t           off = 0;
-  v.crcd   = stage_vec(h, dv, b.crcd, off);
-  v.cbs    = stage_vec(h, dv, b.cbs, off);
-  v.staged = off;
-  off      = (off + 15) & ~(size_t)15;
-  v.tbcrc  = reinterpret_cast<uint32_t*>(dv + off);
-  v.total  = off + (size_t)b.n * 4;
-  return v;
+  b.crcd  = img.put(d.crcd);
+  b.cbs   = img.put(d.cbs);
+  b.tbcrc = img.reserve<uint32_t>(b.n);
 }
 
 // TB CRC of every transport block, then ONE kernel per codeblock: assembly (TB bits, TB CRC, padding, CRC24B, fillers), LDPC encoder and
 // rate matcher with the codeblock in LDS (pdsch_cb_encode.hip).
-unsigned g_pdsch_cb_counts[2] = {0, 0}; // codeblocks encoded by the bit-packed kernel / in total (miphy_debug_pdsch_cb_counts)
+std::atomic<unsigned> g_pdsch_cb_counts[2]; // codeblocks encoded by the bit-packed kernel / in total (miphy_debug_pdsch_cb_counts)
 
-int launch_pdsch_encode(miphy_ctx* ctx, uint32_t n, uint32_t ncb, size_t max_lds, const pdsch_encode_dev& v, const uint8_t* tb_in, uint8_t* codeword_out,
-                        hipStream_t s, uint32_t npacked, size_t max_lds_pk)
+int launch_pdsch_encode(miphy_ctx* ctx, const pdsch_encode_build& b, void* buf, const uint8_t* tb_in, uint8_t* codeword_out, hipStream_t s)
 {
   int rc;
-  g_pdsch_cb_counts[0] += npacked, g_pdsch_cb_counts[1] += ncb;
-  if ((rc = miphy_crc_batch(ctx, v.crcd, 1, n, tb_in, v.tbcrc, s)))
+  g_pdsch_cb_counts[0] += b.npacked, g_pdsch_cb_counts[1] += b.ncb;
+  uint32_t* tbcrc = b.tbcrc.at(buf);
+  if ((rc = miphy_crc_batch(ctx, b.crcd.at(buf), 1, b.n, tb_in, tbcrc, s)))
     return rc;
-  return miphy_pdsch_cb_encode_launch(ctx, v.cbs, ncb, max_lds, tb_in, v.tbcrc, codeword_out, s, npacked, max_lds_pk);
+  return miphy_pdsch_cb_encode_launch(ctx, b.cbs.at(buf), b.ncb, b.max_lds, tb_in, tbcrc, codeword_out, s, b.npacked, b.max_lds_pk);
 }
 } // namespace
 
 // Test hook: how many codeblocks of the PDSCH encoder launches since the last reset went to the bit-packed kernel, and how many in total.
 extern "C" void miphy_debug_pdsch_cb_counts(unsigned out[2], int reset)
 {
-  out[0] = g_pdsch_cb_counts[0], out[1] = g_pdsch_cb_counts[1];
-  if (reset)
-    g_pdsch_cb_counts[0] = g_pdsch_cb_counts[1] = 0;
+  for (int k = 0; k < 2; ++k)
+    out[k] = reset ? g_pdsch_cb_counts[k].exchange(0) : g_pdsch_cb_counts[k].load();
 }
 
 extern "C" int miphy_pdsch_encode_batch(miphy_ctx* ctx, const miphy_pdsch_tb_desc* tbs, uint32_t n, const uint8_t* tb_in, uint8_t* codeword_out, void* stream)
@@ -891,68 +822,49 @@ extern "C" int miphy_pdsch_encode_batch(miphy_ctx* ctx, const miphy_pdsch_tb_des
     return MIPHY_OK;
   hipStream_t        s = (hipStream_t)stream;
   pdsch_encode_build b;
-  int                rc = build_pdsch_encode(tbs, n, b);
+  pdsch_encode_descs d;
+  int                rc = build_pdsch_encode(tbs, n, b, d);
   if (rc)
     return rc;
-  const size_t bytes = pdsch_encode_bytes(b);
-  void*        wsv   = nullptr;
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_GENERAL, bytes, &wsv)))
+  device_image img;
+  pdsch_encode_image(b, d, img);
+  void* buf = nullptr;
+  if ((rc = miphy_image_to_workspace(ctx, MIPHY_WS_GENERAL, img, s, &buf)))
     return rc;
-  std::vector<uint8_t>   host(bytes);
-  const pdsch_encode_dev v = layout_pdsch_encode(b, host.data(), (uint8_t*)wsv);
-  if ((rc = miphy_upload(ctx, wsv, host.data(), v.staged, s)))
-    return rc;
-  return launch_pdsch_encode(ctx, n, b.ncb, b.max_lds, v, tb_in, codeword_out, s, b.npacked, b.max_lds_pk);
+  return launch_pdsch_encode(ctx, b, buf, tb_in, codeword_out, s);
 }
 
 // ---- prepared form (internal: the PDSCH processor plan of pdsch_proc.hip builds on it): segmentation and descriptor upload once, a run
 // is launches only.
 struct miphy_pdsch_encode_prepared {
-  miphy_ctx*       ctx;
-  uint32_t         n, ncb;
-  size_t           max_lds, max_lds_pk;
-  uint32_t         npacked;
-  pdsch_encode_dev v;
-  void*            d_buf;
+  miphy_ctx*         ctx = nullptr;
+  pdsch_encode_build b;
+  miphy_device_block buf; // [staged descriptors | TB checksums]
 };
 
 int miphy_pdsch_encode_prepare(miphy_ctx* ctx, const miphy_pdsch_tb_desc* tbs, uint32_t n, miphy_pdsch_encode_prepared** out)
 {
   MIPHY_REQUIRE(ctx && tbs && out && n > 0, "miphy_pdsch_encode_prepare: null argument or empty batch");
-  pdsch_encode_build b;
-  int                rc = build_pdsch_encode(tbs, n, b);
+  std::unique_ptr<miphy_pdsch_encode_prepared> p(new miphy_pdsch_encode_prepared());
+  p->ctx = ctx;
+  pdsch_encode_descs d;
+  int                rc = build_pdsch_encode(tbs, n, p->b, d);
   if (rc)
     return rc;
-  const size_t bytes = pdsch_encode_bytes(b);
-  auto*        p     = new miphy_pdsch_encode_prepared();
-  p->ctx = ctx, p->n = n, p->ncb = b.ncb, p->max_lds = b.max_lds, p->max_lds_pk = b.max_lds_pk, p->npacked = b.npacked, p->d_buf = nullptr;
-  std::vector<uint8_t> host(bytes);
-  hipError_t           e = hipMalloc(&p->d_buf, bytes);
-  if (e == hipSuccess) {
-    p->v = layout_pdsch_encode(b, host.data(), (uint8_t*)p->d_buf);
-    e    = hipMemcpy(p->d_buf, host.data(), p->v.staged, hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) {
-    miphy_set_error("miphy_pdsch_encode_prepare: %s", hipGetErrorString(e));
-    if (p->d_buf)
-      (void)hipFree(p->d_buf);
-    delete p;
-    return MIPHY_EHIP;
-  }
-  *out = p;
+  device_image img;
+  pdsch_encode_image(p->b, d, img);
+  if ((rc = miphy_image_to_block("miphy_pdsch_encode_prepare", img, p->buf)))
+    return rc;
+  *out = p.release();
   return MIPHY_OK;
 }
 
 int miphy_pdsch_encode_prepared_run(miphy_pdsch_encode_prepared* p, const uint8_t* tb_in, uint8_t* codeword_out, hipStream_t s)
 {
-  return launch_pdsch_encode(p->ctx, p->n, p->ncb, p->max_lds, p->v, tb_in, codeword_out, s, p->npacked, p->max_lds_pk);
+  return launch_pdsch_encode(p->ctx, p->b, p->buf.get(), tb_in, codeword_out, s);
 }
 
 void miphy_pdsch_encode_prepared_destroy(miphy_pdsch_encode_prepared* p)
 {
-  if (!p)
-    return;
-  if (p->d_buf)
-    (void)hipFree(p->d_buf);
   delete p;
 }

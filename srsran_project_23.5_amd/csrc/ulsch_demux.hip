@@ -190,17 +190,14 @@ extern "C" int miphy_ulsch_demultiplex_batch(miphy_ctx* ctx, const miphy_ulsch_d
     MIPHY_REQUIRE(plans[i].nof_ack_re * plans[i].bits_per_re == jobs[i].nof_enc_harq_ack_bits, "ulsch_demultiplex: job %u: HARQ-ACK length is not a whole number of elements", i);
     dj[i] = {jobs[i].in_offset, jobs[i].sch_offset, jobs[i].harq_ack_offset, jobs[i].csi_part1_offset, jobs[i].csi_part2_offset};
   }
-  hipStream_t  s     = (hipStream_t)stream;
-  const size_t bytes = n * (sizeof(ulsch_plan) + sizeof(demux_dev_job)) + 64;
-  void*        ws    = nullptr;
-  int          rc    = miphy_get_workspace(ctx, MIPHY_WS_GENERAL, bytes, &ws);
-  if (rc)
-    return rc;
-  auto* d_plans = static_cast<ulsch_plan*>(ws);
-  auto* d_jobs  = reinterpret_cast<demux_dev_job*>(d_plans + n);
-  if ((rc = miphy_upload(ctx, d_plans, plans.data(), n * sizeof(ulsch_plan), s)) || (rc = miphy_upload(ctx, d_jobs, dj.data(), n * sizeof(demux_dev_job), s)))
+  hipStream_t  s = (hipStream_t)stream;
+  device_image img;
+  const auto   s_plans = img.put(plans);
+  const auto   s_jobs  = img.put(dj);
+  void*        ws      = nullptr;
+  if (int rc = miphy_image_to_workspace(ctx, MIPHY_WS_GENERAL, img, s, &ws))
     return rc; // (the host vectors go out of scope: the bytes travel through the pinned ring)
-  hipLaunchKernelGGL(ulsch_demux_kernel, dim3(n, 14), dim3(256), 0, s, d_plans, d_jobs, llr_in, sch_out, harq_ack_out, csi_part1_out, csi_part2_out);
+  hipLaunchKernelGGL(ulsch_demux_kernel, dim3(n, 14), dim3(256), 0, s, s_plans.at(ws), s_jobs.at(ws), llr_in, sch_out, harq_ack_out, csi_part1_out, csi_part2_out);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }

@@ -361,3 +361,135 @@ def test_mixed_class_plan_replays_as_a_hip_graph(form):
         miphy.lib().miphy_debug_force_ldpc_kernel(0)
         torch.cuda.synchronize()
         ctx.close()
+
+
+def test_smallest_full_image_and_creates_that_fail(ctx):
+    """The smallest PUSCH batch in which every array of the decode's device image is non-empty: two new transmissions of one codeblock each, one
+    on base graph 1 with Z = 384 (a packed class that dematches while it loads), one on base graph 2 with Z = 24 (a wave class: a bundle, and a
+    dematcher descriptor of its own). Per call and as a plan: bits, iteration counts and result records as the oracle's. Then every create
+    function -- PUSCH decode plan, LDPC decode plan, PDSCH process plan and the prepared PDSCH encode inside it -- refuses a batch with one
+    invalid entry with MIPHY_EINVAL, and a valid create and run on the same context afterwards still gives the oracle's results."""
+    import torch
+    import miphy
+    import dl_grid as D
+    import oracle_lib as O
+    from miphy.ldpc import make_dec_descs
+    from test_pdsch_mod_gpu import _words
+    rng = np.random.default_rng(2024)
+
+    def refused(what, make):
+        with pytest.raises(RuntimeError, match=r"miphy error -1: .*" + what):
+            make()
+
+    # ---- PUSCH decode
+    tbs, slot, llr_off, tb_off = [], 0, 0, 0
+    for bg, nbytes, nprb, Z, sigma in [(1, 1000, 52, 384, 0.6), (2, 16, 2, 24, 0.6)]:
+        seg = miphy.sch_segmentation(nbytes, bg)
+        assert (seg.nof_cbs, seg.Z) == (1, Z)
+        tb = rng.integers(0, 256, nbytes, dtype=np.uint8)
+        nsym = nprb * 156
+        llr = noisy(o_pdsch_encode(bg, 0, 2, 0, 1, nsym, tb), sigma, rng)
+        tbs.append(dict(bg=bg, nsym=nsym, tb=tb, llr=llr, slot=slot, llr_off=llr_off, tb_off=tb_off))
+        slot, llr_off, tb_off = slot + 1, llr_off + (llr.size + 15) // 16 * 16, tb_off + (nbytes + 15) // 16 * 16
+    n = len(tbs)
+    d = np.zeros(n, dtype=miphy.PuschTbDesc)
+    llr_h = np.zeros(llr_off, np.int8)
+    for i, x in enumerate(tbs):
+        d[i] = (x["bg"], 0, 2, 1, 1, 1, 6, 0, x["nsym"], x["tb"].size, x["slot"], x["llr_off"], x["tb_off"])
+        llr_h[x["llr_off"]:x["llr_off"] + x["llr"].size] = x["llr"]
+        od = OraclePuschDecoder(x["bg"], 2, 0, 1, x["nsym"], x["tb"].size)
+        x["ok"], x["tbo"], x["mm"] = od.decode(x["llr"], 0, True, 6, True)
+        x["soft"] = od.softbuf.copy()
+    assert all(x["ok"] for x in tbs)
+    llr_d = torch.from_numpy(llr_h).cuda()
+
+    def decode_and_check(run):
+        soft_d = torch.full((slot * miphy.HARQ_CB_STRIDE,), 33, dtype=torch.int8, device="cuda")
+        msgs_d = torch.zeros(slot * miphy.HARQ_MSG_STRIDE, dtype=torch.uint8, device="cuda")
+        crc_d = torch.ones(slot, dtype=torch.uint8, device="cuda")
+        res_d = torch.zeros(n * miphy.PuschResult.itemsize, dtype=torch.uint8, device="cuda")
+        tb_d = torch.full((tb_off,), 0xEE, dtype=torch.uint8, device="cuda")
+        run(llr_d, soft_d, msgs_d, crc_d, tb_d, res_d)
+        torch.cuda.synchronize()
+        res, got, soft = res_d.cpu().numpy().view(miphy.PuschResult), tb_d.cpu().numpy(), soft_d.cpu().numpy().reshape(slot, miphy.HARQ_CB_STRIDE)
+        for i, x in enumerate(tbs):
+            r = res[i]
+            assert bool(r["tb_crc_ok"]) and int(r["nof_codeblocks_total"]) == 1 and int(r["nof_decoded"]) == 1, (i, r)
+            assert (int(r["iters_min"]), int(r["iters_max"])) == x["mm"] and float(r["iters_mean"]) == float(x["mm"][0]), (i, r, x["mm"])
+            assert np.array_equal(got[x["tb_off"]:x["tb_off"] + x["tb"].size], x["tb"]) and np.array_equal(x["tbo"], x["tb"]), i
+            assert np.array_equal(soft[x["slot"], :x["soft"].size], x["soft"]), i
+        return res.copy(), got
+
+    miphy.lib().miphy_debug_ldpc_kernels_used(1)
+    res_call, tb_call = decode_and_check(lambda *a: ctx.pusch_decode_batch(d, *a))
+    used = int(miphy.lib().miphy_debug_ldpc_kernels_used(1))
+    assert used & 2 and used & 4 and used & 16, used  # packed + dematching while it loads, and the wave kernel (MIPHY_LDPC_KERNEL_WAVE)
+    bad = d.copy()
+    bad[1]["mod"] = 3
+    refused("invalid modulation", lambda: ctx.pusch_decode_plan(bad))
+    plan = ctx.pusch_decode_plan(d)
+    assert plan.info()[0] == 2 and plan.nof_launches() == 2
+    for _ in range(2):
+        res_plan, tb_plan = decode_and_check(plan.run)
+        assert np.array_equal(res_plan, res_call) and np.array_equal(tb_plan, tb_call)
+    plan.close()
+
+    # ---- LDPC decode plan: two BG1 / Z = 384 codeblocks as in smoke(), the second descriptor of the refused batch with no iterations
+    bg, Z, nf, mod, E, ncb = 1, 384, 8, 8, 8968, 2
+    K, N = 22 * Z, 66 * Z
+    sb, exp = np.zeros((ncb, N), np.int8), []
+    for i in range(ncb):
+        msg = rng.integers(0, 2, K, dtype=np.uint8)
+        c = O.o_crc_bits(O.CRC24B, msg[:K - nf - 24])
+        msg[K - nf - 24:K - nf] = [(c >> (23 - j)) & 1 for j in range(24)]
+        msg[K - nf:] = 254
+        rm = O.o_rate_match(0, mod, 0, nf, O.o_ldpc_encode(bg, Z, msg, N), E)
+        sb[i] = O.o_rate_dematch(0, mod, 0, nf, 1, noisy(rm, 0.25, rng), np.zeros(N, np.int8))
+        exp.append(O.o_ldpc_decode(bg, Z, sb[i], nf, O.CRC24B, 6))
+    descs = make_dec_descs(ncb, bg, Z, N, miphy.CRC24B, 6, nf)
+    bad = descs.copy()
+    bad[1]["max_iter"] = 0
+    refused("max_iter", lambda: miphy.LdpcDecodePlan(ctx, bad))
+    lplan = miphy.LdpcDecodePlan(ctx, descs)
+    out_d = torch.zeros(ncb * K // 8, dtype=torch.uint8, device="cuda")
+    it_d = torch.zeros(ncb, dtype=torch.int32, device="cuda")
+    lplan.run(torch.from_numpy(sb.reshape(-1)).cuda(), out_d, it_d)
+    torch.cuda.synchronize()
+    for i in range(ncb):
+        assert int(it_d[i].item()) == exp[i][0] and exp[i][0] > 0, i
+        assert np.array_equal(out_d.cpu().numpy().reshape(ncb, K // 8)[i], exp[i][1]), i
+    lplan.close()
+
+    # ---- PDSCH process plan: one PDU refused by the processor's own rules, one by the prepared encoder underneath it
+    nprb, dsyms = 25, (2,)
+    rb = np.zeros(nprb, np.uint8)
+    rb[3:7] = 1
+    pdus = np.zeros(2, dtype=miphy.PdschPdu)
+    want, ptbs = [], []
+    for i, nbytes in enumerate((40, 24)):
+        tb = rng.integers(0, 256, nbytes, dtype=np.uint8)
+        p = pdus[i]
+        p["slot_in_frame"], p["rnti"], p["n_id"], p["dmrs_scrambling_id"], p["tbs_lbrm_bytes"], p["tb_bytes"] = 3 + i, 0x1234 + i, 77, 99, 400, nbytes
+        p["bg"], p["rv"], p["mod"], p["port"], p["start_symbol"], p["nof_symbols"] = 2, 0, 2, 0, 0, 14
+        p["nof_cdm_groups_without_data"], p["n_scid"], p["ref_point_prb0"], p["nof_reserved"] = 1, 0, 0, 0
+        p["dmrs_symbols_mask"], p["grid_nof_prb"], p["bwp_start_rb"], p["bwp_size_rb"], p["rb_mask"] = 1 << 2, nprb, 0, nprb, _words(rb)
+        p["tb_offset"], p["grid_offset"] = 64 * i, i * 14 * nprb * 12
+        g = np.zeros((1, 14, nprb * 12), dtype=np.complex64)
+        D.o_pdsch_process(dict(bg=2, rv=0, mod=2, lbrm_bytes=400, tb=tb, rnti=0x1234 + i, n_id=77, slot=3 + i, scr=99, n_scid=0, start=0, nof=14, dmrs_symbols=dsyms,
+                               cdm=1, bwp=(0, nprb), rb=rb, reserved=[], port=0, ref_point_prb0=0, dmrs_dB=0.0, data_dB=0.0), g)
+        want.append(g.reshape(-1))
+        ptbs.append(tb)
+    bad = pdus.copy()
+    bad[1]["nof_cdm_groups_without_data"] = 3
+    refused("CDM groups", lambda: miphy.PdschProcessPlan(ctx, bad))
+    bad = pdus.copy()
+    bad[1]["tb_bytes"] = 0
+    refused("sch: transport block size 0 bytes", lambda: miphy.PdschProcessPlan(ctx, bad))
+    pplan = miphy.PdschProcessPlan(ctx, pdus)
+    tb_all = np.zeros(128, np.uint8)
+    tb_all[0:40], tb_all[64:88] = ptbs[0], ptbs[1]
+    gd = torch.zeros(2 * 14 * nprb * 12, dtype=torch.complex64, device="cuda")
+    pplan.run(torch.from_numpy(tb_all).cuda(), gd)
+    torch.cuda.synchronize()
+    assert np.array_equal(gd.cpu().numpy().view(np.uint32), np.concatenate(want).view(np.uint32))
+    pplan.close()
