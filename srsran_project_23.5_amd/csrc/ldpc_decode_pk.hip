@@ -19,10 +19,13 @@ namespace {
 
 // Is the checksum of the first L hard bits zero? (every thread of the block must call) Mask / popcount form where the polynomial has a
 // table (zi >= 0), by division otherwise; words strided over the block's threads.
-__device__ __forceinline__ bool block_crc_is_zero(const int8_t* soft, const miphy_graph_tables* __restrict__ tab, int zi, int order, int L,
-                                                  uint32_t* red, int tid, int nt)
+// `kept` receives this lane's words of the K message bits, decided on the way (crc_zmask_partial<true>): every evaluation stands in front of
+// the output or of another evaluation, so the words of the last one are the output (store_kept_words).
+template <bool KEEP>
+__device__ __forceinline__ bool block_crc_is_zero(const int8_t* soft, const miphy_graph_tables* __restrict__ tab, int zi, int order, int L, int K,
+                                                  uint32_t* kept, uint32_t* red, int tid, int nt)
 {
-  return block_xor(crc_zmask_partial(soft, tab, zi, order, L, tid, nt), red, tid, nt) == 0;
+  return block_xor(crc_zmask_partial<KEEP>(soft, tab, zi, order, L, tid, nt, K, kept), red, tid, nt) == 0;
 }
 
 __device__ __forceinline__ uint32_t block_crc(const int8_t* soft, const miphy_graph_tables* __restrict__ tab, int crc_id, uint32_t poly,
@@ -184,10 +187,12 @@ __device__ __attribute__((noinline)) void pk_fused_load(int8_t* __restrict__ sof
 // (ldpc_decoder_impl.cpp:86-99). Inlined into the kernel: a function has to wait for its stores before it returns (25 KB per
 // codeblock on their way to HBM), here they drain under the first layers. Returns this lane's candidate for the position behind the
 // last non-zero soft bit.
-__device__ __forceinline__ int pk_fused_image_out(const int8_t* __restrict__ soft, int8_t* __restrict__ llr_img, int Z, int bgi, int in_len, int tid, int nt)
+// The search starts at the end of the data, `end` = E + F (everything behind it was just written as zero, pk_fused_load), and goes back
+// until a vector holds a non-zero byte -- in practice the last one: every wavefront looks at the same 64 vectors per step, highest vector
+// in lane 0, and stops on a wave-uniform test, so that no wavefront waits for another and every lane reaches the caller's atomicMax.
+__device__ __forceinline__ int pk_fused_image_out(const int8_t* __restrict__ soft, int8_t* __restrict__ llr_img, int Z, int bgi, int in_len, int end, int tid, int nt)
 {
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  int          last = 0;
   u32x4*       dst  = reinterpret_cast<u32x4*>(llr_img);
   const uint4* src  = reinterpret_cast<const uint4*>(soft + 2 * Z);
   const int    nimg = in_len >> 4, nall = ((miphy_bg_N_short(bgi) * Z) >> 4);
@@ -198,11 +203,18 @@ __device__ __forceinline__ int pk_fused_image_out(const int8_t* __restrict__ sof
     const uint4 v = src[q];
     const u32x4 o = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(o, dst + q);
-    last = last_nonzero_behind(v, q, last);
   }
   const u32x4 zero = {0, 0, 0, 0};
   for (int q = nimg + tid; q < nall; q += nt)
     __builtin_nontemporal_store(zero, dst + q);
+  int last = 0;
+  for (int hi = __builtin_amdgcn_readfirstlane((min(end, in_len) - 1) >> 4); hi >= 0; hi -= 64) {
+    const int q = hi - (tid & 63);
+    if (q >= 0)
+      last = last_nonzero_behind(src[q], q, 0);
+    if (__builtin_amdgcn_ballot_w64(last != 0))
+      break;
+  }
   return last;
 }
 
@@ -255,6 +267,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   const int tid = threadIdx.x;
   const int nt  = blockDim.x;
   constexpr bool SPLIT = PARTS > 1;
+  constexpr bool KEEPW = FUSED && !SPLIT; // the checksum's words are kept for the output (crc_zmask_partial<true>)
   static_assert(PARTS == 1 || PARTS == 2 || PARTS == 4, "parts of the latency form");
   static_assert(!(SPLIT && GMSG), "the latency form keeps its messages in LDS");
   static_assert(!ATAB || (FUSED && !GMSG && !SPLIT), "address tables: the throughput form that dematches, messages in LDS");
@@ -341,7 +354,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
   if (FUSED) {
     const miphy_ldpc_rdm_desc rd = load_words(rdm + cb);
     pk_fused_load(soft, (global_ci8)(rm_in_base + rd.in_offset), (int)rd.E, (int)dsc.nof_filler_bits, (int)rd.mod, Z, bgK, soft_bytes, pre[0], pre[1], pre[2], tid, nt);
-    last = pk_fused_image_out(soft, const_cast<int8_t*>(llr), Z, bgi, in_len, tid, nt);
+    last = pk_fused_image_out(soft, const_cast<int8_t*>(llr), Z, bgi, in_len, (int)rd.E + (int)dsc.nof_filler_bits, tid, nt);
   } else {
     last = cb_plain_load(soft, llr, in_len, Z, soft_bytes, tid, nt);
   }
@@ -391,6 +404,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
 
   int       result_iters = 0;
   const int max_iter     = dsc.max_iter;
+  uint32_t  kept[2]      = {0, 0}; // this lane's words of the hard bits, as the last checksum evaluation decided them
   PROF_T(p_loaded);
   PROF_ADD(0, p_start, p_loaded);
   // The two wrap constants of the address computations live in VECTOR registers: a VOP2 add / sub with a scalar operand issues at
@@ -468,7 +482,7 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
       PROF_ADD(2, p_l1, p_l2);
     }
     if (use_crc && !final_only) {
-      if (zi >= 0 ? block_crc_is_zero(soft, tab, zi, (int)order, L, red, tid, nt) : block_crc(soft, tab, dsc.crc_poly, poly, order, K, L, red, tid, nt) == 0) {
+      if (zi >= 0 ? block_crc_is_zero<KEEPW>(soft, tab, zi, (int)order, L, K, kept, red, tid, nt) : block_crc(soft, tab, dsc.crc_poly, poly, order, K, L, red, tid, nt) == 0) {
         result_iters = it + 1;
         break;
       }
@@ -482,13 +496,17 @@ ldpc_decode_pk_kernel(const miphy_ldpc_dec_desc* __restrict__ descs,
     prefetch(red[15]);
   }
   if (final_only)
-    result_iters = (zi >= 0 ? block_crc_is_zero(soft, tab, zi, (int)order, L, red, tid, nt) : block_crc(soft, tab, dsc.crc_poly, poly, order, K, L, red, tid, nt) == 0)
+    result_iters = (zi >= 0 ? block_crc_is_zero<KEEPW>(soft, tab, zi, (int)order, L, K, kept, red, tid, nt) : block_crc(soft, tab, dsc.crc_poly, poly, order, K, L, red, tid, nt) == 0)
                        ? max_iter
                        : 0;
   PROF_T(p_crc);
   PROF_ADD(3, p_dec, p_crc);
 
-  store_hard_words(soft, out, K, tid, nt);
+  // A mask-table checksum has decided this lane's words of the output: its last evaluation is the one after the last layer visit.
+  if (KEEPW && zi >= 0 && (final_only || max_iter > 0))
+    store_kept_words(soft, out, K, tid, nt, kept);
+  else
+    store_hard_words(soft, out, K, tid, nt);
   if (tid == 0) {
     iters_out[cb] = result_iters;
     // A codeblock that is dematched here is a first transmission: its flag is written either way, which is the reset the caller

@@ -617,67 +617,68 @@ __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b, uint32_t 
   return r;
 }
 
-// Hard decision of 32 consecutive soft bits starting at soft[32*t]; returns the big-endian numeric value (first bit in
-// bit 31). Positions >= K are masked to 0. bit = (llr <= 0), log_likelihood_ratio.h:86.
+// Hard decision of the 32 consecutive soft bits starting at soft[32 t] (16-byte aligned); returns the big-endian numeric value (first bit
+// in bit 31). Positions >= K are masked to 0. bit = (llr <= 0), log_likelihood_ratio.h:86.
+// Four soft bytes per operation: bit 7 of a byte of ((x & 0x7f..) + 0x7f..) says "low seven bits non-zero", and the byte is > 0 when that
+// bit is set and its sign bit is clear. v_dot4_u32_u8 then gathers the four flags of a dword (0x80 or 0 per byte) MSB first: with the byte
+// weights {0x80, 0x40, 0x20, 0x10} for an even dword and {8, 4, 2, 1} for the odd one behind it, two chained dot products give 128 times
+// the eight bits of a byte of the word, and the accumulator input takes the byte in front of it. The word is the complement of the
+// "> 0" bits. It is the word of crc_zmask as well (miphy_internal.h): checksum and output share one decision.
 __device__ __forceinline__ uint32_t hard_word(const int8_t* soft, int t, int K)
 {
-  const uint32_t* p = reinterpret_cast<const uint32_t*>(soft) + 8 * t;
-  uint32_t        w = 0;
+  const uint4*   p  = reinterpret_cast<const uint4*>(soft) + 2 * t;
+  const uint4    lo = p[0], hi = p[1];
+  const uint32_t x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  uint32_t       h[2]; // 128 times bits 0..15 and bits 16..31 of the word, as numbers
 #pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    const uint32_t x = p[q];
+  for (int k = 0; k < 2; ++k) {
+    uint32_t acc = 0;
 #pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int v = (int8_t)(x >> (8 * b));
-      w |= (uint32_t)(v <= 0) << (31 - (4 * q + b));
+    for (int q = 4 * k; q < 4 * k + 4; ++q) {
+      const uint32_t xq  = x[q ^ 1]; // the odd dword of a pair first: its byte is the inner accumulator
+      const uint32_t nz  = (xq & 0x7f7f7f7fu) + 0x7f7f7f7fu;
+      const uint32_t pos = ~xq & nz & 0x80808080u;
+      if (q == 4 * k + 2)
+        acc <<= 8;
+      acc = __builtin_amdgcn_udot4(pos, (q & 1) ? 0x10204080u : 0x01020408u, acc, false);
     }
+    h[k] = acc;
   }
+  uint32_t  w   = ~((h[0] << 9) | (h[1] >> 7));
   const int rem = K - 32 * t;
   if (rem < 32)
     w &= (rem <= 0) ? 0u : (0xffffffffu << (32 - rem));
   return w;
 }
 
-// Hard-decision flags of the 32 soft bits of group t in the layout of crc_zmask: bit (q + 8 b) = (soft[32 t + 4 q + b] <= 0).
-// Per dword of four soft bytes: bit 7 of a byte of ((x & 0x7f..) + 0x7f..) says "low seven bits non-zero"; the byte is <= 0 when
-// its sign bit is set or that bit is clear.
-__device__ __forceinline__ uint32_t hard_flags(const int8_t* soft, int t)
-{
-  const uint4* p  = reinterpret_cast<const uint4*>(soft) + 2 * t;
-  const uint4  lo = p[0], hi = p[1];
-  const uint32_t x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  uint32_t       w    = 0;
-#pragma unroll
-  for (int q = 7; q >= 0; --q) {
-    const uint32_t nz  = (x[q] & 0x7f7f7f7fu) + 0x7f7f7f7fu;
-    const uint32_t le0 = (x[q] | ~nz) & 0x80808080u;
-    w                  = (w << 1) | (le0 >> 7);
-  }
-  return w;
-}
-
 // Checksum of the first L hard bits in the mask / popcount form (crc_zmask in miphy_internal.h: no bit-serial division, no position
 // weights): this lane's parity word over the message words first, first + stride, ... The XOR of the lanes' words is zero exactly when
 // the checksum is. zi = table index of the polynomial, order = its degree.
+// KEEP (the packed kernel's evaluation in front of the output): the lane decides every word of the K >= L message bits it is about to
+// store -- the same words on the same lanes as store_hard_words -- and returns its first two in `kept`, masked at K, so that the output
+// does not read and decide the soft bits again (store_kept_words).
+template <bool KEEP = false>
 __device__ __forceinline__ uint32_t crc_zmask_partial(const int8_t* soft, const miphy_graph_tables* __restrict__ tab, int zi, int order, int L, int first,
-                                                      int stride)
+                                                      int stride, int K = 0, uint32_t* kept = nullptr)
 {
-  const int nw = (L + 31) >> 5;
+  const int nw = (L + 31) >> 5, nk = KEEP ? (K + 31) >> 5 : nw;
   uint32_t  acc[24];
 #pragma unroll
   for (int k = 0; k < 24; ++k)
     acc[k] = 0;
-  for (int t = first; t < nw; t += stride) {
-    uint32_t  w   = hard_flags(soft, t);
-    const int rem = L - 32 * t;
-    if (rem < 32) { // last word: positions 4 q + b >= rem are not message bits
-      uint32_t valid = 0;
-      for (int q = 0; q < 8; ++q) {
-        const int      nb = min(4, max(0, rem - 4 * q));                      // message bits among the four of dword q
-        const uint32_t lo = (nb >= 4) ? 0xffffffffu : ((1u << (8 * nb)) - 1u); // their byte lanes
-        valid |= (0x01010101u & lo) << q;
-      }
-      w &= valid;
+  [[maybe_unused]] uint32_t k0 = 0, k1 = 0;
+  [[maybe_unused]] int      i  = 0;
+  for (int t = first; t < nk; t += stride) {
+    uint32_t w = hard_word(soft, t, KEEP ? K : L);
+    if constexpr (KEEP) {
+      k0 = (i == 0) ? w : k0;
+      k1 = (i == 1) ? w : k1;
+      ++i;
+      if (t >= nw)
+        continue;
+      const int rem = L - 32 * t;
+      if (rem < 32) // last word of the checksum: positions >= L are not message bits
+        w &= 0xffffffffu << (32 - rem);
     }
     const uint4* m = reinterpret_cast<const uint4*>(tab->crc_zmask[zi][nw - 1 - t]);
 #pragma unroll
@@ -689,11 +690,14 @@ __device__ __forceinline__ uint32_t crc_zmask_partial(const int8_t* soft, const 
       acc[4 * g + 3] += __builtin_popcount(w & mk.w);
     }
   }
+  if constexpr (KEEP)
+    kept[0] = k0, kept[1] = k1;
+  // bit 0 of every count, one funnel shift each: count k enters at bit 31 and ends at bit 8 + k
   uint32_t par = 0;
 #pragma unroll
   for (int k = 0; k < 24; ++k)
-    par |= (acc[k] & 1u) << k;
-  return par & ((1u << order) - 1u);
+    par = __builtin_amdgcn_alignbit(acc[k], par, 1);
+  return (par >> 8) & ((1u << order) - 1u);
 }
 
 // The same by division, for polynomials without a mask table (CRC24C, CRC11): the partial remainder of each 32-bit word times its
@@ -741,22 +745,41 @@ __device__ __forceinline__ uint32_t block_xor(uint32_t part, uint32_t* red, int 
   return crc;
 }
 
+// One word of the final hard bits (MSB first) to its place among the K message bits: a dword where the output allows it, bytes otherwise.
+__device__ __forceinline__ void store_hard_word(uint8_t* out, bool out_aligned, uint32_t w, int t, int K)
+{
+  const int nbytes = min(4, (K - 32 * t + 7) / 8);
+  if (nbytes == 4 && out_aligned) {
+    reinterpret_cast<uint32_t*>(out)[t] = __builtin_bswap32(w); // MSB-first bytes
+  } else {
+    for (int q = 0; q < nbytes; ++q)
+      out[4 * t + q] = (uint8_t)(w >> (24 - 8 * q));
+  }
+}
+
 // The final hard bits of a codeblock, MSB first, words first, first + stride, ... of the K message bits. `base` as in update_rows_pk
 // (the wave kernel's group offset: added per word, which is the code the kernel had with the loop written out).
 __device__ __forceinline__ void store_hard_words(const int8_t* soft, uint8_t* out, int K, int first, int stride, uint32_t base = 0)
 {
   const bool out_aligned = ((uintptr_t)out & 3u) == 0;
   const int  kwords      = (K + 31) >> 5;
-  for (int t = first; t < kwords; t += stride) {
-    const uint32_t w      = hard_word(soft + base, t, K);
-    const int      nbytes = min(4, (K - 32 * t + 7) / 8);
-    if (nbytes == 4 && out_aligned) {
-      reinterpret_cast<uint32_t*>(out)[t] = __builtin_bswap32(w); // MSB-first bytes
-    } else {
-      for (int q = 0; q < nbytes; ++q)
-        out[4 * t + q] = (uint8_t)(w >> (24 - 8 * q));
-    }
-  }
+  for (int t = first; t < kwords; t += stride)
+    store_hard_word(out, out_aligned, hard_word(soft + base, t, K), t, K);
+}
+
+// The same where the checksum in front of the output has decided this lane's words already (crc_zmask_partial<true>): the first two come
+// from `kept`; a lane with more words (no geometry of the packed kernel has one: K / 32 <= 0.6875 Z + 1 words on >= Z / 2 lanes) decides
+// the others here.
+__device__ __forceinline__ void store_kept_words(const int8_t* soft, uint8_t* out, int K, int first, int stride, const uint32_t* kept)
+{
+  const bool out_aligned = ((uintptr_t)out & 3u) == 0;
+  const int  kwords      = (K + 31) >> 5;
+  if (first < kwords)
+    store_hard_word(out, out_aligned, kept[0], first, K);
+  if (first + stride < kwords)
+    store_hard_word(out, out_aligned, kept[1], first + stride, K);
+  for (int t = first + 2 * stride; t < kwords; t += stride)
+    store_hard_word(out, out_aligned, hard_word(soft, t, K), t, K);
 }
 
 } // namespace

@@ -146,10 +146,10 @@ static void build_tables(miphy_graph_tables* t)
       }
       for (int u = 0; u < MIPHY_CRC_ZMASK_WORDS; ++u)
         for (int jl = 0; jl < 32; ++jl) { // j = 32 u + jl
-          const int i_local = 31 - jl, q = i_local >> 2, b = i_local & 3;
+          const int i_local = 31 - jl;
           for (unsigned k = 0; k < ORDER[p]; ++k)
             if ((c >> k) & 1u) {
-              t->crc_zmask[zi][u][k] |= 1u << (q + 8 * b);
+              t->crc_zmask[zi][u][k] |= 1u << jl;
               if (p == 0)
                 t->crc_zmask_packed24a[u][k] |= 1u << (8 * (i_local >> 3) + 7 - (i_local & 7));
             }

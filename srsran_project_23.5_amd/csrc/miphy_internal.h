@@ -32,7 +32,7 @@ struct miphy_graph_tables {
   // 2 = CRC16) and word u counted from the END of the message padded with zeros to a multiple of 32 bits, crc_zmask[.][u][k] selects
   // the bits of that word whose weight x^(distance to the end + order) mod P has bit k set; bit k of the checksum of the padded
   // message is the parity of the sum over u of popcount(word & mask). (M(x) x^r mod P == 0 <=> M(x) mod P == 0, so the padding
-  // does not change the verdict.) Word layout: bit (q + 8 b) of a word is message bit 4 q + b of its group of 32 (see hard_flags()).
+  // does not change the verdict.) Word layout: MSB first, bit 31 - i of a word is message bit i of its group of 32 (hard_word(): the word of the output).
   // ([k][u], coalesced across the lanes, was measured: 24 dword loads per lane instead of 6 x 16 bytes cost the decoder 1 %; the 25 KB
   // table is cache resident either way.)
   uint32_t crc_zmask[3][MIPHY_CRC_ZMASK_WORDS][24];
