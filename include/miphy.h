@@ -440,7 +440,8 @@ int miphy_channel_equalize_batch(miphy_ctx* ctx, const miphy_equalizer_job* jobs
  *   lib/phy/upper/channel_modulation/modulation_mapper_impl.cpp:31-146
  *   include/srsran/phy/upper/signal_processors/dmrs_pdsch_processor.h:36-66, lib/.../dmrs_pdsch_processor_impl.cpp:30-169
  * Modulator: one codeword on one layer, PRBs mapped in ascending order (what 23.5 supports: its layer mapper and its
- * non-contiguous mapping path are broken, see csrc/pdsch_mod.hip); DM-RS pattern of the bandwidth part and up to four reserved RE
+ * non-contiguous mapping path are broken, see csrc/pdsch_mod.hip; 1..4 layers and PRB lists in another mapping order are further
+ * down: miphy_pdsch_modulate_layers_batch, miphy_pdsch_modulate_mapped_batch); DM-RS pattern of the bandwidth part and up to four reserved RE
  * patterns are skipped. The codeword is one bit per byte (the layout miphy_pdsch_encode_batch writes). Only the mapped REs of
  * the grid are written. */
 typedef struct {
@@ -503,7 +504,8 @@ int miphy_dmrs_pdsch_map_batch(miphy_ctx* ctx, const miphy_dmrs_pdsch_job* jobs,
  * the mapped REs of the named ports are written. The pi/2-BPSK rotation follows the parity of the codeword symbol L i + ly. A batch of
  * one-layer jobs writes the bytes miphy_pdsch_modulate_batch writes. Host jobs are checked before anything is enqueued (1..4 layers,
  * distinct ports below 16, nof_bits = REs x L x mod and the rules of the one-layer entry point); a device-resident job that breaks a
- * rule is skipped by the kernels. Not supported: two codewords (5..8 layers), precoding matrices, interleaved VRB-to-PRB mapping. */
+ * rule is skipped by the kernels. PRBs are mapped in ascending order here; any other order, the interleaved VRB-to-PRB mapping of TS 38.211
+ * 7.3.1.6 among them, goes through miphy_pdsch_modulate_mapped_batch below. Not supported: two codewords (5..8 layers), precoding matrices. */
 typedef struct {
   miphy_pdsch_mod_job base; /* base.port is ignored; base.nof_bits = miphy_pdsch_mod_layers_nof_re() x nof_layers x mod */
   uint8_t nof_layers;       /* 1..4 */
@@ -514,6 +516,50 @@ typedef struct {
 uint32_t miphy_pdsch_mod_layers_nof_re(const miphy_pdsch_mod_layers_job* job); /* host: data REs per layer; 0 on an invalid job */
 int miphy_pdsch_modulate_layers_batch(miphy_ctx* ctx, const miphy_pdsch_mod_layers_job* jobs, int jobs_on_device, uint32_t n,
                                       const uint8_t* codewords /* device */, float* grid /* device cf_t */, void* stream);
+
+/* VRB-to-PRB mapping of TS 38.211 7.3.1.6 (host function): the PRBs of the set VRBs of vrb_mask, in ascending VRB order -- the mapping
+ * order miphy_pdsch_modulate_mapped_batch and miphy_pdsch_process_mapped_batch take. (The contract is the standard, not the 23.5
+ * reference: its vrb_to_prb_mapper takes the size of the first bundle from the BWP size where 7.3.1.6 takes it from the BWP start, and
+ * starts the last bundle one PRB too low.)
+ * With L = bundle_size, N = region_size_rb and s = align_rb mod L there are N_bundle = ceil((N + s) / L) bundles; VRB n lies in bundle
+ * j = floor((n + s) / L) at position (n + s) mod L. Bundle N_bundle - 1 maps to itself; any other j = 2 c + r (r < 2) maps to
+ * f(j) = r C + c with C = floor(N_bundle / 2). PRB(n) = first_prb + f(j) L + (n + s) mod L - s; with L = 0, PRB(n) = first_prb + n.
+ * The three cases of 7.3.1.6:
+ *   DCI 1_0 in the Type0-PDCCH common search space of CORESET 0: L = 2, align_rb = 0, N = N_BWP,init^size,
+ *                                                               first_prb = BWP start + N_CORESET^start;
+ *   DCI 1_0 in any other common search space:                   the same with align_rb = N_BWP,i^start + N_CORESET^start;
+ *   every other case:                                           L = L_i, align_rb = N_BWP,i^start, N = N_BWP,i^size, first_prb = BWP start.
+ * prb_list[0 .. *nof_prb - 1] receives the PRBs (grid numbering), prb_mask (may be NULL) their set. MIPHY_EINVAL, no list or mask
+ * written, for: L outside {0, 2, 4}; N outside 1..275; first_prb + N > 275; a set bit of vrb_mask at or above N; cap < the number of set
+ * VRBs -- *nof_prb is that number then too, so that the caller can size the list. */
+typedef struct {
+  uint8_t  bundle_size;    /* L: 0 = non-interleaved, 2 or 4 */
+  uint8_t  pad;
+  uint16_t align_rb;       /* the bundle raster is aligned to this RB number: only align_rb mod L matters */
+  uint16_t region_size_rb; /* N: VRBs 0 .. N-1 exist */
+  uint16_t first_prb;      /* grid PRB that PRB 0 of the region is */
+} miphy_vrb_to_prb;
+int miphy_vrb_to_prb_list(const miphy_vrb_to_prb* map, const uint64_t vrb_mask[5], uint16_t* prb_list, uint32_t cap, uint32_t* nof_prb,
+                          uint64_t prb_mask[5] /* may be NULL */);
+
+/* PDSCH modulator with the PRBs of a job in a mapping order of the caller's: miphy_pdsch_modulate_layers_batch, except that within each OFDM
+ * symbol the data REs are taken PRB by PRB in the order of the job's list (subcarriers ascending inside a PRB) -- position i of the list is
+ * the i-th PRB in mapping order, what orc_pdsch_modulate calls prb_list. Which REs carry data, the layer mapping, scrambling, constellations,
+ * scaling and ports do not depend on the order, and miphy_pdsch_mod_layers_nof_re(&job.layers) stays the size function. The list of job j is
+ * prb_lists[prb_list_offset .. prb_list_offset + nof_prb - 1]; prb_lists lives where the jobs live (host lists are staged with host jobs).
+ * nof_prb = 0: no list, the PRBs of rb_mask ascending -- the bytes miphy_pdsch_modulate_layers_batch writes. A list must satisfy:
+ * prb_list_offset + nof_prb <= nof_list_entries; every entry is below grid_nof_prb, has its bit set in rb_mask and appears once; nof_prb
+ * is the number of set bits of rb_mask. A host job that breaks a rule is refused with MIPHY_EINVAL and the rule's message, nothing enqueued;
+ * a device-resident job that breaks one is skipped by the kernels before any entry is used as an address. */
+typedef struct {
+  miphy_pdsch_mod_layers_job layers; /* layers.base.rb_mask = the PRBs of the list, as before */
+  uint32_t prb_list_offset;          /* uint16 index into prb_lists */
+  uint16_t nof_prb;                  /* 0: no list -- ascending order of rb_mask */
+  uint16_t pad;
+} miphy_pdsch_mod_mapped_job;
+int miphy_pdsch_modulate_mapped_batch(miphy_ctx* ctx, const miphy_pdsch_mod_mapped_job* jobs, int jobs_on_device, uint32_t n,
+                                      const uint16_t* prb_lists /* where the jobs are; may be NULL when nof_list_entries is 0 */,
+                                      uint32_t nof_list_entries, const uint8_t* codewords /* device */, float* grid /* device cf_t */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Polar code chains  --  replace the chain of srsran::polar_code::set + polar_allocator::allocate + polar_encoder::encode
@@ -1155,6 +1201,23 @@ typedef struct {
 /* Data REs of the allocation per layer; 0 on an invalid PDU. Host function. */
 uint32_t miphy_pdsch_layers_pdu_nof_re(const miphy_pdsch_layers_pdu* pdu);
 int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsch_layers_pdu* pdus /* host */, uint32_t n, const uint8_t* tb_in /* device */,
+                                     float* grid /* device cf_t; only the mapped REs are written */, void* stream);
+
+/* PDSCH processor with the PRBs of a PDU in a mapping order of the caller's (interleaved VRB-to-PRB mapping, TS 38.211 7.3.1.6: the list
+ * miphy_vrb_to_prb_list gives). miphy_pdsch_process_layers_batch with miphy_pdsch_modulate_mapped_batch in the middle; the contract is the
+ * oracle chain orc_pdsch_encode -> orc_pdsch_modulate(the list) -> orc_dmrs_pdsch_map(rb_mask): the DM-RS does not depend on the mapping
+ * order. The list of PDU p is prb_lists[prb_list_offset .. + nof_prb - 1] (host memory) and obeys the list rule of
+ * miphy_pdsch_modulate_mapped_batch; nof_prb = 0: no list, and a batch without lists writes the bytes miphy_pdsch_process_layers_batch
+ * writes. Every PDU and every list is checked before anything is enqueued or allocated, with the limits of the layered processor. PDUs are
+ * host records; there is no prepared plan for this entry point. Not supported: two codewords, precoding. */
+typedef struct {
+  miphy_pdsch_layers_pdu layers; /* layers.base.rb_mask = the PRBs of the list */
+  uint32_t prb_list_offset;      /* uint16 index into prb_lists */
+  uint16_t nof_prb;              /* 0: no list -- ascending order of rb_mask */
+  uint16_t pad;
+} miphy_pdsch_mapped_pdu;
+int miphy_pdsch_process_mapped_batch(miphy_ctx* ctx, const miphy_pdsch_mapped_pdu* pdus /* host */, uint32_t n, const uint16_t* prb_lists /* host */,
+                                     uint32_t nof_list_entries, const uint8_t* tb_in /* device */,
                                      float* grid /* device cf_t; only the mapped REs are written */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------

@@ -2357,9 +2357,25 @@ inline void put_written_res(srsran::resource_grid_writer& grid, unsigned port, u
   }
 }
 
+/// The list rule of miphy_pdsch_modulate_mapped_batch on a PRB list in mapping order (rb_allocation::get_prb_indices) and the PRB mask of the
+/// same allocation (rb_allocation::get_prb_mask): every entry inside the mask and set in it, none twice, as many entries as set bits.
+inline bool prb_list_obeys_list_rule(const srsran::static_vector<uint16_t, srsran::MAX_RB>& list, const srsran::bounded_bitset<srsran::MAX_RB>& mask)
+{
+  srsran::bounded_bitset<srsran::MAX_RB> seen(mask.size());
+  for (uint16_t rb : list) {
+    if (rb >= mask.size() || !mask.test(rb) || seen.test(rb)) {
+      return false;
+    }
+    seen.set(rb);
+  }
+  return list.size() == mask.count();
+}
+
 /// srsran::pdsch_modulator over miphy_pdsch_modulate_batch (pdsch_modulator.h:98). One codeword on one layer, contiguous
 /// allocation -- the configurations the 23.5 software modulator handles correctly -- and, beyond it, one codeword on two to four
-/// layers (config.ports.size() layers, layer ly on port config.ports[ly]) over miphy_pdsch_modulate_layers_batch.
+/// layers (config.ports.size() layers, layer ly on port config.ports[ly]) over miphy_pdsch_modulate_layers_batch. An allocation that is
+/// not contiguous or is interleaved goes over miphy_pdsch_modulate_mapped_batch with rb_allocation::get_prb_indices as the list in
+/// mapping order (where the reference's vrb_to_prb_mapper deviates from TS 38.211 7.3.1.6).
 class pdsch_modulator_hip : public srsran::pdsch_modulator
 {
 public:
@@ -2368,7 +2384,6 @@ public:
   {
     const unsigned nlayers = config.ports.size();
     srsran_assert(nlayers >= 1 && nlayers <= 4 && codewords.size() == 1, "Only one codeword on one to four layers is supported.");
-    srsran_assert(config.freq_allocation.is_contiguous(), "Only contiguous allocations are supported.");
     const srsran::bounded_bitset<srsran::MAX_RB> prb = config.freq_allocation.get_prb_mask(config.bwp_start_rb, config.bwp_size_rb);
     const unsigned                               nprb = prb.size(), nsc = nprb * 12;
     miphy_pdsch_mod_job j = {};
@@ -2397,7 +2412,15 @@ public:
     auto* d_g  = static_cast<float*>(c->buf(1, host.size() * sizeof(srsran::cf_t)));
     c->h2d(d_cw, bits.data(), bits.size());
     c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
-    if (nlayers == 1) {
+    if (!config.freq_allocation.is_contiguous()) {
+      const srsran::static_vector<uint16_t, srsran::MAX_RB> list = config.freq_allocation.get_prb_indices(config.bwp_start_rb, config.bwp_size_rb);
+      miphy_pdsch_mod_mapped_job                            mj   = {};
+      mj.layers.base = j, mj.layers.nof_layers = nlayers, mj.prb_list_offset = 0, mj.nof_prb = list.size();
+      for (unsigned ly = 0; ly != nlayers; ++ly) {
+        mj.layers.ports[ly] = ly; // the staging grid has one port per layer
+      }
+      context::check(miphy_pdsch_modulate_mapped_batch(c->ctx, &mj, 0, 1, list.data(), list.size(), d_cw, d_g, c->stream), "pdsch_modulate_mapped");
+    } else if (nlayers == 1) {
       context::check(miphy_pdsch_modulate_batch(c->ctx, &j, 0, 1, d_cw, d_g, c->stream), "pdsch_modulate");
     } else {
       miphy_pdsch_mod_layers_job lj = {};
@@ -2474,7 +2497,9 @@ private:
 // ---------------------------------------------------------------------------------------------------------------- PDSCH processor
 /// srsran::pdsch_processor over miphy_pdsch_process_batch (pdsch_processor.h:164-166): encoding, modulation and DM-RS generation
 /// in one device pass; the transport block goes up, the written resource elements come back. A PDU of one codeword on two to four
-/// layers (pdu.ports.size() layers, layer ly and DM-RS port 1000 + ly on port pdu.ports[ly]) goes to miphy_pdsch_process_layers_batch.
+/// layers (pdu.ports.size() layers, layer ly and DM-RS port 1000 + ly on port pdu.ports[ly]) goes to miphy_pdsch_process_layers_batch, a
+/// PDU whose allocation is not contiguous or is interleaved to miphy_pdsch_process_mapped_batch with rb_allocation::get_prb_indices as
+/// its list in mapping order.
 class pdsch_processor_hip : public srsran::pdsch_processor
 {
 public:
@@ -2486,7 +2511,6 @@ public:
     const unsigned nlayers = pdu.ports.size();
     srsran_assert(nlayers >= 1 && nlayers <= 4 && pdu.codewords.size() == 1 && data.size() == 1, "Only one codeword on one to four layers is supported.");
     srsran_assert(pdu.dmrs == srsran::dmrs_type::TYPE1, "Only DM-RS Type 1 is currently supported.");
-    srsran_assert(pdu.freq_alloc.is_contiguous(), "Only contiguous allocation is currently supported.");
     const srsran::bounded_bitset<srsran::MAX_RB> prb  = pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb);
     const unsigned                               nprb = prb.size(), nsc = nprb * 12;
     miphy_pdsch_pdu p = {};
@@ -2510,7 +2534,15 @@ public:
     auto* d_g  = static_cast<float*>(c->buf(1, host.size() * sizeof(srsran::cf_t)));
     c->h2d(d_tb, data[0].data(), data[0].size());
     c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
-    if (nlayers == 1) {
+    if (!pdu.freq_alloc.is_contiguous()) {
+      const srsran::static_vector<uint16_t, srsran::MAX_RB> list = pdu.freq_alloc.get_prb_indices(pdu.bwp_start_rb, pdu.bwp_size_rb);
+      miphy_pdsch_mapped_pdu                                mp   = {};
+      mp.layers.base = p, mp.layers.nof_layers = nlayers, mp.prb_list_offset = 0, mp.nof_prb = list.size();
+      for (unsigned ly = 0; ly != nlayers; ++ly) {
+        mp.layers.ports[ly] = ly; // the staging grid has one port per layer
+      }
+      context::check(miphy_pdsch_process_mapped_batch(c->ctx, &mp, 1, list.data(), list.size(), d_tb, d_g, c->stream), "pdsch_process_mapped");
+    } else if (nlayers == 1) {
       context::check(miphy_pdsch_process_batch(c->ctx, &p, 1, d_tb, d_g, c->stream), "pdsch_process");
     } else {
       miphy_pdsch_layers_pdu lp = {};
@@ -2811,7 +2843,9 @@ public:
     require(pdu.ports.size() >= 1 && pdu.ports.size() <= 4 && pdu.codewords.size() == 1 && data.size() == 1,
             "Only one codeword on one to four layers is supported.");
     require(pdu.dmrs == srsran::dmrs_type::TYPE1, "Only DM-RS Type 1 is currently supported.");
-    require(pdu.freq_alloc.is_contiguous(), "Only contiguous allocation is currently supported.");
+    require(pdu.freq_alloc.is_contiguous() || prb_list_obeys_list_rule(pdu.freq_alloc.get_prb_indices(pdu.bwp_start_rb, pdu.bwp_size_rb),
+                                                                       pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb)),
+            "The PRB list of the allocation names a PRB twice or one outside its mask.");
     for (uint8_t port : pdu.ports) {
       require(port < nports, "Transmit port outside the resource grid.");
     }
@@ -2890,15 +2924,25 @@ private:
     const unsigned                      n = queue.size(), nsc = nprb * 12;
     std::vector<miphy_pdsch_pdu>        pdus;  // one layer
     std::vector<miphy_pdsch_layers_pdu> lpdus; // two to four layers
+    std::vector<miphy_pdsch_mapped_pdu> mpdus; // an allocation that is not contiguous or is interleaved, one to four layers ...
+    std::vector<uint16_t>               lists; // ... and their PRBs in mapping order (rb_allocation::get_prb_indices)
     std::vector<size_t>                 tb_offset(n);
     size_t                              tb_bytes = 0;
-    pdus.reserve(n), lpdus.reserve(n);
+    pdus.reserve(n), lpdus.reserve(n), mpdus.reserve(n);
     for (unsigned i = 0; i != n; ++i) {
       const srsran::pdsch_processor::pdu_t&        pdu = queue[i].pdu;
       const srsran::bounded_bitset<srsran::MAX_RB> prb = pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb);
       srsran_assert(prb.size() <= nprb, "The allocation exceeds the resource grid.");
       const unsigned nlayers = pdu.ports.size();
-      if (nlayers == 1) {
+      const bool     mapped  = !pdu.freq_alloc.is_contiguous();
+      if (mapped) {
+        const srsran::static_vector<uint16_t, srsran::MAX_RB> list = pdu.freq_alloc.get_prb_indices(pdu.bwp_start_rb, pdu.bwp_size_rb);
+        miphy_pdsch_mapped_pdu                                mp   = {};
+        mp.layers.nof_layers = nlayers, mp.prb_list_offset = lists.size(), mp.nof_prb = list.size();
+        std::copy(pdu.ports.begin(), pdu.ports.end(), mp.layers.ports);
+        lists.insert(lists.end(), list.begin(), list.end());
+        mpdus.push_back(mp);
+      } else if (nlayers == 1) {
         pdus.push_back(miphy_pdsch_pdu{});
       } else {
         miphy_pdsch_layers_pdu lp = {};
@@ -2906,7 +2950,7 @@ private:
         std::copy(pdu.ports.begin(), pdu.ports.end(), lp.ports);
         lpdus.push_back(lp);
       }
-      miphy_pdsch_pdu& p = nlayers == 1 ? pdus.back() : lpdus.back().base;
+      miphy_pdsch_pdu& p = mapped ? mpdus.back().layers.base : (nlayers == 1 ? pdus.back() : lpdus.back().base);
       p.slot_in_frame = pdu.slot.slot_index(), p.rnti = pdu.rnti, p.n_id = pdu.n_id, p.dmrs_scrambling_id = pdu.scrambling_id;
       p.tbs_lbrm_bytes = pdu.tbs_lbrm_bytes, p.tb_bytes = queue[i].data.size();
       p.ratio_pdsch_dmrs_to_sss_dB = pdu.ratio_pdsch_dmrs_to_sss_dB, p.ratio_pdsch_data_to_sss_dB = pdu.ratio_pdsch_data_to_sss_dB;
@@ -2940,6 +2984,10 @@ private:
     }
     if (!lpdus.empty()) {
       context::check(miphy_pdsch_process_layers_batch(wc->ctx, lpdus.data(), lpdus.size(), d_tb, d_g, wc->stream), "pdsch_process_layers");
+    }
+    if (!mpdus.empty()) {
+      context::check(miphy_pdsch_process_mapped_batch(wc->ctx, mpdus.data(), mpdus.size(), lists.data(), lists.size(), d_tb, d_g, wc->stream),
+                     "pdsch_process_mapped");
     }
     wc->d2h(host.data(), d_g, host.size() * sizeof(srsran::cf_t));
     wc->sync();
@@ -3665,8 +3713,9 @@ public:
   bool is_valid(const srsran::pdsch_processor::pdu_t& pdu) const override
   {
     // device path: one codeword on one to four layers (the number of ports is the number of layers) on distinct ports, DM-RS type 1,
-    // contiguous (non-interleaved) allocation, at most four reserved patterns. The reference validator stops at one layer: it judges
-    // everything else on a copy of the PDU that keeps the first port.
+    // at most four reserved patterns, and an allocation that is contiguous and not interleaved or whose PRB list in mapping order
+    // (rb_allocation::get_prb_indices) passes the list rule of miphy_pdsch_process_mapped_batch. The reference validator stops at one
+    // layer: it judges everything else on a copy of the PDU that keeps the first port.
     const unsigned nlayers = pdu.ports.size();
     if (nlayers < 1 || nlayers > 4) {
       return false;
@@ -3680,11 +3729,21 @@ public:
     }
     srsran::pdsch_processor::pdu_t one = pdu;
     one.ports.resize(1);
+    if (!pdu.freq_alloc.is_contiguous()) {
+      // The reference validator refuses these outright: the allocation is judged here (its own BWP check, then the list rule) and the
+      // rest of the PDU on a copy with one PRB in its place.
+      if (!pdu.freq_alloc.is_bwp_valid(pdu.bwp_start_rb, pdu.bwp_size_rb) ||
+          !prb_list_obeys_list_rule(pdu.freq_alloc.get_prb_indices(pdu.bwp_start_rb, pdu.bwp_size_rb),
+                                    pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb))) {
+        return false;
+      }
+      one.freq_alloc = srsran::rb_allocation::make_type1(0, 1);
+    }
     if (!ref->is_valid(one)) {
       return false;
     }
-    return pdu.codewords.size() == 1 && pdu.dmrs == srsran::dmrs_type::TYPE1 && pdu.freq_alloc.is_contiguous() &&
-           pdu.cp == srsran::cyclic_prefix::NORMAL && pdu.reserved.get_nof_entries() <= 4;
+    return pdu.codewords.size() == 1 && pdu.dmrs == srsran::dmrs_type::TYPE1 && pdu.cp == srsran::cyclic_prefix::NORMAL &&
+           pdu.reserved.get_nof_entries() <= 4;
   }
 
 private:

@@ -101,6 +101,14 @@ int    miphy_pdsch_mod_job_check(const char* who, const char* what, uint32_t i, 
 // kernels validate); max_layers = the largest nof_layers of the batch, 4 for device-resident jobs.
 int    miphy_pdsch_modulate_layers_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_layers_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
                                            const uint8_t* codewords, float* grid, hipStream_t s);
+// The list rule of miphy_pdsch_modulate_mapped_batch on the host (pdsch_mod.hip), for that entry point and for the mapped PDSCH processor: MIPHY_EINVAL
+// and the message "<who>: <what> <i>: ..." on the first rule the list of `job` breaks; a job without a list (nof_prb = 0) passes.
+int    miphy_pdsch_mod_list_check(const char* who, const char* what, uint32_t i, const miphy_pdsch_mod_mapped_job& job, const uint16_t* prb_lists,
+                                  uint32_t nof_list_entries);
+// The staging (host jobs and host lists in one region of the ring) and the two launches of miphy_pdsch_modulate_mapped_batch for jobs that passed
+// miphy_pdsch_mod_job_check and miphy_pdsch_mod_list_check, or that sit on the device with their lists.
+int    miphy_pdsch_modulate_mapped_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_mapped_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
+                                           const uint16_t* prb_lists, uint32_t nof_list_entries, const uint8_t* codewords, float* grid, hipStream_t s);
 
 // One codeblock of the transport-block level PDSCH encoder (pdsch_cb_encode.hip): assembly from the transport block, LDPC encoding and rate
 // matching in one kernel.

@@ -19,6 +19,10 @@
 // pdsch_symbol_setup and maps its elements through pdsch_layers_fast (16QAM / 256QAM on aligned codewords) or pdsch_map_elements (everything
 // else). Which REs carry data is stated once, in pdsch_keep_rule_of and pdsch_keep_mask, for the four kernels and the host's count; what a job
 // must satisfy is stated once, in PDSCH_MOD_FIELD_RULES, for the kernels' predicate and the host's messages.
+// A third entry point (miphy_pdsch_modulate_mapped_batch) takes the PRBs of a job as a list in mapping order -- the interleaved VRB-to-PRB mapping of
+// TS 38.211 7.3.1.6 (miphy_vrb_to_prb_list), or any other order; the contract is the oracle's orc_pdsch_modulate, which walks its prb_list as given. Its
+// two kernels (pdsch_seq_mapped_kernel, pdsch_mod_mapped_kernel) are the bodies of the layered ones with a list: the first holds the list to
+// PDSCH_MOD_LIST_RULES / PDSCH_MOD_LIST_ENTRY_RULES once per job, the second fills prb_of[] from it, and everything behind prb_of[] is shared.
 #include "gold_device.h"
 #include "mod_device.h"
 #include "miphy_ext.h"
@@ -131,13 +135,24 @@ struct pdsch_symbol_lds {
 };
 
 // Fills S for OFDM symbol sy of the job, every thread of the workgroup (at least one wavefront) calling; returns the data REs of the symbol.
-__device__ __forceinline__ int pdsch_symbol_setup(const miphy_pdsch_mod_job& j, int sy, pdsch_symbol_lds& S, int tid, int nt)
+// list: the nof_list (1 .. 275) allocated PRBs in mapping order, a list that passed pdsch_list_ok (the mapped kernels) -- one coalesced read of
+// at most 550 bytes into prb_of[], which keep_of[] and off_of[] then follow; null (a literal from the other kernels, so that the branch
+// folds): the PRBs of rb_mask, ascending.
+__device__ __forceinline__ int pdsch_symbol_setup(const miphy_pdsch_mod_job& j, int sy, pdsch_symbol_lds& S, int tid, int nt, const uint16_t* list = nullptr,
+                                                  int nof_list = 0)
 {
   const pdsch_keep_rule keep      = pdsch_keep_rule_of(j);
   const int             nprb_grid = j.grid_nof_prb;
   pdsch_load_masks(j, S.rbm, S.resm, tid);
+  if (list) {
+    for (int i = tid; i < nof_list; i += nt)
+      S.prb_of[i] = list[i];
+    if (tid == 0)
+      S.nprb = nof_list;
+  }
   __syncthreads();
-  build_prb_list(S.rbm, nprb_grid, 0, S.prb_of, &S.nprb, tid, nt);
+  if (!list)
+    build_prb_list(S.rbm, nprb_grid, 0, S.prb_of, &S.nprb, tid, nt);
   __syncthreads();
   const int nprb = S.nprb;
   for (int i = tid; i < nprb; i += nt)
@@ -655,6 +670,39 @@ __device__ __forceinline__ bool layers_job_ok(const miphy_pdsch_mod_layers_job& 
   return pdsch_mod_fields_ok(j.base);
 }
 
+// What the PRB list of a mapped job m must satisfy, once, for the same two readers. The rules of the list as a whole: nof_list_entries = entries of
+// the batch's list array, rbm = the five words of the job's rb_mask (the job itself on the host, the copy in LDS on the device) ...
+#define PDSCH_MOD_LIST_RULES(R)                                                                                                                        \
+  R((uint64_t)m.prb_list_offset + m.nof_prb <= nof_list_entries, "PRB list [%u, %u + %u) exceeds the %u list entries", m.prb_list_offset,             \
+    m.prb_list_offset, (unsigned)m.nof_prb, nof_list_entries)                                                                                         \
+  R((unsigned)m.nof_prb == pdsch_mask_popcount(rbm), "PRB list of %u entries for the %u PRBs of rb_mask", (unsigned)m.nof_prb, pdsch_mask_popcount(rbm))
+// ... and of its entry i, PRB e, evaluated in this order: test_and_set(e) marks e in a 5-word bitmap and returns whether it was marked before, and is
+// reached only by an e below grid_nof_prb <= 275 (PDSCH_MOD_FIELD_RULES hold). A list that passes names every PRB of rb_mask once.
+#define PDSCH_MOD_LIST_ENTRY_RULES(R)                                                                                                                  \
+  R(e < m.layers.base.grid_nof_prb, "PRB list entry %u: PRB %u outside the grid of %u PRBs", i, e, (unsigned)m.layers.base.grid_nof_prb)               \
+  R((rbm[e >> 6] >> (e & 63)) & 1ull, "PRB list entry %u: PRB %u is not in rb_mask", i, e)                                                             \
+  R(!test_and_set(e), "PRB list entry %u: PRB %u appears twice", i, e)
+
+__host__ __device__ __forceinline__ unsigned pdsch_mask_popcount(const uint64_t* rbm)
+{
+  unsigned c = 0;
+  for (int w = 0; w < 5; ++w)
+    c += (unsigned)__builtin_popcountll(rbm[w]);
+  return c;
+}
+
+#define PDSCH_RULE_HOLDS(cond, ...) &&(cond)
+__host__ __device__ __forceinline__ bool pdsch_list_ok(const miphy_pdsch_mod_mapped_job& m, uint32_t nof_list_entries, const uint64_t* rbm)
+{
+  return true PDSCH_MOD_LIST_RULES(PDSCH_RULE_HOLDS);
+}
+template <class F>
+__host__ __device__ __forceinline__ bool pdsch_list_entry_ok(const miphy_pdsch_mod_mapped_job& m, const uint64_t* rbm, unsigned i, unsigned e, F&& test_and_set)
+{
+  return true PDSCH_MOD_LIST_ENTRY_RULES(PDSCH_RULE_HOLDS);
+}
+#undef PDSCH_RULE_HOLDS
+
 // Both LFSR sequences of c(n), held as words in LDS, from `have` (>= 31) to nwords words: the word recurrences w[i] = w[i-28] ^ w[i-31] (x1) and
 // w[i] = w[i-28] ^ w[i-29] ^ w[i-30] ^ w[i-31] (x2) in their squares, as gold_x2_sequence does for x2 alone.
 __device__ __forceinline__ void gold_words_extend(uint32_t* w1, uint32_t* w2, int have, int nwords, int tid, int nt)
@@ -680,14 +728,21 @@ __device__ __forceinline__ void gold_words_extend(uint32_t* w1, uint32_t* w2, in
 // each runs the 31-word head, the word recurrences do the rest. `stride` = sequence words reserved per transmission. Chunk 0 also validates
 // the job and counts its elements: info[0..13] = elements per layer before every OFDM symbol, info[14] = elements per layer, info[15] = 1 when
 // the job is valid and its bit count is elements x L x mod.
-__global__ void __launch_bounds__(512) pdsch_seq_layers_kernel(const miphy_pdsch_mod_layers_job* __restrict__ jobs, const gold_tables* __restrict__ gt,
-                                                               uint32_t* __restrict__ seq, int* __restrict__ info_out, uint32_t stride)
+// mj: the mapped job whose layers job lj is, null (a literal, so that everything about lists folds away) in the kernel of the entry point without
+// lists. Chunk 0 of a mapped job with a list also holds the list to PDSCH_MOD_LIST_RULES and PDSCH_MOD_LIST_ENTRY_RULES -- one coalesced read of
+// the list, the duplicate test an atomicOr on a 5-word bitmap in LDS -- and clears info[15] when it breaks one: pdsch_mod_mapped_kernel uses no
+// entry of a list as an address unless info[15] is set.
+__device__ __forceinline__ void pdsch_seq_layers_body(const miphy_pdsch_mod_layers_job* __restrict__ lj, const miphy_pdsch_mod_mapped_job* __restrict__ mj,
+                                                      const uint16_t* __restrict__ prb_lists, uint32_t nof_list_entries,
+                                                      const gold_tables* __restrict__ gt, uint32_t* __restrict__ seq, int* __restrict__ info_out,
+                                                      uint32_t stride)
 {
   __shared__ uint32_t w1[PDSCH_SEQ_CHUNK], w2[PDSCH_SEQ_CHUNK];
   __shared__ uint64_t rbm[5], resm[4][5];
   __shared__ int      cnt[14];
-  const miphy_pdsch_mod_layers_job* __restrict__ lj = jobs + blockIdx.x;
-  const miphy_pdsch_mod_job* __restrict__ jp        = &lj->base;
+  __shared__ unsigned long long seen[5];
+  __shared__ int                list_bad;
+  const miphy_pdsch_mod_job* __restrict__ jp = &lj->base;
   const int      tid = threadIdx.x, nt = blockDim.x, chunk = blockIdx.y;
   const bool     ok       = layers_job_ok(*lj);
   const uint32_t nof_bits = jp->nof_bits;
@@ -700,6 +755,26 @@ __global__ void __launch_bounds__(512) pdsch_seq_layers_kernel(const miphy_pdsch
       return;
     }
     pdsch_count_symbols(*jp, rbm, resm, cnt, tid, nt);
+    bool list_ok = true;
+    if (mj && mj->nof_prb != 0) {
+      const miphy_pdsch_mod_mapped_job& m = *mj;
+      list_ok = pdsch_list_ok(m, nof_list_entries, rbm); // (uniform: the entries are read only where the whole list lies inside the array)
+      if (tid < 5)
+        seen[tid] = 0;
+      if (tid == 5)
+        list_bad = 0;
+      __syncthreads();
+      if (list_ok) {
+        const uint16_t* list = prb_lists + m.prb_list_offset;
+        for (unsigned i = tid; i < m.nof_prb; i += nt) {
+          const unsigned e = list[i];
+          if (!pdsch_list_entry_ok(m, rbm, i, e, [&](unsigned q) { return (atomicOr(&seen[q >> 6], 1ull << (q & 63)) >> (q & 63)) & 1ull; }))
+            list_bad = 1;
+        }
+      }
+      __syncthreads();
+      list_ok = list_ok && !list_bad;
+    }
     if (tid == 0) {
       int run = 0;
       for (int s = 0; s < 14; ++s) {
@@ -707,7 +782,7 @@ __global__ void __launch_bounds__(512) pdsch_seq_layers_kernel(const miphy_pdsch
         run += cnt[s];
       }
       info[14] = run;
-      info[15] = ((uint64_t)run * lj->nof_layers * jp->mod == nof_bits) ? 1 : 0;
+      info[15] = (list_ok && (uint64_t)run * lj->nof_layers * jp->mod == nof_bits) ? 1 : 0;
     }
   }
   if (!ok || !fits)
@@ -728,22 +803,35 @@ __global__ void __launch_bounds__(512) pdsch_seq_layers_kernel(const miphy_pdsch
     o[i] = w1[i] ^ w2[i];
 }
 
-__global__ void __launch_bounds__(256) pdsch_mod_layers_kernel(const miphy_pdsch_mod_layers_job* __restrict__ jobs, const uint8_t* __restrict__ cw_base,
-                                                               float2* __restrict__ grid, const uint32_t* __restrict__ seq_base,
-                                                               const int* __restrict__ info_base, uint32_t stride)
+__global__ void __launch_bounds__(512) pdsch_seq_layers_kernel(const miphy_pdsch_mod_layers_job* __restrict__ jobs, const gold_tables* __restrict__ gt,
+                                                               uint32_t* __restrict__ seq, int* __restrict__ info_out, uint32_t stride)
+{
+  pdsch_seq_layers_body(jobs + blockIdx.x, nullptr, nullptr, 0, gt, seq, info_out, stride);
+}
+
+__global__ void __launch_bounds__(512) pdsch_seq_mapped_kernel(const miphy_pdsch_mod_mapped_job* __restrict__ jobs, const uint16_t* __restrict__ prb_lists,
+                                                               uint32_t nof_list_entries, const gold_tables* __restrict__ gt, uint32_t* __restrict__ seq,
+                                                               int* __restrict__ info_out, uint32_t stride)
+{
+  pdsch_seq_layers_body(&jobs[blockIdx.x].layers, jobs + blockIdx.x, prb_lists, nof_list_entries, gt, seq, info_out, stride);
+}
+
+// list: the job's PRBs in mapping order (nof_list of them, pdsch_mod_mapped_kernel), null: rb_mask ascending.
+__device__ __forceinline__ void pdsch_mod_layers_body(const miphy_pdsch_mod_layers_job* __restrict__ lj, const uint16_t* list, int nof_list,
+                                                      const uint8_t* __restrict__ cw_base, float2* __restrict__ grid, const uint32_t* __restrict__ seq_base,
+                                                      const int* __restrict__ info_base, uint32_t stride)
 {
   __shared__ pdsch_symbol_lds S;
-  const miphy_pdsch_mod_layers_job* __restrict__ lj = jobs + blockIdx.x;
-  const miphy_pdsch_mod_job* __restrict__ jp        = &lj->base;
+  const miphy_pdsch_mod_job* __restrict__ jp = &lj->base;
   const int* info = info_base + (size_t)blockIdx.x * PDSCH_LAYERS_INFO;
   const int  sy = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
-  if (!info[15]) // invalid job (pdsch_seq_layers_kernel): skipped
+  if (!info[15]) // invalid job or list (pdsch_seq_layers_body): skipped
     return;
   const int start_symbol = jp->start_symbol, nof_symbols = jp->nof_symbols;
   if (sy < start_symbol || sy >= start_symbol + nof_symbols)
     return;
   const int prefix = info[sy]; // elements per layer of the transmission in earlier symbols
-  if (pdsch_symbol_setup(*jp, sy, S, tid, nt) == 0)
+  if (pdsch_symbol_setup(*jp, sy, S, tid, nt, list, nof_list) == 0)
     return;
   const int       mod = jp->mod, L = lj->nof_layers;
   const uint32_t* seq = seq_base + (size_t)blockIdx.x * stride;
@@ -771,6 +859,25 @@ __global__ void __launch_bounds__(256) pdsch_mod_layers_kernel(const miphy_pdsch
     return;
   }
   pdsch_map_elements(S, L, mod, prefix, seq, cw, g, scale, scaling, tid, nt);
+}
+
+__global__ void __launch_bounds__(256) pdsch_mod_layers_kernel(const miphy_pdsch_mod_layers_job* __restrict__ jobs, const uint8_t* __restrict__ cw_base,
+                                                               float2* __restrict__ grid, const uint32_t* __restrict__ seq_base,
+                                                               const int* __restrict__ info_base, uint32_t stride)
+{
+  pdsch_mod_layers_body(jobs + blockIdx.x, nullptr, 0, cw_base, grid, seq_base, info_base, stride);
+}
+
+// The mapping kernel of miphy_pdsch_modulate_mapped_batch: pdsch_mod_layers_kernel with prb_of[] filled from the job's list. Only the order in which
+// prb_of[] is filled differs, so pdsch_layers_fast and pdsch_map_elements serve it as they are. The list was held to its rules by chunk 0 of
+// pdsch_seq_mapped_kernel (info[15]); a job with nof_prb = 0 has none.
+__global__ void __launch_bounds__(256) pdsch_mod_mapped_kernel(const miphy_pdsch_mod_mapped_job* __restrict__ jobs, const uint16_t* __restrict__ prb_lists,
+                                                               const uint8_t* __restrict__ cw_base, float2* __restrict__ grid,
+                                                               const uint32_t* __restrict__ seq_base, const int* __restrict__ info_base, uint32_t stride)
+{
+  const miphy_pdsch_mod_mapped_job* __restrict__ mj = jobs + blockIdx.x;
+  const int nof_list = mj->nof_prb;
+  pdsch_mod_layers_body(&mj->layers, nof_list ? prb_lists + mj->prb_list_offset : nullptr, nof_list, cw_base, grid, seq_base, info_base, stride);
 }
 
 uint32_t host_nof_re(const miphy_pdsch_mod_job& j)
@@ -905,6 +1012,119 @@ int miphy_pdsch_modulate_layers_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_la
   hipLaunchKernelGGL(pdsch_seq_layers_kernel, dim3(n, 2 * max_layers), dim3(512), 0, s, (const miphy_pdsch_mod_layers_job*)d_jobs, gt, (uint32_t*)seq, info, stride);
   hipLaunchKernelGGL(pdsch_mod_layers_kernel, dim3(n, 14), dim3(256), 0, s, (const miphy_pdsch_mod_layers_job*)d_jobs, codewords, (float2*)grid,
                      (const uint32_t*)seq, (const int*)info, stride);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- PDSCH modulator, PRB lists in mapping order
+extern "C" int miphy_vrb_to_prb_list(const miphy_vrb_to_prb* map, const uint64_t vrb_mask[5], uint16_t* prb_list, uint32_t cap, uint32_t* nof_prb,
+                                     uint64_t prb_mask[5])
+{
+  MIPHY_REQUIRE(map && vrb_mask && nof_prb && (prb_list || cap == 0), "miphy_vrb_to_prb_list: null argument");
+  const unsigned L = map->bundle_size, N = map->region_size_rb;
+  MIPHY_REQUIRE(L == 0 || L == 2 || L == 4, "vrb_to_prb_list: invalid bundle size %u (0, 2 or 4)", L);
+  MIPHY_REQUIRE(N >= 1 && N <= 275, "vrb_to_prb_list: invalid region size %u (1..275)", N);
+  MIPHY_REQUIRE((unsigned)map->first_prb + N <= 275, "vrb_to_prb_list: the region [%u, %u + %u) exceeds 275 PRBs", (unsigned)map->first_prb,
+                (unsigned)map->first_prb, N);
+  unsigned count = 0;
+  for (unsigned n = 0; n < 320; ++n)
+    if ((vrb_mask[n >> 6] >> (n & 63)) & 1ull) {
+      MIPHY_REQUIRE(n < N, "vrb_to_prb_list: VRB %u outside the region of %u", n, N);
+      ++count;
+    }
+  *nof_prb = count;
+  MIPHY_REQUIRE(count <= cap, "vrb_to_prb_list: %u PRBs for a list of %u", count, cap);
+  // TS 38.211 7.3.1.6: bundles of L on a raster aligned to align_rb, the last one in place, the others through the 2 x C block interleaver
+  const unsigned s = L ? map->align_rb % L : 0, nb = L ? (N + s + L - 1) / L : 0, C = nb / 2;
+  uint64_t       set[5] = {};
+  unsigned       i      = 0;
+  for (unsigned n = 0; n < N; ++n) {
+    if (!((vrb_mask[n >> 6] >> (n & 63)) & 1ull))
+      continue;
+    unsigned prb = map->first_prb + n;
+    if (L) {
+      const unsigned j = (n + s) / L, f = j == nb - 1 ? j : (j % 2) * C + j / 2;
+      prb              = map->first_prb + f * L + (n + s) % L - s;
+    }
+    prb_list[i++] = (uint16_t)prb;
+    set[prb >> 6] |= 1ull << (prb & 63);
+  }
+  for (int w = 0; prb_mask && w < 5; ++w)
+    prb_mask[w] = set[w];
+  return MIPHY_OK;
+}
+
+int miphy_pdsch_mod_list_check(const char* who, const char* what, uint32_t idx, const miphy_pdsch_mod_mapped_job& m, const uint16_t* prb_lists,
+                               uint32_t nof_list_entries)
+{
+  if (m.nof_prb == 0)
+    return MIPHY_OK;
+  const uint64_t* rbm = m.layers.base.rb_mask;
+  MIPHY_REQUIRE(prb_lists, "%s: %s %u: a PRB list and no list array", who, what, idx);
+#define PDSCH_RULE_REQUIRE(cond, fmt, ...) MIPHY_REQUIRE(cond, "%s: %s %u: " fmt, who, what, idx, ##__VA_ARGS__);
+  PDSCH_MOD_LIST_RULES(PDSCH_RULE_REQUIRE)
+  uint64_t   seen[5]      = {};
+  const auto test_and_set = [&seen](unsigned q) {
+    const bool was = (seen[q >> 6] >> (q & 63)) & 1ull;
+    seen[q >> 6] |= 1ull << (q & 63);
+    return was;
+  };
+  for (unsigned i = 0; i < m.nof_prb; ++i) {
+    const unsigned e = prb_lists[m.prb_list_offset + i];
+    PDSCH_MOD_LIST_ENTRY_RULES(PDSCH_RULE_REQUIRE)
+  }
+#undef PDSCH_RULE_REQUIRE
+  return MIPHY_OK;
+}
+
+extern "C" int miphy_pdsch_modulate_mapped_batch(miphy_ctx* ctx, const miphy_pdsch_mod_mapped_job* jobs, int jobs_on_device, uint32_t n, const uint16_t* prb_lists,
+                                                 uint32_t nof_list_entries, const uint8_t* codewords, float* grid, void* stream)
+{
+  MIPHY_REQUIRE(ctx && jobs && codewords && grid && (prb_lists || nof_list_entries == 0), "miphy_pdsch_modulate_mapped_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "pdsch_modulate_mapped: batch too large (max 65535 transmissions per call)");
+  uint32_t max_layers = 4; // device-resident jobs: the kernels validate them and their lists, the scratch is sized for the most they may ask
+  if (!jobs_on_device) {
+    max_layers = 1;
+    for (uint32_t i = 0; i < n; ++i) {
+      const miphy_pdsch_mod_layers_job& lj = jobs[i].layers;
+      int rc = miphy_pdsch_mod_job_check("pdsch_modulate_mapped", "job", i, lj.base, lj.nof_layers, lj.ports, 0);
+      if (rc || (rc = miphy_pdsch_mod_list_check("pdsch_modulate_mapped", "job", i, jobs[i], prb_lists, nof_list_entries)))
+        return rc;
+      max_layers = lj.nof_layers > max_layers ? lj.nof_layers : max_layers;
+    }
+  }
+  return miphy_pdsch_modulate_mapped_enqueue(ctx, jobs, jobs_on_device, n, max_layers, prb_lists, nof_list_entries, codewords, grid, (hipStream_t)stream);
+}
+
+int miphy_pdsch_modulate_mapped_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_mapped_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
+                                        const uint16_t* prb_lists, uint32_t nof_list_entries, const uint8_t* codewords, float* grid, hipStream_t s)
+{
+  const gold_tables* gt = nullptr;
+  int                rc = miphy_get_gold_tables(ctx, &gt);
+  if (rc)
+    return rc;
+  const miphy_pdsch_mod_mapped_job* d_jobs  = jobs;
+  const uint16_t*                   d_lists = prb_lists;
+  if (!jobs_on_device) { // host jobs and host lists: one region of the staging ring, one upload
+    device_image img;
+    const auto   js = img.put(jobs, (size_t)n);
+    const auto   ls = img.put(prb_lists, (size_t)nof_list_entries);
+    const void*  base = nullptr;
+    if ((rc = miphy_image_to_ring(ctx, img, s, &base)))
+      return rc;
+    d_jobs = js.at(base), d_lists = ls.at(base);
+  }
+  // scratch: as miphy_pdsch_modulate_layers_enqueue lays it out
+  const uint32_t stride = max_layers * (uint32_t)PDSCH_SEQ_STRIDE;
+  void*          seq    = nullptr;
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, (size_t)n * stride * sizeof(uint32_t) + (size_t)n * PDSCH_LAYERS_INFO * sizeof(int), &seq)))
+    return rc;
+  int* info = reinterpret_cast<int*>(static_cast<uint8_t*>(seq) + (size_t)n * stride * sizeof(uint32_t));
+  hipLaunchKernelGGL(pdsch_seq_mapped_kernel, dim3(n, 2 * max_layers), dim3(512), 0, s, d_jobs, d_lists, nof_list_entries, gt, (uint32_t*)seq, info, stride);
+  hipLaunchKernelGGL(pdsch_mod_mapped_kernel, dim3(n, 14), dim3(256), 0, s, d_jobs, d_lists, codewords, (float2*)grid, (const uint32_t*)seq, (const int*)info,
+                     stride);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }

@@ -120,6 +120,32 @@ extern "C" uint32_t miphy_pdsch_layers_pdu_nof_re(const miphy_pdsch_layers_pdu* 
   return miphy_pdsch_pdu_nof_re(&pdu->base);
 }
 
+namespace {
+// derive_pdsch_jobs for PDU i of a layered batch, with the layered modulator job and the encoder's limits: what miphy_pdsch_process_layers_batch and
+// miphy_pdsch_process_mapped_batch both ask of a PDU. max_layers: the largest nof_layers so far.
+int derive_layers_jobs(const char* who, uint32_t i, const miphy_pdsch_layers_pdu& p, miphy_pdsch_tb_desc& t, miphy_pdsch_mod_layers_job& lj, miphy_dmrs_pdsch_job& d,
+                       size_t& cw_bytes, uint32_t& max_layers)
+{
+  const uint32_t L = p.nof_layers;
+  lj               = {};
+  if (int rc = derive_pdsch_jobs(who, i, p.base, L, p.ports, t, lj.base, d, cw_bytes))
+    return rc;
+  lj.nof_layers = (uint8_t)L;
+  for (uint32_t ly = 0; ly < 4; ++ly)
+    lj.ports[ly] = p.ports[ly];
+  max_layers = L > max_layers ? L : max_layers;
+  // what the encoder accepts (sch.hip, ldpc_segmenter_impl.cpp:104-141): at most 52 codeblocks, none of them empty
+  const uint32_t nre = t.nof_ch_symbols / L; // REs per layer
+  const uint64_t tbs = (uint64_t)p.base.tb_bytes * 8, B = tbs + (tbs <= 3824 ? 16 : 24), Kcb = p.base.bg == 1 ? 8448 : 3840;
+  const uint64_t ncb = B <= Kcb ? 1 : (B + Kcb - 24 - 1) / (Kcb - 24);
+  MIPHY_REQUIRE(p.base.tb_bytes > 0 && ncb <= 52, "%s: PDU %u: transport block of %u bytes outside what the encoder accepts (1 .. %u bytes on base graph %u)", who, i,
+                p.base.tb_bytes, p.base.bg == 1 ? 54753u : 24801u, (unsigned)p.base.bg);
+  MIPHY_REQUIRE(p.base.rv <= 3, "%s: PDU %u: invalid redundancy version", who, i);
+  MIPHY_REQUIRE(nre >= ncb, "%s: PDU %u: %u REs per layer cannot carry %u codeblocks", who, i, nre, (unsigned)ncb);
+  return MIPHY_OK;
+}
+} // namespace
+
 extern "C" int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsch_layers_pdu* pdus, uint32_t n, const uint8_t* tb_in, float* grid, void* stream)
 {
   MIPHY_REQUIRE(ctx && pdus && tb_in && grid, "miphy_pdsch_process_layers_batch: null argument");
@@ -133,25 +159,9 @@ extern "C" int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsc
   size_t                                  cw_bytes   = 0;
   uint32_t                                max_layers = 1;
   int                                     rc;
-  for (uint32_t i = 0; i < n; ++i) {
-    const miphy_pdsch_layers_pdu& p = pdus[i];
-    const uint32_t                L = p.nof_layers;
-    lj[i] = {};
-    if ((rc = derive_pdsch_jobs("pdsch_process_layers", i, p.base, L, p.ports, tb[i], lj[i].base, dj[i], cw_bytes)))
+  for (uint32_t i = 0; i < n; ++i)
+    if ((rc = derive_layers_jobs("pdsch_process_layers", i, pdus[i], tb[i], lj[i], dj[i], cw_bytes, max_layers)))
       return rc;
-    lj[i].nof_layers = (uint8_t)L;
-    for (uint32_t ly = 0; ly < 4; ++ly)
-      lj[i].ports[ly] = p.ports[ly];
-    max_layers = L > max_layers ? L : max_layers;
-    // what the encoder accepts (sch.hip, ldpc_segmenter_impl.cpp:104-141): at most 52 codeblocks, none of them empty
-    const uint32_t nre = tb[i].nof_ch_symbols / L; // REs per layer
-    const uint64_t tbs = (uint64_t)p.base.tb_bytes * 8, B = tbs + (tbs <= 3824 ? 16 : 24), Kcb = p.base.bg == 1 ? 8448 : 3840;
-    const uint64_t ncb = B <= Kcb ? 1 : (B + Kcb - 24 - 1) / (Kcb - 24);
-    MIPHY_REQUIRE(p.base.tb_bytes > 0 && ncb <= 52, "pdsch_process_layers: PDU %u: transport block of %u bytes outside what the encoder accepts (1 .. %u bytes on base graph %u)",
-                  i, p.base.tb_bytes, p.base.bg == 1 ? 54753u : 24801u, (unsigned)p.base.bg);
-    MIPHY_REQUIRE(p.base.rv <= 3, "pdsch_process_layers: PDU %u: invalid redundancy version", i);
-    MIPHY_REQUIRE(nre >= ncb, "pdsch_process_layers: PDU %u: %u REs per layer cannot carry %u codeblocks", i, nre, (unsigned)ncb);
-  }
   void* work = nullptr; // codewords (one bit per byte) in a workspace of the context
   if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, cw_bytes + 64, &work)))
     return rc;
@@ -159,6 +169,41 @@ extern "C" int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsc
   if ((rc = miphy_pdsch_encode_batch(ctx, tb.data(), n, tb_in, d_cw, s)))
     return rc;
   if ((rc = miphy_pdsch_modulate_layers_enqueue(ctx, lj.data(), 0, n, max_layers, d_cw, grid, s))) // (the jobs passed miphy_pdsch_mod_job_check in derive_pdsch_jobs)
+    return rc;
+  return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s);
+}
+
+// ---- PRB lists in mapping order (interleaved VRB-to-PRB mapping): the same composition with the mapped modulator in the middle. The DM-RS job takes
+// rb_mask, as derive_pdsch_jobs fills it: the DM-RS does not depend on the mapping order.
+extern "C" int miphy_pdsch_process_mapped_batch(miphy_ctx* ctx, const miphy_pdsch_mapped_pdu* pdus, uint32_t n, const uint16_t* prb_lists,
+                                                uint32_t nof_list_entries, const uint8_t* tb_in, float* grid, void* stream)
+{
+  MIPHY_REQUIRE(ctx && pdus && tb_in && grid && (prb_lists || nof_list_entries == 0), "miphy_pdsch_process_mapped_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "pdsch_process_mapped: at most 65535 PDUs per call");
+  hipStream_t                             s = (hipStream_t)stream;
+  std::vector<miphy_pdsch_tb_desc>        tb(n);
+  std::vector<miphy_dmrs_pdsch_job>       dj(n);
+  std::vector<miphy_pdsch_mod_mapped_job> mj(n);
+  size_t                                  cw_bytes   = 0;
+  uint32_t                                max_layers = 1;
+  int                                     rc;
+  for (uint32_t i = 0; i < n; ++i) {
+    mj[i] = {};
+    if ((rc = derive_layers_jobs("pdsch_process_mapped", i, pdus[i].layers, tb[i], mj[i].layers, dj[i], cw_bytes, max_layers)))
+      return rc;
+    mj[i].prb_list_offset = pdus[i].prb_list_offset, mj[i].nof_prb = pdus[i].nof_prb;
+    if ((rc = miphy_pdsch_mod_list_check("pdsch_process_mapped", "PDU", i, mj[i], prb_lists, nof_list_entries)))
+      return rc;
+  }
+  void* work = nullptr; // codewords (one bit per byte) in a workspace of the context
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, cw_bytes + 64, &work)))
+    return rc;
+  uint8_t* d_cw = static_cast<uint8_t*>(work);
+  if ((rc = miphy_pdsch_encode_batch(ctx, tb.data(), n, tb_in, d_cw, s)))
+    return rc;
+  if ((rc = miphy_pdsch_modulate_mapped_enqueue(ctx, mj.data(), 0, n, max_layers, prb_lists, nof_list_entries, d_cw, grid, s)))
     return rc;
   return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s);
 }

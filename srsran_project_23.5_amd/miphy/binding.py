@@ -99,6 +99,9 @@ def lib():
         l.miphy_pdsch_layers_pdu_nof_re.argtypes = [C.c_void_p]
         l.miphy_pdsch_layers_pdu_nof_re.restype = C.c_uint32
         l.miphy_pdsch_process_layers_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.miphy_vrb_to_prb_list.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        l.miphy_pdsch_modulate_mapped_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.miphy_pdsch_process_mapped_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         l.miphy_ofh_iq_decompress_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         l.miphy_ofh_iq_compress_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         l.miphy_pdcch_process_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -276,6 +279,34 @@ def pdsch_layers_pdu_nof_re(pdu):
     """Data REs per layer of one PdschLayersPdu record (host computation in the library); 0 on an invalid PDU."""
     a = np.ascontiguousarray(np.asarray(pdu, dtype=PdschLayersPdu).reshape(1))
     return int(lib().miphy_pdsch_layers_pdu_nof_re(a.ctypes.data_as(C.c_void_p)))
+
+
+# Mirror miphy_pdsch_mod_mapped_job and miphy_pdsch_mapped_pdu: the layered records plus the place of the PRB list (mapping order) in the batch's
+# uint16 list array; nof_prb = 0: no list, rb_mask ascending.
+PdschModMappedJob = np.dtype([("layers", PdschModLayersJob), ("prb_list_offset", np.uint32), ("nof_prb", np.uint16), ("pad", np.uint16)], align=True)
+assert PdschModMappedJob.itemsize == 296 and PdschModMappedJob.fields["prb_list_offset"][1] == 288 and PdschModMappedJob.fields["nof_prb"][1] == 292
+PdschMappedPdu = np.dtype([("layers", PdschLayersPdu), ("prb_list_offset", np.uint32), ("nof_prb", np.uint16), ("pad", np.uint16)], align=True)
+assert PdschMappedPdu.itemsize == 320 and PdschMappedPdu.fields["prb_list_offset"][1] == 312 and PdschMappedPdu.fields["nof_prb"][1] == 316
+# Mirrors miphy_vrb_to_prb.
+VrbToPrb = np.dtype([("bundle_size", np.uint8), ("pad", np.uint8), ("align_rb", np.uint16), ("region_size_rb", np.uint16), ("first_prb", np.uint16)], align=True)
+assert VrbToPrb.itemsize == 8
+
+
+def vrb_to_prb_list(bundle_size, align_rb, region_size_rb, first_prb, vrbs=None, cap=None):
+    """VRB-to-PRB mapping of TS 38.211 7.3.1.6 (miphy_vrb_to_prb_list, host computation in the library): the PRBs of the VRBs `vrbs` (any iterable
+    of VRB numbers below 320; None: all of the region) in ascending VRB order, which is the mapping order of the mapped PDSCH entry points.
+    Returns (uint16 list, the five words of its PRB mask). cap: entries the list may hold (default: 275). RuntimeError with "miphy error -1"
+    where the library returns MIPHY_EINVAL."""
+    m = np.zeros(1, dtype=VrbToPrb)
+    m[0]["bundle_size"], m[0]["align_rb"], m[0]["region_size_rb"], m[0]["first_prb"] = bundle_size, align_rb, region_size_rb, first_prb
+    vrb_mask = np.zeros(5, np.uint64)
+    for v in (range(min(int(region_size_rb), 320)) if vrbs is None else vrbs):
+        vrb_mask[int(v) >> 6] |= np.uint64(1) << np.uint64(int(v) & 63)
+    cap = 275 if cap is None else int(cap)
+    out, n, pm = np.zeros(max(cap, 1), np.uint16), C.c_uint32(0), np.zeros(5, np.uint64)
+    check(lib().miphy_vrb_to_prb_list(m.ctypes.data_as(C.c_void_p), vrb_mask.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), cap, C.byref(n),
+                                      pm.ctypes.data_as(C.c_void_p)))
+    return out[:n.value].copy(), pm
 
 
 # Mirrors miphy_csi_rs_job.
@@ -625,6 +656,30 @@ class Context:
         assert isinstance(pdus, np.ndarray) and pdus.dtype == PdschLayersPdu
         pdus = np.ascontiguousarray(pdus)
         check(lib().miphy_pdsch_process_layers_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, _dptr(tb_in), _dptr(grid), _stream_ptr(stream)))
+
+    def pdsch_modulate_mapped_batch(self, jobs, prb_lists, codewords, grid, stream=None):
+        """pdsch_modulate_layers_batch with the PRBs of each job in the mapping order of its list (interleaved VRB-to-PRB mapping: vrb_to_prb_list).
+        jobs and prb_lists live in the same place: a PdschModMappedJob array with a uint16 numpy array (None: no lists), or uint8 and int16 /
+        uint16 device tensors holding the same bytes."""
+        import torch
+        jobs, n, ptr, on_dev = self._descs(jobs, PdschModMappedJob)
+        if on_dev:
+            assert prb_lists is None or prb_lists.dtype in (torch.int16, torch.uint16)
+            lptr, nl = (_dptr(prb_lists), prb_lists.numel()) if prb_lists is not None and prb_lists.numel() else (None, 0)
+        else:
+            prb_lists = np.zeros(0, np.uint16) if prb_lists is None else np.ascontiguousarray(prb_lists)
+            assert prb_lists.dtype == np.uint16
+            lptr, nl = (C.c_void_p(prb_lists.ctypes.data), prb_lists.size) if prb_lists.size else (None, 0)
+        check(lib().miphy_pdsch_modulate_mapped_batch(self.h, ptr, on_dev, n, lptr, nl, _dptr(codewords), _dptr(grid), _stream_ptr(stream)))
+
+    def pdsch_process_mapped_batch(self, pdus, prb_lists, tb_in, grid, stream=None):
+        """pdsch_process_layers_batch for PDUs whose PRBs are mapped in the order of their lists (host descriptors, host uint16 lists or None)."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PdschMappedPdu
+        pdus = np.ascontiguousarray(pdus)
+        prb_lists = np.zeros(0, np.uint16) if prb_lists is None else np.ascontiguousarray(prb_lists)
+        assert prb_lists.dtype == np.uint16
+        lptr, nl = (C.c_void_p(prb_lists.ctypes.data), prb_lists.size) if prb_lists.size else (None, 0)
+        check(lib().miphy_pdsch_process_mapped_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, lptr, nl, _dptr(tb_in), _dptr(grid), _stream_ptr(stream)))
 
     def csi_rs_map_batch(self, jobs, grid, stream=None):
         jobs, n, ptr, on_dev = self._descs(jobs, CsiRsJob)

@@ -11,7 +11,11 @@ of --batch transmissions per call, one stream, calls back to back between two de
   3/4 of the codeword, capped at the encoder's 52 codeblocks of base graph 1 (54 753 bytes): the code rate falls with L and is printed.
 Every figure is the median of --reps repetitions of --iters calls, the variants alternating; the spread (min .. max) is printed with it. One
 JSON line per variant. There is no CPU path: without a device this fails.
-Run:  python tools/pdsch_layers_throughput.py [--batch N] [--iters N] [--reps R] [--mod 1|2|4|6|8]"""
+- --mapping ascending | interleaved2 | interleaved4 times, instead of the above, miphy_pdsch_modulate_mapped_batch next to
+  miphy_pdsch_modulate_layers_batch (the yardstick) at L = 1, 2, 4 with device-resident jobs: without lists (the same bytes) and with every job's
+  PRBs in the interleaved order of TS 38.211 7.3.1.6 at bundle size 2 or 4 (miphy_vrb_to_prb_list). Kernel times proper:
+  rocprofv3 --kernel-trace --stats -d OUT -- python tools/pdsch_layers_throughput.py --mapping interleaved2 --trace --reps 2
+Run:  python tools/pdsch_layers_throughput.py [--batch N] [--iters N] [--reps R] [--mod 1|2|4|6|8] [--mapping M [--trace]]"""
 import argparse
 import json
 import os
@@ -91,17 +95,56 @@ def measure(fns, iters, reps):
     return [(float(np.median(v)), float(min(v)), float(max(v))) for v in t]
 
 
+def mapped_section(ctx, a, grid, gen):
+    """--mapping: per L the layered entry point (the yardstick of the session), the mapped entry point without lists (nof_prb = 0: the same bytes)
+    and, unless the mapping is "ascending", the mapped entry point with every job's list in the interleaved order of TS 38.211 7.3.1.6 at bundle
+    size 2 or 4 (every job its own copy of the list) -- device-resident jobs and lists, the three alternating."""
+    n, mod = a.batch, a.mod
+    bundle = {"ascending": 0, "interleaved2": 2, "interleaved4": 4}[a.mapping]
+    fns, meta = [], []
+    for L in (1, 2, 4):
+        jobs, nre = mod_jobs(n, L, True, mod)
+        cw = torch.randint(0, 2, (n * nre * L * mod,), dtype=torch.uint8, device="cuda", generator=gen)
+        d_jobs = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
+        fns.append(lambda j=d_jobs, cw=cw: ctx.pdsch_modulate_layers_batch(j, cw, grid))
+        meta.append(("layers_entry", "ascending", L, nre))
+        for mapping in ([] if a.trace and bundle else ["ascending"]) + ([a.mapping] if bundle else []):
+            mj = np.zeros(n, dtype=miphy.PdschModMappedJob)
+            mj["layers"] = jobs
+            lists = None
+            if mapping != "ascending":
+                one = miphy.vrb_to_prb_list(bundle, 0, NPRB, 0)[0]
+                mj["prb_list_offset"], mj["nof_prb"] = np.arange(n) * one.size, one.size
+                lists = torch.from_numpy(np.tile(one, n).view(np.int16)).cuda()
+            d_mj = torch.from_numpy(mj.view(np.uint8).copy()).cuda()
+            fns.append(lambda j=d_mj, ls=lists, cw=cw: ctx.pdsch_modulate_mapped_batch(j, ls, cw, grid))
+            meta.append(("mapped_entry", mapping, L, nre))
+    for (name, mapping, L, nre), (us, lo, hi) in zip(meta, measure(fns, a.iters, a.reps)):
+        mapped = n * nre * L
+        print(json.dumps({"what": "modulate", "entry": name, "mapping": mapping, "jobs": "device", "layers": L, "mod": mod, "batch": n, "re_per_layer": nre,
+                          "us_per_call": round(us, 2), "us_per_call_spread": [round(lo, 2), round(hi, 2)], "ps_per_re_layer": round(us * 1e6 / mapped, 2),
+                          "store_GBps": round(mapped * 8 / us * 1e-3, 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--mod", type=int, default=8, choices=(1, 2, 4, 6, 8), help="bits per symbol")
+    ap.add_argument("--mapping", choices=("ascending", "interleaved2", "interleaved4"), default=None,
+                    help="time miphy_pdsch_modulate_mapped_batch next to miphy_pdsch_modulate_layers_batch instead (device jobs, L = 1, 2, 4)")
+    ap.add_argument("--trace", action="store_true",
+                    help="with --mapping interleaved2 / interleaved4: leave out the mapped entry point without lists, so that a kernel trace of the run "
+                         "holds pdsch_mod_mapped_kernel at that mapping alone, next to pdsch_mod_layers_kernel")
     a = ap.parse_args()
     n, mod = a.batch, a.mod
     ctx = miphy.Context(0)
     gen = torch.Generator(device="cuda").manual_seed(1)
     grid = torch.zeros(n * 4 * 14 * NSC, dtype=torch.complex64, device="cuda")
+    if a.mapping is not None:
+        mapped_section(ctx, a, grid, gen)
+        return
     variants = [("one_layer_entry", 1, False), ("layers_entry", 1, True), ("layers_entry", 2, True), ("layers_entry", 4, True)]
 
     # ---- modulator alone
