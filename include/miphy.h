@@ -500,12 +500,13 @@ int miphy_dmrs_pdsch_map_batch(miphy_ctx* ctx, const miphy_dmrs_pdsch_job* jobs,
 
 /* PDSCH modulator, one codeword on 1..4 layers (beyond the 23.5 reference; the contract is the oracle's orc_pdsch_modulate). Layer
  * mapping of TS 38.211 7.3.1.3, x^(ly)(i) = d(L i + ly): the resource element of rank i carries codeword symbol L i + ly on grid port
- * ports[ly]. No precoding. Everything else as miphy_pdsch_modulate_batch: same scrambling, constellations, scaling and RE selection, only
+ * ports[ly], as it is. Everything else as miphy_pdsch_modulate_batch: same scrambling, constellations, scaling and RE selection, only
  * the mapped REs of the named ports are written. The pi/2-BPSK rotation follows the parity of the codeword symbol L i + ly. A batch of
  * one-layer jobs writes the bytes miphy_pdsch_modulate_batch writes. Host jobs are checked before anything is enqueued (1..4 layers,
  * distinct ports below 16, nof_bits = REs x L x mod and the rules of the one-layer entry point); a device-resident job that breaks a
  * rule is skipped by the kernels. PRBs are mapped in ascending order here; any other order, the interleaved VRB-to-PRB mapping of TS 38.211
- * 7.3.1.6 among them, goes through miphy_pdsch_modulate_mapped_batch below. Not supported: two codewords (5..8 layers), precoding matrices. */
+ * 7.3.1.6 among them, goes through miphy_pdsch_modulate_mapped_batch below, precoding matrices through miphy_pdsch_modulate_precoded_batch.
+ * Not supported: two codewords (5..8 layers). */
 typedef struct {
   miphy_pdsch_mod_job base; /* base.port is ignored; base.nof_bits = miphy_pdsch_mod_layers_nof_re() x nof_layers x mod */
   uint8_t nof_layers;       /* 1..4 */
@@ -560,6 +561,80 @@ typedef struct {
 int miphy_pdsch_modulate_mapped_batch(miphy_ctx* ctx, const miphy_pdsch_mod_mapped_job* jobs, int jobs_on_device, uint32_t n,
                                       const uint16_t* prb_lists /* where the jobs are; may be NULL when nof_list_entries is 0 */,
                                       uint32_t nof_list_entries, const uint8_t* codewords /* device */, float* grid /* device cf_t */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Precoding  --  layers to antenna ports through one weight matrix per PRG
+ *   include/srsran/ran/precoding/precoding_configuration.h (the layout: weights per layer, port and PRG, PRG 0 starts at CRB 0),
+ *   include/srsran/phy/upper/precoding/channel_precoder.h, lib/phy/upper/precoding/channel_precoder_generic.cpp:27-48 (the arithmetic:
+ *   the product of the first layer, then the other layers accumulated).
+ * The 23.5 reference has the precoder block and the configuration and does not join them (its resource_grid_mapper asserts one layer and
+ * one port), so the fused entry points below go beyond its processors; their contract is y_a = sum_ly W[prg][a][ly] x_ly in the order of
+ * channel_precoder_generic, every product and sum in single precision (fused multiply-adds: each real or imaginary part is a dot product
+ * of 2 L real terms, within 2 L 2^-24 of the sum of the absolute values of its terms from the exact value). Every entry point computes
+ * the sum with the same sequence of operations, so the same inputs give the same bits through each of them.
+ * PRG g covers the grid PRBs [g prg_size, (g + 1) prg_size); W[g][a][ly] is weights[weights_offset + (g nof_ports + a) nof_layers + ly]
+ * (cf_t), the memory order of precoding_configuration (layer fastest, then port, then PRG). Antenna port a is grid port ports[a].
+ * The rules of a precoding: nof_layers 1..4 and equal to the job's; nof_ports nof_layers..16; ports distinct and below 16;
+ * prg_size >= 1, nof_prg >= 1; nof_prg x prg_size above the highest PRB of rb_mask; weights_offset + nof_prg x nof_ports x nof_layers <=
+ * nof_weights. A host job that breaks one is refused with MIPHY_EINVAL and the rule's message, nothing enqueued; a device-resident job that
+ * breaks one is skipped before any weight is read. The weights themselves are not judged. */
+typedef struct {
+  uint8_t  nof_layers;     /* 1..4 */
+  uint8_t  nof_ports;      /* nof_layers..16 */
+  uint8_t  ports[16];      /* grid port of each antenna port, distinct, < 16 */
+  uint16_t prg_size;       /* PRBs per PRG, >= 1 (wideband: nof_prg = 1 and prg_size = the grid) */
+  uint16_t nof_prg;        /* >= 1 */
+  uint16_t pad0;
+  uint32_t weights_offset; /* cf_t index of W[0][0][0] in the call's weights */
+  uint32_t pad1;
+} miphy_precoding;
+typedef char miphy_precoding_is_32_bytes[sizeof(miphy_precoding) == 32 ? 1 : -1];
+
+/* channel_precoder::apply_precoding for a batch: out[a][i] = sum_ly W[a][ly] in[ly][i], i < nof_re, with one matrix per job. Jobs and
+ * weights live in the same place, host or device. A job of nof_re = 0 writes nothing and is held to the rules all the same. Rules: the
+ * layer and port ranges above; weights_offset + nof_ports x nof_layers <= nof_weights; in_stride >= nof_re where nof_layers > 1 and
+ * out_stride >= nof_re where nof_ports > 1. */
+typedef struct {
+  uint32_t nof_re;
+  uint8_t  nof_layers;     /* 1..4 */
+  uint8_t  nof_ports;      /* nof_layers..16 */
+  uint16_t pad0;
+  uint32_t weights_offset; /* cf_t index of W[0][0]: [port][layer] */
+  uint32_t pad1;
+  uint64_t in_offset;      /* cf_t offset of layer 0 in `in`: [layer][in_stride] */
+  uint64_t in_stride;
+  uint64_t out_offset;     /* cf_t offset of antenna port 0 in `out`: [port][out_stride] */
+  uint64_t out_stride;
+} miphy_precode_job;
+int miphy_channel_precode_batch(miphy_ctx* ctx, const miphy_precode_job* jobs, int jobs_on_device, uint32_t n,
+                                const float* weights /* cf_t, where the jobs are */, uint32_t nof_weights, const float* in /* device cf_t */,
+                                float* out /* device cf_t */, void* stream);
+
+/* PDSCH modulator with precoding: miphy_pdsch_modulate_mapped_batch (with or without a list), except that the data RE of rank i, in grid
+ * PRB r, receives y_a = sum_ly W[r / prg_size][a][ly] x^(ly)(i) on grid port precoding.ports[a] for every antenna port a. mapped.layers.ports
+ * is ignored. Every data RE of every one of the nof_ports ports is stored (a zero matrix row stores zeros), nothing else is touched. The
+ * PRG of an RE follows the place of its PRB in the grid, never its place in the list. miphy_pdsch_mod_layers_nof_re(&job.mapped.layers)
+ * stays the size function. Jobs, lists and weights live in the same place. Not supported: two codewords (5..8 layers). */
+typedef struct {
+  miphy_pdsch_mod_mapped_job mapped;
+  miphy_precoding            precoding; /* precoding.nof_layers = mapped.layers.nof_layers */
+} miphy_pdsch_mod_precoded_job;
+int miphy_pdsch_modulate_precoded_batch(miphy_ctx* ctx, const miphy_pdsch_mod_precoded_job* jobs, int jobs_on_device, uint32_t n,
+                                        const uint16_t* prb_lists /* where the jobs are; may be NULL when nof_list_entries is 0 */,
+                                        uint32_t nof_list_entries, const float* weights /* cf_t, where the jobs are */, uint32_t nof_weights,
+                                        const uint8_t* codewords /* device */, float* grid /* device cf_t */, void* stream);
+
+/* PDSCH DM-RS with precoding. base.nof_ports = precoding.nof_layers (1..4) DM-RS ports 1000.. of type 1 or 2; base.ports is ignored. On an
+ * RE of a CDM group that holds at least one of these DM-RS ports, antenna port a receives sum W[prg][a][ly] r_ly over the layers ly of that
+ * group, r_ly being what miphy_dmrs_pdsch_map_batch writes for DM-RS port ly; REs of a CDM group without a layer are not written. Host
+ * jobs are held to the rules of miphy_dmrs_pdsch_map_batch too; a device-resident job is held to those that keep its addresses in bounds. */
+typedef struct {
+  miphy_dmrs_pdsch_job base;
+  miphy_precoding      precoding;
+} miphy_dmrs_pdsch_precoded_job;
+int miphy_dmrs_pdsch_map_precoded_batch(miphy_ctx* ctx, const miphy_dmrs_pdsch_precoded_job* jobs, int jobs_on_device, uint32_t n,
+                                        const float* weights /* cf_t, where the jobs are */, uint32_t nof_weights, float* grid /* device cf_t */,
+                                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Polar code chains  --  replace the chain of srsran::polar_code::set + polar_allocator::allocate + polar_encoder::encode
@@ -1209,7 +1284,7 @@ int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsch_layers_pd
  * order. The list of PDU p is prb_lists[prb_list_offset .. + nof_prb - 1] (host memory) and obeys the list rule of
  * miphy_pdsch_modulate_mapped_batch; nof_prb = 0: no list, and a batch without lists writes the bytes miphy_pdsch_process_layers_batch
  * writes. Every PDU and every list is checked before anything is enqueued or allocated, with the limits of the layered processor. PDUs are
- * host records; there is no prepared plan for this entry point. Not supported: two codewords, precoding. */
+ * host records; there is no prepared plan for this entry point. Precoding: miphy_pdsch_process_precoded_batch. Not supported: two codewords. */
 typedef struct {
   miphy_pdsch_layers_pdu layers; /* layers.base.rb_mask = the PRBs of the list */
   uint32_t prb_list_offset;      /* uint16 index into prb_lists */
@@ -1219,6 +1294,19 @@ typedef struct {
 int miphy_pdsch_process_mapped_batch(miphy_ctx* ctx, const miphy_pdsch_mapped_pdu* pdus /* host */, uint32_t n, const uint16_t* prb_lists /* host */,
                                      uint32_t nof_list_entries, const uint8_t* tb_in /* device */,
                                      float* grid /* device cf_t; only the mapped REs are written */, void* stream);
+
+/* PDSCH processor with precoding: miphy_pdsch_process_mapped_batch with miphy_pdsch_modulate_precoded_batch and
+ * miphy_dmrs_pdsch_map_precoded_batch in the middle -- the same matrices for the data and its DM-RS, the two scalings of the one-layer
+ * processor. mapped.layers.ports is ignored: antenna port a is grid port precoding.ports[a]. PDUs, lists and weights are host memory; every
+ * PDU, list and precoding is checked before anything is enqueued or allocated. Not supported: two codewords, a prepared plan,
+ * device-resident PDUs. */
+typedef struct {
+  miphy_pdsch_mapped_pdu mapped;
+  miphy_precoding        precoding; /* precoding.nof_layers = mapped.layers.nof_layers */
+} miphy_pdsch_precoded_pdu;
+int miphy_pdsch_process_precoded_batch(miphy_ctx* ctx, const miphy_pdsch_precoded_pdu* pdus /* host */, uint32_t n, const uint16_t* prb_lists /* host */,
+                                       uint32_t nof_list_entries, const float* weights /* host cf_t */, uint32_t nof_weights,
+                                       const uint8_t* tb_in /* device */, float* grid /* device cf_t; only the mapped REs are written */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * PDCCH processor (whole PDUs)  --  replaces srsran::pdcch_processor::process after the CCE-to-PRB mapping

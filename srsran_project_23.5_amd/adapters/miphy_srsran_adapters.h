@@ -25,6 +25,7 @@
 #include "srsran/phy/upper/channel_processors/channel_processor_factories.h"
 #include "srsran/phy/upper/downlink_processor.h"
 #include "srsran/phy/upper/equalization/equalization_factories.h"
+#include "srsran/phy/upper/precoding/precoding_factories.h"
 #include "srsran/phy/upper/resource_grid_mapper.h"
 #include "srsran/phy/upper/upper_phy_rg_gateway.h"
 #include "srsran/ran/csi_rs/csi_rs_pattern.h"
@@ -2371,6 +2372,87 @@ inline bool prb_list_obeys_list_rule(const srsran::static_vector<uint16_t, srsra
   return list.size() == mask.count();
 }
 
+/// A precoding_configuration as the C ABI takes it: the miphy_precoding record (antenna port a on grid port a, weights_offset 0) and, in `weights`, the
+/// coefficients in the order W[prg][port][layer] -- the memory order of the configuration's own tensor (layer fastest, then port, then PRG).
+inline miphy_precoding precoding_of(const srsran::precoding_configuration& config, std::vector<srsran::cf_t>& weights)
+{
+  const unsigned  nlayers = config.get_nof_layers(), nports = config.get_nof_ports(), nprg = config.get_nof_prg();
+  miphy_precoding p       = {};
+  p.nof_layers = nlayers, p.nof_ports = nports, p.prg_size = config.get_prg_size(), p.nof_prg = nprg, p.weights_offset = 0;
+  for (unsigned a = 0; a != 16; ++a) {
+    p.ports[a] = a;
+  }
+  weights.resize(static_cast<size_t>(nprg) * nports * nlayers);
+  for (unsigned g = 0; g != nprg; ++g) {
+    for (unsigned a = 0; a != nports; ++a) {
+      for (unsigned ly = 0; ly != nlayers; ++ly) {
+        weights[(static_cast<size_t>(g) * nports + a) * nlayers + ly] = config.get_coefficient(ly, a, g);
+      }
+    }
+  }
+  return p;
+}
+
+/// srsran::channel_precoder over miphy_channel_precode_batch (channel_precoder.h): the layers go up, the antenna ports come back.
+class channel_precoder_hip : public srsran::channel_precoder
+{
+public:
+  explicit channel_precoder_hip(std::shared_ptr<context> c) : c(std::move(c)) {}
+  void apply_precoding(srsran::re_buffer_writer& output, const srsran::re_buffer_reader& input, const srsran::precoding_weight_matrix& precoding) override
+  {
+    const unsigned nre = input.get_nof_re(), nlayers = precoding.get_nof_layers(), nports = precoding.get_nof_ports();
+    srsran_assert(input.get_nof_slices() == nlayers && output.get_nof_slices() == nports && output.get_nof_re() == nre,
+                  "The input, the output and the weights do not agree on {} layers, {} ports and {} REs.", nlayers, nports, nre);
+    if (nre == 0) {
+      return;
+    }
+    miphy_precode_job j = {};
+    j.nof_re = nre, j.nof_layers = nlayers, j.nof_ports = nports, j.in_stride = nre, j.out_stride = nre;
+    host.resize(static_cast<size_t>(nlayers) * nre);
+    weights.resize(static_cast<size_t>(nports) * nlayers);
+    for (unsigned ly = 0; ly != nlayers; ++ly) {
+      const srsran::span<const srsran::cf_t> x = input.get_slice(ly);
+      std::copy(x.begin(), x.end(), host.begin() + static_cast<size_t>(ly) * nre);
+    }
+    for (unsigned a = 0; a != nports; ++a) {
+      const srsran::span<const srsran::cf_t> w = precoding.get_port_coefficients(a);
+      std::copy(w.begin(), w.end(), weights.begin() + static_cast<size_t>(a) * nlayers);
+    }
+    auto* d_in  = static_cast<float*>(c->buf(0, host.size() * sizeof(srsran::cf_t)));
+    auto* d_out = static_cast<float*>(c->buf(1, static_cast<size_t>(nports) * nre * sizeof(srsran::cf_t)));
+    c->h2d(d_in, host.data(), host.size() * sizeof(srsran::cf_t));
+    context::check(miphy_channel_precode_batch(c->ctx, &j, 0, 1, reinterpret_cast<const float*>(weights.data()), weights.size(), d_in, d_out, c->stream),
+                   "channel_precode");
+    host.resize(static_cast<size_t>(nports) * nre);
+    c->d2h(host.data(), d_out, host.size() * sizeof(srsran::cf_t));
+    c->sync();
+    for (unsigned a = 0; a != nports; ++a) {
+      const srsran::span<srsran::cf_t> y = output.get_slice(a);
+      std::copy(host.begin() + static_cast<size_t>(a) * nre, host.begin() + static_cast<size_t>(a + 1) * nre, y.begin());
+    }
+  }
+
+private:
+  std::shared_ptr<context>  c;
+  std::vector<srsran::cf_t> host, weights;
+};
+
+/// Replaces create_channel_precoder_factory("generic" / "auto") (precoding_factories.h).
+class channel_precoder_factory_hip : public srsran::channel_precoder_factory
+{
+public:
+  explicit channel_precoder_factory_hip(std::shared_ptr<context> c) : c(std::move(c)) {}
+  std::unique_ptr<srsran::channel_precoder> create() override { return std::make_unique<channel_precoder_hip>(c); }
+
+private:
+  std::shared_ptr<context> c;
+};
+
+inline std::shared_ptr<srsran::channel_precoder_factory> create_channel_precoder_factory_hip(std::shared_ptr<context> c)
+{
+  return std::make_shared<channel_precoder_factory_hip>(std::move(c));
+}
+
 /// srsran::pdsch_modulator over miphy_pdsch_modulate_batch (pdsch_modulator.h:98). One codeword on one layer, contiguous
 /// allocation -- the configurations the 23.5 software modulator handles correctly -- and, beyond it, one codeword on two to four
 /// layers (config.ports.size() layers, layer ly on port config.ports[ly]) over miphy_pdsch_modulate_layers_batch. An allocation that is
@@ -2386,27 +2468,7 @@ public:
     srsran_assert(nlayers >= 1 && nlayers <= 4 && codewords.size() == 1, "Only one codeword on one to four layers is supported.");
     const srsran::bounded_bitset<srsran::MAX_RB> prb = config.freq_allocation.get_prb_mask(config.bwp_start_rb, config.bwp_size_rb);
     const unsigned                               nprb = prb.size(), nsc = nprb * 12;
-    miphy_pdsch_mod_job j = {};
-    j.rnti = config.rnti, j.n_id = config.n_id, j.scaling = config.scaling;
-    j.mod  = srsran::get_bits_per_symbol(config.modulation1);
-    j.port = 0; // the staging grid has a single port
-    j.start_symbol = config.start_symbol_index, j.nof_symbols = config.nof_symbols;
-    j.dmrs_type    = (config.dmrs_config_type == srsran::dmrs_type::TYPE1) ? 1 : 2;
-    j.nof_cdm_groups_without_data = config.nof_cdm_groups_without_data;
-    j.grid_nof_prb = nprb, j.bwp_start_rb = config.bwp_start_rb, j.bwp_size_rb = config.bwp_size_rb;
-    for (unsigned l = 0; l != 14 && l != config.dmrs_symb_pos.size(); ++l) {
-      if (config.dmrs_symb_pos.test(l)) {
-        j.dmrs_symbols_mask |= static_cast<uint16_t>(1U << l);
-      }
-    }
-    prb.for_each(0, nprb, [&j](unsigned r) { j.rb_mask[r >> 6] |= 1ULL << (r & 63); });
-    j.nof_reserved = reserved_rectangles(config.reserved, nprb, j.reserved);
-    const srsran::bit_buffer& cw = codewords[0];
-    j.nof_bits                   = cw.size();
-    bits.resize(cw.size());
-    for (unsigned i = 0; i != cw.size(); ++i) {
-      bits[i] = cw.extract<uint8_t>(i, 1);
-    }
+    const miphy_pdsch_mod_job                    j    = job_of(config, codewords[0], prb);
     host.assign(static_cast<size_t>(nlayers) * 14 * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernel"
     auto* d_cw = static_cast<uint8_t*>(c->buf(0, bits.size() + 16));
     auto* d_g  = static_cast<float*>(c->buf(1, host.size() * sizeof(srsran::cf_t)));
@@ -2437,10 +2499,71 @@ public:
     }
   }
 
+  /// The same with precoding (not part of srsran::pdsch_modulator, whose 23.5 form carries none): config.ports.size() stays the number of layers, the
+  /// layers go through the per-PRG matrices of `precoding` (PRG 0 starts at CRB 0) onto its antenna ports, antenna port a being grid port a, over
+  /// miphy_pdsch_modulate_precoded_batch -- with the allocation's PRB list in mapping order where it is not contiguous.
+  void modulate(srsran::resource_grid_writer& grid, srsran::span<const srsran::bit_buffer> codewords, const config_t& config,
+                const srsran::precoding_configuration& precoding)
+  {
+    const unsigned nlayers = config.ports.size();
+    srsran_assert(nlayers >= 1 && nlayers <= 4 && codewords.size() == 1, "Only one codeword on one to four layers is supported.");
+    srsran_assert(precoding.get_nof_layers() == nlayers, "The precoding is for {} layers, the transmission has {}.", precoding.get_nof_layers(), nlayers);
+    const srsran::bounded_bitset<srsran::MAX_RB> prb = config.freq_allocation.get_prb_mask(config.bwp_start_rb, config.bwp_size_rb);
+    const unsigned                               nprb = prb.size(), nsc = nprb * 12, nports = precoding.get_nof_ports();
+    miphy_pdsch_mod_precoded_job                 pj   = {};
+    pj.mapped.layers.base = job_of(config, codewords[0], prb), pj.mapped.layers.nof_layers = nlayers;
+    srsran::static_vector<uint16_t, srsran::MAX_RB> list;
+    if (!config.freq_allocation.is_contiguous()) {
+      list              = config.freq_allocation.get_prb_indices(config.bwp_start_rb, config.bwp_size_rb);
+      pj.mapped.nof_prb = list.size();
+    }
+    pj.precoding = precoding_of(precoding, weights);
+    host.assign(static_cast<size_t>(nports) * 14 * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernel"
+    auto* d_cw = static_cast<uint8_t*>(c->buf(0, bits.size() + 16));
+    auto* d_g  = static_cast<float*>(c->buf(1, host.size() * sizeof(srsran::cf_t)));
+    c->h2d(d_cw, bits.data(), bits.size());
+    c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
+    context::check(miphy_pdsch_modulate_precoded_batch(c->ctx, &pj, 0, 1, list.data(), list.size(), reinterpret_cast<const float*>(weights.data()), weights.size(),
+                                                       d_cw, d_g, c->stream),
+                   "pdsch_modulate_precoded");
+    c->d2h(host.data(), d_g, host.size() * sizeof(srsran::cf_t));
+    c->sync();
+    for (unsigned a = 0; a != nports; ++a) {
+      put_written_res(grid, a, nsc, host.data() + static_cast<size_t>(a) * 14 * nsc);
+    }
+  }
+
 private:
+  /// The modulator job of a configuration on a staging grid of `prb.size()` PRBs; the codeword's bits go to `bits`, one per byte.
+  miphy_pdsch_mod_job job_of(const config_t& config, const srsran::bit_buffer& cw, const srsran::bounded_bitset<srsran::MAX_RB>& prb)
+  {
+    const unsigned      nprb = prb.size();
+    miphy_pdsch_mod_job j    = {};
+    j.rnti = config.rnti, j.n_id = config.n_id, j.scaling = config.scaling;
+    j.mod  = srsran::get_bits_per_symbol(config.modulation1);
+    j.port = 0; // the staging grid has a single port
+    j.start_symbol = config.start_symbol_index, j.nof_symbols = config.nof_symbols;
+    j.dmrs_type    = (config.dmrs_config_type == srsran::dmrs_type::TYPE1) ? 1 : 2;
+    j.nof_cdm_groups_without_data = config.nof_cdm_groups_without_data;
+    j.grid_nof_prb = nprb, j.bwp_start_rb = config.bwp_start_rb, j.bwp_size_rb = config.bwp_size_rb;
+    for (unsigned l = 0; l != 14 && l != config.dmrs_symb_pos.size(); ++l) {
+      if (config.dmrs_symb_pos.test(l)) {
+        j.dmrs_symbols_mask |= static_cast<uint16_t>(1U << l);
+      }
+    }
+    prb.for_each(0, nprb, [&j](unsigned r) { j.rb_mask[r >> 6] |= 1ULL << (r & 63); });
+    j.nof_reserved = reserved_rectangles(config.reserved, nprb, j.reserved);
+    j.nof_bits     = cw.size();
+    bits.resize(cw.size());
+    for (unsigned i = 0; i != cw.size(); ++i) {
+      bits[i] = cw.extract<uint8_t>(i, 1);
+    }
+    return j;
+  }
+
   std::shared_ptr<context>  c;
   std::vector<uint8_t>      bits;
-  std::vector<srsran::cf_t> host;
+  std::vector<srsran::cf_t> host, weights;
 };
 
 /// srsran::dmrs_pdsch_processor over miphy_dmrs_pdsch_map_batch (dmrs_pdsch_processor.h:65).
@@ -2513,22 +2636,7 @@ public:
     srsran_assert(pdu.dmrs == srsran::dmrs_type::TYPE1, "Only DM-RS Type 1 is currently supported.");
     const srsran::bounded_bitset<srsran::MAX_RB> prb  = pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb);
     const unsigned                               nprb = prb.size(), nsc = nprb * 12;
-    miphy_pdsch_pdu p = {};
-    p.slot_in_frame = pdu.slot.slot_index(), p.rnti = pdu.rnti, p.n_id = pdu.n_id, p.dmrs_scrambling_id = pdu.scrambling_id;
-    p.tbs_lbrm_bytes = pdu.tbs_lbrm_bytes, p.tb_bytes = data[0].size();
-    p.ratio_pdsch_dmrs_to_sss_dB = pdu.ratio_pdsch_dmrs_to_sss_dB, p.ratio_pdsch_data_to_sss_dB = pdu.ratio_pdsch_data_to_sss_dB;
-    p.bg = bg_id(pdu.ldpc_base_graph), p.rv = pdu.codewords[0].rv, p.mod = srsran::get_bits_per_symbol(pdu.codewords[0].modulation);
-    p.port = 0; // the staging grid has a single port
-    p.start_symbol = pdu.start_symbol_index, p.nof_symbols = pdu.nof_symbols, p.nof_cdm_groups_without_data = pdu.nof_cdm_groups_without_data;
-    p.n_scid = pdu.n_scid ? 1 : 0, p.ref_point_prb0 = (pdu.ref_point == pdu_t::PRB0) ? 1 : 0;
-    p.grid_nof_prb = nprb, p.bwp_start_rb = pdu.bwp_start_rb, p.bwp_size_rb = pdu.bwp_size_rb;
-    for (unsigned l = 0; l != 14 && l != pdu.dmrs_symbol_mask.size(); ++l) {
-      if (pdu.dmrs_symbol_mask.test(l)) {
-        p.dmrs_symbols_mask |= static_cast<uint16_t>(1U << l);
-      }
-    }
-    prb.for_each(0, nprb, [&p](unsigned r) { p.rb_mask[r >> 6] |= 1ULL << (r & 63); });
-    p.nof_reserved = reserved_rectangles(pdu.reserved, nprb, p.reserved);
+    const miphy_pdsch_pdu                        p    = pdu_of(pdu, data[0].size(), prb);
     host.assign(static_cast<size_t>(nlayers) * 14 * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernels"
     auto* d_tb = static_cast<uint8_t*>(c->buf(0, data[0].size() + 16));
     auto* d_g  = static_cast<float*>(c->buf(1, host.size() * sizeof(srsran::cf_t)));
@@ -2559,9 +2667,69 @@ public:
     }
   }
 
+  /// The same with precoding (not part of srsran::pdsch_processor: the 23.5 pdu_t carries none): pdu.ports.size() stays the number of layers, the data
+  /// and its DM-RS go through the per-PRG matrices of `precoding` onto its antenna ports, antenna port a being grid port a, over
+  /// miphy_pdsch_process_precoded_batch.
+  void process(srsran::resource_grid_writer&                                                        grid,
+               srsran::static_vector<srsran::span<const uint8_t>, srsran::pdsch_processor::MAX_NOF_TRANSPORT_BLOCKS> data,
+               const pdu_t&                                                                         pdu,
+               const srsran::precoding_configuration&                                               precoding)
+  {
+    const unsigned nlayers = pdu.ports.size();
+    srsran_assert(nlayers >= 1 && nlayers <= 4 && pdu.codewords.size() == 1 && data.size() == 1, "Only one codeword on one to four layers is supported.");
+    srsran_assert(pdu.dmrs == srsran::dmrs_type::TYPE1, "Only DM-RS Type 1 is currently supported.");
+    srsran_assert(precoding.get_nof_layers() == nlayers, "The precoding is for {} layers, the transmission has {}.", precoding.get_nof_layers(), nlayers);
+    const srsran::bounded_bitset<srsran::MAX_RB> prb  = pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb);
+    const unsigned                               nprb = prb.size(), nsc = nprb * 12, nports = precoding.get_nof_ports();
+    miphy_pdsch_precoded_pdu                     pp   = {};
+    pp.mapped.layers.base = pdu_of(pdu, data[0].size(), prb), pp.mapped.layers.nof_layers = nlayers;
+    srsran::static_vector<uint16_t, srsran::MAX_RB> list;
+    if (!pdu.freq_alloc.is_contiguous()) {
+      list              = pdu.freq_alloc.get_prb_indices(pdu.bwp_start_rb, pdu.bwp_size_rb);
+      pp.mapped.nof_prb = list.size();
+    }
+    pp.precoding = precoding_of(precoding, weights);
+    host.assign(static_cast<size_t>(nports) * 14 * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernels"
+    auto* d_tb = static_cast<uint8_t*>(c->buf(0, data[0].size() + 16));
+    auto* d_g  = static_cast<float*>(c->buf(1, host.size() * sizeof(srsran::cf_t)));
+    c->h2d(d_tb, data[0].data(), data[0].size());
+    c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
+    context::check(miphy_pdsch_process_precoded_batch(c->ctx, &pp, 1, list.data(), list.size(), reinterpret_cast<const float*>(weights.data()), weights.size(), d_tb,
+                                                      d_g, c->stream),
+                   "pdsch_process_precoded");
+    c->d2h(host.data(), d_g, host.size() * sizeof(srsran::cf_t));
+    c->sync();
+    for (unsigned a = 0; a != nports; ++a) {
+      put_written_res(grid, a, nsc, host.data() + static_cast<size_t>(a) * 14 * nsc);
+    }
+  }
+
 private:
+  /// The processor's record of a PDU with a transport block of tb_bytes on a staging grid of `prb.size()` PRBs.
+  static miphy_pdsch_pdu pdu_of(const pdu_t& pdu, size_t tb_bytes, const srsran::bounded_bitset<srsran::MAX_RB>& prb)
+  {
+    const unsigned  nprb = prb.size();
+    miphy_pdsch_pdu p    = {};
+    p.slot_in_frame = pdu.slot.slot_index(), p.rnti = pdu.rnti, p.n_id = pdu.n_id, p.dmrs_scrambling_id = pdu.scrambling_id;
+    p.tbs_lbrm_bytes = pdu.tbs_lbrm_bytes, p.tb_bytes = tb_bytes;
+    p.ratio_pdsch_dmrs_to_sss_dB = pdu.ratio_pdsch_dmrs_to_sss_dB, p.ratio_pdsch_data_to_sss_dB = pdu.ratio_pdsch_data_to_sss_dB;
+    p.bg = bg_id(pdu.ldpc_base_graph), p.rv = pdu.codewords[0].rv, p.mod = srsran::get_bits_per_symbol(pdu.codewords[0].modulation);
+    p.port = 0; // the staging grid has a single port
+    p.start_symbol = pdu.start_symbol_index, p.nof_symbols = pdu.nof_symbols, p.nof_cdm_groups_without_data = pdu.nof_cdm_groups_without_data;
+    p.n_scid = pdu.n_scid ? 1 : 0, p.ref_point_prb0 = (pdu.ref_point == pdu_t::PRB0) ? 1 : 0;
+    p.grid_nof_prb = nprb, p.bwp_start_rb = pdu.bwp_start_rb, p.bwp_size_rb = pdu.bwp_size_rb;
+    for (unsigned l = 0; l != 14 && l != pdu.dmrs_symbol_mask.size(); ++l) {
+      if (pdu.dmrs_symbol_mask.test(l)) {
+        p.dmrs_symbols_mask |= static_cast<uint16_t>(1U << l);
+      }
+    }
+    prb.for_each(0, nprb, [&p](unsigned r) { p.rb_mask[r >> 6] |= 1ULL << (r & 63); });
+    p.nof_reserved = reserved_rectangles(pdu.reserved, nprb, p.reserved);
+    return p;
+  }
+
   std::shared_ptr<context>  c;
-  std::vector<srsran::cf_t> host;
+  std::vector<srsran::cf_t> host, weights;
 };
 
 /// Replaces create_pdsch_processor_factory_sw(encoder, modulator, dmrs) (channel_processor_factories.h:153-156).

@@ -109,6 +109,18 @@ int    miphy_pdsch_mod_list_check(const char* who, const char* what, uint32_t i,
 // miphy_pdsch_mod_job_check and miphy_pdsch_mod_list_check, or that sit on the device with their lists.
 int    miphy_pdsch_modulate_mapped_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_mapped_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
                                            const uint16_t* prb_lists, uint32_t nof_list_entries, const uint8_t* codewords, float* grid, hipStream_t s);
+// The rules of a precoding on the host (pdsch_mod.hip: PDSCH_PRECODING_RULES, which the kernels hold device-resident jobs to), for the precoded entry
+// points and the precoded PDSCH processor: nof_layers = the layers of the job, rb_mask = its five mask words, nof_weights = cf_t entries of the call's
+// weights. MIPHY_EINVAL and the message "<who>: <what> <i>: precoding: ..." on the first rule broken.
+int    miphy_precoding_check(const char* who, const char* what, uint32_t i, const miphy_precoding& p, unsigned nof_layers, const uint64_t* rb_mask,
+                             uint32_t nof_weights);
+// The rules of a precoded DM-RS job on the host: those of its DM-RS part, then miphy_precoding_check.
+int    miphy_dmrs_pdsch_precoded_job_check(const char* who, const char* what, uint32_t i, const miphy_dmrs_pdsch_precoded_job& job, uint32_t nof_weights);
+// The staging (host jobs, lists and weights in one region of the ring) and the two launches of miphy_pdsch_modulate_precoded_batch for jobs that passed
+// miphy_pdsch_mod_job_check, miphy_pdsch_mod_list_check and miphy_precoding_check, or that sit on the device with their lists and weights.
+int    miphy_pdsch_modulate_precoded_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_precoded_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
+                                             const uint16_t* prb_lists, uint32_t nof_list_entries, const float* weights, uint32_t nof_weights,
+                                             const uint8_t* codewords, float* grid, hipStream_t s);
 
 // One codeblock of the transport-block level PDSCH encoder (pdsch_cb_encode.hip): assembly from the transport block, LDPC encoding and rate
 // matching in one kernel.

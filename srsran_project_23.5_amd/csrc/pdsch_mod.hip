@@ -23,6 +23,11 @@
 // TS 38.211 7.3.1.6 (miphy_vrb_to_prb_list), or any other order; the contract is the oracle's orc_pdsch_modulate, which walks its prb_list as given. Its
 // two kernels (pdsch_seq_mapped_kernel, pdsch_mod_mapped_kernel) are the bodies of the layered ones with a list: the first holds the list to
 // PDSCH_MOD_LIST_RULES / PDSCH_MOD_LIST_ENTRY_RULES once per job, the second fills prb_of[] from it, and everything behind prb_of[] is shared.
+// Precoding (layers to antenna ports through one weight matrix per PRG; the contract of the arithmetic is channel_precoder_generic.cpp:27-48, that of the
+// layout precoding_configuration.h, and the reference joins neither to its modulator): miphy_pdsch_modulate_precoded_batch is the mapped entry point whose
+// mapping kernel (pdsch_mod_precoded_kernel) hands the L symbols of an element to a pdsch_precoder instead of storing them; dmrs_pdsch_precoded_kernel
+// does the same for the DM-RS of the L layers, channel_precode_kernel is the precoder as a block of its own. precode_sum holds the arithmetic for all
+// three, PDSCH_PRECODING_RULES what a precoding must satisfy, for the kernels' predicate and the host's messages.
 #include "gold_device.h"
 #include "mod_device.h"
 #include "miphy_ext.h"
@@ -188,6 +193,48 @@ __device__ __forceinline__ int pdsch_symbol_setup(const miphy_pdsch_mod_job& j, 
   return S.n_re;
 }
 
+// y = w[0] x[0] + ... + w[n - 1] x[n - 1] (complex, n = 1 .. 4) in the order of channel_precoder_generic.cpp:41-45: the product of the first layer, then
+// the others accumulated. A fixed sequence of one multiplication and fused multiply-adds per part, nothing left to the compiler's contraction: the three
+// precoding kernels call it, and the same inputs give the same bits in each. A weight 1 + 0j alone returns x[0] bit for bit.
+__device__ __forceinline__ float2 precode_sum(const float2* __restrict__ w, const float2 (&x)[4], const int n)
+{
+  const float2 w0 = w[0];
+  float        re = w0.x * x[0].x, im = w0.x * x[0].y;
+  re = fmaf(-w0.y, x[0].y, re), im = fmaf(w0.y, x[0].x, im);
+#pragma unroll
+  for (int ly = 1; ly < 4; ++ly) {
+    if (ly >= n)
+      break;
+    const float2 wl = w[ly];
+    re = fmaf(wl.x, x[ly].x, re), im = fmaf(wl.x, x[ly].y, im);
+    re = fmaf(-wl.y, x[ly].y, re), im = fmaf(wl.y, x[ly].x, im);
+  }
+  return make_float2(re, im);
+}
+
+// Where the L symbols of a data element go. Without precoding (the modulators of 1..4 layers): layer ly to g[ly], in the mapping functions themselves.
+struct pdsch_no_precoding {
+  static constexpr bool on = false;
+};
+// With precoding (pdsch_mod_precoded_kernel): antenna port a = 0 .. P - 1 receives the sum of its row of the matrix of the element's PRG, on the symbol's
+// row of grid port ports[a]. The matrix (at most 64 cf_t) is read with plain loads: the twelve REs of a PRB, and with prg_size > 1 their neighbours, read
+// the same addresses, which L1 and L2 serve ("precoding").
+struct pdsch_precoder {
+  static constexpr bool on = true;
+  const float2*  W;       // W[0][0][0] of the job
+  float2*        sym;     // the OFDM symbol's row of grid port 0
+  size_t         pstride; // elements from one grid port to the next
+  const uint8_t* ports;   // grid port of each antenna port (a copy in LDS)
+  int            P, L;
+  unsigned       prg_size;
+  __device__ __forceinline__ void store(const float2 (&x)[4], const int n, const int col) const
+  {
+    const float2* w = W + (size_t)(((unsigned)col / 12u) / prg_size) * (unsigned)(P * L);
+    for (int a = 0; a < P; ++a)
+      sym[ports[a] * pstride + col] = precode_sum(w + a * L, x, n);
+  }
+};
+
 // Bit 0 of each of the mod bytes at cp (one bit per byte, b0 first) gathered into bit t = t-th bit: one wide load where the run of bytes is
 // aligned, then bit 0 of every byte through a multiplication ((x & 0x01010101) * 0x01020408 puts bytes 0..3 into bits 24..27).
 __device__ __forceinline__ uint32_t gather_bits(const uint8_t* cp, int mod)
@@ -219,8 +266,10 @@ __device__ __forceinline__ uint32_t gather_bits(const uint8_t* cp, int mod)
 // symbols x 8 bits = 1 478 400 bits. Layer ly goes to g[ly], the symbol's row of its grid port. This function and pdsch_layers_fast take their
 // arguments by reference, as a lambda captures them: taken by value, both mapping kernels come out two to four registers above the 80 that six
 // waves per SIMD allow (tools/kernel_resources.sh).
+template <class PRE = pdsch_no_precoding>
 __device__ __forceinline__ void pdsch_map_elements(const pdsch_symbol_lds& S, const int& L, const int& mod, const int& prefix, const uint32_t* const& seq,
-                                                   const uint8_t* const& cw, float2* const (&g)[4], const bool& scale, const float& scaling, const int& tid, const int& nt)
+                                                   const uint8_t* const& cw, float2* const (&g)[4], const bool& scale, const float& scaling, const int& tid, const int& nt,
+                                                   const PRE& pre = PRE())
 {
   const int      nprb = S.nprb;
   const uint32_t mask = (1u << mod) - 1u;
@@ -236,6 +285,7 @@ __device__ __forceinline__ void pdsch_map_elements(const pdsch_symbol_lds& S, co
     const uint32_t cb  = (uint32_t)(two >> (bi & 31)); // scrambling bits of the element's L symbols, bit t = t-th bit
     const uint8_t* cp  = cw + (size_t)bi;
     const int      col = S.prb_of[i] * 12 + k;
+    float2         xs[4]; // (the precoded kernel alone: the element's layers, then all antenna ports)
 #pragma unroll
     for (int ly = 0; ly < 4; ++ly) {
       if (ly >= L)
@@ -246,8 +296,13 @@ __device__ __forceinline__ void pdsch_map_elements(const pdsch_symbol_lds& S, co
         x.x = x.x * scaling;
         x.y = x.y * scaling;
       }
-      g[ly][col] = x;
+      if constexpr (PRE::on)
+        xs[ly] = x;
+      else
+        g[ly][col] = x;
     }
+    if constexpr (PRE::on)
+      pre.store(xs, L, col);
   }
 }
 
@@ -255,9 +310,9 @@ __device__ __forceinline__ void pdsch_map_elements(const pdsch_symbol_lds& S, co
 // LL x MOD bytes of each as one wide load and the two words of its scrambling window -- are issued before the first of them is mapped, unconditionally
 // (an element that carries no data reads element 0 of the symbol and is not stored). The one-element-at-a-time loop above pays one memory round trip
 // per element: thirteen per thread on 273 PRBs. The group shrinks as the element grows, so that the loaded words stay in registers.
-template <int LL, int MOD>
+template <int LL, int MOD, class PRE = pdsch_no_precoding>
 __device__ __forceinline__ void pdsch_layers_fast(const pdsch_symbol_lds& S, const int& prefix, const uint32_t* const& seq, const uint8_t* const& cw,
-                                                  float2* const (&g)[4], const bool& scale, const float& scaling, const int& tid)
+                                                  float2* const (&g)[4], const bool& scale, const float& scaling, const int& tid, const PRE& pre = PRE())
 {
   constexpr int NW = LL * MOD / 4; // codeword words of one element
   constexpr int IT = (275 * 12 + 255) / 256, G = NW >= 6 ? 4 : (NW >= 3 ? 7 : IT);
@@ -292,6 +347,7 @@ __device__ __forceinline__ void pdsch_layers_fast(const pdsch_symbol_lds& S, con
       for (int w = 0; w < NW; ++w)
         raw |= (((cv[u].v[w] & 0x01010101u) * 0x01020408u) >> 24) << (4 * w);
       const uint32_t bits = raw ^ cb; // scrambled bits of the element, layer after layer
+      float2         xs[4];           // (the precoded kernel alone)
 #pragma unroll
       for (int ly = 0; ly < LL; ++ly) {
         float2 x = map_symbol(MOD, (bits >> (ly * MOD)) & ((1u << MOD) - 1u), 0u);
@@ -299,9 +355,14 @@ __device__ __forceinline__ void pdsch_layers_fast(const pdsch_symbol_lds& S, con
           x.x = x.x * scaling;
           x.y = x.y * scaling;
         }
-        if (dst[u] >= 0)
+        if constexpr (PRE::on)
+          xs[ly] = x;
+        else if (dst[u] >= 0)
           g[ly][dst[u]] = x;
       }
+      if constexpr (PRE::on)
+        if (dst[u] >= 0)
+          pre.store(xs, LL, dst[u]);
     }
   }
 }
@@ -701,6 +762,74 @@ __host__ __device__ __forceinline__ bool pdsch_list_entry_ok(const miphy_pdsch_m
 {
   return true PDSCH_MOD_LIST_ENTRY_RULES(PDSCH_RULE_HOLDS);
 }
+
+// What a precoding p must satisfy, once more for the same two readers: L = the layers of the job it belongs to (the modulator's nof_layers, the DM-RS
+// job's nof_ports), rbm = the five words of the job's rb_mask, nof_weights = cf_t entries of the call's weights. Evaluated in this order; a precoding
+// that passes indexes its weights only inside the array, for every PRB of rb_mask.
+#define PDSCH_PRECODING_RULES(R)                                                                                                                       \
+  R(p.nof_layers >= 1 && p.nof_layers <= 4, "precoding: invalid number of layers %u (1..4)", (unsigned)p.nof_layers)                                  \
+  R(p.nof_layers == L, "precoding: %u layers for a job of %u", (unsigned)p.nof_layers, (unsigned)L)                                                   \
+  R(p.nof_ports >= p.nof_layers && p.nof_ports <= 16, "precoding: invalid number of antenna ports %u (%u..16)", (unsigned)p.nof_ports,                \
+    (unsigned)p.nof_layers)                                                                                                                           \
+  R(precoding_ports_ok(p), "precoding: the antenna ports need distinct grid ports below 16")                                                          \
+  R(p.prg_size >= 1 && p.nof_prg >= 1, "precoding: invalid PRG size %u or number of PRGs %u", (unsigned)p.prg_size, (unsigned)p.nof_prg)              \
+  R((uint32_t)p.nof_prg * p.prg_size >= pdsch_mask_span(rbm), "precoding: %u PRGs of %u PRBs do not reach PRB %u of rb_mask", (unsigned)p.nof_prg,    \
+    (unsigned)p.prg_size, pdsch_mask_span(rbm) - 1u)                                                                                                  \
+  R((uint64_t)p.weights_offset + (uint64_t)p.nof_prg * p.nof_ports * p.nof_layers <= nof_weights,                                                     \
+    "precoding: weights [%u, %u + %u x %u x %u) exceed the %u weights", p.weights_offset, p.weights_offset, (unsigned)p.nof_prg, (unsigned)p.nof_ports, \
+    (unsigned)p.nof_layers, nof_weights)
+
+__host__ __device__ __forceinline__ bool precoding_ports_ok(const miphy_precoding& p)
+{
+  unsigned seen = 0;
+  for (unsigned a = 0; a < p.nof_ports && a < 16; ++a) {
+    const unsigned q = p.ports[a];
+    if (q >= 16 || ((seen >> q) & 1u))
+      return false;
+    seen |= 1u << q;
+  }
+  return true;
+}
+
+// One above the highest PRB set in the mask, 0 for an empty one.
+__host__ __device__ __forceinline__ unsigned pdsch_mask_span(const uint64_t* rbm)
+{
+  for (int w = 4; w >= 0; --w)
+    if (rbm[w])
+      return (unsigned)(64 * w + 64 - __builtin_clzll(rbm[w]));
+  return 0;
+}
+
+__host__ __device__ __forceinline__ bool pdsch_precoding_ok(const miphy_precoding& p, unsigned L, const uint64_t* rbm, uint32_t nof_weights)
+{
+  return true PDSCH_PRECODING_RULES(PDSCH_RULE_HOLDS);
+}
+
+// What a job j of miphy_channel_precode_batch must satisfy.
+#define PRECODE_JOB_RULES(R)                                                                                                                           \
+  R(j.nof_layers >= 1 && j.nof_layers <= 4, "invalid number of layers %u (1..4)", (unsigned)j.nof_layers)                                             \
+  R(j.nof_ports >= j.nof_layers && j.nof_ports <= 16, "invalid number of antenna ports %u (%u..16)", (unsigned)j.nof_ports, (unsigned)j.nof_layers)   \
+  R((uint64_t)j.weights_offset + (uint64_t)j.nof_ports * j.nof_layers <= nof_weights, "weights [%u, %u + %u x %u) exceed the %u weights",             \
+    j.weights_offset, j.weights_offset, (unsigned)j.nof_ports, (unsigned)j.nof_layers, nof_weights)                                                   \
+  R(j.nof_layers == 1 || j.in_stride >= j.nof_re, "input rows of %u REs overlap at a stride of %llu", j.nof_re, (unsigned long long)j.in_stride)      \
+  R(j.nof_ports == 1 || j.out_stride >= j.nof_re, "output rows of %u REs overlap at a stride of %llu", j.nof_re, (unsigned long long)j.out_stride)
+
+__host__ __device__ __forceinline__ bool precode_job_ok(const miphy_precode_job& j, uint32_t nof_weights)
+{
+  return true PRECODE_JOB_RULES(PDSCH_RULE_HOLDS);
+}
+
+// What the DM-RS part j of a precoded DM-RS job must satisfy: the rules of miphy_dmrs_pdsch_map_batch with the ports of one codeword.
+#define DMRS_PRECODED_FIELD_RULES(R)                                                                                                                   \
+  R(j.dmrs_type == 1 || j.dmrs_type == 2, "invalid DM-RS type")                                                                                       \
+  R(j.nof_ports >= 1 && j.nof_ports <= 4, "invalid number of DM-RS ports %u (1..4 with precoding)", (unsigned)j.nof_ports)                            \
+  R(j.grid_nof_prb >= 1 && j.grid_nof_prb <= 275 && j.reference_point_k_rb < j.grid_nof_prb, "invalid grid")                                          \
+  R(j.symbols_mask < (1u << 14), "invalid symbol mask")
+
+__host__ __device__ __forceinline__ bool dmrs_precoded_fields_ok(const miphy_dmrs_pdsch_job& j)
+{
+  return true DMRS_PRECODED_FIELD_RULES(PDSCH_RULE_HOLDS);
+}
 #undef PDSCH_RULE_HOLDS
 
 // Both LFSR sequences of c(n), held as words in LDS, from `have` (>= 31) to nwords words: the word recurrences w[i] = w[i-28] ^ w[i-31] (x1) and
@@ -732,10 +861,13 @@ __device__ __forceinline__ void gold_words_extend(uint32_t* w1, uint32_t* w2, in
 // lists. Chunk 0 of a mapped job with a list also holds the list to PDSCH_MOD_LIST_RULES and PDSCH_MOD_LIST_ENTRY_RULES -- one coalesced read of
 // the list, the duplicate test an atomicOr on a 5-word bitmap in LDS -- and clears info[15] when it breaks one: pdsch_mod_mapped_kernel uses no
 // entry of a list as an address unless info[15] is set.
+// pc: the precoding of the job, null (a literal again) in the kernels of the entry points without one. Chunk 0 of a precoded job holds it to
+// PDSCH_PRECODING_RULES as well, and does not look at the layers' ports, which such a job does not use: pdsch_mod_precoded_kernel reads no weight unless
+// info[15] is set.
 __device__ __forceinline__ void pdsch_seq_layers_body(const miphy_pdsch_mod_layers_job* __restrict__ lj, const miphy_pdsch_mod_mapped_job* __restrict__ mj,
                                                       const uint16_t* __restrict__ prb_lists, uint32_t nof_list_entries,
                                                       const gold_tables* __restrict__ gt, uint32_t* __restrict__ seq, int* __restrict__ info_out,
-                                                      uint32_t stride)
+                                                      uint32_t stride, const miphy_precoding* __restrict__ pc = nullptr, uint32_t nof_weights = 0)
 {
   __shared__ uint32_t w1[PDSCH_SEQ_CHUNK], w2[PDSCH_SEQ_CHUNK];
   __shared__ uint64_t rbm[5], resm[4][5];
@@ -744,7 +876,7 @@ __device__ __forceinline__ void pdsch_seq_layers_body(const miphy_pdsch_mod_laye
   __shared__ int                list_bad;
   const miphy_pdsch_mod_job* __restrict__ jp = &lj->base;
   const int      tid = threadIdx.x, nt = blockDim.x, chunk = blockIdx.y;
-  const bool     ok       = layers_job_ok(*lj);
+  const bool     ok       = pc ? lj->nof_layers >= 1 && lj->nof_layers <= 4 && pdsch_mod_fields_ok(*jp) : layers_job_ok(*lj);
   const uint32_t nof_bits = jp->nof_bits;
   const bool     fits     = nof_bits <= 32u * (stride - 2u); // + the 64-bit window of the last resource element
   if (chunk == 0) {
@@ -775,6 +907,8 @@ __device__ __forceinline__ void pdsch_seq_layers_body(const miphy_pdsch_mod_laye
       __syncthreads();
       list_ok = list_ok && !list_bad;
     }
+    if (pc)
+      list_ok = list_ok && pdsch_precoding_ok(*pc, lj->nof_layers, rbm, nof_weights);
     if (tid == 0) {
       int run = 0;
       for (int s = 0; s < 14; ++s) {
@@ -878,6 +1012,166 @@ __global__ void __launch_bounds__(256) pdsch_mod_mapped_kernel(const miphy_pdsch
   const miphy_pdsch_mod_mapped_job* __restrict__ mj = jobs + blockIdx.x;
   const int nof_list = mj->nof_prb;
   pdsch_mod_layers_body(&mj->layers, nof_list ? prb_lists + mj->prb_list_offset : nullptr, nof_list, cw_base, grid, seq_base, info_base, stride);
+}
+
+// ---------------------------------------------------------------------------------------------------- precoding: layers to antenna ports
+// Beyond the 23.5 reference, which has the precoder block (channel_precoder_generic.cpp:27-48, the contract of precode_sum) and the layout
+// (precoding_configuration.h) and does not join them to its modulator.
+__global__ void __launch_bounds__(512) pdsch_seq_precoded_kernel(const miphy_pdsch_mod_precoded_job* __restrict__ jobs, const uint16_t* __restrict__ prb_lists,
+                                                                 uint32_t nof_list_entries, uint32_t nof_weights, const gold_tables* __restrict__ gt,
+                                                                 uint32_t* __restrict__ seq, int* __restrict__ info_out, uint32_t stride)
+{
+  const miphy_pdsch_mod_precoded_job* __restrict__ pj = jobs + blockIdx.x;
+  pdsch_seq_layers_body(&pj->mapped.layers, &pj->mapped, prb_lists, nof_list_entries, gt, seq, info_out, stride, &pj->precoding, nof_weights);
+}
+
+// The mapping kernel of miphy_pdsch_modulate_precoded_batch: pdsch_mod_mapped_kernel whose elements go through a pdsch_precoder. The job, its list and
+// its precoding were held to their rules by chunk 0 of pdsch_seq_precoded_kernel (info[15]).
+__global__ void __launch_bounds__(256) pdsch_mod_precoded_kernel(const miphy_pdsch_mod_precoded_job* __restrict__ jobs, const uint16_t* __restrict__ prb_lists,
+                                                                 const float2* __restrict__ weights, const uint8_t* __restrict__ cw_base, float2* __restrict__ grid,
+                                                                 const uint32_t* __restrict__ seq_base, const int* __restrict__ info_base, uint32_t stride)
+{
+  __shared__ pdsch_symbol_lds S;
+  __shared__ uint8_t          aports[16];
+  const miphy_pdsch_mod_precoded_job* __restrict__ pj = jobs + blockIdx.x;
+  const miphy_pdsch_mod_job* __restrict__ jp          = &pj->mapped.layers.base;
+  const int* info = info_base + (size_t)blockIdx.x * PDSCH_LAYERS_INFO;
+  const int  sy = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+  if (!info[15]) // invalid job, list or precoding: skipped
+    return;
+  const int start_symbol = jp->start_symbol, nof_symbols = jp->nof_symbols;
+  if (sy < start_symbol || sy >= start_symbol + nof_symbols)
+    return;
+  const int prefix   = info[sy];
+  const int nof_list = pj->mapped.nof_prb;
+  if (tid < 16)
+    aports[tid] = pj->precoding.ports[tid]; // (read behind the barriers of pdsch_symbol_setup)
+  if (pdsch_symbol_setup(*jp, sy, S, tid, nt, nof_list ? prb_lists + pj->mapped.prb_list_offset : nullptr, nof_list) == 0)
+    return;
+  const int       mod = jp->mod, L = pj->mapped.layers.nof_layers;
+  const uint32_t* seq = seq_base + (size_t)blockIdx.x * stride;
+  const float     scaling = jp->scaling;
+  const bool      scale   = isnormal(scaling);
+  const uint8_t*  cw      = cw_base + jp->cw_offset;
+  const int       nsc     = jp->grid_nof_prb * 12;
+  float2* const   g[4]    = {nullptr, nullptr, nullptr, nullptr}; // (no layer is stored as it is)
+  const pdsch_precoder pre = {weights + pj->precoding.weights_offset, grid + jp->grid_offset + (size_t)sy * nsc, (size_t)14 * nsc, aports,
+                              (int)pj->precoding.nof_ports, L, pj->precoding.prg_size};
+  if ((mod == 4 || mod == 8) && (((uintptr_t)(cw + (size_t)prefix * L * mod)) & 3u) == 0) {
+#define MIPHY_LAYERS_FAST(LL, MOD) pdsch_layers_fast<LL, MOD>(S, prefix, seq, cw, g, scale, scaling, tid, pre)
+    switch (L * 16 + mod) {
+      case 1 * 16 + 4: MIPHY_LAYERS_FAST(1, 4); break;
+      case 2 * 16 + 4: MIPHY_LAYERS_FAST(2, 4); break;
+      case 3 * 16 + 4: MIPHY_LAYERS_FAST(3, 4); break;
+      case 4 * 16 + 4: MIPHY_LAYERS_FAST(4, 4); break;
+      case 1 * 16 + 8: MIPHY_LAYERS_FAST(1, 8); break;
+      case 2 * 16 + 8: MIPHY_LAYERS_FAST(2, 8); break;
+      case 3 * 16 + 8: MIPHY_LAYERS_FAST(3, 8); break;
+      default: MIPHY_LAYERS_FAST(4, 8); break;
+    }
+#undef MIPHY_LAYERS_FAST
+    return;
+  }
+  pdsch_map_elements(S, L, mod, prefix, seq, cw, g, scale, scaling, tid, nt, pre);
+}
+
+// dmrs_pdsch_kernel for the L = nof_ports DM-RS ports 1000 .. 1000 + L - 1 of one codeword behind a precoding: the same sequence, the same weights wf1
+// and wt (and idx counting allocated PRBs only); where that kernel stores r_ly on the grid port of DM-RS port ly, this one stores, on every antenna port,
+// the sum over the layers of the RE's CDM group (layers 2 c and 2 c + 1 share group c, of type 1 and of type 2). A group without a layer is not written.
+__global__ void __launch_bounds__(256) dmrs_pdsch_precoded_kernel(const miphy_dmrs_pdsch_precoded_job* __restrict__ jobs, const float2* __restrict__ weights,
+                                                                  uint32_t nof_weights, const gold_tables* __restrict__ gt, float2* __restrict__ grid)
+{
+  __shared__ uint32_t w1[128], w2[128];
+  __shared__ uint16_t prb_of[276];
+  __shared__ uint64_t rbm[5], full[5];
+  __shared__ int      nprb_s;
+  __shared__ uint8_t  aports[16];
+  const miphy_dmrs_pdsch_job* __restrict__ jp = &jobs[blockIdx.x].base;
+  const miphy_precoding* __restrict__ pc      = &jobs[blockIdx.x].precoding;
+  const int      sy   = blockIdx.y;
+  const int      tid  = threadIdx.x, nt = blockDim.x;
+  const unsigned syms = jp->symbols_mask;
+  if (!((syms >> sy) & 1u) || !dmrs_precoded_fields_ok(*jp))
+    return;
+  const int nprb_grid = jp->grid_nof_prb, ref = jp->reference_point_k_rb;
+  const bool type2 = jp->dmrs_type == 2;
+  const int  npr   = type2 ? 4 : 6;
+  if (tid < 5) { // PRBs below the reference point are never generated (dmrs_helper.h:53)
+    uint64_t m = jp->rb_mask[tid];
+    full[tid]  = m;
+    for (int b = 0; b < 64; ++b)
+      if (tid * 64 + b < ref)
+        m &= ~(1ull << b);
+    rbm[tid] = m;
+  }
+  if (tid >= 64 && tid < 80)
+    aports[tid - 64] = pc->ports[tid - 64];
+  __syncthreads();
+  if (!pdsch_precoding_ok(*pc, jp->nof_ports, full, nof_weights)) // (uniform: before any weight is read)
+    return;
+  build_prb_list(rbm, nprb_grid, 0, prb_of, &nprb_s, tid, nt);
+  const uint64_t t      = ((uint64_t)(14u * jp->slot_in_frame + (uint32_t)sy + 1u) * (2ull * jp->scrambling_id + 1ull)) % (1ull << 31);
+  const uint32_t c_init = (uint32_t)((t * (1ull << 17) + (2ull * jp->scrambling_id + (jp->n_scid ? 1u : 0u))) % (1ull << 31));
+  const int      nbits  = 2 * npr * (nprb_grid - ref);
+  __syncthreads();
+  gold_long_block(*gt, c_init, 0, ((nbits + 31) >> 5) + 1, w1, w2, w1, tid, nt);
+  const int      nprb    = nprb_s;
+  const float    amp     = (float)(0.70710678118654752440 * (double)jp->amplitude);
+  const int      l_prime = (sy != 0 && ((syms >> (sy - 1)) & 1u)) ? 1 : 0;
+  const int      L = jp->nof_ports, P = pc->nof_ports;
+  const unsigned prg_size = pc->prg_size;
+  const float2*  W   = weights + pc->weights_offset;
+  float2*        sym = grid + jp->grid_offset + (size_t)sy * (nprb_grid * 12);
+  const size_t   pstride = (size_t)14 * (nprb_grid * 12);
+  for (int idx = tid; idx < nprb * npr; idx += nt) {
+    const int i = idx / npr, q = idx - i * npr;
+    const int rb = prb_of[i];
+    const int gI = (rb - ref) * npr + q;                 // position in the sequence, counted from the reference point
+    const int k  = !type2 ? 2 * q : (q < 2 ? q : 4 + q); // type 1: 0,2,..,10 ; type 2: 0,1,6,7
+    const float re0 = ((w1[(2 * gI) >> 5] >> ((2 * gI) & 31)) & 1u) ? -amp : amp;
+    const float im0 = ((w1[(2 * gI + 1) >> 5] >> ((2 * gI + 1) & 31)) & 1u) ? -amp : amp;
+    const float2* wm = W + (size_t)((unsigned)rb / prg_size) * (unsigned)(P * L);
+    for (int c = 0; 2 * c < L; ++c) { // CDM group c: DM-RS ports 2 c and 2 c + 1
+      const int n = min(2, L - 2 * c);
+      float2    x[4];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int   p   = 2 * c + u; // (p < 4: wt = 1, as dmrs_pdsch_kernel has it for these ports)
+        const float wf1 = (p & 1) ? -1.f : 1.f;
+        const float wt  = (l_prime && p >= (type2 ? 6 : 4)) ? -1.f : 1.f;
+        const float w   = wt * ((idx & 1) ? wf1 : 1.f); // idx = index in the generated sequence (allocated PRBs only)
+        x[u]            = make_float2(re0 * w, im0 * w);
+      }
+      x[2] = x[3] = make_float2(0.f, 0.f);
+      const int col = rb * 12 + k + (!type2 ? c : 2 * c);
+      for (int a = 0; a < P; ++a)
+        sym[aports[a] * pstride + col] = precode_sum(wm + a * L + 2 * c, x, n);
+    }
+  }
+}
+
+// channel_precoder::apply_precoding for a batch: workgroups (job, slice of its REs), one RE per thread and turn, all antenna ports in its loop -- the
+// loads of a layer and the stores of a port run along the REs.
+__global__ void __launch_bounds__(256) channel_precode_kernel(const miphy_precode_job* __restrict__ jobs, const float2* __restrict__ weights, uint32_t nof_weights,
+                                                              const float2* __restrict__ in, float2* __restrict__ out)
+{
+  const miphy_precode_job& j = jobs[blockIdx.x];
+  if (!precode_job_ok(j, nof_weights)) // (before any weight is read)
+    return;
+  const int      L = j.nof_layers, P = j.nof_ports;
+  const uint32_t nof_re = j.nof_re;
+  const float2*  w  = weights + j.weights_offset;
+  const float2*  xi = in + j.in_offset;
+  float2*        yo = out + j.out_offset;
+  const uint64_t in_stride = j.in_stride, out_stride = j.out_stride;
+  for (uint64_t i = blockIdx.y * blockDim.x + threadIdx.x; i < nof_re; i += gridDim.y * blockDim.x) {
+    float2 x[4];
+#pragma unroll
+    for (int ly = 0; ly < 4; ++ly)
+      x[ly] = ly < L ? xi[(uint64_t)ly * in_stride + i] : make_float2(0.f, 0.f);
+    for (int a = 0; a < P; ++a)
+      yo[(uint64_t)a * out_stride + i] = precode_sum(w + a * L, x, L);
+  }
 }
 
 uint32_t host_nof_re(const miphy_pdsch_mod_job& j)
@@ -1159,6 +1453,151 @@ extern "C" int miphy_dmrs_pdsch_map_batch(miphy_ctx* ctx, const miphy_dmrs_pdsch
 int miphy_dmrs_pdsch_map_launch(const miphy_dmrs_pdsch_job* d_jobs, uint32_t n, const gold_tables* gt, float* grid, hipStream_t s)
 {
   hipLaunchKernelGGL(dmrs_pdsch_kernel, dim3(n, 14), dim3(256), 0, s, d_jobs, gt, (float2*)grid);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- precoding
+int miphy_precoding_check(const char* who, const char* what, uint32_t idx, const miphy_precoding& p, unsigned L, const uint64_t* rbm, uint32_t nof_weights)
+{
+#define PDSCH_RULE_REQUIRE(cond, fmt, ...) MIPHY_REQUIRE(cond, "%s: %s %u: " fmt, who, what, idx, ##__VA_ARGS__);
+  PDSCH_PRECODING_RULES(PDSCH_RULE_REQUIRE)
+#undef PDSCH_RULE_REQUIRE
+  return MIPHY_OK;
+}
+
+extern "C" int miphy_channel_precode_batch(miphy_ctx* ctx, const miphy_precode_job* jobs, int jobs_on_device, uint32_t n, const float* weights,
+                                           uint32_t nof_weights, const float* in, float* out, void* stream)
+{
+  MIPHY_REQUIRE(ctx && jobs && weights && in && out, "miphy_channel_precode_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "channel_precode: batch too large (max 65535 jobs per call)");
+  hipStream_t              s       = (hipStream_t)stream;
+  const miphy_precode_job* d_jobs  = jobs;
+  const float2*            d_w     = reinterpret_cast<const float2*>(weights);
+  uint32_t                 slices  = 16; // device-resident jobs: their sizes are not known here, every workgroup strides over its job's REs
+  if (!jobs_on_device) {
+    uint32_t max_re = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const miphy_precode_job& j = jobs[i];
+#define PRECODE_RULE_REQUIRE(cond, fmt, ...) MIPHY_REQUIRE(cond, "channel_precode: job %u: " fmt, i, ##__VA_ARGS__);
+      PRECODE_JOB_RULES(PRECODE_RULE_REQUIRE)
+#undef PRECODE_RULE_REQUIRE
+      max_re = j.nof_re > max_re ? j.nof_re : max_re;
+    }
+    if (max_re == 0)
+      return MIPHY_OK;
+    slices = (max_re + 255u) / 256u < 64u ? (max_re + 255u) / 256u : 64u;
+    device_image img; // host jobs and host weights: one region of the staging ring, one upload
+    const auto   js   = img.put(jobs, (size_t)n);
+    const auto   ws   = img.put(d_w, (size_t)nof_weights);
+    const void*  base = nullptr;
+    if (int rc = miphy_image_to_ring(ctx, img, s, &base))
+      return rc;
+    d_jobs = js.at(base), d_w = ws.at(base);
+  }
+  hipLaunchKernelGGL(channel_precode_kernel, dim3(n, slices), dim3(256), 0, s, d_jobs, d_w, nof_weights, (const float2*)in, (float2*)out);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
+}
+
+extern "C" int miphy_pdsch_modulate_precoded_batch(miphy_ctx* ctx, const miphy_pdsch_mod_precoded_job* jobs, int jobs_on_device, uint32_t n,
+                                                   const uint16_t* prb_lists, uint32_t nof_list_entries, const float* weights, uint32_t nof_weights,
+                                                   const uint8_t* codewords, float* grid, void* stream)
+{
+  MIPHY_REQUIRE(ctx && jobs && weights && codewords && grid && (prb_lists || nof_list_entries == 0), "miphy_pdsch_modulate_precoded_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "pdsch_modulate_precoded: batch too large (max 65535 transmissions per call)");
+  uint32_t max_layers = 4; // device-resident jobs: the kernels validate them, their lists and precodings; the scratch is sized for the most they may ask
+  if (!jobs_on_device) {
+    max_layers = 1;
+    const uint8_t no_ports[4] = {0, 1, 2, 3}; // (layers.ports is ignored)
+    for (uint32_t i = 0; i < n; ++i) {
+      const miphy_pdsch_mod_layers_job& lj = jobs[i].mapped.layers;
+      int rc = miphy_pdsch_mod_job_check("pdsch_modulate_precoded", "job", i, lj.base, lj.nof_layers, no_ports, 0);
+      if (rc || (rc = miphy_pdsch_mod_list_check("pdsch_modulate_precoded", "job", i, jobs[i].mapped, prb_lists, nof_list_entries)) ||
+          (rc = miphy_precoding_check("pdsch_modulate_precoded", "job", i, jobs[i].precoding, lj.nof_layers, lj.base.rb_mask, nof_weights)))
+        return rc;
+      max_layers = lj.nof_layers > max_layers ? lj.nof_layers : max_layers;
+    }
+  }
+  return miphy_pdsch_modulate_precoded_enqueue(ctx, jobs, jobs_on_device, n, max_layers, prb_lists, nof_list_entries, weights, nof_weights, codewords, grid,
+                                               (hipStream_t)stream);
+}
+
+int miphy_pdsch_modulate_precoded_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_precoded_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
+                                          const uint16_t* prb_lists, uint32_t nof_list_entries, const float* weights, uint32_t nof_weights,
+                                          const uint8_t* codewords, float* grid, hipStream_t s)
+{
+  const gold_tables* gt = nullptr;
+  int                rc = miphy_get_gold_tables(ctx, &gt);
+  if (rc)
+    return rc;
+  const miphy_pdsch_mod_precoded_job* d_jobs  = jobs;
+  const uint16_t*                     d_lists = prb_lists;
+  const float2*                       d_w     = reinterpret_cast<const float2*>(weights);
+  if (!jobs_on_device) { // host jobs, lists and weights: one region of the staging ring, one upload
+    device_image img;
+    const auto   js = img.put(jobs, (size_t)n);
+    const auto   ls = img.put(prb_lists, (size_t)nof_list_entries);
+    const auto   ws = img.put(d_w, (size_t)nof_weights);
+    const void*  base = nullptr;
+    if ((rc = miphy_image_to_ring(ctx, img, s, &base)))
+      return rc;
+    d_jobs = js.at(base), d_lists = ls.at(base), d_w = ws.at(base);
+  }
+  // scratch: as miphy_pdsch_modulate_layers_enqueue lays it out
+  const uint32_t stride = max_layers * (uint32_t)PDSCH_SEQ_STRIDE;
+  void*          seq    = nullptr;
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, (size_t)n * stride * sizeof(uint32_t) + (size_t)n * PDSCH_LAYERS_INFO * sizeof(int), &seq)))
+    return rc;
+  int* info = reinterpret_cast<int*>(static_cast<uint8_t*>(seq) + (size_t)n * stride * sizeof(uint32_t));
+  hipLaunchKernelGGL(pdsch_seq_precoded_kernel, dim3(n, 2 * max_layers), dim3(512), 0, s, d_jobs, d_lists, nof_list_entries, nof_weights, gt, (uint32_t*)seq, info,
+                     stride);
+  hipLaunchKernelGGL(pdsch_mod_precoded_kernel, dim3(n, 14), dim3(256), 0, s, d_jobs, d_lists, d_w, codewords, (float2*)grid, (const uint32_t*)seq,
+                     (const int*)info, stride);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
+}
+
+int miphy_dmrs_pdsch_precoded_job_check(const char* who, const char* what, uint32_t i, const miphy_dmrs_pdsch_precoded_job& pj, uint32_t nof_weights)
+{
+  const miphy_dmrs_pdsch_job& j = pj.base;
+#define DMRS_RULE_REQUIRE(cond, fmt, ...) MIPHY_REQUIRE(cond, "%s: %s %u: " fmt, who, what, i, ##__VA_ARGS__);
+  DMRS_PRECODED_FIELD_RULES(DMRS_RULE_REQUIRE)
+#undef DMRS_RULE_REQUIRE
+  return miphy_precoding_check(who, what, i, pj.precoding, j.nof_ports, j.rb_mask, nof_weights);
+}
+
+extern "C" int miphy_dmrs_pdsch_map_precoded_batch(miphy_ctx* ctx, const miphy_dmrs_pdsch_precoded_job* jobs, int jobs_on_device, uint32_t n, const float* weights,
+                                                   uint32_t nof_weights, float* grid, void* stream)
+{
+  MIPHY_REQUIRE(ctx && jobs && weights && grid, "miphy_dmrs_pdsch_map_precoded_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "dmrs_pdsch_map_precoded: batch too large (max 65535 transmissions per call)");
+  for (uint32_t i = 0; !jobs_on_device && i < n; ++i)
+    if (int rc = miphy_dmrs_pdsch_precoded_job_check("dmrs_pdsch_map_precoded", "job", i, jobs[i], nof_weights))
+      return rc;
+  hipStream_t        s  = (hipStream_t)stream;
+  const gold_tables* gt = nullptr;
+  int                rc = miphy_get_gold_tables(ctx, &gt);
+  if (rc)
+    return rc;
+  const miphy_dmrs_pdsch_precoded_job* d_jobs = jobs;
+  const float2*                        d_w    = reinterpret_cast<const float2*>(weights);
+  if (!jobs_on_device) {
+    device_image img;
+    const auto   js   = img.put(jobs, (size_t)n);
+    const auto   ws   = img.put(d_w, (size_t)nof_weights);
+    const void*  base = nullptr;
+    if ((rc = miphy_image_to_ring(ctx, img, s, &base)))
+      return rc;
+    d_jobs = js.at(base), d_w = ws.at(base);
+  }
+  hipLaunchKernelGGL(dmrs_pdsch_precoded_kernel, dim3(n, 14), dim3(256), 0, s, d_jobs, d_w, nof_weights, gt, (float2*)grid);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }

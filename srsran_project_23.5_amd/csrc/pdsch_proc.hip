@@ -208,6 +208,47 @@ extern "C" int miphy_pdsch_process_mapped_batch(miphy_ctx* ctx, const miphy_pdsc
   return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s);
 }
 
+// ---- precoding: the mapped composition with the two precoded kernels in the middle, the same matrices for the data and its DM-RS. The layers' ports are
+// not used (antenna port a is grid port precoding.ports[a]): the PDU's rules are checked with the layers on ports 0 .. L - 1.
+extern "C" int miphy_pdsch_process_precoded_batch(miphy_ctx* ctx, const miphy_pdsch_precoded_pdu* pdus, uint32_t n, const uint16_t* prb_lists,
+                                                  uint32_t nof_list_entries, const float* weights, uint32_t nof_weights, const uint8_t* tb_in, float* grid,
+                                                  void* stream)
+{
+  MIPHY_REQUIRE(ctx && pdus && weights && tb_in && grid && (prb_lists || nof_list_entries == 0), "miphy_pdsch_process_precoded_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "pdsch_process_precoded: at most 65535 PDUs per call");
+  hipStream_t                                s = (hipStream_t)stream;
+  std::vector<miphy_pdsch_tb_desc>           tb(n);
+  std::vector<miphy_dmrs_pdsch_precoded_job> dj(n);
+  std::vector<miphy_pdsch_mod_precoded_job>  mj(n);
+  size_t                                     cw_bytes   = 0;
+  uint32_t                                   max_layers = 1;
+  int                                        rc;
+  for (uint32_t i = 0; i < n; ++i) {
+    mj[i] = {}, dj[i] = {};
+    miphy_pdsch_layers_pdu lp = pdus[i].mapped.layers;
+    for (uint8_t ly = 0; ly < 4; ++ly)
+      lp.ports[ly] = ly;
+    if ((rc = derive_layers_jobs("pdsch_process_precoded", i, lp, tb[i], mj[i].mapped.layers, dj[i].base, cw_bytes, max_layers)))
+      return rc;
+    mj[i].mapped.prb_list_offset = pdus[i].mapped.prb_list_offset, mj[i].mapped.nof_prb = pdus[i].mapped.nof_prb;
+    mj[i].precoding = dj[i].precoding = pdus[i].precoding;
+    if ((rc = miphy_pdsch_mod_list_check("pdsch_process_precoded", "PDU", i, mj[i].mapped, prb_lists, nof_list_entries)) ||
+        (rc = miphy_dmrs_pdsch_precoded_job_check("pdsch_process_precoded", "PDU", i, dj[i], nof_weights)))
+      return rc;
+  }
+  void* work = nullptr; // codewords (one bit per byte) in a workspace of the context
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, cw_bytes + 64, &work)))
+    return rc;
+  uint8_t* d_cw = static_cast<uint8_t*>(work);
+  if ((rc = miphy_pdsch_encode_batch(ctx, tb.data(), n, tb_in, d_cw, s)))
+    return rc;
+  if ((rc = miphy_pdsch_modulate_precoded_enqueue(ctx, mj.data(), 0, n, max_layers, prb_lists, nof_list_entries, weights, nof_weights, d_cw, grid, s)))
+    return rc;
+  return miphy_dmrs_pdsch_map_precoded_batch(ctx, dj.data(), 0, n, weights, nof_weights, grid, s);
+}
+
 // ---- prepared form: PDU validation, segmentation, every descriptor upload and the scratch happen once; a run is the seven launches of the
 // chain, nothing staged or allocated, no host synchronisation -- for allocations that repeat slot after slot (and for batches whose descriptors exceed the staging ring,
 // where the per-call form has to wait for its upload).

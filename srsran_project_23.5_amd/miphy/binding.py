@@ -102,6 +102,13 @@ def lib():
         l.miphy_vrb_to_prb_list.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         l.miphy_pdsch_modulate_mapped_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         l.miphy_pdsch_process_mapped_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_channel_precode_batch"):  # (an older build named by MIPHY_LIBRARY for an A-B has none of them)
+            l.miphy_channel_precode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.miphy_pdsch_modulate_precoded_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                              C.c_void_p, C.c_void_p]
+            l.miphy_dmrs_pdsch_map_precoded_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            l.miphy_pdsch_process_precoded_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                             C.c_void_p, C.c_void_p]
         l.miphy_ofh_iq_decompress_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         l.miphy_ofh_iq_compress_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         l.miphy_pdcch_process_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -287,6 +294,20 @@ PdschModMappedJob = np.dtype([("layers", PdschModLayersJob), ("prb_list_offset",
 assert PdschModMappedJob.itemsize == 296 and PdschModMappedJob.fields["prb_list_offset"][1] == 288 and PdschModMappedJob.fields["nof_prb"][1] == 292
 PdschMappedPdu = np.dtype([("layers", PdschLayersPdu), ("prb_list_offset", np.uint32), ("nof_prb", np.uint16), ("pad", np.uint16)], align=True)
 assert PdschMappedPdu.itemsize == 320 and PdschMappedPdu.fields["prb_list_offset"][1] == 312 and PdschMappedPdu.fields["nof_prb"][1] == 316
+# Mirrors miphy_precoding: nof_layers layers onto nof_ports antenna ports (grid port ports[a]) through one matrix per PRG of prg_size grid PRBs;
+# W[g][a][ly] is cf_t entry weights_offset + (g nof_ports + a) nof_layers + ly of the call's weights.
+Precoding = np.dtype([("nof_layers", np.uint8), ("nof_ports", np.uint8), ("ports", np.uint8, 16), ("prg_size", np.uint16), ("nof_prg", np.uint16),
+                      ("pad0", np.uint16), ("weights_offset", np.uint32), ("pad1", np.uint32)], align=True)
+assert Precoding.itemsize == 32 and Precoding.fields["prg_size"][1] == 18 and Precoding.fields["weights_offset"][1] == 24
+# Mirrors miphy_precode_job: one matrix [port][layer], input [layer][in_stride], output [port][out_stride] (cf_t offsets and strides).
+PrecodeJob = np.dtype([("nof_re", np.uint32), ("nof_layers", np.uint8), ("nof_ports", np.uint8), ("pad0", np.uint16), ("weights_offset", np.uint32),
+                       ("pad1", np.uint32), ("in_offset", np.uint64), ("in_stride", np.uint64), ("out_offset", np.uint64), ("out_stride", np.uint64)], align=True)
+assert PrecodeJob.itemsize == 48 and PrecodeJob.fields["in_offset"][1] == 16
+# Mirror miphy_pdsch_mod_precoded_job, miphy_dmrs_pdsch_precoded_job and miphy_pdsch_precoded_pdu: the record without precoding, then the precoding.
+PdschModPrecodedJob = np.dtype([("mapped", PdschModMappedJob), ("precoding", Precoding)], align=True)
+DmrsPdschPrecodedJob = np.dtype([("base", DmrsPdschJob), ("precoding", Precoding)], align=True)
+PdschPrecodedPdu = np.dtype([("mapped", PdschMappedPdu), ("precoding", Precoding)], align=True)
+assert PdschModPrecodedJob.itemsize == 328 and DmrsPdschPrecodedJob.itemsize == 120 and PdschPrecodedPdu.itemsize == 352
 # Mirrors miphy_vrb_to_prb.
 VrbToPrb = np.dtype([("bundle_size", np.uint8), ("pad", np.uint8), ("align_rb", np.uint16), ("region_size_rb", np.uint16), ("first_prb", np.uint16)], align=True)
 assert VrbToPrb.itemsize == 8
@@ -680,6 +701,51 @@ class Context:
         assert prb_lists.dtype == np.uint16
         lptr, nl = (C.c_void_p(prb_lists.ctypes.data), prb_lists.size) if prb_lists.size else (None, 0)
         check(lib().miphy_pdsch_process_mapped_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, lptr, nl, _dptr(tb_in), _dptr(grid), _stream_ptr(stream)))
+
+    # ------------------------------------------------------------------ precoding: layers to antenna ports through per-PRG weights
+    @staticmethod
+    def _host_or_device(a, on_dev, np_dtype, torch_dtypes, what):
+        """(pointer, elements) of an array that lives where the jobs live: numpy of np_dtype, or a device tensor of one of torch_dtypes."""
+        if on_dev:
+            assert a is None or a.dtype in torch_dtypes, what
+            return (_dptr(a), a.numel()) if a is not None and a.numel() else (None, 0)
+        a = np.zeros(0, np_dtype) if a is None else np.ascontiguousarray(a)
+        assert a.dtype == np_dtype, what
+        return (C.c_void_p(a.ctypes.data), a.size) if a.size else (None, 0)
+
+    def channel_precode_batch(self, jobs, weights, x, out, stream=None):
+        """channel_precoder::apply_precoding for a batch of PrecodeJob: out[a][i] = sum_ly W[a][ly] x[ly][i]. jobs and weights live in the same place: a
+        PrecodeJob array with a complex64 numpy array, or uint8 and complex64 device tensors; x and out are complex64 device tensors."""
+        import torch
+        jobs, n, ptr, on_dev = self._descs(jobs, PrecodeJob)
+        wptr, nw = self._host_or_device(weights, on_dev, np.complex64, (torch.complex64,), "weights")
+        check(lib().miphy_channel_precode_batch(self.h, ptr, on_dev, n, wptr, nw, _dptr(x), _dptr(out), _stream_ptr(stream)))
+
+    def pdsch_modulate_precoded_batch(self, jobs, prb_lists, weights, codewords, grid, stream=None):
+        """pdsch_modulate_mapped_batch whose data REs go through the per-PRG matrices of each job's precoding onto its antenna ports. jobs, prb_lists
+        (None: no lists) and weights live in the same place: PdschModPrecodedJob / uint16 / complex64 numpy arrays, or uint8 / int16 / complex64
+        device tensors."""
+        import torch
+        jobs, n, ptr, on_dev = self._descs(jobs, PdschModPrecodedJob)
+        lptr, nl = self._host_or_device(prb_lists, on_dev, np.uint16, (torch.int16, torch.uint16), "prb_lists")
+        wptr, nw = self._host_or_device(weights, on_dev, np.complex64, (torch.complex64,), "weights")
+        check(lib().miphy_pdsch_modulate_precoded_batch(self.h, ptr, on_dev, n, lptr, nl, wptr, nw, _dptr(codewords), _dptr(grid), _stream_ptr(stream)))
+
+    def dmrs_pdsch_map_precoded_batch(self, jobs, weights, grid, stream=None):
+        """dmrs_pdsch_map_batch for the DM-RS ports of one codeword behind a precoding (DmrsPdschPrecodedJob; weights where the jobs are)."""
+        import torch
+        jobs, n, ptr, on_dev = self._descs(jobs, DmrsPdschPrecodedJob)
+        wptr, nw = self._host_or_device(weights, on_dev, np.complex64, (torch.complex64,), "weights")
+        check(lib().miphy_dmrs_pdsch_map_precoded_batch(self.h, ptr, on_dev, n, wptr, nw, _dptr(grid), _stream_ptr(stream)))
+
+    def pdsch_process_precoded_batch(self, pdus, prb_lists, weights, tb_in, grid, stream=None):
+        """pdsch_process_mapped_batch with precoding (host PdschPrecodedPdu records, host uint16 lists or None, host complex64 weights)."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PdschPrecodedPdu
+        pdus = np.ascontiguousarray(pdus)
+        lptr, nl = self._host_or_device(prb_lists, 0, np.uint16, (), "prb_lists")
+        wptr, nw = self._host_or_device(weights, 0, np.complex64, (), "weights")
+        check(lib().miphy_pdsch_process_precoded_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, lptr, nl, wptr, nw, _dptr(tb_in), _dptr(grid),
+                                                       _stream_ptr(stream)))
 
     def csi_rs_map_batch(self, jobs, grid, stream=None):
         jobs, n, ptr, on_dev = self._descs(jobs, CsiRsJob)

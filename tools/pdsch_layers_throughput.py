@@ -15,7 +15,11 @@ JSON line per variant. There is no CPU path: without a device this fails.
   miphy_pdsch_modulate_layers_batch (the yardstick) at L = 1, 2, 4 with device-resident jobs: without lists (the same bytes) and with every job's
   PRBs in the interleaved order of TS 38.211 7.3.1.6 at bundle size 2 or 4 (miphy_vrb_to_prb_list). Kernel times proper:
   rocprofv3 --kernel-trace --stats -d OUT -- python tools/pdsch_layers_throughput.py --mapping interleaved2 --trace --reps 2
-Run:  python tools/pdsch_layers_throughput.py [--batch N] [--iters N] [--reps R] [--mod 1|2|4|6|8] [--mapping M [--trace]]"""
+- --precoding PORTS times, instead of the above, miphy_pdsch_modulate_precoded_batch onto PORTS antenna ports next to
+  miphy_pdsch_modulate_layers_batch (the yardstick) at every L of 1, 2, 4 that PORTS can carry, with device-resident jobs and weights (every job its own
+  matrices, PRGs of --prg-size PRBs), the two alternating. Per call, per stored (RE, port), and the bytes stored (8 per (RE, port); the yardstick
+  stores 8 per (RE, layer)). With --trace the yardstick is left out, so that a kernel trace holds pdsch_mod_precoded_kernel alone.
+Run:  python tools/pdsch_layers_throughput.py [--batch N] [--iters N] [--reps R] [--mod 1|2|4|6|8] [--mapping M | --precoding PORTS [--prg-size S]] [--trace]"""
 import argparse
 import json
 import os
@@ -126,6 +130,39 @@ def mapped_section(ctx, a, grid, gen):
                           "store_GBps": round(mapped * 8 / us * 1e-3, 1)}), flush=True)
 
 
+def precoded_section(ctx, a, gen):
+    """--precoding: per L the layered entry point (the yardstick of the session) and the precoded entry point onto a.precoding antenna ports, without
+    lists -- device-resident jobs and weights, alternating."""
+    n, mod, P = a.batch, a.mod, a.precoding
+    grid = torch.zeros(n * max(P, 4) * 14 * NSC, dtype=torch.complex64, device="cuda")
+    nof_prg = -(-NPRB // a.prg_size)
+    fns, meta = [], []
+    for L in (1, 2, 4):
+        if L > P:
+            continue
+        jobs, nre = mod_jobs(n, L, True, mod)
+        cw = torch.randint(0, 2, (n * nre * L * mod,), dtype=torch.uint8, device="cuda", generator=gen)
+        if not a.trace:
+            d_jobs = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
+            fns.append(lambda j=d_jobs, cw=cw: ctx.pdsch_modulate_layers_batch(j, cw, grid))
+            meta.append(("layers_entry", L, L, nre))
+        pj = np.zeros(n, dtype=miphy.PdschModPrecodedJob)
+        pj["mapped"]["layers"] = jobs
+        pj["mapped"]["layers"]["base"]["grid_offset"] = np.arange(n, dtype=np.uint64) * np.uint64(P * 14 * NSC)
+        pc = pj["precoding"]
+        pc["nof_layers"], pc["nof_ports"], pc["ports"], pc["prg_size"], pc["nof_prg"] = L, P, np.arange(16), a.prg_size, nof_prg
+        pc["weights_offset"] = np.arange(n) * (nof_prg * P * L)
+        w = torch.view_as_complex(torch.rand((n * nof_prg * P * L, 2), dtype=torch.float32, device="cuda", generator=gen) - 0.5)
+        d_pj = torch.from_numpy(pj.view(np.uint8).copy()).cuda()
+        fns.append(lambda j=d_pj, w=w, cw=cw: ctx.pdsch_modulate_precoded_batch(j, None, w, cw, grid))
+        meta.append(("precoded_entry", L, P, nre))
+    for (name, L, ports, nre), (us, lo, hi) in zip(meta, measure(fns, a.iters, a.reps)):
+        stored = n * nre * ports
+        print(json.dumps({"what": "modulate", "entry": name, "jobs": "device", "layers": L, "ports": ports, "prg_size": a.prg_size, "mod": mod, "batch": n,
+                          "re_per_layer": nre, "us_per_call": round(us, 2), "us_per_call_spread": [round(lo, 2), round(hi, 2)],
+                          "ps_per_re_port": round(us * 1e6 / stored, 2), "store_GBps": round(stored * 8 / us * 1e-3, 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
@@ -135,12 +172,18 @@ def main():
     ap.add_argument("--mapping", choices=("ascending", "interleaved2", "interleaved4"), default=None,
                     help="time miphy_pdsch_modulate_mapped_batch next to miphy_pdsch_modulate_layers_batch instead (device jobs, L = 1, 2, 4)")
     ap.add_argument("--trace", action="store_true",
-                    help="with --mapping interleaved2 / interleaved4: leave out the mapped entry point without lists, so that a kernel trace of the run "
+                    help="with --precoding: leave out the yardstick; with --mapping interleaved2 / interleaved4: leave out the mapped entry point without lists, so that a kernel trace of the run "
                          "holds pdsch_mod_mapped_kernel at that mapping alone, next to pdsch_mod_layers_kernel")
+    ap.add_argument("--precoding", type=int, default=None, metavar="PORTS",
+                    help="time miphy_pdsch_modulate_precoded_batch onto PORTS (1..16) antenna ports next to miphy_pdsch_modulate_layers_batch instead (device jobs)")
+    ap.add_argument("--prg-size", type=int, default=4, help="with --precoding: PRBs per PRG")
     a = ap.parse_args()
     n, mod = a.batch, a.mod
     ctx = miphy.Context(0)
     gen = torch.Generator(device="cuda").manual_seed(1)
+    if a.precoding is not None:
+        precoded_section(ctx, a, gen)
+        return
     grid = torch.zeros(n * 4 * 14 * NSC, dtype=torch.complex64, device="cuda")
     if a.mapping is not None:
         mapped_section(ctx, a, grid, gen)
