@@ -91,36 +91,30 @@ size_t miphy_pdsch_modulate_scratch_bytes(uint32_t n);
 int    miphy_pdsch_modulate_launch(const miphy_pdsch_mod_job* d_jobs, uint32_t n, const gold_tables* gt, const uint8_t* codewords, float* grid, void* seq,
                                    hipStream_t s);
 int    miphy_dmrs_pdsch_map_launch(const miphy_dmrs_pdsch_job* d_jobs, uint32_t n, const gold_tables* gt, float* grid, hipStream_t s);
-// The one list of rules for a modulator job on the host (pdsch_mod.hip), for the two modulator entry points and for the PDSCH processors, which
+// The one list of rules for a modulator job on the host (pdsch_mod.hip), for the modulator entry points and for the PDSCH processors, which
 // refuse a batch before they enqueue anything: MIPHY_EINVAL and the message "<who>: <what> <i>: ..." on the first rule the job breaks. ports: the grid
 // port of each of the nof_layers layers, null for the one-layer entry points (the port is job.port, and the messages name no layer). nof_re: the
 // data REs per layer where the caller has counted them already, 0: counted here.
 int    miphy_pdsch_mod_job_check(const char* who, const char* what, uint32_t i, const miphy_pdsch_mod_job& job, unsigned nof_layers, const uint8_t* ports,
                                  uint32_t nof_re);
-// The staging and the two launches of miphy_pdsch_modulate_layers_batch for jobs that passed that check (or that sit on the device, which the
-// kernels validate); max_layers = the largest nof_layers of the batch, 4 for device-resident jobs.
-int    miphy_pdsch_modulate_layers_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_layers_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
-                                           const uint8_t* codewords, float* grid, hipStream_t s);
-// The list rule of miphy_pdsch_modulate_mapped_batch on the host (pdsch_mod.hip), for that entry point and for the mapped PDSCH processor: MIPHY_EINVAL
-// and the message "<who>: <what> <i>: ..." on the first rule the list of `job` breaks; a job without a list (nof_prb = 0) passes.
+// The list rules of a mapped job on the host (pdsch_mod.hip: PDSCH_MOD_LIST_RULES and PDSCH_MOD_LIST_ENTRY_RULES, which the kernels hold device-resident
+// jobs to): MIPHY_EINVAL and the message "<who>: <what> <i>: ..." on the first rule the list of `job` breaks; a job without a list (nof_prb = 0) passes.
 int    miphy_pdsch_mod_list_check(const char* who, const char* what, uint32_t i, const miphy_pdsch_mod_mapped_job& job, const uint16_t* prb_lists,
                                   uint32_t nof_list_entries);
-// The staging (host jobs and host lists in one region of the ring) and the two launches of miphy_pdsch_modulate_mapped_batch for jobs that passed
-// miphy_pdsch_mod_job_check and miphy_pdsch_mod_list_check, or that sit on the device with their lists.
-int    miphy_pdsch_modulate_mapped_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_mapped_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
-                                           const uint16_t* prb_lists, uint32_t nof_list_entries, const uint8_t* codewords, float* grid, hipStream_t s);
-// The rules of a precoding on the host (pdsch_mod.hip: PDSCH_PRECODING_RULES, which the kernels hold device-resident jobs to), for the precoded entry
-// points and the precoded PDSCH processor: nof_layers = the layers of the job, rb_mask = its five mask words, nof_weights = cf_t entries of the call's
-// weights. MIPHY_EINVAL and the message "<who>: <what> <i>: precoding: ..." on the first rule broken.
+// The rules of a precoding on the host (pdsch_mod.hip: PDSCH_PRECODING_RULES, likewise): nof_layers = the layers of the job, rb_mask = its five mask
+// words, nof_weights = cf_t entries of the call's weights. MIPHY_EINVAL and the message "<who>: <what> <i>: precoding: ..." on the first rule broken.
 int    miphy_precoding_check(const char* who, const char* what, uint32_t i, const miphy_precoding& p, unsigned nof_layers, const uint64_t* rb_mask,
                              uint32_t nof_weights);
 // The rules of a precoded DM-RS job on the host: those of its DM-RS part, then miphy_precoding_check.
 int    miphy_dmrs_pdsch_precoded_job_check(const char* who, const char* what, uint32_t i, const miphy_dmrs_pdsch_precoded_job& job, uint32_t nof_weights);
-// The staging (host jobs, lists and weights in one region of the ring) and the two launches of miphy_pdsch_modulate_precoded_batch for jobs that passed
-// miphy_pdsch_mod_job_check, miphy_pdsch_mod_list_check and miphy_precoding_check, or that sit on the device with their lists and weights.
-int    miphy_pdsch_modulate_precoded_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_precoded_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
-                                             const uint16_t* prb_lists, uint32_t nof_list_entries, const float* weights, uint32_t nof_weights,
-                                             const uint8_t* codewords, float* grid, hipStream_t s);
+// The staging, the scratch and the two launches behind miphy_pdsch_modulate_layers_batch, _mapped_batch and _precoded_batch (pdsch_mod.hip), for JOB =
+// miphy_pdsch_mod_layers_job, miphy_pdsch_mod_mapped_job or miphy_pdsch_mod_precoded_job: jobs that passed the checks above, or that sit on the device
+// with their lists and weights, where the kernels validate them. Host jobs go to the staging ring in one upload together with the host lists (mapped and
+// precoded jobs) and the host weights (precoded jobs); the arrays a kind of job does not have are not looked at. max_layers = the largest nof_layers of
+// the batch, 4 for device-resident jobs.
+template <class JOB>
+int miphy_pdsch_modulate_layered_enqueue(miphy_ctx* ctx, const JOB* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers, const uint16_t* prb_lists,
+                                         uint32_t nof_list_entries, const float* weights, uint32_t nof_weights, const uint8_t* codewords, float* grid, hipStream_t s);
 
 // One codeblock of the transport-block level PDSCH encoder (pdsch_cb_encode.hip): assembly from the transport block, LDPC encoding and rate
 // matching in one kernel.

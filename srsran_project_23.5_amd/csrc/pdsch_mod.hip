@@ -1,37 +1,41 @@
-// PDSCH modulator and PDSCH DM-RS mapping: the transmit-side counterpart of pusch_demod.hip.
+// PDSCH modulator and PDSCH DM-RS mapping, the transmit-side counterpart of pusch_demod.hip; PDCCH, SS/PBCH block and NZP-CSI-RS mapping.
 //
 // Behaviour contract:
 //   lib/phy/upper/channel_processors/pdsch_modulator_impl.cpp:30-282 (scrambling c_init = rnti * 2^15 + q * 2^14 + n_id, modulation,
 //   optional scaling, mapping to the allocated PRBs in ascending order skipping the DM-RS pattern of the bandwidth part and the
 //   reserved RE patterns), lib/phy/upper/channel_modulation/modulation_mapper_impl.cpp:31-146 (constellation = integer level *
 //   sqrtf(1 / average power)), lib/phy/upper/signal_processors/dmrs_pdsch_processor_impl.cpp:30-169 + dmrs_helper.h:44-96.
-// One transmit layer / one codeword and contiguous (ascending) PRB mapping: the 23.5 reference cannot do more -- its layer mapper
-// indexes out of bounds for more than one layer (pdsch_modulator_impl.cpp:80-103) and its non-contiguous mapping path writes a
-// single PRB (map_to_prb_other). Every resource element is written once, with the exact single-precision value of the reference
-// (level * scale [* scaling]).
-// Beyond the reference: one codeword on 1..4 layers (miphy_pdsch_modulate_layers_batch), the layer mapping of TS 38.211 7.3.1.3 as the oracle's
-// orc_pdsch_modulate states it, layer ly on grid port ports[ly], no precoding.
+// The 23.5 reference maps one layer of one codeword to ascending PRBs and cannot do more: its layer mapper indexes out of bounds for more than one
+// layer (pdsch_modulator_impl.cpp:80-103), its non-contiguous mapping path writes a single PRB (map_to_prb_other), and it joins its precoder
+// (channel_precoder_generic.cpp:27-48, precoding_configuration.h) to no modulator. Beyond it the contract is the oracle's orc_pdsch_modulate: the layer
+// mapping of TS 38.211 7.3.1.3 and a prb_list walked as given. Every resource element is written once, with the exact single-precision value of the
+// reference (level * scale [* scaling]); a precoded one with precode_sum of those values.
 //
-// Two entry points, two kernels each, one set of helpers. A sequence kernel per entry point (pdsch_seq_kernel: one workgroup per transmission,
-// x1 from the table; pdsch_seq_layers_kernel: chunks with both registers jumped, for sequences L times as long) writes the scrambling sequence
-// and, through pdsch_count_symbols, the data elements of the transmission before every OFDM symbol. A mapping kernel per entry point
-// (pdsch_mod_kernel, pdsch_mod_layers_kernel), one workgroup per (transmission, OFDM symbol), fills a pdsch_symbol_lds through
-// pdsch_symbol_setup and maps its elements through pdsch_layers_fast (16QAM / 256QAM on aligned codewords) or pdsch_map_elements (everything
-// else). Which REs carry data is stated once, in pdsch_keep_rule_of and pdsch_keep_mask, for the four kernels and the host's count; what a job
-// must satisfy is stated once, in PDSCH_MOD_FIELD_RULES, for the kernels' predicate and the host's messages.
-// A third entry point (miphy_pdsch_modulate_mapped_batch) takes the PRBs of a job as a list in mapping order -- the interleaved VRB-to-PRB mapping of
-// TS 38.211 7.3.1.6 (miphy_vrb_to_prb_list), or any other order; the contract is the oracle's orc_pdsch_modulate, which walks its prb_list as given. Its
-// two kernels (pdsch_seq_mapped_kernel, pdsch_mod_mapped_kernel) are the bodies of the layered ones with a list: the first holds the list to
-// PDSCH_MOD_LIST_RULES / PDSCH_MOD_LIST_ENTRY_RULES once per job, the second fills prb_of[] from it, and everything behind prb_of[] is shared.
-// Precoding (layers to antenna ports through one weight matrix per PRG; the contract of the arithmetic is channel_precoder_generic.cpp:27-48, that of the
-// layout precoding_configuration.h, and the reference joins neither to its modulator): miphy_pdsch_modulate_precoded_batch is the mapped entry point whose
-// mapping kernel (pdsch_mod_precoded_kernel) hands the L symbols of an element to a pdsch_precoder instead of storing them; dmrs_pdsch_precoded_kernel
-// does the same for the DM-RS of the L layers, channel_precode_kernel is the precoder as a block of its own. precode_sum holds the arithmetic for all
-// three, PDSCH_PRECODING_RULES what a precoding must satisfy, for the kernels' predicate and the host's messages.
+// Two paths. The one-layer path, miphy_pdsch_modulate_batch (and the prepared plan of pdsch_proc.hip): pdsch_seq_kernel, one workgroup per
+// transmission with x1 from the table, and pdsch_mod_kernel. The layered path, one codeword on 1..4 layers, with three front doors that differ in what a
+// job carries and in nothing else:
+//   miphy_pdsch_modulate_layers_batch    miphy_pdsch_mod_layers_job: layer ly on grid port ports[ly], PRBs of rb_mask ascending
+//   miphy_pdsch_modulate_mapped_batch    ... and a PRB list in mapping order: the interleaved VRB-to-PRB mapping of TS 38.211 7.3.1.6
+//                                        (miphy_vrb_to_prb_list) or any other order
+//   miphy_pdsch_modulate_precoded_batch  ... and a miphy_precoding: the L symbols of an element through the weight matrix of its PRG onto antenna ports
+// Behind the doors: one host loop (pdsch_modulate_layered: job, list, precoding, in that order), one enqueue (miphy_pdsch_modulate_layered_enqueue: staging,
+// the scratch of pdsch_layers_scratch_of, two launches), one sequence body (pdsch_seq_layers_body: chunks of the L-fold sequence with both registers
+// jumped; chunk 0 holds a device-resident job, its list and its precoding to the rules and says so in info[15]) and one mapping body
+// (pdsch_mod_layers_body, parametrised on the sink: pdsch_no_precoding or pdsch_precoder). The __global__ kernels of a door (pdsch_seq_layers_kernel /
+// _mapped_ / _precoded_, pdsch_mod_layers_kernel / _mapped_ / _precoded_) only pick the parts of its job.
+// Both paths share the helpers: a sequence kernel leaves, through pdsch_count_symbols, the data elements of the transmission before every OFDM
+// symbol; a mapping workgroup (transmission, OFDM symbol) fills a pdsch_symbol_lds through pdsch_symbol_setup and maps its elements through
+// pdsch_layers_fast (16QAM / 256QAM on aligned codewords) or pdsch_map_elements (everything else). Which REs carry data is stated once, in
+// pdsch_keep_rule_of and pdsch_keep_mask, for every kernel and the host's count. What a job, a list and a precoding must satisfy is stated once each
+// (PDSCH_MOD_FIELD_RULES, PDSCH_MOD_LIST_RULES / PDSCH_MOD_LIST_ENTRY_RULES, PDSCH_PRECODING_RULES), for the kernels' predicate and the host's messages.
+// DM-RS: dmrs_pdsch_kernel and, behind a precoding, dmrs_pdsch_precoded_kernel generate an OFDM symbol through the same helpers (dmrs_pdsch_symbol_setup,
+// dmrs_pdsch_re_of, dmrs_pdsch_weight) and differ in their store loop; channel_precode_kernel is the precoder as a block of its own, and precode_sum
+// holds the arithmetic for all three precoding kernels.
 #include "gold_device.h"
 #include "mod_device.h"
 #include "miphy_ext.h"
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -212,9 +216,23 @@ __device__ __forceinline__ float2 precode_sum(const float2* __restrict__ w, cons
   return make_float2(re, im);
 }
 
-// Where the L symbols of a data element go. Without precoding (the modulators of 1..4 layers): layer ly to g[ly], in the mapping functions themselves.
+// Where the L symbols of a data element go: the sink of a mapping kernel. A sink type says what it stages in LDS ahead of the barriers of
+// pdsch_symbol_setup (stage) and how it is built, behind them, from the job (the constructor: lj = the layers job, pc = its precoding and weights = the
+// call's weights where the entry point has them, slot = element 0 of the job's grid, nsc = subcarriers of a grid row, staged = what stage returned).
+// Without precoding (the modulators of 1..4 layers): layer ly to g[ly], the symbol's row of grid port ports[ly], in the mapping functions themselves.
 struct pdsch_no_precoding {
   static constexpr bool on = false;
+  float2*               g[4];
+  __device__ __forceinline__ static const uint8_t* stage(const miphy_precoding*, int) { return nullptr; }
+  __device__ __forceinline__ pdsch_no_precoding(const miphy_pdsch_mod_layers_job& lj, const miphy_precoding*, const float2*, const uint8_t*, float2* slot, int sy,
+                                                int nsc)
+  {
+    const int L = lj.nof_layers;
+#pragma unroll
+    for (int ly = 0; ly < 4; ++ly)
+      g[ly] = slot + ((size_t)lj.ports[ly < L ? ly : 0] * 14 + sy) * nsc;
+  }
+  __device__ __forceinline__ explicit pdsch_no_precoding(float2* row) : g{row, nullptr, nullptr, nullptr} {} // (one layer: pdsch_mod_kernel)
 };
 // With precoding (pdsch_mod_precoded_kernel): antenna port a = 0 .. P - 1 receives the sum of its row of the matrix of the element's PRG, on the symbol's
 // row of grid port ports[a]. The matrix (at most 64 cf_t) is read with plain loads: the twelve REs of a PRB, and with prg_size > 1 their neighbours, read
@@ -227,6 +245,19 @@ struct pdsch_precoder {
   const uint8_t* ports;   // grid port of each antenna port (a copy in LDS)
   int            P, L;
   unsigned       prg_size;
+  __device__ __forceinline__ static const uint8_t* stage(const miphy_precoding* pc, int tid)
+  {
+    __shared__ uint8_t aports[16];
+    if (tid < 16)
+      aports[tid] = pc->ports[tid]; // (read behind the barriers of pdsch_symbol_setup)
+    return aports;
+  }
+  __device__ __forceinline__ pdsch_precoder(const miphy_pdsch_mod_layers_job& lj, const miphy_precoding* pc, const float2* weights, const uint8_t* staged, float2* slot,
+                                            int sy, int nsc)
+      : W(weights + pc->weights_offset), sym(slot + (size_t)sy * nsc), pstride((size_t)14 * nsc), ports(staged), P(pc->nof_ports), L(lj.nof_layers),
+        prg_size(pc->prg_size)
+  {
+  }
   __device__ __forceinline__ void store(const float2 (&x)[4], const int n, const int col) const
   {
     const float2* w = W + (size_t)(((unsigned)col / 12u) / prg_size) * (unsigned)(P * L);
@@ -263,13 +294,12 @@ __device__ __forceinline__ uint32_t gather_bits(const uint8_t* cp, int mod)
 // 7.3.1.3: x^(ly)(i) = d(L i + ly), so the resource element of rank i_re in the transmission (prefix = its rank at the start of the symbol) owns
 // the codeword symbols L i_re .. L i_re + L - 1: L mod consecutive bytes of the codeword and L mod <= 32 consecutive bits of the scrambling
 // sequence, one 64-bit window of two sequence words. Bit offsets stay in 32 bits: the longest codeword is 4 layers x 275 PRB x 12 x 14
-// symbols x 8 bits = 1 478 400 bits. Layer ly goes to g[ly], the symbol's row of its grid port. This function and pdsch_layers_fast take their
+// symbols x 8 bits = 1 478 400 bits. The element's symbols go to the sink `out`. This function and pdsch_layers_fast take their
 // arguments by reference, as a lambda captures them: taken by value, both mapping kernels come out two to four registers above the 80 that six
 // waves per SIMD allow (tools/kernel_resources.sh).
-template <class PRE = pdsch_no_precoding>
+template <class PRE>
 __device__ __forceinline__ void pdsch_map_elements(const pdsch_symbol_lds& S, const int& L, const int& mod, const int& prefix, const uint32_t* const& seq,
-                                                   const uint8_t* const& cw, float2* const (&g)[4], const bool& scale, const float& scaling, const int& tid, const int& nt,
-                                                   const PRE& pre = PRE())
+                                                   const uint8_t* const& cw, const PRE& out, const bool& scale, const float& scaling, const int& tid, const int& nt)
 {
   const int      nprb = S.nprb;
   const uint32_t mask = (1u << mod) - 1u;
@@ -299,10 +329,10 @@ __device__ __forceinline__ void pdsch_map_elements(const pdsch_symbol_lds& S, co
       if constexpr (PRE::on)
         xs[ly] = x;
       else
-        g[ly][col] = x;
+        out.g[ly][col] = x;
     }
     if constexpr (PRE::on)
-      pre.store(xs, L, col);
+      out.store(xs, L, col);
   }
 }
 
@@ -310,9 +340,9 @@ __device__ __forceinline__ void pdsch_map_elements(const pdsch_symbol_lds& S, co
 // LL x MOD bytes of each as one wide load and the two words of its scrambling window -- are issued before the first of them is mapped, unconditionally
 // (an element that carries no data reads element 0 of the symbol and is not stored). The one-element-at-a-time loop above pays one memory round trip
 // per element: thirteen per thread on 273 PRBs. The group shrinks as the element grows, so that the loaded words stay in registers.
-template <int LL, int MOD, class PRE = pdsch_no_precoding>
+template <int LL, int MOD, class PRE>
 __device__ __forceinline__ void pdsch_layers_fast(const pdsch_symbol_lds& S, const int& prefix, const uint32_t* const& seq, const uint8_t* const& cw,
-                                                  float2* const (&g)[4], const bool& scale, const float& scaling, const int& tid, const PRE& pre = PRE())
+                                                  const PRE& out, const bool& scale, const float& scaling, const int& tid)
 {
   constexpr int NW = LL * MOD / 4; // codeword words of one element
   constexpr int IT = (275 * 12 + 255) / 256, G = NW >= 6 ? 4 : (NW >= 3 ? 7 : IT);
@@ -358,11 +388,11 @@ __device__ __forceinline__ void pdsch_layers_fast(const pdsch_symbol_lds& S, con
         if constexpr (PRE::on)
           xs[ly] = x;
         else if (dst[u] >= 0)
-          g[ly][dst[u]] = x;
+          out.g[ly][dst[u]] = x;
       }
       if constexpr (PRE::on)
         if (dst[u] >= 0)
-          pre.store(xs, LL, dst[u]);
+          out.store(xs, LL, dst[u]);
     }
   }
 }
@@ -416,7 +446,7 @@ __global__ void __launch_bounds__(256) pdsch_mod_kernel(const miphy_pdsch_mod_jo
   const float     scaling = jp->scaling;
   const bool      scale   = isnormal(scaling);
   const uint8_t*  cw      = cw_base + jp->cw_offset;
-  float2* const   g[4]    = {grid + jp->grid_offset + ((size_t)jp->port * 14 + sy) * (jp->grid_nof_prb * 12), nullptr, nullptr, nullptr};
+  const pdsch_no_precoding g(grid + jp->grid_offset + ((size_t)jp->port * 14 + sy) * (jp->grid_nof_prb * 12));
   if (mod == 8 && (((uintptr_t)(cw + (size_t)prefix * 8)) & 3u) == 0) {
     pdsch_layers_fast<1, 8>(S, prefix, seq, cw, g, scale, scaling, tid);
     return;
@@ -428,53 +458,98 @@ __global__ void __launch_bounds__(256) pdsch_mod_kernel(const miphy_pdsch_mod_jo
   pdsch_map_elements(S, 1, mod, prefix, seq, cw, g, scale, scaling, tid, nt);
 }
 
-__global__ void __launch_bounds__(256) dmrs_pdsch_kernel(const miphy_dmrs_pdsch_job* __restrict__ jobs, const gold_tables* __restrict__ gt,
-                                                         float2* __restrict__ grid)
+// What the two PDSCH DM-RS kernels share of a workgroup's (job, OFDM symbol): the LDS, the sequence and every value of an RE up to its store.
+struct dmrs_pdsch_lds {
+  uint32_t w1[128], w2[128]; // the symbol's sequence c(n) in w1 (w2: the second register while it is generated)
+  uint16_t prb_of[276];      // the allocated PRBs at and above the reference point, ascending
+  uint64_t rbm[5];
+  int      nprb;
+};
+struct dmrs_pdsch_symbol {
+  int   nprb, npr, ref, l_prime; // allocated PRBs, DM-RS REs per PRB and port, reference point, 1 = second symbol of a double-symbol DM-RS
+  bool  type2;
+  float amp;
+};
+struct dmrs_pdsch_re {
+  int   rb, k;    // PRB and, within it, subcarrier of CDM group 0
+  float re0, im0; // the sequence value r(n) of the RE
+};
+
+// rb_mask of the job into D.rbm, cut at the reference point: PRBs below it are never generated (dmrs_helper.h:53). full: where the uncut words go as
+// well, null (a literal) where nobody asks. The caller synchronises.
+__device__ __forceinline__ void dmrs_pdsch_load_mask(const miphy_dmrs_pdsch_job& j, dmrs_pdsch_lds& D, uint64_t* full, int tid)
 {
-  __shared__ uint32_t w1[128], w2[128];
-  __shared__ uint16_t prb_of[276];
-  __shared__ uint64_t rbm[5];
-  __shared__ int      nprb_s;
-  const miphy_dmrs_pdsch_job* __restrict__ jp = jobs + blockIdx.x;
-  const int      sy   = blockIdx.y;
-  const int      tid  = threadIdx.x, nt = blockDim.x;
-  const unsigned syms = jp->symbols_mask;
-  if (!((syms >> sy) & 1u))
-    return;
-  const int nprb_grid = jp->grid_nof_prb, ref = jp->reference_point_k_rb;
-  const bool type2 = jp->dmrs_type == 2;
-  const int  npr   = type2 ? 4 : 6;
-  if (tid < 5) { // PRBs below the reference point are never generated (dmrs_helper.h:53)
-    uint64_t m = jp->rb_mask[tid];
+  const int ref = j.reference_point_k_rb;
+  if (tid < 5) {
+    uint64_t m = j.rb_mask[tid];
+    if (full)
+      full[tid] = m;
     for (int b = 0; b < 64; ++b)
       if (tid * 64 + b < ref)
         m &= ~(1ull << b);
-    rbm[tid] = m;
+    D.rbm[tid] = m;
   }
+}
+
+// Behind dmrs_pdsch_load_mask and a barrier: the PRB list and the Gold sequence of OFDM symbol sy (dmrs_pdsch_processor_impl.cpp:30-169) into D, and
+// what the symbol's REs have in common.
+__device__ __forceinline__ dmrs_pdsch_symbol dmrs_pdsch_symbol_setup(const miphy_dmrs_pdsch_job& j, int sy, const gold_tables& gt, dmrs_pdsch_lds& D, int tid, int nt)
+{
+  dmrs_pdsch_symbol y;
+  const unsigned    syms      = j.symbols_mask;
+  const int         nprb_grid = j.grid_nof_prb;
+  y.ref = j.reference_point_k_rb, y.type2 = j.dmrs_type == 2, y.npr = y.type2 ? 4 : 6;
+  build_prb_list(D.rbm, nprb_grid, 0, D.prb_of, &D.nprb, tid, nt);
+  const uint64_t t      = ((uint64_t)(14u * j.slot_in_frame + (uint32_t)sy + 1u) * (2ull * j.scrambling_id + 1ull)) % (1ull << 31);
+  const uint32_t c_init = (uint32_t)((t * (1ull << 17) + (2ull * j.scrambling_id + (j.n_scid ? 1u : 0u))) % (1ull << 31));
+  const int      nbits  = 2 * y.npr * (nprb_grid - y.ref);
   __syncthreads();
-  build_prb_list(rbm, nprb_grid, 0, prb_of, &nprb_s, tid, nt);
-  const uint64_t t      = ((uint64_t)(14u * jp->slot_in_frame + (uint32_t)sy + 1u) * (2ull * jp->scrambling_id + 1ull)) % (1ull << 31);
-  const uint32_t c_init = (uint32_t)((t * (1ull << 17) + (2ull * jp->scrambling_id + (jp->n_scid ? 1u : 0u))) % (1ull << 31));
-  const int      nbits  = 2 * npr * (nprb_grid - ref);
+  gold_long_block(gt, c_init, 0, ((nbits + 31) >> 5) + 1, D.w1, D.w2, D.w1, tid, nt);
+  y.nprb    = D.nprb;
+  y.amp     = (float)(0.70710678118654752440 * (double)j.amplitude);
+  y.l_prime = (sy != 0 && ((syms >> (sy - 1)) & 1u)) ? 1 : 0;
+  return y;
+}
+
+// RE idx = 0 .. nprb x npr - 1 of the symbol: idx is also its index in the generated sequence, which counts allocated PRBs only.
+__device__ __forceinline__ dmrs_pdsch_re dmrs_pdsch_re_of(const dmrs_pdsch_lds& D, const dmrs_pdsch_symbol& y, int idx)
+{
+  dmrs_pdsch_re r;
+  const int     i = idx / y.npr, q = idx - i * y.npr;
+  r.rb            = D.prb_of[i];
+  const int gI    = (r.rb - y.ref) * y.npr + q;            // position in the sequence, counted from the reference point
+  r.k             = !y.type2 ? 2 * q : (q < 2 ? q : 4 + q); // type 1: 0,2,..,10 ; type 2: 0,1,6,7
+  r.re0           = ((D.w1[(2 * gI) >> 5] >> ((2 * gI) & 31)) & 1u) ? -y.amp : y.amp;
+  r.im0           = ((D.w1[(2 * gI + 1) >> 5] >> ((2 * gI + 1) & 31)) & 1u) ? -y.amp : y.amp;
+  return r;
+}
+
+// w_f(k') w_t(l') of DM-RS port p on RE idx (TS 38.211 Tables 7.4.1.1.2-1 and -2).
+__device__ __forceinline__ float dmrs_pdsch_weight(int p, int idx, const dmrs_pdsch_symbol& y)
+{
+  const float wf1 = (p & 1) ? -1.f : 1.f;
+  const float wt  = (y.l_prime && p >= (y.type2 ? 6 : 4)) ? -1.f : 1.f;
+  return wt * ((idx & 1) ? wf1 : 1.f);
+}
+
+__global__ void __launch_bounds__(256) dmrs_pdsch_kernel(const miphy_dmrs_pdsch_job* __restrict__ jobs, const gold_tables* __restrict__ gt,
+                                                         float2* __restrict__ grid)
+{
+  __shared__ dmrs_pdsch_lds D;
+  const miphy_dmrs_pdsch_job* __restrict__ jp = jobs + blockIdx.x;
+  const int sy = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+  if (!((jp->symbols_mask >> sy) & 1u))
+    return;
+  dmrs_pdsch_load_mask(*jp, D, nullptr, tid);
   __syncthreads();
-  gold_long_block(*gt, c_init, 0, ((nbits + 31) >> 5) + 1, w1, w2, w1, tid, nt);
-  const int   nprb    = nprb_s;
-  const float amp     = (float)(0.70710678118654752440 * (double)jp->amplitude);
-  const int   l_prime = (sy != 0 && ((syms >> (sy - 1)) & 1u)) ? 1 : 0;
-  const int   nports  = jp->nof_ports;
-  for (int idx = tid; idx < nprb * npr; idx += nt) {
-    const int i = idx / npr, q = idx - i * npr;
-    const int rb = prb_of[i];
-    const int gI = (rb - ref) * npr + q;                 // position in the sequence, counted from the reference point
-    const int k  = !type2 ? 2 * q : (q < 2 ? q : 4 + q); // type 1: 0,2,..,10 ; type 2: 0,1,6,7
-    const float re0 = ((w1[(2 * gI) >> 5] >> ((2 * gI) & 31)) & 1u) ? -amp : amp;
-    const float im0 = ((w1[(2 * gI + 1) >> 5] >> ((2 * gI + 1) & 31)) & 1u) ? -amp : amp;
+  const dmrs_pdsch_symbol y = dmrs_pdsch_symbol_setup(*jp, sy, *gt, D, tid, nt);
+  const int nprb_grid = jp->grid_nof_prb, nports = jp->nof_ports;
+  for (int idx = tid; idx < y.nprb * y.npr; idx += nt) {
+    const dmrs_pdsch_re r = dmrs_pdsch_re_of(D, y, idx);
     for (int p = 0; p < nports; ++p) {
-      const int   delta = !type2 ? (p >> 1) & 1 : 2 * ((p >> 1) % 3);
-      const float wf1   = (p & 1) ? -1.f : 1.f;
-      const float wt    = (l_prime && p >= (type2 ? 6 : 4)) ? -1.f : 1.f;
-      const float w     = wt * ((idx & 1) ? wf1 : 1.f); // idx = index in the generated sequence (allocated PRBs only)
-      grid[jp->grid_offset + ((size_t)jp->ports[p] * 14 + sy) * (nprb_grid * 12) + rb * 12 + k + delta] = make_float2(re0 * w, im0 * w);
+      const int   delta = !y.type2 ? (p >> 1) & 1 : 2 * ((p >> 1) % 3);
+      const float w     = dmrs_pdsch_weight(p, idx, y);
+      grid[jp->grid_offset + ((size_t)jp->ports[p] * 14 + sy) * (nprb_grid * 12) + r.rb * 12 + r.k + delta] = make_float2(r.re0 * w, r.im0 * w);
     }
   }
 }
@@ -950,8 +1025,13 @@ __global__ void __launch_bounds__(512) pdsch_seq_mapped_kernel(const miphy_pdsch
   pdsch_seq_layers_body(&jobs[blockIdx.x].layers, jobs + blockIdx.x, prb_lists, nof_list_entries, gt, seq, info_out, stride);
 }
 
-// list: the job's PRBs in mapping order (nof_list of them, pdsch_mod_mapped_kernel), null: rb_mask ascending.
+// The one mapping body of the three layered entry points: workgroup (transmission, OFDM symbol). list: the job's PRBs in mapping order (nof_list of
+// them; the mapped and precoded kernels), null: rb_mask ascending. SINK: where the elements go (pdsch_no_precoding, pdsch_precoder); pc and weights are
+// the job's precoding and the call's weights for the sink that takes them, null (literals) otherwise. The job, its list and its precoding were held to
+// their rules by chunk 0 of the sequence kernel (info[15]).
+template <class SINK>
 __device__ __forceinline__ void pdsch_mod_layers_body(const miphy_pdsch_mod_layers_job* __restrict__ lj, const uint16_t* list, int nof_list,
+                                                      const miphy_precoding* __restrict__ pc, const float2* __restrict__ weights,
                                                       const uint8_t* __restrict__ cw_base, float2* __restrict__ grid, const uint32_t* __restrict__ seq_base,
                                                       const int* __restrict__ info_base, uint32_t stride)
 {
@@ -959,12 +1039,13 @@ __device__ __forceinline__ void pdsch_mod_layers_body(const miphy_pdsch_mod_laye
   const miphy_pdsch_mod_job* __restrict__ jp = &lj->base;
   const int* info = info_base + (size_t)blockIdx.x * PDSCH_LAYERS_INFO;
   const int  sy = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
-  if (!info[15]) // invalid job or list (pdsch_seq_layers_body): skipped
+  if (!info[15]) // invalid job, list or precoding (pdsch_seq_layers_body): skipped
     return;
   const int start_symbol = jp->start_symbol, nof_symbols = jp->nof_symbols;
   if (sy < start_symbol || sy >= start_symbol + nof_symbols)
     return;
-  const int prefix = info[sy]; // elements per layer of the transmission in earlier symbols
+  const int      prefix = info[sy]; // elements per layer of the transmission in earlier symbols
+  const uint8_t* staged = SINK::stage(pc, tid);
   if (pdsch_symbol_setup(*jp, sy, S, tid, nt, list, nof_list) == 0)
     return;
   const int       mod = jp->mod, L = lj->nof_layers;
@@ -972,11 +1053,7 @@ __device__ __forceinline__ void pdsch_mod_layers_body(const miphy_pdsch_mod_laye
   const float     scaling = jp->scaling;
   const bool      scale   = isnormal(scaling);
   const uint8_t*  cw      = cw_base + jp->cw_offset;
-  const int       nsc     = jp->grid_nof_prb * 12;
-  float2*         g[4];
-#pragma unroll
-  for (int ly = 0; ly < 4; ++ly)
-    g[ly] = grid + jp->grid_offset + ((size_t)lj->ports[ly < L ? ly : 0] * 14 + sy) * nsc;
+  const SINK      g(*lj, pc, weights, staged, grid + jp->grid_offset, sy, jp->grid_nof_prb * 12);
   if ((mod == 4 || mod == 8) && (((uintptr_t)(cw + (size_t)prefix * L * mod)) & 3u) == 0) {
 #define MIPHY_LAYERS_FAST(LL, MOD) pdsch_layers_fast<LL, MOD>(S, prefix, seq, cw, g, scale, scaling, tid)
     switch (L * 16 + mod) {
@@ -999,19 +1076,19 @@ __global__ void __launch_bounds__(256) pdsch_mod_layers_kernel(const miphy_pdsch
                                                                float2* __restrict__ grid, const uint32_t* __restrict__ seq_base,
                                                                const int* __restrict__ info_base, uint32_t stride)
 {
-  pdsch_mod_layers_body(jobs + blockIdx.x, nullptr, 0, cw_base, grid, seq_base, info_base, stride);
+  pdsch_mod_layers_body<pdsch_no_precoding>(jobs + blockIdx.x, nullptr, 0, nullptr, nullptr, cw_base, grid, seq_base, info_base, stride);
 }
 
-// The mapping kernel of miphy_pdsch_modulate_mapped_batch: pdsch_mod_layers_kernel with prb_of[] filled from the job's list. Only the order in which
-// prb_of[] is filled differs, so pdsch_layers_fast and pdsch_map_elements serve it as they are. The list was held to its rules by chunk 0 of
-// pdsch_seq_mapped_kernel (info[15]); a job with nof_prb = 0 has none.
+// The mapping kernel of miphy_pdsch_modulate_mapped_batch: prb_of[] filled from the job's list. Only the order in which prb_of[] is filled differs, so
+// everything behind it serves the list as it is. A job with nof_prb = 0 has no list.
 __global__ void __launch_bounds__(256) pdsch_mod_mapped_kernel(const miphy_pdsch_mod_mapped_job* __restrict__ jobs, const uint16_t* __restrict__ prb_lists,
                                                                const uint8_t* __restrict__ cw_base, float2* __restrict__ grid,
                                                                const uint32_t* __restrict__ seq_base, const int* __restrict__ info_base, uint32_t stride)
 {
   const miphy_pdsch_mod_mapped_job* __restrict__ mj = jobs + blockIdx.x;
   const int nof_list = mj->nof_prb;
-  pdsch_mod_layers_body(&mj->layers, nof_list ? prb_lists + mj->prb_list_offset : nullptr, nof_list, cw_base, grid, seq_base, info_base, stride);
+  pdsch_mod_layers_body<pdsch_no_precoding>(&mj->layers, nof_list ? prb_lists + mj->prb_list_offset : nullptr, nof_list, nullptr, nullptr, cw_base, grid, seq_base,
+                                            info_base, stride);
 }
 
 // ---------------------------------------------------------------------------------------------------- precoding: layers to antenna ports
@@ -1025,125 +1102,56 @@ __global__ void __launch_bounds__(512) pdsch_seq_precoded_kernel(const miphy_pds
   pdsch_seq_layers_body(&pj->mapped.layers, &pj->mapped, prb_lists, nof_list_entries, gt, seq, info_out, stride, &pj->precoding, nof_weights);
 }
 
-// The mapping kernel of miphy_pdsch_modulate_precoded_batch: pdsch_mod_mapped_kernel whose elements go through a pdsch_precoder. The job, its list and
-// its precoding were held to their rules by chunk 0 of pdsch_seq_precoded_kernel (info[15]).
+// The mapping kernel of miphy_pdsch_modulate_precoded_batch: the mapped one whose elements go through a pdsch_precoder.
 __global__ void __launch_bounds__(256) pdsch_mod_precoded_kernel(const miphy_pdsch_mod_precoded_job* __restrict__ jobs, const uint16_t* __restrict__ prb_lists,
                                                                  const float2* __restrict__ weights, const uint8_t* __restrict__ cw_base, float2* __restrict__ grid,
                                                                  const uint32_t* __restrict__ seq_base, const int* __restrict__ info_base, uint32_t stride)
 {
-  __shared__ pdsch_symbol_lds S;
-  __shared__ uint8_t          aports[16];
   const miphy_pdsch_mod_precoded_job* __restrict__ pj = jobs + blockIdx.x;
-  const miphy_pdsch_mod_job* __restrict__ jp          = &pj->mapped.layers.base;
-  const int* info = info_base + (size_t)blockIdx.x * PDSCH_LAYERS_INFO;
-  const int  sy = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
-  if (!info[15]) // invalid job, list or precoding: skipped
-    return;
-  const int start_symbol = jp->start_symbol, nof_symbols = jp->nof_symbols;
-  if (sy < start_symbol || sy >= start_symbol + nof_symbols)
-    return;
-  const int prefix   = info[sy];
   const int nof_list = pj->mapped.nof_prb;
-  if (tid < 16)
-    aports[tid] = pj->precoding.ports[tid]; // (read behind the barriers of pdsch_symbol_setup)
-  if (pdsch_symbol_setup(*jp, sy, S, tid, nt, nof_list ? prb_lists + pj->mapped.prb_list_offset : nullptr, nof_list) == 0)
-    return;
-  const int       mod = jp->mod, L = pj->mapped.layers.nof_layers;
-  const uint32_t* seq = seq_base + (size_t)blockIdx.x * stride;
-  const float     scaling = jp->scaling;
-  const bool      scale   = isnormal(scaling);
-  const uint8_t*  cw      = cw_base + jp->cw_offset;
-  const int       nsc     = jp->grid_nof_prb * 12;
-  float2* const   g[4]    = {nullptr, nullptr, nullptr, nullptr}; // (no layer is stored as it is)
-  const pdsch_precoder pre = {weights + pj->precoding.weights_offset, grid + jp->grid_offset + (size_t)sy * nsc, (size_t)14 * nsc, aports,
-                              (int)pj->precoding.nof_ports, L, pj->precoding.prg_size};
-  if ((mod == 4 || mod == 8) && (((uintptr_t)(cw + (size_t)prefix * L * mod)) & 3u) == 0) {
-#define MIPHY_LAYERS_FAST(LL, MOD) pdsch_layers_fast<LL, MOD>(S, prefix, seq, cw, g, scale, scaling, tid, pre)
-    switch (L * 16 + mod) {
-      case 1 * 16 + 4: MIPHY_LAYERS_FAST(1, 4); break;
-      case 2 * 16 + 4: MIPHY_LAYERS_FAST(2, 4); break;
-      case 3 * 16 + 4: MIPHY_LAYERS_FAST(3, 4); break;
-      case 4 * 16 + 4: MIPHY_LAYERS_FAST(4, 4); break;
-      case 1 * 16 + 8: MIPHY_LAYERS_FAST(1, 8); break;
-      case 2 * 16 + 8: MIPHY_LAYERS_FAST(2, 8); break;
-      case 3 * 16 + 8: MIPHY_LAYERS_FAST(3, 8); break;
-      default: MIPHY_LAYERS_FAST(4, 8); break;
-    }
-#undef MIPHY_LAYERS_FAST
-    return;
-  }
-  pdsch_map_elements(S, L, mod, prefix, seq, cw, g, scale, scaling, tid, nt, pre);
+  pdsch_mod_layers_body<pdsch_precoder>(&pj->mapped.layers, nof_list ? prb_lists + pj->mapped.prb_list_offset : nullptr, nof_list, &pj->precoding, weights, cw_base,
+                                        grid, seq_base, info_base, stride);
 }
 
-// dmrs_pdsch_kernel for the L = nof_ports DM-RS ports 1000 .. 1000 + L - 1 of one codeword behind a precoding: the same sequence, the same weights wf1
-// and wt (and idx counting allocated PRBs only); where that kernel stores r_ly on the grid port of DM-RS port ly, this one stores, on every antenna port,
+// dmrs_pdsch_kernel for the L = nof_ports DM-RS ports 1000 .. 1000 + L - 1 of one codeword behind a precoding, through the same helpers: where that
+// kernel stores r_ly on the grid port of DM-RS port ly, this one stores, on every antenna port,
 // the sum over the layers of the RE's CDM group (layers 2 c and 2 c + 1 share group c, of type 1 and of type 2). A group without a layer is not written.
 __global__ void __launch_bounds__(256) dmrs_pdsch_precoded_kernel(const miphy_dmrs_pdsch_precoded_job* __restrict__ jobs, const float2* __restrict__ weights,
                                                                   uint32_t nof_weights, const gold_tables* __restrict__ gt, float2* __restrict__ grid)
 {
-  __shared__ uint32_t w1[128], w2[128];
-  __shared__ uint16_t prb_of[276];
-  __shared__ uint64_t rbm[5], full[5];
-  __shared__ int      nprb_s;
-  __shared__ uint8_t  aports[16];
+  __shared__ dmrs_pdsch_lds D;
+  __shared__ uint64_t       full[5];
+  __shared__ uint8_t        aports[16];
   const miphy_dmrs_pdsch_job* __restrict__ jp = &jobs[blockIdx.x].base;
   const miphy_precoding* __restrict__ pc      = &jobs[blockIdx.x].precoding;
-  const int      sy   = blockIdx.y;
-  const int      tid  = threadIdx.x, nt = blockDim.x;
-  const unsigned syms = jp->symbols_mask;
-  if (!((syms >> sy) & 1u) || !dmrs_precoded_fields_ok(*jp))
+  const int sy = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+  if (!((jp->symbols_mask >> sy) & 1u) || !dmrs_precoded_fields_ok(*jp))
     return;
-  const int nprb_grid = jp->grid_nof_prb, ref = jp->reference_point_k_rb;
-  const bool type2 = jp->dmrs_type == 2;
-  const int  npr   = type2 ? 4 : 6;
-  if (tid < 5) { // PRBs below the reference point are never generated (dmrs_helper.h:53)
-    uint64_t m = jp->rb_mask[tid];
-    full[tid]  = m;
-    for (int b = 0; b < 64; ++b)
-      if (tid * 64 + b < ref)
-        m &= ~(1ull << b);
-    rbm[tid] = m;
-  }
+  dmrs_pdsch_load_mask(*jp, D, full, tid);
   if (tid >= 64 && tid < 80)
     aports[tid - 64] = pc->ports[tid - 64];
   __syncthreads();
   if (!pdsch_precoding_ok(*pc, jp->nof_ports, full, nof_weights)) // (uniform: before any weight is read)
     return;
-  build_prb_list(rbm, nprb_grid, 0, prb_of, &nprb_s, tid, nt);
-  const uint64_t t      = ((uint64_t)(14u * jp->slot_in_frame + (uint32_t)sy + 1u) * (2ull * jp->scrambling_id + 1ull)) % (1ull << 31);
-  const uint32_t c_init = (uint32_t)((t * (1ull << 17) + (2ull * jp->scrambling_id + (jp->n_scid ? 1u : 0u))) % (1ull << 31));
-  const int      nbits  = 2 * npr * (nprb_grid - ref);
-  __syncthreads();
-  gold_long_block(*gt, c_init, 0, ((nbits + 31) >> 5) + 1, w1, w2, w1, tid, nt);
-  const int      nprb    = nprb_s;
-  const float    amp     = (float)(0.70710678118654752440 * (double)jp->amplitude);
-  const int      l_prime = (sy != 0 && ((syms >> (sy - 1)) & 1u)) ? 1 : 0;
-  const int      L = jp->nof_ports, P = pc->nof_ports;
+  const dmrs_pdsch_symbol y = dmrs_pdsch_symbol_setup(*jp, sy, *gt, D, tid, nt);
+  const int      nprb_grid = jp->grid_nof_prb, L = jp->nof_ports, P = pc->nof_ports;
   const unsigned prg_size = pc->prg_size;
   const float2*  W   = weights + pc->weights_offset;
   float2*        sym = grid + jp->grid_offset + (size_t)sy * (nprb_grid * 12);
   const size_t   pstride = (size_t)14 * (nprb_grid * 12);
-  for (int idx = tid; idx < nprb * npr; idx += nt) {
-    const int i = idx / npr, q = idx - i * npr;
-    const int rb = prb_of[i];
-    const int gI = (rb - ref) * npr + q;                 // position in the sequence, counted from the reference point
-    const int k  = !type2 ? 2 * q : (q < 2 ? q : 4 + q); // type 1: 0,2,..,10 ; type 2: 0,1,6,7
-    const float re0 = ((w1[(2 * gI) >> 5] >> ((2 * gI) & 31)) & 1u) ? -amp : amp;
-    const float im0 = ((w1[(2 * gI + 1) >> 5] >> ((2 * gI + 1) & 31)) & 1u) ? -amp : amp;
-    const float2* wm = W + (size_t)((unsigned)rb / prg_size) * (unsigned)(P * L);
+  for (int idx = tid; idx < y.nprb * y.npr; idx += nt) {
+    const dmrs_pdsch_re r  = dmrs_pdsch_re_of(D, y, idx);
+    const float2*       wm = W + (size_t)((unsigned)r.rb / prg_size) * (unsigned)(P * L);
     for (int c = 0; 2 * c < L; ++c) { // CDM group c: DM-RS ports 2 c and 2 c + 1
       const int n = min(2, L - 2 * c);
       float2    x[4];
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        const int   p   = 2 * c + u; // (p < 4: wt = 1, as dmrs_pdsch_kernel has it for these ports)
-        const float wf1 = (p & 1) ? -1.f : 1.f;
-        const float wt  = (l_prime && p >= (type2 ? 6 : 4)) ? -1.f : 1.f;
-        const float w   = wt * ((idx & 1) ? wf1 : 1.f); // idx = index in the generated sequence (allocated PRBs only)
-        x[u]            = make_float2(re0 * w, im0 * w);
+        const float w = dmrs_pdsch_weight(2 * c + u, idx, y); // (ports below 4: w_t = 1)
+        x[u]          = make_float2(r.re0 * w, r.im0 * w);
       }
       x[2] = x[3] = make_float2(0.f, 0.f);
-      const int col = rb * 12 + k + (!type2 ? c : 2 * c);
+      const int col = r.rb * 12 + r.k + (!y.type2 ? c : 2 * c);
       for (int a = 0; a < P; ++a)
         sym[aports[a] * pstride + col] = precode_sum(wm + a * L + 2 * c, x, n);
     }
@@ -1267,47 +1275,127 @@ extern "C" uint32_t miphy_pdsch_mod_layers_nof_re(const miphy_pdsch_mod_layers_j
   return miphy_pdsch_mod_nof_re(&j->base);
 }
 
+namespace {
+// The three layered entry points take one kind of job each -- miphy_pdsch_mod_layers_job, miphy_pdsch_mod_mapped_job (a layers job and its PRB list) or
+// miphy_pdsch_mod_precoded_job (a mapped job and its precoding) -- and share everything else. The parts of a job: null where its kind has none.
+struct pdsch_job_parts {
+  const miphy_pdsch_mod_layers_job* layers;
+  const miphy_pdsch_mod_mapped_job* mapped;
+  const miphy_precoding*            precoding;
+};
+pdsch_job_parts parts_of(const miphy_pdsch_mod_layers_job& j) { return {&j, nullptr, nullptr}; }
+pdsch_job_parts parts_of(const miphy_pdsch_mod_mapped_job& j) { return {&j.layers, &j, nullptr}; }
+pdsch_job_parts parts_of(const miphy_pdsch_mod_precoded_job& j) { return {&j.mapped.layers, &j.mapped, &j.precoding}; }
+
+// The scratch of a layered call in MIPHY_WS_SEQUENCES: the scrambling sequences (a transmission on L layers has L times the bits of one layer: the stride
+// grows with the batch's largest L), then PDSCH_LAYERS_INFO ints per transmission.
+struct pdsch_layers_scratch {
+  uint32_t stride; // sequence words per transmission
+  size_t   seq_bytes, bytes;
+  int*     info(void* seq) const { return reinterpret_cast<int*>(static_cast<uint8_t*>(seq) + seq_bytes); }
+};
+pdsch_layers_scratch pdsch_layers_scratch_of(uint32_t n, uint32_t max_layers)
+{
+  const uint32_t stride    = max_layers * (uint32_t)PDSCH_SEQ_STRIDE;
+  const size_t   seq_bytes = (size_t)n * stride * sizeof(uint32_t);
+  return {stride, seq_bytes, seq_bytes + (size_t)n * PDSCH_LAYERS_INFO * sizeof(int)};
+}
+
+// What the three public functions do behind their null-argument test: the host's rules for every host job, in the order job, list, precoding (so the first
+// message reported is that of the first rule the first bad job breaks), then the enqueue.
+template <class JOB>
+int pdsch_modulate_layered(const char* who, miphy_ctx* ctx, const JOB* jobs, int jobs_on_device, uint32_t n, const uint16_t* prb_lists, uint32_t nof_list_entries,
+                           const float* weights, uint32_t nof_weights, const uint8_t* codewords, float* grid, void* stream)
+{
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "%s: batch too large (max 65535 transmissions per call)", who);
+  uint32_t max_layers = 4; // device-resident jobs: the kernels validate them, their lists and precodings; the scratch is sized for the most they may ask
+  if (!jobs_on_device) {
+    max_layers = 1;
+    const uint8_t no_ports[4] = {0, 1, 2, 3}; // (a precoded job's layers.ports is ignored)
+    for (uint32_t i = 0; i < n; ++i) {
+      const pdsch_job_parts             j  = parts_of(jobs[i]);
+      const miphy_pdsch_mod_layers_job& lj = *j.layers;
+      int rc = miphy_pdsch_mod_job_check(who, "job", i, lj.base, lj.nof_layers, j.precoding ? no_ports : lj.ports, 0);
+      if (!rc && j.mapped)
+        rc = miphy_pdsch_mod_list_check(who, "job", i, *j.mapped, prb_lists, nof_list_entries);
+      if (!rc && j.precoding)
+        rc = miphy_precoding_check(who, "job", i, *j.precoding, lj.nof_layers, lj.base.rb_mask, nof_weights);
+      if (rc)
+        return rc;
+      max_layers = lj.nof_layers > max_layers ? lj.nof_layers : max_layers;
+    }
+  }
+  return miphy_pdsch_modulate_layered_enqueue(ctx, jobs, jobs_on_device, n, max_layers, prb_lists, nof_list_entries, weights, nof_weights, codewords, grid,
+                                              (hipStream_t)stream);
+}
+} // namespace
+
+template <class JOB>
+int miphy_pdsch_modulate_layered_enqueue(miphy_ctx* ctx, const JOB* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers, const uint16_t* prb_lists,
+                                         uint32_t nof_list_entries, const float* weights, uint32_t nof_weights, const uint8_t* codewords, float* grid, hipStream_t s)
+{
+  constexpr bool     precoded = std::is_same<JOB, miphy_pdsch_mod_precoded_job>::value, mapped = precoded || std::is_same<JOB, miphy_pdsch_mod_mapped_job>::value;
+  const gold_tables* gt       = nullptr;
+  int                rc       = miphy_get_gold_tables(ctx, &gt);
+  if (rc)
+    return rc;
+  const JOB*      d_jobs  = jobs;
+  const uint16_t* d_lists = prb_lists;
+  const float2*   d_w     = reinterpret_cast<const float2*>(weights);
+  if (!jobs_on_device) { // host jobs with the host lists and host weights of their kind: one region of the staging ring, one upload
+    device_image         img;
+    const auto           js = img.put(jobs, (size_t)n);
+    image_slot<uint16_t> ls;
+    image_slot<float2>   ws;
+    if (mapped)
+      ls = img.put(prb_lists, (size_t)nof_list_entries);
+    if (precoded)
+      ws = img.put(d_w, (size_t)nof_weights);
+    const void* base = nullptr;
+    if ((rc = miphy_image_to_ring(ctx, img, s, &base)))
+      return rc;
+    d_jobs = js.at(base);
+    if (mapped)
+      d_lists = ls.at(base);
+    if (precoded)
+      d_w = ws.at(base);
+  }
+  const pdsch_layers_scratch sc  = pdsch_layers_scratch_of(n, max_layers);
+  void*                      seq = nullptr;
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, sc.bytes, &seq)))
+    return rc;
+  uint32_t* const sq = static_cast<uint32_t*>(seq);
+  int* const      info = sc.info(seq);
+  const dim3      chunks(n, 2 * max_layers), symbols(n, 14);
+  if constexpr (precoded) {
+    hipLaunchKernelGGL(pdsch_seq_precoded_kernel, chunks, dim3(512), 0, s, d_jobs, d_lists, nof_list_entries, nof_weights, gt, sq, info, sc.stride);
+    hipLaunchKernelGGL(pdsch_mod_precoded_kernel, symbols, dim3(256), 0, s, d_jobs, d_lists, d_w, codewords, (float2*)grid, (const uint32_t*)sq, (const int*)info,
+                       sc.stride);
+  } else if constexpr (mapped) {
+    hipLaunchKernelGGL(pdsch_seq_mapped_kernel, chunks, dim3(512), 0, s, d_jobs, d_lists, nof_list_entries, gt, sq, info, sc.stride);
+    hipLaunchKernelGGL(pdsch_mod_mapped_kernel, symbols, dim3(256), 0, s, d_jobs, d_lists, codewords, (float2*)grid, (const uint32_t*)sq, (const int*)info, sc.stride);
+  } else {
+    hipLaunchKernelGGL(pdsch_seq_layers_kernel, chunks, dim3(512), 0, s, d_jobs, gt, sq, info, sc.stride);
+    hipLaunchKernelGGL(pdsch_mod_layers_kernel, symbols, dim3(256), 0, s, d_jobs, codewords, (float2*)grid, (const uint32_t*)sq, (const int*)info, sc.stride);
+  }
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
+}
+#define PDSCH_ENQUEUE_FOR(JOB)                                                                                                                                 \
+  template int miphy_pdsch_modulate_layered_enqueue<JOB>(miphy_ctx*, const JOB*, int, uint32_t, uint32_t, const uint16_t*, uint32_t, const float*, uint32_t,   \
+                                                         const uint8_t*, float*, hipStream_t);
+PDSCH_ENQUEUE_FOR(miphy_pdsch_mod_layers_job)
+PDSCH_ENQUEUE_FOR(miphy_pdsch_mod_mapped_job)
+PDSCH_ENQUEUE_FOR(miphy_pdsch_mod_precoded_job)
+#undef PDSCH_ENQUEUE_FOR
+
 extern "C" int miphy_pdsch_modulate_layers_batch(miphy_ctx* ctx, const miphy_pdsch_mod_layers_job* jobs, int jobs_on_device, uint32_t n, const uint8_t* codewords,
                                                  float* grid, void* stream)
 {
   MIPHY_REQUIRE(ctx && jobs && codewords && grid, "miphy_pdsch_modulate_layers_batch: null argument");
-  if (n == 0)
-    return MIPHY_OK;
-  MIPHY_REQUIRE(n <= 65535, "pdsch_modulate_layers: batch too large (max 65535 transmissions per call)");
-  uint32_t max_layers = 4; // device-resident jobs: the kernels validate them, the scratch is sized for the most they may ask
-  if (!jobs_on_device) {
-    max_layers = 1;
-    for (uint32_t i = 0; i < n; ++i) {
-      if (int rc = miphy_pdsch_mod_job_check("pdsch_modulate_layers", "job", i, jobs[i].base, jobs[i].nof_layers, jobs[i].ports, 0))
-        return rc;
-      max_layers = jobs[i].nof_layers > max_layers ? jobs[i].nof_layers : max_layers;
-    }
-  }
-  return miphy_pdsch_modulate_layers_enqueue(ctx, jobs, jobs_on_device, n, max_layers, codewords, grid, (hipStream_t)stream);
-}
-
-int miphy_pdsch_modulate_layers_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_layers_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
-                                        const uint8_t* codewords, float* grid, hipStream_t s)
-{
-  const gold_tables* gt = nullptr;
-  int                rc = miphy_get_gold_tables(ctx, &gt);
-  if (rc)
-    return rc;
-  const void* d_jobs = nullptr;
-  if ((rc = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pdsch_mod_layers_job) * (size_t)n, s, &d_jobs)))
-    return rc;
-  // scratch: the scrambling sequences (a transmission on L layers has L times the bits of one layer: the stride grows with the batch's
-  // largest L), then PDSCH_LAYERS_INFO ints per transmission
-  const uint32_t stride = max_layers * (uint32_t)PDSCH_SEQ_STRIDE;
-  void*          seq    = nullptr;
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, (size_t)n * stride * sizeof(uint32_t) + (size_t)n * PDSCH_LAYERS_INFO * sizeof(int), &seq)))
-    return rc;
-  int* info = reinterpret_cast<int*>(static_cast<uint8_t*>(seq) + (size_t)n * stride * sizeof(uint32_t));
-  hipLaunchKernelGGL(pdsch_seq_layers_kernel, dim3(n, 2 * max_layers), dim3(512), 0, s, (const miphy_pdsch_mod_layers_job*)d_jobs, gt, (uint32_t*)seq, info, stride);
-  hipLaunchKernelGGL(pdsch_mod_layers_kernel, dim3(n, 14), dim3(256), 0, s, (const miphy_pdsch_mod_layers_job*)d_jobs, codewords, (float2*)grid,
-                     (const uint32_t*)seq, (const int*)info, stride);
-  MIPHY_HIP_CHECK(hipGetLastError());
-  return MIPHY_OK;
+  return pdsch_modulate_layered("pdsch_modulate_layers", ctx, jobs, jobs_on_device, n, nullptr, 0, nullptr, 0, codewords, grid, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------- PDSCH modulator, PRB lists in mapping order
@@ -1375,52 +1463,7 @@ extern "C" int miphy_pdsch_modulate_mapped_batch(miphy_ctx* ctx, const miphy_pds
                                                  uint32_t nof_list_entries, const uint8_t* codewords, float* grid, void* stream)
 {
   MIPHY_REQUIRE(ctx && jobs && codewords && grid && (prb_lists || nof_list_entries == 0), "miphy_pdsch_modulate_mapped_batch: null argument");
-  if (n == 0)
-    return MIPHY_OK;
-  MIPHY_REQUIRE(n <= 65535, "pdsch_modulate_mapped: batch too large (max 65535 transmissions per call)");
-  uint32_t max_layers = 4; // device-resident jobs: the kernels validate them and their lists, the scratch is sized for the most they may ask
-  if (!jobs_on_device) {
-    max_layers = 1;
-    for (uint32_t i = 0; i < n; ++i) {
-      const miphy_pdsch_mod_layers_job& lj = jobs[i].layers;
-      int rc = miphy_pdsch_mod_job_check("pdsch_modulate_mapped", "job", i, lj.base, lj.nof_layers, lj.ports, 0);
-      if (rc || (rc = miphy_pdsch_mod_list_check("pdsch_modulate_mapped", "job", i, jobs[i], prb_lists, nof_list_entries)))
-        return rc;
-      max_layers = lj.nof_layers > max_layers ? lj.nof_layers : max_layers;
-    }
-  }
-  return miphy_pdsch_modulate_mapped_enqueue(ctx, jobs, jobs_on_device, n, max_layers, prb_lists, nof_list_entries, codewords, grid, (hipStream_t)stream);
-}
-
-int miphy_pdsch_modulate_mapped_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_mapped_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
-                                        const uint16_t* prb_lists, uint32_t nof_list_entries, const uint8_t* codewords, float* grid, hipStream_t s)
-{
-  const gold_tables* gt = nullptr;
-  int                rc = miphy_get_gold_tables(ctx, &gt);
-  if (rc)
-    return rc;
-  const miphy_pdsch_mod_mapped_job* d_jobs  = jobs;
-  const uint16_t*                   d_lists = prb_lists;
-  if (!jobs_on_device) { // host jobs and host lists: one region of the staging ring, one upload
-    device_image img;
-    const auto   js = img.put(jobs, (size_t)n);
-    const auto   ls = img.put(prb_lists, (size_t)nof_list_entries);
-    const void*  base = nullptr;
-    if ((rc = miphy_image_to_ring(ctx, img, s, &base)))
-      return rc;
-    d_jobs = js.at(base), d_lists = ls.at(base);
-  }
-  // scratch: as miphy_pdsch_modulate_layers_enqueue lays it out
-  const uint32_t stride = max_layers * (uint32_t)PDSCH_SEQ_STRIDE;
-  void*          seq    = nullptr;
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, (size_t)n * stride * sizeof(uint32_t) + (size_t)n * PDSCH_LAYERS_INFO * sizeof(int), &seq)))
-    return rc;
-  int* info = reinterpret_cast<int*>(static_cast<uint8_t*>(seq) + (size_t)n * stride * sizeof(uint32_t));
-  hipLaunchKernelGGL(pdsch_seq_mapped_kernel, dim3(n, 2 * max_layers), dim3(512), 0, s, d_jobs, d_lists, nof_list_entries, gt, (uint32_t*)seq, info, stride);
-  hipLaunchKernelGGL(pdsch_mod_mapped_kernel, dim3(n, 14), dim3(256), 0, s, d_jobs, d_lists, codewords, (float2*)grid, (const uint32_t*)seq, (const int*)info,
-                     stride);
-  MIPHY_HIP_CHECK(hipGetLastError());
-  return MIPHY_OK;
+  return pdsch_modulate_layered("pdsch_modulate_mapped", ctx, jobs, jobs_on_device, n, prb_lists, nof_list_entries, nullptr, 0, codewords, grid, stream);
 }
 
 extern "C" int miphy_dmrs_pdsch_map_batch(miphy_ctx* ctx, const miphy_dmrs_pdsch_job* jobs, int jobs_on_device, uint32_t n, float* grid, void* stream)
@@ -1507,59 +1550,7 @@ extern "C" int miphy_pdsch_modulate_precoded_batch(miphy_ctx* ctx, const miphy_p
                                                    const uint8_t* codewords, float* grid, void* stream)
 {
   MIPHY_REQUIRE(ctx && jobs && weights && codewords && grid && (prb_lists || nof_list_entries == 0), "miphy_pdsch_modulate_precoded_batch: null argument");
-  if (n == 0)
-    return MIPHY_OK;
-  MIPHY_REQUIRE(n <= 65535, "pdsch_modulate_precoded: batch too large (max 65535 transmissions per call)");
-  uint32_t max_layers = 4; // device-resident jobs: the kernels validate them, their lists and precodings; the scratch is sized for the most they may ask
-  if (!jobs_on_device) {
-    max_layers = 1;
-    const uint8_t no_ports[4] = {0, 1, 2, 3}; // (layers.ports is ignored)
-    for (uint32_t i = 0; i < n; ++i) {
-      const miphy_pdsch_mod_layers_job& lj = jobs[i].mapped.layers;
-      int rc = miphy_pdsch_mod_job_check("pdsch_modulate_precoded", "job", i, lj.base, lj.nof_layers, no_ports, 0);
-      if (rc || (rc = miphy_pdsch_mod_list_check("pdsch_modulate_precoded", "job", i, jobs[i].mapped, prb_lists, nof_list_entries)) ||
-          (rc = miphy_precoding_check("pdsch_modulate_precoded", "job", i, jobs[i].precoding, lj.nof_layers, lj.base.rb_mask, nof_weights)))
-        return rc;
-      max_layers = lj.nof_layers > max_layers ? lj.nof_layers : max_layers;
-    }
-  }
-  return miphy_pdsch_modulate_precoded_enqueue(ctx, jobs, jobs_on_device, n, max_layers, prb_lists, nof_list_entries, weights, nof_weights, codewords, grid,
-                                               (hipStream_t)stream);
-}
-
-int miphy_pdsch_modulate_precoded_enqueue(miphy_ctx* ctx, const miphy_pdsch_mod_precoded_job* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers,
-                                          const uint16_t* prb_lists, uint32_t nof_list_entries, const float* weights, uint32_t nof_weights,
-                                          const uint8_t* codewords, float* grid, hipStream_t s)
-{
-  const gold_tables* gt = nullptr;
-  int                rc = miphy_get_gold_tables(ctx, &gt);
-  if (rc)
-    return rc;
-  const miphy_pdsch_mod_precoded_job* d_jobs  = jobs;
-  const uint16_t*                     d_lists = prb_lists;
-  const float2*                       d_w     = reinterpret_cast<const float2*>(weights);
-  if (!jobs_on_device) { // host jobs, lists and weights: one region of the staging ring, one upload
-    device_image img;
-    const auto   js = img.put(jobs, (size_t)n);
-    const auto   ls = img.put(prb_lists, (size_t)nof_list_entries);
-    const auto   ws = img.put(d_w, (size_t)nof_weights);
-    const void*  base = nullptr;
-    if ((rc = miphy_image_to_ring(ctx, img, s, &base)))
-      return rc;
-    d_jobs = js.at(base), d_lists = ls.at(base), d_w = ws.at(base);
-  }
-  // scratch: as miphy_pdsch_modulate_layers_enqueue lays it out
-  const uint32_t stride = max_layers * (uint32_t)PDSCH_SEQ_STRIDE;
-  void*          seq    = nullptr;
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, (size_t)n * stride * sizeof(uint32_t) + (size_t)n * PDSCH_LAYERS_INFO * sizeof(int), &seq)))
-    return rc;
-  int* info = reinterpret_cast<int*>(static_cast<uint8_t*>(seq) + (size_t)n * stride * sizeof(uint32_t));
-  hipLaunchKernelGGL(pdsch_seq_precoded_kernel, dim3(n, 2 * max_layers), dim3(512), 0, s, d_jobs, d_lists, nof_list_entries, nof_weights, gt, (uint32_t*)seq, info,
-                     stride);
-  hipLaunchKernelGGL(pdsch_mod_precoded_kernel, dim3(n, 14), dim3(256), 0, s, d_jobs, d_lists, d_w, codewords, (float2*)grid, (const uint32_t*)seq,
-                     (const int*)info, stride);
-  MIPHY_HIP_CHECK(hipGetLastError());
-  return MIPHY_OK;
+  return pdsch_modulate_layered("pdsch_modulate_precoded", ctx, jobs, jobs_on_device, n, prb_lists, nof_list_entries, weights, nof_weights, codewords, grid, stream);
 }
 
 int miphy_dmrs_pdsch_precoded_job_check(const char* who, const char* what, uint32_t i, const miphy_dmrs_pdsch_precoded_job& pj, uint32_t nof_weights)

@@ -85,6 +85,21 @@ int derive_one_layer_jobs(const miphy_pdsch_pdu* pdus, uint32_t n, std::vector<m
       return rc;
   return MIPHY_OK;
 }
+
+// The tail of every processor: the codewords (one bit per byte) in a workspace of the context, the encoder, then the form's modulator on the codewords
+// and its DM-RS mapper.
+template <class MOD, class DMRS>
+int pdsch_process_tail(miphy_ctx* ctx, const std::vector<miphy_pdsch_tb_desc>& tb, size_t cw_bytes, const uint8_t* tb_in, hipStream_t s, MOD&& modulate, DMRS&& map_dmrs)
+{
+  void* work = nullptr;
+  int   rc   = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, cw_bytes + 64, &work);
+  if (rc)
+    return rc;
+  uint8_t* d_cw = static_cast<uint8_t*>(work);
+  if ((rc = miphy_pdsch_encode_batch(ctx, tb.data(), (uint32_t)tb.size(), tb_in, d_cw, s)) || (rc = modulate(d_cw)))
+    return rc;
+  return map_dmrs();
+}
 } // namespace
 
 extern "C" int miphy_pdsch_process_batch(miphy_ctx* ctx, const miphy_pdsch_pdu* pdus, uint32_t n, const uint8_t* tb_in, float* grid, void* stream)
@@ -100,19 +115,14 @@ extern "C" int miphy_pdsch_process_batch(miphy_ctx* ctx, const miphy_pdsch_pdu* 
   int                               rc = derive_one_layer_jobs(pdus, n, tb, mj, dj, cw_bytes);
   if (rc)
     return rc;
-  void* work = nullptr; // codewords (one bit per byte) in a workspace of the context
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, cw_bytes + 64, &work)))
-    return rc;
-  uint8_t* d_cw = static_cast<uint8_t*>(work);
-  if ((rc = miphy_pdsch_encode_batch(ctx, tb.data(), n, tb_in, d_cw, s)))
-    return rc;
-  if ((rc = miphy_pdsch_modulate_batch(ctx, mj.data(), 0, n, d_cw, grid, s)))
-    return rc;
-  return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s);
+  return pdsch_process_tail(
+      ctx, tb, cw_bytes, tb_in, s, [&](const uint8_t* cw) { return miphy_pdsch_modulate_batch(ctx, mj.data(), 0, n, cw, grid, s); },
+      [&] { return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s); });
 }
 
-// ---- one codeword on 1..4 layers: the same composition with the encoder's nof_layers = L and nof_ch_symbols = REs x L, the layered modulator
-// and the DM-RS on L ports.
+// ---- one codeword on 1..4 layers, in three forms: layers on named grid ports, the same with the PRBs in the mapping order of a list (interleaved
+// VRB-to-PRB mapping), the same behind a precoding. One composition: the encoder's nof_layers = L and nof_ch_symbols = REs x L, the layered modulator
+// of the form, the DM-RS on L ports.
 extern "C" uint32_t miphy_pdsch_layers_pdu_nof_re(const miphy_pdsch_layers_pdu* pdu)
 {
   if (!pdu || pdu->nof_layers < 1 || pdu->nof_layers > 4)
@@ -121,10 +131,18 @@ extern "C" uint32_t miphy_pdsch_layers_pdu_nof_re(const miphy_pdsch_layers_pdu* 
 }
 
 namespace {
-// derive_pdsch_jobs for PDU i of a layered batch, with the layered modulator job and the encoder's limits: what miphy_pdsch_process_layers_batch and
-// miphy_pdsch_process_mapped_batch both ask of a PDU. max_layers: the largest nof_layers so far.
-int derive_layers_jobs(const char* who, uint32_t i, const miphy_pdsch_layers_pdu& p, miphy_pdsch_tb_desc& t, miphy_pdsch_mod_layers_job& lj, miphy_dmrs_pdsch_job& d,
-                       size_t& cw_bytes, uint32_t& max_layers)
+// The arrays of a layered call next to its PDUs: null / 0 where the form has none.
+struct pdsch_pdu_arrays {
+  const uint16_t* prb_lists;
+  uint32_t        nof_list_entries;
+  const float*    weights;
+  uint32_t        nof_weights;
+};
+
+// derive_pdsch_jobs for PDU i of a layered batch, with the layered modulator job and the encoder's limits: what every layered processor asks of a PDU.
+// max_layers: the largest nof_layers so far.
+int derive_layers_jobs(const char* who, uint32_t i, const miphy_pdsch_layers_pdu& p, const pdsch_pdu_arrays&, miphy_pdsch_tb_desc& t, miphy_pdsch_mod_layers_job& lj,
+                       miphy_dmrs_pdsch_job& d, size_t& cw_bytes, uint32_t& max_layers)
 {
   const uint32_t L = p.nof_layers;
   lj               = {};
@@ -144,109 +162,84 @@ int derive_layers_jobs(const char* who, uint32_t i, const miphy_pdsch_layers_pdu
   MIPHY_REQUIRE(nre >= ncb, "%s: PDU %u: %u REs per layer cannot carry %u codeblocks", who, i, nre, (unsigned)ncb);
   return MIPHY_OK;
 }
+
+// The same for a mapped PDU: the records of its layers, then its list under the list rules. The DM-RS job takes rb_mask, as derive_pdsch_jobs fills it:
+// the DM-RS does not depend on the mapping order.
+int derive_layers_jobs(const char* who, uint32_t i, const miphy_pdsch_mapped_pdu& p, const pdsch_pdu_arrays& a, miphy_pdsch_tb_desc& t, miphy_pdsch_mod_mapped_job& mj,
+                       miphy_dmrs_pdsch_job& d, size_t& cw_bytes, uint32_t& max_layers)
+{
+  if (int rc = derive_layers_jobs(who, i, p.layers, a, t, mj.layers, d, cw_bytes, max_layers))
+    return rc;
+  mj.prb_list_offset = p.prb_list_offset, mj.nof_prb = p.nof_prb;
+  return miphy_pdsch_mod_list_check(who, "PDU", i, mj, a.prb_lists, a.nof_list_entries);
+}
+
+// The same for a precoded PDU: the records of the mapped PDU, then the same matrices for the data and its DM-RS under the precoding rules. The layers'
+// ports are not used (antenna port a is grid port precoding.ports[a]): the PDU's rules are checked with the layers on ports 0 .. L - 1.
+int derive_layers_jobs(const char* who, uint32_t i, const miphy_pdsch_precoded_pdu& p, const pdsch_pdu_arrays& a, miphy_pdsch_tb_desc& t,
+                       miphy_pdsch_mod_precoded_job& mj, miphy_dmrs_pdsch_precoded_job& dj, size_t& cw_bytes, uint32_t& max_layers)
+{
+  miphy_pdsch_mapped_pdu mp = p.mapped;
+  for (uint8_t ly = 0; ly < 4; ++ly)
+    mp.layers.ports[ly] = ly;
+  if (int rc = derive_layers_jobs(who, i, mp, a, t, mj.mapped, dj.base, cw_bytes, max_layers))
+    return rc;
+  mj.precoding = dj.precoding = p.precoding;
+  return miphy_dmrs_pdsch_precoded_job_check(who, "PDU", i, dj, a.nof_weights);
+}
+
+// A layered processor behind its null-argument test: the records of every PDU (MJ: the modulator job of the form, DJ: its DM-RS job), refused before
+// anything is enqueued or allocated, then the tail. map_dmrs(jobs, stream): the DM-RS mapper of the form.
+template <class MJ, class DJ, class PDU, class DMRS>
+int pdsch_process_layered(const char* who, miphy_ctx* ctx, const PDU* pdus, uint32_t n, const pdsch_pdu_arrays& a, const uint8_t* tb_in, float* grid, void* stream,
+                          DMRS&& map_dmrs)
+{
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "%s: at most 65535 PDUs per call", who);
+  hipStream_t                      s = (hipStream_t)stream;
+  std::vector<miphy_pdsch_tb_desc> tb(n);
+  std::vector<MJ>                  mj(n);
+  std::vector<DJ>                  dj(n);
+  size_t                           cw_bytes   = 0;
+  uint32_t                         max_layers = 1;
+  for (uint32_t i = 0; i < n; ++i)
+    if (int rc = derive_layers_jobs(who, i, pdus[i], a, tb[i], mj[i], dj[i], cw_bytes, max_layers))
+      return rc;
+  return pdsch_process_tail(
+      ctx, tb, cw_bytes, tb_in, s,
+      [&](const uint8_t* cw) { // (the jobs passed the modulator's host rules in derive_layers_jobs)
+        return miphy_pdsch_modulate_layered_enqueue(ctx, mj.data(), 0, n, max_layers, a.prb_lists, a.nof_list_entries, a.weights, a.nof_weights, cw, grid, s);
+      },
+      [&] { return map_dmrs(dj.data(), s); });
+}
 } // namespace
 
 extern "C" int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsch_layers_pdu* pdus, uint32_t n, const uint8_t* tb_in, float* grid, void* stream)
 {
   MIPHY_REQUIRE(ctx && pdus && tb_in && grid, "miphy_pdsch_process_layers_batch: null argument");
-  if (n == 0)
-    return MIPHY_OK;
-  MIPHY_REQUIRE(n <= 65535, "pdsch_process_layers: at most 65535 PDUs per call");
-  hipStream_t                             s = (hipStream_t)stream;
-  std::vector<miphy_pdsch_tb_desc>        tb(n);
-  std::vector<miphy_dmrs_pdsch_job>       dj(n);
-  std::vector<miphy_pdsch_mod_layers_job> lj(n);
-  size_t                                  cw_bytes   = 0;
-  uint32_t                                max_layers = 1;
-  int                                     rc;
-  for (uint32_t i = 0; i < n; ++i)
-    if ((rc = derive_layers_jobs("pdsch_process_layers", i, pdus[i], tb[i], lj[i], dj[i], cw_bytes, max_layers)))
-      return rc;
-  void* work = nullptr; // codewords (one bit per byte) in a workspace of the context
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, cw_bytes + 64, &work)))
-    return rc;
-  uint8_t* d_cw = static_cast<uint8_t*>(work);
-  if ((rc = miphy_pdsch_encode_batch(ctx, tb.data(), n, tb_in, d_cw, s)))
-    return rc;
-  if ((rc = miphy_pdsch_modulate_layers_enqueue(ctx, lj.data(), 0, n, max_layers, d_cw, grid, s))) // (the jobs passed miphy_pdsch_mod_job_check in derive_pdsch_jobs)
-    return rc;
-  return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s);
+  return pdsch_process_layered<miphy_pdsch_mod_layers_job, miphy_dmrs_pdsch_job>(
+      "pdsch_process_layers", ctx, pdus, n, {nullptr, 0, nullptr, 0}, tb_in, grid, stream,
+      [&](const miphy_dmrs_pdsch_job* dj, hipStream_t s) { return miphy_dmrs_pdsch_map_batch(ctx, dj, 0, n, grid, s); });
 }
 
-// ---- PRB lists in mapping order (interleaved VRB-to-PRB mapping): the same composition with the mapped modulator in the middle. The DM-RS job takes
-// rb_mask, as derive_pdsch_jobs fills it: the DM-RS does not depend on the mapping order.
 extern "C" int miphy_pdsch_process_mapped_batch(miphy_ctx* ctx, const miphy_pdsch_mapped_pdu* pdus, uint32_t n, const uint16_t* prb_lists,
                                                 uint32_t nof_list_entries, const uint8_t* tb_in, float* grid, void* stream)
 {
   MIPHY_REQUIRE(ctx && pdus && tb_in && grid && (prb_lists || nof_list_entries == 0), "miphy_pdsch_process_mapped_batch: null argument");
-  if (n == 0)
-    return MIPHY_OK;
-  MIPHY_REQUIRE(n <= 65535, "pdsch_process_mapped: at most 65535 PDUs per call");
-  hipStream_t                             s = (hipStream_t)stream;
-  std::vector<miphy_pdsch_tb_desc>        tb(n);
-  std::vector<miphy_dmrs_pdsch_job>       dj(n);
-  std::vector<miphy_pdsch_mod_mapped_job> mj(n);
-  size_t                                  cw_bytes   = 0;
-  uint32_t                                max_layers = 1;
-  int                                     rc;
-  for (uint32_t i = 0; i < n; ++i) {
-    mj[i] = {};
-    if ((rc = derive_layers_jobs("pdsch_process_mapped", i, pdus[i].layers, tb[i], mj[i].layers, dj[i], cw_bytes, max_layers)))
-      return rc;
-    mj[i].prb_list_offset = pdus[i].prb_list_offset, mj[i].nof_prb = pdus[i].nof_prb;
-    if ((rc = miphy_pdsch_mod_list_check("pdsch_process_mapped", "PDU", i, mj[i], prb_lists, nof_list_entries)))
-      return rc;
-  }
-  void* work = nullptr; // codewords (one bit per byte) in a workspace of the context
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, cw_bytes + 64, &work)))
-    return rc;
-  uint8_t* d_cw = static_cast<uint8_t*>(work);
-  if ((rc = miphy_pdsch_encode_batch(ctx, tb.data(), n, tb_in, d_cw, s)))
-    return rc;
-  if ((rc = miphy_pdsch_modulate_mapped_enqueue(ctx, mj.data(), 0, n, max_layers, prb_lists, nof_list_entries, d_cw, grid, s)))
-    return rc;
-  return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s);
+  return pdsch_process_layered<miphy_pdsch_mod_mapped_job, miphy_dmrs_pdsch_job>(
+      "pdsch_process_mapped", ctx, pdus, n, {prb_lists, nof_list_entries, nullptr, 0}, tb_in, grid, stream,
+      [&](const miphy_dmrs_pdsch_job* dj, hipStream_t s) { return miphy_dmrs_pdsch_map_batch(ctx, dj, 0, n, grid, s); });
 }
 
-// ---- precoding: the mapped composition with the two precoded kernels in the middle, the same matrices for the data and its DM-RS. The layers' ports are
-// not used (antenna port a is grid port precoding.ports[a]): the PDU's rules are checked with the layers on ports 0 .. L - 1.
 extern "C" int miphy_pdsch_process_precoded_batch(miphy_ctx* ctx, const miphy_pdsch_precoded_pdu* pdus, uint32_t n, const uint16_t* prb_lists,
                                                   uint32_t nof_list_entries, const float* weights, uint32_t nof_weights, const uint8_t* tb_in, float* grid,
                                                   void* stream)
 {
   MIPHY_REQUIRE(ctx && pdus && weights && tb_in && grid && (prb_lists || nof_list_entries == 0), "miphy_pdsch_process_precoded_batch: null argument");
-  if (n == 0)
-    return MIPHY_OK;
-  MIPHY_REQUIRE(n <= 65535, "pdsch_process_precoded: at most 65535 PDUs per call");
-  hipStream_t                                s = (hipStream_t)stream;
-  std::vector<miphy_pdsch_tb_desc>           tb(n);
-  std::vector<miphy_dmrs_pdsch_precoded_job> dj(n);
-  std::vector<miphy_pdsch_mod_precoded_job>  mj(n);
-  size_t                                     cw_bytes   = 0;
-  uint32_t                                   max_layers = 1;
-  int                                        rc;
-  for (uint32_t i = 0; i < n; ++i) {
-    mj[i] = {}, dj[i] = {};
-    miphy_pdsch_layers_pdu lp = pdus[i].mapped.layers;
-    for (uint8_t ly = 0; ly < 4; ++ly)
-      lp.ports[ly] = ly;
-    if ((rc = derive_layers_jobs("pdsch_process_precoded", i, lp, tb[i], mj[i].mapped.layers, dj[i].base, cw_bytes, max_layers)))
-      return rc;
-    mj[i].mapped.prb_list_offset = pdus[i].mapped.prb_list_offset, mj[i].mapped.nof_prb = pdus[i].mapped.nof_prb;
-    mj[i].precoding = dj[i].precoding = pdus[i].precoding;
-    if ((rc = miphy_pdsch_mod_list_check("pdsch_process_precoded", "PDU", i, mj[i].mapped, prb_lists, nof_list_entries)) ||
-        (rc = miphy_dmrs_pdsch_precoded_job_check("pdsch_process_precoded", "PDU", i, dj[i], nof_weights)))
-      return rc;
-  }
-  void* work = nullptr; // codewords (one bit per byte) in a workspace of the context
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, cw_bytes + 64, &work)))
-    return rc;
-  uint8_t* d_cw = static_cast<uint8_t*>(work);
-  if ((rc = miphy_pdsch_encode_batch(ctx, tb.data(), n, tb_in, d_cw, s)))
-    return rc;
-  if ((rc = miphy_pdsch_modulate_precoded_enqueue(ctx, mj.data(), 0, n, max_layers, prb_lists, nof_list_entries, weights, nof_weights, d_cw, grid, s)))
-    return rc;
-  return miphy_dmrs_pdsch_map_precoded_batch(ctx, dj.data(), 0, n, weights, nof_weights, grid, s);
+  return pdsch_process_layered<miphy_pdsch_mod_precoded_job, miphy_dmrs_pdsch_precoded_job>(
+      "pdsch_process_precoded", ctx, pdus, n, {prb_lists, nof_list_entries, weights, nof_weights}, tb_in, grid, stream,
+      [&](const miphy_dmrs_pdsch_precoded_job* dj, hipStream_t s) { return miphy_dmrs_pdsch_map_precoded_batch(ctx, dj, 0, n, weights, nof_weights, grid, s); });
 }
 
 // ---- prepared form: PDU validation, segmentation, every descriptor upload and the scratch happen once; a run is the seven launches of the

@@ -678,31 +678,6 @@ class Context:
         pdus = np.ascontiguousarray(pdus)
         check(lib().miphy_pdsch_process_layers_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, _dptr(tb_in), _dptr(grid), _stream_ptr(stream)))
 
-    def pdsch_modulate_mapped_batch(self, jobs, prb_lists, codewords, grid, stream=None):
-        """pdsch_modulate_layers_batch with the PRBs of each job in the mapping order of its list (interleaved VRB-to-PRB mapping: vrb_to_prb_list).
-        jobs and prb_lists live in the same place: a PdschModMappedJob array with a uint16 numpy array (None: no lists), or uint8 and int16 /
-        uint16 device tensors holding the same bytes."""
-        import torch
-        jobs, n, ptr, on_dev = self._descs(jobs, PdschModMappedJob)
-        if on_dev:
-            assert prb_lists is None or prb_lists.dtype in (torch.int16, torch.uint16)
-            lptr, nl = (_dptr(prb_lists), prb_lists.numel()) if prb_lists is not None and prb_lists.numel() else (None, 0)
-        else:
-            prb_lists = np.zeros(0, np.uint16) if prb_lists is None else np.ascontiguousarray(prb_lists)
-            assert prb_lists.dtype == np.uint16
-            lptr, nl = (C.c_void_p(prb_lists.ctypes.data), prb_lists.size) if prb_lists.size else (None, 0)
-        check(lib().miphy_pdsch_modulate_mapped_batch(self.h, ptr, on_dev, n, lptr, nl, _dptr(codewords), _dptr(grid), _stream_ptr(stream)))
-
-    def pdsch_process_mapped_batch(self, pdus, prb_lists, tb_in, grid, stream=None):
-        """pdsch_process_layers_batch for PDUs whose PRBs are mapped in the order of their lists (host descriptors, host uint16 lists or None)."""
-        assert isinstance(pdus, np.ndarray) and pdus.dtype == PdschMappedPdu
-        pdus = np.ascontiguousarray(pdus)
-        prb_lists = np.zeros(0, np.uint16) if prb_lists is None else np.ascontiguousarray(prb_lists)
-        assert prb_lists.dtype == np.uint16
-        lptr, nl = (C.c_void_p(prb_lists.ctypes.data), prb_lists.size) if prb_lists.size else (None, 0)
-        check(lib().miphy_pdsch_process_mapped_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, lptr, nl, _dptr(tb_in), _dptr(grid), _stream_ptr(stream)))
-
-    # ------------------------------------------------------------------ precoding: layers to antenna ports through per-PRG weights
     @staticmethod
     def _host_or_device(a, on_dev, np_dtype, torch_dtypes, what):
         """(pointer, elements) of an array that lives where the jobs live: numpy of np_dtype, or a device tensor of one of torch_dtypes."""
@@ -713,6 +688,23 @@ class Context:
         assert a.dtype == np_dtype, what
         return (C.c_void_p(a.ctypes.data), a.size) if a.size else (None, 0)
 
+    def pdsch_modulate_mapped_batch(self, jobs, prb_lists, codewords, grid, stream=None):
+        """pdsch_modulate_layers_batch with the PRBs of each job in the mapping order of its list (interleaved VRB-to-PRB mapping: vrb_to_prb_list).
+        jobs and prb_lists live in the same place: a PdschModMappedJob array with a uint16 numpy array (None: no lists), or uint8 and int16 /
+        uint16 device tensors holding the same bytes."""
+        import torch
+        jobs, n, ptr, on_dev = self._descs(jobs, PdschModMappedJob)
+        lptr, nl = self._host_or_device(prb_lists, on_dev, np.uint16, (torch.int16, torch.uint16), "prb_lists")
+        check(lib().miphy_pdsch_modulate_mapped_batch(self.h, ptr, on_dev, n, lptr, nl, _dptr(codewords), _dptr(grid), _stream_ptr(stream)))
+
+    def pdsch_process_mapped_batch(self, pdus, prb_lists, tb_in, grid, stream=None):
+        """pdsch_process_layers_batch for PDUs whose PRBs are mapped in the order of their lists (host descriptors, host uint16 lists or None)."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PdschMappedPdu
+        pdus = np.ascontiguousarray(pdus)
+        lptr, nl = self._host_or_device(prb_lists, 0, np.uint16, (), "prb_lists")
+        check(lib().miphy_pdsch_process_mapped_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, lptr, nl, _dptr(tb_in), _dptr(grid), _stream_ptr(stream)))
+
+    # ------------------------------------------------------------------ precoding: layers to antenna ports through per-PRG weights
     def channel_precode_batch(self, jobs, weights, x, out, stream=None):
         """channel_precoder::apply_precoding for a batch of PrecodeJob: out[a][i] = sum_ly W[a][ly] x[ly][i]. jobs and weights live in the same place: a
         PrecodeJob array with a complex64 numpy array, or uint8 and complex64 device tensors; x and out are complex64 device tensors."""
