@@ -506,7 +506,7 @@ int miphy_dmrs_pdsch_map_batch(miphy_ctx* ctx, const miphy_dmrs_pdsch_job* jobs,
  * distinct ports below 16, nof_bits = REs x L x mod and the rules of the one-layer entry point); a device-resident job that breaks a
  * rule is skipped by the kernels. PRBs are mapped in ascending order here; any other order, the interleaved VRB-to-PRB mapping of TS 38.211
  * 7.3.1.6 among them, goes through miphy_pdsch_modulate_mapped_batch below, precoding matrices through miphy_pdsch_modulate_precoded_batch.
- * Not supported: two codewords (5..8 layers). */
+ * Two codewords (5..8 layers): miphy_pdsch_modulate_codewords_batch below. */
 typedef struct {
   miphy_pdsch_mod_job base; /* base.port is ignored; base.nof_bits = miphy_pdsch_mod_layers_nof_re() x nof_layers x mod */
   uint8_t nof_layers;       /* 1..4 */
@@ -562,6 +562,35 @@ int miphy_pdsch_modulate_mapped_batch(miphy_ctx* ctx, const miphy_pdsch_mod_mapp
                                       const uint16_t* prb_lists /* where the jobs are; may be NULL when nof_list_entries is 0 */,
                                       uint32_t nof_list_entries, const uint8_t* codewords /* device */, float* grid /* device cf_t */, void* stream);
 
+/* PDSCH modulator on one or two codewords, 1..8 layers (TS 38.211 Table 7.3.1.3-1; the contract is orc_pdsch_modulate with two codeword
+ * arguments). With L = nof_layers = 5..8, codeword 0 has L0 = floor(L / 2) layers and codeword 1 has L1 = L - L0: layer ly < L0 carries
+ * d0(L0 i + ly) and layer L0 + m carries d1(L1 i + m) on the resource element of rank i, layer ly on grid port ports[ly]. Codeword q is
+ * scrambled with c_init = rnti 2^15 + q 2^14 + n_id; the pi/2-BPSK rotation follows the parity of the symbol index within its own codeword;
+ * one scaling applies to both. RE selection, the list and its order, and "only the mapped REs of the named ports are written" are as in
+ * miphy_pdsch_modulate_mapped_batch, and one job costs one symbol setup and one launch pair for both codewords. With L = 1..4 the job is
+ * one codeword: mod1, nof_bits1 and cw1_offset are ignored and the call writes the bytes miphy_pdsch_modulate_mapped_batch writes.
+ * Rules: those of the fields and the list of the mapped entry point; L in 1..8; ports[0 .. L - 1] distinct and below 16; with L >= 5 mod1
+ * valid; nof_bits = REs x L0 x mod (L0 = L up to four layers) and nof_bits1 = REs x L1 x mod1. A host job that breaks one is refused with
+ * MIPHY_EINVAL and "pdsch_modulate_codewords: job <i>: ...", nothing enqueued; a device-resident job that breaks any rule of either
+ * codeword is skipped whole. Still out: precoding of two codewords (miphy_precoding stays one codeword on 1..4 layers). */
+typedef struct {
+  miphy_pdsch_mod_mapped_job mapped; /* codeword 0 (base.mod, base.nof_bits, base.cw_offset) and everything the two codewords share;
+                                        mapped.layers.nof_layers and mapped.layers.ports are ignored */
+  uint8_t  nof_layers;               /* 1..8; 1..4: one codeword, 5..8: two */
+  uint8_t  mod1;                     /* codeword 1: bits per symbol */
+  uint8_t  ports[8];                 /* grid port of each layer, distinct, < 16 */
+  uint8_t  pad[2];
+  uint32_t nof_bits1;                /* codeword 1: miphy_pdsch_mod_codewords_nof_re() x L1 x mod1 */
+  uint64_t cw1_offset;               /* codeword 1: byte offset (one bit per byte) */
+} miphy_pdsch_mod_codewords_job;
+typedef char miphy_pdsch_mod_codewords_job_is_320_bytes[sizeof(miphy_pdsch_mod_codewords_job) == 320 ? 1 : -1];
+
+uint32_t miphy_pdsch_mod_codewords_nof_re(const miphy_pdsch_mod_codewords_job* job); /* host: data REs per layer; 0 on an invalid job */
+int miphy_pdsch_modulate_codewords_batch(miphy_ctx* ctx, const miphy_pdsch_mod_codewords_job* jobs, int jobs_on_device, uint32_t n,
+                                         const uint16_t* prb_lists /* where the jobs are; may be NULL when nof_list_entries is 0 */,
+                                         uint32_t nof_list_entries, const uint8_t* codewords /* device */, float* grid /* device cf_t */,
+                                         void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Precoding  --  layers to antenna ports through one weight matrix per PRG
  *   include/srsran/ran/precoding/precoding_configuration.h (the layout: weights per layer, port and PRG, PRG 0 starts at CRB 0),
@@ -614,7 +643,8 @@ int miphy_channel_precode_batch(miphy_ctx* ctx, const miphy_precode_job* jobs, i
  * PRB r, receives y_a = sum_ly W[r / prg_size][a][ly] x^(ly)(i) on grid port precoding.ports[a] for every antenna port a. mapped.layers.ports
  * is ignored. Every data RE of every one of the nof_ports ports is stored (a zero matrix row stores zeros), nothing else is touched. The
  * PRG of an RE follows the place of its PRB in the grid, never its place in the list. miphy_pdsch_mod_layers_nof_re(&job.mapped.layers)
- * stays the size function. Jobs, lists and weights live in the same place. Not supported: two codewords (5..8 layers). */
+ * stays the size function. Jobs, lists and weights live in the same place. Two codewords (5..8 layers) go through
+ * miphy_pdsch_modulate_codewords_batch, without precoding; still out: precoding of two codewords. */
 typedef struct {
   miphy_pdsch_mod_mapped_job mapped;
   miphy_precoding            precoding; /* precoding.nof_layers = mapped.layers.nof_layers */
@@ -1284,7 +1314,8 @@ int miphy_pdsch_process_layers_batch(miphy_ctx* ctx, const miphy_pdsch_layers_pd
  * order. The list of PDU p is prb_lists[prb_list_offset .. + nof_prb - 1] (host memory) and obeys the list rule of
  * miphy_pdsch_modulate_mapped_batch; nof_prb = 0: no list, and a batch without lists writes the bytes miphy_pdsch_process_layers_batch
  * writes. Every PDU and every list is checked before anything is enqueued or allocated, with the limits of the layered processor. PDUs are
- * host records; there is no prepared plan for this entry point. Precoding: miphy_pdsch_process_precoded_batch. Not supported: two codewords. */
+ * host records; there is no prepared plan for this entry point. Precoding: miphy_pdsch_process_precoded_batch. Two codewords (5..8 layers):
+ * miphy_pdsch_process_codewords_batch. */
 typedef struct {
   miphy_pdsch_layers_pdu layers; /* layers.base.rb_mask = the PRBs of the list */
   uint32_t prb_list_offset;      /* uint16 index into prb_lists */
@@ -1295,11 +1326,42 @@ int miphy_pdsch_process_mapped_batch(miphy_ctx* ctx, const miphy_pdsch_mapped_pd
                                      uint32_t nof_list_entries, const uint8_t* tb_in /* device */,
                                      float* grid /* device cf_t; only the mapped REs are written */, void* stream);
 
+/* PDSCH processor on one or two transport blocks, 1..8 layers: miphy_pdsch_process_mapped_batch with miphy_pdsch_modulate_codewords_batch in
+ * the middle. With L = nof_layers = 5..8 the PDU carries two transport blocks: block q is encoded on its own L_q layers (L0 = floor(L / 2),
+ * L1 = L - L0) with its own base graph, redundancy version and modulation; tbs_lbrm_bytes, the scrambling identities, the two power ratios
+ * and the allocation are shared (pdsch_processor::pdu_t). The contract is the oracle chain: orc_pdsch_encode per transport block with
+ * nof_layers = L_q and nof_ch_symbols = REs x L_q, orc_pdsch_modulate with both codewords and the list, orc_dmrs_pdsch_map on DM-RS ports
+ * 1000 .. 1000 + L - 1 of type 1, DM-RS port p on grid port ports[p]. Every PDU, list and both transport blocks are checked before anything
+ * is enqueued or allocated ("pdsch_process_codewords: PDU <i>: ..."; the rules of the PDU record that every processor words as
+ * "pdsch_process: PDU <i>: ..." keep that wording, for either transport block): per transport block at most 52 codeblocks, at least one RE
+ * per layer for each codeblock, rv <= 3. DM-RS ports 1004 .. 1007 of type 1 exist only on a double-symbol DM-RS, so for L >= 5 two more rules apply:
+ * nof_cdm_groups_without_data = 2, and every set bit of dmrs_symbols_mask belongs to a run of exactly two adjacent symbols. With L <= 4 the
+ * fields of transport block 1 are ignored, and the call writes the bytes miphy_pdsch_process_mapped_batch writes and refuses what it
+ * refuses. mapped.layers.nof_layers and mapped.layers.ports are ignored. Still out: precoding of two codewords, a prepared plan,
+ * device-resident PDUs, more than 52 codeblocks per transport block. */
+typedef struct {
+  miphy_pdsch_mapped_pdu mapped; /* transport block 0 (base.bg, rv, mod, tb_bytes, tb_offset) and everything the two share */
+  uint8_t  nof_layers;           /* 1..8; 1..4: one transport block, 5..8: two */
+  uint8_t  ports[8];             /* grid port of each layer (and of DM-RS port 1000 + layer), distinct, < 16 */
+  uint8_t  bg1;                  /* transport block 1 */
+  uint8_t  rv1;
+  uint8_t  mod1;
+  uint32_t tb_bytes1;
+  uint64_t tb_offset1;
+} miphy_pdsch_codewords_pdu;
+typedef char miphy_pdsch_codewords_pdu_is_344_bytes[sizeof(miphy_pdsch_codewords_pdu) == 344 ? 1 : -1];
+
+/* Data REs of the allocation per layer; 0 on an invalid PDU. Host function. */
+uint32_t miphy_pdsch_codewords_pdu_nof_re(const miphy_pdsch_codewords_pdu* pdu);
+int miphy_pdsch_process_codewords_batch(miphy_ctx* ctx, const miphy_pdsch_codewords_pdu* pdus /* host */, uint32_t n, const uint16_t* prb_lists /* host */,
+                                        uint32_t nof_list_entries, const uint8_t* tb_in /* device */,
+                                        float* grid /* device cf_t; only the mapped REs are written */, void* stream);
+
 /* PDSCH processor with precoding: miphy_pdsch_process_mapped_batch with miphy_pdsch_modulate_precoded_batch and
  * miphy_dmrs_pdsch_map_precoded_batch in the middle -- the same matrices for the data and its DM-RS, the two scalings of the one-layer
  * processor. mapped.layers.ports is ignored: antenna port a is grid port precoding.ports[a]. PDUs, lists and weights are host memory; every
- * PDU, list and precoding is checked before anything is enqueued or allocated. Not supported: two codewords, a prepared plan,
- * device-resident PDUs. */
+ * PDU, list and precoding is checked before anything is enqueued or allocated. Still out: precoding of two codewords (they go, without
+ * precoding, through miphy_pdsch_process_codewords_batch), a prepared plan, device-resident PDUs. */
 typedef struct {
   miphy_pdsch_mapped_pdu mapped;
   miphy_precoding        precoding; /* precoding.nof_layers = mapped.layers.nof_layers */

@@ -2457,7 +2457,8 @@ inline std::shared_ptr<srsran::channel_precoder_factory> create_channel_precoder
 /// allocation -- the configurations the 23.5 software modulator handles correctly -- and, beyond it, one codeword on two to four
 /// layers (config.ports.size() layers, layer ly on port config.ports[ly]) over miphy_pdsch_modulate_layers_batch. An allocation that is
 /// not contiguous or is interleaved goes over miphy_pdsch_modulate_mapped_batch with rb_allocation::get_prb_indices as the list in
-/// mapping order (where the reference's vrb_to_prb_mapper deviates from TS 38.211 7.3.1.6).
+/// mapping order (where the reference's vrb_to_prb_mapper deviates from TS 38.211 7.3.1.6). Two codewords on five to eight
+/// layers (TS 38.211 Table 7.3.1.3-1) go over miphy_pdsch_modulate_codewords_batch, with the list where the allocation is not contiguous.
 class pdsch_modulator_hip : public srsran::pdsch_modulator
 {
 public:
@@ -2465,16 +2466,37 @@ public:
   void modulate(srsran::resource_grid_writer& grid, srsran::span<const srsran::bit_buffer> codewords, const config_t& config) override
   {
     const unsigned nlayers = config.ports.size();
-    srsran_assert(nlayers >= 1 && nlayers <= 4 && codewords.size() == 1, "Only one codeword on one to four layers is supported.");
+    srsran_assert((nlayers >= 1 && nlayers <= 4 && codewords.size() == 1) || (nlayers >= 5 && nlayers <= 8 && codewords.size() == 2),
+                  "Only one codeword on one to four layers or two codewords on five to eight layers are supported.");
     const srsran::bounded_bitset<srsran::MAX_RB> prb = config.freq_allocation.get_prb_mask(config.bwp_start_rb, config.bwp_size_rb);
     const unsigned                               nprb = prb.size(), nsc = nprb * 12;
     const miphy_pdsch_mod_job                    j    = job_of(config, codewords[0], prb);
+    const size_t                                 cw1_offset = (bits.size() + 15) & ~static_cast<size_t>(15);
+    if (codewords.size() == 2) { // the bits of codeword 1 behind those of codeword 0
+      bits.resize(cw1_offset + codewords[1].size());
+      for (unsigned i = 0; i != codewords[1].size(); ++i) {
+        bits[cw1_offset + i] = codewords[1].extract<uint8_t>(i, 1);
+      }
+    }
     host.assign(static_cast<size_t>(nlayers) * 14 * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernel"
     auto* d_cw = static_cast<uint8_t*>(c->buf(0, bits.size() + 16));
     auto* d_g  = static_cast<float*>(c->buf(1, host.size() * sizeof(srsran::cf_t)));
     c->h2d(d_cw, bits.data(), bits.size());
     c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
-    if (!config.freq_allocation.is_contiguous()) {
+    if (codewords.size() == 2) {
+      srsran::static_vector<uint16_t, srsran::MAX_RB> list;
+      miphy_pdsch_mod_codewords_job                   cj = {};
+      if (!config.freq_allocation.is_contiguous()) {
+        list              = config.freq_allocation.get_prb_indices(config.bwp_start_rb, config.bwp_size_rb);
+        cj.mapped.nof_prb = list.size();
+      }
+      cj.mapped.layers.base = j, cj.nof_layers = nlayers, cj.mod1 = srsran::get_bits_per_symbol(config.modulation2);
+      cj.nof_bits1 = codewords[1].size(), cj.cw1_offset = cw1_offset;
+      for (unsigned ly = 0; ly != nlayers; ++ly) {
+        cj.ports[ly] = ly; // the staging grid has one port per layer
+      }
+      context::check(miphy_pdsch_modulate_codewords_batch(c->ctx, &cj, 0, 1, list.data(), list.size(), d_cw, d_g, c->stream), "pdsch_modulate_codewords");
+    } else if (!config.freq_allocation.is_contiguous()) {
       const srsran::static_vector<uint16_t, srsran::MAX_RB> list = config.freq_allocation.get_prb_indices(config.bwp_start_rb, config.bwp_size_rb);
       miphy_pdsch_mod_mapped_job                            mj   = {};
       mj.layers.base = j, mj.layers.nof_layers = nlayers, mj.prb_list_offset = 0, mj.nof_prb = list.size();
@@ -2621,6 +2643,7 @@ private:
 /// srsran::pdsch_processor over miphy_pdsch_process_batch (pdsch_processor.h:164-166): encoding, modulation and DM-RS generation
 /// in one device pass; the transport block goes up, the written resource elements come back. A PDU of one codeword on two to four
 /// layers (pdu.ports.size() layers, layer ly and DM-RS port 1000 + ly on port pdu.ports[ly]) goes to miphy_pdsch_process_layers_batch, a
+/// PDU of two codewords on five to eight layers to miphy_pdsch_process_codewords_batch (data[q] is transport block q), a
 /// PDU whose allocation is not contiguous or is interleaved to miphy_pdsch_process_mapped_batch with rb_allocation::get_prb_indices as
 /// its list in mapping order.
 class pdsch_processor_hip : public srsran::pdsch_processor
@@ -2632,17 +2655,36 @@ public:
                const pdu_t&                                                                         pdu) override
   {
     const unsigned nlayers = pdu.ports.size();
-    srsran_assert(nlayers >= 1 && nlayers <= 4 && pdu.codewords.size() == 1 && data.size() == 1, "Only one codeword on one to four layers is supported.");
+    const bool     two     = pdu.codewords.size() == 2;
+    srsran_assert((nlayers >= 1 && nlayers <= 4 && pdu.codewords.size() == 1 && data.size() == 1) || (nlayers >= 5 && nlayers <= 8 && two && data.size() == 2),
+                  "Only one codeword on one to four layers or two codewords on five to eight layers are supported.");
     srsran_assert(pdu.dmrs == srsran::dmrs_type::TYPE1, "Only DM-RS Type 1 is currently supported.");
     const srsran::bounded_bitset<srsran::MAX_RB> prb  = pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb);
     const unsigned                               nprb = prb.size(), nsc = nprb * 12;
     const miphy_pdsch_pdu                        p    = pdu_of(pdu, data[0].size(), prb);
+    const size_t                                 tb1_offset = (data[0].size() + 15) & ~static_cast<size_t>(15); // transport block 1 behind block 0
     host.assign(static_cast<size_t>(nlayers) * 14 * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernels"
-    auto* d_tb = static_cast<uint8_t*>(c->buf(0, data[0].size() + 16));
+    auto* d_tb = static_cast<uint8_t*>(c->buf(0, tb1_offset + (two ? data[1].size() : 0) + 16));
     auto* d_g  = static_cast<float*>(c->buf(1, host.size() * sizeof(srsran::cf_t)));
     c->h2d(d_tb, data[0].data(), data[0].size());
+    if (two) {
+      c->h2d(d_tb + tb1_offset, data[1].data(), data[1].size());
+    }
     c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
-    if (!pdu.freq_alloc.is_contiguous()) {
+    if (two) {
+      srsran::static_vector<uint16_t, srsran::MAX_RB> list;
+      miphy_pdsch_codewords_pdu                       cp = {};
+      if (!pdu.freq_alloc.is_contiguous()) {
+        list              = pdu.freq_alloc.get_prb_indices(pdu.bwp_start_rb, pdu.bwp_size_rb);
+        cp.mapped.nof_prb = list.size();
+      }
+      cp.mapped.layers.base = p, cp.nof_layers = nlayers;
+      second_block_of(pdu, data[1].size(), tb1_offset, cp);
+      for (unsigned ly = 0; ly != nlayers; ++ly) {
+        cp.ports[ly] = ly; // the staging grid has one port per layer
+      }
+      context::check(miphy_pdsch_process_codewords_batch(c->ctx, &cp, 1, list.data(), list.size(), d_tb, d_g, c->stream), "pdsch_process_codewords");
+    } else if (!pdu.freq_alloc.is_contiguous()) {
       const srsran::static_vector<uint16_t, srsran::MAX_RB> list = pdu.freq_alloc.get_prb_indices(pdu.bwp_start_rb, pdu.bwp_size_rb);
       miphy_pdsch_mapped_pdu                                mp   = {};
       mp.layers.base = p, mp.layers.nof_layers = nlayers, mp.prb_list_offset = 0, mp.nof_prb = list.size();
@@ -2702,6 +2744,13 @@ public:
     for (unsigned a = 0; a != nports; ++a) {
       put_written_res(grid, a, nsc, host.data() + static_cast<size_t>(a) * 14 * nsc);
     }
+  }
+
+  /// Transport block 1 of a two-codeword PDU (tb_bytes at tb_offset of the call's transport blocks) into its record; the base graph is the PDU's.
+  static void second_block_of(const pdu_t& pdu, size_t tb_bytes, size_t tb_offset, miphy_pdsch_codewords_pdu& cp)
+  {
+    cp.bg1 = bg_id(pdu.ldpc_base_graph), cp.rv1 = pdu.codewords[1].rv, cp.mod1 = srsran::get_bits_per_symbol(pdu.codewords[1].modulation);
+    cp.tb_bytes1 = tb_bytes, cp.tb_offset1 = tb_offset;
   }
 
 private:
@@ -2951,7 +3000,8 @@ private:
 // ---------------------------------------------------------------------------------------------------------------- downlink processor
 /// srsran::downlink_processor (downlink_processor.h:45-111, lib/phy/upper/downlink_processor_single_executor_impl.cpp:54-199) that
 /// batches the PDSCH PDUs of a slot: process_pdsch() queues, finish_processing_pdus() -- the reference's own end-of-slot call --
-/// runs miphy_pdsch_process_batch over the one-layer PDUs and miphy_pdsch_process_layers_batch over those of two to four layers, on
+/// runs miphy_pdsch_process_batch over the one-layer PDUs, miphy_pdsch_process_layers_batch over those of two to four layers and, behind
+/// the mapped ones, miphy_pdsch_process_codewords_batch over those of two codewords on five to eight layers, on
 /// the same device grid (transport blocks up once, written REs down once), puts the REs into the grid
 /// and sends it through the gateway. PDCCH, SSB and CSI-RS go to the CPU processors given at construction, at once. Same
 /// observable behaviour as the reference processor with its executor: nothing happens without a configured grid, the grid is zeroed
@@ -3008,8 +3058,9 @@ public:
     }
     // The PDU validator of the factory rejects these up front (pdsch_pdu_validator_hip); a caller that skips it fails loudly here
     // also in release builds.
-    require(pdu.ports.size() >= 1 && pdu.ports.size() <= 4 && pdu.codewords.size() == 1 && data.size() == 1,
-            "Only one codeword on one to four layers is supported.");
+    require((pdu.ports.size() >= 1 && pdu.ports.size() <= 4 && pdu.codewords.size() == 1 && data.size() == 1) ||
+                (pdu.ports.size() >= 5 && pdu.ports.size() <= 8 && pdu.codewords.size() == 2 && data.size() == 2),
+            "Only one codeword on one to four layers or two codewords on five to eight layers are supported.");
     require(pdu.dmrs == srsran::dmrs_type::TYPE1, "Only DM-RS Type 1 is currently supported.");
     require(pdu.freq_alloc.is_contiguous() || prb_list_obeys_list_rule(pdu.freq_alloc.get_prb_indices(pdu.bwp_start_rb, pdu.bwp_size_rb),
                                                                        pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb)),
@@ -3017,7 +3068,7 @@ public:
     for (uint8_t port : pdu.ports) {
       require(port < nports, "Transmit port outside the resource grid.");
     }
-    queue.push_back(entry{data[0], pdu});
+    queue.push_back(entry{data[0], pdu, data.size() == 2 ? data[1] : srsran::span<const uint8_t>()});
   }
   void configure_resource_grid(const srsran::resource_grid_context& context, srsran::resource_grid& grid_) override
   {
@@ -3094,16 +3145,29 @@ private:
     std::vector<miphy_pdsch_layers_pdu> lpdus; // two to four layers
     std::vector<miphy_pdsch_mapped_pdu> mpdus; // an allocation that is not contiguous or is interleaved, one to four layers ...
     std::vector<uint16_t>               lists; // ... and their PRBs in mapping order (rb_allocation::get_prb_indices)
-    std::vector<size_t>                 tb_offset(n);
+    std::vector<miphy_pdsch_codewords_pdu> cpdus; // two codewords on five to eight layers, with a list of their own array where not contiguous
+    std::vector<uint16_t>                  clists;
+    std::vector<size_t>                 tb_offset(n), tb1_offset(n);
     size_t                              tb_bytes = 0;
-    pdus.reserve(n), lpdus.reserve(n), mpdus.reserve(n);
+    pdus.reserve(n), lpdus.reserve(n), mpdus.reserve(n), cpdus.reserve(n);
     for (unsigned i = 0; i != n; ++i) {
       const srsran::pdsch_processor::pdu_t&        pdu = queue[i].pdu;
       const srsran::bounded_bitset<srsran::MAX_RB> prb = pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb);
       srsran_assert(prb.size() <= nprb, "The allocation exceeds the resource grid.");
       const unsigned nlayers = pdu.ports.size();
-      const bool     mapped  = !pdu.freq_alloc.is_contiguous();
-      if (mapped) {
+      const bool     two     = pdu.codewords.size() == 2;
+      const bool     mapped  = !two && !pdu.freq_alloc.is_contiguous();
+      if (two) {
+        miphy_pdsch_codewords_pdu cp = {};
+        cp.nof_layers                = nlayers;
+        std::copy(pdu.ports.begin(), pdu.ports.end(), cp.ports);
+        if (!pdu.freq_alloc.is_contiguous()) {
+          const srsran::static_vector<uint16_t, srsran::MAX_RB> list = pdu.freq_alloc.get_prb_indices(pdu.bwp_start_rb, pdu.bwp_size_rb);
+          cp.mapped.prb_list_offset = clists.size(), cp.mapped.nof_prb = list.size();
+          clists.insert(clists.end(), list.begin(), list.end());
+        }
+        cpdus.push_back(cp);
+      } else if (mapped) {
         const srsran::static_vector<uint16_t, srsran::MAX_RB> list = pdu.freq_alloc.get_prb_indices(pdu.bwp_start_rb, pdu.bwp_size_rb);
         miphy_pdsch_mapped_pdu                                mp   = {};
         mp.layers.nof_layers = nlayers, mp.prb_list_offset = lists.size(), mp.nof_prb = list.size();
@@ -3118,7 +3182,7 @@ private:
         std::copy(pdu.ports.begin(), pdu.ports.end(), lp.ports);
         lpdus.push_back(lp);
       }
-      miphy_pdsch_pdu& p = mapped ? mpdus.back().layers.base : (nlayers == 1 ? pdus.back() : lpdus.back().base);
+      miphy_pdsch_pdu& p = two ? cpdus.back().mapped.layers.base : mapped ? mpdus.back().layers.base : (nlayers == 1 ? pdus.back() : lpdus.back().base);
       p.slot_in_frame = pdu.slot.slot_index(), p.rnti = pdu.rnti, p.n_id = pdu.n_id, p.dmrs_scrambling_id = pdu.scrambling_id;
       p.tbs_lbrm_bytes = pdu.tbs_lbrm_bytes, p.tb_bytes = queue[i].data.size();
       p.ratio_pdsch_dmrs_to_sss_dB = pdu.ratio_pdsch_dmrs_to_sss_dB, p.ratio_pdsch_data_to_sss_dB = pdu.ratio_pdsch_data_to_sss_dB;
@@ -3137,10 +3201,18 @@ private:
       p.tb_offset = tb_bytes, p.grid_offset = 0;
       tb_offset[i] = tb_bytes;
       tb_bytes += (queue[i].data.size() + 15) & ~static_cast<size_t>(15);
+      if (two) { // transport block 1 behind block 0
+        pdsch_processor_hip::second_block_of(pdu, queue[i].data1.size(), tb_bytes, cpdus.back());
+        tb1_offset[i] = tb_bytes;
+        tb_bytes += (queue[i].data1.size() + 15) & ~static_cast<size_t>(15);
+      }
     }
     tbs.assign(tb_bytes + 16, 0);
     for (unsigned i = 0; i != n; ++i) {
       std::memcpy(&tbs[tb_offset[i]], queue[i].data.data(), queue[i].data.size());
+      if (!queue[i].data1.empty()) {
+        std::memcpy(&tbs[tb1_offset[i]], queue[i].data1.data(), queue[i].data1.size());
+      }
     }
     host.assign(static_cast<size_t>(nports) * 14 * nsc, srsran::cf_t(NAN, NAN)); // NaN marks "not written by the kernels"
     auto* d_tb = static_cast<uint8_t*>(wc->buf(0, tbs.size()));
@@ -3157,6 +3229,10 @@ private:
       context::check(miphy_pdsch_process_mapped_batch(wc->ctx, mpdus.data(), mpdus.size(), lists.data(), lists.size(), d_tb, d_g, wc->stream),
                      "pdsch_process_mapped");
     }
+    if (!cpdus.empty()) { // one more batch behind the others, on the same grid and stream
+      context::check(miphy_pdsch_process_codewords_batch(wc->ctx, cpdus.data(), cpdus.size(), clists.data(), clists.size(), d_tb, d_g, wc->stream),
+                     "pdsch_process_codewords");
+    }
     wc->d2h(host.data(), d_g, host.size() * sizeof(srsran::cf_t));
     wc->sync();
     for (unsigned p = 0; p != nports; ++p) {
@@ -3168,6 +3244,7 @@ private:
   struct entry {
     srsran::span<const uint8_t>    data;
     srsran::pdsch_processor::pdu_t pdu;
+    srsran::span<const uint8_t>    data1; // transport block 1 of a two-codeword PDU, empty otherwise
   };
   std::shared_ptr<context>                      c;
   srsran::upper_phy_rg_gateway&                 gateway;
@@ -3880,13 +3957,31 @@ public:
   explicit pdsch_pdu_validator_hip(std::unique_ptr<srsran::pdsch_pdu_validator> ref) : ref(std::move(ref)) {}
   bool is_valid(const srsran::pdsch_processor::pdu_t& pdu) const override
   {
-    // device path: one codeword on one to four layers (the number of ports is the number of layers) on distinct ports, DM-RS type 1,
-    // at most four reserved patterns, and an allocation that is contiguous and not interleaved or whose PRB list in mapping order
-    // (rb_allocation::get_prb_indices) passes the list rule of miphy_pdsch_process_mapped_batch. The reference validator stops at one
-    // layer: it judges everything else on a copy of the PDU that keeps the first port.
-    const unsigned nlayers = pdu.ports.size();
-    if (nlayers < 1 || nlayers > 4) {
+    // device path: one codeword on one to four layers or two codewords on five to eight (TS 38.211 Table 7.3.1.3-1; the number of ports is
+    // the number of layers) on distinct ports, DM-RS type 1, at most four reserved patterns, and an allocation that is contiguous and not
+    // interleaved or whose PRB list in mapping order (rb_allocation::get_prb_indices) passes the list rule of
+    // miphy_pdsch_process_mapped_batch. Two codewords on four or fewer ports (which the standard does not have) and one codeword on five or
+    // more stay refused. The reference validator stops at one layer and one codeword: it judges everything else on a copy of the PDU that
+    // keeps the first port and the first codeword.
+    const unsigned nlayers = pdu.ports.size(), ncw = pdu.codewords.size();
+    if (!((nlayers >= 1 && nlayers <= 4 && ncw == 1) || (nlayers >= 5 && nlayers <= 8 && ncw == 2))) {
       return false;
+    }
+    if (ncw == 2) {
+      // DM-RS ports 1004 .. 1007 of type 1 exist only on a double-symbol DM-RS with two CDM groups (miphy_pdsch_process_codewords_batch):
+      // every DM-RS symbol in a run of exactly two
+      if (pdu.nof_cdm_groups_without_data != 2) {
+        return false;
+      }
+      for (unsigned l = 0, run = 0; l <= pdu.dmrs_symbol_mask.size(); ++l) {
+        if (l != pdu.dmrs_symbol_mask.size() && pdu.dmrs_symbol_mask.test(l)) {
+          ++run;
+        } else if (run != 0 && run != 2) {
+          return false;
+        } else {
+          run = 0;
+        }
+      }
     }
     for (unsigned a = 0; a != nlayers; ++a) {
       for (unsigned b = 0; b != a; ++b) {
@@ -3897,6 +3992,7 @@ public:
     }
     srsran::pdsch_processor::pdu_t one = pdu;
     one.ports.resize(1);
+    one.codewords.resize(1);
     if (!pdu.freq_alloc.is_contiguous()) {
       // The reference validator refuses these outright: the allocation is judged here (its own BWP check, then the list rule) and the
       // rest of the PDU on a copy with one PRB in its place.
@@ -3910,8 +4006,7 @@ public:
     if (!ref->is_valid(one)) {
       return false;
     }
-    return pdu.codewords.size() == 1 && pdu.dmrs == srsran::dmrs_type::TYPE1 && pdu.cp == srsran::cyclic_prefix::NORMAL &&
-           pdu.reserved.get_nof_entries() <= 4;
+    return pdu.dmrs == srsran::dmrs_type::TYPE1 && pdu.cp == srsran::cyclic_prefix::NORMAL && pdu.reserved.get_nof_entries() <= 4;
   }
 
 private:

@@ -101,6 +101,10 @@ int    miphy_pdsch_mod_job_check(const char* who, const char* what, uint32_t i, 
 // jobs to): MIPHY_EINVAL and the message "<who>: <what> <i>: ..." on the first rule the list of `job` breaks; a job without a list (nof_prb = 0) passes.
 int    miphy_pdsch_mod_list_check(const char* who, const char* what, uint32_t i, const miphy_pdsch_mod_mapped_job& job, const uint16_t* prb_lists,
                                   uint32_t nof_list_entries);
+// The rules of a codewords job on the host (pdsch_mod.hip: PDSCH_MOD_CODEWORDS_RULES, the field rules, the list rules and PDSCH_MOD_CODEWORDS_SIZE_RULES, in
+// that order, which the kernels hold device-resident jobs to); nof_re = data REs per layer when the caller knows them, 0 = count here.
+int    miphy_pdsch_mod_codewords_check(const char* who, const char* what, uint32_t i, const miphy_pdsch_mod_codewords_job& job, const uint16_t* prb_lists,
+                                       uint32_t nof_list_entries, uint32_t nof_re);
 // The rules of a precoding on the host (pdsch_mod.hip: PDSCH_PRECODING_RULES, likewise): nof_layers = the layers of the job, rb_mask = its five mask
 // words, nof_weights = cf_t entries of the call's weights. MIPHY_EINVAL and the message "<who>: <what> <i>: precoding: ..." on the first rule broken.
 int    miphy_precoding_check(const char* who, const char* what, uint32_t i, const miphy_precoding& p, unsigned nof_layers, const uint64_t* rb_mask,
@@ -108,10 +112,10 @@ int    miphy_precoding_check(const char* who, const char* what, uint32_t i, cons
 // The rules of a precoded DM-RS job on the host: those of its DM-RS part, then miphy_precoding_check.
 int    miphy_dmrs_pdsch_precoded_job_check(const char* who, const char* what, uint32_t i, const miphy_dmrs_pdsch_precoded_job& job, uint32_t nof_weights);
 // The staging, the scratch and the two launches behind miphy_pdsch_modulate_layers_batch, _mapped_batch and _precoded_batch (pdsch_mod.hip), for JOB =
-// miphy_pdsch_mod_layers_job, miphy_pdsch_mod_mapped_job or miphy_pdsch_mod_precoded_job: jobs that passed the checks above, or that sit on the device
-// with their lists and weights, where the kernels validate them. Host jobs go to the staging ring in one upload together with the host lists (mapped and
+// miphy_pdsch_mod_layers_job, miphy_pdsch_mod_mapped_job, miphy_pdsch_mod_precoded_job or miphy_pdsch_mod_codewords_job (_codewords_batch): jobs that
+// passed the checks above, or that sit on the device with their lists and weights, where the kernels validate them. Host jobs go to the staging ring in one upload together with the host lists (mapped and
 // precoded jobs) and the host weights (precoded jobs); the arrays a kind of job does not have are not looked at. max_layers = the largest nof_layers of
-// the batch, 4 for device-resident jobs.
+// the batch (codewords jobs: the largest layer count of one codeword), 4 for device-resident jobs.
 template <class JOB>
 int miphy_pdsch_modulate_layered_enqueue(miphy_ctx* ctx, const JOB* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers, const uint16_t* prb_lists,
                                          uint32_t nof_list_entries, const float* weights, uint32_t nof_weights, const uint8_t* codewords, float* grid, hipStream_t s);

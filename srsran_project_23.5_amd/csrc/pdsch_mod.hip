@@ -18,6 +18,10 @@
 //   miphy_pdsch_modulate_mapped_batch    ... and a PRB list in mapping order: the interleaved VRB-to-PRB mapping of TS 38.211 7.3.1.6
 //                                        (miphy_vrb_to_prb_list) or any other order
 //   miphy_pdsch_modulate_precoded_batch  ... and a miphy_precoding: the L symbols of an element through the weight matrix of its PRG onto antenna ports
+// and a fourth for one or two codewords on 1..8 layers (TS 38.211 Table 7.3.1.3-1), which shares the same bodies:
+//   miphy_pdsch_modulate_codewords_batch miphy_pdsch_mod_codewords_job: a mapped job plus codeword 1 and eight ports. pdsch_seq_codewords_kernel generates
+//                                        both sequences of a job (the codeword is one more grid dimension), pdsch_mod_codewords_kernel maps codeword 0 and
+//                                        behind it codeword 1 in one workgroup: one symbol setup, one prefix and one launch pair for both
 // Behind the doors: one host loop (pdsch_modulate_layered: job, list, precoding, in that order), one enqueue (miphy_pdsch_modulate_layered_enqueue: staging,
 // the scratch of pdsch_layers_scratch_of, two launches), one sequence body (pdsch_seq_layers_body: chunks of the L-fold sequence with both registers
 // jumped; chunk 0 holds a device-resident job, its list and its precoding to the rules and says so in info[15]) and one mapping body
@@ -27,14 +31,17 @@
 // symbol; a mapping workgroup (transmission, OFDM symbol) fills a pdsch_symbol_lds through pdsch_symbol_setup and maps its elements through
 // pdsch_layers_fast (16QAM / 256QAM on aligned codewords) or pdsch_map_elements (everything else). Which REs carry data is stated once, in
 // pdsch_keep_rule_of and pdsch_keep_mask, for every kernel and the host's count. What a job, a list and a precoding must satisfy is stated once each
-// (PDSCH_MOD_FIELD_RULES, PDSCH_MOD_LIST_RULES / PDSCH_MOD_LIST_ENTRY_RULES, PDSCH_PRECODING_RULES), for the kernels' predicate and the host's messages.
+// (PDSCH_MOD_FIELD_RULES, PDSCH_MOD_LIST_RULES / PDSCH_MOD_LIST_ENTRY_RULES, PDSCH_PRECODING_RULES, PDSCH_MOD_CODEWORDS_RULES / PDSCH_MOD_CODEWORDS_SIZE_RULES),
+// for the kernels' predicate and the host's messages.
 // DM-RS: dmrs_pdsch_kernel and, behind a precoding, dmrs_pdsch_precoded_kernel generate an OFDM symbol through the same helpers (dmrs_pdsch_symbol_setup,
 // dmrs_pdsch_re_of, dmrs_pdsch_weight) and differ in their store loop; channel_precode_kernel is the precoder as a block of its own, and precode_sum
 // holds the arithmetic for all three precoding kernels.
 #include "gold_device.h"
 #include "mod_device.h"
 #include "miphy_ext.h"
+#include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <type_traits>
 
 namespace {
@@ -233,6 +240,13 @@ struct pdsch_no_precoding {
       g[ly] = slot + ((size_t)lj.ports[ly < L ? ly : 0] * 14 + sy) * nsc;
   }
   __device__ __forceinline__ explicit pdsch_no_precoding(float2* row) : g{row, nullptr, nullptr, nullptr} {} // (one layer: pdsch_mod_kernel)
+  // (one codeword of a codewords job: its L layers on its slice of the job's ports, layer ly on the port in byte ly of `ports`)
+  __device__ __forceinline__ pdsch_no_precoding(uint32_t ports, int L, float2* slot, int sy, int nsc)
+  {
+#pragma unroll
+    for (int ly = 0; ly < 4; ++ly)
+      g[ly] = slot + ((size_t)((ports >> (ly < L ? 8 * ly : 0)) & 0xffu) * 14 + sy) * nsc;
+  }
 };
 // With precoding (pdsch_mod_precoded_kernel): antenna port a = 0 .. P - 1 receives the sum of its row of the matrix of the element's PRG, on the symbol's
 // row of grid port ports[a]. The matrix (at most 64 cf_t) is read with plain loads: the twelve REs of a PRB, and with prg_size > 1 their neighbours, read
@@ -806,6 +820,54 @@ __device__ __forceinline__ bool layers_job_ok(const miphy_pdsch_mod_layers_job& 
   return pdsch_mod_fields_ok(j.base);
 }
 
+// One or two codewords on 1..8 layers (miphy_pdsch_mod_codewords_job, TS 38.211 Table 7.3.1.3-1): the layers of each codeword and its first layer.
+struct pdsch_codewords_split {
+  unsigned L0, L1; // L1 = 0: one codeword
+};
+__host__ __device__ __forceinline__ pdsch_codewords_split pdsch_codewords_split_of(unsigned L)
+{
+  const unsigned L0 = L > 4 ? L / 2 : L;
+  return {L0, L - L0};
+}
+
+__host__ __device__ __forceinline__ bool pdsch_codewords_ports_ok(const miphy_pdsch_mod_codewords_job& c)
+{
+  unsigned seen = 0;
+  for (unsigned ly = 0; ly < c.nof_layers && ly < 8; ++ly) {
+    const unsigned p = c.ports[ly];
+    if (p >= 16 || ((seen >> p) & 1u))
+      return false;
+    seen |= 1u << p;
+  }
+  return true;
+}
+
+__host__ __device__ __forceinline__ bool pdsch_mod_order_ok(unsigned mod) { return mod == 1 || mod == 2 || mod == 4 || mod == 6 || mod == 8; }
+
+// What a codewords job c adds to the rules of its mapped job (the fields of c.mapped.layers.base, the list), once more for the kernels' predicate and the
+// host's messages, evaluated in this order ...
+#define PDSCH_MOD_CODEWORDS_RULES(R)                                                                                                                   \
+  R(c.nof_layers >= 1 && c.nof_layers <= 8, "invalid number of layers %u (1..4: one codeword, 5..8: two)", (unsigned)c.nof_layers)                    \
+  R(pdsch_codewords_ports_ok(c), "the layers need distinct grid ports below 16")                                                                      \
+  R(c.nof_layers <= 4 || pdsch_mod_order_ok(c.mod1), "invalid modulation order %u of codeword 1", (unsigned)c.mod1)
+// ... and, with nre = the data REs per layer of its allocation and cs = pdsch_codewords_split_of(c.nof_layers), of the size of each codeword.
+#define PDSCH_MOD_CODEWORDS_SIZE_RULES(R)                                                                                                              \
+  R(c.mapped.layers.base.nof_bits == (uint64_t)nre * cs.L0 * c.mapped.layers.base.mod, "codeword 0 of %u bits, the allocation holds %u on %u layers", \
+    c.mapped.layers.base.nof_bits, (unsigned)(nre * cs.L0 * c.mapped.layers.base.mod), cs.L0)                                                          \
+  R(cs.L1 == 0 || c.nof_bits1 == (uint64_t)nre * cs.L1 * c.mod1, "codeword 1 of %u bits, the allocation holds %u on %u layers", c.nof_bits1,          \
+    (unsigned)(nre * cs.L1 * c.mod1), cs.L1)
+
+#define PDSCH_RULE_HOLDS(cond, ...) &&(cond)
+__host__ __device__ __forceinline__ bool pdsch_codewords_job_ok(const miphy_pdsch_mod_codewords_job& c)
+{
+  return true PDSCH_MOD_CODEWORDS_RULES(PDSCH_RULE_HOLDS) && pdsch_mod_fields_ok(c.mapped.layers.base);
+}
+__host__ __device__ __forceinline__ bool pdsch_codewords_sizes_ok(const miphy_pdsch_mod_codewords_job& c, const pdsch_codewords_split& cs, uint32_t nre)
+{
+  return true PDSCH_MOD_CODEWORDS_SIZE_RULES(PDSCH_RULE_HOLDS);
+}
+#undef PDSCH_RULE_HOLDS
+
 // What the PRB list of a mapped job m must satisfy, once, for the same two readers. The rules of the list as a whole: nof_list_entries = entries of
 // the batch's list array, rbm = the five words of the job's rb_mask (the job itself on the host, the copy in LDS on the device) ...
 #define PDSCH_MOD_LIST_RULES(R)                                                                                                                        \
@@ -939,10 +1001,15 @@ __device__ __forceinline__ void gold_words_extend(uint32_t* w1, uint32_t* w2, in
 // pc: the precoding of the job, null (a literal again) in the kernels of the entry points without one. Chunk 0 of a precoded job holds it to
 // PDSCH_PRECODING_RULES as well, and does not look at the layers' ports, which such a job does not use: pdsch_mod_precoded_kernel reads no weight unless
 // info[15] is set.
+// cj: the codewords job whose mapped job mj is, null (a literal) in the kernels of one codeword. Workgroup (transmission, chunk, codeword q) of such a job
+// generates the chunk of the sequence of codeword q (c_init + q 2^14) on that codeword's bit count, into sequence 2 x transmission + q of the scratch;
+// chunk 0 of codeword 0 does the counting and the prefixes once and sets info[15] only if PDSCH_MOD_CODEWORDS_RULES and PDSCH_MOD_CODEWORDS_SIZE_RULES
+// hold as well -- the job, its list and the bit counts of both codewords. A codeword has at most four layers, so `stride` is bounded as before.
 __device__ __forceinline__ void pdsch_seq_layers_body(const miphy_pdsch_mod_layers_job* __restrict__ lj, const miphy_pdsch_mod_mapped_job* __restrict__ mj,
                                                       const uint16_t* __restrict__ prb_lists, uint32_t nof_list_entries,
                                                       const gold_tables* __restrict__ gt, uint32_t* __restrict__ seq, int* __restrict__ info_out,
-                                                      uint32_t stride, const miphy_precoding* __restrict__ pc = nullptr, uint32_t nof_weights = 0)
+                                                      uint32_t stride, const miphy_precoding* __restrict__ pc = nullptr, uint32_t nof_weights = 0,
+                                                      const miphy_pdsch_mod_codewords_job* __restrict__ cj = nullptr)
 {
   __shared__ uint32_t w1[PDSCH_SEQ_CHUNK], w2[PDSCH_SEQ_CHUNK];
   __shared__ uint64_t rbm[5], resm[4][5];
@@ -951,10 +1018,13 @@ __device__ __forceinline__ void pdsch_seq_layers_body(const miphy_pdsch_mod_laye
   __shared__ int                list_bad;
   const miphy_pdsch_mod_job* __restrict__ jp = &lj->base;
   const int      tid = threadIdx.x, nt = blockDim.x, chunk = blockIdx.y;
-  const bool     ok       = pc ? lj->nof_layers >= 1 && lj->nof_layers <= 4 && pdsch_mod_fields_ok(*jp) : layers_job_ok(*lj);
-  const uint32_t nof_bits = jp->nof_bits;
-  const bool     fits     = nof_bits <= 32u * (stride - 2u); // + the 64-bit window of the last resource element
-  if (chunk == 0) {
+  const unsigned q        = cj ? blockIdx.z : 0u; // the codeword of this workgroup
+  const pdsch_codewords_split cs = pdsch_codewords_split_of(cj ? cj->nof_layers : 0u);
+  const bool     ok       = cj ? pdsch_codewords_job_ok(*cj) : pc ? lj->nof_layers >= 1 && lj->nof_layers <= 4 && pdsch_mod_fields_ok(*jp) : layers_job_ok(*lj);
+  const uint32_t nof_bits = (cj && q) ? cj->nof_bits1 : jp->nof_bits;
+  const uint32_t seq_bits = 32u * (stride - 2u); // + the 64-bit window of the last resource element
+  const bool     fits     = cj ? jp->nof_bits <= seq_bits && (cs.L1 == 0 || cj->nof_bits1 <= seq_bits) : nof_bits <= seq_bits;
+  if (chunk == 0 && q == 0) {
     int* info = info_out + (size_t)blockIdx.x * PDSCH_LAYERS_INFO;
     if (!ok || !fits) {
       if (tid == 0)
@@ -991,10 +1061,11 @@ __device__ __forceinline__ void pdsch_seq_layers_body(const miphy_pdsch_mod_laye
         run += cnt[s];
       }
       info[14] = run;
-      info[15] = (list_ok && (uint64_t)run * lj->nof_layers * jp->mod == nof_bits) ? 1 : 0;
+      const bool sized = cj ? pdsch_codewords_sizes_ok(*cj, cs, (uint32_t)run) : (uint64_t)run * lj->nof_layers * jp->mod == nof_bits;
+      info[15]         = (list_ok && sized) ? 1 : 0;
     }
   }
-  if (!ok || !fits)
+  if (!ok || !fits || (q && cs.L1 == 0))
     return;
   const int nwords = (int)((nof_bits + 31u) >> 5) + 2;
   const int first  = chunk * PDSCH_SEQ_CHUNK;
@@ -1003,11 +1074,11 @@ __device__ __forceinline__ void pdsch_seq_layers_body(const miphy_pdsch_mod_laye
   const int n = min(PDSCH_SEQ_CHUNK, nwords - first), head = min(n, 31);
   if (tid == 0 || tid == 64) { // one lane of two wavefronts: x1 and x2 side by side
     const bool is_x2 = tid == 64;
-    lfsr_head(gold_state(*gt, is_x2, (jp->rnti << 15) + jp->n_id, 32u * (uint32_t)first), is_x2, head, is_x2 ? w2 : w1);
+    lfsr_head(gold_state(*gt, is_x2, (jp->rnti << 15) + (q << 14) + jp->n_id, 32u * (uint32_t)first), is_x2, head, is_x2 ? w2 : w1);
   }
   __syncthreads();
   gold_words_extend(w1, w2, head, n, tid, nt);
-  uint32_t* o = seq + (size_t)blockIdx.x * stride + first;
+  uint32_t* o = seq + ((size_t)blockIdx.x * (cj ? 2u : 1u) + q) * stride + first;
   for (int i = tid; i < n; i += nt)
     o[i] = w1[i] ^ w2[i];
 }
@@ -1025,15 +1096,28 @@ __global__ void __launch_bounds__(512) pdsch_seq_mapped_kernel(const miphy_pdsch
   pdsch_seq_layers_body(&jobs[blockIdx.x].layers, jobs + blockIdx.x, prb_lists, nof_list_entries, gt, seq, info_out, stride);
 }
 
+// The sequence kernel of miphy_pdsch_modulate_codewords_batch: grid (transmission, chunk, codeword).
+__global__ void __launch_bounds__(512) pdsch_seq_codewords_kernel(const miphy_pdsch_mod_codewords_job* __restrict__ jobs, const uint16_t* __restrict__ prb_lists,
+                                                                  uint32_t nof_list_entries, const gold_tables* __restrict__ gt, uint32_t* __restrict__ seq,
+                                                                  int* __restrict__ info_out, uint32_t stride)
+{
+  const miphy_pdsch_mod_codewords_job* __restrict__ cj = jobs + blockIdx.x;
+  pdsch_seq_layers_body(&cj->mapped.layers, &cj->mapped, prb_lists, nof_list_entries, gt, seq, info_out, stride, nullptr, 0, cj);
+}
+
 // The one mapping body of the three layered entry points: workgroup (transmission, OFDM symbol). list: the job's PRBs in mapping order (nof_list of
 // them; the mapped and precoded kernels), null: rb_mask ascending. SINK: where the elements go (pdsch_no_precoding, pdsch_precoder); pc and weights are
 // the job's precoding and the call's weights for the sink that takes them, null (literals) otherwise. The job, its list and its precoding were held to
 // their rules by chunk 0 of the sequence kernel (info[15]).
-template <class SINK>
+// cj (CODEWORDS): the codewords job whose layers job lj is, null otherwise. Such a workgroup pays the symbol setup and the prefix once and then maps
+// codeword 0 and, where the job has two, codeword 1 behind it: each with its own modulation, sequence, bytes and wide-load condition, through a sink built
+// from its slice of the job's ports.
+template <class SINK, bool CODEWORDS = false>
 __device__ __forceinline__ void pdsch_mod_layers_body(const miphy_pdsch_mod_layers_job* __restrict__ lj, const uint16_t* list, int nof_list,
                                                       const miphy_precoding* __restrict__ pc, const float2* __restrict__ weights,
                                                       const uint8_t* __restrict__ cw_base, float2* __restrict__ grid, const uint32_t* __restrict__ seq_base,
-                                                      const int* __restrict__ info_base, uint32_t stride)
+                                                      const int* __restrict__ info_base, uint32_t stride,
+                                                      const miphy_pdsch_mod_codewords_job* __restrict__ cj = nullptr)
 {
   __shared__ pdsch_symbol_lds S;
   const miphy_pdsch_mod_job* __restrict__ jp = &lj->base;
@@ -1048,28 +1132,66 @@ __device__ __forceinline__ void pdsch_mod_layers_body(const miphy_pdsch_mod_laye
   const uint8_t* staged = SINK::stage(pc, tid);
   if (pdsch_symbol_setup(*jp, sy, S, tid, nt, list, nof_list) == 0)
     return;
-  const int       mod = jp->mod, L = lj->nof_layers;
-  const uint32_t* seq = seq_base + (size_t)blockIdx.x * stride;
-  const float     scaling = jp->scaling;
-  const bool      scale   = isnormal(scaling);
-  const uint8_t*  cw      = cw_base + jp->cw_offset;
-  const SINK      g(*lj, pc, weights, staged, grid + jp->grid_offset, sy, jp->grid_nof_prb * 12);
-  if ((mod == 4 || mod == 8) && (((uintptr_t)(cw + (size_t)prefix * L * mod)) & 3u) == 0) {
+  // (the dispatch of one codeword, written once for the two branches below: the wide-load sweeps where the codeword allows them -- 16QAM / 256QAM, the
+  // symbol's first byte of the codeword aligned to words -- and the general loop otherwise; DONE leaves the codeword)
 #define MIPHY_LAYERS_FAST(LL, MOD) pdsch_layers_fast<LL, MOD>(S, prefix, seq, cw, g, scale, scaling, tid)
-    switch (L * 16 + mod) {
-      case 1 * 16 + 4: MIPHY_LAYERS_FAST(1, 4); break;
-      case 2 * 16 + 4: MIPHY_LAYERS_FAST(2, 4); break;
-      case 3 * 16 + 4: MIPHY_LAYERS_FAST(3, 4); break;
-      case 4 * 16 + 4: MIPHY_LAYERS_FAST(4, 4); break;
-      case 1 * 16 + 8: MIPHY_LAYERS_FAST(1, 8); break;
-      case 2 * 16 + 8: MIPHY_LAYERS_FAST(2, 8); break;
-      case 3 * 16 + 8: MIPHY_LAYERS_FAST(3, 8); break;
-      default: MIPHY_LAYERS_FAST(4, 8); break;
-    }
-#undef MIPHY_LAYERS_FAST
-    return;
-  }
+#define MIPHY_MAP_CODEWORD(DONE)                                                                                                                       \
+  if ((mod == 4 || mod == 8) && (((uintptr_t)(cw + (size_t)prefix * L * mod)) & 3u) == 0) {                                                           \
+    switch (L * 16 + mod) {                                                                                                                           \
+      case 1 * 16 + 4: MIPHY_LAYERS_FAST(1, 4); break;                                                                                                \
+      case 2 * 16 + 4: MIPHY_LAYERS_FAST(2, 4); break;                                                                                                \
+      case 3 * 16 + 4: MIPHY_LAYERS_FAST(3, 4); break;                                                                                                \
+      case 4 * 16 + 4: MIPHY_LAYERS_FAST(4, 4); break;                                                                                                \
+      case 1 * 16 + 8: MIPHY_LAYERS_FAST(1, 8); break;                                                                                                \
+      case 2 * 16 + 8: MIPHY_LAYERS_FAST(2, 8); break;                                                                                                \
+      case 3 * 16 + 8: MIPHY_LAYERS_FAST(3, 8); break;                                                                                                \
+      default: MIPHY_LAYERS_FAST(4, 8); break;                                                                                                        \
+    }                                                                                                                                                 \
+    DONE;                                                                                                                                             \
+  }                                                                                                                                                   \
   pdsch_map_elements(S, L, mod, prefix, seq, cw, g, scale, scaling, tid, nt);
+  if constexpr (!CODEWORDS) {
+    const int       mod = jp->mod, L = lj->nof_layers;
+    const uint32_t* seq = seq_base + (size_t)blockIdx.x * stride;
+    const float     scaling = jp->scaling;
+    const bool      scale   = isnormal(scaling);
+    const uint8_t*  cw      = cw_base + jp->cw_offset;
+    const SINK      g(*lj, pc, weights, staged, grid + jp->grid_offset, sy, jp->grid_nof_prb * 12);
+    MIPHY_MAP_CODEWORD(return)
+  } else {
+    // every field of the job into registers ahead of the first store: a load behind one is no scalar load any more
+    // (nof_layers, mod1 and the eight ports as the three aligned words they lie in: byte loads would come back in vector registers and stay there across
+    // the first codeword)
+    static_assert(offsetof(miphy_pdsch_mod_codewords_job, nof_layers) % 4 == 0 && offsetof(miphy_pdsch_mod_codewords_job, mod1) == offsetof(miphy_pdsch_mod_codewords_job, nof_layers) + 1 &&
+                      offsetof(miphy_pdsch_mod_codewords_job, ports) == offsetof(miphy_pdsch_mod_codewords_job, nof_layers) + 2,
+                  "nof_layers, mod1 and ports[8] of a codewords job are read as three aligned words");
+    const uint32_t* const       tail = reinterpret_cast<const uint32_t*>(&cj->nof_layers);
+    const uint32_t              t0 = tail[0], t1 = tail[1], t2 = tail[2];
+    const pdsch_codewords_split cs   = pdsch_codewords_split_of(t0 & 0xffu);
+    const int                   mod0 = jp->mod, mod1 = (int)((t0 >> 8) & 0xffu), nsc = jp->grid_nof_prb * 12;
+    const uint64_t              off0 = jp->cw_offset, off1 = cj->cw1_offset;
+    float2* const               slot = grid + jp->grid_offset;
+    const float                 scaling = jp->scaling;
+    const bool                  scale   = isnormal(scaling);
+    const uint64_t              ports   = (uint64_t)(t0 >> 16) | ((uint64_t)t1 << 16) | ((uint64_t)(t2 & 0xffffu) << 48); // ports[ly] in byte ly
+    const uint32_t* const seq0 = seq_base + (size_t)blockIdx.x * 2u * stride;
+    do {
+      const int                mod = mod0, L = (int)cs.L0;
+      const uint32_t*          seq = seq0;
+      const uint8_t*           cw  = cw_base + off0;
+      const pdsch_no_precoding g((uint32_t)ports, L, slot, sy, nsc);
+      MIPHY_MAP_CODEWORD(break)
+    } while (0);
+    if (cs.L1) {
+      const int                mod = mod1, L = (int)cs.L1;
+      const uint32_t*          seq = seq0 + stride;
+      const uint8_t*           cw  = cw_base + off1;
+      const pdsch_no_precoding g((uint32_t)(ports >> (8u * cs.L0)), L, slot, sy, nsc);
+      MIPHY_MAP_CODEWORD(return)
+    }
+  }
+#undef MIPHY_MAP_CODEWORD
+#undef MIPHY_LAYERS_FAST
 }
 
 __global__ void __launch_bounds__(256) pdsch_mod_layers_kernel(const miphy_pdsch_mod_layers_job* __restrict__ jobs, const uint8_t* __restrict__ cw_base,
@@ -1089,6 +1211,17 @@ __global__ void __launch_bounds__(256) pdsch_mod_mapped_kernel(const miphy_pdsch
   const int nof_list = mj->nof_prb;
   pdsch_mod_layers_body<pdsch_no_precoding>(&mj->layers, nof_list ? prb_lists + mj->prb_list_offset : nullptr, nof_list, nullptr, nullptr, cw_base, grid, seq_base,
                                             info_base, stride);
+}
+
+// The mapping kernel of miphy_pdsch_modulate_codewords_batch: the mapped one, both codewords of a job in one workgroup.
+__global__ void __launch_bounds__(256) pdsch_mod_codewords_kernel(const miphy_pdsch_mod_codewords_job* __restrict__ jobs, const uint16_t* __restrict__ prb_lists,
+                                                                  const uint8_t* __restrict__ cw_base, float2* __restrict__ grid,
+                                                                  const uint32_t* __restrict__ seq_base, const int* __restrict__ info_base, uint32_t stride)
+{
+  const miphy_pdsch_mod_codewords_job* __restrict__ cj = jobs + blockIdx.x;
+  const int nof_list = cj->mapped.nof_prb;
+  pdsch_mod_layers_body<pdsch_no_precoding, true>(&cj->mapped.layers, nof_list ? prb_lists + cj->mapped.prb_list_offset : nullptr, nof_list, nullptr, nullptr,
+                                                  cw_base, grid, seq_base, info_base, stride, cj);
 }
 
 // ---------------------------------------------------------------------------------------------------- precoding: layers to antenna ports
@@ -1279,25 +1412,28 @@ namespace {
 // The three layered entry points take one kind of job each -- miphy_pdsch_mod_layers_job, miphy_pdsch_mod_mapped_job (a layers job and its PRB list) or
 // miphy_pdsch_mod_precoded_job (a mapped job and its precoding) -- and share everything else. The parts of a job: null where its kind has none.
 struct pdsch_job_parts {
-  const miphy_pdsch_mod_layers_job* layers;
-  const miphy_pdsch_mod_mapped_job* mapped;
-  const miphy_precoding*            precoding;
+  const miphy_pdsch_mod_layers_job*    layers;
+  const miphy_pdsch_mod_mapped_job*    mapped;
+  const miphy_precoding*               precoding;
+  const miphy_pdsch_mod_codewords_job* codewords; // (its layers part carries neither the layers nor the ports: the host holds it to its own check)
 };
-pdsch_job_parts parts_of(const miphy_pdsch_mod_layers_job& j) { return {&j, nullptr, nullptr}; }
-pdsch_job_parts parts_of(const miphy_pdsch_mod_mapped_job& j) { return {&j.layers, &j, nullptr}; }
-pdsch_job_parts parts_of(const miphy_pdsch_mod_precoded_job& j) { return {&j.mapped.layers, &j.mapped, &j.precoding}; }
+pdsch_job_parts parts_of(const miphy_pdsch_mod_layers_job& j) { return {&j, nullptr, nullptr, nullptr}; }
+pdsch_job_parts parts_of(const miphy_pdsch_mod_mapped_job& j) { return {&j.layers, &j, nullptr, nullptr}; }
+pdsch_job_parts parts_of(const miphy_pdsch_mod_precoded_job& j) { return {&j.mapped.layers, &j.mapped, &j.precoding, nullptr}; }
+pdsch_job_parts parts_of(const miphy_pdsch_mod_codewords_job& j) { return {&j.mapped.layers, &j.mapped, nullptr, &j}; }
 
 // The scratch of a layered call in MIPHY_WS_SEQUENCES: the scrambling sequences (a transmission on L layers has L times the bits of one layer: the stride
-// grows with the batch's largest L), then PDSCH_LAYERS_INFO ints per transmission.
+// grows with the batch's largest L), then PDSCH_LAYERS_INFO ints per transmission. A call on codewords jobs keeps nof_seq = 2 sequences per transmission,
+// sequence 2 x transmission + q for codeword q, and max_layers is the largest layer count of one codeword (at most four).
 struct pdsch_layers_scratch {
   uint32_t stride; // sequence words per transmission
   size_t   seq_bytes, bytes;
   int*     info(void* seq) const { return reinterpret_cast<int*>(static_cast<uint8_t*>(seq) + seq_bytes); }
 };
-pdsch_layers_scratch pdsch_layers_scratch_of(uint32_t n, uint32_t max_layers)
+pdsch_layers_scratch pdsch_layers_scratch_of(uint32_t n, uint32_t max_layers, uint32_t nof_seq = 1)
 {
   const uint32_t stride    = max_layers * (uint32_t)PDSCH_SEQ_STRIDE;
-  const size_t   seq_bytes = (size_t)n * stride * sizeof(uint32_t);
+  const size_t   seq_bytes = (size_t)n * nof_seq * stride * sizeof(uint32_t);
   return {stride, seq_bytes, seq_bytes + (size_t)n * PDSCH_LAYERS_INFO * sizeof(int)};
 }
 
@@ -1311,12 +1447,20 @@ int pdsch_modulate_layered(const char* who, miphy_ctx* ctx, const JOB* jobs, int
     return MIPHY_OK;
   MIPHY_REQUIRE(n <= 65535, "%s: batch too large (max 65535 transmissions per call)", who);
   uint32_t max_layers = 4; // device-resident jobs: the kernels validate them, their lists and precodings; the scratch is sized for the most they may ask
+                           // (a codewords job of eight layers among them: four layers per codeword)
   if (!jobs_on_device) {
     max_layers = 1;
     const uint8_t no_ports[4] = {0, 1, 2, 3}; // (a precoded job's layers.ports is ignored)
     for (uint32_t i = 0; i < n; ++i) {
       const pdsch_job_parts             j  = parts_of(jobs[i]);
       const miphy_pdsch_mod_layers_job& lj = *j.layers;
+      if (j.codewords) { // (its own rules, those of the fields and of the list, in that order)
+        if (int rc = miphy_pdsch_mod_codewords_check(who, "job", i, *j.codewords, prb_lists, nof_list_entries, 0))
+          return rc;
+        const pdsch_codewords_split cs = pdsch_codewords_split_of(j.codewords->nof_layers);
+        max_layers                     = std::max(max_layers, std::max(cs.L0, cs.L1));
+        continue;
+      }
       int rc = miphy_pdsch_mod_job_check(who, "job", i, lj.base, lj.nof_layers, j.precoding ? no_ports : lj.ports, 0);
       if (!rc && j.mapped)
         rc = miphy_pdsch_mod_list_check(who, "job", i, *j.mapped, prb_lists, nof_list_entries);
@@ -1336,7 +1480,8 @@ template <class JOB>
 int miphy_pdsch_modulate_layered_enqueue(miphy_ctx* ctx, const JOB* jobs, int jobs_on_device, uint32_t n, uint32_t max_layers, const uint16_t* prb_lists,
                                          uint32_t nof_list_entries, const float* weights, uint32_t nof_weights, const uint8_t* codewords, float* grid, hipStream_t s)
 {
-  constexpr bool     precoded = std::is_same<JOB, miphy_pdsch_mod_precoded_job>::value, mapped = precoded || std::is_same<JOB, miphy_pdsch_mod_mapped_job>::value;
+  constexpr bool     precoded = std::is_same<JOB, miphy_pdsch_mod_precoded_job>::value, cwjob = std::is_same<JOB, miphy_pdsch_mod_codewords_job>::value;
+  constexpr bool     mapped   = precoded || cwjob || std::is_same<JOB, miphy_pdsch_mod_mapped_job>::value;
   const gold_tables* gt       = nullptr;
   int                rc       = miphy_get_gold_tables(ctx, &gt);
   if (rc)
@@ -1362,14 +1507,18 @@ int miphy_pdsch_modulate_layered_enqueue(miphy_ctx* ctx, const JOB* jobs, int jo
     if (precoded)
       d_w = ws.at(base);
   }
-  const pdsch_layers_scratch sc  = pdsch_layers_scratch_of(n, max_layers);
+  const pdsch_layers_scratch sc  = pdsch_layers_scratch_of(n, max_layers, cwjob ? 2 : 1);
   void*                      seq = nullptr;
   if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, sc.bytes, &seq)))
     return rc;
   uint32_t* const sq = static_cast<uint32_t*>(seq);
   int* const      info = sc.info(seq);
-  const dim3      chunks(n, 2 * max_layers), symbols(n, 14);
-  if constexpr (precoded) {
+  const dim3      chunks(n, 2 * max_layers, cwjob ? 2 : 1), symbols(n, 14);
+  if constexpr (cwjob) {
+    hipLaunchKernelGGL(pdsch_seq_codewords_kernel, chunks, dim3(512), 0, s, d_jobs, d_lists, nof_list_entries, gt, sq, info, sc.stride);
+    hipLaunchKernelGGL(pdsch_mod_codewords_kernel, symbols, dim3(256), 0, s, d_jobs, d_lists, codewords, (float2*)grid, (const uint32_t*)sq, (const int*)info,
+                       sc.stride);
+  } else if constexpr (precoded) {
     hipLaunchKernelGGL(pdsch_seq_precoded_kernel, chunks, dim3(512), 0, s, d_jobs, d_lists, nof_list_entries, nof_weights, gt, sq, info, sc.stride);
     hipLaunchKernelGGL(pdsch_mod_precoded_kernel, symbols, dim3(256), 0, s, d_jobs, d_lists, d_w, codewords, (float2*)grid, (const uint32_t*)sq, (const int*)info,
                        sc.stride);
@@ -1389,6 +1538,7 @@ int miphy_pdsch_modulate_layered_enqueue(miphy_ctx* ctx, const JOB* jobs, int jo
 PDSCH_ENQUEUE_FOR(miphy_pdsch_mod_layers_job)
 PDSCH_ENQUEUE_FOR(miphy_pdsch_mod_mapped_job)
 PDSCH_ENQUEUE_FOR(miphy_pdsch_mod_precoded_job)
+PDSCH_ENQUEUE_FOR(miphy_pdsch_mod_codewords_job)
 #undef PDSCH_ENQUEUE_FOR
 
 extern "C" int miphy_pdsch_modulate_layers_batch(miphy_ctx* ctx, const miphy_pdsch_mod_layers_job* jobs, int jobs_on_device, uint32_t n, const uint8_t* codewords,
@@ -1464,6 +1614,38 @@ extern "C" int miphy_pdsch_modulate_mapped_batch(miphy_ctx* ctx, const miphy_pds
 {
   MIPHY_REQUIRE(ctx && jobs && codewords && grid && (prb_lists || nof_list_entries == 0), "miphy_pdsch_modulate_mapped_batch: null argument");
   return pdsch_modulate_layered("pdsch_modulate_mapped", ctx, jobs, jobs_on_device, n, prb_lists, nof_list_entries, nullptr, 0, codewords, grid, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------- PDSCH modulator, one or two codewords on 1..8 layers
+extern "C" uint32_t miphy_pdsch_mod_codewords_nof_re(const miphy_pdsch_mod_codewords_job* j)
+{
+  if (!j || j->nof_layers < 1 || j->nof_layers > 8)
+    return 0;
+  return miphy_pdsch_mod_nof_re(&j->mapped.layers.base);
+}
+
+int miphy_pdsch_mod_codewords_check(const char* who, const char* what, uint32_t i, const miphy_pdsch_mod_codewords_job& c, const uint16_t* prb_lists,
+                                    uint32_t nof_list_entries, uint32_t nre)
+{
+#define PDSCH_RULE_REQUIRE(cond, fmt, ...) MIPHY_REQUIRE(cond, "%s: %s %u: " fmt, who, what, i, ##__VA_ARGS__);
+  PDSCH_MOD_CODEWORDS_RULES(PDSCH_RULE_REQUIRE)
+  const miphy_pdsch_mod_job& j = c.mapped.layers.base;
+  PDSCH_MOD_FIELD_RULES(PDSCH_RULE_REQUIRE)
+  if (int rc = miphy_pdsch_mod_list_check(who, what, i, c.mapped, prb_lists, nof_list_entries))
+    return rc;
+  if (nre == 0)
+    nre = host_nof_re(j);
+  const pdsch_codewords_split cs = pdsch_codewords_split_of(c.nof_layers);
+  PDSCH_MOD_CODEWORDS_SIZE_RULES(PDSCH_RULE_REQUIRE)
+#undef PDSCH_RULE_REQUIRE
+  return MIPHY_OK;
+}
+
+extern "C" int miphy_pdsch_modulate_codewords_batch(miphy_ctx* ctx, const miphy_pdsch_mod_codewords_job* jobs, int jobs_on_device, uint32_t n,
+                                                    const uint16_t* prb_lists, uint32_t nof_list_entries, const uint8_t* codewords, float* grid, void* stream)
+{
+  MIPHY_REQUIRE(ctx && jobs && codewords && grid && (prb_lists || nof_list_entries == 0), "miphy_pdsch_modulate_codewords_batch: null argument");
+  return pdsch_modulate_layered("pdsch_modulate_codewords", ctx, jobs, jobs_on_device, n, prb_lists, nof_list_entries, nullptr, 0, codewords, grid, stream);
 }
 
 extern "C" int miphy_dmrs_pdsch_map_batch(miphy_ctx* ctx, const miphy_dmrs_pdsch_job* jobs, int jobs_on_device, uint32_t n, float* grid, void* stream)

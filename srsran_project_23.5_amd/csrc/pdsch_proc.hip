@@ -5,6 +5,7 @@
 #include "gold_device.h"
 #include "miphy_ext.h"
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -120,7 +121,7 @@ extern "C" int miphy_pdsch_process_batch(miphy_ctx* ctx, const miphy_pdsch_pdu* 
       [&] { return miphy_dmrs_pdsch_map_batch(ctx, dj.data(), 0, n, grid, s); });
 }
 
-// ---- one codeword on 1..4 layers, in three forms: layers on named grid ports, the same with the PRBs in the mapping order of a list (interleaved
+// ---- one codeword on 1..4 layers, in three forms (and, further down, one or two on 1..8 layers through the same composition): layers on named grid ports, the same with the PRBs in the mapping order of a list (interleaved
 // VRB-to-PRB mapping), the same behind a precoding. One composition: the encoder's nof_layers = L and nof_ch_symbols = REs x L, the layered modulator
 // of the form, the DM-RS on L ports.
 extern "C" uint32_t miphy_pdsch_layers_pdu_nof_re(const miphy_pdsch_layers_pdu* pdu)
@@ -188,8 +189,59 @@ int derive_layers_jobs(const char* who, uint32_t i, const miphy_pdsch_precoded_p
   return miphy_dmrs_pdsch_precoded_job_check(who, "PDU", i, dj, a.nof_weights);
 }
 
+// The same for a PDU of one or two transport blocks on 1..8 layers. Up to four layers it is the mapped PDU it contains, on nof_layers and ports of its own:
+// the same records, the same refusals. From five, transport block q goes through the records of a layered PDU on its own L_q layers and its slice of the
+// ports -- so every rule of a transport block, the encoder's limits among them, holds for each -- and leaves the encoder's record of block 1 in `second`;
+// the modulator job carries both codewords and the DM-RS job all L ports. DM-RS ports 1004 .. 1007 of type 1 exist only on a double-symbol DM-RS with two
+// CDM groups, hence the two rules of their own.
+int derive_layers_jobs(const char* who, uint32_t i, const miphy_pdsch_codewords_pdu& p, const pdsch_pdu_arrays& a, miphy_pdsch_tb_desc& t,
+                       miphy_pdsch_mod_codewords_job& cj, miphy_dmrs_pdsch_job& d, size_t& cw_bytes, uint32_t& max_layers, std::vector<miphy_pdsch_tb_desc>& second)
+{
+  const uint32_t L = p.nof_layers;
+  cj               = {};
+  cj.nof_layers    = (uint8_t)L;
+  for (uint32_t ly = 0; ly < 8; ++ly)
+    cj.ports[ly] = p.ports[ly];
+  if (L <= 4) {
+    miphy_pdsch_mapped_pdu mp = p.mapped;
+    mp.layers.nof_layers      = (uint8_t)L;
+    for (uint32_t ly = 0; ly < 4; ++ly)
+      mp.layers.ports[ly] = p.ports[ly];
+    return derive_layers_jobs(who, i, mp, a, t, cj.mapped, d, cw_bytes, max_layers);
+  }
+  MIPHY_REQUIRE(L <= 8, "%s: PDU %u: invalid number of layers %u (1..4: one transport block, 5..8: two)", who, i, L);
+  const miphy_pdsch_pdu& b = p.mapped.layers.base;
+  MIPHY_REQUIRE(b.nof_cdm_groups_without_data == 2, "%s: PDU %u: %u layers need 2 CDM groups without data", who, i, L);
+  const uint32_t m = b.dmrs_symbols_mask, first = m & ~(m << 1), last = m & ~(m >> 1); // the first and the last symbol of every run
+  MIPHY_REQUIRE((first << 1) == last, "%s: PDU %u: %u layers need a double-symbol DM-RS (every DM-RS symbol in a run of exactly two)", who, i, L);
+  const uint32_t         L0 = L / 2, L1 = L - L0;
+  miphy_pdsch_layers_pdu lp = p.mapped.layers;
+  lp.nof_layers             = (uint8_t)L0;
+  for (uint32_t ly = 0; ly < 4; ++ly)
+    lp.ports[ly] = p.ports[ly];
+  if (int rc = derive_layers_jobs(who, i, lp, a, t, cj.mapped.layers, d, cw_bytes, max_layers))
+    return rc;
+  lp.nof_layers = (uint8_t)L1;
+  for (uint32_t ly = 0; ly < 4; ++ly)
+    lp.ports[ly] = p.ports[ly + L0 < 8 ? ly + L0 : 7];
+  lp.base.bg = p.bg1, lp.base.rv = p.rv1, lp.base.mod = p.mod1, lp.base.tb_bytes = p.tb_bytes1, lp.base.tb_offset = p.tb_offset1;
+  miphy_pdsch_tb_desc        t1;
+  miphy_pdsch_mod_layers_job lj1;
+  miphy_dmrs_pdsch_job       d1;
+  if (int rc = derive_layers_jobs(who, i, lp, a, t1, lj1, d1, cw_bytes, max_layers))
+    return rc;
+  second.push_back(t1);
+  cj.mapped.prb_list_offset = p.mapped.prb_list_offset, cj.mapped.nof_prb = p.mapped.nof_prb;
+  cj.mod1 = p.mod1, cj.nof_bits1 = lj1.base.nof_bits, cj.cw1_offset = lj1.base.cw_offset;
+  d.nof_ports = (uint8_t)L;
+  for (uint32_t ly = 0; ly < L; ++ly)
+    d.ports[ly] = p.ports[ly];
+  return miphy_pdsch_mod_codewords_check(who, "PDU", i, cj, a.prb_lists, a.nof_list_entries, t.nof_ch_symbols / L0);
+}
+
 // A layered processor behind its null-argument test: the records of every PDU (MJ: the modulator job of the form, DJ: its DM-RS job), refused before
-// anything is enqueued or allocated, then the tail. map_dmrs(jobs, stream): the DM-RS mapper of the form.
+// anything is enqueued or allocated, then the tail. map_dmrs(jobs, stream): the DM-RS mapper of the form. The encoder runs over all transport blocks of the
+// batch: one per PDU and, behind them, the second blocks of the PDUs that have two.
 template <class MJ, class DJ, class PDU, class DMRS>
 int pdsch_process_layered(const char* who, miphy_ctx* ctx, const PDU* pdus, uint32_t n, const pdsch_pdu_arrays& a, const uint8_t* tb_in, float* grid, void* stream,
                           DMRS&& map_dmrs)
@@ -203,9 +255,17 @@ int pdsch_process_layered(const char* who, miphy_ctx* ctx, const PDU* pdus, uint
   std::vector<DJ>                  dj(n);
   size_t                           cw_bytes   = 0;
   uint32_t                         max_layers = 1;
-  for (uint32_t i = 0; i < n; ++i)
-    if (int rc = derive_layers_jobs(who, i, pdus[i], a, tb[i], mj[i], dj[i], cw_bytes, max_layers))
+  std::vector<miphy_pdsch_tb_desc> second;
+  for (uint32_t i = 0; i < n; ++i) {
+    int rc;
+    if constexpr (std::is_same<PDU, miphy_pdsch_codewords_pdu>::value)
+      rc = derive_layers_jobs(who, i, pdus[i], a, tb[i], mj[i], dj[i], cw_bytes, max_layers, second);
+    else
+      rc = derive_layers_jobs(who, i, pdus[i], a, tb[i], mj[i], dj[i], cw_bytes, max_layers);
+    if (rc)
       return rc;
+  }
+  tb.insert(tb.end(), second.begin(), second.end());
   return pdsch_process_tail(
       ctx, tb, cw_bytes, tb_in, s,
       [&](const uint8_t* cw) { // (the jobs passed the modulator's host rules in derive_layers_jobs)
@@ -240,6 +300,23 @@ extern "C" int miphy_pdsch_process_precoded_batch(miphy_ctx* ctx, const miphy_pd
   return pdsch_process_layered<miphy_pdsch_mod_precoded_job, miphy_dmrs_pdsch_precoded_job>(
       "pdsch_process_precoded", ctx, pdus, n, {prb_lists, nof_list_entries, weights, nof_weights}, tb_in, grid, stream,
       [&](const miphy_dmrs_pdsch_precoded_job* dj, hipStream_t s) { return miphy_dmrs_pdsch_map_precoded_batch(ctx, dj, 0, n, weights, nof_weights, grid, s); });
+}
+
+// ---- one or two transport blocks on 1..8 layers
+extern "C" uint32_t miphy_pdsch_codewords_pdu_nof_re(const miphy_pdsch_codewords_pdu* pdu)
+{
+  if (!pdu || pdu->nof_layers < 1 || pdu->nof_layers > 8)
+    return 0;
+  return miphy_pdsch_pdu_nof_re(&pdu->mapped.layers.base);
+}
+
+extern "C" int miphy_pdsch_process_codewords_batch(miphy_ctx* ctx, const miphy_pdsch_codewords_pdu* pdus, uint32_t n, const uint16_t* prb_lists,
+                                                   uint32_t nof_list_entries, const uint8_t* tb_in, float* grid, void* stream)
+{
+  MIPHY_REQUIRE(ctx && pdus && tb_in && grid && (prb_lists || nof_list_entries == 0), "miphy_pdsch_process_codewords_batch: null argument");
+  return pdsch_process_layered<miphy_pdsch_mod_codewords_job, miphy_dmrs_pdsch_job>(
+      "pdsch_process_codewords", ctx, pdus, n, {prb_lists, nof_list_entries, nullptr, 0}, tb_in, grid, stream,
+      [&](const miphy_dmrs_pdsch_job* dj, hipStream_t s) { return miphy_dmrs_pdsch_map_batch(ctx, dj, 0, n, grid, s); });
 }
 
 // ---- prepared form: PDU validation, segmentation, every descriptor upload and the scratch happen once; a run is the seven launches of the

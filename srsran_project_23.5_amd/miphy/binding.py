@@ -102,6 +102,12 @@ def lib():
         l.miphy_vrb_to_prb_list.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         l.miphy_pdsch_modulate_mapped_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         l.miphy_pdsch_process_mapped_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_pdsch_modulate_codewords_batch"):  # (an older build named by MIPHY_LIBRARY for an A-B has none of them)
+            l.miphy_pdsch_modulate_codewords_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.miphy_pdsch_process_codewords_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            for f in (l.miphy_pdsch_mod_codewords_nof_re, l.miphy_pdsch_codewords_pdu_nof_re):
+                f.argtypes = [C.c_void_p]
+                f.restype = C.c_uint32
         if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_channel_precode_batch"):  # (an older build named by MIPHY_LIBRARY for an A-B has none of them)
             l.miphy_channel_precode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
             l.miphy_pdsch_modulate_precoded_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
@@ -294,6 +300,28 @@ PdschModMappedJob = np.dtype([("layers", PdschModLayersJob), ("prb_list_offset",
 assert PdschModMappedJob.itemsize == 296 and PdschModMappedJob.fields["prb_list_offset"][1] == 288 and PdschModMappedJob.fields["nof_prb"][1] == 292
 PdschMappedPdu = np.dtype([("layers", PdschLayersPdu), ("prb_list_offset", np.uint32), ("nof_prb", np.uint16), ("pad", np.uint16)], align=True)
 assert PdschMappedPdu.itemsize == 320 and PdschMappedPdu.fields["prb_list_offset"][1] == 312 and PdschMappedPdu.fields["nof_prb"][1] == 316
+# Mirror miphy_pdsch_mod_codewords_job and miphy_pdsch_codewords_pdu: the mapped records (codeword / transport block 0 and everything the two share; the
+# layers and ports inside them are ignored), nof_layers 1..8 with the grid port of each, and codeword / transport block 1, which exists from five layers.
+PdschModCodewordsJob = np.dtype([("mapped", PdschModMappedJob), ("nof_layers", np.uint8), ("mod1", np.uint8), ("ports", np.uint8, 8), ("pad", np.uint8, 2),
+                                 ("nof_bits1", np.uint32), ("cw1_offset", np.uint64)], align=True)
+assert PdschModCodewordsJob.itemsize == 320 and PdschModCodewordsJob.fields["ports"][1] == 298 and PdschModCodewordsJob.fields["nof_bits1"][1] == 308
+PdschCodewordsPdu = np.dtype([("mapped", PdschMappedPdu), ("nof_layers", np.uint8), ("ports", np.uint8, 8), ("bg1", np.uint8), ("rv1", np.uint8),
+                              ("mod1", np.uint8), ("tb_bytes1", np.uint32), ("tb_offset1", np.uint64)], align=True)
+assert PdschCodewordsPdu.itemsize == 344 and PdschCodewordsPdu.fields["bg1"][1] == 329 and PdschCodewordsPdu.fields["tb_bytes1"][1] == 332
+
+
+def pdsch_mod_codewords_nof_re(job):
+    """Data REs per layer of one PdschModCodewordsJob record (host computation in the library); 0 on an invalid job."""
+    a = np.ascontiguousarray(np.asarray(job, dtype=PdschModCodewordsJob).reshape(1))
+    return int(lib().miphy_pdsch_mod_codewords_nof_re(a.ctypes.data_as(C.c_void_p)))
+
+
+def pdsch_codewords_pdu_nof_re(pdu):
+    """Data REs per layer of one PdschCodewordsPdu record (host computation in the library); 0 on an invalid PDU."""
+    a = np.ascontiguousarray(np.asarray(pdu, dtype=PdschCodewordsPdu).reshape(1))
+    return int(lib().miphy_pdsch_codewords_pdu_nof_re(a.ctypes.data_as(C.c_void_p)))
+
+
 # Mirrors miphy_precoding: nof_layers layers onto nof_ports antenna ports (grid port ports[a]) through one matrix per PRG of prg_size grid PRBs;
 # W[g][a][ly] is cf_t entry weights_offset + (g nof_ports + a) nof_layers + ly of the call's weights.
 Precoding = np.dtype([("nof_layers", np.uint8), ("nof_ports", np.uint8), ("ports", np.uint8, 16), ("prg_size", np.uint16), ("nof_prg", np.uint16),
@@ -703,6 +731,21 @@ class Context:
         pdus = np.ascontiguousarray(pdus)
         lptr, nl = self._host_or_device(prb_lists, 0, np.uint16, (), "prb_lists")
         check(lib().miphy_pdsch_process_mapped_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, lptr, nl, _dptr(tb_in), _dptr(grid), _stream_ptr(stream)))
+
+    def pdsch_modulate_codewords_batch(self, jobs, prb_lists, codewords, grid, stream=None):
+        """pdsch_modulate_mapped_batch for one or two codewords on 1..8 layers (PdschModCodewordsJob; from five layers the job carries codeword 1 as
+        well, TS 38.211 Table 7.3.1.3-1). jobs and prb_lists live in the same place, as there."""
+        import torch
+        jobs, n, ptr, on_dev = self._descs(jobs, PdschModCodewordsJob)
+        lptr, nl = self._host_or_device(prb_lists, on_dev, np.uint16, (torch.int16, torch.uint16), "prb_lists")
+        check(lib().miphy_pdsch_modulate_codewords_batch(self.h, ptr, on_dev, n, lptr, nl, _dptr(codewords), _dptr(grid), _stream_ptr(stream)))
+
+    def pdsch_process_codewords_batch(self, pdus, prb_lists, tb_in, grid, stream=None):
+        """pdsch_process_mapped_batch for PDUs of one or two transport blocks on 1..8 layers (host PdschCodewordsPdu records, host uint16 lists or None)."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PdschCodewordsPdu
+        pdus = np.ascontiguousarray(pdus)
+        lptr, nl = self._host_or_device(prb_lists, 0, np.uint16, (), "prb_lists")
+        check(lib().miphy_pdsch_process_codewords_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, lptr, nl, _dptr(tb_in), _dptr(grid), _stream_ptr(stream)))
 
     # ------------------------------------------------------------------ precoding: layers to antenna ports through per-PRG weights
     def channel_precode_batch(self, jobs, weights, x, out, stream=None):

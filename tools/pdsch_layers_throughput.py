@@ -19,7 +19,12 @@ JSON line per variant. There is no CPU path: without a device this fails.
   miphy_pdsch_modulate_layers_batch (the yardstick) at every L of 1, 2, 4 that PORTS can carry, with device-resident jobs and weights (every job its own
   matrices, PRGs of --prg-size PRBs), the two alternating. Per call, per stored (RE, port), and the bytes stored (8 per (RE, port); the yardstick
   stores 8 per (RE, layer)). With --trace the yardstick is left out, so that a kernel trace holds pdsch_mod_precoded_kernel alone.
-Run:  python tools/pdsch_layers_throughput.py [--batch N] [--iters N] [--reps R] [--mod 1|2|4|6|8] [--mapping M | --precoding PORTS [--prg-size S]] [--trace]"""
+- --codewords times, instead of the above, miphy_pdsch_modulate_codewords_batch on two codewords -- L = 5 at (256QAM, 256QAM), L = 8 at (256QAM,
+  256QAM) and L = 8 at (256QAM, 16QAM) -- next to its yardstick: two back-to-back miphy_pdsch_modulate_layers_batch calls with L0 and L1 layers on the
+  same allocation and the same grid ports, which are the stores the new call makes without the shared symbol setup and launch pair. Device-resident
+  jobs, the two alternating. Per call, per mapped (RE, layer), and the bytes stored.
+Run:  python tools/pdsch_layers_throughput.py [--batch N] [--iters N] [--reps R] [--mod 1|2|4|6|8] [--mapping M | --precoding PORTS [--prg-size S] | --codewords]
+      [--trace]"""
 import argparse
 import json
 import os
@@ -163,6 +168,40 @@ def precoded_section(ctx, a, gen):
                           "ps_per_re_port": round(us * 1e6 / stored, 2), "store_GBps": round(stored * 8 / us * 1e-3, 1)}), flush=True)
 
 
+def codewords_section(ctx, a, gen):
+    """--codewords: per (L, mod0, mod1) the yardstick (two layered calls, L0 and L1 layers) and the codewords entry point, device-resident jobs,
+    alternating."""
+    n = a.batch
+    grid = torch.zeros(n * 8 * 14 * NSC, dtype=torch.complex64, device="cuda")
+    goff = np.arange(n, dtype=np.uint64) * np.uint64(8 * 14 * NSC)
+    fns, meta = [], []
+    for L, mods in ((5, (8, 8)), (8, (8, 8)), (8, (8, 4))):
+        L0, L1 = L // 2, L - L // 2
+        halves, cws = [], []
+        for Lq, mod, first in ((L0, mods[0], 0), (L1, mods[1], L0)):
+            jobs, nre = mod_jobs(n, Lq, True, mod)
+            jobs["base"]["grid_offset"], jobs["ports"] = goff, first + np.arange(4) % Lq
+            halves.append(jobs)
+            cws.append(torch.randint(0, 2, (n * nre * Lq * mod,), dtype=torch.uint8, device="cuda", generator=gen))
+        cw = torch.cat(cws)
+        d0, d1 = (torch.from_numpy(h.view(np.uint8).copy()).cuda() for h in halves)
+        fns.append(lambda d0=d0, d1=d1, c0=cws[0], c1=cws[1]: (ctx.pdsch_modulate_layers_batch(d0, c0, grid), ctx.pdsch_modulate_layers_batch(d1, c1, grid)))
+        meta.append(("two_layers_calls", L, mods, nre))
+        cj = np.zeros(n, dtype=miphy.PdschModCodewordsJob)
+        cj["mapped"]["layers"] = halves[0]
+        cj["nof_layers"], cj["ports"], cj["mod1"] = L, np.arange(8), mods[1]
+        cj["nof_bits1"] = halves[1]["base"]["nof_bits"]
+        cj["cw1_offset"] = np.uint64(cws[0].numel()) + halves[1]["base"]["cw_offset"]
+        d_cj = torch.from_numpy(cj.view(np.uint8).copy()).cuda()
+        fns.append(lambda j=d_cj, cw=cw: ctx.pdsch_modulate_codewords_batch(j, None, cw, grid))
+        meta.append(("codewords_entry", L, mods, nre))
+    for (name, L, mods, nre), (us, lo, hi) in zip(meta, measure(fns, a.iters, a.reps)):
+        mapped = n * nre * L
+        print(json.dumps({"what": "modulate", "entry": name, "jobs": "device", "layers": L, "mods": list(mods), "batch": n, "re_per_layer": nre,
+                          "us_per_call": round(us, 2), "us_per_call_spread": [round(lo, 2), round(hi, 2)], "ps_per_re_layer": round(us * 1e6 / mapped, 2),
+                          "store_GBps": round(mapped * 8 / us * 1e-3, 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
@@ -177,12 +216,17 @@ def main():
     ap.add_argument("--precoding", type=int, default=None, metavar="PORTS",
                     help="time miphy_pdsch_modulate_precoded_batch onto PORTS (1..16) antenna ports next to miphy_pdsch_modulate_layers_batch instead (device jobs)")
     ap.add_argument("--prg-size", type=int, default=4, help="with --precoding: PRBs per PRG")
+    ap.add_argument("--codewords", action="store_true",
+                    help="time miphy_pdsch_modulate_codewords_batch on two codewords (L = 5 and 8) next to two miphy_pdsch_modulate_layers_batch calls instead (device jobs)")
     a = ap.parse_args()
     n, mod = a.batch, a.mod
     ctx = miphy.Context(0)
     gen = torch.Generator(device="cuda").manual_seed(1)
     if a.precoding is not None:
         precoded_section(ctx, a, gen)
+        return
+    if a.codewords:
+        codewords_section(ctx, a, gen)
         return
     grid = torch.zeros(n * 4 * 14 * NSC, dtype=torch.complex64, device="cuda")
     if a.mapping is not None:
