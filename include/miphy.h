@@ -407,8 +407,30 @@ int miphy_pusch_demodulate_batch(miphy_ctx* ctx, const miphy_pusch_demod_job* jo
                                  const float* grid /* device cf_t */, const float* ce /* device cf_t */, const float* scalars /* device */,
                                  int8_t* llr_out /* device */, void* stream);
 
+/* PUSCH demodulator for one codeword on 1..4 transmit layers  --  beyond the 23.5 reference, whose demodulator asserts one layer
+ * (pusch_demodulator_impl.h, "layer demapping is not implemented"): zero forcing of L layers on P >= L receive ports (the arithmetic of
+ * miphy_channel_equalize_layers_batch, tx_scaling = 1) and the layer demapping of TS 38.211 6.3.1.3 in front of the same soft demapper.
+ *   estimate: as miphy_dmrs_pusch_estimate_batch writes it, [layer][rx port][ce_nof_symbols][nsc], with ce_compact [layer][rx port][nsc];
+ *             noise variance at scalars[scalars_offset + 2]
+ *   output:   data element i (ranked symbol-major, subcarrier ascending, as on one layer), layer ly, bit b at
+ *             llr_offset + (L i + ly) mod + b, descrambled with c((L i + ly) mod + b), c_init = rnti * 2^15 + n_id; pi/2-BPSK rotates
+ *             with the parity of L i + ly
+ * base.nof_llr must equal miphy_pusch_demod_layers_nof_llr(); UCI placeholders and EVM are not available (base.nof_placeholders = 0,
+ * evm_offset ignored). A batch may mix layer counts; a job on one layer writes the bytes of miphy_pusch_demodulate_batch. A host job that
+ * breaks a rule is MIPHY_EINVAL with nothing enqueued, a device-resident one is skipped. */
+typedef struct {
+  miphy_pusch_demod_job base;
+  uint8_t               nof_tx_layers; /* 1..4, <= base.nof_rx_ports */
+  uint8_t               reserved[7];
+} miphy_pusch_demod_layers_job;
+/* Number of LLRs of `job` (data REs x layers x mod); 0 on an invalid job. Host function. */
+uint32_t miphy_pusch_demod_layers_nof_llr(const miphy_pusch_demod_layers_job* job);
+int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n,
+                                        const float* grid /* device cf_t */, const float* ce /* device cf_t */, const float* scalars /* device */,
+                                        int8_t* llr_out /* device */, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
- * Channel equalizer on its own  --  replaces srsran::channel_equalizer::equalize of the zero-forcing equalizer
+ * Channel equalizer on its own --  replaces srsran::channel_equalizer::equalize of the zero-forcing equalizer
  * (include/srsran/phy/upper/equalization/channel_equalizer.h:27-114, lib/phy/upper/equalization/channel_equalizer_zf_impl.cpp:123-162).
  * Topologies are the reference's: one transmit layer with 1..4 receive ports (equalize_zf_1xn.h:120-158) and two layers on two ports
  * (equalize_zf_2x2.cpp:30-117); anything else is MIPHY_EINVAL where the reference asserts. The noise variance is the one of the
@@ -432,6 +454,15 @@ typedef struct {
 int miphy_channel_equalize_batch(miphy_ctx* ctx, const miphy_equalizer_job* jobs, int jobs_on_device, uint32_t n, const float* ch_symbols /* device cf_t */,
                                  const float* ch_estimates /* device cf_t */, float* eq_symbols /* device cf_t */, float* eq_noise_vars /* device */,
                                  void* stream);
+/* The same jobs and tensor layouts for 1..4 transmit layers on nof_rx_ports = layers..4 receive ports (beyond the reference, which stops
+ * at 1 x N and 2 x 2): x = (H^H H)^-1 H^H y / tx_scaling, noise variance noise_var [(H^H H)^-1]_ll / tx_scaling^2, in single precision
+ * in a fixed order of operations (csrc/equalize_device.h: one layer and two layers as the reference, so 1 x N and 2 x 2 give the bytes of
+ * miphy_channel_equalize_batch; three and four layers by an LDL^H factorisation without square roots). If a determinant or pivot is not
+ * a normal number, or noise_var is not normal and positive, every layer of the element gets symbol 0 and noise variance +inf. Any other
+ * topology, or tx_scaling <= 0, is MIPHY_EINVAL for host jobs and skipped for device-resident ones. */
+int miphy_channel_equalize_layers_batch(miphy_ctx* ctx, const miphy_equalizer_job* jobs, int jobs_on_device, uint32_t n,
+                                        const float* ch_symbols /* device cf_t */, const float* ch_estimates /* device cf_t */,
+                                        float* eq_symbols /* device cf_t */, float* eq_noise_vars /* device */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * PDSCH modulator and PDSCH DM-RS  --  replace srsran::pdsch_modulator::modulate and srsran::dmrs_pdsch_processor::map

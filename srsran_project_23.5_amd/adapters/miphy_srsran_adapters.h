@@ -894,7 +894,8 @@ private:
 
 // ---------------------------------------------------------------------------------------------------------------- PUSCH demodulator
 /// srsran::pusch_demodulator over miphy_pusch_demodulate_batch (pusch_demodulator.h:105-108): equaliser, soft demapper and
-/// descrambler of pusch_demodulator_impl in one device pass. No UCI placeholders, no EVM report (status.evm stays empty).
+/// descrambler of pusch_demodulator_impl in one device pass. No UCI placeholders, no EVM report (status.evm stays empty). Two to four
+/// transmit layers (which the reference's demodulator asserts against) go to miphy_pusch_demodulate_layers_batch.
 class pusch_demodulator_hip : public srsran::pusch_demodulator
 {
 public:
@@ -904,7 +905,8 @@ public:
                                  const srsran::channel_estimate&            estimates,
                                  const configuration&                       config) override
   {
-    srsran_assert(config.nof_tx_layers == 1, "Only a single transmit layer is supported.");
+    const unsigned nl = config.nof_tx_layers;
+    srsran_assert(nl >= 1 && nl <= 4 && nl <= config.rx_ports.size(), "One to four transmit layers on at least as many receive ports are supported.");
     bool has_placeholders = false;
     config.placeholders.for_each(config.modulation, config.nof_tx_layers, [&has_placeholders](unsigned, unsigned) { has_placeholders = true; });
     if (has_placeholders) {
@@ -912,7 +914,9 @@ public:
     }
     const unsigned nprb = config.rb_mask.size(), nsc = nprb * 12, nports = config.rx_ports.size();
     const unsigned nsymb = config.start_symbol_index + config.nof_symbols;
-    miphy_pusch_demod_job j = {};
+    miphy_pusch_demod_layers_job lj = {};
+    lj.nof_tx_layers                = nl;
+    miphy_pusch_demod_job& j        = lj.base;
     j.rnti                  = config.rnti;
     j.n_id                  = config.n_id;
     j.mod                   = srsran::get_bits_per_symbol(config.modulation);
@@ -939,11 +943,13 @@ public:
         grid.get(srsran::span<srsran::cf_t>(host.data() + (static_cast<size_t>(p) * 14 + l) * nsc, nsc), config.rx_ports[p], l, 0);
       }
     }
-    ce_host.resize(static_cast<size_t>(nports) * nsymb * nsc);
-    for (unsigned p = 0; p != nports; ++p) {
-      for (unsigned l = 0; l != nsymb; ++l) {
-        auto v = estimates.get_symbol_ch_estimate(l, p, 0);
-        std::memcpy(ce_host.data() + (static_cast<size_t>(p) * nsymb + l) * nsc, v.data(), nsc * sizeof(srsran::cf_t));
+    ce_host.resize(static_cast<size_t>(nl) * nports * nsymb * nsc); // [layer][rx port][symbol][subcarrier]
+    for (unsigned ly = 0; ly != nl; ++ly) {
+      for (unsigned p = 0; p != nports; ++p) {
+        for (unsigned l = 0; l != nsymb; ++l) {
+          auto v = estimates.get_symbol_ch_estimate(l, p, ly);
+          std::memcpy(ce_host.data() + ((static_cast<size_t>(ly) * nports + p) * nsymb + l) * nsc, v.data(), nsc * sizeof(srsran::cf_t));
+        }
       }
     }
     float sc[5] = {0, 0, estimates.get_noise_variance(0, 0), 0, 0};
@@ -954,7 +960,11 @@ public:
     c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
     c->h2d(d_ce, ce_host.data(), ce_host.size() * sizeof(srsran::cf_t));
     c->h2d(d_sc, sc, sizeof(sc));
-    context::check(miphy_pusch_demodulate_batch(c->ctx, &j, 0, 1, d_g, d_ce, d_sc, d_llr, c->stream), "pusch_demodulate");
+    if (nl == 1) {
+      context::check(miphy_pusch_demodulate_batch(c->ctx, &j, 0, 1, d_g, d_ce, d_sc, d_llr, c->stream), "pusch_demodulate");
+    } else { // beyond the reference: L x P zero forcing and the layer demapping of TS 38.211 6.3.1.3
+      context::check(miphy_pusch_demodulate_layers_batch(c->ctx, &lj, 0, 1, d_g, d_ce, d_sc, d_llr, c->stream), "pusch_demodulate_layers");
+    }
     static_assert(sizeof(srsran::log_likelihood_ratio) == 1, "LLRs are int8");
     c->d2h(codeword.data(), d_llr, codeword.size());
     c->sync();
@@ -3846,7 +3856,8 @@ inline std::shared_ptr<srsran::port_channel_estimator_factory> create_port_chann
 
 // ---------------------------------------------------------------------------------------------------------------- channel equalizer
 /// srsran::channel_equalizer over miphy_channel_equalize_batch (channel_equalizer.h:93-100, channel_equalizer_zf_impl.cpp:123-162):
-/// one transmit layer on up to four ports or two layers on two ports. Inside pusch_processor_hip the one-layer case runs fused with
+/// one transmit layer on up to four ports or two layers on two ports; the topologies beyond the reference (up to four layers on at least
+/// as many ports, at most four) go to miphy_channel_equalize_layers_batch. Inside pusch_processor_hip the one-layer case runs fused with
 /// the soft demapper; this class is the block for whoever builds a demodulator of their own around the reference interfaces.
 class channel_equalizer_hip : public srsran::channel_equalizer
 {
@@ -3871,7 +3882,8 @@ public:
             "Post-equalization noise variances do not match the channel dimensions.");
     require(noise_var_estimates.size() == npt, "Number of noise variance estimates does not match the number of Rx ports.");
     require(tx_scaling > 0, "Tx scaling factor must be positive.");
-    require((nl == 1 && npt >= 1 && npt <= 4) || (nl == 2 && npt == 2), "Invalid channel spatial topology.");
+    const bool reference_topology = (nl == 1 && npt >= 1 && npt <= 4) || (nl == 2 && npt == 2);
+    require(reference_topology || (nl >= 1 && nl <= 4 && npt >= nl && npt <= 4), "Invalid channel spatial topology.");
     if (nre == 0) {
       return;
     }
@@ -3885,7 +3897,11 @@ public:
     auto*        d_v = static_cast<float*>(c->buf(3, nz * sizeof(float)));
     c->h2d(d_y, ch_symbols.get_view<2>({}).data(), ny * sizeof(srsran::cf_t));
     c->h2d(d_h, ch_estimates.get_view<3>({}).data(), nh * sizeof(srsran::cf_t));
-    context::check(miphy_channel_equalize_batch(c->ctx, &j, 0, 1, d_y, d_h, d_z, d_v, c->stream), "channel_equalize");
+    if (reference_topology) {
+      context::check(miphy_channel_equalize_batch(c->ctx, &j, 0, 1, d_y, d_h, d_z, d_v, c->stream), "channel_equalize");
+    } else { // beyond the reference: 2..4 layers on at least as many ports
+      context::check(miphy_channel_equalize_layers_batch(c->ctx, &j, 0, 1, d_y, d_h, d_z, d_v, c->stream), "channel_equalize_layers");
+    }
     c->d2h(eq_symbols.get_view<2>({}).data(), d_z, nz * sizeof(srsran::cf_t));
     c->d2h(eq_noise_vars.get_view<2>({}).data(), d_v, nz * sizeof(float));
     c->sync();

@@ -165,6 +165,31 @@ __device__ __forceinline__ uint32_t gold_state(const gold_tables& t, bool is_x2,
   return st;
 }
 
+// gold_state by the 32 lanes of one half of a wavefront (lane = 0 .. 31 inside the half, every lane of the half active; all of them get the
+// window): the jump is a chain of matrix-vector products in which lane i contributes column i and a 5-step XOR butterfly adds them up.
+__device__ __forceinline__ uint32_t gold_state_wave(const gold_tables& t, bool is_x2, uint32_t c_init, uint32_t offset, int lane)
+{
+  auto xor32 = [](uint32_t v) {
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1)
+      v ^= __shfl_xor(v, o); // stays inside the 32-lane half
+    return v;
+  };
+  uint32_t st = t.j.x1_1600;
+  if (is_x2)
+    st = xor32((lane < 31 && ((c_init >> lane) & 1u)) ? t.j.x2_col[lane] : 0u);
+  // all columns this lane may need are fetched up front (independent loads: one memory latency instead of one per set bit)
+  uint32_t cols[GOLD_POW];
+#pragma unroll
+  for (int k = 0; k < GOLD_POW; ++k)
+    cols[k] = (lane < 31 && ((offset >> k) & 1u)) ? (is_x2 ? t.x2_pow[k][lane] : t.x1_pow[k][lane]) : 0u;
+#pragma unroll
+  for (int k = 0; k < GOLD_POW; ++k)
+    if ((offset >> k) & 1u) // uniform
+      st = xor32(((st >> lane) & 1u) ? cols[k] : 0u);
+  return st;
+}
+
 // c(offset .. offset + nbits - 1), bit-packed LSB first into out[0 .. nwords), for ONE long sequence. All of it runs on the first
 // wavefront, x1 on lanes 0-31 and x2 on lanes 32-63, without workgroup barriers: the jump to `offset` is a chain of matrix-vector
 // products in which lane i contributes column i and a 5-step XOR butterfly adds them up; lane 0 of each half produces the 31-word
@@ -178,24 +203,7 @@ __device__ __forceinline__ void gold_long_block(const gold_tables& t, uint32_t c
   if (tid < 64) {
     const bool is_x2 = tid >= 32;
     const int  lane  = tid & 31;
-    auto       xor32 = [](uint32_t v) {
-#pragma unroll
-      for (int o = 16; o >= 1; o >>= 1)
-        v ^= __shfl_xor(v, o); // stays inside the 32-lane half
-      return v;
-    };
-    uint32_t st = t.j.x1_1600;
-    if (is_x2)
-      st = xor32((lane < 31 && ((c_init >> lane) & 1u)) ? t.j.x2_col[lane] : 0u);
-    // all columns this lane may need are fetched up front (independent loads: one memory latency instead of one per set bit)
-    uint32_t cols[GOLD_POW];
-#pragma unroll
-    for (int k = 0; k < GOLD_POW; ++k)
-      cols[k] = (lane < 31 && ((offset >> k) & 1u)) ? (is_x2 ? t.x2_pow[k][lane] : t.x1_pow[k][lane]) : 0u;
-#pragma unroll
-    for (int k = 0; k < GOLD_POW; ++k)
-      if ((offset >> k) & 1u) // uniform
-        st = xor32(((st >> lane) & 1u) ? cols[k] : 0u);
+    const uint32_t st = gold_state_wave(t, is_x2, c_init, offset, lane);
     volatile uint32_t* w = is_x2 ? w2 : w1;
     if (lane == 0)
       lfsr_head(st, is_x2, head, is_x2 ? w2 : w1);
@@ -211,6 +219,45 @@ __device__ __forceinline__ void gold_long_block(const gold_tables& t, uint32_t c
   for (int i = tid; i < nwords; i += nt)
     out[i] = w1[i] ^ w2[i];
   __syncthreads();
+}
+
+// Both LFSR sequences of c(n), held as words in LDS, from `have` (>= 31) to nwords words: the word recurrences w[i] = w[i-28] ^ w[i-31] (x1) and
+// w[i] = w[i-28] ^ w[i-29] ^ w[i-30] ^ w[i-31] (x2) in their squares, as gold_x2_sequence does for x2 alone.
+__device__ __forceinline__ void gold_words_extend(uint32_t* w1, uint32_t* w2, int have, int nwords, int tid, int nt)
+{
+  int k = 0;
+  while ((62 << k) <= have)
+    ++k;
+  while (have < nwords) {
+    const int d = 1 << k, end = min(have + 28 * d, nwords);
+    for (int i = have + tid; i < end; i += nt) {
+      w1[i] = w1[i - 28 * d] ^ w1[i - 31 * d];
+      w2[i] = w2[i - 28 * d] ^ w2[i - 29 * d] ^ w2[i - 30 * d] ^ w2[i - 31 * d];
+    }
+    __syncthreads();
+    have += 28 * d;
+    while ((62 << k) <= have)
+      ++k;
+  }
+}
+
+// One piece of a sequence longer than the x1 table (transmissions on several layers): c(32 first .. 32 (first + n) - 1) as n words at out, by a whole
+// workgroup (nt >= 64) with two LDS arrays of n words. Both LFSRs jump to the piece's first bit on the first wavefront, x1 on lanes 0-31 and x2 on
+// lanes 32-63 (gold_state_wave), lane 0 of each half runs the 31-word head, the word recurrences do the rest. Shared by the sequence kernels of the
+// layered PDSCH modulator and of the layered PUSCH demodulator.
+__device__ __forceinline__ void gold_piece(const gold_tables& t, uint32_t c_init, int first, int n, uint32_t* w1, uint32_t* w2, uint32_t* out, int tid, int nt)
+{
+  const int head = min(n, 31);
+  if (tid < 64) {
+    const bool     is_x2 = tid >= 32;
+    const uint32_t st    = gold_state_wave(t, is_x2, c_init, 32u * (uint32_t)first, tid & 31);
+    if ((tid & 31) == 0)
+      lfsr_head(st, is_x2, head, is_x2 ? w2 : w1);
+  }
+  __syncthreads();
+  gold_words_extend(w1, w2, head, n, tid, nt);
+  for (int i = tid; i < n; i += nt)
+    out[i] = w1[i] ^ w2[i];
 }
 
 // Device copy of the tables, created on first use and cached in the context.

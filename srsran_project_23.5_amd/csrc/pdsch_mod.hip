@@ -969,26 +969,6 @@ __host__ __device__ __forceinline__ bool dmrs_precoded_fields_ok(const miphy_dmr
 }
 #undef PDSCH_RULE_HOLDS
 
-// Both LFSR sequences of c(n), held as words in LDS, from `have` (>= 31) to nwords words: the word recurrences w[i] = w[i-28] ^ w[i-31] (x1) and
-// w[i] = w[i-28] ^ w[i-29] ^ w[i-30] ^ w[i-31] (x2) in their squares, as gold_x2_sequence does for x2 alone.
-__device__ __forceinline__ void gold_words_extend(uint32_t* w1, uint32_t* w2, int have, int nwords, int tid, int nt)
-{
-  int k = 0;
-  while ((62 << k) <= have)
-    ++k;
-  while (have < nwords) {
-    const int d = 1 << k, end = min(have + 28 * d, nwords);
-    for (int i = have + tid; i < end; i += nt) {
-      w1[i] = w1[i - 28 * d] ^ w1[i - 31 * d];
-      w2[i] = w2[i - 28 * d] ^ w2[i - 29 * d] ^ w2[i - 30 * d] ^ w2[i - 31 * d];
-    }
-    __syncthreads();
-    have += 28 * d;
-    while ((62 << k) <= have)
-      ++k;
-  }
-}
-
 // Sibling of pdsch_seq_kernel for transmissions on L layers, whose sequence is L times longer than the x1 table and than one workgroup's LDS:
 // workgroup (transmission, chunk) generates PDSCH_SEQ_CHUNK words of it -- both LFSRs jump to the chunk's first bit (gold_state), one lane
 // each runs the 31-word head, the word recurrences do the rest. `stride` = sequence words reserved per transmission. Chunk 0 also validates
@@ -1071,16 +1051,8 @@ __device__ __forceinline__ void pdsch_seq_layers_body(const miphy_pdsch_mod_laye
   const int first  = chunk * PDSCH_SEQ_CHUNK;
   if (first >= nwords)
     return;
-  const int n = min(PDSCH_SEQ_CHUNK, nwords - first), head = min(n, 31);
-  if (tid == 0 || tid == 64) { // one lane of two wavefronts: x1 and x2 side by side
-    const bool is_x2 = tid == 64;
-    lfsr_head(gold_state(*gt, is_x2, (jp->rnti << 15) + (q << 14) + jp->n_id, 32u * (uint32_t)first), is_x2, head, is_x2 ? w2 : w1);
-  }
-  __syncthreads();
-  gold_words_extend(w1, w2, head, n, tid, nt);
-  uint32_t* o = seq + ((size_t)blockIdx.x * (cj ? 2u : 1u) + q) * stride + first;
-  for (int i = tid; i < n; i += nt)
-    o[i] = w1[i] ^ w2[i];
+  const int n = min(PDSCH_SEQ_CHUNK, nwords - first);
+  gold_piece(*gt, (jp->rnti << 15) + (q << 14) + jp->n_id, first, n, w1, w2, seq + ((size_t)blockIdx.x * (cj ? 2u : 1u) + q) * stride + first, tid, nt);
 }
 
 __global__ void __launch_bounds__(512) pdsch_seq_layers_kernel(const miphy_pdsch_mod_layers_job* __restrict__ jobs, const gold_tables* __restrict__ gt,

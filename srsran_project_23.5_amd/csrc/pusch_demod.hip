@@ -14,6 +14,7 @@
 #define NR_DEMOD_TABLE_ATTR __device__
 #include "gold_device.h"
 #include "demod_device.h"
+#include "equalize_device.h"
 #include "mod_device.h"
 #include "miphy_ext.h"
 #include "tables/nr_demod_tables.h"
@@ -726,7 +727,362 @@ __global__ void __launch_bounds__(64) pusch_evm_reduce_kernel(const miphy_pusch_
   evm_sums[jp->evm_offset + sy] = s;
 }
 
+// ------------------------------------------------------------------------------------------------ one codeword on 1..4 transmit layers
+// Beyond the 23.5 reference (pusch_demodulator_impl.h asserts one layer): L x P zero forcing (equalize_device.h) and the layer demapping of
+// TS 38.211 6.3.1.3 -- element i of layer ly is codeword symbol L i + ly -- in front of the same soft demapper and descrambler.
+
+// Data elements per layer of a job whose fields hold the rules below (popcounts: the kernels evaluate it once per workgroup).
+__host__ __device__ __forceinline__ unsigned pusch_demod_count_re(const miphy_pusch_demod_job& j)
+{
+  const unsigned dm = (j.dmrs_type == 1 ? 6u : 4u) * j.nof_cdm_groups_without_data; // DM-RS elements per PRB (dmrs_prb_mask)
+  unsigned nprb = 0;
+  for (int w = 0; w < 5; ++w) {
+    const int left = (int)j.grid_nof_prb - 64 * w;
+    if (left > 0) {
+      const uint64_t m = j.rb_mask[w] & (left >= 64 ? ~0ull : ((1ull << left) - 1ull));
+#ifdef __HIP_DEVICE_COMPILE__
+      nprb += (unsigned)__popcll(m);
+#else
+      nprb += (unsigned)__builtin_popcountll(m);
+#endif
+    }
+  }
+  unsigned nsym_dmrs = 0;
+  for (unsigned s = j.start_symbol; s < (unsigned)j.start_symbol + j.nof_symbols; ++s)
+    nsym_dmrs += (j.dmrs_symbols_mask >> s) & 1u;
+  return nprb * (12u * (j.nof_symbols - nsym_dmrs) + (12u - dm) * nsym_dmrs);
+}
+
+// What a layered job (j = its base, L = its layers) must satisfy, once, evaluated in this order: R(condition, message of the host, its arguments).
+// The kernels skip a device-resident job that breaks a rule (pusch_demod_layers_job_ok), the host refuses one with the rule's message.
+#define PUSCH_DEMOD_LAYERS_RULES(R)                                                                                                                    \
+  R(L >= 1 && L <= 4, "invalid number of transmit layers %u", L)                                                                                      \
+  R(j.nof_rx_ports >= 1 && j.nof_rx_ports <= 4, "invalid number of receive ports")                                                                    \
+  R(L <= j.nof_rx_ports, "%u transmit layers on %u receive ports", L, (unsigned)j.nof_rx_ports)                                                       \
+  R(j.mod == 1 || j.mod == 2 || j.mod == 4 || j.mod == 6 || j.mod == 8, "invalid modulation order %u", (unsigned)j.mod)                               \
+  R(j.nof_symbols >= 1 && j.start_symbol + j.nof_symbols <= 14, "invalid time allocation")                                                            \
+  R(j.ce_compact || (j.ce_nof_symbols >= j.start_symbol + j.nof_symbols && j.ce_nof_symbols <= 14), "channel estimate too short")                     \
+  R(j.dmrs_type == 1 || j.dmrs_type == 2, "invalid DM-RS type")                                                                                       \
+  R(j.nof_cdm_groups_without_data >= 1 && j.nof_cdm_groups_without_data <= (j.dmrs_type == 1 ? 2 : 3), "invalid number of CDM groups without data")   \
+  R(j.grid_nof_prb >= 1 && j.grid_nof_prb <= 275, "invalid grid width")                                                                               \
+  R(j.n_id < 1024, "invalid scrambling identifier")                                                                                                   \
+  R(j.rnti < 65536, "invalid RNTI")                                                                                                                   \
+  R(j.nof_placeholders == 0, "UCI placeholders are not supported on this entry point")                                                                \
+  R(j.nof_llr == pusch_demod_count_re(j) * L * j.mod, "%u LLRs requested, the allocation holds %u on %u layers", j.nof_llr,                           \
+    pusch_demod_count_re(j) * L * j.mod, L)
+
+__host__ __device__ __forceinline__ bool pusch_demod_layers_job_ok(const miphy_pusch_demod_layers_job& lj)
+{
+  const miphy_pusch_demod_job& j = lj.base;
+  const unsigned               L = lj.nof_tx_layers;
+#define PUSCH_RULE_HOLDS(cond, ...) &&(cond)
+  return true PUSCH_DEMOD_LAYERS_RULES(PUSCH_RULE_HOLDS);
+#undef PUSCH_RULE_HOLDS
+}
+
+// Scrambling sequence of a layered transmission: up to four times the x1 table and one workgroup's LDS. A sequence that fits both is made whole by
+// workgroup (transmission, 0) as pusch_scrambling_kernel makes it (x1 from the table, x2 from the basis and the doubling recurrence); a longer one in
+// pieces of SEQ_PIECE words, workgroup (transmission, piece) jumping both shift registers to the piece's first bit (gold_piece).
+// seq: [transmission][stride] words.
+constexpr int SEQ_PIECE = SEQ_STRIDE / 2;
+__global__ void __launch_bounds__(SCR_THREADS) pusch_seq_layers_kernel(const miphy_pusch_demod_layers_job* __restrict__ jobs, const gold_tables* __restrict__ gt,
+                                                               uint32_t* __restrict__ seq, uint32_t stride)
+{
+  __shared__ uint32_t w[SEQ_STRIDE]; // one sequence, or w1 | w2 of a piece
+  const miphy_pusch_demod_layers_job* __restrict__ lj = jobs + blockIdx.x;
+  if (!pusch_demod_layers_job_ok(*lj)) // uniform
+    return;
+  const int      tid = threadIdx.x, nt = blockDim.x;
+  const int      nwords = min((int)((lj->base.nof_llr + 31u) >> 5) + 2, (int)stride); // + the 64-bit window of the last resource element
+  const uint32_t c_init = (lj->base.rnti << 15) + lj->base.n_id;
+  uint32_t*      o      = seq + (size_t)blockIdx.x * stride;
+  if (nwords <= SEQ_STRIDE) {
+    if (blockIdx.y != 0)
+      return;
+    gold_x2_sequence(*gt, c_init, nwords, w, tid, nt);
+    for (int i = tid; i < nwords; i += nt)
+      o[i] = w[i] ^ gt->x1_seq[i];
+    return;
+  }
+  const int first = (int)blockIdx.y * SEQ_PIECE;
+  if (first >= nwords)
+    return;
+  gold_piece(*gt, c_init, first, min(SEQ_PIECE, nwords - first), w, w + SEQ_PIECE, o + first, tid, nt);
+}
+
+// MOD soft bits of one equalised symbol, descrambled with the low MOD bits of `bits`, to q: the packed demapper where no NaN can appear, the exact
+// sequence otherwise; one wide store where q is aligned to it, bytes otherwise.
+template <int MOD>
+__device__ __forceinline__ void demod_emit(float re, float im, float nvar, unsigned sym_idx, uint32_t bits, const float2* tab, int8_t* q)
+{
+#pragma clang fp contract(off)
+  const float rcp_chk = (nvar > 0.f) ? 1.0f / nvar : 0.0f;
+  const bool  fast    = fabsf(re) < INFINITY && fabsf(im) < INFINITY && rcp_chk < INFINITY;
+  uint64_t    w       = 0;
+  bool        packed  = false;
+  if constexpr (MOD >= 2) {
+    if (fast) {
+      w      = demod_symbol_packed<MOD>(re, im, nvar, tab, bits);
+      packed = true;
+    }
+  }
+  if (!packed) {
+    int l[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (fast)
+      demod_symbol<MOD, true>(re, im, nvar, sym_idx, tab, l);
+    else
+      demod_symbol<MOD, false>(re, im, nvar, sym_idx, tab, l);
+#pragma unroll
+    for (int b = 0; b < MOD; ++b) {
+      const int m = -(int)((bits >> b) & 1u); // 0 / -1
+      w |= (uint64_t)(uint8_t)(int8_t)((l[b] ^ m) - m) << (8 * b);
+    }
+  }
+  constexpr unsigned WIDTH = MOD == 8 ? 8 : MOD == 4 ? 4 : MOD == 1 ? 1 : 2;
+  if (((uintptr_t)q % WIDTH) == 0) {
+    if (MOD == 8)
+      *reinterpret_cast<uint2*>(q) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+    else if (MOD == 6) {
+      uint16_t* q2 = reinterpret_cast<uint16_t*>(q);
+      q2[0] = (uint16_t)w, q2[1] = (uint16_t)(w >> 16), q2[2] = (uint16_t)(w >> 32);
+    } else if (MOD == 4)
+      *reinterpret_cast<uint32_t*>(q) = (uint32_t)w;
+    else if (MOD == 2)
+      *reinterpret_cast<uint16_t*>(q) = (uint16_t)w;
+    else
+      q[0] = (int8_t)w;
+  } else {
+#pragma unroll
+    for (int b = 0; b < MOD; ++b)
+      q[b] = (int8_t)(w >> (8 * b));
+  }
+}
+
+// One thread = one allocated subcarrier walked over the OFDM symbols, as demod_columns: with the compact estimate zf_prepare runs once and its result
+// stays in registers, per element only the samples are loaded and zf_apply runs. The L symbols of an element are L consecutive symbols of the
+// codeword: L MOD consecutive bytes, descrambled with L MOD (<= 32) consecutive chips.
+template <int MOD, int L>
+__device__ __forceinline__ void demod_layers_columns(const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab)
+{
+  const int  nsc = a.nsc, np = a.nports;
+  const bool compact = a.ce_nof_symbols == 1;
+  float2     h[L][4];
+#pragma unroll
+  for (int l = 0; l < L; ++l)
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      h[l][p] = make_float2(0.f, 0.f);
+  auto load_h = [&](int row) { // estimate [layer][rx port][ce_nof_symbols][nsc]
+#pragma unroll
+    for (int l = 0; l < L; ++l)
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        if (p < np)
+          h[l][p] = a.ce[((size_t)(l * np + p) * a.ce_nof_symbols + row) * nsc + sc];
+  };
+  zf_prepared<L> q;
+  if (!active)
+    return;
+  if (compact) {
+    load_h(0);
+    zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
+  }
+  int prefix = a.prefix0; // data elements per layer of the transmission before the current symbol
+  for (int sy = a.start_symbol; sy < a.end_symbol; ++sy) {
+    const bool is_dmrs = (a.dmrs_syms >> sy) & 1;
+    const int  npp     = is_dmrs ? a.per_dm : 12;
+    const int  r       = is_dmrs ? (a.per_dm ? r_dm : -1) : a_idx;
+    if (r >= 0) {
+      float2 y[4], x[L];
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        y[p] = (p < np) ? a.grid[((size_t)((a.rxp >> (8 * p)) & 0xffu) * 14 + sy) * nsc + sc] : make_float2(0.f, 0.f);
+      if (!compact) {
+        load_h(sy);
+        zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
+      }
+      zf_apply<L>(h, np, y, q, x);
+      const uint32_t e0   = (uint32_t)(prefix + r) * (uint32_t)L; // first of the element's L codeword symbols
+      const uint32_t bo   = e0 * (uint32_t)MOD;
+      const uint64_t two  = (uint64_t)a.seq[bo >> 5] | ((uint64_t)a.seq[(bo >> 5) + 1] << 32);
+      const uint32_t bits = (uint32_t)(two >> (bo & 31u));
+      int8_t*        q0   = a.llr + (size_t)bo;
+#pragma unroll
+      for (int l = 0; l < L; ++l)
+        demod_emit<MOD>(x[l].x, x[l].y, q.nvar[l], e0 + l, bits >> (l * MOD), tab, q0 + l * MOD);
+    }
+    prefix += a.nprb * npp;
+  }
+}
+
+// ONE_LAYER: the one-layer walk itself (demod_columns), the bytes of miphy_pusch_demodulate_batch; otherwise L = 2..4.
+template <int MOD, bool ONE_LAYER>
+__device__ __forceinline__ void demod_layers_dispatch(int L, const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab,
+                                                      float* evm_red, int tid)
+{
+  if constexpr (ONE_LAYER) {
+    demod_columns<MOD>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+    return;
+  }
+  switch (L) { // uniform
+    case 2:
+      demod_layers_columns<MOD, 2>(a, active, sc, a_idx, r_dm, tab);
+      break;
+    case 3:
+      demod_layers_columns<MOD, 3>(a, active, sc, a_idx, r_dm, tab);
+      break;
+    default:
+      demod_layers_columns<MOD, 4>(a, active, sc, a_idx, r_dm, tab);
+      break;
+  }
+}
+
+// grid (transmissions, chunks of 256 allocated subcarriers, parts of the OFDM symbols), as pusch_demod_kernel. seq: [transmission][stride] words.
+// Two kernels share a batch: ONE_LAYER takes its jobs on one layer, with the registers and the occupancy of pusch_demod_kernel, the other those on
+// two to four layers (four 4 x 4 matrices in registers); a workgroup leaves at once when the job belongs to the other kernel.
+template <bool ONE_LAYER>
+__global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1) pusch_demod_layers_kernel(const miphy_pusch_demod_layers_job* __restrict__ jobs, const float2* __restrict__ grid,
+                                                                            const float2* __restrict__ ce, const float* __restrict__ scalars,
+                                                                            int8_t* __restrict__ llr, const uint32_t* __restrict__ seq, uint32_t stride)
+{
+  __shared__ uint16_t prb_of[276];
+  __shared__ int      nprb_s;
+  __shared__ float2   tab[64];
+  __shared__ uint64_t rbm[5];
+  __shared__ float    evm_red[4];
+  const int L = jobs[blockIdx.x].nof_tx_layers;
+  if ((L == 1) != ONE_LAYER) // uniform
+    return;
+  if (!pusch_demod_layers_job_ok(jobs[blockIdx.x])) // uniform: a device-resident job the host has not seen is skipped
+    return;
+  const demod_job_words j   = demod_load_job(&jobs[blockIdx.x].base);
+  const int             tid = threadIdx.x;
+  const demod_tab_entry te  = demod_table_entry(j.mod(), tid);
+  const float           noise_var = scalars[j.scalars_offset() + 2];
+  const int             nprb = demod_prb_list(j, rbm, prb_of, &nprb_s, tid, DEMOD_THREADS);
+  demod_table_store(tab, te);
+  if ((int)blockIdx.y * DEMOD_THREADS >= nprb * 12)
+    return; // uniform
+  const unsigned dmask = dmrs_prb_mask(j.dmrs_type(), j.cdm_groups());
+  demod_args     a;
+  a.per_dm       = 12 - __popc(dmask);
+  a.dmrs_syms    = j.dmrs_symbols_mask();
+  a.start_symbol = j.start_symbol();
+  a.end_symbol   = a.start_symbol + j.nof_symbols();
+  a.nprb         = nprb;
+  a.prefix0      = 0;
+  if (gridDim.z > 1) { // uniform
+    const int per = (a.end_symbol - a.start_symbol + (int)gridDim.z - 1) / (int)gridDim.z;
+    const int f = a.start_symbol + (int)blockIdx.z * per, l = min(a.end_symbol, f + per);
+    if (f >= l)
+      return;
+    for (int sy = a.start_symbol; sy < f; ++sy)
+      a.prefix0 += nprb * (((a.dmrs_syms >> sy) & 1u) ? a.per_dm : 12);
+    a.start_symbol = f;
+    a.end_symbol   = l;
+  }
+  a.nsc            = j.grid_nof_prb() * 12;
+  a.nports         = j.nof_rx_ports();
+  a.ce_nof_symbols = j.ce_compact() ? 1 : j.ce_nof_symbols();
+  a.rxp            = j.rx_ports();
+  a.grid           = grid + j.grid_offset();
+  a.ce             = ce + j.ce_offset();
+  a.llr            = llr + j.llr_offset();
+  a.noise_var      = noise_var;
+  a.nph            = 0;
+  a.ph             = nullptr;
+  a.evm_part       = nullptr;
+  a.seq            = seq + (size_t)blockIdx.x * stride;
+  const int  a_idx  = (int)blockIdx.y * DEMOD_THREADS + tid;
+  const bool active = a_idx < nprb * 12;
+  const int  pr     = a_idx / 12, k = a_idx - 12 * pr;
+  const int  sc     = active ? (int)prb_of[pr] * 12 + k : 0;
+  const int  r_dm   = ((dmask >> k) & 1u) ? -1 : pr * a.per_dm + __popc(~dmask & ((1u << k) - 1u));
+  __syncthreads(); // interval tables in LDS
+  switch (j.mod()) {
+    case 8:
+      demod_layers_dispatch<8, ONE_LAYER>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      break;
+    case 6:
+      demod_layers_dispatch<6, ONE_LAYER>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      break;
+    case 4:
+      demod_layers_dispatch<4, ONE_LAYER>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      break;
+    case 2:
+      demod_layers_dispatch<2, ONE_LAYER>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      break;
+    default:
+      demod_layers_dispatch<1, ONE_LAYER>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      break;
+  }
+}
+
 } // namespace
+
+extern "C" uint32_t miphy_pusch_demod_layers_nof_llr(const miphy_pusch_demod_layers_job* lj)
+{
+  if (!lj || lj->nof_tx_layers < 1 || lj->nof_tx_layers > 4 || lj->nof_tx_layers > lj->base.nof_rx_ports)
+    return 0;
+  return miphy_pusch_demod_nof_llr(&lj->base) * lj->nof_tx_layers;
+}
+
+extern "C" int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                                   const float* ce, const float* scalars, int8_t* llr, void* stream)
+{
+  MIPHY_REQUIRE(ctx && jobs && grid && ce && scalars && llr, "miphy_pusch_demodulate_layers_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "pusch_demodulate_layers: batch too large (max 65535 transmissions per call)");
+  uint32_t max_chunks = DEMOD_MAX_CHUNKS, max_layers = 4, max_words = 4 * SEQ_STRIDE; // device-resident jobs: the widest grid on four layers
+  bool     one_layer = true, more_layers = true;                                      // ... and both kernels
+  if (!jobs_on_device) {
+    uint32_t max_prb = 1, max_llr = 0;
+    max_layers = 1, one_layer = more_layers = false;
+    for (uint32_t i = 0; i < n; ++i) {
+      const miphy_pusch_demod_job& j = jobs[i].base;
+      const unsigned               L = jobs[i].nof_tx_layers;
+#define PUSCH_RULE_REQUIRE(cond, msg, ...) MIPHY_REQUIRE(cond, "pusch_demodulate_layers: job %u: " msg, i, ##__VA_ARGS__);
+      PUSCH_DEMOD_LAYERS_RULES(PUSCH_RULE_REQUIRE)
+#undef PUSCH_RULE_REQUIRE
+      uint32_t np = 0;
+      for (unsigned r = 0; r < j.grid_nof_prb; ++r)
+        np += (uint32_t)((j.rb_mask[r >> 6] >> (r & 63)) & 1ull);
+      max_prb    = np > max_prb ? np : max_prb;
+      max_layers = L > max_layers ? L : max_layers;
+      one_layer |= L == 1, more_layers |= L > 1;
+      max_llr    = j.nof_llr > max_llr ? j.nof_llr : max_llr;
+    }
+    max_chunks = (max_prb * 12 + DEMOD_THREADS - 1) / DEMOD_THREADS;
+    max_words  = ((max_llr + 31u) >> 5) + 2;
+  }
+  hipStream_t        s  = (hipStream_t)stream;
+  const gold_tables* gt = nullptr;
+  int                rc = miphy_get_gold_tables(ctx, &gt);
+  if (rc)
+    return rc;
+  const void* d_jobs = nullptr;
+  rc                 = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pusch_demod_layers_job) * (size_t)n, s, &d_jobs);
+  if (rc)
+    return rc;
+  const uint32_t stride = max_layers * (uint32_t)SEQ_STRIDE;
+  void*          work   = nullptr;
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, (size_t)n * stride * sizeof(uint32_t), &work)))
+    return rc;
+  uint32_t*   seq = static_cast<uint32_t*>(work);
+  const auto* dj  = (const miphy_pusch_demod_layers_job*)d_jobs;
+  hipLaunchKernelGGL(pusch_seq_layers_kernel, dim3(n, max_words <= (uint32_t)SEQ_STRIDE ? 1u : (max_words + SEQ_PIECE - 1) / SEQ_PIECE), dim3(SCR_THREADS), 0, s,
+                     dj, gt, seq, stride);
+  const uint32_t sym_parts = std::max(1u, std::min(4u, (uint32_t)ctx->num_cus / (n * max_chunks)));
+  if (one_layer)
+    hipLaunchKernelGGL(pusch_demod_layers_kernel<true>, dim3(n, max_chunks, sym_parts), dim3(DEMOD_THREADS), 0, s, dj, (const float2*)grid, (const float2*)ce,
+                       scalars, llr, (const uint32_t*)seq, stride);
+  if (more_layers)
+    hipLaunchKernelGGL(pusch_demod_layers_kernel<false>, dim3(n, max_chunks, sym_parts), dim3(DEMOD_THREADS), 0, s, dj, (const float2*)grid,
+                       (const float2*)ce, scalars, llr, (const uint32_t*)seq, stride);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
+}
 
 extern "C" uint32_t miphy_pusch_demod_nof_llr(const miphy_pusch_demod_job* j)
 {

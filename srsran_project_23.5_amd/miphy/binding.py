@@ -137,6 +137,11 @@ def lib():
         l.miphy_ulsch_placeholders.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         l.miphy_ulsch_demultiplex_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 6
         l.miphy_channel_equalize_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
+        if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_pusch_demodulate_layers_batch"):  # (an older build named by MIPHY_LIBRARY for an A-B has none of them)
+            l.miphy_channel_equalize_layers_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
+            l.miphy_pusch_demodulate_layers_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
+            l.miphy_pusch_demod_layers_nof_llr.argtypes = [C.c_void_p]
+            l.miphy_pusch_demod_layers_nof_llr.restype = C.c_uint32
         l.miphy_polar_block_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("miphy_ofdm_demodulate_symbols", "miphy_ofdm_modulate_symbols"):
             getattr(l, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -226,6 +231,17 @@ def pusch_demod_nof_llr(job):
     """Codeword length (data REs x bits per symbol) of one PuschDemodJob record (host computation in the library)."""
     a = np.ascontiguousarray(np.asarray(job, dtype=PuschDemodJob).reshape(1))
     return int(lib().miphy_pusch_demod_nof_llr(a.ctypes.data_as(C.c_void_p)))
+
+
+# Mirrors miphy_pusch_demod_layers_job: one codeword on 1..4 transmit layers.
+PuschDemodLayersJob = np.dtype([("base", PuschDemodJob), ("nof_tx_layers", np.uint8), ("reserved", np.uint8, 7)], align=True)
+assert PuschDemodLayersJob.itemsize == 128 and PuschDemodLayersJob.fields["nof_tx_layers"][1] == 120, PuschDemodLayersJob.itemsize
+
+
+def pusch_demod_layers_nof_llr(job):
+    """Codeword length (data REs x layers x bits per symbol) of one PuschDemodLayersJob record; 0 for an invalid one."""
+    a = np.ascontiguousarray(np.asarray(job, dtype=PuschDemodLayersJob).reshape(1))
+    return int(lib().miphy_pusch_demod_layers_nof_llr(a.ctypes.data_as(C.c_void_p)))
 
 
 # Mirrors miphy_re_pattern / miphy_pdsch_mod_job / miphy_dmrs_pdsch_job.
@@ -865,6 +881,17 @@ class Context:
         jobs, n, ptr, on_dev = self._descs(jobs, EqualizerJob)
         check(lib().miphy_channel_equalize_batch(self.h, ptr, on_dev, n, _dptr(ch_symbols), _dptr(ch_estimates), _dptr(eq_symbols), _dptr(eq_noise_vars),
                                                  _stream_ptr(stream)))
+
+    def channel_equalize_layers_batch(self, jobs, ch_symbols, ch_estimates, eq_symbols, eq_noise_vars, stream=None):
+        """Zero forcing of 1..4 layers on at least as many (at most 4) receive ports for a batch of EqualizerJob records."""
+        jobs, n, ptr, on_dev = self._descs(jobs, EqualizerJob)
+        check(lib().miphy_channel_equalize_layers_batch(self.h, ptr, on_dev, n, _dptr(ch_symbols), _dptr(ch_estimates), _dptr(eq_symbols),
+                                                        _dptr(eq_noise_vars), _stream_ptr(stream)))
+
+    def pusch_demodulate_layers_batch(self, jobs, grid, ce, scalars, llr, stream=None):
+        """PUSCH demodulator for one codeword on 1..4 transmit layers: a batch of PuschDemodLayersJob records."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschDemodLayersJob)
+        check(lib().miphy_pusch_demodulate_layers_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _dptr(llr), _stream_ptr(stream)))
 
     def polar_block_batch(self, code, op, param, n, x, out, stream=None):
         check(lib().miphy_polar_block_batch(self.h, C.byref(code) if code is not None else None, op, param, n, _dptr(x), _dptr(out), _stream_ptr(stream)))
