@@ -357,6 +357,25 @@ int miphy_dmrs_pusch_estimate_batch(miphy_ctx* ctx, const miphy_pusch_chest_job*
                                     const float* grid /* device cf_t */, float* ce /* device cf_t */, float* scalars /* device */,
                                     void* stream);
 
+/* DM-RS estimator for PUSCH on 1..4 transmit layers  --  beyond the 23.5 reference, whose estimator runs each layer through the one-layer
+ * least-squares fit and never undoes the frequency-domain OCC: layers 2g and 2g+1 share CDM group g and its resource elements, so its
+ * estimates of a shared group come out as h_2g +- h_2g+1. Same jobs, arguments and output layouts as miphy_dmrs_pusch_estimate_batch;
+ * DM-RS type 1, single-symbol DM-RS, layer ly = DM-RS port ly, no hopping, no external pilots. Per (job, rx port, CDM group g), over the
+ * np = 6 nprb pilots i of the allocated PRBs (ascending, concatenated; subcarriers 12 r + 2 q + g), r_d[i] = layer 0's pilot:
+ *   z[i]   = (sum_d x_d[i] conj(r_d[i])) / (nds beta)
+ *   only layer 2g present (one layer; layer 2 of three): as miphy_dmrs_pusch_estimate_batch; a job on one layer gives its bytes.
+ *   both present: s_a[m] = (z[2m] + z[2m+1]) / 2, s_b[m] = (z[2m] - z[2m+1]) / 2, m = 0 .. np/2 - 1 (three pairs per PRB, none across PRBs);
+ *     estimate: the reference's linear interpolator over the 12 nprb concatenated subcarriers with anchors s_l[m] at 4m + 1 + g (edges held)
+ *     epre = sum |x|^2 / (np nds); rsrp_l = beta^2 sum_m |s_l[m]|^2 / (np/2)
+ *     noise_var = (sum |x_d[i] - beta r_d[i] (A + (-1)^i B)|^2 / np * 6) / (6 nds - 2), A, B = per-PRB means of s_a, s_b, the same for both
+ *     layers; with nds < 3 noise_var = 0.001 epre as on one layer; snr_l = (rsrp_l / beta^2) / noise_var (1000 when noise_var is 0)
+ *     time alignment per layer: the 4096-point IDFT and peak rule of the one-layer estimator with s_l[m] on both pilot subcarriers of pair m
+ * A host job with hop_symbol != 0 (or breaking a rule of miphy_dmrs_pusch_estimate_batch) is MIPHY_EINVAL with nothing enqueued; a
+ * device-resident one is skipped. Out: double-symbol DM-RS (TD-OCC), DM-RS type 2, hopping. */
+int miphy_dmrs_pusch_estimate_layers_batch(miphy_ctx* ctx, const miphy_pusch_chest_job* jobs, int jobs_on_device, uint32_t n,
+                                           const float* grid /* device cf_t */, float* ce /* device cf_t */, float* scalars /* device */,
+                                           void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * PUSCH demodulator  --  replaces srsran::pusch_demodulator::demodulate (the block between the channel estimator
  * and the decoder), i.e. channel_equalizer::equalize + demodulation_mapper::demodulate_soft + descrambling in one pass
@@ -893,6 +912,22 @@ int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus /* 
 int miphy_pusch_process_batch(miphy_ctx* ctx, const miphy_pusch_pdu* pdus /* host */, uint32_t n, const float* grid /* device cf_t */,
                               int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out /* device */,
                               miphy_pusch_result* results /* device, n */, float* scalars_out /* device, n x 20 */, void* stream);
+
+/* PUSCH processor for one codeword on 1..4 transmit layers  --  beyond the 23.5 reference (pusch_processor_impl.cpp asserts one layer). One
+ * call chains, on one stream, miphy_dmrs_pusch_estimate_layers_batch (compact estimate), miphy_pusch_demodulate_layers_batch and
+ * miphy_pusch_decode_batch (nof_layers = nof_tx_layers); estimates and LLRs stay in a workspace of the context. DM-RS type 1, single-symbol
+ * DM-RS, two CDM groups without data; no UCI and no EVM (the layered demodulator has neither), hence no _ex form. A batch may mix layer
+ * counts; a PDU on one layer gives the bytes of miphy_pusch_process_batch for its base record (transport block, result, first 20 scalars).
+ * scalars_out: per PDU 80 floats, [rx port][layer][5] at 5 * (port * nof_tx_layers + layer) as the estimator writes them. A PDU that breaks
+ * a rule is MIPHY_EINVAL with nothing enqueued. */
+typedef struct {
+  miphy_pusch_pdu base;
+  uint8_t         nof_tx_layers; /* 1..4, <= base.nof_rx_ports */
+  uint8_t         reserved[7];
+} miphy_pusch_layers_pdu;
+int miphy_pusch_process_layers_batch(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus /* host */, uint32_t n, const float* grid /* device cf_t */,
+                                     int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out /* device */,
+                                     miphy_pusch_result* results /* device, n */, float* scalars_out /* device, n x 80 */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * UL-SCH demultiplexer  --  replaces srsran::ulsch_demultiplex::demultiplex / get_placeholders (UCI multiplexed on PUSCH)

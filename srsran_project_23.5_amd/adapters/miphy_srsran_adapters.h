@@ -813,11 +813,13 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------------------------- estimator
-/// srsran::dmrs_pusch_estimator over miphy_dmrs_pusch_estimate_batch (dmrs_pusch_estimator.h:84).
+/// srsran::dmrs_pusch_estimator over miphy_dmrs_pusch_estimate_batch (dmrs_pusch_estimator.h:84). \c separate_layers: through
+/// miphy_dmrs_pusch_estimate_layers_batch, which separates the layers that share a CDM group (beyond the reference, whose estimate of such a
+/// layer holds the other one too); the default is the reference's arithmetic.
 class dmrs_pusch_estimator_hip : public srsran::dmrs_pusch_estimator
 {
 public:
-  explicit dmrs_pusch_estimator_hip(std::shared_ptr<context> c) : c(std::move(c)) {}
+  explicit dmrs_pusch_estimator_hip(std::shared_ptr<context> c, bool separate_layers = false) : c(std::move(c)), separate_layers(separate_layers) {}
   void estimate(srsran::channel_estimate& estimate, const srsran::resource_grid_reader& grid, const configuration& config) override
   {
     srsran_assert(config.type == srsran::dmrs_type::TYPE1, "Only DM-RS type 1 is supported.");
@@ -866,7 +868,8 @@ public:
       }
     }
     c->h2d(d_ce, ce_host.data(), ce_n * sizeof(srsran::cf_t));
-    context::check(miphy_dmrs_pusch_estimate_batch(c->ctx, &j, 0, 1, d_g, d_ce, d_sc, c->stream), "dmrs_pusch_estimate");
+    context::check((separate_layers ? miphy_dmrs_pusch_estimate_layers_batch : miphy_dmrs_pusch_estimate_batch)(c->ctx, &j, 0, 1, d_g, d_ce, d_sc, c->stream),
+                   "dmrs_pusch_estimate");
     std::vector<float> sc(nports * nl * 5);
     c->d2h(ce_host.data(), d_ce, ce_n * sizeof(srsran::cf_t));
     c->d2h(sc.data(), d_sc, sc.size() * sizeof(float));
@@ -889,6 +892,7 @@ public:
 
 private:
   std::shared_ptr<context>  c;
+  bool                      separate_layers;
   std::vector<srsran::cf_t> host, ce_host;
 };
 
@@ -1659,9 +1663,12 @@ class pusch_processor_hip : public srsran::pusch_processor
 public:
   /// \c uci_dec: uci_decoder_hip (the fields are decoded on the device behind the demultiplexer) or the reference's CPU UCI decoder
   /// (the soft bits come back and are decoded on the host); without it PDUs with multiplexed UCI are refused. \c enable_evm as in create_pusch_demodulator_factory_sw.
+  /// \c max_layers: 1 (the reference's limit) to 4; a PDU on two to four layers goes through miphy_pusch_process_layers_batch, which has
+  /// neither UCI nor EVM.
   pusch_processor_hip(std::shared_ptr<context> c, unsigned nof_iterations, bool early_stop, std::unique_ptr<srsran::uci_decoder> uci_dec_ = nullptr,
-                      bool enable_evm_ = false) :
-    c(std::move(c)), dec_nof_iterations(nof_iterations), dec_enable_early_stop(early_stop), uci_dec(std::move(uci_dec_)), enable_evm(enable_evm_)
+                      bool enable_evm_ = false, unsigned max_layers_ = 1) :
+    c(std::move(c)), dec_nof_iterations(nof_iterations), dec_enable_early_stop(early_stop), uci_dec(std::move(uci_dec_)), enable_evm(enable_evm_),
+    max_layers(max_layers_)
   {
   }
   void process(srsran::span<uint8_t>                    data,
@@ -1673,11 +1680,16 @@ public:
     const bool has_uci = pdu.uci.nof_harq_ack != 0 || pdu.uci.nof_csi_part1 != 0 || pdu.uci.nof_csi_part2 != 0;
     require(!has_uci || uci_dec != nullptr, "pusch_processor_hip: a PDU with multiplexed UCI needs the UCI decoder (see the factory).");
     require(has_uci || pdu.codeword.has_value(), "pusch_processor_hip: the PDU carries neither a codeword nor UCI.");
-    require(pdu.dmrs == srsran::dmrs_type::TYPE1 && pdu.nof_cdm_groups_without_data == 2 && pdu.nof_tx_layers == 1,
-            "Only DM-RS type 1, two CDM groups without data and one layer are supported.");
+    const unsigned nl = pdu.nof_tx_layers;
+    require(pdu.dmrs == srsran::dmrs_type::TYPE1 && pdu.nof_cdm_groups_without_data == 2 && nl >= 1 && nl <= max_layers,
+            "Only DM-RS type 1, two CDM groups without data and one layer (up to max_layers with the layered path) are supported.");
+    require(nl == 1 || (!has_uci && !enable_evm && pdu.codeword.has_value() && nl <= pdu.rx_ports.size()),
+            "pusch_processor_hip: two to four layers need a codeword, at least as many receive ports, no UCI and no EVM.");
     const srsran::bounded_bitset<srsran::MAX_RB> rb_mask = pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb);
     const unsigned nprb = rb_mask.size(), nsc = nprb * 12, nports = pdu.rx_ports.size();
-    miphy_pusch_pdu p = {};
+    miphy_pusch_layers_pdu lp = {};
+    miphy_pusch_pdu&       p  = lp.base;
+    lp.nof_tx_layers          = static_cast<uint8_t>(nl);
     p.numerology = pdu.slot.numerology(), p.slot_in_frame = pdu.slot.slot_index(), p.rnti = pdu.rnti, p.n_id = pdu.n_id;
     p.dmrs_scrambling_id = pdu.scrambling_id, p.Nref = pdu.tbs_lbrm_bytes * 8, p.tb_bytes = data.size(), p.harq_cb_index = 0;
     p.n_scid = pdu.n_scid, p.mod = srsran::get_bits_per_symbol(pdu.mcs_descr.modulation), p.nof_rx_ports = nports;
@@ -1730,12 +1742,12 @@ public:
     }
     auto*    resident = dynamic_cast<rx_softbuffer_hip*>(&softbuffer);
     auto*    d_g    = static_cast<float*>(c->buf(0, host.size() * sizeof(srsran::cf_t)));
-    auto*    d_misc = static_cast<uint8_t*>(c->buf(3, 64 + 64 + 128 + data.size() + 64));
+    auto*    d_misc = static_cast<uint8_t*>(c->buf(3, 64 + 64 + 384 + data.size() + 64));
     auto*    d_uci  = static_cast<int8_t*>(c->buf(4, nof_uci_llr + 64));
     auto*    d_evm  = reinterpret_cast<float*>(d_misc + 56); // [0,52) codeblock CRC flags of a host softbuffer, [56,60) EVM, [64,..) result
     auto*    d_res  = reinterpret_cast<miphy_pusch_result*>(d_misc + 64);
     auto*    d_sc   = reinterpret_cast<float*>(d_misc + 128);
-    uint8_t* d_tb   = d_misc + 256;
+    uint8_t* d_tb   = d_misc + 512; // (80 scalars of a PDU on four layers in front of it)
     int8_t*  d_soft = nullptr;
     uint8_t *d_msg = nullptr, *d_crc = nullptr;
     std::vector<uint8_t> crc_h(sg.nof_cbs);
@@ -1759,8 +1771,13 @@ public:
     }
     c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
     c->h2d(d_tb, data.data(), data.size());
-    context::check(miphy_pusch_process_batch_ex(c->ctx, &p, &u, 1, d_g, d_soft, d_msg, d_crc, d_tb, d_res, d_sc, d_uci, enable_evm ? d_evm : nullptr, c->stream),
-                   "pusch_process");
+    if (nl > 1) {
+      context::check(miphy_pusch_process_layers_batch(c->ctx, &lp, 1, d_g, d_soft, d_msg, d_crc, d_tb, d_res, d_sc, c->stream), "pusch_process_layers");
+    } else {
+      context::check(
+          miphy_pusch_process_batch_ex(c->ctx, &p, &u, 1, d_g, d_soft, d_msg, d_crc, d_tb, d_res, d_sc, d_uci, enable_evm ? d_evm : nullptr, c->stream),
+          "pusch_process");
+    }
     // With the device UCI decoder the fields are decoded behind _ex on the same stream: only payload bits and verdicts come back.
     const auto*          uci_dec_hip   = dynamic_cast<const uci_decoder_hip*>(uci_dec.get());
     const bool           uci_on_device = has_uci && uci_dec_hip != nullptr;
@@ -1792,7 +1809,7 @@ public:
       c->d2h(uci_out.data(), d_uci_out, nof_uci_out); // (verdict slots without a job are not read)
     }
     miphy_pusch_result r;
-    float              sc[20], evm = 0.F;
+    float              sc[80], evm = 0.F; // [rx port][layer][5]; layer 0 is what the channel state information averages
     uci_llr.resize(uci_on_device ? 0 : nof_uci_llr);
     if (nof_uci_llr && !uci_on_device) {
       c->d2h(uci_llr.data(), d_uci, nof_uci_llr);
@@ -1801,7 +1818,7 @@ public:
       c->d2h(&evm, d_evm, sizeof(evm));
     }
     c->d2h(&r, d_res, sizeof(r));
-    c->d2h(sc, d_sc, sizeof(sc));
+    c->d2h(sc, d_sc, (nl > 1 ? 80 : 20) * sizeof(float));
     c->d2h(data.data(), d_tb, data.size());
     if (resident == nullptr) {
       c->d2h(crc_h.data(), d_crc, sg.nof_cbs);
@@ -1824,7 +1841,8 @@ public:
     float                             epre = 0, rsrp = 0, snr = 0;
     double                            ta   = 0;
     for (unsigned i = 0; i != nports; ++i) {
-      rsrp += sc[5 * i + 0], epre += sc[5 * i + 1], snr += sc[5 * i + 3], ta += sc[5 * i + 4];
+      const float* s = sc + 5 * i * nl;
+      rsrp += s[0], epre += s[1], snr += s[3], ta += s[4];
     }
     csi.epre_dB        = srsran::convert_power_to_dB(epre / static_cast<float>(nports));
     csi.rsrp_dB        = srsran::convert_power_to_dB(rsrp / static_cast<float>(nports));
@@ -1894,6 +1912,7 @@ private:
   bool                      dec_enable_early_stop;
   std::unique_ptr<srsran::uci_decoder>      uci_dec;
   bool                                      enable_evm;
+  unsigned                                  max_layers;
   std::vector<srsran::cf_t>                 host;
   std::vector<srsran::log_likelihood_ratio> uci_llr;
   std::vector<uint8_t>                      uci_out;
@@ -1905,18 +1924,22 @@ class pusch_processor_factory_hip : public srsran::pusch_processor_factory
 {
 public:
   /// \c uci_dec_factory: the reference's create_uci_decoder_factory_sw(...) for PDUs with multiplexed UCI (nullptr: such PDUs are
-  /// rejected by the validator); \c enable_evm as in create_pusch_demodulator_factory_sw.
+  /// rejected by the validator); \c enable_evm as in create_pusch_demodulator_factory_sw; \c max_layers: 1 to 4, for the processor and
+  /// its validator (above one layer: miphy_pusch_process_layers_batch, beyond the reference).
   pusch_processor_factory_hip(std::shared_ptr<context>                     c,
                               unsigned                                     nof_iterations,
                               bool                                         early_stop,
                               std::shared_ptr<srsran::uci_decoder_factory> uci_dec_factory = nullptr,
-                              bool                                         enable_evm      = false) :
-    c(std::move(c)), nof_iterations(nof_iterations), early_stop(early_stop), uci_dec_factory(std::move(uci_dec_factory)), enable_evm(enable_evm)
+                              bool                                         enable_evm      = false,
+                              unsigned                                     max_layers      = 1) :
+    c(std::move(c)), nof_iterations(nof_iterations), early_stop(early_stop), uci_dec_factory(std::move(uci_dec_factory)), enable_evm(enable_evm),
+    max_layers(max_layers)
   {
   }
   std::unique_ptr<srsran::pusch_processor> create() override
   {
-    return std::make_unique<pusch_processor_hip>(c, nof_iterations, early_stop, uci_dec_factory ? uci_dec_factory->create() : nullptr, enable_evm);
+    return std::make_unique<pusch_processor_hip>(c, nof_iterations, early_stop, uci_dec_factory ? uci_dec_factory->create() : nullptr, enable_evm,
+                                                 max_layers);
   }
   std::unique_ptr<srsran::pusch_pdu_validator> create_validator() override; // defined at the end of this header
 
@@ -1926,6 +1949,7 @@ private:
   bool                                         early_stop;
   std::shared_ptr<srsran::uci_decoder_factory> uci_dec_factory;
   bool                                         enable_evm;
+  unsigned                                     max_layers;
 };
 
 // ---------------------------------------------------------------------------------------------------------------- uplink processor
@@ -3414,7 +3438,17 @@ MIPHY_SIMPLE_FACTORY(ldpc_rate_matcher_factory_hip, ldpc_rate_matcher_factory, l
 MIPHY_SIMPLE_FACTORY(ldpc_rate_dematcher_factory_hip, ldpc_rate_dematcher_factory, ldpc_rate_dematcher, ldpc_rate_dematcher_hip)
 MIPHY_SIMPLE_FACTORY(pdsch_encoder_factory_hip, pdsch_encoder_factory, pdsch_encoder, pdsch_encoder_hip)
 MIPHY_SIMPLE_FACTORY(pusch_decoder_factory_hip, pusch_decoder_factory, pusch_decoder, pusch_decoder_hip)
-MIPHY_SIMPLE_FACTORY(dmrs_pusch_estimator_factory_hip, dmrs_pusch_estimator_factory, dmrs_pusch_estimator, dmrs_pusch_estimator_hip)
+/// \c separate_layers as in dmrs_pusch_estimator_hip.
+class dmrs_pusch_estimator_factory_hip : public srsran::dmrs_pusch_estimator_factory
+{
+public:
+  explicit dmrs_pusch_estimator_factory_hip(std::shared_ptr<context> c, bool separate_layers = false) : c(std::move(c)), separate_layers(separate_layers) {}
+  std::unique_ptr<srsran::dmrs_pusch_estimator> create() override { return std::make_unique<dmrs_pusch_estimator_hip>(c, separate_layers); }
+
+private:
+  std::shared_ptr<context> c;
+  bool                     separate_layers;
+};
 MIPHY_SIMPLE_FACTORY(pdcch_encoder_factory_hip, pdcch_encoder_factory, pdcch_encoder, pdcch_encoder_hip)
 MIPHY_SIMPLE_FACTORY(pusch_demodulator_factory_hip, pusch_demodulator_factory, pusch_demodulator, pusch_demodulator_hip)
 MIPHY_SIMPLE_FACTORY(pdsch_modulator_factory_hip, pdsch_modulator_factory, pdsch_modulator, pdsch_modulator_hip)
@@ -3460,9 +3494,9 @@ inline std::shared_ptr<srsran::pusch_decoder_factory> create_pusch_decoder_facto
 {
   return std::make_shared<pusch_decoder_factory_hip>(std::move(c));
 }
-inline std::shared_ptr<srsran::dmrs_pusch_estimator_factory> create_dmrs_pusch_estimator_factory_hip(std::shared_ptr<context> c)
+inline std::shared_ptr<srsran::dmrs_pusch_estimator_factory> create_dmrs_pusch_estimator_factory_hip(std::shared_ptr<context> c, bool separate_layers = false)
 {
-  return std::make_shared<dmrs_pusch_estimator_factory_hip>(std::move(c));
+  return std::make_shared<dmrs_pusch_estimator_factory_hip>(std::move(c), separate_layers);
 }
 inline std::shared_ptr<srsran::pdcch_encoder_factory> create_pdcch_encoder_factory_hip(std::shared_ptr<context> c)
 {
@@ -3932,9 +3966,22 @@ inline std::shared_ptr<srsran::channel_equalizer_factory> create_channel_equaliz
 class pusch_pdu_validator_hip : public srsran::pusch_pdu_validator
 {
 public:
-  pusch_pdu_validator_hip(std::unique_ptr<srsran::pusch_pdu_validator> ref, bool uci_supported) : ref(std::move(ref)), uci_supported(uci_supported) {}
+  /// \c max_layers: 1 (the reference's limit, the default) to 4 with pusch_processor_hip's layered path behind it.
+  pusch_pdu_validator_hip(std::unique_ptr<srsran::pusch_pdu_validator> ref, bool uci_supported, unsigned max_layers = 1) :
+    ref(std::move(ref)), uci_supported(uci_supported), max_layers(max_layers)
+  {
+  }
   bool is_valid(const srsran::pusch_processor::pdu_t& pdu) const override
   {
+    if (pdu.nof_tx_layers > 1) {
+      // Beyond the reference, whose validator stops at one layer (pusch_processor_impl.cpp:40-42): its other rules (DM-RS type 1, two CDM groups
+      // without data among them) on a copy on one layer; one codeword on at most max_layers layers, on at least as many ports, no UCI.
+      srsran::pusch_processor::pdu_t one = pdu;
+      one.nof_tx_layers                  = 1;
+      const bool has_uci                 = pdu.uci.nof_harq_ack != 0 || pdu.uci.nof_csi_part1 != 0 || pdu.uci.nof_csi_part2 != 0;
+      return pdu.nof_tx_layers <= max_layers && pdu.nof_tx_layers <= 4 && pdu.nof_tx_layers <= pdu.rx_ports.size() && !has_uci && pdu.codeword.has_value() &&
+             is_valid(one);
+    }
     // The reference's validator (pusch_processor_impl.cpp:54-58) refuses HARQ-ACK and CSI part 1 above 11 bits because its UCI decoder
     // does. With the device UCI decoder behind the processor those fields may have up to 1706 bits (polar coded): the reference's
     // remaining rules are applied to a copy of the PDU whose long fields are shortened to 11 bits, which none of them looks at
@@ -3965,6 +4012,7 @@ public:
 private:
   std::unique_ptr<srsran::pusch_pdu_validator> ref;
   bool                                         uci_supported;
+  unsigned                                     max_layers;
 };
 
 class pdsch_pdu_validator_hip : public srsran::pdsch_pdu_validator
@@ -4045,7 +4093,7 @@ inline std::unique_ptr<srsran::pusch_pdu_validator> pusch_processor_factory_hip:
   pc.ch_estimate_dimensions.nof_tx_layers = 1;
   pc.dec_nof_iterations                   = nof_iterations;
   pc.dec_enable_early_stop                = early_stop;
-  return std::make_unique<pusch_pdu_validator_hip>(srsran::create_pusch_processor_factory_sw(pc)->create_validator(), uci_dec_factory != nullptr);
+  return std::make_unique<pusch_pdu_validator_hip>(srsran::create_pusch_processor_factory_sw(pc)->create_validator(), uci_dec_factory != nullptr, max_layers);
 }
 
 inline std::unique_ptr<srsran::pdsch_pdu_validator> pdsch_processor_factory_hip::create_validator()

@@ -36,6 +36,91 @@ extern "C" int miphy_pusch_process_batch(miphy_ctx* ctx, const miphy_pusch_pdu* 
                                       stream);
 }
 
+// One codeword on 1..4 layers: the layered estimator, the layered demodulator and the decoder on one stream (include/miphy.h). Every rule is
+// checked before anything is enqueued; the stages check their own rules again on the jobs built here.
+extern "C" int miphy_pusch_process_layers_batch(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus, uint32_t n, const float* grid, int8_t* harq_softbits,
+                                                uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results,
+                                                float* scalars_out, void* stream)
+{
+  MIPHY_REQUIRE(ctx && pdus && grid && harq_softbits && harq_msgs && harq_crc_ok && tb_out && results && scalars_out,
+                "miphy_pusch_process_layers_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  hipStream_t                               s = (hipStream_t)stream;
+  std::vector<miphy_pusch_chest_job>        cj(n);
+  std::vector<miphy_pusch_demod_layers_job> dj(n);
+  std::vector<miphy_pusch_tb_desc>          tb(n);
+  size_t                                    ce_elems = 0, llr_bytes = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const miphy_pusch_pdu& p = pdus[i].base;
+    const unsigned         L = pdus[i].nof_tx_layers;
+    MIPHY_REQUIRE(p.nof_rx_ports >= 1 && p.nof_rx_ports <= 4, "pusch_process: PDU %u: invalid number of receive ports", i);
+    MIPHY_REQUIRE(L >= 1 && L <= 4, "pusch_process: PDU %u: invalid number of layers %u", i, L);
+    MIPHY_REQUIRE(L <= p.nof_rx_ports, "pusch_process: PDU %u: %u layers on %u receive ports", i, L, (unsigned)p.nof_rx_ports);
+    MIPHY_REQUIRE(p.numerology <= 4, "pusch_process: PDU %u: invalid numerology", i);
+    MIPHY_REQUIRE(p.nof_symbols >= 1 && p.start_symbol + p.nof_symbols <= 14, "pusch_process: PDU %u: invalid time allocation", i);
+    MIPHY_REQUIRE(p.grid_nof_prb >= 1 && p.grid_nof_prb <= 275, "pusch_process: PDU %u: invalid grid width", i);
+    unsigned nds = 0;
+    for (unsigned l = p.start_symbol; l < (unsigned)p.start_symbol + p.nof_symbols; ++l)
+      nds += (p.dmrs_symbols_mask >> l) & 1;
+    MIPHY_REQUIRE(nds >= 1 && nds <= 4, "pusch_process: PDU %u: %u DM-RS symbols in the allocation (1..4 supported)", i, nds);
+    MIPHY_REQUIRE(p.mod == 1 || p.mod == 2 || p.mod == 4 || p.mod == 6 || p.mod == 8, "pusch_process: PDU %u: invalid modulation", i);
+    // (the decoder's rules on the transport block, which it would only find behind the two stages in front of it)
+    MIPHY_REQUIRE((p.bg == 1 || p.bg == 2) && p.rv <= 3 && p.nof_ldpc_iterations > 0, "pusch_process: PDU %u: invalid base graph, redundancy version or iterations", i);
+    miphy_sch_segmentation sg = {};
+    MIPHY_REQUIRE(miphy_sch_segmentation_info(p.tb_bytes, p.bg, &sg) == MIPHY_OK, "pusch_process: PDU %u: transport block of %u bytes cannot be segmented", i, p.tb_bytes);
+    MIPHY_REQUIRE((sg.cb_info_bits % 8) == 0 || sg.nof_cbs == 1,
+                  "pusch_process: PDU %u: %u bytes is not a TS 38.214 transport block size (codeblock payloads are not byte aligned)", i, p.tb_bytes);
+    const uint32_t         nsc = p.grid_nof_prb * 12u;
+    miphy_pusch_chest_job& c   = cj[i];
+    c                          = {};
+    c.numerology = p.numerology, c.slot_in_frame = p.slot_in_frame, c.scrambling_id = p.dmrs_scrambling_id;
+    c.scaling = powf(10.0f, 3.0f / 20.0f); // two CDM groups without data -> +3 dB, as on one layer
+    c.n_scid = p.n_scid, c.nof_tx_layers = (uint8_t)L, c.nof_rx_ports = p.nof_rx_ports, c.first_symbol = p.start_symbol, c.nof_symbols = p.nof_symbols;
+    c.symbols_mask = p.dmrs_symbols_mask, c.grid_nof_prb = p.grid_nof_prb;
+    c.ce_compact   = 1;
+    miphy_pusch_demod_layers_job& lj = dj[i];
+    lj                               = {};
+    lj.nof_tx_layers                 = (uint8_t)L;
+    miphy_pusch_demod_job& d         = lj.base;
+    d.rnti = p.rnti, d.n_id = p.n_id, d.mod = p.mod, d.nof_rx_ports = p.nof_rx_ports, d.start_symbol = p.start_symbol, d.nof_symbols = p.nof_symbols;
+    d.dmrs_type = 1, d.nof_cdm_groups_without_data = 2, d.ce_nof_symbols = (uint8_t)(p.start_symbol + p.nof_symbols), d.ce_compact = 1;
+    d.dmrs_symbols_mask = p.dmrs_symbols_mask, d.grid_nof_prb = p.grid_nof_prb;
+    for (int k = 0; k < 4; ++k)
+      c.rx_ports[k] = p.rx_ports[k], d.rx_ports[k] = p.rx_ports[k];
+    for (int k = 0; k < 5; ++k)
+      c.rb_mask[k] = p.rb_mask[k], d.rb_mask[k] = p.rb_mask[k];
+    c.grid_offset = d.grid_offset = p.grid_offset;
+    c.ce_offset = d.ce_offset = ce_elems;
+    c.scalars_offset = d.scalars_offset = (uint64_t)i * 80; // [4 ports][4 layers][5] floats per PDU
+    d.llr_offset                       = llr_bytes;
+    d.nof_llr                          = miphy_pusch_demod_layers_nof_llr(&lj);
+    MIPHY_REQUIRE(d.nof_llr > 0, "pusch_process: PDU %u: empty allocation", i);
+    miphy_pusch_tb_desc& t = tb[i];
+    t                      = {};
+    t.bg = p.bg, t.rv = p.rv, t.mod = p.mod, t.nof_layers = (uint8_t)L, t.new_data = p.new_data, t.use_early_stop = p.use_early_stop;
+    t.nof_ldpc_iterations = p.nof_ldpc_iterations, t.Nref = p.Nref, t.nof_ch_symbols = d.nof_llr / p.mod, t.tb_bytes = p.tb_bytes;
+    t.harq_cb_index = p.harq_cb_index, t.tb_offset = p.tb_offset, t.llr_offset = llr_bytes;
+    ce_elems += (size_t)L * p.nof_rx_ports * nsc;
+    llr_bytes += (d.nof_llr + 15u) & ~15u;
+  }
+  // [channel estimates cf_t | codeword LLRs] in the processor's workspace; the estimator scalars go straight to the caller's array.
+  device_image img;
+  const auto   s_ce  = img.reserve<float>(ce_elems * 2, 256);
+  const auto   s_llr = img.reserve<int8_t>(llr_bytes, 256);
+  void*        work  = nullptr;
+  int          rc    = miphy_image_to_workspace(ctx, MIPHY_WS_PUSCH_PROC, img, s, &work);
+  if (rc)
+    return rc;
+  float*  d_ce  = s_ce.at(work);
+  int8_t* d_llr = s_llr.at(work);
+  if ((rc = miphy_dmrs_pusch_estimate_layers_batch(ctx, cj.data(), 0, n, grid, d_ce, scalars_out, s)))
+    return rc;
+  if ((rc = miphy_pusch_demodulate_layers_batch(ctx, dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, s)))
+    return rc;
+  return miphy_pusch_decode_batch(ctx, tb.data(), n, d_llr, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, s);
+}
+
 extern "C" int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pusch_uci* uci, uint32_t n, const float* grid,
                                             int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results,
                                             float* scalars_out, int8_t* uci_llr_out, float* evm_out, void* stream)

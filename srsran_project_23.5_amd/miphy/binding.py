@@ -142,6 +142,9 @@ def lib():
             l.miphy_pusch_demodulate_layers_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
             l.miphy_pusch_demod_layers_nof_llr.argtypes = [C.c_void_p]
             l.miphy_pusch_demod_layers_nof_llr.restype = C.c_uint32
+        if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_pusch_process_layers_batch"):  # (likewise)
+            l.miphy_dmrs_pusch_estimate_layers_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
+            l.miphy_pusch_process_layers_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 8
         l.miphy_polar_block_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("miphy_ofdm_demodulate_symbols", "miphy_ofdm_modulate_symbols"):
             getattr(l, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -397,6 +400,10 @@ PuschPdu = np.dtype([("numerology", np.uint32), ("slot_in_frame", np.uint32), ("
                      ("reserved0", np.uint8), ("nof_ldpc_iterations", np.uint16), ("dmrs_symbols_mask", np.uint16), ("grid_nof_prb", np.uint16),
                      ("pad", np.uint32), ("rb_mask", np.uint64, 5), ("grid_offset", np.uint64), ("tb_offset", np.uint64)], align=True)
 assert PuschPdu.itemsize == 112 and PuschPdu.fields["rb_mask"][1] == 56, PuschPdu.itemsize
+
+# Mirrors miphy_pusch_layers_pdu.
+PuschLayersPdu = np.dtype([("base", PuschPdu), ("nof_tx_layers", np.uint8), ("reserved", np.uint8, 7)], align=True)
+assert PuschLayersPdu.itemsize == 120 and PuschLayersPdu.fields["nof_tx_layers"][1] == 112, PuschLayersPdu.itemsize
 
 
 # Mirrors miphy_pusch_uci.
@@ -843,6 +850,13 @@ class Context:
             on_dev |= (int(max_ports) << 8) | (int(max_layers) << 12)
         check(lib().miphy_dmrs_pusch_estimate_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _stream_ptr(stream)))
 
+    def dmrs_pusch_estimate_layers_batch(self, jobs, grid, ce, scalars, stream=None, max_ports=0, max_layers=0):
+        """The estimator that separates the layers of a CDM group (PUSCH on 1..4 layers): jobs, outputs and hints as dmrs_pusch_estimate_batch."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschChestJob)
+        if on_dev:
+            on_dev |= (int(max_ports) << 8) | (int(max_layers) << 12)
+        check(lib().miphy_dmrs_pusch_estimate_layers_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _stream_ptr(stream)))
+
     def port_channel_estimate_batch(self, jobs, grid, pilots, ce, scalars, stream=None):
         """port_channel_estimator::compute: pilots given by the caller (device complex64), optional intra-slot hopping."""
         jobs, n, ptr, on_dev = self._descs(jobs, PuschChestJob)
@@ -914,6 +928,14 @@ class Context:
         pdus = np.ascontiguousarray(pdus)
         check(lib().miphy_pusch_process_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, _dptr(grid), _dptr(harq_softbits), _dptr(harq_msgs),
                                               _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars), _stream_ptr(stream)))
+
+    def pusch_process_layers_batch(self, pdus, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, stream=None):
+        """One codeword on 1..4 layers. pdus: numpy PuschLayersPdu array (host); results as pusch_process_batch; scalars: float32 n x 80,
+        [rx port][layer][5] of PDU i at 80 i + 5 (port * nof_tx_layers + layer)."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PuschLayersPdu
+        pdus = np.ascontiguousarray(pdus)
+        check(lib().miphy_pusch_process_layers_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, _dptr(grid), _dptr(harq_softbits), _dptr(harq_msgs),
+                                                     _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars), _stream_ptr(stream)))
 
     def pusch_process_batch_ex(self, pdus, uci, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, uci_llr, evm, stream=None):
         """PDUs with multiplexed UCI (uci: numpy PuschUci array or None) and the EVM (evm: float32 device tensor of n or None)."""
