@@ -434,9 +434,20 @@ int miphy_pusch_demodulate_batch(miphy_ctx* ctx, const miphy_pusch_demod_job* jo
  *   output:   data element i (ranked symbol-major, subcarrier ascending, as on one layer), layer ly, bit b at
  *             llr_offset + (L i + ly) mod + b, descrambled with c((L i + ly) mod + b), c_init = rnti * 2^15 + n_id; pi/2-BPSK rotates
  *             with the parity of L i + ly
- * base.nof_llr must equal miphy_pusch_demod_layers_nof_llr(); UCI placeholders and EVM are not available (base.nof_placeholders = 0,
- * evm_offset ignored). A batch may mix layer counts; a job on one layer writes the bytes of miphy_pusch_demodulate_batch. A host job that
- * breaks a rule is MIPHY_EINVAL with nothing enqueued, a device-resident one is skipped. */
+ * base.nof_llr must equal miphy_pusch_demod_layers_nof_llr(). A batch may mix layer counts; a job on one layer writes the bytes of
+ * miphy_pusch_demodulate_batch. A host job that breaks a rule is MIPHY_EINVAL with nothing enqueued, a device-resident one is skipped.
+ * miphy_pusch_demodulate_layers_batch takes no UCI placeholders and reports no EVM (base.nof_placeholders = 0, evm_offset ignored); _ex does:
+ *   placeholders: as on one layer, the list of a job (base.placeholders_offset, base.nof_placeholders) holds resource element indices in
+ *             codeword order, ascending, as miphy_ulsch_placeholders(nof_layers = L) returns them. Listed element i carries the pattern
+ *             [c0 y x ..] in each of its L codeword symbols L i + ly: there bit 0 is descrambled with its own chip c((L i + ly) mod), bit 1
+ *             with that same chip, the others not at all (TS 38.211 6.3.1.1, TS 38.212 6.3.2). nof_placeholders != 0 needs the list and
+ *             mod >= 2.
+ *   EVM:      evm_sums[base.evm_offset + sy], sy = 0..13, receives the sum over the data elements of OFDM symbol sy and their L layers of
+ *             |hard-decided symbol - equalised symbol|^2, the hard decision taken on the soft bits before descrambling, the pi/2-BPSK
+ *             rotation by the parity of L i + ly; 0 for a symbol without data. EVM = sqrt(sum over symbols / (data REs x L)). The order of
+ *             the additions is fixed, so two runs give the same bits, whatever the size of the batch.
+ * The LLRs of a job do not depend on whether EVM is asked for; without placeholders they are those of the plain entry point. A job on one layer
+ * gives the LLRs and the sums of miphy_pusch_demodulate_batch_ex. */
 typedef struct {
   miphy_pusch_demod_job base;
   uint8_t               nof_tx_layers; /* 1..4, <= base.nof_rx_ports */
@@ -447,6 +458,9 @@ uint32_t miphy_pusch_demod_layers_nof_llr(const miphy_pusch_demod_layers_job* jo
 int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n,
                                         const float* grid /* device cf_t */, const float* ce /* device cf_t */, const float* scalars /* device */,
                                         int8_t* llr_out /* device */, void* stream);
+int miphy_pusch_demodulate_layers_batch_ex(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                           const float* ce, const float* scalars, int8_t* llr_out, const uint16_t* placeholders /* device, may be NULL */,
+                                           float* evm_sums /* device, may be NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Channel equalizer on its own --  replaces srsran::channel_equalizer::equalize of the zero-forcing equalizer
@@ -916,10 +930,16 @@ int miphy_pusch_process_batch(miphy_ctx* ctx, const miphy_pusch_pdu* pdus /* hos
 /* PUSCH processor for one codeword on 1..4 transmit layers  --  beyond the 23.5 reference (pusch_processor_impl.cpp asserts one layer). One
  * call chains, on one stream, miphy_dmrs_pusch_estimate_layers_batch (compact estimate), miphy_pusch_demodulate_layers_batch and
  * miphy_pusch_decode_batch (nof_layers = nof_tx_layers); estimates and LLRs stay in a workspace of the context. DM-RS type 1, single-symbol
- * DM-RS, two CDM groups without data; no UCI and no EVM (the layered demodulator has neither), hence no _ex form. A batch may mix layer
+ * DM-RS, two CDM groups without data. A batch may mix layer
  * counts; a PDU on one layer gives the bytes of miphy_pusch_process_batch for its base record (transport block, result, first 20 scalars).
  * scalars_out: per PDU 80 floats, [rx port][layer][5] at 5 * (port * nof_tx_layers + layer) as the estimator writes them. A PDU that breaks
- * a rule is MIPHY_EINVAL with nothing enqueued. */
+ * a rule is MIPHY_EINVAL with nothing enqueued.
+ * _ex: with multiplexed UCI and the EVM, as miphy_pusch_process_batch_ex: miphy_pusch_demodulate_layers_batch_ex in the middle, the EVM of a PDU
+ * is sqrt(sum of its 14 sums / (data REs x nof_tx_layers)), miphy_ulsch_demultiplex_batch with nof_layers = nof_tx_layers in front of the
+ * decoder. PDUs without codeword are demodulated and demultiplexed only, their result record is zero; one with neither codeword nor UCI is
+ * refused. A PDU on one layer gives the bytes of miphy_pusch_process_batch_ex (UCI soft bits and EVM included). miphy_pusch_uci_jobs and
+ * miphy_pusch_uci_field_jobs read only `mod` of a PDU record: pass them the `base` records (contiguous) to decode the fields behind this call.
+ * Still out above one layer: the slot batch of the uplink processor, a prepared plan, double-symbol DM-RS, DM-RS type 2, frequency hopping. */
 typedef struct {
   miphy_pusch_pdu base;
   uint8_t         nof_tx_layers; /* 1..4, <= base.nof_rx_ports */
@@ -928,6 +948,10 @@ typedef struct {
 int miphy_pusch_process_layers_batch(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus /* host */, uint32_t n, const float* grid /* device cf_t */,
                                      int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out /* device */,
                                      miphy_pusch_result* results /* device, n */, float* scalars_out /* device, n x 80 */, void* stream);
+int miphy_pusch_process_layers_batch_ex(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus /* host */, const miphy_pusch_uci* uci /* host or NULL */,
+                                        uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
+                                        miphy_pusch_result* results, float* scalars_out /* n x 80 */, int8_t* uci_llr_out,
+                                        float* evm_out /* device, n, may be NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * UL-SCH demultiplexer  --  replaces srsran::ulsch_demultiplex::demultiplex / get_placeholders (UCI multiplexed on PUSCH)

@@ -1656,15 +1656,15 @@ inline std::shared_ptr<srsran::ofdm_prach_demodulator_factory> create_ofdm_prach
 
 // ---------------------------------------------------------------------------------------------------------------- PUSCH processor
 /// srsran::pusch_processor over miphy_pusch_process_batch (pusch_processor.h:158-162): estimation, demodulation and decoding in one
-/// device pass for PDUs that carry a codeword and no UCI; the resource grid goes to the device once, the transport block, the
-/// HARQ buffer of the rx_softbuffer and the channel state information come back.
+/// device pass, with the UCI multiplexed on the PUSCH demultiplexed and decoded behind it; the resource grid goes to the device once, the
+/// transport block, the HARQ buffer of the rx_softbuffer, the UCI fields and the channel state information come back.
 class pusch_processor_hip : public srsran::pusch_processor
 {
 public:
   /// \c uci_dec: uci_decoder_hip (the fields are decoded on the device behind the demultiplexer) or the reference's CPU UCI decoder
   /// (the soft bits come back and are decoded on the host); without it PDUs with multiplexed UCI are refused. \c enable_evm as in create_pusch_demodulator_factory_sw.
-  /// \c max_layers: 1 (the reference's limit) to 4; a PDU on two to four layers goes through miphy_pusch_process_layers_batch, which has
-  /// neither UCI nor EVM.
+  /// \c max_layers: 1 (the reference's limit) to 4; a PDU on two to four layers goes through miphy_pusch_process_layers_batch_ex, with UCI
+  /// and EVM as on one layer.
   pusch_processor_hip(std::shared_ptr<context> c, unsigned nof_iterations, bool early_stop, std::unique_ptr<srsran::uci_decoder> uci_dec_ = nullptr,
                       bool enable_evm_ = false, unsigned max_layers_ = 1) :
     c(std::move(c)), dec_nof_iterations(nof_iterations), dec_enable_early_stop(early_stop), uci_dec(std::move(uci_dec_)), enable_evm(enable_evm_),
@@ -1683,8 +1683,7 @@ public:
     const unsigned nl = pdu.nof_tx_layers;
     require(pdu.dmrs == srsran::dmrs_type::TYPE1 && pdu.nof_cdm_groups_without_data == 2 && nl >= 1 && nl <= max_layers,
             "Only DM-RS type 1, two CDM groups without data and one layer (up to max_layers with the layered path) are supported.");
-    require(nl == 1 || (!has_uci && !enable_evm && pdu.codeword.has_value() && nl <= pdu.rx_ports.size()),
-            "pusch_processor_hip: two to four layers need a codeword, at least as many receive ports, no UCI and no EVM.");
+    require(nl <= pdu.rx_ports.size(), "pusch_processor_hip: the layers need at least as many receive ports.");
     const srsran::bounded_bitset<srsran::MAX_RB> rb_mask = pdu.freq_alloc.get_prb_mask(pdu.bwp_start_rb, pdu.bwp_size_rb);
     const unsigned nprb = rb_mask.size(), nsc = nprb * 12, nports = pdu.rx_ports.size();
     miphy_pusch_layers_pdu lp = {};
@@ -1772,7 +1771,9 @@ public:
     c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
     c->h2d(d_tb, data.data(), data.size());
     if (nl > 1) {
-      context::check(miphy_pusch_process_layers_batch(c->ctx, &lp, 1, d_g, d_soft, d_msg, d_crc, d_tb, d_res, d_sc, c->stream), "pusch_process_layers");
+      context::check(miphy_pusch_process_layers_batch_ex(
+                         c->ctx, &lp, &u, 1, d_g, d_soft, d_msg, d_crc, d_tb, d_res, d_sc, d_uci, enable_evm ? d_evm : nullptr, c->stream),
+                     "pusch_process_layers");
     } else {
       context::check(
           miphy_pusch_process_batch_ex(c->ctx, &p, &u, 1, d_g, d_soft, d_msg, d_crc, d_tb, d_res, d_sc, d_uci, enable_evm ? d_evm : nullptr, c->stream),
@@ -3975,12 +3976,11 @@ public:
   {
     if (pdu.nof_tx_layers > 1) {
       // Beyond the reference, whose validator stops at one layer (pusch_processor_impl.cpp:40-42): its other rules (DM-RS type 1, two CDM groups
-      // without data among them) on a copy on one layer; one codeword on at most max_layers layers, on at least as many ports, no UCI.
+      // without data among them, a codeword or UCI, UCI only with a UCI decoder behind the processor, the long fields) on a copy on one layer; at
+      // most max_layers layers, on at least as many ports.
       srsran::pusch_processor::pdu_t one = pdu;
       one.nof_tx_layers                  = 1;
-      const bool has_uci                 = pdu.uci.nof_harq_ack != 0 || pdu.uci.nof_csi_part1 != 0 || pdu.uci.nof_csi_part2 != 0;
-      return pdu.nof_tx_layers <= max_layers && pdu.nof_tx_layers <= 4 && pdu.nof_tx_layers <= pdu.rx_ports.size() && !has_uci && pdu.codeword.has_value() &&
-             is_valid(one);
+      return pdu.nof_tx_layers <= max_layers && pdu.nof_tx_layers <= 4 && pdu.nof_tx_layers <= pdu.rx_ports.size() && is_valid(one);
     }
     // The reference's validator (pusch_processor_impl.cpp:54-58) refuses HARQ-ACK and CSI part 1 above 11 bits because its UCI decoder
     // does. With the device UCI decoder behind the processor those fields may have up to 1706 bits (polar coded): the reference's

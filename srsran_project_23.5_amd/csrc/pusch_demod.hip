@@ -702,13 +702,9 @@ __global__ void __launch_bounds__(DEMOD_THREADS, DEMOD_MIN_WAVES) pusch_demod_ke
 }
 
 // Per-symbol EVM sums of a transmission from the per-chunk partials, chunks added in order (deterministic); symbols without data: 0.
-__global__ void __launch_bounds__(64) pusch_evm_reduce_kernel(const miphy_pusch_demod_job* __restrict__ jobs, const float* __restrict__ evm_part,
-                                                              float* __restrict__ evm_sums)
+// part: the transmission's [14][DEMOD_MAX_CHUNKS] partials.
+__device__ __forceinline__ void evm_reduce_symbol(const miphy_pusch_demod_job* __restrict__ jp, const float* __restrict__ part, float* __restrict__ evm_sums, int sy)
 {
-  const miphy_pusch_demod_job* __restrict__ jp = jobs + blockIdx.x;
-  const int sy = threadIdx.x;
-  if (sy >= 14)
-    return;
   int nprb = 0;
   for (int w = 0; w < 5; ++w) {
     const int left = (int)jp->grid_nof_prb - 64 * w;
@@ -720,11 +716,17 @@ __global__ void __launch_bounds__(64) pusch_evm_reduce_kernel(const miphy_pusch_
   float          s     = 0.f;
   if (sy >= jp->start_symbol && sy < jp->start_symbol + jp->nof_symbols && npp != 0) {
     const int    nch = (nprb * 12 + DEMOD_THREADS - 1) / DEMOD_THREADS;
-    const float* p   = evm_part + ((size_t)blockIdx.x * 14 + sy) * DEMOD_MAX_CHUNKS;
+    const float* p   = part + (size_t)sy * DEMOD_MAX_CHUNKS;
     for (int c = 0; c < nch; ++c)
       s += p[c];
   }
   evm_sums[jp->evm_offset + sy] = s;
+}
+__global__ void __launch_bounds__(64) pusch_evm_reduce_kernel(const miphy_pusch_demod_job* __restrict__ jobs, const float* __restrict__ evm_part,
+                                                              float* __restrict__ evm_sums)
+{
+  if (threadIdx.x < 14)
+    evm_reduce_symbol(jobs + blockIdx.x, evm_part + (size_t)blockIdx.x * 14 * DEMOD_MAX_CHUNKS, evm_sums, threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------ one codeword on 1..4 transmit layers
@@ -755,6 +757,7 @@ __host__ __device__ __forceinline__ unsigned pusch_demod_count_re(const miphy_pu
 
 // What a layered job (j = its base, L = its layers) must satisfy, once, evaluated in this order: R(condition, message of the host, its arguments).
 // The kernels skip a device-resident job that breaks a rule (pusch_demod_layers_job_ok), the host refuses one with the rule's message.
+// have_ph: the call came with a placeholder list (never through miphy_pusch_demodulate_layers_batch); ex: the host's entry point is the _ex one.
 #define PUSCH_DEMOD_LAYERS_RULES(R)                                                                                                                    \
   R(L >= 1 && L <= 4, "invalid number of transmit layers %u", L)                                                                                      \
   R(j.nof_rx_ports >= 1 && j.nof_rx_ports <= 4, "invalid number of receive ports")                                                                    \
@@ -767,11 +770,12 @@ __host__ __device__ __forceinline__ unsigned pusch_demod_count_re(const miphy_pu
   R(j.grid_nof_prb >= 1 && j.grid_nof_prb <= 275, "invalid grid width")                                                                               \
   R(j.n_id < 1024, "invalid scrambling identifier")                                                                                                   \
   R(j.rnti < 65536, "invalid RNTI")                                                                                                                   \
-  R(j.nof_placeholders == 0, "UCI placeholders are not supported on this entry point")                                                                \
+  R(j.nof_placeholders == 0 || (have_ph && j.mod >= 2), "%s",                                                                                         \
+    ex ? "placeholders need the list and a modulation order of at least 2" : "UCI placeholders are not supported on this entry point")                \
   R(j.nof_llr == pusch_demod_count_re(j) * L * j.mod, "%u LLRs requested, the allocation holds %u on %u layers", j.nof_llr,                           \
     pusch_demod_count_re(j) * L * j.mod, L)
 
-__host__ __device__ __forceinline__ bool pusch_demod_layers_job_ok(const miphy_pusch_demod_layers_job& lj)
+__host__ __device__ __forceinline__ bool pusch_demod_layers_job_ok(const miphy_pusch_demod_layers_job& lj, bool have_ph)
 {
   const miphy_pusch_demod_job& j = lj.base;
   const unsigned               L = lj.nof_tx_layers;
@@ -780,17 +784,25 @@ __host__ __device__ __forceinline__ bool pusch_demod_layers_job_ok(const miphy_p
 #undef PUSCH_RULE_HOLDS
 }
 
+// pusch_evm_reduce_kernel for layered jobs; a job the demodulator skipped keeps its 14 floats.
+__global__ void __launch_bounds__(64) pusch_evm_reduce_layers_kernel(const miphy_pusch_demod_layers_job* __restrict__ jobs, const float* __restrict__ evm_part,
+                                                                     float* __restrict__ evm_sums, bool have_ph)
+{
+  if (threadIdx.x < 14 && pusch_demod_layers_job_ok(jobs[blockIdx.x], have_ph))
+    evm_reduce_symbol(&jobs[blockIdx.x].base, evm_part + (size_t)blockIdx.x * 14 * DEMOD_MAX_CHUNKS, evm_sums, threadIdx.x);
+}
+
 // Scrambling sequence of a layered transmission: up to four times the x1 table and one workgroup's LDS. A sequence that fits both is made whole by
 // workgroup (transmission, 0) as pusch_scrambling_kernel makes it (x1 from the table, x2 from the basis and the doubling recurrence); a longer one in
 // pieces of SEQ_PIECE words, workgroup (transmission, piece) jumping both shift registers to the piece's first bit (gold_piece).
 // seq: [transmission][stride] words.
 constexpr int SEQ_PIECE = SEQ_STRIDE / 2;
 __global__ void __launch_bounds__(SCR_THREADS) pusch_seq_layers_kernel(const miphy_pusch_demod_layers_job* __restrict__ jobs, const gold_tables* __restrict__ gt,
-                                                               uint32_t* __restrict__ seq, uint32_t stride)
+                                                               uint32_t* __restrict__ seq, uint32_t stride, bool have_ph)
 {
   __shared__ uint32_t w[SEQ_STRIDE]; // one sequence, or w1 | w2 of a piece
   const miphy_pusch_demod_layers_job* __restrict__ lj = jobs + blockIdx.x;
-  if (!pusch_demod_layers_job_ok(*lj)) // uniform
+  if (!pusch_demod_layers_job_ok(*lj, have_ph)) // uniform
     return;
   const int      tid = threadIdx.x, nt = blockDim.x;
   const int      nwords = min((int)((lj->base.nof_llr + 31u) >> 5) + 2, (int)stride); // + the 64-bit window of the last resource element
@@ -808,6 +820,30 @@ __global__ void __launch_bounds__(SCR_THREADS) pusch_seq_layers_kernel(const mip
   if (first >= nwords)
     return;
   gold_piece(*gt, c_init, first, min(SEQ_PIECE, nwords - first), w, w + SEQ_PIECE, o + first, tid, nt);
+}
+
+// MOD soft bits packed in w (LLR b in byte b) to q: one wide store where q is aligned to it, bytes otherwise.
+template <int MOD>
+__device__ __forceinline__ void demod_store(uint64_t w, int8_t* q)
+{
+  constexpr unsigned WIDTH = MOD == 8 ? 8 : MOD == 4 ? 4 : MOD == 1 ? 1 : 2;
+  if (((uintptr_t)q % WIDTH) == 0) {
+    if (MOD == 8)
+      *reinterpret_cast<uint2*>(q) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+    else if (MOD == 6) {
+      uint16_t* q2 = reinterpret_cast<uint16_t*>(q);
+      q2[0] = (uint16_t)w, q2[1] = (uint16_t)(w >> 16), q2[2] = (uint16_t)(w >> 32);
+    } else if (MOD == 4)
+      *reinterpret_cast<uint32_t*>(q) = (uint32_t)w;
+    else if (MOD == 2)
+      *reinterpret_cast<uint16_t*>(q) = (uint16_t)w;
+    else
+      q[0] = (int8_t)w;
+  } else {
+#pragma unroll
+    for (int b = 0; b < MOD; ++b)
+      q[b] = (int8_t)(w >> (8 * b));
+  }
 }
 
 // MOD soft bits of one equalised symbol, descrambled with the low MOD bits of `bits`, to q: the packed demapper where no NaN can appear, the exact
@@ -838,23 +874,122 @@ __device__ __forceinline__ void demod_emit(float re, float im, float nvar, unsig
       w |= (uint64_t)(uint8_t)(int8_t)((l[b] ^ m) - m) << (8 * b);
     }
   }
-  constexpr unsigned WIDTH = MOD == 8 ? 8 : MOD == 4 ? 4 : MOD == 1 ? 1 : 2;
-  if (((uintptr_t)q % WIDTH) == 0) {
-    if (MOD == 8)
-      *reinterpret_cast<uint2*>(q) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-    else if (MOD == 6) {
-      uint16_t* q2 = reinterpret_cast<uint16_t*>(q);
-      q2[0] = (uint16_t)w, q2[1] = (uint16_t)(w >> 16), q2[2] = (uint16_t)(w >> 32);
-    } else if (MOD == 4)
-      *reinterpret_cast<uint32_t*>(q) = (uint32_t)w;
-    else if (MOD == 2)
-      *reinterpret_cast<uint16_t*>(q) = (uint16_t)w;
-    else
-      q[0] = (int8_t)w;
-  } else {
+  demod_store<MOD>(w, q);
+}
+
+// The variant of demod_emit behind UCI placeholders and the EVM: always the exact sequence, whose soft bits l[] the EVM needs before they are
+// descrambled (as demod_columns does for such jobs; the bytes are those of demod_emit). placeholder: the symbol holds [c0 y x ..], bit 1 takes the
+// chip of bit 0 and the bits behind it none. Returns |hard-decided symbol - equalised symbol|^2 (evm_calculator_generic_impl.cpp:31-47).
+template <int MOD>
+__device__ __forceinline__ float demod_emit_exact(float re, float im, float nvar, unsigned sym_idx, uint32_t bits, bool placeholder, const float2* tab, int8_t* q)
+{
+#pragma clang fp contract(off)
+  const float rcp_chk = (nvar > 0.f) ? 1.0f / nvar : 0.0f;
+  const bool  fast    = fabsf(re) < INFINITY && fabsf(im) < INFINITY && rcp_chk < INFINITY;
+  int         l[8]    = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (fast)
+    demod_symbol<MOD, true>(re, im, nvar, sym_idx, tab, l);
+  else
+    demod_symbol<MOD, false>(re, im, nvar, sym_idx, tab, l);
+  uint32_t hb = 0;
 #pragma unroll
-    for (int b = 0; b < MOD; ++b)
-      q[b] = (int8_t)(w >> (8 * b));
+  for (int b = 0; b < MOD; ++b)
+    hb |= (uint32_t)(l[b] <= 0) << b;
+  const float2 id = map_symbol(MOD, hb, sym_idx);
+  const float  er = id.x - re, ei = id.y - im;
+  if (placeholder)
+    bits = (bits & 1u) ? 3u : 0u;
+  uint64_t w = 0;
+#pragma unroll
+  for (int b = 0; b < MOD; ++b) {
+    const int m = -(int)((bits >> b) & 1u); // 0 / -1
+    w |= (uint64_t)(uint8_t)(int8_t)((l[b] ^ m) - m) << (8 * b);
+  }
+  demod_store<MOD>(w, q);
+  return er * er + ei * ei;
+}
+
+// The variant of demod_layers_columns (below) for a batch with placeholders or EVM. The list is searched once per element: a listed element carries
+// the pattern in each of its L codeword symbols. EVM: the terms of an element's layers are added in layer order, then the wavefront shuffle tree,
+// the four wavefronts in sequence and (pusch_evm_reduce_layers_kernel) the chunks in order, as demod_columns does, so a symbol's sum has one value.
+template <int MOD, int L>
+__device__ __forceinline__ void demod_layers_columns_ex(const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab, float* evm_red, int tid)
+{
+#pragma clang fp contract(off)
+  const int  nsc = a.nsc, np = a.nports;
+  const bool compact = a.ce_nof_symbols == 1;
+  float2     h[L][4];
+#pragma unroll
+  for (int l = 0; l < L; ++l)
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      h[l][p] = make_float2(0.f, 0.f);
+  auto load_h = [&](int row) { // estimate [layer][rx port][ce_nof_symbols][nsc]
+#pragma unroll
+    for (int l = 0; l < L; ++l)
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        if (p < np)
+          h[l][p] = a.ce[((size_t)(l * np + p) * a.ce_nof_symbols + row) * nsc + sc];
+  };
+  zf_prepared<L> q;
+  if (active && compact) {
+    load_h(0);
+    zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
+  }
+  int prefix = a.prefix0; // data elements per layer of the transmission before the current symbol
+  for (int sy = a.start_symbol; sy < a.end_symbol; ++sy) { // (uniform: every thread of the workgroup reaches the barriers)
+    const bool is_dmrs = (a.dmrs_syms >> sy) & 1;
+    const int  npp     = is_dmrs ? a.per_dm : 12;
+    const int  r       = is_dmrs ? (a.per_dm ? r_dm : -1) : a_idx;
+    float      evm_acc = 0.f;
+    if (active && r >= 0) {
+      float2 y[4], x[L];
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        y[p] = (p < np) ? a.grid[((size_t)((a.rxp >> (8 * p)) & 0xffu) * 14 + sy) * nsc + sc] : make_float2(0.f, 0.f);
+      if (!compact) {
+        load_h(sy);
+        zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
+      }
+      zf_apply<L>(h, np, y, q, x);
+      const unsigned el   = (unsigned)(prefix + r);  // the element's index in the codeword, what the placeholder list holds
+      const uint32_t e0   = el * (uint32_t)L;        // first of the element's L codeword symbols
+      const uint32_t bo   = e0 * (uint32_t)MOD;
+      const uint64_t two  = (uint64_t)a.seq[bo >> 5] | ((uint64_t)a.seq[(bo >> 5) + 1] << 32);
+      const uint32_t bits = (uint32_t)(two >> (bo & 31u));
+      int8_t*        q0   = a.llr + (size_t)bo;
+      bool           found = false;
+      for (int lo = 0, hi = a.nph - 1; lo <= hi;) { // binary search, as demod_columns
+        const int      mid = (lo + hi) >> 1;
+        const unsigned v   = a.ph[mid];
+        if (v == el) {
+          found = true;
+          break;
+        }
+        if (v < el)
+          lo = mid + 1;
+        else
+          hi = mid - 1;
+      }
+#pragma unroll
+      for (int l = 0; l < L; ++l) {
+        const float t = demod_emit_exact<MOD>(x[l].x, x[l].y, q.nvar[l], e0 + l, bits >> (l * MOD), found, tab, q0 + l * MOD);
+        evm_acc       = l ? evm_acc + t : t;
+      }
+    }
+    if (a.evm_part && npp != 0) { // uniform
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1)
+        evm_acc += __shfl_xor(evm_acc, off);
+      __syncthreads();
+      if ((tid & 63) == 0)
+        evm_red[tid >> 6] = evm_acc;
+      __syncthreads();
+      if (tid == 0)
+        a.evm_part[sy * DEMOD_MAX_CHUNKS + blockIdx.y] = ((evm_red[0] + evm_red[1]) + evm_red[2]) + evm_red[3];
+    }
+    prefix += a.nprb * npp;
   }
 }
 
@@ -915,13 +1050,28 @@ __device__ __forceinline__ void demod_layers_columns(const demod_args& a, bool a
   }
 }
 
-// ONE_LAYER: the one-layer walk itself (demod_columns), the bytes of miphy_pusch_demodulate_batch; otherwise L = 2..4.
-template <int MOD, bool ONE_LAYER>
+// ONE_LAYER: the one-layer walk itself (demod_columns), the bytes of miphy_pusch_demodulate_batch(_ex); otherwise L = 2..4, EX: with placeholders
+// and EVM.
+template <int MOD, bool ONE_LAYER, bool EX>
 __device__ __forceinline__ void demod_layers_dispatch(int L, const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab,
                                                       float* evm_red, int tid)
 {
   if constexpr (ONE_LAYER) {
     demod_columns<MOD>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+    return;
+  }
+  if constexpr (EX) {
+    switch (L) { // uniform
+      case 2:
+        demod_layers_columns_ex<MOD, 2>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+        break;
+      case 3:
+        demod_layers_columns_ex<MOD, 3>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+        break;
+      default:
+        demod_layers_columns_ex<MOD, 4>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+        break;
+    }
     return;
   }
   switch (L) { // uniform
@@ -940,10 +1090,13 @@ __device__ __forceinline__ void demod_layers_dispatch(int L, const demod_args& a
 // grid (transmissions, chunks of 256 allocated subcarriers, parts of the OFDM symbols), as pusch_demod_kernel. seq: [transmission][stride] words.
 // Two kernels share a batch: ONE_LAYER takes its jobs on one layer, with the registers and the occupancy of pusch_demod_kernel, the other those on
 // two to four layers (four 4 x 4 matrices in registers); a workgroup leaves at once when the job belongs to the other kernel.
-template <bool ONE_LAYER>
+// EX: the instances of a call with a placeholder list or EVM sums (miphy_pusch_demodulate_layers_batch_ex), which take the exact demapper; the
+// other two never see `placeholders` and `evm_part`, so the throughput path keeps its registers. evm_part: [transmission][14][DEMOD_MAX_CHUNKS].
+template <bool ONE_LAYER, bool EX>
 __global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1) pusch_demod_layers_kernel(const miphy_pusch_demod_layers_job* __restrict__ jobs, const float2* __restrict__ grid,
                                                                             const float2* __restrict__ ce, const float* __restrict__ scalars,
-                                                                            int8_t* __restrict__ llr, const uint32_t* __restrict__ seq, uint32_t stride)
+                                                                            int8_t* __restrict__ llr, const uint32_t* __restrict__ seq, uint32_t stride,
+                                                                            const uint16_t* __restrict__ placeholders, float* __restrict__ evm_part)
 {
   __shared__ uint16_t prb_of[276];
   __shared__ int      nprb_s;
@@ -953,7 +1106,7 @@ __global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1
   const int L = jobs[blockIdx.x].nof_tx_layers;
   if ((L == 1) != ONE_LAYER) // uniform
     return;
-  if (!pusch_demod_layers_job_ok(jobs[blockIdx.x])) // uniform: a device-resident job the host has not seen is skipped
+  if (!pusch_demod_layers_job_ok(jobs[blockIdx.x], EX && placeholders)) // uniform: a device-resident job the host has not seen is skipped
     return;
   const demod_job_words j   = demod_load_job(&jobs[blockIdx.x].base);
   const int             tid = threadIdx.x;
@@ -992,6 +1145,11 @@ __global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1
   a.nph            = 0;
   a.ph             = nullptr;
   a.evm_part       = nullptr;
+  if constexpr (EX) {
+    a.nph      = placeholders ? (int)j.nof_placeholders() : 0;
+    a.ph       = placeholders ? placeholders + j.placeholders_offset() : nullptr;
+    a.evm_part = evm_part ? evm_part + (size_t)blockIdx.x * 14 * DEMOD_MAX_CHUNKS : nullptr;
+  }
   a.seq            = seq + (size_t)blockIdx.x * stride;
   const int  a_idx  = (int)blockIdx.y * DEMOD_THREADS + tid;
   const bool active = a_idx < nprb * 12;
@@ -1001,19 +1159,19 @@ __global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1
   __syncthreads(); // interval tables in LDS
   switch (j.mod()) {
     case 8:
-      demod_layers_dispatch<8, ONE_LAYER>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_layers_dispatch<8, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
       break;
     case 6:
-      demod_layers_dispatch<6, ONE_LAYER>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_layers_dispatch<6, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
       break;
     case 4:
-      demod_layers_dispatch<4, ONE_LAYER>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_layers_dispatch<4, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
       break;
     case 2:
-      demod_layers_dispatch<2, ONE_LAYER>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_layers_dispatch<2, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
       break;
     default:
-      demod_layers_dispatch<1, ONE_LAYER>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_layers_dispatch<1, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
       break;
   }
 }
@@ -1027,8 +1185,10 @@ extern "C" uint32_t miphy_pusch_demod_layers_nof_llr(const miphy_pusch_demod_lay
   return miphy_pusch_demod_nof_llr(&lj->base) * lj->nof_tx_layers;
 }
 
-extern "C" int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
-                                                   const float* ce, const float* scalars, int8_t* llr, void* stream)
+// Both entry points. ex: miphy_pusch_demodulate_layers_batch_ex (only the message of the placeholder rule depends on it). The EX kernels run when the
+// call has EVM sums or a job with placeholders; device-resident jobs cannot be looked at, there the two pointers decide.
+static int pusch_demodulate_layers(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n, const float* grid, const float* ce,
+                                   const float* scalars, int8_t* llr, const uint16_t* placeholders, float* evm_sums, bool ex, void* stream)
 {
   MIPHY_REQUIRE(ctx && jobs && grid && ce && scalars && llr, "miphy_pusch_demodulate_layers_batch: null argument");
   if (n == 0)
@@ -1036,9 +1196,12 @@ extern "C" int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_p
   MIPHY_REQUIRE(n <= 65535, "pusch_demodulate_layers: batch too large (max 65535 transmissions per call)");
   uint32_t max_chunks = DEMOD_MAX_CHUNKS, max_layers = 4, max_words = 4 * SEQ_STRIDE; // device-resident jobs: the widest grid on four layers
   bool     one_layer = true, more_layers = true;                                      // ... and both kernels
+  const bool have_ph = placeholders != nullptr;
+  bool       extras  = have_ph || evm_sums;
   if (!jobs_on_device) {
     uint32_t max_prb = 1, max_llr = 0;
     max_layers = 1, one_layer = more_layers = false;
+    extras     = evm_sums != nullptr;
     for (uint32_t i = 0; i < n; ++i) {
       const miphy_pusch_demod_job& j = jobs[i].base;
       const unsigned               L = jobs[i].nof_tx_layers;
@@ -1052,6 +1215,7 @@ extern "C" int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_p
       max_layers = L > max_layers ? L : max_layers;
       one_layer |= L == 1, more_layers |= L > 1;
       max_llr    = j.nof_llr > max_llr ? j.nof_llr : max_llr;
+      extras |= j.nof_placeholders != 0;
     }
     max_chunks = (max_prb * 12 + DEMOD_THREADS - 1) / DEMOD_THREADS;
     max_words  = ((max_llr + 31u) >> 5) + 2;
@@ -1067,21 +1231,42 @@ extern "C" int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_p
     return rc;
   const uint32_t stride = max_layers * (uint32_t)SEQ_STRIDE;
   void*          work   = nullptr;
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, (size_t)n * stride * sizeof(uint32_t), &work)))
+  const size_t   seq_bytes = (size_t)n * stride * sizeof(uint32_t);
+  const size_t   evm_bytes = evm_sums ? (size_t)n * 14 * DEMOD_MAX_CHUNKS * sizeof(float) : 0; // per-(symbol, chunk) partials behind the sequences
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, seq_bytes + evm_bytes, &work)))
     return rc;
-  uint32_t*   seq = static_cast<uint32_t*>(work);
+  uint32_t*   seq      = static_cast<uint32_t*>(work);
+  float*      evm_part = evm_sums ? reinterpret_cast<float*>(static_cast<uint8_t*>(work) + seq_bytes) : nullptr;
   const auto* dj  = (const miphy_pusch_demod_layers_job*)d_jobs;
   hipLaunchKernelGGL(pusch_seq_layers_kernel, dim3(n, max_words <= (uint32_t)SEQ_STRIDE ? 1u : (max_words + SEQ_PIECE - 1) / SEQ_PIECE), dim3(SCR_THREADS), 0, s,
-                     dj, gt, seq, stride);
+                     dj, gt, seq, stride, have_ph);
   const uint32_t sym_parts = std::max(1u, std::min(4u, (uint32_t)ctx->num_cus / (n * max_chunks)));
+  const dim3 blocks(n, max_chunks, sym_parts);
+  auto       launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, blocks, dim3(DEMOD_THREADS), 0, s, dj, (const float2*)grid, (const float2*)ce, scalars, llr, (const uint32_t*)seq, stride,
+                       placeholders, evm_part);
+  };
   if (one_layer)
-    hipLaunchKernelGGL(pusch_demod_layers_kernel<true>, dim3(n, max_chunks, sym_parts), dim3(DEMOD_THREADS), 0, s, dj, (const float2*)grid, (const float2*)ce,
-                       scalars, llr, (const uint32_t*)seq, stride);
+    launch(extras ? pusch_demod_layers_kernel<true, true> : pusch_demod_layers_kernel<true, false>);
   if (more_layers)
-    hipLaunchKernelGGL(pusch_demod_layers_kernel<false>, dim3(n, max_chunks, sym_parts), dim3(DEMOD_THREADS), 0, s, dj, (const float2*)grid,
-                       (const float2*)ce, scalars, llr, (const uint32_t*)seq, stride);
+    launch(extras ? pusch_demod_layers_kernel<false, true> : pusch_demod_layers_kernel<false, false>);
+  if (evm_sums)
+    hipLaunchKernelGGL(pusch_evm_reduce_layers_kernel, dim3(n), dim3(64), 0, s, dj, (const float*)evm_part, evm_sums, have_ph);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
+}
+
+extern "C" int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                                   const float* ce, const float* scalars, int8_t* llr, void* stream)
+{
+  return pusch_demodulate_layers(ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, nullptr, nullptr, false, stream);
+}
+
+extern "C" int miphy_pusch_demodulate_layers_batch_ex(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n,
+                                                      const float* grid, const float* ce, const float* scalars, int8_t* llr, const uint16_t* placeholders,
+                                                      float* evm_sums, void* stream)
+{
+  return pusch_demodulate_layers(ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, placeholders, evm_sums, true, stream);
 }
 
 extern "C" uint32_t miphy_pusch_demod_nof_llr(const miphy_pusch_demod_job* j)

@@ -3,7 +3,8 @@
 // Behaviour contract: lib/phy/upper/channel_processors/pusch_processor_impl.cpp:108-330 for PDUs without UCI (the reference
 // itself restricts the rest: DM-RS type 1, two CDM groups without data, one layer: pusch_processor_impl.cpp:96-104,331-345).
 // This is host-side composition of miphy_dmrs_pusch_estimate_batch, miphy_pusch_demodulate_batch and miphy_pusch_decode_batch
-// with the parameters the reference derives (DM-RS scaling from the SCH-to-DM-RS power ratio, codeword length from the allocation).
+// with the parameters the reference derives (DM-RS scaling from the SCH-to-DM-RS power ratio, codeword length from the allocation);
+// with multiplexed UCI, miphy_ulsch_demultiplex_batch between the last two. One codeword on 1..4 layers goes through the layered stages.
 #include "miphy_ext.h"
 #include <cmath>
 #include <vector>
@@ -26,6 +27,201 @@ __global__ void zero_results_kernel(miphy_pusch_result* __restrict__ r, uint32_t
   if (i < n)
     r[i] = miphy_pusch_result{};
 }
+
+// What the _ex processors enqueue for a batch, built once from the PDUs: the one-layer entry point (lpdus == NULL: every PDU on one layer, 20 scalars
+// per PDU, the one-layer rules) and the layered one (the layer count of each PDU, 80 scalars, the layered rules) differ in nothing else.
+struct pusch_batch {
+  std::vector<miphy_pusch_chest_job>        cj;
+  std::vector<miphy_pusch_demod_layers_job> dj;
+  std::vector<miphy_pusch_tb_desc>          tb;
+  std::vector<miphy_ulsch_demux_job>        xj;       // PDUs with multiplexed UCI
+  std::vector<uint16_t>                     ph;       // their repetition placeholders, back to back
+  std::vector<uint32_t>                     nof_sym;  // data REs x layers per PDU (EVM)
+  std::vector<uint32_t>                     tb_index; // PDU of every transport-block descriptor
+  size_t                                    ce_elems = 0, llr_bytes = 0, sch_bytes = 0;
+};
+
+int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus, const miphy_pusch_uci* uci, uint32_t n, bool have_uci_out,
+                      pusch_batch& b)
+{
+  b.cj.resize(n), b.dj.resize(n), b.nof_sym.resize(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const miphy_pusch_pdu& p = lpdus ? lpdus[i].base : pdus[i];
+    const unsigned         L = lpdus ? lpdus[i].nof_tx_layers : 1;
+    const miphy_pusch_uci* u = uci ? &uci[i] : nullptr;
+    const bool has_uci = u && (u->nof_harq_ack_bits || u->nof_csi_part1_bits || u->nof_csi_part2_bits);
+    const bool has_tb  = !u || u->has_codeword;
+    MIPHY_REQUIRE(p.nof_rx_ports >= 1 && p.nof_rx_ports <= 4, "pusch_process: PDU %u: invalid number of receive ports", i);
+    if (lpdus) {
+      MIPHY_REQUIRE(L >= 1 && L <= 4, "pusch_process: PDU %u: invalid number of layers %u", i, L);
+      MIPHY_REQUIRE(L <= p.nof_rx_ports, "pusch_process: PDU %u: %u layers on %u receive ports", i, L, (unsigned)p.nof_rx_ports);
+      MIPHY_REQUIRE(p.numerology <= 4, "pusch_process: PDU %u: invalid numerology", i);
+    }
+    MIPHY_REQUIRE(p.nof_symbols >= 1 && p.start_symbol + p.nof_symbols <= 14, "pusch_process: PDU %u: invalid time allocation", i);
+    if (!lpdus)
+      MIPHY_REQUIRE(p.dmrs_symbols_mask != 0, "pusch_process: PDU %u: no DM-RS symbol", i);
+    MIPHY_REQUIRE(p.grid_nof_prb >= 1 && p.grid_nof_prb <= 275, "pusch_process: PDU %u: invalid grid width", i);
+    if (lpdus) {
+      unsigned nds = 0;
+      for (unsigned l = p.start_symbol; l < (unsigned)p.start_symbol + p.nof_symbols; ++l)
+        nds += (p.dmrs_symbols_mask >> l) & 1;
+      MIPHY_REQUIRE(nds >= 1 && nds <= 4, "pusch_process: PDU %u: %u DM-RS symbols in the allocation (1..4 supported)", i, nds);
+      MIPHY_REQUIRE(p.mod == 1 || p.mod == 2 || p.mod == 4 || p.mod == 6 || p.mod == 8, "pusch_process: PDU %u: invalid modulation", i);
+      if (has_tb) { // (the decoder's rules on the transport block, which it would only find behind the stages in front of it)
+        MIPHY_REQUIRE((p.bg == 1 || p.bg == 2) && p.rv <= 3 && p.nof_ldpc_iterations > 0, "pusch_process: PDU %u: invalid base graph, redundancy version or iterations", i);
+        miphy_sch_segmentation sg = {};
+        MIPHY_REQUIRE(miphy_sch_segmentation_info(p.tb_bytes, p.bg, &sg) == MIPHY_OK, "pusch_process: PDU %u: transport block of %u bytes cannot be segmented", i, p.tb_bytes);
+        MIPHY_REQUIRE((sg.cb_info_bits % 8) == 0 || sg.nof_cbs == 1,
+                      "pusch_process: PDU %u: %u bytes is not a TS 38.214 transport block size (codeblock payloads are not byte aligned)", i, p.tb_bytes);
+      }
+    }
+    const uint32_t nsc = p.grid_nof_prb * 12u, nsym_ce = (uint32_t)p.start_symbol + p.nof_symbols;
+    miphy_pusch_chest_job& c = b.cj[i];
+    c                        = {};
+    c.numerology = p.numerology, c.slot_in_frame = p.slot_in_frame, c.scrambling_id = p.dmrs_scrambling_id;
+    // pusch_processor_impl.cpp:150: amplitude of the DM-RS relative to the data, two CDM groups without data -> +3 dB
+    c.scaling = powf(10.0f, 3.0f / 20.0f);
+    c.n_scid = p.n_scid, c.nof_tx_layers = (uint8_t)L, c.nof_rx_ports = p.nof_rx_ports, c.first_symbol = p.start_symbol, c.nof_symbols = p.nof_symbols;
+    c.symbols_mask = p.dmrs_symbols_mask, c.grid_nof_prb = p.grid_nof_prb;
+    c.ce_compact   = 1; // the estimate only feeds the demodulator below: one row per port instead of a copy per symbol
+    miphy_pusch_demod_layers_job& lj = b.dj[i];
+    lj                               = {};
+    lj.nof_tx_layers                 = (uint8_t)L;
+    miphy_pusch_demod_job& d         = lj.base;
+    d.rnti = p.rnti, d.n_id = p.n_id, d.mod = p.mod, d.nof_rx_ports = p.nof_rx_ports, d.start_symbol = p.start_symbol, d.nof_symbols = p.nof_symbols;
+    d.dmrs_type = 1, d.nof_cdm_groups_without_data = 2, d.ce_nof_symbols = (uint8_t)nsym_ce, d.ce_compact = 1;
+    d.dmrs_symbols_mask = p.dmrs_symbols_mask, d.grid_nof_prb = p.grid_nof_prb;
+    for (int k = 0; k < 4; ++k)
+      c.rx_ports[k] = p.rx_ports[k], d.rx_ports[k] = p.rx_ports[k];
+    for (int k = 0; k < 5; ++k)
+      c.rb_mask[k] = p.rb_mask[k], d.rb_mask[k] = p.rb_mask[k];
+    c.grid_offset = d.grid_offset = p.grid_offset;
+    c.ce_offset = d.ce_offset = b.ce_elems;
+    // per PDU [4 ports][5] floats of layer 0, or [4 ports][4 layers][5]
+    c.scalars_offset = d.scalars_offset = (uint64_t)i * (lpdus ? 80 : 20);
+    d.llr_offset                       = b.llr_bytes;
+    d.nof_llr                          = lpdus ? miphy_pusch_demod_layers_nof_llr(&lj) : miphy_pusch_demod_nof_llr(&d);
+    MIPHY_REQUIRE(d.nof_llr > 0, "pusch_process: PDU %u: empty allocation", i);
+    d.evm_offset = (uint64_t)i * 14;
+    b.nof_sym[i] = d.nof_llr / p.mod;
+    uint64_t sch_llr_offset = b.llr_bytes; // where the decoder reads the UL-SCH soft bits: the codeword itself unless UCI is multiplexed
+    uint32_t nof_sch_llr    = d.nof_llr;
+    if (has_uci) {
+      MIPHY_REQUIRE(have_uci_out, "pusch_process: PDU %u carries UCI but uci_llr_out is NULL", i);
+      miphy_ulsch_demux_job x = {};
+      uint32_t              nprb = 0;
+      for (unsigned r = 0; r < p.grid_nof_prb; ++r)
+        nprb += (uint32_t)((p.rb_mask[r >> 6] >> (r & 63)) & 1ull);
+      x.mod = p.mod, x.nof_layers = (uint8_t)L, x.start_symbol = p.start_symbol, x.nof_symbols = p.nof_symbols, x.dmrs_type = 1, x.nof_cdm_groups_without_data = 2;
+      x.dmrs_symbols_mask = p.dmrs_symbols_mask, x.nof_prb = (uint16_t)nprb, x.nof_harq_ack_rvd = u->nof_harq_ack_rvd;
+      x.nof_enc_harq_ack_bits = u->nof_enc_harq_ack_bits, x.nof_enc_csi_part1_bits = u->nof_enc_csi_part1_bits;
+      x.nof_enc_csi_part2_bits = u->nof_enc_csi_part2_bits;
+      x.nof_harq_ack_bits = u->nof_harq_ack_bits, x.nof_csi_part1_bits = u->nof_csi_part1_bits, x.nof_csi_part2_bits = u->nof_csi_part2_bits;
+      uint32_t nin = 0;
+      int      rc  = miphy_ulsch_demux_sizes(&x, &nin, &nof_sch_llr);
+      if (rc)
+        return rc;
+      MIPHY_REQUIRE(nin == d.nof_llr, "pusch_process: PDU %u: the UL-SCH multiplexing covers %u soft bits, the allocation holds %u", i, nin, d.nof_llr);
+      x.in_offset = b.llr_bytes, x.sch_offset = b.sch_bytes, x.harq_ack_offset = u->harq_ack_offset, x.csi_part1_offset = u->csi_part1_offset;
+      x.csi_part2_offset = u->csi_part2_offset;
+      b.xj.push_back(x);
+      // repetition placeholders of the descrambler
+      uint32_t nph = 0;
+      if ((rc = miphy_ulsch_placeholders(&x, nullptr, 0, &nph)))
+        return rc;
+      d.placeholders_offset = (uint32_t)b.ph.size(), d.nof_placeholders = nph;
+      b.ph.resize(b.ph.size() + nph);
+      if (nph && (rc = miphy_ulsch_placeholders(&x, b.ph.data() + d.placeholders_offset, nph, &nph)))
+        return rc;
+      sch_llr_offset = b.sch_bytes; // relative to the SCH region, rebased below
+      b.sch_bytes += (nof_sch_llr + 15u) & ~15u;
+    }
+    // include/miphy.h: has_codeword = 0 means the PDU carries no transport block -- whatever its UCI fields say. A PDU with neither is
+    // not a PUSCH transmission.
+    MIPHY_REQUIRE(has_tb || has_uci, "pusch_process: PDU %u: neither a codeword nor UCI", i);
+    if (has_tb) {
+      miphy_pusch_tb_desc t = {};
+      t.bg = p.bg, t.rv = p.rv, t.mod = p.mod, t.nof_layers = (uint8_t)L, t.new_data = p.new_data, t.use_early_stop = p.use_early_stop;
+      t.nof_ldpc_iterations = p.nof_ldpc_iterations, t.Nref = p.Nref, t.nof_ch_symbols = nof_sch_llr / p.mod, t.tb_bytes = p.tb_bytes;
+      t.harq_cb_index = p.harq_cb_index, t.tb_offset = p.tb_offset;
+      t.llr_offset = has_uci ? (uint64_t)1 << 63 | sch_llr_offset : sch_llr_offset; // bit 63: offset inside the SCH region (resolved below)
+      b.tb.push_back(t);
+      b.tb_index.push_back(i);
+    }
+    b.ce_elems += (size_t)L * p.nof_rx_ports * nsc;
+    b.llr_bytes += (d.nof_llr + 15u) & ~15u;
+  }
+  for (auto& t : b.tb) // SCH region behind the codeword LLRs
+    if (t.llr_offset >> 63)
+      t.llr_offset = (t.llr_offset & ~((uint64_t)1 << 63)) + b.llr_bytes;
+  for (auto& x : b.xj)
+    x.sch_offset += b.llr_bytes;
+  return MIPHY_OK;
+}
+
+// Estimator, demodulator with placeholders and EVM, EVM finish (divisor: data REs x layers), demultiplexer and decoder on one stream. Every rule is
+// checked before anything is enqueued (pusch_batch_build); the stages check their own rules again on the jobs built there.
+int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus, const miphy_pusch_uci* uci, uint32_t n,
+                     const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results,
+                     float* scalars_out, int8_t* uci_llr_out, float* evm_out, hipStream_t s)
+{
+  pusch_batch b;
+  int         rc = pusch_batch_build(pdus, lpdus, uci, n, uci_llr_out != nullptr, b);
+  if (rc)
+    return rc;
+  // [placeholders | data REs || channel estimates cf_t | codeword LLRs, UL-SCH LLRs of the PDUs with UCI | EVM sums] in a workspace of the
+  // context, the two arrays in front uploaded as one; the estimator scalars go straight to the caller's array.
+  device_image img;
+  const auto   s_ph  = img.put(b.ph);
+  const auto   s_nre = img.put(b.nof_sym.data(), evm_out ? n : 0); // (read by the EVM kernel only)
+  const auto   s_ce  = img.reserve<float>(b.ce_elems * 2, 256);
+  const auto   s_llr = img.reserve<int8_t>(b.llr_bytes + b.sch_bytes, 256);
+  const auto   s_evm = img.reserve<float>(evm_out ? (size_t)n * 14 : 0);
+  void*        work  = nullptr;
+  if ((rc = miphy_image_to_workspace(ctx, MIPHY_WS_PUSCH_PROC, img, s, &work)))
+    return rc;
+  float*          d_ce  = s_ce.at(work);
+  int8_t*         d_llr = s_llr.at(work);
+  float*          d_evm = evm_out ? s_evm.at(work) : nullptr;
+  const uint16_t* d_ph  = b.ph.empty() ? nullptr : s_ph.at(work);
+  uint32_t*       d_nre = s_nre.at(work);
+  if (lpdus) {
+    if ((rc = miphy_dmrs_pusch_estimate_layers_batch(ctx, b.cj.data(), 0, n, grid, d_ce, scalars_out, s)))
+      return rc;
+    if ((rc = miphy_pusch_demodulate_layers_batch_ex(ctx, b.dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, d_ph, d_evm, s)))
+      return rc;
+  } else {
+    std::vector<miphy_pusch_demod_job> dj(n);
+    for (uint32_t i = 0; i < n; ++i)
+      dj[i] = b.dj[i].base;
+    if ((rc = miphy_dmrs_pusch_estimate_batch(ctx, b.cj.data(), 0, n, grid, d_ce, scalars_out, s)))
+      return rc;
+    if ((rc = miphy_pusch_demodulate_batch_ex(ctx, dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, d_ph, d_evm, s)))
+      return rc;
+  }
+  if (evm_out) {
+    hipLaunchKernelGGL(evm_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_evm, d_nre, evm_out, n);
+    MIPHY_HIP_CHECK(hipGetLastError());
+  }
+  if (!b.xj.empty() &&
+      (rc = miphy_ulsch_demultiplex_batch(ctx, b.xj.data(), (uint32_t)b.xj.size(), d_llr, d_llr, uci_llr_out, uci_llr_out, uci_llr_out, s)))
+    return rc;
+  if (b.tb.size() == n) // the common case: every PDU has a transport block, results in PDU order
+    return miphy_pusch_decode_batch(ctx, b.tb.data(), n, d_llr, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, s);
+  // Some PDUs carry UCI only: decode the others into a compact result array, then put the records in PDU order.
+  hipLaunchKernelGGL(zero_results_kernel, dim3((n + 255) / 256), dim3(256), 0, s, results, n);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  if (b.tb.empty())
+    return MIPHY_OK;
+  void* rws = nullptr;
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, b.tb.size() * sizeof(miphy_pusch_result), &rws)))
+    return rc;
+  if ((rc = miphy_pusch_decode_batch(ctx, b.tb.data(), (uint32_t)b.tb.size(), d_llr, harq_softbits, harq_msgs, harq_crc_ok, tb_out, (miphy_pusch_result*)rws, s)))
+    return rc;
+  for (size_t k = 0; k < b.tb.size(); ++k)
+    MIPHY_HIP_CHECK(hipMemcpyAsync(results + b.tb_index[k], (miphy_pusch_result*)rws + k, sizeof(miphy_pusch_result), hipMemcpyDeviceToDevice, s));
+  return MIPHY_OK;
+}
 } // namespace
 
 extern "C" int miphy_pusch_process_batch(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, uint32_t n, const float* grid, int8_t* harq_softbits,
@@ -36,89 +232,25 @@ extern "C" int miphy_pusch_process_batch(miphy_ctx* ctx, const miphy_pusch_pdu* 
                                       stream);
 }
 
-// One codeword on 1..4 layers: the layered estimator, the layered demodulator and the decoder on one stream (include/miphy.h). Every rule is
-// checked before anything is enqueued; the stages check their own rules again on the jobs built here.
-extern "C" int miphy_pusch_process_layers_batch(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus, uint32_t n, const float* grid, int8_t* harq_softbits,
-                                                uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results,
-                                                float* scalars_out, void* stream)
+// One codeword on 1..4 layers, with multiplexed UCI and the EVM (include/miphy.h).
+extern "C" int miphy_pusch_process_layers_batch_ex(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus, const miphy_pusch_uci* uci, uint32_t n, const float* grid,
+                                                   int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
+                                                   miphy_pusch_result* results, float* scalars_out, int8_t* uci_llr_out, float* evm_out, void* stream)
 {
   MIPHY_REQUIRE(ctx && pdus && grid && harq_softbits && harq_msgs && harq_crc_ok && tb_out && results && scalars_out,
                 "miphy_pusch_process_layers_batch: null argument");
   if (n == 0)
     return MIPHY_OK;
-  hipStream_t                               s = (hipStream_t)stream;
-  std::vector<miphy_pusch_chest_job>        cj(n);
-  std::vector<miphy_pusch_demod_layers_job> dj(n);
-  std::vector<miphy_pusch_tb_desc>          tb(n);
-  size_t                                    ce_elems = 0, llr_bytes = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    const miphy_pusch_pdu& p = pdus[i].base;
-    const unsigned         L = pdus[i].nof_tx_layers;
-    MIPHY_REQUIRE(p.nof_rx_ports >= 1 && p.nof_rx_ports <= 4, "pusch_process: PDU %u: invalid number of receive ports", i);
-    MIPHY_REQUIRE(L >= 1 && L <= 4, "pusch_process: PDU %u: invalid number of layers %u", i, L);
-    MIPHY_REQUIRE(L <= p.nof_rx_ports, "pusch_process: PDU %u: %u layers on %u receive ports", i, L, (unsigned)p.nof_rx_ports);
-    MIPHY_REQUIRE(p.numerology <= 4, "pusch_process: PDU %u: invalid numerology", i);
-    MIPHY_REQUIRE(p.nof_symbols >= 1 && p.start_symbol + p.nof_symbols <= 14, "pusch_process: PDU %u: invalid time allocation", i);
-    MIPHY_REQUIRE(p.grid_nof_prb >= 1 && p.grid_nof_prb <= 275, "pusch_process: PDU %u: invalid grid width", i);
-    unsigned nds = 0;
-    for (unsigned l = p.start_symbol; l < (unsigned)p.start_symbol + p.nof_symbols; ++l)
-      nds += (p.dmrs_symbols_mask >> l) & 1;
-    MIPHY_REQUIRE(nds >= 1 && nds <= 4, "pusch_process: PDU %u: %u DM-RS symbols in the allocation (1..4 supported)", i, nds);
-    MIPHY_REQUIRE(p.mod == 1 || p.mod == 2 || p.mod == 4 || p.mod == 6 || p.mod == 8, "pusch_process: PDU %u: invalid modulation", i);
-    // (the decoder's rules on the transport block, which it would only find behind the two stages in front of it)
-    MIPHY_REQUIRE((p.bg == 1 || p.bg == 2) && p.rv <= 3 && p.nof_ldpc_iterations > 0, "pusch_process: PDU %u: invalid base graph, redundancy version or iterations", i);
-    miphy_sch_segmentation sg = {};
-    MIPHY_REQUIRE(miphy_sch_segmentation_info(p.tb_bytes, p.bg, &sg) == MIPHY_OK, "pusch_process: PDU %u: transport block of %u bytes cannot be segmented", i, p.tb_bytes);
-    MIPHY_REQUIRE((sg.cb_info_bits % 8) == 0 || sg.nof_cbs == 1,
-                  "pusch_process: PDU %u: %u bytes is not a TS 38.214 transport block size (codeblock payloads are not byte aligned)", i, p.tb_bytes);
-    const uint32_t         nsc = p.grid_nof_prb * 12u;
-    miphy_pusch_chest_job& c   = cj[i];
-    c                          = {};
-    c.numerology = p.numerology, c.slot_in_frame = p.slot_in_frame, c.scrambling_id = p.dmrs_scrambling_id;
-    c.scaling = powf(10.0f, 3.0f / 20.0f); // two CDM groups without data -> +3 dB, as on one layer
-    c.n_scid = p.n_scid, c.nof_tx_layers = (uint8_t)L, c.nof_rx_ports = p.nof_rx_ports, c.first_symbol = p.start_symbol, c.nof_symbols = p.nof_symbols;
-    c.symbols_mask = p.dmrs_symbols_mask, c.grid_nof_prb = p.grid_nof_prb;
-    c.ce_compact   = 1;
-    miphy_pusch_demod_layers_job& lj = dj[i];
-    lj                               = {};
-    lj.nof_tx_layers                 = (uint8_t)L;
-    miphy_pusch_demod_job& d         = lj.base;
-    d.rnti = p.rnti, d.n_id = p.n_id, d.mod = p.mod, d.nof_rx_ports = p.nof_rx_ports, d.start_symbol = p.start_symbol, d.nof_symbols = p.nof_symbols;
-    d.dmrs_type = 1, d.nof_cdm_groups_without_data = 2, d.ce_nof_symbols = (uint8_t)(p.start_symbol + p.nof_symbols), d.ce_compact = 1;
-    d.dmrs_symbols_mask = p.dmrs_symbols_mask, d.grid_nof_prb = p.grid_nof_prb;
-    for (int k = 0; k < 4; ++k)
-      c.rx_ports[k] = p.rx_ports[k], d.rx_ports[k] = p.rx_ports[k];
-    for (int k = 0; k < 5; ++k)
-      c.rb_mask[k] = p.rb_mask[k], d.rb_mask[k] = p.rb_mask[k];
-    c.grid_offset = d.grid_offset = p.grid_offset;
-    c.ce_offset = d.ce_offset = ce_elems;
-    c.scalars_offset = d.scalars_offset = (uint64_t)i * 80; // [4 ports][4 layers][5] floats per PDU
-    d.llr_offset                       = llr_bytes;
-    d.nof_llr                          = miphy_pusch_demod_layers_nof_llr(&lj);
-    MIPHY_REQUIRE(d.nof_llr > 0, "pusch_process: PDU %u: empty allocation", i);
-    miphy_pusch_tb_desc& t = tb[i];
-    t                      = {};
-    t.bg = p.bg, t.rv = p.rv, t.mod = p.mod, t.nof_layers = (uint8_t)L, t.new_data = p.new_data, t.use_early_stop = p.use_early_stop;
-    t.nof_ldpc_iterations = p.nof_ldpc_iterations, t.Nref = p.Nref, t.nof_ch_symbols = d.nof_llr / p.mod, t.tb_bytes = p.tb_bytes;
-    t.harq_cb_index = p.harq_cb_index, t.tb_offset = p.tb_offset, t.llr_offset = llr_bytes;
-    ce_elems += (size_t)L * p.nof_rx_ports * nsc;
-    llr_bytes += (d.nof_llr + 15u) & ~15u;
-  }
-  // [channel estimates cf_t | codeword LLRs] in the processor's workspace; the estimator scalars go straight to the caller's array.
-  device_image img;
-  const auto   s_ce  = img.reserve<float>(ce_elems * 2, 256);
-  const auto   s_llr = img.reserve<int8_t>(llr_bytes, 256);
-  void*        work  = nullptr;
-  int          rc    = miphy_image_to_workspace(ctx, MIPHY_WS_PUSCH_PROC, img, s, &work);
-  if (rc)
-    return rc;
-  float*  d_ce  = s_ce.at(work);
-  int8_t* d_llr = s_llr.at(work);
-  if ((rc = miphy_dmrs_pusch_estimate_layers_batch(ctx, cj.data(), 0, n, grid, d_ce, scalars_out, s)))
-    return rc;
-  if ((rc = miphy_pusch_demodulate_layers_batch(ctx, dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, s)))
-    return rc;
-  return miphy_pusch_decode_batch(ctx, tb.data(), n, d_llr, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, s);
+  return pusch_process_ex(ctx, nullptr, pdus, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+                          (hipStream_t)stream);
+}
+
+extern "C" int miphy_pusch_process_layers_batch(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus, uint32_t n, const float* grid, int8_t* harq_softbits,
+                                                uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results,
+                                                float* scalars_out, void* stream)
+{
+  return miphy_pusch_process_layers_batch_ex(ctx, pdus, nullptr, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, nullptr,
+                                             nullptr, stream);
 }
 
 extern "C" int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pusch_uci* uci, uint32_t n, const float* grid,
@@ -129,146 +261,6 @@ extern "C" int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pd
                 "miphy_pusch_process_batch: null argument");
   if (n == 0)
     return MIPHY_OK;
-  hipStream_t                        s = (hipStream_t)stream;
-  std::vector<miphy_pusch_chest_job> cj(n);
-  std::vector<miphy_pusch_demod_job> dj(n);
-  std::vector<miphy_pusch_tb_desc>   tb;
-  std::vector<miphy_ulsch_demux_job> xj;        // PDUs with multiplexed UCI
-  std::vector<uint16_t>              ph;        // their repetition placeholders, back to back
-  std::vector<uint32_t>              nof_re(n); // data REs per PDU (EVM)
-  std::vector<uint32_t>              no_tb;     // PDUs without a transport block
-  std::vector<uint32_t>              tb_index;  // PDU of every transport-block descriptor
-  size_t                             ce_elems = 0, llr_bytes = 0, sch_bytes = 0;
-  bool                               any_uci  = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const miphy_pusch_pdu& p = pdus[i];
-    MIPHY_REQUIRE(p.nof_rx_ports >= 1 && p.nof_rx_ports <= 4, "pusch_process: PDU %u: invalid number of receive ports", i);
-    MIPHY_REQUIRE(p.nof_symbols >= 1 && p.start_symbol + p.nof_symbols <= 14, "pusch_process: PDU %u: invalid time allocation", i);
-    MIPHY_REQUIRE(p.dmrs_symbols_mask != 0, "pusch_process: PDU %u: no DM-RS symbol", i);
-    MIPHY_REQUIRE(p.grid_nof_prb >= 1 && p.grid_nof_prb <= 275, "pusch_process: PDU %u: invalid grid width", i);
-    const uint32_t nsc = p.grid_nof_prb * 12u, nsym_ce = (uint32_t)p.start_symbol + p.nof_symbols;
-    miphy_pusch_chest_job& c = cj[i];
-    c                        = {};
-    c.numerology = p.numerology, c.slot_in_frame = p.slot_in_frame, c.scrambling_id = p.dmrs_scrambling_id;
-    // pusch_processor_impl.cpp:150: amplitude of the DM-RS relative to the data, two CDM groups without data -> +3 dB
-    c.scaling = powf(10.0f, 3.0f / 20.0f);
-    c.n_scid = p.n_scid, c.nof_tx_layers = 1, c.nof_rx_ports = p.nof_rx_ports, c.first_symbol = p.start_symbol, c.nof_symbols = p.nof_symbols;
-    c.symbols_mask = p.dmrs_symbols_mask, c.grid_nof_prb = p.grid_nof_prb;
-    c.ce_compact   = 1; // the estimate only feeds the demodulator below: one row per port instead of a copy per symbol
-    miphy_pusch_demod_job& d = dj[i];
-    d                        = {};
-    d.rnti = p.rnti, d.n_id = p.n_id, d.mod = p.mod, d.nof_rx_ports = p.nof_rx_ports, d.start_symbol = p.start_symbol, d.nof_symbols = p.nof_symbols;
-    d.dmrs_type = 1, d.nof_cdm_groups_without_data = 2, d.ce_nof_symbols = (uint8_t)nsym_ce, d.ce_compact = 1;
-    d.dmrs_symbols_mask = p.dmrs_symbols_mask, d.grid_nof_prb = p.grid_nof_prb;
-    for (int k = 0; k < 4; ++k)
-      c.rx_ports[k] = p.rx_ports[k], d.rx_ports[k] = p.rx_ports[k];
-    for (int k = 0; k < 5; ++k)
-      c.rb_mask[k] = p.rb_mask[k], d.rb_mask[k] = p.rb_mask[k];
-    c.grid_offset = d.grid_offset = p.grid_offset;
-    c.ce_offset = d.ce_offset = ce_elems;
-    c.scalars_offset = d.scalars_offset = (uint64_t)i * 20; // [4 ports][5] floats per PDU, layer 0
-    d.llr_offset                       = llr_bytes;
-    d.nof_llr                          = miphy_pusch_demod_nof_llr(&d);
-    MIPHY_REQUIRE(d.nof_llr > 0, "pusch_process: PDU %u: empty allocation", i);
-    d.evm_offset = (uint64_t)i * 14;
-    nof_re[i]    = d.nof_llr / p.mod;
-    uint64_t sch_llr_offset = llr_bytes; // where the decoder reads the UL-SCH soft bits: the codeword itself unless UCI is multiplexed
-    uint32_t nof_sch_llr    = d.nof_llr;
-    const miphy_pusch_uci* u = uci ? &uci[i] : nullptr;
-    const bool has_uci = u && (u->nof_harq_ack_bits || u->nof_csi_part1_bits || u->nof_csi_part2_bits);
-    if (has_uci) {
-      MIPHY_REQUIRE(uci_llr_out, "pusch_process: PDU %u carries UCI but uci_llr_out is NULL", i);
-      any_uci = true;
-      miphy_ulsch_demux_job x = {};
-      uint32_t              nprb = 0;
-      for (unsigned r = 0; r < p.grid_nof_prb; ++r)
-        nprb += (uint32_t)((p.rb_mask[r >> 6] >> (r & 63)) & 1ull);
-      x.mod = p.mod, x.nof_layers = 1, x.start_symbol = p.start_symbol, x.nof_symbols = p.nof_symbols, x.dmrs_type = 1, x.nof_cdm_groups_without_data = 2;
-      x.dmrs_symbols_mask = p.dmrs_symbols_mask, x.nof_prb = (uint16_t)nprb, x.nof_harq_ack_rvd = u->nof_harq_ack_rvd;
-      x.nof_enc_harq_ack_bits = u->nof_enc_harq_ack_bits, x.nof_enc_csi_part1_bits = u->nof_enc_csi_part1_bits;
-      x.nof_enc_csi_part2_bits = u->nof_enc_csi_part2_bits;
-      x.nof_harq_ack_bits = u->nof_harq_ack_bits, x.nof_csi_part1_bits = u->nof_csi_part1_bits, x.nof_csi_part2_bits = u->nof_csi_part2_bits;
-      uint32_t nin = 0;
-      int      rc  = miphy_ulsch_demux_sizes(&x, &nin, &nof_sch_llr);
-      if (rc)
-        return rc;
-      MIPHY_REQUIRE(nin == d.nof_llr, "pusch_process: PDU %u: the UL-SCH multiplexing covers %u soft bits, the allocation holds %u", i, nin, d.nof_llr);
-      x.in_offset = llr_bytes, x.sch_offset = sch_bytes, x.harq_ack_offset = u->harq_ack_offset, x.csi_part1_offset = u->csi_part1_offset;
-      x.csi_part2_offset = u->csi_part2_offset;
-      xj.push_back(x);
-      // repetition placeholders of the descrambler
-      uint32_t nph = 0;
-      if ((rc = miphy_ulsch_placeholders(&x, nullptr, 0, &nph)))
-        return rc;
-      d.placeholders_offset = (uint32_t)ph.size(), d.nof_placeholders = nph;
-      ph.resize(ph.size() + nph);
-      if (nph && (rc = miphy_ulsch_placeholders(&x, ph.data() + d.placeholders_offset, nph, &nph)))
-        return rc;
-      sch_llr_offset = sch_bytes; // relative to the SCH region, rebased below
-      sch_bytes += (nof_sch_llr + 15u) & ~15u;
-    }
-    // include/miphy.h: has_codeword = 0 means the PDU carries no transport block -- whatever its UCI fields say. A PDU with neither is
-    // not a PUSCH transmission.
-    MIPHY_REQUIRE(!u || u->has_codeword || has_uci, "pusch_process: PDU %u: neither a codeword nor UCI", i);
-    if (!u || u->has_codeword) {
-      miphy_pusch_tb_desc t = {};
-      t.bg = p.bg, t.rv = p.rv, t.mod = p.mod, t.nof_layers = 1, t.new_data = p.new_data, t.use_early_stop = p.use_early_stop;
-      t.nof_ldpc_iterations = p.nof_ldpc_iterations, t.Nref = p.Nref, t.nof_ch_symbols = nof_sch_llr / p.mod, t.tb_bytes = p.tb_bytes;
-      t.harq_cb_index = p.harq_cb_index, t.tb_offset = p.tb_offset;
-      t.llr_offset = has_uci ? (uint64_t)1 << 63 | sch_llr_offset : sch_llr_offset; // bit 63: offset inside the SCH region (resolved below)
-      tb.push_back(t);
-      tb_index.push_back(i);
-    } else {
-      no_tb.push_back(i);
-    }
-    ce_elems += (size_t)p.nof_rx_ports * nsc;
-    llr_bytes += (d.nof_llr + 15u) & ~15u;
-  }
-  for (auto& t : tb) // SCH region behind the codeword LLRs
-    if (t.llr_offset >> 63)
-      t.llr_offset = (t.llr_offset & ~((uint64_t)1 << 63)) + llr_bytes;
-  for (auto& x : xj)
-    x.sch_offset += llr_bytes;
-  // [placeholders | data REs || channel estimates cf_t | codeword LLRs, UL-SCH LLRs of the PDUs with UCI | EVM sums] in a workspace of the
-  // context, the two arrays in front uploaded as one; the estimator scalars go straight to the caller's array.
-  device_image img;
-  const auto   s_ph  = img.put(ph);
-  const auto   s_nre = img.put(nof_re.data(), evm_out ? n : 0); // (read by the EVM kernel only)
-  const auto   s_ce  = img.reserve<float>(ce_elems * 2, 256);
-  const auto   s_llr = img.reserve<int8_t>(llr_bytes + sch_bytes, 256);
-  const auto   s_evm = img.reserve<float>(evm_out ? (size_t)n * 14 : 0);
-  void*        work  = nullptr;
-  int          rc    = miphy_image_to_workspace(ctx, MIPHY_WS_PUSCH_PROC, img, s, &work);
-  if (rc)
-    return rc;
-  float*    d_ce  = s_ce.at(work);
-  int8_t*   d_llr = s_llr.at(work);
-  float*    d_evm = s_evm.at(work);
-  uint16_t* d_ph  = s_ph.at(work);
-  uint32_t* d_nre = s_nre.at(work);
-  if ((rc = miphy_dmrs_pusch_estimate_batch(ctx, cj.data(), 0, n, grid, d_ce, scalars_out, s)))
-    return rc;
-  if ((rc = miphy_pusch_demodulate_batch_ex(ctx, dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, ph.empty() ? nullptr : d_ph, evm_out ? d_evm : nullptr, s)))
-    return rc;
-  if (evm_out) {
-    hipLaunchKernelGGL(evm_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_evm, d_nre, evm_out, n);
-    MIPHY_HIP_CHECK(hipGetLastError());
-  }
-  if (any_uci && (rc = miphy_ulsch_demultiplex_batch(ctx, xj.data(), (uint32_t)xj.size(), d_llr, d_llr, uci_llr_out, uci_llr_out, uci_llr_out, s)))
-    return rc;
-  if (tb.size() == n) // the common case: every PDU has a transport block, results in PDU order
-    return miphy_pusch_decode_batch(ctx, tb.data(), n, d_llr, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, s);
-  // Some PDUs carry UCI only: decode the others into a compact result array, then put the records in PDU order.
-  hipLaunchKernelGGL(zero_results_kernel, dim3((n + 255) / 256), dim3(256), 0, s, results, n);
-  MIPHY_HIP_CHECK(hipGetLastError());
-  if (tb.empty())
-    return MIPHY_OK;
-  void* rws = nullptr;
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_OUTPUT, tb.size() * sizeof(miphy_pusch_result), &rws)))
-    return rc;
-  if ((rc = miphy_pusch_decode_batch(ctx, tb.data(), (uint32_t)tb.size(), d_llr, harq_softbits, harq_msgs, harq_crc_ok, tb_out, (miphy_pusch_result*)rws, s)))
-    return rc;
-  for (size_t k = 0; k < tb.size(); ++k)
-    MIPHY_HIP_CHECK(hipMemcpyAsync(results + tb_index[k], (miphy_pusch_result*)rws + k, sizeof(miphy_pusch_result), hipMemcpyDeviceToDevice, s));
-  return MIPHY_OK;
+  return pusch_process_ex(ctx, pdus, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+                          (hipStream_t)stream);
 }

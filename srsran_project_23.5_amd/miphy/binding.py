@@ -145,6 +145,9 @@ def lib():
         if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_pusch_process_layers_batch"):  # (likewise)
             l.miphy_dmrs_pusch_estimate_layers_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
             l.miphy_pusch_process_layers_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 8
+        if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_pusch_process_layers_batch_ex"):  # (likewise)
+            l.miphy_pusch_demodulate_layers_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 7
+            l.miphy_pusch_process_layers_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 10
         l.miphy_polar_block_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("miphy_ofdm_demodulate_symbols", "miphy_ofdm_modulate_symbols"):
             getattr(l, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -501,7 +504,8 @@ def uci_polar_info(nof_bits, nof_llr):
 def pusch_uci_jobs(pdus, uci):
     """pusch_uci_field_jobs for PDUs whose fields may be longer than 11 bits (host function): fields of 1..11 bits become UciFieldJob
     records, those of 12..1706 bits UciPolarJob records, all payloads packed into one buffer in (PDU, field) order. Returns
-    (short_jobs, short_field, polar_jobs, polar_field) with *_field = 3 * pdu + field."""
+    (short_jobs, short_field, polar_jobs, polar_field) with *_field = 3 * pdu + field. Only `mod` of a PDU record is read: for
+    PuschLayersPdu records pass pdus["base"]."""
     assert isinstance(pdus, np.ndarray) and pdus.dtype == PuschPdu and isinstance(uci, np.ndarray) and uci.dtype == PuschUci
     assert pdus.size == uci.size
     pdus, uci = np.ascontiguousarray(pdus), np.ascontiguousarray(uci)
@@ -907,6 +911,14 @@ class Context:
         jobs, n, ptr, on_dev = self._descs(jobs, PuschDemodLayersJob)
         check(lib().miphy_pusch_demodulate_layers_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _dptr(llr), _stream_ptr(stream)))
 
+    def pusch_demodulate_layers_batch_ex(self, jobs, grid, ce, scalars, llr, placeholders=None, evm_sums=None, stream=None):
+        """pusch_demodulate_layers_batch with the repetition placeholders (device uint16: resource element indices as ulsch_placeholders gives them
+        for the job's layer count) and / or the per-symbol EVM sums (device float32, 14 per job at evm_offset, summed over the layers)."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschDemodLayersJob)
+        check(lib().miphy_pusch_demodulate_layers_batch_ex(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _dptr(llr),
+                                                           _dptr(placeholders) if placeholders is not None else None,
+                                                           _dptr(evm_sums) if evm_sums is not None else None, _stream_ptr(stream)))
+
     def polar_block_batch(self, code, op, param, n, x, out, stream=None):
         check(lib().miphy_polar_block_batch(self.h, C.byref(code) if code is not None else None, op, param, n, _dptr(x), _dptr(out), _stream_ptr(stream)))
 
@@ -936,6 +948,21 @@ class Context:
         pdus = np.ascontiguousarray(pdus)
         check(lib().miphy_pusch_process_layers_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, _dptr(grid), _dptr(harq_softbits), _dptr(harq_msgs),
                                                      _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars), _stream_ptr(stream)))
+
+    def pusch_process_layers_batch_ex(self, pdus, uci, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, uci_llr, evm, stream=None):
+        """pusch_process_layers_batch for PDUs with multiplexed UCI (uci: numpy PuschUci array or None) and the EVM (evm: float32 device tensor of n or
+        None). The field jobs behind it: pusch_uci_jobs(pdus["base"], uci)."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PuschLayersPdu
+        pdus = np.ascontiguousarray(pdus)
+        up = None
+        if uci is not None:
+            assert isinstance(uci, np.ndarray) and uci.dtype == PuschUci and uci.size == pdus.size
+            uci = np.ascontiguousarray(uci)
+            up = C.c_void_p(uci.ctypes.data)
+        check(lib().miphy_pusch_process_layers_batch_ex(self.h, C.c_void_p(pdus.ctypes.data), up, pdus.size, _dptr(grid), _dptr(harq_softbits),
+                                                        _dptr(harq_msgs), _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars),
+                                                        _dptr(uci_llr) if uci_llr is not None else None, _dptr(evm) if evm is not None else None,
+                                                        _stream_ptr(stream)))
 
     def pusch_process_batch_ex(self, pdus, uci, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, uci_llr, evm, stream=None):
         """PDUs with multiplexed UCI (uci: numpy PuschUci array or None) and the EVM (evm: float32 device tensor of n or None)."""
