@@ -46,6 +46,20 @@ static inline __host__ __device__ int miphy_crc_zmask_index(int crc_id)
   return crc_id == 0 ? 0 : (crc_id == 1 ? 1 : (crc_id == 3 ? 2 : -1));
 }
 
+// Allocated PRBs of a five-word mask on a grid of grid_nof_prb PRBs: word popcounts, the bits behind the grid masked off. Whatever
+// grid_nof_prb holds, no word behind the fifth is read. (Uniform arguments: scalar popcounts on the device.)
+static inline __host__ __device__ unsigned miphy_count_prb(const uint64_t* rb_mask, unsigned grid_nof_prb)
+{
+  unsigned n = 0;
+#pragma unroll
+  for (int w = 0; w < 5; ++w) {
+    const int left = (int)grid_nof_prb - 64 * w;
+    if (left > 0)
+      n += (unsigned)__builtin_popcountll(rb_mask[w] & (left >= 64 ? ~0ull : ((1ull << left) - 1ull)));
+  }
+  return n;
+}
+
 // Geometry of an LDPC codeblock, for host and device alike: the kernels carve their LDS up with the very functions the launch planner
 // sizes it with. bgi = base graph - 1.
 static constexpr __host__ __device__ int miphy_bg_K(int bgi) // systematic columns

@@ -196,7 +196,7 @@ struct demod_args {
   const uint16_t* ph;  // repetition placeholders of this transmission (sorted RE indices), nph of them
   int             nph;
   float*          evm_part; // per (OFDM symbol, chunk) partial sums of |hard-decided symbol - equalised symbol|^2 of this transmission, or nullptr
-  const uint32_t* seq;      // the transmission's scrambling sequence (pusch_scrambling_kernel)
+  const uint32_t* seq;      // the transmission's scrambling sequence (pusch_seq_kernel)
   int             start_symbol, end_symbol, per_dm, nprb;
   int             prefix0; // data elements of the transmission before start_symbol (a workgroup may own a part of the symbols)
   unsigned        dmrs_syms;
@@ -204,6 +204,80 @@ struct demod_args {
 
 constexpr int DEMOD_THREADS = 256;
 constexpr int DEMOD_MAX_CHUNKS = (275 * 12 + DEMOD_THREADS - 1) / DEMOD_THREADS; // 13
+
+// MOD soft bits packed in w (LLR b in byte b) to q: one wide store where q is aligned to it (demod_aligned), bytes otherwise. The one-layer
+// walks test the first element of a symbol (uniform: a scalar branch), the layered ones q itself; the two agree for every MOD, since the
+// elements of a symbol lie MOD bytes apart.
+template <int MOD>
+__device__ __forceinline__ bool demod_aligned(const int8_t* q)
+{
+  return ((uintptr_t)q % (MOD == 8 ? 8 : MOD == 4 ? 4 : MOD == 1 ? 1 : 2)) == 0;
+}
+template <int MOD>
+__device__ __forceinline__ void demod_store(uint64_t w, int8_t* q, bool aligned)
+{
+  if (aligned) {
+    if (MOD == 8)
+      *reinterpret_cast<uint2*>(q) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+    else if (MOD == 6) {
+      uint16_t* q2 = reinterpret_cast<uint16_t*>(q);
+      q2[0] = (uint16_t)w, q2[1] = (uint16_t)(w >> 16), q2[2] = (uint16_t)(w >> 32);
+    } else if (MOD == 4)
+      *reinterpret_cast<uint32_t*>(q) = (uint32_t)w;
+    else if (MOD == 2)
+      *reinterpret_cast<uint16_t*>(q) = (uint16_t)w;
+    else
+      q[0] = (int8_t)w;
+  } else {
+#pragma unroll
+    for (int b = 0; b < MOD; ++b)
+      q[b] = (int8_t)(w >> (8 * b));
+  }
+}
+
+// The soft bits l[0 .. MOD - 1] descrambled with the low MOD bits of `bits` (chip set: negated), packed as demod_store takes them.
+template <int MOD>
+__device__ __forceinline__ uint64_t demod_descramble_pack(const int* l, uint32_t bits)
+{
+  uint64_t w = 0;
+#pragma unroll
+  for (int b = 0; b < MOD; ++b) {
+    const int m = -(int)((bits >> b) & 1u); // 0 / -1
+    w |= (uint64_t)(uint8_t)(int8_t)((l[b] ^ m) - m) << (8 * b);
+  }
+  return w;
+}
+
+// Whether element `re` of the codeword is in the transmission's placeholder list: binary search (pusch_demodulator_impl.cpp:117-149).
+__device__ __forceinline__ bool demod_is_placeholder(const demod_args& a, unsigned re)
+{
+  for (int lo = 0, hi = a.nph - 1; lo <= hi;) {
+    const int      mid = (lo + hi) >> 1;
+    const unsigned v   = a.ph[mid];
+    if (v == re)
+      return true;
+    if (v < re)
+      lo = mid + 1;
+    else
+      hi = mid - 1;
+  }
+  return false;
+}
+
+// EVM partial of the workgroup for symbol sy from every thread's term, in one order whatever the launch: wavefront shuffle tree, then the four
+// wavefronts in sequence; thread 0 writes it. Every thread of the workgroup calls it (barriers).
+__device__ __forceinline__ void demod_evm_sum(const demod_args& a, int sy, float evm_acc, float* evm_red, int tid)
+{
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1)
+    evm_acc += __shfl_xor(evm_acc, off);
+  __syncthreads();
+  if ((tid & 63) == 0)
+    evm_red[tid >> 6] = evm_acc;
+  __syncthreads();
+  if (tid == 0)
+    a.evm_part[sy * DEMOD_MAX_CHUNKS + blockIdx.y] = ((evm_red[0] + evm_red[1]) + evm_red[2]) + evm_red[3];
+}
 
 // One thread = one allocated subcarrier, walked over the OFDM symbols of the allocation: with the compact estimate (one row per port,
 // valid for every symbol) the channel coefficients, 1 / sum |h|^2, the post-equalisation noise variance and its reciprocal are
@@ -286,33 +360,21 @@ __device__ __forceinline__ void demod_columns_deep(const demod_args& a, bool act
     const bool     fast    = fabsf(z_re) < INFINITY && fabsf(z_im) < INFINITY && rcp_chk < INFINITY;
     const unsigned re      = (unsigned)(prefix + max(r, 0));
     int8_t*        q       = a.llr + (size_t)re * MOD;
-    const bool     aligned = ((uintptr_t)(a.llr + (size_t)prefix * MOD) % (MOD == 8 ? 8 : MOD == 4 ? 4 : 2)) == 0;
+    const bool     aligned = demod_aligned<MOD>(a.llr + (size_t)prefix * MOD); // uniform
     const uint32_t sh      = (re * (uint32_t)MOD) & 31u;
     const uint32_t bits    = (MOD == 6) ? (uint32_t)((((uint64_t)w1[k] << 32) | w0[k]) >> sh) : (w0[k] >> sh);
     const uint64_t w       = demod_symbol_packed<MOD>(z_re, z_im, nv, tab, bits); // (garbage where !fast: replaced below)
     const bool     has     = active && r >= 0 && sy < a.end_symbol;
     if (has) {
       if (fast && aligned) {
-        if (MOD == 8)
-          *reinterpret_cast<uint2*>(q) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-        else if (MOD == 6) {
-          uint16_t* q2 = reinterpret_cast<uint16_t*>(q);
-          q2[0] = (uint16_t)w, q2[1] = (uint16_t)(w >> 16), q2[2] = (uint16_t)(w >> 32);
-        } else if (MOD == 4)
-          *reinterpret_cast<uint32_t*>(q) = (uint32_t)w;
-        else
-          *reinterpret_cast<uint16_t*>(q) = (uint16_t)w;
-      } else {
+        demod_store<MOD>(w, q, true);
+      } else { // (rare: the exact sequence and bytes; taking w for a fast lane here costs the walk two more spilled registers)
         int l[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (fast)
           demod_symbol<MOD, true>(z_re, z_im, nv, re, tab, l);
         else
           demod_symbol<MOD, false>(z_re, z_im, nv, re, tab, l);
-#pragma unroll
-        for (int b = 0; b < MOD; ++b) {
-          const int m = -(int)((bits >> b) & 1u);
-          q[b]        = (int8_t)((l[b] ^ m) - m);
-        }
+        demod_store<MOD>(demod_descramble_pack<MOD>(l, bits), q, false);
       }
     }
     if (sy < a.end_symbol)
@@ -425,20 +487,12 @@ __device__ __forceinline__ void demod_columns(const demod_args& a, bool active, 
       const bool     fast = fabsf(z_re) < INFINITY && fabsf(z_im) < INFINITY && rcp_chk < INFINITY;
       const unsigned re   = (unsigned)(prefix + r); // index of the element in the codeword
       int8_t*        q    = a.llr + (size_t)re * MOD;
-      const bool     aligned = ((uintptr_t)(a.llr + (size_t)prefix * MOD) % (MOD == 8 ? 8 : MOD == 4 ? 4 : MOD == 1 ? 1 : 2)) == 0;
+      const bool     aligned = demod_aligned<MOD>(a.llr + (size_t)prefix * MOD); // uniform
       // descrambling chips: bit b of this element is sequence bit re * MOD + b (window requested one symbol ahead)
       uint32_t bits = (uint32_t)(two >> ((re * (uint32_t)MOD) & 31u));
-      if (MOD >= 2 && fast && aligned && !a.evm_part && !a.nph) { // the common case: quantise, descramble and pack in one go
-        const uint64_t w = demod_symbol_packed<MOD>(z_re, z_im, nv, tab, bits);
-        if (MOD == 8)
-          *reinterpret_cast<uint2*>(q) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-        else if (MOD == 6) {
-          uint16_t* q2 = reinterpret_cast<uint16_t*>(q);
-          q2[0] = (uint16_t)w, q2[1] = (uint16_t)(w >> 16), q2[2] = (uint16_t)(w >> 32);
-        } else if (MOD == 4)
-          *reinterpret_cast<uint32_t*>(q) = (uint32_t)w;
-        else
-          *reinterpret_cast<uint16_t*>(q) = (uint16_t)w;
+      uint64_t w;
+      if (MOD >= 2 && fast && !a.evm_part && !a.nph) { // the common case: quantise, descramble and pack in one go
+        w = demod_symbol_packed<MOD>(z_re, z_im, nv, tab, bits);
       } else {
         int l[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (fast)
@@ -454,87 +508,16 @@ __device__ __forceinline__ void demod_columns(const demod_args& a, bool active, 
           const float  er = id.x - z_re, ei = id.y - z_im;
           evm_acc         = er * er + ei * ei;
         }
-        if (a.nph) { // binary search of this element in the placeholder list (pusch_demodulator_impl.cpp:117-149)
-          int  lo = 0, hi = a.nph - 1;
-          bool found = false;
-          while (lo <= hi) {
-            const int      mid = (lo + hi) >> 1;
-            const unsigned v   = a.ph[mid];
-            if (v == re) {
-              found = true;
-              break;
-            }
-            if (v < re)
-              lo = mid + 1;
-            else
-              hi = mid - 1;
-          }
-          if (found)
-            bits = (bits & 1u) ? 3u : 0u; // y repeats the chip of bit 0, the x placeholders behind it are not scrambled
-        }
-#pragma unroll
-        for (int b = 0; b < MOD; ++b) {
-          const int m = -(int)((bits >> b) & 1u); // 0 / -1
-          l[b]        = (l[b] ^ m) - m;
-        }
-        uint64_t w = 0;
-#pragma unroll
-        for (int b = 0; b < MOD; ++b)
-          w |= (uint64_t)(uint8_t)(int8_t)l[b] << (8 * b);
-        if (aligned) {
-          if (MOD == 8)
-            *reinterpret_cast<uint2*>(q) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-          else if (MOD == 6) {
-            uint16_t* q2 = reinterpret_cast<uint16_t*>(q);
-            q2[0] = (uint16_t)w, q2[1] = (uint16_t)(w >> 16), q2[2] = (uint16_t)(w >> 32);
-          } else if (MOD == 4)
-            *reinterpret_cast<uint32_t*>(q) = (uint32_t)w;
-          else if (MOD == 2)
-            *reinterpret_cast<uint16_t*>(q) = (uint16_t)w;
-          else
-            q[0] = (int8_t)w;
-        } else {
-#pragma unroll
-          for (int b = 0; b < MOD; ++b)
-            q[b] = (int8_t)(w >> (8 * b));
-        }
+        if (demod_is_placeholder(a, re))
+          bits = (bits & 1u) ? 3u : 0u; // y repeats the chip of bit 0, the x placeholders behind it are not scrambled
+        w = demod_descramble_pack<MOD>(l, bits);
       }
+      demod_store<MOD>(w, q, aligned);
     }
-    if (a.evm_part && npp != 0) { // deterministic order: wavefront shuffle tree, then the four wavefronts in sequence (uniform branch)
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1)
-        evm_acc += __shfl_xor(evm_acc, off);
-      __syncthreads();
-      if ((tid & 63) == 0)
-        evm_red[tid >> 6] = evm_acc;
-      __syncthreads();
-      if (tid == 0)
-        a.evm_part[sy * DEMOD_MAX_CHUNKS + blockIdx.y] = ((evm_red[0] + evm_red[1]) + evm_red[2]) + evm_red[3];
-    }
+    if (a.evm_part && npp != 0) // uniform
+      demod_evm_sum(a, sy, evm_acc, evm_red, tid);
     prefix += a.nprb * npp;
   }
-}
-
-// Scrambling sequence of every transmission, one workgroup each: c(0 .. nof_llr - 1) from c_init = rnti * 2^15 + n_id, x1 from the
-// table, x2 by the doubling word recurrence (gold_device.h). The OFDM symbols of a transmission use consecutive pieces of it, so no
-// jump-ahead is needed; inside the demodulator the generation was a serial chain that held three of four wavefronts of every
-// (transmission, symbol) workgroup at a barrier (0.13 of 0.37 ms per 1024 slots). seq: [transmission][SEQ_STRIDE] words.
-constexpr int SEQ_STRIDE = GOLD_X1_WORDS;
-#ifndef SCR_THREADS
-#define SCR_THREADS 512
-#endif
-__global__ void __launch_bounds__(SCR_THREADS) pusch_scrambling_kernel(const miphy_pusch_demod_job* __restrict__ jobs, const gold_tables* __restrict__ gt,
-                                                                uint32_t* __restrict__ seq)
-{
-  __shared__ uint32_t w[SEQ_STRIDE];
-  const miphy_pusch_demod_job* __restrict__ jp = jobs + blockIdx.x;
-  const int tid = threadIdx.x, nt = blockDim.x;
-  int       nwords = (int)((jp->nof_llr + 31u) >> 5) + 2; // + the 64-bit window of the last resource element
-  nwords           = nwords > SEQ_STRIDE ? SEQ_STRIDE : nwords;
-  gold_x2_sequence(*gt, (jp->rnti << 15) + jp->n_id, nwords, w, tid, nt);
-  uint32_t* o = seq + (size_t)blockIdx.x * SEQ_STRIDE;
-  for (int i = tid; i < nwords; i += nt)
-    o[i] = w[i] ^ gt->x1_seq[i];
 }
 
 // The descriptor as 30 dwords in scalar registers: its sub-dword fields read one by one become VECTOR byte / short loads with a wait
@@ -554,6 +537,11 @@ struct demod_job_words {
   __device__ __forceinline__ unsigned dmrs_symbols_mask() const { return w[5] & 0xffffu; }
   __device__ __forceinline__ int      grid_nof_prb() const { return (int)(w[5] >> 16); }
   __device__ __forceinline__ uint64_t rb_mask(int k) const { return (uint64_t)w[8 + 2 * k] | ((uint64_t)w[9 + 2 * k] << 32); }
+  __device__ __forceinline__ int      nof_prb() const // allocated PRBs
+  {
+    const uint64_t m[5] = {rb_mask(0), rb_mask(1), rb_mask(2), rb_mask(3), rb_mask(4)};
+    return (int)miphy_count_prb(m, (unsigned)grid_nof_prb());
+  }
   __device__ __forceinline__ uint64_t grid_offset() const { return (uint64_t)w[18] | ((uint64_t)w[19] << 32); }
   __device__ __forceinline__ uint64_t ce_offset() const { return (uint64_t)w[20] | ((uint64_t)w[21] << 32); }
   __device__ __forceinline__ uint64_t scalars_offset() const { return (uint64_t)w[22] | ((uint64_t)w[23] << 32); }
@@ -576,8 +564,8 @@ __device__ __forceinline__ demod_job_words demod_load_job(const miphy_pusch_demo
   return j;
 }
 
-// Allocated PRBs of a job: count and, for the lanes of a workgroup, the compact list prb_of[rank] (LDS). Uniform result.
-__device__ __forceinline__ int demod_prb_list(const demod_job_words& j, uint64_t* rbm, uint16_t* prb_of, int* nprb_s, int tid, int nt)
+// Allocated PRBs of a job for the lanes of a workgroup: the compact list prb_of[rank] (LDS).
+__device__ __forceinline__ void demod_prb_list(const demod_job_words& j, uint64_t* rbm, uint16_t* prb_of, int tid, int nt)
 {
   const int nprb_grid = j.grid_nof_prb();
   if (tid == 0) {
@@ -596,54 +584,313 @@ __device__ __forceinline__ int demod_prb_list(const demod_job_words& j, uint64_t
       prb_of[idx] = (uint16_t)r;
     }
   }
-  int c = 0; // uniform: scalar popcounts
-#pragma unroll
-  for (int w = 0; w < 5; ++w) {
-    const int left = nprb_grid - 64 * w;
-    if (left > 0)
-      c += __popcll(j.rb_mask(w) & (left >= 64 ? ~0ull : ((1ull << left) - 1ull)));
-  }
-  (void)nprb_s;
   __syncthreads();
-  return c;
+}
+
+// Per-symbol EVM sums of a transmission from the per-chunk partials, chunks added in order (deterministic); symbols without data: 0.
+// part: the transmission's [14][DEMOD_MAX_CHUNKS] partials.
+__device__ __forceinline__ void evm_reduce_symbol(const miphy_pusch_demod_job* __restrict__ jp, const float* __restrict__ part, float* __restrict__ evm_sums, int sy)
+{
+  const int      nprb  = (int)miphy_count_prb(jp->rb_mask, jp->grid_nof_prb);
+  const unsigned dmask = dmrs_prb_mask(jp->dmrs_type, jp->nof_cdm_groups_without_data);
+  const int      npp   = ((jp->dmrs_symbols_mask >> sy) & 1) ? 12 - __popc(dmask) : 12;
+  float          s     = 0.f;
+  if (sy >= jp->start_symbol && sy < jp->start_symbol + jp->nof_symbols && npp != 0) {
+    const int    nch = (nprb * 12 + DEMOD_THREADS - 1) / DEMOD_THREADS;
+    const float* p   = part + (size_t)sy * DEMOD_MAX_CHUNKS;
+    for (int c = 0; c < nch; ++c)
+      s += p[c];
+  }
+  evm_sums[jp->evm_offset + sy] = s;
+}
+
+// ------------------------------------------------------------------------------------------------ one codeword on 1..4 transmit layers
+// Beyond the 23.5 reference (pusch_demodulator_impl.h asserts one layer): L x P zero forcing (equalize_device.h) and the layer demapping of
+// TS 38.211 6.3.1.3 -- element i of layer ly is codeword symbol L i + ly -- in front of the same soft demapper and descrambler.
+
+// Data elements per layer of a job whose fields hold the rules below (popcounts: the kernels evaluate it once per workgroup).
+__host__ __device__ __forceinline__ unsigned pusch_demod_count_re(const miphy_pusch_demod_job& j)
+{
+  const unsigned dm = (j.dmrs_type == 1 ? 6u : 4u) * j.nof_cdm_groups_without_data; // DM-RS elements per PRB (dmrs_prb_mask)
+  const unsigned nprb = miphy_count_prb(j.rb_mask, j.grid_nof_prb);
+  unsigned       nsym_dmrs = 0;
+  for (unsigned s = j.start_symbol; s < (unsigned)j.start_symbol + j.nof_symbols; ++s)
+    nsym_dmrs += (j.dmrs_symbols_mask >> s) & 1u;
+  return nprb * (12u * (j.nof_symbols - nsym_dmrs) + (12u - dm) * nsym_dmrs);
+}
+
+// The two records of a job, miphy_pusch_demod_job and miphy_pusch_demod_layers_job: the base record and the layer count. A base record is on one layer.
+__host__ __device__ __forceinline__ const miphy_pusch_demod_job& pusch_demod_base(const miphy_pusch_demod_job& job) { return job; }
+__host__ __device__ __forceinline__ const miphy_pusch_demod_job& pusch_demod_base(const miphy_pusch_demod_layers_job& job) { return job.base; }
+__host__ __device__ __forceinline__ unsigned pusch_demod_layers(const miphy_pusch_demod_job&) { return 1; }
+__host__ __device__ __forceinline__ unsigned pusch_demod_layers(const miphy_pusch_demod_layers_job& job) { return job.nof_tx_layers; }
+
+// What a job (j = its base record, L = its layers) must satisfy, once, evaluated in this order: R(condition, message of the host, its arguments).
+// The host refuses a job that breaks a rule with the rule's message; the kernels skip a device-resident layered job that does
+// (pusch_demod_layers_job_ok), and take a device-resident base record as it is.
+// have_ph: the call came with a placeholder list (never through miphy_pusch_demodulate_layers_batch); ex: the host's entry point is an _ex one.
+#define PUSCH_DEMOD_LAYERS_RULES(R)                                                                                                                    \
+  R(L >= 1 && L <= 4, "invalid number of transmit layers %u", L)                                                                                      \
+  R(j.nof_rx_ports >= 1 && j.nof_rx_ports <= 4, "invalid number of receive ports")                                                                    \
+  R(L <= j.nof_rx_ports, "%u transmit layers on %u receive ports", L, (unsigned)j.nof_rx_ports)                                                       \
+  R(j.mod == 1 || j.mod == 2 || j.mod == 4 || j.mod == 6 || j.mod == 8, "invalid modulation order %u", (unsigned)j.mod)                               \
+  R(j.nof_symbols >= 1 && j.start_symbol + j.nof_symbols <= 14, "invalid time allocation")                                                            \
+  R(j.ce_compact || (j.ce_nof_symbols >= j.start_symbol + j.nof_symbols && j.ce_nof_symbols <= 14), "channel estimate too short")                     \
+  R(j.dmrs_type == 1 || j.dmrs_type == 2, "invalid DM-RS type")                                                                                       \
+  R(j.nof_cdm_groups_without_data >= 1 && j.nof_cdm_groups_without_data <= (j.dmrs_type == 1 ? 2 : 3), "invalid number of CDM groups without data")   \
+  R(j.grid_nof_prb >= 1 && j.grid_nof_prb <= 275, "invalid grid width")                                                                               \
+  R(j.n_id < 1024, "invalid scrambling identifier")                                                                                                   \
+  R(j.rnti < 65536, "invalid RNTI")                                                                                                                   \
+  R(j.nof_placeholders == 0 || (have_ph && j.mod >= 2), "%s",                                                                                         \
+    ex ? "placeholders need the list and a modulation order of at least 2" : "UCI placeholders are not supported on this entry point")                \
+  /* pusch_demodulator_impl.cpp:76-80: the codeword length must match the number of data REs */                                                       \
+  R(j.nof_llr == pusch_demod_count_re(j) * L * j.mod, "%u LLRs requested, the allocation holds %u on %u layers", j.nof_llr,                           \
+    pusch_demod_count_re(j) * L * j.mod, L)
+
+__host__ __device__ __forceinline__ bool pusch_demod_layers_job_ok(const miphy_pusch_demod_layers_job& lj, bool have_ph)
+{
+  const miphy_pusch_demod_job& j = lj.base;
+  const unsigned               L = lj.nof_tx_layers;
+#define PUSCH_RULE_HOLDS(cond, ...) &&(cond)
+  return true PUSCH_DEMOD_LAYERS_RULES(PUSCH_RULE_HOLDS);
+#undef PUSCH_RULE_HOLDS
+}
+__device__ __forceinline__ bool pusch_demod_layers_job_ok(const miphy_pusch_demod_job&, bool) { return true; } // (a base record is not checked on the device)
+
+// Per-symbol EVM sums of every transmission; a job the demodulator skipped keeps its 14 floats.
+template <typename JOB>
+__global__ void __launch_bounds__(64) pusch_evm_reduce_kernel(const JOB* __restrict__ jobs, const float* __restrict__ evm_part, float* __restrict__ evm_sums, bool have_ph)
+{
+  if (threadIdx.x < 14 && pusch_demod_layers_job_ok(jobs[blockIdx.x], have_ph))
+    evm_reduce_symbol(&pusch_demod_base(jobs[blockIdx.x]), evm_part + (size_t)blockIdx.x * 14 * DEMOD_MAX_CHUNKS, evm_sums, threadIdx.x);
+}
+
+// Scrambling sequence of every transmission: c(0 .. nof_llr - 1) from c_init = rnti * 2^15 + n_id. The OFDM symbols of a transmission use
+// consecutive pieces of it, so no jump-ahead is needed; inside the demodulator the generation was a serial chain that held three of four
+// wavefronts of every (transmission, symbol) workgroup at a barrier (0.13 of 0.37 ms per 1024 slots).
+// A sequence of up to SEQ_STRIDE words (every one-layer transmission) fits the x1 table and one workgroup's LDS: workgroup (transmission, 0) makes it
+// whole, x1 from the table, x2 by the doubling word recurrence (gold_device.h). A layered transmission has up to four times as much: a longer sequence
+// is made in pieces of SEQ_PIECE words, workgroup (transmission, piece) jumping both shift registers to the piece's first bit (gold_piece).
+// seq: [transmission][stride] words; a call with base records has stride = SEQ_STRIDE and one workgroup per transmission.
+constexpr int SEQ_STRIDE = GOLD_X1_WORDS;
+constexpr int SEQ_PIECE  = SEQ_STRIDE / 2;
+#ifndef SCR_THREADS
+#define SCR_THREADS 512
+#endif
+template <typename JOB>
+__global__ void __launch_bounds__(SCR_THREADS) pusch_seq_kernel(const JOB* __restrict__ jobs, const gold_tables* __restrict__ gt, uint32_t* __restrict__ seq,
+                                                                uint32_t stride, bool have_ph)
+{
+  __shared__ uint32_t w[SEQ_STRIDE]; // one sequence, or w1 | w2 of a piece
+  if (!pusch_demod_layers_job_ok(jobs[blockIdx.x], have_ph)) // uniform
+    return;
+  const miphy_pusch_demod_job* __restrict__ jp = &pusch_demod_base(jobs[blockIdx.x]);
+  const int      tid = threadIdx.x, nt = blockDim.x;
+  const int      nwords = min((int)((jp->nof_llr + 31u) >> 5) + 2, (int)stride); // + the 64-bit window of the last resource element
+  const uint32_t c_init = (jp->rnti << 15) + jp->n_id;
+  uint32_t*      o      = seq + (size_t)blockIdx.x * stride;
+  if (nwords <= SEQ_STRIDE) {
+    if (blockIdx.y != 0)
+      return;
+    gold_x2_sequence(*gt, c_init, nwords, w, tid, nt);
+    for (int i = tid; i < nwords; i += nt)
+      o[i] = w[i] ^ gt->x1_seq[i];
+    return;
+  }
+  const int first = (int)blockIdx.y * SEQ_PIECE;
+  if (first >= nwords)
+    return;
+  gold_piece(*gt, c_init, first, min(SEQ_PIECE, nwords - first), w, w + SEQ_PIECE, o + first, tid, nt);
+}
+
+// MOD soft bits of one equalised symbol, descrambled with the low MOD bits of `bits`, to q: the packed demapper where no NaN can appear, the exact
+// sequence otherwise; one wide store where q is aligned to it, bytes otherwise.
+template <int MOD>
+__device__ __forceinline__ void demod_emit(float re, float im, float nvar, unsigned sym_idx, uint32_t bits, const float2* tab, int8_t* q)
+{
+#pragma clang fp contract(off)
+  const float rcp_chk = (nvar > 0.f) ? 1.0f / nvar : 0.0f;
+  const bool  fast    = fabsf(re) < INFINITY && fabsf(im) < INFINITY && rcp_chk < INFINITY;
+  uint64_t    w       = 0;
+  bool        packed  = false;
+  if constexpr (MOD >= 2) {
+    if (fast) {
+      w      = demod_symbol_packed<MOD>(re, im, nvar, tab, bits);
+      packed = true;
+    }
+  }
+  if (!packed) {
+    int l[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (fast)
+      demod_symbol<MOD, true>(re, im, nvar, sym_idx, tab, l);
+    else
+      demod_symbol<MOD, false>(re, im, nvar, sym_idx, tab, l);
+    w = demod_descramble_pack<MOD>(l, bits);
+  }
+  demod_store<MOD>(w, q, demod_aligned<MOD>(q));
+}
+
+// The variant of demod_emit behind UCI placeholders and the EVM: always the exact sequence, whose soft bits l[] the EVM needs before they are
+// descrambled (as demod_columns does for such jobs; the bytes are those of demod_emit). placeholder: the symbol holds [c0 y x ..], bit 1 takes the
+// chip of bit 0 and the bits behind it none. Returns |hard-decided symbol - equalised symbol|^2 (evm_calculator_generic_impl.cpp:31-47).
+template <int MOD>
+__device__ __forceinline__ float demod_emit_exact(float re, float im, float nvar, unsigned sym_idx, uint32_t bits, bool placeholder, const float2* tab, int8_t* q)
+{
+#pragma clang fp contract(off)
+  const float rcp_chk = (nvar > 0.f) ? 1.0f / nvar : 0.0f;
+  const bool  fast    = fabsf(re) < INFINITY && fabsf(im) < INFINITY && rcp_chk < INFINITY;
+  int         l[8]    = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (fast)
+    demod_symbol<MOD, true>(re, im, nvar, sym_idx, tab, l);
+  else
+    demod_symbol<MOD, false>(re, im, nvar, sym_idx, tab, l);
+  uint32_t hb = 0;
+#pragma unroll
+  for (int b = 0; b < MOD; ++b)
+    hb |= (uint32_t)(l[b] <= 0) << b;
+  const float2 id = map_symbol(MOD, hb, sym_idx);
+  const float  er = id.x - re, ei = id.y - im;
+  if (placeholder)
+    bits = (bits & 1u) ? 3u : 0u;
+  demod_store<MOD>(demod_descramble_pack<MOD>(l, bits), q, demod_aligned<MOD>(q));
+  return er * er + ei * ei;
+}
+
+// One thread = one allocated subcarrier walked over the OFDM symbols, as demod_columns: with the compact estimate zf_prepare runs once and its result
+// stays in registers, per element only the samples are loaded and zf_apply runs. The L symbols of an element are L consecutive symbols of the
+// codeword: L MOD consecutive bytes, descrambled with L MOD (<= 32) consecutive chips.
+// EX: for a batch with placeholders or EVM. The list is searched once per element: a listed element carries the pattern in each of its L codeword
+// symbols. EVM: the terms of an element's layers are added in layer order, then demod_evm_sum and (pusch_evm_reduce_kernel) the chunks in order, as
+// demod_columns does, so a symbol's sum has one value. Every thread of the workgroup reaches the barriers of the sum; without EX a lane that owns
+// no subcarrier leaves at once.
+template <int MOD, int L, bool EX>
+__device__ __forceinline__ void demod_layers_columns(const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab, float* evm_red, int tid)
+{
+#pragma clang fp contract(off)
+  const int  nsc = a.nsc, np = a.nports;
+  const bool compact = a.ce_nof_symbols == 1;
+  float2     h[L][4];
+#pragma unroll
+  for (int l = 0; l < L; ++l)
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      h[l][p] = make_float2(0.f, 0.f);
+  auto load_h = [&](int row) { // estimate [layer][rx port][ce_nof_symbols][nsc]
+#pragma unroll
+    for (int l = 0; l < L; ++l)
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        if (p < np)
+          h[l][p] = a.ce[((size_t)(l * np + p) * a.ce_nof_symbols + row) * nsc + sc];
+  };
+  zf_prepared<L> q;
+  if (!EX && !active)
+    return;
+  if (active && compact) {
+    load_h(0);
+    zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
+  }
+  int prefix = a.prefix0; // data elements per layer of the transmission before the current symbol
+  for (int sy = a.start_symbol; sy < a.end_symbol; ++sy) { // (uniform)
+    const bool is_dmrs = (a.dmrs_syms >> sy) & 1;
+    const int  npp     = is_dmrs ? a.per_dm : 12;
+    const int  r       = is_dmrs ? (a.per_dm ? r_dm : -1) : a_idx;
+    float      evm_acc = 0.f;
+    if (active && r >= 0) {
+      float2 y[4], x[L];
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+        y[p] = (p < np) ? a.grid[((size_t)((a.rxp >> (8 * p)) & 0xffu) * 14 + sy) * nsc + sc] : make_float2(0.f, 0.f);
+      if (!compact) {
+        load_h(sy);
+        zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
+      }
+      zf_apply<L>(h, np, y, q, x);
+      const unsigned el   = (unsigned)(prefix + r);  // the element's index in the codeword, what the placeholder list holds
+      const uint32_t e0   = el * (uint32_t)L;        // first of the element's L codeword symbols
+      const uint32_t bo   = e0 * (uint32_t)MOD;
+      const uint64_t two  = (uint64_t)a.seq[bo >> 5] | ((uint64_t)a.seq[(bo >> 5) + 1] << 32);
+      const uint32_t bits = (uint32_t)(two >> (bo & 31u));
+      int8_t*        q0   = a.llr + (size_t)bo;
+      if constexpr (EX) {
+        const bool found = demod_is_placeholder(a, el);
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+          const float t = demod_emit_exact<MOD>(x[l].x, x[l].y, q.nvar[l], e0 + l, bits >> (l * MOD), found, tab, q0 + l * MOD);
+          evm_acc       = l ? evm_acc + t : t;
+        }
+      } else {
+#pragma unroll
+        for (int l = 0; l < L; ++l)
+          demod_emit<MOD>(x[l].x, x[l].y, q.nvar[l], e0 + l, bits >> (l * MOD), tab, q0 + l * MOD);
+      }
+    }
+    if constexpr (EX) {
+      if (a.evm_part && npp != 0) // uniform
+        demod_evm_sum(a, sy, evm_acc, evm_red, tid);
+    }
+    prefix += a.nprb * npp;
+  }
+}
+
+// ONE_LAYER: the one-layer walk (demod_columns), which follows the reference operation for operation; otherwise L = 2..4. EX: with placeholders and EVM.
+template <int MOD, bool ONE_LAYER, bool EX>
+__device__ __forceinline__ void demod_dispatch(int L, const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab, float* evm_red, int tid)
+{
+  if constexpr (ONE_LAYER) {
+    demod_columns<MOD>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+    return;
+  }
+  switch (L) { // uniform
+    case 2:
+      demod_layers_columns<MOD, 2, EX>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      break;
+    case 3:
+      demod_layers_columns<MOD, 3, EX>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      break;
+    default:
+      demod_layers_columns<MOD, 4, EX>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      break;
+  }
 }
 
 // grid (transmissions, chunks of 256 allocated subcarriers, parts of the OFDM symbols): a batch that fills the chip walks all symbols of a
 // chunk in one workgroup (the channel row is set up once); a small one (a single slot: 13 chunks) is cut along the symbols as well, which
-// shortens the dependent walk of every thread.
+// shortens the dependent walk of every thread. seq: [transmission][stride] words. evm_part: [transmission][14][DEMOD_MAX_CHUNKS].
+// JOB: miphy_pusch_demod_job or miphy_pusch_demod_layers_job. The jobs of a batch go to up to two instances: ONE_LAYER takes those on one layer
+// (every base record), the other those on two to four layers (four 4 x 4 matrices in registers: a lower occupancy); a workgroup leaves at once when
+// the job belongs to the other instance.
+// EX: the instances of a call with a placeholder list or EVM sums, which take the exact demapper; the others never see `placeholders` and `evm_part`,
+// so the throughput path keeps its registers.
 #ifndef DEMOD_MIN_WAVES
 #define DEMOD_MIN_WAVES 6 // 80 registers (four of them spilled outside the walk): 0.207 against 0.214 ms per 1024 slots at five
 #endif
-__global__ void __launch_bounds__(DEMOD_THREADS, DEMOD_MIN_WAVES) pusch_demod_kernel(const miphy_pusch_demod_job* __restrict__ jobs, const float2* __restrict__ grid,
-                                                                    const float2* __restrict__ ce, const float* __restrict__ scalars,
-                                                                    int8_t* __restrict__ llr, const uint16_t* __restrict__ placeholders,
-                                                                    float* __restrict__ evm_part, const uint32_t* __restrict__ seq)
+template <typename JOB, bool ONE_LAYER, bool EX>
+__global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1) pusch_demod_kernel(const JOB* __restrict__ jobs, const float2* __restrict__ grid,
+                                                                                     const float2* __restrict__ ce, const float* __restrict__ scalars,
+                                                                                     int8_t* __restrict__ llr, const uint32_t* __restrict__ seq, uint32_t stride,
+                                                                                     const uint16_t* __restrict__ placeholders, float* __restrict__ evm_part)
 {
   __shared__ uint16_t prb_of[276];
-  __shared__ int      nprb_s;
   __shared__ float2   tab[64];
   __shared__ uint64_t rbm[5];
   __shared__ float    evm_red[4];
-  const demod_job_words j    = demod_load_job(jobs + blockIdx.x);
+  const int L = (int)pusch_demod_layers(jobs[blockIdx.x]);
+  if ((L == 1) != ONE_LAYER) // uniform
+    return;
+  if (!pusch_demod_layers_job_ok(jobs[blockIdx.x], EX && placeholders)) // uniform: a device-resident job the host has not seen is skipped
+    return;
+  const demod_job_words j    = demod_load_job(&pusch_demod_base(jobs[blockIdx.x]));
   const int             tid  = threadIdx.x;
-  { // A chunk behind the allocation leaves before it has requested or built anything (the grid is sized for the widest allocation of the
-    // batch: in a slot shared by eight UEs most workgroups of the narrow ones are such chunks). Scalar popcounts of the descriptor words.
-    int c = 0;
-#pragma unroll
-    for (int w = 0; w < 5; ++w) {
-      const int left = j.grid_nof_prb() - 64 * w;
-      if (left > 0)
-        c += __popcll(j.rb_mask(w) & (left >= 64 ? ~0ull : ((1ull << left) - 1ull)));
-    }
-    if ((int)blockIdx.y * DEMOD_THREADS >= c * 12)
-      return; // uniform
-  }
-  const demod_tab_entry te   = demod_table_entry(j.mod(), tid);            // requested now, stored behind the PRB list
-  const float           noise_var_early = scalars[j.scalars_offset() + 2]; // likewise
-  const int             nprb = demod_prb_list(j, rbm, prb_of, &nprb_s, tid, DEMOD_THREADS);
-  demod_table_store(tab, te); // (made visible by the barrier in front of the walk; a workgroup that leaves below needs no table)
+  const int             nprb = j.nof_prb(); // scalar popcounts of the descriptor words
+  // A chunk behind the allocation leaves before it has requested or built anything (the grid is sized for the widest allocation of the
+  // batch: in a slot shared by eight UEs most workgroups of the narrow ones are such chunks).
   if ((int)blockIdx.y * DEMOD_THREADS >= nprb * 12)
     return; // uniform
+  const demod_tab_entry te        = demod_table_entry(j.mod(), tid);            // requested now, stored behind the PRB list
+  const float           noise_var = scalars[j.scalars_offset() + 2]; // likewise
+  demod_prb_list(j, rbm, prb_of, tid, DEMOD_THREADS);
+  demod_table_store(tab, te); // (made visible by the barrier in front of the walk)
   const unsigned dmask = dmrs_prb_mask(j.dmrs_type(), j.cdm_groups());
   demod_args     a;
   a.per_dm         = 12 - __popc(dmask);
@@ -669,478 +916,6 @@ __global__ void __launch_bounds__(DEMOD_THREADS, DEMOD_MIN_WAVES) pusch_demod_ke
   a.grid           = grid + j.grid_offset();
   a.ce             = ce + j.ce_offset();
   a.llr            = llr + j.llr_offset();
-  a.noise_var      = noise_var_early;
-  a.nph            = placeholders ? (int)j.nof_placeholders() : 0;
-  a.ph             = placeholders ? placeholders + j.placeholders_offset() : nullptr;
-  a.evm_part       = evm_part ? evm_part + (size_t)blockIdx.x * 14 * DEMOD_MAX_CHUNKS : nullptr;
-  a.seq            = seq + (size_t)blockIdx.x * SEQ_STRIDE;
-  // this thread's subcarrier
-  const int  a_idx  = (int)blockIdx.y * DEMOD_THREADS + tid;
-  const bool active = a_idx < nprb * 12;
-  const int  pr     = a_idx / 12, k = a_idx - 12 * pr;
-  const int  sc     = active ? (int)prb_of[pr] * 12 + k : 0;
-  const int  r_dm   = ((dmask >> k) & 1u) ? -1 : pr * a.per_dm + __popc(~dmask & ((1u << k) - 1u));
-  const int  mod    = j.mod();
-  __syncthreads(); // interval tables in LDS
-  switch (mod) {
-    case 8:
-      demod_columns<8>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
-      break;
-    case 6:
-      demod_columns<6>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
-      break;
-    case 4:
-      demod_columns<4>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
-      break;
-    case 2:
-      demod_columns<2>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
-      break;
-    default:
-      demod_columns<1>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
-      break;
-  }
-}
-
-// Per-symbol EVM sums of a transmission from the per-chunk partials, chunks added in order (deterministic); symbols without data: 0.
-// part: the transmission's [14][DEMOD_MAX_CHUNKS] partials.
-__device__ __forceinline__ void evm_reduce_symbol(const miphy_pusch_demod_job* __restrict__ jp, const float* __restrict__ part, float* __restrict__ evm_sums, int sy)
-{
-  int nprb = 0;
-  for (int w = 0; w < 5; ++w) {
-    const int left = (int)jp->grid_nof_prb - 64 * w;
-    if (left > 0)
-      nprb += __popcll(jp->rb_mask[w] & (left >= 64 ? ~0ull : ((1ull << left) - 1ull)));
-  }
-  const unsigned dmask = dmrs_prb_mask(jp->dmrs_type, jp->nof_cdm_groups_without_data);
-  const int      npp   = ((jp->dmrs_symbols_mask >> sy) & 1) ? 12 - __popc(dmask) : 12;
-  float          s     = 0.f;
-  if (sy >= jp->start_symbol && sy < jp->start_symbol + jp->nof_symbols && npp != 0) {
-    const int    nch = (nprb * 12 + DEMOD_THREADS - 1) / DEMOD_THREADS;
-    const float* p   = part + (size_t)sy * DEMOD_MAX_CHUNKS;
-    for (int c = 0; c < nch; ++c)
-      s += p[c];
-  }
-  evm_sums[jp->evm_offset + sy] = s;
-}
-__global__ void __launch_bounds__(64) pusch_evm_reduce_kernel(const miphy_pusch_demod_job* __restrict__ jobs, const float* __restrict__ evm_part,
-                                                              float* __restrict__ evm_sums)
-{
-  if (threadIdx.x < 14)
-    evm_reduce_symbol(jobs + blockIdx.x, evm_part + (size_t)blockIdx.x * 14 * DEMOD_MAX_CHUNKS, evm_sums, threadIdx.x);
-}
-
-// ------------------------------------------------------------------------------------------------ one codeword on 1..4 transmit layers
-// Beyond the 23.5 reference (pusch_demodulator_impl.h asserts one layer): L x P zero forcing (equalize_device.h) and the layer demapping of
-// TS 38.211 6.3.1.3 -- element i of layer ly is codeword symbol L i + ly -- in front of the same soft demapper and descrambler.
-
-// Data elements per layer of a job whose fields hold the rules below (popcounts: the kernels evaluate it once per workgroup).
-__host__ __device__ __forceinline__ unsigned pusch_demod_count_re(const miphy_pusch_demod_job& j)
-{
-  const unsigned dm = (j.dmrs_type == 1 ? 6u : 4u) * j.nof_cdm_groups_without_data; // DM-RS elements per PRB (dmrs_prb_mask)
-  unsigned nprb = 0;
-  for (int w = 0; w < 5; ++w) {
-    const int left = (int)j.grid_nof_prb - 64 * w;
-    if (left > 0) {
-      const uint64_t m = j.rb_mask[w] & (left >= 64 ? ~0ull : ((1ull << left) - 1ull));
-#ifdef __HIP_DEVICE_COMPILE__
-      nprb += (unsigned)__popcll(m);
-#else
-      nprb += (unsigned)__builtin_popcountll(m);
-#endif
-    }
-  }
-  unsigned nsym_dmrs = 0;
-  for (unsigned s = j.start_symbol; s < (unsigned)j.start_symbol + j.nof_symbols; ++s)
-    nsym_dmrs += (j.dmrs_symbols_mask >> s) & 1u;
-  return nprb * (12u * (j.nof_symbols - nsym_dmrs) + (12u - dm) * nsym_dmrs);
-}
-
-// What a layered job (j = its base, L = its layers) must satisfy, once, evaluated in this order: R(condition, message of the host, its arguments).
-// The kernels skip a device-resident job that breaks a rule (pusch_demod_layers_job_ok), the host refuses one with the rule's message.
-// have_ph: the call came with a placeholder list (never through miphy_pusch_demodulate_layers_batch); ex: the host's entry point is the _ex one.
-#define PUSCH_DEMOD_LAYERS_RULES(R)                                                                                                                    \
-  R(L >= 1 && L <= 4, "invalid number of transmit layers %u", L)                                                                                      \
-  R(j.nof_rx_ports >= 1 && j.nof_rx_ports <= 4, "invalid number of receive ports")                                                                    \
-  R(L <= j.nof_rx_ports, "%u transmit layers on %u receive ports", L, (unsigned)j.nof_rx_ports)                                                       \
-  R(j.mod == 1 || j.mod == 2 || j.mod == 4 || j.mod == 6 || j.mod == 8, "invalid modulation order %u", (unsigned)j.mod)                               \
-  R(j.nof_symbols >= 1 && j.start_symbol + j.nof_symbols <= 14, "invalid time allocation")                                                            \
-  R(j.ce_compact || (j.ce_nof_symbols >= j.start_symbol + j.nof_symbols && j.ce_nof_symbols <= 14), "channel estimate too short")                     \
-  R(j.dmrs_type == 1 || j.dmrs_type == 2, "invalid DM-RS type")                                                                                       \
-  R(j.nof_cdm_groups_without_data >= 1 && j.nof_cdm_groups_without_data <= (j.dmrs_type == 1 ? 2 : 3), "invalid number of CDM groups without data")   \
-  R(j.grid_nof_prb >= 1 && j.grid_nof_prb <= 275, "invalid grid width")                                                                               \
-  R(j.n_id < 1024, "invalid scrambling identifier")                                                                                                   \
-  R(j.rnti < 65536, "invalid RNTI")                                                                                                                   \
-  R(j.nof_placeholders == 0 || (have_ph && j.mod >= 2), "%s",                                                                                         \
-    ex ? "placeholders need the list and a modulation order of at least 2" : "UCI placeholders are not supported on this entry point")                \
-  R(j.nof_llr == pusch_demod_count_re(j) * L * j.mod, "%u LLRs requested, the allocation holds %u on %u layers", j.nof_llr,                           \
-    pusch_demod_count_re(j) * L * j.mod, L)
-
-__host__ __device__ __forceinline__ bool pusch_demod_layers_job_ok(const miphy_pusch_demod_layers_job& lj, bool have_ph)
-{
-  const miphy_pusch_demod_job& j = lj.base;
-  const unsigned               L = lj.nof_tx_layers;
-#define PUSCH_RULE_HOLDS(cond, ...) &&(cond)
-  return true PUSCH_DEMOD_LAYERS_RULES(PUSCH_RULE_HOLDS);
-#undef PUSCH_RULE_HOLDS
-}
-
-// pusch_evm_reduce_kernel for layered jobs; a job the demodulator skipped keeps its 14 floats.
-__global__ void __launch_bounds__(64) pusch_evm_reduce_layers_kernel(const miphy_pusch_demod_layers_job* __restrict__ jobs, const float* __restrict__ evm_part,
-                                                                     float* __restrict__ evm_sums, bool have_ph)
-{
-  if (threadIdx.x < 14 && pusch_demod_layers_job_ok(jobs[blockIdx.x], have_ph))
-    evm_reduce_symbol(&jobs[blockIdx.x].base, evm_part + (size_t)blockIdx.x * 14 * DEMOD_MAX_CHUNKS, evm_sums, threadIdx.x);
-}
-
-// Scrambling sequence of a layered transmission: up to four times the x1 table and one workgroup's LDS. A sequence that fits both is made whole by
-// workgroup (transmission, 0) as pusch_scrambling_kernel makes it (x1 from the table, x2 from the basis and the doubling recurrence); a longer one in
-// pieces of SEQ_PIECE words, workgroup (transmission, piece) jumping both shift registers to the piece's first bit (gold_piece).
-// seq: [transmission][stride] words.
-constexpr int SEQ_PIECE = SEQ_STRIDE / 2;
-__global__ void __launch_bounds__(SCR_THREADS) pusch_seq_layers_kernel(const miphy_pusch_demod_layers_job* __restrict__ jobs, const gold_tables* __restrict__ gt,
-                                                               uint32_t* __restrict__ seq, uint32_t stride, bool have_ph)
-{
-  __shared__ uint32_t w[SEQ_STRIDE]; // one sequence, or w1 | w2 of a piece
-  const miphy_pusch_demod_layers_job* __restrict__ lj = jobs + blockIdx.x;
-  if (!pusch_demod_layers_job_ok(*lj, have_ph)) // uniform
-    return;
-  const int      tid = threadIdx.x, nt = blockDim.x;
-  const int      nwords = min((int)((lj->base.nof_llr + 31u) >> 5) + 2, (int)stride); // + the 64-bit window of the last resource element
-  const uint32_t c_init = (lj->base.rnti << 15) + lj->base.n_id;
-  uint32_t*      o      = seq + (size_t)blockIdx.x * stride;
-  if (nwords <= SEQ_STRIDE) {
-    if (blockIdx.y != 0)
-      return;
-    gold_x2_sequence(*gt, c_init, nwords, w, tid, nt);
-    for (int i = tid; i < nwords; i += nt)
-      o[i] = w[i] ^ gt->x1_seq[i];
-    return;
-  }
-  const int first = (int)blockIdx.y * SEQ_PIECE;
-  if (first >= nwords)
-    return;
-  gold_piece(*gt, c_init, first, min(SEQ_PIECE, nwords - first), w, w + SEQ_PIECE, o + first, tid, nt);
-}
-
-// MOD soft bits packed in w (LLR b in byte b) to q: one wide store where q is aligned to it, bytes otherwise.
-template <int MOD>
-__device__ __forceinline__ void demod_store(uint64_t w, int8_t* q)
-{
-  constexpr unsigned WIDTH = MOD == 8 ? 8 : MOD == 4 ? 4 : MOD == 1 ? 1 : 2;
-  if (((uintptr_t)q % WIDTH) == 0) {
-    if (MOD == 8)
-      *reinterpret_cast<uint2*>(q) = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-    else if (MOD == 6) {
-      uint16_t* q2 = reinterpret_cast<uint16_t*>(q);
-      q2[0] = (uint16_t)w, q2[1] = (uint16_t)(w >> 16), q2[2] = (uint16_t)(w >> 32);
-    } else if (MOD == 4)
-      *reinterpret_cast<uint32_t*>(q) = (uint32_t)w;
-    else if (MOD == 2)
-      *reinterpret_cast<uint16_t*>(q) = (uint16_t)w;
-    else
-      q[0] = (int8_t)w;
-  } else {
-#pragma unroll
-    for (int b = 0; b < MOD; ++b)
-      q[b] = (int8_t)(w >> (8 * b));
-  }
-}
-
-// MOD soft bits of one equalised symbol, descrambled with the low MOD bits of `bits`, to q: the packed demapper where no NaN can appear, the exact
-// sequence otherwise; one wide store where q is aligned to it, bytes otherwise.
-template <int MOD>
-__device__ __forceinline__ void demod_emit(float re, float im, float nvar, unsigned sym_idx, uint32_t bits, const float2* tab, int8_t* q)
-{
-#pragma clang fp contract(off)
-  const float rcp_chk = (nvar > 0.f) ? 1.0f / nvar : 0.0f;
-  const bool  fast    = fabsf(re) < INFINITY && fabsf(im) < INFINITY && rcp_chk < INFINITY;
-  uint64_t    w       = 0;
-  bool        packed  = false;
-  if constexpr (MOD >= 2) {
-    if (fast) {
-      w      = demod_symbol_packed<MOD>(re, im, nvar, tab, bits);
-      packed = true;
-    }
-  }
-  if (!packed) {
-    int l[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (fast)
-      demod_symbol<MOD, true>(re, im, nvar, sym_idx, tab, l);
-    else
-      demod_symbol<MOD, false>(re, im, nvar, sym_idx, tab, l);
-#pragma unroll
-    for (int b = 0; b < MOD; ++b) {
-      const int m = -(int)((bits >> b) & 1u); // 0 / -1
-      w |= (uint64_t)(uint8_t)(int8_t)((l[b] ^ m) - m) << (8 * b);
-    }
-  }
-  demod_store<MOD>(w, q);
-}
-
-// The variant of demod_emit behind UCI placeholders and the EVM: always the exact sequence, whose soft bits l[] the EVM needs before they are
-// descrambled (as demod_columns does for such jobs; the bytes are those of demod_emit). placeholder: the symbol holds [c0 y x ..], bit 1 takes the
-// chip of bit 0 and the bits behind it none. Returns |hard-decided symbol - equalised symbol|^2 (evm_calculator_generic_impl.cpp:31-47).
-template <int MOD>
-__device__ __forceinline__ float demod_emit_exact(float re, float im, float nvar, unsigned sym_idx, uint32_t bits, bool placeholder, const float2* tab, int8_t* q)
-{
-#pragma clang fp contract(off)
-  const float rcp_chk = (nvar > 0.f) ? 1.0f / nvar : 0.0f;
-  const bool  fast    = fabsf(re) < INFINITY && fabsf(im) < INFINITY && rcp_chk < INFINITY;
-  int         l[8]    = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (fast)
-    demod_symbol<MOD, true>(re, im, nvar, sym_idx, tab, l);
-  else
-    demod_symbol<MOD, false>(re, im, nvar, sym_idx, tab, l);
-  uint32_t hb = 0;
-#pragma unroll
-  for (int b = 0; b < MOD; ++b)
-    hb |= (uint32_t)(l[b] <= 0) << b;
-  const float2 id = map_symbol(MOD, hb, sym_idx);
-  const float  er = id.x - re, ei = id.y - im;
-  if (placeholder)
-    bits = (bits & 1u) ? 3u : 0u;
-  uint64_t w = 0;
-#pragma unroll
-  for (int b = 0; b < MOD; ++b) {
-    const int m = -(int)((bits >> b) & 1u); // 0 / -1
-    w |= (uint64_t)(uint8_t)(int8_t)((l[b] ^ m) - m) << (8 * b);
-  }
-  demod_store<MOD>(w, q);
-  return er * er + ei * ei;
-}
-
-// The variant of demod_layers_columns (below) for a batch with placeholders or EVM. The list is searched once per element: a listed element carries
-// the pattern in each of its L codeword symbols. EVM: the terms of an element's layers are added in layer order, then the wavefront shuffle tree,
-// the four wavefronts in sequence and (pusch_evm_reduce_layers_kernel) the chunks in order, as demod_columns does, so a symbol's sum has one value.
-template <int MOD, int L>
-__device__ __forceinline__ void demod_layers_columns_ex(const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab, float* evm_red, int tid)
-{
-#pragma clang fp contract(off)
-  const int  nsc = a.nsc, np = a.nports;
-  const bool compact = a.ce_nof_symbols == 1;
-  float2     h[L][4];
-#pragma unroll
-  for (int l = 0; l < L; ++l)
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-      h[l][p] = make_float2(0.f, 0.f);
-  auto load_h = [&](int row) { // estimate [layer][rx port][ce_nof_symbols][nsc]
-#pragma unroll
-    for (int l = 0; l < L; ++l)
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-        if (p < np)
-          h[l][p] = a.ce[((size_t)(l * np + p) * a.ce_nof_symbols + row) * nsc + sc];
-  };
-  zf_prepared<L> q;
-  if (active && compact) {
-    load_h(0);
-    zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
-  }
-  int prefix = a.prefix0; // data elements per layer of the transmission before the current symbol
-  for (int sy = a.start_symbol; sy < a.end_symbol; ++sy) { // (uniform: every thread of the workgroup reaches the barriers)
-    const bool is_dmrs = (a.dmrs_syms >> sy) & 1;
-    const int  npp     = is_dmrs ? a.per_dm : 12;
-    const int  r       = is_dmrs ? (a.per_dm ? r_dm : -1) : a_idx;
-    float      evm_acc = 0.f;
-    if (active && r >= 0) {
-      float2 y[4], x[L];
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-        y[p] = (p < np) ? a.grid[((size_t)((a.rxp >> (8 * p)) & 0xffu) * 14 + sy) * nsc + sc] : make_float2(0.f, 0.f);
-      if (!compact) {
-        load_h(sy);
-        zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
-      }
-      zf_apply<L>(h, np, y, q, x);
-      const unsigned el   = (unsigned)(prefix + r);  // the element's index in the codeword, what the placeholder list holds
-      const uint32_t e0   = el * (uint32_t)L;        // first of the element's L codeword symbols
-      const uint32_t bo   = e0 * (uint32_t)MOD;
-      const uint64_t two  = (uint64_t)a.seq[bo >> 5] | ((uint64_t)a.seq[(bo >> 5) + 1] << 32);
-      const uint32_t bits = (uint32_t)(two >> (bo & 31u));
-      int8_t*        q0   = a.llr + (size_t)bo;
-      bool           found = false;
-      for (int lo = 0, hi = a.nph - 1; lo <= hi;) { // binary search, as demod_columns
-        const int      mid = (lo + hi) >> 1;
-        const unsigned v   = a.ph[mid];
-        if (v == el) {
-          found = true;
-          break;
-        }
-        if (v < el)
-          lo = mid + 1;
-        else
-          hi = mid - 1;
-      }
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        const float t = demod_emit_exact<MOD>(x[l].x, x[l].y, q.nvar[l], e0 + l, bits >> (l * MOD), found, tab, q0 + l * MOD);
-        evm_acc       = l ? evm_acc + t : t;
-      }
-    }
-    if (a.evm_part && npp != 0) { // uniform
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1)
-        evm_acc += __shfl_xor(evm_acc, off);
-      __syncthreads();
-      if ((tid & 63) == 0)
-        evm_red[tid >> 6] = evm_acc;
-      __syncthreads();
-      if (tid == 0)
-        a.evm_part[sy * DEMOD_MAX_CHUNKS + blockIdx.y] = ((evm_red[0] + evm_red[1]) + evm_red[2]) + evm_red[3];
-    }
-    prefix += a.nprb * npp;
-  }
-}
-
-// One thread = one allocated subcarrier walked over the OFDM symbols, as demod_columns: with the compact estimate zf_prepare runs once and its result
-// stays in registers, per element only the samples are loaded and zf_apply runs. The L symbols of an element are L consecutive symbols of the
-// codeword: L MOD consecutive bytes, descrambled with L MOD (<= 32) consecutive chips.
-template <int MOD, int L>
-__device__ __forceinline__ void demod_layers_columns(const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab)
-{
-  const int  nsc = a.nsc, np = a.nports;
-  const bool compact = a.ce_nof_symbols == 1;
-  float2     h[L][4];
-#pragma unroll
-  for (int l = 0; l < L; ++l)
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-      h[l][p] = make_float2(0.f, 0.f);
-  auto load_h = [&](int row) { // estimate [layer][rx port][ce_nof_symbols][nsc]
-#pragma unroll
-    for (int l = 0; l < L; ++l)
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-        if (p < np)
-          h[l][p] = a.ce[((size_t)(l * np + p) * a.ce_nof_symbols + row) * nsc + sc];
-  };
-  zf_prepared<L> q;
-  if (!active)
-    return;
-  if (compact) {
-    load_h(0);
-    zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
-  }
-  int prefix = a.prefix0; // data elements per layer of the transmission before the current symbol
-  for (int sy = a.start_symbol; sy < a.end_symbol; ++sy) {
-    const bool is_dmrs = (a.dmrs_syms >> sy) & 1;
-    const int  npp     = is_dmrs ? a.per_dm : 12;
-    const int  r       = is_dmrs ? (a.per_dm ? r_dm : -1) : a_idx;
-    if (r >= 0) {
-      float2 y[4], x[L];
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-        y[p] = (p < np) ? a.grid[((size_t)((a.rxp >> (8 * p)) & 0xffu) * 14 + sy) * nsc + sc] : make_float2(0.f, 0.f);
-      if (!compact) {
-        load_h(sy);
-        zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
-      }
-      zf_apply<L>(h, np, y, q, x);
-      const uint32_t e0   = (uint32_t)(prefix + r) * (uint32_t)L; // first of the element's L codeword symbols
-      const uint32_t bo   = e0 * (uint32_t)MOD;
-      const uint64_t two  = (uint64_t)a.seq[bo >> 5] | ((uint64_t)a.seq[(bo >> 5) + 1] << 32);
-      const uint32_t bits = (uint32_t)(two >> (bo & 31u));
-      int8_t*        q0   = a.llr + (size_t)bo;
-#pragma unroll
-      for (int l = 0; l < L; ++l)
-        demod_emit<MOD>(x[l].x, x[l].y, q.nvar[l], e0 + l, bits >> (l * MOD), tab, q0 + l * MOD);
-    }
-    prefix += a.nprb * npp;
-  }
-}
-
-// ONE_LAYER: the one-layer walk itself (demod_columns), the bytes of miphy_pusch_demodulate_batch(_ex); otherwise L = 2..4, EX: with placeholders
-// and EVM.
-template <int MOD, bool ONE_LAYER, bool EX>
-__device__ __forceinline__ void demod_layers_dispatch(int L, const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab,
-                                                      float* evm_red, int tid)
-{
-  if constexpr (ONE_LAYER) {
-    demod_columns<MOD>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
-    return;
-  }
-  if constexpr (EX) {
-    switch (L) { // uniform
-      case 2:
-        demod_layers_columns_ex<MOD, 2>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
-        break;
-      case 3:
-        demod_layers_columns_ex<MOD, 3>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
-        break;
-      default:
-        demod_layers_columns_ex<MOD, 4>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
-        break;
-    }
-    return;
-  }
-  switch (L) { // uniform
-    case 2:
-      demod_layers_columns<MOD, 2>(a, active, sc, a_idx, r_dm, tab);
-      break;
-    case 3:
-      demod_layers_columns<MOD, 3>(a, active, sc, a_idx, r_dm, tab);
-      break;
-    default:
-      demod_layers_columns<MOD, 4>(a, active, sc, a_idx, r_dm, tab);
-      break;
-  }
-}
-
-// grid (transmissions, chunks of 256 allocated subcarriers, parts of the OFDM symbols), as pusch_demod_kernel. seq: [transmission][stride] words.
-// Two kernels share a batch: ONE_LAYER takes its jobs on one layer, with the registers and the occupancy of pusch_demod_kernel, the other those on
-// two to four layers (four 4 x 4 matrices in registers); a workgroup leaves at once when the job belongs to the other kernel.
-// EX: the instances of a call with a placeholder list or EVM sums (miphy_pusch_demodulate_layers_batch_ex), which take the exact demapper; the
-// other two never see `placeholders` and `evm_part`, so the throughput path keeps its registers. evm_part: [transmission][14][DEMOD_MAX_CHUNKS].
-template <bool ONE_LAYER, bool EX>
-__global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1) pusch_demod_layers_kernel(const miphy_pusch_demod_layers_job* __restrict__ jobs, const float2* __restrict__ grid,
-                                                                            const float2* __restrict__ ce, const float* __restrict__ scalars,
-                                                                            int8_t* __restrict__ llr, const uint32_t* __restrict__ seq, uint32_t stride,
-                                                                            const uint16_t* __restrict__ placeholders, float* __restrict__ evm_part)
-{
-  __shared__ uint16_t prb_of[276];
-  __shared__ int      nprb_s;
-  __shared__ float2   tab[64];
-  __shared__ uint64_t rbm[5];
-  __shared__ float    evm_red[4];
-  const int L = jobs[blockIdx.x].nof_tx_layers;
-  if ((L == 1) != ONE_LAYER) // uniform
-    return;
-  if (!pusch_demod_layers_job_ok(jobs[blockIdx.x], EX && placeholders)) // uniform: a device-resident job the host has not seen is skipped
-    return;
-  const demod_job_words j   = demod_load_job(&jobs[blockIdx.x].base);
-  const int             tid = threadIdx.x;
-  const demod_tab_entry te  = demod_table_entry(j.mod(), tid);
-  const float           noise_var = scalars[j.scalars_offset() + 2];
-  const int             nprb = demod_prb_list(j, rbm, prb_of, &nprb_s, tid, DEMOD_THREADS);
-  demod_table_store(tab, te);
-  if ((int)blockIdx.y * DEMOD_THREADS >= nprb * 12)
-    return; // uniform
-  const unsigned dmask = dmrs_prb_mask(j.dmrs_type(), j.cdm_groups());
-  demod_args     a;
-  a.per_dm       = 12 - __popc(dmask);
-  a.dmrs_syms    = j.dmrs_symbols_mask();
-  a.start_symbol = j.start_symbol();
-  a.end_symbol   = a.start_symbol + j.nof_symbols();
-  a.nprb         = nprb;
-  a.prefix0      = 0;
-  if (gridDim.z > 1) { // uniform
-    const int per = (a.end_symbol - a.start_symbol + (int)gridDim.z - 1) / (int)gridDim.z;
-    const int f = a.start_symbol + (int)blockIdx.z * per, l = min(a.end_symbol, f + per);
-    if (f >= l)
-      return;
-    for (int sy = a.start_symbol; sy < f; ++sy)
-      a.prefix0 += nprb * (((a.dmrs_syms >> sy) & 1u) ? a.per_dm : 12);
-    a.start_symbol = f;
-    a.end_symbol   = l;
-  }
-  a.nsc            = j.grid_nof_prb() * 12;
-  a.nports         = j.nof_rx_ports();
-  a.ce_nof_symbols = j.ce_compact() ? 1 : j.ce_nof_symbols();
-  a.rxp            = j.rx_ports();
-  a.grid           = grid + j.grid_offset();
-  a.ce             = ce + j.ce_offset();
-  a.llr            = llr + j.llr_offset();
   a.noise_var      = noise_var;
   a.nph            = 0;
   a.ph             = nullptr;
@@ -1151,6 +926,7 @@ __global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1
     a.evm_part = evm_part ? evm_part + (size_t)blockIdx.x * 14 * DEMOD_MAX_CHUNKS : nullptr;
   }
   a.seq            = seq + (size_t)blockIdx.x * stride;
+  // this thread's subcarrier
   const int  a_idx  = (int)blockIdx.y * DEMOD_THREADS + tid;
   const bool active = a_idx < nprb * 12;
   const int  pr     = a_idx / 12, k = a_idx - 12 * pr;
@@ -1159,43 +935,37 @@ __global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1
   __syncthreads(); // interval tables in LDS
   switch (j.mod()) {
     case 8:
-      demod_layers_dispatch<8, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_dispatch<8, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
       break;
     case 6:
-      demod_layers_dispatch<6, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_dispatch<6, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
       break;
     case 4:
-      demod_layers_dispatch<4, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_dispatch<4, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
       break;
     case 2:
-      demod_layers_dispatch<2, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_dispatch<2, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
       break;
     default:
-      demod_layers_dispatch<1, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_dispatch<1, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
       break;
   }
 }
 
-} // namespace
-
-extern "C" uint32_t miphy_pusch_demod_layers_nof_llr(const miphy_pusch_demod_layers_job* lj)
+// All four entry points: `who` names the entry in the messages, ex: it is an _ex one (only the message of the placeholder rule depends on it). The EX
+// instances run when the call has EVM sums or a job with placeholders; device-resident jobs cannot be looked at, there the two pointers decide.
+template <typename JOB>
+int pusch_demodulate(const char* who, miphy_ctx* ctx, const JOB* jobs, int jobs_on_device, uint32_t n, const float* grid, const float* ce, const float* scalars,
+                     int8_t* llr, const uint16_t* placeholders, float* evm_sums, bool ex, void* stream)
 {
-  if (!lj || lj->nof_tx_layers < 1 || lj->nof_tx_layers > 4 || lj->nof_tx_layers > lj->base.nof_rx_ports)
-    return 0;
-  return miphy_pusch_demod_nof_llr(&lj->base) * lj->nof_tx_layers;
-}
-
-// Both entry points. ex: miphy_pusch_demodulate_layers_batch_ex (only the message of the placeholder rule depends on it). The EX kernels run when the
-// call has EVM sums or a job with placeholders; device-resident jobs cannot be looked at, there the two pointers decide.
-static int pusch_demodulate_layers(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n, const float* grid, const float* ce,
-                                   const float* scalars, int8_t* llr, const uint16_t* placeholders, float* evm_sums, bool ex, void* stream)
-{
-  MIPHY_REQUIRE(ctx && jobs && grid && ce && scalars && llr, "miphy_pusch_demodulate_layers_batch: null argument");
+  constexpr bool layered = std::is_same<JOB, miphy_pusch_demod_layers_job>::value;
+  MIPHY_REQUIRE(ctx && jobs && grid && ce && scalars && llr, "miphy_%s_batch: null argument", who);
   if (n == 0)
     return MIPHY_OK;
-  MIPHY_REQUIRE(n <= 65535, "pusch_demodulate_layers: batch too large (max 65535 transmissions per call)");
-  uint32_t max_chunks = DEMOD_MAX_CHUNKS, max_layers = 4, max_words = 4 * SEQ_STRIDE; // device-resident jobs: the widest grid on four layers
-  bool     one_layer = true, more_layers = true;                                      // ... and both kernels
+  MIPHY_REQUIRE(n <= 65535, "%s: batch too large (max 65535 transmissions per call)", who);
+  // device-resident jobs: the widest grid, layered records on four layers and in both instances
+  uint32_t   max_chunks = DEMOD_MAX_CHUNKS, max_layers = layered ? 4 : 1, max_words = max_layers * SEQ_STRIDE;
+  bool       one_layer = true, more_layers = layered;
   const bool have_ph = placeholders != nullptr;
   bool       extras  = have_ph || evm_sums;
   if (!jobs_on_device) {
@@ -1203,18 +973,15 @@ static int pusch_demodulate_layers(miphy_ctx* ctx, const miphy_pusch_demod_layer
     max_layers = 1, one_layer = more_layers = false;
     extras     = evm_sums != nullptr;
     for (uint32_t i = 0; i < n; ++i) {
-      const miphy_pusch_demod_job& j = jobs[i].base;
-      const unsigned               L = jobs[i].nof_tx_layers;
-#define PUSCH_RULE_REQUIRE(cond, msg, ...) MIPHY_REQUIRE(cond, "pusch_demodulate_layers: job %u: " msg, i, ##__VA_ARGS__);
+      const miphy_pusch_demod_job& j = pusch_demod_base(jobs[i]);
+      const unsigned               L = pusch_demod_layers(jobs[i]);
+#define PUSCH_RULE_REQUIRE(cond, msg, ...) MIPHY_REQUIRE(cond, "%s: job %u: " msg, who, i, ##__VA_ARGS__);
       PUSCH_DEMOD_LAYERS_RULES(PUSCH_RULE_REQUIRE)
 #undef PUSCH_RULE_REQUIRE
-      uint32_t np = 0;
-      for (unsigned r = 0; r < j.grid_nof_prb; ++r)
-        np += (uint32_t)((j.rb_mask[r >> 6] >> (r & 63)) & 1ull);
-      max_prb    = np > max_prb ? np : max_prb;
-      max_layers = L > max_layers ? L : max_layers;
+      max_prb    = std::max(max_prb, miphy_count_prb(j.rb_mask, j.grid_nof_prb));
+      max_layers = std::max(max_layers, L);
       one_layer |= L == 1, more_layers |= L > 1;
-      max_llr    = j.nof_llr > max_llr ? j.nof_llr : max_llr;
+      max_llr    = std::max(max_llr, j.nof_llr);
       extras |= j.nof_placeholders != 0;
     }
     max_chunks = (max_prb * 12 + DEMOD_THREADS - 1) / DEMOD_THREADS;
@@ -1226,7 +993,7 @@ static int pusch_demodulate_layers(miphy_ctx* ctx, const miphy_pusch_demod_layer
   if (rc)
     return rc;
   const void* d_jobs = nullptr;
-  rc                 = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pusch_demod_layers_job) * (size_t)n, s, &d_jobs);
+  rc                 = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(JOB) * (size_t)n, s, &d_jobs);
   if (rc)
     return rc;
   const uint32_t stride = max_layers * (uint32_t)SEQ_STRIDE;
@@ -1237,9 +1004,9 @@ static int pusch_demodulate_layers(miphy_ctx* ctx, const miphy_pusch_demod_layer
     return rc;
   uint32_t*   seq      = static_cast<uint32_t*>(work);
   float*      evm_part = evm_sums ? reinterpret_cast<float*>(static_cast<uint8_t*>(work) + seq_bytes) : nullptr;
-  const auto* dj  = (const miphy_pusch_demod_layers_job*)d_jobs;
-  hipLaunchKernelGGL(pusch_seq_layers_kernel, dim3(n, max_words <= (uint32_t)SEQ_STRIDE ? 1u : (max_words + SEQ_PIECE - 1) / SEQ_PIECE), dim3(SCR_THREADS), 0, s,
-                     dj, gt, seq, stride, have_ph);
+  const auto* dj       = (const JOB*)d_jobs;
+  hipLaunchKernelGGL(pusch_seq_kernel<JOB>, dim3(n, max_words <= (uint32_t)SEQ_STRIDE ? 1u : (max_words + SEQ_PIECE - 1) / SEQ_PIECE), dim3(SCR_THREADS), 0, s, dj, gt,
+                     seq, stride, have_ph);
   const uint32_t sym_parts = std::max(1u, std::min(4u, (uint32_t)ctx->num_cus / (n * max_chunks)));
   const dim3 blocks(n, max_chunks, sym_parts);
   auto       launch = [&](auto kernel) {
@@ -1247,27 +1014,18 @@ static int pusch_demodulate_layers(miphy_ctx* ctx, const miphy_pusch_demod_layer
                        placeholders, evm_part);
   };
   if (one_layer)
-    launch(extras ? pusch_demod_layers_kernel<true, true> : pusch_demod_layers_kernel<true, false>);
-  if (more_layers)
-    launch(extras ? pusch_demod_layers_kernel<false, true> : pusch_demod_layers_kernel<false, false>);
+    launch(extras ? pusch_demod_kernel<JOB, true, true> : pusch_demod_kernel<JOB, true, false>);
+  if constexpr (layered) {
+    if (more_layers)
+      launch(extras ? pusch_demod_kernel<JOB, false, true> : pusch_demod_kernel<JOB, false, false>);
+  }
   if (evm_sums)
-    hipLaunchKernelGGL(pusch_evm_reduce_layers_kernel, dim3(n), dim3(64), 0, s, dj, (const float*)evm_part, evm_sums, have_ph);
+    hipLaunchKernelGGL(pusch_evm_reduce_kernel<JOB>, dim3(n), dim3(64), 0, s, dj, (const float*)evm_part, evm_sums, have_ph);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }
 
-extern "C" int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
-                                                   const float* ce, const float* scalars, int8_t* llr, void* stream)
-{
-  return pusch_demodulate_layers(ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, nullptr, nullptr, false, stream);
-}
-
-extern "C" int miphy_pusch_demodulate_layers_batch_ex(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n,
-                                                      const float* grid, const float* ce, const float* scalars, int8_t* llr, const uint16_t* placeholders,
-                                                      float* evm_sums, void* stream)
-{
-  return pusch_demodulate_layers(ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, placeholders, evm_sums, true, stream);
-}
+} // namespace
 
 extern "C" uint32_t miphy_pusch_demod_nof_llr(const miphy_pusch_demod_job* j)
 {
@@ -1276,13 +1034,25 @@ extern "C" uint32_t miphy_pusch_demod_nof_llr(const miphy_pusch_demod_job* j)
   unsigned dm = 0;
   for (unsigned k = 0; k < 12; ++k)
     dm += (j->dmrs_type == 1) ? ((k % 2) < j->nof_cdm_groups_without_data) : ((k % 6) < 2u * j->nof_cdm_groups_without_data);
-  unsigned nprb = 0;
-  for (unsigned r = 0; r < j->grid_nof_prb; ++r)
-    nprb += (unsigned)((j->rb_mask[r >> 6] >> (r & 63)) & 1ull);
-  unsigned n = 0;
+  const unsigned nprb = miphy_count_prb(j->rb_mask, j->grid_nof_prb);
+  unsigned       n    = 0;
   for (unsigned s = j->start_symbol; s < (unsigned)j->start_symbol + j->nof_symbols && s < 14; ++s)
     n += nprb * (((j->dmrs_symbols_mask >> s) & 1) ? 12 - dm : 12);
   return n * j->mod;
+}
+
+extern "C" uint32_t miphy_pusch_demod_layers_nof_llr(const miphy_pusch_demod_layers_job* lj)
+{
+  if (!lj || lj->nof_tx_layers < 1 || lj->nof_tx_layers > 4 || lj->nof_tx_layers > lj->base.nof_rx_ports)
+    return 0;
+  return miphy_pusch_demod_nof_llr(&lj->base) * lj->nof_tx_layers;
+}
+
+extern "C" int miphy_pusch_demodulate_batch_ex(miphy_ctx* ctx, const miphy_pusch_demod_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                               const float* ce, const float* scalars, int8_t* llr, const uint16_t* placeholders, float* evm_sums,
+                                               void* stream)
+{
+  return pusch_demodulate("pusch_demodulate", ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, placeholders, evm_sums, true, stream);
 }
 
 extern "C" int miphy_pusch_demodulate_batch(miphy_ctx* ctx, const miphy_pusch_demod_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
@@ -1291,65 +1061,15 @@ extern "C" int miphy_pusch_demodulate_batch(miphy_ctx* ctx, const miphy_pusch_de
   return miphy_pusch_demodulate_batch_ex(ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, nullptr, nullptr, stream);
 }
 
-extern "C" int miphy_pusch_demodulate_batch_ex(miphy_ctx* ctx, const miphy_pusch_demod_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
-                                               const float* ce, const float* scalars, int8_t* llr, const uint16_t* placeholders, float* evm_sums,
-                                               void* stream)
+extern "C" int miphy_pusch_demodulate_layers_batch_ex(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n,
+                                                      const float* grid, const float* ce, const float* scalars, int8_t* llr, const uint16_t* placeholders,
+                                                      float* evm_sums, void* stream)
 {
-  MIPHY_REQUIRE(ctx && jobs && grid && ce && scalars && llr, "miphy_pusch_demodulate_batch: null argument");
-  if (n == 0)
-    return MIPHY_OK;
-  MIPHY_REQUIRE(n <= 65535, "pusch_demodulate: batch too large (max 65535 transmissions per call)");
-  uint32_t max_chunks = DEMOD_MAX_CHUNKS; // device-resident jobs: the widest grid
-  if (!jobs_on_device) {
-    uint32_t max_prb = 1;
-    for (uint32_t i = 0; i < n; ++i) {
-      uint32_t np = 0;
-      for (unsigned r = 0; r < jobs[i].grid_nof_prb && r < 275; ++r)
-        np += (uint32_t)((jobs[i].rb_mask[r >> 6] >> (r & 63)) & 1ull);
-      max_prb = np > max_prb ? np : max_prb;
-    }
-    max_chunks = (max_prb * 12 + DEMOD_THREADS - 1) / DEMOD_THREADS;
-    for (uint32_t i = 0; i < n; ++i) {
-      const miphy_pusch_demod_job& j = jobs[i];
-      MIPHY_REQUIRE(j.mod == 1 || j.mod == 2 || j.mod == 4 || j.mod == 6 || j.mod == 8, "pusch_demodulate: job %u: invalid modulation order %u", i, j.mod);
-      MIPHY_REQUIRE(j.nof_rx_ports >= 1 && j.nof_rx_ports <= 4, "pusch_demodulate: job %u: invalid number of receive ports", i);
-      MIPHY_REQUIRE(j.nof_symbols >= 1 && j.start_symbol + j.nof_symbols <= 14, "pusch_demodulate: job %u: invalid time allocation", i);
-      MIPHY_REQUIRE(j.ce_compact || (j.ce_nof_symbols >= j.start_symbol + j.nof_symbols && j.ce_nof_symbols <= 14),
-                    "pusch_demodulate: job %u: channel estimate too short", i);
-      MIPHY_REQUIRE(j.dmrs_type == 1 || j.dmrs_type == 2, "pusch_demodulate: job %u: invalid DM-RS type", i);
-      MIPHY_REQUIRE(j.nof_cdm_groups_without_data >= 1 && j.nof_cdm_groups_without_data <= (j.dmrs_type == 1 ? 2 : 3),
-                    "pusch_demodulate: job %u: invalid number of CDM groups without data", i);
-      MIPHY_REQUIRE(j.grid_nof_prb >= 1 && j.grid_nof_prb <= 275, "pusch_demodulate: job %u: invalid grid width", i);
-      MIPHY_REQUIRE(j.n_id < 1024, "pusch_demodulate: job %u: invalid scrambling identifier", i);
-      MIPHY_REQUIRE(j.rnti < 65536, "pusch_demodulate: job %u: invalid RNTI", i);
-      // pusch_demodulator_impl.cpp:76-80: the codeword length must match the number of data REs
-      MIPHY_REQUIRE(j.nof_llr == miphy_pusch_demod_nof_llr(&j), "pusch_demodulate: job %u: %u LLRs requested, the allocation holds %u", i, j.nof_llr,
-                    miphy_pusch_demod_nof_llr(&j));
-      MIPHY_REQUIRE(j.nof_placeholders == 0 || (placeholders && j.mod >= 2), "pusch_demodulate: job %u: placeholders need the list and a modulation order of at least 2", i);
-    }
-  }
-  hipStream_t        s  = (hipStream_t)stream;
-  const gold_tables* gt = nullptr;
-  int                rc = miphy_get_gold_tables(ctx, &gt);
-  if (rc)
-    return rc;
-  const void* d_jobs = nullptr;
-  rc                 = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pusch_demod_job) * (size_t)n, s, &d_jobs);
-  if (rc)
-    return rc;
-  void*        work      = nullptr;
-  const size_t seq_bytes = (size_t)n * SEQ_STRIDE * sizeof(uint32_t);
-  const size_t evm_bytes = evm_sums ? (size_t)n * 14 * DEMOD_MAX_CHUNKS * sizeof(float) : 0;
-  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, seq_bytes + evm_bytes, &work)))
-    return rc;
-  uint32_t* seq      = static_cast<uint32_t*>(work);
-  float*    evm_part = evm_sums ? reinterpret_cast<float*>(static_cast<uint8_t*>(work) + seq_bytes) : nullptr;
-  hipLaunchKernelGGL(pusch_scrambling_kernel, dim3(n), dim3(SCR_THREADS), 0, s, (const miphy_pusch_demod_job*)d_jobs, gt, seq);
-  const uint32_t sym_parts = std::max(1u, std::min(4u, (uint32_t)ctx->num_cus / (n * max_chunks)));
-  hipLaunchKernelGGL(pusch_demod_kernel, dim3(n, max_chunks, sym_parts), dim3(DEMOD_THREADS), 0, s, (const miphy_pusch_demod_job*)d_jobs, (const float2*)grid,
-                     (const float2*)ce, scalars, llr, placeholders, evm_part, (const uint32_t*)seq);
-  if (evm_sums)
-    hipLaunchKernelGGL(pusch_evm_reduce_kernel, dim3(n), dim3(64), 0, s, (const miphy_pusch_demod_job*)d_jobs, (const float*)evm_part, evm_sums);
-  MIPHY_HIP_CHECK(hipGetLastError());
-  return MIPHY_OK;
+  return pusch_demodulate("pusch_demodulate_layers", ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, placeholders, evm_sums, true, stream);
+}
+
+extern "C" int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                                   const float* ce, const float* scalars, int8_t* llr, void* stream)
+{
+  return pusch_demodulate("pusch_demodulate_layers", ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, nullptr, nullptr, false, stream);
 }

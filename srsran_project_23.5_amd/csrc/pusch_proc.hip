@@ -108,10 +108,8 @@ int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu*
     uint32_t nof_sch_llr    = d.nof_llr;
     if (has_uci) {
       MIPHY_REQUIRE(have_uci_out, "pusch_process: PDU %u carries UCI but uci_llr_out is NULL", i);
-      miphy_ulsch_demux_job x = {};
-      uint32_t              nprb = 0;
-      for (unsigned r = 0; r < p.grid_nof_prb; ++r)
-        nprb += (uint32_t)((p.rb_mask[r >> 6] >> (r & 63)) & 1ull);
+      miphy_ulsch_demux_job x    = {};
+      const uint32_t        nprb = miphy_count_prb(p.rb_mask, p.grid_nof_prb);
       x.mod = p.mod, x.nof_layers = (uint8_t)L, x.start_symbol = p.start_symbol, x.nof_symbols = p.nof_symbols, x.dmrs_type = 1, x.nof_cdm_groups_without_data = 2;
       x.dmrs_symbols_mask = p.dmrs_symbols_mask, x.nof_prb = (uint16_t)nprb, x.nof_harq_ack_rvd = u->nof_harq_ack_rvd;
       x.nof_enc_harq_ack_bits = u->nof_enc_harq_ack_bits, x.nof_enc_csi_part1_bits = u->nof_enc_csi_part1_bits;

@@ -238,6 +238,84 @@ def test_placeholders_and_evm_match_oracle(ctx, mod, ports, cdm):
     assert abs(evm - oe) <= 2e-6 * oe + 1e-7, (evm, oe)
 
 
+@pytest.mark.parametrize("mod", [6, 2])
+def test_placeholders_and_evm_with_device_jobs(ctx, mod):
+    """pusch_demodulate_batch_ex with the jobs in device memory: the launch is sized for the widest grid, the two pointers (not the jobs)
+    choose the kernel instance, and the workgroups of a chunk behind a narrow allocation leave in front of the barriers of the EVM sum.
+    Two transmissions on a 24-PRB grid, symbols 2..13, DM-RS on 2 and 11, two receive ports: 22 PRB (two chunks, eight live lanes in
+    the second; data on the DM-RS symbols) and 4 PRB (none), each with a short placeholder list and its EVM sums between sentinels;
+    two jobs leave compute units idle, so the symbols are cut into parts as well. At modulation order 6 an element's chips straddle a
+    word. LLRs bit-equal to the oracle, each EVM within the tolerance of test_placeholders_and_evm_match_oracle; host- and
+    device-resident jobs, and the same jobs as layered records on one layer, give the same bytes; nothing else is written."""
+    import torch
+    import miphy
+    rng = np.random.default_rng(7700 + mod)
+    nprb, ports, start, nof = 24, 2, 2, 12
+    nsc = nprb * 12
+    dm = np.zeros(14, np.uint8)
+    dm[[2, 11]] = 1
+    rbs = [np.ones(nprb, np.uint8), np.zeros(nprb, np.uint8)]
+    rbs[0][[5, 17]] = 0
+    rbs[1][[3, 4, 9, 20]] = 1
+    cdms, rntis, n_ids, nvs = [1, 2], [0x4321, 17], [1001, 5], [0.07, 0.2]
+    grid = (rng.standard_normal((ports, 14, nsc)) + 1j * rng.standard_normal((ports, 14, nsc))).astype(np.complex64)
+    ce = (rng.standard_normal((ports, 14, nsc)) + 1j * rng.standard_normal((ports, 14, nsc))).astype(np.complex64)
+    jobs, phs, exp, n_res = [], [], [], []
+    llr_off, ph_off, evm_off = 8, 5, 3  # the first codeword aligned, the second at an odd address
+    for k in range(2):
+        n_re = O.pusch_nof_re(start, nof, dm, 0, cdms[k], rbs[k])
+        ph = np.sort(rng.choice(n_re, 9, replace=False)).astype(np.uint16)
+        ph[0], ph[-1] = 0, n_re - 1  # the first and the last element of the codeword
+        j = _job(miphy, rntis[k], n_ids[k], mod, start, nof, dm, 0, cdms[k], rbs[k], ports, 14, sc_off=5 * k, llr_off=llr_off)
+        j["placeholders_offset"], j["nof_placeholders"], j["evm_offset"] = ph_off, ph.size, evm_off
+        assert j["nof_llr"] == n_re * mod
+        jobs.append(j)
+        phs.append(ph)
+        n_res.append(n_re)
+        exp.append(O.o_pusch_demodulate_ex(rntis[k], n_ids[k], mod, start, nof, dm, 0, cdms[k], rbs[k], grid, ce, nvs[k], placeholders=ph))
+        llr_off = (llr_off + n_re * mod + 8) // 8 * 8 + 3
+        ph_off += ph.size + 3
+        evm_off += 14 + 2
+    assert n_res == [22 * (10 * 12 + 2 * 6), 4 * 10 * 12]
+    jobs = np.array(jobs, dtype=miphy.PuschDemodJob)
+    ljobs = np.zeros(2, dtype=miphy.PuschDemodLayersJob)
+    ljobs["base"], ljobs["nof_tx_layers"] = jobs, 1
+    ph_all = np.full(ph_off, 0xffff, np.uint16)
+    for j, ph in zip(jobs, phs):
+        ph_all[int(j["placeholders_offset"]):int(j["placeholders_offset"]) + ph.size] = ph
+    g = torch.from_numpy(grid.reshape(-1)).cuda()
+    h = torch.from_numpy(ce.reshape(-1)).cuda()
+    sc = np.zeros(10, np.float32)
+    sc[2::5] = nvs
+    sc_d = torch.from_numpy(sc).cuda()
+    ph_d = torch.from_numpy(ph_all.view(np.int16)).cuda()
+
+    def run(entry, records, device_jobs):
+        out = torch.full((llr_off + 64,), 99, dtype=torch.int8, device="cuda")
+        evm_d = torch.full((evm_off,), -1.0, dtype=torch.float32, device="cuda")
+        entry(torch.from_numpy(records.view(np.uint8)).cuda() if device_jobs else records, g, h, sc_d, out, ph_d, evm_d)
+        torch.cuda.synchronize()
+        return out.cpu().numpy(), evm_d.cpu().numpy()
+
+    got, e = run(ctx.pusch_demodulate_batch_ex, jobs, True)
+    used, summed = np.zeros(got.size, bool), np.zeros(e.size, bool)
+    for k, j in enumerate(jobs):
+        lo, eo = int(j["llr_offset"]), int(j["evm_offset"])
+        o, oe = exp[k]
+        assert np.array_equal(got[lo:lo + o.size], o), (k, np.nonzero(got[lo:lo + o.size] != o)[0][:8])
+        used[lo:lo + o.size] = True
+        summed[eo:eo + 14] = True
+        assert e[eo] == 0.0 and e[eo + 1] == 0.0  # symbols outside the allocation contribute 0
+        evm = float(np.sqrt(e[eo:eo + 14].astype(np.float64).sum() / n_res[k]))
+        print("job %d: EVM %.9g, oracle %.9g" % (k, evm, oe))
+        assert abs(evm - oe) <= 2e-6 * oe + 1e-7, (k, evm, oe)
+    assert np.all(got[~used] == 99) and np.all(e[~summed] == -1.0)
+    for entry, records, device_jobs in ((ctx.pusch_demodulate_batch_ex, jobs, False), (ctx.pusch_demodulate_layers_batch_ex, ljobs, False),
+                                        (ctx.pusch_demodulate_layers_batch_ex, ljobs, True)):
+        got2, e2 = run(entry, records, device_jobs)
+        assert np.array_equal(got2, got) and np.array_equal(e2.view(np.uint32), e.view(np.uint32)), (entry.__name__, device_jobs)
+
+
 # ------------------------------------------------------------------------------------------------ port lists, short estimates, the symbol split
 def _item(rng, mod, sel, compact, cdm, type2, rb, start, nof, dsyms, ce_rows=14):
     """One transmission received on the grid ports `sel` of a four-port grid (the other ports are NaN: a read of a port the job does not name

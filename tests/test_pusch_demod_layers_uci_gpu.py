@@ -109,7 +109,7 @@ def run(ctx, slots, phs=None, evm=True, device_jobs=False, first_llr=0, entry="e
 
 def additions(c):
     """A: float32 additions on the longest path from a term to the stored sum of an OFDM symbol (csrc/pusch_demod.hip): L - 1 over the layers of an
-    element, 6 in the wavefront shuffle tree, 3 over the four wavefronts, chunks - 1 in pusch_evm_reduce_layers_kernel (its sum starts from 0)."""
+    element, 6 in the wavefront shuffle tree, 3 over the four wavefronts, chunks - 1 in pusch_evm_reduce_kernel (its sum starts from 0)."""
     chunks = -(-len(c["prbs"]) * 12 // 256)
     return (c["nl"] - 1) + 6 + 3 + (chunks - 1)
 

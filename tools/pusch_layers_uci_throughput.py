@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What UCI placeholders and the EVM cost above one layer (csrc/pusch_demod.hip: the EX instances of pusch_demod_layers_kernel, which take the exact
+"""What UCI placeholders and the EVM cost above one layer (csrc/pusch_demod.hip: the EX instances of pusch_demod_kernel, which take the exact
 demapper; csrc/pusch_proc.hip: miphy_pusch_process_layers_batch_ex).
 
 Demodulator legs: L = 2 and 4 on four ports, 273 PRB x 14 symbols (DM-RS on symbol 2, two CDM groups without data), 256QAM, the compact estimate,
