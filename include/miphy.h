@@ -463,7 +463,84 @@ int miphy_pusch_demodulate_layers_batch_ex(miphy_ctx* ctx, const miphy_pusch_dem
                                            float* evm_sums /* device, may be NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
- * Channel equalizer on its own --  replaces srsran::channel_equalizer::equalize of the zero-forcing equalizer
+ * PUSCH with transform precoding (DFT-s-OFDM, TS 38.211 6.3.1.4)  --  beyond the 23.5 reference, which has no transform precoding anywhere
+ * in its uplink chain. The waveform is single-layer by specification. Restated in numpy from the standard in tests/pusch_tp_ref.py.
+ *
+ * The de-precoder on its own: row s of a job holds the M = 12 N_PRB equalised elements x[k] of one data OFDM symbol and their noise
+ * variances v[k]; it gives
+ *   y[n] = (1 / sqrt(M)) sum_k x[k] e^(+j 2 pi k n / M), n = 0 .. M-1, and one noise variance per row,
+ *   v = (sum over the normal elements of v[k]) / (number of normal elements); +inf when no element is normal.
+ * An element is normal when v[k] is positive and finite. Any other element (the equalisers mark an element they could not invert with
+ * symbol 0 and variance +inf) enters the IDFT as 0, whatever its symbol holds, and is left out of the mean. The additions of the mean run
+ * in one fixed order (csrc/tp_device.h), so a row has one value whatever the batch. N_PRB = 2^a 3^b 5^c <= 270: the 53 sizes M = 12 ... 3240.
+ * A host job with another M is MIPHY_EUNSUPP, one with nof_symbols > 14 MIPHY_EINVAL, with nothing enqueued; a device-resident one is skipped. */
+typedef struct {
+  uint32_t M;                     /* elements per row */
+  uint32_t nof_symbols;           /* rows, at most 14 */
+  uint64_t eq_symbols_offset;     /* cf_t offset into eq_symbols: [row][M] */
+  uint64_t eq_noise_vars_offset;  /* float offset into eq_noise_vars: [row][M] */
+  uint64_t out_symbols_offset;    /* cf_t offset into out_symbols: [row][M] */
+  uint64_t out_noise_var_offset;  /* float offset into out_noise_var: [row] */
+} miphy_transform_deprecode_job;
+int miphy_transform_deprecode_batch(miphy_ctx* ctx, const miphy_transform_deprecode_job* jobs, int jobs_on_device, uint32_t n,
+                                    const float* eq_symbols /* device cf_t */, const float* eq_noise_vars /* device */,
+                                    float* out_symbols /* device cf_t */, float* out_noise_var /* device */, void* stream);
+
+/* The demodulator of a transform-precoded PUSCH: miphy_pusch_demod_job unchanged, and beyond the rules of miphy_pusch_demodulate_batch
+ *   rb_mask is contiguous and holds N_PRB = 2^a 3^b 5^c <= 270 PRBs; dmrs_type = 1; nof_cdm_groups_without_data = 2 (a DM-RS symbol carries
+ *   no data, so every data symbol has exactly M = 12 N_PRB elements).
+ * A host job that breaks a rule is MIPHY_EINVAL with nothing enqueued; a device-resident one is skipped. One workgroup per (transmission,
+ * data OFDM symbol): the M elements of the 1..4 ports are equalised as miphy_channel_equalize_batch does (one layer, tx_scaling = 1, noise
+ * variance scalars[scalars_offset + 2], compact or per-symbol estimate), de-precoded as miphy_transform_deprecode_batch does, and y[n] with
+ * the symbol's v goes through the soft demapper and descrambler of miphy_pusch_demodulate_batch:
+ *   bit b of y[n] of the r-th data symbol at llr_offset + (r M + n) mod + b, descrambled with c((r M + n) mod + b); pi/2-BPSK rotates by the
+ *   parity of r M + n. A symbol without a normal element gives zero LLRs.
+ * The bytes are those of the composition extraction, miphy_channel_equalize_batch, miphy_transform_deprecode_batch, soft demapper, descrambler.
+ * _ex: placeholders as miphy_pusch_demodulate_batch_ex (element indices r M + n in codeword order, mod >= 2); evm_sums[evm_offset + sy] is
+ * the sum over the M de-precoded symbols of OFDM symbol sy of |hard-decided symbol - y[n]|^2, added in a fixed order, 0 for a symbol
+ * without data. The LLRs do not depend on whether EVM is asked for. miphy_pusch_demod_nof_llr gives nof_llr. */
+int miphy_pusch_demodulate_tp_batch(miphy_ctx* ctx, const miphy_pusch_demod_job* jobs, int jobs_on_device, uint32_t n,
+                                    const float* grid /* device cf_t */, const float* ce /* device cf_t */, const float* scalars /* device */,
+                                    int8_t* llr_out /* device */, void* stream);
+int miphy_pusch_demodulate_tp_batch_ex(miphy_ctx* ctx, const miphy_pusch_demod_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                       const float* ce, const float* scalars, int8_t* llr_out, const uint16_t* placeholders /* device, may be NULL */,
+                                       float* evm_sums /* device, may be NULL */, void* stream);
+
+/* Low-PAPR sequence r_{u,v}(n) with alpha = 0 (TS 38.211 5.2.2), n = 0 .. length-1, u = 0..29, v = 0..1. Host function, `out` on the host.
+ *   length 12: Table 5.2.2.2-2 (the table PUCCH formats 0 and 1 use); v is not looked at
+ *   length 30: exp(-j pi (u+1)(n+1)(n+2) / 31); v is not looked at
+ *   length 6 N >= 36: x_q(n mod N_ZC), x_q(m) = exp(-j pi q m (m+1) / N_ZC), N_ZC the largest prime below the length,
+ *     q = floor(qbar + 1/2) + v (-1)^floor(2 qbar), qbar = N_ZC (u+1) / 31 (the standard uses v = 1 from length 72 on only; the formula is evaluated as given). The phase q m (m+1) is reduced
+ *     modulo 2 N_ZC in integers before it is turned into an angle.
+ * Lengths 6, 18 and 24 (allocations of 1, 3 and 4 PRBs) are defined by Tables 5.2.2.2-1, -3 and -4, which this library does not hold:
+ * MIPHY_EUNSUPP here and in the two entry points below. Such an allocation is estimated by miphy_port_channel_estimate_batch with pilots
+ * of the caller and demodulated by miphy_pusch_demodulate_tp_batch. Any other length or index is MIPHY_EINVAL. */
+int miphy_low_papr_sequence(uint32_t u, uint32_t v, uint32_t length, float* out /* host cf_t */);
+
+/* DM-RS of a transform-precoded PUSCH (TS 38.211 6.4.1.1.1.2): one layer on DM-RS port 0 (even subcarriers), type 1, no intra-slot hopping.
+ * Of `base`: scrambling_id = n_ID^RS (0..1007), n_scid = 0, nof_tx_layers = 1, hop_symbol = 0, re_odd_mask = 0, rb_mask contiguous with a PRB
+ * count 2^a 3^b 5^c <= 270 other than 1, 3 and 4 (MIPHY_EUNSUPP, above). DM-RS symbol l of slot n_s = base.slot_in_frame carries
+ * r_{u,v}(n), n < 6 N_PRB, with u = (f_gh + n_ID^RS) mod 30 and
+ *   hopping 0: f_gh = 0, v = 0
+ *   hopping 1 (group):    f_gh = (sum_{m<8} 2^m c(8 (14 n_s + l) + m)) mod 30 with c_init = floor(n_ID^RS / 30), v = 0
+ *   hopping 2 (sequence): f_gh = 0, v = c(14 n_s + l) with c_init = n_ID^RS where 6 N_PRB >= 72, else 0.
+ * miphy_dmrs_pusch_tp_pilots_batch writes the pilots of every job at pilots[base.pilots_offset ...] in the layout miphy_port_channel_estimate_batch
+ * reads: [DM-RS symbol][6 N_PRB]. miphy_dmrs_pusch_estimate_tp_batch is that kernel, the pilots in a workspace of the context, followed by the
+ * kernel of miphy_port_channel_estimate_batch: its estimate and scalars are those of that entry point fed the pilots (base.pilots_offset is
+ * ignored). A host job that breaks a rule is MIPHY_EINVAL (MIPHY_EUNSUPP for 1, 3 and 4 PRBs) with nothing enqueued; a device-resident one is
+ * skipped (jobs_on_device as miphy_port_channel_estimate_batch, the port hint included). */
+typedef struct {
+  miphy_pusch_chest_job base;
+  uint8_t               hopping; /* 0 neither, 1 group hopping, 2 sequence hopping */
+  uint8_t               reserved[7];
+} miphy_pusch_chest_tp_job;
+int miphy_dmrs_pusch_tp_pilots_batch(miphy_ctx* ctx, const miphy_pusch_chest_tp_job* jobs, int jobs_on_device, uint32_t n, float* pilots /* device cf_t */,
+                                     void* stream);
+int miphy_dmrs_pusch_estimate_tp_batch(miphy_ctx* ctx, const miphy_pusch_chest_tp_job* jobs, int jobs_on_device, uint32_t n,
+                                       const float* grid /* device cf_t */, float* ce /* device cf_t */, float* scalars /* device */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Channel equalizer on its own--  replaces srsran::channel_equalizer::equalize of the zero-forcing equalizer
  * (include/srsran/phy/upper/equalization/channel_equalizer.h:27-114, lib/phy/upper/equalization/channel_equalizer_zf_impl.cpp:123-162).
  * Topologies are the reference's: one transmit layer with 1..4 receive ports (equalize_zf_1xn.h:120-158) and two layers on two ports
  * (equalize_zf_2x2.cpp:30-117); anything else is MIPHY_EINVAL where the reference asserts. The noise variance is the one of the
@@ -952,6 +1029,27 @@ int miphy_pusch_process_layers_batch_ex(miphy_ctx* ctx, const miphy_pusch_layers
                                         uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
                                         miphy_pusch_result* results, float* scalars_out /* n x 80 */, int8_t* uci_llr_out,
                                         float* evm_out /* device, n, may be NULL */, void* stream);
+
+/* PUSCH processor for a transform-precoded PUSCH (DFT-s-OFDM)  --  beyond the 23.5 reference, whose pusch_processor::pdu_t cannot express the
+ * waveform. One call chains, on one stream, miphy_dmrs_pusch_estimate_tp_batch (compact estimate, scaling 10^(3/20), base.dmrs_scrambling_id =
+ * n_ID^RS, base.n_scid = 0, `hopping` as in miphy_pusch_chest_tp_job), miphy_pusch_demodulate_tp_batch_ex, miphy_ulsch_demultiplex_batch when
+ * UCI is multiplexed and miphy_pusch_decode_batch; the bytes are those of the stages called one by one. One layer, DM-RS type 1, two CDM
+ * groups without data, a contiguous allocation of 2^a 3^b 5^c <= 270 PRBs other than 1, 3 and 4 (MIPHY_EUNSUPP: their DM-RS tables are not in
+ * the library; such a PDU is served by miphy_port_channel_estimate_batch with the caller's pilots, miphy_pusch_demodulate_tp_batch and
+ * miphy_pusch_decode_batch). Outputs, scalars_out (20 per PDU), UCI soft bits and EVM as miphy_pusch_process_batch_ex. A PDU that breaks a
+ * rule is MIPHY_EINVAL with nothing enqueued. Out: a prepared plan, graph capture, the slot batch of the uplink processor. */
+typedef struct {
+  miphy_pusch_pdu base;
+  uint8_t         hopping; /* 0 neither, 1 group hopping, 2 sequence hopping (TS 38.211 6.4.1.1.1.2) */
+  uint8_t         reserved[7];
+} miphy_pusch_tp_pdu;
+int miphy_pusch_process_tp_batch(miphy_ctx* ctx, const miphy_pusch_tp_pdu* pdus /* host */, uint32_t n, const float* grid /* device cf_t */,
+                                 int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out /* device */,
+                                 miphy_pusch_result* results /* device, n */, float* scalars_out /* device, n x 20 */, void* stream);
+int miphy_pusch_process_tp_batch_ex(miphy_ctx* ctx, const miphy_pusch_tp_pdu* pdus /* host */, const miphy_pusch_uci* uci /* host or NULL */, uint32_t n,
+                                    const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
+                                    miphy_pusch_result* results, float* scalars_out /* n x 20 */, int8_t* uci_llr_out,
+                                    float* evm_out /* device, n, may be NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * UL-SCH demultiplexer  --  replaces srsran::ulsch_demultiplex::demultiplex / get_placeholders (UCI multiplexed on PUSCH)

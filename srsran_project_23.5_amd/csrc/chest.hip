@@ -795,6 +795,39 @@ extern "C" int miphy_dmrs_pusch_estimate_batch(miphy_ctx* ctx, const miphy_pusch
   return chest_launch(ctx, jobs, jobs_on_device, n, grid, nullptr, ce, scalars, stream, "miphy_dmrs_pusch_estimate_batch");
 }
 
+// Transform-precoded PUSCH (TS 38.211 6.4.1.1.1.2): the low-PAPR pilots of every job into a workspace of the context (transform_precoding.hip), then
+// chest_kernel<true> on a copy of the base records that points at them -- the estimate and scalars of miphy_port_channel_estimate_batch fed those pilots.
+extern "C" int miphy_dmrs_pusch_estimate_tp_batch(miphy_ctx* ctx, const miphy_pusch_chest_tp_job* jobs, int jobs_on_device, uint32_t n, const float* grid, float* ce,
+                                                  float* scalars, void* stream)
+{
+  const char* what = "miphy_dmrs_pusch_estimate_tp_batch";
+  MIPHY_REQUIRE(ctx && jobs && grid && ce && scalars, "%s: null argument", what);
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "%s: at most 65535 jobs per call", what);
+  unsigned max_ports, max_layers, max_nprb = 270;
+  int      rc = chest_hints(jobs_on_device, max_ports, max_layers, what);
+  if (rc)
+    return rc;
+  if (!jobs_on_device && (rc = miphy_tp_chest_validate(what, jobs, n, max_nprb, max_ports)))
+    return rc;
+  hipStream_t s      = (hipStream_t)stream;
+  const void* d_jobs = nullptr;
+  if ((rc = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pusch_chest_tp_job) * (size_t)n, s, &d_jobs)))
+    return rc;
+  // [base records | pilots: per job four DM-RS symbols of the widest allocation]
+  const uint32_t stride     = 4u * 6u * max_nprb;
+  const size_t   base_bytes = (sizeof(miphy_pusch_chest_job) * (size_t)n + 255) & ~(size_t)255;
+  void*          work       = nullptr;
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_GENERAL, base_bytes + (size_t)n * stride * sizeof(float2), &work)))
+    return rc;
+  auto*  base   = static_cast<miphy_pusch_chest_job*>(work);
+  float* pilots = reinterpret_cast<float*>(static_cast<uint8_t*>(work) + base_bytes);
+  if ((rc = miphy_tp_pilots_launch(ctx, (const miphy_pusch_chest_tp_job*)d_jobs, n, pilots, base, stride, s)))
+    return rc;
+  return chest_enqueue(ctx, base, n, max_ports, 1, grid, pilots, ce, scalars, s);
+}
+
 extern "C" int miphy_port_channel_estimate_batch(miphy_ctx* ctx, const miphy_pusch_chest_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
                                                  const float* pilots, float* ce, float* scalars, void* stream)
 {

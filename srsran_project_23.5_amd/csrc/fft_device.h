@@ -1,4 +1,5 @@
-// In-LDS Stockham FFT (autosort, decimation in frequency) for N = 2^a * 3^b <= 4096, one workgroup per transform.
+// In-LDS Stockham FFT (autosort, decimation in frequency) for N = 2^a * 3^b <= 4096, one workgroup per transform; with R5 (the
+// transform-precoding sizes, tp_device.h) N = 2^a * 3^b * 5^c.
 // Unnormalised, sign -1 for DIRECT and +1 for INVERSE like srsran::dft_processor
 // (include/srsran/phy/generic_functions/dft_processor.h:34-73, lib/phy/generic_functions/dft_processor_generic_impl.cpp:191).
 //
@@ -88,6 +89,24 @@ __device__ __forceinline__ void dft3(cplx& a0, cplx& a1, cplx& a2)
   a2             = csub(m, r);
 }
 
+// Radix 5 (Winograd form: the real parts c1 = cos(2 pi / 5), c2 = cos(4 pi / 5) and the imaginary parts s1, s2 of the two conjugate pairs).
+template <bool INV>
+__device__ __forceinline__ void dft5(cplx& a0, cplx& a1, cplx& a2, cplx& a3, cplx& a4)
+{
+  const float c1 = 0.30901699437494742410f, c2 = -0.80901699437494742410f;
+  const float s1 = 0.95105651629515357212f, s2 = 0.58778525229247312917f;
+  const cplx  p14 = cadd(a1, a4), m14 = csub(a1, a4), p23 = cadd(a2, a3), m23 = csub(a2, a3);
+  const cplx  r1 = {a0.x + (c1 * p14.x + c2 * p23.x), a0.y + (c1 * p14.y + c2 * p23.y)};
+  const cplx  r2 = {a0.x + (c2 * p14.x + c1 * p23.x), a0.y + (c2 * p14.y + c1 * p23.y)};
+  const cplx  i1 = cmul_mi<INV>(cplx{s1 * m14.x + s2 * m23.x, s1 * m14.y + s2 * m23.y}); // -+ i (s1 (a1 - a4) + s2 (a2 - a3))
+  const cplx  i2 = cmul_mi<INV>(cplx{s2 * m14.x - s1 * m23.x, s2 * m14.y - s1 * m23.y});
+  a0             = cadd(a0, cadd(p14, p23));
+  a1             = cadd(r1, i1);
+  a4             = csub(r1, i1);
+  a2             = cadd(r2, i2);
+  a3             = csub(r2, i2);
+}
+
 template <bool INV>
 __device__ __forceinline__ void dft8(cplx* a)
 {
@@ -120,7 +139,7 @@ __device__ __forceinline__ void fft_pass(cplx* x, int N, int n, int s, const cpl
   const int m  = n / R;
   const int nb = N / R; // butterflies
   // Butterflies per thread: nb <= MAXB * nt.
-  constexpr int MAXB = ((R == 8) ? 2 : (R == 4) ? 4 : (R == 2) ? 8 : 6) / (WIDE ? 2 : 1);
+  constexpr int MAXB = ((R == 8) ? 2 : (R == 4 || R == 5) ? 4 : (R == 2) ? 8 : 6) / (WIDE ? 2 : 1);
   cplx          a[MAXB][R];
   cplx          w1s[MAXB];
   int           ps[MAXB], qs[MAXB];
@@ -153,6 +172,8 @@ __device__ __forceinline__ void fft_pass(cplx* x, int N, int n, int s, const cpl
         dft3<INV>(v[0], v[1], v[2]);
       else if (R == 4)
         dft4<INV>(v[0], v[1], v[2], v[3]);
+      else if (R == 5)
+        dft5<INV>(v[0], v[1], v[2], v[3], v[4]);
       else
         dft8<INV>(v);
       if (m > 1) { // twiddle exp(-+ 2 pi i p k / n) = W_N^(p k s)
@@ -173,8 +194,9 @@ __device__ __forceinline__ void fft_pass(cplx* x, int N, int n, int s, const cpl
   __syncthreads();
 }
 
-// Full transform of the N points in LDS buffer x (natural order in, natural order out).
-template <bool INV, bool WIDE>
+// Full transform of the N points in LDS buffer x (natural order in, natural order out). R5: N may hold factors 5, whose passes run last (an
+// instance without R5 has no radix-5 code, and every size without a factor 5 takes the same passes in the same order through either).
+template <bool INV, bool WIDE, bool R5 = false>
 __device__ __forceinline__ void fft_lds_w(cplx* x, int N, const cplx* __restrict__ tw, int tid, int nt)
 {
   int n = N, s = 1;
@@ -198,14 +220,21 @@ __device__ __forceinline__ void fft_lds_w(cplx* x, int N, const cplx* __restrict
     n /= 3;
     s *= 3;
   }
+  if constexpr (R5) {
+    while (n % 5 == 0) {
+      fft_pass<5, INV, WIDE>(x, N, n, s, tw, tid, nt);
+      n /= 5;
+      s *= 5;
+    }
+  }
 }
-template <bool INV>
+template <bool INV, bool R5 = false>
 __device__ __forceinline__ void fft_lds(cplx* x, int N, const cplx* __restrict__ tw, int tid, int nt)
 {
   if (N <= 8 * nt)
-    fft_lds_w<INV, true>(x, N, tw, tid, nt);
+    fft_lds_w<INV, true, R5>(x, N, tw, tid, nt);
   else
-    fft_lds_w<INV, false>(x, N, tw, tid, nt);
+    fft_lds_w<INV, false, R5>(x, N, tw, tid, nt);
 }
 
 // N = 4096 = 8^4 on 512 threads (the 100 MHz / 30 kHz symbol): one radix-8 butterfly per thread and pass with every stride a

@@ -55,6 +55,8 @@ struct miphy_ctx_ext {
   std::vector<void*>                                            to_free;
   void*                                                         d_gold = nullptr; // Gold-sequence jump table (chest.hip)
   void*                                                         d_pi_il_max = nullptr; // polar interleaver pattern (polar.hip)
+  const float**                                                 d_tp_twiddles = nullptr; // transform precoding: twiddle table of 12 N_PRB points at [N_PRB]
+  float*                                                        d_low_papr12  = nullptr; // ... and r_{u,0} of length 12, [u][12] cf_t (transform_precoding.hip)
 };
 
 // A device copy of `bytes` of host memory that lives as long as the context (freed by miphy_destroy): what the context's caches hold.
@@ -72,6 +74,16 @@ int miphy_keep_device_copy(miphy_ctx* ctx, const T* src, size_t count, T** out)
 
 // Returns the device twiddle table for size N (creates and caches it).
 int miphy_get_twiddles(miphy_ctx* ctx, uint32_t N, const float** out);
+
+// Transform precoding (transform_precoding.hip). The device array of the twiddle tables of the 53 de-precoding sizes, table of 12 N_PRB points at
+// [N_PRB] (null where N_PRB is none of them), created on first use.
+int miphy_tp_twiddles(miphy_ctx* ctx, const float* const** out);
+// The host rules of a batch of transform-precoded DM-RS jobs (MIPHY_EINVAL / MIPHY_EUNSUPP and a message that begins with `who`), its widest allocation
+// and largest port count; and the pilots kernel on staged jobs: with base_out, a copy of the base records for chest_kernel with the pilots of job i at
+// i * stride (cf_t) of `pilots`, a job that breaks a rule without receive ports; without, the pilots at the jobs' pilots_offset.
+int miphy_tp_chest_validate(const char* who, const miphy_pusch_chest_tp_job* jobs, uint32_t n, unsigned& max_nprb, unsigned& max_ports);
+int miphy_tp_pilots_launch(miphy_ctx* ctx, const miphy_pusch_chest_tp_job* d_jobs, uint32_t n, float* pilots, miphy_pusch_chest_job* base_out, uint32_t stride,
+                           hipStream_t s);
 
 // miphy_uci_polar_decode_list_batch (uci_polar.hip) for a caller inside the library whose status bytes sit in records of its own: the
 // verdict of field i goes to status[status_index[i]] (status_index null: status[i]). `who` names the caller in the error messages.

@@ -16,6 +16,7 @@
 #include "demod_device.h"
 #include "equalize_device.h"
 #include "mod_device.h"
+#include "tp_device.h"
 #include "miphy_ext.h"
 #include "tables/nr_demod_tables.h"
 #include <cmath>
@@ -1025,7 +1026,227 @@ int pusch_demodulate(const char* who, miphy_ctx* ctx, const JOB* jobs, int jobs_
   return MIPHY_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ transform precoding (DFT-s-OFDM, TS 38.211 6.3.1.4)
+// Beyond the 23.5 reference: one workgroup per (transmission, data OFDM symbol) equalises the symbol's M = 12 N_PRB elements into LDS (zf_prepare / zf_apply
+// on one layer: the arithmetic of the stand-alone equaliser), de-precodes them there (tp_device.h: the function of the stand-alone de-precoder) and
+// runs the soft demapper and descrambler above on y[n] with the symbol's one noise variance. Every data symbol has M elements (no data on a DM-RS symbol), so
+// the r-th data symbol owns the codeword elements r M ... r M + M - 1.
+
+// What a transform-precoded job must satisfy beyond PUSCH_DEMOD_LAYERS_RULES on one layer (contiguous, nprb: what tp_contiguous found).
+#define PUSCH_DEMOD_TP_RULES(R)                                                                                                             \
+  R(j.dmrs_type == 1, "transform precoding needs DM-RS type 1")                                                                             \
+  R(j.nof_cdm_groups_without_data == 2, "transform precoding needs two CDM groups without data (no data on a DM-RS symbol)")                \
+  R(contiguous, "transform precoding needs a contiguous allocation")                                                                        \
+  R(tp_nprb_ok(nprb), "transform precoding needs 2^a*3^b*5^c <= 270 PRBs, the allocation holds %u", nprb)
+
+__device__ __forceinline__ bool pusch_demod_tp_job_ok(const miphy_pusch_demod_job& j, bool have_ph, unsigned& first, unsigned& nprb)
+{
+  const unsigned L = 1;
+#define PUSCH_RULE_HOLDS(cond, ...) &&(cond)
+  if (!(true PUSCH_DEMOD_LAYERS_RULES(PUSCH_RULE_HOLDS)))
+    return false;
+  const bool contiguous = tp_contiguous(j.rb_mask, j.grid_nof_prb, first, nprb);
+  return true PUSCH_DEMOD_TP_RULES(PUSCH_RULE_HOLDS);
+#undef PUSCH_RULE_HOLDS
+}
+
+// The M de-precoded symbols of a data symbol (x: tp_deprecode_symbol ran) to soft bits: lane t takes n = t, t + TP_THREADS, ... e0: the symbol's first
+// codeword element. EX: placeholders and the EVM term of every symbol, added per lane in ascending n, then over the wavefront by the xor tree, then
+// the four wavefronts in sequence.
+template <int MOD, bool EX>
+__device__ __forceinline__ void demod_tp_symbols(const demod_args& a, const cplx* x, int M, float scale, float v, unsigned e0, const float2* tab, float* evm_out,
+                                                 float* red, int tid)
+{
+  float evm_acc = 0.f;
+  for (int n = tid; n < M; n += TP_THREADS) {
+    const float2   y   = tp_symbol(x, n, scale);
+    const unsigned re  = e0 + (unsigned)n;
+    const uint32_t bo  = re * (uint32_t)MOD;
+    const uint64_t two = (uint64_t)a.seq[bo >> 5] | ((uint64_t)a.seq[(bo >> 5) + 1] << 32);
+    const uint32_t bits = (uint32_t)(two >> (bo & 31u));
+    int8_t*        q    = a.llr + (size_t)bo;
+    if constexpr (EX) {
+      const float t = demod_emit_exact<MOD>(y.x, y.y, v, re, bits, a.nph && demod_is_placeholder(a, re), tab, q);
+      evm_acc       = evm_acc + t;
+    } else {
+      demod_emit<MOD>(y.x, y.y, v, re, bits, tab, q);
+    }
+  }
+  if constexpr (EX) {
+    if (evm_out) { // uniform
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1)
+        evm_acc += __shfl_xor(evm_acc, off);
+      if ((tid & 63) == 0)
+        red[tid >> 6] = evm_acc;
+      __syncthreads();
+      if (tid == 0)
+        *evm_out = ((red[0] + red[1]) + red[2]) + red[3];
+    }
+  }
+}
+
+// grid (transmissions, 14 OFDM symbols); dynamic LDS: the padded buffer of the widest allocation of the batch.
+template <bool EX>
+__global__ void __launch_bounds__(TP_THREADS) pusch_demod_tp_kernel(const miphy_pusch_demod_job* __restrict__ jobs, const float2* __restrict__ grid,
+                                                                    const float2* __restrict__ ce, const float* __restrict__ scalars, int8_t* __restrict__ llr,
+                                                                    const uint32_t* __restrict__ seq, uint32_t stride, const float* const* __restrict__ tws,
+                                                                    const uint16_t* __restrict__ placeholders, float* __restrict__ evm_sums)
+{
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) unsigned char tp_smem[];
+  __shared__ float2 tab[64];
+  __shared__ float  red[8];
+  cplx*             x = reinterpret_cast<cplx*>(tp_smem);
+  unsigned          first = 0, nprb = 0;
+  if (!pusch_demod_tp_job_ok(jobs[blockIdx.x], EX && placeholders, first, nprb)) // uniform: a device-resident job the host has not seen is skipped
+    return;
+  const demod_job_words j   = demod_load_job(jobs + blockIdx.x);
+  const int             tid = threadIdx.x, sy = blockIdx.y;
+  const int             start = j.start_symbol(), end = start + j.nof_symbols();
+  const unsigned        dm    = j.dmrs_symbols_mask();
+  float*                evm_out = nullptr;
+  if constexpr (EX)
+    evm_out = evm_sums ? evm_sums + j.evm_offset() + sy : nullptr;
+  if (sy < start || sy >= end || ((dm >> sy) & 1u)) { // no data on this symbol
+    if (evm_out && tid == 0)
+      *evm_out = 0.f;
+    return;
+  }
+  const int             M  = 12 * (int)nprb;
+  const unsigned        r  = (unsigned)__popc(~dm & ((1u << sy) - 1u) & ~((1u << start) - 1u)); // data symbols in front of this one
+  const demod_tab_entry te = demod_table_entry(j.mod(), tid);
+  const float           noise_var = scalars[j.scalars_offset() + 2];
+  const int             nsc = j.grid_nof_prb() * 12, np = j.nof_rx_ports();
+  const int             rows = j.ce_compact() ? 1 : j.ce_nof_symbols(), row = j.ce_compact() ? 0 : sy;
+  const float2*         g  = grid + j.grid_offset();
+  const float2*         hc = ce + j.ce_offset();
+  const uint32_t        rxp = j.rx_ports();
+  tp_var_acc            acc;
+  // four elements of a lane at a time: their samples and coefficients are requested together (unconditionally: a lane behind the end repeats the last
+  // element and drops what it computes), then equalised in ascending order
+  constexpr int B = 4;
+#pragma unroll 1
+  for (int k0 = tid; k0 < M; k0 += B * TP_THREADS) {
+    float2 h[B][1][4], y[B][4];
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      const int sc = (int)first * 12 + min(k0 + b * TP_THREADS, M - 1);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        h[b][0][p] = (p < np) ? hc[((size_t)p * rows + row) * nsc + sc] : make_float2(0.f, 0.f);
+        y[b][p]    = (p < np) ? g[((size_t)((rxp >> (8 * p)) & 0xffu) * 14 + sy) * nsc + sc] : make_float2(0.f, 0.f);
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      const int k = k0 + b * TP_THREADS;
+      if (k < M) {
+        float2         xo[1];
+        zf_prepared<1> q;
+        zf_prepare<1>(h[b], np, noise_var, 1.0f, q);
+        zf_apply<1>(h[b], np, y[b], q, xo);
+        tp_put(x, k, xo[0], q.nvar[0], acc);
+      }
+    }
+  }
+  demod_table_store(tab, te); // (made visible by the barriers of the transform)
+  const float v     = tp_deprecode_symbol(x, M, reinterpret_cast<const cplx*>(tws[nprb]), acc, red, tid);
+  const float scale = tp_scale(M);
+  demod_args  a;
+  a.llr = llr + j.llr_offset();
+  a.seq = seq + (size_t)blockIdx.x * stride;
+  a.nph = 0, a.ph = nullptr;
+  if constexpr (EX) {
+    a.nph = placeholders ? (int)j.nof_placeholders() : 0;
+    a.ph  = placeholders ? placeholders + j.placeholders_offset() : nullptr;
+  }
+  const unsigned e0 = r * (unsigned)M;
+  switch (j.mod()) {
+    case 8:
+      demod_tp_symbols<8, EX>(a, x, M, scale, v, e0, tab, evm_out, red, tid);
+      break;
+    case 6:
+      demod_tp_symbols<6, EX>(a, x, M, scale, v, e0, tab, evm_out, red, tid);
+      break;
+    case 4:
+      demod_tp_symbols<4, EX>(a, x, M, scale, v, e0, tab, evm_out, red, tid);
+      break;
+    case 2:
+      demod_tp_symbols<2, EX>(a, x, M, scale, v, e0, tab, evm_out, red, tid);
+      break;
+    default:
+      demod_tp_symbols<1, EX>(a, x, M, scale, v, e0, tab, evm_out, red, tid);
+      break;
+  }
+}
+
+int pusch_demodulate_tp(const char* who, miphy_ctx* ctx, const miphy_pusch_demod_job* jobs, int jobs_on_device, uint32_t n, const float* grid, const float* ce,
+                        const float* scalars, int8_t* llr, const uint16_t* placeholders, float* evm_sums, bool ex, void* stream)
+{
+  MIPHY_REQUIRE(ctx && jobs && grid && ce && scalars && llr, "miphy_%s_batch: null argument", who);
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "%s: batch too large (max 65535 transmissions per call)", who);
+  uint32_t   max_nprb = TP_MAX_PRB; // device-resident jobs: the widest allocation
+  const bool have_ph  = placeholders != nullptr;
+  bool       extras   = have_ph || evm_sums;
+  if (!jobs_on_device) {
+    max_nprb = 1;
+    extras   = evm_sums != nullptr;
+    for (uint32_t i = 0; i < n; ++i) {
+      const miphy_pusch_demod_job& j = jobs[i];
+      const unsigned               L = 1;
+#define PUSCH_RULE_REQUIRE(cond, msg, ...) MIPHY_REQUIRE(cond, "%s: job %u: " msg, who, i, ##__VA_ARGS__);
+      PUSCH_DEMOD_LAYERS_RULES(PUSCH_RULE_REQUIRE)
+      unsigned   first, nprb;
+      const bool contiguous = tp_contiguous(j.rb_mask, j.grid_nof_prb, first, nprb);
+      PUSCH_DEMOD_TP_RULES(PUSCH_RULE_REQUIRE)
+#undef PUSCH_RULE_REQUIRE
+      max_nprb = std::max(max_nprb, nprb);
+      extras |= j.nof_placeholders != 0;
+    }
+  }
+  hipStream_t         s   = (hipStream_t)stream;
+  const gold_tables*  gt  = nullptr;
+  const float* const* tws = nullptr;
+  int                 rc;
+  if ((rc = miphy_get_gold_tables(ctx, &gt)) || (rc = miphy_tp_twiddles(ctx, &tws)))
+    return rc;
+  const void* d_jobs = nullptr;
+  if ((rc = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pusch_demod_job) * (size_t)n, s, &d_jobs)))
+    return rc;
+  const uint32_t stride = (uint32_t)SEQ_STRIDE;
+  void*          work   = nullptr;
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_SEQUENCES, (size_t)n * stride * sizeof(uint32_t), &work)))
+    return rc;
+  uint32_t*   seq = static_cast<uint32_t*>(work);
+  const auto* dj  = (const miphy_pusch_demod_job*)d_jobs;
+  hipLaunchKernelGGL(pusch_seq_kernel<miphy_pusch_demod_job>, dim3(n, 1), dim3(SCR_THREADS), 0, s, dj, gt, seq, stride, have_ph);
+  const size_t lds = fft_lds_bytes(12 * (size_t)max_nprb);
+  if (extras)
+    hipLaunchKernelGGL(pusch_demod_tp_kernel<true>, dim3(n, 14), dim3(TP_THREADS), lds, s, dj, (const float2*)grid, (const float2*)ce, scalars, llr,
+                       (const uint32_t*)seq, stride, tws, placeholders, evm_sums);
+  else
+    hipLaunchKernelGGL(pusch_demod_tp_kernel<false>, dim3(n, 14), dim3(TP_THREADS), lds, s, dj, (const float2*)grid, (const float2*)ce, scalars, llr,
+                       (const uint32_t*)seq, stride, tws, placeholders, evm_sums);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
+}
+
 } // namespace
+
+extern "C" int miphy_pusch_demodulate_tp_batch_ex(miphy_ctx* ctx, const miphy_pusch_demod_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                                  const float* ce, const float* scalars, int8_t* llr, const uint16_t* placeholders, float* evm_sums, void* stream)
+{
+  return pusch_demodulate_tp("pusch_demodulate_tp", ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, placeholders, evm_sums, true, stream);
+}
+
+extern "C" int miphy_pusch_demodulate_tp_batch(miphy_ctx* ctx, const miphy_pusch_demod_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                               const float* ce, const float* scalars, int8_t* llr, void* stream)
+{
+  return pusch_demodulate_tp("pusch_demodulate_tp", ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, nullptr, nullptr, false, stream);
+}
 
 extern "C" uint32_t miphy_pusch_demod_nof_llr(const miphy_pusch_demod_job* j)
 {

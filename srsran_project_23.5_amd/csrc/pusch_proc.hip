@@ -4,7 +4,8 @@
 // itself restricts the rest: DM-RS type 1, two CDM groups without data, one layer: pusch_processor_impl.cpp:96-104,331-345).
 // This is host-side composition of miphy_dmrs_pusch_estimate_batch, miphy_pusch_demodulate_batch and miphy_pusch_decode_batch
 // with the parameters the reference derives (DM-RS scaling from the SCH-to-DM-RS power ratio, codeword length from the allocation);
-// with multiplexed UCI, miphy_ulsch_demultiplex_batch between the last two. One codeword on 1..4 layers goes through the layered stages.
+// with multiplexed UCI, miphy_ulsch_demultiplex_batch between the last two. One codeword on 1..4 layers goes through the layered stages, a
+// transform-precoded PUSCH (DFT-s-OFDM) through miphy_dmrs_pusch_estimate_tp_batch and miphy_pusch_demodulate_tp_batch.
 #include "miphy_ext.h"
 #include <cmath>
 #include <vector>
@@ -29,9 +30,12 @@ __global__ void zero_results_kernel(miphy_pusch_result* __restrict__ r, uint32_t
 }
 
 // What the _ex processors enqueue for a batch, built once from the PDUs: the one-layer entry point (lpdus == NULL: every PDU on one layer, 20 scalars
-// per PDU, the one-layer rules) and the layered one (the layer count of each PDU, 80 scalars, the layered rules) differ in nothing else.
+// per PDU, the one-layer rules) and the layered one (the layer count of each PDU, 80 scalars, the layered rules) differ in nothing else. The waveform:
+// with tpdus (transform precoding: one layer, 20 scalars) the estimator jobs carry the hopping mode (tcj) and the PDUs are held to the rules of the two
+// transform-precoded stages.
 struct pusch_batch {
   std::vector<miphy_pusch_chest_job>        cj;
+  std::vector<miphy_pusch_chest_tp_job>     tcj;      // transform precoding: cj with the hopping mode
   std::vector<miphy_pusch_demod_layers_job> dj;
   std::vector<miphy_pusch_tb_desc>          tb;
   std::vector<miphy_ulsch_demux_job>        xj;       // PDUs with multiplexed UCI
@@ -41,12 +45,13 @@ struct pusch_batch {
   size_t                                    ce_elems = 0, llr_bytes = 0, sch_bytes = 0;
 };
 
-int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus, const miphy_pusch_uci* uci, uint32_t n, bool have_uci_out,
-                      pusch_batch& b)
+int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus, const miphy_pusch_tp_pdu* tpdus, const miphy_pusch_uci* uci, uint32_t n,
+                      bool have_uci_out, pusch_batch& b)
 {
   b.cj.resize(n), b.dj.resize(n), b.nof_sym.resize(n);
+  const bool strict = lpdus || tpdus; // the entry points beyond the reference check what their stages would only find once the estimator is enqueued
   for (uint32_t i = 0; i < n; ++i) {
-    const miphy_pusch_pdu& p = lpdus ? lpdus[i].base : pdus[i];
+    const miphy_pusch_pdu& p = lpdus ? lpdus[i].base : (tpdus ? tpdus[i].base : pdus[i]);
     const unsigned         L = lpdus ? lpdus[i].nof_tx_layers : 1;
     const miphy_pusch_uci* u = uci ? &uci[i] : nullptr;
     const bool has_uci = u && (u->nof_harq_ack_bits || u->nof_csi_part1_bits || u->nof_csi_part2_bits);
@@ -55,18 +60,21 @@ int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu*
     if (lpdus) {
       MIPHY_REQUIRE(L >= 1 && L <= 4, "pusch_process: PDU %u: invalid number of layers %u", i, L);
       MIPHY_REQUIRE(L <= p.nof_rx_ports, "pusch_process: PDU %u: %u layers on %u receive ports", i, L, (unsigned)p.nof_rx_ports);
-      MIPHY_REQUIRE(p.numerology <= 4, "pusch_process: PDU %u: invalid numerology", i);
     }
+    if (strict)
+      MIPHY_REQUIRE(p.numerology <= 4, "pusch_process: PDU %u: invalid numerology", i);
     MIPHY_REQUIRE(p.nof_symbols >= 1 && p.start_symbol + p.nof_symbols <= 14, "pusch_process: PDU %u: invalid time allocation", i);
-    if (!lpdus)
+    if (!strict)
       MIPHY_REQUIRE(p.dmrs_symbols_mask != 0, "pusch_process: PDU %u: no DM-RS symbol", i);
     MIPHY_REQUIRE(p.grid_nof_prb >= 1 && p.grid_nof_prb <= 275, "pusch_process: PDU %u: invalid grid width", i);
-    if (lpdus) {
+    if (strict) {
       unsigned nds = 0;
       for (unsigned l = p.start_symbol; l < (unsigned)p.start_symbol + p.nof_symbols; ++l)
         nds += (p.dmrs_symbols_mask >> l) & 1;
       MIPHY_REQUIRE(nds >= 1 && nds <= 4, "pusch_process: PDU %u: %u DM-RS symbols in the allocation (1..4 supported)", i, nds);
       MIPHY_REQUIRE(p.mod == 1 || p.mod == 2 || p.mod == 4 || p.mod == 6 || p.mod == 8, "pusch_process: PDU %u: invalid modulation", i);
+      if (tpdus)
+        MIPHY_REQUIRE(p.n_id < 1024 && p.rnti < 65536, "pusch_process: PDU %u: invalid scrambling identifier or RNTI", i);
       if (has_tb) { // (the decoder's rules on the transport block, which it would only find behind the stages in front of it)
         MIPHY_REQUIRE((p.bg == 1 || p.bg == 2) && p.rv <= 3 && p.nof_ldpc_iterations > 0, "pusch_process: PDU %u: invalid base graph, redundancy version or iterations", i);
         miphy_sch_segmentation sg = {};
@@ -154,17 +162,27 @@ int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu*
       t.llr_offset = (t.llr_offset & ~((uint64_t)1 << 63)) + b.llr_bytes;
   for (auto& x : b.xj)
     x.sch_offset += b.llr_bytes;
+  if (tpdus) { // the rules of the transform-precoded stages on the allocation and the DM-RS (contiguous, 2^a 3^b 5^c PRBs, n_ID^RS, hopping mode)
+    b.tcj.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      b.tcj[i]         = {};
+      b.tcj[i].base    = b.cj[i];
+      b.tcj[i].hopping = tpdus[i].hopping;
+    }
+    unsigned max_nprb, max_ports;
+    return miphy_tp_chest_validate("pusch_process_tp", b.tcj.data(), n, max_nprb, max_ports);
+  }
   return MIPHY_OK;
 }
 
 // Estimator, demodulator with placeholders and EVM, EVM finish (divisor: data REs x layers), demultiplexer and decoder on one stream. Every rule is
 // checked before anything is enqueued (pusch_batch_build); the stages check their own rules again on the jobs built there.
-int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus, const miphy_pusch_uci* uci, uint32_t n,
-                     const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results,
+int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus, const miphy_pusch_tp_pdu* tpdus, const miphy_pusch_uci* uci,
+                     uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results,
                      float* scalars_out, int8_t* uci_llr_out, float* evm_out, hipStream_t s)
 {
   pusch_batch b;
-  int         rc = pusch_batch_build(pdus, lpdus, uci, n, uci_llr_out != nullptr, b);
+  int         rc = pusch_batch_build(pdus, lpdus, tpdus, uci, n, uci_llr_out != nullptr, b);
   if (rc)
     return rc;
   // [placeholders | data REs || channel estimates cf_t | codeword LLRs, UL-SCH LLRs of the PDUs with UCI | EVM sums] in a workspace of the
@@ -192,10 +210,17 @@ int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pu
     std::vector<miphy_pusch_demod_job> dj(n);
     for (uint32_t i = 0; i < n; ++i)
       dj[i] = b.dj[i].base;
-    if ((rc = miphy_dmrs_pusch_estimate_batch(ctx, b.cj.data(), 0, n, grid, d_ce, scalars_out, s)))
-      return rc;
-    if ((rc = miphy_pusch_demodulate_batch_ex(ctx, dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, d_ph, d_evm, s)))
-      return rc;
+    if (tpdus) {
+      if ((rc = miphy_dmrs_pusch_estimate_tp_batch(ctx, b.tcj.data(), 0, n, grid, d_ce, scalars_out, s)))
+        return rc;
+      if ((rc = miphy_pusch_demodulate_tp_batch_ex(ctx, dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, d_ph, d_evm, s)))
+        return rc;
+    } else {
+      if ((rc = miphy_dmrs_pusch_estimate_batch(ctx, b.cj.data(), 0, n, grid, d_ce, scalars_out, s)))
+        return rc;
+      if ((rc = miphy_pusch_demodulate_batch_ex(ctx, dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, d_ph, d_evm, s)))
+        return rc;
+    }
   }
   if (evm_out) {
     hipLaunchKernelGGL(evm_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, s, d_evm, d_nre, evm_out, n);
@@ -239,7 +264,7 @@ extern "C" int miphy_pusch_process_layers_batch_ex(miphy_ctx* ctx, const miphy_p
                 "miphy_pusch_process_layers_batch: null argument");
   if (n == 0)
     return MIPHY_OK;
-  return pusch_process_ex(ctx, nullptr, pdus, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+  return pusch_process_ex(ctx, nullptr, pdus, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
                           (hipStream_t)stream);
 }
 
@@ -259,6 +284,27 @@ extern "C" int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pd
                 "miphy_pusch_process_batch: null argument");
   if (n == 0)
     return MIPHY_OK;
-  return pusch_process_ex(ctx, pdus, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+  return pusch_process_ex(ctx, pdus, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
                           (hipStream_t)stream);
+}
+
+// A transform-precoded PUSCH (DFT-s-OFDM), with multiplexed UCI and the EVM (include/miphy.h).
+extern "C" int miphy_pusch_process_tp_batch_ex(miphy_ctx* ctx, const miphy_pusch_tp_pdu* pdus, const miphy_pusch_uci* uci, uint32_t n, const float* grid,
+                                               int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results,
+                                               float* scalars_out, int8_t* uci_llr_out, float* evm_out, void* stream)
+{
+  MIPHY_REQUIRE(ctx && pdus && grid && harq_softbits && harq_msgs && harq_crc_ok && tb_out && results && scalars_out,
+                "miphy_pusch_process_tp_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  return pusch_process_ex(ctx, nullptr, nullptr, pdus, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+                          (hipStream_t)stream);
+}
+
+extern "C" int miphy_pusch_process_tp_batch(miphy_ctx* ctx, const miphy_pusch_tp_pdu* pdus, uint32_t n, const float* grid, int8_t* harq_softbits,
+                                            uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results, float* scalars_out,
+                                            void* stream)
+{
+  return miphy_pusch_process_tp_batch_ex(ctx, pdus, nullptr, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, nullptr, nullptr,
+                                         stream);
 }

@@ -148,6 +148,15 @@ def lib():
         if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_pusch_process_layers_batch_ex"):  # (likewise)
             l.miphy_pusch_demodulate_layers_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 7
             l.miphy_pusch_process_layers_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 10
+        if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_pusch_demodulate_tp_batch"):  # (likewise)
+            l.miphy_transform_deprecode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
+            l.miphy_pusch_demodulate_tp_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
+            l.miphy_pusch_demodulate_tp_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 7
+            l.miphy_low_papr_sequence.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+            l.miphy_dmrs_pusch_tp_pilots_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+            l.miphy_dmrs_pusch_estimate_tp_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
+            l.miphy_pusch_process_tp_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 8
+            l.miphy_pusch_process_tp_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 10
         l.miphy_polar_block_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("miphy_ofdm_demodulate_symbols", "miphy_ofdm_modulate_symbols"):
             getattr(l, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -248,6 +257,21 @@ def pusch_demod_layers_nof_llr(job):
     """Codeword length (data REs x layers x bits per symbol) of one PuschDemodLayersJob record; 0 for an invalid one."""
     a = np.ascontiguousarray(np.asarray(job, dtype=PuschDemodLayersJob).reshape(1))
     return int(lib().miphy_pusch_demod_layers_nof_llr(a.ctypes.data_as(C.c_void_p)))
+
+
+# Transform precoding (DFT-s-OFDM). Mirrors miphy_transform_deprecode_job and miphy_pusch_chest_tp_job.
+TransformDeprecodeJob = np.dtype([("M", np.uint32), ("nof_symbols", np.uint32), ("eq_symbols_offset", np.uint64), ("eq_noise_vars_offset", np.uint64),
+                                  ("out_symbols_offset", np.uint64), ("out_noise_var_offset", np.uint64)], align=True)
+assert TransformDeprecodeJob.itemsize == 40
+PuschChestTpJob = np.dtype([("base", PuschChestJob), ("hopping", np.uint8), ("reserved", np.uint8, 7)], align=True)
+assert PuschChestTpJob.itemsize == 160 and PuschChestTpJob.fields["hopping"][1] == 152, PuschChestTpJob.itemsize
+
+
+def low_papr_sequence(u, v, length):
+    """r_{u,v}(n), alpha = 0, of TS 38.211 5.2.2 as complex64 (host computation in the library): length 12, 30 or 6 N >= 36."""
+    out = np.zeros(int(length), dtype=np.complex64)
+    check(lib().miphy_low_papr_sequence(int(u), int(v), int(length), out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 # Mirrors miphy_re_pattern / miphy_pdsch_mod_job / miphy_dmrs_pdsch_job.
@@ -407,6 +431,11 @@ assert PuschPdu.itemsize == 112 and PuschPdu.fields["rb_mask"][1] == 56, PuschPd
 # Mirrors miphy_pusch_layers_pdu.
 PuschLayersPdu = np.dtype([("base", PuschPdu), ("nof_tx_layers", np.uint8), ("reserved", np.uint8, 7)], align=True)
 assert PuschLayersPdu.itemsize == 120 and PuschLayersPdu.fields["nof_tx_layers"][1] == 112, PuschLayersPdu.itemsize
+
+
+# Mirrors miphy_pusch_tp_pdu: a transform-precoded PUSCH.
+PuschTpPdu = np.dtype([("base", PuschPdu), ("hopping", np.uint8), ("reserved", np.uint8, 7)], align=True)
+assert PuschTpPdu.itemsize == 120 and PuschTpPdu.fields["hopping"][1] == 112, PuschTpPdu.itemsize
 
 
 # Mirrors miphy_pusch_uci.
@@ -918,6 +947,61 @@ class Context:
         check(lib().miphy_pusch_demodulate_layers_batch_ex(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _dptr(llr),
                                                            _dptr(placeholders) if placeholders is not None else None,
                                                            _dptr(evm_sums) if evm_sums is not None else None, _stream_ptr(stream)))
+
+    # ------------------------------------------------------------------ PUSCH with transform precoding (DFT-s-OFDM)
+    def transform_deprecode_batch(self, jobs, eq_symbols, eq_noise_vars, out_symbols, out_noise_var, stream=None):
+        """The de-precoding IDFT of M = 12 N_PRB points and the mean noise variance per row: a batch of TransformDeprecodeJob records."""
+        jobs, n, ptr, on_dev = self._descs(jobs, TransformDeprecodeJob)
+        check(lib().miphy_transform_deprecode_batch(self.h, ptr, on_dev, n, _dptr(eq_symbols), _dptr(eq_noise_vars), _dptr(out_symbols),
+                                                    _dptr(out_noise_var), _stream_ptr(stream)))
+
+    def pusch_demodulate_tp_batch(self, jobs, grid, ce, scalars, llr, stream=None):
+        """PUSCH demodulator for a transform-precoded transmission: a batch of PuschDemodJob records (contiguous allocation of 2^a 3^b 5^c PRBs,
+        DM-RS type 1, two CDM groups without data)."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschDemodJob)
+        check(lib().miphy_pusch_demodulate_tp_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _dptr(llr), _stream_ptr(stream)))
+
+    def pusch_demodulate_tp_batch_ex(self, jobs, grid, ce, scalars, llr, placeholders=None, evm_sums=None, stream=None):
+        """pusch_demodulate_tp_batch with the repetition placeholders (device uint16) and / or the per-symbol EVM sums (device float32, 14 per job at
+        evm_offset, over the de-precoded symbols)."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschDemodJob)
+        check(lib().miphy_pusch_demodulate_tp_batch_ex(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _dptr(llr),
+                                                       _dptr(placeholders) if placeholders is not None else None,
+                                                       _dptr(evm_sums) if evm_sums is not None else None, _stream_ptr(stream)))
+
+    def dmrs_pusch_tp_pilots_batch(self, jobs, pilots, stream=None):
+        """The low-PAPR DM-RS of a batch of PuschChestTpJob records, [DM-RS symbol][6 N_PRB] complex64 at each job's pilots_offset."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschChestTpJob)
+        check(lib().miphy_dmrs_pusch_tp_pilots_batch(self.h, ptr, on_dev, n, _dptr(pilots), _stream_ptr(stream)))
+
+    def dmrs_pusch_estimate_tp_batch(self, jobs, grid, ce, scalars, stream=None, max_ports=0):
+        """DM-RS estimator of a transform-precoded PUSCH: jobs PuschChestTpJob, outputs and the port hint as dmrs_pusch_estimate_batch."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschChestTpJob)
+        if on_dev:
+            on_dev |= int(max_ports) << 8
+        check(lib().miphy_dmrs_pusch_estimate_tp_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _stream_ptr(stream)))
+
+    def pusch_process_tp_batch(self, pdus, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, stream=None):
+        """A transform-precoded PUSCH. pdus: numpy PuschTpPdu array (host); results and scalars (float32 n x 20) as pusch_process_batch."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PuschTpPdu
+        pdus = np.ascontiguousarray(pdus)
+        check(lib().miphy_pusch_process_tp_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, _dptr(grid), _dptr(harq_softbits), _dptr(harq_msgs),
+                                                 _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars), _stream_ptr(stream)))
+
+    def pusch_process_tp_batch_ex(self, pdus, uci, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, uci_llr, evm, stream=None):
+        """pusch_process_tp_batch for PDUs with multiplexed UCI (uci: numpy PuschUci array or None) and the EVM (evm: float32 device tensor of n or
+        None). The field jobs behind it: pusch_uci_jobs(pdus["base"], uci)."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PuschTpPdu
+        pdus = np.ascontiguousarray(pdus)
+        up = None
+        if uci is not None:
+            assert isinstance(uci, np.ndarray) and uci.dtype == PuschUci and uci.size == pdus.size
+            uci = np.ascontiguousarray(uci)
+            up = C.c_void_p(uci.ctypes.data)
+        check(lib().miphy_pusch_process_tp_batch_ex(self.h, C.c_void_p(pdus.ctypes.data), up, pdus.size, _dptr(grid), _dptr(harq_softbits),
+                                                    _dptr(harq_msgs), _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars),
+                                                    _dptr(uci_llr) if uci_llr is not None else None, _dptr(evm) if evm is not None else None,
+                                                    _stream_ptr(stream)))
 
     def polar_block_batch(self, code, op, param, n, x, out, stream=None):
         check(lib().miphy_polar_block_batch(self.h, C.byref(code) if code is not None else None, op, param, n, _dptr(x), _dptr(out), _stream_ptr(stream)))
