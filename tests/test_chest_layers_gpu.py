@@ -1,120 +1,21 @@
 """GPU: miphy_dmrs_pusch_estimate_layers_batch against the float64 restatement of tests/pusch_layers_estimator_cases.py, with the tolerances of
-tests/test_chest_gpu.py (coefficients 1e-4 of the largest estimate, RSRP / EPRE / noise / SNR 1e-4 relative, time alignment 1.01 IDFT taps). The
+tests/chest_batch.py (coefficients 1e-4 of the largest estimate, RSRP / EPRE / noise / SNR 1e-4 relative, time alignment 1.01 IDFT taps). The
 grids carry that file's background noise, so no scalar compared is a difference of nearly equal numbers. Sentinels: estimate 1.0, scalars -77."""
 import numpy as np
 import pytest
 
 import pusch_layers_estimator_cases as E
+from chest_batch import SC_SENTINEL, SCATTERED, run as run_batch, select_ports
 
 pytestmark = pytest.mark.gpu
 
-CE_GUARD, SC_GUARD, SC_SENTINEL = 5, 3, -77.0
-_expected = {}  # restatement per case object, computed once
 
-
-def expected(case, sel):
-    key = (id(case), tuple(sel) if sel is not None else None)
-    if key not in _expected:
-        g = case[-1]
-        _expected[key] = (case, E.estimate(*(case if sel is None else case[:-1] + (np.ascontiguousarray(g[sel]),))))
-    return _expected[key][1]
-
-
-def select_ports(case, sel):
-    g = case[-1].copy()
-    assert g.shape[0] == 4
-    g[[p for p in range(4) if p not in sel]] = np.nan
-    return case[:-1] + (g,), list(sel)
-
-
-def run(ctx, cases, sels=None, compact=False, device=None, room_4x4=False, check=True, entry="dmrs_pusch_estimate_layers_batch", hop=None):
-    """The cases as one batch (tests/test_chest_gpu.py's run() for the layered entry point). Returns per job (estimate [nl][ports][rows][nsc],
-    scalars [ports][nl][5]) as written; everything outside the records must keep its sentinel."""
-    import torch
-    import miphy
-    sels = sels or [None] * len(cases)
-    jobs = np.zeros(len(cases), dtype=miphy.PuschChestJob)
-    grids, g_off, ce_off, sc_off, shapes = [], 0, CE_GUARD, SC_GUARD, []
-    for i, ((mu, slot, t2, scr, nscid, scaling, sm, rb, first, nof, nl, g), sel) in enumerate(zip(cases, sels)):
-        nsc = g.shape[2]
-        nports = g.shape[0] if sel is None else len(sel)
-        j = jobs[i]
-        j["numerology"], j["slot_in_frame"], j["scrambling_id"], j["scaling"] = mu, slot, scr, scaling
-        j["n_scid"], j["nof_tx_layers"], j["nof_rx_ports"], j["first_symbol"], j["nof_symbols"] = nscid, nl, nports, first, nof
-        if sel is None:
-            j["rx_ports"] = [0, 1, 2, 3]
-        else:
-            spare = [p for p in range(4) if p not in sel]
-            j["rx_ports"] = list(sel) + spare[:1] * (4 - len(sel))
-        j["ce_compact"] = int(compact)
-        j["symbols_mask"] = sum(int(b) << l for l, b in enumerate(sm))
-        j["grid_nof_prb"] = rb.size
-        m = [0] * 5
-        for r in np.nonzero(rb)[0]:
-            m[r >> 6] |= 1 << (int(r) & 63)
-        j["rb_mask"] = m
-        if hop is not None and i == hop[0]:
-            j["hop_symbol"], j["rb_mask2"] = hop[1], m
-        j["grid_offset"], j["ce_offset"], j["scalars_offset"] = g_off, ce_off, sc_off
-        grids.append(g.reshape(-1))
-        g_off += g.size
-        rows = 1 if compact else first + nof
-        shapes.append((nl, nports, rows, nsc))
-        ce_off += (16 if room_4x4 else nl * nports) * rows * nsc + CE_GUARD
-        sc_off += (16 if room_4x4 else nports * nl) * 5 + SC_GUARD
-    g_d = torch.from_numpy(np.concatenate(grids)).cuda()
-    ce_d = torch.ones(ce_off, dtype=torch.complex64, device="cuda")
-    sc_d = torch.full((sc_off,), SC_SENTINEL, dtype=torch.float32, device="cuda")
-    call = getattr(ctx, entry)
-    if hop is not None:
-        with pytest.raises(RuntimeError, match="miphy error -1"):
-            call(jobs, g_d, ce_d, sc_d)
-        torch.cuda.synchronize()
-        assert bool((ce_d == 1.0).all()) and bool((sc_d == SC_SENTINEL).all()), "a refused batch writes nothing"
-        return None
-    if device is None:
-        call(jobs, g_d, ce_d, sc_d)
-    else:
-        hint = dict(max_ports=int(jobs["nof_rx_ports"].max()), max_layers=int(jobs["nof_tx_layers"].max())) if device == "hint" else {}
-        call(torch.from_numpy(jobs.view(np.uint8)).cuda(), g_d, ce_d, sc_d, **hint)
-    torch.cuda.synchronize()
-    ce, sc = ce_d.cpu().numpy(), sc_d.cpu().numpy()
-    used_ce, used_sc = np.zeros(ce.size, bool), np.zeros(sc.size, bool)
-    out = []
-    for i, shp in enumerate(shapes):
-        c0, s0 = int(jobs[i]["ce_offset"]), int(jobs[i]["scalars_offset"])
-        n_ce, n_sc = int(np.prod(shp)), shp[0] * shp[1] * 5
-        used_ce[c0:c0 + n_ce] = True
-        used_sc[s0:s0 + n_sc] = True
-        out.append((ce[c0:c0 + n_ce].reshape(shp), sc[s0:s0 + n_sc].reshape(shp[1], shp[0], 5)))
-    assert np.all(ce[~used_ce] == 1.0) and np.all(sc[~used_sc] == np.float32(SC_SENTINEL)), "written outside the jobs' records"
-    if not check:
-        return out
-    for i, (a, sel) in enumerate(zip(cases, sels)):
-        mu, rb, first = a[0], a[7], a[8]
-        exp_ce, exp_sc = expected(a, sel)
-        got_ce, got_sc = out[i]
-        mask = np.repeat(rb.astype(bool), 12)
-        if compact:
-            exp_ce = exp_ce[:, :, first:first + 1]
-        else:
-            assert np.all(got_ce[:, :, :first] == 1.0), "rows in front of the allocation are left untouched"
-            got_ce, exp_ce = got_ce[:, :, first:], exp_ce[:, :, first:]
-        err = np.abs(got_ce[..., mask] - exp_ce[..., mask]).max() / np.abs(exp_ce[..., mask]).max()
-        print("job %d: estimate error %.3g of the largest estimate" % (i, err))
-        assert err < 1e-4, (i, err)
-        assert np.all(got_ce[..., ~mask] == 1.0), "unallocated PRBs are left untouched"
-        for k in range(4):
-            rel = np.abs(got_sc[..., k] - exp_sc[..., k]) / (np.abs(exp_sc[..., k]) + 1e-30)
-            print("job %d: scalar %d relative error %.3g" % (i, k, rel.max()))
-            assert rel.max() < 1e-4, (i, k, got_sc[..., k], exp_sc[..., k])
-        tap = 1.0 / (4096 * 15000.0 * (1 << mu))
-        assert np.abs(got_sc[..., 4] - exp_sc[..., 4]).max() <= 1.01 * tap, (i, got_sc[..., 4], exp_sc[..., 4])
-    return out
+def run(ctx, cases, sels=None, entry="dmrs_pusch_estimate_layers_batch", **kw):
+    """chest_batch.run() for the layered entry point against the restatement."""
+    return run_batch(ctx, cases, entry, E.estimate, sels, **kw)
 
 
 TWO_PIECES = list(range(2, 10)) + list(range(14, 18))  # 12 PRBs: a pair must not reach across the gap, interpolation does
-SCATTERED = [63, 64, 65, 127, 128, 191, 192, 255, 256, 274]  # on a 275-PRB grid: an allocation in every 64-bit word of rb_mask
 
 
 def test_small_and_split_allocations(ctx):
@@ -208,3 +109,30 @@ def test_hopping_is_refused(ctx):
     """A host job with hop_symbol != 0: MIPHY_EINVAL, nothing enqueued -- the jobs in front of it included."""
     cases = _mixed(np.random.default_rng(69))[:3]
     run(ctx, cases, hop=(2, 7))
+
+
+def test_device_resident_jobs_that_break_a_rule(ctx):
+    """Nobody checks device-resident jobs on the host: the kernels hold them to the rules of host jobs (chest_job_rule), skip a job that breaks one
+    and still serve its neighbours. 1, 2 and 3 layers, sound and broken side by side; every breach is one that could not touch memory even if
+    the check were lost. The broken jobs' records keep their sentinels, the sound jobs give the bytes of a host run of the sound jobs alone."""
+    rng = np.random.default_rng(70)
+    cases, sels = [], []
+    for k, nl in enumerate((1, 2, 3, 1, 2, 3)):  # two ports each; three layers on two ports: two of the four ports of a case the builder can make
+        case = E.make_case(rng, 24, slice(2 + k, 8 + 2 * k), 4 if nl == 3 else 2, nl, [2, 7, 11], delay=float(k % 3), slot=k, scr=40 + k)[0]
+        case, sel = select_ports(case, [3, 1]) if nl == 3 else (case, None)
+        cases.append(case)
+        sels.append(sel)
+    sound, broken = [0, 2, 4], {1: ("scaling", 0.0), 3: ("hop_symbol", 7), 5: ("symbols_mask", 0)}
+    assert sorted(cases[i][10] for i in sound) == sorted(cases[i][10] for i in broken) == [1, 2, 3]
+
+    def breach(jobs):
+        for i, (field, value) in broken.items():
+            jobs[i][field] = value
+
+    host = run(ctx, [cases[i] for i in sound], [sels[i] for i in sound])
+    for device in ("nohint", "hint"):
+        dev = run(ctx, cases, sels, device=device, check=False, edit=breach)
+        for (hce, hsc), i in zip(host, sound):
+            assert hce.tobytes() == dev[i][0].tobytes() and hsc.tobytes() == dev[i][1].tobytes(), (device, i)
+        for i in broken:
+            assert np.all(dev[i][0] == 1.0) and np.all(dev[i][1] == np.float32(SC_SENTINEL)), (device, i, "a skipped job writes nothing")
