@@ -1271,6 +1271,74 @@ int miphy_pucch_process_batch_ex(miphy_ctx* ctx, const miphy_pucch_job* jobs /* 
                                  int8_t* llr_out /* device or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * PUCCH processor, formats 3 and 4 (DFT-s-OFDM, TS 38.211 6.3.2.6 and 6.4.1.3.3)  --  beyond the 23.5 reference, whose demodulator asserts
+ * "PUCCH Format 3 not supported" / "PUCCH Format 4 not supported" (pucch_demodulator_impl.cpp) and whose format3_configuration and
+ * format4_configuration hold nothing but the cyclic prefix. The contract is the standard, restated in numpy in tests/pucch_f34_tx.py
+ * (transmitter) and tests/pucch_f34_ref.py (receiver); the arithmetic of the receiver is stated at the top of csrc/pucch_f34.hip.
+ * n PDUs read one device grid through their windows as the PDUs of miphy_pucch_process_batch do, one workgroup each: channel estimation
+ * per port and hop on the DM-RS symbols of Table 6.4.1.3.3.2-1 (all 12 REs of a PRB, low-PAPR sequence of 12 nof_prb elements with the
+ * cyclic-shift hopping of format 1), zero forcing 1 x N, de-precoding, format-4 despreading, QPSK or pi/2-BPSK soft demapping and
+ * descrambling (c_init = rnti 2^15 + n_id_scrambling). The K = nof_harq_ack + nof_sr + nof_csi_part1 bits are decoded by the short-block
+ * detector inside the kernel (3..11 bits) or by the polar decoder behind it on the same stream (12 bits and more, list size `list_size`
+ * with the meaning it has in miphy_pucch_process_batch_ex), which stores its verdict over the status byte. Nothing waits for the device.
+ * Rules (miphy_pucch_f34_info, and therefore the batch call; MIPHY_EINVAL unless stated, the rule in miphy_last_error()):
+ * format 3 with nof_prb in {1, 3, 4, 5, 6, 8, 9, 10, 12, 15, 16}; nof_prb = 2 needs the length-24 table the library does not hold:
+ * MIPHY_EUNSUPP, as miphy_low_papr_sequence answers; format 4 with nof_prb = 1, occ_length 2 or 4, occ_index < occ_length; nof_symbols
+ * 4..14; K >= 3; nof_csi_part2 == 0 (the two-part multiplexing of TS 38.212 6.3.1.6 is not done); K <= 11: K < E; K >= 12: what
+ * miphy_uci_polar_info(K, E) says; numerology, slot, ports, BWP, PRBs and grid as for miphy_pucch_job. Normal cyclic prefix, no group
+ * or sequence hopping (u = n_id_hopping mod 30, v = 0). The code-rate limit is not a rule.
+ * E = Qm 12 nof_prb (data symbols) for format 3 and Qm (12 / occ_length) (data symbols) for format 4, Qm = 1 for pi/2-BPSK, else 2.
+ * Outputs: `payload` K bytes from payload_offset (HARQ-ACK, SR, CSI part 1), results[i] as for format 2 (detection_metric 0),
+ * `llr_out` (device or NULL) the E soft bits from llr_offset, `est_out` (device float or NULL) from est_offset (in floats) the estimate
+ * the data path used: cf_t [port][hop: 1 or 2][12 nof_prb], then nof_ports floats of noise variance. Without llr_out the soft bits of the
+ * polar-coded PDUs pass through a workspace of the context. Jobs are HOST memory only; every job is checked before anything is enqueued;
+ * n == 0 enqueues nothing. */
+typedef struct {
+  uint8_t  format;             /* 3 or 4 */
+  uint8_t  numerology;         /* 0..4 */
+  uint16_t slot;               /* slot index within the frame */
+  uint8_t  nof_ports;          /* receive ports 1..4 (ports 0 .. nof_ports - 1 of the grid window) */
+  uint8_t  start_symbol;
+  uint8_t  nof_symbols;        /* 4..14 */
+  uint8_t  intra_slot_hopping; /* 1: the first floor(nof_symbols / 2) symbols on starting_prb, the others on second_hop_prb */
+  uint16_t bwp_start_rb, bwp_size_rb;
+  uint16_t starting_prb;       /* within the BWP */
+  uint16_t second_hop_prb;     /* within the BWP, with hopping */
+  uint8_t  nof_prb;            /* format 3: see above; format 4: 1 */
+  uint8_t  pi2_bpsk;           /* 0: QPSK, 1: pi/2-BPSK */
+  uint8_t  additional_dmrs;    /* 0 or 1 */
+  uint8_t  occ_length;         /* format 4: 2 or 4 */
+  uint8_t  occ_index;          /* format 4: below occ_length */
+  uint8_t  reserved0[3];
+  uint16_t nof_harq_ack, nof_sr, nof_csi_part1, nof_csi_part2; /* K = the first three, 3 and more; CSI part 2 must be 0 */
+  uint16_t n_id_hopping;       /* 0..1023: u and the cyclic-shift hopping */
+  uint16_t n_id_scrambling;    /* 0..1023 */
+  uint16_t rnti;
+  uint16_t reserved1;
+  uint32_t grid_nprb;          /* width of the grid window in PRBs (>= bwp_start_rb + bwp_size_rb) */
+  uint32_t reserved2;
+  uint64_t grid_offset;        /* cf_t offset of the window in `grid` */
+  uint64_t payload_offset;     /* byte offset in `payload` */
+  uint64_t llr_offset;         /* int8 offset in `llr_out` */
+  uint64_t est_offset;         /* float offset in `est_out` */
+} miphy_pucch_f34_job;
+
+typedef struct {
+  uint32_t dmrs_symbols_mask;   /* bit l: symbol l of the slot carries DM-RS */
+  uint32_t nof_dmrs_symbols[2]; /* per hop ([1] = 0 without hopping) */
+  uint32_t nof_data_symbols[2]; /* per hop */
+  uint32_t M;                   /* 12 nof_prb */
+  uint32_t E;                   /* soft bits */
+  uint32_t polar;               /* 0: short block code (K <= 11), 1: polar code */
+} miphy_pucch_f34_info_t;
+
+/* Host function, no device. */
+int miphy_pucch_f34_info(const miphy_pucch_f34_job* job, miphy_pucch_f34_info_t* out);
+int miphy_pucch_process_f34_batch(miphy_ctx* ctx, const miphy_pucch_f34_job* jobs /* HOST */, uint32_t n, uint32_t list_size,
+                                  const float* grid /* device cf_t */, uint8_t* payload /* device */, miphy_pucch_result* results /* device, n */,
+                                  int8_t* llr_out /* device or NULL */, float* est_out /* device or NULL */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * PRACH detector and generator  --  replace srsran::prach_detector::detect and srsran::prach_generator::generate
  *   lib/phy/upper/channel_processors/prach_detector_simple_impl.cpp:35-169 (RSSI, per preamble: correlation in the frequency domain,
  *   unnormalised IDFT, peak of |c|^2, metric peak / (rssi preamble_power L L) against 0.07, delay sign and window),

@@ -1056,6 +1056,37 @@ private:
 /// the listed ports too, but its format-1 detector and format-2 demodulator index the grid and the estimates by position
 /// (pucch_detector_impl.cpp:264-303, pucch_demodulator_impl.cpp:93-125); the two agree only when ports[i] == i, so another list goes to
 /// the CPU processor when there is one.
+/// Formats 3 and 4 on the device: the reference's format3_configuration and format4_configuration hold nothing but the cyclic prefix and cannot
+/// express a PDU, so those process() overrides stay as they are and process_f34_batch() takes pucch_f34_configuration records instead.
+
+/// One PUCCH format 3 or 4 PDU for pucch_processor_hip::process_f34_batch: the fields of pucch_processor::format2_configuration with their
+/// meaning (\c n_id scrambles the data; there is no \c n_id_0, the DM-RS of these formats is a low-PAPR sequence) plus what the two formats add.
+struct pucch_f34_configuration {
+  srsran::optional<srsran::pucch_context>           context;
+  srsran::slot_point                                slot;
+  srsran::cyclic_prefix                             cp = srsran::cyclic_prefix::NORMAL;
+  srsran::static_vector<uint8_t, srsran::MAX_PORTS> ports;
+  unsigned                                          bwp_size_rb  = 0;
+  unsigned                                          bwp_start_rb = 0;
+  unsigned                                          starting_prb = 0;
+  srsran::optional<unsigned>                        second_hop_prb;
+  unsigned                                          nof_prb            = 1; ///< Format 3: 1, 3, 4, 5, 6, 8, 9, 10, 12, 15 or 16; format 4: 1.
+  unsigned                                          start_symbol_index = 0;
+  unsigned                                          nof_symbols        = 4; ///< 4 to 14.
+  uint16_t                                          rnti               = 0;
+  unsigned                                          n_id               = 0; ///< Data scrambling identity {0, ..., 1023}.
+  unsigned                                          nof_harq_ack       = 0;
+  unsigned                                          nof_sr             = 0;
+  unsigned                                          nof_csi_part1      = 0;
+  unsigned                                          nof_csi_part2      = 0; ///< Must be 0: CSI part 2 is not decoded on PUCCH.
+  unsigned                                          format             = 3; ///< 3 or 4.
+  bool                                              pi2_bpsk           = false;
+  bool                                              additional_dmrs    = false;
+  unsigned                                          occ_length         = 0; ///< Format 4: 2 or 4.
+  unsigned                                          occ_index          = 0; ///< Format 4: below occ_length.
+  unsigned                                          n_id_hopping       = 0; ///< Sequence group and cyclic-shift hopping identity {0, ..., 1023}.
+};
+
 class pucch_processor_hip : public srsran::pucch_processor
 {
 public:
@@ -1146,6 +1177,75 @@ public:
     auto* d_g = static_cast<float*>(c->buf(6, host.size() * sizeof(srsran::cf_t)));
     c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
     download(run(jobs, d_g), jobs, f1, f2, out1, out2);
+  }
+
+  /// A slot's PUCCH formats 3 and 4 in one launch of miphy_pucch_process_f34_batch (the list size of the processor decodes the payloads of 12 bits and
+  /// more): the grid goes to the device once, as in process_batch(); every result gets its pucch_uci_message (HARQ-ACK, SR, CSI part 1) and the CSI
+  /// exactly as process_batch() fills them for format 2. The library's rules (miphy_pucch_f34_info) are the validator: a PDU that breaks one fails the
+  /// call with the rule as message before anything is enqueued.
+  void process_f34_batch(const srsran::resource_grid_reader&          grid,
+                         srsran::span<const pucch_f34_configuration>  configs,
+                         srsran::span<srsran::pucch_processor_result> out)
+  {
+    require(out.size() == configs.size(), "pucch_processor_hip::process_f34_batch: one result per configuration.");
+    const size_t n = configs.size();
+    if (n == 0) {
+      return;
+    }
+    std::vector<miphy_pucch_f34_job> jobs(n);
+    unsigned                         nports = 0, nprb = 0;
+    size_t                           pay_bytes = 0;
+    for (size_t i = 0; i != n; ++i) {
+      const pucch_f34_configuration& cfg = configs[i];
+      require(cfg.cp == srsran::cyclic_prefix::NORMAL, "pucch_processor_hip: only the normal cyclic prefix is supported.");
+      require(cfg.ports.size() >= 1 && cfg.ports.size() <= 4, "The number of receive ports must be 1 to 4.");
+      require(identity_ports(cfg.ports), "pucch_processor_hip::process_f34_batch: receive ports must be 0, 1, ... in order.");
+      miphy_pucch_f34_job& j = jobs[i];
+      j                      = {};
+      j.format = static_cast<uint8_t>(cfg.format), j.numerology = cfg.slot.numerology(), j.slot = cfg.slot.slot_index();
+      j.nof_ports = static_cast<uint8_t>(cfg.ports.size()), j.start_symbol = static_cast<uint8_t>(cfg.start_symbol_index);
+      j.nof_symbols = static_cast<uint8_t>(cfg.nof_symbols), j.intra_slot_hopping = cfg.second_hop_prb.has_value() ? 1 : 0;
+      j.bwp_start_rb = static_cast<uint16_t>(cfg.bwp_start_rb), j.bwp_size_rb = static_cast<uint16_t>(cfg.bwp_size_rb);
+      j.starting_prb   = static_cast<uint16_t>(cfg.starting_prb);
+      j.second_hop_prb = static_cast<uint16_t>(cfg.second_hop_prb.has_value() ? cfg.second_hop_prb.value() : 0);
+      j.nof_prb = static_cast<uint8_t>(cfg.nof_prb), j.pi2_bpsk = cfg.pi2_bpsk ? 1 : 0, j.additional_dmrs = cfg.additional_dmrs ? 1 : 0;
+      j.occ_length = static_cast<uint8_t>(cfg.occ_length), j.occ_index = static_cast<uint8_t>(cfg.occ_index);
+      j.nof_harq_ack = static_cast<uint16_t>(cfg.nof_harq_ack), j.nof_sr = static_cast<uint16_t>(cfg.nof_sr);
+      j.nof_csi_part1 = static_cast<uint16_t>(cfg.nof_csi_part1), j.nof_csi_part2 = static_cast<uint16_t>(cfg.nof_csi_part2);
+      j.n_id_hopping = static_cast<uint16_t>(cfg.n_id_hopping), j.n_id_scrambling = static_cast<uint16_t>(cfg.n_id), j.rnti = cfg.rnti;
+      j.payload_offset = pay_bytes;
+      pay_bytes += static_cast<size_t>(cfg.nof_harq_ack) + cfg.nof_sr + cfg.nof_csi_part1;
+      nports = std::max<unsigned>(nports, j.nof_ports), nprb = std::max<unsigned>(nprb, cfg.bwp_start_rb + cfg.bwp_size_rb);
+    }
+    require(nprb >= 1 && nprb <= 275, "pucch_processor_hip::process_f34_batch: the BWPs must lie within 275 PRBs.");
+    const unsigned nsc = 12 * nprb;
+    for (auto& j : jobs) { // every PDU reads the first nof_ports ports of the one staged grid, whose rows are nprb PRBs wide
+      j.grid_nprb = nprb;
+    }
+    host.resize(static_cast<size_t>(nports) * 14 * nsc);
+    for (unsigned p = 0; p != nports; ++p) {
+      for (unsigned l = 0; l != 14; ++l) {
+        grid.get(srsran::span<srsran::cf_t>(host.data() + (static_cast<size_t>(p) * 14 + l) * nsc, nsc), p, l, 0);
+      }
+    }
+    auto* d_g = static_cast<float*>(c->buf(6, host.size() * sizeof(srsran::cf_t)));
+    c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
+    const size_t res_bytes = n * sizeof(miphy_pucch_result), bytes = res_bytes + pay_bytes;
+    auto*        d         = static_cast<uint8_t*>(c->buf(7, bytes));
+    context::check(miphy_pucch_process_f34_batch(c->ctx, jobs.data(), static_cast<uint32_t>(n), list_size, d_g, d + res_bytes,
+                                                 reinterpret_cast<miphy_pucch_result*>(d), nullptr, nullptr, c->stream),
+                   "pucch_process_f34");
+    nof_run = n;
+    down.resize(bytes);
+    c->d2h(down.data(), d, bytes);
+    c->sync();
+    for (size_t i = 0; i != n; ++i) { // unpack() reads the counts and the payload offset of a format-2 job
+      miphy_pucch_job j = {};
+      j.format = 2, j.payload_offset = jobs[i].payload_offset;
+      srsran::pucch_uci_message::configuration mc = {};
+      mc.nof_harq_ack = jobs[i].nof_harq_ack, mc.nof_sr = jobs[i].nof_sr, mc.nof_csi_part1 = jobs[i].nof_csi_part1;
+      unpack_message(down.data(), i, j, mc, out[i]);
+    }
   }
 
 private:
@@ -1252,13 +1352,19 @@ private:
   /// pucch_processor_result of job i (pucch_processor_impl.cpp:95-100 and 167-186).
   void unpack(const uint8_t* h, size_t i, const miphy_pucch_job& j, srsran::pucch_processor_result& r) const
   {
-    miphy_pucch_result res;
-    std::memcpy(&res, h + i * sizeof(miphy_pucch_result), sizeof(res));
     srsran::pucch_uci_message::configuration mc = {};
     mc.nof_harq_ack = j.nof_harq_ack;
     if (j.format == 2) {
       mc.nof_sr = j.nof_sr, mc.nof_csi_part1 = j.nof_csi_part1, mc.nof_csi_part2 = j.nof_csi_part2;
     }
+    unpack_message(h, i, j, mc, r);
+  }
+  /// The same for a message of the bit counts \c mc (formats 3 and 4 count in 16 bits): record i, the payload at j.payload_offset.
+  void unpack_message(const uint8_t* h, size_t i, const miphy_pucch_job& j, const srsran::pucch_uci_message::configuration& mc,
+                      srsran::pucch_processor_result& r) const
+  {
+    miphy_pucch_result res;
+    std::memcpy(&res, h + i * sizeof(miphy_pucch_result), sizeof(res));
     r.message                   = srsran::pucch_uci_message(mc);
     srsran::span<uint8_t> bits  = r.message.get_full_payload();
     const uint8_t*        pay   = h + nof_run * sizeof(miphy_pucch_result) + j.payload_offset;

@@ -175,6 +175,8 @@ def lib():
         l.miphy_debug_uci_polar_list_segments.restype = None
         l.miphy_pucch_process_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
         l.miphy_pucch_process_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
+        l.miphy_pucch_f34_info.argtypes = [C.c_void_p, C.c_void_p]
+        l.miphy_pucch_process_f34_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6
         l.miphy_prach_detect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_prach_generate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 2
         l.miphy_prach_demod_info.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
@@ -469,6 +471,28 @@ assert PucchJob.itemsize == 64
 PucchResult = np.dtype([("status", np.uint8), ("reserved", np.uint8, 3), ("detection_metric", np.float32), ("epre_db", np.float32),
                         ("rsrp_db", np.float32), ("sinr_db", np.float32), ("time_alignment_s", np.float32)], align=True)
 assert PucchResult.itemsize == 24
+# miphy_pucch_f34_job / miphy_pucch_f34_info_t (include/miphy.h)
+PucchF34Job = np.dtype([("format", np.uint8), ("numerology", np.uint8), ("slot", np.uint16), ("nof_ports", np.uint8), ("start_symbol", np.uint8),
+                        ("nof_symbols", np.uint8), ("intra_slot_hopping", np.uint8), ("bwp_start_rb", np.uint16), ("bwp_size_rb", np.uint16),
+                        ("starting_prb", np.uint16), ("second_hop_prb", np.uint16), ("nof_prb", np.uint8), ("pi2_bpsk", np.uint8),
+                        ("additional_dmrs", np.uint8), ("occ_length", np.uint8), ("occ_index", np.uint8), ("reserved0", np.uint8, 3),
+                        ("nof_harq_ack", np.uint16), ("nof_sr", np.uint16), ("nof_csi_part1", np.uint16), ("nof_csi_part2", np.uint16),
+                        ("n_id_hopping", np.uint16), ("n_id_scrambling", np.uint16), ("rnti", np.uint16), ("reserved1", np.uint16),
+                        ("grid_nprb", np.uint32), ("reserved2", np.uint32), ("grid_offset", np.uint64), ("payload_offset", np.uint64),
+                        ("llr_offset", np.uint64), ("est_offset", np.uint64)], align=True)
+assert PucchF34Job.itemsize == 80
+PucchF34Info = np.dtype([("dmrs_symbols_mask", np.uint32), ("nof_dmrs_symbols", np.uint32, 2), ("nof_data_symbols", np.uint32, 2), ("M", np.uint32),
+                         ("E", np.uint32), ("polar", np.uint32)], align=True)
+assert PucchF34Info.itemsize == 32
+
+
+def pucch_f34_info(job):
+    """What the PUCCH format 3 / 4 processor derives from one PucchF34Job record (host function, no device): a PucchF34Info record.
+    Raises with the library's error code (-1 = MIPHY_EINVAL, -4 = MIPHY_EUNSUPP for format 3 on 2 PRBs) and the rule in the message."""
+    j = np.ascontiguousarray(np.asarray(job, PucchF34Job).reshape(1))
+    out = np.zeros(1, PucchF34Info)
+    check(lib().miphy_pucch_f34_info(C.c_void_p(j.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out[0]
 # MIPHY_PRACH_FORMAT_*: PRACH_FORMATS.index("B4") is the format number of a PrachJob
 PRACH_FORMATS = ("0", "1", "2", "3", "A1", "A2", "A3", "B1", "B4", "C0", "C2", "A1/B1", "A2/B2", "A3/B3")
 # miphy_prach_job / miphy_prach_result / miphy_prach_preamble_result / miphy_prach_gen_job (include/miphy.h)
@@ -1122,6 +1146,22 @@ class Context:
         assert llr is None or llr.dtype == torch.int8
         check(lib().miphy_pucch_process_batch_ex(self.h, C.c_void_p(jobs.ctypes.data), jobs.size, int(list_size), _dptr(grid), _dptr(payload),
                                                  _dptr(results), None if llr is None else _dptr(llr), _stream_ptr(stream)))
+
+    def pucch_process_f34_batch(self, jobs, list_size, grid, payload, results, llr=None, est=None, stream=None):
+        """PUCCH formats 3 and 4 (jobs: numpy PucchF34Job array, HOST memory only): grid complex64 device tensor, payload uint8 (one bit
+        per byte), results a uint8 device tensor of n * PucchResult.itemsize bytes, llr None or an int8 device tensor for the soft bits,
+        est None or a float32 device tensor for the estimates the data path used ([port][hop][12 nof_prb] cf_t, then the noise variance
+        per port, from each job's est_offset). Payloads above 11 bits are polar decoded at list size 1, 2, 4 or 8. Only enqueues."""
+        import torch
+        assert isinstance(jobs, np.ndarray) and jobs.dtype == PucchF34Job, "pucch_process_f34_batch takes host jobs"
+        jobs = np.ascontiguousarray(jobs)
+        assert grid.dtype == torch.complex64 and payload.dtype == torch.uint8 and results.dtype == torch.uint8
+        assert results.numel() >= jobs.size * PucchResult.itemsize
+        assert llr is None or llr.dtype == torch.int8
+        assert est is None or est.dtype == torch.float32
+        check(lib().miphy_pucch_process_f34_batch(self.h, C.c_void_p(jobs.ctypes.data), jobs.size, int(list_size), _dptr(grid), _dptr(payload),
+                                                  _dptr(results), None if llr is None else _dptr(llr), None if est is None else _dptr(est),
+                                                  _stream_ptr(stream)))
 
     def prach_detect_batch(self, jobs, symbols, results, preambles, stream=None):
         """PRACH detector (jobs: numpy PrachJob array, or a uint8 device tensor holding the same bytes), one job per occasion: symbols
