@@ -1339,6 +1339,74 @@ int miphy_pucch_process_f34_batch(miphy_ctx* ctx, const miphy_pucch_f34_job* job
                                   int8_t* llr_out /* device or NULL */, float* est_out /* device or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * PUCCH processor, format 0 (TS 38.211 6.3.2.3, TS 38.213 9.2.3)  --  beyond the 23.5 reference, whose pucch_detector::format0_configuration is an
+ * empty struct and whose pucch_processor::format0_configuration cannot express a PDU. The contract is the standard, restated in numpy in
+ * tests/pucch_f0_tx.py (transmitter) and tests/pucch_f0_ref.py (receiver, thresholds included); the arithmetic of the detector is stated at the top of
+ * csrc/pucch_f0.hip. Format 0 has no DM-RS: the detector decides between the cyclic shifts of the PDU's hypotheses without a channel estimate, against a
+ * noise level that is either given (noise_var) or estimated from the cyclic shifts of the PRB that nobody uses (used_shifts_mask: bit k' set = some PDU
+ * of this resource may use the unhopped shift k'; the scheduler knows). n PDUs read one device grid through their windows as the PDUs of
+ * miphy_pucch_process_batch do, one wavefront each, four to a workgroup, in one launch.
+ * Hypotheses, in this order (m_cs of TS 38.213 9.2.3 added to initial_cyclic_shift modulo 12): one HARQ-ACK bit: 0 -> 0, 1 -> 6; two (b0, b1):
+ * (0,0) -> 0, (0,1) -> 3, (1,1) -> 6, (1,0) -> 9; SR alone: 0; SR with HARQ-ACK: those hypotheses (negative SR) followed by the positive-SR ones, one
+ * bit: 0 -> 3, 1 -> 9, two bits: (0,0) -> 1, (0,1) -> 4, (1,1) -> 7, (1,0) -> 10. H = 1, 2, 4, 4 or 8.
+ * Results: `payload` receives the best hypothesis whatever the verdict, nof_harq_ack bytes then nof_sr bytes from payload_offset (SR alone: 1 when the
+ * verdict is VALID, else 0); results[i].status is MIPHY_UCI_STATUS_VALID when the metric (energy of the best hypothesis over the noise energy of one
+ * shift) reaches the threshold, else _INVALID; detection_metric = metric / threshold, as format 1 normalises it; epre_db = 10 log10 of the energy per
+ * (port, symbol) summed over the twelve shifts, rsrp_db of the best hypothesis, sinr_db of that over the per-RE noise variance; time_alignment_s = 0 (a
+ * delay and a cyclic shift cannot be told apart without DM-RS). `energy_out` (device float or NULL) receives the twelve unhopped shift energies E[k']
+ * from energy_offset. The detector assumes a channel that is flat over the PRB; a timing offset leaks energy into neighbouring shifts.
+ * threshold = 0 asks for the default: a false-alarm probability of 1 % per PDU, union bound over the H hypotheses, in closed form from the degrees of
+ * freedom D = nof_ports nof_symbols and F = free shifts (miphy_pucch_f0_info reports it). The default is host arithmetic: host jobs get it filled in,
+ * device-resident jobs must carry a threshold > 0.
+ * Rules (miphy_pucch_f0_info, and therefore the batch call; MIPHY_EINVAL with the rule in miphy_last_error()): format 0; numerology, slot, ports, BWP,
+ * PRBs and grid as for miphy_pucch_job; nof_symbols 1..2 within the slot; intra_slot_hopping only with two symbols; initial_cyclic_shift 0..11;
+ * nof_harq_ack 0..2, nof_sr 0..1, not both 0; used_shifts_mask below 2^12; n_id 0..1023; threshold and noise_var finite and not negative; with
+ * noise_var = 0 at least one shift outside used_shifts_mask and the PDU's own hypotheses. Normal cyclic prefix, no group or sequence hopping
+ * (u = n_id mod 30, v = 0). Host jobs are all checked before anything is enqueued; a device job that fails a rule, or carries threshold 0, is skipped
+ * (nothing of it is written). n == 0 enqueues nothing. The call only enqueues and allocates nothing on the device once the context holds the Gold
+ * tables (any earlier PUCCH call), so with device jobs it can be captured in a HIP graph. */
+typedef struct {
+  uint8_t  format;               /* 0 */
+  uint8_t  numerology;           /* 0..4 */
+  uint16_t slot;                 /* slot index within the frame */
+  uint8_t  nof_ports;            /* receive ports 1..4 (ports 0 .. nof_ports - 1 of the grid window) */
+  uint8_t  start_symbol;         /* 0..13 */
+  uint8_t  nof_symbols;          /* 1..2 */
+  uint8_t  intra_slot_hopping;   /* 1 (two symbols only): the second symbol is on second_hop_prb */
+  uint16_t bwp_start_rb, bwp_size_rb;
+  uint16_t starting_prb;         /* within the BWP */
+  uint16_t second_hop_prb;       /* within the BWP, with hopping */
+  uint8_t  initial_cyclic_shift; /* 0..11 */
+  uint8_t  nof_harq_ack;         /* 0..2 */
+  uint8_t  nof_sr;               /* 0..1 */
+  uint8_t  reserved0;
+  uint16_t used_shifts_mask;     /* bit k': the unhopped shift k' may carry a signal of some PDU of this PRB */
+  uint16_t n_id;                 /* 0..1023: group u = n_id mod 30 and the cyclic-shift hopping c_init */
+  float    threshold;            /* on the metric; 0 = the default (host jobs only) */
+  float    noise_var;            /* per-RE noise variance; 0 = estimate it from the free shifts */
+  uint32_t grid_nprb;            /* width of the grid window in PRBs (>= bwp_start_rb + bwp_size_rb) */
+  uint32_t reserved1;
+  uint64_t grid_offset;          /* cf_t offset of the window in `grid` */
+  uint64_t payload_offset;       /* byte offset in `payload` */
+  uint64_t energy_offset;        /* float offset in `energy_out` */
+} miphy_pucch_f0_job;
+
+typedef struct {
+  uint32_t nof_hypotheses; /* H */
+  uint8_t  shifts[8];      /* unhopped cyclic shift of every hypothesis, in the order above */
+  uint32_t D;              /* nof_ports nof_symbols */
+  uint32_t free_mask;      /* shifts neither in used_shifts_mask nor among the hypotheses */
+  uint32_t F;              /* their number */
+  float    threshold;      /* what the batch call would compare the metric with */
+} miphy_pucch_f0_info_t;
+
+/* Host function, no device. */
+int miphy_pucch_f0_info(const miphy_pucch_f0_job* job, miphy_pucch_f0_info_t* out);
+int miphy_pucch_process_f0_batch(miphy_ctx* ctx, const miphy_pucch_f0_job* jobs, int jobs_on_device, uint32_t n, const float* grid /* device cf_t */,
+                                 uint8_t* payload /* device */, miphy_pucch_result* results /* device, n */, float* energy_out /* device or NULL */,
+                                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * PRACH detector and generator  --  replace srsran::prach_detector::detect and srsran::prach_generator::generate
  *   lib/phy/upper/channel_processors/prach_detector_simple_impl.cpp:35-169 (RSSI, per preamble: correlation in the frequency domain,
  *   unnormalised IDFT, peak of |c|^2, metric peak / (rssi preamble_power L L) against 0.07, delay sign and window),

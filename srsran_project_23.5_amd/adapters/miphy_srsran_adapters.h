@@ -1058,6 +1058,8 @@ private:
 /// the CPU processor when there is one.
 /// Formats 3 and 4 on the device: the reference's format3_configuration and format4_configuration hold nothing but the cyclic prefix and cannot
 /// express a PDU, so those process() overrides stay as they are and process_f34_batch() takes pucch_f34_configuration records instead.
+/// Format 0 on the device likewise: the reference's format0_configuration holds three fields, so process(grid, format0_configuration) stays as it is
+/// and process_f0_batch() takes pucch_f0_configuration records.
 
 /// One PUCCH format 3 or 4 PDU for pucch_processor_hip::process_f34_batch: the fields of pucch_processor::format2_configuration with their
 /// meaning (\c n_id scrambles the data; there is no \c n_id_0, the DM-RS of these formats is a low-PAPR sequence) plus what the two formats add.
@@ -1085,6 +1087,28 @@ struct pucch_f34_configuration {
   unsigned                                          occ_length         = 0; ///< Format 4: 2 or 4.
   unsigned                                          occ_index          = 0; ///< Format 4: below occ_length.
   unsigned                                          n_id_hopping       = 0; ///< Sequence group and cyclic-shift hopping identity {0, ..., 1023}.
+};
+
+/// One PUCCH format 0 PDU for pucch_processor_hip::process_f0_batch: the fields of pucch_processor::format1_configuration that apply, with their
+/// meaning, plus the SR opportunity, the cyclic shifts other PDUs of the PRB may use and, optionally, a threshold and a noise variance of the caller's.
+struct pucch_f0_configuration {
+  srsran::optional<srsran::pucch_context>           context;
+  srsran::slot_point                                slot;
+  srsran::cyclic_prefix                             cp = srsran::cyclic_prefix::NORMAL;
+  srsran::static_vector<uint8_t, srsran::MAX_PORTS> ports;
+  unsigned                                          bwp_size_rb  = 0;
+  unsigned                                          bwp_start_rb = 0;
+  unsigned                                          starting_prb = 0;
+  srsran::optional<unsigned>                        second_hop_prb;           ///< Two symbols only: the PRB of the second one.
+  unsigned                                          start_symbol_index   = 0; ///< 0 to 13.
+  unsigned                                          nof_symbols          = 1; ///< 1 or 2.
+  unsigned                                          initial_cyclic_shift = 0; ///< 0 to 11.
+  unsigned                                          n_id                 = 0; ///< Sequence group and cyclic-shift hopping identity {0, ..., 1023}.
+  unsigned                                          nof_harq_ack         = 0; ///< 0 to 2.
+  bool                                              sr_opportunity       = false;
+  uint16_t                                          used_shifts_mask     = 0; ///< Bit k: some PDU of this PRB may use the cyclic shift k (before hopping).
+  srsran::optional<float>                           threshold;                ///< On the metric; without it the 1 % false-alarm default.
+  srsran::optional<float>                           noise_variance;           ///< Per RE; without it estimated from the free cyclic shifts.
 };
 
 class pucch_processor_hip : public srsran::pucch_processor
@@ -1244,6 +1268,74 @@ public:
       j.format = 2, j.payload_offset = jobs[i].payload_offset;
       srsran::pucch_uci_message::configuration mc = {};
       mc.nof_harq_ack = jobs[i].nof_harq_ack, mc.nof_sr = jobs[i].nof_sr, mc.nof_csi_part1 = jobs[i].nof_csi_part1;
+      unpack_message(down.data(), i, j, mc, out[i]);
+    }
+  }
+
+  /// A slot's PUCCH format 0 in one launch of miphy_pucch_process_f0_batch: the grid goes to the device once, as in process_batch(); every result gets
+  /// its pucch_uci_message (HARQ-ACK bits, then the SR bit of an SR opportunity), the detection metric and the CSI as process_batch() fills them for
+  /// format 1. The library's rules (miphy_pucch_f0_info) are the validator: a PDU that breaks one fails the call with the rule as message before
+  /// anything is enqueued.
+  void process_f0_batch(const srsran::resource_grid_reader&          grid,
+                        srsran::span<const pucch_f0_configuration>   configs,
+                        srsran::span<srsran::pucch_processor_result> out)
+  {
+    require(out.size() == configs.size(), "pucch_processor_hip::process_f0_batch: one result per configuration.");
+    const size_t n = configs.size();
+    if (n == 0) {
+      return;
+    }
+    std::vector<miphy_pucch_f0_job> jobs(n);
+    unsigned                        nports = 0, nprb = 0;
+    size_t                          pay_bytes = 0;
+    for (size_t i = 0; i != n; ++i) {
+      const pucch_f0_configuration& cfg = configs[i];
+      require(cfg.cp == srsran::cyclic_prefix::NORMAL, "pucch_processor_hip: only the normal cyclic prefix is supported.");
+      require(cfg.ports.size() >= 1 && cfg.ports.size() <= 4, "The number of receive ports must be 1 to 4.");
+      require(identity_ports(cfg.ports), "pucch_processor_hip::process_f0_batch: receive ports must be 0, 1, ... in order.");
+      miphy_pucch_f0_job& j = jobs[i];
+      j                     = {};
+      j.format = 0, j.numerology = cfg.slot.numerology(), j.slot = cfg.slot.slot_index();
+      j.nof_ports = static_cast<uint8_t>(cfg.ports.size()), j.start_symbol = static_cast<uint8_t>(cfg.start_symbol_index);
+      j.nof_symbols = static_cast<uint8_t>(cfg.nof_symbols), j.intra_slot_hopping = cfg.second_hop_prb.has_value() ? 1 : 0;
+      j.bwp_start_rb = static_cast<uint16_t>(cfg.bwp_start_rb), j.bwp_size_rb = static_cast<uint16_t>(cfg.bwp_size_rb);
+      j.starting_prb   = static_cast<uint16_t>(cfg.starting_prb);
+      j.second_hop_prb = static_cast<uint16_t>(cfg.second_hop_prb.has_value() ? cfg.second_hop_prb.value() : 0);
+      j.initial_cyclic_shift = static_cast<uint8_t>(cfg.initial_cyclic_shift), j.nof_harq_ack = static_cast<uint8_t>(cfg.nof_harq_ack);
+      j.nof_sr = cfg.sr_opportunity ? 1 : 0, j.used_shifts_mask = cfg.used_shifts_mask, j.n_id = static_cast<uint16_t>(cfg.n_id);
+      j.threshold = cfg.threshold.has_value() ? cfg.threshold.value() : 0.f;
+      j.noise_var = cfg.noise_variance.has_value() ? cfg.noise_variance.value() : 0.f;
+      j.payload_offset = pay_bytes;
+      pay_bytes += static_cast<size_t>(cfg.nof_harq_ack) + j.nof_sr;
+      nports = std::max<unsigned>(nports, j.nof_ports), nprb = std::max<unsigned>(nprb, cfg.bwp_start_rb + cfg.bwp_size_rb);
+    }
+    require(nprb >= 1 && nprb <= 275, "pucch_processor_hip::process_f0_batch: the BWPs must lie within 275 PRBs.");
+    const unsigned nsc = 12 * nprb;
+    for (auto& j : jobs) { // every PDU reads the first nof_ports ports of the one staged grid, whose rows are nprb PRBs wide
+      j.grid_nprb = nprb;
+    }
+    host.resize(static_cast<size_t>(nports) * 14 * nsc);
+    for (unsigned p = 0; p != nports; ++p) {
+      for (unsigned l = 0; l != 14; ++l) {
+        grid.get(srsran::span<srsran::cf_t>(host.data() + (static_cast<size_t>(p) * 14 + l) * nsc, nsc), p, l, 0);
+      }
+    }
+    auto* d_g = static_cast<float*>(c->buf(6, host.size() * sizeof(srsran::cf_t)));
+    c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
+    const size_t res_bytes = n * sizeof(miphy_pucch_result), bytes = res_bytes + pay_bytes;
+    auto*        d         = static_cast<uint8_t*>(c->buf(7, bytes));
+    context::check(miphy_pucch_process_f0_batch(c->ctx, jobs.data(), 0, static_cast<uint32_t>(n), d_g, d + res_bytes, reinterpret_cast<miphy_pucch_result*>(d),
+                                                nullptr, c->stream),
+                   "pucch_process_f0");
+    nof_run = n;
+    down.resize(bytes);
+    c->d2h(down.data(), d, bytes);
+    c->sync();
+    for (size_t i = 0; i != n; ++i) { // unpack_message() reads the format (1: the result carries a detection metric) and the payload offset
+      miphy_pucch_job j = {};
+      j.format = 1, j.payload_offset = jobs[i].payload_offset;
+      srsran::pucch_uci_message::configuration mc = {};
+      mc.nof_harq_ack = jobs[i].nof_harq_ack, mc.nof_sr = jobs[i].nof_sr;
       unpack_message(down.data(), i, j, mc, out[i]);
     }
   }

@@ -177,6 +177,8 @@ def lib():
         l.miphy_pucch_process_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
         l.miphy_pucch_f34_info.argtypes = [C.c_void_p, C.c_void_p]
         l.miphy_pucch_process_f34_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6
+        l.miphy_pucch_f0_info.argtypes = [C.c_void_p, C.c_void_p]
+        l.miphy_pucch_process_f0_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
         l.miphy_prach_detect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_prach_generate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 2
         l.miphy_prach_demod_info.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
@@ -492,6 +494,29 @@ def pucch_f34_info(job):
     j = np.ascontiguousarray(np.asarray(job, PucchF34Job).reshape(1))
     out = np.zeros(1, PucchF34Info)
     check(lib().miphy_pucch_f34_info(C.c_void_p(j.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out[0]
+
+
+# miphy_pucch_f0_job / miphy_pucch_f0_info_t (include/miphy.h)
+PucchF0Job = np.dtype([("format", np.uint8), ("numerology", np.uint8), ("slot", np.uint16), ("nof_ports", np.uint8), ("start_symbol", np.uint8),
+                       ("nof_symbols", np.uint8), ("intra_slot_hopping", np.uint8), ("bwp_start_rb", np.uint16), ("bwp_size_rb", np.uint16),
+                       ("starting_prb", np.uint16), ("second_hop_prb", np.uint16), ("initial_cyclic_shift", np.uint8), ("nof_harq_ack", np.uint8),
+                       ("nof_sr", np.uint8), ("reserved0", np.uint8), ("used_shifts_mask", np.uint16), ("n_id", np.uint16), ("threshold", np.float32),
+                       ("noise_var", np.float32), ("grid_nprb", np.uint32), ("reserved1", np.uint32), ("grid_offset", np.uint64),
+                       ("payload_offset", np.uint64), ("energy_offset", np.uint64)], align=True)
+assert PucchF0Job.itemsize == 64
+PucchF0Info = np.dtype([("nof_hypotheses", np.uint32), ("shifts", np.uint8, 8), ("D", np.uint32), ("free_mask", np.uint32), ("F", np.uint32),
+                        ("threshold", np.float32)], align=True)
+assert PucchF0Info.itemsize == 28
+
+
+def pucch_f0_info(job):
+    """What the PUCCH format 0 detector derives from one PucchF0Job record (host function, no device): a PucchF0Info record -- the
+    hypotheses' unhopped cyclic shifts in table order, D, the free shifts and the threshold the batch call would use. Raises with the
+    library's error code (-1 = MIPHY_EINVAL) and the rule in the message."""
+    j = np.ascontiguousarray(np.asarray(job, PucchF0Job).reshape(1))
+    out = np.zeros(1, PucchF0Info)
+    check(lib().miphy_pucch_f0_info(C.c_void_p(j.ctypes.data), C.c_void_p(out.ctypes.data)))
     return out[0]
 # MIPHY_PRACH_FORMAT_*: PRACH_FORMATS.index("B4") is the format number of a PrachJob
 PRACH_FORMATS = ("0", "1", "2", "3", "A1", "A2", "A3", "B1", "B4", "C0", "C2", "A1/B1", "A2/B2", "A3/B3")
@@ -1162,6 +1187,23 @@ class Context:
         check(lib().miphy_pucch_process_f34_batch(self.h, C.c_void_p(jobs.ctypes.data), jobs.size, int(list_size), _dptr(grid), _dptr(payload),
                                                   _dptr(results), None if llr is None else _dptr(llr), None if est is None else _dptr(est),
                                                   _stream_ptr(stream)))
+
+    def pucch_process_f0_batch(self, jobs, grid, payload, results, energy=None, jobs_on_device=False, stream=None):
+        """PUCCH format 0 (jobs: numpy PucchF0Job array, or with jobs_on_device a uint8 device tensor holding the same bytes, every job with
+        a threshold > 0): grid complex64 device tensor, payload uint8 (one bit per byte: nof_harq_ack bytes, then nof_sr), results a uint8
+        device tensor of n * PucchResult.itemsize bytes, energy None or a float32 device tensor for the twelve unhopped shift energies of
+        each PDU from its energy_offset. Only enqueues."""
+        import torch
+        assert jobs_on_device == (not isinstance(jobs, np.ndarray)), "host jobs are a numpy array, device jobs a uint8 tensor with jobs_on_device=True"
+        jobs, n, ptr, on_dev = self._descs(jobs, PucchF0Job)
+        assert grid.dtype == torch.complex64 and payload.dtype == torch.uint8 and results.dtype == torch.uint8
+        assert results.numel() >= n * PucchResult.itemsize
+        assert energy is None or energy.dtype == torch.float32
+        if not on_dev and n:  # the extents the kernel may touch lie inside the tensors (the library sees raw pointers)
+            assert (jobs["payload_offset"].astype(np.int64) + jobs["nof_harq_ack"] + jobs["nof_sr"]).max() <= payload.numel(), "payload outside `payload`"
+            assert energy is None or jobs["energy_offset"].astype(np.int64).max() + 12 <= energy.numel(), "energies outside `energy`"
+        check(lib().miphy_pucch_process_f0_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(payload), _dptr(results),
+                                                 None if energy is None else _dptr(energy), _stream_ptr(stream)))
 
     def prach_detect_batch(self, jobs, symbols, results, preambles, stream=None):
         """PRACH detector (jobs: numpy PrachJob array, or a uint8 device tensor holding the same bytes), one job per occasion: symbols
