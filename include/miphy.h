@@ -1407,6 +1407,86 @@ int miphy_pucch_process_f0_batch(miphy_ctx* ctx, const miphy_pucch_f0_job* jobs,
                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * SRS channel estimator (TS 38.211 6.4.1.4)  --  beyond the 23.5 reference, which has no SRS code. The contract is the standard, restated in numpy in
+ * tests/srs_tx.py (transmitter) and tests/srs_ref.py (float64 receiver); the arithmetic is stated at the top of csrc/srs.hip. It measures what the
+ * precoding entry points consume: one channel matrix per PRG (and the per-UE time alignment); the library still does not compute weights from it.
+ * One job is the symbols of one SRS resource that lie on the same PRBs, in one slot. Decision: the job carries the resolved frequency position
+ * (start_prb, nof_prb). The hopping pattern, C_SRS / B_SRS / n_shift / n_RRC and TS 38.211 Table 6.4.1.4.3-1 stay with the scheduler, and a
+ * frequency-hopping resource is submitted as one job per hop. n jobs read one device grid through their windows as the PDUs of
+ * miphy_pucch_process_f0_batch do (receive port r, symbol l of the slot, subcarrier k at grid_offset + (14 r + l) 12 grid_nprb + k; start_prb in
+ * grid numbering), one workgroup each, in one launch.
+ * The signal, normal cyclic prefix: n_cs_max = 8 (comb 2) or 12 (comb 4); transmit port i has n_cs,i = (cyclic_shift + n_cs_max i / N_ap) mod n_cs_max
+ * and the comb offset (comb_offset + K / 2) mod K when N_ap = 4, i is 1 or 3 and cyclic_shift >= n_cs_max / 2, else comb_offset; M = 12 nof_prb / K
+ * elements per symbol; u = (f_gh + n_id) mod 30 with f_gh from group hopping (hopping = 1) and v from sequence hopping (hopping = 2, M >= 72), both with
+ * c_init = n_id and the symbol index in the slot. M = 12 is the table of the PUCCH kernels, M >= 36 Zadoff-Chu (N_ZC up to 1627: nof_prb 272 at comb 2
+ * has M = 1632, above what miphy_low_papr_sequence serves, whose limit stays); M = 24 is MIPHY_EUNSUPP (TS 38.211 Table 5.2.2.2-4 is not held).
+ * Estimates: with P = the transmit ports that share a comb (N_ap, or 2 when four ports split over two combs), Q = 12 prg_size / K comb elements per PRG
+ * and G = nof_prb / prg_size PRGs, `h_out` receives H[g][rx][tx] as cf_t from h_offset (G nof_rx_ports nof_tx_ports of them): the channel at the centre
+ * element of the PRG on the port's comb, as the grid shows it (the delay is not removed from it). results[i]: h_wb[rx][tx] the mean over the PRGs of
+ * the delay-compensated estimates (unused entries 0); noise_var (linear, per element) from the residual of the fit; epre_db of the SRS elements;
+ * rsrp_db[tx] (unused entries 0); sinr_db of the mean RSRP over noise_var; time_alignment_s, one delay per job from the phase of the lag-P correlation
+ * of the comb elements. The unambiguous delay range is |tau| < 1 / (2 delta_f K P) (miphy_srs_info reports it): a larger delay wraps. The estimator
+ * takes a comb to carry the job's ports and nothing else; UEs that share a comb at cyclic shifts n_cs_max / P apart are estimated as the ports of one
+ * job with that P, and UEs on other comb offsets or PRBs do not enter.
+ * Rules (miphy_srs_info, and therefore the batch calls; MIPHY_EINVAL, or MIPHY_EUNSUPP for M = 24, with the rule in miphy_last_error()): numerology
+ * 0..4 and the slot within its frame; nof_rx_ports 1..4; nof_tx_ports 1, 2 or 4; nof_symbols 1, 2 or 4 within the slot; comb_size 2 or 4, comb_offset
+ * below it; cyclic_shift below n_cs_max; n_id 0..1023; hopping 0..2; prg_size 1, 2 or 4; nof_prb a multiple of 4 in 4..272; start_prb + nof_prb within
+ * grid_nprb <= 275; Q a multiple of P (the ports of a comb are separated over whole periods of their relative cyclic shifts).
+ * miphy_srs_pilots_batch writes the transmitted sequences [symbol][tx port][M] of every job from pilots_offset: it pins sequence, hopping and cyclic
+ * shifts independently of the estimator. Host jobs are all checked before anything is enqueued; a device job that fails a rule is skipped (nothing of it
+ * is written). n == 0 enqueues nothing. The calls only enqueue and allocate nothing on the device once the context holds the Gold tables (any earlier
+ * PUCCH or SRS call), so with device jobs they can be captured in a HIP graph. */
+typedef struct {
+  uint8_t  numerology;    /* 0..4 */
+  uint8_t  nof_rx_ports;  /* receive ports 1..4 (ports 0 .. nof_rx_ports - 1 of the grid window) */
+  uint16_t slot;          /* slot index within the frame */
+  uint8_t  nof_tx_ports;  /* N_ap: 1, 2 or 4 */
+  uint8_t  start_symbol;  /* 0..13 */
+  uint8_t  nof_symbols;   /* 1, 2 or 4 */
+  uint8_t  comb_size;     /* K: 2 or 4 */
+  uint8_t  comb_offset;   /* below comb_size */
+  uint8_t  cyclic_shift;  /* n_cs: below 8 (comb 2) or 12 (comb 4) */
+  uint8_t  hopping;       /* 0 neither, 1 group, 2 sequence */
+  uint8_t  prg_size;      /* PRBs per estimate: 1, 2 or 4 */
+  uint16_t start_prb;     /* first PRB of the allocation, in grid numbering */
+  uint16_t nof_prb;       /* a multiple of 4 in 4..272 */
+  uint16_t n_id;          /* 0..1023: sequence identity */
+  uint16_t reserved0;
+  uint32_t grid_nprb;     /* width of the grid window in PRBs (>= start_prb + nof_prb) */
+  uint64_t grid_offset;   /* cf_t offset of the window in `grid` */
+  uint64_t h_offset;      /* cf_t offset in `h_out` */
+  uint64_t pilots_offset; /* cf_t offset in `pilots` (miphy_srs_pilots_batch) */
+} miphy_srs_job;
+
+typedef struct {
+  uint32_t M;                /* sequence length, 12 nof_prb / comb_size */
+  uint32_t Q;                /* comb elements per PRG */
+  uint32_t P;                /* transmit ports that share a comb */
+  uint32_t G;                /* PRGs */
+  uint32_t nof_combs;        /* 1, or 2 when four ports split */
+  uint8_t  cyclic_shifts[4]; /* n_cs,i per transmit port (unused entries 0) */
+  uint8_t  comb_offsets[4];  /* comb offset per transmit port (unused entries 0) */
+  uint32_t nof_h;            /* cf_t of the job in `h_out`: G nof_rx_ports nof_tx_ports */
+  float    max_delay_s;      /* the estimate is unambiguous for |delay| below this: 1 / (2 delta_f K P) */
+} miphy_srs_info_t;
+
+typedef struct {
+  float    h_wb[4][4][2];    /* [rx][tx][re, im]: mean over the PRGs of the delay-compensated estimates; unused entries 0 */
+  float    noise_var;        /* linear, per element */
+  float    epre_db;
+  float    rsrp_db[4];       /* per transmit port; unused entries 0 */
+  float    sinr_db;
+  float    time_alignment_s;
+  uint32_t reserved[2];      /* not written */
+} miphy_srs_result;
+
+/* Host function, no device. */
+int miphy_srs_info(const miphy_srs_job* job, miphy_srs_info_t* out);
+int miphy_srs_pilots_batch(miphy_ctx* ctx, const miphy_srs_job* jobs, int jobs_on_device, uint32_t n, float* pilots /* device cf_t */, void* stream);
+int miphy_srs_estimate_batch(miphy_ctx* ctx, const miphy_srs_job* jobs, int jobs_on_device, uint32_t n, const float* grid /* device cf_t */,
+                             float* h_out /* device cf_t */, miphy_srs_result* results /* device, n */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * PRACH detector and generator  --  replace srsran::prach_detector::detect and srsran::prach_generator::generate
  *   lib/phy/upper/channel_processors/prach_detector_simple_impl.cpp:35-169 (RSSI, per preamble: correlation in the frequency domain,
  *   unnormalised IDFT, peak of |c|^2, metric peak / (rssi preamble_power L L) against 0.07, delay sign and window),

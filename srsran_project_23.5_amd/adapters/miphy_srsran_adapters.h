@@ -1580,6 +1580,128 @@ create_pucch_processor_factory_hip(std::shared_ptr<context> c, const srsran::cha
   return std::make_shared<pucch_processor_factory_hip>(std::move(c), dims, std::move(cpu_factory), list_size, long_payloads);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- SRS estimator
+/// The 23.5 reference has no SRS estimator, so there is no interface to derive from: srs_estimator_hip::estimate_batch() takes
+/// srs_estimator_configuration records over miphy_srs_estimate_batch and returns one srs_estimator_result each.
+
+/// One SRS resource at one frequency position in one slot (a frequency-hopping resource is one configuration per hop; the scheduler resolves the
+/// position from C_SRS, B_SRS, n_shift and n_RRC).
+struct srs_estimator_configuration {
+  srsran::slot_point                                slot;
+  srsran::cyclic_prefix                             cp = srsran::cyclic_prefix::NORMAL;
+  srsran::static_vector<uint8_t, srsran::MAX_PORTS> ports;                  ///< Receive ports 0, 1, ... in order, 1 to 4.
+  unsigned                                          nof_tx_ports       = 1; ///< 1, 2 or 4.
+  unsigned                                          start_symbol_index = 13;
+  unsigned                                          nof_symbols        = 1; ///< 1, 2 or 4.
+  unsigned                                          start_prb          = 0; ///< First PRB of the allocation in the grid.
+  unsigned                                          nof_prb            = 4; ///< A multiple of 4 up to 272.
+  unsigned                                          comb_size          = 2; ///< 2 or 4.
+  unsigned                                          comb_offset        = 0;
+  unsigned                                          cyclic_shift       = 0; ///< Below 8 (comb 2) or 12 (comb 4).
+  unsigned                                          n_id               = 0; ///< Sequence identity {0, ..., 1023}.
+  bool                                              group_hopping      = false;
+  bool                                              sequence_hopping   = false; ///< Not together with group hopping.
+  unsigned                                          prg_size           = 4; ///< PRBs per channel matrix: 1, 2 or 4.
+};
+
+struct srs_estimator_result {
+  unsigned                  nof_prg = 0, nof_rx_ports = 0, nof_tx_ports = 0;
+  std::vector<srsran::cf_t> channel;  ///< [PRG][rx port][tx port]: the channel at the centre of each PRG, what per-PRG precoding weights are computed from.
+  srsran::cf_t              wideband[4][4] = {}; ///< [rx port][tx port], delay compensated.
+  float                     noise_variance = 0.f;
+  float                     epre_dB        = 0.f;
+  float                     rsrp_dB[4]     = {};
+  float                     sinr_dB        = 0.f;
+  srsran::phy_time_unit     time_alignment;
+};
+
+class srs_estimator_hip
+{
+public:
+  explicit srs_estimator_hip(std::shared_ptr<context> c) : c(std::move(c)) {}
+
+  /// A slot's SRS in one launch of miphy_srs_estimate_batch: the grid goes to the device once (the ports of the widest configuration, the PRBs up to
+  /// the end of the furthest allocation), estimates and records come back in one download. The library's rules (miphy_srs_info) are the validator:
+  /// a configuration that breaks one fails the call with the rule as message before anything is enqueued.
+  void estimate_batch(const srsran::resource_grid_reader&           grid,
+                      srsran::span<const srs_estimator_configuration> configs,
+                      srsran::span<srs_estimator_result>              out)
+  {
+    require(out.size() == configs.size(), "srs_estimator_hip::estimate_batch: one result per configuration.");
+    const size_t n = configs.size();
+    if (n == 0) {
+      return;
+    }
+    std::vector<miphy_srs_job> jobs(n);
+    unsigned                   nports = 0, nprb = 0;
+    size_t                     nof_h = 0;
+    for (size_t i = 0; i != n; ++i) {
+      const srs_estimator_configuration& cfg = configs[i];
+      require(cfg.cp == srsran::cyclic_prefix::NORMAL, "srs_estimator_hip: only the normal cyclic prefix is supported.");
+      require(cfg.ports.size() >= 1 && cfg.ports.size() <= 4, "The number of receive ports must be 1 to 4.");
+      for (unsigned p = 0; p != cfg.ports.size(); ++p) {
+        require(cfg.ports[p] == p, "srs_estimator_hip::estimate_batch: receive ports must be 0, 1, ... in order.");
+      }
+      require(!(cfg.group_hopping && cfg.sequence_hopping), "srs_estimator_hip: group and sequence hopping exclude each other.");
+      miphy_srs_job& j = jobs[i];
+      j                = {};
+      j.numerology = static_cast<uint8_t>(cfg.slot.numerology()), j.slot = static_cast<uint16_t>(cfg.slot.slot_index());
+      j.nof_rx_ports = static_cast<uint8_t>(cfg.ports.size()), j.nof_tx_ports = static_cast<uint8_t>(cfg.nof_tx_ports);
+      j.start_symbol = static_cast<uint8_t>(cfg.start_symbol_index), j.nof_symbols = static_cast<uint8_t>(cfg.nof_symbols);
+      j.comb_size = static_cast<uint8_t>(cfg.comb_size), j.comb_offset = static_cast<uint8_t>(cfg.comb_offset);
+      j.cyclic_shift = static_cast<uint8_t>(cfg.cyclic_shift), j.hopping = cfg.group_hopping ? 1 : (cfg.sequence_hopping ? 2 : 0);
+      j.prg_size = static_cast<uint8_t>(cfg.prg_size), j.start_prb = static_cast<uint16_t>(cfg.start_prb), j.nof_prb = static_cast<uint16_t>(cfg.nof_prb);
+      j.n_id = static_cast<uint16_t>(cfg.n_id), j.h_offset = nof_h;
+      miphy_srs_info_t info = {};
+      j.grid_nprb           = cfg.start_prb + cfg.nof_prb; // for the rules; every job then reads the one staged grid
+      context::check(miphy_srs_info(&j, &info), "srs_info");
+      nof_h += info.nof_h;
+      nports = std::max<unsigned>(nports, j.nof_rx_ports), nprb = std::max<unsigned>(nprb, cfg.start_prb + cfg.nof_prb);
+    }
+    const unsigned nsc = 12 * nprb;
+    for (auto& j : jobs) {
+      j.grid_nprb = nprb;
+    }
+    host.resize(static_cast<size_t>(nports) * 14 * nsc);
+    for (unsigned p = 0; p != nports; ++p) {
+      for (unsigned l = 0; l != 14; ++l) {
+        grid.get(srsran::span<srsran::cf_t>(host.data() + (static_cast<size_t>(p) * 14 + l) * nsc, nsc), p, l, 0);
+      }
+    }
+    auto* d_g = static_cast<float*>(c->buf(6, host.size() * sizeof(srsran::cf_t)));
+    c->h2d(d_g, host.data(), host.size() * sizeof(srsran::cf_t));
+    const size_t res_bytes = n * sizeof(miphy_srs_result), bytes = res_bytes + nof_h * sizeof(srsran::cf_t);
+    auto*        d         = static_cast<uint8_t*>(c->buf(7, bytes));
+    context::check(miphy_srs_estimate_batch(c->ctx, jobs.data(), 0, static_cast<uint32_t>(n), d_g, reinterpret_cast<float*>(d + res_bytes),
+                                            reinterpret_cast<miphy_srs_result*>(d), c->stream),
+                   "srs_estimate");
+    down.resize(bytes);
+    c->d2h(down.data(), d, bytes);
+    c->sync();
+    for (size_t i = 0; i != n; ++i) {
+      miphy_srs_result res;
+      std::memcpy(&res, down.data() + i * sizeof(miphy_srs_result), sizeof(res));
+      srs_estimator_result& r = out[i];
+      r.nof_rx_ports = jobs[i].nof_rx_ports, r.nof_tx_ports = jobs[i].nof_tx_ports, r.nof_prg = jobs[i].nof_prb / jobs[i].prg_size;
+      r.channel.resize(static_cast<size_t>(r.nof_prg) * r.nof_rx_ports * r.nof_tx_ports);
+      std::memcpy(r.channel.data(), down.data() + res_bytes + jobs[i].h_offset * sizeof(srsran::cf_t), r.channel.size() * sizeof(srsran::cf_t));
+      for (unsigned rx = 0; rx != 4; ++rx) {
+        for (unsigned tx = 0; tx != 4; ++tx) {
+          r.wideband[rx][tx] = srsran::cf_t(res.h_wb[rx][tx][0], res.h_wb[rx][tx][1]);
+        }
+      }
+      r.noise_variance = res.noise_var, r.epre_dB = res.epre_db, r.sinr_dB = res.sinr_db;
+      std::copy(res.rsrp_db, res.rsrp_db + 4, r.rsrp_dB);
+      r.time_alignment = srsran::phy_time_unit::from_seconds(res.time_alignment_s);
+    }
+  }
+
+private:
+  std::shared_ptr<context>  c;
+  std::vector<srsran::cf_t> host;
+  std::vector<uint8_t>      down;
+};
+
 // ---------------------------------------------------------------------------------------------------------------- PRACH
 static_assert(static_cast<unsigned>(srsran::prach_format_type::three) == MIPHY_PRACH_FORMAT_3 &&
                   static_cast<unsigned>(srsran::prach_format_type::A1) == MIPHY_PRACH_FORMAT_A1 &&

@@ -179,6 +179,9 @@ def lib():
         l.miphy_pucch_process_f34_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6
         l.miphy_pucch_f0_info.argtypes = [C.c_void_p, C.c_void_p]
         l.miphy_pucch_process_f0_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
+        l.miphy_srs_info.argtypes = [C.c_void_p, C.c_void_p]
+        l.miphy_srs_pilots_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 2
+        l.miphy_srs_estimate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_prach_detect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_prach_generate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 2
         l.miphy_prach_demod_info.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
@@ -517,6 +520,31 @@ def pucch_f0_info(job):
     j = np.ascontiguousarray(np.asarray(job, PucchF0Job).reshape(1))
     out = np.zeros(1, PucchF0Info)
     check(lib().miphy_pucch_f0_info(C.c_void_p(j.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out[0]
+
+
+# miphy_srs_job / miphy_srs_info_t / miphy_srs_result (include/miphy.h)
+SrsJob = np.dtype([("numerology", np.uint8), ("nof_rx_ports", np.uint8), ("slot", np.uint16), ("nof_tx_ports", np.uint8), ("start_symbol", np.uint8),
+                   ("nof_symbols", np.uint8), ("comb_size", np.uint8), ("comb_offset", np.uint8), ("cyclic_shift", np.uint8), ("hopping", np.uint8),
+                   ("prg_size", np.uint8), ("start_prb", np.uint16), ("nof_prb", np.uint16), ("n_id", np.uint16), ("reserved0", np.uint16),
+                   ("grid_nprb", np.uint32), ("grid_offset", np.uint64), ("h_offset", np.uint64), ("pilots_offset", np.uint64)], align=True)
+assert SrsJob.itemsize == 48
+SrsInfo = np.dtype([("M", np.uint32), ("Q", np.uint32), ("P", np.uint32), ("G", np.uint32), ("nof_combs", np.uint32), ("cyclic_shifts", np.uint8, 4),
+                    ("comb_offsets", np.uint8, 4), ("nof_h", np.uint32), ("max_delay_s", np.float32)], align=True)
+assert SrsInfo.itemsize == 36
+SrsResult = np.dtype([("h_wb", np.float32, (4, 4, 2)), ("noise_var", np.float32), ("epre_db", np.float32), ("rsrp_db", np.float32, 4),
+                      ("sinr_db", np.float32), ("time_alignment_s", np.float32), ("reserved", np.uint32, 2)], align=True)
+assert SrsResult.itemsize == 168
+
+
+def srs_info(job):
+    """What the SRS estimator derives from one SrsJob record (host function, no device): an SrsInfo record -- the sequence length M, the comb
+    elements per PRG Q, the ports that share a comb P, the PRGs G, cyclic shift and comb offset per transmit port, the cf_t count of the job's
+    estimate and the unambiguous delay range. Raises with the library's error code (-1 = MIPHY_EINVAL, -4 = MIPHY_EUNSUPP for M = 24) and the
+    rule in the message."""
+    j = np.ascontiguousarray(np.asarray(job, SrsJob).reshape(1))
+    out = np.zeros(1, SrsInfo)
+    check(lib().miphy_srs_info(C.c_void_p(j.ctypes.data), C.c_void_p(out.ctypes.data)))
     return out[0]
 # MIPHY_PRACH_FORMAT_*: PRACH_FORMATS.index("B4") is the format number of a PrachJob
 PRACH_FORMATS = ("0", "1", "2", "3", "A1", "A2", "A3", "B1", "B4", "C0", "C2", "A1/B1", "A2/B2", "A3/B3")
@@ -1204,6 +1232,34 @@ class Context:
             assert energy is None or jobs["energy_offset"].astype(np.int64).max() + 12 <= energy.numel(), "energies outside `energy`"
         check(lib().miphy_pucch_process_f0_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(payload), _dptr(results),
                                                  None if energy is None else _dptr(energy), _stream_ptr(stream)))
+
+    def srs_pilots_batch(self, jobs, pilots, jobs_on_device=False, stream=None):
+        """The transmitted SRS sequences (jobs: numpy SrsJob array, or with jobs_on_device a uint8 device tensor holding the same bytes): pilots a
+        complex64 device tensor that receives [symbol][tx port][M] of every job from its pilots_offset. Only enqueues."""
+        import torch
+        assert jobs_on_device == (not isinstance(jobs, np.ndarray)), "host jobs are a numpy array, device jobs a uint8 tensor with jobs_on_device=True"
+        jobs, n, ptr, on_dev = self._descs(jobs, SrsJob)
+        assert pilots.dtype == torch.complex64
+        if not on_dev and n:  # the extents the kernel may touch lie inside the tensor (the library sees raw pointers)
+            size = jobs["nof_symbols"].astype(np.int64) * jobs["nof_tx_ports"] * 12 * jobs["nof_prb"] // np.maximum(jobs["comb_size"], 1)
+            assert (jobs["pilots_offset"].astype(np.int64) + size).max() <= pilots.numel(), "sequences outside `pilots`"
+        check(lib().miphy_srs_pilots_batch(self.h, ptr, on_dev, n, _dptr(pilots), _stream_ptr(stream)))
+
+    def srs_estimate_batch(self, jobs, grid, h, results, jobs_on_device=False, stream=None):
+        """SRS channel estimator (jobs: numpy SrsJob array, or with jobs_on_device a uint8 device tensor holding the same bytes): grid and h
+        complex64 device tensors, h receives H[PRG][rx][tx] of every job from its h_offset; results a uint8 device tensor of
+        n * SrsResult.itemsize bytes (view it with .cpu().numpy().view(SrsResult)). Only enqueues."""
+        import torch
+        assert jobs_on_device == (not isinstance(jobs, np.ndarray)), "host jobs are a numpy array, device jobs a uint8 tensor with jobs_on_device=True"
+        jobs, n, ptr, on_dev = self._descs(jobs, SrsJob)
+        assert grid.dtype == torch.complex64 and h.dtype == torch.complex64 and results.dtype == torch.uint8
+        assert results.numel() >= n * SrsResult.itemsize
+        if not on_dev and n:  # the extents the kernel may touch lie inside the tensors (the library sees raw pointers)
+            i64 = {k: jobs[k].astype(np.int64) for k in ("nof_prb", "prg_size", "nof_rx_ports", "nof_tx_ports", "h_offset", "grid_offset", "grid_nprb")}
+            size = i64["nof_prb"] // np.maximum(i64["prg_size"], 1) * i64["nof_rx_ports"] * i64["nof_tx_ports"]
+            assert (i64["h_offset"] + size).max() <= h.numel(), "estimates outside `h`"
+            assert (i64["grid_offset"] + i64["nof_rx_ports"] * 14 * 12 * i64["grid_nprb"]).max() <= grid.numel(), "grid windows outside `grid`"
+        check(lib().miphy_srs_estimate_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(h), _dptr(results), _stream_ptr(stream)))
 
     def prach_detect_batch(self, jobs, symbols, results, preambles, stream=None):
         """PRACH detector (jobs: numpy PrachJob array, or a uint8 device tensor holding the same bytes), one job per occasion: symbols
