@@ -218,6 +218,20 @@ for i, (mod, ports, cdm, nprb_grid, start, nof, dsyms) in enumerate([(8, 1, 2, 1
     d["bits_%d" % i] = bits
 save("pusch_demod", **d)
 
+# ------------------------------------------------------------------ soft demapper on crafted edges (tests/demod_edges.py): boundaries, rounding ties,
+# the clip, non-finite symbols and abnormal variances, straight into the reference's demapper. Each set twice: whole (a multiple of 32 symbols: the
+# reference's vector body) and in slices of 7 symbols, a call each (its scalar code).
+import demod_edges as DE  # noqa: E402
+
+d = {}
+for mod in DE.MODS:
+    x, nv = DE.fixture_inputs(mod)
+    assert x.size % 32 == 0
+    d["sym_%d" % mod], d["nv_%d" % mod] = x, nv
+    d["llr_vec_%d" % mod] = O.r_demodulate_soft(mod, x, nv)
+    d["llr_sc_%d" % mod] = np.concatenate([O.r_demodulate_soft(mod, x[i:i + 7], nv[i:i + 7]) for i in range(0, x.size, 7)])
+save("demod_edges", **d)
+
 # ------------------------------------------------------------------ PDSCH modulator + PDSCH DM-RS
 d = {}
 for i, mod in enumerate((1, 2, 4, 6, 8)):

@@ -1654,8 +1654,11 @@ static int8_t demod_quantize(float v, float range_limit)
 
 static float demod_interval(float x, float rcp_noise, float rcp_width, int count, const float* slope, const float* intercept)
 {
-  int idx = (int)floorf(x * rcp_width) + count / 2;
-  idx     = idx < 0 ? 0 : (idx > count - 1 ? count - 1 : idx);
+  /* avx2_helpers.h:173-192 converts the position with cvtps2dq (the scalar code with cvttss2si): NaN and everything outside int32, a huge positive
+   * value too, become INT_MIN, which the clamp takes to interval 0. Stated here, not left to the conversion of the machine at hand. */
+  const float pos = floorf(x * rcp_width);
+  int         idx = (fabsf(pos) < 2147483648.0f) ? (int)pos + count / 2 : 0;
+  idx             = idx < 0 ? 0 : (idx > count - 1 ? count - 1 : idx);
   float t = slope[idx] * x;
   t       = t + intercept[idx];
   return t * rcp_noise;

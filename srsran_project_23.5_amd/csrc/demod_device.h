@@ -24,10 +24,15 @@ static __device__ __forceinline__ int demod_quantize_fast(float v, float scale)
 // The exact soft demapper of one equalised symbol (demodulation_mapper_*.cpp restated): shared by the PUSCH demodulator, which also has a packed
 // variant for the common case (pusch_demod.hip), and the PUCCH format 3 / 4 processor (pucch_f34.hip). tab: the LDS interval tables of QAM64 / QAM256
 // (not read below them).
+// The reference converts the interval position with cvtps2dq / cvttss2si, which turn NaN and everything outside int32 -- a huge POSITIVE component
+// too -- into INT_MIN, and the clamp then takes that to interval 0. The conversion of this target saturates (v_cvt_i32_f32: INT_MAX); adding the
+// offset in unsigned arithmetic wraps that to a negative index, interval 0 again. (With a signed addition the compiler assumes no overflow and
+// clamps first: a huge positive component then lands in the last interval, where half of the tables have the opposite slope.
+// tests/test_demod_edges_gpu.py holds the toolchain to this.)
 static __device__ __forceinline__ int demod_interval_idx(float x, float rcp_width, int count)
 {
 #pragma clang fp contract(off)
-  const int idx = (int)floorf(x * rcp_width) + count / 2;
+  const int idx = (int)((unsigned)(int)floorf(x * rcp_width) + (unsigned)(count / 2));
   return idx < 0 ? 0 : (idx > count - 1 ? count - 1 : idx);
 }
 static __device__ __forceinline__ float demod_interval_at(float x, float rcp_noise, float2 si)

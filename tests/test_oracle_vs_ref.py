@@ -239,6 +239,23 @@ def test_pusch_demodulator():
         assert diff.max() <= 1 and (diff == 0).mean() > 0.99, (mod, ports, diff.max(), (diff == 0).mean())
 
 
+def test_soft_demapper_on_crafted_edges():
+    """The comparison of test_demod_edges.py::test_oracle_matches_reference_fixture, live: interval boundaries, rounding ties, the clip, non-finite
+    symbols and abnormal variances (tests/demod_edges.py) through the reference's vector body (one call, a multiple of 32 symbols) and its scalar
+    code (slices of 7 symbols). Tolerance: one quantisation step; left out: the class demod_edges.reference_comparable names."""
+    import demod_edges as DE
+    for mod in DE.MODS:
+        x, nv = DE.fixture_inputs(mod)
+        assert x.size % 32 == 0
+        pairs = [("vector body", O.o_demodulate_soft(mod, x, nv), O.r_demodulate_soft(mod, x, nv)),
+                 ("scalar code", np.concatenate([O.o_demodulate_soft(mod, x[i:i + 7], nv[i:i + 7]) for i in range(0, x.size, 7)]),
+                  np.concatenate([O.r_demodulate_soft(mod, x[i:i + 7], nv[i:i + 7]) for i in range(0, x.size, 7)]))]
+        for name, o, r in pairs:
+            worst, exact = DE.compare_with_reference(mod, nv, o, r)
+            print("modulation order %d, %s: max |oracle - reference| = %d, exact share %.4f" % (mod, name, worst, exact))
+            assert worst <= 1, (mod, name, worst)
+
+
 def test_pusch_demodulator_placeholders_and_evm():
     """UCI on PUSCH in the demodulator (pusch_demodulator_impl.cpp:89-152): repetition placeholders in the descrambler and the EVM of
     the demodulation status, oracle vs reference. LLRs within one quantisation step (the reference's approximate reciprocal), EVM
