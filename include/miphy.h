@@ -376,6 +376,33 @@ int miphy_dmrs_pusch_estimate_layers_batch(miphy_ctx* ctx, const miphy_pusch_che
                                            const float* grid /* device cf_t */, float* ce /* device cf_t */, float* scalars /* device */,
                                            void* stream);
 
+/* Noise-plus-interference covariance across the receive ports, from the DM-RS residuals of the estimator above  --  beyond the 23.5 reference,
+ * which has no MMSE equaliser to feed ("MMSE equalizer is not implemented yet"). Reads the grid only. With e[g][p][d][i] the residual whose
+ * energy the estimator turns into noise_var (g the CDM group, p the receive port, d the DM-RS symbol, i the pilot of the allocated PRBs):
+ *   both layers of the group present:  e = x_d[i] - beta r_d[i] (A + (-1)^i B),  A, B the per-PRB means of s_a, s_b
+ *   a layer alone in its group:        e = x_d[i] - beta r_d[i] (per-PRB mean of z)
+ * the allocated PRBs, in ascending order, are cut into PRGs of prg_size PRBs (the last one may be short; prg_size 0: one PRG), and for PRG j of
+ * n_j PRBs, with f_g = 2 where group g carries two layers, else 1:
+ *   C_j[p][q] = (sum_g sum_d sum_{i in PRG j} e[g][p][d][i] conj(e[g][q][d][i])) / (n_j sum_g (6 nds - f_g))
+ *   C_j[p][p] += loading (sum_p C_j[p][p]) / P
+ * Without loading the whole-allocation diagonal is the estimator's noise_var of the port (one layer, two layers), from three DM-RS symbols on;
+ * the 0.001 epre substitution below three does not apply here: the divisor is positive from one DM-RS symbol on. The sums run in one fixed
+ * order without atomics: a PRG's matrix has the same bits whatever else is in the batch. Every matrix is written in full, Hermitian, with
+ * diagonal imaginary parts 0. Rules: those of miphy_dmrs_pusch_estimate_layers_batch on `base` (hopping included), and loading finite and
+ * >= 0: a host job that breaks one is MIPHY_EINVAL with nothing enqueued, a device-resident one is skipped; the hints of
+ * MIPHY_JOBS_ON_DEVICE_HINT are accepted. Out: more than 4 receive ports, DM-RS type 2, double-symbol DM-RS, frequency hopping, a covariance
+ * per OFDM symbol. */
+typedef struct {
+  miphy_pusch_chest_job base; /* ce_offset, scalars_offset and ce_compact are ignored */
+  uint64_t cov_offset;        /* cf_t offset: [PRG][P][P], row p, column q: C[p][q] ~ E[n_p conj(n_q)], P = base.nof_rx_ports */
+  float    loading;           /* >= 0, finite */
+  uint16_t prg_size;          /* PRBs per matrix, counted over the ALLOCATED PRBs in ascending order; 0 = one matrix for the allocation */
+  uint8_t  reserved[2];
+} miphy_pusch_ncov_job;
+uint32_t miphy_pusch_noise_covariance_nof_prg(const miphy_pusch_ncov_job* job); /* host; matrices the job writes, 0 on an invalid job */
+int      miphy_pusch_noise_covariance_batch(miphy_ctx* ctx, const miphy_pusch_ncov_job* jobs, int jobs_on_device, uint32_t n,
+                                            const float* grid /* device cf_t */, float* cov /* device cf_t */, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * PUSCH demodulator  --  replaces srsran::pusch_demodulator::demodulate (the block between the channel estimator
  * and the decoder), i.e. channel_equalizer::equalize + demodulation_mapper::demodulate_soft + descrambling in one pass
@@ -461,6 +488,29 @@ int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_pusch_demod_
 int miphy_pusch_demodulate_layers_batch_ex(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
                                            const float* ce, const float* scalars, int8_t* llr_out, const uint16_t* placeholders /* device, may be NULL */,
                                            float* evm_sums /* device, may be NULL */, void* stream);
+
+/* The same demodulator with MMSE-IRC in place of zero forcing (beyond the reference, like the layers themselves): the equaliser is
+ * miphy_channel_equalize_mmse_batch at tx_scaling 1 (declared further down; csrc/mmse_device.h), fed one covariance matrix per PRG as
+ * miphy_pusch_noise_covariance_batch writes them. The bytes are those of extraction, that equaliser, the soft demapper and the descrambler
+ * one after the other; placeholders and EVM of _ex follow the rules above unchanged. 1..4 layers, ONE LAYER INCLUDED: interference rejection on
+ * one layer with two or four ports is the common case (such a job does not give the bytes of miphy_pusch_demodulate_batch: another equaliser).
+ * The scalar noise variance is not read: `scalars` may be NULL and base.base.scalars_offset is ignored. With a compact estimate the matrices
+ * A and B of a subcarrier are set up once for all its symbols. The LLR count is miphy_pusch_demod_layers_nof_llr(&job.base). Rules and
+ * refusals: those of the layered entry points. Out: MMSE for the transform-precoded path, a covariance per OFDM symbol. */
+typedef struct {
+  miphy_pusch_demod_layers_job base;
+  uint64_t cov_offset;   /* cf_t offset into cov: [PRG][P][P], P = base.base.nof_rx_ports */
+  uint16_t prg_size;     /* as in miphy_pusch_ncov_job: PRG of a subcarrier = rank of its PRB among the allocated ones / prg_size; 0 = matrix 0 */
+  uint8_t  reserved[6];
+} miphy_pusch_demod_mmse_job;
+int miphy_pusch_demodulate_layers_mmse_batch(miphy_ctx* ctx, const miphy_pusch_demod_mmse_job* jobs, int jobs_on_device, uint32_t n,
+                                             const float* grid /* device cf_t */, const float* ce /* device cf_t */,
+                                             const float* scalars /* device, not read, may be NULL */, const float* cov /* device cf_t */,
+                                             int8_t* llr_out /* device */, void* stream);
+int miphy_pusch_demodulate_layers_mmse_batch_ex(miphy_ctx* ctx, const miphy_pusch_demod_mmse_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                                const float* ce, const float* scalars /* may be NULL */, const float* cov, int8_t* llr_out,
+                                                const uint16_t* placeholders /* device, may be NULL */, float* evm_sums /* device, may be NULL */,
+                                                void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * PUSCH with transform precoding (DFT-s-OFDM, TS 38.211 6.3.1.4)  --  beyond the 23.5 reference, which has no transform precoding anywhere
@@ -573,6 +623,26 @@ int miphy_channel_equalize_batch(miphy_ctx* ctx, const miphy_equalizer_job* jobs
 int miphy_channel_equalize_layers_batch(miphy_ctx* ctx, const miphy_equalizer_job* jobs, int jobs_on_device, uint32_t n,
                                         const float* ch_symbols /* device cf_t */, const float* ch_estimates /* device cf_t */,
                                         float* eq_symbols /* device cf_t */, float* eq_noise_vars /* device */, void* stream);
+/* MMSE with interference rejection (MMSE-IRC) on the same topologies and tensor layouts  --  beyond the reference, whose equaliser tests say
+ * "MMSE equalizer is not implemented yet". Model y = t H x + n with E[n n^H] = C (t = tx_scaling), one P x P matrix per run of re_per_cov
+ * elements, as miphy_pusch_noise_covariance_batch writes them; only C's lower triangle and the real parts of its diagonal are read:
+ *   W = C^-1;  A = t^2 H^H W H + I;  B = A^-1;  x~ = t B H^H W y
+ *   gamma_l = 1 - B_ll;  x_l = x~_l / gamma_l (unbiased);  nvar_l = B_ll / gamma_l
+ * in single precision in a fixed order of operations (csrc/mmse_device.h: LDL^H factorisations of C and of A without square roots, gamma
+ * taken as (B t^2 H^H W H)_ll, which does not cancel at low SINR). With C = noise_var I the symbols tend to those of the zero-forcing entry
+ * point as noise_var -> 0; on one layer they are its maximum-ratio combination at every noise_var. If a pivot of either factorisation or a
+ * gamma_l is not a normal positive number, every layer of the element gets symbol 0 and noise variance +inf. base.noise_var is ignored.
+ * Invalid topologies and tx_scaling <= 0: as miphy_channel_equalize_layers_batch. */
+typedef struct {
+  miphy_equalizer_job base; /* nof_tx_layers 1..4 on nof_rx_ports = layers..4 */
+  uint64_t cov_offset;      /* cf_t offset into cov: [matrix][P][P], P = base.nof_rx_ports */
+  uint32_t re_per_cov;      /* element i uses matrix i / re_per_cov; 0 = matrix 0 for every element */
+  uint32_t reserved;
+} miphy_equalizer_mmse_job;
+int miphy_channel_equalize_mmse_batch(miphy_ctx* ctx, const miphy_equalizer_mmse_job* jobs, int jobs_on_device, uint32_t n,
+                                      const float* ch_symbols /* device cf_t */, const float* ch_estimates /* device cf_t */,
+                                      const float* cov /* device cf_t */, float* eq_symbols /* device cf_t */, float* eq_noise_vars /* device */,
+                                      void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * PDSCH modulator and PDSCH DM-RS  --  replace srsran::pdsch_modulator::modulate and srsran::dmrs_pdsch_processor::map
@@ -1029,6 +1099,27 @@ int miphy_pusch_process_layers_batch_ex(miphy_ctx* ctx, const miphy_pusch_layers
                                         uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
                                         miphy_pusch_result* results, float* scalars_out /* n x 80 */, int8_t* uci_llr_out,
                                         float* evm_out /* device, n, may be NULL */, void* stream);
+
+/* The layered processor with MMSE-IRC  --  beyond the reference. The arguments of miphy_pusch_process_layers_batch_ex; one call chains, on one
+ * stream, miphy_dmrs_pusch_estimate_layers_batch (compact estimate), miphy_pusch_noise_covariance_batch (the PDU's prg_size and loading; the
+ * matrices stay in the workspace of the context next to estimates and LLRs), miphy_pusch_demodulate_layers_mmse_batch_ex,
+ * miphy_ulsch_demultiplex_batch where UCI is multiplexed and miphy_pusch_decode_batch: transport blocks, result records, scalars, UCI soft bits
+ * and EVM are the bytes of the stages called one by one. scalars_out is that of the layered processor: the estimator's scalar noise_var stays what
+ * it is (forced to 0.001 epre below three DM-RS symbols), the demodulator does not read it. 1..4 layers; IRC needs more ports than layers to
+ * null anything. Rules and refusals: those of the layered processor, and loading finite and >= 0; a PDU that breaks one is MIPHY_EINVAL with
+ * nothing enqueued. Out: more than 4 receive ports, DM-RS type 2, double-symbol DM-RS, frequency hopping, MMSE for the transform-precoded
+ * path, a covariance per OFDM symbol, the slot batch of the uplink processor, a prepared plan, the srsRAN adapters (23.5 has no MMSE factory
+ * to implement). */
+typedef struct {
+  miphy_pusch_layers_pdu base;
+  float    loading;  /* as in miphy_pusch_ncov_job */
+  uint16_t prg_size; /* PRBs per covariance matrix, counted over the allocated PRBs; 0 = one matrix for the allocation */
+  uint8_t  reserved[2];
+} miphy_pusch_mmse_pdu;
+int miphy_pusch_process_layers_mmse_batch(miphy_ctx* ctx, const miphy_pusch_mmse_pdu* pdus /* host */, const miphy_pusch_uci* uci /* host or NULL */,
+                                          uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
+                                          miphy_pusch_result* results, float* scalars_out /* n x 80 */, int8_t* uci_llr_out,
+                                          float* evm_out /* device, n, may be NULL */, void* stream);
 
 /* PUSCH processor for a transform-precoded PUSCH (DFT-s-OFDM)  --  beyond the 23.5 reference, whose pusch_processor::pdu_t cannot express the
  * waveform. One call chains, on one stream, miphy_dmrs_pusch_estimate_tp_batch (compact estimate, scaling 10^(3/20), base.dmrs_scrambling_id =

@@ -10,6 +10,8 @@
 //   chest_kernel<false>  workgroup per (job, rx port, layer): miphy_dmrs_pusch_estimate_batch, one-layer jobs of miphy_dmrs_pusch_estimate_layers_batch;
 //   chest_kernel<true>   the same with the caller's pilots and hopping: miphy_port_channel_estimate_batch, miphy_dmrs_pusch_estimate_tp_batch;
 //   chest_layers_kernel  workgroup per (job, rx port, CDM group), the group's layers separated: jobs on two to four layers of the layered entry.
+// A third kernel, ncov_kernel (wavefront per (job, PRG)), forms the same DM-RS residuals again and turns them into the noise-plus-interference
+// covariance across the ports: miphy_pusch_noise_covariance_batch. It takes the helpers and the job rules from here and writes no estimate.
 // What they share stands once, in front of them: the thread count, the LDS layout (chest_lds, which also sizes the launches), the job rules
 // (chest_job_rule: chest_validate on the host, device-resident jobs of the layered entry on the device) and the chest_* helpers. What differs
 // stays in the kernels: pilot ownership, despreading, the two-parameter noise fit, external pilots, hopping. Behind the kernels: chest_prologue
@@ -227,7 +229,14 @@ __device__ __forceinline__ cplx chest_ls(const float2 (&x)[4], int nds, float& e
   return acc;
 }
 
-// Residual energy at one pilot: |rx + h * pilot(d)|^2 over the DM-RS symbols, h = -(the predicted channel), added to noise_acc term by term.
+// The residual at one pilot of one DM-RS symbol: rx + h * pilot, h = -(the predicted channel).
+__device__ __forceinline__ cplx chest_residual_at(float2 x, cplx h, cplx pilot)
+{
+  const cplx pred = cmul(h, pilot);
+  return cplx{pred.x + x.x, pred.y + x.y};
+}
+
+// Residual energy at one pilot: |rx + h * pilot(d)|^2 over the DM-RS symbols, added to noise_acc term by term.
 template <class Pilot>
 __device__ __forceinline__ void chest_residual(const float2 (&x)[4], int nds, cplx h, float& noise_acc, const Pilot& pilot)
 {
@@ -235,9 +244,8 @@ __device__ __forceinline__ void chest_residual(const float2 (&x)[4], int nds, cp
   for (int d = 0; d < 4; ++d) {
     if (d >= nds)
       continue;
-    const cplx  pred = cmul(h, pilot(d));
-    const float er = pred.x + x[d].x, ei = pred.y + x[d].y;
-    noise_acc += er * er + ei * ei;
+    const cplx e = chest_residual_at(x[d], h, pilot(d));
+    noise_acc += e.x * e.x + e.y * e.y;
   }
 }
 
@@ -642,6 +650,175 @@ __global__ void __launch_bounds__(CHEST_THREADS, 4) chest_layers_kernel(const mi
     chest_scalars(scalars, job, port, 2 * grp + tid, tid ? rsrp[1] : rsrp[0], epre, noise_var, tid ? ta[1] : ta[0], true, true);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Noise-plus-interference covariance across the receive ports, from the residuals whose energy chest_layers_kernel turns into noise_var
+// (miphy_pusch_noise_covariance_batch; include/miphy.h has the formula). A workgroup serves (job, eight PRGs): the PRB list and the Gold
+// sequences are put together once, as in the estimator, then every wavefront takes one PRG. Its lanes own pilot pairs, 63 per pass -- 21 whole
+// PRBs, so the three pairs of a PRB sit on neighbouring lanes and the per-PRB means come from three lane reads, summed in the estimator's order.
+// Per CDM group a lane holds the residuals of its two pilots on every port and DM-RS symbol and adds their P (P + 1) / 2 products to its own
+// accumulators (groups, pilots of the pair, DM-RS symbols: ascending); the lanes are then summed in a fixed butterfly. No atomics: a PRG's matrix
+// has the same bits whatever else is in the batch.
+constexpr int NCOV_PAIRS = 63, NCOV_PRG_PER_BLOCK = CHEST_THREADS / 64;
+
+__host__ __device__ inline bool ncov_job_ok(const miphy_pusch_ncov_job& j)
+{
+  return chest_job_rule(j.base, false) == CHEST_RULE_NONE && j.loading >= 0.f && j.loading <= 3.402823466e+38f; // (NaN fails both)
+}
+
+__host__ __device__ inline unsigned ncov_nof_prg(unsigned nprb, unsigned prg_size)
+{
+  return prg_size ? (nprb + prg_size - 1) / prg_size : 1u;
+}
+
+__global__ void __launch_bounds__(CHEST_THREADS) ncov_kernel(const miphy_pusch_ncov_job* __restrict__ jobs, const gold_jump* __restrict__ gj,
+                                                             const float2* __restrict__ grid, float2* __restrict__ cov)
+{
+  __shared__ uint32_t cbits[4 * 104];
+  __shared__ uint64_t rbm[5];
+  __shared__ uint16_t prb_of[276];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const miphy_pusch_ncov_job& jm = jobs[blockIdx.x];
+  if (!ncov_job_ok(jm)) // (uniform) a device-resident job that breaks a rule
+    return;
+  const miphy_pusch_chest_job job = load_words(&jm.base);
+  const int L = job.nof_tx_layers, P = job.nof_rx_ports;
+  const int nprb_grid = job.grid_nof_prb, nsc = nprb_grid * 12;
+  int       dsym[4];
+  const int nds  = chest_dmrs_symbols(job.symbols_mask, job.first_symbol, job.first_symbol + job.nof_symbols, dsym);
+  const int nprb = chest_prb_list(jm.base.rb_mask, nprb_grid, rbm, prb_of, tid);
+  const int per  = jm.prg_size ? (int)jm.prg_size : nprb;
+  const int nprg = (nprb + per - 1) / per;
+  if ((int)blockIdx.y * NCOV_PRG_PER_BLOCK >= nprg) // (uniform) the launch is sized for the job with the most PRGs
+    return;
+  uint32_t c_init[4];
+  chest_c_init(job, dsym, nds, c_init);
+  gold_bits_block(*reinterpret_cast<const gold_tables*>(gj), c_init[0], c_init[1], c_init[2], c_init[3], nds, 12 * nprb_grid, cbits, tid);
+  const int prg = blockIdx.y * NCOV_PRG_PER_BLOCK + wave;
+  if (prg >= nprg) // (per wavefront; no barrier follows)
+    return;
+  const int   prb0 = prg * per, n_j = min(per, nprb - prb0), npairs = 3 * n_j;
+  const int   ngrp = (L + 1) / 2;
+  const float beta = job.scaling, ts = 1.0f / ((float)nds * beta);
+  float       cd[4] = {0.f, 0.f, 0.f, 0.f}; // C_pp
+  cplx        co[6];                        // C_pq, p > q, at p (p - 1) / 2 + q
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+    co[k] = {0.f, 0.f};
+  const int b3 = lane - lane % 3; // the first lane of this lane's PRB
+  for (int base = 0; base < npairs; base += NCOV_PAIRS) {
+    const int  m    = base + lane;
+    const bool live = lane < NCOV_PAIRS && m < npairs;
+    const int  r    = prb_of[prb0 + (live ? m / 3 : 0)], t3 = m % 3;
+    const int  gp0  = r * 6 + 2 * t3;
+    cplx       pil[2][4];
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+        pil[e][d] = d < nds ? chest_qpsk_pilot(cbits, d, gp0 + e) : cplx{0.f, 0.f};
+#pragma nounroll
+    for (int grp = 0; grp < ngrp; ++grp) {
+      const bool pair = 2 * grp + 1 < L; // both layers of the group are present
+      cplx       res[4][2][4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        float2 x[2][4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          x[0][d] = x[1][d] = make_float2(0.f, 0.f);
+          if (live && p < P && d < nds) {
+            const float2* src = chest_port_grid(grid, job, p) + (size_t)dsym[d] * nsc + r * 12 + 4 * t3 + grp;
+            x[0][d] = src[0];
+            x[1][d] = src[2];
+          }
+        }
+        cplx z[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          float      unused = 0.f;
+          const cplx acc    = chest_ls(x[e], nds, unused, [&](int d) { return pil[e][d]; });
+          z[e]              = {acc.x * ts, acc.y * ts};
+        }
+        if (pair) { // s_a, s_b of the pair
+          const cplx sa = {(z[0].x + z[1].x) * 0.5f, (z[0].y + z[1].y) * 0.5f}, sb = {(z[0].x - z[1].x) * 0.5f, (z[0].y - z[1].y) * 0.5f};
+          z[0] = sa, z[1] = sb;
+        }
+        cplx s[2]; // the PRB's sums of the even and of the odd entries, lanes in order
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const cplx v0 = {__shfl(z[e].x, b3), __shfl(z[e].y, b3)}, v1 = {__shfl(z[e].x, b3 + 1), __shfl(z[e].y, b3 + 1)},
+                     v2 = {__shfl(z[e].x, b3 + 2), __shfl(z[e].y, b3 + 2)};
+          s[e] = cadd(cadd(v0, v1), v2);
+        }
+        cplx ma, mb; // a layer alone: the mean of its six z, no second parameter
+        if (pair)
+          ma = {s[0].x / 3.f, s[0].y / 3.f}, mb = {s[1].x / 3.f, s[1].y / 3.f};
+        else
+          ma = {(s[0].x + s[1].x) / 6.f, (s[0].y + s[1].y) / 6.f}, mb = {0.f, 0.f};
+        const cplx h[2] = {{(ma.x + mb.x) * -beta, (ma.y + mb.y) * -beta}, {(ma.x - mb.x) * -beta, (ma.y - mb.y) * -beta}};
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+#pragma unroll
+          for (int d = 0; d < 4; ++d)
+            res[p][e][d] = (live && p < P && d < nds) ? chest_residual_at(x[e][d], h[e], pil[e][d]) : cplx{0.f, 0.f};
+      }
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+#pragma unroll
+          for (int p = 0; p < 4; ++p) {
+            const cplx a = res[p][e][d];
+            cd[p] += a.x * a.x + a.y * a.y;
+#pragma unroll
+            for (int q = 0; q < p; ++q) { // a conj(b)
+              const cplx b = res[q][e][d];
+              co[p * (p - 1) / 2 + q].x += a.x * b.x + a.y * b.y;
+              co[p * (p - 1) / 2 + q].y += a.y * b.x - a.x * b.y;
+            }
+          }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      cd[p] += __shfl_xor(cd[p], off);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      co[k].x += __shfl_xor(co[k].x, off);
+      co[k].y += __shfl_xor(co[k].y, off);
+    }
+  }
+  if (lane != 0)
+    return;
+  int fitted = 0; // sum over the groups of 6 nds - f_g
+  for (int grp = 0; grp < ngrp; ++grp)
+    fitted += 6 * nds - (2 * grp + 1 < L ? 2 : 1);
+  const float div = (float)n_j * (float)fitted;
+  float       tr  = 0.f;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    cd[p] = cd[p] / div;
+    if (p < P)
+      tr += cd[p];
+  }
+  const float load = jm.loading * tr / (float)P;
+  float2*     out  = cov + jm.cov_offset + (size_t)prg * P * P;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    if (p >= P)
+      continue;
+    out[p * P + p] = make_float2(cd[p] + load, 0.f);
+#pragma unroll
+    for (int q = 0; q < p; ++q) {
+      const float2 v = make_float2(co[p * (p - 1) / 2 + q].x / div, co[p * (p - 1) / 2 + q].y / div);
+      out[p * P + q] = v;
+      out[q * P + p] = make_float2(v.x, -v.y);
+    }
+  }
+}
+
 } // namespace
 
 // The rules a batch of host jobs is held to (chest_job_rule), and its largest port and layer counts.
@@ -826,4 +1003,48 @@ extern "C" int miphy_port_channel_estimate_batch(miphy_ctx* ctx, const miphy_pus
 {
   MIPHY_REQUIRE(pilots, "miphy_port_channel_estimate_batch: null pilots");
   return chest_launch(ctx, jobs, jobs_on_device, n, grid, pilots, ce, scalars, stream, "miphy_port_channel_estimate_batch");
+}
+
+extern "C" uint32_t miphy_pusch_noise_covariance_nof_prg(const miphy_pusch_ncov_job* job)
+{
+  if (!job || !ncov_job_ok(*job))
+    return 0;
+  return ncov_nof_prg(miphy_count_prb(job->base.rb_mask, job->base.grid_nof_prb), job->prg_size);
+}
+
+// One matrix per PRG of every job, straight from the grid: the estimator's residuals are formed again (same helpers), nothing of its output is read.
+extern "C" int miphy_pusch_noise_covariance_batch(miphy_ctx* ctx, const miphy_pusch_ncov_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                                  float* cov, void* stream)
+{
+  const char* what = "miphy_pusch_noise_covariance_batch";
+  unsigned    max_ports, max_layers, max_prg = 275; // device-resident jobs: one PRB per PRG on the widest grid
+  int         rc = chest_prologue(what, ctx && jobs && grid && cov, n, UINT32_MAX, jobs_on_device, max_ports, max_layers, [&](unsigned& mp, unsigned& ml) -> int {
+    std::vector<miphy_pusch_chest_job> base(n);
+    for (uint32_t i = 0; i < n; ++i)
+      base[i] = jobs[i].base;
+    const int r = chest_validate(base.data(), n, false, mp, ml);
+    if (r)
+      return r;
+    max_prg = 1;
+    for (uint32_t i = 0; i < n; ++i) {
+      MIPHY_REQUIRE(ncov_job_ok(jobs[i]), "pusch_noise_covariance: job %u: the diagonal loading should be finite and not negative", i);
+      const unsigned g = ncov_nof_prg(miphy_count_prb(jobs[i].base.rb_mask, jobs[i].base.grid_nof_prb), jobs[i].prg_size);
+      max_prg          = g > max_prg ? g : max_prg;
+    }
+    return (int)MIPHY_OK;
+  });
+  if (rc || n == 0)
+    return rc;
+  hipStream_t s      = (hipStream_t)stream;
+  const void* d_jobs = nullptr;
+  if ((rc = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pusch_ncov_job) * (size_t)n, s, &d_jobs)))
+    return rc;
+  const cplx*      tw;
+  const gold_jump* gold;
+  if ((rc = chest_resources(ctx, &tw, &gold)))
+    return rc;
+  hipLaunchKernelGGL(ncov_kernel, dim3(n, (max_prg + NCOV_PRG_PER_BLOCK - 1) / NCOV_PRG_PER_BLOCK), dim3(CHEST_THREADS), 0, s,
+                     (const miphy_pusch_ncov_job*)d_jobs, gold, (const float2*)grid, (float2*)cov);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
 }

@@ -2,8 +2,10 @@
 // the choice of the noise variance), equalize_zf_1xn.h:120-158 (one layer, scalar path: exact reciprocal) and equalize_zf_2x2.cpp:30-117.
 // HBM-bound streaming kernel: per resource element 2 * ports * (1 + layers) floats in, 3 * layers floats out, every operand read once
 // with consecutive lanes on consecutive elements; grid = (chunks of 1024 elements, jobs).
+// Beyond the reference: zero forcing of 1..4 layers (equalize_device.h) and MMSE-IRC against a noise covariance matrix (mmse_device.h), same tiling.
 #include "miphy_internal.h"
 #include "equalize_device.h"
+#include "mmse_device.h"
 #include <math.h>
 
 namespace {
@@ -145,7 +147,106 @@ __global__ __launch_bounds__(EQ_THREADS) void equalize_layers_kernel(const miphy
   }
 }
 
+// MMSE-IRC (mmse_device.h) with the tiling of equalize_layers_kernel. A thread's elements are EQ_THREADS apart, so the covariance matrix of
+// element i, i / re_per_cov, changes rarely along its walk: the matrix is loaded and factored when it changes, not per element.
+template <int L>
+__device__ __forceinline__ void equalize_mmse_elements(const miphy_equalizer_mmse_job& jm, uint32_t lo, uint32_t hi, const float2* __restrict__ y,
+                                                       const float2* __restrict__ h, const float2* __restrict__ cov, float2* __restrict__ z,
+                                                       float* __restrict__ nv)
+{
+  const miphy_equalizer_job& j   = jm.base;
+  const uint32_t             nre = j.nof_re;
+  const int                  np  = j.nof_rx_ports;
+  mmse_factored              f;
+  uint32_t                   cur = UINT32_MAX;
+  for (uint32_t i = lo + threadIdx.x; i < hi; i += EQ_THREADS) {
+    const uint32_t mi = jm.re_per_cov ? i / jm.re_per_cov : 0u;
+    if (mi != cur) {
+      cur = mi;
+      const float2* cm = cov + (size_t)mi * np * np;
+      float2        c[4][4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int q = 0; q <= p; ++q)
+          c[p][q] = (p < np) ? cm[p * np + q] : make_float2(0.f, 0.f);
+      mmse_factor(c, np, f);
+    }
+    float2 hh[L][4], yy[4], x[L];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      yy[p] = (p < np) ? y[(size_t)p * nre + i] : make_float2(0.f, 0.f);
+#pragma unroll
+      for (int l = 0; l < L; ++l)
+        hh[l][p] = (p < np) ? h[((size_t)l * np + p) * nre + i] : make_float2(0.f, 0.f);
+    }
+    mmse_prepared<L> q;
+    mmse_prepare<L>(hh, np, f, j.tx_scaling, q);
+    mmse_apply<L>(np, f, yy, q, x);
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+      z[(size_t)l * nre + i]  = x[l];
+      nv[(size_t)l * nre + i] = q.nvar[l];
+    }
+  }
+}
+
+__global__ __launch_bounds__(EQ_THREADS) void equalize_mmse_kernel(const miphy_equalizer_mmse_job* __restrict__ jobs, const float2* __restrict__ ch_symbols,
+                                                                   const float2* __restrict__ ch_estimates, const float2* __restrict__ cov,
+                                                                   float2* __restrict__ eq_symbols, float* __restrict__ eq_noise_vars)
+{
+  const miphy_equalizer_mmse_job jm = jobs[blockIdx.y];
+  const miphy_equalizer_job&     j  = jm.base;
+  const uint32_t lo = blockIdx.x * EQ_RE_PER_BLOCK;
+  if (lo >= j.nof_re || !equalize_layers_topology_ok(j) || !(j.tx_scaling > 0.f)) // (a device-resident job the host has not seen: skipped)
+    return;
+  const uint32_t hi = min(j.nof_re, lo + EQ_RE_PER_BLOCK);
+  const float2*  y  = ch_symbols + j.ch_symbols_offset;
+  const float2*  h  = ch_estimates + j.ch_estimates_offset;
+  const float2*  c  = cov + jm.cov_offset;
+  float2*        z  = eq_symbols + j.eq_symbols_offset;
+  float*         nv = eq_noise_vars + j.eq_noise_vars_offset;
+  switch (j.nof_tx_layers) {
+    case 1: equalize_mmse_elements<1>(jm, lo, hi, y, h, c, z, nv); break;
+    case 2: equalize_mmse_elements<2>(jm, lo, hi, y, h, c, z, nv); break;
+    case 3: equalize_mmse_elements<3>(jm, lo, hi, y, h, c, z, nv); break;
+    default: equalize_mmse_elements<4>(jm, lo, hi, y, h, c, z, nv); break;
+  }
+}
+
 } // namespace
+
+extern "C" int miphy_channel_equalize_mmse_batch(miphy_ctx* ctx, const miphy_equalizer_mmse_job* jobs, int jobs_on_device, uint32_t n, const float* ch_symbols,
+                                                 const float* ch_estimates, const float* cov, float* eq_symbols, float* eq_noise_vars, void* stream)
+{
+  MIPHY_REQUIRE(ctx && jobs && ch_symbols && ch_estimates && cov && eq_symbols && eq_noise_vars, "miphy_channel_equalize_mmse_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  MIPHY_REQUIRE(n <= 65535, "channel_equalize_mmse: at most 65535 jobs per call");
+  uint32_t max_re = 275 * 12 * 14; // device-resident jobs: the largest slot
+  if (!jobs_on_device) {
+    max_re = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const miphy_equalizer_job& j = jobs[i].base;
+      MIPHY_REQUIRE(equalize_layers_topology_ok(j), "Invalid channel spatial topology: %u Rx ports, %u Tx layers (1..4 layers on at least as many ports, at most 4).",
+                    j.nof_rx_ports, j.nof_tx_layers);
+      MIPHY_REQUIRE(j.tx_scaling > 0.f, "Tx scaling factor must be positive.");
+      max_re = j.nof_re > max_re ? j.nof_re : max_re;
+    }
+    if (max_re == 0)
+      return MIPHY_OK;
+  }
+  hipStream_t s      = (hipStream_t)stream;
+  const void* d_jobs = nullptr;
+  int         rc     = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_equalizer_mmse_job) * (size_t)n, s, &d_jobs);
+  if (rc)
+    return rc;
+  hipLaunchKernelGGL(equalize_mmse_kernel, dim3((max_re + EQ_RE_PER_BLOCK - 1) / EQ_RE_PER_BLOCK, n), dim3(EQ_THREADS), 0, s,
+                     (const miphy_equalizer_mmse_job*)d_jobs, (const float2*)ch_symbols, (const float2*)ch_estimates, (const float2*)cov, (float2*)eq_symbols,
+                     eq_noise_vars);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
+}
 
 extern "C" int miphy_channel_equalize_layers_batch(miphy_ctx* ctx, const miphy_equalizer_job* jobs, int jobs_on_device, uint32_t n, const float* ch_symbols,
                                                    const float* ch_estimates, float* eq_symbols, float* eq_noise_vars, void* stream)

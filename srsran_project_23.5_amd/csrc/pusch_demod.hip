@@ -11,10 +11,13 @@
 // once. The descrambling sequence of the symbol is produced in LDS by jumping the two LFSRs to the symbol's first bit
 // (gold_device.h). Floating point: single IEEE operations in a fixed order (no contraction), exact division,
 // so the LLRs are reproducible bit for bit by a scalar CPU restatement; against the reference AVX2 build they are within one step.
+// Beyond the reference: 1..4 layers (zero forcing, equalize_device.h), transform precoding, and MMSE-IRC on 1..4 layers (mmse_device.h) in the
+// frame of the layered walk.
 #define NR_DEMOD_TABLE_ATTR __device__
 #include "gold_device.h"
 #include "demod_device.h"
 #include "equalize_device.h"
+#include "mmse_device.h"
 #include "mod_device.h"
 #include "tp_device.h"
 #include "miphy_ext.h"
@@ -561,6 +564,9 @@ __host__ __device__ __forceinline__ const miphy_pusch_demod_job& pusch_demod_bas
 __host__ __device__ __forceinline__ const miphy_pusch_demod_job& pusch_demod_base(const miphy_pusch_demod_layers_job& job) { return job.base; }
 __host__ __device__ __forceinline__ unsigned pusch_demod_layers(const miphy_pusch_demod_job&) { return 1; }
 __host__ __device__ __forceinline__ unsigned pusch_demod_layers(const miphy_pusch_demod_layers_job& job) { return job.nof_tx_layers; }
+// (the MMSE record: a layered record and where its covariance matrices are)
+__host__ __device__ __forceinline__ const miphy_pusch_demod_job& pusch_demod_base(const miphy_pusch_demod_mmse_job& job) { return job.base.base; }
+__host__ __device__ __forceinline__ unsigned pusch_demod_layers(const miphy_pusch_demod_mmse_job& job) { return job.base.nof_tx_layers; }
 
 // What a job (j = its base record, L = its layers) must satisfy, once, evaluated in this order: R(condition, message of the host, its arguments).
 // The host refuses a job that breaks a rule with the rule's message; the kernels skip a device-resident layered job that does
@@ -593,6 +599,7 @@ __host__ __device__ __forceinline__ bool pusch_demod_layers_job_ok(const miphy_p
 #undef PUSCH_RULE_HOLDS
 }
 __device__ __forceinline__ bool pusch_demod_layers_job_ok(const miphy_pusch_demod_job&, bool) { return true; } // (a base record is not checked on the device)
+__host__ __device__ __forceinline__ bool pusch_demod_layers_job_ok(const miphy_pusch_demod_mmse_job& mj, bool have_ph) { return pusch_demod_layers_job_ok(mj.base, have_ph); }
 
 // Per-symbol EVM sums of every transmission; a job the demodulator skipped keeps its 14 floats.
 template <typename JOB>
@@ -700,8 +707,11 @@ __device__ __forceinline__ float demod_emit_exact(float re, float im, float nvar
 // symbols. EVM: the terms of an element's layers are added in layer order, then demod_evm_sum and (pusch_evm_reduce_kernel) the chunks in order, as
 // demod_columns does, so a symbol's sum has one value. Every thread of the workgroup reaches the barriers of the sum; without EX a lane that owns
 // no subcarrier leaves at once.
-template <int MOD, int L, bool EX>
-__device__ __forceinline__ void demod_layers_columns(const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab, float* evm_red, int tid)
+// MMSE: mmse_prepare / mmse_apply (mmse_device.h) in place of zf_prepare / zf_apply. cm: the covariance matrix of this thread's PRG, [P][P]; a subcarrier
+// stays in its PRG, so the matrix is loaded and factored once, in front of the walk. a.noise_var is not used.
+template <int MOD, int L, bool EX, bool MMSE = false>
+__device__ __forceinline__ void demod_layers_columns(const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab, float* evm_red, int tid,
+                                                     const float2* cm = nullptr)
 {
 #pragma clang fp contract(off)
   const int  nsc = a.nsc, np = a.nports;
@@ -720,12 +730,27 @@ __device__ __forceinline__ void demod_layers_columns(const demod_args& a, bool a
         if (p < np)
           h[l][p] = a.ce[((size_t)(l * np + p) * a.ce_nof_symbols + row) * nsc + sc];
   };
-  zf_prepared<L> q;
+  std::conditional_t<MMSE, mmse_prepared<L>, zf_prepared<L>> q;
+  mmse_factored                                              f; // (MMSE only)
   if (!EX && !active)
     return;
+  if constexpr (MMSE) {
+    if (active) {
+      float2 c[4][4];
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int k = 0; k <= p; ++k)
+          c[p][k] = (p < np) ? cm[p * np + k] : make_float2(0.f, 0.f);
+      mmse_factor(c, np, f);
+    }
+  }
   if (active && compact) {
     load_h(0);
-    zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
+    if constexpr (MMSE)
+      mmse_prepare<L>(h, np, f, 1.0f, q);
+    else
+      zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
   }
   int prefix = a.prefix0; // data elements per layer of the transmission before the current symbol
   for (int sy = a.start_symbol; sy < a.end_symbol; ++sy) { // (uniform)
@@ -740,9 +765,15 @@ __device__ __forceinline__ void demod_layers_columns(const demod_args& a, bool a
         y[p] = (p < np) ? a.grid[((size_t)((a.rxp >> (8 * p)) & 0xffu) * 14 + sy) * nsc + sc] : make_float2(0.f, 0.f);
       if (!compact) {
         load_h(sy);
-        zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
+        if constexpr (MMSE)
+          mmse_prepare<L>(h, np, f, 1.0f, q);
+        else
+          zf_prepare<L>(h, np, a.noise_var, 1.0f, q);
       }
-      zf_apply<L>(h, np, y, q, x);
+      if constexpr (MMSE)
+        mmse_apply<L>(np, f, y, q, x);
+      else
+        zf_apply<L>(h, np, y, q, x);
       const unsigned el   = (unsigned)(prefix + r);  // the element's index in the codeword, what the placeholder list holds
       const uint32_t e0   = el * (uint32_t)L;        // first of the element's L codeword symbols
       const uint32_t bo   = e0 * (uint32_t)MOD;
@@ -771,9 +802,28 @@ __device__ __forceinline__ void demod_layers_columns(const demod_args& a, bool a
 }
 
 // ONE_LAYER: the one-layer walk (demod_columns), which follows the reference operation for operation; otherwise L = 2..4. EX: with placeholders and EVM.
-template <int MOD, bool ONE_LAYER, bool EX>
-__device__ __forceinline__ void demod_dispatch(int L, const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab, float* evm_red, int tid)
+// MMSE: every layer count, one included, goes through demod_layers_columns with the thread's covariance matrix cm.
+template <int MOD, bool ONE_LAYER, bool EX, bool MMSE = false>
+__device__ __forceinline__ void demod_dispatch(int L, const demod_args& a, bool active, int sc, int a_idx, int r_dm, const float2* tab, float* evm_red, int tid,
+                                               const float2* cm = nullptr)
 {
+  if constexpr (MMSE) {
+    switch (L) { // uniform
+      case 1:
+        demod_layers_columns<MOD, 1, EX, true>(a, active, sc, a_idx, r_dm, tab, evm_red, tid, cm);
+        break;
+      case 2:
+        demod_layers_columns<MOD, 2, EX, true>(a, active, sc, a_idx, r_dm, tab, evm_red, tid, cm);
+        break;
+      case 3:
+        demod_layers_columns<MOD, 3, EX, true>(a, active, sc, a_idx, r_dm, tab, evm_red, tid, cm);
+        break;
+      default:
+        demod_layers_columns<MOD, 4, EX, true>(a, active, sc, a_idx, r_dm, tab, evm_red, tid, cm);
+        break;
+    }
+    return;
+  }
   if constexpr (ONE_LAYER) {
     demod_columns<MOD>(a, active, sc, a_idx, r_dm, tab, evm_red, tid);
     return;
@@ -802,18 +852,21 @@ __device__ __forceinline__ void demod_dispatch(int L, const demod_args& a, bool 
 #ifndef DEMOD_MIN_WAVES
 #define DEMOD_MIN_WAVES 6 // 80 registers (four of them spilled outside the walk): 0.207 against 0.214 ms per 1024 slots at five
 #endif
+// The body of both kernels below. A miphy_pusch_demod_mmse_job batch has one instance for every layer count (ONE_LAYER = false), which takes the
+// covariance matrices `cov` and never reads `scalars`.
 template <typename JOB, bool ONE_LAYER, bool EX>
-__global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1) pusch_demod_kernel(const JOB* __restrict__ jobs, const float2* __restrict__ grid,
-                                                                                     const float2* __restrict__ ce, const float* __restrict__ scalars,
-                                                                                     int8_t* __restrict__ llr, const uint32_t* __restrict__ seq, uint32_t stride,
-                                                                                     const uint16_t* __restrict__ placeholders, float* __restrict__ evm_part)
+__device__ __forceinline__ void pusch_demod_body(const JOB* __restrict__ jobs, const float2* __restrict__ grid, const float2* __restrict__ ce,
+                                                 const float* __restrict__ scalars, int8_t* __restrict__ llr, const uint32_t* __restrict__ seq, uint32_t stride,
+                                                 const uint16_t* __restrict__ placeholders, float* __restrict__ evm_part, const float2* __restrict__ cov)
 {
+  constexpr bool MMSE = std::is_same<JOB, miphy_pusch_demod_mmse_job>::value;
+  static_assert(!MMSE || !ONE_LAYER, "the MMSE walk is the layered one");
   __shared__ uint16_t prb_of[276];
   __shared__ float2   tab[64];
   __shared__ uint64_t rbm[5];
   __shared__ float    evm_red[4];
   const int L = (int)pusch_demod_layers(jobs[blockIdx.x]);
-  if ((L == 1) != ONE_LAYER) // uniform
+  if (!MMSE && (L == 1) != ONE_LAYER) // uniform
     return;
   if (!pusch_demod_layers_job_ok(jobs[blockIdx.x], EX && placeholders)) // uniform: a device-resident job the host has not seen is skipped
     return;
@@ -825,7 +878,9 @@ __global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1
   if ((int)blockIdx.y * DEMOD_THREADS >= nprb * 12)
     return; // uniform
   const demod_tab_entry te        = demod_table_entry(j.mod(), tid);            // requested now, stored behind the PRB list
-  const float           noise_var = scalars[j.scalars_offset() + 2]; // likewise
+  float                 noise_var = 0.f;
+  if constexpr (!MMSE)
+    noise_var = scalars[j.scalars_offset() + 2]; // likewise
   demod_prb_list(j, rbm, prb_of, tid, DEMOD_THREADS);
   demod_table_store(tab, te); // (made visible by the barrier in front of the walk)
   const unsigned dmask = dmrs_prb_mask(j.dmrs_type(), j.cdm_groups());
@@ -869,34 +924,58 @@ __global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1
   const int  pr     = a_idx / 12, k = a_idx - 12 * pr;
   const int  sc     = active ? (int)prb_of[pr] * 12 + k : 0;
   const int  r_dm   = ((dmask >> k) & 1u) ? -1 : pr * a.per_dm + __popc(~dmask & ((1u << k) - 1u));
+  const float2* cm = nullptr; // MMSE: the matrix of this thread's PRG = rank of its PRB among the allocated ones / prg_size
+  if constexpr (MMSE) {
+    const unsigned prg_size = jobs[blockIdx.x].prg_size;
+    cm = cov + jobs[blockIdx.x].cov_offset + (size_t)((active && prg_size) ? (unsigned)pr / prg_size : 0u) * (unsigned)(a.nports * a.nports);
+  }
   __syncthreads(); // interval tables in LDS
   switch (j.mod()) {
     case 8:
-      demod_dispatch<8, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_dispatch<8, ONE_LAYER, EX, MMSE>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid, cm);
       break;
     case 6:
-      demod_dispatch<6, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_dispatch<6, ONE_LAYER, EX, MMSE>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid, cm);
       break;
     case 4:
-      demod_dispatch<4, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_dispatch<4, ONE_LAYER, EX, MMSE>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid, cm);
       break;
     case 2:
-      demod_dispatch<2, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_dispatch<2, ONE_LAYER, EX, MMSE>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid, cm);
       break;
     default:
-      demod_dispatch<1, ONE_LAYER, EX>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid);
+      demod_dispatch<1, ONE_LAYER, EX, MMSE>(L, a, active, sc, a_idx, r_dm, tab, evm_red, tid, cm);
       break;
   }
+}
+
+template <typename JOB, bool ONE_LAYER, bool EX>
+__global__ void __launch_bounds__(DEMOD_THREADS, ONE_LAYER ? DEMOD_MIN_WAVES : 1) pusch_demod_kernel(const JOB* __restrict__ jobs, const float2* __restrict__ grid,
+                                                                                     const float2* __restrict__ ce, const float* __restrict__ scalars,
+                                                                                     int8_t* __restrict__ llr, const uint32_t* __restrict__ seq, uint32_t stride,
+                                                                                     const uint16_t* __restrict__ placeholders, float* __restrict__ evm_part)
+{
+  pusch_demod_body<JOB, ONE_LAYER, EX>(jobs, grid, ce, scalars, llr, seq, stride, placeholders, evm_part, nullptr);
+}
+
+template <bool EX>
+__global__ void __launch_bounds__(DEMOD_THREADS, 1) pusch_demod_mmse_kernel(const miphy_pusch_demod_mmse_job* __restrict__ jobs, const float2* __restrict__ grid,
+                                                                            const float2* __restrict__ ce, const float2* __restrict__ cov, int8_t* __restrict__ llr,
+                                                                            const uint32_t* __restrict__ seq, uint32_t stride,
+                                                                            const uint16_t* __restrict__ placeholders, float* __restrict__ evm_part)
+{
+  pusch_demod_body<miphy_pusch_demod_mmse_job, false, EX>(jobs, grid, ce, nullptr, llr, seq, stride, placeholders, evm_part, cov);
 }
 
 // All four entry points: `who` names the entry in the messages, ex: it is an _ex one (only the message of the placeholder rule depends on it). The EX
 // instances run when the call has EVM sums or a job with placeholders; device-resident jobs cannot be looked at, there the two pointers decide.
 template <typename JOB>
 int pusch_demodulate(const char* who, miphy_ctx* ctx, const JOB* jobs, int jobs_on_device, uint32_t n, const float* grid, const float* ce, const float* scalars,
-                     int8_t* llr, const uint16_t* placeholders, float* evm_sums, bool ex, void* stream)
+                     const float* cov, int8_t* llr, const uint16_t* placeholders, float* evm_sums, bool ex, void* stream)
 {
-  constexpr bool layered = std::is_same<JOB, miphy_pusch_demod_layers_job>::value;
-  MIPHY_REQUIRE(ctx && jobs && grid && ce && scalars && llr, "miphy_%s_batch: null argument", who);
+  constexpr bool mmse    = std::is_same<JOB, miphy_pusch_demod_mmse_job>::value; // scalars: not read, may be null; cov: the matrices
+  constexpr bool layered = mmse || std::is_same<JOB, miphy_pusch_demod_layers_job>::value;
+  MIPHY_REQUIRE(ctx && jobs && grid && ce && (mmse ? cov != nullptr : scalars != nullptr) && llr, "miphy_%s_batch: null argument", who);
   if (n == 0)
     return MIPHY_OK;
   MIPHY_REQUIRE(n <= 65535, "%s: batch too large (max 65535 transmissions per call)", who);
@@ -946,15 +1025,20 @@ int pusch_demodulate(const char* who, miphy_ctx* ctx, const JOB* jobs, int jobs_
                      seq, stride, have_ph);
   const uint32_t sym_parts = std::max(1u, std::min(4u, (uint32_t)ctx->num_cus / (n * max_chunks)));
   const dim3 blocks(n, max_chunks, sym_parts);
-  auto       launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, blocks, dim3(DEMOD_THREADS), 0, s, dj, (const float2*)grid, (const float2*)ce, scalars, llr, (const uint32_t*)seq, stride,
-                       placeholders, evm_part);
-  };
-  if (one_layer)
-    launch(extras ? pusch_demod_kernel<JOB, true, true> : pusch_demod_kernel<JOB, true, false>);
-  if constexpr (layered) {
-    if (more_layers)
-      launch(extras ? pusch_demod_kernel<JOB, false, true> : pusch_demod_kernel<JOB, false, false>);
+  if constexpr (mmse) { // one instance for every layer count
+    hipLaunchKernelGGL(extras ? pusch_demod_mmse_kernel<true> : pusch_demod_mmse_kernel<false>, blocks, dim3(DEMOD_THREADS), 0, s, dj, (const float2*)grid,
+                       (const float2*)ce, (const float2*)cov, llr, (const uint32_t*)seq, stride, placeholders, evm_part);
+  } else {
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, blocks, dim3(DEMOD_THREADS), 0, s, dj, (const float2*)grid, (const float2*)ce, scalars, llr, (const uint32_t*)seq, stride,
+                         placeholders, evm_part);
+    };
+    if (one_layer)
+      launch(extras ? pusch_demod_kernel<JOB, true, true> : pusch_demod_kernel<JOB, true, false>);
+    if constexpr (layered) {
+      if (more_layers)
+        launch(extras ? pusch_demod_kernel<JOB, false, true> : pusch_demod_kernel<JOB, false, false>);
+    }
   }
   if (evm_sums)
     hipLaunchKernelGGL(pusch_evm_reduce_kernel<JOB>, dim3(n), dim3(64), 0, s, dj, (const float*)evm_part, evm_sums, have_ph);
@@ -1209,7 +1293,7 @@ extern "C" int miphy_pusch_demodulate_batch_ex(miphy_ctx* ctx, const miphy_pusch
                                                const float* ce, const float* scalars, int8_t* llr, const uint16_t* placeholders, float* evm_sums,
                                                void* stream)
 {
-  return pusch_demodulate("pusch_demodulate", ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, placeholders, evm_sums, true, stream);
+  return pusch_demodulate("pusch_demodulate", ctx, jobs, jobs_on_device, n, grid, ce, scalars, nullptr, llr, placeholders, evm_sums, true, stream);
 }
 
 extern "C" int miphy_pusch_demodulate_batch(miphy_ctx* ctx, const miphy_pusch_demod_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
@@ -1222,11 +1306,24 @@ extern "C" int miphy_pusch_demodulate_layers_batch_ex(miphy_ctx* ctx, const miph
                                                       const float* grid, const float* ce, const float* scalars, int8_t* llr, const uint16_t* placeholders,
                                                       float* evm_sums, void* stream)
 {
-  return pusch_demodulate("pusch_demodulate_layers", ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, placeholders, evm_sums, true, stream);
+  return pusch_demodulate("pusch_demodulate_layers", ctx, jobs, jobs_on_device, n, grid, ce, scalars, nullptr, llr, placeholders, evm_sums, true, stream);
 }
 
 extern "C" int miphy_pusch_demodulate_layers_batch(miphy_ctx* ctx, const miphy_pusch_demod_layers_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
                                                    const float* ce, const float* scalars, int8_t* llr, void* stream)
 {
-  return pusch_demodulate("pusch_demodulate_layers", ctx, jobs, jobs_on_device, n, grid, ce, scalars, llr, nullptr, nullptr, false, stream);
+  return pusch_demodulate("pusch_demodulate_layers", ctx, jobs, jobs_on_device, n, grid, ce, scalars, nullptr, llr, nullptr, nullptr, false, stream);
+}
+
+extern "C" int miphy_pusch_demodulate_layers_mmse_batch_ex(miphy_ctx* ctx, const miphy_pusch_demod_mmse_job* jobs, int jobs_on_device, uint32_t n,
+                                                           const float* grid, const float* ce, const float* scalars, const float* cov, int8_t* llr,
+                                                           const uint16_t* placeholders, float* evm_sums, void* stream)
+{
+  return pusch_demodulate("pusch_demodulate_layers_mmse", ctx, jobs, jobs_on_device, n, grid, ce, scalars, cov, llr, placeholders, evm_sums, true, stream);
+}
+
+extern "C" int miphy_pusch_demodulate_layers_mmse_batch(miphy_ctx* ctx, const miphy_pusch_demod_mmse_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                                        const float* ce, const float* scalars, const float* cov, int8_t* llr, void* stream)
+{
+  return pusch_demodulate("pusch_demodulate_layers_mmse", ctx, jobs, jobs_on_device, n, grid, ce, scalars, cov, llr, nullptr, nullptr, false, stream);
 }

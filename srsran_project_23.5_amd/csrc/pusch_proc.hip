@@ -5,7 +5,8 @@
 // This is host-side composition of miphy_dmrs_pusch_estimate_batch, miphy_pusch_demodulate_batch and miphy_pusch_decode_batch
 // with the parameters the reference derives (DM-RS scaling from the SCH-to-DM-RS power ratio, codeword length from the allocation);
 // with multiplexed UCI, miphy_ulsch_demultiplex_batch between the last two. One codeword on 1..4 layers goes through the layered stages, a
-// transform-precoded PUSCH (DFT-s-OFDM) through miphy_dmrs_pusch_estimate_tp_batch and miphy_pusch_demodulate_tp_batch.
+// transform-precoded PUSCH (DFT-s-OFDM) through miphy_dmrs_pusch_estimate_tp_batch and miphy_pusch_demodulate_tp_batch, a layered PDU with MMSE-IRC
+// through the layered estimator, miphy_pusch_noise_covariance_batch and miphy_pusch_demodulate_layers_mmse_batch_ex.
 #include "miphy_ext.h"
 #include <cmath>
 #include <vector>
@@ -32,7 +33,8 @@ __global__ void zero_results_kernel(miphy_pusch_result* __restrict__ r, uint32_t
 // What the _ex processors enqueue for a batch, built once from the PDUs: the one-layer entry point (lpdus == NULL: every PDU on one layer, 20 scalars
 // per PDU, the one-layer rules) and the layered one (the layer count of each PDU, 80 scalars, the layered rules) differ in nothing else. The waveform:
 // with tpdus (transform precoding: one layer, 20 scalars) the estimator jobs carry the hopping mode (tcj) and the PDUs are held to the rules of the two
-// transform-precoded stages.
+// transform-precoded stages. With mpdus (MMSE-IRC: layered PDUs, their rules and scalars) there is a covariance job per PDU (nj) and the demodulator
+// jobs carry where its matrices are (mj).
 struct pusch_batch {
   std::vector<miphy_pusch_chest_job>        cj;
   std::vector<miphy_pusch_chest_tp_job>     tcj;      // transform precoding: cj with the hopping mode
@@ -42,17 +44,28 @@ struct pusch_batch {
   std::vector<uint16_t>                     ph;       // their repetition placeholders, back to back
   std::vector<uint32_t>                     nof_sym;  // data REs x layers per PDU (EVM)
   std::vector<uint32_t>                     tb_index; // PDU of every transport-block descriptor
-  size_t                                    ce_elems = 0, llr_bytes = 0, sch_bytes = 0;
+  std::vector<miphy_pusch_ncov_job>         nj;       // MMSE-IRC: cj with the PRG size, the loading and where the matrices go
+  std::vector<miphy_pusch_demod_mmse_job>   mj;       // MMSE-IRC: dj with the PRG size and where the matrices are
+  size_t                                    ce_elems = 0, llr_bytes = 0, sch_bytes = 0, cov_elems = 0;
 };
 
-int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus, const miphy_pusch_tp_pdu* tpdus, const miphy_pusch_uci* uci, uint32_t n,
-                      bool have_uci_out, pusch_batch& b)
+int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus_in, const miphy_pusch_tp_pdu* tpdus, const miphy_pusch_mmse_pdu* mpdus,
+                      const miphy_pusch_uci* uci, uint32_t n, bool have_uci_out, pusch_batch& b)
 {
   b.cj.resize(n), b.dj.resize(n), b.nof_sym.resize(n);
+  std::vector<miphy_pusch_layers_pdu> layered_of_mmse; // the layered PDU inside every MMSE PDU, in one array like lpdus_in
+  if (mpdus) {
+    layered_of_mmse.resize(n);
+    for (uint32_t i = 0; i < n; ++i)
+      layered_of_mmse[i] = mpdus[i].base;
+  }
+  const miphy_pusch_layers_pdu* lpdus = mpdus ? layered_of_mmse.data() : lpdus_in;
   const bool strict = lpdus || tpdus; // the entry points beyond the reference check what their stages would only find once the estimator is enqueued
   for (uint32_t i = 0; i < n; ++i) {
     const miphy_pusch_pdu& p = lpdus ? lpdus[i].base : (tpdus ? tpdus[i].base : pdus[i]);
     const unsigned         L = lpdus ? lpdus[i].nof_tx_layers : 1;
+    if (mpdus)
+      MIPHY_REQUIRE(mpdus[i].loading >= 0.f && mpdus[i].loading <= 3.402823466e+38f, "pusch_process: PDU %u: the diagonal loading should be finite and not negative", i);
     const miphy_pusch_uci* u = uci ? &uci[i] : nullptr;
     const bool has_uci = u && (u->nof_harq_ack_bits || u->nof_csi_part1_bits || u->nof_csi_part2_bits);
     const bool has_tb  = !u || u->has_codeword;
@@ -162,6 +175,23 @@ int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu*
       t.llr_offset = (t.llr_offset & ~((uint64_t)1 << 63)) + b.llr_bytes;
   for (auto& x : b.xj)
     x.sch_offset += b.llr_bytes;
+  if (mpdus) { // the covariance and demodulator jobs: the estimator's and the layered demodulator's with the PRG size; matrices back to back
+    b.nj.resize(n), b.mj.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      b.nj[i]            = {};
+      b.nj[i].base       = b.cj[i];
+      b.nj[i].cov_offset = b.cov_elems;
+      b.nj[i].loading    = mpdus[i].loading;
+      b.nj[i].prg_size   = mpdus[i].prg_size;
+      b.mj[i]            = {};
+      b.mj[i].base       = b.dj[i];
+      b.mj[i].cov_offset = b.cov_elems;
+      b.mj[i].prg_size   = mpdus[i].prg_size;
+      const uint32_t nprg = miphy_pusch_noise_covariance_nof_prg(&b.nj[i]);
+      MIPHY_REQUIRE(nprg > 0, "pusch_process: PDU %u: the noise covariance estimator refuses its job", i);
+      b.cov_elems += (size_t)nprg * b.cj[i].nof_rx_ports * b.cj[i].nof_rx_ports;
+    }
+  }
   if (tpdus) { // the rules of the transform-precoded stages on the allocation and the DM-RS (contiguous, 2^a 3^b 5^c PRBs, n_ID^RS, hopping mode)
     b.tcj.resize(n);
     for (uint32_t i = 0; i < n; ++i) {
@@ -177,12 +207,12 @@ int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu*
 
 // Estimator, demodulator with placeholders and EVM, EVM finish (divisor: data REs x layers), demultiplexer and decoder on one stream. Every rule is
 // checked before anything is enqueued (pusch_batch_build); the stages check their own rules again on the jobs built there.
-int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus, const miphy_pusch_tp_pdu* tpdus, const miphy_pusch_uci* uci,
-                     uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results,
-                     float* scalars_out, int8_t* uci_llr_out, float* evm_out, hipStream_t s)
+int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus, const miphy_pusch_tp_pdu* tpdus,
+                     const miphy_pusch_mmse_pdu* mpdus, const miphy_pusch_uci* uci, uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs,
+                     uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results, float* scalars_out, int8_t* uci_llr_out, float* evm_out, hipStream_t s)
 {
   pusch_batch b;
-  int         rc = pusch_batch_build(pdus, lpdus, tpdus, uci, n, uci_llr_out != nullptr, b);
+  int         rc = pusch_batch_build(pdus, lpdus, tpdus, mpdus, uci, n, uci_llr_out != nullptr, b);
   if (rc)
     return rc;
   // [placeholders | data REs || channel estimates cf_t | codeword LLRs, UL-SCH LLRs of the PDUs with UCI | EVM sums] in a workspace of the
@@ -193,6 +223,7 @@ int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pu
   const auto   s_ce  = img.reserve<float>(b.ce_elems * 2, 256);
   const auto   s_llr = img.reserve<int8_t>(b.llr_bytes + b.sch_bytes, 256);
   const auto   s_evm = img.reserve<float>(evm_out ? (size_t)n * 14 : 0);
+  const auto   s_cov = mpdus ? img.reserve<float>(b.cov_elems * 2, 256) : image_slot<float>{}; // (MMSE-IRC only: the covariance matrices of every PDU)
   void*        work  = nullptr;
   if ((rc = miphy_image_to_workspace(ctx, MIPHY_WS_PUSCH_PROC, img, s, &work)))
     return rc;
@@ -201,7 +232,15 @@ int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pu
   float*          d_evm = evm_out ? s_evm.at(work) : nullptr;
   const uint16_t* d_ph  = b.ph.empty() ? nullptr : s_ph.at(work);
   uint32_t*       d_nre = s_nre.at(work);
-  if (lpdus) {
+  if (mpdus) {
+    float* d_cov = s_cov.at(work);
+    if ((rc = miphy_dmrs_pusch_estimate_layers_batch(ctx, b.cj.data(), 0, n, grid, d_ce, scalars_out, s)))
+      return rc;
+    if ((rc = miphy_pusch_noise_covariance_batch(ctx, b.nj.data(), 0, n, grid, d_cov, s)))
+      return rc;
+    if ((rc = miphy_pusch_demodulate_layers_mmse_batch_ex(ctx, b.mj.data(), 0, n, grid, d_ce, scalars_out, d_cov, d_llr, d_ph, d_evm, s)))
+      return rc;
+  } else if (lpdus) {
     if ((rc = miphy_dmrs_pusch_estimate_layers_batch(ctx, b.cj.data(), 0, n, grid, d_ce, scalars_out, s)))
       return rc;
     if ((rc = miphy_pusch_demodulate_layers_batch_ex(ctx, b.dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, d_ph, d_evm, s)))
@@ -264,7 +303,7 @@ extern "C" int miphy_pusch_process_layers_batch_ex(miphy_ctx* ctx, const miphy_p
                 "miphy_pusch_process_layers_batch: null argument");
   if (n == 0)
     return MIPHY_OK;
-  return pusch_process_ex(ctx, nullptr, pdus, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+  return pusch_process_ex(ctx, nullptr, pdus, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
                           (hipStream_t)stream);
 }
 
@@ -284,7 +323,7 @@ extern "C" int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pd
                 "miphy_pusch_process_batch: null argument");
   if (n == 0)
     return MIPHY_OK;
-  return pusch_process_ex(ctx, pdus, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+  return pusch_process_ex(ctx, pdus, nullptr, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
                           (hipStream_t)stream);
 }
 
@@ -297,7 +336,7 @@ extern "C" int miphy_pusch_process_tp_batch_ex(miphy_ctx* ctx, const miphy_pusch
                 "miphy_pusch_process_tp_batch: null argument");
   if (n == 0)
     return MIPHY_OK;
-  return pusch_process_ex(ctx, nullptr, nullptr, pdus, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+  return pusch_process_ex(ctx, nullptr, nullptr, pdus, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
                           (hipStream_t)stream);
 }
 
@@ -307,4 +346,17 @@ extern "C" int miphy_pusch_process_tp_batch(miphy_ctx* ctx, const miphy_pusch_tp
 {
   return miphy_pusch_process_tp_batch_ex(ctx, pdus, nullptr, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, nullptr, nullptr,
                                          stream);
+}
+
+// One codeword on 1..4 layers through MMSE-IRC: the layered processor with the covariance estimator between its estimator and an MMSE demodulator.
+extern "C" int miphy_pusch_process_layers_mmse_batch(miphy_ctx* ctx, const miphy_pusch_mmse_pdu* pdus, const miphy_pusch_uci* uci, uint32_t n, const float* grid,
+                                                     int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
+                                                     miphy_pusch_result* results, float* scalars_out, int8_t* uci_llr_out, float* evm_out, void* stream)
+{
+  MIPHY_REQUIRE(ctx && pdus && grid && harq_softbits && harq_msgs && harq_crc_ok && tb_out && results && scalars_out,
+                "miphy_pusch_process_layers_mmse_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  return pusch_process_ex(ctx, nullptr, nullptr, nullptr, pdus, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out,
+                          evm_out, (hipStream_t)stream);
 }

@@ -157,6 +157,14 @@ def lib():
             l.miphy_dmrs_pusch_estimate_tp_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
             l.miphy_pusch_process_tp_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 8
             l.miphy_pusch_process_tp_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 10
+        if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_channel_equalize_mmse_batch"):  # (likewise)
+            l.miphy_pusch_noise_covariance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 3
+            l.miphy_pusch_noise_covariance_nof_prg.argtypes = [C.c_void_p]
+            l.miphy_pusch_noise_covariance_nof_prg.restype = C.c_uint32
+            l.miphy_channel_equalize_mmse_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 6
+            l.miphy_pusch_demodulate_layers_mmse_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 6
+            l.miphy_pusch_demodulate_layers_mmse_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 8
+            l.miphy_pusch_process_layers_mmse_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 10
         l.miphy_polar_block_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("miphy_ofdm_demodulate_symbols", "miphy_ofdm_modulate_symbols"):
             getattr(l, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -239,6 +247,18 @@ assert PuschChestJob.itemsize == 152, PuschChestJob.itemsize
 assert PuschChestJob.fields["rb_mask"][1] == 32 and PuschChestJob.fields["symbols_mask"][1] == 28
 
 
+# Mirrors miphy_pusch_ncov_job: the noise-plus-interference covariance of an allocation, one P x P matrix per PRG.
+PuschNcovJob = np.dtype([("base", PuschChestJob), ("cov_offset", np.uint64), ("loading", np.float32), ("prg_size", np.uint16), ("reserved", np.uint8, 2)],
+                        align=True)
+assert PuschNcovJob.itemsize == 168 and PuschNcovJob.fields["cov_offset"][1] == 152, PuschNcovJob.itemsize
+
+
+def pusch_noise_covariance_nof_prg(job):
+    """Matrices one PuschNcovJob record writes (host computation in the library); 0 for an invalid one."""
+    a = np.ascontiguousarray(np.asarray(job, dtype=PuschNcovJob).reshape(1))
+    return int(lib().miphy_pusch_noise_covariance_nof_prg(a.ctypes.data_as(C.c_void_p)))
+
+
 # Mirrors miphy_pusch_demod_job.
 PuschDemodJob = np.dtype([("rnti", np.uint32), ("n_id", np.uint32), ("mod", np.uint8), ("nof_rx_ports", np.uint8), ("start_symbol", np.uint8),
                           ("nof_symbols", np.uint8), ("dmrs_type", np.uint8), ("nof_cdm_groups_without_data", np.uint8),
@@ -264,6 +284,11 @@ def pusch_demod_layers_nof_llr(job):
     """Codeword length (data REs x layers x bits per symbol) of one PuschDemodLayersJob record; 0 for an invalid one."""
     a = np.ascontiguousarray(np.asarray(job, dtype=PuschDemodLayersJob).reshape(1))
     return int(lib().miphy_pusch_demod_layers_nof_llr(a.ctypes.data_as(C.c_void_p)))
+
+
+# Mirrors miphy_pusch_demod_mmse_job: a layered demodulator job and its covariance matrices.
+PuschDemodMmseJob = np.dtype([("base", PuschDemodLayersJob), ("cov_offset", np.uint64), ("prg_size", np.uint16), ("reserved", np.uint8, 6)], align=True)
+assert PuschDemodMmseJob.itemsize == 144 and PuschDemodMmseJob.fields["cov_offset"][1] == 128, PuschDemodMmseJob.itemsize
 
 
 # Transform precoding (DFT-s-OFDM). Mirrors miphy_transform_deprecode_job and miphy_pusch_chest_tp_job.
@@ -438,6 +463,11 @@ assert PuschPdu.itemsize == 112 and PuschPdu.fields["rb_mask"][1] == 56, PuschPd
 # Mirrors miphy_pusch_layers_pdu.
 PuschLayersPdu = np.dtype([("base", PuschPdu), ("nof_tx_layers", np.uint8), ("reserved", np.uint8, 7)], align=True)
 assert PuschLayersPdu.itemsize == 120 and PuschLayersPdu.fields["nof_tx_layers"][1] == 112, PuschLayersPdu.itemsize
+
+
+# Mirrors miphy_pusch_mmse_pdu: a layered PDU through MMSE-IRC.
+PuschMmsePdu = np.dtype([("base", PuschLayersPdu), ("loading", np.float32), ("prg_size", np.uint16), ("reserved", np.uint8, 2)], align=True)
+assert PuschMmsePdu.itemsize == 128 and PuschMmsePdu.fields["loading"][1] == 120, PuschMmsePdu.itemsize
 
 
 # Mirrors miphy_pusch_tp_pdu: a transform-precoded PUSCH.
@@ -708,6 +738,9 @@ EqualizerJob = np.dtype([("nof_re", np.uint32), ("nof_rx_ports", np.uint8), ("no
                          ("tx_scaling", np.float32), ("ch_symbols_offset", np.uint64), ("ch_estimates_offset", np.uint64), ("eq_symbols_offset", np.uint64),
                          ("eq_noise_vars_offset", np.uint64)], align=True)
 assert EqualizerJob.itemsize == 48, EqualizerJob.itemsize
+# Mirrors miphy_equalizer_mmse_job.
+EqualizerMmseJob = np.dtype([("base", EqualizerJob), ("cov_offset", np.uint64), ("re_per_cov", np.uint32), ("reserved", np.uint32)], align=True)
+assert EqualizerMmseJob.itemsize == 64 and EqualizerMmseJob.fields["cov_offset"][1] == 48, EqualizerMmseJob.itemsize
 
 # Mirrors miphy_crc_desc.
 CrcDesc = np.dtype([("bit_offset", np.uint64), ("nbits", np.uint32), ("poly", np.uint32)], align=True)
@@ -967,6 +1000,14 @@ class Context:
             on_dev |= (int(max_ports) << 8) | (int(max_layers) << 12)
         check(lib().miphy_dmrs_pusch_estimate_layers_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _stream_ptr(stream)))
 
+    def pusch_noise_covariance_batch(self, jobs, grid, cov, stream=None, max_ports=0, max_layers=0):
+        """Noise-plus-interference covariance per PRG from the DM-RS residuals (PuschNcovJob records; cov: device complex64); hints as
+        dmrs_pusch_estimate_batch."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschNcovJob)
+        if on_dev:
+            on_dev |= (int(max_ports) << 8) | (int(max_layers) << 12)
+        check(lib().miphy_pusch_noise_covariance_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(cov), _stream_ptr(stream)))
+
     def port_channel_estimate_batch(self, jobs, grid, pilots, ce, scalars, stream=None):
         """port_channel_estimator::compute: pilots given by the caller (device complex64), optional intra-slot hopping."""
         jobs, n, ptr, on_dev = self._descs(jobs, PuschChestJob)
@@ -1012,6 +1053,12 @@ class Context:
         check(lib().miphy_channel_equalize_layers_batch(self.h, ptr, on_dev, n, _dptr(ch_symbols), _dptr(ch_estimates), _dptr(eq_symbols),
                                                         _dptr(eq_noise_vars), _stream_ptr(stream)))
 
+    def channel_equalize_mmse_batch(self, jobs, ch_symbols, ch_estimates, cov, eq_symbols, eq_noise_vars, stream=None):
+        """MMSE-IRC of 1..4 layers on at least as many (at most 4) receive ports for a batch of EqualizerMmseJob records (cov: device complex64)."""
+        jobs, n, ptr, on_dev = self._descs(jobs, EqualizerMmseJob)
+        check(lib().miphy_channel_equalize_mmse_batch(self.h, ptr, on_dev, n, _dptr(ch_symbols), _dptr(ch_estimates), _dptr(cov), _dptr(eq_symbols),
+                                                      _dptr(eq_noise_vars), _stream_ptr(stream)))
+
     def pusch_demodulate_layers_batch(self, jobs, grid, ce, scalars, llr, stream=None):
         """PUSCH demodulator for one codeword on 1..4 transmit layers: a batch of PuschDemodLayersJob records."""
         jobs, n, ptr, on_dev = self._descs(jobs, PuschDemodLayersJob)
@@ -1024,6 +1071,20 @@ class Context:
         check(lib().miphy_pusch_demodulate_layers_batch_ex(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _dptr(llr),
                                                            _dptr(placeholders) if placeholders is not None else None,
                                                            _dptr(evm_sums) if evm_sums is not None else None, _stream_ptr(stream)))
+
+    def pusch_demodulate_layers_mmse_batch(self, jobs, grid, ce, cov, llr, scalars=None, stream=None):
+        """pusch_demodulate_layers_batch with MMSE-IRC in place of zero forcing: a batch of PuschDemodMmseJob records, cov: device complex64
+        [PRG][P][P] per job. The scalars are not read."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschDemodMmseJob)
+        check(lib().miphy_pusch_demodulate_layers_mmse_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars) if scalars is not None else None,
+                                                             _dptr(cov), _dptr(llr), _stream_ptr(stream)))
+
+    def pusch_demodulate_layers_mmse_batch_ex(self, jobs, grid, ce, cov, llr, placeholders=None, evm_sums=None, scalars=None, stream=None):
+        """pusch_demodulate_layers_mmse_batch with the placeholders and / or EVM sums of pusch_demodulate_layers_batch_ex."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschDemodMmseJob)
+        check(lib().miphy_pusch_demodulate_layers_mmse_batch_ex(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars) if scalars is not None else None,
+                                                                _dptr(cov), _dptr(llr), _dptr(placeholders) if placeholders is not None else None,
+                                                                _dptr(evm_sums) if evm_sums is not None else None, _stream_ptr(stream)))
 
     # ------------------------------------------------------------------ PUSCH with transform precoding (DFT-s-OFDM)
     def transform_deprecode_batch(self, jobs, eq_symbols, eq_noise_vars, out_symbols, out_noise_var, stream=None):
@@ -1109,6 +1170,21 @@ class Context:
         pdus = np.ascontiguousarray(pdus)
         check(lib().miphy_pusch_process_layers_batch(self.h, C.c_void_p(pdus.ctypes.data), pdus.size, _dptr(grid), _dptr(harq_softbits), _dptr(harq_msgs),
                                                      _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars), _stream_ptr(stream)))
+
+    def pusch_process_layers_mmse_batch(self, pdus, uci, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, uci_llr=None, evm=None, stream=None):
+        """pusch_process_layers_batch_ex with MMSE-IRC (host PuschMmsePdu records): the covariance estimator behind the layered estimator, the MMSE
+        demodulator in place of the zero-forcing one."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PuschMmsePdu
+        pdus = np.ascontiguousarray(pdus)
+        up = None
+        if uci is not None:
+            assert isinstance(uci, np.ndarray) and uci.dtype == PuschUci and uci.size == pdus.size
+            uci = np.ascontiguousarray(uci)
+            up = C.c_void_p(uci.ctypes.data)
+        check(lib().miphy_pusch_process_layers_mmse_batch(self.h, C.c_void_p(pdus.ctypes.data), up, pdus.size, _dptr(grid), _dptr(harq_softbits),
+                                                          _dptr(harq_msgs), _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars),
+                                                          _dptr(uci_llr) if uci_llr is not None else None, _dptr(evm) if evm is not None else None,
+                                                          _stream_ptr(stream)))
 
     def pusch_process_layers_batch_ex(self, pdus, uci, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, uci_llr, evm, stream=None):
         """pusch_process_layers_batch for PDUs with multiplexed UCI (uci: numpy PuschUci array or None) and the EVM (evm: float32 device tensor of n or
