@@ -1500,7 +1500,7 @@ int miphy_pucch_process_f0_batch(miphy_ctx* ctx, const miphy_pucch_f0_job* jobs,
 /* ------------------------------------------------------------------------------------------------------------------
  * SRS channel estimator (TS 38.211 6.4.1.4)  --  beyond the 23.5 reference, which has no SRS code. The contract is the standard, restated in numpy in
  * tests/srs_tx.py (transmitter) and tests/srs_ref.py (float64 receiver); the arithmetic is stated at the top of csrc/srs.hip. It measures what the
- * precoding entry points consume: one channel matrix per PRG (and the per-UE time alignment); the library still does not compute weights from it.
+ * precoding entry points consume: one channel matrix per PRG (and the per-UE time alignment); miphy_precoding_weights_batch computes the weights from it.
  * One job is the symbols of one SRS resource that lie on the same PRBs, in one slot. Decision: the job carries the resolved frequency position
  * (start_prb, nof_prb). The hopping pattern, C_SRS / B_SRS / n_shift / n_RRC and TS 38.211 Table 6.4.1.4.3-1 stay with the scheduler, and a
  * frequency-hopping resource is submitted as one job per hop. n jobs read one device grid through their windows as the PDUs of
@@ -1576,6 +1576,70 @@ int miphy_srs_info(const miphy_srs_job* job, miphy_srs_info_t* out);
 int miphy_srs_pilots_batch(miphy_ctx* ctx, const miphy_srs_job* jobs, int jobs_on_device, uint32_t n, float* pilots /* device cf_t */, void* stream);
 int miphy_srs_estimate_batch(miphy_ctx* ctx, const miphy_srs_job* jobs, int jobs_on_device, uint32_t n, const float* grid /* device cf_t */,
                              float* h_out /* device cf_t */, miphy_srs_result* results /* device, n */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Precoding weights from SRS channel matrices  --  beyond the 23.5 reference, which computes no precoding. The contract is restated in numpy in
+ * tests/precoding_weights_ref.py (float64, and float32 in the kernel's operation order); the arithmetic is stated at the top of
+ * csrc/precoding_weights.hip. It joins miphy_srs_estimate_batch to the precoding entry points without leaving the device.
+ * A job serves nof_ues = 1..4 co-scheduled UEs on A = nof_ports = 1..4 gNB antenna ports (the SRS jobs' nof_rx_ports). UE k: h_offset names the block
+ * H_k[g][a][u] as miphy_srs_estimate_batch wrote it for a sounding of nof_prb PRBs from start_prb (grid numbering) at prg_size 1, 2 or 4, with
+ * nof_ue_ports U_k = 1, 2 or 4 (the SRS job's nof_tx_ports); it is served nof_layers l_k = 1..U_k layers. L = sum l_k <= 4 and <= A.
+ * The output PRGs are those of miphy_precoding: PRG j covers the grid PRBs [j prg_size, (j + 1) prg_size), j < nof_prg. For every one of them:
+ *  1. R_k = (sum_i w_i conj(H_k[i]) H_k[i]^T) / sum_i w_i (A x A) over the SRS PRGs i whose PRBs meet PRG j, w_i = the PRBs they share; where none
+ *     does, the nearest sounded SRS PRG alone (the band edge). Gram matrices are averaged, never H: the estimate keeps the UE's delay as a phase ramp.
+ *  2. Eigen-decomposition of R_k by cyclic Jacobi: five sweeps over (p, q) = (0,1), (0,2), .. (A-2, A-1); a rotation is skipped when |R_pq|^2 is not a
+ *     positive normal number. Eigenvalues descending, on a tie the lower column first; a negative one (rounding) counts as 0.
+ *  3. Rows g_(k,i) = sqrt(lambda_(k,i)) v_(k,i)^H, i < l_k, stacked UE by UE into G (L x A).
+ *  4. W = G^H (G G^H + reg I)^-1 (regularised zero forcing; for one UE plain eigen-beamforming), every column scaled to 2-norm `amplitude`, then turned
+ *     so that its entry on antenna port 0 is real and not negative (left as it is where that entry is below 2^-10 of the norm).
+ *  5. Abnormal rule: if a pivot of the factorisation or the squared norm of a column is not a positive normal number (more layers than the channel has
+ *     rank at reg = 0; a zero matrix), every UE gets zero weights and zero sig / leak for that PRG. Nothing else is affected.
+ * UE k receives W[j][a][i] at weights[weights_offset + (j A + a) l_k + i] (cf_t): the memory order of miphy_precoding, so a PDSCH job of that UE with
+ * nof_ports = A and this prg_size / nof_prg points straight at it; and, where `metrics` is not NULL, three floats per PRG and layer at
+ * metrics[metrics_offset + 3 (j l_k + i)]: lambda, sig = |g w_own|^2 and leak = sum over the job's other columns of |g w_other|^2.
+ * Rules (miphy_precoding_weights_info, and therefore the batch call; MIPHY_EINVAL with the rule in miphy_last_error()): nof_ues 1..4; nof_ports 1..4;
+ * prg_size and nof_prg >= 1; reg finite and >= 0; amplitude a positive normal number; per UE prg_size 1, 2 or 4, nof_prb a multiple of 4 in 4..272 with
+ * start_prb + nof_prb <= 275, nof_ue_ports 1, 2 or 4, nof_layers 1..nof_ue_ports; L <= 4 and <= nof_ports; and, in the batch call,
+ * weights_offset + nof_prg A l_k <= nof_weights. Host jobs are all checked before anything is enqueued; a device-resident job that breaks a rule is
+ * skipped with nothing written. n == 0 enqueues nothing. The call only enqueues and allocates nothing, so with device jobs it can be captured in a HIP
+ * graph. A job's bits depend on the job alone: it takes the lane form (one lane per output PRG) when no output PRG meets more than 8 SRS PRGs of a
+ * UE, else the wave form (one wavefront per output PRG); miphy_precoding_weights_info reports which. */
+typedef struct {
+  uint64_t h_offset;       /* cf_t offset of H_k[0][0][0] in `h` */
+  uint32_t weights_offset; /* cf_t index of this UE's W[0][0][0] in `weights` */
+  uint32_t metrics_offset; /* float index of this UE's first metric in `metrics` */
+  uint16_t start_prb;      /* first PRB of the sounding, in grid numbering */
+  uint16_t nof_prb;        /* a multiple of 4 in 4..272 */
+  uint8_t  prg_size;       /* PRBs per SRS estimate: 1, 2 or 4 */
+  uint8_t  nof_ue_ports;   /* U: 1, 2 or 4 */
+  uint8_t  nof_layers;     /* 1..U */
+  uint8_t  reserved0;
+} miphy_precoding_weights_ue;
+
+typedef struct {
+  uint8_t  nof_ues;   /* 1..4 */
+  uint8_t  nof_ports; /* A: 1..4 */
+  uint16_t prg_size;  /* PRBs per output PRG, >= 1 (wideband: nof_prg = 1 and prg_size = the grid) */
+  uint16_t nof_prg;   /* >= 1 */
+  uint16_t reserved0;
+  float    reg;       /* >= 0, in units of |h|^2 */
+  float    amplitude; /* > 0: the 2-norm of every column */
+  miphy_precoding_weights_ue ue[4]; /* entries from nof_ues on are not read */
+} miphy_precoding_weights_job;
+
+typedef struct {
+  uint32_t nof_layers;     /* L */
+  uint32_t nof_weights[4]; /* cf_t per UE: nof_prg A l_k (unused entries 0) */
+  uint32_t nof_metrics[4]; /* floats per UE: 3 nof_prg l_k (unused entries 0) */
+  uint32_t max_srs_prg;    /* the largest number of SRS PRGs of one UE under one output PRG */
+  uint32_t wave_form;      /* 0: lane form, 1: wave form */
+} miphy_precoding_weights_info_t;
+
+/* Host function, no device. */
+int miphy_precoding_weights_info(const miphy_precoding_weights_job* job, miphy_precoding_weights_info_t* out);
+int miphy_precoding_weights_batch(miphy_ctx* ctx, const miphy_precoding_weights_job* jobs, int jobs_on_device, uint32_t n,
+                                  const float* h /* device cf_t */, float* weights /* device cf_t */, uint32_t nof_weights,
+                                  float* metrics /* device float, or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * PRACH detector and generator  --  replace srsran::prach_detector::detect and srsran::prach_generator::generate

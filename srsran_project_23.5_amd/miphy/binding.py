@@ -190,6 +190,9 @@ def lib():
         l.miphy_srs_info.argtypes = [C.c_void_p, C.c_void_p]
         l.miphy_srs_pilots_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 2
         l.miphy_srs_estimate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
+        if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_precoding_weights_batch"):  # (an older build named by MIPHY_LIBRARY for an A-B has neither)
+            l.miphy_precoding_weights_info.argtypes = [C.c_void_p, C.c_void_p]
+            l.miphy_precoding_weights_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         l.miphy_prach_detect_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 4
         l.miphy_prach_generate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 2
         l.miphy_prach_demod_info.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
@@ -575,6 +578,29 @@ def srs_info(job):
     j = np.ascontiguousarray(np.asarray(job, SrsJob).reshape(1))
     out = np.zeros(1, SrsInfo)
     check(lib().miphy_srs_info(C.c_void_p(j.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out[0]
+
+
+# miphy_precoding_weights_ue / miphy_precoding_weights_job / miphy_precoding_weights_info_t (include/miphy.h)
+PrecodingWeightsUe = np.dtype([("h_offset", np.uint64), ("weights_offset", np.uint32), ("metrics_offset", np.uint32), ("start_prb", np.uint16),
+                               ("nof_prb", np.uint16), ("prg_size", np.uint8), ("nof_ue_ports", np.uint8), ("nof_layers", np.uint8),
+                               ("reserved0", np.uint8)], align=True)
+assert PrecodingWeightsUe.itemsize == 24
+PrecodingWeightsJob = np.dtype([("nof_ues", np.uint8), ("nof_ports", np.uint8), ("prg_size", np.uint16), ("nof_prg", np.uint16), ("reserved0", np.uint16),
+                                ("reg", np.float32), ("amplitude", np.float32), ("ue", PrecodingWeightsUe, 4)], align=True)
+assert PrecodingWeightsJob.itemsize == 112
+PrecodingWeightsInfo = np.dtype([("nof_layers", np.uint32), ("nof_weights", np.uint32, 4), ("nof_metrics", np.uint32, 4), ("max_srs_prg", np.uint32),
+                                 ("wave_form", np.uint32)], align=True)
+assert PrecodingWeightsInfo.itemsize == 44
+
+
+def precoding_weights_info(job):
+    """What miphy_precoding_weights_batch derives from one PrecodingWeightsJob record (host function, no device): a PrecodingWeightsInfo record --
+    the layers of all UEs L, the cf_t and float counts of each UE's weights and metrics, the largest number of SRS PRGs of one UE under one
+    output PRG, and whether the job takes the wave form. Raises with the library's error code (-1 = MIPHY_EINVAL) and the rule in the message."""
+    j = np.ascontiguousarray(np.asarray(job, PrecodingWeightsJob).reshape(1))
+    out = np.zeros(1, PrecodingWeightsInfo)
+    check(lib().miphy_precoding_weights_info(C.c_void_p(j.ctypes.data), C.c_void_p(out.ctypes.data)))
     return out[0]
 # MIPHY_PRACH_FORMAT_*: PRACH_FORMATS.index("B4") is the format number of a PrachJob
 PRACH_FORMATS = ("0", "1", "2", "3", "A1", "A2", "A3", "B1", "B4", "C0", "C2", "A1/B1", "A2/B2", "A3/B3")
@@ -1336,6 +1362,28 @@ class Context:
             assert (i64["h_offset"] + size).max() <= h.numel(), "estimates outside `h`"
             assert (i64["grid_offset"] + i64["nof_rx_ports"] * 14 * 12 * i64["grid_nprb"]).max() <= grid.numel(), "grid windows outside `grid`"
         check(lib().miphy_srs_estimate_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(h), _dptr(results), _stream_ptr(stream)))
+
+    def precoding_weights_batch(self, jobs, h, weights, metrics=None, jobs_on_device=False, stream=None):
+        """Precoding weights from SRS channel matrices (jobs: numpy PrecodingWeightsJob array, or with jobs_on_device a uint8 device tensor holding
+        the same bytes): h the complex64 device tensor miphy_srs_estimate_batch wrote, weights a complex64 device tensor that receives
+        W[PRG][port][layer] of every UE from its weights_offset (the layout of miphy_precoding), metrics None or a float32 device tensor for
+        (lambda, sig, leak) per PRG and layer from each UE's metrics_offset. Only enqueues."""
+        import torch
+        assert jobs_on_device == (not isinstance(jobs, np.ndarray)), "host jobs are a numpy array, device jobs a uint8 tensor with jobs_on_device=True"
+        jobs, n, ptr, on_dev = self._descs(jobs, PrecodingWeightsJob)
+        assert h.dtype == torch.complex64 and weights.dtype == torch.complex64 and (metrics is None or metrics.dtype == torch.float32)
+        if not on_dev and n:  # the extents the kernels may touch lie inside the tensors (the library sees raw pointers, and the weights' extent)
+            for k in range(4):
+                used = jobs["nof_ues"] > k
+                if not used.any():
+                    continue
+                u = {f: jobs["ue"][f][used, k].astype(np.int64) for f in PrecodingWeightsUe.names}
+                ports, prgs = jobs["nof_ports"][used].astype(np.int64), jobs["nof_prg"][used].astype(np.int64)
+                size = u["nof_prb"] // np.maximum(u["prg_size"], 1) * ports * u["nof_ue_ports"]
+                assert (u["h_offset"] + size).max() <= h.numel(), "estimates outside `h`"
+                assert metrics is None or (u["metrics_offset"] + 3 * prgs * u["nof_layers"]).max() <= metrics.numel(), "metrics outside `metrics`"
+        check(lib().miphy_precoding_weights_batch(self.h, ptr, on_dev, n, _dptr(h), _dptr(weights), weights.numel(),
+                                                  None if metrics is None else _dptr(metrics), _stream_ptr(stream)))
 
     def prach_detect_batch(self, jobs, symbols, results, preambles, stream=None):
         """PRACH detector (jobs: numpy PrachJob array, or a uint8 device tensor holding the same bytes), one job per occasion: symbols
