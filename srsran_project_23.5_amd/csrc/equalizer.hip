@@ -12,12 +12,6 @@ namespace {
 
 constexpr int EQ_THREADS = 256, EQ_RE_PER_BLOCK = 1024;
 
-__device__ __forceinline__ bool is_normal(float x)
-{
-  const float a = fabsf(x);
-  return a >= 1.17549435e-38f && a < INFINITY; // std::isnormal: neither zero, subnormal, infinite nor NaN
-}
-
 __global__ __launch_bounds__(EQ_THREADS) void equalize_kernel(const miphy_equalizer_job* __restrict__ jobs, const float2* __restrict__ ch_symbols,
                                                               const float2* __restrict__ ch_estimates, float2* __restrict__ eq_symbols,
                                                               float* __restrict__ eq_noise_vars)
@@ -34,7 +28,7 @@ __global__ __launch_bounds__(EQ_THREADS) void equalize_kernel(const miphy_equali
   float2*        z  = eq_symbols + j.eq_symbols_offset;
   float*         nv = eq_noise_vars + j.eq_noise_vars_offset;
   const float    noise_var = j.noise_var, tx = j.tx_scaling;
-  const bool     nv_ok = is_normal(noise_var) && noise_var > 0.f;
+  const bool     nv_ok = zf_is_normal(noise_var) && noise_var > 0.f;
   if (j.nof_tx_layers == 1) {
     const int np = j.nof_rx_ports;
     for (uint32_t i = lo + threadIdx.x; i < hi; i += EQ_THREADS) {
@@ -51,7 +45,7 @@ __global__ __launch_bounds__(EQ_THREADS) void equalize_kernel(const miphy_equali
       const float d_pinv = tx * ch_mod_sq;
       float2      o      = make_float2(0.f, 0.f);
       float       v      = INFINITY;
-      if (is_normal(d_pinv) && nv_ok) {
+      if (zf_is_normal(d_pinv) && nv_ok) {
         const float rcp = 1.0f / d_pinv;
         o               = make_float2(acc_re * rcp, acc_im * rcp);
         v               = rcp * (noise_var / tx);
@@ -79,7 +73,7 @@ __global__ __launch_bounds__(EQ_THREADS) void equalize_kernel(const miphy_equali
     const float d_nvars = tx * d_pinv;
     float2      o0 = make_float2(0.f, 0.f), o1 = o0;
     float       v0 = INFINITY, v1 = INFINITY;
-    if (is_normal(d_pinv) && nv_ok) {
+    if (zf_is_normal(d_pinv) && nv_ok) {
       const float rp = 1.0f / d_pinv, rn = 1.0f / d_nvars;
       // (n1 m0 - xi m1) / d ; (n0 m1 - conj(xi) m0) / d
       o0 = make_float2((n1 * m0r - (xr * m1r - xi * m1i)) * rp, (n1 * m0i - (xr * m1i + xi * m1r)) * rp);

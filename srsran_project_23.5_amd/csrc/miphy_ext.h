@@ -1,6 +1,7 @@
 // Host-side caches hanging off a context: FFT twiddle tables, OFDM symbol plans, polar tables.
 #pragma once
 #include "miphy_internal.h"
+#include <cstddef>
 #include <map>
 #include <memory>
 #include <tuple>
@@ -56,7 +57,6 @@ struct miphy_ctx_ext {
   void*                                                         d_gold = nullptr; // Gold-sequence jump table (chest.hip)
   void*                                                         d_pi_il_max = nullptr; // polar interleaver pattern (polar.hip)
   const float**                                                 d_tp_twiddles = nullptr; // transform precoding: twiddle table of 12 N_PRB points at [N_PRB]
-  float*                                                        d_low_papr12  = nullptr; // ... and r_{u,0} of length 12, [u][12] cf_t (transform_precoding.hip)
 };
 
 // A device copy of `bytes` of host memory that lives as long as the context (freed by miphy_destroy): what the context's caches hold.
@@ -89,6 +89,43 @@ int miphy_tp_pilots_launch(miphy_ctx* ctx, const miphy_pusch_chest_tp_job* d_job
 // verdict of field i goes to status[status_index[i]] (status_index null: status[i]). `who` names the caller in the error messages.
 int miphy_uci_polar_decode_fields(const char* who, miphy_ctx* ctx, const miphy_uci_polar_job* jobs, uint32_t n, uint32_t list_size, const int8_t* llr,
                                   uint8_t* payload, uint8_t* status, const uint32_t* status_index, hipStream_t s);
+// The long-PDU path of the coherent PUCCH entry points (JOB = miphy_pucch_job in pucch.hip, miphy_pucch_f34_job in pucch_f34.hip), behind the
+// caller's own rule loop: `longs` names the polar-coded PDUs (above 11 bits) in job order with the (K, E) the rules derived. Builds their fields for
+// miphy_uci_polar_decode_fields with the byte offset of each status in the miphy_pucch_result array; with llr_out null, routes their soft bits through
+// MIPHY_WS_PUCCH_LLR, llr_stride bytes each, in a private copy of the jobs; stages the jobs. llr_long: the long PDUs' soft bits, null without any.
+struct miphy_pucch_long_pdu {
+  uint32_t job, K, E;
+};
+struct miphy_pucch_long_staged {
+  const void*                      d_jobs   = nullptr;
+  int8_t*                          llr_long = nullptr;
+  std::vector<miphy_uci_polar_job> fields;
+  std::vector<uint32_t>            status_at;
+};
+template <class JOB>
+int miphy_pucch_stage_long(miphy_ctx* ctx, const JOB* jobs, uint32_t n, const std::vector<miphy_pucch_long_pdu>& longs, size_t llr_stride, int8_t* llr_out,
+                           hipStream_t s, miphy_pucch_long_staged& out)
+{
+  for (const miphy_pucch_long_pdu& l : longs) {
+    miphy_uci_polar_job pj = {};
+    pj.nof_bits = (uint16_t)l.K, pj.nof_llr = l.E, pj.llr_offset = jobs[l.job].llr_offset, pj.payload_offset = jobs[l.job].payload_offset;
+    out.fields.push_back(pj);
+    out.status_at.push_back(l.job * (uint32_t)sizeof(miphy_pucch_result) + (uint32_t)offsetof(miphy_pucch_result, status));
+  }
+  out.llr_long = longs.empty() ? nullptr : llr_out;
+  std::vector<JOB> own;
+  if (!longs.empty() && !llr_out) {
+    void* w = nullptr;
+    if (const int rc = miphy_get_workspace(ctx, MIPHY_WS_PUCCH_LLR, llr_stride * longs.size(), &w))
+      return rc;
+    out.llr_long = (int8_t*)w;
+    own.assign(jobs, jobs + n);
+    for (size_t k = 0; k < longs.size(); ++k)
+      out.fields[k].llr_offset = own[longs[k].job].llr_offset = (uint64_t)llr_stride * k;
+    jobs = own.data();
+  }
+  return miphy_stage_descs(ctx, jobs, 0, sizeof(JOB) * (size_t)n, s, &out.d_jobs);
+}
 
 // Prepared PDSCH encode (sch.hip): segmentation and descriptor upload once; used by the PDSCH processor plan (pdsch_proc.hip).
 struct miphy_pdsch_encode_prepared;

@@ -18,6 +18,7 @@
 #include "fft_device.h"
 #include "miphy_ext.h"
 #include "prach_info.h"
+#include "wave_device.h"
 #define NR_PRACH_TABLE_ATTR __device__
 #include "tables/nr_prach_tables.h"
 #include <algorithm>
@@ -96,14 +97,6 @@ __device__ __forceinline__ float2 prach_sample(const prach_root& r, uint32_t L, 
   sincosf((PRACH_PI * (float)k) / (float)(2 * L), &s, &c);
   const float amp = sqrtf((float)L);
   return make_float2(amp * c, amp * s);
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1)
-    v += __shfl_xor(v, off);
-  return v;
 }
 
 __global__ void __launch_bounds__(PRACH_THREADS)

@@ -1,8 +1,11 @@
-// Device functions shared by the PUCCH kernels (pucch.hip: formats 1 and 2; pucch_f34.hip: formats 3 and 4): Gold-sequence words, the
-// wavefront sum, the time alignment of one hop and the final per-port quantities of port_channel_estimator_average_impl::compute.
+// Device functions shared by the PUCCH kernels and the SRS estimator. Included by pucch.hip (formats 1 and 2) and pucch_f34.hip (formats 3 and 4):
+// Gold-sequence words, the cyclic shift of a symbol, the time alignment of one hop, the final per-port quantities of
+// port_channel_estimator_average_impl::compute, their sum over the ports and the record written from it; by pucch_f0.hip (format 0) and srs.hip:
+// to_db and, through wave_device.h, the wavefront sum and the complex products.
 #pragma once
 #include "gold_device.h"
 #include "miphy_internal.h"
+#include "wave_device.h"
 
 namespace {
 
@@ -17,21 +20,11 @@ __device__ __forceinline__ uint32_t gold_word(const gold_tables& gt, uint32_t c_
   return (s1 ^ s2) | (((x1_step28(s1) ^ x2_step28(s2)) & 1u) << 31);
 }
 
-__device__ __forceinline__ float wave_sum(float v)
+// Cyclic-shift index of symbol l_abs of the slot (TS 38.211 6.3.2.2.2): alpha = (m0 + n_cs(n_s, l)) mod 12 in twelfths of a turn, n_cs = the eight
+// Gold bits c(8 (14 n_s + l) .. + 7) of c_init = n_id. Formats 1, 3 and 4; format 0 takes both of its symbols' n_cs in one wavefront jump.
+__device__ __forceinline__ int pucch_alpha(const gold_tables& gt, uint32_t n_id, uint32_t slot, uint32_t l_abs, uint32_t m0)
 {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1)
-    v += __shfl_xor(v, off);
-  return v;
-}
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b)
-{
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 cmulc(float2 a, float2 b) // a * conj(b)
-{
-  return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
+  return (int)((m0 + (gold_word(gt, n_id, 8u * (14u * slot + l_abs)) & 0xffu)) % 12u);
 }
 
 // Time alignment of one hop in IDFT taps (estimate_time_alignment, port_channel_estimator_average_impl.cpp:307-347): the first maximum
@@ -94,6 +87,25 @@ __device__ __forceinline__ port_csi finish_port(float epre, float rsrp, float no
 __device__ __forceinline__ float to_db(float v)
 {
   return 10.0f * log10f(v);
+}
+
+// The CSI of a coherent PDU: the per-port quantities added in port order (channel_estimation.h:211-233 averages them linearly) and the noise variance
+// of the first port, which the equaliser takes.
+struct pucch_csi_sum {
+  float epre = 0.f, rsrp = 0.f, snr = 0.f, ta = 0.f, noise0 = 0.f;
+
+  __device__ __forceinline__ void add(const port_csi& c, bool is_first_port)
+  {
+    epre += c.epre, rsrp += c.rsrp, snr += c.snr, ta += c.ta;
+    noise0 = is_first_port ? c.noise : noise0;
+  }
+};
+// The record of a PDU on nports ports, by one lane.
+__device__ __forceinline__ void pucch_write_result(miphy_pucch_result& r, const pucch_csi_sum& sum, int nports, uint8_t status, float detection_metric)
+{
+  const float np = (float)nports;
+  r.status = status, r.detection_metric = detection_metric, r.time_alignment_s = sum.ta / np;
+  r.epre_db = to_db(sum.epre / np), r.rsrp_db = to_db(sum.rsrp / np), r.sinr_db = to_db(sum.snr / np);
 }
 
 } // namespace

@@ -32,10 +32,9 @@
 // 5 pass + q and then shift k of it (D > 5: two passes); w(n) is exchanged inside the wavefront, the twiddles are twelve constants, the energies are
 // unhopped and added over the pairs through wavefront shuffles. Both symbols' n_cs are sixteen consecutive Gold bits: one jump, the x1 register on lanes
 // 0-31 and x2 on lanes 32-63 (gold_state_wave). No LDS, no barrier, no scratch.
-#include "gold_device.h"
+#include "low_papr_device.h"
 #include "miphy_ext.h"
 #include "pucch_device.h"
-#include "tables/nr_low_papr_tables.h"
 #include <cmath>
 #include <vector>
 
@@ -149,7 +148,8 @@ __global__ void __launch_bounds__(64 * F0_PDUS_PER_WG) pucch_f0_kernel(const mip
   const float2* g    = grid + j.grid_offset;
   const int     prb0 = j.bwp_start_rb + j.starting_prb, prb1 = j.bwp_start_rb + (j.intra_slot_hopping ? j.second_hop_prb : j.starting_prb);
 
-  // n_cs of the first symbol in bits 0..7 and of the second in bits 8..15: c(8 (14 n_s + l) ...) of c_init = n_id.
+  // n_cs of the first symbol in bits 0..7 and of the second in bits 8..15: c(8 (14 n_s + l) ...) of c_init = n_id, the rule of pucch_alpha
+  // (pucch_device.h) for both symbols in one wavefront jump.
   uint32_t ncs;
   {
     const uint32_t st = gold_state_wave(*gt, lane >= 32, j.n_id, 8u * (14u * j.slot + (uint32_t)s), lane & 31);
@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(64 * F0_PDUS_PER_WG) pucch_f0_kernel(const mip
   const int    q = lane / 12, k = lane - 12 * q; // lanes 60..63 (q = 5) hold nothing
   const int    base = q < 5 ? 12 * q : 0;
   const int    u = j.n_id % 30;
-  const float2 r = make_float2(NR_LOW_PAPR12[u][0][k][0], NR_LOW_PAPR12[u][0][k][1]);
+  const float2 r = low_papr12(u, k);
   float        E = 0.f; // lane k' < 12: E[k']
   for (int d0 = 0; d0 < D; d0 += 5) {
     const int    d = d0 + q, p = d / nsym, l = d - p * nsym;

@@ -5,11 +5,11 @@
 // The signal. DM-RS symbols by length (offsets from start_symbol, Table 6.4.1.3.3.2-1): 4: {1}, with hopping {0, 2}; 5: {0, 3}; 6, 7: {1, 4}; 8: {1, 5};
 // 9: {1, 6}; 10, 11: {2, 7}; 12: {2, 8}; 13: {2, 9}; 14: {3, 10}; with additional DM-RS 10: {1, 3, 6, 8}; 11: {1, 3, 6, 9}; 12: {1, 4, 7, 10};
 // 13: {1, 4, 7, 11}; 14: {1, 5, 8, 12}. With hopping the first floor(N / 2) symbols are on starting_prb, the others on second_hop_prb. DM-RS symbol l
-// (absolute) carries r(n) = e^(j alpha_l n) rbar_(u,0)(n), n < M = 12 nof_prb, u = n_id_hopping mod 30, alpha_l = 2 pi / 12 ((m0 + n_cs(n_s, l)) mod 12),
-// n_cs = the eight Gold bits of c_init = n_id_hopping from 8 (14 n_s + l) as for format 1; m0 = 0 (format 3), {0, 6}[occ_index] (format 4, two
-// sequences), {0, 6, 3, 9}[occ_index] (four). Data: E = Qm M (data symbols) bits for format 3, Qm (12 / N_SF) (data symbols) for format 4, scrambled
-// with c_init = rnti 2^15 + n_id_scrambling, QPSK or pi/2-BPSK (rotation by the parity of the symbol index); format 4 spreads the 12 / N_SF symbols of an
-// OFDM symbol to y(k) = w_n(k) d(k mod (12 / N_SF)), w_n(k) = g_n^floor(k N_SF / 12) with g = (1, -1) for two sequences and (1, -j, -1, +j) for four;
+// (absolute) carries r(n) = e^(j alpha_l n) rbar_(u,0)(n), n < M = 12 nof_prb, rbar the base sequence of low_papr_device.h, u = n_id_hopping mod 30,
+// alpha_l = 2 pi / 12 ((m0 + n_cs(n_s, l)) mod 12) as for format 1 (pucch_alpha of pucch_device.h, c_init = n_id_hopping); m0 = 0 (format 3),
+// {0, 6}[occ_index] (format 4, two sequences), {0, 6, 3, 9}[occ_index] (four). Data: E = Qm M (data symbols) bits for format 3, Qm (12 / N_SF) (data
+// symbols) for format 4, scrambled with c_init = rnti 2^15 + n_id_scrambling, QPSK or pi/2-BPSK (rotation by the parity of the symbol index); format 4
+// spreads the 12 / N_SF symbols of an OFDM symbol to y(k) = w_n(k) d(k mod (12 / N_SF)), w_n(k) = g_n^floor(k N_SF / 12) with g = (1, -1) for two sequences and (1, -j, -1, +j) for four;
 // every data symbol is transform precoded, z = DFT_M(y) / sqrt(M).
 //
 // The receiver, per receive port and hop (the arithmetic of port_channel_estimator_average_impl::compute with all 12 REs of a PRB as DM-RS: window 12,
@@ -42,13 +42,12 @@
 // most a workgroup per CU, so what a call costs is the latency of one PDU's chain (DESIGN.md section 5 has the measurement and what was tried on it).
 #include "demod_device.h"
 #include "equalize_device.h"
+#include "low_papr_device.h"
 #include "miphy_ext.h"
 #include "pucch_device.h"
-#include "tables/nr_low_papr_tables.h"
 #include "tp_device.h"
 #include "uci_device.h"
 #include "uci_polar_info.h"
-#include <cstddef>
 #include <vector>
 
 namespace {
@@ -215,9 +214,8 @@ __global__ void __launch_bounds__(TP_THREADS) pucch_f34_kernel(const miphy_pucch
     L.scr[tid] = gold_word(*gt, (uint32_t)j.rnti * 32768u + j.n_id_scrambling, 32u * (uint32_t)tid);
   if (tid >= F34_MAX_M && tid < F34_MAX_M + ndm_all) {
     const int      d  = tid - F34_MAX_M;
-    const uint32_t w  = gold_word(*gt, j.n_id_hopping, 8u * (14u * j.slot + (uint32_t)dm_l[d]));
     const uint32_t m0 = !f4 ? 0u : (occ == 2 ? 6u * j.occ_index : (uint32_t)((0x9360u >> (4 * j.occ_index)) & 0xfu)); // {0, 6, 3, 9}
-    L.alpha[d]        = (int)((m0 + (w & 0xffu)) % 12u);
+    L.alpha[d]        = pucch_alpha(*gt, j.n_id_hopping, j.slot, (uint32_t)dm_l[d], m0);
   }
   __syncthreads();
 
@@ -227,17 +225,10 @@ __global__ void __launch_bounds__(TP_THREADS) pucch_f34_kernel(const miphy_pucch
   {
     // rbar from the table's row of shift 0 (M = 12) or in closed form, then the shift as an exact twelfth of a turn: the table's rows of the other shifts
     // hold the reference's format-1 values, whose single-precision angles of up to 63 rad are off by up to 4e-6.
-    float2 rbar = make_float2(0.f, 0.f);
-    if (mine && M == 12)
-      rbar = make_float2(NR_LOW_PAPR12[u][0][k][0], NR_LOW_PAPR12[u][0][k][1]);
-    if (mine && M > 12) {
-      const unsigned nzc = tp_prime_below((unsigned)M), q = tp_zc_root((unsigned)u, 0, nzc);
-      unsigned       num, den;
-      tp_phase((unsigned)u, q, nzc, (unsigned)M, (unsigned)k, num, den);
-      float sn, cs;
-      sincospif((float)num / (float)den, &sn, &cs);
-      rbar = make_float2(cs, -sn);
-    }
+    const unsigned nzc  = low_papr_prime_below((unsigned)M);
+    float2         rbar = make_float2(0.f, 0.f);
+    if (mine)
+      rbar = low_papr_element((unsigned)u, low_papr_zc_root((unsigned)u, 0, nzc), nzc, (unsigned)M, (unsigned)k);
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
       pil[d] = make_float2(0.f, 0.f);
@@ -318,7 +309,8 @@ __global__ void __launch_bounds__(TP_THREADS) pucch_f34_kernel(const miphy_pucch
       L.ta[c] = ta;
   }
   __syncthreads();
-  float sum_epre = 0.f, sum_rsrp = 0.f, sum_snr = 0.f, sum_ta = 0.f, noise0 = 0.f, noise_mine = 0.f;
+  pucch_csi_sum csi;
+  float         noise_mine = 0.f;
   for (int p = 0; p < nports; ++p) {
     float epre = 0.f, rsrp = 0.f, noise = 0.f, ta = 0.f;
     for (int h = 0; h < nh; ++h) {
@@ -329,9 +321,7 @@ __global__ void __launch_bounds__(TP_THREADS) pucch_f34_kernel(const miphy_pucch
       ta += L.ta[p * nh + h];
     }
     const port_csi c = finish_port(epre, rsrp, noise, ta, M * ndm_all, 12, ndm_all, hop, j.numerology);
-    sum_epre += c.epre, sum_rsrp += c.rsrp, sum_snr += c.snr, sum_ta += c.ta;
-    if (p == 0)
-      noise0 = c.noise;
+    csi.add(c, p == 0);
     if (p == tid)
       noise_mine = c.noise;
   }
@@ -364,7 +354,7 @@ __global__ void __launch_bounds__(TP_THREADS) pucch_f34_kernel(const miphy_pucch
         y[p]     = p < nports ? g[((size_t)p * 14 + s + i) * nsc + 12 * prb[h] + k] : make_float2(0.f, 0.f);
       }
       zf_prepared<1> q;
-      zf_prepare<1>(hh, nports, noise0, 1.0f, q);
+      zf_prepare<1>(hh, nports, csi.noise0, 1.0f, q);
       zf_apply<1>(hh, nports, y, q, xo);
       tp_put(L.x, k, xo[0], q.nvar[0], acc);
     }
@@ -410,16 +400,8 @@ __global__ void __launch_bounds__(TP_THREADS) pucch_f34_kernel(const miphy_pucch
     uci_short_block_field(K, (uint32_t)lay.Qm, (uint32_t)lay.E, L.llr, payload + j.payload_offset, &L.status, (uint32_t)lane); // the verdict by lane 0, read by lane 0
     status = L.status;
   }
-  if (tid == 0) {
-    const float         np = (float)nports;
-    miphy_pucch_result& res = results[blockIdx.x];
-    res.status             = status;
-    res.detection_metric   = 0.f;
-    res.epre_db            = to_db(sum_epre / np);
-    res.rsrp_db            = to_db(sum_rsrp / np);
-    res.sinr_db            = to_db(sum_snr / np);
-    res.time_alignment_s   = sum_ta / np;
-  }
+  if (tid == 0)
+    pucch_write_result(results[blockIdx.x], csi, nports, status, 0.f);
 }
 
 } // namespace
@@ -448,52 +430,29 @@ extern "C" int miphy_pucch_process_f34_batch(miphy_ctx* ctx, const miphy_pucch_f
     return MIPHY_OK;
   MIPHY_REQUIRE(n <= (1u << 24), "%s: at most 2^24 PDUs per call", who);
   // Every job is checked before anything is enqueued; the PDUs above 11 bits become the polar decoder's fields, in job order.
-  std::vector<miphy_uci_polar_job> fields;
-  std::vector<uint32_t>            status_at, job_of; // byte offset of the field's status inside `results`; its job
+  std::vector<miphy_pucch_long_pdu> longs;
   for (uint32_t i = 0; i < n; ++i) {
     const miphy_pucch_f34_job& j = jobs[i];
     f34_layout                 lay;
     if (const int rc = f34_check(who, i, j, lay))
       return rc;
     const uint32_t K = (uint32_t)j.nof_harq_ack + j.nof_sr + j.nof_csi_part1;
-    if (K <= 11)
-      continue;
-    miphy_uci_polar_job pj = {};
-    pj.nof_bits = (uint16_t)K, pj.nof_llr = (uint32_t)lay.E, pj.llr_offset = j.llr_offset, pj.payload_offset = j.payload_offset;
-    fields.push_back(pj);
-    status_at.push_back(i * (uint32_t)sizeof(miphy_pucch_result) + (uint32_t)offsetof(miphy_pucch_result, status));
-    job_of.push_back(i);
+    if (K > 11)
+      longs.push_back({i, K, (uint32_t)lay.E});
   }
-  const gold_tables*  gt  = nullptr;
-  const float* const* tws = nullptr;
-  int                 rc;
-  if ((rc = miphy_get_gold_tables(ctx, &gt)) || (rc = miphy_tp_twiddles(ctx, &tws)))
+  hipStream_t             s   = (hipStream_t)stream;
+  const gold_tables*      gt  = nullptr;
+  const float* const*     tws = nullptr;
+  miphy_pucch_long_staged st;
+  int                     rc;
+  if ((rc = miphy_get_gold_tables(ctx, &gt)) || (rc = miphy_tp_twiddles(ctx, &tws)) || (rc = miphy_pucch_stage_long(ctx, jobs, n, longs, F34_MAX_LLR, llr_out, s, st)))
     return rc;
-  hipStream_t s = (hipStream_t)stream;
-  // Without llr_out the soft bits of the polar-coded PDUs go through the context's workspace, F34_MAX_LLR bytes each, and the staged copy of their jobs
-  // points there.
-  int8_t*                          llr_long = llr_out;
-  std::vector<miphy_pucch_f34_job> own;
-  if (!fields.empty() && !llr_out) {
-    void* w = nullptr;
-    if ((rc = miphy_get_workspace(ctx, MIPHY_WS_PUCCH_LLR, (size_t)F34_MAX_LLR * fields.size(), &w)))
-      return rc;
-    llr_long = (int8_t*)w;
-    own.assign(jobs, jobs + n);
-    for (size_t f = 0; f < fields.size(); ++f) {
-      fields[f].llr_offset      = (uint64_t)F34_MAX_LLR * f;
-      own[job_of[f]].llr_offset = (uint64_t)F34_MAX_LLR * f;
-    }
-    jobs = own.data();
-  }
-  const void* d_jobs = nullptr;
-  if ((rc = miphy_stage_descs(ctx, jobs, 0, sizeof(miphy_pucch_f34_job) * (size_t)n, s, &d_jobs)))
-    return rc;
-  hipLaunchKernelGGL(pucch_f34_kernel, dim3(n), dim3(TP_THREADS), 0, s, (const miphy_pucch_f34_job*)d_jobs, gt, tws, (const float2*)grid, payload, results, llr_out,
-                     fields.empty() ? (int8_t*)nullptr : llr_long, est_out);
+  hipLaunchKernelGGL(pucch_f34_kernel, dim3(n), dim3(TP_THREADS), 0, s, (const miphy_pucch_f34_job*)st.d_jobs, gt, tws, (const float2*)grid, payload, results, llr_out,
+                     st.llr_long, est_out);
   MIPHY_HIP_CHECK(hipGetLastError());
-  if (fields.empty())
+  if (st.fields.empty())
     return MIPHY_OK;
   // Behind the kernel on the same stream: the decoder's verdict lands on the status byte after the kernel wrote the record.
-  return miphy_uci_polar_decode_fields(who, ctx, fields.data(), (uint32_t)fields.size(), list_size, llr_long, payload, (uint8_t*)results, status_at.data(), s);
+  return miphy_uci_polar_decode_fields(who, ctx, st.fields.data(), (uint32_t)st.fields.size(), list_size, st.llr_long, payload, (uint8_t*)results,
+                                       st.status_at.data(), s);
 }

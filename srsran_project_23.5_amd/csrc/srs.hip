@@ -4,9 +4,9 @@
 //
 // The signal, normal cyclic prefix. n_cs_max = 8 (K = 2) or 12 (K = 4). Transmit port i: n_cs,i = (n_cs + n_cs_max i / N_ap) mod n_cs_max; its comb offset is
 // (kbar + K / 2) mod K when N_ap = 4, i is 1 or 3 and n_cs >= n_cs_max / 2, else kbar. M = 12 nof_prb / K. Element n of symbol l sits on subcarrier
-// 12 start_prb + offset_i + K n and carries r_(u,v)(n) e^(j 2 pi n_cs,i n / n_cs_max). u = (f_gh + n_id) mod 30; group hopping: f_gh = the eight Gold bits
-// of c_init = n_id from 8 (14 n_s + l), modulo 30; sequence hopping: v = c(14 n_s + l) where M >= 72; l is the symbol index in the slot. r of length 12 is
-// the table the PUCCH kernels hold, from 36 on Zadoff-Chu with the phases of tp_phase (reduced in 64-bit integers; N_ZC up to 1627).
+// 12 start_prb + offset_i + K n and carries r_(u,v)(n) e^(j 2 pi n_cs,i n / n_cs_max). (u, v) by the group and sequence hopping of low_papr_device.h
+// (low_papr_hop with c_init = n_id for the group; l is the symbol index in the slot); r is the base sequence of that header: the table at length 12, from
+// 36 on Zadoff-Chu with the phases of low_papr_phase (reduced in 64-bit integers; N_ZC up to 1627).
 //
 // The arithmetic. P = the ports that share a comb (N_ap, or 2 on each of two combs when four ports split), Q = 12 prg_size / K elements per PRG, a
 // multiple of P (a rule), G = nof_prb / prg_size. Per comb c in use, n_ref = the cyclic shift of its lowest port, d_i = (n_cs,i - n_ref) mod n_cs_max:
@@ -33,11 +33,9 @@
 // elements of the pair sit in two registers per lane (element e and e + 64, added in that order, then the xor tree), so H and then the residual come
 // from the same loads; the wavefront's sums over its pairs are kept in LDS in pair order, and lane 0 adds the four wavefronts in sequence. Every sum has
 // an order that depends on the job alone: a job's output is bit-identical whatever else is in the call. No atomics.
-#include "gold_device.h"
+#include "low_papr_device.h"
 #include "miphy_ext.h"
 #include "pucch_device.h"
-#include "tables/nr_low_papr_tables.h"
-#include "tp_device.h"
 #include <algorithm>
 #include <cmath>
 
@@ -155,24 +153,13 @@ __device__ __forceinline__ float2 srs_shift(uint32_t a, uint32_t n, uint32_t ncs
   const uint32_t m = srs_mod(a * n, ncs_max) * unit;
   return make_float2(SRS_TW[m][0], SRS_TW[m][1]);
 }
-__device__ __forceinline__ float2 conj2(float2 a)
-{
-  return make_float2(a.x, -a.y);
-}
 
 // Sequence group, sequence number and Zadoff-Chu root of symbol l_abs of the slot (one lane).
 __device__ __forceinline__ void srs_uvq(const gold_tables& gt, const miphy_srs_job& j, uint32_t M, uint32_t nzc, uint32_t l_abs, uint32_t& u, uint32_t& q)
 {
-  uint32_t f_gh = 0, v = 0;
-  if (j.hopping == 1) {
-    const uint32_t off = 8u * (14u * j.slot + l_abs);
-    f_gh               = ((gold_state(gt, false, 0, off) ^ gold_state(gt, true, j.n_id, off)) & 0xffu) % 30u;
-  } else if (j.hopping == 2 && M >= 72) {
-    const uint32_t off = 14u * j.slot + l_abs;
-    v                  = (gold_state(gt, false, 0, off) ^ gold_state(gt, true, j.n_id, off)) & 1u;
-  }
-  u = (f_gh + j.n_id) % 30u;
-  q = M >= 36 ? tp_zc_root(u, v, nzc) : 0u;
+  uint32_t v;
+  low_papr_hop(gt, j.hopping, j.n_id, j.n_id, j.slot, l_abs, M, u, v);
+  q = low_papr_zc_root(u, v, nzc);
 }
 
 // r_(u,v)(n) e^(j 2 pi a n / n_cs_max) with one angle: the base sequence's phase -pi num / den and the shift's 2 pi a n / n_cs_max over the common
@@ -180,9 +167,9 @@ __device__ __forceinline__ void srs_uvq(const gold_tables& gt, const miphy_srs_j
 __device__ __forceinline__ float2 srs_element(uint32_t M, uint32_t u, uint32_t q, uint32_t nzc, uint32_t n, uint32_t a, uint32_t ncs_max)
 {
   if (M == 12)
-    return cmulc(make_float2(NR_LOW_PAPR12[u][0][n][0], NR_LOW_PAPR12[u][0][n][1]), srs_shift(a, n, ncs_max, 24u / ncs_max));
+    return cmulc(low_papr12(u, n), srs_shift(a, n, ncs_max, 24u / ncs_max));
   unsigned num, den;
-  tp_phase(u, q, nzc, M, n, num, den);
+  low_papr_phase(u, q, nzc, M, n, num, den);
   const uint32_t full = 2u * den * ncs_max;
   const uint32_t t    = (2u * den * srs_mod(a * n, ncs_max) + full - num * ncs_max) % full; // the angle is pi t / (den n_cs_max)
   float          sn, cs;
@@ -201,7 +188,7 @@ __global__ void __launch_bounds__(SRS_THREADS) srs_pilots_kernel(const miphy_srs
   srs_derived d;
   miphy_srs_derive(j, d);
   if (threadIdx.x == 0) {
-    uq[2] = d.M >= 36 ? tp_prime_below(d.M) : 0u;
+    uq[2] = low_papr_prime_below(d.M);
     srs_uvq(*gt, j, d.M, uq[2], j.start_symbol + l, uq[0], uq[1]);
   }
   __syncthreads();
@@ -243,7 +230,7 @@ __global__ void __launch_bounds__(SRS_THREADS) srs_estimate_kernel(const miphy_s
 
   // ---- the sequences
   if (tid == 0)
-    s_nzc = M >= 36 ? tp_prime_below(M) : 0u;
+    s_nzc = low_papr_prime_below(M);
   for (uint32_t i = tid; i < 4 * (sizeof(srs_sums) / sizeof(float)); i += SRS_THREADS)
     reinterpret_cast<float*>(sums)[i] = 0.f;
   __syncthreads();
@@ -252,7 +239,7 @@ __global__ void __launch_bounds__(SRS_THREADS) srs_estimate_kernel(const miphy_s
   __syncthreads();
   for (uint32_t e = tid; e < ncopies * M; e += SRS_THREADS) {
     const uint32_t c = e / M, n = e - c * M;
-    seq[e]           = conj2(srs_element(M, uq[c][0], uq[c][1], s_nzc, n, 0, d.ncs_max));
+    seq[e]           = cconj(srs_element(M, uq[c][0], uq[c][1], s_nzc, n, 0, d.ncs_max));
   }
   __syncthreads();
 

@@ -114,41 +114,3 @@ __device__ __forceinline__ float2 tp_symbol(const cplx* x, int n, float scale)
   const cplx v = x[fpad(n)];
   return make_float2(v.x * scale, v.y * scale);
 }
-
-// ---- low-PAPR sequences of length 30 and 6 N >= 36 (TS 38.211 5.2.2.1), for transform_precoding.hip and pucch_f34.hip
-// Largest prime below len (36 <= len <= 1620).
-__host__ __device__ inline unsigned tp_prime_below(unsigned len)
-{
-  for (unsigned c = len - 1; c > 2; --c) {
-    bool prime = true;
-    for (unsigned d = 2; d * d <= c; ++d)
-      if (c % d == 0) {
-        prime = false;
-        break;
-      }
-    if (prime)
-      return c;
-  }
-  return 2;
-}
-// Root q of the Zadoff-Chu sequence of (u, v) with length N_ZC (TS 38.211 5.2.2.1): floor(qbar + 1/2) + v (-1)^floor(2 qbar), qbar = N_ZC (u+1) / 31.
-__host__ __device__ inline unsigned tp_zc_root(unsigned u, unsigned v, unsigned nzc)
-{
-  const unsigned t = 2 * nzc * (u + 1);
-  const int      q = (int)((t + 31) / 62) + (v ? (((t / 31) & 1u) ? -1 : 1) : 0);
-  return (unsigned)q;
-}
-// Phase of element n as a fraction f of pi, r(n) = exp(-j pi f), reduced to [0, 2) in integers: len = 30 or len >= 36.
-__host__ __device__ inline void tp_phase(unsigned u, unsigned q, unsigned nzc, unsigned len, unsigned n, unsigned& num, unsigned& den)
-{
-  if (len == 30) {
-    num = ((u + 1) * (n + 1) * (n + 2)) % 62u, den = 31u;
-    return;
-  }
-  const uint64_t m = n % nzc;
-  num = (unsigned)(((uint64_t)q * m * (m + 1)) % (2ull * nzc)), den = nzc;
-}
-__host__ __device__ inline bool tp_papr_length_ok(unsigned len)
-{
-  return len == 12 || len == 30 || (len >= 36 && len % 6 == 0 && len <= 6u * TP_MAX_PRB);
-}

@@ -1,11 +1,11 @@
 // PUSCH with transform precoding (DFT-s-OFDM, TS 38.211 6.3.1.4), the blocks of its own: the de-precoder (miphy_transform_deprecode_batch) and the
 // low-PAPR DM-RS (TS 38.211 5.2.2, 6.4.1.1.1.2: miphy_low_papr_sequence, miphy_dmrs_pusch_tp_pilots_batch). Beyond the 23.5 reference, which has no
 // transform precoding; the contract is TS 38.211 itself, restated in numpy in tests/pusch_tp_ref.py. The fused demodulator is in pusch_demod.hip, the
-// estimator entry point in chest.hip, the processor in pusch_proc.hip; the per-symbol function they share with this file is tp_device.h.
+// estimator entry point in chest.hip, the processor in pusch_proc.hip; the per-symbol function they share with this file is tp_device.h, the sequences
+// and their hopping low_papr_device.h.
 #include "tp_device.h"
-#include "gold_device.h"
+#include "low_papr_device.h"
 #include "miphy_ext.h"
-#include "tables/nr_low_papr_tables.h"
 #include <cmath>
 #include <vector>
 
@@ -137,8 +137,8 @@ constexpr int TP_MAX_DMRS = 4;
 // at i * stride + [DM-RS symbol][6 nprb] and that offset in the copy; a job that breaks a rule gets no receive port there, so the estimator's workgroups
 // leave at once. Without base_out the pilots go to the job's pilots_offset.
 __global__ void __launch_bounds__(TP_THREADS) tp_pilots_kernel(const miphy_pusch_chest_tp_job* __restrict__ jobs, const gold_tables* __restrict__ gt,
-                                                               const float2* __restrict__ papr12, float2* __restrict__ pilots,
-                                                               miphy_pusch_chest_job* __restrict__ base_out, uint32_t stride)
+                                                               float2* __restrict__ pilots, miphy_pusch_chest_job* __restrict__ base_out,
+                                                               uint32_t stride)
 {
   __shared__ uint32_t                     uv[2];
   const miphy_pusch_chest_tp_job&          jm  = jobs[blockIdx.x];
@@ -171,33 +171,14 @@ __global__ void __launch_bounds__(TP_THREADS) tp_pilots_kernel(const miphy_pusch
   if (l < 0) // uniform
     return;
   const unsigned len = 6 * nprb, n_id = b.scrambling_id;
-  if (tid == 0) {
-    unsigned f_gh = 0, v = 0;
-    if (jm.hopping == 1) {
-      const uint32_t off = 8u * (14u * b.slot_in_frame + (uint32_t)l);
-      f_gh               = ((gold_state(*gt, false, 0, off) ^ gold_state(*gt, true, n_id / 30u, off)) & 0xffu) % 30u;
-    } else if (jm.hopping == 2 && len >= 72) {
-      const uint32_t off = 14u * b.slot_in_frame + (uint32_t)l;
-      v                  = (gold_state(*gt, false, 0, off) ^ gold_state(*gt, true, n_id, off)) & 1u;
-    }
-    uv[0] = (f_gh + n_id) % 30u, uv[1] = v;
-  }
+  if (tid == 0)
+    low_papr_hop(*gt, jm.hopping, n_id / 30u, n_id, b.slot_in_frame, (uint32_t)l, len, uv[0], uv[1]);
   __syncthreads();
   const unsigned u = uv[0], v = uv[1];
   float2*        out = pilots + (base_out ? (size_t)blockIdx.x * stride : (size_t)b.pilots_offset) + (size_t)d * len;
-  if (len == 12) {
-    if (tid < 12)
-      out[tid] = papr12[u * 12 + tid];
-    return;
-  }
-  const unsigned nzc = len == 30 ? 31u : tp_prime_below(len), q = len == 30 ? 0u : tp_zc_root(u, v, nzc);
-  for (unsigned n = tid; n < len; n += TP_THREADS) {
-    unsigned num, den;
-    tp_phase(u, q, nzc, len, n, num, den);
-    float sn, cs;
-    sincospif((float)num / (float)den, &sn, &cs);
-    out[n] = make_float2(cs, -sn);
-  }
+  const unsigned nzc = low_papr_prime_below(len), q = low_papr_zc_root(u, v, nzc);
+  for (unsigned n = tid; n < len; n += TP_THREADS)
+    out[n] = low_papr_element(u, q, nzc, len, n);
 }
 
 } // namespace
@@ -209,19 +190,12 @@ extern "C" int miphy_low_papr_sequence(uint32_t u, uint32_t v, uint32_t length, 
     miphy_set_error("miphy_low_papr_sequence: length %u needs TS 38.211 Tables 5.2.2.2-1, -3, -4, which the library does not hold", length);
     return MIPHY_EUNSUPP;
   }
-  MIPHY_REQUIRE(tp_papr_length_ok(length), "miphy_low_papr_sequence: invalid length %u", length);
+  MIPHY_REQUIRE(low_papr_length_ok(length), "miphy_low_papr_sequence: invalid length %u", length);
   MIPHY_REQUIRE(u < 30 && v < 2, "miphy_low_papr_sequence: invalid sequence (u = %u, v = %u)", u, v);
-  if (length == 12) {
-    for (unsigned n = 0; n < 12; ++n)
-      out[2 * n] = NR_LOW_PAPR12[u][0][n][0], out[2 * n + 1] = NR_LOW_PAPR12[u][0][n][1];
-    return MIPHY_OK;
-  }
-  const unsigned nzc = length == 30 ? 31u : tp_prime_below(length), q = length == 30 ? 0u : tp_zc_root(u, v, nzc);
+  const unsigned nzc = low_papr_prime_below(length), q = low_papr_zc_root(u, v, nzc);
   for (unsigned n = 0; n < length; ++n) {
-    unsigned num, den;
-    tp_phase(u, q, nzc, length, n, num, den);
-    const double a = M_PI * (double)num / (double)den;
-    out[2 * n] = (float)std::cos(a), out[2 * n + 1] = (float)-std::sin(a);
+    const float2 r = low_papr_element_host(u, q, nzc, length, n);
+    out[2 * n] = r.x, out[2 * n + 1] = r.y;
   }
   return MIPHY_OK;
 }
@@ -252,21 +226,9 @@ int miphy_tp_pilots_launch(miphy_ctx* ctx, const miphy_pusch_chest_tp_job* d_job
                            hipStream_t s)
 {
   const gold_tables* gt = nullptr;
-  int                rc = miphy_get_gold_tables(ctx, &gt);
-  if (rc)
+  if (const int rc = miphy_get_gold_tables(ctx, &gt))
     return rc;
-  if (!ctx->ext->d_low_papr12) {
-    std::vector<float> h(30 * 12 * 2);
-    for (unsigned u = 0; u < 30; ++u)
-      for (unsigned k = 0; k < 12; ++k)
-        h[2 * (u * 12 + k)] = NR_LOW_PAPR12[u][0][k][0], h[2 * (u * 12 + k) + 1] = NR_LOW_PAPR12[u][0][k][1];
-    float* d = nullptr;
-    if ((rc = miphy_keep_device_copy(ctx, h.data(), h.size(), &d)))
-      return rc;
-    ctx->ext->d_low_papr12 = d;
-  }
-  hipLaunchKernelGGL(tp_pilots_kernel, dim3(n, TP_MAX_DMRS), dim3(TP_THREADS), 0, s, d_jobs, gt, (const float2*)ctx->ext->d_low_papr12, (float2*)pilots, base_out,
-                     stride);
+  hipLaunchKernelGGL(tp_pilots_kernel, dim3(n, TP_MAX_DMRS), dim3(TP_THREADS), 0, s, d_jobs, gt, (float2*)pilots, base_out, stride);
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
 }
