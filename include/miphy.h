@@ -376,6 +376,41 @@ int miphy_dmrs_pusch_estimate_layers_batch(miphy_ctx* ctx, const miphy_pusch_che
                                            const float* grid /* device cf_t */, float* ce /* device cf_t */, float* scalars /* device */,
                                            void* stream);
 
+/* The layered estimator with carrier frequency offset (CFO) estimation and compensation  --  beyond the 23.5 reference, whose estimator
+ * averages the DM-RS symbols and copies one estimate to every OFDM symbol. A residual offset of the UE's oscillator (or a line-of-sight Doppler
+ * shift) f rotates OFDM symbol l by the common phase 2 pi f tau_l; the average then fits no symbol but one and shrinks. Here the offset is
+ * estimated from the DM-RS symbols of the job, the fit of the layered estimator is run on derotated DM-RS, and the estimate is written per symbol,
+ * rotated back. The model is a common phase per OFDM symbol: inter-carrier interference inside a symbol is ignored.
+ *   symbol times: tau_l = start of the useful part of OFDM symbol l in the slot, normal cyclic prefix: symbol j lasts 2048 + 144 samples at
+ *     2048 * 2^mu * 15 kHz, and 16 * 2^mu samples more where (14 slot_in_frame + j) mod (7 * 2^mu) = 0 (the rule of miphy_ofdm_symbol_size). Only
+ *     differences of tau enter. Extended CP cannot be expressed by the job.
+ *   per-symbol fits, per (rx port p, CDM group g, DM-RS symbol d): z_d[i] = x_d[i] conj(r_d[i]) / beta over the pilots of the allocated PRBs;
+ *     both layers of the group present: s_{a,d}[m] = (z_d[2m] + z_d[2m+1]) / 2, s_{b,d}[m] = (z_d[2m] - z_d[2m+1]) / 2; a layer alone: s_d = z_d
+ *   correlation, per pair of consecutive DM-RS symbols (d, d+1) of the allocation, all ports and layers in one sum (a UE has one oscillator):
+ *     C_d = sum_p sum_layers sum_m s_{l,d+1}[m] conj(s_{l,d}[m]),   E_d = sum_p sum_layers sqrt(sum_m |s_{l,d+1}|^2 sum_m |s_{l,d}|^2)
+ *     added in the fixed order (port, layer, gap) ascending, without atomics: a job gives the same bits whatever else is in the batch
+ *   offset, dt_d = tau_{d+1} - tau_d:  cfo_hz = sum_d |C_d| arg(C_d) / (2 pi dt_d) / sum_d |C_d|,   rho = sum_d |C_d| / sum_d E_d  (0 <= rho <= 1:
+ *     how much of the DM-RS energy the common rotation explains); one DM-RS symbol, or sum |C_d| = 0: cfo_hz = 0, rho = 0.
+ *     Unambiguous for |f| < 1 / (2 max dt_d): +-1.56 kHz for DM-RS on symbols 2 and 11 at 30 kHz, +-7 kHz for neighbouring DM-RS symbols at 15 kHz.
+ *   estimate: phi_l = 2 pi cfo_hz (tau_l - tau_ref), tau_ref = the first DM-RS symbol of the allocation. The arithmetic of
+ *     miphy_dmrs_pusch_estimate_layers_batch (least squares, despreading, interpolation, EPRE, RSRP, noise residual, SNR, time alignment; a job on
+ *     one layer follows the rule of a layer alone in its group; noise_var = 0.001 epre below three DM-RS symbols) on x_d exp(-j phi_d) gives H[k]
+ *     and the scalars; H_l[k] = H[k] exp(+j phi_l) is written to every symbol l of the allocation. The scalars are those of the derotated fit: the
+ *     noise variance does not contain the energy of the rotation.
+ * base.ce_compact must be 0 (the estimate differs from symbol to symbol); base.nof_tx_layers 1..4; otherwise the rules, hints
+ * (MIPHY_JOBS_ON_DEVICE_HINT) and output layouts of miphy_dmrs_pusch_estimate_layers_batch. A host job that breaks a rule (ce_compact != 0 and
+ * hopping included) is MIPHY_EINVAL with nothing enqueued; a device-resident one is skipped. Two launches on the stream: the correlation partials
+ * of every (job, port, layer, gap) go to a workspace of the context, the estimate kernel adds them up.
+ * Out: time interpolation of the channel magnitude between DM-RS symbols, offsets beyond the unambiguous range, extended CP, MMSE-IRC and
+ * transform-precoded variants, prepared plans. */
+typedef struct {
+  miphy_pusch_chest_job base;   /* ce_compact must be 0; nof_tx_layers 1..4; the rules of the layered estimator otherwise */
+  uint64_t cfo_offset;          /* float offset: {cfo_hz, rho} of the job */
+} miphy_pusch_chest_cfo_job;
+int miphy_dmrs_pusch_estimate_cfo_batch(miphy_ctx* ctx, const miphy_pusch_chest_cfo_job* jobs, int jobs_on_device, uint32_t n,
+                                        const float* grid /* device cf_t */, float* ce /* device cf_t */, float* scalars /* device */,
+                                        float* cfo /* device */, void* stream);
+
 /* Noise-plus-interference covariance across the receive ports, from the DM-RS residuals of the estimator above  --  beyond the 23.5 reference,
  * which has no MMSE equaliser to feed ("MMSE equalizer is not implemented yet"). Reads the grid only. With e[g][p][d][i] the residual whose
  * energy the estimator turns into noise_var (g the CDM group, p the receive port, d the DM-RS symbol, i the pilot of the allocated PRBs):
@@ -1099,6 +1134,17 @@ int miphy_pusch_process_layers_batch_ex(miphy_ctx* ctx, const miphy_pusch_layers
                                         uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
                                         miphy_pusch_result* results, float* scalars_out /* n x 80 */, int8_t* uci_llr_out,
                                         float* evm_out /* device, n, may be NULL */, void* stream);
+
+/* The layered processor for a UE with a carrier frequency offset  --  beyond the reference. miphy_pusch_process_layers_batch_ex with
+ * miphy_dmrs_pusch_estimate_cfo_batch in front: the estimate is kept per OFDM symbol in the workspace of the context ([layer][port]
+ * [start_symbol + nof_symbols][grid_nof_prb * 12] per PDU, up to fourteen times the compact one) and the demodulator jobs read it with
+ * ce_compact = 0; every other stage is unchanged. Transport blocks, results, scalars, UCI soft bits and EVM are the bytes of the stages called
+ * one by one. cfo_out: per PDU {cfo_hz, rho}. Rules and refusals: those of the layered processor; a PDU that breaks one is MIPHY_EINVAL with
+ * nothing enqueued. Out: MMSE-IRC and transform precoding with an offset, the slot batch of the uplink processor, a prepared plan. */
+int miphy_pusch_process_layers_cfo_batch(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus /* host */, const miphy_pusch_uci* uci /* host or NULL */,
+                                         uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
+                                         miphy_pusch_result* results, float* scalars_out /* n x 80 */, int8_t* uci_llr_out,
+                                         float* evm_out /* device, n, may be NULL */, float* cfo_out /* device, n x 2 */, void* stream);
 
 /* The layered processor with MMSE-IRC  --  beyond the reference. The arguments of miphy_pusch_process_layers_batch_ex; one call chains, on one
  * stream, miphy_dmrs_pusch_estimate_layers_batch (compact estimate), miphy_pusch_noise_covariance_batch (the PDU's prg_size and loading; the

@@ -815,11 +815,19 @@ private:
 // ---------------------------------------------------------------------------------------------------------------- estimator
 /// srsran::dmrs_pusch_estimator over miphy_dmrs_pusch_estimate_batch (dmrs_pusch_estimator.h:84). \c separate_layers: through
 /// miphy_dmrs_pusch_estimate_layers_batch, which separates the layers that share a CDM group (beyond the reference, whose estimate of such a
-/// layer holds the other one too); the default is the reference's arithmetic.
+/// layer holds the other one too); the default is the reference's arithmetic. \c compensate_cfo: through miphy_dmrs_pusch_estimate_cfo_batch,
+/// which separates the layers too, estimates the carrier frequency offset from the DM-RS symbols and writes an estimate that differs from symbol to
+/// symbol into the reference's channel_estimate; 23.5 has no field for the offset, so the last {cfo_hz, rho} are kept for last_cfo_hz() / last_cfo_rho().
 class dmrs_pusch_estimator_hip : public srsran::dmrs_pusch_estimator
 {
 public:
-  explicit dmrs_pusch_estimator_hip(std::shared_ptr<context> c, bool separate_layers = false) : c(std::move(c)), separate_layers(separate_layers) {}
+  explicit dmrs_pusch_estimator_hip(std::shared_ptr<context> c, bool separate_layers = false, bool compensate_cfo = false) :
+    c(std::move(c)), separate_layers(separate_layers), compensate_cfo(compensate_cfo)
+  {
+  }
+  /// The offset in Hz and the normalised correlation of the last estimate() with \c compensate_cfo (0 before the first one).
+  float last_cfo_hz() const { return cfo[0]; }
+  float last_cfo_rho() const { return cfo[1]; }
   void estimate(srsran::channel_estimate& estimate, const srsran::resource_grid_reader& grid, const configuration& config) override
   {
     srsran_assert(config.type == srsran::dmrs_type::TYPE1, "Only DM-RS type 1 is supported.");
@@ -868,8 +876,16 @@ public:
       }
     }
     c->h2d(d_ce, ce_host.data(), ce_n * sizeof(srsran::cf_t));
-    context::check((separate_layers ? miphy_dmrs_pusch_estimate_layers_batch : miphy_dmrs_pusch_estimate_batch)(c->ctx, &j, 0, 1, d_g, d_ce, d_sc, c->stream),
-                   "dmrs_pusch_estimate");
+    if (compensate_cfo) {
+      miphy_pusch_chest_cfo_job fj = {};
+      fj.base                      = j;
+      auto* d_cfo                  = static_cast<float*>(c->buf(3, 2 * sizeof(float)));
+      context::check(miphy_dmrs_pusch_estimate_cfo_batch(c->ctx, &fj, 0, 1, d_g, d_ce, d_sc, d_cfo, c->stream), "dmrs_pusch_estimate_cfo");
+      c->d2h(cfo, d_cfo, sizeof(cfo));
+    } else {
+      context::check((separate_layers ? miphy_dmrs_pusch_estimate_layers_batch : miphy_dmrs_pusch_estimate_batch)(c->ctx, &j, 0, 1, d_g, d_ce, d_sc, c->stream),
+                     "dmrs_pusch_estimate");
+    }
     std::vector<float> sc(nports * nl * 5);
     c->d2h(ce_host.data(), d_ce, ce_n * sizeof(srsran::cf_t));
     c->d2h(sc.data(), d_sc, sc.size() * sizeof(float));
@@ -892,7 +908,8 @@ public:
 
 private:
   std::shared_ptr<context>  c;
-  bool                      separate_layers;
+  bool                      separate_layers, compensate_cfo;
+  float                     cfo[2] = {0.F, 0.F};
   std::vector<srsran::cf_t> host, ce_host;
 };
 
@@ -3759,16 +3776,19 @@ MIPHY_SIMPLE_FACTORY(ldpc_rate_matcher_factory_hip, ldpc_rate_matcher_factory, l
 MIPHY_SIMPLE_FACTORY(ldpc_rate_dematcher_factory_hip, ldpc_rate_dematcher_factory, ldpc_rate_dematcher, ldpc_rate_dematcher_hip)
 MIPHY_SIMPLE_FACTORY(pdsch_encoder_factory_hip, pdsch_encoder_factory, pdsch_encoder, pdsch_encoder_hip)
 MIPHY_SIMPLE_FACTORY(pusch_decoder_factory_hip, pusch_decoder_factory, pusch_decoder, pusch_decoder_hip)
-/// \c separate_layers as in dmrs_pusch_estimator_hip.
+/// \c separate_layers and \c compensate_cfo as in dmrs_pusch_estimator_hip.
 class dmrs_pusch_estimator_factory_hip : public srsran::dmrs_pusch_estimator_factory
 {
 public:
-  explicit dmrs_pusch_estimator_factory_hip(std::shared_ptr<context> c, bool separate_layers = false) : c(std::move(c)), separate_layers(separate_layers) {}
-  std::unique_ptr<srsran::dmrs_pusch_estimator> create() override { return std::make_unique<dmrs_pusch_estimator_hip>(c, separate_layers); }
+  explicit dmrs_pusch_estimator_factory_hip(std::shared_ptr<context> c, bool separate_layers = false, bool compensate_cfo = false) :
+    c(std::move(c)), separate_layers(separate_layers), compensate_cfo(compensate_cfo)
+  {
+  }
+  std::unique_ptr<srsran::dmrs_pusch_estimator> create() override { return std::make_unique<dmrs_pusch_estimator_hip>(c, separate_layers, compensate_cfo); }
 
 private:
   std::shared_ptr<context> c;
-  bool                     separate_layers;
+  bool                     separate_layers, compensate_cfo;
 };
 MIPHY_SIMPLE_FACTORY(pdcch_encoder_factory_hip, pdcch_encoder_factory, pdcch_encoder, pdcch_encoder_hip)
 MIPHY_SIMPLE_FACTORY(pusch_demodulator_factory_hip, pusch_demodulator_factory, pusch_demodulator, pusch_demodulator_hip)
@@ -3815,9 +3835,10 @@ inline std::shared_ptr<srsran::pusch_decoder_factory> create_pusch_decoder_facto
 {
   return std::make_shared<pusch_decoder_factory_hip>(std::move(c));
 }
-inline std::shared_ptr<srsran::dmrs_pusch_estimator_factory> create_dmrs_pusch_estimator_factory_hip(std::shared_ptr<context> c, bool separate_layers = false)
+inline std::shared_ptr<srsran::dmrs_pusch_estimator_factory> create_dmrs_pusch_estimator_factory_hip(std::shared_ptr<context> c, bool separate_layers = false,
+                                                                                                     bool compensate_cfo = false)
 {
-  return std::make_shared<dmrs_pusch_estimator_factory_hip>(std::move(c), separate_layers);
+  return std::make_shared<dmrs_pusch_estimator_factory_hip>(std::move(c), separate_layers, compensate_cfo);
 }
 inline std::shared_ptr<srsran::pdcch_encoder_factory> create_pdcch_encoder_factory_hip(std::shared_ptr<context> c)
 {

@@ -12,6 +12,9 @@
 //   chest_layers_kernel  workgroup per (job, rx port, CDM group), the group's layers separated: jobs on two to four layers of the layered entry.
 // A third kernel, ncov_kernel (wavefront per (job, PRG)), forms the same DM-RS residuals again and turns them into the noise-plus-interference
 // covariance across the ports: miphy_pusch_noise_covariance_batch. It takes the helpers and the job rules from here and writes no estimate.
+// Behind them, cfo_corr_kernel and chest_cfo_kernel (workgroup per (job, rx port, CDM group), two launches): chest_layers_kernel for 1..4 layers with a
+// carrier frequency offset estimated from consecutive DM-RS symbols, taken out of the DM-RS elements and put back per OFDM symbol:
+// miphy_dmrs_pusch_estimate_cfo_batch.
 // What they share stands once, in front of them: the thread count, the LDS layout (chest_lds, which also sizes the launches), the job rules
 // (chest_job_rule: chest_validate on the host, device-resident jobs of the layered entry on the device) and the chest_* helpers. What differs
 // stays in the kernels: pilot ownership, despreading, the two-parameter noise fit, external pilots, hopping. Behind the kernels: chest_prologue
@@ -819,29 +822,370 @@ __global__ void __launch_bounds__(CHEST_THREADS) ncov_kernel(const miphy_pusch_n
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Carrier frequency offset (miphy_dmrs_pusch_estimate_cfo_batch; include/miphy.h has the arithmetic). The offset of a job is a sum over the
+// workgroups of (job, port, CDM group), so there are two launches and no atomics: cfo_corr_kernel leaves, per (job, port, layer, gap between
+// consecutive DM-RS symbols), the correlation of the per-symbol fits and the root of the product of their energies in a workspace;
+// chest_cfo_kernel -- every workgroup of the job, in the same fixed order, so all get the same bits -- adds them up to cfo_hz and rho, turns the
+// offset into one phasor per OFDM symbol and then follows chest_layers_kernel on derotated DM-RS elements, storing every symbol rotated back.
+constexpr int CFO_PART_FLOATS = 4;                       // Re C, Im C, sqrt(energy product), spare: one 16-byte store
+constexpr int CFO_JOB_FLOATS  = 4 * 4 * 3 * CFO_PART_FLOATS; // [port][layer][gap]
+constexpr int CFO_LDS_BYTES   = 128;                     // behind chest_lds: 14 phasors, cfo_hz, rho
+
+__host__ __device__ inline bool cfo_job_ok(const miphy_pusch_chest_cfo_job& j)
+{
+  return chest_job_rule(j.base, false) == CHEST_RULE_NONE && j.base.ce_compact == 0;
+}
+
+// tau_l - tau_ref in samples at 2048 * 2^mu * 15 kHz, tau the start of the useful part of an OFDM symbol of the slot (normal cyclic prefix): a
+// symbol lasts 2048 + 144 samples, 16 * 2^mu more where (14 slot + j) mod (7 * 2^mu) = 0 (the rule of miphy_ofdm_symbol_size).
+__host__ __device__ inline int cfo_symbol_delta(unsigned mu, unsigned slot, int ref, int l)
+{
+  const auto extra = [&](int j) -> int { return (14u * slot + (unsigned)j) % (7u << mu) == 0 ? (16 << mu) : 0; };
+  const int  lo = l < ref ? l : ref, hi = l < ref ? ref : l;
+  int        d  = extra(hi) - extra(lo);
+  for (int j = lo; j < hi; ++j)
+    d += 2048 + 144 + extra(j);
+  return l < ref ? -d : d;
+}
+
+__device__ __forceinline__ float cfo_sample_rate(unsigned mu)
+{
+  return 2048.f * 15000.f * (float)(1u << mu);
+}
+
+// The DM-RS elements of the pilot pairs of this thread (the fetch of chest_layers_kernel).
+__device__ __forceinline__ void cfo_fetch(float2 (&xq)[CL_PK][2][4], const float2* g, const uint16_t* prb_of, const int (&dsym)[4], int nds, int npairs, int nsc, int grp,
+                                          int tid)
+{
+#pragma unroll
+  for (int kk = 0; kk < CL_PK; ++kk) {
+    const int m = tid + kk * CHEST_THREADS;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      xq[kk][0][d] = xq[kk][1][d] = make_float2(0.f, 0.f);
+      if (m < npairs && d < nds) {
+        const float2* src = g + (size_t)dsym[d] * nsc + prb_of[m / 3] * 12 + 4 * (m % 3) + grp;
+        xq[kk][0][d] = src[0];
+        xq[kk][1][d] = src[2];
+      }
+    }
+  }
+}
+
+// Workgroup per (job, rx port, CDM group), the grid of chest_layers_kernel; no IDFT buffer and no LS vector, so 2.3 KB of LDS.
+__global__ void __launch_bounds__(CHEST_THREADS) cfo_corr_kernel(const miphy_pusch_chest_cfo_job* __restrict__ jobs, const gold_jump* __restrict__ gj,
+                                                                 const float2* __restrict__ grid, float* __restrict__ parts, int ports_dim)
+{
+  __shared__ uint32_t cbits[4 * 104];
+  __shared__ uint64_t rbm[5];
+  __shared__ uint16_t prb_of[276];
+  __shared__ float    red[CHEST_THREADS / 64];
+  const int tid = threadIdx.x;
+  const miphy_pusch_chest_cfo_job& jm = jobs[blockIdx.x];
+  const int port = blockIdx.y % ports_dim, grp = blockIdx.y / ports_dim;
+  const int L    = jm.base.nof_tx_layers;
+  // (uniform) a job without this port or group; a device-resident job that breaks a rule
+  if (port >= jm.base.nof_rx_ports || 2 * grp >= L || !cfo_job_ok(jm))
+    return;
+  const miphy_pusch_chest_job job = load_words(&jm.base);
+  int       dsym[4];
+  const int nds = chest_dmrs_symbols(job.symbols_mask, job.first_symbol, job.first_symbol + job.nof_symbols, dsym);
+  if (nds < 2) // no gap: chest_cfo_kernel reads nothing
+    return;
+  const bool pair = 2 * grp + 1 < L; // both layers of the group are present
+  const int  nprb_grid = job.grid_nof_prb, nsc = nprb_grid * 12;
+  const int  nprb = chest_prb_list(jm.base.rb_mask, nprb_grid, rbm, prb_of, tid);
+  const int  npairs = nprb * 3;
+  float2     xq[CL_PK][2][4];
+  cfo_fetch(xq, chest_port_grid(grid, job, port), prb_of, dsym, nds, npairs, nsc, grp, tid);
+  uint32_t c_init[4];
+  chest_c_init(job, dsym, nds, c_init);
+  gold_bits_block(*reinterpret_cast<const gold_tables*>(gj), c_init[0], c_init[1], c_init[2], c_init[3], nds, 12 * nprb_grid, cbits, tid);
+
+  // s[e]: both layers present, s_a and s_b of the pair; a layer alone, its z on the two pilots of the pair
+  const float ib = 1.0f / job.scaling;
+  cplx        cacc[2][3];
+  float       eacc[2][4];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      cacc[e][d] = {0.f, 0.f};
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      eacc[e][d] = 0.f;
+  }
+#pragma unroll
+  for (int kk = 0; kk < CL_PK; ++kk) {
+    const int m = tid + kk * CHEST_THREADS;
+    if (m >= npairs)
+      continue;
+    const int gp0 = prb_of[m / 3] * 6 + 2 * (m % 3);
+    cplx      prev[2] = {{0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      if (d >= nds)
+        continue;
+      cplx s[2];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const cplx   p = chest_qpsk_pilot(cbits, d, gp0 + e);
+        const float2 x = xq[kk][e][d];
+        s[e]           = {(x.x * p.x + x.y * p.y) * ib, (x.y * p.x - x.x * p.y) * ib};
+      }
+      if (pair) {
+        const cplx sa = {(s[0].x + s[1].x) * 0.5f, (s[0].y + s[1].y) * 0.5f}, sb = {(s[0].x - s[1].x) * 0.5f, (s[0].y - s[1].y) * 0.5f};
+        s[0] = sa, s[1] = sb;
+      }
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        eacc[e][d] += s[e].x * s[e].x + s[e].y * s[e].y;
+        if (d > 0) { // s_{d} conj(s_{d-1})
+          cacc[e][d - 1].x += s[e].x * prev[e].x + s[e].y * prev[e].y;
+          cacc[e][d - 1].y += s[e].y * prev[e].x - s[e].x * prev[e].y;
+        }
+        prev[e] = s[e];
+      }
+    }
+  }
+  // a layer alone: the sums over its even and odd pilots are one sum
+  if (!pair) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      eacc[0][d] += eacc[1][d];
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      cacc[0][d] = cadd(cacc[0][d], cacc[1][d]);
+  }
+  const int nlay = pair ? 2 : 1;
+  float*    out  = parts + (size_t)blockIdx.x * CFO_JOB_FLOATS + (size_t)(port * 4 + 2 * grp) * 3 * CFO_PART_FLOATS;
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    if (e >= nlay) // (uniform)
+      continue;
+    float en[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      if (d < nds)
+        en[d] = block_sum(eacc[e][d], red, tid);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      if (d >= nds - 1)
+        continue;
+      const float cr = block_sum(cacc[e][d].x, red, tid), ci = block_sum(cacc[e][d].y, red, tid);
+      if (tid == 0)
+        *reinterpret_cast<float4*>(out + (e * 3 + d) * CFO_PART_FLOATS) = make_float4(cr, ci, sqrtf(en[d + 1] * en[d]), 0.f);
+    }
+  }
+}
+
+// chest_layers_kernel for jobs on one to four layers, with the offset taken out of the DM-RS elements and put back into every stored symbol.
+__global__ void __launch_bounds__(CHEST_THREADS, 4) chest_cfo_kernel(const miphy_pusch_chest_cfo_job* __restrict__ jobs,
+                                                                     const gold_jump* __restrict__ gj,
+                                                                     const cplx* __restrict__ tw,
+                                                                     const float2* __restrict__ grid,
+                                                                     float2* __restrict__ ce_out,
+                                                                     float* __restrict__ scalars,
+                                                                     const float* __restrict__ parts,
+                                                                     float* __restrict__ cfo_out,
+                                                                     int ports_dim) // blockIdx.y = CDM group * ports_dim + port
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const chest_lds lds(smem);
+  float2*         ph    = reinterpret_cast<float2*>(smem + chest_lds::BYTES); // 14: exp(+j phi_l)
+  float*          cfo_s = reinterpret_cast<float*>(ph + 14);                   // cfo_hz, rho
+  constexpr int nt = CHEST_THREADS;
+  const int     tid = threadIdx.x;
+  const miphy_pusch_chest_cfo_job& jm = jobs[blockIdx.x];
+  const int port = blockIdx.y % ports_dim, grp = blockIdx.y / ports_dim;
+  const int L    = jm.base.nof_tx_layers;
+  // (uniform) a job without this port or group; a device-resident job that breaks a rule
+  if (port >= jm.base.nof_rx_ports || 2 * grp >= L || !cfo_job_ok(jm))
+    return;
+  const miphy_pusch_chest_job job = load_words(&jm.base);
+  const bool pair = 2 * grp + 1 < L; // both layers of the group are present
+  const int  nlay = pair ? 2 : 1;
+  const int  nprb_grid = job.grid_nof_prb, nsc = nprb_grid * 12;
+  const int  first = job.first_symbol, nsymb_out = first + job.nof_symbols;
+  int        dsym[4];
+  const int  nds  = chest_dmrs_symbols(job.symbols_mask, first, nsymb_out, dsym);
+  const int  nprb = chest_prb_list(jm.base.rb_mask, nprb_grid, lds.rbm, lds.prb_of, tid);
+  const int  np = nprb * 6, npairs = nprb * 3;
+  const float beta = job.scaling;
+  float2      xq[CL_PK][2][4];
+  cfo_fetch(xq, chest_port_grid(grid, job, port), lds.prb_of, dsym, nds, npairs, nsc, grp, tid);
+
+  // ---- the offset from the partials of every (port, layer, gap) of the job, under the memory requests above
+  if (tid == 0) {
+    cplx  c[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+    float e[3] = {0.f, 0.f, 0.f};
+    const float* pj = parts + (size_t)blockIdx.x * CFO_JOB_FLOATS;
+    for (int p = 0; p < (nds >= 2 ? (int)job.nof_rx_ports : 0); ++p)
+      for (int l = 0; l < L; ++l)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          if (d >= nds - 1)
+            continue;
+          const float4 v = *reinterpret_cast<const float4*>(pj + ((p * 4 + l) * 3 + d) * CFO_PART_FLOATS);
+          c[d].x += v.x, c[d].y += v.y, e[d] += v.z;
+        }
+    float num = 0.f, sum_c = 0.f, sum_e = 0.f;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      if (d >= nds - 1)
+        continue;
+      const float mag = sqrtf(c[d].x * c[d].x + c[d].y * c[d].y);
+      const int   ds  = cfo_symbol_delta(job.numerology, job.slot_in_frame, dsym[d], dsym[d + 1]);
+      if (mag > 0.f)
+        num += mag * (atan2f(c[d].y, c[d].x) * 0.15915494309189533577f) * (cfo_sample_rate(job.numerology) / (float)ds);
+      sum_c += mag, sum_e += e[d];
+    }
+    const bool have = sum_c > 0.f;
+    cfo_s[0] = have ? num / sum_c : 0.f;
+    cfo_s[1] = have ? sum_c / sum_e : 0.f;
+  }
+  __syncthreads();
+  const float cfo_hz = cfo_s[0];
+  if (tid < 14) {
+    float sn, cs;
+    sincospif(2.f * cfo_hz * ((float)cfo_symbol_delta(job.numerology, job.slot_in_frame, dsym[0], tid) / cfo_sample_rate(job.numerology)), &sn, &cs);
+    ph[tid] = make_float2(cs, sn);
+  }
+  uint32_t c_init[4];
+  chest_c_init(job, dsym, nds, c_init);
+  gold_bits_block(*reinterpret_cast<const gold_tables*>(gj), c_init[0], c_init[1], c_init[2], c_init[3], nds, 12 * nprb_grid, lds.cbits, tid); // (barrier: ph[])
+  if (tid == 0 && port == 0 && grp == 0) {
+    float* o = cfo_out + jm.cfo_offset;
+    o[0] = cfo_hz, o[1] = cfo_s[1];
+  }
+  // x_d exp(-j phi_d)
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    if (d >= nds)
+      continue;
+    const float2 r = ph[dsym[d]];
+#pragma unroll
+    for (int kk = 0; kk < CL_PK; ++kk)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const float2 x = xq[kk][e][d];
+        xq[kk][e][d]   = make_float2(x.x * r.x + x.y * r.y, x.y * r.x - x.x * r.y);
+      }
+  }
+
+  // ---- from here chest_layers_kernel: least squares against layer 0's pilot, despreading, EPRE, RSRP
+  const float ts = 1.0f / ((float)nds * beta);
+  float       epre_acc = 0.f, ra_acc = 0.f, rb_acc = 0.f;
+#pragma unroll
+  for (int kk = 0; kk < CL_PK; ++kk) {
+    const int m = tid + kk * nt;
+    if (m >= npairs)
+      continue;
+    const int gp0 = lds.prb_of[m / 3] * 6 + 2 * (m % 3);
+    cplx      z[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const cplx acc = chest_ls(xq[kk][e], nds, epre_acc, [&](int d) { return chest_qpsk_pilot(lds.cbits, d, gp0 + e); });
+      z[e]           = {acc.x * ts, acc.y * ts};
+    }
+    if (pair) {
+      const cplx sa = {(z[0].x + z[1].x) * 0.5f, (z[0].y + z[1].y) * 0.5f}, sb = {(z[0].x - z[1].x) * 0.5f, (z[0].y - z[1].y) * 0.5f};
+      lds.lse[2 * m] = sa, lds.lse[2 * m + 1] = sb;
+      ra_acc += sa.x * sa.x + sa.y * sa.y;
+      rb_acc += sb.x * sb.x + sb.y * sb.y;
+    } else {
+      lds.lse[2 * m] = z[0], lds.lse[2 * m + 1] = z[1];
+      ra_acc += z[0].x * z[0].x + z[0].y * z[0].y + z[1].x * z[1].x + z[1].y * z[1].y;
+    }
+  }
+  const float epre    = block_sum(epre_acc, lds.red, tid) / (float)(np * nds);
+  const float rs_norm = beta * beta / (float)(pair ? npairs : np);
+  float       rsrp[2];
+  rsrp[0] = block_sum(ra_acc, lds.red, tid) * rs_norm;
+  rsrp[1] = pair ? block_sum(rb_acc, lds.red, tid) * rs_norm : 0.f;
+  __syncthreads(); // lse[]
+
+  // ---- interpolation, to every OFDM symbol with the symbol's phasor
+  const int sh = pair ? 2 : 1, off = pair ? 1 + grp : grp, ninp = pair ? npairs : np;
+  for (int l = 0; l < nlay; ++l) {
+    float2*    dst0   = chest_ce_rows(ce_out, job, 2 * grp + l, port);
+    const auto anchor = [&](int i) -> cplx { return pair ? lds.lse[2 * i + l] : lds.lse[i]; };
+    for (int k = tid; k < nprb * 12; k += nt) {
+      const cplx   v   = chest_interpolate<false>(anchor, k, sh, off, ninp);
+      const size_t col = (size_t)lds.prb_of[k / 12] * 12 + (k % 12);
+      for (int sy = first; sy < nsymb_out; ++sy) {
+        const float2 r = ph[sy];
+        dst0[(size_t)sy * nsc + col] = make_float2(v.x * r.x - v.y * r.y, v.x * r.y + v.y * r.x);
+      }
+    }
+  }
+
+  // ---- noise, as chest_layers_kernel, on the derotated elements
+  float noise_var = 0.001f * epre; // convert_dB_to_power(-30) * epre
+  if (nds >= 3) {
+    float noise_acc = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < CL_PK; ++kk) {
+      const int m = tid + kk * nt;
+      if (m >= npairs)
+        continue;
+      const int  b  = (m / 3) * 6;
+      const cplx ea = cadd(cadd(lds.lse[b], lds.lse[b + 2]), lds.lse[b + 4]), eo = cadd(cadd(lds.lse[b + 1], lds.lse[b + 3]), lds.lse[b + 5]);
+      cplx       ma, mb; // a layer alone: the mean of its six z, no second parameter
+      if (pair)
+        ma = {ea.x / 3.f, ea.y / 3.f}, mb = {eo.x / 3.f, eo.y / 3.f};
+      else
+        ma = {(ea.x + eo.x) / 6.f, (ea.y + eo.y) / 6.f}, mb = {0.f, 0.f};
+      const cplx h[2] = {{(ma.x + mb.x) * -beta, (ma.y + mb.y) * -beta}, {(ma.x - mb.x) * -beta, (ma.y - mb.y) * -beta}};
+      const int  gp0  = lds.prb_of[m / 3] * 6 + 2 * (m % 3);
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+        chest_residual(xq[kk][e], nds, h[e], noise_acc, [&](int d) { return chest_qpsk_pilot(lds.cbits, d, gp0 + e); });
+    }
+    noise_var = block_sum(noise_acc, lds.red, tid) / (float)np * 6.f / (float)(6 * nds - nlay);
+  }
+
+  // ---- time alignment per layer
+  float ta[2] = {0.f, 0.f};
+  for (int l = 0; l < nlay; ++l) {
+    chest_clear_idft(lds.fbuf, tid);
+    __syncthreads();
+    for (int i = tid; i < np; i += nt)
+      lds.fbuf[fpad(lds.prb_of[i / 6] * 12 + 2 * (i % 6) + grp)] = pair ? lds.lse[(i & ~1) + l] : lds.lse[i];
+    __syncthreads();
+    fft4096_lds<true>(lds.fbuf, tw, tid);
+    ta[l] = chest_ta_peak(lds.fbuf, lds.red, tid);
+  }
+
+  // ---- side-band scalars, per layer; the noise variance is the group's
+  if (tid < nlay)
+    chest_scalars(scalars, job, port, 2 * grp + tid, tid ? rsrp[1] : rsrp[0], epre, noise_var, tid ? ta[1] : ta[0], true, true);
+}
+
 } // namespace
 
 // The rules a batch of host jobs is held to (chest_job_rule), and its largest port and layer counts.
-static int chest_validate(const miphy_pusch_chest_job* jobs, uint32_t n, bool pilots, unsigned& max_ports, unsigned& max_layers)
+static int chest_validate(const miphy_pusch_chest_job* jobs, uint32_t n, bool pilots, unsigned& max_ports, unsigned& max_layers, const char* what = "pusch_chest")
 {
   max_ports = max_layers = 1;
   for (uint32_t i = 0; i < n; ++i) {
     const miphy_pusch_chest_job& j = jobs[i];
     const chest_rule r = chest_job_rule(j, pilots);
-    MIPHY_REQUIRE(r != CHEST_RULE_NUMEROLOGY, "pusch_chest: job %u: invalid numerology", i);
-    MIPHY_REQUIRE(r != CHEST_RULE_LAYERS, "pusch_chest: job %u: invalid number of layers %u", i, j.nof_tx_layers);
-    MIPHY_REQUIRE(r != CHEST_RULE_PORTS, "pusch_chest: job %u: invalid number of rx ports %u", i, j.nof_rx_ports);
-    MIPHY_REQUIRE(r != CHEST_RULE_GRID, "pusch_chest: job %u: invalid grid width", i);
-    MIPHY_REQUIRE(r != CHEST_RULE_SYMBOLS, "pusch_chest: job %u: invalid symbol range", i);
-    MIPHY_REQUIRE(r != CHEST_RULE_SCALING, "pusch_chest: job %u: the DM-RS to data scaling factor should be a positive number", i);
-    MIPHY_REQUIRE(r != CHEST_RULE_DMRS, "pusch_chest: job %u: %u DM-RS symbols (1..4 supported)", i,
+    MIPHY_REQUIRE(r != CHEST_RULE_NUMEROLOGY, "%s: job %u: invalid numerology", what, i);
+    MIPHY_REQUIRE(r != CHEST_RULE_LAYERS, "%s: job %u: invalid number of layers %u", what, i, j.nof_tx_layers);
+    MIPHY_REQUIRE(r != CHEST_RULE_PORTS, "%s: job %u: invalid number of rx ports %u", what, i, j.nof_rx_ports);
+    MIPHY_REQUIRE(r != CHEST_RULE_GRID, "%s: job %u: invalid grid width", what, i);
+    MIPHY_REQUIRE(r != CHEST_RULE_SYMBOLS, "%s: job %u: invalid symbol range", what, i);
+    MIPHY_REQUIRE(r != CHEST_RULE_SCALING, "%s: job %u: the DM-RS to data scaling factor should be a positive number", what, i);
+    MIPHY_REQUIRE(r != CHEST_RULE_DMRS, "%s: job %u: %u DM-RS symbols (1..4 supported)", what, i,
                   chest_nof_dmrs(j.symbols_mask, j.first_symbol, j.first_symbol + j.nof_symbols));
-    MIPHY_REQUIRE(r != CHEST_RULE_NO_HOPPING, "pusch_chest: job %u: intra-slot frequency hopping is served by miphy_port_channel_estimate_batch", i);
-    MIPHY_REQUIRE(r != CHEST_RULE_HOP_SYMBOL, "pusch_chest: job %u: hop symbol outside the allocation", i);
-    MIPHY_REQUIRE(r != CHEST_RULE_HOP_COMPACT, "pusch_chest: job %u: the compact estimate holds one hop only", i);
-    MIPHY_REQUIRE(r != CHEST_RULE_HOP_DMRS, "pusch_chest: job %u: every hop needs a DM-RS symbol", i);
-    MIPHY_REQUIRE(r != CHEST_RULE_HOP_PRBS, "pusch_chest: job %u: the hops have different numbers of PRBs", i);
-    MIPHY_REQUIRE(r != CHEST_RULE_EMPTY, "pusch_chest: job %u: empty allocation", i);
+    MIPHY_REQUIRE(r != CHEST_RULE_NO_HOPPING, "%s: job %u: intra-slot frequency hopping is served by miphy_port_channel_estimate_batch", what, i);
+    MIPHY_REQUIRE(r != CHEST_RULE_HOP_SYMBOL, "%s: job %u: hop symbol outside the allocation", what, i);
+    MIPHY_REQUIRE(r != CHEST_RULE_HOP_COMPACT, "%s: job %u: the compact estimate holds one hop only", what, i);
+    MIPHY_REQUIRE(r != CHEST_RULE_HOP_DMRS, "%s: job %u: every hop needs a DM-RS symbol", what, i);
+    MIPHY_REQUIRE(r != CHEST_RULE_HOP_PRBS, "%s: job %u: the hops have different numbers of PRBs", what, i);
+    MIPHY_REQUIRE(r != CHEST_RULE_EMPTY, "%s: job %u: empty allocation", what, i);
     max_ports  = j.nof_rx_ports > max_ports ? j.nof_rx_ports : max_ports;
     max_layers = j.nof_tx_layers > max_layers ? j.nof_tx_layers : max_layers;
   }
@@ -962,6 +1306,48 @@ extern "C" int miphy_dmrs_pusch_estimate_layers_batch(miphy_ctx* ctx, const miph
       return rc;
   }
   return layered ? chest_layers_enqueue(ctx, d_jobs, n, max_ports, max_layers, grid, ce, scalars, s) : MIPHY_OK;
+}
+
+// The layered estimator with the carrier frequency offset estimated and compensated: cfo_corr_kernel, then chest_cfo_kernel, on the grid of
+// chest_layers_kernel; jobs on one layer run there too (a layer alone in its group). The partials live in a workspace of the context.
+extern "C" int miphy_dmrs_pusch_estimate_cfo_batch(miphy_ctx* ctx, const miphy_pusch_chest_cfo_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                                   float* ce, float* scalars, float* cfo, void* stream)
+{
+  const char* what = "miphy_dmrs_pusch_estimate_cfo_batch";
+  unsigned    max_ports, max_layers;
+  int         rc = chest_prologue(what, ctx && jobs && grid && ce && scalars && cfo, n, UINT32_MAX, jobs_on_device, max_ports, max_layers,
+                                  [&](unsigned& mp, unsigned& ml) -> int {
+                            std::vector<miphy_pusch_chest_job> base(n);
+                            for (uint32_t i = 0; i < n; ++i)
+                              base[i] = jobs[i].base;
+                            const int r = chest_validate(base.data(), n, false, mp, ml, what);
+                            if (r)
+                              return r;
+                            for (uint32_t i = 0; i < n; ++i)
+                              MIPHY_REQUIRE(jobs[i].base.ce_compact == 0, "%s: job %u: the estimate differs from symbol to symbol, ce_compact must be 0", what, i);
+                            return (int)MIPHY_OK;
+                          });
+  if (rc || n == 0)
+    return rc;
+  hipStream_t s      = (hipStream_t)stream;
+  const void* d_jobs = nullptr;
+  if ((rc = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pusch_chest_cfo_job) * (size_t)n, s, &d_jobs)))
+    return rc;
+  void* parts = nullptr;
+  if ((rc = miphy_get_workspace(ctx, MIPHY_WS_GENERAL, sizeof(float) * CFO_JOB_FLOATS * (size_t)n, &parts)))
+    return rc;
+  const cplx*      tw;
+  const gold_jump* gold;
+  if ((rc = chest_resources(ctx, &tw, &gold)))
+    return rc;
+  const dim3 blocks(n, max_ports * (max_layers > 2 ? 2 : 1));
+  hipLaunchKernelGGL(cfo_corr_kernel, blocks, dim3(CHEST_THREADS), 0, s, (const miphy_pusch_chest_cfo_job*)d_jobs, gold, (const float2*)grid, (float*)parts,
+                     (int)max_ports);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(chest_cfo_kernel, blocks, dim3(CHEST_THREADS), chest_lds::BYTES + CFO_LDS_BYTES, s, (const miphy_pusch_chest_cfo_job*)d_jobs, gold, tw,
+                     (const float2*)grid, (float2*)ce, scalars, (const float*)parts, cfo, (int)max_ports);
+  MIPHY_HIP_CHECK(hipGetLastError());
+  return MIPHY_OK;
 }
 
 extern "C" int miphy_dmrs_pusch_estimate_batch(miphy_ctx* ctx, const miphy_pusch_chest_job* jobs, int jobs_on_device, uint32_t n, const float* grid, float* ce,

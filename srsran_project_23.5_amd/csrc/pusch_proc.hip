@@ -6,7 +6,8 @@
 // with the parameters the reference derives (DM-RS scaling from the SCH-to-DM-RS power ratio, codeword length from the allocation);
 // with multiplexed UCI, miphy_ulsch_demultiplex_batch between the last two. One codeword on 1..4 layers goes through the layered stages, a
 // transform-precoded PUSCH (DFT-s-OFDM) through miphy_dmrs_pusch_estimate_tp_batch and miphy_pusch_demodulate_tp_batch, a layered PDU with MMSE-IRC
-// through the layered estimator, miphy_pusch_noise_covariance_batch and miphy_pusch_demodulate_layers_mmse_batch_ex.
+// through the layered estimator, miphy_pusch_noise_covariance_batch and miphy_pusch_demodulate_layers_mmse_batch_ex. A layered PDU of a UE with a carrier
+// frequency offset goes through miphy_dmrs_pusch_estimate_cfo_batch, whose estimate differs from symbol to symbol and is kept per symbol.
 #include "miphy_ext.h"
 #include <cmath>
 #include <vector>
@@ -50,7 +51,7 @@ struct pusch_batch {
 };
 
 int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus_in, const miphy_pusch_tp_pdu* tpdus, const miphy_pusch_mmse_pdu* mpdus,
-                      const miphy_pusch_uci* uci, uint32_t n, bool have_uci_out, pusch_batch& b)
+                      const miphy_pusch_uci* uci, uint32_t n, bool have_uci_out, bool ce_per_symbol, pusch_batch& b)
 {
   b.cj.resize(n), b.dj.resize(n), b.nof_sym.resize(n);
   std::vector<miphy_pusch_layers_pdu> layered_of_mmse; // the layered PDU inside every MMSE PDU, in one array like lpdus_in
@@ -104,13 +105,15 @@ int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu*
     c.scaling = powf(10.0f, 3.0f / 20.0f);
     c.n_scid = p.n_scid, c.nof_tx_layers = (uint8_t)L, c.nof_rx_ports = p.nof_rx_ports, c.first_symbol = p.start_symbol, c.nof_symbols = p.nof_symbols;
     c.symbols_mask = p.dmrs_symbols_mask, c.grid_nof_prb = p.grid_nof_prb;
-    c.ce_compact   = 1; // the estimate only feeds the demodulator below: one row per port instead of a copy per symbol
+    // the estimate only feeds the demodulator below: one row per port instead of a copy per symbol -- unless the symbols differ (ce_per_symbol: the
+    // estimator that compensates a carrier frequency offset)
+    c.ce_compact = ce_per_symbol ? 0 : 1;
     miphy_pusch_demod_layers_job& lj = b.dj[i];
     lj                               = {};
     lj.nof_tx_layers                 = (uint8_t)L;
     miphy_pusch_demod_job& d         = lj.base;
     d.rnti = p.rnti, d.n_id = p.n_id, d.mod = p.mod, d.nof_rx_ports = p.nof_rx_ports, d.start_symbol = p.start_symbol, d.nof_symbols = p.nof_symbols;
-    d.dmrs_type = 1, d.nof_cdm_groups_without_data = 2, d.ce_nof_symbols = (uint8_t)nsym_ce, d.ce_compact = 1;
+    d.dmrs_type = 1, d.nof_cdm_groups_without_data = 2, d.ce_nof_symbols = (uint8_t)nsym_ce, d.ce_compact = c.ce_compact;
     d.dmrs_symbols_mask = p.dmrs_symbols_mask, d.grid_nof_prb = p.grid_nof_prb;
     for (int k = 0; k < 4; ++k)
       c.rx_ports[k] = p.rx_ports[k], d.rx_ports[k] = p.rx_ports[k];
@@ -167,7 +170,7 @@ int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu*
       b.tb.push_back(t);
       b.tb_index.push_back(i);
     }
-    b.ce_elems += (size_t)L * p.nof_rx_ports * nsc;
+    b.ce_elems += (size_t)L * p.nof_rx_ports * nsc * (ce_per_symbol ? nsym_ce : 1u);
     b.llr_bytes += (d.nof_llr + 15u) & ~15u;
   }
   for (auto& t : b.tb) // SCH region behind the codeword LLRs
@@ -209,10 +212,10 @@ int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu*
 // checked before anything is enqueued (pusch_batch_build); the stages check their own rules again on the jobs built there.
 int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus, const miphy_pusch_tp_pdu* tpdus,
                      const miphy_pusch_mmse_pdu* mpdus, const miphy_pusch_uci* uci, uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs,
-                     uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results, float* scalars_out, int8_t* uci_llr_out, float* evm_out, hipStream_t s)
+                     uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results, float* scalars_out, int8_t* uci_llr_out, float* evm_out, float* cfo_out, hipStream_t s)
 {
   pusch_batch b;
-  int         rc = pusch_batch_build(pdus, lpdus, tpdus, mpdus, uci, n, uci_llr_out != nullptr, b);
+  int         rc = pusch_batch_build(pdus, lpdus, tpdus, mpdus, uci, n, uci_llr_out != nullptr, cfo_out != nullptr, b);
   if (rc)
     return rc;
   // [placeholders | data REs || channel estimates cf_t | codeword LLRs, UL-SCH LLRs of the PDUs with UCI | EVM sums] in a workspace of the
@@ -239,6 +242,14 @@ int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pu
     if ((rc = miphy_pusch_noise_covariance_batch(ctx, b.nj.data(), 0, n, grid, d_cov, s)))
       return rc;
     if ((rc = miphy_pusch_demodulate_layers_mmse_batch_ex(ctx, b.mj.data(), 0, n, grid, d_ce, scalars_out, d_cov, d_llr, d_ph, d_evm, s)))
+      return rc;
+  } else if (lpdus && cfo_out) { // (layered PDUs only) the per-symbol estimate of the offset-compensating estimator, {cfo_hz, rho} of PDU i at 2 i
+    std::vector<miphy_pusch_chest_cfo_job> fj(n);
+    for (uint32_t i = 0; i < n; ++i)
+      fj[i].base = b.cj[i], fj[i].cfo_offset = 2ull * i;
+    if ((rc = miphy_dmrs_pusch_estimate_cfo_batch(ctx, fj.data(), 0, n, grid, d_ce, scalars_out, cfo_out, s)))
+      return rc;
+    if ((rc = miphy_pusch_demodulate_layers_batch_ex(ctx, b.dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, d_ph, d_evm, s)))
       return rc;
   } else if (lpdus) {
     if ((rc = miphy_dmrs_pusch_estimate_layers_batch(ctx, b.cj.data(), 0, n, grid, d_ce, scalars_out, s)))
@@ -303,7 +314,7 @@ extern "C" int miphy_pusch_process_layers_batch_ex(miphy_ctx* ctx, const miphy_p
                 "miphy_pusch_process_layers_batch: null argument");
   if (n == 0)
     return MIPHY_OK;
-  return pusch_process_ex(ctx, nullptr, pdus, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+  return pusch_process_ex(ctx, nullptr, pdus, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out, nullptr,
                           (hipStream_t)stream);
 }
 
@@ -323,7 +334,7 @@ extern "C" int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pd
                 "miphy_pusch_process_batch: null argument");
   if (n == 0)
     return MIPHY_OK;
-  return pusch_process_ex(ctx, pdus, nullptr, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+  return pusch_process_ex(ctx, pdus, nullptr, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out, nullptr,
                           (hipStream_t)stream);
 }
 
@@ -336,7 +347,7 @@ extern "C" int miphy_pusch_process_tp_batch_ex(miphy_ctx* ctx, const miphy_pusch
                 "miphy_pusch_process_tp_batch: null argument");
   if (n == 0)
     return MIPHY_OK;
-  return pusch_process_ex(ctx, nullptr, nullptr, pdus, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+  return pusch_process_ex(ctx, nullptr, nullptr, pdus, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out, nullptr,
                           (hipStream_t)stream);
 }
 
@@ -346,6 +357,20 @@ extern "C" int miphy_pusch_process_tp_batch(miphy_ctx* ctx, const miphy_pusch_tp
 {
   return miphy_pusch_process_tp_batch_ex(ctx, pdus, nullptr, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, nullptr, nullptr,
                                          stream);
+}
+
+// The layered processor with the estimator that estimates and compensates a carrier frequency offset in front (include/miphy.h).
+extern "C" int miphy_pusch_process_layers_cfo_batch(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus, const miphy_pusch_uci* uci, uint32_t n, const float* grid,
+                                                    int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
+                                                    miphy_pusch_result* results, float* scalars_out, int8_t* uci_llr_out, float* evm_out, float* cfo_out,
+                                                    void* stream)
+{
+  MIPHY_REQUIRE(ctx && pdus && grid && harq_softbits && harq_msgs && harq_crc_ok && tb_out && results && scalars_out && cfo_out,
+                "miphy_pusch_process_layers_cfo_batch: null argument");
+  if (n == 0)
+    return MIPHY_OK;
+  return pusch_process_ex(ctx, nullptr, pdus, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+                          cfo_out, (hipStream_t)stream);
 }
 
 // One codeword on 1..4 layers through MMSE-IRC: the layered processor with the covariance estimator between its estimator and an MMSE demodulator.
@@ -358,5 +383,5 @@ extern "C" int miphy_pusch_process_layers_mmse_batch(miphy_ctx* ctx, const miphy
   if (n == 0)
     return MIPHY_OK;
   return pusch_process_ex(ctx, nullptr, nullptr, nullptr, pdus, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out,
-                          evm_out, (hipStream_t)stream);
+                          evm_out, nullptr, (hipStream_t)stream);
 }

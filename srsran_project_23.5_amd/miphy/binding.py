@@ -165,6 +165,9 @@ def lib():
             l.miphy_pusch_demodulate_layers_mmse_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 6
             l.miphy_pusch_demodulate_layers_mmse_batch_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 8
             l.miphy_pusch_process_layers_mmse_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 10
+        if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_dmrs_pusch_estimate_cfo_batch"):  # (likewise)
+            l.miphy_dmrs_pusch_estimate_cfo_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
+            l.miphy_pusch_process_layers_cfo_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 11
         l.miphy_polar_block_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("miphy_ofdm_demodulate_symbols", "miphy_ofdm_modulate_symbols"):
             getattr(l, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -254,6 +257,11 @@ assert PuschChestJob.fields["rb_mask"][1] == 32 and PuschChestJob.fields["symbol
 PuschNcovJob = np.dtype([("base", PuschChestJob), ("cov_offset", np.uint64), ("loading", np.float32), ("prg_size", np.uint16), ("reserved", np.uint8, 2)],
                         align=True)
 assert PuschNcovJob.itemsize == 168 and PuschNcovJob.fields["cov_offset"][1] == 152, PuschNcovJob.itemsize
+
+
+# Mirrors miphy_pusch_chest_cfo_job: the layered estimator with the carrier frequency offset estimated and compensated; {cfo_hz, rho} at cfo_offset.
+PuschChestCfoJob = np.dtype([("base", PuschChestJob), ("cfo_offset", np.uint64)], align=True)
+assert PuschChestCfoJob.itemsize == 160 and PuschChestCfoJob.fields["cfo_offset"][1] == 152, PuschChestCfoJob.itemsize
 
 
 def pusch_noise_covariance_nof_prg(job):
@@ -1026,6 +1034,14 @@ class Context:
             on_dev |= (int(max_ports) << 8) | (int(max_layers) << 12)
         check(lib().miphy_dmrs_pusch_estimate_layers_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _stream_ptr(stream)))
 
+    def dmrs_pusch_estimate_cfo_batch(self, jobs, grid, ce, scalars, cfo, stream=None, max_ports=0, max_layers=0):
+        """The layered estimator with the carrier frequency offset estimated from the DM-RS symbols and compensated (PuschChestCfoJob records,
+        ce_compact = 0: the estimate is written per symbol; cfo: device float32, {cfo_hz, rho} per job at cfo_offset); hints as dmrs_pusch_estimate_batch."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschChestCfoJob)
+        if on_dev:
+            on_dev |= (int(max_ports) << 8) | (int(max_layers) << 12)
+        check(lib().miphy_dmrs_pusch_estimate_cfo_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _dptr(cfo), _stream_ptr(stream)))
+
     def pusch_noise_covariance_batch(self, jobs, grid, cov, stream=None, max_ports=0, max_layers=0):
         """Noise-plus-interference covariance per PRG from the DM-RS residuals (PuschNcovJob records; cov: device complex64); hints as
         dmrs_pusch_estimate_batch."""
@@ -1211,6 +1227,21 @@ class Context:
                                                           _dptr(harq_msgs), _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars),
                                                           _dptr(uci_llr) if uci_llr is not None else None, _dptr(evm) if evm is not None else None,
                                                           _stream_ptr(stream)))
+
+    def pusch_process_layers_cfo_batch(self, pdus, uci, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, uci_llr, evm, cfo, stream=None):
+        """pusch_process_layers_batch_ex with dmrs_pusch_estimate_cfo_batch in front and a per-symbol estimate behind it; cfo: device float32 [n][2],
+        {cfo_hz, rho} per PDU."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PuschLayersPdu
+        pdus = np.ascontiguousarray(pdus)
+        up = None
+        if uci is not None:
+            assert isinstance(uci, np.ndarray) and uci.dtype == PuschUci and uci.size == pdus.size
+            uci = np.ascontiguousarray(uci)
+            up = C.c_void_p(uci.ctypes.data)
+        check(lib().miphy_pusch_process_layers_cfo_batch(self.h, C.c_void_p(pdus.ctypes.data), up, pdus.size, _dptr(grid), _dptr(harq_softbits),
+                                                         _dptr(harq_msgs), _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars),
+                                                         _dptr(uci_llr) if uci_llr is not None else None, _dptr(evm) if evm is not None else None,
+                                                         _dptr(cfo), _stream_ptr(stream)))
 
     def pusch_process_layers_batch_ex(self, pdus, uci, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, uci_llr, evm, stream=None):
         """pusch_process_layers_batch for PDUs with multiplexed UCI (uci: numpy PuschUci array or None) and the EVM (evm: float32 device tensor of n or
