@@ -401,8 +401,8 @@ int miphy_dmrs_pusch_estimate_layers_batch(miphy_ctx* ctx, const miphy_pusch_che
  * (MIPHY_JOBS_ON_DEVICE_HINT) and output layouts of miphy_dmrs_pusch_estimate_layers_batch. A host job that breaks a rule (ce_compact != 0 and
  * hopping included) is MIPHY_EINVAL with nothing enqueued; a device-resident one is skipped. Two launches on the stream: the correlation partials
  * of every (job, port, layer, gap) go to a workspace of the context, the estimate kernel adds them up.
- * Out: time interpolation of the channel magnitude between DM-RS symbols, offsets beyond the unambiguous range, extended CP, MMSE-IRC and
- * transform-precoded variants, prepared plans. */
+ * Out: offsets beyond the unambiguous range, extended CP, MMSE-IRC and transform-precoded variants, prepared plans. A channel whose magnitude
+ * changes between the DM-RS symbols is followed by miphy_dmrs_pusch_estimate_tv_batch below. */
 typedef struct {
   miphy_pusch_chest_job base;   /* ce_compact must be 0; nof_tx_layers 1..4; the rules of the layered estimator otherwise */
   uint64_t cfo_offset;          /* float offset: {cfo_hz, rho} of the job */
@@ -410,6 +410,44 @@ typedef struct {
 int miphy_dmrs_pusch_estimate_cfo_batch(miphy_ctx* ctx, const miphy_pusch_chest_cfo_job* jobs, int jobs_on_device, uint32_t n,
                                         const float* grid /* device cf_t */, float* ce /* device cf_t */, float* scalars /* device */,
                                         float* cfo /* device */, void* stream);
+
+/* The estimator above for a channel that changes within the slot (Doppler spread: magnitude and phase move differently per path and per receive
+ * port, which one common phase per symbol does not follow)  --  beyond the 23.5 reference. The DM-RS symbols are not averaged: the per-symbol fits
+ * are kept apart, derotated by the common offset, and interpolated in time. Notation (tau_l, dsym[d], nds, beta, s_{l,d}[m], phi_l) as above;
+ * cfo_hz and rho are exactly those of miphy_dmrs_pusch_estimate_cfo_batch (the same correlation launch and partials).
+ *   per-symbol fits, per (rx port p, CDM group g, DM-RS symbol d): S_d[m] = s_{.,d}[m] exp(-j phi_{dsym[d]}), despread where both layers of the group
+ *     are present, z_d on all six pilots of a PRB for a layer alone
+ *   time weights w[l][d], for every OFDM symbol l of the allocation and DM-RS symbol d, from differences of tau only; rows sum to 1; nds = 1: w = 1
+ *     MIPHY_TIME_INTERPOLATE: j = the largest index with dsym[j] <= l, clamped to 0 .. nds - 2; u = (tau_l - tau_dsym[j]) / (tau_dsym[j+1] - tau_dsym[j]);
+ *       w[l][j] = 1 - u, w[l][j+1] = u, every other weight 0. u outside [0, 1] extrapolates from the nearest two DM-RS symbols.
+ *     MIPHY_TIME_LINE: w[l][d] = 1 / nds + (tau_l - tm)(tau_dsym[d] - tm) / sum_d' (tau_dsym[d'] - tm)^2, tm the mean of the DM-RS symbol times: one
+ *       least-squares line over all DM-RS symbols. With two DM-RS symbols the two modes coincide.
+ *   estimate: A_l[m] = sum_d w[l][d] S_d[m] are the anchors of symbol l; H_l[k] = the layered estimator's frequency interpolation of A_l (the same
+ *     anchor positions, edges held) times exp(+j phi_l), written to every symbol l of the allocation, allocated PRBs only. The fits are derotated
+ *     before they are blended: a linear blend of two rotated phasors shrinks.
+ *   scalars: epre, rsrp and time alignment from the time mean sum_d S_d / nds (what the least squares of the estimator above computes). The noise is
+ *     measured against the fit in time, not against the mean: F_d = sum_d' w[dsym[d]][d'] S_d'; A_d, B_d = the per-PRB means of F_{a,d}, F_{b,d} (a layer
+ *     alone: the per-PRB mean of its six, B_d = 0); e_d[i] = x'_d[i] - beta r_d[i] (A_d + (-1)^i B_d) with x'_d the derotated element;
+ *     noise_var = sum |e|^2 / nprb / (6 nds - nlay R), nlay the layers of the group, R = nds for INTERPOLATE and min(nds, 2) for LINE (the parameters
+ *     fitted per layer and PRB), from two DM-RS symbols on; one DM-RS symbol: noise_var = 0.001 epre. snr by the rule of the other estimators.
+ *   variation, per (rx port, layer): var = sum_m sum_d |S_d[m] - mean_d S[m]|^2 / sum_m sum_d |S_d[m]|^2, the share of the derotated DM-RS energy that
+ *     the time average does not explain: near 0 for a UE that stands still, towards 1 for a fast one. 0 with one DM-RS symbol or no energy.
+ * Every sum runs in a fixed order without atomics: a job gives the same bits alone and inside any batch. Rules, hints, refusals and output layouts
+ * of miphy_dmrs_pusch_estimate_cfo_batch, and time_mode one of the two values with the reserved bytes 0: a host job that breaks a rule is
+ * MIPHY_EINVAL with nothing enqueued, a device-resident one is skipped. Two launches on the stream, as above.
+ * Out: more than a line or a polygon in time (no Wiener filter, no smoothing across slots), extended CP, MMSE-IRC and transform-precoded variants,
+ * prepared plans. */
+#define MIPHY_TIME_INTERPOLATE 1 /* piecewise linear between DM-RS symbols */
+#define MIPHY_TIME_LINE 2        /* one least-squares line over all DM-RS symbols */
+typedef struct {
+  miphy_pusch_chest_cfo_job base; /* every rule of the CFO estimator holds */
+  uint64_t var_offset;            /* float offset: per (rx port, layer) one float at port * nof_tx_layers + layer */
+  uint8_t  time_mode;             /* MIPHY_TIME_INTERPOLATE or MIPHY_TIME_LINE */
+  uint8_t  reserved[7];           /* 0 */
+} miphy_pusch_chest_tv_job;       /* 176 bytes */
+int miphy_dmrs_pusch_estimate_tv_batch(miphy_ctx* ctx, const miphy_pusch_chest_tv_job* jobs, int jobs_on_device, uint32_t n,
+                                       const float* grid /* device cf_t */, float* ce /* device cf_t */, float* scalars /* device */,
+                                       float* cfo /* device */, float* var /* device */, void* stream);
 
 /* Noise-plus-interference covariance across the receive ports, from the DM-RS residuals of the estimator above  --  beyond the 23.5 reference,
  * which has no MMSE equaliser to feed ("MMSE equalizer is not implemented yet"). Reads the grid only. With e[g][p][d][i] the residual whose
@@ -1145,6 +1183,18 @@ int miphy_pusch_process_layers_cfo_batch(miphy_ctx* ctx, const miphy_pusch_layer
                                          uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
                                          miphy_pusch_result* results, float* scalars_out /* n x 80 */, int8_t* uci_llr_out,
                                          float* evm_out /* device, n, may be NULL */, float* cfo_out /* device, n x 2 */, void* stream);
+
+/* The layered processor for a UE whose channel changes within the slot  --  beyond the reference. miphy_pusch_process_layers_cfo_batch with
+ * miphy_dmrs_pusch_estimate_tv_batch in front (time_mode: MIPHY_TIME_INTERPOLATE or MIPHY_TIME_LINE, one value for the batch); the per-symbol
+ * estimate in the workspace and everything behind it are unchanged. Transport blocks, results, scalars, UCI soft bits, EVM, cfo_out and var_out
+ * are the bytes of the stages called one by one. var_out: 16 floats per PDU, the variation of (port, layer) at port * nof_tx_layers + layer, the
+ * rest untouched. Rules and refusals: those of the layered processor, and the mode; a PDU that breaks one is MIPHY_EINVAL with nothing enqueued.
+ * Out: MMSE-IRC and transform precoding, the slot batch of the uplink processor, a prepared plan, extended CP. */
+int miphy_pusch_process_layers_tv_batch(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus /* host */, const miphy_pusch_uci* uci /* host or NULL */,
+                                        uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
+                                        miphy_pusch_result* results, float* scalars_out /* n x 80 */, int8_t* uci_llr_out,
+                                        float* evm_out /* device, n, may be NULL */, float* cfo_out /* device, n x 2 */, uint32_t time_mode,
+                                        float* var_out /* device, n x 16 */, void* stream);
 
 /* The layered processor with MMSE-IRC  --  beyond the reference. The arguments of miphy_pusch_process_layers_batch_ex; one call chains, on one
  * stream, miphy_dmrs_pusch_estimate_layers_batch (compact estimate), miphy_pusch_noise_covariance_batch (the PDU's prg_size and loading; the

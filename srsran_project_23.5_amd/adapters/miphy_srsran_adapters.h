@@ -818,12 +818,28 @@ private:
 /// layer holds the other one too); the default is the reference's arithmetic. \c compensate_cfo: through miphy_dmrs_pusch_estimate_cfo_batch,
 /// which separates the layers too, estimates the carrier frequency offset from the DM-RS symbols and writes an estimate that differs from symbol to
 /// symbol into the reference's channel_estimate; 23.5 has no field for the offset, so the last {cfo_hz, rho} are kept for last_cfo_hz() / last_cfo_rho().
+/// \c time: what becomes of the DM-RS symbols of a slot. \c average (the default, the reference's rule) fits one channel to all of them;
+/// \c interpolate and \c line go through miphy_dmrs_pusch_estimate_tv_batch, which compensates the offset too, keeps the fits of the DM-RS symbols
+/// apart and blends them in time (a polygon through them, or one least-squares line) for a channel that changes within the slot; the share of the
+/// DM-RS energy the average does not explain is kept for last_variation().
+enum class time_strategy { average, interpolate, line };
 class dmrs_pusch_estimator_hip : public srsran::dmrs_pusch_estimator
 {
 public:
-  explicit dmrs_pusch_estimator_hip(std::shared_ptr<context> c, bool separate_layers = false, bool compensate_cfo = false) :
-    c(std::move(c)), separate_layers(separate_layers), compensate_cfo(compensate_cfo)
+  explicit dmrs_pusch_estimator_hip(std::shared_ptr<context> c, bool separate_layers = false, bool compensate_cfo = false,
+                                    time_strategy time = time_strategy::average) :
+    c(std::move(c)), separate_layers(separate_layers), compensate_cfo(compensate_cfo), time(time)
   {
+  }
+  /// The variation of (rx port, layer) of the last estimate() with a \c time strategy other than average (0 before the first one), and the largest
+  /// of them: what a scheduler reads to tell a moving UE from a still one.
+  float last_variation(unsigned port, unsigned layer) const { return port < 4 && layer < nof_var_layers ? variation[port * nof_var_layers + layer] : 0.F; }
+  float last_variation() const
+  {
+    float v = 0.F;
+    for (float x : variation)
+      v = x > v ? x : v;
+    return v;
   }
   /// The offset in Hz and the normalised correlation of the last estimate() with \c compensate_cfo (0 before the first one).
   float last_cfo_hz() const { return cfo[0]; }
@@ -876,7 +892,19 @@ public:
       }
     }
     c->h2d(d_ce, ce_host.data(), ce_n * sizeof(srsran::cf_t));
-    if (compensate_cfo) {
+    if (time != time_strategy::average) {
+      miphy_pusch_chest_tv_job vj = {};
+      vj.base.base                = j;
+      vj.time_mode                = time == time_strategy::interpolate ? MIPHY_TIME_INTERPOLATE : MIPHY_TIME_LINE;
+      auto* d_cfo                 = static_cast<float*>(c->buf(3, (2 + 16) * sizeof(float)));
+      context::check(miphy_dmrs_pusch_estimate_tv_batch(c->ctx, &vj, 0, 1, d_g, d_ce, d_sc, d_cfo, d_cfo + 2, c->stream), "dmrs_pusch_estimate_tv");
+      float out[2 + 16] = {};
+      c->d2h(out, d_cfo, (2 + nports * nl) * sizeof(float));
+      cfo[0] = out[0], cfo[1] = out[1];
+      nof_var_layers = nl;
+      for (unsigned k = 0; k != 16; ++k)
+        variation[k] = k < nports * nl ? out[2 + k] : 0.F;
+    } else if (compensate_cfo) {
       miphy_pusch_chest_cfo_job fj = {};
       fj.base                      = j;
       auto* d_cfo                  = static_cast<float*>(c->buf(3, 2 * sizeof(float)));
@@ -909,7 +937,9 @@ public:
 private:
   std::shared_ptr<context>  c;
   bool                      separate_layers, compensate_cfo;
-  float                     cfo[2] = {0.F, 0.F};
+  time_strategy             time;
+  float                     cfo[2] = {0.F, 0.F}, variation[16] = {};
+  unsigned                  nof_var_layers = 1;
   std::vector<srsran::cf_t> host, ce_host;
 };
 
@@ -3776,19 +3806,24 @@ MIPHY_SIMPLE_FACTORY(ldpc_rate_matcher_factory_hip, ldpc_rate_matcher_factory, l
 MIPHY_SIMPLE_FACTORY(ldpc_rate_dematcher_factory_hip, ldpc_rate_dematcher_factory, ldpc_rate_dematcher, ldpc_rate_dematcher_hip)
 MIPHY_SIMPLE_FACTORY(pdsch_encoder_factory_hip, pdsch_encoder_factory, pdsch_encoder, pdsch_encoder_hip)
 MIPHY_SIMPLE_FACTORY(pusch_decoder_factory_hip, pusch_decoder_factory, pusch_decoder, pusch_decoder_hip)
-/// \c separate_layers and \c compensate_cfo as in dmrs_pusch_estimator_hip.
+/// \c separate_layers, \c compensate_cfo and \c time as in dmrs_pusch_estimator_hip.
 class dmrs_pusch_estimator_factory_hip : public srsran::dmrs_pusch_estimator_factory
 {
 public:
-  explicit dmrs_pusch_estimator_factory_hip(std::shared_ptr<context> c, bool separate_layers = false, bool compensate_cfo = false) :
-    c(std::move(c)), separate_layers(separate_layers), compensate_cfo(compensate_cfo)
+  explicit dmrs_pusch_estimator_factory_hip(std::shared_ptr<context> c, bool separate_layers = false, bool compensate_cfo = false,
+                                            time_strategy time = time_strategy::average) :
+    c(std::move(c)), separate_layers(separate_layers), compensate_cfo(compensate_cfo), time(time)
   {
   }
-  std::unique_ptr<srsran::dmrs_pusch_estimator> create() override { return std::make_unique<dmrs_pusch_estimator_hip>(c, separate_layers, compensate_cfo); }
+  std::unique_ptr<srsran::dmrs_pusch_estimator> create() override
+  {
+    return std::make_unique<dmrs_pusch_estimator_hip>(c, separate_layers, compensate_cfo, time);
+  }
 
 private:
   std::shared_ptr<context> c;
   bool                     separate_layers, compensate_cfo;
+  time_strategy            time;
 };
 MIPHY_SIMPLE_FACTORY(pdcch_encoder_factory_hip, pdcch_encoder_factory, pdcch_encoder, pdcch_encoder_hip)
 MIPHY_SIMPLE_FACTORY(pusch_demodulator_factory_hip, pusch_demodulator_factory, pusch_demodulator, pusch_demodulator_hip)
@@ -3836,9 +3871,10 @@ inline std::shared_ptr<srsran::pusch_decoder_factory> create_pusch_decoder_facto
   return std::make_shared<pusch_decoder_factory_hip>(std::move(c));
 }
 inline std::shared_ptr<srsran::dmrs_pusch_estimator_factory> create_dmrs_pusch_estimator_factory_hip(std::shared_ptr<context> c, bool separate_layers = false,
-                                                                                                     bool compensate_cfo = false)
+                                                                                                     bool compensate_cfo = false,
+                                                                                                     time_strategy time = time_strategy::average)
 {
-  return std::make_shared<dmrs_pusch_estimator_factory_hip>(std::move(c), separate_layers, compensate_cfo);
+  return std::make_shared<dmrs_pusch_estimator_factory_hip>(std::move(c), separate_layers, compensate_cfo, time);
 }
 inline std::shared_ptr<srsran::pdcch_encoder_factory> create_pdcch_encoder_factory_hip(std::shared_ptr<context> c)
 {

@@ -14,7 +14,8 @@
 // covariance across the ports: miphy_pusch_noise_covariance_batch. It takes the helpers and the job rules from here and writes no estimate.
 // Behind them, cfo_corr_kernel and chest_cfo_kernel (workgroup per (job, rx port, CDM group), two launches): chest_layers_kernel for 1..4 layers with a
 // carrier frequency offset estimated from consecutive DM-RS symbols, taken out of the DM-RS elements and put back per OFDM symbol:
-// miphy_dmrs_pusch_estimate_cfo_batch.
+// miphy_dmrs_pusch_estimate_cfo_batch. chest_tv_kernel takes chest_cfo_kernel's place where the channel changes within the slot: the fits of the DM-RS
+// symbols are kept apart and interpolated in time: miphy_dmrs_pusch_estimate_tv_batch.
 // What they share stands once, in front of them: the thread count, the LDS layout (chest_lds, which also sizes the launches), the job rules
 // (chest_job_rule: chest_validate on the host, device-resident jobs of the layered entry on the device) and the chest_* helpers. What differs
 // stays in the kernels: pilot ownership, despreading, the two-parameter noise fit, external pilots, hopping. Behind the kernels: chest_prologue
@@ -837,6 +838,32 @@ __host__ __device__ inline bool cfo_job_ok(const miphy_pusch_chest_cfo_job& j)
   return chest_job_rule(j.base, false) == CHEST_RULE_NONE && j.base.ce_compact == 0;
 }
 
+__host__ __device__ inline bool tv_job_ok(const miphy_pusch_chest_tv_job& j)
+{
+  bool ok = cfo_job_ok(j.base) && (j.time_mode == MIPHY_TIME_INTERPOLATE || j.time_mode == MIPHY_TIME_LINE);
+  for (int i = 0; i < 7; ++i)
+    ok = ok && j.reserved[i] == 0;
+  return ok;
+}
+
+// What cfo_corr_kernel sees of either record: the rules it is held to and the CFO record in front.
+__host__ __device__ inline bool cfo_record_ok(const miphy_pusch_chest_cfo_job& j)
+{
+  return cfo_job_ok(j);
+}
+__host__ __device__ inline bool cfo_record_ok(const miphy_pusch_chest_tv_job& j)
+{
+  return tv_job_ok(j);
+}
+__host__ __device__ inline const miphy_pusch_chest_cfo_job& cfo_record(const miphy_pusch_chest_cfo_job& j)
+{
+  return j;
+}
+__host__ __device__ inline const miphy_pusch_chest_cfo_job& cfo_record(const miphy_pusch_chest_tv_job& j)
+{
+  return j.base;
+}
+
 // tau_l - tau_ref in samples at 2048 * 2^mu * 15 kHz, tau the start of the useful part of an OFDM symbol of the slot (normal cyclic prefix): a
 // symbol lasts 2048 + 144 samples, 16 * 2^mu more where (14 slot + j) mod (7 * 2^mu) = 0 (the rule of miphy_ofdm_symbol_size).
 __host__ __device__ inline int cfo_symbol_delta(unsigned mu, unsigned slot, int ref, int l)
@@ -873,8 +900,72 @@ __device__ __forceinline__ void cfo_fetch(float2 (&xq)[CL_PK][2][4], const float
   }
 }
 
+// cfo_hz and rho of the job (blockIdx.x) into cfo_s[0..1] from the partials of every (port, layer, gap) (thread 0, in a fixed order: every workgroup of the job gets
+// the same bits), then exp(+j phi_l) of the fourteen symbols into ph[]; returns cfo_hz. The text of chest_cfo_kernel, which keeps its own: called from here the compiler
+// fuses three of that kernel's multiply-adds differently, and its bytes are pinned. Holds one barrier; ph[] may be read after the caller's next one.
+__device__ __forceinline__ float cfo_offset_phasors(const miphy_pusch_chest_job& job, const float* parts, const int (&dsym)[4], int nds, int L, float2* ph, float* cfo_s,
+                                                   int tid)
+{
+  if (tid == 0) {
+    cplx  c[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+    float e[3] = {0.f, 0.f, 0.f};
+    const float* pj = parts + (size_t)blockIdx.x * CFO_JOB_FLOATS;
+    for (int p = 0; p < (nds >= 2 ? (int)job.nof_rx_ports : 0); ++p)
+      for (int l = 0; l < L; ++l)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          if (d >= nds - 1)
+            continue;
+          const float4 v = *reinterpret_cast<const float4*>(pj + ((p * 4 + l) * 3 + d) * CFO_PART_FLOATS);
+          c[d].x += v.x, c[d].y += v.y, e[d] += v.z;
+        }
+    float num = 0.f, sum_c = 0.f, sum_e = 0.f;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      if (d >= nds - 1)
+        continue;
+      const float mag = sqrtf(c[d].x * c[d].x + c[d].y * c[d].y);
+      const int   ds  = cfo_symbol_delta(job.numerology, job.slot_in_frame, dsym[d], dsym[d + 1]);
+      if (mag > 0.f)
+        num += mag * (atan2f(c[d].y, c[d].x) * 0.15915494309189533577f) * (cfo_sample_rate(job.numerology) / (float)ds);
+      sum_c += mag, sum_e += e[d];
+    }
+    const bool have = sum_c > 0.f;
+    cfo_s[0] = have ? num / sum_c : 0.f;
+    cfo_s[1] = have ? sum_c / sum_e : 0.f;
+  }
+  __syncthreads();
+  const float cfo_hz = cfo_s[0];
+  if (tid < 14) {
+    float sn, cs;
+    sincospif(2.f * cfo_hz * ((float)cfo_symbol_delta(job.numerology, job.slot_in_frame, dsym[0], tid) / cfo_sample_rate(job.numerology)), &sn, &cs);
+    ph[tid] = make_float2(cs, sn);
+  }
+  return cfo_hz;
+}
+
+// x_d exp(-j phi_d) on the fetched DM-RS elements.
+__device__ __forceinline__ void cfo_derotate(float2 (&xq)[CL_PK][2][4], const float2* ph, const int (&dsym)[4], int nds)
+{
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    if (d >= nds)
+      continue;
+    const float2 r = ph[dsym[d]];
+#pragma unroll
+    for (int kk = 0; kk < CL_PK; ++kk)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const float2 x = xq[kk][e][d];
+        xq[kk][e][d]   = make_float2(x.x * r.x + x.y * r.y, x.y * r.x - x.x * r.y);
+      }
+  }
+}
+
 // Workgroup per (job, rx port, CDM group), the grid of chest_layers_kernel; no IDFT buffer and no LS vector, so 2.3 KB of LDS.
-__global__ void __launch_bounds__(CHEST_THREADS) cfo_corr_kernel(const miphy_pusch_chest_cfo_job* __restrict__ jobs, const gold_jump* __restrict__ gj,
+// JOB: miphy_pusch_chest_cfo_job or miphy_pusch_chest_tv_job (the stride of the records and the rules differ, nothing else).
+template <class JOB>
+__global__ void __launch_bounds__(CHEST_THREADS) cfo_corr_kernel(const JOB* __restrict__ jobs, const gold_jump* __restrict__ gj,
                                                                  const float2* __restrict__ grid, float* __restrict__ parts, int ports_dim)
 {
   __shared__ uint32_t cbits[4 * 104];
@@ -882,11 +973,11 @@ __global__ void __launch_bounds__(CHEST_THREADS) cfo_corr_kernel(const miphy_pus
   __shared__ uint16_t prb_of[276];
   __shared__ float    red[CHEST_THREADS / 64];
   const int tid = threadIdx.x;
-  const miphy_pusch_chest_cfo_job& jm = jobs[blockIdx.x];
+  const miphy_pusch_chest_cfo_job& jm = cfo_record(jobs[blockIdx.x]);
   const int port = blockIdx.y % ports_dim, grp = blockIdx.y / ports_dim;
   const int L    = jm.base.nof_tx_layers;
   // (uniform) a job without this port or group; a device-resident job that breaks a rule
-  if (port >= jm.base.nof_rx_ports || 2 * grp >= L || !cfo_job_ok(jm))
+  if (port >= jm.base.nof_rx_ports || 2 * grp >= L || !cfo_record_ok(jobs[blockIdx.x]))
     return;
   const miphy_pusch_chest_job job = load_words(&jm.base);
   int       dsym[4];
@@ -1059,20 +1150,7 @@ __global__ void __launch_bounds__(CHEST_THREADS, 4) chest_cfo_kernel(const miphy
     float* o = cfo_out + jm.cfo_offset;
     o[0] = cfo_hz, o[1] = cfo_s[1];
   }
-  // x_d exp(-j phi_d)
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    if (d >= nds)
-      continue;
-    const float2 r = ph[dsym[d]];
-#pragma unroll
-    for (int kk = 0; kk < CL_PK; ++kk)
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const float2 x = xq[kk][e][d];
-        xq[kk][e][d]   = make_float2(x.x * r.x + x.y * r.y, x.y * r.x - x.x * r.y);
-      }
-  }
+  cfo_derotate(xq, ph, dsym, nds); // x_d exp(-j phi_d)
 
   // ---- from here chest_layers_kernel: least squares against layer 0's pilot, despreading, EPRE, RSRP
   const float ts = 1.0f / ((float)nds * beta);
@@ -1161,6 +1239,282 @@ __global__ void __launch_bounds__(CHEST_THREADS, 4) chest_cfo_kernel(const miphy
   // ---- side-band scalars, per layer; the noise variance is the group's
   if (tid < nlay)
     chest_scalars(scalars, job, port, 2 * grp + tid, tid ? rsrp[1] : rsrp[0], epre, noise_var, tid ? ta[1] : ta[0], true, true);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// A channel that changes within the slot (miphy_dmrs_pusch_estimate_tv_batch; include/miphy.h has the arithmetic). chest_cfo_kernel up to the
+// derotated DM-RS elements; then the fits of the DM-RS symbols are kept apart, one vector per symbol in LDS, and blended in time with the weights
+// w[l][d]. Frequency interpolation and the time blend are both linear, so a thread interpolates the nds vectors once per subcarrier, keeps the nds
+// values in registers and runs the loop over the symbols from them: no barrier in the store loop, every store 512 consecutive columns of one row.
+// LDS: the fit vectors (4 x 1 650 pilots, 52.8 KB) lie over the IDFT buffer and the LS vector of chest_lds, which are idle until the time
+// alignment; the time mean waits in registers until the fits are dead and then takes the LS vector's place. 55.5 KB: two workgroups on a CU.
+struct tv_lds {
+  static constexpr size_t FITS_BYTES = 4 * MAX_PILOTS * sizeof(cplx), TAIL = chest_lds::BYTES - chest_lds::CBITS, PH = FITS_BYTES + TAIL,
+                          WT = PH + CFO_LDS_BYTES, BYTES = WT + 14 * 4 * sizeof(float);
+  static_assert(FITS_BYTES >= chest_lds::CBITS && FITS_BYTES % 16 == 0 && WT % 16 == 0, "the IDFT buffer and the LS vector lie inside the fit vectors");
+  cplx*     fits;   // nds vectors of np fits, vector d at d * np; s_a / s_b interleaved like chest_lds::lse
+  cplx*     fbuf;   // over fits: the IDFT buffer
+  cplx*     lse;    // over fits, behind fbuf: the time mean, for the time alignment
+  uint32_t* cbits;  // from here the arrays of chest_lds
+  uint64_t* rbm;
+  uint16_t* prb_of;
+  float*    red;
+  float2*   ph;     // 14: exp(+j phi_l)
+  float*    cfo_s;  // cfo_hz, rho
+  float*    wt;     // 14 x 4: w[l][d]
+  __device__ __forceinline__ explicit tv_lds(unsigned char* s)
+    : fits(reinterpret_cast<cplx*>(s)), fbuf(reinterpret_cast<cplx*>(s)), lse(reinterpret_cast<cplx*>(s + chest_lds::LSE)),
+      cbits(reinterpret_cast<uint32_t*>(s + FITS_BYTES)), rbm(reinterpret_cast<uint64_t*>(s + FITS_BYTES + (chest_lds::RBM - chest_lds::CBITS))),
+      prb_of(reinterpret_cast<uint16_t*>(s + FITS_BYTES + (chest_lds::PRB_OF - chest_lds::CBITS))),
+      red(reinterpret_cast<float*>(s + FITS_BYTES + (chest_lds::RED - chest_lds::CBITS))), ph(reinterpret_cast<float2*>(s + PH)),
+      cfo_s(reinterpret_cast<float*>(s + PH) + 28), wt(reinterpret_cast<float*>(s + WT))
+  {
+  }
+};
+
+// w[l][0..3] of OFDM symbol l, from differences of the symbol times only (samples are whole numbers below 2^24: exact in single precision).
+__device__ __forceinline__ float4 tv_weights(const miphy_pusch_chest_job& job, const int (&dsym)[4], int nds, int mode, int l)
+{
+  float w[4] = {1.f, 0.f, 0.f, 0.f};
+  if (nds >= 2 && mode == MIPHY_TIME_INTERPOLATE) {
+    int j = 0;
+#pragma unroll
+    for (int d = 1; d < 3; ++d)
+      if (d < nds - 1 && dsym[d] <= l)
+        j = d;
+    int lo = dsym[0], hi = dsym[1];
+#pragma unroll
+    for (int d = 1; d < 3; ++d)
+      if (d == j)
+        lo = dsym[d], hi = dsym[d + 1];
+    const float u = (float)cfo_symbol_delta(job.numerology, job.slot_in_frame, lo, l) / (float)cfo_symbol_delta(job.numerology, job.slot_in_frame, lo, hi);
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      w[d] = d == j ? 1.f - u : (d == j + 1 ? u : 0.f);
+  } else if (nds >= 2) {
+    float t[4], tm = 0.f, q = 0.f;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      t[d] = d < nds ? (float)cfo_symbol_delta(job.numerology, job.slot_in_frame, dsym[0], dsym[d]) : 0.f;
+      tm += t[d];
+    }
+    tm /= (float)nds;
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      if (d < nds)
+        q += (t[d] - tm) * (t[d] - tm);
+    const float tl = (float)cfo_symbol_delta(job.numerology, job.slot_in_frame, dsym[0], l) - tm;
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      w[d] = d < nds ? 1.f / (float)nds + tl * (t[d] - tm) / q : 0.f;
+  }
+  return make_float4(w[0], w[1], w[2], w[3]);
+}
+
+__global__ void __launch_bounds__(CHEST_THREADS, 4) chest_tv_kernel(const miphy_pusch_chest_tv_job* __restrict__ jobs,
+                                                                    const gold_jump* __restrict__ gj,
+                                                                    const cplx* __restrict__ tw,
+                                                                    const float2* __restrict__ grid,
+                                                                    float2* __restrict__ ce_out,
+                                                                    float* __restrict__ scalars,
+                                                                    const float* __restrict__ parts,
+                                                                    float* __restrict__ cfo_out,
+                                                                    float* __restrict__ var_out,
+                                                                    int ports_dim) // blockIdx.y = CDM group * ports_dim + port
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const tv_lds  lds(smem);
+  constexpr int nt = CHEST_THREADS;
+  const int     tid = threadIdx.x;
+  const miphy_pusch_chest_tv_job& jm = jobs[blockIdx.x];
+  const int port = blockIdx.y % ports_dim, grp = blockIdx.y / ports_dim;
+  const int L    = jm.base.base.nof_tx_layers;
+  // (uniform) a job without this port or group; a device-resident job that breaks a rule
+  if (port >= jm.base.base.nof_rx_ports || 2 * grp >= L || !tv_job_ok(jm))
+    return;
+  const miphy_pusch_chest_job job = load_words(&jm.base.base);
+  const int  mode = jm.time_mode;
+  const bool pair = 2 * grp + 1 < L; // both layers of the group are present
+  const int  nlay = pair ? 2 : 1;
+  const int  nprb_grid = job.grid_nof_prb, nsc = nprb_grid * 12;
+  const int  first = job.first_symbol, nsymb_out = first + job.nof_symbols;
+  int        dsym[4];
+  const int  nds  = chest_dmrs_symbols(job.symbols_mask, first, nsymb_out, dsym);
+  const int  nprb = chest_prb_list(jm.base.base.rb_mask, nprb_grid, lds.rbm, lds.prb_of, tid);
+  const int  np = nprb * 6, npairs = nprb * 3;
+  const float beta = job.scaling;
+  float2      xq[CL_PK][2][4];
+  cfo_fetch(xq, chest_port_grid(grid, job, port), lds.prb_of, dsym, nds, npairs, nsc, grp, tid);
+
+  // ---- the offset and the phasors as chest_cfo_kernel, the time weights next to them
+  const float cfo_hz = cfo_offset_phasors(job, parts, dsym, nds, L, lds.ph, lds.cfo_s, tid);
+  if (tid < 14)
+    *reinterpret_cast<float4*>(lds.wt + 4 * tid) = tv_weights(job, dsym, nds, mode, tid);
+  uint32_t c_init[4];
+  chest_c_init(job, dsym, nds, c_init);
+  gold_bits_block(*reinterpret_cast<const gold_tables*>(gj), c_init[0], c_init[1], c_init[2], c_init[3], nds, 12 * nprb_grid, lds.cbits, tid); // (barrier: ph[], wt[])
+  if (tid == 0 && port == 0 && grp == 0) {
+    float* o = cfo_out + jm.base.cfo_offset;
+    o[0] = cfo_hz, o[1] = lds.cfo_s[1];
+  }
+  cfo_derotate(xq, lds.ph, dsym, nds); // x_d exp(-j phi_d)
+
+  // ---- the fit of every DM-RS symbol on its own: least squares against layer 0's pilot, despreading; the time mean, EPRE, RSRP and the energy the
+  // mean leaves over. S[e]: both layers present, S_a and S_b of the pair; a layer alone, its z on the two pilots of the pair.
+  const float ib = 1.0f / beta, inds = 1.0f / (float)nds;
+  cplx        mean[CL_PK][2];
+  float       epre_acc = 0.f, r_acc[2] = {0.f, 0.f}, dev_acc[2] = {0.f, 0.f}, en_acc[2] = {0.f, 0.f};
+#pragma unroll
+  for (int kk = 0; kk < CL_PK; ++kk) {
+    const int m = tid + kk * nt;
+    mean[kk][0] = mean[kk][1] = {0.f, 0.f};
+    if (m >= npairs)
+      continue;
+    const int gp0 = lds.prb_of[m / 3] * 6 + 2 * (m % 3);
+    cplx      S[4][2];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      S[d][0] = S[d][1] = {0.f, 0.f};
+      if (d >= nds)
+        continue;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const cplx   p = chest_qpsk_pilot(lds.cbits, d, gp0 + e);
+        const float2 x = xq[kk][e][d];
+        S[d][e]        = {(x.x * p.x + x.y * p.y) * ib, (x.y * p.x - x.x * p.y) * ib};
+        epre_acc += x.x * x.x + x.y * x.y;
+      }
+      if (pair) {
+        const cplx sa = {(S[d][0].x + S[d][1].x) * 0.5f, (S[d][0].y + S[d][1].y) * 0.5f}, sb = {(S[d][0].x - S[d][1].x) * 0.5f, (S[d][0].y - S[d][1].y) * 0.5f};
+        S[d][0] = sa, S[d][1] = sb;
+      }
+      lds.fits[d * np + 2 * m] = S[d][0], lds.fits[d * np + 2 * m + 1] = S[d][1];
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+        mean[kk][e] = cadd(mean[kk][e], S[d][e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      mean[kk][e] = {mean[kk][e].x * inds, mean[kk][e].y * inds};
+      r_acc[e] += mean[kk][e].x * mean[kk][e].x + mean[kk][e].y * mean[kk][e].y;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        if (d >= nds)
+          continue;
+        const cplx dv = {S[d][e].x - mean[kk][e].x, S[d][e].y - mean[kk][e].y};
+        dev_acc[e] += dv.x * dv.x + dv.y * dv.y;
+        en_acc[e] += S[d][e].x * S[d][e].x + S[d][e].y * S[d][e].y;
+      }
+    }
+  }
+  if (!pair) // a layer alone: the sums over its even and odd pilots are one sum
+    r_acc[0] += r_acc[1], dev_acc[0] += dev_acc[1], en_acc[0] += en_acc[1];
+  const float epre    = block_sum(epre_acc, lds.red, tid) / (float)(np * nds);
+  const float rs_norm = beta * beta / (float)(pair ? npairs : np);
+  float       rsrp[2] = {0.f, 0.f}, var[2] = {0.f, 0.f};
+#pragma unroll
+  for (int l = 0; l < 2; ++l) {
+    if (l >= nlay) // (uniform)
+      continue;
+    rsrp[l] = block_sum(r_acc[l], lds.red, tid) * rs_norm;
+    const float dev = block_sum(dev_acc[l], lds.red, tid), en = block_sum(en_acc[l], lds.red, tid);
+    var[l] = (nds >= 2 && en > 0.f) ? dev / en : 0.f;
+  }
+  __syncthreads(); // fits[]
+
+  // ---- frequency interpolation of every fit vector, once per subcarrier; then every OFDM symbol from registers: the blend in time, the symbol's phasor
+  const int sh = pair ? 2 : 1, off = pair ? 1 + grp : grp, ninp = pair ? npairs : np;
+  for (int l = 0; l < nlay; ++l) {
+    float2* dst0 = chest_ce_rows(ce_out, job, 2 * grp + l, port);
+    for (int k = tid; k < nprb * 12; k += nt) {
+      cplx v[4];
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        v[d] = {0.f, 0.f};
+        if (d >= nds)
+          continue;
+        const cplx* f      = lds.fits + d * np;
+        const auto  anchor = [&](int i) -> cplx { return pair ? f[2 * i + l] : f[i]; };
+        v[d]               = chest_interpolate<false>(anchor, k, sh, off, ninp);
+      }
+      const size_t col = (size_t)lds.prb_of[k / 12] * 12 + (k % 12);
+      for (int sy = first; sy < nsymb_out; ++sy) {
+        const float4 w = *reinterpret_cast<const float4*>(lds.wt + 4 * sy);
+        const float2 r = lds.ph[sy];
+        const cplx   a = {w.x * v[0].x + w.y * v[1].x + w.z * v[2].x + w.w * v[3].x, w.x * v[0].y + w.y * v[1].y + w.z * v[2].y + w.w * v[3].y};
+        dst0[(size_t)sy * nsc + col] = make_float2(a.x * r.x - a.y * r.y, a.x * r.y + a.y * r.x);
+      }
+    }
+  }
+
+  // ---- noise against the fit in time: F_d = sum_d' w[dsym[d]][d'] S_d', its per-PRB means predict the observations of DM-RS symbol d
+  float noise_var = 0.001f * epre; // convert_dB_to_power(-30) * epre
+  if (nds >= 2) {
+    float noise_acc = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < CL_PK; ++kk) {
+      const int m = tid + kk * nt;
+      if (m >= npairs)
+        continue;
+      const int b = (m / 3) * 6;
+      cplx      ea[4], eo[4]; // per-PRB sums of the even and odd entries of every fit vector
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        ea[d] = eo[d] = {0.f, 0.f};
+        if (d >= nds)
+          continue;
+        const cplx* f = lds.fits + d * np + b;
+        ea[d] = cadd(cadd(f[0], f[2]), f[4]), eo[d] = cadd(cadd(f[1], f[3]), f[5]);
+      }
+      const int gp0 = lds.prb_of[m / 3] * 6 + 2 * (m % 3);
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        if (d >= nds)
+          continue;
+        const float4 w  = *reinterpret_cast<const float4*>(lds.wt + 4 * dsym[d]);
+        const cplx   fa = {w.x * ea[0].x + w.y * ea[1].x + w.z * ea[2].x + w.w * ea[3].x, w.x * ea[0].y + w.y * ea[1].y + w.z * ea[2].y + w.w * ea[3].y};
+        const cplx   fo = {w.x * eo[0].x + w.y * eo[1].x + w.z * eo[2].x + w.w * eo[3].x, w.x * eo[0].y + w.y * eo[1].y + w.z * eo[2].y + w.w * eo[3].y};
+        cplx         ma, mb; // a layer alone: the mean of its six, no second parameter
+        if (pair)
+          ma = {fa.x / 3.f, fa.y / 3.f}, mb = {fo.x / 3.f, fo.y / 3.f};
+        else
+          ma = {(fa.x + fo.x) / 6.f, (fa.y + fo.y) / 6.f}, mb = {0.f, 0.f};
+        const cplx h[2] = {{(ma.x + mb.x) * -beta, (ma.y + mb.y) * -beta}, {(ma.x - mb.x) * -beta, (ma.y - mb.y) * -beta}};
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const cplx r = chest_residual_at(xq[kk][e][d], h[e], chest_qpsk_pilot(lds.cbits, d, gp0 + e));
+          noise_acc += r.x * r.x + r.y * r.y;
+        }
+      }
+    }
+    const int fitted = mode == MIPHY_TIME_INTERPOLATE ? nds : 2; // parameters in time per layer and PRB (nds >= 2 here)
+    noise_var        = block_sum(noise_acc, lds.red, tid) / (float)nprb / (float)(6 * nds - nlay * fitted);
+  }
+
+  // ---- the fits are dead: the time mean takes the place of the LS vector, and from here chest_layers_kernel's time alignment per layer
+  __syncthreads();
+#pragma unroll
+  for (int kk = 0; kk < CL_PK; ++kk) {
+    const int m = tid + kk * nt;
+    if (m < npairs)
+      lds.lse[2 * m] = mean[kk][0], lds.lse[2 * m + 1] = mean[kk][1];
+  }
+  float ta[2] = {0.f, 0.f};
+  for (int l = 0; l < nlay; ++l) {
+    chest_clear_idft(lds.fbuf, tid);
+    __syncthreads(); // (lse[] too)
+    for (int i = tid; i < np; i += nt)
+      lds.fbuf[fpad(lds.prb_of[i / 6] * 12 + 2 * (i % 6) + grp)] = pair ? lds.lse[(i & ~1) + l] : lds.lse[i];
+    __syncthreads();
+    fft4096_lds<true>(lds.fbuf, tw, tid);
+    ta[l] = chest_ta_peak(lds.fbuf, lds.red, tid);
+  }
+
+  // ---- side-band scalars and the variation, per layer; the noise variance is the group's
+  if (tid < nlay) {
+    chest_scalars(scalars, job, port, 2 * grp + tid, tid ? rsrp[1] : rsrp[0], epre, noise_var, tid ? ta[1] : ta[0], true, true);
+    var_out[jm.var_offset + (size_t)port * L + 2 * grp + tid] = tid ? var[1] : var[0];
+  }
 }
 
 } // namespace
@@ -1308,30 +1662,30 @@ extern "C" int miphy_dmrs_pusch_estimate_layers_batch(miphy_ctx* ctx, const miph
   return layered ? chest_layers_enqueue(ctx, d_jobs, n, max_ports, max_layers, grid, ce, scalars, s) : MIPHY_OK;
 }
 
-// The layered estimator with the carrier frequency offset estimated and compensated: cfo_corr_kernel, then chest_cfo_kernel, on the grid of
-// chest_layers_kernel; jobs on one layer run there too (a layer alone in its group). The partials live in a workspace of the context.
-extern "C" int miphy_dmrs_pusch_estimate_cfo_batch(miphy_ctx* ctx, const miphy_pusch_chest_cfo_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
-                                                   float* ce, float* scalars, float* cfo, void* stream)
+// The rules of the estimators behind cfo_corr_kernel on host jobs: those of the layered estimator on base_of(job), and an estimate per symbol.
+template <class Job, class Base>
+static int chest_cfo_validate(const Job* jobs, uint32_t n, Base&& base_of, const char* what, unsigned& max_ports, unsigned& max_layers)
 {
-  const char* what = "miphy_dmrs_pusch_estimate_cfo_batch";
-  unsigned    max_ports, max_layers;
-  int         rc = chest_prologue(what, ctx && jobs && grid && ce && scalars && cfo, n, UINT32_MAX, jobs_on_device, max_ports, max_layers,
-                                  [&](unsigned& mp, unsigned& ml) -> int {
-                            std::vector<miphy_pusch_chest_job> base(n);
-                            for (uint32_t i = 0; i < n; ++i)
-                              base[i] = jobs[i].base;
-                            const int r = chest_validate(base.data(), n, false, mp, ml, what);
-                            if (r)
-                              return r;
-                            for (uint32_t i = 0; i < n; ++i)
-                              MIPHY_REQUIRE(jobs[i].base.ce_compact == 0, "%s: job %u: the estimate differs from symbol to symbol, ce_compact must be 0", what, i);
-                            return (int)MIPHY_OK;
-                          });
-  if (rc || n == 0)
-    return rc;
-  hipStream_t s      = (hipStream_t)stream;
+  std::vector<miphy_pusch_chest_job> base(n);
+  for (uint32_t i = 0; i < n; ++i)
+    base[i] = base_of(jobs[i]);
+  const int r = chest_validate(base.data(), n, false, max_ports, max_layers, what);
+  if (r)
+    return r;
+  for (uint32_t i = 0; i < n; ++i)
+    MIPHY_REQUIRE(base[i].ce_compact == 0, "%s: job %u: the estimate differs from symbol to symbol, ce_compact must be 0", what, i);
+  return MIPHY_OK;
+}
+
+// The two launches of the estimators with a carrier frequency offset on staged jobs (records of job_bytes each, a miphy_pusch_chest_cfo_job in front):
+// cfo_corr_kernel, whose partials live in a workspace of the context, then the estimate kernel (var: chest_tv_kernel, else chest_cfo_kernel) on the
+// grid of chest_layers_kernel; jobs on one layer run there too (a layer alone in its group).
+static int chest_cfo_enqueue(miphy_ctx* ctx, const void* jobs, int jobs_on_device, size_t job_bytes, uint32_t n, unsigned max_ports, unsigned max_layers,
+                             const float* grid, float* ce, float* scalars, float* cfo, float* var, hipStream_t s)
+{
   const void* d_jobs = nullptr;
-  if ((rc = miphy_stage_descs(ctx, jobs, jobs_on_device, sizeof(miphy_pusch_chest_cfo_job) * (size_t)n, s, &d_jobs)))
+  int         rc     = miphy_stage_descs(ctx, jobs, jobs_on_device, job_bytes * (size_t)n, s, &d_jobs);
+  if (rc)
     return rc;
   void* parts = nullptr;
   if ((rc = miphy_get_workspace(ctx, MIPHY_WS_GENERAL, sizeof(float) * CFO_JOB_FLOATS * (size_t)n, &parts)))
@@ -1341,13 +1695,57 @@ extern "C" int miphy_dmrs_pusch_estimate_cfo_batch(miphy_ctx* ctx, const miphy_p
   if ((rc = chest_resources(ctx, &tw, &gold)))
     return rc;
   const dim3 blocks(n, max_ports * (max_layers > 2 ? 2 : 1));
-  hipLaunchKernelGGL(cfo_corr_kernel, blocks, dim3(CHEST_THREADS), 0, s, (const miphy_pusch_chest_cfo_job*)d_jobs, gold, (const float2*)grid, (float*)parts,
-                     (int)max_ports);
-  MIPHY_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(chest_cfo_kernel, blocks, dim3(CHEST_THREADS), chest_lds::BYTES + CFO_LDS_BYTES, s, (const miphy_pusch_chest_cfo_job*)d_jobs, gold, tw,
-                     (const float2*)grid, (float2*)ce, scalars, (const float*)parts, cfo, (int)max_ports);
+  if (var) {
+    hipLaunchKernelGGL(cfo_corr_kernel<miphy_pusch_chest_tv_job>, blocks, dim3(CHEST_THREADS), 0, s, (const miphy_pusch_chest_tv_job*)d_jobs, gold,
+                       (const float2*)grid, (float*)parts, (int)max_ports);
+    MIPHY_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(chest_tv_kernel, blocks, dim3(CHEST_THREADS), tv_lds::BYTES, s, (const miphy_pusch_chest_tv_job*)d_jobs, gold, tw, (const float2*)grid,
+                       (float2*)ce, scalars, (const float*)parts, cfo, var, (int)max_ports);
+  } else {
+    hipLaunchKernelGGL(cfo_corr_kernel<miphy_pusch_chest_cfo_job>, blocks, dim3(CHEST_THREADS), 0, s, (const miphy_pusch_chest_cfo_job*)d_jobs, gold,
+                       (const float2*)grid, (float*)parts, (int)max_ports);
+    MIPHY_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(chest_cfo_kernel, blocks, dim3(CHEST_THREADS), chest_lds::BYTES + CFO_LDS_BYTES, s, (const miphy_pusch_chest_cfo_job*)d_jobs, gold, tw,
+                       (const float2*)grid, (float2*)ce, scalars, (const float*)parts, cfo, (int)max_ports);
+  }
   MIPHY_HIP_CHECK(hipGetLastError());
   return MIPHY_OK;
+}
+
+// The layered estimator with the carrier frequency offset estimated and compensated.
+extern "C" int miphy_dmrs_pusch_estimate_cfo_batch(miphy_ctx* ctx, const miphy_pusch_chest_cfo_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                                   float* ce, float* scalars, float* cfo, void* stream)
+{
+  const char* what = "miphy_dmrs_pusch_estimate_cfo_batch";
+  unsigned    max_ports, max_layers;
+  int         rc = chest_prologue(what, ctx && jobs && grid && ce && scalars && cfo, n, UINT32_MAX, jobs_on_device, max_ports, max_layers,
+                                  [&](unsigned& mp, unsigned& ml) -> int {
+                            return chest_cfo_validate(jobs, n, [](const miphy_pusch_chest_cfo_job& j) -> const miphy_pusch_chest_job& { return j.base; }, what, mp, ml);
+                          });
+  if (rc || n == 0)
+    return rc;
+  return chest_cfo_enqueue(ctx, jobs, jobs_on_device, sizeof(miphy_pusch_chest_cfo_job), n, max_ports, max_layers, grid, ce, scalars, cfo, nullptr, (hipStream_t)stream);
+}
+
+// The same for a channel that changes within the slot: the fits of the DM-RS symbols kept apart and interpolated in time (chest_tv_kernel).
+extern "C" int miphy_dmrs_pusch_estimate_tv_batch(miphy_ctx* ctx, const miphy_pusch_chest_tv_job* jobs, int jobs_on_device, uint32_t n, const float* grid,
+                                                  float* ce, float* scalars, float* cfo, float* var, void* stream)
+{
+  const char* what = "miphy_dmrs_pusch_estimate_tv_batch";
+  unsigned    max_ports, max_layers;
+  int         rc = chest_prologue(what, ctx && jobs && grid && ce && scalars && cfo && var, n, UINT32_MAX, jobs_on_device, max_ports, max_layers,
+                                  [&](unsigned& mp, unsigned& ml) -> int {
+                            const int r =
+                                chest_cfo_validate(jobs, n, [](const miphy_pusch_chest_tv_job& j) -> const miphy_pusch_chest_job& { return j.base.base; }, what, mp, ml);
+                            if (r)
+                              return r;
+                            for (uint32_t i = 0; i < n; ++i)
+                              MIPHY_REQUIRE(tv_job_ok(jobs[i]), "%s: job %u: time_mode must be MIPHY_TIME_INTERPOLATE or MIPHY_TIME_LINE, the reserved bytes 0", what, i);
+                            return (int)MIPHY_OK;
+                          });
+  if (rc || n == 0)
+    return rc;
+  return chest_cfo_enqueue(ctx, jobs, jobs_on_device, sizeof(miphy_pusch_chest_tv_job), n, max_ports, max_layers, grid, ce, scalars, cfo, var, (hipStream_t)stream);
 }
 
 extern "C" int miphy_dmrs_pusch_estimate_batch(miphy_ctx* ctx, const miphy_pusch_chest_job* jobs, int jobs_on_device, uint32_t n, const float* grid, float* ce,

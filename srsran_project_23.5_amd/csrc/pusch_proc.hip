@@ -7,7 +7,8 @@
 // with multiplexed UCI, miphy_ulsch_demultiplex_batch between the last two. One codeword on 1..4 layers goes through the layered stages, a
 // transform-precoded PUSCH (DFT-s-OFDM) through miphy_dmrs_pusch_estimate_tp_batch and miphy_pusch_demodulate_tp_batch, a layered PDU with MMSE-IRC
 // through the layered estimator, miphy_pusch_noise_covariance_batch and miphy_pusch_demodulate_layers_mmse_batch_ex. A layered PDU of a UE with a carrier
-// frequency offset goes through miphy_dmrs_pusch_estimate_cfo_batch, whose estimate differs from symbol to symbol and is kept per symbol.
+// frequency offset goes through miphy_dmrs_pusch_estimate_cfo_batch, whose estimate differs from symbol to symbol and is kept per symbol; one whose
+// channel changes within the slot through miphy_dmrs_pusch_estimate_tv_batch in its place.
 #include "miphy_ext.h"
 #include <cmath>
 #include <vector>
@@ -212,7 +213,8 @@ int pusch_batch_build(const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu*
 // checked before anything is enqueued (pusch_batch_build); the stages check their own rules again on the jobs built there.
 int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pusch_layers_pdu* lpdus, const miphy_pusch_tp_pdu* tpdus,
                      const miphy_pusch_mmse_pdu* mpdus, const miphy_pusch_uci* uci, uint32_t n, const float* grid, int8_t* harq_softbits, uint8_t* harq_msgs,
-                     uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results, float* scalars_out, int8_t* uci_llr_out, float* evm_out, float* cfo_out, hipStream_t s)
+                     uint8_t* harq_crc_ok, uint8_t* tb_out, miphy_pusch_result* results, float* scalars_out, int8_t* uci_llr_out, float* evm_out, float* cfo_out,
+                     uint32_t time_mode, float* var_out, hipStream_t s)
 {
   pusch_batch b;
   int         rc = pusch_batch_build(pdus, lpdus, tpdus, mpdus, uci, n, uci_llr_out != nullptr, cfo_out != nullptr, b);
@@ -242,6 +244,14 @@ int pusch_process_ex(miphy_ctx* ctx, const miphy_pusch_pdu* pdus, const miphy_pu
     if ((rc = miphy_pusch_noise_covariance_batch(ctx, b.nj.data(), 0, n, grid, d_cov, s)))
       return rc;
     if ((rc = miphy_pusch_demodulate_layers_mmse_batch_ex(ctx, b.mj.data(), 0, n, grid, d_ce, scalars_out, d_cov, d_llr, d_ph, d_evm, s)))
+      return rc;
+  } else if (lpdus && var_out) { // (layered PDUs only) the per-symbol estimate that follows the channel through the slot; the variation of PDU i at 16 i
+    std::vector<miphy_pusch_chest_tv_job> vj(n);
+    for (uint32_t i = 0; i < n; ++i)
+      vj[i] = {}, vj[i].base.base = b.cj[i], vj[i].base.cfo_offset = 2ull * i, vj[i].var_offset = 16ull * i, vj[i].time_mode = (uint8_t)time_mode;
+    if ((rc = miphy_dmrs_pusch_estimate_tv_batch(ctx, vj.data(), 0, n, grid, d_ce, scalars_out, cfo_out, var_out, s)))
+      return rc;
+    if ((rc = miphy_pusch_demodulate_layers_batch_ex(ctx, b.dj.data(), 0, n, grid, d_ce, scalars_out, d_llr, d_ph, d_evm, s)))
       return rc;
   } else if (lpdus && cfo_out) { // (layered PDUs only) the per-symbol estimate of the offset-compensating estimator, {cfo_hz, rho} of PDU i at 2 i
     std::vector<miphy_pusch_chest_cfo_job> fj(n);
@@ -315,7 +325,7 @@ extern "C" int miphy_pusch_process_layers_batch_ex(miphy_ctx* ctx, const miphy_p
   if (n == 0)
     return MIPHY_OK;
   return pusch_process_ex(ctx, nullptr, pdus, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out, nullptr,
-                          (hipStream_t)stream);
+                          0, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int miphy_pusch_process_layers_batch(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus, uint32_t n, const float* grid, int8_t* harq_softbits,
@@ -335,7 +345,7 @@ extern "C" int miphy_pusch_process_batch_ex(miphy_ctx* ctx, const miphy_pusch_pd
   if (n == 0)
     return MIPHY_OK;
   return pusch_process_ex(ctx, pdus, nullptr, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out, nullptr,
-                          (hipStream_t)stream);
+                          0, nullptr, (hipStream_t)stream);
 }
 
 // A transform-precoded PUSCH (DFT-s-OFDM), with multiplexed UCI and the EVM (include/miphy.h).
@@ -348,7 +358,7 @@ extern "C" int miphy_pusch_process_tp_batch_ex(miphy_ctx* ctx, const miphy_pusch
   if (n == 0)
     return MIPHY_OK;
   return pusch_process_ex(ctx, nullptr, nullptr, pdus, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out, nullptr,
-                          (hipStream_t)stream);
+                          0, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int miphy_pusch_process_tp_batch(miphy_ctx* ctx, const miphy_pusch_tp_pdu* pdus, uint32_t n, const float* grid, int8_t* harq_softbits,
@@ -370,7 +380,23 @@ extern "C" int miphy_pusch_process_layers_cfo_batch(miphy_ctx* ctx, const miphy_
   if (n == 0)
     return MIPHY_OK;
   return pusch_process_ex(ctx, nullptr, pdus, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
-                          cfo_out, (hipStream_t)stream);
+                          cfo_out, 0, nullptr, (hipStream_t)stream);
+}
+
+// The layered processor with the estimator that follows a channel through the slot in front (include/miphy.h).
+extern "C" int miphy_pusch_process_layers_tv_batch(miphy_ctx* ctx, const miphy_pusch_layers_pdu* pdus, const miphy_pusch_uci* uci, uint32_t n, const float* grid,
+                                                   int8_t* harq_softbits, uint8_t* harq_msgs, uint8_t* harq_crc_ok, uint8_t* tb_out,
+                                                   miphy_pusch_result* results, float* scalars_out, int8_t* uci_llr_out, float* evm_out, float* cfo_out,
+                                                   uint32_t time_mode, float* var_out, void* stream)
+{
+  MIPHY_REQUIRE(ctx && pdus && grid && harq_softbits && harq_msgs && harq_crc_ok && tb_out && results && scalars_out && cfo_out && var_out,
+                "miphy_pusch_process_layers_tv_batch: null argument");
+  MIPHY_REQUIRE(time_mode == MIPHY_TIME_INTERPOLATE || time_mode == MIPHY_TIME_LINE,
+                "miphy_pusch_process_layers_tv_batch: time_mode must be MIPHY_TIME_INTERPOLATE or MIPHY_TIME_LINE");
+  if (n == 0)
+    return MIPHY_OK;
+  return pusch_process_ex(ctx, nullptr, pdus, nullptr, nullptr, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out, evm_out,
+                          cfo_out, time_mode, var_out, (hipStream_t)stream);
 }
 
 // One codeword on 1..4 layers through MMSE-IRC: the layered processor with the covariance estimator between its estimator and an MMSE demodulator.
@@ -383,5 +409,5 @@ extern "C" int miphy_pusch_process_layers_mmse_batch(miphy_ctx* ctx, const miphy
   if (n == 0)
     return MIPHY_OK;
   return pusch_process_ex(ctx, nullptr, nullptr, nullptr, pdus, uci, n, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars_out, uci_llr_out,
-                          evm_out, nullptr, (hipStream_t)stream);
+                          evm_out, nullptr, 0, nullptr, (hipStream_t)stream);
 }

@@ -168,6 +168,9 @@ def lib():
         if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_dmrs_pusch_estimate_cfo_batch"):  # (likewise)
             l.miphy_dmrs_pusch_estimate_cfo_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 5
             l.miphy_pusch_process_layers_cfo_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 11
+        if not os.environ.get("MIPHY_LIBRARY") or hasattr(l, "miphy_dmrs_pusch_estimate_tv_batch"):  # (likewise)
+            l.miphy_dmrs_pusch_estimate_tv_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32] + [C.c_void_p] * 6
+            l.miphy_pusch_process_layers_tv_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 10 + [C.c_uint32, C.c_void_p, C.c_void_p]
         l.miphy_polar_block_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("miphy_ofdm_demodulate_symbols", "miphy_ofdm_modulate_symbols"):
             getattr(l, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -262,6 +265,13 @@ assert PuschNcovJob.itemsize == 168 and PuschNcovJob.fields["cov_offset"][1] == 
 # Mirrors miphy_pusch_chest_cfo_job: the layered estimator with the carrier frequency offset estimated and compensated; {cfo_hz, rho} at cfo_offset.
 PuschChestCfoJob = np.dtype([("base", PuschChestJob), ("cfo_offset", np.uint64)], align=True)
 assert PuschChestCfoJob.itemsize == 160 and PuschChestCfoJob.fields["cfo_offset"][1] == 152, PuschChestCfoJob.itemsize
+
+
+# Mirrors miphy_pusch_chest_tv_job: the CFO estimator for a channel that changes within the slot; the variation of (port, layer) at var_offset +
+# port * nof_tx_layers + layer; time_mode TIME_INTERPOLATE or TIME_LINE.
+TIME_INTERPOLATE, TIME_LINE = 1, 2
+PuschChestTvJob = np.dtype([("base", PuschChestCfoJob), ("var_offset", np.uint64), ("time_mode", np.uint8), ("reserved", np.uint8, 7)], align=True)
+assert PuschChestTvJob.itemsize == 176 and PuschChestTvJob.fields["var_offset"][1] == 160 and PuschChestTvJob.fields["time_mode"][1] == 168, PuschChestTvJob.itemsize
 
 
 def pusch_noise_covariance_nof_prg(job):
@@ -1042,6 +1052,14 @@ class Context:
             on_dev |= (int(max_ports) << 8) | (int(max_layers) << 12)
         check(lib().miphy_dmrs_pusch_estimate_cfo_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _dptr(cfo), _stream_ptr(stream)))
 
+    def dmrs_pusch_estimate_tv_batch(self, jobs, grid, ce, scalars, cfo, var, stream=None, max_ports=0, max_layers=0):
+        """dmrs_pusch_estimate_cfo_batch for a channel that changes within the slot (PuschChestTvJob records): the fits of the DM-RS symbols are kept apart
+        and interpolated in time (time_mode); var: device float32, the variation of every (port, layer) at var_offset; hints as dmrs_pusch_estimate_batch."""
+        jobs, n, ptr, on_dev = self._descs(jobs, PuschChestTvJob)
+        if on_dev:
+            on_dev |= (int(max_ports) << 8) | (int(max_layers) << 12)
+        check(lib().miphy_dmrs_pusch_estimate_tv_batch(self.h, ptr, on_dev, n, _dptr(grid), _dptr(ce), _dptr(scalars), _dptr(cfo), _dptr(var), _stream_ptr(stream)))
+
     def pusch_noise_covariance_batch(self, jobs, grid, cov, stream=None, max_ports=0, max_layers=0):
         """Noise-plus-interference covariance per PRG from the DM-RS residuals (PuschNcovJob records; cov: device complex64); hints as
         dmrs_pusch_estimate_batch."""
@@ -1242,6 +1260,22 @@ class Context:
                                                          _dptr(harq_msgs), _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars),
                                                          _dptr(uci_llr) if uci_llr is not None else None, _dptr(evm) if evm is not None else None,
                                                          _dptr(cfo), _stream_ptr(stream)))
+
+    def pusch_process_layers_tv_batch(self, pdus, uci, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, uci_llr, evm, cfo, time_mode, var,
+                                      stream=None):
+        """pusch_process_layers_cfo_batch with dmrs_pusch_estimate_tv_batch in front (time_mode: TIME_INTERPOLATE or TIME_LINE); var: device float32 [n][16],
+        the variation of (port, layer) of every PDU at port * nof_tx_layers + layer."""
+        assert isinstance(pdus, np.ndarray) and pdus.dtype == PuschLayersPdu
+        pdus = np.ascontiguousarray(pdus)
+        up = None
+        if uci is not None:
+            assert isinstance(uci, np.ndarray) and uci.dtype == PuschUci and uci.size == pdus.size
+            uci = np.ascontiguousarray(uci)
+            up = C.c_void_p(uci.ctypes.data)
+        check(lib().miphy_pusch_process_layers_tv_batch(self.h, C.c_void_p(pdus.ctypes.data), up, pdus.size, _dptr(grid), _dptr(harq_softbits),
+                                                        _dptr(harq_msgs), _dptr(harq_crc_ok), _dptr(tb_out), _dptr(results), _dptr(scalars),
+                                                        _dptr(uci_llr) if uci_llr is not None else None, _dptr(evm) if evm is not None else None,
+                                                        _dptr(cfo), int(time_mode), _dptr(var), _stream_ptr(stream)))
 
     def pusch_process_layers_batch_ex(self, pdus, uci, grid, harq_softbits, harq_msgs, harq_crc_ok, tb_out, results, scalars, uci_llr, evm, stream=None):
         """pusch_process_layers_batch for PDUs with multiplexed UCI (uci: numpy PuschUci array or None) and the EVM (evm: float32 device tensor of n or
